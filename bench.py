@@ -19,7 +19,13 @@ line carries the sharded batch's own rate (acceptors/s, us per compose->shortest
 value = arcs/s over the whole job, arcs per rank-step = E(T) [each arc of T relaxed at least once]
         + E_composed (arcs emitted by compose before trim) + E_relaxed on the composed FSTs (== E_composed).
 
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds everything else the line
+has carried: the untimed extras (cold queries, other sizes and configurations, batch sweep, look-ahead, multi-GPU
+figures), the per-part and roofline passes, and the CPU baseline with its parity guards.  --dump-outputs DIR writes the
+results of the last timed step as .npy files (see dump_outputs).
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 20 --warmup 3
 """
@@ -58,6 +64,11 @@ def parse_args():
     ap.add_argument("--sigma", type=int, default=256)
     ap.add_argument("--batch-per-gpu", type=int, default=64)
     ap.add_argument("--acc-len", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the untimed extras, the per-part and roofline passes and "
+                         "the CPU baseline (the options below that tune those apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0's results)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config5-states", type=int, default=5_000_000,
                     help="states of the HCLG-shaped operand of the configs[4] extra (0 = skip it)")
@@ -82,7 +93,10 @@ def parse_args():
                          "(round 4), and its resident launch leaves the batch kernel the compute units it needs.  "
                          "s2-first was the order of rounds 2-3, when every sweep was a GPU-wide launch.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.overlap = not args.serial
+    args.extras = args.full and not args.no_extras
     return args
 
 
@@ -325,6 +339,54 @@ def roofline_vs_size(ctx, sizes, fanout, sigma):
             "points": rows}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, sp, outs, n_arcs):
+    """--dump-outputs: the results of the last timed step, as a caller of the step receives them (path FSTs, read back as
+    flat arrays), in float64 (labels, state ids and f32 weights are exact in it):
+      shortest_path_T_info    [n_states, start (-1: none), n_arcs]
+      shortest_path_T_arcs    one row per arc in stored order: [source state, ilabel, olabel, weight, nextstate]
+      shortest_path_T_finals  one row per final state: [state, final weight]
+      batch_info              one row per batch problem: [problem index, n_states, start, n_arcs]
+      batch_arcs, batch_finals  the same rows as above with the problem index in front
+      composed_arcs           [arcs the batch's compositions emitted]
+    A batch too large for DUMP_MAX_BYTES in all is written as a seeded sample of its problems (batch_info lists them)."""
+    import numpy as np
+
+    def rows(fst):
+        f = fst.to_flat()
+        n, off, a, fin = int(f["n_states"]), f["offsets"], f["arcs"], f["finals"]
+        src = np.repeat(np.arange(n, dtype=np.float64), np.diff(off.astype(np.int64)))
+        arcs = np.stack([src] + [a[k].astype(np.float64) for k in ("ilabel", "olabel", "weight", "nextstate")], axis=1)
+        fs = np.flatnonzero(np.isfinite(fin))
+        finals = np.stack([fs.astype(np.float64), fin[fs].astype(np.float64)], axis=1)
+        return [n, -1 if f["start"] is None else int(f["start"]), len(a)], arcs, finals
+
+    info, arcs, finals = rows(sp)
+    files = {"shortest_path_T_info": np.array(info, dtype=np.float64), "shortest_path_T_arcs": arcs,
+             "shortest_path_T_finals": finals, "composed_arcs": np.array([n_arcs], dtype=np.float64)}
+    budget = DUMP_MAX_BYTES - sum(v.nbytes for v in files.values())
+    order = np.random.default_rng(0).permutation(len(outs))  # (the whole batch whenever it fits: the sample is sorted back)
+    b_info, b_arcs, b_finals, used = [], [], [], 0
+    for i in order:
+        info, arcs, finals = rows(outs[i])
+        cost = 8 * (4 + 6 * len(arcs) + 3 * len(finals))
+        if used + cost > budget:
+            break
+        used += cost
+        b_info.append([int(i)] + info)
+        b_arcs.append(np.concatenate([np.full((len(arcs), 1), float(i)), arcs], axis=1))
+        b_finals.append(np.concatenate([np.full((len(finals), 1), float(i)), finals], axis=1))
+    keep = np.argsort([r[0] for r in b_info], kind="stable")
+    files["batch_info"] = np.array([b_info[k] for k in keep], dtype=np.float64).reshape(-1, 4)
+    files["batch_arcs"] = np.concatenate([b_arcs[k] for k in keep] or [np.zeros((0, 6))], axis=0)
+    files["batch_finals"] = np.concatenate([b_finals[k] for k in keep] or [np.zeros((0, 3))], axis=0)
+    os.makedirs(path, exist_ok=True)
+    for name, v in files.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     import numpy as np
@@ -383,17 +445,18 @@ def main():
             flats = [t] + synth.make_acceptors(t, n_total, args.acc_len, seed0=1000)
             if not args.no_extras:  # (before T leaves rank 0: their end states are final states of T everywhere)
                 sweep_accs = synth.make_acceptors(t, SWEEP_MAX, args.acc_len, seed0=50_000)
-            if not args.no_extras:  # (every rank takes its share of them in the multi-GPU extras: batch_strong / batch_weak_4096)
+            if args.extras:  # (every rank takes its share of them in the multi-GPU extras: batch_strong / batch_weak_4096)
                 flats = flats + sweep_accs
         flats = wdist.broadcast_flat_fsts(flats, 0, device)
         t, accs_all = flats[0], flats[1:1 + n_total]
-        if not args.no_extras:
+        if args.extras:
             sweep_accs = flats[1 + n_total:]
     else:
         t = synth.make_transducer(args.states, args.fanout, args.sigma, 0.0, seed=3)
         accs_all = synth.make_acceptors(t, n_total, args.acc_len, seed0=1000)
         if not args.no_extras:  # the acceptors of the batch_sweep extra: generated BEFORE T is uploaded (make_acceptors
-            # marks the walks' end states final in T: the device copy and the CPU baseline must see the same T)
+            # marks the walks' end states final in T: the device copy and the CPU baseline must see the same T).  Drawn
+            # without --full too: the walks' final states are part of the workload, the same T with and without --full.
             sweep_accs = synth.make_acceptors(t, SWEEP_MAX, args.acc_len, seed0=50_000)
     # Several GPUs: every rank holds T.  The unit that scales is the (acceptor, T) problem; the direct shortest_path(T) of a
     # step is a DIFFERENT query on every rank — the single-source solve from rank r's own start state (T is strongly
@@ -413,7 +476,7 @@ def main():
     # a FRESH handle of T, HBM-resident: the first shortest_path builds the mailbox region plan and takes the parent
     # pass; the second builds the transpose for the backtrace; from the third on the solve is one predicted batch
     cold = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.extras:
         dcold = rustfst_amd.DeviceFst.from_arrays(t["n_states"], t["start"], t["offsets"], t["arcs"], t["finals"], t["props"], ctx)
         torch.cuda.synchronize(device)
         cold = []
@@ -439,7 +502,7 @@ def main():
     # shortest_path on T through this engine: OpenFST vector file -> host parse + upload to HBM, the (cold: fresh handle)
     # solve, result path -> OpenFST bytes -> file
     harness = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.extras:
         import tempfile
         f_in = os.path.join(tempfile.gettempdir(), f"wfst_bench_T_{os.getpid()}.fst")
         f_out = f_in + ".out"
@@ -476,7 +539,7 @@ def main():
     def chain_us(label, n=15):
         """the relaxation chain of a repeated shortest_path(T) on the bench's handle by HIP events (profiling mode 2), median of n;
         recorded under `label` (roofline.chain_us_by_point: the same bracket at several points of the run)"""
-        if rank != 0:
+        if rank != 0 or not args.full:
             return None
         ctx.set_profiling(2)
         v = []
@@ -575,7 +638,7 @@ def main():
             step()
         drain()
         gather_check = None
-        if world > 1 or force_dist:
+        if (world > 1 or force_dist) and args.full:
             # (untimed) what the exchange delivered for the last priming step must be a ONE-rank run of the whole global batch:
             # every rank composes all n_total acceptors on its own GPU once and compares, record for record, in global order
             whole, _ = rustfst_amd.compose_shortest_path_batch(rustfst_amd.DeviceFst.upload_many(accs_all, ctx2), dt2, ctx=ctx2)
@@ -607,6 +670,9 @@ def main():
         # what the TIMED steps returned: the untimed extras below run step() again on other batches (step_512_acceptors) and
         # must not change what the CPU leg's parity guards compare with
         timed_last = {k: last[k] for k in ("sp", "outs", "n_arcs")}
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, timed_last["sp"], timed_last["outs"], timed_last["n_arcs"])
+        sweeps = ctx.stats()["sweeps"]  # (launches of the last solve on ctx)
         step_phases_us = None
         chain_us("after_timed_steps")
         if args.overlap and phases[4]:
@@ -631,7 +697,7 @@ def main():
         #  * batch_weak_4096: 4096 acceptors PER GPU (every rank the same 4096: throughput only), where the batch kernel has
         #    enough waves in flight for the per-acceptor time to be flat (0.23 us): the weak-scaling figure of the sharded leg.
         dist_extras = None
-        if (world > 1 or force_dist) and not args.no_extras and args.overlap:
+        if (world > 1 or force_dist) and args.extras and args.overlap:
             import torch.distributed as dist
 
             def timed_all(fn, reps):
@@ -714,9 +780,11 @@ def main():
                 torch.cuda.synchronize(device)
                 best = min(best, time.perf_counter() - c0)
             return 1e3 * best
-        ms_sp_t = alone(lambda: dt.shortest_path())
-        ms_batch = alone(lambda: rustfst_amd.compose_shortest_path_batch(daccs, dt2, ctx=ctx2))
-        sweeps = ctx.stats()["sweeps"]
+        ms_sp_t = ms_batch = None
+        if args.full:
+            ms_sp_t = alone(lambda: dt.shortest_path())
+            ms_batch = alone(lambda: rustfst_amd.compose_shortest_path_batch(daccs, dt2, ctx=ctx2))
+            sweeps = ctx.stats()["sweeps"]
         relax_kernel = ("sssp_relax_kernel", "sssp_mbox_kernel", "sssp_mbox_resident_kernel", "sssp_relax_kernel + sssp_bin_expand/apply_kernel")[int(ctx.stats()["relax_kernel"])]
 
         # ------------------------------------------------------------------ configs[1]: ONE 1000-arc string against a
@@ -726,7 +794,7 @@ def main():
         # different state every time (wfst_fst_set_start on the resident handle: region plan, transpose and packed arcs stay;
         # the launch prediction was learned on the PREVIOUS source)
         varied = None
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and args.extras:
             rng_v = np.random.default_rng(20261001)
             srcs = [int(x) for x in rng_v.integers(0, int(t["n_states"]), 24)]
             v_ms = []
@@ -755,7 +823,7 @@ def main():
         # ------------------------------------------------------------------ two queries at once: the resident lease of a device has
         # two units, and a context set to half the device takes one (tools/two_queries.py)
         two_q = None
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and args.extras:
             ch1, ch2 = rustfst_amd.Context(local_rank), rustfst_amd.Context(local_rank)
             ch1.set_resident_share(1)
             ch2.set_resident_share(1)
@@ -789,7 +857,7 @@ def main():
             for _ in range(3):
                 dt.shortest_path()
         config2 = None
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and args.extras:
             t2 = synth.make_transducer(100_000, args.fanout, args.sigma, 0.0, seed=2)
             a2 = synth.make_acceptors(t2, 1, 1000, seed0=2)
             d2 = rustfst_amd.DeviceFst.from_arrays(t2["n_states"], t2["start"], t2["offsets"], t2["arcs"], t2["finals"], t2["props"], ctx)
@@ -808,7 +876,7 @@ def main():
         # ------------------------------------------------------------------ batch_sweep: where the fused batch saturates
         chain_us("after_config2")
         batch_sweep = None
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and args.extras:
             batch_sweep = []
             for bsz in (64, 512, SWEEP_MAX):
                 db = rustfst_amd.HandleArray(rustfst_amd.DeviceFst.upload_many(sweep_accs[:bsz], ctx2))
@@ -840,7 +908,7 @@ def main():
         # 512 acceptors here — the one-GPU form of configs[3])
         chain_us("after_batch_sweep")
         step_512 = None
-        if rank == 0 and world == 1 and not args.no_extras and args.overlap:
+        if rank == 0 and world == 1 and args.extras and args.overlap:
             daccs_keep, order_keep = daccs, args.order
             daccs = rustfst_amd.HandleArray(rustfst_amd.DeviceFst.upload_many(sweep_accs[:512], ctx2))
             step_512 = {"workload": f"the timed step with ALL 512 acceptors (len {args.acc_len}) of configs[3] on this one GPU: "
@@ -875,13 +943,13 @@ def main():
         # composition + n = 10 shortest paths (rustfst-cli/src/cmds/compose.rs:77-181 wires the look-ahead recipe)
         chain_us("after_step_512")
         config5 = None
-        if rank == 0 and not args.no_extras and args.config5_states > 0:
+        if rank == 0 and args.extras and args.config5_states > 0:
             config5 = config5_extra(args.config5_states, ctx, device)
         chain_us("after_config5")
 
         # ------------------------------------------------------------------ the same roofline figure at other sizes
         rvs = None
-        if rank == 0 and not args.no_extras and args.roofline_sizes:
+        if rank == 0 and args.extras and args.roofline_sizes:
             rvs = roofline_vs_size(ctx, [int(x) for x in args.roofline_sizes.split(",") if x], args.fanout, args.sigma)
         chain_us("after_roofline_vs_size")
 
@@ -889,7 +957,7 @@ def main():
         # HIP events bracket every sssp_relax_kernel launch on ctx's stream (wfst_ctx_set_profiling);
         # achieved = algorithmic bytes (20 B per arc relaxed + 12 B per frontier state) / kernel time.
         roofline = None
-        if rank == 0:
+        if rank == 0 and args.full:
             ctx.reset_stats()
             ctx.set_profiling(True)
             dt.shortest_path()
@@ -970,7 +1038,7 @@ def main():
         # problem walking ~200 dependent BFS levels), so its fraction of the HBM peak is tiny by construction;
         # algorithmic bytes per expanded state = 24 + 16 f1 + 4 f1 ceil(log2(f2 + 1)) + 48 m  
         batch_kernel = None
-        if rank == 0:
+        if rank == 0 and args.full:
             import math
             ctx2.reset_stats()
             ctx2.set_profiling(True)
@@ -994,7 +1062,7 @@ def main():
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1): the oracle
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle_py
         ot = oracle_py.OracleFst.from_flat(t["n_states"], t["start"], t["offsets"], t["arcs"], t["finals"], t["props"])
         oaccs = [oracle_py.OracleFst.from_flat(a["n_states"], a["start"], a["offsets"], a["arcs"], a["finals"], a["props"])
@@ -1016,7 +1084,7 @@ def main():
         # only parallelism a CPU deployment has): threads of the C++ restatement, one acceptor at a time each
         all_cores = None
         n_cores = min(os.cpu_count() or 1, len(oaccs))  # one acceptor per thread at most
-        if not args.no_extras and n_cores > 1:
+        if args.extras and n_cores > 1:
             _, o_arcs_mt, sec_mt = oracle_py.compose_shortest_path_batch(oaccs, ot, n_threads=n_cores)
             reps = max(1, min(50, int(2.0 / max(sec_mt, 1e-4))))
             sec_mt = min(oracle_py.compose_shortest_path_batch(oaccs, ot, n_threads=n_cores)[2] for _ in range(reps))
@@ -1100,7 +1168,7 @@ def main():
         out = {
             "metric": "arcs relaxed/sec (compose -> shortest_path, 1M-state / 10M-arc FST)",
             "value": round(value, 1), "unit": "arcs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak", "full": bool(args.full),
             "ms_per_step_stats": {"mean": round(float(ms.mean()), 4), "std": round(float(ms.std()), 4), "min": round(float(ms.min()), 4),
                                   "p50": round(float(np.percentile(ms, 50)), 4), "p99": round(float(np.percentile(ms, 99)), 4),
                                   "timed_seconds": round(elapsed, 3), "clock": "host perf_counter per step on rank 0"},
@@ -1120,8 +1188,9 @@ def main():
                               "holds one GPU's share); the same step with all 512 on one GPU is `step_512_acceptors`",
                 "parallelism": f"acceptor-sharded x{world}, T replicated, RCCL all-gather of results only",
             },
-            "ms_shortest_path_T": round(ms_sp_t, 4), "ms_compose_shortest_path_batch": round(ms_batch, 4),
-            "ms_per_compose_shortest_path": round(ms_batch / max(1, len(mine)), 5),
+            "ms_shortest_path_T": None if ms_sp_t is None else round(ms_sp_t, 4),
+            "ms_compose_shortest_path_batch": None if ms_batch is None else round(ms_batch, 4),
+            "ms_per_compose_shortest_path": None if ms_batch is None else round(ms_batch / max(1, len(mine)), 5),
             "relaxation_sweeps": int(sweeps), "composed_arcs_per_batch": int(timed_last["n_arcs"]),
             "setup_seconds": round(gen_s, 2), "priming_steps": 3,
             "cold_query_ms": None if cold is None else {

@@ -1,5 +1,5 @@
 """Assembles profiles/<tag>_end_of_round.md, <tag>_counters.md and <tag>_bench_line.json from the scratch output of
-tools/profile_round.sh (gpurun_out/prof_<tag>/, gpurun_out/pmc_<tag>/) and a default bench line:
+tools/profile_round.sh (its prof_<tag>/ and pmc_<tag>/ output folders) and a `bench.py --full` line:
 python tools/make_profile_docs.py <tag> <bench_line.json> [suite summary]     (run after tools/pmc_to_json.py)"""
 import contextlib, io, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,9 +41,9 @@ open(os.path.join(dst, f"{tag}_bench_line.json"), "w").write(line + "\n")
 rf = d.get("roofline", {})
 c5 = (d.get("config5") or {}).get("wide_lookahead", {})
 md = [f"# {tag} — end of round: rocprofv3 evidence (MI355X, commit {head})\n",
-      "Collected by `tools/profile_round.sh` + the default `python bench.py` in one `gpurun` call" + (f" ({suite})" if suite else "") +
+      "Collected by `tools/profile_round.sh` + `python bench.py --full` in one session on the GPU" + (f" ({suite})" if suite else "") +
       "; raw rocpd databases stay in `gpurun_out/` (scratch).\n",
-      "## default bench line (`python bench.py`)\n```\n" + line + "\n```\n",
+      "## bench line (`python bench.py --full`)\n```\n" + line + "\n```\n",
       f"Headline: **{d['value'] / 1e9:.2f} G arcs/s, {d['ms_per_step']} ms per step**; `shortest_path(T)` alone {d.get('ms_shortest_path_T')} ms, fused batch "
       f"alone {d.get('ms_compose_shortest_path_batch')} ms.  `roofline`: {rf.get('launches')} launches, {rf.get('solve_relax_kernel_ms')} ms of relaxation "
       f"kernels per solve (HIP events, un-profiled) -> 212 MB / that = {rf.get('achieved')} GB/s = **{rf.get('frac')}** of 8 TB/s; traffic "
@@ -59,7 +59,7 @@ md = [f"# {tag} — end of round: rocprofv3 evidence (MI355X, commit {head})\n",
       clean(read("sp_alone_unprofiled.log")) + "```\n",
       "Kernel durations of the profiled process (sum per solve below) against its own event bracket: the profiler's per-dispatch completion handling "
       "stretches a chain of back-to-back launches; the bench line's figure is the un-profiled bracket.\n",
-      "## kernel table: the bench step (`rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras`)\n",
+      "## kernel table: the bench step (`rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-extras`)\n",
       cap(rocpd_summary.trace, os.path.join(src, "trace_results.db")),
       "\n## the relaxation alone at 1M states (`tools/sp_repeat.py 1000000 12`)\n", cap(rocpd_summary.trace, os.path.join(src, "sp_alone_results.db")),
       "\n## 2M states (8192-state blocks, every launch resident)\n", cap(rocpd_summary.trace, os.path.join(src, "sp_2m_results.db"), 424e6),

@@ -12,7 +12,7 @@ mkdir -p $OUT $OUTP
 T0=$(date +%s)
 stamp() { echo "[t+$(( $(date +%s) - T0 ))s] $1"; }
 cd /tmp
-timeout -k 5 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+timeout -k 5 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python $R/bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-extras > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 timeout -k 5 300 rocprofv3 --kernel-trace -d $OUT -o sp_alone -- python $R/tools/sp_repeat.py 1000000 12 > $OUT/sp_alone.log 2>&1
 timeout -k 5 300 python $R/tools/sp_repeat.py 1000000 12 > $OUT/sp_alone_unprofiled.log 2>&1
 timeout -k 5 300 rocprofv3 --kernel-trace -d $OUT -o sp_2m -- python $R/tools/sp_repeat.py 2000000 8 > $OUT/sp_2m.log 2>&1
