@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -150,6 +150,41 @@ wfst_status wfst_shortest_path(wfst_ctx* ctx, const wfst_fst* fst, const wfst_sh
 /* single-source (min,+) distances from the start state (what single_shortest_path computes into
  * `distance`, shortest_path.rs:173-239) copied to host arrays of n_states entries; hops may be NULL. */
 wfst_status wfst_shortest_distance(wfst_ctx* ctx, const wfst_fst* fst, float* distance, uint32_t* hops);
+
+/* ---- shortest_distance(fst, reverse) / shortest_distance_with_config (rustfst/src/algorithms/shortest_distance.rs:307-336).
+ *      cfg == NULL: {reverse 0, delta KSHORTESTDELTA = 1e-6} (ShortestDistanceConfig::default, :260-266).
+ *      reverse == 0: exactly wfst_shortest_distance.  reverse != 0: reverse(fst), distances from its super-initial state,
+ *      entry 0 dropped (:322-334); defined without a start state too (the reversed FST always starts at 0).  The reversed
+ *      FST is built on the GPU once and cached on the handle (set_start keeps it).
+ *      distance[n_states]; entries past the reference's Vec length are +inf; *len (may be NULL) = that Vec length: one plus
+ *      the largest state id the reference's search touches (every state reachable from its source).
+ *      delta must be finite and >= 0; like wfst_shortest_distance the device returns the exact fixed point, the reference
+ *      ignores improvements of at most delta (identical on weights of a grid coarser than delta). ---- */
+typedef struct {
+  uint32_t reverse; /* bool */
+  float delta;
+} wfst_shortest_distance_config;
+wfst_status wfst_shortest_distance_with_config(wfst_ctx* ctx, const wfst_fst* fst, const wfst_shortest_distance_config* cfg,
+                                               float* distance, uint32_t* len);
+
+/* ---- push_weights / push_weights_with_config (rustfst/src/algorithms/push.rs:76-170): distances (reverse ones for
+ *      ReweightToInitial), reweight, then with remove_total_weight remove_weight of the total (push.rs:120-170).
+ *      reweight_type: 0 = ReweightToInitial, 1 = ReweightToFinal (reweight.rs enum order); anything else is KO.
+ *      cfg == NULL: PushWeightsConfig::default() = {KDELTA, false} (push.rs:41-48); delta as in
+ *      wfst_shortest_distance_with_config.  The reference works in place; here a NEW handle is returned (it may have one
+ *      state more than fst: reweight.rs:129-138).  Weights and property word follow the reference bit for bit. ---- */
+typedef struct {
+  float delta;
+  uint32_t remove_total_weight; /* bool */
+} wfst_push_weights_config;
+wfst_status wfst_push_weights(wfst_ctx* ctx, const wfst_fst* fst, uint32_t reweight_type, const wfst_push_weights_config* cfg,
+                              wfst_fst** out);
+
+/* ---- reweight (rustfst/src/algorithms/reweight.rs:29-154): reweight(fst, potentials[0..n_potentials), reweight_type);
+ *      potentials on the host, +inf = zero, a state >= n_potentials has potential zero.  NULL potentials with
+ *      n_potentials > 0 is KO; reweight_type as in wfst_push_weights.  A NEW handle. ---- */
+wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* potentials, uint64_t n_potentials,
+                          uint32_t reweight_type, wfst_fst** out);
 
 /* ---- connect: fst_connect (rustfst-ffi/src/algorithms/connect.rs:14-23) = rustfst::algorithms::connect
  *      (rustfst/src/algorithms/connect.rs:51-66): the states that are accessible from the start state and can reach a

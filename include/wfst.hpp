@@ -13,6 +13,9 @@
 //   tr_sort(&mut fst, ILabelCompare{} | OLabelCompare{})         tr_sort(fst, ILabelCompare{} | OLabelCompare{})
 //   project(&mut fst, ProjectType::ProjectInput)                 project(fst, ProjectType::ProjectInput)
 //   connect(&mut fst) / rm_epsilon(&mut fst)                     connect(fst) / rm_epsilon(fst)
+//   shortest_distance(&fst, reverse) -> Vec<W>                   shortest_distance(fst, reverse) -> std::vector<float>
+//   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
+//   push_weights(&mut fst, ..) / push_weights_with_config(..)    push_weights(..) / push_weights_with_config(..)  push.rs:76-118
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -200,6 +203,41 @@ inline void rm_epsilon(VectorFst& fst) {
   check(wfst_rm_epsilon(Context::current().get(), a.h, &c.h));
   fst = detail::download(c);
 }
+
+// shortest_distance (shortest_distance.rs:307-336): the reference's Vec, its length included
+inline std::vector<float> shortest_distance_with_config(const VectorFst& fst, bool reverse, float delta = 1e-6f) {
+  detail::DeviceFst a;
+  detail::upload(fst, a);
+  uint32_t n = 0, len = 0;
+  check(wfst_fst_info(a.h, &n, nullptr, nullptr, nullptr));
+  std::vector<float> d(n);
+  const wfst_shortest_distance_config cfg{reverse ? 1u : 0u, delta};
+  check(wfst_shortest_distance_with_config(Context::current().get(), a.h, &cfg, d.data(), &len));
+  d.resize(len);
+  return d;
+}
+inline std::vector<float> shortest_distance(const VectorFst& fst, bool reverse) { return shortest_distance_with_config(fst, reverse); }
+
+// reweight (reweight.rs:29-154) and push_weights[_with_config] (push.rs:76-118): in place, like the reference
+enum class ReweightType : uint32_t { ReweightToInitial = 0, ReweightToFinal = 1 };  // reweight.rs:11-17
+struct PushWeightsConfig {  // push.rs:34-48
+  float delta = 1.0f / 1024.0f;
+  bool remove_total_weight = false;
+};
+inline void reweight(VectorFst& fst, const std::vector<float>& potentials, ReweightType reweight_type) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_reweight(Context::current().get(), a.h, potentials.data(), potentials.size(), (uint32_t)reweight_type, &c.h));
+  fst = detail::download(c);
+}
+inline void push_weights_with_config(VectorFst& fst, ReweightType reweight_type, const PushWeightsConfig& config) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  const wfst_push_weights_config cfg{config.delta, config.remove_total_weight ? 1u : 0u};
+  check(wfst_push_weights(Context::current().get(), a.h, (uint32_t)reweight_type, &cfg, &c.h));
+  fst = detail::download(c);
+}
+inline void push_weights(VectorFst& fst, ReweightType reweight_type) { push_weights_with_config(fst, reweight_type, PushWeightsConfig{}); }
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

@@ -30,10 +30,18 @@ from .fst import (  # noqa: F401
     set_default_context,
     shortestpath,
     shortestpath_with_config,
+    KDELTA,
+    PushWeightsConfig,
+    ReweightType,
+    push_weights,
+    push_weights_with_config,
+    reweight,
+    shortest_distance,
 )
 
 __all__ = [
     "ComposeConfig", "ComposeFilter", "Context", "DeviceFst", "ShortestPathConfig", "Tr", "VectorFst", "acceptor",
     "compose", "compose_shortest_path_batch", "compose_shortest_path_batch_begin", "compose_shortest_path_batch_packed", "shortest_path_batch", "last_nbest_path", "HandleArray", "LookAhead", "ProjectType", "project", "compose_with_config", "default_context", "set_default_context",
-    "shortestpath", "shortestpath_with_config", "WfstError", "TR_DTYPE", "LIB_PATH",
+    "shortestpath", "shortestpath_with_config", "WfstError",
+    "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance", "TR_DTYPE", "LIB_PATH",
 ]

@@ -1,4 +1,5 @@
 // api.cpp — the extern "C" surface declared in include/wfst.h (conventions: rustfst-ffi/src/lib.rs:29-97).
+#include <cmath>
 #include <cstdlib>
 
 #include "common.h"
@@ -419,6 +420,45 @@ wfst_status wfst_shortest_distance(wfst_ctx* ctx, const wfst_fst* fst, float* di
     if (!ctx || !fst || !distance) throw Error("null pointer");
     HIP_CHECK(hipSetDevice(ctx->device));
     shortest_distance(ctx, fst, distance, hops);
+  });
+}
+
+// shortest_distance_with_config (shortest_distance.rs:313-336); ShortestDistanceConfig::default() when cfg == NULL
+wfst_status wfst_shortest_distance_with_config(wfst_ctx* ctx, const wfst_fst* fst, const wfst_shortest_distance_config* cfg,
+                                               float* distance, uint32_t* len) {
+  return wrap([&] {
+    const wfst_shortest_distance_config c = cfg ? *cfg : wfst_shortest_distance_config{0u, 1e-6f};
+    if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("shortest_distance: delta must be finite and >= 0");
+    if (!ctx || !fst || !distance) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    shortest_distance_ex(ctx, fst, c.reverse != 0, distance, len);
+  });
+}
+
+// push_weights_with_config (push.rs:89-118); PushWeightsConfig::default() = {KDELTA, false} when cfg == NULL
+wfst_status wfst_push_weights(wfst_ctx* ctx, const wfst_fst* fst, uint32_t reweight_type, const wfst_push_weights_config* cfg,
+                              wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    const wfst_push_weights_config c = cfg ? *cfg : wfst_push_weights_config{1.0f / 1024.0f, 0u};
+    if (reweight_type > 1) throw Error("push_weights: unknown reweight_type " + std::to_string(reweight_type));
+    if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("push_weights: delta must be finite and >= 0");
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = push_weights_fst(ctx, fst, reweight_type, c.remove_total_weight != 0);
+  });
+}
+
+// reweight (reweight.rs:29-154) with caller-given potentials
+wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* potentials, uint64_t n_potentials,
+                          uint32_t reweight_type, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (reweight_type > 1) throw Error("reweight: unknown reweight_type " + std::to_string(reweight_type));
+    if (!potentials && n_potentials) throw Error("reweight: potentials is NULL but n_potentials > 0");
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = reweight_fst(ctx, fst, potentials, n_potentials, reweight_type);
   });
 }
 

@@ -281,6 +281,10 @@ struct wfst_fst {
   // transpose (in-arcs as {source state, arc position}) for the shortest-path backtrace; built on the second
   // shortest_path query of a large FST (sssp.hip reverse_csr)
   mutable std::shared_ptr<wfst::RevCsr> rev_dev;
+  // reverse(fst) as a device handle of its own (push.hip: reverse distances, co-reachability): built on first use, its
+  // mailbox plan with it; independent of the start state (the reversed FST always starts at 0), so set_start keeps it
+  mutable std::shared_ptr<wfst_fst> rev_fst;
+  mutable std::mutex rev_mu;
   // region plan of the mailbox relaxation sweeps; depends on (source, target) pairs only, built on first use
   mutable std::shared_ptr<wfst::MboxPlan> mbox;
   mutable std::shared_ptr<wfst::MboxPlan> mbox13;  // the same with blocks of 8192 states (resident launches of 1M .. 2M-state FSTs)
@@ -339,6 +343,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job);
 void shortest_path_n1_abandon(wfst_sp_job* job);
 wfst_ctx* sp_job_ctx(wfst_sp_job* job);
 void shortest_distance(wfst_ctx* ctx, const wfst_fst* f, float* distance, uint32_t* hops);
+void shortest_distance_device(wfst_ctx* ctx, const wfst_fst* f, float* d_distance);
 // nshortest.hip
 wfst_fst* shortest_path_nbest(wfst_ctx* ctx, const wfst_fst* f, uint64_t nshortest, float delta, bool unique = false);
 // nbest_batch.hip
@@ -390,6 +395,10 @@ wfst_fst* connect_and_adopt(wfst_ctx* ctx, uint32_t n, int64_t start, const uint
                             bool all_accessible, uint64_t out_props);
 // rm_epsilon.hip
 wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f);
+// push.hip: shortest_distance(fst, reverse) with the reference's Vec length, reweight, push_weights (new handles)
+void shortest_distance_ex(wfst_ctx* ctx, const wfst_fst* f, bool reverse, float* distance, uint32_t* len);
+wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials, uint64_t n_potentials, uint32_t reweight_type);
+wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_type, bool remove_total_weight);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,
                        uint64_t out_props, uint64_t est_s);
 }  // namespace wfst

@@ -232,6 +232,41 @@ inline uint64_t project(uint64_t in, bool project_output) {
   return (in & ~ALL) | out;
 }
 
+// ---- reweight() / remove_weight() bookkeeping (algorithms/reweight.rs, algorithms/push.rs:150-170)
+// keep_only_relevant_properties (trs_iter_mut.rs:293-305): set_arc_properties() is empty (properties.rs:278-280), so every
+// set_weight_unchecked keeps the label / epsilon bits and WEIGHTED / UNWEIGHTED only
+constexpr uint64_t ARC_RELEVANT = ACCEPTOR | NOT_ACCEPTOR | EPSILONS | NO_EPSILONS | I_EPSILONS | NO_I_EPSILONS | O_EPSILONS |
+                                  NO_O_EPSILONS | WEIGHTED | UNWEIGHTED;
+inline bool weighted(float w) { return !is_zero(w) && !is_one(w); }
+// TrsIterMut::set_weight_unchecked -> compute_new_properties_weights (trs_iter_mut.rs:210-215, 279-291, 342-350)
+inline uint64_t set_weight(uint64_t in, float old_w, float new_w) {
+  uint64_t out = in;
+  if (weighted(old_w)) out &= ~WEIGHTED;
+  if (weighted(new_w)) out = (out | WEIGHTED) & ~UNWEIGHTED;
+  return out & ARC_RELEVANT;
+}
+// FstProperties::weight_invariant_properties (properties.rs:436-465)
+constexpr uint64_t WEIGHT_INVARIANT = ACCEPTOR | NOT_ACCEPTOR | I_DETERMINISTIC | NOT_I_DETERMINISTIC | O_DETERMINISTIC |
+                                      NOT_O_DETERMINISTIC | EPSILONS | NO_EPSILONS | I_EPSILONS | NO_I_EPSILONS | O_EPSILONS |
+                                      NO_O_EPSILONS | I_LABEL_SORTED | NOT_I_LABEL_SORTED | O_LABEL_SORTED | NOT_O_LABEL_SORTED |
+                                      CYCLIC | ACYCLIC | INITIAL_CYCLIC | INITIAL_ACYCLIC | TOP_SORTED | NOT_TOP_SORTED |
+                                      ACCESSIBLE | NOT_ACCESSIBLE | COACCESSIBLE | NOT_COACCESSIBLE | STRING | NOT_STRING;
+// reweight_properties (mutate_properties.rs:640-644), applied with the all_properties() mask (reweight.rs:148-151)
+inline uint64_t reweight(uint64_t in) { return in & WEIGHT_INVARIANT & ~COACCESSIBLE; }
+// the trinary pairs (fst_properties/utils.rs:4-9 known_properties): a pair is known when either of its bits is set
+inline bool knows(uint64_t p, uint64_t pos_bit) { return (p & (pos_bit | (pos_bit << 1))) != 0; }
+// compute_and_update_properties(mask) with a mask of DFS bits only (fst_traits/mutable_fst.rs:435-441,
+// compute_fst_properties.rs:13-58): the SccVisitor's word replaces the four DFS pairs, nothing else changes
+constexpr uint64_t DFS_BITS = ACYCLIC | CYCLIC | INITIAL_ACYCLIC | INITIAL_CYCLIC | ACCESSIBLE | NOT_ACCESSIBLE | COACCESSIBLE |
+                              NOT_COACCESSIBLE;
+// SccVisitor's bits (visitors/scc_visitors.rs) from four plain facts about the graph: every state reachable from the start,
+// every state reaches a final state, some cycle anywhere (the DFS also starts from unreachable states), the start on a cycle
+inline uint64_t dfs_bits(bool accessible, bool coaccessible, bool cyclic, bool initial_cyclic) {
+  return (accessible ? ACCESSIBLE : NOT_ACCESSIBLE) | (coaccessible ? COACCESSIBLE : NOT_COACCESSIBLE) |
+         (cyclic ? CYCLIC : ACYCLIC) | (initial_cyclic ? INITIAL_CYCLIC : INITIAL_ACYCLIC);
+}
+inline uint64_t merge_dfs(uint64_t in, uint64_t dfs) { return (in & ~DFS_BITS) | (dfs & DFS_BITS); }
+
 inline uint64_t compose_result(uint64_t p1, uint64_t p2, bool connected, bool has_start) {
   // start None: LazyFst::compute returns F2::new() untouched (lazy_fst.rs:229-232)
   uint64_t p = has_start ? compose(p1, p2) : NULL_PROPS;

@@ -2122,6 +2122,19 @@ void shortest_distance(wfst_ctx* ctx, const wfst_fst* f, float* distance, uint32
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
+// the same distances left in HBM (d_distance[n_states], +inf = unreachable) for device consumers (push.hip); f must have a
+// start state
+void shortest_distance_device(wfst_ctx* ctx, const wfst_fst* f, float* d_distance) {
+  const uint32_t n = f->n_states;
+  if (f->start < 0 || n == 0) throw Error("shortest_distance_device: no start state");
+  ensure_device(const_cast<wfst_fst*>(f));
+  Solve sv;
+  run_relaxation(ctx, f, sv);
+  sssp_export_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(sv.key.p, d_distance, nullptr, n);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
 // Transpose of f (in-arcs as {source, position}); built the SECOND time shortest_path sees the same large FST — a one-shot
 // query keeps the parent pass, a resident transducer that is queried again pays the build once, inside its second query:
 // ~0.3 ms for 10 M arcs through the mailbox plan (rev_bucket_kernel / rev_place_kernel), ~1.2 ms by the two atomic passes for

@@ -18,6 +18,7 @@ from . import _lib
 from ._lib import TR_DTYPE, WfstError, check
 
 KSHORTESTDELTA = 1e-6  # rustfst/src/lib.rs:271
+KDELTA = 1.0 / 1024.0  # rustfst/src/lib.rs:266
 
 
 class Tr:
@@ -315,13 +316,49 @@ class DeviceFst:
         check(_lib.lib().wfst_fst_set_start(self.ctx._h, self._h, int(state)), "Error setting start state")
         return self
 
-    def shortest_distance(self, want_hops: bool = False):
+    def shortest_distance(self, want_hops: bool = False, reverse: bool = False, delta: Optional[float] = None):
+        """Distances from the start state (wfst_shortest_distance), or with reverse=True the distances TO the final states
+        (shortest_distance(fst, true), shortest_distance.rs:322-334; wfst_shortest_distance_with_config): n_states
+        entries, +inf where the reference's Vec ends.  `delta` is checked (finite, >= 0); the device returns the exact
+        fixed point.  hops exist for the forward search only."""
+        if reverse or delta is not None:
+            if want_hops:
+                raise ValueError("want_hops is not available with reverse=True or a delta")
+            return self.shortest_distance_with_len(reverse=reverse, delta=delta)[0]
         n = self.num_states
         dist = np.zeros(n, dtype=np.float32)
         hops = np.zeros(n, dtype=np.uint32) if want_hops else None
         check(_lib.lib().wfst_shortest_distance(self.ctx._h, self._h, dist.ctypes.data,
                                                 hops.ctypes.data if want_hops else None), "wfst_shortest_distance")
         return (dist, hops) if want_hops else dist
+
+    def shortest_distance_with_len(self, reverse: bool = False, delta: Optional[float] = None):
+        """(distance[n_states], len): len is the length of the reference's Vec (wfst_shortest_distance_with_config);
+        distance[:len] is what shortest_distance_with_config returns."""
+        n = self.num_states
+        dist = np.zeros(n, dtype=np.float32)
+        ln = C.c_uint32()
+        cfg = _lib.ShortestDistanceConfig(1 if reverse else 0, KSHORTESTDELTA if delta is None else float(delta))
+        check(_lib.lib().wfst_shortest_distance_with_config(self.ctx._h, self._h, C.byref(cfg), dist.ctypes.data,
+                                                            C.byref(ln)), "wfst_shortest_distance_with_config")
+        return dist, ln.value
+
+    def reweight(self, potentials, reweight_type: "ReweightType") -> "DeviceFst":
+        """algorithms::reweight (reweight.rs:29-154) with the given potentials (+inf = zero; states past the end have
+        potential zero): a NEW FST."""
+        pot = np.ascontiguousarray(potentials, dtype=np.float32)
+        out = C.c_void_p()
+        check(_lib.lib().wfst_reweight(self.ctx._h, self._h, pot.ctypes.data if pot.size else None, int(pot.size),
+                                       ReweightType(reweight_type).value, C.byref(out)), "Error during reweight")
+        return DeviceFst(out, self.ctx)
+
+    def push_weights(self, reweight_type: "ReweightType", config: Optional["PushWeightsConfig"] = None) -> "DeviceFst":
+        """algorithms::push_weights_with_config (push.rs:89-118): a NEW FST."""
+        out = C.c_void_p()
+        cfg = config._c() if config is not None else None
+        check(_lib.lib().wfst_push_weights(self.ctx._h, self._h, ReweightType(reweight_type).value, cfg, C.byref(out)),
+              "Error during push_weights")
+        return DeviceFst(out, self.ctx)
 
 
 class HandleArray:
@@ -613,6 +650,22 @@ class ShortestPathConfig:
         return C.pointer(_lib.ShortestPathConfig(self.delta, self.nshortest, 1 if self.unique else 0))
 
 
+class ReweightType(Enum):  # rustfst/src/algorithms/reweight.rs:11-17 (enum order = the C-ABI's reweight_type)
+    REWEIGHT_TO_INITIAL = 0
+    REWEIGHT_TO_FINAL = 1
+
+
+class PushWeightsConfig:
+    """rustfst/src/algorithms/push.rs:34-68: PushWeightsConfig::default() = {KDELTA, remove_total_weight false}."""
+
+    def __init__(self, delta: float = KDELTA, remove_total_weight: bool = False):
+        self.delta = float(delta)
+        self.remove_total_weight = bool(remove_total_weight)
+
+    def _c(self):
+        return C.pointer(_lib.PushWeightsConfig(self.delta, 1 if self.remove_total_weight else 0))
+
+
 # ------------------------------------------------------------------ VectorFst mirror
 class VectorFst:
     """Mutable FST stored in vectors (rustfst-python/rustfst/fst/vector_fst.py:29-790, subset on the path)."""
@@ -775,6 +828,20 @@ class VectorFst:
         self._dev = None
         return self
 
+    def push_weights(self, reweight_type: "ReweightType", config: Optional[PushWeightsConfig] = None) -> "VectorFst":
+        """push_weights_with_config (push.rs:89-118) in place on the device copy; returns this FST."""
+        res = self.to_device().push_weights(reweight_type, config).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def reweight(self, potentials, reweight_type: "ReweightType") -> "VectorFst":
+        """reweight (reweight.rs:29-154) in place on the device copy; returns this FST."""
+        res = self.to_device().reweight(potentials, reweight_type).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
     def project(self, proj_type: Union["ProjectType", None] = None) -> "VectorFst":
         """rustfst-python vector_fst.py:525-538 `project` (algorithms/project.py:27-50): projects THIS FST in place and
         returns it (the reference returns self).  The device copy is projected and becomes this object's host data; the
@@ -822,3 +889,26 @@ def acceptor(labels: Sequence[int], weight: float = 0.0) -> VectorFst:
         cur = nxt
     fst.set_final(cur, weight)
     return fst
+
+
+def shortest_distance(fst: Union[VectorFst, DeviceFst], reverse: bool = False) -> np.ndarray:
+    """algorithms::shortest_distance(fst, reverse) (shortest_distance.rs:307-311): the reference's Vec (its length
+    included)."""
+    dev = fst.to_device() if isinstance(fst, VectorFst) else fst
+    dist, n = dev.shortest_distance_with_len(reverse=reverse)
+    return dist[:n]
+
+
+def reweight(fst: VectorFst, potentials, reweight_type: ReweightType) -> VectorFst:
+    """algorithms::reweight (reweight.rs:29-154): in place, returns fst."""
+    return fst.reweight(potentials, reweight_type)
+
+
+def push_weights(fst: VectorFst, reweight_type: ReweightType) -> VectorFst:
+    """algorithms::push_weights (push.rs:76-82): in place, returns fst."""
+    return fst.push_weights(reweight_type)
+
+
+def push_weights_with_config(fst: VectorFst, reweight_type: ReweightType, config: PushWeightsConfig) -> VectorFst:
+    """algorithms::push_weights_with_config (push.rs:89-118): in place, returns fst."""
+    return fst.push_weights(reweight_type, config)

@@ -1,0 +1,732 @@
+"""shortest_distance(fst, reverse), reweight and push_weights (wfst_shortest_distance_with_config, wfst_reweight,
+wfst_push_weights): C-ABI surface without a GPU, the K14 known answers, and on the device parity with a restatement of
+rustfst's algorithms/reweight.rs + push.rs (written out below) over the oracle's distances, plus invariants that do not
+depend on that restatement."""
+import ctypes as C
+import inspect
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from rustfst_amd import synth
+from rustfst_amd._lib import TR_DTYPE
+
+from helpers import random_fst_flat, to_device, to_oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "k14_push.json")
+NEW_SYMBOLS = ("wfst_shortest_distance_with_config", "wfst_push_weights", "wfst_reweight")
+
+# ---------------------------------------------------------------- property bits (fst_properties/properties.rs:22-103)
+B = dict(ACCEPTOR=16, NOT_ACCEPTOR=17, I_DETERMINISTIC=18, NOT_I_DETERMINISTIC=19, O_DETERMINISTIC=20,
+         NOT_O_DETERMINISTIC=21, EPSILONS=22, NO_EPSILONS=23, I_EPSILONS=24, NO_I_EPSILONS=25, O_EPSILONS=26,
+         NO_O_EPSILONS=27, I_LABEL_SORTED=28, NOT_I_LABEL_SORTED=29, O_LABEL_SORTED=30, NOT_O_LABEL_SORTED=31,
+         WEIGHTED=32, UNWEIGHTED=33, CYCLIC=34, ACYCLIC=35, INITIAL_CYCLIC=36, INITIAL_ACYCLIC=37, TOP_SORTED=38,
+         NOT_TOP_SORTED=39, ACCESSIBLE=40, NOT_ACCESSIBLE=41, COACCESSIBLE=42, NOT_COACCESSIBLE=43, STRING=44,
+         NOT_STRING=45, WEIGHTED_CYCLES=46, UNWEIGHTED_CYCLES=47)
+globals().update({k: 1 << v for k, v in B.items()})
+
+
+def _m(*names):
+    return sum(1 << B[n] for n in names)
+
+
+LABEL_BITS = ("ACCEPTOR", "NOT_ACCEPTOR", "I_DETERMINISTIC", "NOT_I_DETERMINISTIC", "O_DETERMINISTIC",
+              "NOT_O_DETERMINISTIC", "EPSILONS", "NO_EPSILONS", "I_EPSILONS", "NO_I_EPSILONS", "O_EPSILONS",
+              "NO_O_EPSILONS", "I_LABEL_SORTED", "NOT_I_LABEL_SORTED", "O_LABEL_SORTED", "NOT_O_LABEL_SORTED")
+# properties.rs:166-300 / 436-465
+SET_START_MASK = _m(*LABEL_BITS, "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC", "TOP_SORTED", "NOT_TOP_SORTED",
+                    "COACCESSIBLE", "NOT_COACCESSIBLE", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
+SET_FINAL_MASK = _m(*LABEL_BITS, "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
+                    "NOT_TOP_SORTED", "ACCESSIBLE", "NOT_ACCESSIBLE", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
+ADD_STATE_MASK = _m(*LABEL_BITS, "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC",
+                    "TOP_SORTED", "NOT_TOP_SORTED", "NOT_ACCESSIBLE", "NOT_COACCESSIBLE", "NOT_STRING",
+                    "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
+ADD_ARC_MASK = _m("NOT_ACCEPTOR", "NOT_I_DETERMINISTIC", "NOT_O_DETERMINISTIC", "EPSILONS", "I_EPSILONS", "O_EPSILONS",
+                  "NOT_I_LABEL_SORTED", "NOT_O_LABEL_SORTED", "WEIGHTED", "CYCLIC", "INITIAL_CYCLIC", "NOT_TOP_SORTED",
+                  "ACCESSIBLE", "COACCESSIBLE", "WEIGHTED_CYCLES")
+ARC_RELEVANT = _m("ACCEPTOR", "NOT_ACCEPTOR", "EPSILONS", "NO_EPSILONS", "I_EPSILONS", "NO_I_EPSILONS", "O_EPSILONS",
+                  "NO_O_EPSILONS", "WEIGHTED", "UNWEIGHTED")
+WEIGHT_INVARIANT = _m(*LABEL_BITS, "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
+                      "NOT_TOP_SORTED", "ACCESSIBLE", "NOT_ACCESSIBLE", "COACCESSIBLE", "NOT_COACCESSIBLE", "STRING",
+                      "NOT_STRING")
+DFS_BITS = _m("CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "ACCESSIBLE", "NOT_ACCESSIBLE", "COACCESSIBLE",
+              "NOT_COACCESSIBLE")
+ALL = 0x0000FFFFFFFF0000
+
+# ---------------------------------------------------------------- TropicalWeight (tropical_weight.rs, semiring.rs)
+F32, INF = np.float32, np.float32(np.inf)
+KDELTA = F32(1.0 / 1024.0)
+
+
+def times(a, b):  # tropical_weight.rs:60-70
+    a, b = F32(a), F32(b)
+    return a if a == INF else (b if b == INF else F32(a + b))
+
+
+def divide(a, b):  # tropical_weight.rs:128-131: plain a - b
+    with np.errstate(invalid="ignore"):
+        return F32(F32(a) - F32(b))
+
+
+def approx_eq(a, b):  # semiring.rs:159-168
+    return bool(F32(a) <= F32(F32(b) + KDELTA) and F32(b) <= F32(F32(a) + KDELTA))
+
+
+def is_zero(w):
+    return approx_eq(w, INF)
+
+
+def is_one(w):
+    return approx_eq(w, 0.0)
+
+
+def weighted(w):
+    return not is_zero(w) and not is_one(w)
+
+
+# ---------------------------------------------------------------- mutate_properties.rs / trs_iter_mut.rs
+def p_set_final(p, old, new):  # mutate_properties.rs:15-37 (None = no final weight)
+    if old is not None and weighted(old):
+        p &= ~WEIGHTED
+    if new is not None and weighted(new):
+        p = (p | WEIGHTED) & ~UNWEIGHTED
+    return p & (SET_FINAL_MASK | WEIGHTED | UNWEIGHTED)
+
+
+def p_set_weight(p, old, new):  # trs_iter_mut.rs:279-305, 342-350
+    if weighted(old):
+        p &= ~WEIGHTED
+    if weighted(new):
+        p = (p | WEIGHTED) & ~UNWEIGHTED
+    return p & ARC_RELEVANT
+
+
+def p_add_state(p):  # :39-41
+    return p & ADD_STATE_MASK
+
+
+def p_add_tr(p, state, il, ol, w, ns):  # :43-100 (the new state has no previous arc)
+    if il != ol:
+        p = (p | NOT_ACCEPTOR) & ~ACCEPTOR
+    if il == 0:
+        p = (p | I_EPSILONS) & ~NO_I_EPSILONS
+        if ol == 0:
+            p = (p | EPSILONS) & ~NO_EPSILONS
+    if ol == 0:
+        p = (p | O_EPSILONS) & ~NO_O_EPSILONS
+    if weighted(w):
+        p = (p | WEIGHTED) & ~UNWEIGHTED
+    if ns <= state:
+        p = (p | NOT_TOP_SORTED) & ~TOP_SORTED
+    p &= ADD_ARC_MASK | ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | \
+        UNWEIGHTED | TOP_SORTED
+    if p & TOP_SORTED:
+        p |= ACYCLIC | INITIAL_ACYCLIC
+    return p
+
+
+def p_set_start(p):  # :7-13
+    out = p & SET_START_MASK
+    if p & ACYCLIC:
+        out |= INITIAL_ACYCLIC
+    return out
+
+
+# ---------------------------------------------------------------- graph facts (what SccVisitor's DFS decides)
+def _csr_next(flat):
+    return np.asarray(flat["offsets"], dtype=np.int64), np.asarray(flat["arcs"]["nextstate"], dtype=np.int64)
+
+
+def _reach(n, off, nxt, seeds, mark_seeds=True):
+    """states reachable from `seeds` (vectorised frontier search); the seeds count only when mark_seeds"""
+    vis = np.zeros(n, dtype=bool)
+    fr = np.asarray(seeds, dtype=np.int64)
+    if mark_seeds:
+        vis[fr] = True
+    while fr.size:
+        cnt = off[fr + 1] - off[fr]
+        idx = np.repeat(off[fr] - np.cumsum(np.r_[0, cnt[:-1]]), cnt) + np.arange(cnt.sum())
+        t = np.unique(nxt[idx])
+        t = t[~vis[t]]
+        vis[t] = True
+        fr = t
+    return vis
+
+
+def _transpose(n, off, nxt):
+    src = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    order = np.argsort(nxt, kind="stable")
+    roff = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(roff, nxt + 1, 1)
+    return np.cumsum(roff), src[order]
+
+
+def graph_facts(flat):
+    """(accessible, coaccessible, cyclic, initial_cyclic) of the graph: every state reachable from the start, every state
+    reaches a final state, a cycle anywhere, the start on a cycle — the four DFS pairs compute_fst_properties fills in
+    (visitors/scc_visitors.rs: a new DFS tree for an unreachable state, back arcs, back arcs into the start, SCCs without
+    a final state)."""
+    n, s0 = flat["n_states"], flat["start"]
+    off, nxt = _csr_next(flat)
+    accessible = bool(_reach(n, off, nxt, [s0]).all())
+    roff, rsrc = _transpose(n, off, nxt)
+    finals = np.nonzero(np.isfinite(flat["finals"]))[0]
+    coaccessible = bool(_reach(n, roff, rsrc, finals).all()) if finals.size else n == 0
+    indeg = np.bincount(nxt, minlength=n)
+    fr, removed = np.nonzero(indeg == 0)[0], 0
+    while fr.size:
+        removed += fr.size
+        cnt = off[fr + 1] - off[fr]
+        idx = np.repeat(off[fr] - np.cumsum(np.r_[0, cnt[:-1]]), cnt) + np.arange(cnt.sum())
+        t = nxt[idx]
+        np.subtract.at(indeg, t, 1)
+        t = np.unique(t)
+        fr = t[indeg[t] == 0]
+    cyclic = removed != n
+    initial_cyclic = bool(_reach(n, off, nxt, nxt[off[s0]:off[s0 + 1]])[s0])
+    return accessible, coaccessible, cyclic, initial_cyclic
+
+
+def dfs_bits(facts):
+    a, c, cy, ic = facts
+    return (ACCESSIBLE if a else NOT_ACCESSIBLE) | (COACCESSIBLE if c else NOT_COACCESSIBLE) | \
+        (CYCLIC if cy else ACYCLIC) | (INITIAL_CYCLIC if ic else INITIAL_ACYCLIC)
+
+
+# ---------------------------------------------------------------- restatement of reweight.rs / push.rs
+def reweight_ref(flat, potentials, to_final, facts=None):
+    """reweight(fst, potentials, type) (reweight.rs:29-154), statement by statement; finals as Option (None / value).
+    Returns a mutable dict: n_states, start, rows (list of [ilabel, olabel, weight, nextstate] lists per state), finals,
+    props."""
+    n, start = flat["n_states"], flat["start"]
+    off, arcs = flat["offsets"], flat["arcs"]
+    rows = [[[int(a["ilabel"]), int(a["olabel"]), F32(a["weight"]), int(a["nextstate"])] for a in arcs[off[s]:off[s + 1]]]
+            for s in range(n)]
+    finals = [None if not np.isfinite(f) else F32(f) for f in flat["finals"]]
+    pot = [F32(x) for x in potentials]
+    p = int(flat["props"])
+    fst = dict(n_states=n, start=start, rows=rows, finals=finals)
+    if n == 0:
+        fst["props"] = p
+        return fst
+    zero = INF
+    for state in range(n):
+        if state >= len(pot):  # :42-53
+            if to_final and finals[state] is not None:
+                new = times(zero, finals[state])
+                p = p_set_final(p, finals[state], new)
+                finals[state] = new
+            continue
+        d_s = pot[state]
+        if is_zero(d_s):  # :57-59
+            continue
+        for tr in rows[state]:  # :61-86
+            d_ns = pot[tr[3]] if tr[3] < len(pot) else zero
+            if is_zero(d_ns):
+                continue
+            w = divide(times(d_s, tr[2]), d_ns) if to_final else divide(times(tr[2], d_ns), d_s)
+            p = p_set_weight(p, tr[2], w)
+            tr[2] = w
+    for s in range(n):  # :88-103
+        fw = finals[s]
+        if fw is None:
+            continue
+        d_s = pot[s] if s < len(pot) else zero
+        if to_final:
+            fw = times(fw, d_s)
+        else:
+            if is_zero(d_s):
+                continue
+            fw = divide(fw, d_s)
+        p = p_set_final(p, finals[s], fw)
+        finals[s] = fw
+    if start is not None:  # :105-146
+        d_s = pot[start] if start < len(pot) else zero
+        if not is_one(d_s) and not is_zero(d_s):
+            if not (p & (INITIAL_CYCLIC | INITIAL_ACYCLIC)):  # compute_and_update_properties(INITIAL_ACYCLIC)
+                p = (p & ~DFS_BITS) | dfs_bits(facts if facts is not None else graph_facts(flat))
+            if p & INITIAL_ACYCLIC:
+                for tr in rows[start]:
+                    w = times(divide(0.0, d_s), tr[2]) if to_final else times(d_s, tr[2])
+                    p = p_set_weight(p, tr[2], w)
+                    tr[2] = w
+                if finals[start] is not None:
+                    fw = times(divide(0.0, d_s), finals[start]) if to_final else times(d_s, finals[start])
+                    p = p_set_final(p, finals[start], fw)
+                    finals[start] = fw
+            else:
+                s = n
+                rows.append([])
+                finals.append(None)
+                p = p_add_state(p)
+                w = divide(0.0, d_s) if to_final else d_s
+                p = p_add_tr(p, s, 0, 0, w, start)
+                rows[s].append([0, 0, w, start])
+                p = p_set_start(p)
+                fst["start"] = s
+                fst["n_states"] = n + 1
+    fst["props"] = p & WEIGHT_INVARIANT & ~COACCESSIBLE  # reweight_properties (mutate_properties.rs:640-644)
+    return fst
+
+
+def remove_weight_ref(fst, weight, at_final):  # push.rs:147-170
+    if is_one(weight) or is_zero(weight):
+        return fst
+    p = fst["props"]
+    if at_final:
+        for s in range(fst["n_states"]):
+            if fst["finals"][s] is not None:
+                fw = divide(fst["finals"][s], weight)
+                p = p_set_final(p, fst["finals"][s], fw)
+                fst["finals"][s] = fw
+    elif fst["start"] is not None:
+        st = fst["start"]
+        for tr in fst["rows"][st]:
+            w = divide(tr[2], weight)
+            p = p_set_weight(p, tr[2], w)
+            tr[2] = w
+        if fst["finals"][st] is not None:
+            fw = divide(fst["finals"][st], weight)
+            p = p_set_final(p, fst["finals"][st], fw)
+            fst["finals"][st] = fw
+    fst["props"] = p
+    return fst
+
+
+def push_ref(flat, dist, to_final, remove_total=False, facts=None):
+    """push_weights_with_config (push.rs:89-118) given the Vec shortest_distance_with_config returns (reverse distances
+    for ToInitial)."""
+    total = None
+    if remove_total:  # compute_total_weight (push.rs:120-142), on the FST before reweight
+        if not to_final:
+            s0 = flat["start"]
+            total = F32(dist[s0]) if s0 is not None and s0 < len(dist) else INF
+        else:
+            total = INF
+            for s, d in enumerate(dist):
+                f = flat["finals"][s]
+                total = min(total, times(d, f if np.isfinite(f) else INF))
+    fst = reweight_ref(flat, dist, to_final, facts)
+    if remove_total:
+        fst = remove_weight_ref(fst, total, to_final)
+    return fst
+
+
+def to_flat(fst):
+    """restatement output -> flat arrays as the device stores them (+inf = None: Some(zero) reads as not final)"""
+    rows = fst["rows"]
+    off = np.zeros(fst["n_states"] + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(r) for r in rows]) if rows else []
+    arcs = np.array([tuple(a) for r in rows for a in r], dtype=TR_DTYPE) if off[-1] else np.zeros(0, dtype=TR_DTYPE)
+    finals = np.array([INF if f is None else f for f in fst["finals"]], dtype=np.float32)
+    return dict(n_states=fst["n_states"], start=fst["start"], offsets=off, arcs=arcs, finals=finals,
+                props=fst["props"] & ALL)
+
+
+def reverse_len_rule(flat):
+    """rdistance.len() - 1 (shortest_distance.rs:322-334): the reversed search dequeues every state reachable from the
+    super-initial state (the states that reach a final state, + 1) and grows its Vec to the largest of them."""
+    n = flat["n_states"]
+    off, nxt = _csr_next(flat)
+    roff, rsrc = _transpose(n, off, nxt)
+    finals = np.nonzero(np.isfinite(flat["finals"]))[0]
+    if not finals.size:
+        return 0
+    return int(np.nonzero(_reach(n, roff, rsrc, finals))[0].max()) + 1
+
+
+def assert_same(got, exp, what):
+    assert got["n_states"] == exp["n_states"], f"{what}: num_states {got['n_states']} != {exp['n_states']}"
+    assert got["start"] == exp["start"], f"{what}: start"
+    np.testing.assert_array_equal(got["offsets"], exp["offsets"], err_msg=f"{what}: offsets")
+    for k in ("ilabel", "olabel", "nextstate"):
+        np.testing.assert_array_equal(got["arcs"][k], exp["arcs"][k], err_msg=f"{what}: arcs.{k}")
+    np.testing.assert_array_equal(got["arcs"]["weight"].view(np.uint32), exp["arcs"]["weight"].view(np.uint32),
+                                  err_msg=f"{what}: arc weights (bit pattern)")
+    np.testing.assert_array_equal(got["finals"].view(np.uint32), exp["finals"].view(np.uint32),
+                                  err_msg=f"{what}: final weights (bit pattern)")
+    assert got["props"] == exp["props"], f"{what}: props {got['props']:#x} != {exp['props']:#x}"
+
+
+def golden_cases():
+    with open(GOLDEN) as f:
+        return json.load(f)["cases"]
+
+
+def golden_flat(c):
+    arcs = np.array([tuple(a) for a in c["arcs"]], dtype=TR_DTYPE) if c["arcs"] else np.zeros(0, dtype=TR_DTYPE)
+    fin = np.array([np.inf if f is None else f for f in c["finals"]], dtype=np.float32)
+    return dict(n_states=c["n_states"], start=c["start"], offsets=np.array(c["offsets"], dtype=np.uint32), arcs=arcs,
+                finals=fin, props=int(c["props"], 16))
+
+
+def golden_expected(c):
+    e = c["expected"]
+    arcs = np.array([tuple(a) for a in e["arcs"]], dtype=TR_DTYPE) if e["arcs"] else np.zeros(0, dtype=TR_DTYPE)
+    fin = np.array([np.inf if f is None else f for f in e["finals"]], dtype=np.float32)
+    return dict(n_states=e["n_states"], start=e["start"], offsets=np.array(e["offsets"], dtype=np.uint32), arcs=arcs,
+                finals=fin, props=int(e["props"], 16))
+
+
+# ================================================================ no GPU
+def test_new_symbols_declared_and_bound(wfst_lib):
+    from rustfst_amd import _lib
+    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
+        header = f.read()
+    bound = {name for name, _, _ in _lib.SYMBOLS}
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bwfst_status\s+" + name + r"\s*\(", header), name
+        assert name in bound, name
+        assert hasattr(wfst_lib, name), name
+
+
+def test_config_structs_match_the_header():
+    from rustfst_amd import _lib
+    assert C.sizeof(_lib.ShortestDistanceConfig) == 8
+    assert _lib.ShortestDistanceConfig.reverse.offset == 0 and _lib.ShortestDistanceConfig.delta.offset == 4
+    assert C.sizeof(_lib.PushWeightsConfig) == 8
+    assert _lib.PushWeightsConfig.delta.offset == 0 and _lib.PushWeightsConfig.remove_total_weight.offset == 4
+
+
+def _ko_message(status):
+    from rustfst_amd import _lib
+    assert status == 1
+    msg = C.c_char_p()
+    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
+    text = msg.value.decode()
+    _lib.lib().wfst_string_destroy(msg)
+    return text
+
+
+def test_argument_validation_without_gpu(wfst_lib):
+    from rustfst_amd import _lib
+    out = C.c_void_p()
+    assert "reweight_type" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 2, C.byref(out)))
+    assert "potentials" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 3, 0, C.byref(out)))
+    assert "reweight_type" in _ko_message(wfst_lib.wfst_push_weights(None, None, 7, None, C.byref(out)))
+    bad = _lib.PushWeightsConfig(-1.0, 0)
+    assert "delta" in _ko_message(wfst_lib.wfst_push_weights(None, None, 0, C.byref(bad), C.byref(out)))
+    for d in (-1e-3, float("nan"), float("inf")):
+        cfg = _lib.ShortestDistanceConfig(1, d)
+        assert "delta" in _ko_message(wfst_lib.wfst_shortest_distance_with_config(None, None, C.byref(cfg), None, None))
+    assert out.value is None
+    # valid arguments, no handles: the usual null-pointer KO, nothing dereferenced
+    assert "null" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 1, C.byref(out)))
+
+
+def test_python_surface():
+    import rustfst_amd
+    sig = inspect.signature(rustfst_amd.DeviceFst.shortest_distance)
+    params = list(sig.parameters.values())
+    assert params[1].name == "want_hops" and params[1].default is False  # the old positional signature
+    assert sig.parameters["reverse"].default is False and sig.parameters["delta"].default is None
+    assert rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL.value == 0 and rustfst_amd.ReweightType.REWEIGHT_TO_FINAL.value == 1
+    cfg = rustfst_amd.PushWeightsConfig()
+    assert cfg.delta == 1.0 / 1024.0 and cfg.remove_total_weight is False
+    for name in ("shortest_distance", "reweight", "push_weights", "push_weights_with_config"):
+        assert callable(getattr(rustfst_amd, name))
+    with pytest.raises(ValueError):
+        rustfst_amd.DeviceFst.shortest_distance(None, want_hops=True, reverse=True)
+
+
+def _golden_run_ref(c):
+    flat = golden_flat(c)
+    to_final = c["reweight_type"] == 1
+    if c["op"] == "reweight":
+        return to_flat(reweight_ref(flat, c["potentials"], to_final))
+    return to_flat(push_ref(flat, c["distance"], to_final, c["remove_total_weight"]))
+
+
+def test_k14_restatement_reproduces_the_derivations():
+    """the hand derivations of K14_DERIVATION.md, replayed by this file's restatement (checks the restatement itself)"""
+    cases = golden_cases()
+    assert 6 <= len(cases) <= 8
+    for c in cases:
+        assert_same(_golden_run_ref(c), golden_expected(c), c["name"])
+
+
+# ================================================================ GPU
+def _dev_flat(d):
+    return d.to_flat()
+
+
+@pytest.mark.gpu
+def test_k14_on_the_device(gpu_ctx):
+    import rustfst_amd
+    for c in golden_cases():
+        dev = to_device(golden_flat(c), gpu_ctx)
+        rt = rustfst_amd.ReweightType(c["reweight_type"])
+        if c["op"] == "reweight":
+            got = dev.reweight(np.array(c["potentials"], dtype=np.float32), rt)
+        else:
+            got = dev.push_weights(rt, rustfst_amd.PushWeightsConfig(remove_total_weight=c["remove_total_weight"]))
+        assert_same(got.to_flat(), golden_expected(c), c["name"])
+
+
+SHAPES = [(1, 2, 4), (2, 1, 3), (5, 3, 4), (17, 3, 6), (40, 4, 8), (120, 5, 16), (300, 2, 32), (1000, 6, 64)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_reverse_distances_match_the_oracle(gpu_ctx, oracle, shape):
+    n, fan, sigma = shape
+    for seed in range(4):
+        rng = np.random.default_rng(1000 * n + seed)
+        flat = random_fst_flat(rng, n, fan, sigma, p_final=0.25)
+        exp = to_oracle(oracle, flat).reverse().shortest_distance()[1:]
+        dev = to_device(flat, gpu_ctx)
+        got, ln = dev.shortest_distance_with_len(reverse=True)
+        np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32), err_msg=f"{shape} seed {seed}")
+        assert ln == reverse_len_rule(flat), f"{shape} seed {seed}"
+        assert np.all(np.isinf(got[ln:]))
+        # forward: unchanged, and its length is 1 + the largest reachable id
+        fwd, fl = dev.shortest_distance_with_len()
+        np.testing.assert_array_equal(fwd.view(np.uint32), dev.shortest_distance().view(np.uint32))
+        off, nxt = _csr_next(flat)
+        assert fl == int(np.nonzero(_reach(n, off, nxt, [0]))[0].max()) + 1
+
+
+@pytest.mark.gpu
+def test_reverse_distances_transducer_and_no_start(gpu_ctx, oracle):
+    t = synth.make_transducer(100_000)
+    exp = to_oracle(oracle, t).reverse().shortest_distance()[1:]
+    dev = to_device(t, gpu_ctx)
+    got, ln = dev.shortest_distance_with_len(reverse=True)
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+    assert ln == reverse_len_rule(t)
+    again = dev.shortest_distance(reverse=True)  # the cached reversed handle
+    np.testing.assert_array_equal(again.view(np.uint32), got.view(np.uint32))
+    # no start state: reverse distances are still defined
+    rng = np.random.default_rng(5)
+    flat = random_fst_flat(rng, 30, 3, 5)
+    flat["start"] = None
+    got, ln = to_device(flat, gpu_ctx).shortest_distance_with_len(reverse=True)
+    exp = to_oracle(oracle, flat).reverse().shortest_distance()[1:]
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+    assert ln == reverse_len_rule(flat)
+
+
+def _random_potentials(rng, n):
+    k = int(rng.integers(0, n + 3))
+    pot = rng.integers(-2000, 2000, k).astype(np.float32) / 256
+    pot[rng.random(k) < 0.2] = np.inf
+    if k and rng.random() < 0.5:
+        pot[0] = rng.choice([0.0, 1.0 / 2048, -1.0 / 2048, 3.0])  # start potential: one, approximately one, or not
+    return pot
+
+
+@pytest.mark.gpu
+def test_reweight_matches_the_restatement(gpu_ctx):
+    import rustfst_amd
+    for seed in range(48):
+        rng = np.random.default_rng(7000 + seed)
+        n = int(rng.integers(1, 40))
+        flat = random_fst_flat(rng, n, 4, 6, p_eps_i=0.2, p_eps_o=0.2, acyclic=bool(seed % 3 == 0))
+        flat["props"] |= [0, INITIAL_ACYCLIC, INITIAL_CYCLIC, ACYCLIC | INITIAL_ACYCLIC][seed % 4]
+        pot = _random_potentials(rng, n)
+        dev = to_device(flat, gpu_ctx)
+        for rt in (0, 1):
+            got = dev.reweight(pot, rustfst_amd.ReweightType(rt)).to_flat()
+            exp = to_flat(reweight_ref(flat, list(pot), rt == 1))
+            assert_same(got, exp, f"seed {seed} type {rt}")
+
+
+def _oracle_dist(oracle, flat, to_final):
+    o = to_oracle(oracle, flat)
+    if to_final:
+        if flat["start"] is None:
+            return []
+        n = flat["n_states"]
+        off, nxt = _csr_next(flat)
+        ln = int(np.nonzero(_reach(n, off, nxt, [flat["start"]]))[0].max()) + 1
+        return list(o.shortest_distance()[:ln])
+    return list(o.reverse().shortest_distance()[1:][:reverse_len_rule(flat)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("remove", [False, True])
+def test_push_weights_matches_the_restatement(gpu_ctx, oracle, remove):
+    import rustfst_amd
+    cfg = rustfst_amd.PushWeightsConfig(remove_total_weight=remove)
+    for seed in range(24):
+        rng = np.random.default_rng(9000 + seed)
+        n = int(rng.integers(1, 60))
+        flat = random_fst_flat(rng, n, 4, 8, p_eps_i=0.1, acyclic=bool(seed % 2))
+        dev = to_device(flat, gpu_ctx)
+        for rt in (0, 1):
+            got = dev.push_weights(rustfst_amd.ReweightType(rt), cfg).to_flat()
+            exp = to_flat(push_ref(flat, _oracle_dist(oracle, flat, rt == 1), rt == 1, remove))
+            assert_same(got, exp, f"seed {seed} type {rt} remove {remove}")
+
+
+@pytest.mark.gpu
+def test_push_invariants(gpu_ctx, oracle):
+    import rustfst_amd
+    for seed in range(12):
+        rng = np.random.default_rng(300 + seed)
+        flat = random_fst_flat(rng, 80, 4, 8, acyclic=bool(seed % 2))
+        dev = to_device(flat, gpu_ctx)
+        best = oracle.OracleFst.shortest_path(to_oracle(oracle, flat)).total_weight
+        pushed = dev.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL).to_flat()
+        # every coaccessible state but the start: min(out-arc weights, final weight) is exactly 0
+        n = flat["n_states"]
+        off, nxt = _csr_next(flat)
+        roff, rsrc = _transpose(n, off, nxt)
+        fin = np.nonzero(np.isfinite(flat["finals"]))[0]
+        coacc = _reach(n, roff, rsrc, fin) if fin.size else np.zeros(n, dtype=bool)
+        po, pa, pf = pushed["offsets"], pushed["arcs"], pushed["finals"]
+        for s in np.nonzero(coacc)[0]:
+            if s == pushed["start"] or s == flat["start"]:
+                continue
+            ws = list(pa["weight"][po[s]:po[s + 1]]) + [pf[s]]
+            assert min(ws) == 0.0, f"seed {seed} state {s}: {ws}"
+        # the best path's weight: unchanged, and 0 once the total weight is removed
+        got = to_oracle(oracle, pushed).shortest_path().total_weight
+        assert got == pytest.approx(best, abs=1e-3) or (np.isinf(got) and np.isinf(best))
+        removed = dev.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL,
+                                   rustfst_amd.PushWeightsConfig(remove_total_weight=True)).to_flat()
+        got = to_oracle(oracle, removed).shortest_path().total_weight
+        if np.isfinite(best):
+            assert abs(got) <= 1e-3, f"seed {seed}: {got}"
+        fin_pushed = dev.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_FINAL,
+                                      rustfst_amd.PushWeightsConfig(remove_total_weight=True)).to_flat()
+        got = to_oracle(oracle, fin_pushed).shortest_path().total_weight
+        if np.isfinite(best):
+            assert abs(got) <= 1e-3, f"seed {seed} to final: {got}"
+
+
+@pytest.mark.gpu
+def test_compose_with_pushed_transducer(gpu_ctx):
+    import rustfst_amd
+    t = synth.make_transducer(2000, 8, 32, 0.0, seed=11)
+    accs = synth.make_acceptors(t, 6, 12, seed0=77)
+    dt = to_device(t, gpu_ctx)
+    total = float(dt.shortest_distance(reverse=True)[0])
+    for remove in (False, True):
+        pt = dt.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL,
+                             rustfst_amd.PushWeightsConfig(remove_total_weight=remove))
+        pt.tr_sort(True)  # (reweight keeps the arc order; the sort only restores the word's sortedness bit)
+        for a in accs:
+            da = to_device(a, gpu_ctx)
+            p0 = da.compose(dt).shortest_path().to_flat()
+            p1 = da.compose(pt).shortest_path().to_flat()
+
+            def weight(p):
+                if p["n_states"] == 0:
+                    return np.inf
+                return float(np.sum(p["arcs"]["weight"], dtype=np.float64) + np.sum(p["finals"][np.isfinite(p["finals"])]))
+            w0, w1 = weight(p0), weight(p1)
+            if np.isinf(w0):
+                assert np.isinf(w1)
+                continue
+            assert w1 == pytest.approx(w0 - (total if remove else 0.0), abs=1e-2)
+
+
+@pytest.mark.gpu
+def test_start_state_cyclicity(gpu_ctx):
+    """the start branch on FSTs whose word does not know INITIAL_ACYCLIC: both outcomes, the DFS bits in the word"""
+    import rustfst_amd
+    arcs = lambda rows: np.array(rows, dtype=TR_DTYPE)  # noqa: E731
+    # 0 -> 1 -> 2 (final), 1 -> 0: the start on a cycle
+    cyc = dict(n_states=3, start=0, offsets=np.array([0, 1, 3, 3], dtype=np.uint32),
+               arcs=arcs([(1, 1, 1.0, 1), (2, 2, 0.5, 2), (3, 3, 2.0, 0)]),
+               finals=np.array([np.inf, np.inf, 0.25], dtype=np.float32), props=0)
+    # start 0 without arcs (final), 1 -> 2 (final) -> 1 unreachable from it
+    acy = dict(n_states=3, start=0, offsets=np.array([0, 0, 1, 2], dtype=np.uint32),
+               arcs=arcs([(2, 2, 0.5, 2), (3, 3, 2.0, 1)]),
+               finals=np.array([0.75, np.inf, 0.25], dtype=np.float32), props=0)
+    for flat, facts in ((cyc, (True, True, True, True)), (acy, (False, True, True, False))):
+        assert graph_facts(flat) == facts
+        dev = to_device(flat, gpu_ctx)
+        for rt in (0, 1):
+            pot = np.array([2.5, 1.0, 0.5][:flat["n_states"]], dtype=np.float32)
+            got = dev.reweight(pot, rustfst_amd.ReweightType(rt)).to_flat()
+            assert_same(got, to_flat(reweight_ref(flat, list(pot), rt == 1)), f"facts {facts} type {rt}")
+            p = got["props"]
+            assert bool(p & CYCLIC) and not p & ACYCLIC  # merged by the DFS, kept by every later step
+            if facts[3]:  # a new start state; add_state drops ACCESSIBLE, set_start both INITIAL bits
+                assert got["n_states"] == flat["n_states"] + 1 and got["start"] == flat["n_states"]
+                assert not p & (INITIAL_CYCLIC | INITIAL_ACYCLIC | NOT_ACCESSIBLE)
+            else:  # the start reweighted in place (no arcs: only set_final's mask)
+                assert got["n_states"] == flat["n_states"] and got["start"] == 0
+                assert p & INITIAL_ACYCLIC and not p & INITIAL_CYCLIC
+                assert p & NOT_ACCESSIBLE and not p & ACCESSIBLE
+
+
+@pytest.mark.gpu
+def test_source_handle_unchanged(gpu_ctx):
+    import rustfst_amd
+    t = synth.make_transducer(5000, 6, 32, 0.0, seed=4)
+    dev = to_device(t, gpu_ctx)
+    before = dev.to_flat()
+    sp0 = dev.shortest_path().to_flat()
+    for rt in (0, 1):
+        for remove in (False, True):
+            dev.push_weights(rustfst_amd.ReweightType(rt), rustfst_amd.PushWeightsConfig(remove_total_weight=remove))
+    dev.reweight(np.arange(5000, dtype=np.float32) / 64, rustfst_amd.ReweightType.REWEIGHT_TO_FINAL)
+    after = dev.to_flat()
+    assert_same(after, before, "source after push")
+    sp1 = dev.shortest_path().to_flat()
+    assert_same(sp1, sp0, "shortest_path on the source")
+
+
+def _push_to_initial_numpy(flat, dist, facts):
+    """the restatement for ToInitial with the Vec as long as the FST (past the end = +inf: the same thing for reweight),
+    vectorised: the arc loop of reweight.rs:55-86 is one independent update per arc"""
+    n = flat["n_states"]
+    d = np.asarray(dist, dtype=np.float32)
+    off = flat["offsets"].astype(np.int64)
+    arcs = flat["arcs"].copy()
+    src = np.repeat(np.arange(n), np.diff(off))
+    d_s, d_n, w = d[src], d[arcs["nextstate"]], arcs["weight"]
+    keep = np.isinf(d_s) | np.isinf(d_n)
+    with np.errstate(invalid="ignore"):
+        wt = np.where(np.isinf(w), w, (w + d_n).astype(np.float32))
+        neww = (wt - d_s).astype(np.float32)
+    arcs["weight"] = np.where(keep, w, neww)
+    fin = flat["finals"].copy()
+    sel = np.isfinite(fin) & np.isfinite(d)
+    fin[sel] = (fin[sel] - d[sel]).astype(np.float32)
+    out = dict(flat, arcs=arcs, finals=fin)
+    # the word through the same steps as reweight_ref; the start branch needs only d[start], the word and the DFS facts
+    p = int(flat["props"])
+    if len(arcs):
+        p &= ARC_RELEVANT
+    if sel.any():
+        p = p_set_final(p, None, None)
+    s0, ds0 = flat["start"], d[flat["start"]]
+    if not is_one(ds0) and not is_zero(ds0):
+        if not (p & (INITIAL_CYCLIC | INITIAL_ACYCLIC)):
+            p = (p & ~DFS_BITS) | dfs_bits(facts)
+        assert not p & INITIAL_ACYCLIC  # (T: arc 0 of every state runs round a ring)
+        p = p_set_start(p_add_tr(p_add_state(p), n, 0, 0, ds0, s0))
+        out["n_states"], out["start"] = n + 1, n
+        out["offsets"] = np.r_[flat["offsets"], flat["offsets"][-1] + 1].astype(np.uint32)
+        out["arcs"] = np.r_[arcs, np.array([(0, 0, ds0, s0)], dtype=TR_DTYPE)]
+        out["finals"] = np.r_[fin, np.float32(np.inf)].astype(np.float32)
+    out["props"] = p & WEIGHT_INVARIANT & ~COACCESSIBLE & ALL
+    return out
+
+
+@pytest.mark.gpu
+def test_push_large_transducer(gpu_ctx, oracle):
+    """T of 1M states / 10M arcs: push (ToInitial) and shortest_path, all on the device, against the vectorised
+    restatement over the oracle's reverse distances"""
+    import rustfst_amd
+    t = synth.make_transducer(1_000_000)
+    dev = to_device(t, gpu_ctx)
+    pushed = dev.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL)
+    sp = pushed.shortest_path().to_flat()
+    got = pushed.to_flat()
+    dist = to_oracle(oracle, t).reverse().shortest_distance()[1:]
+    exp = _push_to_initial_numpy(t, dist, graph_facts(t))
+    assert_same(got, exp, "T 1M")
+    assert sp["n_states"] > 0
+    # the best path costs what it cost before the push
+    sp0 = dev.shortest_path().to_flat()
+    w = lambda p: float(np.sum(p["arcs"]["weight"], dtype=np.float64) + p["finals"][np.isfinite(p["finals"])].sum())  # noqa: E731
+    assert w(sp) == pytest.approx(w(sp0), abs=1e-2)
