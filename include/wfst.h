@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -191,6 +191,27 @@ wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* poten
  *      final state, renumbered stably (del_states, vector_fst/mutable_fst.rs:132-189), arcs into deleted states dropped.
  *      The reference trims in place; here a NEW handle is returned (the caller destroys the old one). ---- */
 wfst_status wfst_connect(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+
+/* ---- determinize / determinize_with_config (rustfst/src/algorithms/determinize/determinize_static.rs:149-190) of an
+ *      ACCEPTOR: DeterminizeFsa with DefaultCommonDivisor (determinize_fsa_op.rs:43-196) in LazyFst::compute's FIFO
+ *      first-touch order (lazy/lazy_fst.rs:226-269).  The reference branches on the stored property word: without
+ *      ACCEPTOR in it (a transducer, or an acceptor whose word does not say so) it takes the gallic transducer path,
+ *      which is not supported here: KO "transducers are not supported" (callers keep rustfst's own call).
+ *      det_type: 0 Functional, 1 NonFunctional, 2 Disambiguate (rustfst-ffi/src/algorithms/determinize.rs:17-25),
+ *      anything else is KO; for an acceptor it changes only the property word (determinize_properties,
+ *      mutate_properties.rs:247-279, through NO_EPSILONS).  cfg == NULL: DeterminizeConfig::default() = {KDELTA,
+ *      Functional}.  delta must be finite and > 0 (the reference quantizes to NaN with 0).
+ *      Subset order: after merging duplicate destinations the reference collects a subset from a HashMap, an
+ *      unspecified order that takes part in its identity; here elements stay in ascending state order (as in the
+ *      `unique` n-best branch), so every weighted subset is one state.  A subset joins the LOWEST-id state with the same
+ *      states and pairwise approx_eq weights (|a - b| <= KDELTA, whatever delta is).  No start state: the empty FST.
+ *      A cyclic weighted acceptor without the twins property does not determinize: KO beyond 16 M states / 256 M
+ *      subset elements.  A NEW handle; fst is left as it is. ---- */
+typedef struct {
+  float delta;
+  uint32_t det_type;
+} wfst_determinize_config;
+wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_determinize_config* cfg, wfst_fst** out);
 
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no

@@ -16,6 +16,7 @@
 //   shortest_distance(&fst, reverse) -> Vec<W>                   shortest_distance(fst, reverse) -> std::vector<float>
 //   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
 //   push_weights(&mut fst, ..) / push_weights_with_config(..)    push_weights(..) / push_weights_with_config(..)  push.rs:76-118
+//   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -238,6 +239,21 @@ inline void push_weights_with_config(VectorFst& fst, ReweightType reweight_type,
   fst = detail::download(c);
 }
 inline void push_weights(VectorFst& fst, ReweightType reweight_type) { push_weights_with_config(fst, reweight_type, PushWeightsConfig{}); }
+
+// determinize[_with_config] (determinize_static.rs:149-190): acceptors only (a transducer throws); a new FST, like the reference
+enum class DeterminizeType : uint32_t { DeterminizeFunctional = 0, DeterminizeNonFunctional = 1, DeterminizeDisambiguate = 2 };
+struct DeterminizeConfig {  // determinize_static.rs:128-147
+  float delta = 1.0f / 1024.0f;
+  DeterminizeType det_type = DeterminizeType::DeterminizeFunctional;
+};
+inline VectorFst determinize_with_config(const VectorFst& fst, const DeterminizeConfig& config) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  const wfst_determinize_config cfg{config.delta, (uint32_t)config.det_type};
+  check(wfst_determinize(Context::current().get(), a.h, &cfg, &c.h));
+  return detail::download(c);
+}
+inline VectorFst determinize(const VectorFst& fst) { return determinize_with_config(fst, DeterminizeConfig{}); }
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

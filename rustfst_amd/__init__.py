@@ -37,11 +37,16 @@ from .fst import (  # noqa: F401
     push_weights_with_config,
     reweight,
     shortest_distance,
+    DeterminizeConfig,
+    DeterminizeType,
+    determinize,
+    determinize_with_config,
 )
 
 __all__ = [
     "ComposeConfig", "ComposeFilter", "Context", "DeviceFst", "ShortestPathConfig", "Tr", "VectorFst", "acceptor",
     "compose", "compose_shortest_path_batch", "compose_shortest_path_batch_begin", "compose_shortest_path_batch_packed", "shortest_path_batch", "last_nbest_path", "HandleArray", "LookAhead", "ProjectType", "project", "compose_with_config", "default_context", "set_default_context",
     "shortestpath", "shortestpath_with_config", "WfstError",
-    "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance", "TR_DTYPE", "LIB_PATH",
+    "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance",
+    "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config", "TR_DTYPE", "LIB_PATH",
 ]

@@ -31,6 +31,10 @@ class PushWeightsConfig(C.Structure):
     _fields_ = [("delta", C.c_float), ("remove_total_weight", C.c_uint32)]
 
 
+class DeterminizeConfig(C.Structure):
+    _fields_ = [("delta", C.c_float), ("det_type", C.c_uint32)]
+
+
 TIES_UNKNOWN = (1 << 64) - 1  # WFST_TIES_UNKNOWN
 
 
@@ -89,6 +93,7 @@ SYMBOLS = [
     ("wfst_shortest_distance_with_config", C.c_int, [_vp, _vp, _P(ShortestDistanceConfig), _vp, _P(_u32)]),
     ("wfst_push_weights", C.c_int, [_vp, _vp, _u32, _P(PushWeightsConfig), _P(_vp)]),
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
+    ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

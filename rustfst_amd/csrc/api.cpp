@@ -462,6 +462,19 @@ wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* poten
   });
 }
 
+// determinize_with_config (determinize_static.rs:176-190); DeterminizeConfig::default() = {KDELTA, Functional} when cfg == NULL
+wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_determinize_config* cfg, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    const wfst_determinize_config c = cfg ? *cfg : wfst_determinize_config{1.0f / 1024.0f, 0u};
+    if (c.det_type > 2) throw Error("determinize: unknown det_type " + std::to_string(c.det_type));
+    if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("determinize: delta must be finite and > 0");
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = determinize_fst(ctx, fst, c.delta, c.det_type);
+  });
+}
+
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

@@ -267,6 +267,18 @@ inline uint64_t dfs_bits(bool accessible, bool coaccessible, bool cyclic, bool i
 }
 inline uint64_t merge_dfs(uint64_t in, uint64_t dfs) { return (in & ~DFS_BITS) | (dfs & DFS_BITS); }
 
+// determinize_properties(inprops, has_subsequential_label = false, distinct_psubsequential_labels)
+// (mutate_properties.rs:247-279), as determinize_with_config sets it (determinize_static.rs:186-190)
+inline uint64_t determinize(uint64_t in, bool distinct_psubsequential_labels) {
+  uint64_t out = ACCESSIBLE;
+  if ((in & ACCEPTOR) || ((in & NO_I_EPSILONS) && distinct_psubsequential_labels)) out |= I_DETERMINISTIC;
+  out |= (ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | COACCESSIBLE | STRING) & in;
+  if ((in & NO_I_EPSILONS) && distinct_psubsequential_labels) out |= NO_EPSILONS & in;
+  if (in & ACCESSIBLE) out |= (I_EPSILONS | O_EPSILONS | CYCLIC) & in;
+  if (in & ACCEPTOR) out |= (NO_I_EPSILONS | NO_O_EPSILONS) & in;
+  return out;
+}
+
 inline uint64_t compose_result(uint64_t p1, uint64_t p2, bool connected, bool has_start) {
   // start None: LazyFst::compute returns F2::new() untouched (lazy_fst.rs:229-232)
   uint64_t p = has_start ? compose(p1, p2) : NULL_PROPS;

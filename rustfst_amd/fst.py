@@ -360,6 +360,14 @@ class DeviceFst:
               "Error during push_weights")
         return DeviceFst(out, self.ctx)
 
+    def determinize(self, config: Optional["DeterminizeConfig"] = None) -> "DeviceFst":
+        """algorithms::determinize_with_config (determinize_static.rs:149-190) of an acceptor (wfst_determinize): a NEW
+        FST.  A word without ACCEPTOR (a transducer) raises WfstError: that path stays on rustfst."""
+        out = C.c_void_p()
+        cfg = config._c() if config is not None else None
+        check(_lib.lib().wfst_determinize(self.ctx._h, self._h, cfg, C.byref(out)), "Error during determinization")
+        return DeviceFst(out, self.ctx)
+
 
 class HandleArray:
     """A batch of DeviceFst handles marshalled once for the C-ABI (`const wfst_fst* const*`): callers that submit the
@@ -666,6 +674,23 @@ class PushWeightsConfig:
         return C.pointer(_lib.PushWeightsConfig(self.delta, 1 if self.remove_total_weight else 0))
 
 
+class DeterminizeType(Enum):  # rustfst-python/rustfst/algorithms/determinize.py:15-33 (the ffi numbering)
+    DETERMINIZE_FUNCTIONAL = 0
+    DETERMINIZE_NON_FUNCTIONAL = 1
+    DETERMINIZE_DISAMBIGUATE = 2
+
+
+class DeterminizeConfig:
+    """rustfst-python determinize.py:36-58: DeterminizeConfig(det_type, delta=None); delta None = KDELTA."""
+
+    def __init__(self, det_type: DeterminizeType, delta: Optional[float] = None):
+        self.det_type = DeterminizeType(det_type)
+        self.delta = KDELTA if delta is None else float(delta)
+
+    def _c(self):
+        return C.pointer(_lib.DeterminizeConfig(self.delta, self.det_type.value))
+
+
 # ------------------------------------------------------------------ VectorFst mirror
 class VectorFst:
     """Mutable FST stored in vectors (rustfst-python/rustfst/fst/vector_fst.py:29-790, subset on the path)."""
@@ -842,6 +867,10 @@ class VectorFst:
         self._dev = None
         return self
 
+    def determinize(self, config: Optional[DeterminizeConfig] = None) -> "VectorFst":
+        """rustfst-python vector_fst.py `determinize`: a NEW VectorFst (this one is left as it is)."""
+        return self.to_device().determinize(config).to_vector_fst()
+
     def project(self, proj_type: Union["ProjectType", None] = None) -> "VectorFst":
         """rustfst-python vector_fst.py:525-538 `project` (algorithms/project.py:27-50): projects THIS FST in place and
         returns it (the reference returns self).  The device copy is projected and becomes this object's host data; the
@@ -912,3 +941,13 @@ def push_weights(fst: VectorFst, reweight_type: ReweightType) -> VectorFst:
 def push_weights_with_config(fst: VectorFst, reweight_type: ReweightType, config: PushWeightsConfig) -> VectorFst:
     """algorithms::push_weights_with_config (push.rs:89-118): in place, returns fst."""
     return fst.push_weights(reweight_type, config)
+
+
+def determinize(fst: VectorFst) -> VectorFst:
+    """algorithms::determinize (determinize_static.rs:149-156): a new FST (acceptors only)."""
+    return fst.determinize()
+
+
+def determinize_with_config(fst: VectorFst, config: DeterminizeConfig) -> VectorFst:
+    """algorithms::determinize_with_config (determinize_static.rs:176-190): a new FST (acceptors only)."""
+    return fst.determinize(config)

@@ -1,0 +1,490 @@
+"""determinize / determinize_with_config of acceptors (wfst_determinize): the C-ABI surface without a GPU, a Python
+restatement of rustfst's DeterminizeFsa (written out below) checked against the K12 / K15 known answers and the oracle,
+and on the device parity with the oracle in every regime, closed-form answers at scale, invariants and error handling."""
+import ctypes as C
+import inspect
+import json
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from rustfst_amd import synth
+from rustfst_amd._lib import TR_DTYPE
+
+from helpers import assert_flat_identical, enumerate_paths, random_fst_flat, to_device, to_oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+KDELTA = 1.0 / 1024.0
+INF = np.float32(np.inf)
+f32 = np.float32
+
+# fst_properties/properties.rs:22-103
+ACCEPTOR, I_DETERMINISTIC = 1 << 16, 1 << 18
+NO_EPSILONS, I_EPSILONS, NO_I_EPSILONS, O_EPSILONS, NO_O_EPSILONS = 1 << 23, 1 << 24, 1 << 25, 1 << 26, 1 << 27
+CYCLIC, ACYCLIC, INITIAL_ACYCLIC = 1 << 34, 1 << 35, 1 << 37
+ACCESSIBLE, COACCESSIBLE, STRING = 1 << 40, 1 << 42, 1 << 44
+PATHS = ("narrow", "wide", "auto")
+
+
+# ---------------------------------------------------------------- restatement (determinize_fsa_op.rs, state_table.rs)
+def determinize_props(p, distinct):  # mutate_properties.rs:247-279 with has_subsequential_label = false
+    out = ACCESSIBLE
+    if p & ACCEPTOR or (p & NO_I_EPSILONS and distinct):
+        out |= I_DETERMINISTIC
+    out |= (ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | COACCESSIBLE | STRING) & p
+    if p & NO_I_EPSILONS and distinct:
+        out |= NO_EPSILONS & p
+    if p & ACCESSIBLE:
+        out |= (I_EPSILONS | O_EPSILONS | CYCLIC) & p
+    if p & ACCEPTOR:
+        out |= (NO_I_EPSILONS | NO_O_EPSILONS) & p
+    return out
+
+
+def wplus(a, b):  # plus_assign: exact <
+    return b if b < a else a
+
+
+def wtimes(a, b):
+    return a if a == INF else (b if b == INF else f32(a + b))
+
+
+def quantize(v, delta):  # semiring.rs:132-145
+    if np.isinf(v):
+        return v
+    return f32(f32(np.floor(f32(f32(v / f32(delta)) + f32(0.5)))) * f32(delta))
+
+
+def approx_eq(a, b):  # |a - b| <= KDELTA, whatever delta is
+    return a <= f32(b + f32(KDELTA)) and b <= f32(a + f32(KDELTA))
+
+
+def determinize_ref(flat, delta=KDELTA, det_type=0, max_states=1 << 20):
+    """DeterminizeFsa with DefaultCommonDivisor in LazyFst::compute's FIFO first-touch order; subsets in ascending state
+    order; a candidate joins the lowest-id state with the same states and approx_eq weights."""
+    if not flat["props"] & ACCEPTOR:
+        raise ValueError("transducers are not supported")
+    props = determinize_props(flat["props"], det_type != 1)
+    if flat["start"] is None or flat["n_states"] == 0:
+        return dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
+                    finals=np.zeros(0, np.float32), props=props)
+    off, arcs, fin = flat["offsets"], flat["arcs"], flat["finals"]
+    tuples = [((int(flat["start"]), f32(0.0)),)]
+    by_states = {(int(flat["start"]),): [0]}
+    rows, finals, offsets = [], [], [0]
+
+    def find(t):
+        ids = by_states.setdefault(tuple(s for s, _ in t), [])
+        for i in ids:
+            if all(approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[i])):
+                return i
+        ids.append(len(tuples))
+        tuples.append(t)
+        if len(tuples) > max_states:
+            raise RuntimeError("does not determinize")
+        return len(tuples) - 1
+
+    s = 0
+    while s < len(tuples):
+        cand = [(int(a["ilabel"]), int(a["nextstate"]), wtimes(w, f32(a["weight"])))
+                for q, w in tuples[s] for a in arcs[off[q]:off[q + 1]]]
+        cand.sort(key=lambda c: (c[0], c[1]))  # stable
+        fw = INF
+        for q, w in tuples[s]:
+            fw = wplus(fw, wtimes(w, f32(fin[q])))
+        i = 0
+        while i < len(cand):
+            j, weight = i, INF
+            while j < len(cand) and cand[j][0] == cand[i][0]:
+                weight = wplus(weight, cand[j][2])
+                j += 1
+            merged = []
+            for _, q, w in cand[i:j]:
+                if merged and merged[-1][0] == q:
+                    merged[-1][1] = wplus(merged[-1][1], w)
+                else:
+                    merged.append([q, w])
+            t = tuple((q, quantize(f32(w - weight), delta)) for q, w in merged)
+            rows.append((cand[i][0], cand[i][0], weight, find(t)))
+            i = j
+        offsets.append(len(rows))
+        finals.append(fw)
+        s += 1
+    a = np.zeros(len(rows), TR_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = r
+    return dict(n_states=len(tuples), start=0, offsets=np.array(offsets, np.uint32), arcs=a,
+                finals=np.array(finals, np.float32), props=props)
+
+
+# ---------------------------------------------------------------- inputs
+def golden(name):
+    with open(os.path.join(GOLDEN, name)) as f:
+        return json.load(f)["cases"]
+
+
+def flat_of(e, default_props=ACCEPTOR):
+    """the k15 format (offsets, [il, ol, w, ns] rows, finals with null) or the k12 one (arc rows [s, il, ol, w, ns],
+    finals as [s, w] pairs)"""
+    n = e["n_states"]
+    if "offsets" in e:
+        rows, offsets = e["arcs"], e["offsets"]
+        fin = [np.inf if w is None else w for w in e["finals"]]
+    else:
+        per = [[] for _ in range(n)]
+        for s, il, ol, w, ns in e["arcs"]:
+            per[s].append((il, ol, w, ns))
+        rows, offsets = [r for p in per for r in p], np.cumsum([0] + [len(p) for p in per])
+        fin = [np.inf] * n
+        for s, w in e["finals"]:
+            fin[s] = w
+    arcs = np.zeros(len(rows), TR_DTYPE)
+    for k, r in enumerate(rows):
+        arcs[k] = tuple(r)
+    props = int(e["props"], 16) if "props" in e else default_props
+    return dict(n_states=n, start=e["start"], offsets=np.array(offsets, np.uint32), arcs=arcs,
+                finals=np.array(fin, np.float32), props=props)
+
+
+def random_acceptor(rng, n, fanout, sigma, **kw):
+    f = random_fst_flat(rng, n, fanout, sigma, **kw)
+    f["arcs"]["olabel"] = f["arcs"]["ilabel"]
+    f["props"] |= ACCEPTOR
+    return f
+
+
+def f32_weights(rng, f):
+    f["arcs"]["weight"] = rng.random(len(f["arcs"])).astype(np.float32) * np.float32(3.0)
+    fin = f["finals"]
+    f["finals"] = np.where(np.isfinite(fin), rng.random(len(fin)).astype(np.float32), np.inf).astype(np.float32)
+    return f
+
+
+def parity_inputs():
+    """(name, flat, delta) — acyclic DAGs with small alphabets, epsilon labels, cyclic unweighted, integer and arbitrary
+    f32 weights, non-default deltas"""
+    rng = np.random.default_rng(1515)
+    out = []
+    for k in range(6):
+        n = int(rng.integers(2, 40))
+        out.append((f"dag{k}", random_acceptor(rng, n, 4, 2 + k % 2, acyclic=True), KDELTA))
+    for k in range(3):
+        out.append((f"eps{k}", random_acceptor(rng, 30, 3, 3, p_eps_i=0.3, acyclic=True), KDELTA))
+    for k in range(4):
+        out.append((f"cyclic_unweighted{k}", random_acceptor(rng, 25 + 10 * k, 3, 3, max_w=1, p_eps_i=0.1), KDELTA))
+    for k in range(3):
+        out.append((f"int{k}", random_acceptor(rng, 40, 4, 3, weight_grid=1, max_w=5, acyclic=True), KDELTA))
+    for k in range(3):
+        out.append((f"f32_{k}", f32_weights(rng, random_acceptor(rng, 40, 4, 3, acyclic=True)), KDELTA))
+    for k, d in enumerate((0.5, 0.1, 1.0 / 3.0)):
+        out.append((f"delta{k}", random_acceptor(rng, 40, 4, 3, acyclic=True), d))
+    out.append(("empty", dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
+                              finals=np.zeros(0, np.float32), props=ACCEPTOR), KDELTA))
+    return out
+
+
+def collision_level(S=64, M=200, seed=7):
+    """a start state with S arcs (distinct labels) into states 1..S; each of those has M labels, every label with one
+    arc into A (weight 0) and one into B (weight k * KDELTA, k random in 0..12): the second level holds S * M candidates
+    with the same state set {A, B} and weights a KDELTA apart"""
+    rng = np.random.default_rng(seed)
+    A, B, F = S + 1, S + 2, S + 3
+    rows = [[(j + 1, j + 1, 0.0, j + 1) for j in range(S)]]
+    for s in range(S):
+        r = []
+        for i in range(M):
+            r += [(i + 1, i + 1, 0.0, A), (i + 1, i + 1, float(rng.integers(0, 13)) * KDELTA, B)]
+        rows.append(r)
+    rows += [[(1, 1, 0.0, F)], [(1, 1, 0.0, F)], []]
+    arcs = np.array([x for r in rows for x in r], dtype=TR_DTYPE)
+    offsets = np.cumsum([0] + [len(r) for r in rows]).astype(np.uint32)
+    fin = np.full(S + 4, np.inf, np.float32)
+    fin[F] = 0.0
+    return dict(n_states=S + 4, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
+
+
+def twin_copy(n, seed=3):
+    """D = make_transducer(n) with the first arc per (state, ilabel), olabel = ilabel; N on 2n states (every arc four
+    times, the copy +0.5), finals f(q) on both copies.  Returns (N, expected det(N)): D in FIFO first-touch order from
+    {(0, 0)}, the other states {(r, 0), (r + n, 0.5)}, D's weights and finals."""
+    t = synth.make_transducer(n, seed=seed)
+    off, arcs = t["offsets"].astype(np.int64), t["arcs"]
+    src = np.repeat(np.arange(n), np.diff(off))
+    keep = np.ones(len(arcs), bool)
+    keep[1:] = (src[1:] != src[:-1]) | (arcs["ilabel"][1:] != arcs["ilabel"][:-1])
+    src, da = src[keep], arcs[keep].copy()
+    da["olabel"] = da["ilabel"]
+    doff = np.zeros(n + 1, np.int64)
+    np.add.at(doff, src + 1, 1)
+    doff = np.cumsum(doff)
+    deg = np.diff(doff)
+    fin = t["finals"].astype(np.float32)
+    # N: state q (q < n) and q + n both carry, per kept arc (a, w, r): (a, w, r), (a, w + 0.5, r + n)
+    nd = 2 * deg
+    noff = np.concatenate([[0], np.cumsum(np.concatenate([nd, nd]))]).astype(np.uint32)
+    one = np.empty(2 * len(da), TR_DTYPE)
+    one["ilabel"] = np.repeat(da["ilabel"], 2)
+    one["olabel"] = one["ilabel"]
+    one["weight"] = np.repeat(da["weight"], 2)
+    one["weight"][1::2] = da["weight"] + np.float32(0.5)
+    one["nextstate"] = np.repeat(da["nextstate"], 2)
+    one["nextstate"][1::2] = da["nextstate"] + n
+    N = dict(n_states=2 * n, start=0, offsets=noff, arcs=np.concatenate([one, one]),
+             finals=np.concatenate([fin, fin]), props=ACCEPTOR)
+    # expected: BFS over D; id 0 = the start subset, D state r -> its own id the first time an arc reaches it
+    ids = np.full(n, -1, np.int64)
+    order = [0]  # D state of every result state (the start first)
+    frontier = np.array([0])
+    out_rows = []
+    next_id = 1
+    while len(frontier):
+        seg = [np.arange(doff[q], doff[q + 1]) for q in frontier]
+        idx = np.concatenate(seg) if seg else np.zeros(0, np.int64)
+        tgt = da["nextstate"][idx].astype(np.int64)
+        new = tgt[ids[tgt] < 0]
+        _, first = np.unique(new, return_index=True)
+        fresh = new[np.sort(first)]
+        ids[fresh] = next_id + np.arange(len(fresh))
+        next_id += len(fresh)
+        order += list(fresh)
+        out_rows.append((idx, ids[tgt]))
+        frontier = fresh
+    idx = np.concatenate([r[0] for r in out_rows])
+    dst = np.concatenate([r[1] for r in out_rows])
+    exp_arcs = np.empty(len(idx), TR_DTYPE)
+    exp_arcs["ilabel"] = da["ilabel"][idx]
+    exp_arcs["olabel"] = da["ilabel"][idx]
+    exp_arcs["weight"] = da["weight"][idx]
+    exp_arcs["nextstate"] = dst
+    order = np.array(order)
+    exp = dict(n_states=len(order), start=0,
+               offsets=np.concatenate([[0], np.cumsum(deg[order])]).astype(np.uint32), arcs=exp_arcs,
+               finals=fin[order], props=determinize_props(ACCEPTOR, True))
+    return N, exp
+
+
+def diamond_chain(levels, seed=11):
+    """start 0 -> {1, 2}; states 2k-1, 2k each with arcs (label 1) into 2k+1 and 2k+2; the last two states final"""
+    rng = np.random.default_rng(seed)
+    n = 2 * levels + 1
+    rows = [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)]]
+    for s in range(1, n):
+        if s < n - 2:
+            base = 2 * ((s + 1) // 2) + 1
+            rows.append([(1, 1, float(rng.integers(0, 4)), base), (1, 1, float(rng.integers(0, 4)), base + 1)])
+        else:
+            rows.append([])
+    arcs = np.array([x for r in rows for x in r], dtype=TR_DTYPE)
+    offsets = np.cumsum([0] + [len(r) for r in rows]).astype(np.uint32)
+    fin = np.full(n, np.inf, np.float32)
+    fin[n - 2:] = [0.0, 2.0]
+    return dict(n_states=n, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
+
+
+def same(got, exp, what, props=True):
+    assert_flat_identical(got, exp, what, check_props=props)
+
+
+# ================================================================ no GPU
+def test_new_symbol_declared_and_bound(wfst_lib):
+    from rustfst_amd import _lib
+    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
+        header = f.read()
+    assert re.search(r"\bwfst_status\s+wfst_determinize\s*\(", header)
+    assert re.search(r"typedef struct \{\s*float delta;\s*uint32_t det_type;\s*\} wfst_determinize_config;", header)
+    assert "wfst_determinize" in {name for name, _, _ in _lib.SYMBOLS}
+    assert hasattr(wfst_lib, "wfst_determinize")
+    assert C.sizeof(_lib.DeterminizeConfig) == 8
+    assert _lib.DeterminizeConfig.delta.offset == 0 and _lib.DeterminizeConfig.det_type.offset == 4
+
+
+def _ko_message(status):
+    from rustfst_amd import _lib
+    assert status == 1
+    msg = C.c_char_p()
+    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
+    text = msg.value.decode()
+    _lib.lib().wfst_string_destroy(msg)
+    return text
+
+
+def test_argument_validation_without_gpu(wfst_lib):
+    from rustfst_amd import _lib
+    out = C.c_void_p()
+    assert "null" in _ko_message(wfst_lib.wfst_determinize(None, None, None, C.byref(out)))
+    assert "null" in _ko_message(wfst_lib.wfst_determinize(None, None, None, None))
+    bad = _lib.DeterminizeConfig(KDELTA, 3)
+    assert "det_type" in _ko_message(wfst_lib.wfst_determinize(None, None, C.byref(bad), C.byref(out)))
+    for d in (0.0, -1.0, float("nan"), float("inf")):
+        cfg = _lib.DeterminizeConfig(d, 0)
+        assert "delta" in _ko_message(wfst_lib.wfst_determinize(None, None, C.byref(cfg), C.byref(out)))
+    assert out.value is None
+
+
+def test_python_surface():
+    import rustfst_amd
+    T = rustfst_amd.DeterminizeType
+    assert (T.DETERMINIZE_FUNCTIONAL.value, T.DETERMINIZE_NON_FUNCTIONAL.value, T.DETERMINIZE_DISAMBIGUATE.value) == (0, 1, 2)
+    cfg = rustfst_amd.DeterminizeConfig(T.DETERMINIZE_FUNCTIONAL)
+    assert cfg.delta == KDELTA and cfg.det_type is T.DETERMINIZE_FUNCTIONAL
+    assert rustfst_amd.DeterminizeConfig(T.DETERMINIZE_NON_FUNCTIONAL, 0.25).delta == 0.25
+    for name in ("determinize", "determinize_with_config", "DeterminizeConfig", "DeterminizeType"):
+        assert name in rustfst_amd.__all__ and hasattr(rustfst_amd, name)
+    assert list(inspect.signature(rustfst_amd.DeviceFst.determinize).parameters) == ["self", "config"]
+    assert list(inspect.signature(rustfst_amd.VectorFst.determinize).parameters) == ["self", "config"]
+
+
+def test_restatement_reproduces_k12_and_k15():
+    for c in golden("k12_determinize.json"):
+        got = determinize_ref(flat_of(c["fst"]))
+        same(got, flat_of(c["expected"]), c["name"], props=False)
+    cases = golden("k15_determinize.json")
+    assert len(cases) >= 10
+    for c in cases:
+        same(determinize_ref(flat_of(c["fst"]), c["delta"], c["det_type"]), flat_of(c["expected"]), c["name"])
+    n = {c["name"]: flat_of(c["expected"])["n_states"] for c in cases}
+    assert n["non_transitive_3_4_5"] == 4 and n["non_transitive_4_3_5"] == 3
+
+
+def test_restatement_matches_the_oracle(oracle):
+    for name, flat, delta in parity_inputs() + [("collisions", collision_level(8, 40), KDELTA)]:
+        exp = to_oracle(oracle, flat).determinize_fsa(delta).to_flat()
+        same(determinize_ref(flat, delta), exp, name, props=False)
+    for c in golden("k15_determinize.json"):
+        flat = flat_of(c["fst"])
+        same(to_oracle(oracle, flat).determinize_fsa(c["delta"]).to_flat(), flat_of(c["expected"]), c["name"], props=False)
+
+
+def test_twin_copy_closed_form_matches_the_restatement():
+    N, exp = twin_copy(300)
+    same(determinize_ref(N), exp, "twin copy n=300")
+
+
+# ================================================================ GPU
+def _det(flat, ctx, delta=KDELTA, det_type=0):
+    import rustfst_amd
+    cfg = rustfst_amd.DeterminizeConfig(rustfst_amd.DeterminizeType(det_type), delta)
+    return to_device(flat, ctx).determinize(cfg).to_flat()
+
+
+@pytest.mark.gpu
+def test_known_answers_on_the_device(gpu_ctx, monkeypatch):
+    for path in PATHS:
+        monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+        for c in golden("k12_determinize.json"):
+            same(_det(flat_of(c["fst"]), gpu_ctx), flat_of(c["expected"]), f"{c['name']} {path}", props=False)
+        for c in golden("k15_determinize.json"):
+            same(_det(flat_of(c["fst"]), gpu_ctx, c["delta"], c["det_type"]), flat_of(c["expected"]), f"{c['name']} {path}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", PATHS)
+def test_oracle_parity_in_every_regime(gpu_ctx, oracle, monkeypatch, path):
+    monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+    for name, flat, delta in parity_inputs():
+        exp = to_oracle(oracle, flat).determinize_fsa(delta).to_flat()
+        exp["props"] = determinize_props(flat["props"], True)
+        same(_det(flat, gpu_ctx, delta), exp, f"{name} {path}")
+
+
+@pytest.mark.gpu
+def test_level_full_of_approx_equal_collisions(gpu_ctx, oracle, monkeypatch):
+    flat = collision_level()
+    exp = to_oracle(oracle, flat).determinize_fsa().to_flat()
+    exp["props"] = determinize_props(ACCEPTOR, True)
+    assert exp["n_states"] > 4  # the non-transitive chains split {A, B} into several states
+    for path in PATHS:
+        monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+        same(_det(flat, gpu_ctx), exp, f"collisions {path}")
+
+
+@pytest.mark.gpu
+def test_twin_copy_graph_at_scale(gpu_ctx, oracle, monkeypatch):
+    N, exp = twin_copy(3000)
+    ref = to_oracle(oracle, N).determinize_fsa().to_flat()
+    same(ref, exp, "oracle vs closed form n=3000", props=False)
+    for path in ("wide", "auto"):
+        monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+        same(_det(N, gpu_ctx), exp, f"twin copy n=3000 {path}")
+    monkeypatch.setenv("WFST_DETERMINIZE_PATH", "auto")
+    N, exp = twin_copy(250_000)
+    same(_det(N, gpu_ctx), exp, "twin copy n=250000")
+
+
+@pytest.mark.gpu
+def test_deep_and_thin_diamond_chain(gpu_ctx, oracle, monkeypatch):
+    flat = diamond_chain(20_000)
+    exp = to_oracle(oracle, flat).determinize_fsa().to_flat()
+    exp["props"] = determinize_props(ACCEPTOR, True)
+    assert exp["n_states"] == 20_001
+    monkeypatch.setenv("WFST_DETERMINIZE_PATH", "auto")
+    same(_det(flat, gpu_ctx), exp, "diamond chain auto")
+    small = diamond_chain(300)
+    exp = to_oracle(oracle, small).determinize_fsa().to_flat()
+    exp["props"] = determinize_props(ACCEPTOR, True)
+    for path in ("narrow", "wide"):
+        monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+        same(_det(small, gpu_ctx), exp, f"diamond chain {path}")
+
+
+@pytest.mark.gpu
+def test_invariants_on_small_acyclic_inputs(gpu_ctx):
+    rng = np.random.default_rng(99)
+    for k in range(12):
+        flat = random_acceptor(rng, int(rng.integers(3, 14)), 3, 2, acyclic=True, p_eps_i=0.2)
+        got = _det(flat, gpu_ctx)
+        best_in, best_out = {}, {}
+        for w, il, _ in enumerate_paths(flat):
+            best_in[il] = min(best_in.get(il, math.inf), w)
+        for w, il, _ in enumerate_paths(got):
+            assert il not in best_out, f"case {k}: string {il} accepted twice"
+            best_out[il] = w
+        assert best_in.keys() == best_out.keys(), f"case {k}"
+        for il, w in best_in.items():
+            assert abs(best_out[il] - w) <= 1e-3 * max(1.0, abs(w)), f"case {k}: {il} {best_out[il]} != {w}"
+        off, arcs = got["offsets"], got["arcs"]
+        for s in range(got["n_states"]):
+            labels = arcs["ilabel"][off[s]:off[s + 1]]
+            assert len(set(labels.tolist())) == len(labels) and np.all(np.diff(labels.astype(np.int64)) > 0)
+
+
+@pytest.mark.gpu
+def test_errors_and_isolation(gpu_ctx, monkeypatch):
+    import rustfst_amd
+    rng = np.random.default_rng(5)
+    t = random_fst_flat(rng, 10, 3, 4)  # a transducer (olabels differ, word without ACCEPTOR)
+    with pytest.raises(rustfst_amd.WfstError, match="transducers are not supported"):
+        to_device(t, gpu_ctx).determinize()
+    a = random_acceptor(rng, 10, 3, 4)
+    a["props"] &= ~ACCEPTOR  # an acceptor whose word does not say so: the reference takes the transducer branch
+    with pytest.raises(rustfst_amd.WfstError, match="transducers are not supported"):
+        to_device(a, gpu_ctx).determinize()
+    # no twins property: 0 -1/1-> 0, 0 -1/2-> 1, 1 -1/0-> 1 grows one subset per level
+    arcs = np.array([(1, 1, 1.0, 0), (1, 1, 2.0, 1), (1, 1, 0.0, 1)], dtype=TR_DTYPE)
+    bad = dict(n_states=2, start=0, offsets=np.array([0, 2, 3], np.uint32), arcs=arcs,
+               finals=np.array([np.inf, 0.0], np.float32), props=ACCEPTOR)
+    monkeypatch.setenv("WFST_DETERMINIZE_MAX_STATES", "1000")
+    for path in PATHS:
+        monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+        with pytest.raises(rustfst_amd.WfstError, match="more than"):
+            to_device(bad, gpu_ctx).determinize()
+    monkeypatch.delenv("WFST_DETERMINIZE_MAX_STATES")
+    monkeypatch.setenv("WFST_DETERMINIZE_PATH", "auto")
+    flat = random_acceptor(rng, 30, 3, 3, acyclic=True)
+    dev = to_device(flat, gpu_ctx)
+    before = dev.to_flat()
+    got = dev.determinize().to_flat()  # the same context still works after the KO
+    same(got, determinize_ref(flat), "after the KO")
+    same(dev.to_flat(), before, "source handle")
+    # determinize -> shortest_path has the weight of shortest_path on the input
+    w_in = enumerate_paths(dev.shortest_path().to_flat())
+    w_out = enumerate_paths(dev.determinize().shortest_path().to_flat())
+    assert len(w_in) == len(w_out) == 1 and abs(w_in[0][0] - w_out[0][0]) <= 1e-3
+    # VectorFst: a new FST, the input left as it is
+    v = rustfst_amd.VectorFst.from_flat(flat) if hasattr(rustfst_amd.VectorFst, "from_flat") else dev.to_vector_fst()
+    d = rustfst_amd.determinize(v)
+    assert d is not v and d.num_states() == got["n_states"]
