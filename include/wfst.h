@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -212,6 +212,35 @@ typedef struct {
   uint32_t det_type;
 } wfst_determinize_config;
 wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_determinize_config* cfg, wfst_fst** out);
+
+/* ---- minimize / minimize_with_config (rustfst/src/algorithms/minimize.rs:77-176) of an input-deterministic ACYCLIC
+ *      ACCEPTOR: the AcyclicMinimizer branch (:181-211, 306-387), whose result is a pure function of the input.
+ *      ACCEPTOR, I_DETERMINISTIC and WEIGHTED / UNWEIGHTED come from the stored property word where it knows them and from
+ *      the content otherwise (compute_and_update_properties, :101-106; "unweighted" = every weight within KDELTA of one
+ *      or zero).  Weighted: push_weights(ToInitial), QuantizeMapper(delta), encode(weights and labels), acceptor_minimize,
+ *      decode: the result carries the pushed AND quantized weights and its arcs come in the first-occurrence order of
+ *      their (label, weight) tuples over the untrimmed input, not in label order.  Unweighted: acceptor_minimize on the
+ *      original labels (arcs in label order).  Of every class of equivalent states one member survives: at each height
+ *      (longest path to a state without arcs) the class holding the height's highest state id keeps its highest id,
+ *      every other class its lowest; survivors keep their relative order.
+ *      Tuple identity: the reference's encode table hashes the weight's bits but compares with KDELTA, so two tuples with
+ *      equal labels and weights within 1/1024 merge there only when they meet in one probe group of a randomly seeded
+ *      table.  Here identity is EXACT: equal labels and equal quantized value (-0.0 == +0.0).
+ *      KO (callers keep rustfst's own call): a non-deterministic input, "Refusing to minimize a non-deterministic FST with
+ *      allow_nondet = false", or with allow_nondet != 0 "non-deterministic inputs are not supported"; "transducers are
+ *      not supported" (the gallic path); "cyclic inputs are not supported" (Hopcroft with a LIFO queue: the survivors
+ *      depend on the order of its splits) — for a cycle anywhere, also one that connect would remove; an unweighted input
+ *      whose merged states carry arc weights more than KDELTA apart (the reference keeps both arcs).
+ *      No start state, or nothing left after connect: the empty FST.  A WEIGHTED input without a start state is pushed
+ *      all the same (reweight.rs skips only the start-state step) while every tr_map returns at once, so the reference's
+ *      acceptor_minimize sees the pushed weights: the empty FST when none of them is left, else the reference's own error
+ *      "FST is not an unweighted acceptor" (rustfst fails on that input as well).  cfg == NULL: MinimizeConfig::default() = {KSHORTESTDELTA = 1e-6,
+ *      false}.  delta must be finite and > 0.  A NEW handle; fst is left as it is (the reference works in place). ---- */
+typedef struct {
+  float delta;
+  uint32_t allow_nondet;
+} wfst_minimize_config;
+wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out);
 
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no

@@ -17,6 +17,7 @@
 //   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
 //   push_weights(&mut fst, ..) / push_weights_with_config(..)    push_weights(..) / push_weights_with_config(..)  push.rs:76-118
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
+//   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -254,6 +255,21 @@ inline VectorFst determinize_with_config(const VectorFst& fst, const Determinize
   return detail::download(c);
 }
 inline VectorFst determinize(const VectorFst& fst) { return determinize_with_config(fst, DeterminizeConfig{}); }
+
+// minimize[_with_config] (minimize.rs:77-176): deterministic acyclic acceptors only (anything else throws); in place, like
+// the reference
+struct MinimizeConfig {  // minimize.rs:41-75
+  float delta = 1e-6f;  // KSHORTESTDELTA
+  bool allow_nondet = false;
+};
+inline void minimize_with_config(VectorFst& fst, const MinimizeConfig& config) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  const wfst_minimize_config cfg{config.delta, config.allow_nondet ? 1u : 0u};
+  check(wfst_minimize(Context::current().get(), a.h, &cfg, &c.h));
+  fst = detail::download(c);
+}
+inline void minimize(VectorFst& fst) { minimize_with_config(fst, MinimizeConfig{}); }
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

@@ -41,6 +41,10 @@ from .fst import (  # noqa: F401
     DeterminizeType,
     determinize,
     determinize_with_config,
+    KSHORTESTDELTA,
+    MinimizeConfig,
+    minimize,
+    minimize_with_config,
 )
 
 __all__ = [
@@ -48,5 +52,6 @@ __all__ = [
     "compose", "compose_shortest_path_batch", "compose_shortest_path_batch_begin", "compose_shortest_path_batch_packed", "shortest_path_batch", "last_nbest_path", "HandleArray", "LookAhead", "ProjectType", "project", "compose_with_config", "default_context", "set_default_context",
     "shortestpath", "shortestpath_with_config", "WfstError",
     "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance",
-    "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config", "TR_DTYPE", "LIB_PATH",
+    "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config",
+    "KSHORTESTDELTA", "MinimizeConfig", "minimize", "minimize_with_config", "TR_DTYPE", "LIB_PATH",
 ]

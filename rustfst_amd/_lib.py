@@ -35,6 +35,10 @@ class DeterminizeConfig(C.Structure):
     _fields_ = [("delta", C.c_float), ("det_type", C.c_uint32)]
 
 
+class MinimizeConfig(C.Structure):
+    _fields_ = [("delta", C.c_float), ("allow_nondet", C.c_uint32)]
+
+
 TIES_UNKNOWN = (1 << 64) - 1  # WFST_TIES_UNKNOWN
 
 
@@ -94,6 +98,7 @@ SYMBOLS = [
     ("wfst_push_weights", C.c_int, [_vp, _vp, _u32, _P(PushWeightsConfig), _P(_vp)]),
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
     ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
+    ("wfst_minimize", C.c_int, [_vp, _vp, _P(MinimizeConfig), _P(_vp)]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

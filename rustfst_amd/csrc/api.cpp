@@ -475,6 +475,18 @@ wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_dete
   });
 }
 
+// minimize_with_config (minimize.rs:92-176); MinimizeConfig::default() = {KSHORTESTDELTA, false} when cfg == NULL
+wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    const wfst_minimize_config c = cfg ? *cfg : wfst_minimize_config{1e-6f, 0u};
+    if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("minimize: delta must be finite and > 0");
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = minimize_fst(ctx, fst, c.delta, c.allow_nondet != 0);
+  });
+}
+
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

@@ -401,6 +401,8 @@ wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials
 wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_type, bool remove_total_weight);
 // determinize.hip: determinize_with_config of an acceptor (a NEW handle); det_type in the ffi numbering
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+// minimize.hip: minimize_with_config of a deterministic acyclic acceptor (a NEW handle)
+wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow_nondet);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,
                        uint64_t out_props, uint64_t est_s);
 }  // namespace wfst

@@ -279,6 +279,13 @@ inline uint64_t determinize(uint64_t in, bool distinct_psubsequential_labels) {
   return out;
 }
 
+// ---- minimize (algorithms/minimize.rs, tr_unique.rs:38-51): arcsort_properties() (properties.rs:351-381) = everything
+// but the four label-order bits; delete_arcs_properties() (:300-316)
+constexpr uint64_t ARCSORT_MASK = ALL & ~(I_LABEL_SORTED | NOT_I_LABEL_SORTED | O_LABEL_SORTED | NOT_O_LABEL_SORTED);
+constexpr uint64_t DELETE_ARCS_MASK = ACCEPTOR | I_DETERMINISTIC | O_DETERMINISTIC | NO_EPSILONS | NO_I_EPSILONS |
+                                      NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | UNWEIGHTED | ACYCLIC |
+                                      INITIAL_ACYCLIC | TOP_SORTED | NOT_ACCESSIBLE | NOT_COACCESSIBLE | UNWEIGHTED_CYCLES;
+
 inline uint64_t compose_result(uint64_t p1, uint64_t p2, bool connected, bool has_start) {
   // start None: LazyFst::compute returns F2::new() untouched (lazy_fst.rs:229-232)
   uint64_t p = has_start ? compose(p1, p2) : NULL_PROPS;

@@ -368,6 +368,15 @@ class DeviceFst:
         check(_lib.lib().wfst_determinize(self.ctx._h, self._h, cfg, C.byref(out)), "Error during determinization")
         return DeviceFst(out, self.ctx)
 
+    def minimize(self, config: Optional["MinimizeConfig"] = None) -> "DeviceFst":
+        """algorithms::minimize_with_config (minimize.rs:92-176) of an input-deterministic acyclic acceptor
+        (wfst_minimize): a NEW FST, this one is left as it is.  Transducers, non-deterministic and cyclic inputs raise
+        WfstError: those paths stay on rustfst."""
+        out = C.c_void_p()
+        cfg = config._c() if config is not None else None
+        check(_lib.lib().wfst_minimize(self.ctx._h, self._h, cfg, C.byref(out)), "Error during minimization")
+        return DeviceFst(out, self.ctx)
+
 
 class HandleArray:
     """A batch of DeviceFst handles marshalled once for the C-ABI (`const wfst_fst* const*`): callers that submit the
@@ -691,6 +700,20 @@ class DeterminizeConfig:
         return C.pointer(_lib.DeterminizeConfig(self.delta, self.det_type.value))
 
 
+KSHORTESTDELTA = 1e-6  # rustfst/src/lib.rs
+
+
+class MinimizeConfig:
+    """rustfst-python algorithms/minimize.py: MinimizeConfig(delta=KSHORTESTDELTA, allow_nondet=False)."""
+
+    def __init__(self, delta: Optional[float] = None, allow_nondet: bool = False):
+        self.delta = KSHORTESTDELTA if delta is None else float(delta)
+        self.allow_nondet = bool(allow_nondet)
+
+    def _c(self):
+        return C.pointer(_lib.MinimizeConfig(self.delta, 1 if self.allow_nondet else 0))
+
+
 # ------------------------------------------------------------------ VectorFst mirror
 class VectorFst:
     """Mutable FST stored in vectors (rustfst-python/rustfst/fst/vector_fst.py:29-790, subset on the path)."""
@@ -871,6 +894,13 @@ class VectorFst:
         """rustfst-python vector_fst.py `determinize`: a NEW VectorFst (this one is left as it is)."""
         return self.to_device().determinize(config).to_vector_fst()
 
+    def minimize(self, config: Optional[MinimizeConfig] = None) -> "VectorFst":
+        """rustfst-python vector_fst.py `minimize`: minimizes THIS FST in place on the device copy; returns this FST."""
+        res = self.to_device().minimize(config).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
     def project(self, proj_type: Union["ProjectType", None] = None) -> "VectorFst":
         """rustfst-python vector_fst.py:525-538 `project` (algorithms/project.py:27-50): projects THIS FST in place and
         returns it (the reference returns self).  The device copy is projected and becomes this object's host data; the
@@ -951,3 +981,13 @@ def determinize(fst: VectorFst) -> VectorFst:
 def determinize_with_config(fst: VectorFst, config: DeterminizeConfig) -> VectorFst:
     """algorithms::determinize_with_config (determinize_static.rs:176-190): a new FST (acceptors only)."""
     return fst.determinize(config)
+
+
+def minimize(fst: VectorFst) -> VectorFst:
+    """algorithms::minimize (minimize.rs:77-87): in place, returns fst (deterministic acyclic acceptors only)."""
+    return fst.minimize()
+
+
+def minimize_with_config(fst: VectorFst, config: MinimizeConfig) -> VectorFst:
+    """algorithms::minimize_with_config (minimize.rs:92-176): in place, returns fst."""
+    return fst.minimize(config)
