@@ -242,6 +242,47 @@ typedef struct {
 } wfst_minimize_config;
 wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out);
 
+/* ---- tr_sum (rustfst/src/algorithms/tr_sum.rs:7-22, sum_trs_unchecked: fst_impls/vector_fst/mutable_fst.rs:380-405) and
+ *      tr_unique (tr_unique.rs:8-51, unique_trs_unchecked: mutable_fst.rs:358-377).  Per state a STABLE sort by tr_compare:
+ *      (ilabel, olabel, nextstate), unsigned, the weight not in the key.  tr_sum: of a run of equal keys the first arc
+ *      survives, its weight folded with plus_assign over the run in sorted order (`if rhs < self`: a tie keeps the earlier
+ *      arc's bits, -0.0 / +0.0 included, and NaN never replaces).  tr_unique: Vec::dedup on Tr's ==, i.e. an arc goes when
+ *      its key equals that of the last KEPT arc and the two weights are within KDELTA (TropicalWeight's PartialEq,
+ *      semiring.rs:161-168): weights 0, 0.0009, 0.0018 under one key keep the first and the third.
+ *      Property word: props & arcsort_properties & delete_arcs_properties, for tr_sum also & weight_invariant_properties;
+ *      | null_properties when the FST has no states.  No KO of their own beyond NULL pointers.
+ *      The reference works in place; here a NEW handle is returned and fst is left as it is. ---- */
+wfst_status wfst_tr_sum(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+
+/* ---- optimize: fst_optimize (rustfst-ffi) = rustfst::algorithms::optimize (rustfst/src/algorithms/optimize.rs:11-128) for
+ *      the tropical semiring (IDEMPOTENT), one call over device-resident stages.  Every branch is taken on the STORED
+ *      property word:
+ *        1. ACCEPTOR in the word: acceptor path, else transducer path
+ *        2. rm_epsilon unless the word holds NO_EPSILONS (wfst_rm_epsilon)
+ *        3. tr_sum (wfst_tr_sum); its mask leaves neither UNWEIGHTED nor UNWEIGHTED_CYCLES
+ *        4. on the word after 3:
+ *           I_DETERMINISTIC                        minimize (MinimizeConfig::default()); every KO of wfst_minimize passes
+ *                                                  through with its message unchanged (transducers, cyclic inputs)
+ *           no I_DETERMINISTIC, ACYCLIC, acceptor  determinize (DeterminizeConfig::default()), minimize
+ *           no I_DETERMINISTIC, ACYCLIC, transd.   encode(EncodeLabels), determinize, minimize, decode
+ *                                                  (encode/encode_static.rs, decode_static.rs, table.rs)
+ *           no I_DETERMINISTIC, no ACYCLIC         KO "optimize: inputs whose property word does not hold ACYCLIC are not
+ *                                                  supported" (the reference encodes the weights and ends in the minimizer
+ *                                                  for cyclic machines, which wfst_minimize does not support)
+ *      encode: both labels of an arc become 1 + the index of the first occurrence of its (ilabel, olabel) pair in tr_map's
+ *      scan order (state by state, arcs in stored order); weights and final weights stay, no superfinal state; the word is
+ *      masked by i_label_invariant & o_label_invariant.  decode: the pair back through the table, the same mask, then
+ *      rm_final_epsilon, which on a machine without eps:eps arcs is its closing connect (a transducer whose word holds
+ *      NO_EPSILONS while its arcs do not is KO "eps:eps arcs under a property word that holds NO_EPSILONS are not supported").
+ *      Differs from the reference in ONE respect: the encoded machine's word has lost ACCEPTOR, so the reference determinizes
+ *      it by the gallic construction; here the acceptor construction runs, with the word of the gallic call
+ *      (determinize_properties on the word without ACCEPTOR).  The two results are identical on a label-encoded machine
+ *      (DESIGN.md 3.10).  So upload lattices with ACYCLIC in the word: step 4 branches on it.
+ *      No start state: rm_epsilon returns its input, tr_map (encode, decode) returns at once, determinize yields the empty
+ *      FST.  An input that trims to nothing ends as the empty FST.  A NEW handle; fst is left as it is. ---- */
+wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no
  *      thresholds): every epsilon:epsilon arc removed, the weighted relation kept, the result connected.  The reference

@@ -18,6 +18,8 @@
 //   push_weights(&mut fst, ..) / push_weights_with_config(..)    push_weights(..) / push_weights_with_config(..)  push.rs:76-118
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
+//   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
+//   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -270,6 +272,27 @@ inline void minimize_with_config(VectorFst& fst, const MinimizeConfig& config) {
   fst = detail::download(c);
 }
 inline void minimize(VectorFst& fst) { minimize_with_config(fst, MinimizeConfig{}); }
+
+// tr_sum (tr_sum.rs:7-22), tr_unique (tr_unique.rs:38-51) and optimize (optimize.rs:11-128; acyclic inputs, anything else
+// throws): in place, like the reference
+inline void tr_sum(VectorFst& fst) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_tr_sum(Context::current().get(), a.h, &c.h));
+  fst = detail::download(c);
+}
+inline void tr_unique(VectorFst& fst) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_tr_unique(Context::current().get(), a.h, &c.h));
+  fst = detail::download(c);
+}
+inline void optimize(VectorFst& fst) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_optimize(Context::current().get(), a.h, &c.h));
+  fst = detail::download(c);
+}
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

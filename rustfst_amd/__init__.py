@@ -45,6 +45,9 @@ from .fst import (  # noqa: F401
     MinimizeConfig,
     minimize,
     minimize_with_config,
+    optimize,
+    tr_sum,
+    tr_unique,
 )
 
 __all__ = [
@@ -53,5 +56,5 @@ __all__ = [
     "shortestpath", "shortestpath_with_config", "WfstError",
     "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance",
     "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config",
-    "KSHORTESTDELTA", "MinimizeConfig", "minimize", "minimize_with_config", "TR_DTYPE", "LIB_PATH",
+    "KSHORTESTDELTA", "MinimizeConfig", "minimize", "minimize_with_config", "optimize", "tr_sum", "tr_unique", "TR_DTYPE", "LIB_PATH",
 ]

@@ -99,6 +99,9 @@ SYMBOLS = [
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
     ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
     ("wfst_minimize", C.c_int, [_vp, _vp, _P(MinimizeConfig), _P(_vp)]),
+    ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_optimize", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

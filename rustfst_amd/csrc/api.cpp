@@ -487,6 +487,35 @@ wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimiz
   });
 }
 
+// tr_sum (tr_sum.rs:7-22) / tr_unique (tr_unique.rs:38-51)
+wfst_status wfst_tr_sum(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = tr_sum_fst(ctx, fst, false);
+  });
+}
+
+wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = tr_sum_fst(ctx, fst, true);
+  });
+}
+
+// optimize (optimize.rs:11-128), tropical semiring
+wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = optimize_fst(ctx, fst);
+  });
+}
+
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

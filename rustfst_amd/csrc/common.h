@@ -401,6 +401,12 @@ wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials
 wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_type, bool remove_total_weight);
 // determinize.hip: determinize_with_config of an acceptor (a NEW handle); det_type in the ffi numbering
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+// ... of a label-encoded machine (optimize.hip): no "the word must say ACCEPTOR" check, the gallic call's word
+wfst_fst* determinize_encoded_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+// tr_sum.hip: tr_sum / tr_unique (a NEW handle)
+wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique);
+// optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)
+wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
 // minimize.hip: minimize_with_config of a deterministic acyclic acceptor (a NEW handle)
 wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow_nondet);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,

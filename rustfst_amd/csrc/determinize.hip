@@ -656,11 +656,24 @@ Path path_knob() {
 }  // namespace
 
 // determinize_with_config for an acceptor (determinize_static.rs:176-190, the DeterminizeFsa branch): a NEW handle
+static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
   // the reference branches on the STORED word (determinize_static.rs:181-185): anything else takes the gallic path
   if (!(f->props & props::ACCEPTOR))
     throw Error("determinize: transducers are not supported (the property word does not contain ACCEPTOR); "
                 "use rustfst's determinize");
+  return determinize_acceptor(ctx, f, delta, det_type);
+}
+
+// optimize.hip: a machine whose every arc carries ilabel == olabel >= 1 (encode(EncodeLabels)) and whose word has lost
+// ACCEPTOR.  The reference's gallic branch yields what the acceptor construction yields on such a machine;
+// the word is the gallic call's: determinize_properties on the word as it is, without ACCEPTOR.
+wfst_fst* determinize_encoded_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
+  return determinize_acceptor(ctx, f, delta, det_type);
+}
+
+static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
   const uint64_t out_props = props::determinize(f->props, det_type != 1);
   if (f->start < 0 || f->n_states == 0) {  // compute_start -> None: the empty FST (lazy_fst.rs:229-232)
     HostCsr h;

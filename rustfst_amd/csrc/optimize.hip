@@ -1,0 +1,213 @@
+// optimize.hip — algorithms::optimize (rustfst/src/algorithms/optimize.rs:11-128) for the tropical semiring (IDEMPOTENT),
+// driving the device stages on handles: rm_epsilon, tr_sum, determinize, minimize, and for transducers the label
+// encode / decode of encode/encode_static.rs, decode_static.rs, table.rs (EncodeLabels).  Every branch is taken on the STORED
+// property word, as the reference does.  Branch table (word after tr_sum; UNWEIGHTED and UNWEIGHTED_CYCLES never survive
+// tr_sum's weight_invariant mask, so `intersects(ACYCLIC | UNWEIGHTED | UNWEIGHTED_CYCLES)` is `contains(ACYCLIC)`):
+//   I_DETERMINISTIC                      minimize (its KO answers pass through unchanged)
+//   no I_DETERMINISTIC, ACYCLIC, acc.    determinize, minimize
+//   no I_DETERMINISTIC, ACYCLIC, trans.  encode(EncodeLabels), determinize, minimize, decode
+//   no I_DETERMINISTIC, no ACYCLIC       KO (the reference encodes the weights and ends in the cyclic minimizer)
+// encode   label = 1 + index of the first occurrence of the arc's (ilabel, olabel) pair in tr_map's scan order, which is
+//          the CSR order: a device hash set of the pairs, atomicMin of the arc index per pair (the scheme of
+//          minimize.hip's tuple_kernel), first occurrences flagged and scanned into DENSE ids.
+// decode   a gather of the pair through the table, then rm_final_epsilon: the machine holds no eps:eps arc (labels >= 1
+//          decode to pairs of an epsilon-free FST), so only its closing connect acts.
+// The encoded machine is determinized by the ACCEPTOR construction although its word lacks ACCEPTOR and the reference
+// takes the gallic one: DESIGN.md §3.10 shows the two results are identical on a label-encoded machine.
+#include <algorithm>
+#include <memory>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "common.h"
+#include "fst_props.h"
+
+namespace wfst {
+
+namespace {
+
+constexpr uint32_t TPB = 256;
+constexpr uint64_t EMPTY_KEY = ~0ull;
+constexpr float KSHORTESTDELTA = 1e-6f;
+
+// i_label_invariant_properties() & o_label_invariant_properties() (properties.rs:383-432)
+constexpr uint64_t LABEL_INVARIANT = props::WEIGHTED | props::UNWEIGHTED | props::CYCLIC | props::ACYCLIC | props::INITIAL_CYCLIC |
+                                     props::INITIAL_ACYCLIC | props::TOP_SORTED | props::NOT_TOP_SORTED | props::ACCESSIBLE |
+                                     props::NOT_ACCESSIBLE | props::COACCESSIBLE | props::NOT_COACCESSIBLE | props::STRING |
+                                     props::NOT_STRING | props::WEIGHTED_CYCLES | props::UNWEIGHTED_CYCLES;
+
+__device__ inline uint64_t mix64(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33;
+  x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+
+// the pair of arc p into an open-addressing set (EMPTY_KEY = free); minpos[slot] = the first arc that holds the pair
+__global__ void __launch_bounds__(TPB) enc_insert_kernel(const wfst_tr* __restrict__ arcs, uint32_t n_arcs,
+                                                         unsigned long long* __restrict__ keys, uint32_t mask,
+                                                         uint32_t* __restrict__ minpos, uint32_t* __restrict__ slot_of,
+                                                         uint32_t* __restrict__ err) {
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_arcs; p += gridDim.x * blockDim.x) {
+    const uint64_t key = ((uint64_t)arcs[p].ilabel << 32) | arcs[p].olabel;
+    if (key == EMPTY_KEY) {  // the pair (2^32 - 1, 2^32 - 1) is the free mark
+      atomicOr(err, 1u);
+      slot_of[p] = 0;
+      continue;
+    }
+    uint32_t i = (uint32_t)mix64(key) & mask;
+    for (;;) {
+      unsigned long long cur = __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == EMPTY_KEY) cur = atomicCAS(&keys[i], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+      if (cur == EMPTY_KEY || cur == key) break;
+      i = (i + 1) & mask;
+    }
+    atomicMin(&minpos[i], p);
+    slot_of[p] = i;
+  }
+}
+// first[p] = arc p is the first occurrence of its pair (first[n_arcs] = 0 closes the scan)
+__global__ void enc_first_kernel(const uint32_t* __restrict__ minpos, const uint32_t* __restrict__ slot_of, uint32_t n_arcs,
+                                 uint32_t* __restrict__ first) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p <= n_arcs) first[p] = (p < n_arcs && minpos[slot_of[p]] == p) ? 1u : 0u;
+}
+// both labels become 1 + the rank of the pair's first occurrence; the first occurrence files the pair in the table
+__global__ void enc_label_kernel(const wfst_tr* __restrict__ arcs, uint32_t n_arcs, const uint32_t* __restrict__ minpos,
+                                 const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ rank,
+                                 wfst_tr* __restrict__ enc, uint2* __restrict__ table) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_arcs) return;
+  const wfst_tr a = arcs[p];
+  const uint32_t fp = minpos[slot_of[p]];
+  const uint32_t id = rank[fp];
+  if (fp == p) table[id] = make_uint2(a.ilabel, a.olabel);
+  enc[p] = wfst_tr{id + 1u, id + 1u, a.weight, a.nextstate};
+}
+__global__ void dec_label_kernel(const wfst_tr* __restrict__ arcs, uint32_t n_arcs, const uint2* __restrict__ table,
+                                 uint32_t n_pairs, wfst_tr* __restrict__ out, uint32_t* __restrict__ err) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_arcs) return;
+  const wfst_tr a = arcs[p];
+  if (a.ilabel == 0u || a.ilabel > n_pairs) {  // "Can't decode ilabel" (decode_static.rs:31-37)
+    atomicOr(err, 1u);
+    out[p] = a;
+    return;
+  }
+  const uint2 t = table[a.ilabel - 1u];
+  if (t.x == 0u && t.y == 0u) atomicOr(err, 2u);  // an eps:eps arc survived: the word said NO_EPSILONS and the content did not
+  out[p] = wfst_tr{t.x, t.y, a.weight, a.nextstate};
+}
+
+struct HandleDeleter {
+  void operator()(wfst_fst* p) const {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    delete p;
+  }
+};
+using Handle = std::unique_ptr<wfst_fst, HandleDeleter>;
+
+uint32_t read_flag(wfst_ctx* ctx, const uint32_t* d) {
+  uint32_t v = 0;
+  HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return v;
+}
+
+// encode(EncodeLabels), determinize, minimize, decode (optimize.rs:36-50) of the transducer x
+wfst_fst* encode_deter_mini_decode(wfst_ctx* ctx, const wfst_fst* x) {
+  using namespace props;
+  hipStream_t st = ctx->stream;
+  DevicePool& pool = *ctx->pool;
+  const uint32_t n = x->n_states;
+  const uint64_t E = x->n_arcs;
+  if (E >= (1ull << 31)) throw Error("optimize: input too large");
+  const bool mapped = x->start >= 0;  // tr_map returns at once without a start state (tr_map.rs:86-88): no labels, no mask
+  DBuf<uint2> table(pool, E);
+  uint32_t n_pairs = 0;
+  Handle enc;
+  if (mapped && E) {
+    uint64_t size = 64;
+    while (size < 2 * E) size <<= 1;
+    DBuf<unsigned long long> keys(pool, size);
+    DBuf<uint32_t> minpos(pool, size), slot_of(pool, E), first(pool, E + 1), rank(pool, E + 1), err(pool, 1);
+    DBuf<wfst_tr> arcs(pool, E);
+    HIP_CHECK(hipMemsetAsync(keys.p, 0xFF, size * sizeof(unsigned long long), st));
+    HIP_CHECK(hipMemsetAsync(minpos.p, 0xFF, size * sizeof(uint32_t), st));
+    HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((E + TPB - 1) / TPB, (uint64_t)ctx->n_cus * 32);
+    enc_insert_kernel<<<blocks, TPB, 0, st>>>(x->dev.arcs, (uint32_t)E, keys.p, (uint32_t)size - 1, minpos.p, slot_of.p, err.p);
+    HIP_CHECK(hipGetLastError());
+    if (read_flag(ctx, err.p)) throw Error("optimize: the label pair (4294967295, 4294967295) is not supported");
+    enc_first_kernel<<<(uint32_t)((E + 1 + TPB - 1) / TPB), TPB, 0, st>>>(minpos.p, slot_of.p, (uint32_t)E, first.p);
+    HIP_CHECK(hipGetLastError());
+    size_t temp_bytes = 0;
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, first.p, rank.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    DBuf<uint8_t> temp(pool, temp_bytes);
+    HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, first.p, rank.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    enc_label_kernel<<<(uint32_t)((E + TPB - 1) / TPB), TPB, 0, st>>>(x->dev.arcs, (uint32_t)E, minpos.p, slot_of.p, rank.p, arcs.p,
+                                                                     table.p);
+    HIP_CHECK(hipGetLastError());
+    n_pairs = read_flag(ctx, rank.p + E);
+    enc.reset(adopt_device(ctx, n, E, x->start, x->props & LABEL_INVARIANT, x->dev.offsets, arcs.p, x->dev.finals));
+  } else {
+    enc.reset(adopt_device(ctx, n, E, x->start, mapped ? (x->props & LABEL_INVARIANT) : x->props, x->dev.offsets, x->dev.arcs,
+                           x->dev.finals));
+  }
+  // determinize: the acceptor construction with the gallic call's word
+  Handle det(determinize_encoded_fst(ctx, enc.get(), KDELTA, /*Functional*/ 0u));
+  enc.reset();
+  Handle mini(minimize_fst(ctx, det.get(), KSHORTESTDELTA, false));
+  det.reset();
+  // decode: tr_map(DecodeMapper), then rm_final_epsilon = connect (connect.rs:61-64)
+  ensure_device(mini.get());
+  const uint64_t M = mini->n_arcs;
+  uint64_t p = mini->props;
+  if (mini->start >= 0) p &= LABEL_INVARIANT;
+  p = (delete_states(p) & ~(ACCESSIBLE | NOT_ACCESSIBLE | COACCESSIBLE | NOT_COACCESSIBLE)) | ACCESSIBLE | COACCESSIBLE;
+  DBuf<wfst_tr> dec(pool, M);
+  if (mini->start >= 0 && M) {
+    DBuf<uint32_t> err(pool, 1);
+    HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
+    dec_label_kernel<<<(uint32_t)((M + TPB - 1) / TPB), TPB, 0, st>>>(mini->dev.arcs, (uint32_t)M, table.p, n_pairs, dec.p, err.p);
+    HIP_CHECK(hipGetLastError());
+    const uint32_t bad = read_flag(ctx, err.p);
+    if (bad & 1u) throw Error("optimize: can't decode a label of the minimized machine");
+    // rm_final_epsilon would fold such an arc into a final weight; only its closing connect is implemented
+    if (bad & 2u) throw Error("optimize: eps:eps arcs under a property word that holds NO_EPSILONS are not supported");
+  } else if (M) {
+    HIP_CHECK(hipMemcpyAsync(dec.p, mini->dev.arcs, M * sizeof(wfst_tr), hipMemcpyDeviceToDevice, st));
+  }
+  return connect_and_adopt(ctx, mini->n_states, mini->start, mini->dev.offsets, dec.p, mini->dev.finals, /*all_accessible=*/false, p);
+}
+
+}  // namespace
+
+// optimize (optimize.rs:11-128): a NEW handle; every intermediate handle is destroyed on every exit
+wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f) {
+  using namespace props;
+  const bool acceptor = (f->props & ACCEPTOR) != 0;  // optimize_acceptor / optimize_transducer (:20-24)
+  Handle cur;
+  const wfst_fst* x = f;
+  if (!(x->props & NO_EPSILONS)) {
+    cur.reset(rm_epsilon_fst(ctx, x));
+    x = cur.get();
+  }
+  {
+    Handle summed(tr_sum_fst(ctx, x, false));
+    cur = std::move(summed);
+    x = cur.get();
+  }
+  if (x->props & I_DETERMINISTIC) return minimize_fst(ctx, x, KSHORTESTDELTA, false);
+  if (!(x->props & ACYCLIC))
+    throw Error("optimize: inputs whose property word does not hold ACYCLIC are not supported");
+  if (!acceptor) return encode_deter_mini_decode(ctx, x);
+  Handle det(determinize_fst(ctx, x, KDELTA, /*Functional*/ 0u));
+  cur.reset();
+  return minimize_fst(ctx, det.get(), KSHORTESTDELTA, false);
+}
+
+}  // namespace wfst

@@ -377,6 +377,29 @@ class DeviceFst:
         check(_lib.lib().wfst_minimize(self.ctx._h, self._h, cfg, C.byref(out)), "Error during minimization")
         return DeviceFst(out, self.ctx)
 
+    def tr_sum(self) -> "DeviceFst":
+        """algorithms::tr_sum (tr_sum.rs:7-22, wfst_tr_sum): a NEW FST in which arcs of one state with equal
+        (ilabel, olabel, nextstate) are merged, their weights summed (tropical: the smallest); arcs come out sorted on
+        that key."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_tr_sum(self.ctx._h, self._h, C.byref(out)), "Error during tr_sum")
+        return DeviceFst(out, self.ctx)
+
+    def tr_unique(self) -> "DeviceFst":
+        """algorithms::tr_unique (tr_unique.rs:38-51, wfst_tr_unique): a NEW FST with a single instance of arcs of one
+        state that agree in labels, nextstate and (within KDELTA) weight; arcs come out sorted on the key."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_tr_unique(self.ctx._h, self._h, C.byref(out)), "Error during tr_unique")
+        return DeviceFst(out, self.ctx)
+
+    def optimize(self) -> "DeviceFst":
+        """algorithms::optimize (optimize.rs:11-128, wfst_optimize): rm_epsilon, tr_sum, then determinize + minimize (through
+        a label encoding for transducers) of an ACYCLIC FST: a NEW FST.  Inputs whose property word does not hold ACYCLIC
+        (unless it holds I_DETERMINISTIC) raise WfstError: those stay on rustfst."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_optimize(self.ctx._h, self._h, C.byref(out)), "Error during optimize")
+        return DeviceFst(out, self.ctx)
+
 
 class HandleArray:
     """A batch of DeviceFst handles marshalled once for the C-ABI (`const wfst_fst* const*`): callers that submit the
@@ -901,6 +924,28 @@ class VectorFst:
         self._dev = None
         return self
 
+    def tr_sum(self) -> "VectorFst":
+        """algorithms::tr_sum (tr_sum.rs:7-22): in place on the device copy; returns this FST."""
+        res = self.to_device().tr_sum().to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def tr_unique(self) -> "VectorFst":
+        """rustfst-python vector_fst.py `tr_unique`: keeps a single instance of equal arcs, in place; returns this FST."""
+        res = self.to_device().tr_unique().to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def optimize(self) -> "VectorFst":
+        """rustfst-python vector_fst.py `optimize`: determinization and minimization of THIS FST in place on the device
+        copy (acyclic inputs); returns this FST."""
+        res = self.to_device().optimize().to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
     def project(self, proj_type: Union["ProjectType", None] = None) -> "VectorFst":
         """rustfst-python vector_fst.py:525-538 `project` (algorithms/project.py:27-50): projects THIS FST in place and
         returns it (the reference returns self).  The device copy is projected and becomes this object's host data; the
@@ -986,6 +1031,21 @@ def determinize_with_config(fst: VectorFst, config: DeterminizeConfig) -> Vector
 def minimize(fst: VectorFst) -> VectorFst:
     """algorithms::minimize (minimize.rs:77-87): in place, returns fst (deterministic acyclic acceptors only)."""
     return fst.minimize()
+
+
+def tr_sum(fst: VectorFst) -> VectorFst:
+    """algorithms::tr_sum (tr_sum.rs:7-22): in place, returns fst."""
+    return fst.tr_sum()
+
+
+def tr_unique(fst: VectorFst) -> VectorFst:
+    """algorithms::tr_unique (tr_unique.rs:38-51): in place, returns fst."""
+    return fst.tr_unique()
+
+
+def optimize(fst: VectorFst) -> VectorFst:
+    """algorithms::optimize (optimize.rs:11-128): in place, returns fst (acyclic inputs only)."""
+    return fst.optimize()
 
 
 def minimize_with_config(fst: VectorFst, config: MinimizeConfig) -> VectorFst:

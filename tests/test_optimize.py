@@ -1,0 +1,566 @@
+"""tr_sum, tr_unique and optimize (wfst_tr_sum, wfst_tr_unique, wfst_optimize): the C-ABI surface without a GPU, a literal
+sequential Python restatement of rustfst's tr_sum.rs, tr_unique.rs, encode/decode (EncodeLabels), rm_final_epsilon.rs and
+optimize.rs (tropical semiring) written out below and checked against the hand-derived K17 known answers, and on the device
+bit-exact parity with the restatement: states, offsets, arcs (weights by bit pattern), finals and property word.
+
+The restatement reuses determinize_ref / determinize_props (test_determinize.py), minimize_ref and the property helpers
+(test_minimize.py, test_push_weights.py) and the oracle's rm_epsilon.
+
+Shapes of the arc-list tests, and why: the kernel keeps a state in one register per lane up to 16 arcs, works in chunks of
+16 up to 256 arcs and hands larger states to a radix sort, so the degrees are 0, 1, 16, 17, 256, 257 and 300; duplicate
+runs straddle a 16-arc chunk boundary (the write pass counts survivors per chunk) and cover a whole state."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from rustfst_amd._lib import TR_DTYPE
+
+from helpers import assert_flat_identical, to_device, to_oracle
+import test_determinize as td
+import test_minimize as tm
+import test_push_weights as pw
+from test_push_weights import (ACCEPTOR, NOT_ACCEPTOR, I_DETERMINISTIC, NOT_I_DETERMINISTIC, NO_EPSILONS, EPSILONS,  # noqa: F401
+                               ACYCLIC, CYCLIC, TOP_SORTED, UNWEIGHTED, UNWEIGHTED_CYCLES, ACCESSIBLE, NOT_ACCESSIBLE,
+                               COACCESSIBLE, NOT_COACCESSIBLE, ALL, WEIGHT_INVARIANT)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "k17_optimize.json")
+F32, INF = np.float32, np.float32(np.inf)
+PATHS = ("narrow", "wide", "auto")
+MSG_ACYCLIC = "optimize: inputs whose property word does not hold ACYCLIC are not supported"
+LABEL_INVARIANT = tm.I_LABEL_INVARIANT & tm.O_LABEL_INVARIANT
+Unsupported = tm.Unsupported
+
+
+# ---------------------------------------------------------------- the restatement
+def tr_key(t):  # tr_compare (tr_unique.rs:8-34): ilabel, olabel, nextstate; the weight is not in the key
+    return (t[0], t[1], t[3])
+
+
+def tr_sum(fst):  # tr_sum.rs:7-22, sum_trs_unchecked (vector_fst/mutable_fst.rs:380-405)
+    props = fst["props"]
+    for s, row in enumerate(fst["rows"]):
+        row = sorted(row, key=tr_key)  # stable
+        out = []
+        for t in row:
+            if out and tr_key(out[-1]) == tr_key(t):
+                if F32(t[2]) < F32(out[-1][2]):  # plus_assign (tropical_weight.rs:53-58)
+                    out[-1][2] = F32(t[2])
+            else:
+                out.append(list(t))
+        fst["rows"][s] = out
+    p = props & tm.ARCSORT & tm.DELETE_ARCS & WEIGHT_INVARIANT
+    if not fst["rows"]:
+        p |= tm.NULL_PROPS
+    fst["props"] = p
+
+
+def tr_unique(fst):  # tr_unique.rs:38-51, unique_trs_unchecked (:358-377): Vec::dedup compares with the last KEPT arc
+    props = fst["props"]
+    for s, row in enumerate(fst["rows"]):
+        row = sorted(row, key=tr_key)
+        out = []
+        for t in row:
+            if out and tr_key(out[-1]) == tr_key(t) and pw.approx_eq(out[-1][2], t[2]):  # Tr's ==: the weight within KDELTA
+                continue
+            out.append(list(t))
+        fst["rows"][s] = out
+    p = props & tm.ARCSORT & tm.DELETE_ARCS
+    if not fst["rows"]:
+        p |= tm.NULL_PROPS
+    fst["props"] = p
+
+
+def encode_labels(fst):  # encode(EncodeLabels): encode_static.rs, table.rs; MapNoSuperfinal, weights untouched
+    table, pairs = {}, []
+
+    def arc(tr):
+        k = (tr[0], tr[1])
+        if k not in table:
+            pairs.append(k)
+            table[k] = len(pairs)
+        tr[0] = tr[1] = table[k]
+    tm.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
+    return pairs
+
+
+def rm_final_epsilon(fst):  # rm_final_epsilon.rs:20-78
+    rows, finals = fst["rows"], fst["finals"]
+    n = len(rows)
+    pred = [[] for _ in range(n)]
+    for s, row in enumerate(rows):
+        for tr in row:
+            pred[tr[3]].append(s)
+    co = [f is not None for f in finals]
+    stack = [s for s in range(n) if co[s]]
+    while stack:
+        s = stack.pop()
+        for q in pred[s]:
+            if not co[q]:
+                co[q] = True
+                stack.append(q)
+    fin_set = {s for s in range(n) if finals[s] is not None and not any(co[tr[3]] for tr in rows[s])}
+    p = fst["props"]
+    for s in range(n):
+        weight, dele = None, []
+        for i, tr in enumerate(rows[s]):
+            if tr[3] in fin_set and tr[0] == 0 and tr[1] == 0:
+                if weight is None:
+                    weight = finals[s] if finals[s] is not None else INF
+                v = pw.times(finals[tr[3]], tr[2])
+                weight = v if v < weight else weight
+                dele.append(i)
+        if dele:
+            if not pw.is_zero(weight):
+                p = pw.p_set_final(p, finals[s], weight)
+                finals[s] = weight
+            rows[s] = [tr for i, tr in enumerate(rows[s]) if i not in dele]
+            p &= tm.DELETE_ARCS
+    fst["props"] = p
+    tm.connect(fst)
+
+
+def decode_labels(fst, pairs):  # decode (decode_static.rs): the pair back, the same mask, rm_final_epsilon
+    def arc(tr):
+        tr[0], tr[1] = pairs[tr[0] - 1]
+    tm.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
+    rm_final_epsilon(fst)
+
+
+def norm(flat):
+    start = flat["start"]
+    return dict(flat, start=None if start is None or start < 0 else int(start), props=int(flat["props"]) & ALL)
+
+
+def determinize_encoded(flat):
+    """determinize of a label-encoded machine (ilabel == olabel >= 1, the word without ACCEPTOR): the acceptor
+    construction, the word of the gallic call (determinize_static.rs:177-192)"""
+    out = td.determinize_ref(dict(flat, props=flat["props"] | ACCEPTOR))
+    out["props"] = td.determinize_props(flat["props"], True)
+    return out
+
+
+def det_min(flat, encoded):
+    det = determinize_encoded(flat) if encoded else td.determinize_ref(flat)
+    return tm.minimize_ref(norm(det))
+
+
+def optimize_ref(flat, oracle):
+    """optimize (optimize.rs:11-128) for the tropical semiring; raises Unsupported (or determinize_ref's ValueError) with the
+    KO message"""
+    flat = norm(flat)
+    acceptor = bool(flat["props"] & ACCEPTOR)
+    cur = flat
+    if not cur["props"] & NO_EPSILONS:
+        cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
+    fst = tm.flat_to_fst(cur)
+    tr_sum(fst)
+    cur = tm.fst_to_flat(fst)
+    p = cur["props"]
+    if p & I_DETERMINISTIC:
+        return tm.minimize_ref(cur)
+    if not p & ACYCLIC:  # intersects(ACYCLIC | UNWEIGHTED | UNWEIGHTED_CYCLES): tr_sum's mask left neither of the others
+        assert not p & (UNWEIGHTED | UNWEIGHTED_CYCLES)
+        raise Unsupported(MSG_ACYCLIC)
+    if acceptor:
+        return det_min(cur, False)
+    pairs = encode_labels(fst)
+    mini = tm.flat_to_fst(det_min(tm.fst_to_flat(fst), True))
+    decode_labels(mini, pairs)
+    return tm.fst_to_flat(mini)
+
+
+def apply_op(op, flat, oracle=None):
+    if op == "optimize":
+        return optimize_ref(flat, oracle)
+    fst = tm.flat_to_fst(norm(flat))
+    (tr_sum if op == "tr_sum" else tr_unique)(fst)
+    return tm.fst_to_flat(fst)
+
+
+def content_word(flat):
+    """the word compute_fst_properties finds on the content: every trinary pair known"""
+    fst = tm.flat_to_fst(dict(flat, props=0))
+    tm.compute_and_update(fst, ALL)
+    return fst["props"]
+
+
+# ---------------------------------------------------------------- inputs
+def golden_cases():
+    with open(GOLDEN) as f:
+        return json.load(f)["cases"]
+
+
+def rows_flat(rows, finals, start=0, props=0):
+    return tm.make_flat(len(rows), start, rows, finals, props)
+
+
+def part_a_rows():
+    """degrees at every path boundary; duplicate runs across a chunk boundary and over a whole state"""
+    rng = np.random.default_rng(5)
+    n = 24
+
+    def rnd(k, dup=0.5, sigma=6):
+        row = []
+        for _ in range(k):
+            if row and rng.random() < dup:
+                il, ol, _, ns = row[int(rng.integers(0, len(row)))]
+            else:
+                il, ol, ns = int(rng.integers(0, sigma)), int(rng.integers(0, sigma)), int(rng.integers(0, n))
+            row.append((il, ol, float(rng.integers(0, 8)) / 4, ns))
+        return row
+    rows = [[], rnd(1), rnd(16), rnd(17), rnd(256), rnd(257), rnd(300), rnd(300, dup=0.0, sigma=1000)]
+    rows.append([(3, 3, float(8 - i % 8), 2) for i in range(40)])                    # a run that covers a whole state
+    rows.append([(2, 2, float(i % 5), 1) for i in range(300)])                       # ... of a big state
+    rows.append([(1, 1, 1.0, 0)] * 10 + [(5, 5, float(20 - i), 3) for i in range(12)] + [(9, 9, 0.0, 1)] * 3)  # run over 16
+    rows.append([(i + 1, i + 1, float(i), i % n) for i in range(16)])               # no duplicates
+    rows.append([(i + 1, 7, 0.5, 4) for i in range(40)])                            # no duplicates, chunked
+    rows.append([(7, 7, 0.25 * (i % 3), 5) for i in range(15)] + [(7, 7, 3.0, 5), (7, 7, 0.0, 5), (8, 8, 1.0, 5)])  # run 15..17
+    while len(rows) < n:
+        rows.append(rnd(int(rng.integers(0, 20))))
+    return rows_flat(rows, [INF] * n)
+
+
+def part_b_rows():
+    """keys that differ in one field only, labels >= 2^31, ilabel 0, signed zeros, +inf, empty states, a run in the last state"""
+    big = 0x80000000
+    rows = [
+        [(5, 2, 1.0, 1), (5, 1, 2.0, 1), (5, 2, 0.5, 1), (5, 1, 3.0, 1)],                      # differ in olabel only
+        [],
+        [(5, 5, 1.0, 3), (5, 5, 2.0, 2), (5, 5, 0.5, 3), (5, 5, 3.0, 2)],                      # differ in nextstate only
+        [(big + 1, 1, 1.0, 0), (1, big, 2.0, 0), (big, big + 7, 0.0, 0), (0xFFFFFFFE, 0, 1.0, 0), (7, 7, 1.0, 0),
+         (big + 1, 1, 0.5, 0), (1, big, 2.5, 0)],                                              # unsigned compare
+        [],
+        [],
+        [(0, 0, 1.0, 1), (0, 3, 1.0, 1), (0, 0, 0.5, 1), (3, 0, 2.0, 1), (0, 3, 4.0, 1)],      # ilabel 0
+        [(1, 1, 0.0, 0), (1, 1, -0.0, 0), (2, 2, -0.0, 0), (2, 2, 0.0, 0)],                    # ties keep the earlier bits
+        [(1, 1, INF, 0), (1, 1, INF, 0), (2, 2, INF, 0), (2, 2, 1.0, 0), (3, 3, 1.0, 0), (3, 3, INF, 0)],
+        [(4, 4, 0.0, 2), (4, 4, 0.0009, 2), (4, 4, 0.0018, 2), (4, 4, 0.0027, 2)],             # the KDELTA chain
+        [],
+        [(6, 6, 2.0, 9), (6, 6, 1.0, 9), (6, 6, 1.0, 9), (6, 6, 3.0, 9)],                      # a run in the LAST state
+    ]
+    return rows_flat(rows, [INF, 0.0] + [INF] * 9 + [1.5])
+
+
+def random_arc_lists(seed, n):
+    rng = np.random.default_rng(seed)
+    rows = []
+    for s in range(n):
+        row = []
+        for _ in range(int(rng.integers(0, 12))):
+            if row and rng.random() < 0.5:
+                il, ol, _, ns = row[int(rng.integers(0, len(row)))]
+            else:
+                il, ol, ns = int(rng.integers(0, 4)), int(rng.integers(0, 4)), int(rng.integers(0, n))
+            row.append((il, ol, float(rng.integers(0, 64)) / 1024.0 if rng.random() < 0.5 else float(rng.integers(0, 4)), ns))
+        rows.append(row)
+    return rows_flat(rows, [0.0 if rng.random() < 0.2 else INF for _ in range(n)], props=int(ACYCLIC | ACCESSIBLE))
+
+
+def optimize_input(rng, n, transducer, deterministic=False, eps=True):
+    """an acyclic FST by construction (arcs to higher ids only), integer weights (a grid far coarser than KDELTA), eps:eps
+    arcs and parallel arcs; the word is the one computed from its content"""
+    rows, finals = [], []
+    for s in range(n):
+        row = []
+        labs = rng.permutation(np.arange(1, 4))
+        for k in range(int(rng.integers(1, 4))):  # at least one arc forward: every path ends in the last state, a final one
+            if s + 1 >= n:
+                break
+            il = int(labs[k]) if deterministic else int(rng.integers(1, 4 if transducer else 10))  # nine labels or pairs
+            ol = il if not transducer else int(rng.integers(0, 3)) + 4 * il
+            t = int(rng.integers(s + 1, min(n, s + 5)))
+            row.append((il, ol, float(rng.integers(0, 3)), t))
+            if not deterministic and rng.random() < 0.3:  # a parallel arc: tr_sum has work
+                row.append((il, ol, float(rng.integers(0, 3)), t))
+        if eps and not deterministic and s + 1 < n and rng.random() < 0.2:
+            row.append((0, 0, float(rng.integers(0, 2)), int(rng.integers(s + 1, min(n, s + 4)))))
+        rows.append(row)
+        finals.append(float(rng.integers(0, 2)) if rng.random() < 0.3 or s == n - 1 else INF)
+    flat = rows_flat(rows, finals)
+    flat["props"] = content_word(flat)
+    return flat
+
+
+def regime_cases(seed=21):
+    """(name, flat, branch of step 4 it must take)"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(4):
+        n = int(rng.integers(150, 400))
+        out.append((f"acceptor-{i}", optimize_input(rng, n, False), "det-min"))
+        out.append((f"transducer-{i}", optimize_input(rng, n, True), "encode"))
+        out.append((f"deterministic-{i}", optimize_input(rng, n, False, deterministic=True), "min"))
+    out.append(("acceptor-no-eps", optimize_input(rng, 200, False, eps=False), "det-min"))
+    out.append(("transducer-no-eps", optimize_input(rng, 200, True, eps=False), "encode"))
+    return out
+
+
+def branch_of(flat, oracle):
+    cur = norm(flat)
+    if not cur["props"] & NO_EPSILONS:
+        cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
+    fst = tm.flat_to_fst(cur)
+    tr_sum(fst)
+    if fst["props"] & I_DETERMINISTIC:
+        return "min"
+    if not fst["props"] & ACYCLIC:
+        return "ko"
+    return "det-min" if flat["props"] & ACCEPTOR else "encode"
+
+
+# ================================================================ CPU
+def test_symbols_declared_and_bound(wfst_lib):
+    from rustfst_amd import _lib
+    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
+        header = f.read()
+    for name in ("wfst_tr_sum", "wfst_tr_unique", "wfst_optimize"):
+        assert re.search(r"\bwfst_status\s+" + name + r"\s*\(wfst_ctx\* ctx, const wfst_fst\* fst, wfst_fst\*\* out\)", header)
+        assert name in {n for n, _, _ in _lib.SYMBOLS}
+        assert hasattr(wfst_lib, name)
+
+
+def _ko_message(status):
+    from rustfst_amd import _lib
+    assert status == 1
+    msg = C.c_char_p()
+    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
+    text = msg.value.decode()
+    _lib.lib().wfst_string_destroy(msg)
+    return text
+
+
+def test_argument_validation_without_gpu(wfst_lib):
+    for name in ("wfst_tr_sum", "wfst_tr_unique", "wfst_optimize"):
+        fn = getattr(wfst_lib, name)
+        out = C.c_void_p(1)
+        assert "null" in _ko_message(fn(None, None, C.byref(out)))
+        assert out.value is None
+        assert "null" in _ko_message(fn(None, None, None))
+
+
+def test_python_surface():
+    import rustfst_amd
+    for name in ("optimize", "tr_sum", "tr_unique"):
+        assert name in rustfst_amd.__all__ and callable(getattr(rustfst_amd, name))
+        assert callable(getattr(rustfst_amd.DeviceFst, name)) and callable(getattr(rustfst_amd.VectorFst, name))
+
+
+def golden_error(c, oracle):
+    try:
+        apply_op(c["op"], tm.golden_flat(c), oracle)
+    except (Unsupported, ValueError) as e:
+        return e.args[0]
+    return None
+
+
+def test_k17_restatement_reproduces_the_derivations(oracle):
+    """the hand derivations of K17_DERIVATION.md, replayed by this file's restatement (checks the restatement itself)"""
+    cases = golden_cases()
+    names = {c["name"] for c in cases}
+    assert len(cases) >= 11 and "reference_python_test" in names
+    for c in cases:
+        if "error" in c:
+            msg = golden_error(c, oracle)
+            assert msg is not None and (msg in c["error"] or c["error"] in msg), (c["name"], msg)
+            continue
+        got = apply_op(c["op"], tm.golden_flat(c), oracle)
+        assert_flat_identical(got, tm.golden_flat(c, "expected"), c["name"])
+        for stage, word in c.get("words", {}).items():  # the property word after every stage of the derivation
+            assert stage_words(tm.golden_flat(c), oracle)[stage] == int(word, 16), (c["name"], stage)
+
+
+def stage_words(flat, oracle):
+    """the words the derivations record for an optimize case: after rm_epsilon, tr_sum, encode, determinize, minimize"""
+    out = {}
+    cur = norm(flat)
+    if not cur["props"] & NO_EPSILONS:
+        cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
+    out["rm_epsilon"] = cur["props"]
+    fst = tm.flat_to_fst(cur)
+    tr_sum(fst)
+    out["tr_sum"] = fst["props"]
+    encoded = not flat["props"] & ACCEPTOR
+    if encoded:
+        encode_labels(fst)
+        out["encode"] = fst["props"]
+    cur = tm.fst_to_flat(fst)
+    if not cur["props"] & I_DETERMINISTIC:
+        cur = norm(determinize_encoded(cur) if encoded else td.determinize_ref(cur))
+        out["determinize"] = cur["props"]
+    out["minimize"] = tm.minimize_ref(cur)["props"]
+    return out
+
+
+def test_reference_python_test_machine(oracle):
+    """rustfst-python/tests/algorithms/test_optimize.py: the one transducer result on record that rustfst itself produced
+    (through its gallic determinizer)"""
+    c = next(c for c in golden_cases() if c["name"] == "reference_python_test")
+    got = optimize_ref(tm.golden_flat(c), oracle)
+    assert got["n_states"] == 4 and got["start"] == 0
+    arcs = [(int(a["ilabel"]), int(a["olabel"]), float(a["weight"]), int(a["nextstate"])) for a in got["arcs"]]
+    assert arcs == [(1, 2, 4.0, 1), (1, 3, 7.0, 2), (4, 6, 1.0, 3), (7, 8, 0.0, 3)]
+    assert got["offsets"].tolist() == [0, 2, 3, 4, 4]
+    assert [None if not np.isfinite(f) else float(f) for f in got["finals"]] == [None, 0.0, None, 0.0]
+
+
+def test_transducer_branch_equals_the_acceptor_steps_on_pair_ids(oracle):
+    """a random acyclic acceptor over pair ids whose rows are sorted and whose ids appear in first-occurrence order, and the
+    transducer whose pairs decode them (a monotone map, so tr_sum leaves both in the same order and encode gives the ids
+    back): optimize(transducer) = decode(determinize + minimize of the acceptor)"""
+    rng = np.random.default_rng(9)
+
+    def pair(i):
+        return ((i - 1) // 3 + 1, (i - 1) % 3 + 5)
+    for case in range(20):
+        n, next_id, rows, finals = int(rng.integers(5, 60)), 1, [], []
+        for s in range(n):
+            row = []
+            if s + 1 < n:
+                old = sorted(rng.choice(np.arange(1, next_id), size=min(next_id - 1, int(rng.integers(0, 3))), replace=False)) \
+                    if next_id > 1 else []
+                new = list(range(next_id, next_id + int(rng.integers(0, 3))))
+                next_id += len(new)
+                for i in list(old) + new:
+                    for t in sorted(set(int(x) for x in rng.integers(s + 1, min(n, s + 4), size=int(rng.integers(1, 3))))):
+                        row.append((int(i), int(i), float(rng.integers(0, 3)), t))
+            rows.append(row)
+            finals.append(float(rng.integers(0, 2)) if rng.random() < 0.3 or s == n - 1 else INF)
+        acc = rows_flat(rows, finals)
+        acc["props"] = content_word(acc)
+        tra = rows_flat([[pair(il) + (w, t) for il, _, w, t in r] for r in rows], finals)
+        tra["props"] = content_word(tra)
+        assert not tra["props"] & ACCEPTOR and tra["props"] & ACYCLIC and tra["props"] & NO_EPSILONS
+        assert branch_of(tra, oracle) == "encode" and branch_of(acc, oracle) == "det-min"
+        got = optimize_ref(tra, oracle)
+        fst = tm.flat_to_fst(norm(acc))
+        tr_sum(fst)
+        assert tm.fst_to_flat(fst)["arcs"].tolist() == norm(acc)["arcs"].tolist()
+        mini = tm.flat_to_fst(det_min(tm.fst_to_flat(fst), False))
+        decode_labels(mini, [pair(i) for i in range(1, next_id)])
+        assert_flat_identical(got, tm.fst_to_flat(mini), f"case {case}", check_props=False)
+
+
+def test_tr_sum_is_idempotent_and_keeps_duplicate_free_rows():
+    for flat in (part_a_rows(), part_b_rows(), random_arc_lists(2, 300)):
+        once = apply_op("tr_sum", flat)
+        assert_flat_identical(apply_op("tr_sum", once), once, "tr_sum twice")
+        off = once["offsets"]
+        for s in range(once["n_states"]):
+            keys = [tr_key(t) for t in once["arcs"][off[s]:off[s + 1]].tolist()]
+            assert keys == sorted(set(keys)), s
+    rng = np.random.default_rng(4)
+    rows = [[(int(il), 1, float(rng.integers(0, 9)), int(rng.integers(0, 30))) for il in rng.permutation(40)[:int(rng.integers(0, 30))]]
+            for _ in range(30)]
+    flat = rows_flat(rows, [INF] * 30)
+    got = apply_op("tr_sum", flat)
+    assert np.array_equal(got["offsets"], flat["offsets"])
+    for s, row in enumerate(rows):  # no duplicate keys: the same arcs, sorted
+        seg = got["arcs"][got["offsets"][s]:got["offsets"][s + 1]]
+        assert [tuple(t) for t in seg.tolist()] == sorted((il, ol, float(F32(w)), ns) for il, ol, w, ns in row)
+
+
+def test_kdelta_chain_compares_with_the_last_kept_arc():
+    flat = rows_flat([[(1, 1, 0.0, 0), (1, 1, 0.0009, 0), (1, 1, 0.0018, 0)]], [0.0])
+    assert [float(w) for w in apply_op("tr_unique", flat)["arcs"]["weight"]] == [0.0, float(F32(0.0018))]
+    assert [float(w) for w in apply_op("tr_sum", flat)["arcs"]["weight"]] == [0.0]
+
+
+def test_generator_reaches_every_branch(oracle):
+    """the inputs of the device parity tests, on the CPU: none lands in a KO branch, each takes the branch it is meant for"""
+    seen = set()
+    for name, flat, want in regime_cases():
+        assert branch_of(flat, oracle) == want, name
+        exp = optimize_ref(flat, oracle)
+        assert exp["n_states"] > 0, name
+        seen.add(want)
+        if want != "min":
+            assert flat["props"] & NOT_I_DETERMINISTIC, name
+    assert seen == {"det-min", "encode", "min"}
+    with_eps = [f for _, f, _ in regime_cases() if f["props"] & EPSILONS]
+    assert len(with_eps) >= 8
+
+
+# ================================================================ GPU
+def dev_op(op, flat, ctx):
+    return getattr(to_device(flat, ctx), op)()
+
+
+def check_op(op, flat, ctx, what, oracle=None):
+    dev = to_device(flat, ctx)
+    before = dev.to_flat()
+    got = getattr(dev, op)().to_flat()
+    assert_flat_identical(got, apply_op(op, flat, oracle), f"{op} {what}")
+    assert_flat_identical(dev.to_flat(), before, f"{op} {what}: the input handle")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("op", ["tr_sum", "tr_unique"])
+def test_arc_lists_part_a(gpu_ctx, op):
+    check_op(op, part_a_rows(), gpu_ctx, "degrees 0, 1, 16, 17, 256, 257, 300")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("op", ["tr_sum", "tr_unique"])
+def test_arc_lists_part_b(gpu_ctx, op):
+    check_op(op, part_b_rows(), gpu_ctx, "edge keys and weights")
+    check_op(op, random_arc_lists(3, 3000), gpu_ctx, "3000 random states")
+    check_op(op, rows_flat([], [], start=None), gpu_ctx, "no states")
+    check_op(op, rows_flat([[], []], [INF, 0.0]), gpu_ctx, "no arcs")
+
+
+@pytest.mark.gpu
+def test_k17_on_the_device(gpu_ctx, oracle):
+    import rustfst_amd
+    for c in golden_cases():
+        flat = tm.golden_flat(c)
+        if "error" in c:
+            with pytest.raises(rustfst_amd.WfstError, match=re.escape(c["error"])):
+                dev_op(c["op"], flat, gpu_ctx)
+            continue
+        assert_flat_identical(dev_op(c["op"], flat, gpu_ctx).to_flat(), tm.golden_flat(c, "expected"), c["name"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", PATHS)
+def test_optimize_matches_the_restatement_in_every_regime(gpu_ctx, oracle, monkeypatch, path):
+    monkeypatch.setenv("WFST_DETERMINIZE_PATH", path)
+    monkeypatch.setenv("WFST_MINIMIZE_PATH", path)
+    for name, flat, _ in regime_cases():
+        check_op("optimize", flat, gpu_ctx, f"{name} [{path}]", oracle)
+
+
+@pytest.mark.gpu
+def test_ko_messages_and_the_context_afterwards(gpu_ctx, oracle):
+    import rustfst_amd
+    good = next(c for c in golden_cases() if c["name"] == "reference_python_test")
+    for c in golden_cases():
+        if "error" not in c:
+            continue
+        dev = to_device(tm.golden_flat(c), gpu_ctx)
+        before = dev.to_flat()
+        with pytest.raises(rustfst_amd.WfstError, match=re.escape(c["error"])):
+            dev.optimize()
+        assert_flat_identical(dev.to_flat(), before, c["name"] + ": the input handle")
+        got = dev_op("optimize", tm.golden_flat(good), gpu_ctx).to_flat()  # the context still works
+        assert_flat_identical(got, tm.golden_flat(good, "expected"), "after " + c["name"])
+
+
+@pytest.mark.gpu
+def test_vector_fst_surface_on_the_device(gpu_ctx):
+    import rustfst_amd
+    fst = rustfst_amd.VectorFst()
+    s = [fst.add_state() for _ in range(4)]
+    fst.set_start(s[0])
+    fst.set_final(s[3], 0.0)
+    for src, tr in ((0, (1, 2, 1.0, 1)), (0, (1, 3, 2.0, 2)), (1, (0, 0, 3.0, 3)), (1, (4, 6, 4.0, 3)), (2, (7, 8, 5.0, 3))):
+        fst.add_tr(s[src], rustfst_amd.Tr(*tr))
+    assert rustfst_amd.optimize(fst) is fst
+    assert fst.num_states() == 4
+    got = [(t.ilabel, t.olabel, float(t.weight), t.next_state) for st in range(4) for t in fst.trs(st)]
+    assert got == [(1, 2, 4.0, 1), (1, 3, 7.0, 2), (4, 6, 1.0, 3), (7, 8, 0.0, 3)]
+    assert [fst.final_weight(q) for q in range(4)] == [None, 0.0, None, 0.0]
