@@ -213,6 +213,41 @@ typedef struct {
 } wfst_determinize_config;
 wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_determinize_config* cfg, wfst_fst** out);
 
+/* ---- determinize_with_config (determinize_static.rs:176-190) of n ACCEPTORS in one call: outs[i] is a NEW handle,
+ *      bit-identical (arrays, start state, property word) to what wfst_determinize(ctx, fsts[i], cfg, ..) returns.  cfg is
+ *      shared by all items, NULL = the default as above.  The same handle may appear more than once in fsts.  n == 0: OK.
+ *      One workgroup per item, one launch for every item that is still open: an item whose arena slice (sized on the host
+ *      from its n_states and n_arcs) proves too small is run again in the next launch of the same call with a larger one.
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when NO breadth-first level of item i has more than
+ *      256 states or more than 8192 raw candidates (the sum of the out-degrees of the level's subset elements): the batch
+ *      kernel constructed it (an item without start state or states counts as such: the empty FST).  in_kernel[i] == 0:
+ *      the item went through the single-FST path of wfst_determinize.
+ *      KO — every argument and every item's stored word is checked before anything is launched — when an item's word lacks
+ *      ACCEPTOR or an item exceeds the state / element limit: the single call's message prefixed by "item <i>: ".  On
+ *      any KO every outs[i] is NULL, nothing is leaked and the context works afterwards.
+ *      WFST_DETERMINIZE_BATCH_SCRATCH=lds|global (environment) places the scratch of levels of at most 496 candidates in
+ *      LDS or in the item's slice. ---- */
+wfst_status wfst_determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_determinize_config* cfg,
+                                   wfst_fst** outs, uint8_t* in_kernel);
+
+/* ---- determinize_with_distance (determinize/determinize_static.rs:24-39): the construction above with det_type
+ *      Functional, and out_dist[s] = plus over the elements (q, w) of subset s, in stored (ascending state) order, of
+ *      w (x) in_dist[q]; a state q >= n_in_dist counts as +inf (state_table.rs:25-39,79-96).  *out_dist is allocated by the
+ *      library (release it with wfst_bytes_destroy), *n_out_dist is the result's state count.  in_dist == NULL with
+ *      n_in_dist > 0 is KO; delta as above. ---- */
+wfst_status wfst_determinize_with_distance(wfst_ctx* ctx, const wfst_fst* fst, const float* in_dist, uint64_t n_in_dist,
+                                           float delta, wfst_fst** out, float** out_dist, uint64_t* n_out_dist);
+/* ... of n acceptors in one call (as wfst_determinize_batch): in_dists[i] / n_in_dists[i] per item; *out_dist is ONE
+ *      buffer (wfst_bytes_destroy) holding the items' vectors one after the other, item i at
+ *      [out_offsets[i], out_offsets[i + 1]); out_offsets is the caller's uint64_t[n + 1]. */
+wfst_status wfst_determinize_with_distance_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n,
+                                                 const float* const* in_dists, const uint64_t* n_in_dists, float delta,
+                                                 wfst_fst** outs, float** out_dist, uint64_t* out_offsets, uint8_t* in_kernel);
+/* the last wfst_determinize_batch / wfst_determinize_with_distance_batch call of ctx: launches of the batch kernel, items it
+ *      constructed (in_kernel == 1), items that went through the single-FST path.  All 0 after a KO before any launch. */
+wfst_status wfst_ctx_get_determinize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                 uint64_t* items_single);
+
 /* ---- minimize / minimize_with_config (rustfst/src/algorithms/minimize.rs:77-176) of an input-deterministic ACYCLIC
  *      ACCEPTOR: the AcyclicMinimizer branch (:181-211, 306-387), whose result is a pure function of the input.
  *      ACCEPTOR, I_DETERMINISTIC and WEIGHTED / UNWEIGHTED come from the stored property word where it knows them and from

@@ -17,6 +17,8 @@
 //   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
 //   push_weights(&mut fst, ..) / push_weights_with_config(..)    push_weights(..) / push_weights_with_config(..)  push.rs:76-118
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
+//   determinize_with_distance(&fst, &in_dist, delta)             determinize_with_distance(fst, in_dist, delta)   determinize_static.rs:24-39
+//   (many acceptors in one call)                                 determinize_batch / determinize_with_distance_batch
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
@@ -257,6 +259,62 @@ inline VectorFst determinize_with_config(const VectorFst& fst, const Determinize
   return detail::download(c);
 }
 inline VectorFst determinize(const VectorFst& fst) { return determinize_with_config(fst, DeterminizeConfig{}); }
+// determinize_with_config of many acceptors in one call (wfst_determinize_batch): one workgroup per FST
+inline std::vector<VectorFst> determinize_batch(const std::vector<VectorFst>& fsts, const DeterminizeConfig& config = DeterminizeConfig{}) {
+  std::vector<detail::DeviceFst> in(fsts.size()), out(fsts.size());
+  std::vector<const wfst_fst*> hs(fsts.size());
+  std::vector<wfst_fst*> os(fsts.size(), nullptr);
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    detail::upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+  }
+  const wfst_determinize_config cfg{config.delta, (uint32_t)config.det_type};
+  check(wfst_determinize_batch(Context::current().get(), hs.data(), hs.size(), &cfg, os.data(), nullptr));
+  std::vector<VectorFst> res;
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    out[i].h = os[i];
+    res.push_back(detail::download(out[i]));
+  }
+  return res;
+}
+// determinize_with_distance (determinize_static.rs:24-39): (determinized FST, out_dist)
+inline std::pair<VectorFst, std::vector<float>> determinize_with_distance(const VectorFst& fst, const std::vector<float>& in_dist,
+                                                                          float delta = 1.0f / 1024.0f) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  float* d = nullptr;
+  uint64_t nd = 0;
+  check(wfst_determinize_with_distance(Context::current().get(), a.h, in_dist.data(), in_dist.size(), delta, &c.h, &d, &nd));
+  std::vector<float> dist(d, d + nd);
+  wfst_bytes_destroy(reinterpret_cast<uint8_t*>(d));
+  return {detail::download(c), std::move(dist)};
+}
+inline std::vector<std::pair<VectorFst, std::vector<float>>> determinize_with_distance_batch(
+    const std::vector<VectorFst>& fsts, const std::vector<std::vector<float>>& in_dists, float delta = 1.0f / 1024.0f) {
+  if (in_dists.size() != fsts.size()) throw Error("determinize_with_distance_batch: one in_dist per FST");
+  const size_t n = fsts.size();
+  std::vector<detail::DeviceFst> in(n), out(n);
+  std::vector<const wfst_fst*> hs(n);
+  std::vector<wfst_fst*> os(n, nullptr);
+  std::vector<const float*> ps(n);
+  std::vector<uint64_t> ns(n), off(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    detail::upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+    ps[i] = in_dists[i].data();
+    ns[i] = in_dists[i].size();
+  }
+  float* d = nullptr;
+  check(wfst_determinize_with_distance_batch(Context::current().get(), hs.data(), n, ps.data(), ns.data(), delta, os.data(), &d,
+                                             off.data(), nullptr));
+  std::vector<std::pair<VectorFst, std::vector<float>>> res;
+  for (size_t i = 0; i < n; ++i) {
+    out[i].h = os[i];
+    res.emplace_back(detail::download(out[i]), std::vector<float>(d + off[i], d + off[i + 1]));
+  }
+  wfst_bytes_destroy(reinterpret_cast<uint8_t*>(d));
+  return res;
+}
 
 // minimize[_with_config] (minimize.rs:77-176): deterministic acyclic acceptors only (anything else throws); in place, like
 // the reference

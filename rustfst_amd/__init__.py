@@ -41,6 +41,10 @@ from .fst import (  # noqa: F401
     DeterminizeType,
     determinize,
     determinize_with_config,
+    determinize_batch,
+    determinize_batch_stats,
+    determinize_with_distance,
+    determinize_with_distance_batch,
     KSHORTESTDELTA,
     MinimizeConfig,
     minimize,
@@ -55,6 +59,7 @@ __all__ = [
     "compose", "compose_shortest_path_batch", "compose_shortest_path_batch_begin", "compose_shortest_path_batch_packed", "shortest_path_batch", "last_nbest_path", "HandleArray", "LookAhead", "ProjectType", "project", "compose_with_config", "default_context", "set_default_context",
     "shortestpath", "shortestpath_with_config", "WfstError",
     "KDELTA", "PushWeightsConfig", "ReweightType", "push_weights", "push_weights_with_config", "reweight", "shortest_distance",
-    "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config",
+    "DeterminizeConfig", "DeterminizeType", "determinize", "determinize_with_config", "determinize_batch", "determinize_batch_stats",
+    "determinize_with_distance", "determinize_with_distance_batch",
     "KSHORTESTDELTA", "MinimizeConfig", "minimize", "minimize_with_config", "optimize", "tr_sum", "tr_unique", "TR_DTYPE", "LIB_PATH",
 ]

@@ -98,6 +98,11 @@ SYMBOLS = [
     ("wfst_push_weights", C.c_int, [_vp, _vp, _u32, _P(PushWeightsConfig), _P(_vp)]),
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
     ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
+    ("wfst_determinize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(DeterminizeConfig), _P(_vp), _vp]),
+    ("wfst_determinize_with_distance", C.c_int, [_vp, _vp, _vp, _u64, _f32, _P(_vp), _P(_vp), _P(_u64)]),
+    ("wfst_determinize_with_distance_batch", C.c_int,
+     [_vp, _P(_vp), _sz, _P(_vp), _P(_u64), _f32, _P(_vp), _P(_vp), _P(_u64), _vp]),
+    ("wfst_ctx_get_determinize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_minimize", C.c_int, [_vp, _vp, _P(MinimizeConfig), _P(_vp)]),
     ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),

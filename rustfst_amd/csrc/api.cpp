@@ -475,6 +475,100 @@ wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_dete
   });
 }
 
+// determinize_with_config of n acceptors (one workgroup each); every argument is checked before anything is launched
+static void check_batch_args(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs) {
+  if (outs)
+    for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+  if (!ctx || !fsts || !outs) throw Error("null pointer");
+  for (size_t i = 0; i < n; ++i)
+    if (!fsts[i]) throw Error("item " + std::to_string(i) + ": null FST in batch");
+}
+wfst_status wfst_determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_determinize_config* cfg,
+                                   wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    if (outs)
+      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    const wfst_determinize_config c = cfg ? *cfg : wfst_determinize_config{1.0f / 1024.0f, 0u};
+    if (c.det_type > 2) throw Error("determinize: unknown det_type " + std::to_string(c.det_type));
+    if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("determinize: delta must be finite and > 0");
+    if (ctx) ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
+    if (n == 0) return;
+    check_batch_args(ctx, fsts, n, outs);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    determinize_batch(ctx, fsts, n, c.delta, c.det_type, outs, in_kernel);
+  });
+}
+
+static float* to_malloc(const std::vector<float>& v) {  // released with wfst_bytes_destroy
+  float* p = (float*)std::malloc(std::max<size_t>(v.size(), 1) * sizeof(float));
+  if (!p) throw Error("out of memory");
+  if (!v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(float));
+  return p;
+}
+// determinize_with_distance (determinize_static.rs:24-39)
+wfst_status wfst_determinize_with_distance(wfst_ctx* ctx, const wfst_fst* fst, const float* in_dist, uint64_t n_in_dist,
+                                           float delta, wfst_fst** out, float** out_dist, uint64_t* n_out_dist) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (out_dist) *out_dist = nullptr;
+    if (n_out_dist) *n_out_dist = 0;
+    if (!(delta > 0.0f) || !std::isfinite(delta)) throw Error("determinize: delta must be finite and > 0");
+    if (!in_dist && n_in_dist) throw Error("determinize_with_distance: in_dist is NULL but n_in_dist > 0");
+    if (!ctx || !fst || !out || !out_dist || !n_out_dist) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<float> d;
+    std::unique_ptr<wfst_fst> r(determinize_with_distance_fst(ctx, fst, in_dist, n_in_dist, delta, d));
+    *out_dist = to_malloc(d);
+    *n_out_dist = d.size();
+    *out = r.release();
+  });
+}
+wfst_status wfst_determinize_with_distance_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n,
+                                                 const float* const* in_dists, const uint64_t* n_in_dists, float delta,
+                                                 wfst_fst** outs, float** out_dist, uint64_t* out_offsets, uint8_t* in_kernel) {
+  return wrap([&] {
+    if (outs)
+      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    if (out_dist) *out_dist = nullptr;
+    if (!(delta > 0.0f) || !std::isfinite(delta)) throw Error("determinize: delta must be finite and > 0");
+    if (ctx) ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
+    if (!out_dist || !out_offsets) throw Error("null pointer");
+    out_offsets[0] = 0;
+    if (n == 0) {
+      *out_dist = to_malloc({});
+      return;
+    }
+    if (!in_dists || !n_in_dists) throw Error("null pointer");
+    for (size_t i = 0; i < n; ++i)
+      if (!in_dists[i] && n_in_dists[i])
+        throw Error("item " + std::to_string(i) + ": determinize_with_distance: in_dist is NULL but n_in_dist > 0");
+    check_batch_args(ctx, fsts, n, outs);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<float> d;
+    std::vector<uint64_t> off;
+    determinize_batch(ctx, fsts, n, delta, 0, outs, in_kernel, in_dists, n_in_dists, &d, &off);
+    try {
+      *out_dist = to_malloc(d);
+    } catch (...) {
+      for (size_t i = 0; i < n; ++i) {
+        delete outs[i];
+        outs[i] = nullptr;
+      }
+      throw;
+    }
+    std::memcpy(out_offsets, off.data(), (n + 1) * sizeof(uint64_t));
+  });
+}
+wfst_status wfst_ctx_get_determinize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                 uint64_t* items_single) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (launches) *launches = ctx->det_batch_launches;
+    if (items_in_kernel) *items_in_kernel = ctx->det_batch_in_kernel;
+    if (items_single) *items_single = ctx->det_batch_single;
+  });
+}
+
 // minimize_with_config (minimize.rs:92-176); MinimizeConfig::default() = {KSHORTESTDELTA, false} when cfg == NULL
 wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out) {
   return wrap([&] {

@@ -174,6 +174,8 @@ struct wfst_ctx {
   } sweep_graph[3];  // [0]: first batch of a solve (predicted length), [1]: 8 sweeps per replay, [2]: 64
   wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags (its address is baked into the graphs)
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
+  // the last wfst_determinize_batch / wfst_determinize_with_distance_batch call (wfst_ctx_get_determinize_batch_stats)
+  uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
   int n_cus = 256;
 };
 
@@ -403,6 +405,13 @@ wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_t
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
 // ... of a label-encoded machine (optimize.hip): no "the word must say ACCEPTOR" check, the gallic call's word
 wfst_fst* determinize_encoded_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+// determinize.hip: n acceptors in one call, one workgroup each (new handles; on a throw every outs[i] is null); with
+// out_dist != null also determinize_with_distance's vector per item, concatenated, and its n + 1 offsets
+void determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, uint32_t det_type, wfst_fst** outs,
+                       uint8_t* in_kernel, const float* const* in_dist = nullptr, const uint64_t* n_in_dist = nullptr,
+                       std::vector<float>* out_dist = nullptr, std::vector<uint64_t>* out_off = nullptr);
+wfst_fst* determinize_with_distance_fst(wfst_ctx* ctx, const wfst_fst* f, const float* in_dist, uint64_t n_in_dist, float delta,
+                                        std::vector<float>& out_dist);
 // tr_sum.hip: tr_sum / tr_unique (a NEW handle)
 wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique);
 // optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)

@@ -49,6 +49,10 @@ constexpr uint32_t C_UNRES = 0, C_EXIST = 1, C_CREATE = 2, C_JOIN = 3, C_INVALID
 // narrow regime: levels of at most NARROW_STATES states and NARROW_CANDS candidates stay in the one-workgroup kernel
 constexpr uint32_t NARROW_STATES = 256, NARROW_CANDS = 8192;
 constexpr uint32_t NARROW_LEVELS_PER_LAUNCH = 1u << 16;
+// WFST_DETERMINIZE_BATCH_SCRATCH unset: where the batch kernel keeps the scratch of small levels (profiles/determinize_batch_timing.md)
+#ifndef WFST_DETERMINIZE_BATCH_LDS_DEFAULT
+#define WFST_DETERMINIZE_BATCH_LDS_DEFAULT false
+#endif
 
 __device__ __host__ inline float wplus(float a, float b) { return b < a ? b : a; }  // plus_assign (exact <)
 __device__ __host__ inline float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
@@ -69,7 +73,7 @@ struct Ctl {
   uint32_t rem;      // candidates left unresolved by the last round
   uint32_t levels;   // levels completed
   uint32_t exit;     // narrow kernel: 1 level too wide, 2 budget, 3 need, 4 done, 5 err
-  uint32_t pad;
+  uint32_t start;    // batch kernel: the input's start state (the block seeds state 0 itself)
 };
 
 struct Caps {
@@ -383,6 +387,56 @@ __device__ inline void bar() {
   __threadfence();
   __syncthreads();
 }
+// one level of the narrow regime, every thread of the block: 0 = the level is complete, else the exit code (Ctl::exit).
+// `d` holds the result arrays and the capacities the level is checked against; the phases after the check run on `dl`
+// instead when it is given and the level has at most dl->cap.cands raw candidates (the batch kernel's level scratch in LDS).
+__device__ __forceinline__ uint32_t narrow_level(const Det& d, const Det* dl, Ctl& c, uint32_t& left, uint64_t* lds,
+                                                 uint32_t max_k) {
+  const uint32_t t = threadIdx.x;
+  const uint32_t L = c.hi - c.lo;
+  ph_count(d, c.lo, L, t, TPB);
+  bar();
+  const uint64_t K = block_scan(d.lsc, 0, L, 0, lds);
+  if (t == 0) {
+    d.lsc[L] = K;
+    c.K = (uint32_t)std::min<uint64_t>(K, 0xFFFFFFFFull);
+    ph_check(d, c);
+    if (K > 0xFFFFFFFFull) c.need = 1;
+  }
+  bar();
+  if (c.need || c.K > max_k) return c.need ? 3 : 1;
+  const Det& v = (dl && c.K <= dl->cap.cands) ? *dl : d;
+  ph_clear(v, c.T, t, TPB);
+  ph_expand(v, c.lo, L, t, TPB);
+  bar();
+  ph_lookup(v, c.K, c.T, c.hi, t, TPB);
+  bar();
+  for (uint32_t r = 0; r <= c.K; ++r) {  // (every round settles its leaders: at most K rounds)
+    ph_round_a(v, c.K, r, t, TPB);
+    if (t == 0) left = 0;
+    bar();
+    const uint32_t l = ph_round_b(v, c.K, r, t, TPB);
+    if (l) atomicAdd(&left, l);
+    bar();
+    const bool done = left == 0;
+    __syncthreads();
+    if (done) break;
+  }
+  ph_flags(v, c.K, t, TPB);
+  bar();
+  const uint64_t t1 = block_scan(v.sc1, 0, c.K, 0, lds);
+  const uint64_t t2 = block_scan(v.sc2, 0, c.K, 0, lds);
+  if (t == 0) {
+    v.sc1[c.K] = t1;
+    v.sc2[c.K] = t2;
+  }
+  bar();
+  ph_number(v, c, t, TPB);
+  bar();
+  if (t == 0) ph_advance(v, c);
+  bar();
+  return 0;
+}
 __global__ void __launch_bounds__(TPB) det_narrow_kernel(Det d, uint32_t max_l, uint32_t max_k, uint32_t budget) {
   __shared__ uint64_t lds[TPB];
   __shared__ Ctl c;
@@ -396,52 +450,115 @@ __global__ void __launch_bounds__(TPB) det_narrow_kernel(Det d, uint32_t max_l, 
       if (t == 0) c.exit = c.err ? 5 : (L == 0 ? 4 : (L > max_l ? 1 : 2));
       break;
     }
-    ph_count(d, c.lo, L, t, TPB);
-    bar();
-    const uint64_t K = block_scan(d.lsc, 0, L, 0, lds);
-    if (t == 0) {
-      d.lsc[L] = K;
-      c.K = (uint32_t)std::min<uint64_t>(K, 0xFFFFFFFFull);
-      ph_check(d, c);
-      if (K > 0xFFFFFFFFull) c.need = 1;
-    }
-    bar();
-    if (c.need || c.K > max_k) {
-      if (t == 0) c.exit = c.need ? 3 : 1;
+    const uint32_t x = narrow_level(d, nullptr, c, left, lds, max_k);
+    if (x) {
+      if (t == 0) c.exit = x;
       break;
     }
-    ph_clear(d, c.T, t, TPB);
-    ph_expand(d, c.lo, L, t, TPB);
-    bar();
-    ph_lookup(d, c.K, c.T, c.hi, t, TPB);
-    bar();
-    for (uint32_t r = 0; r <= c.K; ++r) {  // (every round settles its leaders: at most K rounds)
-      ph_round_a(d, c.K, r, t, TPB);
-      if (t == 0) left = 0;
-      bar();
-      const uint32_t l = ph_round_b(d, c.K, r, t, TPB);
-      if (l) atomicAdd(&left, l);
-      bar();
-      const bool done = left == 0;
-      __syncthreads();
-      if (done) break;
-    }
-    ph_flags(d, c.K, t, TPB);
-    bar();
-    const uint64_t t1 = block_scan(d.sc1, 0, c.K, 0, lds);
-    const uint64_t t2 = block_scan(d.sc2, 0, c.K, 0, lds);
-    if (t == 0) {
-      d.sc1[c.K] = t1;
-      d.sc2[c.K] = t2;
-    }
-    bar();
-    ph_number(d, c, t, TPB);
-    bar();
-    if (t == 0) ph_advance(d, c);
-    bar();
   }
   __syncthreads();
   if (t == 0) *d.ctl = c;
+}
+
+// ---------------------------------------------------------------- batch: one workgroup per item, one launch for all
+// Block b runs the narrow level loop on items[b] from the seed to the end.  Exits as above, without the level budget:
+// 1 = a level of more than NARROW_STATES states or NARROW_CANDS raw candidates (the host finishes the item with the
+// single-FST path), 3 = the item's slice is too small (the host grows it and runs the item again), 4 done, 5 err.
+// lds_bytes > 0: the level scratch of levels with at most BATCH_LDS_CANDS candidates lives in LDS.
+constexpr uint32_t BATCH_LDS_CANDS = 496, BATCH_LDS_LTAB = 1024;
+constexpr size_t BATCH_LDS_BYTES = (size_t)BATCH_LDS_CANDS * (3 * 16 + 8 + 8 + 3 * 4) + 2 * 8 * (BATCH_LDS_CANDS + 1) +
+                                   (size_t)BATCH_LDS_LTAB * (8 + 2 * 4);
+__global__ void __launch_bounds__(TPB) det_batch_kernel(const Det* __restrict__ items, uint32_t lds_bytes) {
+  extern __shared__ __align__(16) unsigned char arena[];
+  __shared__ uint64_t lds[TPB];
+  __shared__ Ctl c;
+  __shared__ uint32_t left;
+  const uint32_t t = threadIdx.x;
+  const Det d = items[blockIdx.x];
+  Det dl = d;
+  if (lds_bytes) {  // 16-byte arrays first, then the 8-byte, then the 4-byte ones
+    unsigned char* p = arena;
+    auto take = [&](size_t bytes) {
+      unsigned char* q = p;
+      p += bytes;
+      return q;
+    };
+    dl.ca = (uint4*)take(16 * BATCH_LDS_CANDS);
+    dl.cb = (uint4*)take(16 * BATCH_LDS_CANDS);
+    dl.crec = (uint4*)take(16 * BATCH_LDS_CANDS);
+    dl.ce = (uint2*)take(8 * BATCH_LDS_CANDS);
+    dl.chash = (uint64_t*)take(8 * BATCH_LDS_CANDS);
+    dl.sc1 = (uint64_t*)take(8 * (BATCH_LDS_CANDS + 1));
+    dl.sc2 = (uint64_t*)take(8 * (BATCH_LDS_CANDS + 1));
+    dl.lkey = (uint64_t*)take(8 * BATCH_LDS_LTAB);
+    dl.cst = (uint32_t*)take(4 * BATCH_LDS_CANDS);
+    dl.cdest = (uint32_t*)take(4 * BATCH_LDS_CANDS);
+    dl.cslot = (uint32_t*)take(4 * BATCH_LDS_CANDS);
+    dl.lead = (uint32_t*)take(4 * 2 * BATCH_LDS_LTAB);
+    dl.cap.cands = BATCH_LDS_CANDS;
+    dl.cap.ltab = BATCH_LDS_LTAB;  // (>= 2 * BATCH_LDS_CANDS: ph_check's T fits)
+  }
+  if (t == 0) c = *d.ctl;
+  for (uint32_t i = t; i < d.cap.slots; i += TPB) {
+    d.hkey[i] = EMPTY_KEY;
+    d.hhead[i] = NONE;
+  }
+  bar();
+  if (t == 0) {  // state 0 = {(start, 0.0)} (det_seed_kernel)
+    d.so[0] = 0;
+    d.so[1] = 1;
+    d.se[0] = make_uint2(c.start, __float_as_uint(0.0f));
+    const uint32_t gs = probe(d.hkey, d.cap.slots, hash_states(d.se, 1), true);
+    d.hhead[gs] = 0;
+    d.hnext[0] = NONE;
+  }
+  bar();
+  for (;;) {
+    const uint32_t L = c.hi - c.lo;
+    if (c.err || L == 0 || L > NARROW_STATES) {
+      if (t == 0) c.exit = c.err ? 5 : (L == 0 ? 4 : 1);
+      break;
+    }
+    const uint32_t x = narrow_level(d, lds_bytes ? &dl : nullptr, c, left, lds, NARROW_CANDS);
+    if (x) {
+      if (t == 0) c.exit = x;
+      break;
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    if (c.exit == 4) d.aoff[c.hi] = c.n_arcs;  // CSR: aoff[N] = number of arcs
+    *d.ctl = c;
+  }
+}
+
+// out_dist[s] = plus over the elements (q, w) of subset s, in stored order, of w (x) in_dist[q]; q >= n_in counts as +inf
+// (determinize_static.rs:24-39, state_table.rs:25-39,79-96).  One lane per result state, all jobs of a batch in one launch:
+// job j owns out[off[j], off[j + 1]).
+struct DistJob {
+  const uint32_t* so;
+  const uint2* se;
+  const float* in;
+  uint32_t n_in;
+};
+__global__ void __launch_bounds__(TPB) det_dist_kernel(const DistJob* __restrict__ jobs, const uint32_t* __restrict__ off,
+                                                       uint32_t n_jobs, float* __restrict__ out) {
+  const uint32_t total = off[n_jobs];
+  for (uint32_t g = blockIdx.x * TPB + threadIdx.x; g < total; g += gridDim.x * TPB) {
+    uint32_t lo = 0, hi = n_jobs;  // the job with off[j] <= g < off[j + 1] (empty jobs are skipped by the search)
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (off[mid] <= g) lo = mid; else hi = mid;
+    }
+    const DistJob j = jobs[lo];
+    const uint32_t s = g - off[lo];
+    float acc = INF;
+    for (uint32_t k = j.so[s]; k < j.so[s + 1]; ++k) {
+      const uint2 e = j.se[k];
+      acc = wplus(acc, wtimes(__uint_as_float(e.y), e.x < j.n_in ? j.in[e.x] : INF));
+    }
+    out[g] = acc;
+  }
 }
 
 // ---------------------------------------------------------------- wide regime: one launch per phase
@@ -655,14 +772,30 @@ Path path_knob() {
 
 }  // namespace
 
+// out_dist of determinize_with_distance for ONE result: in_dist on the device, the answer on the host
+struct DistReq {
+  const float* d_in;
+  uint32_t n_in;
+  std::vector<float>* out;  // resized to the result's state count
+};
 // determinize_with_config for an acceptor (determinize_static.rs:176-190, the DeterminizeFsa branch): a NEW handle
-static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
+static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type,
+                                      const DistReq* dq = nullptr);
+static const char* const NOT_ACCEPTOR_MSG =
+    "determinize: transducers are not supported (the property word does not contain ACCEPTOR); use rustfst's determinize";
+static const char* const LIMIT_MSG = "determinize: more than 16 M states (the input does not determinize?)";
+static uint32_t max_states_knob() {
+  uint32_t max_states = 1u << 24;  // the host restatement's limits (nshortest.hip): 16 M states, 256 M elements
+  if (const char* e = std::getenv("WFST_DETERMINIZE_MAX_STATES")) {  // tests: reach the guard in seconds
+    const long v = std::atol(e);
+    if (v > 0 && (uint64_t)v < max_states) max_states = (uint32_t)v;
+  }
+  return max_states;
+}
 
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
   // the reference branches on the STORED word (determinize_static.rs:181-185): anything else takes the gallic path
-  if (!(f->props & props::ACCEPTOR))
-    throw Error("determinize: transducers are not supported (the property word does not contain ACCEPTOR); "
-                "use rustfst's determinize");
+  if (!(f->props & props::ACCEPTOR)) throw Error(NOT_ACCEPTOR_MSG);
   return determinize_acceptor(ctx, f, delta, det_type);
 }
 
@@ -673,20 +806,17 @@ wfst_fst* determinize_encoded_fst(wfst_ctx* ctx, const wfst_fst* f, float delta,
   return determinize_acceptor(ctx, f, delta, det_type);
 }
 
-static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
+static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type, const DistReq* dq) {
   const uint64_t out_props = props::determinize(f->props, det_type != 1);
   if (f->start < 0 || f->n_states == 0) {  // compute_start -> None: the empty FST (lazy_fst.rs:229-232)
     HostCsr h;
     h.offsets.push_back(0);
+    if (dq) dq->out->clear();
     return make_host_fst(ctx, 0, -1, out_props, std::move(h));
   }
   ensure_device(const_cast<wfst_fst*>(f));
   const Path path = path_knob();
-  uint32_t max_states = 1u << 24;  // the host restatement's limits (nshortest.hip): 16 M states, 256 M elements
-  if (const char* e = std::getenv("WFST_DETERMINIZE_MAX_STATES")) {  // tests: reach the guard in seconds
-    const long v = std::atol(e);
-    if (v > 0 && (uint64_t)v < max_states) max_states = (uint32_t)v;
-  }
+  const uint32_t max_states = max_states_knob();
   hipStream_t st = ctx->stream;
   Run run(*ctx->pool, st);
   run.cap.max_states = max_states;
@@ -708,7 +838,7 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
   };
   // every pass of this loop completes at least one level or grows the arrays (bounded by the state limit)
   for (;;) {
-    if (c.err) throw Error("determinize: more than 16 M states (the input does not determinize?)");
+    if (c.err) throw Error(LIMIT_MSG);
     const uint32_t L = c.hi - c.lo;
     if (L == 0) break;
     if (c.need) {  // room for the level that could not start (K slots; every state of it may add K more)
@@ -769,8 +899,302 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
   // CSR: aoff[N] = number of arcs
   const uint32_t N = c.hi;
   HIP_CHECK(hipMemcpyAsync(run.aoff.p + N, &c.n_arcs, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (dq) {  // one job: every state of the result
+    const DistJob job{run.so.p, run.se.p, dq->d_in, dq->n_in};
+    const uint32_t off[2] = {0, N};
+    DBuf<DistJob> d_job(*ctx->pool, 1);
+    DBuf<uint32_t> d_off(*ctx->pool, 2);
+    DBuf<float> d_out(*ctx->pool, N);
+    HIP_CHECK(hipMemcpyAsync(d_job.p, &job, sizeof(job), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_off.p, off, sizeof(off), hipMemcpyHostToDevice, st));
+    det_dist_kernel<<<std::max<uint32_t>(1, std::min<uint32_t>((N + TPB - 1) / TPB, 1024)), TPB, 0, st>>>(d_job.p, d_off.p, 1, d_out.p);
+    HIP_CHECK(hipGetLastError());
+    dq->out->resize(N);
+    HIP_CHECK(hipMemcpyAsync(dq->out->data(), d_out.p, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
   HIP_CHECK(hipStreamSynchronize(st));
   return adopt_device(ctx, N, c.n_arcs, 0, out_props, run.aoff.p, run.oarc.p, run.ofin.p);
+}
+
+// ---------------------------------------------------------------- batch (wfst_determinize_batch)
+namespace {
+struct Slice {  // capacities of one item's slice of the launch's slab
+  uint64_t states, elts, arcs, cands;
+};
+struct Done {  // a finished item: its result arrays inside the slab of the launch that finished it
+  uint32_t N = 0, n_arcs = 0;
+  const uint32_t *aoff = nullptr, *so = nullptr;
+  const wfst_tr* oarc = nullptr;
+  const float* ofin = nullptr;
+  const uint2* se = nullptr;
+};
+// carves one item's arrays out of [base + at, ...): every array 64-byte aligned; base == nullptr only measures
+size_t carve_slice(unsigned char* base, size_t at, const Slice& sl, const wfst_fst* f, float delta, uint32_t max_states, Det* d) {
+  auto take = [&](size_t bytes) {
+    const size_t o = at;
+    at += (bytes + 63) & ~(size_t)63;
+    return base ? base + o : nullptr;
+  };
+  const uint32_t slots = pow2_at_least(2 * sl.states), ltab = pow2_at_least(2 * sl.cands);
+  Det v{};
+  v.so = (uint32_t*)take(4 * (sl.states + 1));
+  v.aoff = (uint32_t*)take(4 * (sl.states + 1));
+  v.ofin = (float*)take(4 * sl.states);
+  v.hnext = (uint32_t*)take(4 * sl.states);
+  v.lsc = (uint64_t*)take(8 * (sl.states + 1));
+  v.se = (uint2*)take(8 * sl.elts);
+  v.oarc = (wfst_tr*)take(sizeof(wfst_tr) * sl.arcs);
+  v.hkey = (uint64_t*)take(8 * (size_t)slots);
+  v.hhead = (uint32_t*)take(4 * (size_t)slots);
+  v.ca = (uint4*)take(16 * sl.cands);
+  v.cb = (uint4*)take(16 * sl.cands);
+  v.crec = (uint4*)take(16 * sl.cands);
+  v.ce = (uint2*)take(8 * sl.cands);
+  v.chash = (uint64_t*)take(8 * sl.cands);
+  v.sc1 = (uint64_t*)take(8 * (sl.cands + 1));
+  v.sc2 = (uint64_t*)take(8 * (sl.cands + 1));
+  v.lkey = (uint64_t*)take(8 * (size_t)ltab);
+  v.cst = (uint32_t*)take(4 * sl.cands);
+  v.cdest = (uint32_t*)take(4 * sl.cands);
+  v.cslot = (uint32_t*)take(4 * sl.cands);
+  v.lead = (uint32_t*)take(4 * 2 * (size_t)ltab);
+  if (d) {
+    v.off = f->dev.offsets;
+    v.arcs = f->dev.arcs;
+    v.fin = f->dev.finals;
+    v.delta = delta;
+    v.cap = Caps{(uint32_t)sl.states, (uint32_t)sl.elts, (uint32_t)sl.arcs, (uint32_t)sl.cands, slots, ltab, max_states, 1u << 28};
+    *d = v;
+  }
+  return at;
+}
+bool lds_scratch_knob() {
+  const char* e = std::getenv("WFST_DETERMINIZE_BATCH_SCRATCH");
+  if (!e || !*e) return WFST_DETERMINIZE_BATCH_LDS_DEFAULT;
+  if (!std::strcmp(e, "lds")) return true;
+  if (!std::strcmp(e, "global")) return false;
+  throw Error(std::string("WFST_DETERMINIZE_BATCH_SCRATCH: expected lds or global, not '") + e + "'");
+}
+bool min_arena_knob() {  // tests: the first launch's slices as small as the kernel allows, so that every item grows
+  const char* e = std::getenv("WFST_DETERMINIZE_BATCH_ARENA");
+  if (!e || !*e) return false;
+  if (!std::strcmp(e, "min")) return true;
+  throw Error(std::string("WFST_DETERMINIZE_BATCH_ARENA: expected min, not '") + e + "'");
+}
+}  // namespace
+
+void determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, uint32_t det_type, wfst_fst** outs,
+                       uint8_t* in_kernel, const float* const* in_dist, const uint64_t* n_in_dist, std::vector<float>* out_dist,
+                       std::vector<uint64_t>* out_off) {
+  ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
+  // every stored word before anything is launched
+  for (size_t i = 0; i < n; ++i)
+    if (!(fsts[i]->props & props::ACCEPTOR)) throw Error("item " + std::to_string(i) + ": " + NOT_ACCEPTOR_MSG);
+  const bool use_lds = lds_scratch_knob(), min_arena = min_arena_knob();
+  const uint32_t max_states = max_states_knob();
+  hipStream_t st = ctx->stream;
+  enum : uint8_t { OPEN, DONE, SINGLE, TRIVIAL };
+  std::vector<uint8_t> state(n, OPEN);
+  std::vector<Slice> slice(n);
+  std::vector<Done> done(n);
+  std::vector<size_t> open;
+  for (size_t i = 0; i < n; ++i) {
+    const wfst_fst* f = fsts[i];
+    if (f->start < 0 || f->n_states == 0) {  // the empty FST: never occupies a workgroup
+      state[i] = TRIVIAL;
+      continue;
+    }
+    ensure_device(const_cast<wfst_fst*>(f));
+    // from the input's sizes alone (no device read): a level of up to `cands` raw candidates on top of as many states as
+    // the input has; whatever needs more reports it and runs again
+    const uint64_t cands = std::min<uint64_t>(std::max<uint64_t>(f->n_arcs, 64), NARROW_CANDS);
+    slice[i] = min_arena ? Slice{1, 1, 1, 1} : Slice{f->n_states + cands + 1, 2ull * f->n_states + cands, f->n_arcs + cands, cands};
+    open.push_back(i);
+  }
+  // in_dist of every item in one upload
+  DBuf<float> d_in;
+  std::vector<size_t> in_at(n, 0);
+  if (out_dist) {
+    std::vector<float> cat;
+    for (size_t i = 0; i < n; ++i) {
+      in_at[i] = cat.size();
+      if (n_in_dist[i]) cat.insert(cat.end(), in_dist[i], in_dist[i] + n_in_dist[i]);
+    }
+    d_in = DBuf<float>(*ctx->pool, cat.size());
+    if (!cat.empty()) HIP_CHECK(hipMemcpyAsync(d_in.p, cat.data(), cat.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+  auto n_in = [&](size_t i) { return (uint32_t)std::min<uint64_t>(n_in_dist[i], 0xFFFFFFFFull); };
+  std::vector<DBuf<unsigned char>> slabs;  // one per launch; the results of finished items stay in theirs until adopted
+  size_t first_err = n;
+  // every launch finishes an item, hands it to the single path, or at least doubles what its slice was short of, and the
+  // limits cap the slices: a bounded number of launches
+  while (!open.empty()) {
+    if (ctx->det_batch_launches >= 64) throw Error("determinize_batch: the arenas did not converge");
+    const size_t m = open.size();
+    std::vector<size_t> at(m + 1);
+    size_t bytes = (m * sizeof(Ctl) + 63) & ~(size_t)63;
+    for (size_t k = 0; k < m; ++k) {
+      at[k] = bytes;
+      bytes = carve_slice(nullptr, bytes, slice[open[k]], nullptr, delta, max_states, nullptr);
+    }
+    slabs.emplace_back(*ctx->pool, bytes);
+    unsigned char* base = slabs.back().p;
+    Ctl* d_ctl = (Ctl*)base;
+    std::vector<Det> dets(m);
+    std::vector<Ctl> ctls(m);
+    for (size_t k = 0; k < m; ++k) {
+      const wfst_fst* f = fsts[open[k]];
+      carve_slice(base, at[k], slice[open[k]], f, delta, max_states, &dets[k]);
+      dets[k].ctl = d_ctl + k;
+      Ctl c{};
+      c.hi = 1;
+      c.n_elts = 1;
+      c.start = (uint32_t)f->start;
+      ctls[k] = c;
+    }
+    DBuf<Det> d_dets(*ctx->pool, m);
+    HIP_CHECK(hipMemcpyAsync(d_dets.p, dets.data(), m * sizeof(Det), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_ctl, ctls.data(), m * sizeof(Ctl), hipMemcpyHostToDevice, st));
+    const uint32_t lds_bytes = use_lds ? (uint32_t)BATCH_LDS_BYTES : 0u;
+    det_batch_kernel<<<(uint32_t)m, TPB, lds_bytes, st>>>(d_dets.p, lds_bytes);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(ctls.data(), d_ctl, m * sizeof(Ctl), hipMemcpyDeviceToHost, st));  // the control blocks, once
+    HIP_CHECK(hipStreamSynchronize(st));
+    ctx->det_batch_launches += 1;
+    std::vector<size_t> still;
+    for (size_t k = 0; k < m; ++k) {
+      const size_t i = open[k];
+      const Ctl& c = ctls[k];
+      const Det& d = dets[k];
+      if (c.exit == 4) {
+        state[i] = DONE;
+        done[i] = Done{c.hi, c.n_arcs, d.aoff, d.so, d.oarc, d.ofin, d.se};
+      } else if (c.exit == 1) {
+        state[i] = SINGLE;
+      } else if (c.exit == 5) {
+        first_err = std::min(first_err, i);
+        state[i] = SINGLE;  // (never run: the call is KO)
+      } else if (c.exit == 3) {
+        Slice& sl = slice[i];
+        const uint64_t K = std::max<uint64_t>(c.K, 1);
+        auto up = [](uint64_t& have, uint64_t want) {
+          if (want > have) have = std::max<uint64_t>(2 * have, want);
+        };
+        const Slice before = sl;
+        up(sl.cands, K);
+        up(sl.states, (uint64_t)c.hi + K + 1);
+        up(sl.elts, (uint64_t)c.n_elts + K);
+        up(sl.arcs, (uint64_t)c.n_arcs + K);
+        if (sl.cands == before.cands && sl.states == before.states && sl.elts == before.elts && sl.arcs == before.arcs)
+          throw Error("determinize_batch: a slice reported a need it already covers");
+        if (sl.states > 0x7FFFFFFFull || sl.elts > 0x7FFFFFFFull || sl.arcs > 0x7FFFFFFFull)
+          throw Error("determinize: more than 2^31 states, elements, arcs or level candidates");
+        still.push_back(i);
+      } else {
+        throw Error("determinize_batch: unexpected exit code " + std::to_string(c.exit));
+      }
+    }
+    open.swap(still);
+  }
+  if (first_err < n) throw Error("item " + std::to_string(first_err) + ": " + LIMIT_MSG);
+  try {
+    std::vector<uint64_t> n_out(n, 0);
+    std::vector<std::vector<float>> single_dist(n);
+    // the items with a level too wide for one workgroup: the single-FST path
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t out_props = props::determinize(fsts[i]->props, det_type != 1);
+      if (state[i] == TRIVIAL) {
+        HostCsr h;
+        h.offsets.push_back(0);
+        outs[i] = make_host_fst(ctx, 0, -1, out_props, std::move(h));
+      } else if (state[i] == SINGLE) {
+        try {
+          if (out_dist) {
+            const DistReq dq{d_in.p + in_at[i], n_in(i), &single_dist[i]};
+            outs[i] = determinize_acceptor(ctx, fsts[i], delta, det_type, &dq);
+          } else {
+            outs[i] = determinize_acceptor(ctx, fsts[i], delta, det_type);
+          }
+        } catch (const std::exception& e) {
+          throw Error("item " + std::to_string(i) + ": " + e.what());
+        }
+        n_out[i] = outs[i]->n_states;
+        ctx->det_batch_single += 1;
+      } else {
+        n_out[i] = done[i].N;
+      }
+      if (in_kernel) in_kernel[i] = state[i] != SINGLE;
+      if (state[i] != SINGLE) ctx->det_batch_in_kernel += 1;
+    }
+    // the items the kernel finished: one adoption, one distance launch
+    std::vector<size_t> idx;
+    std::vector<AdoptDesc> descs;
+    for (size_t i = 0; i < n; ++i)
+      if (state[i] == DONE) {
+        idx.push_back(i);
+        descs.push_back(AdoptDesc{done[i].N, done[i].n_arcs, 0, props::determinize(fsts[i]->props, det_type != 1), done[i].aoff,
+                                  done[i].oarc, done[i].ofin});
+      }
+    std::vector<float> kd;      // out_dist of the kernel's items, in idx order
+    std::vector<uint32_t> koff(idx.size() + 1, 0);
+    if (out_dist && !idx.empty()) {
+      std::vector<DistJob> jobs(idx.size());
+      uint64_t tot = 0;
+      for (size_t k = 0; k < idx.size(); ++k) {
+        const size_t i = idx[k];
+        jobs[k] = DistJob{done[i].so, done[i].se, d_in.p + in_at[i], n_in(i)};
+        tot += done[i].N;
+        if (tot > 0x7FFFFFFFull) throw Error("determinize_batch: more than 2^31 result states in one batch");
+        koff[k + 1] = (uint32_t)tot;
+      }
+      DBuf<DistJob> d_jobs(*ctx->pool, jobs.size());
+      DBuf<uint32_t> d_off(*ctx->pool, koff.size());
+      DBuf<float> d_out(*ctx->pool, tot);
+      HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), jobs.size() * sizeof(DistJob), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(d_off.p, koff.data(), koff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      det_dist_kernel<<<(uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tot + TPB - 1) / TPB, 1024)), TPB, 0, st>>>(
+          d_jobs.p, d_off.p, (uint32_t)jobs.size(), d_out.p);
+      HIP_CHECK(hipGetLastError());
+      kd.resize(tot);
+      HIP_CHECK(hipMemcpyAsync(kd.data(), d_out.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (!idx.empty()) {
+      std::vector<wfst_fst*> got(idx.size(), nullptr);
+      adopt_device_many(ctx, idx.size(), descs.data(), got.data());
+      for (size_t k = 0; k < idx.size(); ++k) outs[idx[k]] = got[k];
+    }
+    if (out_dist) {
+      out_off->assign(n + 1, 0);
+      for (size_t i = 0; i < n; ++i) (*out_off)[i + 1] = (*out_off)[i] + n_out[i];
+      out_dist->assign((*out_off)[n], 0.0f);
+      for (size_t k = 0; k < idx.size(); ++k)
+        std::copy(kd.begin() + koff[k], kd.begin() + koff[k + 1], out_dist->begin() + (*out_off)[idx[k]]);
+      for (size_t i = 0; i < n; ++i)
+        if (state[i] == SINGLE) std::copy(single_dist[i].begin(), single_dist[i].end(), out_dist->begin() + (*out_off)[i]);
+    }
+  } catch (...) {
+    for (size_t i = 0; i < n; ++i) {
+      delete outs[i];
+      outs[i] = nullptr;
+    }
+    throw;
+  }
+}
+
+// determinize_with_distance (determinize_static.rs:24-39): the Functional construction and out_dist, for one acceptor
+wfst_fst* determinize_with_distance_fst(wfst_ctx* ctx, const wfst_fst* f, const float* in_dist, uint64_t n_in_dist, float delta,
+                                        std::vector<float>& out_dist) {
+  if (!(f->props & props::ACCEPTOR)) throw Error(NOT_ACCEPTOR_MSG);
+  DBuf<float> d_in(*ctx->pool, n_in_dist);
+  if (n_in_dist) {
+    HIP_CHECK(hipMemcpyAsync(d_in.p, in_dist, n_in_dist * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
+  const DistReq dq{d_in.p, (uint32_t)std::min<uint64_t>(n_in_dist, 0xFFFFFFFFull), &out_dist};
+  return determinize_acceptor(ctx, f, delta, 0, &dq);
 }
 
 }  // namespace wfst

@@ -642,6 +642,80 @@ def shortest_path_batch(fsts: Sequence[DeviceFst], config: Optional["ShortestPat
     return [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
 
 
+def _handles(fsts):
+    n = len(fsts)
+    return fsts._arr if isinstance(fsts, HandleArray) else (C.c_void_p * n)(*[f._h.value if isinstance(f._h, C.c_void_p) else f._h for f in fsts])
+
+
+def determinize_batch(fsts: Sequence[DeviceFst], config: Optional["DeterminizeConfig"] = None,
+                      ctx: Optional[Context] = None, want_flags: bool = False):
+    """[f.determinize(config) for f in fsts] as ONE call (wfst_determinize_batch): one workgroup per acceptor, one launch
+    for the batch — the form for the many small lattices of a decoding batch.  want_flags: also the uint8 array that
+    says which items the batch kernel constructed (0: a level of more than 256 states or 8192 raw candidates sent the
+    item through the single-FST path)."""
+    n = len(fsts)
+    if n == 0:
+        return ([], np.zeros(0, np.uint8)) if want_flags else []
+    ctx = ctx or fsts[0].ctx
+    outs = (C.c_void_p * n)()
+    flags = np.zeros(n, np.uint8)
+    check(_lib.lib().wfst_determinize_batch(ctx._h, _handles(fsts), n, config._c() if config is not None else None, outs,
+                                            flags.ctypes.data), "wfst_determinize_batch")
+    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
+    return (res, flags) if want_flags else res
+
+
+def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last determinize_batch / determinize_with_distance_batch call of ctx (wfst_ctx_get_determinize_batch_stats)."""
+    ctx = ctx or default_context()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(_lib.lib().wfst_ctx_get_determinize_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
+          "wfst_ctx_get_determinize_batch_stats")
+    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+
+
+def _take_floats(ptr, count):
+    out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(count,)).copy() if count else np.zeros(0, np.float32)
+    _lib.lib().wfst_bytes_destroy(ptr)
+    return out
+
+
+def determinize_with_distance(fst: DeviceFst, in_dist, delta: float = KDELTA):
+    """algorithms::determinize_with_distance (determinize_static.rs:24-39, wfst_determinize_with_distance): the
+    determinized acceptor (a NEW FST) and out_dist, where out_dist[s] is the sum over the elements (q, w) of subset s
+    of w * in_dist[q]; states beyond len(in_dist) count as +inf."""
+    d = np.ascontiguousarray(in_dist, np.float32)
+    out, ptr, cnt = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    check(_lib.lib().wfst_determinize_with_distance(fst.ctx._h, fst._h, d.ctypes.data if len(d) else None, len(d), delta,
+                                                    C.byref(out), C.byref(ptr), C.byref(cnt)),
+          "Error during determinize_with_distance")
+    return DeviceFst(out, fst.ctx), _take_floats(ptr, cnt.value)
+
+
+def determinize_with_distance_batch(fsts: Sequence[DeviceFst], in_dists, delta: float = KDELTA,
+                                    ctx: Optional[Context] = None, want_flags: bool = False):
+    """[determinize_with_distance(f, d, delta) for f, d in zip(fsts, in_dists)] as ONE call
+    (wfst_determinize_with_distance_batch): a list of (DeviceFst, np.ndarray)."""
+    n = len(fsts)
+    if len(in_dists) != n:
+        raise ValueError("one in_dist per FST")
+    if n == 0:
+        return ([], np.zeros(0, np.uint8)) if want_flags else []
+    ctx = ctx or fsts[0].ctx
+    ds = [np.ascontiguousarray(d, np.float32) for d in in_dists]
+    ptrs = (C.c_void_p * n)(*[d.ctypes.data if len(d) else None for d in ds])
+    lens = (C.c_uint64 * n)(*[len(d) for d in ds])
+    outs = (C.c_void_p * n)()
+    off = (C.c_uint64 * (n + 1))()
+    flags = np.zeros(n, np.uint8)
+    ptr = C.c_void_p()
+    check(_lib.lib().wfst_determinize_with_distance_batch(ctx._h, _handles(fsts), n, ptrs, lens, delta, outs, C.byref(ptr),
+                                                          off, flags.ctypes.data), "wfst_determinize_with_distance_batch")
+    cat = _take_floats(ptr, off[n])
+    res = [(DeviceFst(C.c_void_p(outs[i]), ctx), cat[off[i]:off[i + 1]].copy()) for i in range(n)]
+    return (res, flags) if want_flags else res
+
+
 def last_nbest_path(ctx: Optional[Context] = None) -> str:
     """Which search the last shortest_path_batch(nshortest > 1) used (wfst_stats.nbest_device_problems)."""
     ctx = ctx or default_context()
