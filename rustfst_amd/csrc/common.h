@@ -14,10 +14,9 @@
 #include <vector>
 
 #include "../../include/wfst.h"
+#include "tropical.h"
 
 namespace wfst {
-
-constexpr float INF = __builtin_huge_valf();
 
 // one turn of a host spin loop on a word in pinned memory (the completion tickets)
 inline void cpu_relax() {
@@ -310,6 +309,33 @@ struct wfst_fst {
 };
 
 namespace wfst {
+// an intermediate FST handle of an operation: destroyed on every exit, with its device current
+struct HandleDeleter {
+  void operator()(wfst_fst* p) const {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    delete p;
+  }
+};
+using Handle = std::unique_ptr<wfst_fst, HandleDeleter>;
+// 64-bit finalizer (MurmurHash3 fmix64) of the device hash tables
+__device__ inline uint64_t mix64(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33;
+  x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+// device_ops.hip: the host-side plumbing every operation repeats (all of it on ctx->stream)
+// out[i] = in[0] + .. + in[i - 1] for i < count.  The scan runs asynchronously in the returned scratch: keep it alive until
+// the caller's next synchronisation of the stream.
+[[nodiscard]] DBuf<uint8_t> exclusive_scan_u32(wfst_ctx* ctx, const uint32_t* in, uint32_t* out, size_t count);
+uint32_t read_u32(wfst_ctx* ctx, const uint32_t* d);  // one word back to the host; synchronises the stream
+// indeg[arcs[i].nextstate] += 1 over the n_arcs arcs (indeg zeroed by the caller; nothing is launched without arcs)
+void count_indegrees(wfst_ctx* ctx, const wfst_tr* arcs, uint64_t n_arcs, uint32_t* indeg);
+// size of a hash table for v entries: the power of two >= max(v, 64); throws "<what>: ..." beyond 2^31
+uint32_t pow2_at_least(uint64_t v, const char* what);
 // fst_store.hip
 void ensure_device(wfst_fst* f);             // upload host copy if needed (mutates cache only)
 void ensure_host(const wfst_fst* f);         // download if needed

@@ -211,17 +211,6 @@ __device__ __forceinline__ void st_l2(T* p, T v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ uint32_t enc_f32(float f) {
-  uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) {
-  uint32_t b = (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e;
-  return __uint_as_float(b);
-}
-// TropicalWeight::times_assign (semirings/tropical_weight.rs:60-70)
-__device__ __forceinline__ float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
-
 __device__ __forceinline__ uint32_t hash_u64(uint64_t h) {
   h ^= h >> 33;
   h *= 0xff51afd7ed558ccdull;
@@ -395,7 +384,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
     se = load_arc(se_arcs + lane);
     se_key = mi ? se.il : se.ol;
   }
-  const float src_d = dec_f32((uint32_t)(src_sk >> 32));
+  const float src_d = key_f32((uint32_t)(src_sk >> 32));
   const uint32_t src_h1 = (uint32_t)src_sk + 1u;
 
   uint32_t n_arcs = *n_arcs_io;
@@ -493,7 +482,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
           uint64_t cand = KEY_INF;
           if (src_sk != KEY_INF) {
             const float c = (src_d + wsum) + 0.0f;
-            if (c < INF) cand = ((uint64_t)enc_f32(c) << 32) | src_h1;
+            if (c < INF) cand = ((uint64_t)f32_key(c) << 32) | src_h1;
           }
           stg->cand[e] = cand;
         } else {
@@ -545,14 +534,14 @@ __device__ bool relax_states(const Arena& ar, uint32_t lo, uint32_t hi, uint32_t
     if (q < hi) {
       const uint64_t kq = ld_l2(&ar.skey[q]);
       if (kq != KEY_INF) {
-        const float d = dec_f32((uint32_t)(kq >> 32));
+        const float d = key_f32((uint32_t)(kq >> 32));
         const uint32_t h1 = (uint32_t)kq + 1u;
         const uint32_t b = ar.off[q], e = ar.off[q + 1];
         for (uint32_t i = b; i < e && i < n_arcs_total; ++i) {
           const ArcReg a = load_arc(ar.arcs + i);
           const float c = (d + a.w) + 0.0f;
           if (!(c < INF)) continue;
-          const uint64_t ck = ((uint64_t)enc_f32(c) << 32) | h1;
+          const uint64_t ck = ((uint64_t)f32_key(c) << 32) | h1;
           const uint64_t old = atomicMin((unsigned long long*)&ar.skey[a.ns], (unsigned long long)ck);
           if (ck < old) changed = true;
         }
@@ -605,7 +594,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
       const uint32_t slot = ht_insert(ar.hkeys, ar.hvals, caps.H - 1, key0, 0u);
       st_l2(&ar.hvals[slot], 0u);
       ar.tuples[0] = key0;
-      if (FLAGS & FLAG_SP) ar.skey[0] = (uint64_t)enc_f32(0.0f) << 32;
+      if (FLAGS & FLAG_SP) ar.skey[0] = (uint64_t)f32_key(0.0f) << 32;
     }
     wave_sync();
     n_states = 1;
@@ -614,7 +603,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
     // frontier in registers while it is <= 64 states wide: lane i holds state lo + i
     bool fast = true;
     uint64_t f_key = lane == 0 ? pack_tuple(0u, (uint32_t)f1.start, (uint32_t)f2.start) : 0ull;
-    uint64_t f_sk = lane == 0 ? ((uint64_t)enc_f32(0.0f) << 32) : KEY_INF;
+    uint64_t f_sk = lane == 0 ? ((uint64_t)f32_key(0.0f) << 32) : KEY_INF;
     uint4 f_r1 = make_uint4(0, 0, 0, 0), f_r2 = make_uint4(0, 0, 0, 0);
     if (lane == 0) {
       f_r1 = ld_global16(f1.srec + f1.start);
@@ -903,9 +892,9 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
         const uint64_t kq = ld_l2(&ar.skey[q]);
         const float f = ar.fin[q];
         if (kq != KEY_INF && f < INF) {
-          const float tot = (dec_f32((uint32_t)(kq >> 32)) + f) + 0.0f;
+          const float tot = (key_f32((uint32_t)(kq >> 32)) + f) + 0.0f;
           if (tot < INF) {
-            const unsigned long long c = ((unsigned long long)enc_f32(tot) << 32) | q;
+            const unsigned long long c = ((unsigned long long)f32_key(tot) << 32) | q;
             best = c < best ? c : best;
           }
         }
@@ -918,7 +907,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
       res.has_path = 1;
       res.hops = hops;
       res.final_weight = ar.fin[fp];
-      res.total = dec_f32((uint32_t)(best >> 32));
+      res.total = key_f32((uint32_t)(best >> 32));
       // parent[t] = min (s,pos) among layered tight arcs
       for (uint32_t i = lane; i < n_states; i += 64) ar.parent[i] = KEY_INF;
       wave_sync();
@@ -927,14 +916,14 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
         if (q < n_states) {
           const uint64_t kq = ld_l2(&ar.skey[q]);
           if (kq != KEY_INF) {
-            const float d = dec_f32((uint32_t)(kq >> 32));
+            const float d = key_f32((uint32_t)(kq >> 32));
             const uint32_t h1 = (uint32_t)kq + 1u;
             const uint32_t b = ar.off[q], e = ar.off[q + 1];
             for (uint32_t i = b; i < e; ++i) {
               const ArcReg a = load_arc(ar.arcs + i);
               const float c = (d + a.w) + 0.0f;
               if (!(c < INF)) continue;
-              const uint64_t ck = ((uint64_t)enc_f32(c) << 32) | h1, kt = ld_l2(&ar.skey[a.ns]);
+              const uint64_t ck = ((uint64_t)f32_key(c) << 32) | h1, kt = ld_l2(&ar.skey[a.ns]);
               // class 0: tight in distance and hop count; class 1 (top bit): tight in the distance only, from a state
               // with a smaller key (sssp.hip parent_class)
               if (ck == kt)
@@ -1233,7 +1222,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
       if (fin1 != INF && fin2 != INF) my_fin = wtimes(fin1, fin2);
       if (d < INF && my_fin < INF) {
         const float tot = (d + my_fin) + 0.0f;
-        if (tot < INF) best = ((unsigned long long)enc_f32(tot) << 32) | (lo + lane);
+        if (tot < INF) best = ((unsigned long long)f32_key(tot) << 32) | (lo + lane);
       }
     }
   }
@@ -1243,7 +1232,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
     res.has_path = 1;
     res.hops = L;
     res.final_weight = __uint_as_float(rl(__float_as_uint(my_fin), fp - lo));
-    res.total = dec_f32((uint32_t)(best >> 32));
+    res.total = key_f32((uint32_t)(best >> 32));
     if (lane == 0) {  // walk the parents back (LDS); state k of the walk is in level L - k
       uint32_t cur = fp;
       for (uint32_t k = 0; k < L; ++k) {
@@ -1266,11 +1255,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
         const uint32_t ol = s_ol[st];
         const float w = s_w[st];
         store_arc(path_buf + poff + k, il, ol, w, k);
-        // fst_props.h path_arc_facts (is_zero / is_one: the reference's approximate ==, semiring.rs:68-73,159-168)
-        const bool w_zero = w <= INF + props::KDELTA && INF <= w + props::KDELTA;
-        const bool w_one = w <= props::KDELTA && 0.0f <= w + props::KDELTA;
-        facts |= (il != ol ? 1u : 0u) | (il == WFST_EPS_LABEL ? 2u : 0u) | (il == WFST_EPS_LABEL && ol == WFST_EPS_LABEL ? 4u : 0u) |
-                 (ol == WFST_EPS_LABEL ? 8u : 0u) | (!w_zero && !w_one ? 64u : 0u) | 128u;
+        facts |= props::path_arc_facts(il, ol, w);
       }
       for (int d = 32; d >= 1; d >>= 1) facts |= __shfl_xor(facts, d);
       res.facts = facts;

@@ -34,7 +34,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
 
 #include "common.h"
 #include "fst_props.h"
@@ -47,7 +46,6 @@ namespace {
 
 constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
 constexpr uint32_t REJECT = 0xFFFFFFFFu;
-constexpr float KDELTA_F = 1.0f / 1024.0f;  // lib.rs:269
 constexpr uint32_t WIDE_SWITCH_STATES = 2048;  // results larger than this are redone on the wide path
 constexpr uint32_t WIDE_SWITCH_WIDTH = 256;    // ... and so are results with a BFS level wider than this
 constexpr uint32_t WIDE_SWITCH_STATES_ONE = 512;  // the same two limits for a call with ONE composition
@@ -234,7 +232,7 @@ __device__ bool la_filter(const Reach& r, const LaView& f2, const StateCtx& c, c
   if (lweight == INF) return false;  // zero() futures are not allowed
   a2.w = wtimes(a2.w, lweight);
   a2.w -= c.fs.fweight;                                           // divide_assign, tropical_weight.rs:128-131
-  const float q = floorf((lweight / KDELTA_F) + 0.5f) * KDELTA_F;  // quantize, semiring.rs:132-145 (lweight is finite)
+  const float q = floorf((lweight / KDELTA) + 0.5f) * KDELTA;  // quantize, semiring.rs:132-145 (lweight is finite)
   // PushLabelsComposeFilter::filter_tr :193-222 + push_label_filter_tr :339-400
   if (!la_tr || a2.ol != 0u || !has_prefix) {
     *out = FState{f, q, NO_LABEL};

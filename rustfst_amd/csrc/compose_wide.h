@@ -22,8 +22,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.h"
 
 namespace wfst {
@@ -66,7 +64,6 @@ template <class T>
 __device__ __forceinline__ void st_l2(T* p, T v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
 __device__ __forceinline__ uint32_t hash_128(uint64_t lo, uint64_t hi) {
   uint64_t h = lo ^ (hi * 0x9E3779B97F4A7C15ull);
   h ^= h >> 33;
@@ -584,9 +581,6 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
   WideBuffers w;
   wide_alloc(ctx, est_s, est_a, w);
   DBuf<WideCtl> d_ctl(*ctx->pool, 1);
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, w.ar.seg_cnt, w.d_off, 0u, (size_t)0x7FFFFFF0u, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
   struct HostCtl {
     uint32_t head[WIDE_CTL_HEAD / 4];  // status, k_done, pad, lvl ring
     uint32_t n_arcs;
@@ -693,7 +687,7 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
   }
   const uint32_t n_states = hi;
   HIP_CHECK(hipMemsetAsync(w.ar.seg_cnt + n_states, 0, sizeof(uint32_t), st));
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, w.ar.seg_cnt, w.d_off, 0u, (size_t)n_states + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, w.ar.seg_cnt, w.d_off, (size_t)n_states + 1);
   la_gather<G><<<std::min<uint32_t>(max_blocks, (n_states + SPB - 1) / SPB), 256, 0, st>>>(w.ar, w.d_off, w.d_out, n_states, patch_from);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(&hc->n_arcs, w.d_off + n_states, sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -254,10 +254,7 @@ wfst_fst* connect_and_adopt(wfst_ctx* ctx, uint32_t n, int64_t start, const uint
   }
   // stable renumbering of the survivors (del_states, mutable_fst.rs:132-158)
   HIP_CHECK(hipMemsetAsync(co.p + n, 0, sizeof(uint32_t), st));
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, co.p, new_id.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, co.p, new_id.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, co.p, new_id.p, (size_t)n + 1);
   HIP_CHECK(hipMemsetAsync(cnt.p, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
   kept_arc_counts<<<blocks, 256, 0, st>>>(off, arcs, co.p, new_id.p, cnt.p, n);
   HIP_CHECK(hipMemcpyAsync(h + 1, new_id.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -268,7 +265,7 @@ wfst_fst* connect_and_adopt(wfst_ctx* ctx, uint32_t n, int64_t start, const uint
   // the start state survives iff it reaches a final state; if it does not, nothing accessible does: everything goes
   if (t_states == 0 || !h[0]) return empty();
   const int64_t t_start = h[3];
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, cnt.p, t_off.p, 0u, (size_t)t_states + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp2 = exclusive_scan_u32(ctx, cnt.p, t_off.p, (size_t)t_states + 1);
   HIP_CHECK(hipMemcpyAsync(h + 2, t_off.p + t_states, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   const uint32_t t_arcs_n = h[2];

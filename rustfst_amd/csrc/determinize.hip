@@ -32,10 +32,11 @@
 #include <cstring>
 #include <vector>
 
+#pragma clang fp contract(off)  // (before tropical.h comes in: its functions compile without contraction here too)
+
 #include "common.h"
 #include "fst_props.h"
 
-#pragma clang fp contract(off)
 
 namespace wfst {
 
@@ -53,14 +54,6 @@ constexpr uint32_t NARROW_LEVELS_PER_LAUNCH = 1u << 16;
 #ifndef WFST_DETERMINIZE_BATCH_LDS_DEFAULT
 #define WFST_DETERMINIZE_BATCH_LDS_DEFAULT false
 #endif
-
-__device__ __host__ inline float wplus(float a, float b) { return b < a ? b : a; }  // plus_assign (exact <)
-__device__ __host__ inline float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
-__device__ inline float quantize(float v, float delta) {  // semiring.rs:132-145
-  if (__builtin_isinf(v)) return v;
-  return floorf((v / delta) + 0.5f) * delta;
-}
-__device__ inline bool weq(float a, float b) { return a <= b + props::KDELTA && b <= a + props::KDELTA; }
 
 struct Ctl {
   uint32_t lo, hi;   // the level to expand: states [lo, hi)
@@ -674,13 +667,6 @@ __global__ void __launch_bounds__(TPB) det_rehash_kernel(const uint64_t* okey, c
   }
 }
 
-uint32_t pow2_at_least(uint64_t x) {
-  uint64_t p = 64;
-  while (p < x) p <<= 1;
-  if (p > 0x80000000ull) throw Error("determinize: tables beyond 2^31 entries");
-  return (uint32_t)p;
-}
-
 template <class T>
 void grow(DevicePool& pool, DBuf<T>& b, size_t n, size_t keep, hipStream_t st) {
   if (b.p && b.n >= n) return;
@@ -734,11 +720,11 @@ struct Run {
       for (DBuf<uint32_t>* b : {&cst, &cdest, &cslot}) grow(pool, *b, nc, 0, st);
       for (DBuf<uint64_t>* b : {&chash, &sc1, &sc2}) grow(pool, *b, nc + 1, 0, st);
       cap.cands = (uint32_t)nc;
-      cap.ltab = pow2_at_least(2 * nc);
+      cap.ltab = pow2_at_least(2 * nc, "determinize");
       grow(pool, lkey, cap.ltab, 0, st);
       grow(pool, lead, 2 * (size_t)cap.ltab, 0, st);
     }
-    const uint32_t slots = pow2_at_least(2 * (uint64_t)cap.states);
+    const uint32_t slots = pow2_at_least(2 * (uint64_t)cap.states, "determinize");
     if (slots > cap.slots) {
       DBuf<uint64_t> nk(pool, slots);
       DBuf<uint32_t> nh(pool, slots);
@@ -936,7 +922,7 @@ size_t carve_slice(unsigned char* base, size_t at, const Slice& sl, const wfst_f
     at += (bytes + 63) & ~(size_t)63;
     return base ? base + o : nullptr;
   };
-  const uint32_t slots = pow2_at_least(2 * sl.states), ltab = pow2_at_least(2 * sl.cands);
+  const uint32_t slots = pow2_at_least(2 * sl.states, "determinize"), ltab = pow2_at_least(2 * sl.cands, "determinize");
   Det v{};
   v.so = (uint32_t*)take(4 * (sl.states + 1));
   v.aoff = (uint32_t*)take(4 * (sl.states + 1));

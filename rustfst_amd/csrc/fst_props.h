@@ -5,8 +5,16 @@
 #include <cstdint>
 
 #include "../../include/wfst.h"
+#include "tropical.h"
 
 namespace wfst::props {
+
+// TropicalWeight's approximate ==, is_zero / is_one and "weighted" (tropical.h) decide the WEIGHTED / UNWEIGHTED bits
+using wfst::is_one;
+using wfst::is_zero;
+using wfst::KDELTA;
+using wfst::weighted;
+using wfst::weq;
 
 constexpr uint64_t ACCEPTOR = 0x0000000000010000ull, NOT_ACCEPTOR = 0x0000000000020000ull;
 constexpr uint64_t I_DETERMINISTIC = 0x0000000000040000ull, NOT_I_DETERMINISTIC = 0x0000000000080000ull;
@@ -31,8 +39,6 @@ constexpr uint64_t STATIC_BITS = 0x3;
 constexpr uint64_t NULL_PROPS = ACCEPTOR | I_DETERMINISTIC | O_DETERMINISTIC | NO_EPSILONS | NO_I_EPSILONS |
                                 NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | UNWEIGHTED | ACYCLIC |
                                 INITIAL_ACYCLIC | TOP_SORTED | ACCESSIBLE | COACCESSIBLE | STRING | UNWEIGHTED_CYCLES;
-
-constexpr uint64_t LABEL_INVARIANT_COMMON = 0;  // (unused; kept for readability of masks below)
 
 // preserved-by masks: properties.rs:166-300
 constexpr uint64_t SET_START_MASK = ACCEPTOR | NOT_ACCEPTOR | I_DETERMINISTIC | NOT_I_DETERMINISTIC | O_DETERMINISTIC |
@@ -60,13 +66,6 @@ constexpr uint64_t DELETE_STATES_MASK = ACCEPTOR | I_DETERMINISTIC | O_DETERMINI
                                         NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | UNWEIGHTED | ACYCLIC |
                                         INITIAL_ACYCLIC | TOP_SORTED | UNWEIGHTED_CYCLES;
 
-// TropicalWeight::{is_zero,is_one} use the approximate == (semirings/semiring.rs:68-73,159-168); they
-// only feed the WEIGHTED/UNWEIGHTED bits here, so the reference tolerance is kept for bit-parity.
-constexpr float KDELTA = 1.0f / 1024.0f;
-inline bool approx_eq(float a, float b) { return a <= b + KDELTA && b <= a + KDELTA; }
-inline bool is_zero(float w) { return approx_eq(w, __builtin_huge_valf()); }
-inline bool is_one(float w) { return approx_eq(w, 0.0f); }
-
 inline uint64_t set_start(uint64_t in) {  // mutate_properties.rs:7-13
   uint64_t out = in & SET_START_MASK;
   if (in & ACYCLIC) out |= INITIAL_ACYCLIC;
@@ -74,8 +73,8 @@ inline uint64_t set_start(uint64_t in) {  // mutate_properties.rs:7-13
 }
 inline uint64_t set_final(uint64_t in, const float* old_w, const float* new_w) {  // :15-37
   uint64_t out = in;
-  if (old_w && !is_zero(*old_w) && !is_one(*old_w)) out &= ~WEIGHTED;
-  if (new_w && !is_zero(*new_w) && !is_one(*new_w)) {
+  if (old_w && weighted(*old_w)) out &= ~WEIGHTED;
+  if (new_w && weighted(*new_w)) {
     out |= WEIGHTED;
     out &= ~UNWEIGHTED;
   }
@@ -94,7 +93,7 @@ inline uint64_t add_tr(uint64_t in, uint32_t state, const wfst_tr& tr, const wfs
     if (prev->ilabel > tr.ilabel) out = (out | NOT_I_LABEL_SORTED) & ~I_LABEL_SORTED;
     if (prev->olabel > tr.olabel) out = (out | NOT_O_LABEL_SORTED) & ~O_LABEL_SORTED;
   }
-  if (!is_zero(tr.weight) && !is_one(tr.weight)) out = (out | WEIGHTED) & ~UNWEIGHTED;
+  if (weighted(tr.weight)) out = (out | WEIGHTED) & ~UNWEIGHTED;
   if (tr.nextstate <= state) out = (out | NOT_TOP_SORTED) & ~TOP_SORTED;
   out &= ADD_ARC_MASK | ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED |
          UNWEIGHTED | TOP_SORTED;
@@ -103,22 +102,59 @@ inline uint64_t add_tr(uint64_t in, uint32_t state, const wfst_tr& tr, const wfs
 }
 // add_tr over a whole SET of arcs at once.  Every effect of add_tr is a sticky set/clear decided by one fact about the arc,
 // followed by a mask that is the same for every arc, so folding add_tr over any number of arcs (in any order) equals one
-// application with the union of their facts.  facts: 1 il != ol | 2 il == 0 | 4 il == 0 && ol == 0 | 8 ol == 0 |
-// 16 ilabel below its predecessor's | 32 olabel below its predecessor's | 64 weight neither zero nor one | 128 nextstate <= state
+// application with the union of their facts.
+constexpr uint32_t FACT_NOT_ACCEPTOR = 1u;      // ilabel != olabel
+constexpr uint32_t FACT_I_EPSILON = 2u;         // ilabel == 0
+constexpr uint32_t FACT_EPSILON = 4u;           // ilabel == 0 && olabel == 0
+constexpr uint32_t FACT_O_EPSILON = 8u;         // olabel == 0
+constexpr uint32_t FACT_NOT_I_SORTED = 16u;     // ilabel below its predecessor's
+constexpr uint32_t FACT_NOT_O_SORTED = 32u;     // olabel below its predecessor's
+constexpr uint32_t FACT_WEIGHTED = 64u;         // arc weight neither zero nor one
+constexpr uint32_t FACT_NOT_TOP_SORTED = 128u;  // nextstate <= state
+constexpr uint32_t FACT_FINAL_WEIGHTED = 256u;  // a final weight that is not one (no arc fact: minimize.hip's content scan)
+// the facts arc `a` of `state` contributes; prev = the arc before it in the state's list (nullptr: no label-order facts)
+WFST_HD inline uint32_t arc_facts(const wfst_tr& a, const wfst_tr* prev, uint32_t state) {
+  uint32_t facts = (a.ilabel != a.olabel ? FACT_NOT_ACCEPTOR : 0u) | (a.ilabel == WFST_EPS_LABEL ? FACT_I_EPSILON : 0u) |
+                   (a.ilabel == WFST_EPS_LABEL && a.olabel == WFST_EPS_LABEL ? FACT_EPSILON : 0u) |
+                   (a.olabel == WFST_EPS_LABEL ? FACT_O_EPSILON : 0u) | (weighted(a.weight) ? FACT_WEIGHTED : 0u) |
+                   (a.nextstate <= state ? FACT_NOT_TOP_SORTED : 0u);
+  if (prev) facts |= (prev->ilabel > a.ilabel ? FACT_NOT_I_SORTED : 0u) | (prev->olabel > a.olabel ? FACT_NOT_O_SORTED : 0u);
+  return facts;
+}
 inline uint64_t add_trs_by_facts(uint64_t in, uint32_t facts) {
   uint64_t out = in;
-  if (facts & 1u) out = (out | NOT_ACCEPTOR) & ~ACCEPTOR;
-  if (facts & 2u) out = (out | I_EPSILONS) & ~NO_I_EPSILONS;
-  if (facts & 4u) out = (out | EPSILONS) & ~NO_EPSILONS;
-  if (facts & 8u) out = (out | O_EPSILONS) & ~NO_O_EPSILONS;
-  if (facts & 16u) out = (out | NOT_I_LABEL_SORTED) & ~I_LABEL_SORTED;
-  if (facts & 32u) out = (out | NOT_O_LABEL_SORTED) & ~O_LABEL_SORTED;
-  if (facts & 64u) out = (out | WEIGHTED) & ~UNWEIGHTED;
-  if (facts & 128u) out = (out | NOT_TOP_SORTED) & ~TOP_SORTED;
+  if (facts & FACT_NOT_ACCEPTOR) out = (out | NOT_ACCEPTOR) & ~ACCEPTOR;
+  if (facts & FACT_I_EPSILON) out = (out | I_EPSILONS) & ~NO_I_EPSILONS;
+  if (facts & FACT_EPSILON) out = (out | EPSILONS) & ~NO_EPSILONS;
+  if (facts & FACT_O_EPSILON) out = (out | O_EPSILONS) & ~NO_O_EPSILONS;
+  if (facts & FACT_NOT_I_SORTED) out = (out | NOT_I_LABEL_SORTED) & ~I_LABEL_SORTED;
+  if (facts & FACT_NOT_O_SORTED) out = (out | NOT_O_LABEL_SORTED) & ~O_LABEL_SORTED;
+  if (facts & FACT_WEIGHTED) out = (out | WEIGHTED) & ~UNWEIGHTED;
+  if (facts & FACT_NOT_TOP_SORTED) out = (out | NOT_TOP_SORTED) & ~TOP_SORTED;
   out &= ADD_ARC_MASK | ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED |
          UNWEIGHTED | TOP_SORTED;
   if (out & TOP_SORTED) out |= ACYCLIC | INITIAL_ACYCLIC;
   return out;
+}
+// the label / weight part of compute_fst_properties' word (compute_fst_properties.rs:60-190) from the facts of ALL arcs
+// and final weights.  The STRING pair is left out (minimize.hip, its only user, never keeps either bit).
+inline uint64_t content_props(uint32_t facts) {
+  uint64_t p = 0;
+  p |= (facts & FACT_NOT_ACCEPTOR) ? NOT_ACCEPTOR : ACCEPTOR;
+  p |= (facts & FACT_I_EPSILON) ? I_EPSILONS : NO_I_EPSILONS;
+  p |= (facts & FACT_EPSILON) ? EPSILONS : NO_EPSILONS;
+  p |= (facts & FACT_O_EPSILON) ? O_EPSILONS : NO_O_EPSILONS;
+  p |= (facts & FACT_NOT_I_SORTED) ? NOT_I_LABEL_SORTED : I_LABEL_SORTED;
+  p |= (facts & FACT_NOT_O_SORTED) ? NOT_O_LABEL_SORTED : O_LABEL_SORTED;
+  p |= (facts & (FACT_WEIGHTED | FACT_FINAL_WEIGHTED)) ? WEIGHTED : UNWEIGHTED;
+  p |= (facts & FACT_NOT_TOP_SORTED) ? NOT_TOP_SORTED : TOP_SORTED;
+  return p;
+}
+// set_properties_with_mask(comp, known_properties(comp)) (mutable_fst.rs:435-441, utils.rs:4-9)
+inline uint64_t merge_computed(uint64_t p, uint64_t comp) {
+  const uint64_t pos = 0x5555555555555555ull & ALL, neg = 0xAAAAAAAAAAAAAAAAull & ALL;
+  const uint64_t known = (comp & ALL) | ((comp & pos) << 1) | ((comp & neg) >> 1);
+  return (p & ~known) | comp;
 }
 // reverse_properties (mutate_properties.rs:622-638)
 inline uint64_t reverse(uint64_t inprops, bool has_superinitial) {
@@ -151,7 +187,7 @@ inline uint64_t shortest_path(uint64_t p, bool tree) {  // :662-672
 // Property word of the linear FST single_shortest_path_backtrace builds (shortest_path.rs:241-282): state 0 final,
 // state k >= 1 carries the single arc path_arcs[k-1] into state k-1, start = hops; the reference's incremental
 // add_state / set_final / add_tr / set_start bookkeeping, then shortest_path_properties(.., true).
-// add_tr(add_state(p), arc) is a pure function of (p, the five facts the arc contributes).  Arcs are processed in
+// add_tr(add_state(p), arc) is a pure function of (p, the facts the arc contributes).  Arcs are processed in
 // runs of equal facts; inside a run the word reaches a fixed point after a step or two (add_state(out) == in), and
 // the rest of the run is skipped — the result is exactly the incremental one.
 inline uint64_t linear_path_props(bool has_path, uint32_t hops, float final_weight, const wfst_tr* path_arcs) {
@@ -159,12 +195,7 @@ inline uint64_t linear_path_props(bool has_path, uint32_t hops, float final_weig
   if (has_path) {
     p = add_state(p);
     p = set_final(p, nullptr, &final_weight);
-    auto facts_of = [&](uint32_t k) {  // arc of state k
-      const wfst_tr& tr = path_arcs[k - 1];
-      const bool weighted = !is_zero(tr.weight) && !is_one(tr.weight);
-      return (tr.ilabel != tr.olabel ? 1u : 0u) | (tr.ilabel == WFST_EPS_LABEL ? 2u : 0u) |
-             (tr.olabel == WFST_EPS_LABEL ? 4u : 0u) | (weighted ? 8u : 0u) | (tr.nextstate <= k ? 16u : 0u);
-    };
+    auto facts_of = [&](uint32_t k) { return arc_facts(path_arcs[k - 1], nullptr, k); };  // arc of state k
     uint32_t k = 1;
     while (k <= hops) {
       const uint32_t f = facts_of(k);
@@ -182,18 +213,16 @@ inline uint64_t linear_path_props(bool has_path, uint32_t hops, float final_weig
   return shortest_path(p, true) & ALL;
 }
 
-// The same word from the UNION of the arcs' facts, in add_trs_by_facts's encoding (1 il != ol | 2 il == 0 | 4 il == 0 and
-// ol == 0 | 8 ol == 0 | 64 weighted | 128 nextstate <= state; a path's states have one arc each: no label-order facts).
+// The same word from the UNION of the arcs' facts (a path's states have one arc each: no label-order facts).
 // Every effect of add_tr is a sticky set / clear decided by one fact, followed by masks that are the same for every
 // arc: the order of the arcs does not matter, and three applications of the union reach the fixed point.  The
 // string o T kernel ORs the facts of a path's arcs while it writes them (compose.hip: Result::facts), so that the host
 // does not read the arcs back to know the properties; tests/test_host.py (props_check) compares this function with
 // linear_path_props on every fact sequence of up to four arcs.
 constexpr uint32_t PATH_FACTS_NONE = 0xFFFFFFFFu;  // the kernel did not provide them: scan the arcs
-inline uint32_t path_arc_facts(uint32_t ilabel, uint32_t olabel, float weight) {
-  return (ilabel != olabel ? 1u : 0u) | (ilabel == WFST_EPS_LABEL ? 2u : 0u) |
-         (ilabel == WFST_EPS_LABEL && olabel == WFST_EPS_LABEL ? 4u : 0u) | (olabel == WFST_EPS_LABEL ? 8u : 0u) |
-         (!is_zero(weight) && !is_one(weight) ? 64u : 0u) | 128u;
+// (arc k of a backtraced path leaves state k + 1 for state k: FACT_NOT_TOP_SORTED whatever the ids are)
+WFST_HD inline uint32_t path_arc_facts(uint32_t ilabel, uint32_t olabel, float weight) {
+  return arc_facts(wfst_tr{ilabel, olabel, weight, 1u}, nullptr, 0u) | FACT_NOT_TOP_SORTED;
 }
 inline uint64_t linear_path_props_from_facts(bool has_path, uint32_t hops, float final_weight, uint32_t facts_union) {
   uint64_t p = NULL_PROPS;
@@ -237,7 +266,6 @@ inline uint64_t project(uint64_t in, bool project_output) {
 // set_weight_unchecked keeps the label / epsilon bits and WEIGHTED / UNWEIGHTED only
 constexpr uint64_t ARC_RELEVANT = ACCEPTOR | NOT_ACCEPTOR | EPSILONS | NO_EPSILONS | I_EPSILONS | NO_I_EPSILONS | O_EPSILONS |
                                   NO_O_EPSILONS | WEIGHTED | UNWEIGHTED;
-inline bool weighted(float w) { return !is_zero(w) && !is_one(w); }
 // TrsIterMut::set_weight_unchecked -> compute_new_properties_weights (trs_iter_mut.rs:210-215, 279-291, 342-350)
 inline uint64_t set_weight(uint64_t in, float old_w, float new_w) {
   uint64_t out = in;

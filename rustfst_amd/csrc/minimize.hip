@@ -32,12 +32,10 @@
 #include <memory>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
+#pragma clang fp contract(off)  // (before tropical.h comes in: its functions compile without contraction here too)
 
 #include "common.h"
 #include "fst_props.h"
-
-#pragma clang fp contract(off)
 
 namespace wfst {
 
@@ -55,21 +53,7 @@ constexpr uint64_t HI32 = 0xFFFFFFFF00000000ull;
 // ctl words
 constexpr uint32_t C_LO = 0, C_HI = 1, C_TAIL = 2, C_LEVEL = 3, C_CURMAX = 4, C_NEXTMAX = 5, C_NBIG = 6, C_WORDS = 8;
 
-__device__ inline float quantize(float v, float delta) {  // semiring.rs:132-145
-  if (__builtin_isinf(v)) return v;
-  return floorf((v / delta) + 0.5f) * delta;
-}
-__device__ inline bool weq(float a, float b) { return a <= b + props::KDELTA && b <= a + props::KDELTA; }
-__device__ inline bool wweighted(float w) { return !weq(w, INF) && !weq(w, 0.0f); }
 __device__ inline uint32_t wkey(float f) { return f == 0.0f ? 0u : __float_as_uint(f); }  // -0.0 == +0.0
-__device__ inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 // words that other lanes of the SAME launch wrote (narrow regime: level after level in one workgroup): device-scope
 // accesses, which do not stay in a compute unit's vector L1
 __device__ inline uint32_t ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -99,9 +83,7 @@ __device__ inline uint32_t set_insert(unsigned long long* keys, uint32_t mask, u
 }
 
 // ---------------------------------------------------------------- facts of the content (compute_fst_properties.rs:60-190)
-// 16 lanes per state.  bits as props::add_trs_by_facts: 1 il != ol | 2 il == 0 | 4 il == 0 && ol == 0 | 8 ol == 0 |
-// 16 ilabel below its predecessor's | 32 olabel below its predecessor's | 64 arc weight neither zero nor one |
-// 128 nextstate <= state; and 256 a final weight that is not one
+// 16 lanes per state.  The union of props::arc_facts over every arc, and FACT_FINAL_WEIGHTED for a final weight that is not one
 __global__ void __launch_bounds__(TPB) facts_kernel(const uint32_t* __restrict__ off, const wfst_tr* __restrict__ arcs,
                                                     const float* __restrict__ fin, uint32_t n, uint32_t* __restrict__ out) {
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -111,20 +93,11 @@ __global__ void __launch_bounds__(TPB) facts_kernel(const uint32_t* __restrict__
     const uint32_t b = off[s], e = off[s + 1];
     for (uint32_t i = b + lane; i < e; i += 16) {
       const wfst_tr a = arcs[i];
-      if (a.ilabel != a.olabel) facts |= 1u;
-      if (a.ilabel == 0u) facts |= 2u;
-      if (a.ilabel == 0u && a.olabel == 0u) facts |= 4u;
-      if (a.olabel == 0u) facts |= 8u;
-      if (i > b) {
-        if (a.ilabel < arcs[i - 1].ilabel) facts |= 16u;
-        if (a.olabel < arcs[i - 1].olabel) facts |= 32u;
-      }
-      if (wweighted(a.weight)) facts |= 64u;
-      if (a.nextstate <= s) facts |= 128u;
+      facts |= props::arc_facts(a, i > b ? &arcs[i - 1] : nullptr, s);
     }
     if (lane == 0) {
       const float f = fin[s];
-      if (f != INF && !weq(f, 0.0f)) facts |= 256u;
+      if (f != INF && !is_one(f)) facts |= props::FACT_FINAL_WEIGHTED;
     }
   }
   for (int d = 32; d >= 1; d >>= 1) facts |= __shfl_xor(facts, d);
@@ -195,7 +168,8 @@ __global__ void rank_kernel(wfst_tr* __restrict__ enc, uint32_t e2, const uint32
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < e2) enc[i].olabel = minpos[enc[i].olabel];
 }
-// label order / topological order of the encoded FST (only asked for when connect leaves nothing): 16 | 128 as above
+// label order / topological order of the encoded FST (only asked for when connect leaves nothing): FACT_NOT_I_SORTED (its labels
+// are equal pairs, carried in olabel) | FACT_NOT_TOP_SORTED
 __global__ void __launch_bounds__(TPB) enc_facts_kernel(const uint32_t* __restrict__ off2, const wfst_tr* __restrict__ enc,
                                                         uint32_t n, uint32_t* __restrict__ out) {
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,18 +177,14 @@ __global__ void __launch_bounds__(TPB) enc_facts_kernel(const uint32_t* __restri
   uint32_t facts = 0;
   for (uint32_t s = tid >> 4; s < n; s += (gridDim.x * blockDim.x) >> 4)
     for (uint32_t i = off2[s] + lane; i < off2[s + 1]; i += 16) {
-      if (i > off2[s] && enc[i].olabel < enc[i - 1].olabel) facts |= 16u;
-      if (enc[i].nextstate <= s) facts |= 128u;
+      if (i > off2[s] && enc[i].olabel < enc[i - 1].olabel) facts |= props::FACT_NOT_I_SORTED;
+      if (enc[i].nextstate <= s) facts |= props::FACT_NOT_TOP_SORTED;
     }
   for (int d = 32; d >= 1; d >>= 1) facts |= __shfl_xor(facts, d);
   if ((threadIdx.x & 63) == 0 && facts) atomicOr(out, facts);
 }
 
 // ---------------------------------------------------------------- transpose
-__global__ void indegree_kernel(const wfst_tr* __restrict__ arcs, uint64_t n_arcs, uint32_t* __restrict__ indeg) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_arcs; i += (uint64_t)gridDim.x * blockDim.x)
-    atomicAdd(&indeg[arcs[i].nextstate], 1u);
-}
 __global__ void __launch_bounds__(TPB) transpose_fill_kernel(const uint32_t* __restrict__ off, const wfst_tr* __restrict__ arcs,
                                                              uint32_t n, const uint32_t* __restrict__ roff,
                                                              uint32_t* __restrict__ cursor, uint32_t* __restrict__ rsrc) {
@@ -508,10 +478,6 @@ __global__ void __launch_bounds__(TPB) emit_kernel(const uint32_t* __restrict__ 
   }
 }
 
-__global__ void fill_u32_kernel(uint32_t* __restrict__ p, size_t n, uint32_t v) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
 // ---------------------------------------------------------------- host side
 enum class Path { Auto, Narrow, Wide };
 Path path_knob() {
@@ -522,36 +488,13 @@ Path path_knob() {
   throw Error(std::string("WFST_MINIMIZE_PATH: expected auto, narrow or wide, not '") + e + "'");
 }
 
-struct HandleDeleter {
-  void operator()(wfst_fst* p) const {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    delete p;
-  }
-};
-using Handle = std::unique_ptr<wfst_fst, HandleDeleter>;
-
-uint32_t pow2_at_least(uint64_t v) {
-  uint64_t p = 64;
-  while (p < v) p <<= 1;
-  if (p > (1ull << 31)) throw Error("minimize: input too large");
-  return (uint32_t)p;
-}
 uint32_t grid16(wfst_ctx* ctx, uint32_t n) {  // 16 lanes per state
   return std::max<uint32_t>(1, std::min<uint32_t>((n + 15) / 16, (uint32_t)ctx->n_cus * 32));
 }
-void fill_u32(wfst_ctx* ctx, uint32_t* p, size_t n, uint32_t v) {
-  if (!n) return;
-  const uint32_t blocks = (uint32_t)std::min<size_t>((n + TPB - 1) / TPB, (size_t)ctx->n_cus * 32);
-  fill_u32_kernel<<<blocks, TPB, 0, ctx->stream>>>(p, n, v);
-  HIP_CHECK(hipGetLastError());
-}
-void exclusive_scan_u32(wfst_ctx* ctx, const uint32_t* in, uint32_t* out, size_t count) {
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, in, out, 0u, count, rocprim::plus<uint32_t>(), ctx->stream));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, in, out, 0u, count, rocprim::plus<uint32_t>(), ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));  // temp goes back to the pool
+// (the scratch goes back to the pool at once: synchronise first)
+void scan_sync(wfst_ctx* ctx, const uint32_t* in, uint32_t* out, size_t count) {
+  const DBuf<uint8_t> temp = exclusive_scan_u32(ctx, in, out, count);
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
 // facts of the content, gathered once
@@ -568,49 +511,25 @@ void content_facts(wfst_ctx* ctx, const wfst_fst* f, Facts& fa) {
     facts_kernel<<<grid16(ctx, f->n_states), TPB, 0, ctx->stream>>>(f->dev.offsets, f->dev.arcs, f->dev.finals, f->n_states, out.p);
     HIP_CHECK(hipGetLastError());
   }
-  HIP_CHECK(hipMemcpyAsync(&fa.bits, out.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  fa.bits = read_u32(ctx, out.p);
   fa.have = true;
 }
 void content_idet(wfst_ctx* ctx, const wfst_fst* f, Facts& fa) {
   if (fa.have_idet) return;
   uint32_t dup = 0;
   if (f->n_arcs > 1) {
-    const uint32_t size = pow2_at_least(2 * f->n_arcs);
+    const uint32_t size = pow2_at_least(2 * f->n_arcs, "minimize");
     DBuf<unsigned long long> keys(*ctx->pool, size);
     DBuf<uint32_t> out(*ctx->pool, 1);
     HIP_CHECK(hipMemsetAsync(keys.p, 0xFF, (size_t)size * sizeof(unsigned long long), ctx->stream));
     HIP_CHECK(hipMemsetAsync(out.p, 0, sizeof(uint32_t), ctx->stream));
     idet_kernel<<<grid16(ctx, f->n_states), TPB, 0, ctx->stream>>>(f->dev.offsets, f->dev.arcs, f->n_states, keys.p, size - 1, out.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(&dup, out.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    dup = read_u32(ctx, out.p);
   }
   fa.nondet = dup != 0;
   fa.have_idet = true;
 }
-// the label / weight part of compute_fst_properties' word (compute_fst_properties.rs:60-190) from the facts.  The STRING
-// pair is left out: no path through minimize keeps either bit (every branch ends behind a connect, whose mask drops them).
-uint64_t content_props(uint32_t bits) {
-  using namespace props;
-  uint64_t p = 0;
-  p |= (bits & 1u) ? NOT_ACCEPTOR : ACCEPTOR;
-  p |= (bits & 2u) ? I_EPSILONS : NO_I_EPSILONS;
-  p |= (bits & 4u) ? EPSILONS : NO_EPSILONS;
-  p |= (bits & 8u) ? O_EPSILONS : NO_O_EPSILONS;
-  p |= (bits & 16u) ? NOT_I_LABEL_SORTED : I_LABEL_SORTED;
-  p |= (bits & 32u) ? NOT_O_LABEL_SORTED : O_LABEL_SORTED;
-  p |= (bits & (64u | 256u)) ? WEIGHTED : UNWEIGHTED;
-  p |= (bits & 128u) ? NOT_TOP_SORTED : TOP_SORTED;
-  return p;
-}
-// set_properties_with_mask(comp, known_properties(comp)) (mutable_fst.rs:435-441, utils.rs:4-9)
-uint64_t merge_computed(uint64_t p, uint64_t comp) {
-  const uint64_t pos = 0x5555555555555555ull & props::ALL, neg = 0xAAAAAAAAAAAAAAAAull & props::ALL;
-  const uint64_t known = (comp & props::ALL) | ((comp & pos) << 1) | ((comp & neg) >> 1);
-  return (p & ~known) | comp;
-}
-
 struct CoreBufs {
   DBuf<uint32_t> rcnt, roff, rsrc, outdeg, order, ctl, cls, slot_of, smin, smax, big;
   DBuf<unsigned long long> tab;
@@ -630,12 +549,8 @@ void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t
   B.ctl = DBuf<uint32_t>(pool, C_WORDS);
   HIP_CHECK(hipMemsetAsync(B.rcnt.p, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
   HIP_CHECK(hipMemsetAsync(B.ctl.p, 0, C_WORDS * sizeof(uint32_t), st));
-  if (E) {
-    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((E + TPB - 1) / TPB, (uint64_t)ctx->n_cus * 8));
-    indegree_kernel<<<blocks, TPB, 0, st>>>(arcs, E, B.rcnt.p);
-    HIP_CHECK(hipGetLastError());
-  }
-  exclusive_scan_u32(ctx, B.rcnt.p, B.roff.p, (size_t)n + 1);
+  count_indegrees(ctx, arcs, E, B.rcnt.p);
+  scan_sync(ctx, B.rcnt.p, B.roff.p, (size_t)n + 1);
   HIP_CHECK(hipMemsetAsync(B.rcnt.p, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
   if (E) {
     transpose_fill_kernel<<<grid16(ctx, n), TPB, 0, st>>>(off, arcs, n, B.roff.p, B.rcnt.p, B.rsrc.p);
@@ -654,7 +569,7 @@ void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t
   c.by_olabel = by_olabel ? 1u : 0u;
   c.refine = refine ? 1u : 0u;
   if (refine) {
-    const uint32_t size = pow2_at_least(2 * (uint64_t)n);
+    const uint32_t size = pow2_at_least(2 * (uint64_t)n, "minimize");
     B.cls = DBuf<uint32_t>(pool, n);
     B.slot_of = DBuf<uint32_t>(pool, n);
     B.big = DBuf<uint32_t>(pool, n);
@@ -719,17 +634,14 @@ wfst_fst* minimize_connected(wfst_ctx* ctx, const wfst_fst* T, const wfst_tr* en
     HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), st));
     weight_check_kernel<<<(n + TPB - 1) / TPB, TPB, 0, st>>>(B.c, flag.p);
     HIP_CHECK(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (bad)
+    if (read_u32(ctx, flag.p))
       throw Error("minimize: an unweighted input whose merged states carry arc weights further than 1/1024 apart is not "
                   "supported (the reference keeps both arcs); use rustfst's minimize");
   }
   DBuf<uint32_t> keep(pool, (size_t)n + 1), new_id(pool, (size_t)n + 1);
   keep_kernel<<<(n + 1 + TPB - 1) / TPB, TPB, 0, st>>>(B.c.cls, n, superfinal, keep.p);
   HIP_CHECK(hipGetLastError());
-  exclusive_scan_u32(ctx, keep.p, new_id.p, (size_t)n + 1);
+  scan_sync(ctx, keep.p, new_id.p, (size_t)n + 1);
   uint32_t n_out = 0, start_cls = 0;
   HIP_CHECK(hipMemcpyAsync(&n_out, new_id.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(&start_cls, B.c.cls + T->start, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -740,10 +652,8 @@ wfst_fst* minimize_connected(wfst_ctx* ctx, const wfst_fst* T, const wfst_tr* en
   HIP_CHECK(hipMemsetAsync(cnt.p, 0, ((size_t)n_out + 1) * sizeof(uint32_t), st));
   emit_count_kernel<<<grid16(ctx, n), TPB, 0, st>>>(T->dev.offsets, T->dev.arcs, n, superfinal, keep.p, new_id.p, cnt.p);
   HIP_CHECK(hipGetLastError());
-  exclusive_scan_u32(ctx, cnt.p, off_out.p, (size_t)n_out + 1);
-  uint32_t e_out = 0;
-  HIP_CHECK(hipMemcpyAsync(&e_out, off_out.p + n_out, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  scan_sync(ctx, cnt.p, off_out.p, (size_t)n_out + 1);
+  const uint32_t e_out = read_u32(ctx, off_out.p + n_out);
   DBuf<wfst_tr> arcs_out(pool, e_out);
   DBuf<float> fin_out(pool, n_out);
   emit_kernel<<<grid16(ctx, n), TPB, 0, st>>>(T->dev.offsets, T->dev.arcs, T->dev.finals, n, superfinal, keep.p, new_id.p, B.c.cls,
@@ -861,15 +771,13 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
   DBuf<float> fin2(pool, (size_t)np + 1);
   final_flags_kernel<<<(np + 2 + TPB - 1) / TPB, TPB, 0, st>>>(P->dev.finals, np, flag.p);
   HIP_CHECK(hipGetLastError());
-  exclusive_scan_u32(ctx, flag.p, fcnt.p, (size_t)np + 2);
+  scan_sync(ctx, flag.p, fcnt.p, (size_t)np + 2);
   enc_offsets_kernel<<<(np + 1 + TPB - 1) / TPB, TPB, 0, st>>>(P->dev.offsets, fcnt.p, np, off2.p, fin2.p);
   HIP_CHECK(hipGetLastError());
-  uint32_t e2 = 0;
-  HIP_CHECK(hipMemcpyAsync(&e2, off2.p + np, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  const uint32_t e2 = read_u32(ctx, off2.p + np);
   DBuf<wfst_tr> enc(pool, e2);
   {
-    const uint32_t size = pow2_at_least(2 * (uint64_t)e2);
+    const uint32_t size = pow2_at_least(2 * (uint64_t)e2, "minimize");
     DBuf<unsigned long long> keys(pool, size);
     DBuf<uint32_t> minpos(pool, size);
     HIP_CHECK(hipMemsetAsync(keys.p, 0xFF, (size_t)size * sizeof(unsigned long long), st));
@@ -890,12 +798,10 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
     HIP_CHECK(hipMemsetAsync(out.p, 0, sizeof(uint32_t), st));
     enc_facts_kernel<<<grid16(ctx, np + 1), TPB, 0, st>>>(off2.p, enc.p, np + 1, out.p);
     HIP_CHECK(hipGetLastError());
-    uint32_t bits = 0;
-    HIP_CHECK(hipMemcpyAsync(&bits, out.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    const uint32_t bits = read_u32(ctx, out.p);
     uint64_t comp = ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | UNWEIGHTED | ACYCLIC | INITIAL_ACYCLIC | UNWEIGHTED_CYCLES;
-    if (!(bits & 16u)) comp |= I_LABEL_SORTED | O_LABEL_SORTED;
-    if (!(bits & 128u)) comp |= TOP_SORTED;
+    if (!(bits & FACT_NOT_I_SORTED)) comp |= I_LABEL_SORTED | O_LABEL_SORTED;
+    if (!(bits & FACT_NOT_TOP_SORTED)) comp |= TOP_SORTED;
     return empty_fst(ctx, delete_states(comp) | ACCESSIBLE | COACCESSIBLE);
   }
   tr_sort_device(ctx, T.get(), false);  // tr_sort(ILabelCompare) on the encode labels (olabel carries their order)

@@ -43,30 +43,7 @@ struct NbOut {
   uint64_t payload;  // byte offset inside the pinned payload area: offsets[n_states + 1] | finals[n_states] | arcs[n_arcs]
 };
 
-__device__ __forceinline__ uint32_t nb_enc(float f) {
-  uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float nb_dec(uint32_t e) {
-  uint32_t b = (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e;
-  return __uint_as_float(b);
-}
-// TropicalWeight with the reference's semantics (tropical_weight.rs:26-171, semiring.rs:159-168)
-__device__ __forceinline__ float nb_plus(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float nb_times(float a, float b) { return a == INF ? a : (b == INF ? b : (a + b) + 0.0f); }
-__device__ __forceinline__ bool nb_weq(float a, float b) { return a <= b + props::KDELTA && b <= a + props::KDELTA; }
-__device__ __forceinline__ bool nb_is_zero(float w) { return nb_weq(w, INF); }
-__device__ __forceinline__ bool nb_is_one(float w) { return nb_weq(w, 0.0f); }
-__device__ __forceinline__ bool nb_approx_equal(float a, float b, float delta) { return fabsf(a - b) <= delta; }
-__device__ __forceinline__ bool nb_natural_less(float w1, float w2) {  // shortest_path.rs:284-286
-  return nb_weq(nb_plus(w1, w2), w1) && !nb_weq(w1, w2);
-}
-// add_tr's facts (fst_props.h add_trs_by_facts)
-__device__ __forceinline__ uint32_t nb_facts(const wfst_tr& tr, uint32_t state) {
-  const bool weighted = !nb_is_zero(tr.weight) && !nb_is_one(tr.weight);
-  return (tr.ilabel != tr.olabel ? 1u : 0u) | (tr.ilabel == 0u ? 2u : 0u) | (tr.ilabel == 0u && tr.olabel == 0u ? 4u : 0u) |
-         (tr.olabel == 0u ? 8u : 0u) | (weighted ? 64u : 0u) | (tr.nextstate <= state ? 128u : 0u);
-}
+// TropicalWeight: tropical.h.  The kernels here multiply with nb_times, (a + b) + 0.0f, NOT with wtimes.
 
 // scratch slice of one problem (global memory), T = tree capacity:
 //   dist2[n + 1] f32 | roff[n + 2] u32 | rarcs[n_arcs] wfst_tr | super[n] {state + 1, weight} | rcount[n + 2] u32 |
@@ -125,7 +102,7 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
   }
 
   // ---- 1. forward distances: the exact (min,+) fixed point (f32 + is monotone: unique whatever the order)
-  for (uint32_t s = lane; s < n; s += 64) l_dist[s] = s == (uint32_t)pr.start ? nb_enc(0.0f) : nb_enc(INF);
+  for (uint32_t s = lane; s < n; s += 64) l_dist[s] = s == (uint32_t)pr.start ? f32_key(0.0f) : f32_key(INF);
   __syncthreads();
   for (uint32_t round = 0;; ++round) {
     if (round > n + 1u) {  // more rounds than states: only a negative cycle does that (the driver excludes negative weights,
@@ -134,20 +111,20 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
     }
     bool changed = false;
     for (uint32_t s = lane; s < n; s += 64) {
-      const float ds = nb_dec(l_dist[s]);
+      const float ds = key_f32(l_dist[s]);
       if (!(ds < INF)) continue;
       for (uint32_t k = pr.off[s]; k < pr.off[s + 1]; ++k) {
         const wfst_tr a = pr.arcs[k];
         const float c = (ds + a.weight) + 0.0f;
         if (!(c < INF)) continue;
-        const uint32_t e = nb_enc(c);
+        const uint32_t e = f32_key(c);
         if (e < l_dist[a.nextstate]) changed |= atomicMin(&l_dist[a.nextstate], e) > e;
       }
     }
     __syncthreads();
     if (!__any(changed)) break;
   }
-  for (uint32_t s = lane; s < n; s += 64) dist2[s + 1] = nb_dec(l_dist[s]);
+  for (uint32_t s = lane; s < n; s += 64) dist2[s + 1] = key_f32(l_dist[s]);
 
   // ---- 2. reverse: in-degrees, their exclusive scan, then the in-arcs in (source, position) order (one lane: the
   //         order IS the definition); the super-initial arcs: final states in state order
@@ -176,7 +153,7 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
       const float fw = pr.finals[s];
       if (fw != INF) {  // a final weight that is Some (and not zero: +inf is the absence marker)
         super[ns++] = make_uint2(s + 1, __float_as_uint(fw));
-        d = nb_plus(d, nb_times(fw, dist2[s + 1]));  // shortest_path.rs:143-153
+        d = wplus(d, nb_times(fw, dist2[s + 1]));  // shortest_path.rs:143-153
       }
     }
     dist2[0] = d;
@@ -188,7 +165,7 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
     s_pops = 0;
   }
   __syncthreads();
-  if (nb_is_zero(dist2[0])) {  // the start state of rfst is unreachable: FO::new()
+  if (is_zero(dist2[0])) {  // the start state of rfst is unreachable: FO::new()
     finish_empty();
     return;
   }
@@ -207,9 +184,9 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
     auto less = [&](uint32_t x, uint32_t y) {  // ShortestPathCompare::compare
       const float wx = hk[x], wy = hk[y];
       const bool sx = some[x] != 0, sy = some[y] != 0;
-      const bool nl = nb_natural_less(wy, wx);
-      if (!sx && sy) return nl || nb_approx_equal(wx, wy, delta);
-      if (sx && !sy) return nl && !nb_approx_equal(wx, wy, delta);
+      const bool nl = natural_less(wy, wx);
+      if (!sx && sy) return nl || approx_equal(wx, wy, delta);
+      if (sx && !sy) return nl && !approx_equal(wx, wy, delta);
       return nl;
     };
     auto push = [&](uint32_t v) {
@@ -258,7 +235,7 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
       hk[next] = key_of(st, w);
       some[next] = st != NB_NONE;
       o_arc[next] = arc;
-      facts |= nb_facts(arc, next);
+      facts |= props::arc_facts(arc, nullptr, next);
       push(next);
       return true;
     };
@@ -271,11 +248,11 @@ __global__ void __launch_bounds__(64) nbest_wave_kernel(const NbProb* __restrict
       const float pw = p_w[state];
       const uint32_t idx_r = ps == NB_NONE ? 0u : ps + 1u;  // p_first_real
       const float dd = ps == NB_NONE ? 0.0f : dist2[ps];
-      if (nb_natural_less(limit, nb_times(dd, pw))) continue;
+      if (natural_less(limit, nb_times(dd, pw))) continue;
       const uint32_t rc = ++rcount[idx_r];
       if (ps == NB_NONE) {
         const wfst_tr sa{0u, 0u, 0.0f, state};
-        facts |= nb_facts(sa, 0u);
+        facts |= props::arc_facts(sa, nullptr, 0u);
         start_arc[found++] = state;
       }
       if (ps == NB_NONE && rc == nshortest) break;
@@ -535,7 +512,7 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
   }
   const bool staged = sp1_staged(n, pr.n_arcs);
   for (uint32_t s = lane; s < n; s += 64) {
-    key[s] = s == (uint32_t)pr.start ? ((unsigned long long)nb_enc(0.0f) << 32) : SP1_KEY_INF;
+    key[s] = s == (uint32_t)pr.start ? ((unsigned long long)f32_key(0.0f) << 32) : SP1_KEY_INF;
     parent[s] = SP1_KEY_INF;
   }
   if (staged) {
@@ -560,13 +537,13 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
         const unsigned long long ks = key[s];
         if (ks != SP1_KEY_INF && ks != parent[s]) {  // (uniform: every lane reads the same words)
           if (lane == 0) parent[s] = ks;
-          const float ds = nb_dec((uint32_t)(ks >> 32));
+          const float ds = key_f32((uint32_t)(ks >> 32));
           const uint32_t h1 = (uint32_t)ks + 1u;
           for (uint32_t k = l_off[s] + lane; k < l_off[s + 1]; k += 64) {
             const uint2 a = l_wn[k];
             const float c = (ds + __uint_as_float(a.x)) + 0.0f;  // w1 (x) w2 (tropical_weight.rs:60-70)
             if (!(c < INF)) continue;                            // +inf never improves (shortest_path.rs:226)
-            const unsigned long long ck = ((unsigned long long)nb_enc(c) << 32) | h1;
+            const unsigned long long ck = ((unsigned long long)f32_key(c) << 32) | h1;
             if (ck < key[a.y]) changed |= atomicMin(&key[a.y], ck) > ck;
           }
         }
@@ -584,13 +561,13 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
       for (uint32_t s = lane; s < n; s += 64) {
         const unsigned long long ks = key[s];
         if (ks == SP1_KEY_INF) continue;
-        const float ds = nb_dec((uint32_t)(ks >> 32));
+        const float ds = key_f32((uint32_t)(ks >> 32));
         const uint32_t h1 = (uint32_t)ks + 1u;
         for (uint32_t k = pr.off[s]; k < pr.off[s + 1]; ++k) {
           const wfst_tr a = pr.arcs[k];
           const float c = (ds + a.weight) + 0.0f;
           if (!(c < INF)) continue;
-          const unsigned long long ck = ((unsigned long long)nb_enc(c) << 32) | h1;
+          const unsigned long long ck = ((unsigned long long)f32_key(c) << 32) | h1;
           if (ck < key[a.nextstate]) changed |= atomicMin(&key[a.nextstate], ck) > ck;
         }
       }
@@ -612,7 +589,7 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
     pl += nb_al(4 * (size_t)n);
     uint4* const e_arcs = (uint4*)pl;
     for (uint32_t s = lane; s < n; s += 64) {
-      e_dist[s] = key[s] == SP1_KEY_INF ? INF : nb_dec((uint32_t)(key[s] >> 32));
+      e_dist[s] = key[s] == SP1_KEY_INF ? INF : key_f32((uint32_t)(key[s] >> 32));
       e_fin[s] = pr.finals[s];
     }
     for (uint32_t s = lane; s <= n; s += 64) e_off[s] = pr.off[s];
@@ -628,9 +605,9 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
     const float f = pr.finals[s];
     const unsigned long long ks = key[s];
     if (!(f < INF) || ks == SP1_KEY_INF) continue;
-    const float tot = (nb_dec((uint32_t)(ks >> 32)) + f) + 0.0f;
+    const float tot = (key_f32((uint32_t)(ks >> 32)) + f) + 0.0f;
     if (!(tot < INF)) continue;
-    const unsigned long long c = ((unsigned long long)nb_enc(tot) << 32) | s;
+    const unsigned long long c = ((unsigned long long)f32_key(tot) << 32) | s;
     best = c < best ? c : best;
   }
   for (int d = 32; d >= 1; d >>= 1) {
@@ -646,7 +623,7 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
   for (uint32_t s = lane; s < n; s += 64) {
     const unsigned long long ks = key[s];
     if (ks == SP1_KEY_INF) continue;
-    const float ds = nb_dec((uint32_t)(ks >> 32));
+    const float ds = key_f32((uint32_t)(ks >> 32));
     const uint32_t h1 = (uint32_t)ks + 1u, b = staged ? l_off[s] : pr.off[s], e = staged ? l_off[s + 1] : pr.off[s + 1];
     for (uint32_t k = b; k < e; ++k) {
       uint2 a;
@@ -658,7 +635,7 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
       }
       const float c = (ds + __uint_as_float(a.x)) + 0.0f;
       if (!(c < INF)) continue;
-      const unsigned long long ck = ((unsigned long long)nb_enc(c) << 32) | h1;
+      const unsigned long long ck = ((unsigned long long)f32_key(c) << 32) | h1;
       const unsigned long long cls = sp1_parent_class(ck, ks, key[a.y]);
       if (cls != SP1_PARENT_NONE) atomicMin(&parent[a.y], cls | ((unsigned long long)s << 32) | (k - b));
     }
@@ -667,7 +644,7 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
   const uint32_t fp = (uint32_t)best;
   o.has_path = 1u;
   o.final_weight = pr.finals[fp];
-  o.total = nb_dec((uint32_t)(best >> 32));
+  o.total = key_f32((uint32_t)(best >> 32));
   // the walk: one lane follows the parents (LDS) and notes the arc index of every step where the keys were (they are not
   // needed any more: the start state is where the walk ends); the arcs themselves are then fetched by all lanes at once
   // and go to pinned memory in the order make_path_fst expects (arc k enters the k-th created state)

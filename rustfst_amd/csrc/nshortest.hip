@@ -14,7 +14,6 @@
 #include <chrono>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <cstdlib>
@@ -29,10 +28,6 @@ namespace wfst {
 namespace {
 
 // ---------------------------------------------------------------- reverse(): counting sort by nextstate
-__global__ void rev_count_kernel(const wfst_tr* __restrict__ arcs, uint64_t n_arcs, uint32_t* __restrict__ counts) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_arcs; i += (uint64_t)gridDim.x * blockDim.x)
-    atomicAdd(&counts[arcs[i].nextstate], 1u);
-}
 // slot reservation in arbitrary order; the arc index is kept so that each target's segment can be put back
 // into (source state, arc position) order = the order reverse() pushes arcs (reverse.rs:62-67)
 __global__ void rev_place_kernel(const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ arcs, uint32_t n_states,
@@ -118,21 +113,15 @@ std::shared_ptr<RevFst> build_reverse(wfst_ctx* ctx, const wfst_fst* f) {
   DBuf<uint32_t> d_counts(pool, (size_t)n + 1);
   HIP_CHECK(hipMemsetAsync(d_counts.p, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
   const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((E + 255) / 256, (uint64_t)ctx->n_cus * 8));
-  if (E) rev_count_kernel<<<blocks, 256, 0, st>>>(f->dev.arcs, E, d_counts.p);
+  count_indegrees(ctx, f->dev.arcs, E, d_counts.p);
   if (n) HIP_CHECK(hipMemcpyAsync(finals.data(), f->dev.finals, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
   // offsets of the in-arc segments (targets 0..n-1): exclusive scan of the in-degrees on the device
   DevicePool& owner_pool = f->owner_pool ? *f->owner_pool : *ctx->pool;  // cached with the handle: the owner's pool outlives it
   rev->d_roff = DBuf<uint32_t>(owner_pool, (size_t)n + 1);
   rev->d_arcs = DBuf<wfst_tr>(owner_pool, E);
   {
-    size_t temp_bytes = 0;
-    HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, d_counts.p, rev->d_roff.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    DBuf<uint8_t> temp(pool, temp_bytes);
-    HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, d_counts.p, rev->d_roff.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, rev->d_roff.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (total != E) throw Error("reverse: inconsistent arc count");
+    const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, d_counts.p, rev->d_roff.p, (size_t)n + 1);
+    if (read_u32(ctx, rev->d_roff.p + n) != E) throw Error("reverse: inconsistent arc count");
   }
   std::vector<uint32_t> roff;
   if (rev->on_host) {
@@ -151,9 +140,7 @@ std::shared_ptr<RevFst> build_reverse(wfst_ctx* ctx, const wfst_fst* f) {
     rev_emit_kernel<<<(n + 255) / 256, 256, 0, st>>>(f->dev.arcs, rev->d_roff.p, d_tmp.p, n, rev->d_arcs.p, d_big.p, d_big.p + 1,
                                                      d_big.p + 1 + big_cap);
     HIP_CHECK(hipGetLastError());
-    uint32_t n_big = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_big, d_big.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    const uint32_t n_big = read_u32(ctx, d_big.p);
     if (n_big) {  // hub states: segmented radix sort of the {arc index, source} pairs on the arc index
       if (E >= 0x7FFFFFFFull) throw Error("reverse: too many arcs for the segmented sort");
       DBuf<uint2> d_sorted(pool, E);
@@ -198,18 +185,11 @@ __global__ void __launch_bounds__(256) rev_facts_kernel(const uint32_t* __restri
   uint32_t facts = 0;
   for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
     const uint32_t b = roff[t], e = roff[t + 1];
-    uint32_t pil = 0, pol = 0;
+    wfst_tr prev{};
     for (uint32_t i = b; i < e; ++i) {
       const wfst_tr a = rarcs[i];
-      facts |= (a.ilabel != a.olabel ? 1u : 0u) | (a.ilabel == 0u ? 2u : 0u) | (a.ilabel == 0u && a.olabel == 0u ? 4u : 0u) |
-               (a.olabel == 0u ? 8u : 0u) | (i > b && pil > a.ilabel ? 16u : 0u) | (i > b && pol > a.olabel ? 32u : 0u) |
-               (a.nextstate <= t + 1u ? 128u : 0u);
-      const float w = a.weight;
-      const bool is_zero = INF <= w + props::KDELTA;                                  // approx == +inf (semiring.rs:159-168)
-      const bool is_one = w <= props::KDELTA && 0.0f <= w + props::KDELTA;            // approx == 0
-      if (!is_zero && !is_one) facts |= 64u;
-      pil = a.ilabel;
-      pol = a.olabel;
+      facts |= props::arc_facts(a, i > b ? &prev : nullptr, t + 1u);
+      prev = a;
     }
   }
   for (int d = 32; d >= 1; d >>= 1) facts |= __shfl_xor(facts, d);
@@ -255,13 +235,7 @@ const wfst_tr* rev_arcs_of(wfst_ctx* ctx, RevFst& r, uint32_t rs, uint32_t* coun
   return scratch.data();
 }
 
-// ---------------------------------------------------------------- TropicalWeight with the reference's semantics
-inline float wplus(float a, float b) { return b < a ? b : a; }
-inline float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
-inline bool weq(float a, float b) { return props::approx_eq(a, b); }  // KDELTA (semiring.rs:159-168)
-inline bool approx_equal(float a, float b, float delta) { return std::fabs(a - b) <= delta; }
-inline bool natural_less(float w1, float w2) { return weq(wplus(w1, w2), w1) && !weq(w1, w2); }  // shortest_path.rs:284-286
-
+// ---------------------------------------------------------------- the search (TropicalWeight: tropical.h)
 struct Pair {
   bool some;
   uint32_t state;
@@ -455,9 +429,7 @@ wfst_fst* reverse_fst(wfst_ctx* ctx, const wfst_fst* f) {
     rev_facts_kernel<<<blocks, 256, 0, st>>>(d_roff, d_arcs, n, d_facts.p);
   }
   HIP_CHECK(hipGetLastError());
-  uint32_t facts = 0;
-  HIP_CHECK(hipMemcpyAsync(&facts, d_facts.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  uint32_t facts = read_u32(ctx, d_facts.p);
   // property word: the mutations reverse() performs, in its order (add_state x (n+1), set_final(start+1, one), the arcs
   // state by state, set_start(0)), then reverse_properties(iprops, true) | oprops
   uint64_t p = props::NULL_PROPS;
@@ -466,10 +438,7 @@ wfst_fst* reverse_fst(wfst_ctx* ctx, const wfst_fst* f) {
     const float one = 0.0f;
     p = props::set_final(p, nullptr, &one);
   }
-  for (const wfst_tr& a : r.super) {  // state 0: eps:eps arcs into states >= 1
-    if (!props::is_zero(a.weight) && !props::is_one(a.weight)) facts |= 64u;
-    facts |= 2u | 4u | 8u;
-  }
+  for (const wfst_tr& a : r.super) facts |= props::arc_facts(a, nullptr, 0u);  // state 0: eps:eps arcs into states >= 1
   if (n_super + E) p = props::add_trs_by_facts(p, facts);
   p = props::set_start(p);
   p = (props::reverse(f->props, true) | p) & props::ALL;
@@ -482,7 +451,7 @@ template <class ArcsOf, class FinalOf>
 void nbest_search(ArcsOf&& arcs_of, FinalOf&& final_of, const std::vector<float>& distance_2, uint64_t nshortest, float delta,
                   OutFst& ofst) {
   const uint32_t istart = 0;  // rfst.start()
-  if (distance_2.size() <= istart || props::is_zero(distance_2[istart])) return;
+  if (distance_2.size() <= istart || is_zero(distance_2[istart])) return;
   const uint32_t ostart = ofst.add_state();
   ofst.set_start(ostart);
   const uint32_t final_state = ofst.add_state();
@@ -520,7 +489,7 @@ void nbest_search(ArcsOf&& arcs_of, FinalOf&& final_of, const std::vector<float>
       heap.push(next);
     }
     const float fw = final_of(p.state);
-    if (fw != INF && !props::is_zero(fw)) {
+    if (fw != INF && !is_zero(fw)) {
       const float weight = wtimes(p.w, fw);
       const uint32_t next = ofst.add_state();
       pairs.push_back(Pair{false, 0, weight});
@@ -541,10 +510,6 @@ struct DetElt {
   uint32_t state;
   float w;
 };
-inline float quantize(float v, float delta) {  // semirings/semiring.rs:132-145
-  if (std::isinf(v)) return v;
-  return std::floor((v / delta) + 0.5f) * delta;
-}
 void determinize_with_distance(const HostCsr& in, int64_t start, uint64_t in_props, const std::vector<float>& in_dist, float delta,
                                HostCsr& out, std::vector<float>& out_dist) {
   if (!(in_props & props::ACCEPTOR)) throw Error("DeterminizeFsaImpl : expected acceptor as argument");  // determinize_fsa_op.rs:138-140
@@ -609,7 +574,7 @@ void determinize_with_distance(const HostCsr& in, int64_t start, uint64_t in_pro
       i = j;
     }
     out.offsets.push_back((uint32_t)out.arcs.size());
-    out.finals.push_back(props::is_zero(fw) ? INF : fw);
+    out.finals.push_back(is_zero(fw) ? INF : fw);
   }
 }
 

@@ -17,8 +17,6 @@
 #include <algorithm>
 #include <memory>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.h"
 #include "fst_props.h"
 
@@ -35,15 +33,6 @@ constexpr uint64_t LABEL_INVARIANT = props::WEIGHTED | props::UNWEIGHTED | props
                                      props::INITIAL_ACYCLIC | props::TOP_SORTED | props::NOT_TOP_SORTED | props::ACCESSIBLE |
                                      props::NOT_ACCESSIBLE | props::COACCESSIBLE | props::NOT_COACCESSIBLE | props::STRING |
                                      props::NOT_STRING | props::WEIGHTED_CYCLES | props::UNWEIGHTED_CYCLES;
-
-__device__ inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 
 // the pair of arc p into an open-addressing set (EMPTY_KEY = free); minpos[slot] = the first arc that holds the pair
 __global__ void __launch_bounds__(TPB) enc_insert_kernel(const wfst_tr* __restrict__ arcs, uint32_t n_arcs,
@@ -101,22 +90,6 @@ __global__ void dec_label_kernel(const wfst_tr* __restrict__ arcs, uint32_t n_ar
   out[p] = wfst_tr{t.x, t.y, a.weight, a.nextstate};
 }
 
-struct HandleDeleter {
-  void operator()(wfst_fst* p) const {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    delete p;
-  }
-};
-using Handle = std::unique_ptr<wfst_fst, HandleDeleter>;
-
-uint32_t read_flag(wfst_ctx* ctx, const uint32_t* d) {
-  uint32_t v = 0;
-  HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return v;
-}
-
 // encode(EncodeLabels), determinize, minimize, decode (optimize.rs:36-50) of the transducer x
 wfst_fst* encode_deter_mini_decode(wfst_ctx* ctx, const wfst_fst* x) {
   using namespace props;
@@ -130,28 +103,24 @@ wfst_fst* encode_deter_mini_decode(wfst_ctx* ctx, const wfst_fst* x) {
   uint32_t n_pairs = 0;
   Handle enc;
   if (mapped && E) {
-    uint64_t size = 64;
-    while (size < 2 * E) size <<= 1;
+    const uint32_t size = pow2_at_least(2 * E, "optimize");
     DBuf<unsigned long long> keys(pool, size);
     DBuf<uint32_t> minpos(pool, size), slot_of(pool, E), first(pool, E + 1), rank(pool, E + 1), err(pool, 1);
     DBuf<wfst_tr> arcs(pool, E);
-    HIP_CHECK(hipMemsetAsync(keys.p, 0xFF, size * sizeof(unsigned long long), st));
-    HIP_CHECK(hipMemsetAsync(minpos.p, 0xFF, size * sizeof(uint32_t), st));
+    HIP_CHECK(hipMemsetAsync(keys.p, 0xFF, (size_t)size * sizeof(unsigned long long), st));
+    HIP_CHECK(hipMemsetAsync(minpos.p, 0xFF, (size_t)size * sizeof(uint32_t), st));
     HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((E + TPB - 1) / TPB, (uint64_t)ctx->n_cus * 32);
-    enc_insert_kernel<<<blocks, TPB, 0, st>>>(x->dev.arcs, (uint32_t)E, keys.p, (uint32_t)size - 1, minpos.p, slot_of.p, err.p);
+    enc_insert_kernel<<<blocks, TPB, 0, st>>>(x->dev.arcs, (uint32_t)E, keys.p, size - 1, minpos.p, slot_of.p, err.p);
     HIP_CHECK(hipGetLastError());
-    if (read_flag(ctx, err.p)) throw Error("optimize: the label pair (4294967295, 4294967295) is not supported");
+    if (read_u32(ctx, err.p)) throw Error("optimize: the label pair (4294967295, 4294967295) is not supported");
     enc_first_kernel<<<(uint32_t)((E + 1 + TPB - 1) / TPB), TPB, 0, st>>>(minpos.p, slot_of.p, (uint32_t)E, first.p);
     HIP_CHECK(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, first.p, rank.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
-    DBuf<uint8_t> temp(pool, temp_bytes);
-    HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, first.p, rank.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, first.p, rank.p, (size_t)E + 1);
     enc_label_kernel<<<(uint32_t)((E + TPB - 1) / TPB), TPB, 0, st>>>(x->dev.arcs, (uint32_t)E, minpos.p, slot_of.p, rank.p, arcs.p,
                                                                      table.p);
     HIP_CHECK(hipGetLastError());
-    n_pairs = read_flag(ctx, rank.p + E);
+    n_pairs = read_u32(ctx, rank.p + E);
     enc.reset(adopt_device(ctx, n, E, x->start, x->props & LABEL_INVARIANT, x->dev.offsets, arcs.p, x->dev.finals));
   } else {
     enc.reset(adopt_device(ctx, n, E, x->start, mapped ? (x->props & LABEL_INVARIANT) : x->props, x->dev.offsets, x->dev.arcs,
@@ -174,7 +143,7 @@ wfst_fst* encode_deter_mini_decode(wfst_ctx* ctx, const wfst_fst* x) {
     HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
     dec_label_kernel<<<(uint32_t)((M + TPB - 1) / TPB), TPB, 0, st>>>(mini->dev.arcs, (uint32_t)M, table.p, n_pairs, dec.p, err.p);
     HIP_CHECK(hipGetLastError());
-    const uint32_t bad = read_flag(ctx, err.p);
+    const uint32_t bad = read_u32(ctx, err.p);
     if (bad & 1u) throw Error("optimize: can't decode a label of the minimized machine");
     // rm_final_epsilon would fold such an arc into a final weight; only its closing connect is implemented
     if (bad & 2u) throw Error("optimize: eps:eps arcs under a property word that holds NO_EPSILONS are not supported");

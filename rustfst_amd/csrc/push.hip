@@ -7,9 +7,7 @@
 //   INITIAL_ACYCLIC    only when the start branch runs and the word does not know it: reachability (BFS from the start),
 //                      co-reachability (BFS on the reversed handle), cycle existence (in-degree peeling), start on a cycle
 //   the start state    (at most one arc list and one final weight) and the property word: on the host
-// TropicalWeight with the reference's semantics (semirings/tropical_weight.rs:60-70, 128-131, semiring.rs:159-168):
-//   times: inf (x) x = inf, x (x) inf = inf, else a + b in f32;  divide: a - b in f32, no inf check;
-//   is_zero / is_one: the APPROXIMATE == with KDELTA = 1/1024 (a start potential within 1/1024 of 0 is one).
+// TropicalWeight with the reference's semantics: tropical.h (a start potential within 1/1024 of 0 is one).
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -20,23 +18,6 @@
 namespace wfst {
 
 namespace {
-
-constexpr float KD = 1.0f / 1024.0f;  // KDELTA (lib.rs:266)
-__device__ __host__ inline float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
-__device__ __host__ inline float wdivide(float a, float b) { return a - b; }  // DivideLeft == DivideRight (tropical_weight.rs:128-131)
-__device__ __host__ inline bool wzero(float w) { return w <= INF + KD && INF <= w + KD; }
-__device__ __host__ inline bool wone(float w) { return w <= 0.0f + KD && 0.0f <= w + KD; }
-__device__ __host__ inline bool wweighted(float w) { return !wzero(w) && !wone(w); }
-__device__ inline uint32_t f2key(float f) {  // order-preserving encoding of an f32 (as sssp.hip's keys)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float key2f(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
 
 // ---------------------------------------------------------------- structural passes
 // One round of a frontier search: every state of the frontier (16 lanes per state) looks at its arcs.
@@ -78,10 +59,6 @@ __global__ void __launch_bounds__(256) bfs_round_kernel(const uint32_t* __restri
     atomicAdd(&stats[0], pushed);  // states that joined a frontier
     atomicMax(&stats[1], maxid);   // 1 + the largest of them
   }
-}
-__global__ void indegree_kernel(const wfst_tr* __restrict__ arcs, uint64_t n_arcs, uint32_t* __restrict__ indeg) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_arcs; i += (uint64_t)gridDim.x * blockDim.x)
-    atomicAdd(&indeg[arcs[i].nextstate], 1u);
 }
 // the states without in-arcs: the first frontier of the peeling
 __global__ void zero_indegree_kernel(const uint32_t* __restrict__ indeg, uint32_t n, uint32_t* __restrict__ fout,
@@ -183,11 +160,7 @@ uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f) {
   {
     DBuf<uint32_t> indeg(*ctx->pool, n);
     HIP_CHECK(hipMemsetAsync(indeg.p, 0, (size_t)n * sizeof(uint32_t), ctx->stream));
-    if (f->n_arcs) {
-      const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((f->n_arcs + 255) / 256, (uint64_t)ctx->n_cus * 8));
-      indegree_kernel<<<blocks, 256, 0, ctx->stream>>>(f->dev.arcs, f->n_arcs, indeg.p);
-      HIP_CHECK(hipGetLastError());
-    }
+    count_indegrees(ctx, f->dev.arcs, f->n_arcs, indeg.p);
     cyclic = frontier_search(ctx, n, f->dev.offsets, f->dev.arcs, {}, indeg.p, 1).joined != n;
   }
   // INITIAL_CYCLIC: a back arc into the start = the start reachable from its own successors (search seeded with the start,
@@ -197,10 +170,7 @@ uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f) {
     DBuf<uint32_t> vis(*ctx->pool, n);
     HIP_CHECK(hipMemsetAsync(vis.p, 0, (size_t)n * sizeof(uint32_t), ctx->stream));
     frontier_search(ctx, n, f->dev.offsets, f->dev.arcs, {s0}, vis.p, 0);
-    uint32_t v = 0;
-    HIP_CHECK(hipMemcpyAsync(&v, vis.p + s0, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    initial_cyclic = v != 0;
+    initial_cyclic = read_u32(ctx, vis.p + s0) != 0;
   }
   return props::dfs_bits(accessible, coaccessible, cyclic, initial_cyclic);
 }
@@ -219,12 +189,12 @@ __global__ void __launch_bounds__(256) reweight_arcs_kernel(const uint32_t* __re
   uint32_t facts = 0;
   for (uint32_t s = tid >> 4; s < n; s += (gridDim.x * blockDim.x) >> 4) {
     const float d_s = s < len ? pot[s] : INF;
-    const bool skip = wzero(d_s);
+    const bool skip = is_zero(d_s);
     for (uint32_t i = off[s] + lane; i < off[s + 1]; i += 16) {
       wfst_tr a = arcs[i];
       if (!skip) {
         const float d_ns = a.nextstate < len ? pot[a.nextstate] : INF;
-        if (!wzero(d_ns)) {
+        if (!is_zero(d_ns)) {
           a.weight = to_final ? wdivide(wtimes(d_s, a.weight), d_ns) : wdivide(wtimes(a.weight, d_ns), d_s);
           facts |= 1u;
         }
@@ -256,10 +226,10 @@ __global__ void reweight_finals_kernel(const float* __restrict__ fin, uint32_t n
         facts |= 2u;
         if (remove) {
           const float nf = wdivide(f, total);
-          if (wweighted(f) || wweighted(nf)) op = ((unsigned long long)(s + 1) << 1) | (wweighted(nf) ? 1ull : 0ull);
+          if (weighted(f) || weighted(nf)) op = ((unsigned long long)(s + 1) << 1) | (weighted(nf) ? 1ull : 0ull);
           f = nf;
         }
-      } else if (!wzero(d_s)) {
+      } else if (!is_zero(d_s)) {
         f = wdivide(f, d_s);
         facts |= 2u;
       }
@@ -280,9 +250,9 @@ __global__ void reweight_finals_kernel(const float* __restrict__ fin, uint32_t n
 // compute_total_weight, forward case (push.rs:128-141): (+)_s dist[s] (x) final[s] — the tropical sum is a minimum
 __global__ void total_weight_kernel(const float* __restrict__ dist, const float* __restrict__ fin, uint32_t n,
                                     uint32_t* __restrict__ key_out) {
-  uint32_t best = f2key(INF);
+  uint32_t best = f32_key(INF);
   for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x)
-    best = min(best, f2key(wtimes(dist[s], fin[s])));
+    best = min(best, f32_key(wtimes(dist[s], fin[s])));
   for (int d = 32; d >= 1; d >>= 1) best = min(best, (uint32_t)__shfl_xor(best, d));
   if ((threadIdx.x & 63) == 0) atomicMin(key_out, best);
 }
@@ -328,7 +298,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
   hipStream_t st = ctx->stream;
   DevicePool& pool = *ctx->pool;
   // remove_weight does nothing when the total is one or zero (push.rs:150-152)
-  const bool remove = remove_total && !props::is_one(total) && !props::is_zero(total);
+  const bool remove = remove_total && !is_one(total) && !is_zero(total);
   // room for the state reweight may add (reweight.rs:129-138)
   DBuf<uint32_t> off_out(pool, (size_t)n + 2);
   DBuf<wfst_tr> arcs_out(pool, E + 1);
@@ -381,7 +351,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
     HIP_CHECK(hipMemcpy(&sfin, fin_out.p + s, sizeof(float), hipMemcpyDeviceToHost));
   };
   bool start_dirty = false;
-  if (start >= 0 && !props::is_one(d_start) && !props::is_zero(d_start)) {
+  if (start >= 0 && !is_one(d_start) && !is_zero(d_start)) {
     // compute_and_update_properties(INITIAL_ACYCLIC) (:109): the stored bit if the word knows it, else the DFS bits
     if (!props::knows(p, props::INITIAL_CYCLIC)) p = props::merge_dfs(p, structural_bits(ctx, f));
     // (ToFinal: one / d_s = 0 - d_s)
@@ -508,15 +478,12 @@ wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_t
       if (f->start >= 0) HIP_CHECK(hipMemcpy(&total, d + f->start, sizeof(float), hipMemcpyDeviceToHost));
     } else {
       DBuf<uint32_t> key(*ctx->pool, 1);
-      const uint32_t kinf = 0x7F800000u | 0x80000000u;  // the key of +inf (zero)
+      const uint32_t kinf = f32_key(INF);  // zero
       HIP_CHECK(hipMemcpyAsync(key.p, &kinf, sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
       const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)ctx->n_cus * 4));
       total_weight_kernel<<<blocks, 256, 0, ctx->stream>>>(d, f->dev.finals, n, key.p);
       HIP_CHECK(hipGetLastError());
-      uint32_t k = 0;
-      HIP_CHECK(hipMemcpyAsync(&k, key.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      total = key2f(k);
+      total = key_f32(read_u32(ctx, key.p));
     }
   }
   return reweight_device(ctx, f, d, n, reweight_type, remove_total_weight, total);

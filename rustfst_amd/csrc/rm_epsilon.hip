@@ -33,8 +33,6 @@
 // input) — the deviation already documented for shortest_distance.
 #include <algorithm>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.h"
 #include "fst_props.h"
 
@@ -50,7 +48,6 @@ struct RmCaps {
 __host__ __device__ inline size_t rm_arcs_offset(const RmCaps& c) { return ((size_t)c.C * 12 + (size_t)c.K * 4 + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t rm_slice_bytes(const RmCaps& c) { return rm_arcs_offset(c) + (size_t)c.A * 16; }
 
-__device__ __forceinline__ float wtimes(float a, float b) { return a == INF ? a : (b == INF ? b : a + b); }
 __device__ __forceinline__ bool is_eps(const wfst_tr& t) { return t.ilabel == 0u && t.olabel == 0u; }  // EpsilonTrFilter
 
 struct RmView {  // the FST as the reference's loop sees it at this moment
@@ -189,12 +186,6 @@ __device__ __forceinline__ uint32_t rm_hash32(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
-__device__ __forceinline__ uint32_t rm_enc(float f) {  // order-preserving bits (weights may be negative)
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float rm_dec(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
-
 // closure index of state t (0xFFFFFFFF if absent); the table holds index + 1
 __device__ __forceinline__ uint32_t rm_cl_find(const uint32_t* __restrict__ htab, uint32_t hmask, const uint32_t* __restrict__ cl, uint32_t t) {
   for (uint32_t p = rm_hash32(t) & hmask;; p = (p + 1) & hmask) {
@@ -233,7 +224,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
   __builtin_amdgcn_s_barrier();
   if (lane == 0) {
     cl[0] = s;
-    dist[0] = rm_enc(0.0f);
+    dist[0] = f32_key(0.0f);
     htab[rm_hash32(s) & hmask] = 1u;
     hdr[0] = 1u;
   }
@@ -251,7 +242,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
       float dk = INF;
       if (k < n0) {
         tq = v.trs(cl[k], &nq);
-        dk = rm_dec(__hip_atomic_load(&dist[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+        dk = key_f32(__hip_atomic_load(&dist[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
       }
       uint32_t a = 0;
       // a lane that must insert a new closure state claims a table slot; the loop is wave-uniform so that nobody spins on
@@ -299,7 +290,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
           }
           if (j != 0xFFFFFFFFu) {
             if (j != 0xFFFFFFFEu) {
-              const uint32_t cand = rm_enc(wtimes(dk, pend_w));
+              const uint32_t cand = f32_key(wtimes(dk, pend_w));
               if (cand < __hip_atomic_fetch_min(&dist[j], cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) changed = true;
             }
             pend_t = 0xFFFFFFFFu;
@@ -326,7 +317,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
     if (lane == 0) vis[k] = 1u;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     const uint32_t q = cl[k];
-    const float dq = rm_dec(dist[k]);
+    const float dq = key_f32(dist[k]);
     uint32_t nq;
     const wfst_tr* tq = v.trs(q, &nq);
     for (uint32_t a0 = 0; a0 < nq; a0 += 64) {
@@ -359,7 +350,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
         const uint32_t il = __shfl(tr.ilabel, lead), ol = __shfl(tr.olabel, lead), ns = __shfl(tr.nextstate, lead);
         const bool same = wait && tr.ilabel == il && tr.olabel == ol && tr.nextstate == ns;
         // the group's weight: min over its lanes
-        uint32_t wbits = same ? rm_enc(tr.weight) : 0xFFFFFFFFu;
+        uint32_t wbits = same ? f32_key(tr.weight) : 0xFFFFFFFFu;
         for (int d = 32; d >= 1; d >>= 1) wbits = min(wbits, (uint32_t)__shfl_xor(wbits, d));
         uint32_t found = 0xFFFFFFFFu;  // index of this key's arc after the leader's step
         if ((int)lane == lead) {
@@ -371,7 +362,7 @@ __global__ void __launch_bounds__(64) rm_expand_wave(RmView v, const uint32_t* _
             const wfst_tr o = out[ov - 1u];
             if (o.ilabel == il && o.olabel == ol && o.nextstate == ns) break;
           }
-          const float w = rm_dec(wbits);
+          const float w = key_f32(wbits);
           if (ov) {
             if (w < out[ov - 1u].weight) out[ov - 1u].weight = w;  // plus_assign at the first occurrence
             found = ov - 1u;
@@ -650,18 +641,13 @@ wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f) {
   }
   // states that were not rewritten lose their arcs (rm_epsilon_static.rs:137-143): cnt is 0 for them already.
   // CSR of the result before connect
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, cnt.p, off.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, cnt.p, off.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, cnt.p, off.p, (size_t)n + 1);
   uint32_t h[2];
-  HIP_CHECK(hipMemcpyAsync(&h[0], off.p + n, 4, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  h[0] = read_u32(ctx, off.p + n);
   DBuf<wfst_tr> new_arcs(*ctx->pool, h[0]);
   rm_write<<<(n + 255) / 256, 256, 0, st>>>(off.p, cnt.p, arc_ptr.p, new_arcs.p, n, facts.p);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(&h[1], facts.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  h[1] = read_u32(ctx, facts.p);
   // property word: every rewrite applies delete_trs_properties, add_tr over its new arcs and set_final; what
   // rmepsilon_properties(.., delayed = false) then reads are ACCEPTOR / ACYCLIC / INITIAL_ACYCLIC / TOP_SORTED, all of
   // them functions of the three facts; connect finishes with delete_states_properties | ACCESSIBLE | COACCESSIBLE

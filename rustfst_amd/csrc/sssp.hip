@@ -25,8 +25,6 @@
 #include <sys/file.h>
 #include <unistd.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.h"
 #include "fst_props.h"
 
@@ -48,15 +46,6 @@ constexpr uint32_t GROUP = 16;  // lanes cooperating on one frontier state (aver
 // for fine-grained pinned memory: measured, a 512-problem batch read results that had not landed.  The fence costs the
 // tail kernel ~2 us.)
 __device__ __forceinline__ void host_stores_done() { __threadfence_system(); }
-
-__device__ __forceinline__ uint32_t enc_f32(float f) {
-  uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) {
-  uint32_t b = (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e;
-  return __uint_as_float(b);
-}
 
 // Near-far schedule (a Delta-stepping relative that needs no buckets): sweep k only relaxes active states
 // with d <= tau_k; the others stay in the frontier.  When a sweep activates nothing near, tau advances by
@@ -168,8 +157,8 @@ __global__ void __launch_bounds__(256) sssp_setup_kernel(uint64_t* __restrict__ 
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
   for (uint32_t i = tid; i < n; i += nt) {
     const bool is_start = i == start;
-    key[i] = is_start ? (uint64_t)enc_f32(0.0f) << 32 : KEY_INF;
-    shadow[i] = is_start ? enc_f32(0.0f) : 0xFFFFFFFFu;
+    key[i] = is_start ? (uint64_t)f32_key(0.0f) << 32 : KEY_INF;
+    shadow[i] = is_start ? f32_key(0.0f) : 0xFFFFFFFFu;
   }
   for (uint32_t i = tid; i < n_flag_words; i += nt) flag_words[i] = i == (start >> 2) ? 1u << (8u * (start & 3u)) : 0u;
   for (uint32_t i = tid; i < IMP_RING; i += nt) improved[i] = 0;
@@ -316,7 +305,7 @@ __global__ void __launch_bounds__(256) sssp_relax_kernel(const uint32_t* __restr
       // (shuffles stay outside any lane-dependent condition: a bpermute reads 0 from a lane that is masked off)
       const uint32_t ea_all = __shfl(my_e, la), eb_all = __shfl(my_e, lb);
       const uint32_t ea = has_a ? ea_all : 0u, eb = has_b ? eb_all : 0u;
-      const float da = dec_f32((uint32_t)(ks_a >> 32)), db = dec_f32((uint32_t)(ks_b >> 32));
+      const float da = key_f32((uint32_t)(ks_a >> 32)), db = key_f32((uint32_t)(ks_b >> 32));
       const uint32_t ha = (uint32_t)ks_a + 1u, hb = (uint32_t)ks_b + 1u;
       while (__any(ia < ea || ib < eb)) {
         const bool va = ia < ea, vb = ib < eb;
@@ -326,7 +315,7 @@ __global__ void __launch_bounds__(256) sssp_relax_kernel(const uint32_t* __restr
         const float ca = (da + __uint_as_float(aa.x)) + 0.0f;  // w1 (x) w2 = f32 add (tropical_weight.rs:60-70)
         const float cb = (db + __uint_as_float(ab.x)) + 0.0f;
         const bool fa = va && ca < INF, fb = vb && cb < INF;  // +inf never improves (shortest_path.rs:226)
-        const uint64_t cka = ((uint64_t)enc_f32(ca) << 32) | ha, ckb = ((uint64_t)enc_f32(cb) << 32) | hb;
+        const uint64_t cka = ((uint64_t)f32_key(ca) << 32) | ha, ckb = ((uint64_t)f32_key(cb) << 32) | hb;
         // Plain pre-check against a 4-byte SHADOW of the distance half of the key (4 MB for 1M states: half the bytes
         // per gather and a far better L2 hit rate than the 8-byte keys).  shadow[t] is only ever written with values
         // that an atomicMin has installed in key[t], and keys only decrease, so shadow[t] >= enc(d[t]) at all times:
@@ -364,7 +353,7 @@ __global__ void __launch_bounds__(256) sssp_relax_kernel(const uint32_t* __restr
       my_ks = key[sc];
       my_b = offsets[sc];
       my_e = offsets[sc + 1];
-      if (dec_f32((uint32_t)(my_ks >> 32)) > tau) {  // far: stays in the frontier, is not relaxed in this sweep
+      if (key_f32((uint32_t)(my_ks >> 32)) > tau) {  // far: stays in the frontier, is not relaxed in this sweep
         flags_next[sc] = 1;
         any = true;
         act = false;
@@ -465,9 +454,9 @@ __global__ void __launch_bounds__(256) sssp_final_kernel(const float* __restrict
     if (!(f < INF)) continue;  // most states are not final: their key is never fetched
     const uint64_t k = key[s];
     if (k == KEY_INF) continue;
-    const float tot = (dec_f32((uint32_t)(k >> 32)) + f) + 0.0f;
+    const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;
     if (!(tot < INF)) continue;
-    const unsigned long long c = ((unsigned long long)enc_f32(tot) << 32) | s;
+    const unsigned long long c = ((unsigned long long)f32_key(tot) << 32) | s;
     best = c < best ? c : best;
   }
   for (int d = 32; d >= 1; d >>= 1) {
@@ -509,14 +498,14 @@ __global__ void __launch_bounds__(256) sssp_parent_kernel(const uint32_t* __rest
   for (uint32_t s = tid / GROUP; s < n; s += n_groups) {
     const uint64_t ks = key[s];
     if (ks == KEY_INF) continue;
-    const float d = dec_f32((uint32_t)(ks >> 32));
+    const float d = key_f32((uint32_t)(ks >> 32));
     const uint32_t h1 = (uint32_t)ks + 1u;
     const uint32_t b = offsets[s], e = offsets[s + 1];
     for (uint32_t i = b + lane; i < e; i += GROUP) {
       const uint2 a = wn[i];
       const float c = (d + __uint_as_float(a.x)) + 0.0f;
       if (!(c < INF)) continue;
-      const uint64_t ck = ((uint64_t)enc_f32(c) << 32) | h1, kt = key[a.y];
+      const uint64_t ck = ((uint64_t)f32_key(c) << 32) | h1, kt = key[a.y];
       const unsigned long long cls = parent_class(ck, ks, kt);
       if (cls != PARENT_NONE) atomicMin(&parent[a.y], cls | ((unsigned long long)s << 32) | (i - b));
     }
@@ -535,7 +524,7 @@ __global__ void sssp_header_kernel(const float* __restrict__ finals, const uint6
   ctl->f_parent = fp;
   ctl->hops = (uint32_t)key[fp];
   ctl->final_weight = finals[fp];
-  ctl->total = dec_f32((uint32_t)(best >> 32));
+  ctl->total = key_f32((uint32_t)(best >> 32));
 }
 
 // single_shortest_path_backtrace (shortest_path.rs:241-282): walk parent[] from f_parent; the arc of the
@@ -725,8 +714,8 @@ __device__ __forceinline__ uint32_t sssp_walk_back(const uint32_t* __restrict__ 
         const uint4 ra = rev_arc[j];
         const uint64_t ks = key[ra.x];
         if (ks == KEY_INF) continue;
-        const float c = (dec_f32((uint32_t)(ks >> 32)) + __uint_as_float(ra.z)) + 0.0f;
-        if (c < INF && enc_f32(c) == (uint32_t)(kt >> 32)) tn += 1u;
+        const float c = (key_f32((uint32_t)(ks >> 32)) + __uint_as_float(ra.z)) + 0.0f;
+        if (c < INF && f32_key(c) == (uint32_t)(kt >> 32)) tn += 1u;
       }
       if (__any(tn != 0u)) ties += 1u;
       break;
@@ -744,10 +733,10 @@ __device__ __forceinline__ uint32_t sssp_walk_back(const uint32_t* __restrict__ 
       const uint64_t ks = key[ra.x];
       const uint32_t sb = rev_off[ra.x], se = rev_off[ra.x + 1];
       if (ks == KEY_INF) continue;
-      const float c = (dec_f32((uint32_t)(ks >> 32)) + __uint_as_float(ra.z)) + 0.0f;
+      const float c = (key_f32((uint32_t)(ks >> 32)) + __uint_as_float(ra.z)) + 0.0f;
       if (!(c < INF)) continue;
-      if (enc_f32(c) == (uint32_t)(kt >> 32)) tn += 1u;
-      const uint64_t ck = ((uint64_t)enc_f32(c) << 32) | ((uint32_t)ks + 1u);
+      if (f32_key(c) == (uint32_t)(kt >> 32)) tn += 1u;
+      const uint64_t ck = ((uint64_t)f32_key(c) << 32) | ((uint32_t)ks + 1u);
       const unsigned long long cls = parent_class(ck, ks, kt);
       if (cls != PARENT_NONE) {
         const unsigned long long cand = cls | ((unsigned long long)ra.x << 32) | ra.y;
@@ -856,9 +845,9 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
     if (!(f < INF)) continue;  // most states are not final: their key is never fetched
     const uint64_t k = key[s];
     if (k == KEY_INF) continue;
-    const float tot = (dec_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
+    const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
     if (!(tot < INF)) continue;
-    merge(best, tie, ((unsigned long long)enc_f32(tot) << 32) | s, false);
+    merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
   }
   for (int d = 32; d >= 1; d >>= 1) {
     const unsigned long long o = __shfl_xor(best, d);
@@ -927,7 +916,7 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
     return;
   }
   const uint32_t fp = (uint32_t)best;
-  const float final_weight = finals[fp], total = dec_f32((uint32_t)(best >> 32));
+  const float final_weight = finals[fp], total = key_f32((uint32_t)(best >> 32));
   uint32_t k = 0, ties = tie ? 1u : 0u;
   if ((uint32_t)key[fp] > out_cap) pad |= 8u;  // the host falls back to the parent pass
   else k = sssp_walk_back(offsets, arcs, key, rev_off, rev_arc, fp, out, out_cap, pad, s_walk, ties);
@@ -963,9 +952,9 @@ __global__ void __launch_bounds__(256) sssp_final_ref_kernel(const float* __rest
     if (!(f < INF)) continue;
     const uint64_t k = key[s];
     if (k == KEY_INF) continue;
-    const float tot = (dec_f32((uint32_t)(k >> 32)) + f) + 0.0f;
+    const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;
     if (!(tot < INF)) continue;
-    const unsigned long long c = ((unsigned long long)enc_f32(tot) << 32) | rank[s];
+    const unsigned long long c = ((unsigned long long)f32_key(tot) << 32) | rank[s];
     best = c < best ? c : best;
   }
   for (int d = 32; d >= 1; d >>= 1) {
@@ -985,14 +974,14 @@ __global__ void __launch_bounds__(256) sssp_parent_ref_kernel(const uint32_t* __
   for (uint32_t s = tid / GROUP; s < n; s += n_groups) {
     const uint64_t ks = key[s];
     if (ks == KEY_INF) continue;
-    const float d = dec_f32((uint32_t)(ks >> 32));
+    const float d = key_f32((uint32_t)(ks >> 32));
     const uint32_t b = offsets[s], e = offsets[s + 1];
     const unsigned long long rs = (unsigned long long)rank[s] << 32;
     for (uint32_t i = b + lane; i < e; i += GROUP) {
       const uint2 a = wn[i];
       const float c = (d + __uint_as_float(a.x)) + 0.0f;
       if (!(c < INF)) continue;
-      if (enc_f32(c) == (uint32_t)(key[a.y] >> 32)) atomicMin(&parent[a.y], rs | (i - b));
+      if (f32_key(c) == (uint32_t)(key[a.y] >> 32)) atomicMin(&parent[a.y], rs | (i - b));
     }
   }
 }
@@ -1011,7 +1000,7 @@ __global__ void sssp_backtrace_ref_kernel(const uint32_t* __restrict__ offsets, 
   ctl->has_path = 1;
   ctl->f_parent = cur;
   ctl->final_weight = finals[cur];
-  ctl->total = dec_f32((uint32_t)(best >> 32));
+  ctl->total = key_f32((uint32_t)(best >> 32));
   while (cur != start) {
     const unsigned long long p = parent[cur];
     if (p == PARENT_NONE || k >= out_cap) {
@@ -1033,7 +1022,7 @@ __global__ void sssp_export_kernel(const uint64_t* __restrict__ key, float* __re
   uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const uint64_t k = key[s];
-  dist[s] = k == KEY_INF ? INF : dec_f32((uint32_t)(k >> 32));
+  dist[s] = k == KEY_INF ? INF : key_f32((uint32_t)(k >> 32));
   if (hops) hops[s] = k == KEY_INF ? 0xFFFFFFFFu : (uint32_t)k;
 }
 
@@ -1215,10 +1204,7 @@ std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t l
   if (log == 13) mbox_hist_kernel<13><<<nb, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, nb, hist.p);
   else mbox_hist_kernel<12><<<nb, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, nb, hist.p);
   HIP_CHECK(hipMemsetAsync(hist.p + cells, 0, sizeof(uint32_t), st));
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, hist.p, p->roff.p, 0u, cells + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, hist.p, p->roff.p, 0u, cells + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, hist.p, p->roff.p, cells + 1);
   mbox_transpose_kernel<<<(uint32_t)((cells + 255) / 256), 256, 0, st>>>(p->roff.p, nb, p->roff_t.p);
   // lanes per state of the resident kernel's expansion rounds (a lane takes two arcs): the fewest that cover all but 1/64 of
   // the rows in one pass — a lane group without arcs is a lane group that keeps no row in flight — and leave at most 1/16 of
@@ -1250,7 +1236,7 @@ std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t l
     p->roffh_t = DBuf<uint32_t>(owner_pool, cells);
     DBuf<uint32_t> sizes(*ctx->pool, cells + 1);
     res_size_kernel<<<(uint32_t)((cells + 1 + 255) / 256), 256, 0, st>>>(hist.p, (uint32_t)cells, sizes.p);
-    HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, sizes.p, p->roffh.p, 0u, cells + 1, rocprim::plus<uint32_t>(), st));
+    const DBuf<uint8_t> scan_tmp2 = exclusive_scan_u32(ctx, sizes.p, p->roffh.p, cells + 1);
     mbox_transpose_kernel<<<(uint32_t)((cells + 255) / 256), 256, 0, st>>>(p->roffh.p, nb, p->roffh_t.p);
     HIP_CHECK(hipMemcpyAsync(&h_units, p->roffh.p + cells, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipGetLastError());
@@ -1258,7 +1244,7 @@ std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t l
     p->res_units = h_units;
   }
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st));  // hist / temp are released here
+  HIP_CHECK(hipStreamSynchronize(st));  // hist / scan_tmp are released here
   slot = p;
   return p;
 }
@@ -1287,15 +1273,12 @@ std::shared_ptr<BinPlan> bin_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t log
   if (logd == 14) bin_hist_kernel<14><<<p->G, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, p->sg, p->nbin, p->G, hist.p);
   else bin_hist_kernel<13><<<p->G, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, p->sg, p->nbin, p->G, hist.p);
   HIP_CHECK(hipMemsetAsync(hist.p + cells, 0, sizeof(uint32_t), st));
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, hist.p, p->roff.p, 0u, cells + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, hist.p, p->roff.p, 0u, cells + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, hist.p, p->roff.p, cells + 1);
   bin_transpose_kernel<<<(uint32_t)((cells + 255) / 256), 256, 0, st>>>(p->roff.p, p->nbin, p->G, p->roff_t.p);
   uint32_t h_slots = 0;
   HIP_CHECK(hipMemcpyAsync(&h_slots, p->roff.p + cells, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st));  // hist / temp are released here
+  HIP_CHECK(hipStreamSynchronize(st));  // hist / scan_tmp are released here
   p->slots = h_slots;
   f->binplan = p;
   return p;
@@ -2026,7 +2009,7 @@ bool reference_top_rank(const wfst_fst* f, std::vector<uint32_t>& rank) {
     if (f->props & props::UNWEIGHTED) return false;  // LifoQueue
     bool unweighted = true;                          // scc_queue_type's scan
     for (const wfst_tr& a : h.arcs)
-      if (!props::is_zero(a.weight) && !props::is_one(a.weight)) {
+      if (weighted(a.weight)) {
         unweighted = false;
         break;
       }
@@ -2167,15 +2150,12 @@ void reverse_csr_build(wfst_ctx* ctx, const wfst_fst* f, RevCsr& r) {
   const uint32_t blocks = (uint32_t)std::min<uint64_t>((f->n_arcs + 255) / 256, (uint64_t)ctx->n_cus * 8);
   rev_count_kernel<<<blocks, 256, 0, st>>>(f->dev.wn, f->n_arcs, indeg.p);
   // rev_off = exclusive scan of the in-degrees (n + 1 outputs: the extra zero input makes rev_off[n] the total)
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, indeg.p, r.off.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(*ctx->pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, indeg.p, r.off.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, indeg.p, r.off.p, (size_t)n + 1);
   HIP_CHECK(hipMemcpyAsync(cursor.p, r.off.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   const uint32_t fblocks = std::min<uint32_t>((uint32_t)ctx->n_cus * 8, (uint32_t)(((uint64_t)n * GROUP + 255) / 256));
   rev_fill_kernel<<<fblocks, 256, 0, st>>>(f->dev.offsets, f->dev.wn, n, cursor.p, r.arc.p);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st));  // indeg / cursor / temp are released here
+  HIP_CHECK(hipStreamSynchronize(st));  // indeg / cursor / scan_tmp are released here
 }
 }  // namespace
 

@@ -1,5 +1,5 @@
 // sssp_binned.h — the DENSE levels of the atomic frontier sweeps as an owner-computes pass ("binned levels").
-// Included by sssp.hip inside namespace wfst { namespace { ... } } after Ctl / enc_f32 / sweep_tau.
+// Included by sssp.hip inside namespace wfst { namespace { ... } } after Ctl / f32_key / sweep_tau.
 //
 // Same recurrence (single_shortest_path, rustfst/src/algorithms/shortest_path.rs:173-239: relax arc (s, w, t) with
 // nd = d[s] (x) w, keep the minimum), same (d, hops) key, same byte-flag frontier and near-far schedule as
@@ -78,7 +78,7 @@ __device__ __forceinline__ void bin_relax_direct(uint64_t* __restrict__ key, uin
   if (ck < old) {
     atomicMin(&shadow[t], enc_c);  // (several lanes may win in turn: the shadow must end at the smallest)
     flags_next[t] = 1;
-    if (dec_f32(enc_c) <= tau) near_cnt += 1u;
+    if (key_f32(enc_c) <= tau) near_cnt += 1u;
     else far_cnt += 1u;
   }
 }
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(BN_THREADS) sssp_bin_expand_kernel(const uint3
     for (uint32_t r = 0; r < 2; ++r) {
       nr[r] = false;
       if (f[r]) {
-        if (dec_f32((uint32_t)(k[r] >> 32)) > tau) {  // far: stays in the frontier, is not relaxed in this level
+        if (key_f32((uint32_t)(k[r] >> 32)) > tau) {  // far: stays in the frontier, is not relaxed in this level
           flags_next[s0 + r] = 1;
           far_cnt += 1u;
           any = true;
@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(BN_THREADS) sssp_bin_expand_kernel(const uint3
         const uint32_t e = e0 + grp + 4 * u;
         const bool has = e < an;
         const uint4 en = w_ent[has ? e : 0u];
-        d[u] = dec_f32(en.x);
+        d[u] = key_f32(en.x);
         hs[u] = en.y;
         i[u] = has ? en.z + sub : 0u;
         end[u] = has ? en.w : 0u;
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(BN_THREADS) sssp_bin_expand_kernel(const uint3
         for (uint32_t u = 0; u < U; ++u) {
           const float c = (d[u] + __uint_as_float(a[u].x)) + 0.0f;  // w1 (x) w2 = f32 add (tropical_weight.rs:60-70)
           if (i[u] < end[u] && c < INF) {                          // +inf never improves (shortest_path.rs:226)
-            const uint32_t enc = enc_f32(c), t = a[u].y;
+            const uint32_t enc = f32_key(c), t = a[u].y;
             if (hs[u] >= hop_cap) {
               bin_relax_direct(key, shadow, flags_next, t, enc, hs[u], tau, near_cnt, far_cnt);
               any = true;
@@ -348,7 +348,7 @@ __global__ void __launch_bounds__(BN_THREADS) sssp_bin_apply_kernel(uint64_t* __
       key[s] = k;
       shadow[s] = (uint32_t)(k >> 32);
       flags_next[s] = 1;
-      if (dec_f32((uint32_t)(k >> 32)) <= tau) near_cnt += 1u;
+      if (key_f32((uint32_t)(k >> 32)) <= tau) near_cnt += 1u;
       else far_cnt += 1u;
     }
   }

@@ -1,6 +1,6 @@
 // sssp_mailbox.h — owner-computes relaxation sweeps ("mailbox sweeps") for sssp.hip.
 //
-// Included by sssp.hip inside namespace wfst { namespace { ... } } after Ctl / enc_f32.
+// Included by sssp.hip inside namespace wfst { namespace { ... } } after Ctl / f32_key.
 //
 // Same recurrence as sssp_relax_kernel (single_shortest_path, rustfst/src/algorithms/shortest_path.rs:173-239:
 // relax arc (s,w,t) with nd = d[s] (x) w, keep the minimum), same (d, hops) key, same near-far schedule — the
@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restri
   }
   for (uint32_t i = tid; i < n; i += nt) {
     const bool is_start = i == start;
-    key[i] = is_start ? (uint64_t)enc_f32(0.0f) << 32 : KEY_INF;
+    key[i] = is_start ? (uint64_t)f32_key(0.0f) << 32 : KEY_INF;
   }
   for (uint32_t i = tid; i < nb * nb; i += nt) {
     mb.cnt[0][i] = 0;
@@ -183,12 +183,12 @@ __global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restri
     mb.wrote[0][i] = 0;
     mb.wrote[1][i] = 0;
     mb.blk_pend[i] = waits && mine ? 1u : 0u;
-    mb.blk_mind[i] = waits && mine ? enc_f32(0.0f) : 0xFFFFFFFFu;
+    mb.blk_mind[i] = waits && mine ? f32_key(0.0f) : 0xFFFFFFFFu;
     mb.blk_far[i] = 0;
     mb.wl_cnt[i] = !waits && mine ? 1u : 0u;
     if (!waits && mine) {
       const uint32_t b = offsets[start], c = offsets[start + 1] - b;
-      mb.wl[(size_t)i * NW_SEG] = make_uint4(start, b, enc_f32(0.0f), min(c, NW_DEG_SAT));
+      mb.wl[(size_t)i * NW_SEG] = make_uint4(start, b, f32_key(0.0f), min(c, NW_DEG_SAT));
     }
   }
   for (uint32_t i = tid; i < IMP_RING; i += nt) improved[i] = 0;
@@ -399,7 +399,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
           if (c == NW_DEG_SAT) c = offsets[en.x + 1] - en.y;
           i_[u] = en.y + sub;
           end_[u] = en.y + c;
-          d_[u] = dec_f32(en.z);
+          d_[u] = key_f32(en.z);
           h1_[u] = (en.w >> MB_LOG) + 1u;
           if (profile && sub == 0) {
             p_arcs += c;
@@ -422,7 +422,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
         for (uint32_t u = 0; u < NW_UNROLL; ++u) {
           const float c = (d_[u] + __uint_as_float(a[u].x)) + 0.0f;  // w1 (x) w2 = f32 add (tropical_weight.rs:60-70)
           v[u] = v[u] && c < INF;                                    // +inf never improves (shortest_path.rs:226)
-          enc[u] = enc_f32(c);
+          enc[u] = f32_key(c);
           ck[u] = ((unsigned long long)enc[u] << 32) | h1_[u];
           old[u] = 0;
           tb[u] = te[u] = 0;
@@ -448,7 +448,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
           if (won) {
             if (h1_[u] >> MB_HOP_BITS) ctl->pad = 1u;  // hop count beyond the message format: the host refuses the result
             bool listed = false;
-            if (dec_f32(enc[u]) <= tau) {
+            if (key_f32(enc[u]) <= tau) {
               const uint32_t slot = atomicAdd(n_out, 1u);
               if (slot < NW_CAP) {
                 out[slot] = make_uint4(a[u].y, tb[u], enc[u], (h1_[u] << MB_LOG) | min(te[u] - tb[u], NW_DEG_SAT));
@@ -691,7 +691,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
     return;
   }
   const bool waiting = bmind != 0xFFFFFFFFu;  // (blk_mind: the least distance among the block's waiting states)
-  if (!any_in && (!waiting || dec_f32(bmind) > tau)) {
+  if (!any_in && (!waiting || key_f32(bmind) > tau)) {
     // nothing arrives and nobody who waits is near: the block sleeps through this sweep
     if (wrote_out) {
       for (uint32_t d = tid; d < nb; d += MB_THREADS) mb.cnt[par_out][(size_t)d * nb + j] = 0;
@@ -757,7 +757,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
       const bool act = chg || ((pw[r] >> (tl & 31u)) & 1u) != 0;
       if (chg) key[s] = kn[r];
       const uint32_t ed = (uint32_t)(kn[r] >> 32);
-      near_[r] = act && dec_f32(ed) <= tau;
+      near_[r] = act && key_f32(ed) <= tau;
       const bool far = act && !near_[r];
       if (far) my_mind = min(my_mind, ed);
       const unsigned long long fm = __ballot(far), nm = __ballot(near_[r]);
@@ -812,7 +812,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
           const unsigned long long k = lkey[tl_[u]];
           const uint32_t b = l_off[tl_[u]];
           end_[u] = l_off[tl_[u] + 1];
-          d_[u] = dec_f32((uint32_t)(k >> 32));
+          d_[u] = key_f32((uint32_t)(k >> 32));
           h1_[u] = (uint32_t)k + 1u;
           if (profile && sub == 0) p_arcs += end_[u] - b;
           i_[u] = b + sub;
@@ -833,7 +833,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
         for (uint32_t u = 0; u < MB_UNROLL; ++u) {
           const float c = (d_[u] + __uint_as_float(a[u].x)) + 0.0f;  // w1 (x) w2 = f32 add (tropical_weight.rs:60-70)
           v[u] = v[u] && c < INF;                                    // +inf never improves (shortest_path.rs:226)
-          enc[u] = enc_f32(c);
+          enc[u] = f32_key(c);
           if (v[u] && (a[u].y >> MB_LOG) == j) {
             atomicMin(&lkey[a[u].y & (MB_B - 1u)], ((unsigned long long)enc[u] << 32) | h1_[u]);
             v[u] = false;

@@ -123,7 +123,7 @@ __device__ __forceinline__ uint32_t rs_expand_round(uint32_t LPS, uint32_t G, ui
     const unsigned long long k = lkey[tl];
     const uint32_t b = l_off[tl], en = l_off[tl + 1];
     const uint32_t h1 = (uint32_t)k + 1u;
-    d[u] = dec_f32((uint32_t)(k >> 32));
+    d[u] = key_f32((uint32_t)(k >> 32));
     hs[u] = h1 << LOG;
     const uint32_t i0 = b + 2u * sub;
     const bool v0 = has && i0 < en, v1 = has && i0 + 1u < en;
@@ -140,7 +140,7 @@ __device__ __forceinline__ uint32_t rs_expand_round(uint32_t LPS, uint32_t G, ui
   // own instead of jumping around the code; the one branch left is the candidate for a state of this very block (LDS
   // atomicMin at once: sent to itself through region (j -> j) it was 85 us in ONE region of the dense level — arc 0 of every
   // state of the benchmark's transducer stays in the block, and a region is read by four lanes).  Distances on this path are
-  // sums of non-negative weights: enc_f32 is "set the sign bit".
+  // sums of non-negative weights: f32_key is "set the sign bit".
   const uint32_t nb_ = (uint32_t)(l_base - l_cur);  // (the three per-destination tables are nb words each, + RS_DUMMY)
   const uint32_t lane31 = threadIdx.x & (RS_DUMMY - 1u);
   for (uint32_t u = 0; u < U; ++u) {
@@ -190,7 +190,7 @@ __device__ __forceinline__ uint32_t rs_expand_round(uint32_t LPS, uint32_t G, ui
         const uint2 ar = wn[i < en ? i : 0u];
         const float c = (d[u] + __uint_as_float(ar.x)) + 0.0f;
         if (i < en && c < INF) {
-          const uint32_t enc1 = enc_f32(c), db = ar.y >> LOG, tl_ = ar.y & (B - 1u);
+          const uint32_t enc1 = f32_key(c), db = ar.y >> LOG, tl_ = ar.y & (B - 1u);
           if (db == j) {
             const unsigned long long c_ = ((unsigned long long)enc1 << 32) | (hs[u] >> LOG);
             if (c_ < atomicMin(&lkey[tl_], c_)) atomicOr(&l_pend[tl_ >> 5], 1u << (tl_ & 31u));
@@ -474,7 +474,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_resident_kernel(const ui
 
     // ---------------- the marked states: near ones listed (and unmarked), far ones keep waiting
     {
-      const uint32_t enc_tau = enc_f32(tau);  // (the encoding is monotone: d <= tau <=> enc(d) <= enc(tau); +inf lists every marked state)
+      const uint32_t enc_tau = f32_key(tau);  // (the encoding is monotone: d <= tau <=> enc(d) <= enc(tau); +inf lists every marked state)
       unsigned long long nm[R];
       uint32_t n_near = 0, n_far = 0;
       for (uint32_t r = 0; r < R; ++r) {

@@ -20,13 +20,12 @@
 #include <algorithm>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
+
+#pragma clang fp contract(off)  // (before tropical.h comes in: its functions compile without contraction here too)
 
 #include "common.h"
 #include "fst_props.h"
-
-#pragma clang fp contract(off)
 
 namespace wfst {
 namespace {
@@ -44,7 +43,6 @@ __device__ __forceinline__ bool key_less(uint64_t lo_a, uint64_t hi_a, uint64_t 
 __device__ __forceinline__ bool same_key(const wfst_tr& a, const wfst_tr& b) {
   return a.ilabel == b.ilabel && a.olabel == b.olabel && a.nextstate == b.nextstate;
 }
-__device__ __forceinline__ bool weq(float a, float b) { return a <= b + props::KDELTA && b <= a + props::KDELTA; }
 
 // one 16-lane group per state: the state's arcs in (ilabel, olabel, nextstate, position) order into `out`
 __global__ __launch_bounds__(TPB) void trsum_sort_kernel(const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ in,
@@ -227,9 +225,7 @@ wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique) {
   const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n * GROUP + TPB - 1) / TPB, (uint64_t)ctx->n_cus * 32));
   trsum_sort_kernel<<<blocks, TPB, 0, st>>>(f->dev.offsets, f->dev.arcs, sorted.p, n, big_list.p, big_count.p);
   HIP_CHECK(hipGetLastError());
-  uint32_t n_big = 0;
-  HIP_CHECK(hipMemcpyAsync(&n_big, big_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  const uint32_t n_big = read_u32(ctx, big_count.p);
   if (n_big) {
     DBuf<uint32_t> k1(pool, E), k1_out(pool, E), idx(pool, E), idx1(pool, E), idx2(pool, E), seg_b(pool, n_big), seg_e(pool, n_big);
     DBuf<uint64_t> k2(pool, E), k2_out(pool, E);
@@ -256,13 +252,8 @@ wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique) {
   DBuf<uint32_t> cnt(pool, (size_t)n + 1), off_out(pool, (size_t)n + 1);
   trsum_flag_kernel<<<blocks, TPB, 0, st>>>(f->dev.offsets, sorted.p, n, unique ? 1 : 0, keep.p, cnt.p);
   HIP_CHECK(hipGetLastError());
-  size_t temp_bytes = 0;
-  HIP_CHECK(rocprim::exclusive_scan(nullptr, temp_bytes, cnt.p, off_out.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  DBuf<uint8_t> temp(pool, temp_bytes);
-  HIP_CHECK(rocprim::exclusive_scan(temp.p, temp_bytes, cnt.p, off_out.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  uint32_t e_out = 0;
-  HIP_CHECK(hipMemcpyAsync(&e_out, off_out.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, cnt.p, off_out.p, (size_t)n + 1);
+  const uint32_t e_out = read_u32(ctx, off_out.p + n);
   DBuf<wfst_tr> arcs_out(pool, e_out);
   trsum_write_kernel<<<blocks, TPB, 0, st>>>(f->dev.offsets, sorted.p, keep.p, n, unique ? 1 : 0, off_out.p, arcs_out.p);
   HIP_CHECK(hipGetLastError());

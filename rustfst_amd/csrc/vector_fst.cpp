@@ -34,7 +34,7 @@ const VecState& state_at(const wfst_vec_fst* f, uint32_t s) {
 }
 // Tr / TropicalWeight PartialEq: labels + nextstate exact, weight within KDELTA (semiring.rs:159-168)
 bool tr_eq(const wfst_tr& a, const wfst_tr& b) {
-  return a.ilabel == b.ilabel && a.olabel == b.olabel && a.nextstate == b.nextstate && props::approx_eq(a.weight, b.weight);
+  return a.ilabel == b.ilabel && a.olabel == b.olabel && a.nextstate == b.nextstate && weq(a.weight, b.weight);
 }
 }  // namespace
 
@@ -169,7 +169,7 @@ wfst_status wfst_vec_fst_equals(const wfst_vec_fst* a, const wfst_vec_fst* b, in
     for (size_t s = 0; s < a->states.size(); ++s) {
       const VecState &x = a->states[s], &y = b->states[s];
       if (x.has_final != y.has_final) return;
-      if (x.has_final && !props::approx_eq(x.final_w, y.final_w)) return;
+      if (x.has_final && !weq(x.final_w, y.final_w)) return;
       if (x.trs.size() != y.trs.size() || x.niepsilons != y.niepsilons || x.noepsilons != y.noepsilons) return;
       for (size_t i = 0; i < x.trs.size(); ++i)
         if (!tr_eq(x.trs[i], y.trs[i])) return;

@@ -619,7 +619,7 @@ def test_arbitrary_f32_weights_bit_exact_vs_canonical_oracle(oracle, monkeypatch
     subnormals, values whose sums overflow, negative weights on a DAG — bit-identical to the canonical oracle (the exact (min,+)
     fixed point of left-folded f32 sums) under the resident launches, the one-level mailbox launches and the atomic
     sweeps (negative weights always take the atomic sweeps).  What this pins: the order-preserving u32 encoding of f32 distances
-    inside the 64-bit keys (enc_f32 / dec_f32, incl. negative values and subnormals), `+ 0.0f` normalisation, +inf candidates
+    inside the 64-bit keys (f32_key / key_f32, incl. negative values and subnormals), `+ 0.0f` normalisation, +inf candidates
     dropped, and that no kernel flushes subnormals.  semirings/semiring.rs:159-168 is the reference's approximate compare this
     engine does not use."""
     monkeypatch.setenv("WFST_SSSP_MAILBOX", "0" if kernel == "atomic" else "1")

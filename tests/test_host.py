@@ -244,3 +244,15 @@ def test_path_props_from_fact_union(tmp_path):
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert " 0 mismatches" in out.stdout
+    # the same program's two other checks (one compilation for the three):
+    # add_tr folded over the two arcs of a state == add_trs_by_facts of the OR of their arc_facts, on every pair of arcs over
+    # all epsilon / acceptor label combinations, both label orders, nextstate on either side of the state and the weights
+    # 0, 0.0005, 0.75 and inf; and path_arc_facts == arc_facts without a predecessor | FACT_NOT_TOP_SORTED
+    out = subprocess.run([str(exe), "arc_facts"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " 0 mismatches" in out.stdout
+    # the host side of tropical.h (wtimes, quantize with delta 1/1024 and 1e-6, the f32 key round trip) bit for bit against
+    # literal restatements on +-0, denormals, +-KDELTA, the values next to FLT_MAX and inf
+    out = subprocess.run([str(exe), "tropical"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " 0 mismatches" in out.stdout

@@ -1203,3 +1203,69 @@ def test_errors(gpu_ctx):
         got = dev_minimize(f, gpu_ctx).to_flat()
         assert_flat_identical(got, minimize_ref(f), "empty")
         assert got["n_states"] == 0 and got["start"] is None
+
+
+# ---------------------------------------------------------------- the facts of an arc, one at a time
+# (fact bit, its pair in the property word when the fact is present / absent): fst_props.h FACT_* and add_trs_by_facts
+FACT_PAIRS = ((1, NOT_ACCEPTOR, ACCEPTOR), (2, I_EPSILONS, NO_I_EPSILONS), (4, EPSILONS, NO_EPSILONS), (8, O_EPSILONS, NO_O_EPSILONS),
+              (16, NOT_I_LABEL_SORTED, I_LABEL_SORTED), (32, NOT_O_LABEL_SORTED, O_LABEL_SORTED), (64, WEIGHTED, UNWEIGHTED),
+              (128, NOT_TOP_SORTED, TOP_SORTED))
+_KD_UP = float(np.nextafter(pw.KDELTA, F32(1.0)))
+
+
+def _fact_fst(rows, finals=(INF, INF, INF), start=2):
+    return make_flat(3, start, rows, list(finals))
+
+
+# name -> (the FST, the facts reverse() finds).  Three states, start 2, arcs running down (2 -> 1 -> 0) and no final state
+# unless the fact needs one: reverse() then adds no super-initial arcs and turns every arc s -> t into (t + 1) -> (s + 1), which
+# runs upwards, so the reversed FST's arcs carry exactly the facts listed (a fact that implies another, as eps:eps does,
+# brings it along).  minimize() sees the same arcs from their own side, running downwards (always "nextstate <= state").
+FACT_CASES = {
+    "none": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]]), 0),
+    "1_not_acceptor": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 4, 0.0, 1)]]), 1),
+    "2_ilabel_epsilon": (_fact_fst([[], [(4, 4, 0.0, 0)], [(0, 4, 0.0, 1)]]), 1 | 2),
+    "4_epsilon": (_fact_fst([[], [(4, 4, 0.0, 0)], [(0, 0, 0.0, 1)]]), 2 | 4 | 8),
+    "8_olabel_epsilon": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 0, 0.0, 1)]]), 1 | 8),
+    # two arcs of one state into one state: the pair is consecutive for minimize() and, reversed, for reverse()
+    # (state 0's in-arcs, in reverse()'s order: the one from state 1, then these two)
+    "16_ilabel_order": (_fact_fst([[], [(1, 1, 0.0, 0)], [(5, 3, 0.0, 0), (3, 4, 0.0, 0)]]), 1 | 16),
+    "32_olabel_order": (_fact_fst([[], [(1, 1, 0.0, 0)], [(3, 5, 0.0, 0), (4, 3, 0.0, 0)]]), 1 | 32),
+    # is_one is the approximate ==: a weight of exactly KDELTA is still one, the next f32 is a weight
+    "64_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, float(pw.KDELTA), 1)]]), 0),
+    "64_weight_above_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, _KD_UP, 1)]]), 64),
+    "64_weighted": (_fact_fst([[], [(4, 4, 0.75, 0)], [(3, 3, 0.0, 1)]]), 64),
+    # one arc running up, 0 -> 1: reversed it runs down
+    "128_not_top_sorted": (_fact_fst([[(3, 3, 0.0, 1)], [], [(4, 4, 0.0, 1)]]), 128),
+    # ... and all of them running up from start 0: minimize() finds no fact at all, reverse() finds both arcs running down
+    "128_top_sorted_for_minimize": (_fact_fst([[(3, 3, 0.0, 1)], [(4, 4, 0.0, 2)], []], start=0), 128),
+    # a final weight that is not one (minimize.hip's FACT_FINAL_WEIGHTED): reverse() turns it into the weight of the
+    # super-initial state's eps:eps arc
+    "256_final_weight": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]], finals=(F32(0.75), INF, INF)), 2 | 4 | 8 | 64),
+    "256_final_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]], finals=(pw.KDELTA, INF, INF)), 2 | 4 | 8),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(FACT_CASES))
+def test_each_arc_fact_reaches_the_property_word(gpu_ctx, oracle, name):
+    """One tiny FST per fact of fst_props.h's arc_facts (and FACT_FINAL_WEIGHTED), uploaded with an EMPTY property word, so
+    that reverse() (rev_facts_kernel and the host loop over the super-initial arcs) and minimize() (facts_kernel) have to
+    find the fact in the content.  reverse(): FST and word are the oracle's, and the word holds, pair by pair, the negative
+    bit of every listed fact and the positive bit of every other one.  minimize(): FST and word are the restatement's, or
+    both refuse the input in the same words (a transducer)."""
+    from helpers import to_oracle
+    import rustfst_amd
+    flat, rev_facts = FACT_CASES[name]
+    assert flat["props"] == 0
+    got = to_device(flat, gpu_ctx).reverse().to_flat()
+    assert_flat_identical(got, to_oracle(oracle, flat).reverse().to_flat(), f"reverse {name}")
+    for bit, present, absent in FACT_PAIRS:
+        assert got["props"] & (present | absent) == (present if rev_facts & bit else absent), f"reverse {name}: fact {bit}"
+    try:
+        want = minimize_ref(flat)
+    except Unsupported as e:
+        with pytest.raises(rustfst_amd.WfstError, match=re.escape(e.args[0])):
+            dev_minimize(flat, gpu_ctx)
+    else:
+        assert_flat_identical(dev_minimize(flat, gpu_ctx).to_flat(), want, f"minimize {name}")
