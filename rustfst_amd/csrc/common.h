@@ -149,7 +149,7 @@ struct wfst_ctx {
   bool resident_hold = false;        // the repeat of a solve whose resident launch gave up: never a resident one
   uint32_t resident_abort_streak = 0;
   bool resident_allowed() const;
-  void resident_aborted();
+  void resident_aborted(int64_t fixed_pause_ms);  // (< 0: the doubling pause; tests fix it)
   void resident_completed() { resident_abort_streak = 0; }
   // wfst_ctx_set_profiling(ctx, 2): no per-launch events; the sweeps of a repeated (predicted) shortest_path query are timed
   // as ONE chain between two events on the stream, without any synchronisation between launches
@@ -165,13 +165,7 @@ struct wfst_ctx {
   };
   std::vector<SweepSample> sweep_trace;  // profiling only: one entry per relaxation launch of the last solve
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // cached HIP graph of one batch of relaxation sweeps (sssp.hip); rebuilt when any node argument changes
-  struct SweepGraph {
-    hipGraphExec_t exec = nullptr;
-    hipGraph_t graph = nullptr;
-    uint64_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  } sweep_graph[3];  // [0]: first batch of a solve (predicted length), [1]: 8 sweeps per replay, [2]: 64
-  wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags (its address is baked into the graphs)
+  wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags: [0] first batch of a solve, [1] batches of 8 sweeps, [2] of 64
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
   // the last wfst_determinize_batch / wfst_determinize_with_distance_batch call (wfst_ctx_get_determinize_batch_stats)
   uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
@@ -298,7 +292,7 @@ struct wfst_fst {
   mutable std::shared_ptr<wfst::DBuf<uint2>> anext;
   mutable int ieps_state = 0;  // 0 unknown, 1 no input epsilons, 2 has input epsilons
   mutable std::atomic<uint32_t> sp_queries{0};
-  mutable std::atomic<uint32_t> last_sweeps{0};  // sweeps the last relaxation of this FST needed (sizes the first graph replay)
+  mutable std::atomic<uint32_t> last_sweeps{0};  // sweeps the last relaxation of this FST needed (sizes the first batch of the next)
   // mailbox sweeps: bit k set = launch k of the last solve was NOT a busy wide sweep (idle, hand-over or narrow launch):
   // the next solve gates that launch's bulk loads behind its mode / sleep decision
   mutable std::atomic<uint64_t> last_hint_mask{~0ull};

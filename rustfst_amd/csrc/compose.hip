@@ -1490,7 +1490,7 @@ void launch(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const FstView&
   launch_end(ctx, run);
 }
 
-// builds the reference's linear shortest-path FST (see sssp.hip::build_path_fst)
+// builds the reference's linear shortest-path FST (see fst_store.hip::make_path_fst)
 wfst_fst* path_to_fst(wfst_ctx* ctx, const Result& r, const wfst_tr* path_arcs) {
   HostCsr h;
   uint32_t n_states = 0;

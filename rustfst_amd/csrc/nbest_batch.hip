@@ -461,7 +461,7 @@ namespace {
 //   parents   one pass over the arcs: the predecessor sssp_parent_kernel would select for every state (class, source,
 //             position), kept in LDS next to the keys;
 //   walk      one lane follows the parents from the final state; the arcs of the walk go to pinned memory in the order
-//             build_path_fst expects (arc k enters the k-th created state).
+//             make_path_fst expects (arc k enters the k-th created state).
 // The result is what shortest_path_n1 returns for the same FST, bit for bit.  A lone solve through the relaxation kernels
 // costs ~0.5 ms whatever the size (a dozen launches and three synchronisations): 64 composed lattices one after the
 // other were 36 ms; here they are one launch.

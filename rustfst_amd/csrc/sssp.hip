@@ -20,6 +20,8 @@
 #include <cstddef>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
+#include <optional>
 
 #include <fcntl.h>
 #include <sys/file.h>
@@ -31,12 +33,6 @@
 namespace wfst {
 
 namespace {
-
-inline uint32_t __float_as_uint_host(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
 
 constexpr uint64_t KEY_INF = ~0ull;
 constexpr uint32_t GROUP = 16;  // lanes cooperating on one frontier state (average fan-out ~10)
@@ -65,7 +61,7 @@ constexpr uint32_t PROF_SHARDS = 64;
 constexpr uint32_t IMP_RING = 512;  // per-sweep "something happened" flags, indexed by sweep % IMP_RING
 
 struct Ctl {
-  uint32_t base;          // first sweep index of the batch being replayed (graph nodes add their static offset)
+  uint32_t base;          // first sweep index of the batch being replayed (its launches add their static offsets)
   float tau0;             // threshold of sweep 0 (a multiple of delta)
   uint32_t tau[RING];     // f32 bits of the threshold used by sweep k (written by sweep k, read by sweep k+1)
   // number of activations with d <= tau_k made by sweep k: counter sharded 16 ways, shard j at [j * NEAR_STRIDE]
@@ -198,7 +194,7 @@ __global__ void __launch_bounds__(256) sssp_relax_kernel(const uint32_t* __restr
                                                          uint32_t dense_low) {
   // `dense_low` (binned levels, sssp_binned.h; 0xFFFFFFFF = never): this launch is the first of its slot — it predicts the
   // level's frontier, publishes the mode, and leaves the level to the binned kernels behind it when the frontier is that large
-  // the sweep index is (device-side batch base) + (static offset of this launch / graph node)
+  // the sweep index is (device-side batch base) + (static offset of this launch)
   const uint32_t sweep = ctl->base + sweep_offset;
   uint32_t* improved = improved_ring + (sweep % IMP_RING);
   __shared__ uint32_t s_any;   // some activity (improvement or deferral) in this workgroup
@@ -1117,9 +1113,8 @@ bool wfst_ctx::resident_allowed() const {
   if (resident_retry_at_ns == 0) return true;
   return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() >= resident_retry_at_ns;
 }
-void wfst_ctx::resident_aborted() {
-  int64_t pause_ms = 50ll << std::min<uint32_t>(resident_abort_streak, 6u);
-  if (const char* e = std::getenv("WFST_SSSP_RES_RETRY_MS")) pause_ms = std::max<long long>(0ll, std::atoll(e));  // tests
+void wfst_ctx::resident_aborted(int64_t fixed_pause_ms) {
+  const int64_t pause_ms = fixed_pause_ms >= 0 ? fixed_pause_ms : 50ll << std::min<uint32_t>(resident_abort_streak, 6u);
   resident_abort_streak += 1;
   resident_retry_at_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() +
                          pause_ms * 1000000ll;
@@ -1128,7 +1123,75 @@ void wfst_ctx::resident_aborted() {
 namespace wfst {
 namespace {
 
+// The WFST_SSSP_* variables a solve reads (experiments and tests), in the order of the appendix of DESIGN.md, which says what
+// each one does.  An empty optional / null / false = not set: the default stands where the variable is used.
+struct Knobs {
+  std::optional<int> mailbox;           // WFST_SSSP_MAILBOX
+  std::optional<uint32_t> narrow;       // WFST_SSSP_NARROW
+  std::optional<bool> hint;             // WFST_SSSP_HINT
+  bool big = false;                     // WFST_SSSP_BIG
+  std::optional<uint32_t> stg;          // WFST_SSSP_STG
+  std::optional<float> delta;           // WFST_SSSP_DELTA
+  std::optional<uint32_t> near_low;     // WFST_SSSP_NEAR_LOW
+  float tau0_mult = 1.0f;               // WFST_SSSP_TAU0_MULT
+  std::optional<uint32_t> chase_cap, chase_rounds, chase_low;  // WFST_SSSP_CHASE_CAP / _ROUNDS / _LOW
+  const char* mbox_trace = nullptr;     // WFST_SSSP_MBOX_TRACE
+  int resident = 1;                     // WFST_SSSP_RESIDENT
+  std::optional<uint32_t> res_levels;   // WFST_SSSP_RES_LEVELS
+  std::optional<long long> res_tlim_us; // WFST_SSSP_RES_TLIM_US
+  bool log12 = false;                   // WFST_SSSP_LOG12 (by presence)
+  const char* res_trace = nullptr;      // WFST_SSSP_RES_TRACE
+  int binned = 0;                       // WFST_SSSP_BINNED
+  std::optional<long long> dense_low;   // WFST_SSSP_DENSE_LOW
+  bool bin_log14 = false;               // WFST_SSSP_BIN_LOG
+  std::optional<uint32_t> bin_hopcap;   // WFST_SSSP_BIN_HOPCAP
+  int64_t res_retry_ms = -1;            // WFST_SSSP_RES_RETRY_MS (-1: the doubling pause)
+  bool test_fail_log13 = false;         // WFST_SSSP_TEST_FAIL_LOG13 (by presence)
+  bool event_wait = false;              // WFST_SSSP_EVENT_WAIT (by presence)
+  bool log13 = false;                   // WFST_SSSP_LOG13
+  std::optional<int> lps;               // WFST_SSSP_LPS
+  std::optional<int> umax;              // WFST_SSSP_UMAX
+  bool split_tail = false;              // WFST_SSSP_SPLIT_TAIL (by presence)
+  bool count_atomics = false;           // WFST_SSSP_COUNT_ATOMICS (by presence)
+};
+
+// Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
+Knobs read_knobs() {
+  Knobs k;
+  if (const char* e = std::getenv("WFST_SSSP_MAILBOX")) k.mailbox = std::atoi(e);
+  if (const char* e = std::getenv("WFST_SSSP_NARROW")) k.narrow = (uint32_t)std::atol(e);
+  if (const char* e = std::getenv("WFST_SSSP_HINT")) k.hint = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WFST_SSSP_BIG")) k.big = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WFST_SSSP_STG")) k.stg = (uint32_t)std::atoi(e);
+  if (const char* e = std::getenv("WFST_SSSP_DELTA")) k.delta = (float)std::atof(e);
+  if (const char* e = std::getenv("WFST_SSSP_NEAR_LOW")) k.near_low = (uint32_t)std::atol(e);
+  if (const char* e = std::getenv("WFST_SSSP_TAU0_MULT")) k.tau0_mult = (float)std::atof(e);
+  if (const char* e = std::getenv("WFST_SSSP_CHASE_CAP")) k.chase_cap = std::min<uint32_t>((uint32_t)std::atol(e), CHASE_MAX);
+  if (const char* e = std::getenv("WFST_SSSP_CHASE_ROUNDS")) k.chase_rounds = (uint32_t)std::atol(e);
+  if (const char* e = std::getenv("WFST_SSSP_CHASE_LOW")) k.chase_low = (uint32_t)std::atol(e);
+  k.mbox_trace = std::getenv("WFST_SSSP_MBOX_TRACE");
+  if (const char* e = std::getenv("WFST_SSSP_RESIDENT")) k.resident = std::atoi(e);
+  if (const char* e = std::getenv("WFST_SSSP_RES_LEVELS")) k.res_levels = std::max<uint32_t>(2u, std::min<uint32_t>(RS_LEVEL_CAP, (uint32_t)std::atol(e)));
+  if (const char* e = std::getenv("WFST_SSSP_RES_TLIM_US")) k.res_tlim_us = std::atoll(e);
+  k.log12 = std::getenv("WFST_SSSP_LOG12") != nullptr;
+  k.res_trace = std::getenv("WFST_SSSP_RES_TRACE");
+  if (const char* e = std::getenv("WFST_SSSP_BINNED")) k.binned = std::atoi(e);
+  if (const char* e = std::getenv("WFST_SSSP_DENSE_LOW")) k.dense_low = std::atoll(e);
+  if (const char* e = std::getenv("WFST_SSSP_BIN_LOG")) k.bin_log14 = std::atoi(e) == 14;
+  if (const char* e = std::getenv("WFST_SSSP_BIN_HOPCAP")) k.bin_hopcap = (uint32_t)std::atol(e);
+  if (const char* e = std::getenv("WFST_SSSP_RES_RETRY_MS")) k.res_retry_ms = std::max<long long>(0ll, std::atoll(e));
+  k.test_fail_log13 = std::getenv("WFST_SSSP_TEST_FAIL_LOG13") != nullptr;
+  k.event_wait = std::getenv("WFST_SSSP_EVENT_WAIT") != nullptr;
+  if (const char* e = std::getenv("WFST_SSSP_LOG13")) k.log13 = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WFST_SSSP_LPS")) k.lps = std::max(2, std::min(8, std::atoi(e)));
+  if (const char* e = std::getenv("WFST_SSSP_UMAX")) k.umax = std::atoi(e) >= 4 ? 4 : 2;
+  k.split_tail = std::getenv("WFST_SSSP_SPLIT_TAIL") != nullptr;
+  k.count_atomics = std::getenv("WFST_SSSP_COUNT_ATOMICS") != nullptr;
+  return k;
+}
+
 struct Solve {
+  Knobs kn;  // as the environment stood when relax_setup began this solve
   DBuf<uint64_t> key;
   DBuf<uint32_t> shadow;  // enc(d) half of the keys, for the pre-check gathers
   DBuf<uint8_t> flags;  // two frontiers of n bytes
@@ -1154,10 +1217,12 @@ struct Solve {
   uint64_t hint_mask = ~0ull;  // mailbox: bit k = launch k of this FST's last solve was not a busy WIDE sweep (gated launch)
   size_t mb_dyn = 0;         // dynamic LDS bytes of a mailbox launch
   bool force_big = false;    // tests: the many-blocks variant of the kernel on a small FST (WFST_SSSP_BIG=1)
+  decltype(&sssp_mbox_kernel<false>) mbox_kernel = nullptr;  // the variant for this many blocks (bind_mailbox)
   // resident launches (sssp_resident.h): the WIDE levels of the solve inside ONE launch, every workgroup on a CU of its own
   bool resident = false;
   uint32_t log = 12;         // log2 of the block size (13: every launch of the solve is a resident one)
   size_t res_dyn = 0;        // dynamic LDS bytes of a resident launch
+  decltype(&sssp_mbox_resident_kernel<12>) res_kernel = nullptr;  // the variant for this block size (bind_resident)
   DBuf<uint2> rs_msgs;       // two parity buffers of plan->res_units entries
   DBuf<uint32_t> rs_abort;   // one word
   DBuf<unsigned long long> rs_trace;  // WFST_SSSP_RES_TRACE=<file>: per-level stamps
@@ -1173,7 +1238,19 @@ struct Solve {
   BinView bv{};
   uint32_t dense_low = 0xFFFFFFFFu;  // predicted frontier from which a level is a binned one
   size_t bn_dyn_expand = 0, bn_dyn_apply = 0;
+  decltype(&sssp_bin_expand_kernel<13>) bin_expand_kernel = nullptr;  // the variants for this bin size (bind_binned)
+  decltype(&sssp_bin_apply_kernel<13>) bin_apply_kernel = nullptr;
 };
+
+// Raises the dynamic-LDS limit of `kernels`, once per device (a function attribute is per device); `once` belongs to the call site.
+struct OncePerDevice {
+  std::once_flag flag[64];
+};
+void raise_dynamic_lds(OncePerDevice& once, int device, int bytes, std::initializer_list<const void*> kernels) {
+  std::call_once(once.flag[(unsigned)device & 63u], [&] {
+    for (const void* k : kernels) HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  });
+}
 
 constexpr uint32_t MAX_BATCH = 64;
 
@@ -1187,7 +1264,7 @@ bool mbox_eligible(const wfst_fst* f) {
 
 // Region plan of the mailbox sweeps: arcs between every pair of blocks, scanned into region offsets.  Depends only on
 // the (source, target) pairs of the arcs, so tr_sort leaves it valid; cached on the handle (owner's pool).
-std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t log) {
+std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t log, const Knobs& kn) {
   std::lock_guard<std::mutex> lk(f->cache_mu);
   std::shared_ptr<MboxPlan>& slot = log == 13 ? f->mbox13 : f->mbox;
   if (slot) return slot;
@@ -1201,8 +1278,8 @@ std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t l
   p->roff = DBuf<uint32_t>(owner_pool, cells + 1);
   p->roff_t = DBuf<uint32_t>(owner_pool, cells);
   DBuf<uint32_t> hist(*ctx->pool, cells + 1);
-  if (log == 13) mbox_hist_kernel<13><<<nb, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, nb, hist.p);
-  else mbox_hist_kernel<12><<<nb, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, nb, hist.p);
+  const auto hist_kernel = log == 13 ? mbox_hist_kernel<13> : mbox_hist_kernel<12>;
+  hist_kernel<<<nb, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, nb, hist.p);
   HIP_CHECK(hipMemsetAsync(hist.p + cells, 0, sizeof(uint32_t), st));
   const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, hist.p, p->roff.p, cells + 1);
   mbox_transpose_kernel<<<(uint32_t)((cells + 255) / 256), 256, 0, st>>>(p->roff.p, nb, p->roff_t.p);
@@ -1228,7 +1305,7 @@ std::shared_ptr<MboxPlan> mbox_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t l
         p->lps = l;
         break;
       }
-    if (const char* e = std::getenv("WFST_SSSP_LPS")) p->lps = std::max(2, std::min(8, std::atoi(e)));
+    if (kn.lps) p->lps = (uint32_t)*kn.lps;
   }
   uint32_t h_units = 0;
   if (nb <= MB_NBMAX) {  // the resident kernel's regions: header + one slot per arc, 64-byte aligned
@@ -1270,8 +1347,8 @@ std::shared_ptr<BinPlan> bin_plan(wfst_ctx* ctx, const wfst_fst* f, uint32_t log
   p->roff = DBuf<uint32_t>(owner_pool, cells + 1);
   p->roff_t = DBuf<uint32_t>(owner_pool, cells);
   DBuf<uint32_t> hist(*ctx->pool, cells + 1);
-  if (logd == 14) bin_hist_kernel<14><<<p->G, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, p->sg, p->nbin, p->G, hist.p);
-  else bin_hist_kernel<13><<<p->G, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, p->sg, p->nbin, p->G, hist.p);
+  const auto hist_kernel = logd == 14 ? bin_hist_kernel<14> : bin_hist_kernel<13>;
+  hist_kernel<<<p->G, 1024, 0, st>>>(f->dev.offsets, f->dev.wn, n, p->sg, p->nbin, p->G, hist.p);
   HIP_CHECK(hipMemsetAsync(hist.p + cells, 0, sizeof(uint32_t), st));
   const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, hist.p, p->roff.p, cells + 1);
   bin_transpose_kernel<<<(uint32_t)((cells + 255) / 256), 256, 0, st>>>(p->roff.p, p->nbin, p->G, p->roff_t.p);
@@ -1303,62 +1380,37 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
     // resident launches take the odd slots: slot 0 is the head of the search (NARROW), a resident launch runs every WIDE
     // level that follows and the hand-over, the next slot is the NARROW launch that drains the search; whichever kernel
     // finds another mode in its slot does that mode's work (the two kernels leave the same state behind)
-    if (sv.log == 13) {  // (blocks of 8192 states exist in the resident kernel only: it also runs the NARROW launches of such a solve)
-      if (abs_sweep >= RS_MAX_SWEEP) throw Error("shortest_path: relaxation did not converge");
-      sssp_mbox_resident_kernel<13><<<sv.mv.nb, MB_THREADS, sv.res_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, sv.rv, abs_sweep & 1u, n,
-                                                                             sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low,
-                                                                             sv.narrow_t, sv.res_max_levels, sv.res_lps_umax);
-    } else if (sv.resident && !profile && (abs_sweep & 1u) && abs_sweep < RS_MAX_SWEEP)
-      sssp_mbox_resident_kernel<12><<<sv.mv.nb, MB_THREADS, sv.res_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, sv.rv, abs_sweep & 1u, n,
-                                                                             sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low,
-                                                                             sv.narrow_t, sv.res_max_levels, sv.res_lps_umax);
-    else if (sv.mv.nb > MB_NBMAX || sv.force_big)
-      sssp_mbox_kernel<true><<<sv.mv.nb, MB_THREADS, sv.mb_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n,
-                                                                      sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low,
-                                                                      profile, hint, sv.narrow_t);
+    // (blocks of 8192 states exist in the resident kernel only: it also runs the NARROW launches of such a solve)
+    if (sv.log == 13 && abs_sweep >= RS_MAX_SWEEP) throw Error("shortest_path: relaxation did not converge");
+    if (sv.log == 13 || (sv.resident && !profile && (abs_sweep & 1u) && abs_sweep < RS_MAX_SWEEP))
+      sv.res_kernel<<<sv.mv.nb, MB_THREADS, sv.res_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, sv.rv, abs_sweep & 1u, n,
+                                                              sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, sv.narrow_t,
+                                                              sv.res_max_levels, sv.res_lps_umax);
     else
-      sssp_mbox_kernel<false><<<sv.mv.nb, MB_THREADS, sv.mb_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n,
-                                                                       sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low,
-                                                                       profile, hint, sv.narrow_t);
-  }
-  else {
-    sssp_relax_kernel<<<sv.blocks, 256, 0, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.fl[j & 1u], sv.fl[(j & 1u) ^ 1u], n,
-                                                 sv.improved.p, sv.ctl.p, off, sv.delta, sv.near_low, sv.shadow.p, sv.chase_cap,
-                                                 sv.chase_rounds, sv.chase_low, profile, sv.binned ? sv.dense_low : 0xFFFFFFFFu);
+      sv.mbox_kernel<<<sv.mv.nb, MB_THREADS, sv.mb_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n,
+                                                              sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile, hint,
+                                                              sv.narrow_t);
+  } else {
+    uint8_t* const cur = sv.fl[j & 1u];
+    uint8_t* const next = sv.fl[(j & 1u) ^ 1u];
+    sssp_relax_kernel<<<sv.blocks, 256, 0, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, cur, next, n, sv.improved.p, sv.ctl.p, off,
+                                                 sv.delta, sv.near_low, sv.shadow.p, sv.chase_cap, sv.chase_rounds, sv.chase_low,
+                                                 profile, sv.binned ? sv.dense_low : 0xFFFFFFFFu);
     if (sv.binned) {  // the same level as an owner-computes pass: both leave at once unless the launch above published a dense level
-      if (sv.bplan->logd == 14) {
-        sssp_bin_expand_kernel<14><<<sv.bv.G, BN_THREADS, sv.bn_dyn_expand, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.fl[j & 1u],
-                                                                                  sv.fl[(j & 1u) ^ 1u], n, sv.improved.p, sv.ctl.p, off,
-                                                                                  sv.shadow.p, sv.bv, profile);
-        sssp_bin_apply_kernel<14><<<sv.bv.nbin, BN_THREADS, sv.bn_dyn_apply, st>>>(sv.key.p, sv.shadow.p, sv.fl[(j & 1u) ^ 1u], n,
-                                                                                   sv.improved.p, sv.ctl.p, off, sv.bv);
-      } else {
-        sssp_bin_expand_kernel<13><<<sv.bv.G, BN_THREADS, sv.bn_dyn_expand, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.fl[j & 1u],
-                                                                                  sv.fl[(j & 1u) ^ 1u], n, sv.improved.p, sv.ctl.p, off,
-                                                                                  sv.shadow.p, sv.bv, profile);
-        sssp_bin_apply_kernel<13><<<sv.bv.nbin, BN_THREADS, sv.bn_dyn_apply, st>>>(sv.key.p, sv.shadow.p, sv.fl[(j & 1u) ^ 1u], n,
-                                                                                   sv.improved.p, sv.ctl.p, off, sv.bv);
-      }
+      sv.bin_expand_kernel<<<sv.bv.G, BN_THREADS, sv.bn_dyn_expand, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, cur, next, n,
+                                                                          sv.improved.p, sv.ctl.p, off, sv.shadow.p, sv.bv, profile);
+      sv.bin_apply_kernel<<<sv.bv.nbin, BN_THREADS, sv.bn_dyn_apply, st>>>(sv.key.p, sv.shadow.p, next, n, sv.improved.p, sv.ctl.p,
+                                                                           off, sv.bv);
     }
   }
 }
 
-// relax_setup allocates and initialises the state of a solve (keys, frontier flags, control block) and fixes its schedule parameters
-void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
+// ---- relax_setup, piece by piece: the band, the block size and the lease, the mailbox plan, the two views, the binned levels
+
+// near-far only pays on branching graphs (label-correcting re-relaxes them many times); on lattices every
+// arc is relaxed once anyway.  delta = 1.5 x mean arc weight; +inf = plain frontier sweeps.
+float band_from_mean_weight(const wfst_fst* f, const Knobs& kn) {
   const uint32_t n = f->n_states;
-  DevicePool& pool = *ctx->pool;
-  sv.key = DBuf<uint64_t>(pool, n);
-  sv.shadow = DBuf<uint32_t>(pool, n);
-  const size_t n_pad = ((size_t)n + 15) & ~(size_t)15;
-  sv.flags = DBuf<uint8_t>(pool, 2 * n_pad);
-  sv.improved = DBuf<uint32_t>(pool, IMP_RING);
-  sv.ctl = DBuf<Ctl>(pool, 1);
-  hipStream_t st = ctx->stream;
-  sv.fl[0] = sv.flags.p;
-  sv.fl[1] = sv.flags.p + n_pad;
-  sv.blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)ctx->n_cus * 8, (n + 255) / 256));
-  // near-far only pays on branching graphs (label-correcting re-relaxes them many times); on lattices every
-  // arc is relaxed once anyway.  delta = 1.5 x mean arc weight; +inf = plain frontier sweeps.
   float delta = INF;
   if (!f->has_negative && f->mean_weight > 0.0f && n >= 65536 && f->n_arcs >= 2ull * n) {
     delta = 1.5f * f->mean_weight;
@@ -1371,311 +1423,333 @@ void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
     const double deg = (double)f->n_arcs / (double)n;
     if (deg > 10.0 || deg < 8.5) delta = (float)(delta * 10.0 / deg);
   }
-  if (const char* e = std::getenv("WFST_SSSP_DELTA")) delta = (float)std::atof(e);  // experiments / tests
-  if (!(delta > 0.0f)) delta = INF;
-  sv.delta = delta;
-  sv.near_low = 4096;  // activations below which a sweep is launch-latency bound anyway
-  if (const char* e = std::getenv("WFST_SSSP_NEAR_LOW")) sv.near_low = (uint32_t)std::atol(e);
-  float tau0_mult = 1.0f;  // first band = tau0_mult x delta
-  if (const char* e = std::getenv("WFST_SSSP_TAU0_MULT")) tau0_mult = (float)std::atof(e);
+  if (kn.delta) delta = *kn.delta;  // experiments / tests
+  return delta > 0.0f ? delta : INF;
+}
+
+// The band once more, now that the plan knows the states' CHEAPEST arcs: the rule above reads the mean weight as if the
+// weights were uniform on [0, 2 mean) — a state's best of d arcs then costs 2 mean / (d + 1).  Where the cheapest arcs are
+// much cheaper than that (exponential, log-normal weights: a shortest path is made of them) the band shrinks by the same
+// ratio; where every arc costs about the same (unit weights: the search is a breadth-first one) it widens a little.
+// 1M states, fan-out 10 (tools/weight_shapes.py): exponential 410 -> 241 us, unit weights 205 -> ~125; uniform weights
+// (ratio 0.9 .. 1.1): untouched.
+float band_from_cheapest_arcs(const wfst_fst* f, const MboxPlan& plan, float delta, const Knobs& kn) {
+  if (!(delta < INF) || kn.delta || !(plan.mean_min_w > 0.0f) || !(f->mean_weight > 0.0f)) return delta;
+  const double deg = (double)f->n_arcs / (double)f->n_states;
+  const double ratio = (double)plan.mean_min_w * (deg + 1.0) / (2.0 * (double)f->mean_weight);
+  if (ratio < 0.7) return (float)(delta * std::max(ratio, 0.1));
+  if (ratio > 2.0) return delta * 1.4f;
+  return delta;
+}
+
+// log2 of the block size with which the blocks of a resident solve each get a compute unit of their own — 4096 states, or
+// 8192 for the FSTs of 1M .. 2M states that then still fit one block per CU (every launch of such a solve is a resident
+// one) —, 0 when neither does.
+uint32_t resident_block_log(const wfst_ctx* ctx, uint32_t n, const Knobs& kn) {
+  const uint32_t cus = (uint32_t)std::min<int>(ctx->n_cus, (int)MB_NBMAX);
+  const uint32_t nb12 = (n + 4095u) >> 12, nb13 = (uint32_t)(((uint64_t)n + 8191u) >> 13);
+  // wfst_ctx_set_resident_share(ctx, 1): the resident grid may hold at most half of the compute units, so that a large batch
+  // kernel of another context runs BESIDE it (a resident workgroup needs a compute unit of its own; a grid that wants 245 of
+  // 256 waits for whatever holds more than 11 of them).  8192-state blocks where that is enough, one launch per level otherwise.
+  if (ctx->resident_share == 1u) {
+    const uint32_t half = cus / 2u;
+    if (nb12 <= half) return 12;
+    return nb13 <= half && !kn.log12 ? 13 : 0;
+  }
+  if (nb12 <= cus) return nb13 <= cus && kn.log13 ? 13 : 12;  // (WFST_SSSP_LOG13, experiments: half the workgroups)
+  return nb13 <= cus && !kn.log12 ? 13 : 0;
+}
+
+// Resident launches (sssp_resident.h) need every block on a CU of its own for the whole launch, and only one such solve
+// runs per device at a time: the lease is taken first, because it decides the block size (sv.log).  Not under the per-sweep
+// profiler (it times launches), not after a launch of this context gave up waiting.  true = this solve holds the lease.
+bool lease_resident(wfst_ctx* ctx, uint32_t n, Solve& sv) {
+  const uint32_t log = resident_block_log(ctx, n, sv.kn);
+  if (!(sv.kn.resident && log && !ctx->profiling && ctx->resident_allowed() && !sv.kn.big &&
+        sv.lease.acquire(ctx->device, ctx->resident_share == 1u ? 1 : 2)))
+    return false;
+  sv.log = log;
+  return true;
+}
+
+constexpr size_t RES_LDS_BYTES = 160u * 1024u;  // LDS of a compute unit
+// Staging slots per destination that a resident launch on this plan has, 0 when such a launch is not possible: no resident
+// regions (more than MB_NBMAX blocks), a region buffer beyond the buffer-descriptor range, or an LDS without room for 4 slots
+// (up to MB_NBMAX blocks the one-level kernel's budget allows RS_STG_MAX of them, so what is returned is 0 or at least 4).
+// (deeper than the one-level kernel's slots where the LDS has room: a round of the resident kernel holds up to 4 x 16 x
+// (64 / lps) states, 768 with 5 lanes per state)
+uint32_t resident_staging(const MboxPlan& plan) {
+  if (plan.res_units == 0 || plan.res_units * sizeof(uint2) >= 0x7FFFFFF0ull) return 0;
+  const uint32_t nb = plan.nb;
+  const size_t fixed = res_lds_bytes(plan.log, nb, 0);
+  if (fixed + 8u * 4u * nb > RES_LDS_BYTES) return 0;
+  const uint32_t stg_lim = std::min<uint32_t>(RS_STG_MAX, (MB_DYN_BUDGET - 12u * nb) / (8u * nb));  // (the one-level kernel's budget)
+  return (uint32_t)std::min<size_t>(stg_lim, (RES_LDS_BYTES - fixed) / (8u * nb));
+}
+
+// The plan and the buffers of the mailbox sweeps (sv.mbox), with those of the resident launches when `want_res`; returns
+// whether the solve still has the latter.
+// Two message buffers of one slot per arc, the nb^2 region tables and counts come from the pool: on a tight pool (or a
+// dense graph) the atomic sweeps, which need none of it, run instead.  The 8192-state plan exists in the resident kernel
+// only: when it cannot be had (the pool, a region buffer beyond the buffer-descriptor range, no room for staging), the
+// solve is planned again with 4096-state blocks and one launch per level — never refused.
+bool plan_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
+  DevicePool& pool = *ctx->pool;
+  auto release_all = [&] {
+    want_res = false;
+    sv.rs_msgs.reset();
+    sv.rs_abort.reset();
+    sv.lease.release();
+    sv.plan.reset();
+    sv.mb_msgs.reset();
+    sv.mb_words.reset();
+    sv.mb_wl.reset();
+    sv.mbox = false;
+  };
+  auto try_plan = [&](uint32_t log, bool res) -> bool {
+    try {
+      sv.log = log;
+      sv.plan = mbox_plan(ctx, f, log, sv.kn);
+      const uint32_t nb = sv.plan->nb;
+      if (res && resident_staging(*sv.plan) == 0) {
+        if (log == 13) throw Error("resident launch not possible");
+        res = false;
+        sv.lease.release();
+      }
+      sv.mb_msgs = DBuf<uint2>(pool, 2 * (size_t)f->n_arcs);
+      const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << log) / 32);
+      sv.mb_words = DBuf<uint32_t>(pool, 2 * w_cnt + 2 * nb + w_pend + 4 * nb);
+      sv.mb_wl = DBuf<uint4>(pool, (size_t)nb << log);
+      if (res) {  // what the resident launch needs beyond the plan
+        sv.rs_msgs = DBuf<uint2>(pool, 2 * (size_t)sv.plan->res_units);
+        sv.rs_abort = DBuf<uint32_t>(pool, 16);
+      }
+      want_res = res;
+      sv.mbox = true;
+      return true;
+    } catch (const Error&) {
+      (void)hipGetLastError();  // (a refused allocation must not surface at the next launch check)
+      release_all();
+      return false;
+    }
+  };
+  if (sv.kn.test_fail_log13 && sv.log == 13) {  // tests: the 8192-state plan refused
+    release_all();
+    try_plan(12, false);
+  } else if (!try_plan(sv.log, want_res) && sv.log == 13) {
+    try_plan(12, false);
+  }
+  if (!sv.mbox) sv.log = 12;
+  return want_res;
+}
+
+// MboxView over the planned buffers, and the schedule of a solve that takes one launch per level
+void bind_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
+  const uint32_t n = f->n_states, nb = sv.plan->nb;
+  const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << sv.log) / 32);
+  MboxView& mv = sv.mv;
+  mv.roff = sv.plan->roff.p;
+  mv.roff_t = sv.plan->roff_t.p;
+  mv.msgs[0] = sv.mb_msgs.p;
+  mv.msgs[1] = sv.mb_msgs.p + f->n_arcs;
+  uint32_t* w = sv.mb_words.p;
+  mv.cnt[0] = w;
+  mv.cnt[1] = w + w_cnt;
+  w += 2 * w_cnt;
+  mv.wrote[0] = w;
+  mv.wrote[1] = w + nb;
+  w += 2 * nb;
+  mv.pend = w;
+  w += w_pend;
+  mv.blk_pend = w;
+  mv.blk_mind = w + nb;
+  mv.blk_far = w + 2 * nb;
+  mv.wl_cnt = w + 3 * nb;
+  mv.wl = sv.mb_wl.p;
+  mv.nb = nb;
+  // staging depth: what the dynamic LDS budget leaves after the three per-destination tables
+  mv.stg = std::max<uint32_t>(1u, std::min<uint32_t>(MB_STG_MAX, (MB_DYN_BUDGET - 12u * nb) / (8u * nb)));
+  if (sv.kn.stg) mv.stg = std::max<uint32_t>(1u, std::min<uint32_t>(mv.stg, *sv.kn.stg));
+  sv.force_big = sv.kn.big;
+  sv.mbox_kernel = nb > MB_NBMAX || sv.force_big ? sssp_mbox_kernel<true> : sssp_mbox_kernel<false>;
+  sv.mb_dyn = (size_t)nb * mv.stg * sizeof(uint2) + 3u * (size_t)nb * sizeof(uint32_t);
+  static OncePerDevice lds_once;
+  raise_dynamic_lds(lds_once, ctx->device, (int)MB_DYN_BUDGET, {(const void*)sssp_mbox_kernel<false>, (const void*)sssp_mbox_kernel<true>});
+  // A mailbox sweep costs its ~10 us chain of dependent trips whatever it expands, up to ~256 states per block: the
+  // threshold moves on as soon as the near set is below 1/16 of the states (measured, tools/param_sweep.py: 4096 ->
+  // 65536 at 1M / 2M states is 0.407 -> 0.386 and 0.817 -> 0.741 ms; at 300 k states 16384 is the best)
+  if (!sv.kn.near_low) sv.near_low = std::min<uint32_t>(65536u, std::max<uint32_t>(4096u, n / 16u));
+  // hand-over to NARROW launches when the near set plus everything waiting beyond the threshold is this small
+  sv.narrow_t = sv.kn.narrow.value_or(8192u);
+  sv.hint_mask = f->last_hint_mask.load(std::memory_order_relaxed);
+  if (sv.kn.hint) sv.hint_mask = *sv.kn.hint ? ~0ull : 0ull;  // experiments: all / no launches gated
+  mv.dbg = nullptr;
+  if (sv.kn.mbox_trace) {
+    sv.mb_dbg = DBuf<unsigned long long>(*ctx->pool, (size_t)MB_DBG_SWEEPS * nb * 16);
+    HIP_CHECK(hipMemsetAsync(sv.mb_dbg.p, 0, (size_t)MB_DBG_SWEEPS * nb * 16 * 8, ctx->stream));
+    mv.dbg = sv.mb_dbg.p;
+  }
+}
+
+// The resident launch of a mailbox solve that holds the lease and the buffers for one (`want_res`): ResView, its staging
+// depth and its schedule.  Every block needs a CU of its own for the whole launch (1024 threads x 128 registers and ~150 KB
+// of LDS fill one), so the grid must fit the device: lease_resident saw to that.
+void bind_resident(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
+  const uint32_t n = f->n_states, nb = sv.plan->nb;
+  sv.resident = false;
+  sv.rv = ResView{};
+  sv.res_dyn = 0;
+  // (plan_mailbox checked resident_staging already; what is left here is WFST_SSSP_STG, which may set fewer than the 4 slots a
+  // resident launch needs — the tests' way into the one-launch-per-level path of 4096-state blocks)
+  uint32_t stg = want_res && !sv.force_big ? resident_staging(*sv.plan) : 0u;
+  if (sv.kn.stg) stg = std::min<uint32_t>(stg, *sv.kn.stg);
+  if (stg < 4) {
+    if (sv.log == 13) throw Error("shortest_path: internal error (the 8192-state plan without a resident launch)");
+    sv.rs_msgs.reset();
+    sv.rs_abort.reset();
+    sv.lease.release();
+    return;
+  }
+  sv.resident = true;
+  sv.res_kernel = sv.log == 13 ? sssp_mbox_resident_kernel<13> : sssp_mbox_resident_kernel<12>;
+  MboxView& mv = sv.mv;
+  mv.stg = stg;
+  {
+    // states per lane group in the widest round: 4, unless such a round (4 x 16 x (64 / lps) states) would send more than
+    // ~0.8 of the staging slots' worth to an average destination — what overflows leaves as 8-byte stores of its own
+    // (2M states, 8192-state blocks, 21 slots: 454 us with 4, 432 with 2)
+    const uint32_t lps = sv.plan->lps, g = 16u * (64u / lps);
+    const double per_dest = 4.0 * g * ((double)f->n_arcs / (double)n) / (double)nb;
+    const uint32_t umax = sv.kn.umax ? (uint32_t)*sv.kn.umax : per_dest <= 0.8 * mv.stg ? 4u : 2u;
+    sv.res_lps_umax = lps | (umax << 8);
+  }
+  sv.mb_dyn = (size_t)nb * mv.stg * sizeof(uint2) + 3u * (size_t)nb * sizeof(uint32_t);
+  sv.res_dyn = res_lds_bytes(sv.log, nb, mv.stg);
+  ResView& rv = sv.rv;
+  rv.msgs[0] = sv.rs_msgs.p;
+  rv.msgs[1] = sv.rs_msgs.p + sv.plan->res_units;
+  rv.roffh = sv.plan->roffh.p;
+  rv.roffh_t = sv.plan->roffh_t.p;
+  rv.abort = sv.rs_abort.p;
+  rv.bytes = (uint32_t)(sv.plan->res_units * sizeof(uint2));
+  rv.tlim_ticks = 2000000u;  // 20 ms of wall_clock64
+  if (sv.kn.res_tlim_us) rv.tlim_ticks = (uint32_t)std::min<long long>(4000000000ll, *sv.kn.res_tlim_us * 100ll);
+  sv.res_max_levels = sv.kn.res_levels.value_or(RS_LEVEL_CAP);
+  rv.trace = nullptr;
+  if (sv.kn.res_trace) {
+    sv.rs_trace = DBuf<unsigned long long>(*ctx->pool, (size_t)RS_TRACE_LEVELS * nb * 4);
+    HIP_CHECK(hipMemsetAsync(sv.rs_trace.p, 0, (size_t)RS_TRACE_LEVELS * nb * 4 * 8, ctx->stream));
+    rv.trace = sv.rs_trace.p;
+  }
+  // a resident level costs ~7 us when thin (a launch per level: ~10): the band's tail is cut a little later and the
+  // hand-over to the NARROW launch comes a little earlier (measured on C3: 298.8 -> 289.5 us per solve)
+  if (!sv.kn.near_low) sv.near_low = std::min<uint32_t>(65536u, std::max<uint32_t>(4096u, n / 32u));
+  // (what the NARROW launch can hold is ~48 - 96 entries per workgroup: handing it more per workgroup than that sends the
+  // search back and forth between the modes — 150 k states, 37 blocks, threshold 16 384: 7.6 launches and 0.55 ms per
+  // query from random sources; with 64 per block 3 launches and 0.40 ms: tools/varied_sources.py)
+  if (!sv.kn.narrow) sv.narrow_t = std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, nb * (sv.log == 13 ? 128u : 64u)));
+  static OncePerDevice lds_once;
+  raise_dynamic_lds(lds_once, ctx->device, (int)RES_LDS_BYTES,
+                    {(const void*)sssp_mbox_resident_kernel<12>, (const void*)sssp_mbox_resident_kernel<13>});
+}
+
+// Binned levels (sssp_binned.h): the dense levels of the solve as owner-computes passes, chosen per level on the device.
+// Parity-green and measured (profiles/r05*): NOT faster than the atomic sweeps on MI355X at any size tried (5M states:
+// 2.9 vs 2.4 ms; a binned level costs ~50 us + 25 ps per arc against 14.5 ps per arc + 78 ps per atomic), so it is an
+// option, not the default.  WFST_SSSP_BINNED=1: on wherever the message format allows.
+void bind_binned(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
+  const uint32_t n = f->n_states;
+  sv.binned = false;
+  sv.bplan.reset();
+  if (!(bin_eligible(f) && sv.delta < INF && sv.kn.binned >= 1 && ctx->n_cus > 0)) return;
+  const uint32_t logd = n <= (BN_MAXBINS << 13) && !sv.kn.bin_log14 ? 13u : 14u;
+  try {  // (a slot per arc and the region tables come from the pool: on a tight pool the atomic sweeps run every level)
+    sv.bplan = bin_plan(ctx, f, logd);
+    const BinPlan& bp = *sv.bplan;
+    if (bp.slots == 0 || bp.slots >= 0xFFFF0000ull) throw Error("binned levels: region table out of range");
+    sv.bn_msgs = DBuf<uint2>(*ctx->pool, (size_t)bp.slots);
+    sv.bn_cnt = DBuf<uint32_t>(*ctx->pool, (size_t)bp.nbin * bp.G);
+    HIP_CHECK(hipMemsetAsync(sv.bn_cnt.p, 0, (size_t)bp.nbin * bp.G * sizeof(uint32_t), ctx->stream));
+    BinView& bv = sv.bv;
+    bv.roff = bp.roff.p;
+    bv.roff_t = bp.roff_t.p;
+    bv.msgs = sv.bn_msgs.p;
+    bv.cnt = sv.bn_cnt.p;
+    bv.nbin = bp.nbin;
+    bv.G = bp.G;
+    bv.sg = bp.sg;
+    bv.hop_cap = 1u << (32u - logd);
+    if (sv.kn.bin_hopcap) bv.hop_cap = std::max<uint32_t>(1u, std::min<uint32_t>(bv.hop_cap, *sv.kn.bin_hopcap));
+    sv.bn_dyn_expand = bin_expand_lds(bp.nbin);
+    sv.bn_dyn_apply = bin_apply_lds(logd);
+    sv.bin_expand_kernel = logd == 14 ? sssp_bin_expand_kernel<14> : sssp_bin_expand_kernel<13>;
+    sv.bin_apply_kernel = logd == 14 ? sssp_bin_apply_kernel<14> : sssp_bin_apply_kernel<13>;
+    static OncePerDevice lds_once;
+    raise_dynamic_lds(lds_once, ctx->device, BN_LDS_MAX,
+                      {(const void*)sssp_bin_expand_kernel<13>, (const void*)sssp_bin_expand_kernel<14>,
+                       (const void*)sssp_bin_apply_kernel<13>, (const void*)sssp_bin_apply_kernel<14>});
+    // a binned level costs two launches and the keys of every bin that receives anything (12 B per state when all do):
+    // it pays from a frontier of ~1/64 of the states (measured, profiles/r05*: the atomic sweep relaxes ~10 G arcs/s there)
+    sv.dense_low = std::max<uint32_t>(16384u, n / 64u);
+    if (sv.kn.dense_low) sv.dense_low = (uint32_t)std::min<long long>(0xFFFFFFFEll, *sv.kn.dense_low);
+    sv.binned = true;
+  } catch (const Error&) {
+    (void)hipGetLastError();  // (a refused allocation must not surface at the next launch check)
+    sv.bplan.reset();
+    sv.bn_msgs.reset();
+    sv.bn_cnt.reset();
+  }
+}
+
+// relax_setup allocates and initialises the state of a solve (keys, frontier flags, control block) and fixes its schedule parameters
+void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
+  sv.kn = read_knobs();
+  const Knobs& kn = sv.kn;
+  const uint32_t n = f->n_states;
+  DevicePool& pool = *ctx->pool;
+  sv.key = DBuf<uint64_t>(pool, n);
+  sv.shadow = DBuf<uint32_t>(pool, n);
+  const size_t n_pad = ((size_t)n + 15) & ~(size_t)15;
+  sv.flags = DBuf<uint8_t>(pool, 2 * n_pad);
+  sv.improved = DBuf<uint32_t>(pool, IMP_RING);
+  sv.ctl = DBuf<Ctl>(pool, 1);
+  hipStream_t st = ctx->stream;
+  sv.fl[0] = sv.flags.p;
+  sv.fl[1] = sv.flags.p + n_pad;
+  sv.blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)ctx->n_cus * 8, (n + 255) / 256));
+  sv.delta = band_from_mean_weight(f, kn);
+  sv.near_low = kn.near_low.value_or(4096u);  // activations below which a sweep is launch-latency bound anyway
+  const float tau0_mult = kn.tau0_mult > 0.0f ? kn.tau0_mult : 1.0f;  // first band = tau0_mult x delta
   static_assert(sizeof(Ctl) % 4 == 0, "Ctl is cleared word by word");
   // mailbox sweeps where they pay: branching graphs (the near-far case) whose state ids fit the message format
   // ... and few enough blocks that the per-pair regions still hold runs of messages: measured on MI355X (fan-out 10), the
   // mailbox launches win at 1M and 2M states (0.41 vs 0.50 ms, 0.84 vs 0.89), tie at 3M and lose at 5M (3.2 vs 2.4 ms: a
   // region then receives ~3 messages per sweep, and 1221 workgroups take five turns on 256 CUs).  Beyond MB_NB_DEFAULT
   // blocks the atomic sweeps stay the default; WFST_SSSP_MAILBOX=1 still selects the mailbox kernel up to 8M states.
-  bool want_mbox = delta < INF && mbox_eligible(f) && ((n + MB_B - 1) >> MB_LOG) <= MB_NB_DEFAULT;
-  int mbox_mode = want_mbox ? 1 : 0;
-  if (const char* e = std::getenv("WFST_SSSP_MAILBOX")) mbox_mode = mbox_eligible(f) ? std::atoi(e) : 0;
-  // Resident launches (sssp_resident.h) need every block on a CU of its own for the whole launch, and only one such solve
-  // runs per device at a time: the lease is taken first, because it decides the block size — 4096 states, or 8192 for the
-  // FSTs of 1M .. 2M states that then still fit one block per CU (every launch of such a solve is a resident one).
-  bool want_res = false;
+  int mbox_mode = sv.delta < INF && mbox_eligible(f) && ((n + MB_B - 1) >> MB_LOG) <= MB_NB_DEFAULT ? 1 : 0;
+  if (kn.mailbox) mbox_mode = mbox_eligible(f) ? *kn.mailbox : 0;
   sv.log = 12;
   sv.lease.release();
-  if (mbox_mode >= 1) {
-    int want = 1;
-    if (const char* e = std::getenv("WFST_SSSP_RESIDENT")) want = std::atoi(e);
-    const bool big_env = std::getenv("WFST_SSSP_BIG") && std::atoi(std::getenv("WFST_SSSP_BIG")) != 0;
-    const uint32_t cus = (uint32_t)std::min<int>(ctx->n_cus, (int)MB_NBMAX);
-    const uint32_t nb12 = (n + 4095u) >> 12, nb13 = (uint32_t)(((uint64_t)n + 8191u) >> 13);
-    uint32_t log = 0;
-    if (nb12 <= cus) log = 12;
-    else if (nb13 <= cus && !std::getenv("WFST_SSSP_LOG12")) log = 13;
-    if (log == 12 && nb13 <= cus && std::getenv("WFST_SSSP_LOG13") && std::atoi(std::getenv("WFST_SSSP_LOG13")) != 0) log = 13;  // experiments: half the workgroups
-    // wfst_ctx_set_resident_share(ctx, 1): the resident grid may hold at most half of the compute units, so that a large batch
-    // kernel of another context runs BESIDE it (a resident workgroup needs a compute unit of its own; a grid that wants 245 of
-    // 256 waits for whatever holds more than 11 of them).  8192-state blocks where that is enough, one launch per level otherwise.
-    if (ctx->resident_share == 1u) {
-      const uint32_t half = cus / 2u;
-      if (nb12 <= half) log = 12;
-      else if (nb13 <= half && !std::getenv("WFST_SSSP_LOG12")) log = 13;
-      else log = 0;
-    }
-    if (want && log && !ctx->profiling && ctx->resident_allowed() && !big_env &&
-        sv.lease.acquire(ctx->device, ctx->resident_share == 1u ? 1 : 2)) {
-      want_res = true;
-      sv.log = log;
-    }
-  }
-  if (mbox_mode >= 1) {
-    // Two message buffers of one slot per arc, the nb^2 region tables and counts come from the pool: on a tight pool (or a
-    // dense graph) the atomic sweeps, which need none of it, run instead.  The 8192-state plan exists in the resident kernel
-    // only: when it cannot be had (the pool, a region buffer beyond the buffer-descriptor range, no room for staging), the
-    // solve is planned again with 4096-state blocks and one launch per level — never refused.
-    auto release_all = [&] {
-      want_res = false;
-      sv.rs_msgs.reset();
-      sv.rs_abort.reset();
-      sv.lease.release();
-      sv.plan.reset();
-      sv.mb_msgs.reset();
-      sv.mb_words.reset();
-      sv.mb_wl.reset();
-      sv.mbox = false;
-    };
-    auto try_plan = [&](uint32_t log, bool res) -> bool {
-      try {
-        sv.log = log;
-        sv.plan = mbox_plan(ctx, f, log);
-        const uint32_t nb = sv.plan->nb;
-        if (res) {  // what the resident launch needs beyond the plan
-          const uint64_t bytes = sv.plan->res_units * sizeof(uint2);
-          const size_t fixed = res_lds_bytes(log, nb, 0);
-          const bool fits = sv.plan->res_units != 0 && bytes < 0x7FFFFFF0ull && fixed + 8u * 4u * nb <= 160u * 1024u;
-          if (!fits) {
-            if (log == 13) throw Error("resident launch not possible");
-            res = false;
-            sv.lease.release();
-          }
-        }
-        sv.mb_msgs = DBuf<uint2>(pool, 2 * (size_t)f->n_arcs);
-        const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << log) / 32);
-        sv.mb_words = DBuf<uint32_t>(pool, 2 * w_cnt + 2 * nb + w_pend + 4 * nb);
-        sv.mb_wl = DBuf<uint4>(pool, (size_t)nb << log);
-        if (res) {
-          sv.rs_msgs = DBuf<uint2>(pool, 2 * (size_t)sv.plan->res_units);
-          sv.rs_abort = DBuf<uint32_t>(pool, 16);
-        }
-        want_res = res;
-        sv.mbox = true;
-        return true;
-      } catch (const Error&) {
-        (void)hipGetLastError();  // (a refused allocation must not surface at the next launch check)
-        release_all();
-        return false;
-      }
-    };
-    if (std::getenv("WFST_SSSP_TEST_FAIL_LOG13") && sv.log == 13) {  // tests: the 8192-state plan refused
-      release_all();
-      sv.log = 12;
-      try_plan(12, false);
-    } else if (!try_plan(sv.log, want_res) && sv.log == 13) {
-      try_plan(12, false);
-    }
-    if (!sv.mbox) sv.log = 12;
-  }
+  bool want_res = mbox_mode >= 1 && lease_resident(ctx, n, sv);
+  if (mbox_mode >= 1) want_res = plan_mailbox(ctx, f, sv, want_res);
   if (sv.mbox) {
-    // The band once more, now that the plan knows the states' CHEAPEST arcs: the rule above reads the mean weight as if the
-    // weights were uniform on [0, 2 mean) — a state's best of d arcs then costs 2 mean / (d + 1).  Where the cheapest arcs are
-    // much cheaper than that (exponential, log-normal weights: a shortest path is made of them) the band shrinks by the same
-    // ratio; where every arc costs about the same (unit weights: the search is a breadth-first one) it widens a little.
-    // 1M states, fan-out 10 (tools/weight_shapes.py): exponential 410 -> 241 us, unit weights 205 -> ~125; uniform weights
-    // (ratio 0.9 .. 1.1): untouched.
-    if (sv.delta < INF && !std::getenv("WFST_SSSP_DELTA") && sv.plan->mean_min_w > 0.0f && f->mean_weight > 0.0f) {
-      const double deg = (double)f->n_arcs / (double)n;
-      const double ratio = (double)sv.plan->mean_min_w * (deg + 1.0) / (2.0 * (double)f->mean_weight);
-      if (ratio < 0.7) delta = (float)(delta * std::max(ratio, 0.1));
-      else if (ratio > 2.0) delta = delta * 1.4f;
-      sv.delta = delta;
-    }
-    const uint32_t nb = sv.plan->nb;
-    const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << sv.log) / 32);
-    MboxView& mv = sv.mv;
-    mv.roff = sv.plan->roff.p;
-    mv.roff_t = sv.plan->roff_t.p;
-    mv.msgs[0] = sv.mb_msgs.p;
-    mv.msgs[1] = sv.mb_msgs.p + f->n_arcs;
-    uint32_t* w = sv.mb_words.p;
-    mv.cnt[0] = w;
-    mv.cnt[1] = w + w_cnt;
-    w += 2 * w_cnt;
-    mv.wrote[0] = w;
-    mv.wrote[1] = w + nb;
-    w += 2 * nb;
-    mv.pend = w;
-    w += w_pend;
-    mv.blk_pend = w;
-    mv.blk_mind = w + nb;
-    mv.blk_far = w + 2 * nb;
-    mv.wl_cnt = w + 3 * nb;
-    mv.wl = sv.mb_wl.p;
-    mv.nb = nb;
-    // staging depth: what the dynamic LDS budget leaves after the three per-destination tables
-    mv.stg = std::max<uint32_t>(1u, std::min<uint32_t>(MB_STG_MAX, (MB_DYN_BUDGET - 12u * nb) / (8u * nb)));
-    if (const char* e = std::getenv("WFST_SSSP_STG")) mv.stg = std::max<uint32_t>(1u, std::min<uint32_t>(mv.stg, (uint32_t)std::atoi(e)));
-    if (const char* e = std::getenv("WFST_SSSP_BIG")) sv.force_big = std::atoi(e) != 0;
-    sv.mb_dyn = (size_t)nb * mv.stg * sizeof(uint2) + 3u * (size_t)nb * sizeof(uint32_t);
-    static std::once_flag lds_once[64];  // (a function attribute is per device)
-    std::call_once(lds_once[(unsigned)ctx->device & 63u], [] {
-      HIP_CHECK(hipFuncSetAttribute((const void*)sssp_mbox_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MB_DYN_BUDGET));
-      HIP_CHECK(hipFuncSetAttribute((const void*)sssp_mbox_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MB_DYN_BUDGET));
-    });
-    // A mailbox sweep costs its ~10 us chain of dependent trips whatever it expands, up to ~256 states per block: the
-    // threshold moves on as soon as the near set is below 1/16 of the states (measured, tools/param_sweep.py: 4096 ->
-    // 65536 at 1M / 2M states is 0.407 -> 0.386 and 0.817 -> 0.741 ms; at 300 k states 16384 is the best)
-    if (!std::getenv("WFST_SSSP_NEAR_LOW")) sv.near_low = std::min<uint32_t>(65536u, std::max<uint32_t>(4096u, n / 16u));
-    // hand-over to NARROW launches when the near set plus everything waiting beyond the threshold is this small
-    sv.narrow_t = 8192;
-    if (const char* e = std::getenv("WFST_SSSP_NARROW")) sv.narrow_t = (uint32_t)std::atol(e);
-    sv.hint_mask = f->last_hint_mask.load(std::memory_order_relaxed);
-    if (const char* e = std::getenv("WFST_SSSP_HINT")) sv.hint_mask = std::atoi(e) ? ~0ull : 0ull;  // experiments: all / no launches gated
-    mv.dbg = nullptr;
-    if (std::getenv("WFST_SSSP_MBOX_TRACE")) {
-      sv.mb_dbg = DBuf<unsigned long long>(pool, (size_t)MB_DBG_SWEEPS * nb * 16);
-      HIP_CHECK(hipMemsetAsync(sv.mb_dbg.p, 0, (size_t)MB_DBG_SWEEPS * nb * 16 * 8, st));
-      mv.dbg = sv.mb_dbg.p;
-    }
-    // Resident launches: every block needs a CU of its own for the whole launch (1024 threads x 128 registers and ~150 KB of
-    // LDS fill one), so the grid must fit the device, and only one such solve runs per device at a time.  Not under the
-    // per-sweep profiler (it times launches), not after a launch of this context gave up waiting.
-    sv.resident = false;
-    sv.rv = ResView{};
-    sv.res_dyn = 0;
-    {
-      const uint64_t bytes = sv.plan->res_units * sizeof(uint2);
-      constexpr size_t LDS_BYTES = 160u * 1024u;
-      const size_t fixed = res_lds_bytes(sv.log, nb, 0);
-      // (deeper than the one-level kernel's slots where the LDS has room: a round of the resident kernel holds up to 4 x 16 x
-      // (64 / lps) states, 768 with 5 lanes per state)
-      const uint32_t stg_lim = std::min<uint32_t>(RS_STG_MAX, (MB_DYN_BUDGET - 12u * nb) / (8u * nb));  // (mb_dyn below: the one-level kernel's budget)
-      uint32_t stg_res = fixed + 8u * nb <= LDS_BYTES ? (uint32_t)std::min<size_t>(stg_lim, (LDS_BYTES - fixed) / (8u * nb)) : 0u;
-      if (const char* e = std::getenv("WFST_SSSP_STG")) stg_res = std::max<uint32_t>(1u, std::min<uint32_t>(stg_res, (uint32_t)std::atoi(e)));
-      if (want_res && !sv.force_big && sv.plan->res_units != 0 && bytes < 0x7FFFFFF0ull && stg_res >= 4 && sv.rs_msgs.p) {
-        sv.resident = true;
-        mv.stg = stg_res;
-        {
-          // states per lane group in the widest round: 4, unless such a round (4 x 16 x (64 / lps) states) would send more than
-          // ~0.8 of the staging slots' worth to an average destination — what overflows leaves as 8-byte stores of its own
-          // (2M states, 8192-state blocks, 21 slots: 454 us with 4, 432 with 2)
-          const uint32_t lps = sv.plan->lps, g = 16u * (64u / lps);
-          const double per_dest = 4.0 * g * ((double)f->n_arcs / (double)n) / (double)nb;
-          uint32_t umax = per_dest <= 0.8 * mv.stg ? 4u : 2u;
-          if (const char* e = std::getenv("WFST_SSSP_UMAX")) umax = std::atoi(e) >= 4 ? 4u : 2u;
-          sv.res_lps_umax = lps | (umax << 8);
-        }
-        sv.mb_dyn = (size_t)nb * mv.stg * sizeof(uint2) + 3u * (size_t)nb * sizeof(uint32_t);
-        sv.res_dyn = res_lds_bytes(sv.log, nb, mv.stg);
-      } else {
-        if (sv.log == 13) throw Error("shortest_path: internal error (the 8192-state plan without a resident launch)");
-        sv.rs_msgs.reset();
-        sv.rs_abort.reset();
-        sv.lease.release();
-      }
-      if (sv.resident) {
-        ResView& rv = sv.rv;
-        rv.msgs[0] = sv.rs_msgs.p;
-        rv.msgs[1] = sv.rs_msgs.p + sv.plan->res_units;
-        rv.roffh = sv.plan->roffh.p;
-        rv.roffh_t = sv.plan->roffh_t.p;
-        rv.abort = sv.rs_abort.p;
-        rv.bytes = (uint32_t)bytes;
-        rv.tlim_ticks = 2000000u;  // 20 ms of wall_clock64
-        if (const char* e = std::getenv("WFST_SSSP_RES_TLIM_US")) rv.tlim_ticks = (uint32_t)std::min<long long>(4000000000ll, std::atoll(e) * 100ll);
-        sv.res_max_levels = RS_LEVEL_CAP;
-        if (const char* e = std::getenv("WFST_SSSP_RES_LEVELS")) sv.res_max_levels = std::max<uint32_t>(2u, std::min<uint32_t>(RS_LEVEL_CAP, (uint32_t)std::atol(e)));
-        rv.trace = nullptr;
-        if (std::getenv("WFST_SSSP_RES_TRACE")) {
-          sv.rs_trace = DBuf<unsigned long long>(pool, (size_t)RS_TRACE_LEVELS * nb * 4);
-          HIP_CHECK(hipMemsetAsync(sv.rs_trace.p, 0, (size_t)RS_TRACE_LEVELS * nb * 4 * 8, st));
-          rv.trace = sv.rs_trace.p;
-        }
-        // a resident level costs ~7 us when thin (a launch per level: ~10): the band's tail is cut a little later and the
-        // hand-over to the NARROW launch comes a little earlier (measured on C3: 298.8 -> 289.5 us per solve)
-        if (!std::getenv("WFST_SSSP_NEAR_LOW")) sv.near_low = std::min<uint32_t>(65536u, std::max<uint32_t>(4096u, n / 32u));
-        // (what the NARROW launch can hold is ~48 - 96 entries per workgroup: handing it more per workgroup than that sends the
-        // search back and forth between the modes — 150 k states, 37 blocks, threshold 16 384: 7.6 launches and 0.55 ms per
-        // query from random sources; with 64 per block 3 launches and 0.40 ms: tools/varied_sources.py)
-        if (!std::getenv("WFST_SSSP_NARROW")) sv.narrow_t = std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, nb * (sv.log == 13 ? 128u : 64u)));
-        static std::once_flag res_once[64];
-        std::call_once(res_once[(unsigned)ctx->device & 63u], [] {
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_mbox_resident_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_mbox_resident_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-        });
-      }
-    }
-    if (sv.log == 13)
-      sssp_mbox_setup_kernel<13><<<sv.blocks, 256, 0, st>>>(sv.key.p, mv, sv.improved.p, sv.ctl.p, f->dev.offsets, n, (uint32_t)f->start,
-                                                            delta * (tau0_mult > 0.0f ? tau0_mult : 1.0f), sv.narrow_t, sv.rv.msgs[0],
-                                                            sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
-    else
-      sssp_mbox_setup_kernel<12><<<sv.blocks, 256, 0, st>>>(sv.key.p, mv, sv.improved.p, sv.ctl.p, f->dev.offsets, n, (uint32_t)f->start,
-                                                            delta * (tau0_mult > 0.0f ? tau0_mult : 1.0f), sv.narrow_t, sv.rv.msgs[0],
-                                                            sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
+    sv.delta = band_from_cheapest_arcs(f, *sv.plan, sv.delta, kn);
+    bind_mailbox(ctx, f, sv);
+    bind_resident(ctx, f, sv, want_res);
+    const auto setup_kernel = sv.log == 13 ? sssp_mbox_setup_kernel<13> : sssp_mbox_setup_kernel<12>;
+    setup_kernel<<<sv.blocks, 256, 0, st>>>(sv.key.p, sv.mv, sv.improved.p, sv.ctl.p, f->dev.offsets, n, (uint32_t)f->start,
+                                            sv.delta * tau0_mult, sv.narrow_t, sv.rv.msgs[0], sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
   } else {
-    // Binned levels (sssp_binned.h): the dense levels of the solve as owner-computes passes, chosen per level on the device.
-    // Parity-green and measured (profiles/r05*): NOT faster than the atomic sweeps on MI355X at any size tried (5M states:
-    // 2.9 vs 2.4 ms; a binned level costs ~50 us + 25 ps per arc against 14.5 ps per arc + 78 ps per atomic), so it is an
-    // option, not the default.  WFST_SSSP_BINNED=1: on wherever the message format allows.
-    sv.binned = false;
-    sv.bplan.reset();
-    int bin_mode = 0;
-    if (const char* e = std::getenv("WFST_SSSP_BINNED")) bin_mode = bin_eligible(f) && delta < INF ? std::atoi(e) : 0;
-    if (bin_mode >= 1 && !(ctx->n_cus > 0)) bin_mode = 0;
-    if (bin_mode >= 1) {
-      uint32_t logd = n <= (BN_MAXBINS << 13) ? 13u : 14u;
-      if (const char* e = std::getenv("WFST_SSSP_BIN_LOG")) logd = std::atoi(e) == 14 ? 14u : logd;
-      try {  // (a slot per arc and the region tables come from the pool: on a tight pool the atomic sweeps run every level)
-        sv.bplan = bin_plan(ctx, f, logd);
-        const BinPlan& bp = *sv.bplan;
-        if (bp.slots == 0 || bp.slots >= 0xFFFF0000ull) throw Error("binned levels: region table out of range");
-        sv.bn_msgs = DBuf<uint2>(pool, (size_t)bp.slots);
-        sv.bn_cnt = DBuf<uint32_t>(pool, (size_t)bp.nbin * bp.G);
-        HIP_CHECK(hipMemsetAsync(sv.bn_cnt.p, 0, (size_t)bp.nbin * bp.G * sizeof(uint32_t), st));
-        BinView& bv = sv.bv;
-        bv.roff = bp.roff.p;
-        bv.roff_t = bp.roff_t.p;
-        bv.msgs = sv.bn_msgs.p;
-        bv.cnt = sv.bn_cnt.p;
-        bv.nbin = bp.nbin;
-        bv.G = bp.G;
-        bv.sg = bp.sg;
-        bv.hop_cap = 1u << (32u - logd);
-        if (const char* e = std::getenv("WFST_SSSP_BIN_HOPCAP")) bv.hop_cap = std::max<uint32_t>(1u, std::min<uint32_t>(bv.hop_cap, (uint32_t)std::atol(e)));
-        sv.bn_dyn_expand = bin_expand_lds(bp.nbin);
-        sv.bn_dyn_apply = bin_apply_lds(logd);
-        static std::once_flag bn_once[64];  // (a function attribute is per device)
-        std::call_once(bn_once[(unsigned)ctx->device & 63u], [] {
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_bin_expand_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, BN_LDS_MAX));
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_bin_expand_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, BN_LDS_MAX));
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_bin_apply_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, BN_LDS_MAX));
-          HIP_CHECK(hipFuncSetAttribute((const void*)sssp_bin_apply_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, BN_LDS_MAX));
-        });
-        // a binned level costs two launches and the keys of every bin that receives anything (12 B per state when all do):
-        // it pays from a frontier of ~1/64 of the states (measured, profiles/r05*: the atomic sweep relaxes ~10 G arcs/s there)
-        sv.dense_low = std::max<uint32_t>(16384u, n / 64u);
-        if (const char* e = std::getenv("WFST_SSSP_DENSE_LOW")) sv.dense_low = (uint32_t)std::min<long long>(0xFFFFFFFEll, std::atoll(e));
-        sv.binned = true;
-      } catch (const Error&) {
-        (void)hipGetLastError();  // (a refused allocation must not surface at the next launch check)
-        sv.binned = false;
-      }
-      if (!sv.binned) {
-        sv.bplan.reset();
-        sv.bn_msgs.reset();
-        sv.bn_cnt.reset();
-      }
-    }
+    bind_binned(ctx, f, sv);
     sssp_setup_kernel<<<sv.blocks, 256, 0, st>>>(sv.key.p, sv.shadow.p, (uint32_t*)sv.flags.p, (uint32_t)(2 * n_pad / 4),
-                                                 sv.improved.p, sv.ctl.p, n, (uint32_t)f->start,
-                                                 delta * (tau0_mult > 0.0f ? tau0_mult : 1.0f));
+                                                 sv.improved.p, sv.ctl.p, n, (uint32_t)f->start, sv.delta * tau0_mult);
   }
   HIP_CHECK(hipGetLastError());
   ctx->stats.relax_kernel = sv.mbox ? (sv.resident ? 2u : 1u) : (sv.binned ? 3u : 0u);
   sv.sweep_cap = 4ull * n + 64;
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_CAP")) sv.chase_cap = std::min<uint32_t>((uint32_t)std::atol(e), CHASE_MAX);
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_ROUNDS")) sv.chase_rounds = (uint32_t)std::atol(e);
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_LOW")) sv.chase_low = (uint32_t)std::atol(e);
+  if (kn.chase_cap) sv.chase_cap = *kn.chase_cap;
+  if (kn.chase_rounds) sv.chase_rounds = *kn.chase_rounds;
+  if (kn.chase_low) sv.chase_low = *kn.chase_low;
 }
 
 // Queues the sweeps of a solve in batches and finds the sweep that changed nothing.  start() queues the first batch and
@@ -1690,7 +1764,6 @@ struct SweepDriver {
   Solve* sv = nullptr;
   uint32_t n = 0;
   uint32_t* h_imp = nullptr;
-  bool use_graphs = false;
   uint32_t next_sweep = 0, first_count = 8, sweeps_done = 0;
   bool predicted = false;  // the first batch is expected to cover the whole solve: nothing is queued behind it
   bool extended = false;   // more than the first batch was needed
@@ -1703,7 +1776,6 @@ struct SweepDriver {
     sv = s;
     n = fst->n_states;
     h_imp = (uint32_t*)ctx->pinned_flags.get(3 * IMP_RING * sizeof(uint32_t));
-    if (const char* e = std::getenv("WFST_SSSP_GRAPH")) use_graphs = std::atoi(e) != 0;
     // A batch boundary costs ~14 us of idle GPU (profiles/r01d), so the FIRST batch of a solve is sized to what the
     // previous solve of this FST needed (+1 sweep to see the quiet one, rounded up to an even count; batch sizes stay
     // even because the flag parity of a sweep inside a batch is static).
@@ -1721,70 +1793,6 @@ struct SweepDriver {
     evs[1] = ctx->ev1;
   }
 
-  // One HIP graph = one batch (WFST_SSSP_GRAPH=1): `count` sweep kernels (static offsets from the device-side base) and the
-  // advance kernel, chained, built with explicit nodes — stream capture would make every other thread's
-  // hipStreamSynchronize fail while it is active.
-  hipGraphExec_t get_graph(int which, uint32_t count) {
-    wfst_ctx::SweepGraph& g = ctx->sweep_graph[which];
-    const uint32_t blocks = sv->blocks, near_low = sv->near_low;
-    const float delta = sv->delta;
-    const uint64_t key[8] = {(uint64_t)f->dev.offsets, (uint64_t)f->dev.wn ^ ((uint64_t)count << 56), (uint64_t)sv->key.p,
-                             (uint64_t)sv->flags.p,
-                             (uint64_t)sv->improved.p ^ ((uint64_t)sv->shadow.p << 1), (uint64_t)sv->ctl.p,
-                             ((uint64_t)n << 32) | __float_as_uint_host(delta),
-                             (uint64_t)(h_imp + which * IMP_RING) ^ ((uint64_t)near_low << 48) ^ ((uint64_t)sv->chase_cap << 40) ^
-                                 ((uint64_t)sv->chase_rounds << 20) ^ ((uint64_t)sv->chase_low << 4)};
-    if (g.exec && std::memcmp(g.key, key, sizeof(key)) == 0) return g.exec;
-    if (g.exec) HIP_CHECK(hipGraphExecDestroy(g.exec));
-    if (g.graph) HIP_CHECK(hipGraphDestroy(g.graph));
-    g.exec = nullptr;
-    g.graph = nullptr;
-    HIP_CHECK(hipGraphCreate(&g.graph, 0));
-    hipGraphNode_t prev = nullptr;
-    const uint32_t* a_offsets = f->dev.offsets;
-    const uint2* a_wn = f->dev.wn;
-    uint64_t* a_key = sv->key.p;
-    uint32_t a_n = n;
-    uint32_t* a_imp = sv->improved.p;
-    Ctl* a_ctl = sv->ctl.p;
-    float a_delta = delta;
-    uint32_t a_low = near_low;
-    uint32_t* a_shadow = sv->shadow.p;
-    uint32_t a_cap = sv->chase_cap, a_rounds = sv->chase_rounds, a_clow = sv->chase_low, a_profile = 0, a_dense = 0xFFFFFFFFu;
-    for (uint32_t j = 0; j < count; ++j) {
-      uint8_t* a_fc = sv->fl[j & 1u];
-      uint8_t* a_fn = sv->fl[(j & 1u) ^ 1u];
-      uint32_t a_off = j;
-      void* args[] = {&a_offsets, &a_wn,  &a_key,   &a_fc,  &a_fn,     &a_n,   &a_imp,    &a_ctl,
-                      &a_off,     &a_delta, &a_low, &a_shadow, &a_cap, &a_rounds, &a_clow,   &a_profile, &a_dense};
-      hipKernelNodeParams kp{};
-      kp.func = (void*)sssp_relax_kernel;
-      kp.gridDim = dim3(blocks);
-      kp.blockDim = dim3(256);
-      kp.sharedMemBytes = 0;
-      kp.kernelParams = args;
-      kp.extra = nullptr;
-      hipGraphNode_t node;
-      HIP_CHECK(hipGraphAddKernelNode(&node, g.graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp));
-      prev = node;
-    }
-    {
-      uint32_t a_count = count;
-      uint32_t* a_host = h_imp + which * IMP_RING;
-      void* args[] = {&a_ctl, &a_imp, &a_count, &a_host};
-      hipKernelNodeParams kp{};
-      kp.func = (void*)sssp_advance_kernel;
-      kp.gridDim = dim3(1);
-      kp.blockDim = dim3(64);
-      kp.kernelParams = args;
-      hipGraphNode_t node;
-      HIP_CHECK(hipGraphAddKernelNode(&node, g.graph, &prev, 1, &kp));
-    }
-    HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    std::memcpy(g.key, key, sizeof(key));
-    return g.exec;
-  }
-
   // `defer_advance`: the caller queues a kernel behind the batch that closes it (sssp_tail_kernel mirrors the flags and
   // advances the base itself) and records the event
   SweepBatch enqueue_batch(hipEvent_t ev, bool defer_advance = false) {
@@ -1793,18 +1801,15 @@ struct SweepDriver {
     SweepBatch b{next_sweep, 8u, 1};
     if (next_sweep == 0) b = SweepBatch{0u, first_count, 0};
     else if (next_sweep >= 64) b = SweepBatch{next_sweep, MAX_BATCH, 2};
-    if (use_graphs && !sv->mbox && !sv->binned) {
-      HIP_CHECK(hipGraphLaunch(get_graph(b.which, b.count), st));
-    } else {
-      // plain launches: the GPU starts on the first sweep while the host is still queueing the rest (a graph replay of
-      // N nodes only starts after ~2.7 us x N of host-side work: 89 us for the 32-sweep replay, profiles/r01g)
-      const bool time_chain = ctx->chain_timing && b.first == 0;
-      if (time_chain) HIP_CHECK(hipEventRecord(ctx->ev_chain[0], st));
-      for (uint32_t j = 0; j < b.count; ++j) launch_sweep(f, *sv, n, st, j, j, b.first + j, 0u);
-      if (time_chain) HIP_CHECK(hipEventRecord(ctx->ev_chain[1], st));
-      if (!defer_advance) sssp_advance_kernel<<<1, 64, 0, st>>>(sv->ctl.p, sv->improved.p, b.count, h_imp + b.which * IMP_RING);
-      HIP_CHECK(hipGetLastError());
-    }
+    // plain launches: the GPU starts on the first sweep while the host is still queueing the rest (the same batch as a HIP
+    // graph was measured and dropped: a replay of N nodes only starts after ~2.7 us x N of host-side work, 89 us for 32
+    // sweeps, profiles/r01g)
+    const bool time_chain = ctx->chain_timing && b.first == 0;
+    if (time_chain) HIP_CHECK(hipEventRecord(ctx->ev_chain[0], st));
+    for (uint32_t j = 0; j < b.count; ++j) launch_sweep(f, *sv, n, st, j, j, b.first + j, 0u);
+    if (time_chain) HIP_CHECK(hipEventRecord(ctx->ev_chain[1], st));
+    if (!defer_advance) sssp_advance_kernel<<<1, 64, 0, st>>>(sv->ctl.p, sv->improved.p, b.count, h_imp + b.which * IMP_RING);
+    HIP_CHECK(hipGetLastError());
     if (!defer_advance) HIP_CHECK(hipEventRecord(ev, st));
     next_sweep += b.count;
     return b;
@@ -1840,7 +1845,7 @@ struct SweepDriver {
   uint32_t done_ticket = 0;
   bool done_seen = false;  // the ticket arrived: nothing of this job is still running on the stream
   void wait_first_batch() {
-    if (done_word && !std::getenv("WFST_SSSP_EVENT_WAIT")) {
+    if (done_word && !sv->kn.event_wait) {
       const auto t0 = std::chrono::steady_clock::now();
       for (uint32_t spins = 0;; ++spins) {
         if (*done_word == done_ticket) {
@@ -1879,35 +1884,53 @@ struct SweepDriver {
   }
 };
 
-// tuning aid: the phase stamps of a mailbox solve go to the file named by WFST_SSSP_MBOX_TRACE (u64 [64][nb][16])
-void mbox_dump_trace(wfst_ctx* ctx, Solve& sv) {
-  const char* path = std::getenv("WFST_SSSP_MBOX_TRACE");
-  if (!sv.mbox || !sv.mb_dbg.p || !path) return;
-  std::vector<unsigned long long> h((size_t)MB_DBG_SWEEPS * sv.mv.nb * 16);
-  HIP_CHECK(hipMemcpyAsync(h.data(), sv.mb_dbg.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+// tuning aids: the phase stamps of a mailbox solve go to the file named by WFST_SSSP_MBOX_TRACE (u64 [64][nb][16]), the level
+// stamps of its resident launches to the one named by WFST_SSSP_RES_TRACE (u64 [64][nb][4])
+void dump_trace(wfst_ctx* ctx, const char* path, const unsigned long long* stamps, uint32_t rows, uint32_t nb, uint32_t width) {
+  if (!stamps || !path) return;
+  std::vector<unsigned long long> h((size_t)rows * nb * width);
+  HIP_CHECK(hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (FILE* fp = std::fopen(path, "wb")) {
-    const uint32_t hdr[2] = {MB_DBG_SWEEPS, sv.mv.nb};
+    const uint32_t hdr[2] = {rows, nb};
     std::fwrite(hdr, 4, 2, fp);
     std::fwrite(h.data(), 8, h.size(), fp);
     std::fclose(fp);
   }
 }
 
-// tuning aid: the level stamps of the resident launches go to the file named by WFST_SSSP_RES_TRACE (u64 [64][nb][4])
-void res_dump_trace(wfst_ctx* ctx, Solve& sv) {
-  const char* path = std::getenv("WFST_SSSP_RES_TRACE");
-  if (!sv.resident || !sv.rs_trace.p || !path) return;
-  std::vector<unsigned long long> h((size_t)RS_TRACE_LEVELS * sv.mv.nb * 4);
-  HIP_CHECK(hipMemcpyAsync(h.data(), sv.rs_trace.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (FILE* fp = std::fopen(path, "wb")) {
-    const uint32_t hdr[2] = {RS_TRACE_LEVELS, sv.mv.nb};
-    std::fwrite(hdr, 4, 2, fp);
-    std::fwrite(h.data(), 8, h.size(), fp);
-    std::fclose(fp);
-  }
+// the book-keeping of a solve that reached its fixed point after `sweeps` launches
+void record_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, uint32_t sweeps) {
+  sv.lease.release();
+  sv.sweeps = sweeps;
+  ctx->stats.sweeps = sweeps;
+  note_sweeps(f, sweeps);
+  if (sv.mbox) dump_trace(ctx, sv.kn.mbox_trace, sv.mb_dbg.p, MB_DBG_SWEEPS, sv.mv.nb, 16);
+  if (sv.resident) dump_trace(ctx, sv.kn.res_trace, sv.rs_trace.p, RS_TRACE_LEVELS, sv.mv.nb, 4);
 }
+
+// The end of a solve whose first batch `drv` has queued: the rest of the sweeps, then the book-keeping.  false = a resident
+// launch gave up waiting (its grid was not resident as a whole) and nothing of the solve stands: the caller solves again,
+// inside a ResidentHold, with one launch per level.
+bool finish_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, SweepDriver& drv) {
+  drv.finish();
+  if (drv.aborted) {
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->resident_aborted(sv.kn.res_retry_ms);
+    ctx->stats.resident_aborts += 1;
+    sv.lease.release();
+    return false;
+  }
+  if (sv.resident) ctx->resident_completed();
+  f->last_hint_mask.store(drv.hint_mask(), std::memory_order_relaxed);
+  record_solve(ctx, f, sv, drv.sweeps_done);
+  return true;
+}
+struct ResidentHold {  // the repeat of a solve whose resident launch gave up: never a resident one (wfst_ctx::resident_allowed)
+  wfst_ctx* ctx;
+  explicit ResidentHold(wfst_ctx* c) : ctx(c) { ctx->resident_hold = true; }
+  ~ResidentHold() { ctx->resident_hold = false; }
+};
 
 // Runs the relaxation to its fixed point. f must have a device copy and a start state.
 void run_relaxation(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
@@ -1935,7 +1958,7 @@ void run_relaxation(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
       if (k > sweep_cap) throw Error("shortest_path: relaxation did not converge (negative-weight cycle?)");
       sssp_nop_kernel<<<blocks, 256, 0, st>>>(fl[k & 1u], n, sv.improved.p);
       HIP_CHECK(hipEventRecord(ctx->ev0, st));
-      launch_sweep(f, sv, n, st, k, 0u, k, std::getenv("WFST_SSSP_COUNT_ATOMICS") ? 2u : 1u);  // counts the states / arcs it relaxes
+      launch_sweep(f, sv, n, st, k, 0u, k, sv.kn.count_atomics ? 2u : 1u);  // counts the states / arcs it relaxes
       HIP_CHECK(hipEventRecord(ctx->ev1, st));
       sssp_advance_kernel<<<1, 64, 0, st>>>(sv.ctl.p, sv.improved.p, 1u, nullptr);
       HIP_CHECK(hipMemcpyAsync(h_imp, sv.improved.p + (k % IMP_RING), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1954,40 +1977,16 @@ void run_relaxation(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
     }
     ctx->stats.relax_arcs += prev_arcs;
     ctx->stats.relax_states += prev_states;
+    record_solve(ctx, f, sv, sweeps_done);
   } else {
     SweepDriver drv;
     drv.init(ctx, f, &sv);
     drv.start();
-    drv.finish();
-    if (drv.aborted) {  // a resident launch gave up waiting (its grid was not resident as a whole): one launch per level
-      HIP_CHECK(hipStreamSynchronize(st));
-      ctx->resident_aborted();
-      ctx->stats.resident_aborts += 1;
-      sv.lease.release();
-      struct Hold {
-        wfst_ctx* c;
-        ~Hold() { c->resident_hold = false; }
-      } hold{ctx};
-      ctx->resident_hold = true;
+    if (!finish_solve(ctx, f, sv, drv)) {  // a resident launch gave up waiting: one launch per level
+      ResidentHold hold(ctx);
       run_relaxation(ctx, f, sv);
-      return;
     }
-    if (sv.resident) ctx->resident_completed();
-    sweeps_done = drv.sweeps_done;
-    f->last_hint_mask.store(drv.hint_mask(), std::memory_order_relaxed);
   }
-  sv.lease.release();
-  sv.sweeps = sweeps_done;
-  ctx->stats.sweeps = sweeps_done;
-  note_sweeps(f, sweeps_done);
-  mbox_dump_trace(ctx, sv);
-  res_dump_trace(ctx, sv);
-}
-
-// Builds the linear output FST exactly as single_shortest_path_backtrace does, including the property
-// word (add_state / set_final / add_tr / set_start bookkeeping, then shortest_path_properties(.., true)).
-wfst_fst* build_path_fst(wfst_ctx* ctx, bool has_path, uint32_t hops, float final_weight, const wfst_tr* path_arcs) {
-  return make_path_fst(ctx, has_path, hops, final_weight, path_arcs);
 }
 
 // The order in which the reference relaxes the states of an acyclic FST (queues/auto_queue.rs:23-99): state order when the
@@ -2075,12 +2074,34 @@ wfst_fst* shortest_path_reference_order(wfst_ctx* ctx, const wfst_fst* f, const 
   HIP_CHECK(hipStreamSynchronize(st));
   if (hc->pad & 1u) throw Error("shortest_path: hop count overflow in the mailbox sweeps (internal error)");
   if (hc->pad & 4u) throw Error("shortest_path: no admissible predecessor on the path (internal error)");
-  if (!hc->has_path) return build_path_fst(ctx, false, 0, INF, nullptr);
+  if (!hc->has_path) return make_path_fst(ctx, false, 0, INF, nullptr);
   const uint32_t len = hc->hops;
   const float final_weight = hc->final_weight;
   std::vector<wfst_tr> path(len);
   if (len) HIP_CHECK(hipMemcpy(path.data(), out.p, (size_t)len * sizeof(wfst_tr), hipMemcpyDeviceToHost));
-  return build_path_fst(ctx, true, len, final_weight, path.data());
+  return make_path_fst(ctx, true, len, final_weight, path.data());
+}
+
+// What shortest_distance and shortest_distance_device share: the solve, then the keys as plain distances — left in
+// `d_distance`, or, when that is null, copied to `h_distance` (and the hop counts to `h_hops`, unless null) — and the wait.
+void solve_distances(wfst_ctx* ctx, const wfst_fst* f, float* d_distance, float* h_distance, uint32_t* h_hops) {
+  const uint32_t n = f->n_states;
+  hipStream_t st = ctx->stream;
+  ensure_device(const_cast<wfst_fst*>(f));
+  Solve sv;
+  run_relaxation(ctx, f, sv);
+  DBuf<float> d;
+  DBuf<uint32_t> hh;
+  if (!d_distance) {  // (from the pool AFTER the solve: the solve's buffers get the blocks they had last time, api.cpp)
+    d = DBuf<float>(*ctx->pool, n);
+    hh = DBuf<uint32_t>(*ctx->pool, n);
+    d_distance = d.p;
+  }
+  sssp_export_kernel<<<(n + 255) / 256, 256, 0, st>>>(sv.key.p, d_distance, h_hops ? hh.p : nullptr, n);
+  HIP_CHECK(hipGetLastError());
+  if (h_distance) HIP_CHECK(hipMemcpyAsync(h_distance, d.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (h_hops) HIP_CHECK(hipMemcpyAsync(h_hops, hh.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace
@@ -2094,28 +2115,14 @@ void shortest_distance(wfst_ctx* ctx, const wfst_fst* f, float* distance, uint32
     }
     return;
   }
-  ensure_device(const_cast<wfst_fst*>(f));
-  Solve sv;
-  run_relaxation(ctx, f, sv);
-  DBuf<float> d(*ctx->pool, n);
-  DBuf<uint32_t> hh(*ctx->pool, n);
-  sssp_export_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(sv.key.p, d.p, hops ? hh.p : nullptr, n);
-  HIP_CHECK(hipMemcpyAsync(distance, d.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  if (hops) HIP_CHECK(hipMemcpyAsync(hops, hh.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  solve_distances(ctx, f, nullptr, distance, hops);
 }
 
 // the same distances left in HBM (d_distance[n_states], +inf = unreachable) for device consumers (push.hip); f must have a
 // start state
 void shortest_distance_device(wfst_ctx* ctx, const wfst_fst* f, float* d_distance) {
-  const uint32_t n = f->n_states;
-  if (f->start < 0 || n == 0) throw Error("shortest_distance_device: no start state");
-  ensure_device(const_cast<wfst_fst*>(f));
-  Solve sv;
-  run_relaxation(ctx, f, sv);
-  sssp_export_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(sv.key.p, d_distance, nullptr, n);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (f->start < 0 || f->n_states == 0) throw Error("shortest_distance_device: no start state");
+  solve_distances(ctx, f, d_distance, nullptr, nullptr);
 }
 
 // Transpose of f (in-arcs as {source, position}); built the SECOND time shortest_path sees the same large FST — a one-shot
@@ -2134,13 +2141,10 @@ void reverse_csr_build(wfst_ctx* ctx, const wfst_fst* f, RevCsr& r) {
   const MboxPlan* plan = f->mbox ? f->mbox.get() : f->mbox13.get();  // (cache_mu is held by the caller)
   if (plan && !(std::getenv("WFST_SSSP_TRANSPOSE_PLAN") && std::atoi(std::getenv("WFST_SSSP_TRANSPOSE_PLAN")) == 0)) {
     DBuf<uint4> rec(*ctx->pool, f->n_arcs);  // one record per arc, bucketed by destination block
-    if (plan->log == 13) {
-      rev_bucket_kernel<13><<<plan->nb, 1024, plan->nb * sizeof(uint32_t), st>>>(f->dev.offsets, f->dev.wn, n, plan->nb, plan->roff_t.p, rec.p);
-      rev_place_kernel<13><<<plan->nb, 1024, 0, st>>>(plan->roff.p, plan->nb, n, rec.p, r.off.p, r.arc.p);
-    } else {
-      rev_bucket_kernel<12><<<plan->nb, 1024, plan->nb * sizeof(uint32_t), st>>>(f->dev.offsets, f->dev.wn, n, plan->nb, plan->roff_t.p, rec.p);
-      rev_place_kernel<12><<<plan->nb, 1024, 0, st>>>(plan->roff.p, plan->nb, n, rec.p, r.off.p, r.arc.p);
-    }
+    const auto bucket_kernel = plan->log == 13 ? rev_bucket_kernel<13> : rev_bucket_kernel<12>;
+    const auto place_kernel = plan->log == 13 ? rev_place_kernel<13> : rev_place_kernel<12>;
+    bucket_kernel<<<plan->nb, 1024, plan->nb * sizeof(uint32_t), st>>>(f->dev.offsets, f->dev.wn, n, plan->nb, plan->roff_t.p, rec.p);
+    place_kernel<<<plan->nb, 1024, 0, st>>>(plan->roff.p, plan->nb, n, rec.p, r.off.p, r.arc.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st));  // rec is released here
     return;
@@ -2208,7 +2212,7 @@ void queue_tail(wfst_sp_job* j, const SweepBatch* adv = nullptr) {
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
   Solve& sv = j->sv;
-  if (j->rev && !std::getenv("WFST_SSSP_SPLIT_TAIL")) {  // one launch, header straight into pinned memory
+  if (j->rev && !sv.kn.split_tail) {  // one launch, header straight into pinned memory
     sssp_tail_kernel<<<std::min<uint32_t>(TAIL_BLOCKS, (n + 1023) / 1024), 1024, 0, st>>>(
         f->dev.finals, sv.key.p, n, sv.ctl.p, f->dev.offsets, f->dev.arcs, j->rev->off.p, j->rev->arc.p, j->h_path,
         PATH_PINNED, j->h_tail, sv.improved.p, adv ? adv->count : 0u, adv ? j->drv.host_flags(*adv) : nullptr, j->done_ticket);
@@ -2266,8 +2270,7 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   relax_setup(ctx, f, j->sv);
   ctx->stats.sweeps = 0;
   j->drv.init(ctx, f, &j->sv);
-  const bool fuse = j->drv.predicted && j->rev && !std::getenv("WFST_SSSP_SPLIT_TAIL") &&
-                    !(j->drv.use_graphs && !j->sv.mbox && !j->sv.binned);  // (a sweep graph carries its own advance node)
+  const bool fuse = j->drv.predicted && j->rev && !j->sv.kn.split_tail;
   j->drv.start(/*defer_advance=*/fuse);
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket (and the event) finish() waits for
     queue_tail(j.get(), &j->drv.cur);
@@ -2288,34 +2291,16 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   const wfst_fst* f = j->f;
   if (j->trivial) {
     ctx->stats.tied_choices = 0;
-    return build_path_fst(ctx, false, 0, INF, nullptr);
+    return make_path_fst(ctx, false, 0, INF, nullptr);
   }
   if (j->ready) return j->ready;
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
   Solve& sv = j->sv;
-  if (!ctx->profiling) {
-    j->drv.finish();
-    if (j->drv.aborted) {  // a resident launch gave up waiting: the whole query again, one launch per level
-      HIP_CHECK(hipStreamSynchronize(st));
-      ctx->resident_aborted();
-      ctx->stats.resident_aborts += 1;
-      j.reset();  // (its buffers go back to the pool, the lease with them)
-      struct Hold {
-        wfst_ctx* c;
-        ~Hold() { c->resident_hold = false; }
-      } hold{ctx};
-      ctx->resident_hold = true;
-      return shortest_path_n1_end(shortest_path_n1_begin(ctx, f));
-    }
-    if (sv.resident) ctx->resident_completed();
-    sv.lease.release();
-    sv.sweeps = j->drv.sweeps_done;
-    ctx->stats.sweeps = sv.sweeps;
-    note_sweeps(f, sv.sweeps);
-    f->last_hint_mask.store(j->drv.hint_mask(), std::memory_order_relaxed);
-    mbox_dump_trace(ctx, sv);
-    res_dump_trace(ctx, sv);
+  if (!ctx->profiling && !finish_solve(ctx, f, sv, j->drv)) {  // a resident launch gave up waiting: the whole query again
+    j.reset();  // (its buffers go back to the pool)
+    ResidentHold hold(ctx);
+    return shortest_path_n1_end(shortest_path_n1_begin(ctx, f));
   }
   if (j->tail_queued && j->drv.extended) {  // the speculative tail ran on unfinished distances: once more
     HIP_CHECK(hipMemsetAsync(&sv.ctl.p->best, 0xFF, sizeof(unsigned long long), st));
@@ -2330,7 +2315,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   if (ctx->chain_timing && !ctx->profiling) {  // the sweeps of this query as one chain (wfst_ctx_set_profiling(ctx, 2))
     ctx->stats.relax_ms = 0.0;
     ctx->stats.relax_launches = 0;
-    if (j->drv.predicted && !j->drv.extended && !(j->drv.use_graphs && !sv.mbox && !sv.binned)) {
+    if (j->drv.predicted && !j->drv.extended) {
       float ms = 0.0f;
       HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
       ctx->stats.relax_ms = ms;
@@ -2343,7 +2328,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   if (r_pad & 4u) throw Error("shortest_path: no admissible predecessor on the path (inexact weight sums with negative weights)");
   if (!r_has_path) {  // no final state is reachable: the empty FST, and nothing to choose
     ctx->stats.tied_choices = 0;
-    return build_path_fst(ctx, false, 0, INF, nullptr);
+    return make_path_fst(ctx, false, 0, INF, nullptr);
   }
   const uint32_t hops = j->fused_tail ? j->h_tail->hops : hc->hops;
   const float final_weight = j->fused_tail ? j->h_tail->final_weight : hc->final_weight;
@@ -2358,7 +2343,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
       throw Error("shortest_path: ambiguous optimum: " + std::to_string(ties) + " tied choice(s) on the optimal path of a cyclic input — the "
                   "reference's choice there depends on its relaxation order (tie order 1 returns only what is provably its result)");
   }
-  if (j->rev && !(r_pad & 8u)) return build_path_fst(ctx, true, hops, final_weight, j->h_path);
+  if (j->rev && !(r_pad & 8u)) return make_path_fst(ctx, true, hops, final_weight, j->h_path);
   // the parent pass (first query of an FST, or a path longer than the pinned buffer): a path has at most n - 1 arcs
   std::vector<wfst_tr> path;
   uint32_t len = 0;
@@ -2386,7 +2371,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
     path.resize(len);
     if (len) HIP_CHECK(hipMemcpy(path.data(), out.p, (size_t)len * sizeof(wfst_tr), hipMemcpyDeviceToHost));
   }
-  return build_path_fst(ctx, true, len, final_weight, path.data());
+  return make_path_fst(ctx, true, len, final_weight, path.data());
 }
 
 void shortest_path_n1_abandon(wfst_sp_job* job) {
