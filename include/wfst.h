@@ -318,6 +318,36 @@ wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
  *      FST.  An input that trims to nothing ends as the empty FST.  A NEW handle; fst is left as it is. ---- */
 wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
 
+/* ---- union, concat, closure: fst_union / fst_concat (rustfst-ffi/src/algorithms/{union,concat}.rs) =
+ *      rustfst::algorithms::{union::union, concat::concat, closure::closure} (union/union_static.rs:55-118,
+ *      concat/concat_static.rs:53-109, closure/closure_static.rs:25-73).  The reference changes its first operand in place;
+ *      here *out is a NEW handle equal, bit for bit (state numbering, arc order, weights, start, property word), to what the
+ *      reference leaves in that operand, and the inputs are left as they are (cached transposes, plans and words included).
+ *      Results are in general NOT label-sorted (eps arcs are appended last): tr_sort before compose.
+ *      union   compute_and_update_properties(INITIAL_ACYCLIC) on a first (a word that does not know the pair gets the four
+ *              DFS pairs replaced by the searched ones; an arc into the start from a state the start cannot reach is a cross
+ *              arc and leaves it INITIAL_ACYCLIC).  b without start state: a with that word.  Otherwise b's states follow
+ *              a's (nextstate + n_states(a)) and: a without start state -> start(b) WITHOUT the offset, as the reference
+ *              writes it, and b's word; a initial-acyclic -> 0:0/One -> start(b) + n(a) appended last to the start's row;
+ *              else one new state behind b's, with 0:0/One -> start(a), 0:0/One -> start(b) + n(a), becomes the start.  Word:
+ *              union_properties(props1, props2, false) (fst_properties/mutate_properties.rs:692-748).
+ *      concat  a without start state: a.  Otherwise b's states follow a's; every state of a with Some(final weight w) gets
+ *              0:0/w -> start(b) + n(a) appended last if b has a start state, and loses its final weight either way.  Word:
+ *              concat_properties (:186-245) if b has a start state, else what add_state / set_final / add_tr /
+ *              set_final(None) leave.
+ *      closure closure_type 0 = ClosureStar, 1 = ClosurePlus (closure/mod.rs:9-12), anything else KO.  With a start state
+ *              every final state gets 0:0/final weight -> start appended last (the weight stays).  Star: one new state, final
+ *              with One, with 0:0/One -> old start if there was one, becomes the start.  Word: closure_properties (:114-145).
+ *      union_list / concat_list: the left fold over fsts[0..n) (rustfst-python union_list / concat_list) in ONE call — the
+ *              number of kernel launches does not depend on n.  n == 0: KO "fsts must be at least of len 1"; n == 1: a copy.
+ *      KO before anything is launched: a NULL operand or list entry, an operand of another device or context, a result
+ *      that could exceed 2^31 - 2 states or 2^32 - 1 arcs (the rule: wfst_rational_check_sizes below). ---- */
+wfst_status wfst_union(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfst_fst** out);
+wfst_status wfst_concat(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfst_fst** out);
+wfst_status wfst_closure(wfst_ctx* ctx, const wfst_fst* f, uint32_t closure_type, wfst_fst** out);
+wfst_status wfst_union_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
+wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
+
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no
  *      thresholds): every epsilon:epsilon arc removed, the weighted relation kept, the result connected.  The reference
@@ -548,6 +578,11 @@ wfst_status wfst_ctx_set_tie_order(wfst_ctx* ctx, int reference_order);
 wfst_status wfst_ctx_set_resident_share(wfst_ctx* ctx, uint32_t share);
 
 /* ---- measurement hooks (bench.py / tests; not part of the reference surface) ---- */
+/* the size rule of the five rational calls, the function each of them calls first, on bare counts and without a device (op: 0
+ * union, 1 concat, 2 closure star, 3 closure plus; n operands in order).  States: the sum, + 1 for union and closure star.
+ * Arcs by their upper bound: the sum, + n for union, + the states of every operand but the last for concat, + the states
+ * (+ 1 for star) for closure.  KO "<op>: result too large: ..." beyond 2^31 - 2 states or 2^32 - 1 arcs. */
+wfst_status wfst_rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n);
 typedef struct {
   /* relaxation kernel (sssp_relax_*): launches, total device time from HIP events on ctx's stream,
    * and the algorithmic units they processed */

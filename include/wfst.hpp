@@ -22,6 +22,9 @@
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
+//   union(&mut a, &b) / concat(&mut a, &b)                       union_(a, b) / concat(a, b)                       union_static.rs:55-118, concat_static.rs:53-109
+//   closure(&mut fst, ClosureType)                               closure(fst, ClosureType)                         closure_static.rs:25-73
+//   (rustfst-python union_list / concat_list)                    union_list(fsts) / concat_list(fsts)
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -351,6 +354,49 @@ inline void optimize(VectorFst& fst) {
   check(wfst_optimize(Context::current().get(), a.h, &c.h));
   fst = detail::download(c);
 }
+
+// union (union/union_static.rs:55-118), concat (concat/concat_static.rs:53-109) and closure (closure/closure_static.rs:25-73):
+// the first operand is changed in place, like the reference (`union` is a C++ keyword, hence union_).  Results are in general
+// not label-sorted: tr_sort before compose.
+enum class ClosureType : uint32_t { ClosureStar = 0, ClosurePlus = 1 };  // closure/mod.rs:9-12
+inline void union_(VectorFst& a, const VectorFst& b) {
+  detail::DeviceFst x, y, c;
+  detail::upload(a, x);
+  detail::upload(b, y);
+  check(wfst_union(Context::current().get(), x.h, y.h, &c.h));
+  a = detail::download(c);
+}
+inline void concat(VectorFst& a, const VectorFst& b) {
+  detail::DeviceFst x, y, c;
+  detail::upload(a, x);
+  detail::upload(b, y);
+  check(wfst_concat(Context::current().get(), x.h, y.h, &c.h));
+  a = detail::download(c);
+}
+inline void closure(VectorFst& fst, ClosureType closure_type) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_closure(Context::current().get(), a.h, (uint32_t)closure_type, &c.h));
+  fst = detail::download(c);
+}
+// the left folds of rustfst-python's union_list / concat_list in one device call each (wfst_union_list, wfst_concat_list);
+// an empty list throws "fsts must be at least of len 1"
+namespace detail {
+template <class Call>
+inline VectorFst list_call(const std::vector<VectorFst>& fsts, Call call) {
+  std::vector<DeviceFst> in(fsts.size());
+  std::vector<const wfst_fst*> hs(fsts.size());
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+  }
+  DeviceFst c;
+  check(call(Context::current().get(), hs.data(), hs.size(), &c.h));
+  return download(c);
+}
+}  // namespace detail
+inline VectorFst union_list(const std::vector<VectorFst>& fsts) { return detail::list_call(fsts, wfst_union_list); }
+inline VectorFst concat_list(const std::vector<VectorFst>& fsts) { return detail::list_call(fsts, wfst_concat_list); }
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

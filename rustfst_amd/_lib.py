@@ -107,6 +107,12 @@ SYMBOLS = [
     ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_optimize", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_union", C.c_int, [_vp, _vp, _vp, _P(_vp)]),
+    ("wfst_concat", C.c_int, [_vp, _vp, _vp, _P(_vp)]),
+    ("wfst_closure", C.c_int, [_vp, _vp, _u32, _P(_vp)]),
+    ("wfst_union_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
+    ("wfst_concat_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
+    ("wfst_rational_check_sizes", C.c_int, [_u32, _vp, _vp, _sz]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

@@ -606,6 +606,58 @@ wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   });
 }
 
+// union / concat / closure (union_static.rs:55-118, concat_static.rs:53-109, closure_static.rs:25-73) and the list forms
+// (rustfst-python union_list / concat_list): every argument is checked before anything is launched
+wfst_status wfst_union(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !a || !b || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = union_fst(ctx, a, b);
+  });
+}
+wfst_status wfst_concat(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !a || !b || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = concat_fst(ctx, a, b);
+  });
+}
+wfst_status wfst_closure(wfst_ctx* ctx, const wfst_fst* f, uint32_t closure_type, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (closure_type > 1) throw Error("closure: unknown closure_type " + std::to_string(closure_type));  // closure/mod.rs:9-12
+    if (!ctx || !f || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = closure_fst(ctx, f, closure_type == 0);
+  });
+}
+static void check_list_args(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out) {
+  if (out) *out = nullptr;
+  if (n == 0) throw Error("fsts must be at least of len 1");  // rustfst-python/rustfst/algorithms/union.py, concat.py
+  if (!ctx || !fsts || !out) throw Error("null pointer");
+  for (size_t i = 0; i < n; ++i)
+    if (!fsts[i]) throw Error("item " + std::to_string(i) + ": null FST in list");
+}
+wfst_status wfst_union_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out) {
+  return wrap([&] {
+    check_list_args(ctx, fsts, n, out);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = union_list_fst(ctx, fsts, n);
+  });
+}
+wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out) {
+  return wrap([&] {
+    check_list_args(ctx, fsts, n, out);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = concat_list_fst(ctx, fsts, n);
+  });
+}
+wfst_status wfst_rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n) {
+  return wrap([&] { rational_check_sizes(op, n_states, n_arcs, n); });
+}
+
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

@@ -421,6 +421,8 @@ wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f);
 void shortest_distance_ex(wfst_ctx* ctx, const wfst_fst* f, bool reverse, float* distance, uint32_t* len);
 wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials, uint64_t n_potentials, uint32_t reweight_type);
 wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_type, bool remove_total_weight);
+// push.hip: the four DFS pairs compute_and_update_properties(INITIAL_ACYCLIC) fills in (props::merge_dfs), searched on the device
+uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f);
 // determinize.hip: determinize_with_config of an acceptor (a NEW handle); det_type in the ffi numbering
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
 // ... of a label-encoded machine (optimize.hip): no "the word must say ACCEPTOR" check, the gallic call's word
@@ -434,6 +436,15 @@ wfst_fst* determinize_with_distance_fst(wfst_ctx* ctx, const wfst_fst* f, const 
                                         std::vector<float>& out_dist);
 // tr_sum.hip: tr_sum / tr_unique (a NEW handle)
 wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique);
+// rational.hip: union / concat / closure and the list forms (NEW handles; the operands are left as they are)
+wfst_fst* union_fst(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b);
+wfst_fst* concat_fst(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b);
+wfst_fst* closure_fst(wfst_ctx* ctx, const wfst_fst* f, bool star);
+wfst_fst* union_list_fst(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n);
+wfst_fst* concat_list_fst(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n);
+// the size rule of the five calls above, which each of them calls first, on bare counts (op: 0 union, 1 concat, 2 closure
+// star, 3 closure plus): throws "<op>: result too large: ..."
+void rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n);
 // optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)
 wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
 // minimize.hip: minimize_with_config of a deterministic acyclic acceptor (a NEW handle)

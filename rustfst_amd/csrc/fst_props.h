@@ -314,6 +314,47 @@ constexpr uint64_t DELETE_ARCS_MASK = ACCEPTOR | I_DETERMINISTIC | O_DETERMINIST
                                       NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | UNWEIGHTED | ACYCLIC |
                                       INITIAL_ACYCLIC | TOP_SORTED | NOT_ACCESSIBLE | NOT_COACCESSIBLE | UNWEIGHTED_CYCLES;
 
+// ---- the rational operations (algorithms/{union,concat,closure}), all with delayed = false
+// closure_properties (mutate_properties.rs:114-145)
+inline uint64_t closure(uint64_t in) {
+  uint64_t out = (ACCEPTOR | UNWEIGHTED | ACCESSIBLE) & in;
+  if (in & UNWEIGHTED) out |= UNWEIGHTED_CYCLES;
+  out |= (COACCESSIBLE | NOT_TOP_SORTED | NOT_STRING) & in;
+  out |= (NOT_ACCEPTOR | NOT_I_DETERMINISTIC | NOT_O_DETERMINISTIC | NOT_I_LABEL_SORTED | NOT_O_LABEL_SORTED | WEIGHTED |
+          WEIGHTED_CYCLES | NOT_ACCESSIBLE | NOT_COACCESSIBLE) & in;
+  if ((in & WEIGHTED) && (in & ACCESSIBLE) && (in & COACCESSIBLE)) out |= WEIGHTED_CYCLES;
+  return out;
+}
+// what both operands hand on unless a condition below says otherwise (mutate_properties.rs:207-220, 717-729)
+constexpr uint64_t RATIONAL_NEGATIVE = NOT_ACCEPTOR | NOT_I_DETERMINISTIC | NOT_O_DETERMINISTIC | EPSILONS | I_EPSILONS |
+                                       O_EPSILONS | NOT_I_LABEL_SORTED | NOT_O_LABEL_SORTED | WEIGHTED | WEIGHTED_CYCLES |
+                                       CYCLIC | NOT_ACCESSIBLE;
+// concat_properties (mutate_properties.rs:186-245)
+inline uint64_t concat(uint64_t p1, uint64_t p2) {
+  uint64_t out = (ACCEPTOR | UNWEIGHTED | UNWEIGHTED_CYCLES | ACYCLIC) & p1 & p2;
+  out |= (NOT_TOP_SORTED | NOT_STRING) & p1;
+  out |= (NOT_TOP_SORTED | NOT_STRING) & p2;
+  out |= (INITIAL_ACYCLIC | INITIAL_CYCLIC) & p1;
+  out |= (RATIONAL_NEGATIVE | NOT_COACCESSIBLE) & p1;
+  if ((p1 & ACCESSIBLE) && (p1 & COACCESSIBLE)) {
+    out |= (ACCESSIBLE | COACCESSIBLE) & p2;
+    out |= (RATIONAL_NEGATIVE | NOT_COACCESSIBLE) & p2;
+  }
+  return out;
+}
+// union_properties (mutate_properties.rs:692-748)
+inline uint64_t union_(uint64_t p1, uint64_t p2) {
+  uint64_t out = (ACCEPTOR | UNWEIGHTED | UNWEIGHTED_CYCLES | ACYCLIC | ACCESSIBLE) & p1 & p2;
+  out |= INITIAL_ACYCLIC;
+  out |= NOT_TOP_SORTED & p1;
+  out |= NOT_TOP_SORTED & p2;
+  out |= EPSILONS | I_EPSILONS | O_EPSILONS;
+  out |= COACCESSIBLE & p1 & p2;
+  out |= RATIONAL_NEGATIVE & p1;  // (NOT_COACCESSIBLE of the first operand does not hold: the INITIAL_ACYCLIC branch, :715)
+  out |= (RATIONAL_NEGATIVE | NOT_COACCESSIBLE) & p2;
+  return out;
+}
+
 inline uint64_t compose_result(uint64_t p1, uint64_t p2, bool connected, bool has_start) {
   // start None: LazyFst::compute returns F2::new() untouched (lazy_fst.rs:229-232)
   uint64_t p = has_start ? compose(p1, p2) : NULL_PROPS;

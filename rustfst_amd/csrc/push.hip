@@ -144,9 +144,13 @@ const wfst_fst* reversed_handle(wfst_ctx* ctx, const wfst_fst* f) {
   return f->rev_fst.get();
 }
 
+}  // namespace
+
 // The SccVisitor's four facts (visitors/scc_visitors.rs) on f's graph, with f's final states (reweight never changes which
-// states have Some(final weight): set_final is only called on those)
+// states have Some(final weight): set_final is only called on those).  Without a start state dfs_visit returns before it
+// visits anything (dfs_visit.rs:104-110), so the visitor's word is the one it was constructed with: all four positive bits.
 uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f) {
+  if (f->start < 0) return props::dfs_bits(true, true, false, false);
   const uint32_t n = f->n_states;
   const uint32_t s0 = (uint32_t)f->start;
   ensure_device(const_cast<wfst_fst*>(f));
@@ -174,6 +178,8 @@ uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f) {
   }
   return props::dfs_bits(accessible, coaccessible, cyclic, initial_cyclic);
 }
+
+namespace {
 
 // ---------------------------------------------------------------- reweight (reweight.rs:48-103)
 // potentials pot[0..len); a state >= len has potential zero.  16 lanes per state: read the arc and the two potentials,

@@ -400,6 +400,26 @@ class DeviceFst:
         check(_lib.lib().wfst_optimize(self.ctx._h, self._h, C.byref(out)), "Error during optimize")
         return DeviceFst(out, self.ctx)
 
+    def union(self, other: "DeviceFst") -> "DeviceFst":
+        """algorithms::union (union/union_static.rs:55-118, wfst_union): a NEW FST equal to what the reference leaves in
+        its first operand; this FST and `other` are left as they are.  The result is in general not label-sorted."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_union(self.ctx._h, self._h, other._h, C.byref(out)), "Error during union")
+        return DeviceFst(out, self.ctx)
+
+    def concat(self, other: "DeviceFst") -> "DeviceFst":
+        """algorithms::concat (concat/concat_static.rs:53-109, wfst_concat): a NEW FST, the operands are left as they are."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_concat(self.ctx._h, self._h, other._h, C.byref(out)), "Error during concat")
+        return DeviceFst(out, self.ctx)
+
+    def closure(self, closure_type: "ClosureType") -> "DeviceFst":
+        """algorithms::closure (closure/closure_static.rs:25-73, wfst_closure): a NEW FST, this one is left as it is."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_closure(self.ctx._h, self._h, ClosureType(closure_type).value, C.byref(out)),
+              "Error during closure")
+        return DeviceFst(out, self.ctx)
+
 
 class HandleArray:
     """A batch of DeviceFst handles marshalled once for the C-ABI (`const wfst_fst* const*`): callers that submit the
@@ -665,6 +685,24 @@ def determinize_batch(fsts: Sequence[DeviceFst], config: Optional["DeterminizeCo
     return (res, flags) if want_flags else res
 
 
+def _list_call(fn_name, fsts, ctx, what):
+    n = len(fsts)
+    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
+    out = C.c_void_p()
+    check(getattr(_lib.lib(), fn_name)(ctx._h, _handles(fsts), n, C.byref(out)), what)
+    return DeviceFst(out, ctx)
+
+
+def _device_union_list(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None) -> DeviceFst:
+    """the left fold of union over device FSTs as ONE call (wfst_union_list): a NEW FST"""
+    return _list_call("wfst_union_list", fsts, ctx, "Error during union")
+
+
+def _device_concat_list(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None) -> DeviceFst:
+    """the left fold of concat over device FSTs as ONE call (wfst_concat_list): a NEW FST"""
+    return _list_call("wfst_concat_list", fsts, ctx, "Error during concat")
+
+
 def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last determinize_batch / determinize_with_distance_batch call of ctx (wfst_ctx_get_determinize_batch_stats)."""
     ctx = ctx or default_context()
@@ -762,6 +800,11 @@ class ShortestPathConfig:
 
     def _c(self):
         return C.pointer(_lib.ShortestPathConfig(self.delta, self.nshortest, 1 if self.unique else 0))
+
+
+class ClosureType(Enum):  # rustfst/src/algorithms/closure/mod.rs:9-12 (enum order = the C-ABI's closure_type)
+    CLOSURE_STAR = 0
+    CLOSURE_PLUS = 1
 
 
 class ReweightType(Enum):  # rustfst/src/algorithms/reweight.rs:11-17 (enum order = the C-ABI's reweight_type)
@@ -1020,6 +1063,32 @@ class VectorFst:
         self._dev = None
         return self
 
+    def union(self, other_fst: "VectorFst") -> "VectorFst":
+        """rustfst-python vector_fst.py:640 `union` (algorithms/union.py:13-44): THIS FST becomes the union, in place on the
+        device copies; returns this FST.  `other_fst` is left as it is."""
+        ctx = self.to_device().ctx
+        res = self.to_device().union(other_fst.to_device(ctx)).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def concat(self, other: "VectorFst") -> "VectorFst":
+        """rustfst-python vector_fst.py:438 `concat` (algorithms/concat.py): THIS FST becomes the concatenation, in place on
+        the device copies; returns this FST."""
+        ctx = self.to_device().ctx
+        res = self.to_device().concat(other.to_device(ctx)).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def closure(self, closure_type: "ClosureType") -> "VectorFst":
+        """algorithms::closure (closure/closure_static.rs:25-73; not in rustfst-python): in place on the device copy;
+        returns this FST."""
+        res = self.to_device().closure(closure_type).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
     def project(self, proj_type: Union["ProjectType", None] = None) -> "VectorFst":
         """rustfst-python vector_fst.py:525-538 `project` (algorithms/project.py:27-50): projects THIS FST in place and
         returns it (the reference returns self).  The device copy is projected and becomes this object's host data; the
@@ -1125,3 +1194,40 @@ def optimize(fst: VectorFst) -> VectorFst:
 def minimize_with_config(fst: VectorFst, config: MinimizeConfig) -> VectorFst:
     """algorithms::minimize_with_config (minimize.rs:92-176): in place, returns fst."""
     return fst.minimize(config)
+
+
+def union(fst: Union[VectorFst, DeviceFst], other_fst: Union[VectorFst, DeviceFst]) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/union.py `union`: a VectorFst is changed in place and returned; DeviceFsts give a
+    NEW DeviceFst."""
+    return fst.union(other_fst)
+
+
+def concat(fst: Union[VectorFst, DeviceFst], other_fst: Union[VectorFst, DeviceFst]) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/concat.py `concat`."""
+    return fst.concat(other_fst)
+
+
+def closure(fst: Union[VectorFst, DeviceFst], closure_type: ClosureType) -> Union[VectorFst, DeviceFst]:
+    """rustfst::algorithms::closure::closure (closure/closure_static.rs:25-73)."""
+    return fst.closure(closure_type)
+
+
+def _list_form(fsts, device_call):
+    if len(fsts) == 0:
+        raise ValueError("fsts must be at least of len 1")  # rustfst-python/rustfst/algorithms/union.py:58-59
+    if isinstance(fsts, HandleArray) or isinstance(fsts[0], DeviceFst):
+        return device_call(fsts)
+    ctx = fsts[0].to_device().ctx
+    return device_call([f.to_device(ctx) for f in fsts]).to_vector_fst()
+
+
+def union_list(fsts: Sequence[Union[VectorFst, DeviceFst]]) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/union.py:47-64 `union_list`: the left fold of union over copies of `fsts`, as ONE
+    device call (wfst_union_list).  A NEW FST of the items' kind; the items are left as they are."""
+    return _list_form(fsts, _device_union_list)
+
+
+def concat_list(fsts: Sequence[Union[VectorFst, DeviceFst]]) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/concat.py `concat_list`: the left fold of concat, as ONE device call
+    (wfst_concat_list).  A NEW FST of the items' kind."""
+    return _list_form(fsts, _device_concat_list)
