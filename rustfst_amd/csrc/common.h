@@ -16,6 +16,8 @@
 #include "../../include/wfst.h"
 #include "tropical.h"
 
+extern "C" char** environ;
+
 namespace wfst {
 
 // one turn of a host spin loop on a word in pinned memory (the completion tickets)
@@ -27,6 +29,34 @@ inline void cpu_relax() {
 #else
   asm volatile("" ::: "memory");
 #endif
+}
+
+// The WFST_* variables of the process as they stand now: ONE pass over `environ` instead of one getenv (each a walk over
+// the whole environment of a Python / torch process) per variable.  Taken at the start of a solve or a batch call and
+// asked from then on; get() is getenv() for names that begin with "WFST_" — null when the variable is not set.
+// The values point into the environment, like getenv's: valid until somebody changes the variable.
+class EnvSnap {
+ public:
+  EnvSnap() = default;
+  static EnvSnap take();
+  const char* get(const char* name) const {
+    if (vars_.empty()) return nullptr;
+    const size_t len = std::strlen(name);
+    for (const char* e : vars_)
+      if (std::strncmp(e, name, len) == 0 && e[len] == '=') return e + len + 1;
+    return nullptr;
+  }
+  bool has(const char* name) const { return get(name) != nullptr; }
+
+ private:
+  std::vector<const char*> vars_;  // "WFST_NAME=value" entries
+};
+inline EnvSnap EnvSnap::take() {
+  EnvSnap s;
+  if (environ)
+    for (char** e = environ; *e; ++e)
+      if ((*e)[0] == 'W' && std::strncmp(*e, "WFST_", 5) == 0) s.vars_.push_back(*e);
+  return s;
 }
 
 // ---------------------------------------------------------------- errors
@@ -209,6 +239,12 @@ struct RevFst {
 struct RevCsr {
   DBuf<uint32_t> off;  // [n+1]
   DBuf<uint4> arc;     // [E] {source state, position of the arc in the source's arc list, weight bits, 0}
+  // The final states as {state, final weight bits}, in state order: what the tail of a query reads instead of all of
+  // `finals`.  Only for a small, sparse final set (sssp.hip final_list_build); has_fin false = none, the tail scans.
+  // Independent of the start state, like the transpose: wfst_fst_set_start keeps both.
+  DBuf<uint2> fin;
+  uint32_t n_fin = 0;
+  bool has_fin = false;
 };
 // Message-region plan of the mailbox relaxation sweeps (sssp_mailbox.h): offsets of the region reserved for every
 // (source block, destination block) pair, sized by the number of arcs between the two blocks.

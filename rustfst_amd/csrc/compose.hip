@@ -74,6 +74,9 @@ struct ProblemDesc {
   FstView f1;
   uint32_t mode;
   uint32_t filter;  // ComposeFilterEnum value (compose_static.rs:19-33); 0 (Auto) == 3 (Sequence)
+  // string_compose_sp_kernel: where this problem's path arcs go in the packed path buffer.  Handed out by the host
+  // (launch_begin: a path has n_states - 1 arcs at most, known before the launch); compose_wave_kernel draws from a cursor.
+  uint32_t path_off;
 };
 
 struct Caps {
@@ -1022,8 +1025,7 @@ constexpr uint32_t STR_NONE = 0xFFFFFFFFu;
 // 8 workgroups of 8 waves land on one CU per XCD and leave 31 CUs per XCD to the sweeps' 30-31 workgroups per XCD.
 __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDesc* __restrict__ descs, FstView f2,
                                                                 Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
-                                                                uint32_t path_cap, uint32_t* __restrict__ path_cursor,
-                                                                uint32_t n_problems, uint32_t maxs, uint64_t f2_n_arcs,
+                                                                uint32_t path_cap, uint32_t n_problems, uint32_t maxs, uint64_t f2_n_arcs,
                                                                 uint32_t scalar_rows, uint32_t done_ticket) {
   extern __shared__ uint32_t s_dyn[];
   const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -1043,6 +1045,8 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
     }                                                                                                      \
   } while (0)
   const FstView f1 = descs[p].f1;
+  const uint32_t poff = descs[p].path_off;  // this problem's slice of the path buffer (launch_begin); read with the descriptor:
+                                            // it may live in host memory
   Result res;
   res.status = ST_OK;
   res.n_states = res.n_arcs = res.t_states = res.t_arcs = 0;
@@ -1076,7 +1080,18 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   if (lane < L) ch_cur = ld_global16(f1.arcs + lane);
   if (64u + lane < L) ch_nxt = ld_global16(f1.arcs + 64u + lane);
   bool ok = true;
+  // Early issue (vector path): a level of ONE state whose block fits one chunk and matches ONE arc knows the next level's
+  // block — the matched arc's destination range — two instructions after the ballot.  Its rows are asked for there, into
+  // (pf_a, pf_nx), and the level's bookkeeping (on_match, the loop tail, the next label) runs under that load instead of
+  // in front of it; the next level takes the pair when pf is set.  The rows are immutable: a pair that goes unused
+  // (ok = false, the end of the string) is dropped.
+  bool pf = false;
+  const uint32_t L_u = rl(L, 0);  // (L in a scalar register: the early-issue decision stays a scalar branch)
+  uint4 pf_a = make_uint4(0, 0, 0, 0);
+  uint2 pf_nx = make_uint2(0, 0);
   for (uint32_t pos = 0; pos < L && F && ok; ++pos) {
+    const bool use_pf = pf;  // set by the last level: this level is one state, and lanes < min(its arc count, 64) hold its rows
+    pf = false;
     const uint32_t pl = pos & 63u;
     if (pos && pl == 0u) {
       ch_cur = ch_nxt;
@@ -1178,12 +1193,31 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
         const bool have = base + lane < fc;
         uint4 a = make_uint4(0, 0, 0, 0);
         uint2 nx = make_uint2(0, 0);
-        if (have) {
+        if (use_pf && base == 0u) {  // (F == 1: f == 0)
+          a = pf_a;
+          nx = pf_nx;
+        } else if (have) {
           a = ld_global16(f2.arcs + fb + base + lane);
           nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + base + lane));
         }
         uint64_t m = __ballot(have && a.x == label);  // the label-equal run of fst2's (sorted) block, in arc order
         n_arcs += (uint32_t)__popcll(m);
+        if (F == 1u && fc <= 64u && !scalar_rows && pos + 1u < L_u && m != 0ull && (m & (m - 1ull)) == 0ull) {
+          // the one match makes the one state of level pos + 1 (on_match: n_new = 1, its block = [xb, xb + xc)).  Everything
+          // of this level's rows is read off first, so that nothing below waits for vector memory again.
+          const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+          const uint32_t qd = rl(a.w, l), ol = rl(a.y, l), xb = rl(nx.x, l), xc = rl(nx.y, l);
+          const float w2 = __uint_as_float(rl(a.z, l));
+          pf_a = make_uint4(0, 0, 0, 0);
+          pf_nx = make_uint2(0, 0);
+          if (lane < xc) {
+            pf_a = ld_global16(f2.arcs + xb + lane);
+            pf_nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (xb + lane));
+          }
+          pf = true;
+          if (!on_match(f, fd, qd, ol, xb, xc, w2)) ok = false;
+          m = 0;
+        }
         while (m) {
           const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
           m &= m - 1;
@@ -1233,17 +1267,43 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
     res.hops = L;
     res.final_weight = __uint_as_float(rl(__float_as_uint(my_fin), fp - lo));
     res.total = key_f32((uint32_t)(best >> 32));
-    if (lane == 0) {  // walk the parents back (LDS); state k of the walk is in level L - k
-      uint32_t cur = fp;
-      for (uint32_t k = 0; k < L; ++k) {
-        s_pth[k] = cur;
-        cur = s_par[cur];
-      }
-    }
+    // The parents walked back by the whole wave: s_pth[k] = the k-th ancestor of fp (state k of the walk is in level L - k),
+    // by pointer jumping in ceil(log2 L) rounds instead of L dependent LDS round trips of one lane.  Round r knows
+    // s_pth[0 .. m) (m = 2^r) and J = "the m-th ancestor" of every state: s_pth[k] = J(s_pth[k - m]) for k in [m, 2m), then
+    // J <- J o J.  J lives in one 16-bit half of s_par (state ids are below STR_MAXS; 0xFFFF = none, the low half of
+    // STR_NONE) and the next J is written into the other half, so that no lane reads what another one writes in a round.
+    static_assert(STR_MAXS <= 0x8000u, "state ids of the string kernel must fit 16 bits next to the `none` value");
+    if (lane == 0) s_pth[0] = fp;
     lds_handoff();
-    uint32_t poff = 0;
-    if (lane == 0) poff = atomicAdd(path_cursor, L);
-    poff = __shfl(poff, 0);
+    uint32_t sh = 0;  // the half of s_par that holds J
+    for (uint32_t m = 1; m < L; m <<= 1, sh ^= 16u) {
+      for (uint32_t k = m + lane; k < 2u * m && k < L; k += 64) {
+        const uint32_t a = (s_par[s_pth[k - m]] >> sh) & 0xFFFFu;
+        s_pth[k] = a == 0xFFFFu ? 0u : a;  // (never `none` below hop L: the chain from fp to state 0 has exactly L arcs)
+      }
+      if (2u * m < L) {
+        for (uint32_t base = 0; base < hi; base += 256) {  // four loads in flight, then their four dependent loads
+          uint32_t w[4], t[4];
+#pragma unroll
+          for (uint32_t c = 0; c < 4; ++c) {
+            const uint32_t i = base + c * 64u + lane;
+            w[c] = i < hi ? s_par[i] : STR_NONE;
+          }
+#pragma unroll
+          for (uint32_t c = 0; c < 4; ++c) {
+            const uint32_t a = (w[c] >> sh) & 0xFFFFu;
+            t[c] = a == 0xFFFFu ? STR_NONE : s_par[a];
+          }
+#pragma unroll
+          for (uint32_t c = 0; c < 4; ++c) {
+            const uint32_t i = base + c * 64u + lane;
+            const uint32_t keep = (w[c] >> sh) & 0xFFFFu, next = (t[c] >> sh) & 0xFFFFu;
+            if (i < hi) s_par[i] = sh ? (keep << 16) | next : (next << 16) | keep;
+          }
+        }
+      }
+      lds_handoff();
+    }
     if ((uint64_t)poff + L > path_cap) {
       res.status = ST_OVERFLOW_PATH;
     } else {
@@ -1338,6 +1398,8 @@ struct BatchRun {
   uint32_t eager = 0;
   const wfst_tr* host_paths = nullptr;
   bool string_kernel = false;  // this run went through string_compose_sp_kernel
+  uint32_t str_used = 0;       // ... and this many arcs of its path buffer were handed out (ProblemDesc::path_off)
+  const EnvSnap* env = nullptr;  // the WFST_* variables as the batch call found them (null: none of them is asked)
   uint32_t done_ticket = 0;    // ... with results in pinned memory: what every Result::done holds when its problem is finished
   // descriptors read from, results and path arcs written to pinned host memory by the kernel itself: no copy commands
   // (each is a ~3 us API call on the host and a ~5 us command on the GPU) — when the whole path buffer fits there
@@ -1368,18 +1430,36 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
   run.caps = caps;
   run.string_kernel = string_kernel;
   run.stride = string_kernel ? 0 : arena_bytes(caps);
-  run.arena = DBuf<char>(pool, string_kernel ? 256 : run.stride * n);
-  run.d_desc = DBuf<ProblemDesc>(pool, n);
-  run.d_res = DBuf<Result>(pool, n);
-  run.d_cursor = DBuf<uint32_t>(pool, 1);
   uint32_t path_cap = want_paths ? (uint32_t)std::min<uint64_t>((uint64_t)caps.S * n, 0x7FFFFFFFull) : 1u;
   if (exact_path_cap && want_paths) path_cap = std::min(path_cap, exact_path_cap);  // (see ZERO_COPY_ARCS_STRING)
   run.path_cap = path_cap;
   run.eager = want_paths ? std::min(eager_paths, path_cap) : 0u;
   run.zero_copy = want_paths && pinned && run.eager == path_cap && !ctx->profiling;
-  run.paths = DBuf<wfst_tr>(pool, run.zero_copy ? 1 : path_cap);
+  // device blocks: only what the run's kernel reads or writes (a zero-copy string run: none at all — every take and return
+  // of a pool block is host time in front of the launch)
+  if (!string_kernel) {
+    run.arena = DBuf<char>(pool, run.stride * n);
+    run.d_cursor = DBuf<uint32_t>(pool, 1);
+  }
+  if (!run.zero_copy) {
+    run.d_desc = DBuf<ProblemDesc>(pool, n);
+    run.d_res = DBuf<Result>(pool, n);
+    run.paths = DBuf<wfst_tr>(pool, path_cap);
+  }
   ProblemDesc* h_desc = (ProblemDesc*)(pinned ? pinned : (char*)ctx->pinned_big.get(run_pinned_bytes(n, run.eager)));
   std::memcpy(h_desc, descs.data(), n * sizeof(ProblemDesc));
+  run.str_used = 0;
+  if (string_kernel) {
+    // the path of problem i has at most n_states_i - 1 arcs (no input epsilons in fst2): its slice is known here, so the
+    // kernel needs no cursor — no memset command in front of it, no returning atomic at the end of every wave
+    uint64_t off = 0;
+    for (size_t i = 0; i < n; ++i) {
+      h_desc[i].path_off = (uint32_t)off;
+      off += h_desc[i].f1.n_states ? h_desc[i].f1.n_states - 1u : 0u;
+    }
+    if (want_paths && off > path_cap) throw Error("compose_shortest_path_batch: the string run's paths exceed its path buffer (internal error)");
+    run.str_used = (uint32_t)off;
+  }
   run.h_res = (Result*)((char*)h_desc + n * sizeof(ProblemDesc));
   run.h_cursor = (uint32_t*)((char*)run.h_res + n * sizeof(Result));
   run.h_eager = (wfst_tr*)((char*)run.h_cursor + 64);
@@ -1387,12 +1467,14 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
   Result* k_res = run.zero_copy ? run.h_res : run.d_res.p;
   wfst_tr* k_paths = run.zero_copy ? run.h_eager : run.paths.p;
   if (!run.zero_copy) HIP_CHECK(hipMemcpyAsync(run.d_desc.p, h_desc, n * sizeof(ProblemDesc), hipMemcpyHostToDevice, st));
-  HIP_CHECK(hipMemsetAsync(run.d_cursor.p, 0, sizeof(uint32_t), st));
+  if (!string_kernel) HIP_CHECK(hipMemsetAsync(run.d_cursor.p, 0, sizeof(uint32_t), st));
   if (ctx->profiling) HIP_CHECK(hipEventRecord(ctx->ev0, st));
   if (string_kernel) {
     // waves per workgroup x states per problem: 64 KB of LDS per workgroup at most
     uint32_t wpb = 1, maxs = STR_MAXS;
-    if (!std::getenv("WFST_STRING_UNPACKED") && n >= 16) {
+    const EnvSnap none;
+    const EnvSnap& env = run.env ? *run.env : none;
+    if (!env.has("WFST_STRING_UNPACKED") && n >= 16) {
       // a string of L arcs against an input-deterministic-ish T composes to a little more than L states; a problem that
       // outgrows its slice reports ST_NOT_A_STRING_CASE and is redone by the general kernel like any other misfit
       const uint64_t need = max_f1_states ? 2ull * max_f1_states + 64 : STR_MAXS;
@@ -1403,15 +1485,15 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
     // that made a 4096-problem batch 0.7 ms slower; a kernel of milliseconds does not care about 10 us of wake-up latency
     static std::atomic<uint32_t> tickets{0};
     run.done_ticket = 0;
-    if (run.zero_copy && n <= 1024 && !ctx->profiling && !std::getenv("WFST_BATCH_STREAM_WAIT")) {
+    if (run.zero_copy && n <= 1024 && !ctx->profiling && !env.has("WFST_BATCH_STREAM_WAIT")) {
       do run.done_ticket = tickets.fetch_add(1, std::memory_order_relaxed) + 1u; while (run.done_ticket == 0u);
       for (size_t i = 0; i < n; ++i) run.h_res[i].done = 0u;
     }
     string_compose_sp_kernel<<<(uint32_t)((n + wpb - 1) / wpb), 64 * wpb, (size_t)wpb * 16u * maxs, st>>>(
-        k_desc, f2, k_res, k_paths, path_cap, run.d_cursor.p, (uint32_t)n, maxs, f2.n_arcs,
+        k_desc, f2, k_res, k_paths, path_cap, (uint32_t)n, maxs, f2.n_arcs,
         // scalar arc-block loads where a wave is alone on its SIMD (a handful of strings): -7 % per level; with eight waves
         // per compute unit the other waves hide the vector latency anyway and the extra scalar instructions cost 3 %
-        std::getenv("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(std::getenv("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u), run.done_ticket);
+        env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u), run.done_ticket);
   } else
     compose_wave_kernel<FLAGS><<<(uint32_t)n, 64, 0, st>>>(k_desc, f2, caps, run.arena.p, run.stride, k_res, k_paths, path_cap,
                                                             run.d_cursor.p);
@@ -1419,7 +1501,7 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
   if (ctx->profiling) HIP_CHECK(hipEventRecord(ctx->ev1, st));
   if (run.zero_copy) return;
   HIP_CHECK(hipMemcpyAsync(run.h_res, run.d_res.p, n * sizeof(Result), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(run.h_cursor, run.d_cursor.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (!string_kernel) HIP_CHECK(hipMemcpyAsync(run.h_cursor, run.d_cursor.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   if (run.eager)
     HIP_CHECK(hipMemcpyAsync(run.h_eager, run.paths.p, (size_t)run.eager * sizeof(wfst_tr), hipMemcpyDeviceToHost, st));
 }
@@ -1471,7 +1553,8 @@ void launch_end(wfst_ctx* ctx, BatchRun& run) {
   if (want_paths && run.zero_copy) {
     run.host_paths = run.h_eager;  // written by the kernel
   } else if (want_paths) {
-    const uint32_t used = std::min<uint32_t>(*h_cursor, path_cap);
+    // (arcs of the path buffer in use: the host's own sum for a string run, the kernel's cursor otherwise)
+    const uint32_t used = std::min<uint32_t>(run.string_kernel ? run.str_used : *h_cursor, path_cap);
     if (used <= run.eager) {
       run.host_paths = run.h_eager;
     } else {
@@ -1631,6 +1714,7 @@ struct wfst_batch_job {
   wfst::BatchRun run_s;
   wfst::FstView v2_s{};  // fst2 with its per-arc destination ranges
   std::shared_ptr<wfst::PinnedBlock> pin_block;  // descriptors, results and path arcs of the job's runs (pinned host memory)
+  wfst::EnvSnap env;  // the WFST_* variables when the call began: asked by begin, both launch halves and end
 };
 
 namespace wfst {
@@ -1641,6 +1725,8 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   job->ctx = ctx;
   job->n = n;
   if (n == 0) return job.release();
+  job->env = EnvSnap::take();
+  job->run_s.env = &job->env;
   ensure_device(const_cast<wfst_fst*>(t));
   job->v2 = view_of(t);
   job->accs.assign(accs, accs + n);
@@ -1663,7 +1749,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   job->est_a = 2ull * job->est_s;
   // which problems are "string o T" (the decoding case)?
   bool string_ok = (filter == 0 || filter == 3) && t->n_arcs > 0 && t->n_arcs < 0xFFFFFFFFull;
-  if (const char* e = std::getenv("WFST_STRING_KERNEL")) string_ok = string_ok && std::atoi(e) != 0;
+  if (const char* e = job->env.get("WFST_STRING_KERNEL")) string_ok = string_ok && std::atoi(e) != 0;
   if (string_ok) {
     bool any = false;
     for (size_t i = 0; i < n && !any; ++i) any = accs[i]->is_string && accs[i]->n_states <= STR_MAXS;
@@ -1695,7 +1781,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   {  // a run whose whole path buffer fits in pinned memory writes there itself (launch_begin: zero_copy)
     const Caps c0 = make_caps(job->est_s, job->est_a);
     const uint64_t cap_s = (uint64_t)c0.S * d_str.size(), cap_g = (uint64_t)c0.S * d_gen.size();
-    const bool allow = !std::getenv("WFST_BATCH_COPY");  // tests: the copy-command path
+    const bool allow = !job->env.has("WFST_BATCH_COPY");  // tests: the copy-command path
     if (allow && cap_s && cap_s <= ZERO_COPY_ARCS) e_s = (uint32_t)cap_s;
     else if (allow && eager_s && eager_s <= ZERO_COPY_ARCS_STRING) e_s = (uint32_t)eager_s;  // = the run's whole path buffer
     if (allow && cap_g && cap_g <= ZERO_COPY_ARCS) e_g = (uint32_t)cap_g;
@@ -1724,7 +1810,7 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
   // result i: a path FST handle, or (sink) its record — straight from the kernel's result and path buffers
   const size_t rec_words = sink ? 4 + 4 * (size_t)sink->max_arcs : 0;
   // (views only into blocks of serving size: one surviving result would otherwise keep tens of MB pinned)
-  const bool views = job->pin_block && job->pin_block->cap <= (4u << 20) && !std::getenv("WFST_BATCH_EAGER_PATHS");
+  const bool views = job->pin_block && job->pin_block->cap <= (4u << 20) && !job->env.has("WFST_BATCH_EAGER_PATHS");
   auto emit = [&](size_t i, const Result& r, const wfst_tr* arcs, bool in_block) {
     if (sink) pack_path_record(sink->out + i * rec_words, sink->max_arcs, r.has_path != 0, r.hops, r.final_weight, arcs);
     else if (views && in_block && r.has_path && r.hops) outs[i] = path_view_fst(ctx, r, arcs, job->pin_block);
@@ -1732,7 +1818,7 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
   };
   uint64_t tot_arcs = 0, tot_states = 0, n_string_ok = 0;
   double ms = 0;
-  const bool timing = std::getenv("WFST_HOST_TIMING") != nullptr;
+  const bool timing = job->env.has("WFST_HOST_TIMING");
   auto tnow = [] { return std::chrono::steady_clock::now(); };
   auto t_a = tnow();
   try {
@@ -1754,9 +1840,9 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
       }
       // the path FSTs (three small vectors and a handle each: ~0.4 us): a large batch shares them out among host threads
       // (records are a copy of ~3 KB each: fewer threads than for handles — creating a thread costs as much as ~50 records)
-      const unsigned n_thr = std::getenv("WFST_HOST_THREADS")
-                                 ? host_threads(ok.size())
-                                 : (unsigned)std::min<size_t>(std::min(sink ? 8u : 16u, host_threads(1u << 16)), ok.size() / (sink ? 512 : 256));
+      const char* env_thr = job->env.get("WFST_HOST_THREADS");
+      const unsigned n_thr = env_thr ? host_threads(ok.size(), env_thr)
+                                     : (unsigned)std::min<size_t>(std::min(sink ? 8u : 16u, host_threads(1u << 16, nullptr)), ok.size() / (sink ? 512 : 256));
       parallel_chunks(n_thr, ok.size(), 64, [&](unsigned, uint64_t b, uint64_t e) {
         for (uint64_t q = b; q < e; ++q) {
           const Result& r = job->run_s.results[ok[q]];

@@ -12,14 +12,16 @@
 
 namespace wfst {
 
-// threads for a pass over `work_items` items: all cores up to 32 (WFST_HOST_THREADS overrides), one for small inputs
-inline unsigned host_threads(uint64_t work_items) {
+// threads for a pass over `work_items` items: all cores up to 32 (WFST_HOST_THREADS overrides), one for small inputs.
+// `env_threads`: the value of WFST_HOST_THREADS (null: not set), for callers that hold a snapshot of the environment
+inline unsigned host_threads(uint64_t work_items, const char* env_threads) {
   unsigned n = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* e = std::getenv("WFST_HOST_THREADS")) n = (unsigned)std::max(1, std::atoi(e));
+  if (env_threads) n = (unsigned)std::max(1, std::atoi(env_threads));
   n = std::min(n, 32u);
-  if (work_items < (1u << 16) && !std::getenv("WFST_HOST_THREADS")) n = 1;  // (tests force threads on small inputs)
+  if (work_items < (1u << 16) && !env_threads) n = 1;  // (tests force threads on small inputs)
   return n;
 }
+inline unsigned host_threads(uint64_t work_items) { return host_threads(work_items, std::getenv("WFST_HOST_THREADS")); }
 
 // body(thread, begin, end) over [0, n_items) in chunks handed out by an atomic counter; the first exception is rethrown
 template <class F>

@@ -90,6 +90,7 @@ struct Ctl {
   uint32_t tail_ticket, tail_pad;
 };
 constexpr uint32_t TAIL_BLOCKS = 128;
+constexpr uint32_t TAIL_LIST_BLOCKS = 16;  // ... over the handle's list of final states (RevCsr::fin), 4096 entries each
 // what the host needs from the tail of a solve, written straight into pinned memory by sssp_tail_kernel
 struct TailOut {
   uint32_t has_path, hops, pad, f_parent;
@@ -810,7 +811,8 @@ __global__ void __launch_bounds__(64) sssp_backtrace_rev_kernel(const uint32_t* 
 // control block cost ~30 us at the end of every solve; 1024 workgroups each polling and lowering ONE word were most of
 // the final-state search: same-address atomics serialise at ~12 ns.)
 __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict__ finals, const uint64_t* __restrict__ key,
-                                                         uint32_t n, Ctl* __restrict__ ctl,
+                                                         uint32_t n, const uint2* __restrict__ fin_list, uint32_t n_fin,
+                                                         Ctl* __restrict__ ctl,
                                                          const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ arcs,
                                                          const uint32_t* __restrict__ rev_off,
                                                          const uint4* __restrict__ rev_arc, wfst_tr* __restrict__ out,
@@ -836,14 +838,23 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   };
   unsigned long long best = KEY_INF;
   bool tie = false;
-  for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-    const float f = finals[s];
-    if (!(f < INF)) continue;  // most states are not final: their key is never fetched
+  auto candidate = [&](uint32_t s, float f) {
     const uint64_t k = key[s];
-    if (k == KEY_INF) continue;
+    if (k == KEY_INF) return;
     const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
-    if (!(tot < INF)) continue;
+    if (!(tot < INF)) return;
     merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
+  };
+  if (fin_list) {  // the handle's list of its final states {state, final weight}: the same candidates, found without the scan
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_fin; i += gridDim.x * blockDim.x) {
+      const uint2 e = fin_list[i];
+      candidate(e.x, __uint_as_float(e.y));
+    }
+  } else {
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
+      const float f = finals[s];
+      if (f < INF) candidate(s, f);  // most states are not final: their key is never fetched
+    }
   }
   for (int d = 32; d >= 1; d >>= 1) {
     const unsigned long long o = __shfl_xor(best, d);
@@ -859,10 +870,15 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
       const unsigned long long o = s_best[w];
       merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
     }
-    __hip_atomic_store(&ctl->tail_best[blockIdx.x], best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull)), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    s_last = atomicAdd(&ctl->tail_ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    const unsigned long long mine = best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
+    if (gridDim.x == 1) {  // the only workgroup is the last one: nothing to hand over, nothing to draw
+      s_best[0] = mine;
+      s_last = 1u;
+    } else {
+      __hip_atomic_store(&ctl->tail_best[blockIdx.x], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence();
+      s_last = atomicAdd(&ctl->tail_ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    }
   }
   __syncthreads();
   if (!s_last || threadIdx.x >= 64) return;
@@ -882,7 +898,7 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   best = KEY_INF;
   tie = false;
   for (uint32_t b = lane; b < gridDim.x; b += 64) {
-    const unsigned long long o = __hip_atomic_load(&ctl->tail_best[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long o = gridDim.x == 1 ? s_best[0] : __hip_atomic_load(&ctl->tail_best[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
   }
   for (int d = 32; d >= 1; d >>= 1) {
@@ -1153,40 +1169,44 @@ struct Knobs {
   std::optional<int> umax;              // WFST_SSSP_UMAX
   bool split_tail = false;              // WFST_SSSP_SPLIT_TAIL (by presence)
   bool count_atomics = false;           // WFST_SSSP_COUNT_ATOMICS (by presence)
+  int final_list = 1;                   // WFST_SSSP_FINAL_LIST
 };
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
+// One pass over the environment (EnvSnap) instead of a getenv per variable: this runs in front of the first launch.
 Knobs read_knobs() {
+  const EnvSnap env = EnvSnap::take();
   Knobs k;
-  if (const char* e = std::getenv("WFST_SSSP_MAILBOX")) k.mailbox = std::atoi(e);
-  if (const char* e = std::getenv("WFST_SSSP_NARROW")) k.narrow = (uint32_t)std::atol(e);
-  if (const char* e = std::getenv("WFST_SSSP_HINT")) k.hint = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WFST_SSSP_BIG")) k.big = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WFST_SSSP_STG")) k.stg = (uint32_t)std::atoi(e);
-  if (const char* e = std::getenv("WFST_SSSP_DELTA")) k.delta = (float)std::atof(e);
-  if (const char* e = std::getenv("WFST_SSSP_NEAR_LOW")) k.near_low = (uint32_t)std::atol(e);
-  if (const char* e = std::getenv("WFST_SSSP_TAU0_MULT")) k.tau0_mult = (float)std::atof(e);
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_CAP")) k.chase_cap = std::min<uint32_t>((uint32_t)std::atol(e), CHASE_MAX);
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_ROUNDS")) k.chase_rounds = (uint32_t)std::atol(e);
-  if (const char* e = std::getenv("WFST_SSSP_CHASE_LOW")) k.chase_low = (uint32_t)std::atol(e);
-  k.mbox_trace = std::getenv("WFST_SSSP_MBOX_TRACE");
-  if (const char* e = std::getenv("WFST_SSSP_RESIDENT")) k.resident = std::atoi(e);
-  if (const char* e = std::getenv("WFST_SSSP_RES_LEVELS")) k.res_levels = std::max<uint32_t>(2u, std::min<uint32_t>(RS_LEVEL_CAP, (uint32_t)std::atol(e)));
-  if (const char* e = std::getenv("WFST_SSSP_RES_TLIM_US")) k.res_tlim_us = std::atoll(e);
-  k.log12 = std::getenv("WFST_SSSP_LOG12") != nullptr;
-  k.res_trace = std::getenv("WFST_SSSP_RES_TRACE");
-  if (const char* e = std::getenv("WFST_SSSP_BINNED")) k.binned = std::atoi(e);
-  if (const char* e = std::getenv("WFST_SSSP_DENSE_LOW")) k.dense_low = std::atoll(e);
-  if (const char* e = std::getenv("WFST_SSSP_BIN_LOG")) k.bin_log14 = std::atoi(e) == 14;
-  if (const char* e = std::getenv("WFST_SSSP_BIN_HOPCAP")) k.bin_hopcap = (uint32_t)std::atol(e);
-  if (const char* e = std::getenv("WFST_SSSP_RES_RETRY_MS")) k.res_retry_ms = std::max<long long>(0ll, std::atoll(e));
-  k.test_fail_log13 = std::getenv("WFST_SSSP_TEST_FAIL_LOG13") != nullptr;
-  k.event_wait = std::getenv("WFST_SSSP_EVENT_WAIT") != nullptr;
-  if (const char* e = std::getenv("WFST_SSSP_LOG13")) k.log13 = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WFST_SSSP_LPS")) k.lps = std::max(2, std::min(8, std::atoi(e)));
-  if (const char* e = std::getenv("WFST_SSSP_UMAX")) k.umax = std::atoi(e) >= 4 ? 4 : 2;
-  k.split_tail = std::getenv("WFST_SSSP_SPLIT_TAIL") != nullptr;
-  k.count_atomics = std::getenv("WFST_SSSP_COUNT_ATOMICS") != nullptr;
+  if (const char* e = env.get("WFST_SSSP_MAILBOX")) k.mailbox = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_NARROW")) k.narrow = (uint32_t)std::atol(e);
+  if (const char* e = env.get("WFST_SSSP_HINT")) k.hint = std::atoi(e) != 0;
+  if (const char* e = env.get("WFST_SSSP_BIG")) k.big = std::atoi(e) != 0;
+  if (const char* e = env.get("WFST_SSSP_STG")) k.stg = (uint32_t)std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_DELTA")) k.delta = (float)std::atof(e);
+  if (const char* e = env.get("WFST_SSSP_NEAR_LOW")) k.near_low = (uint32_t)std::atol(e);
+  if (const char* e = env.get("WFST_SSSP_TAU0_MULT")) k.tau0_mult = (float)std::atof(e);
+  if (const char* e = env.get("WFST_SSSP_CHASE_CAP")) k.chase_cap = std::min<uint32_t>((uint32_t)std::atol(e), CHASE_MAX);
+  if (const char* e = env.get("WFST_SSSP_CHASE_ROUNDS")) k.chase_rounds = (uint32_t)std::atol(e);
+  if (const char* e = env.get("WFST_SSSP_CHASE_LOW")) k.chase_low = (uint32_t)std::atol(e);
+  k.mbox_trace = env.get("WFST_SSSP_MBOX_TRACE");
+  if (const char* e = env.get("WFST_SSSP_RESIDENT")) k.resident = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_RES_LEVELS")) k.res_levels = std::max<uint32_t>(2u, std::min<uint32_t>(RS_LEVEL_CAP, (uint32_t)std::atol(e)));
+  if (const char* e = env.get("WFST_SSSP_RES_TLIM_US")) k.res_tlim_us = std::atoll(e);
+  k.log12 = env.get("WFST_SSSP_LOG12") != nullptr;
+  k.res_trace = env.get("WFST_SSSP_RES_TRACE");
+  if (const char* e = env.get("WFST_SSSP_BINNED")) k.binned = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_DENSE_LOW")) k.dense_low = std::atoll(e);
+  if (const char* e = env.get("WFST_SSSP_BIN_LOG")) k.bin_log14 = std::atoi(e) == 14;
+  if (const char* e = env.get("WFST_SSSP_BIN_HOPCAP")) k.bin_hopcap = (uint32_t)std::atol(e);
+  if (const char* e = env.get("WFST_SSSP_RES_RETRY_MS")) k.res_retry_ms = std::max<long long>(0ll, std::atoll(e));
+  k.test_fail_log13 = env.get("WFST_SSSP_TEST_FAIL_LOG13") != nullptr;
+  k.event_wait = env.get("WFST_SSSP_EVENT_WAIT") != nullptr;
+  if (const char* e = env.get("WFST_SSSP_LOG13")) k.log13 = std::atoi(e) != 0;
+  if (const char* e = env.get("WFST_SSSP_LPS")) k.lps = std::max(2, std::min(8, std::atoi(e)));
+  if (const char* e = env.get("WFST_SSSP_UMAX")) k.umax = std::atoi(e) >= 4 ? 4 : 2;
+  k.split_tail = env.get("WFST_SSSP_SPLIT_TAIL") != nullptr;
+  k.count_atomics = env.get("WFST_SSSP_COUNT_ATOMICS") != nullptr;
+  if (const char* e = env.get("WFST_SSSP_FINAL_LIST")) k.final_list = std::atoi(e);
   return k;
 }
 
@@ -1794,7 +1814,7 @@ struct SweepDriver {
   }
 
   // `defer_advance`: the caller queues a kernel behind the batch that closes it (sssp_tail_kernel mirrors the flags and
-  // advances the base itself) and records the event
+  // advances the base itself); no event is recorded (wait_first_batch)
   SweepBatch enqueue_batch(hipEvent_t ev, bool defer_advance = false) {
     hipStream_t st = ctx->stream;
     // after the first batch: constant small batches while the solve is shallow, larger ones for deep lattices
@@ -1840,7 +1860,7 @@ struct SweepDriver {
   void start(bool defer_advance = false) { cur = enqueue_batch(evs[0], defer_advance); }
 
   // The fused tail's ticket in pinned memory (wfst_sp_job::h_tail->done), when the first batch ends with one: the host waits
-  // for that word — every result of the launch chain is in host memory before it — and falls back to the event.
+  // for that word — every result of the launch chain is in host memory before it — and falls back to the stream.
   const volatile uint32_t* done_word = nullptr;
   uint32_t done_ticket = 0;
   bool done_seen = false;  // the ticket arrived: nothing of this job is still running on the stream
@@ -1857,7 +1877,10 @@ struct SweepDriver {
         if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;  // (a long solve: sleep on the event)
       }
     }
-    HIP_CHECK(hipEventSynchronize(evs[0]));
+    // (the batch that ends with the fused tail records no event — a host call in front of whatever the caller queues next,
+    // for a wait that is taken only after 2 ms of spinning or under WFST_SSSP_EVENT_WAIT: it waits for the stream instead)
+    if (done_word) HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    else HIP_CHECK(hipEventSynchronize(evs[0]));
   }
 
   void finish() {
@@ -2132,10 +2155,49 @@ void shortest_distance_device(wfst_ctx* ctx, const wfst_fst* f, float* d_distanc
 // waits for the compute units the build holds — 0.65 -> 1.8 ms, and a one-shot query pays for a transpose it never uses.)
 // `force`: the caller needs the in-arcs of the path's states now (tie order 1 on a cyclic input).
 namespace {
+constexpr uint32_t FINAL_LIST_MAX = 65536;  // entries; and at most one state in eight may be final
+
+__global__ void __launch_bounds__(256) final_flag_kernel(const float* __restrict__ finals, uint32_t n, uint32_t* __restrict__ flag) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s <= n) flag[s] = s < n && finals[s] < INF ? 1u : 0u;  // (n + 1 entries: the scan's last output is the count)
+}
+__global__ void __launch_bounds__(256) final_list_kernel(const float* __restrict__ finals, uint32_t n, const uint32_t* __restrict__ pos,
+                                                        uint2* __restrict__ list, uint32_t cap) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const float fw = finals[s];
+  if (fw < INF && pos[s] < cap) list[pos[s]] = make_uint2(s, __float_as_uint(fw));
+}
+
+// The list of final states of f (RevCsr::fin), built with the transpose: sssp_tail_kernel then reads a few thousand pairs
+// instead of n final weights in every query.
+void final_list_build(wfst_ctx* ctx, const wfst_fst* f, DevicePool& owner_pool, RevCsr& r) {
+  const uint32_t n = f->n_states;
+  hipStream_t st = ctx->stream;
+  r.has_fin = false;
+  r.n_fin = 0;
+  if (n < 8 || n >= 0xFFFFFFF0u) return;
+  DBuf<uint32_t> flag(*ctx->pool, (size_t)n + 1), pos(*ctx->pool, (size_t)n + 1);
+  final_flag_kernel<<<n / 256 + 1, 256, 0, st>>>(f->dev.finals, n, flag.p);
+  HIP_CHECK(hipGetLastError());
+  const DBuf<uint8_t> scan_tmp = exclusive_scan_u32(ctx, flag.p, pos.p, (size_t)n + 1);
+  const uint32_t n_fin = read_u32(ctx, pos.p + n);  // (synchronises the stream)
+  if (n_fin > FINAL_LIST_MAX || n_fin > n / 8) return;
+  r.fin = DBuf<uint2>(owner_pool, n_fin);
+  if (n_fin) {
+    final_list_kernel<<<(n + 255) / 256, 256, 0, st>>>(f->dev.finals, n, pos.p, r.fin.p, n_fin);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));  // flag / pos / scan_tmp are released here
+  }
+  r.n_fin = n_fin;
+  r.has_fin = true;
+}
+
 void reverse_csr_build(wfst_ctx* ctx, const wfst_fst* f, RevCsr& r) {
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
   DevicePool& owner_pool = f->owner_pool ? *f->owner_pool : *ctx->pool;  // cached with the handle: the owner's pool outlives it
+  final_list_build(ctx, f, owner_pool, r);
   r.off = DBuf<uint32_t>(owner_pool, (size_t)n + 1);
   r.arc = DBuf<uint4>(owner_pool, f->n_arcs);
   const MboxPlan* plan = f->mbox ? f->mbox.get() : f->mbox13.get();  // (cache_mu is held by the caller)
@@ -2213,8 +2275,14 @@ void queue_tail(wfst_sp_job* j, const SweepBatch* adv = nullptr) {
   hipStream_t st = ctx->stream;
   Solve& sv = j->sv;
   if (j->rev && !sv.kn.split_tail) {  // one launch, header straight into pinned memory
-    sssp_tail_kernel<<<std::min<uint32_t>(TAIL_BLOCKS, (n + 1023) / 1024), 1024, 0, st>>>(
-        f->dev.finals, sv.key.p, n, sv.ctl.p, f->dev.offsets, f->dev.arcs, j->rev->off.p, j->rev->arc.p, j->h_path,
+    // over the handle's list of final states where it has one (WFST_SSSP_FINAL_LIST=0: the scan of `finals`; 2: the list or
+    // an error, for tests): 4 entries per thread, ONE workgroup — no hand-over between workgroups — up to 4096 entries
+    const bool listed = j->rev->has_fin && sv.kn.final_list != 0;
+    const uint32_t blocks = listed ? std::max<uint32_t>(1u, std::min<uint32_t>(TAIL_LIST_BLOCKS, (j->rev->n_fin + 4095) / 4096))
+                                   : std::min<uint32_t>(TAIL_BLOCKS, (n + 1023) / 1024);
+    sssp_tail_kernel<<<blocks, 1024, 0, st>>>(
+        f->dev.finals, sv.key.p, n, listed ? j->rev->fin.p : nullptr, listed ? j->rev->n_fin : 0u, sv.ctl.p, f->dev.offsets, f->dev.arcs,
+        j->rev->off.p, j->rev->arc.p, j->h_path,
         PATH_PINNED, j->h_tail, sv.improved.p, adv ? adv->count : 0u, adv ? j->drv.host_flags(*adv) : nullptr, j->done_ticket);
     j->fused_tail = true;
     return;
@@ -2268,13 +2336,16 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
     return j.release();
   }
   relax_setup(ctx, f, j->sv);
+  if (j->sv.kn.final_list >= 2 && j->rev && !j->rev->has_fin) {  // tests: which of the two tails a handle gets
+    (void)hipStreamSynchronize(ctx->stream);  // (the set-up is queued: the solve's buffers go back to the pool after this)
+    throw Error("shortest_path: WFST_SSSP_FINAL_LIST=2 and the handle has no list of final states");
+  }
   ctx->stats.sweeps = 0;
   j->drv.init(ctx, f, &j->sv);
   const bool fuse = j->drv.predicted && j->rev && !j->sv.kn.split_tail;
   j->drv.start(/*defer_advance=*/fuse);
-  if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket (and the event) finish() waits for
+  if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
     queue_tail(j.get(), &j->drv.cur);
-    HIP_CHECK(hipEventRecord(j->drv.evs[0], ctx->stream));
     j->tail_queued = true;
     j->drv.done_word = &j->h_tail->done;
     j->drv.done_ticket = j->done_ticket;
