@@ -245,6 +245,7 @@ struct RevCsr {
   DBuf<uint2> fin;
   uint32_t n_fin = 0;
   bool has_fin = false;
+  bool fin_nonneg = false;  // no final weight of the list is negative (what the early tail of a query needs)
 };
 // Message-region plan of the mailbox relaxation sweeps (sssp_mailbox.h): offsets of the region reserved for every
 // (source block, destination block) pair, sized by the number of arcs between the two blocks.

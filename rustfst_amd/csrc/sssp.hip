@@ -88,6 +88,12 @@ struct Ctl {
   // fused tail (sssp_tail_kernel): per-workgroup best final state, and the ticket that tells the last workgroup it is last
   unsigned long long tail_best[128];
   uint32_t tail_ticket, tail_pad;
+  // early tail (sssp_early_tail): the least enc(d) a NARROW launch k wrote into key[] (all ones: it lowered nothing), and
+  // what the extra workgroup of such a launch found while the others were still relaxing — (best | TIE_BIT) as in tail_best,
+  // and the launch it ran in (0 = none: launch 0 never runs it).  sssp_tail_kernel decides whether that result stands.
+  uint32_t narrow_low[RING];
+  unsigned long long early_best;
+  uint32_t early_sweep, early_pad;
 };
 constexpr uint32_t TAIL_BLOCKS = 128;
 constexpr uint32_t TAIL_LIST_BLOCKS = 16;  // ... over the handle's list of final states (RevCsr::fin), 4096 entries each
@@ -100,7 +106,22 @@ struct TailOut {
                   // are waiting, on the critical path of every query)
   uint32_t ties;  // states of the returned path with more than one optimal predecessor (the start state: with any), + 1 when
                   // several final states attain the optimum: 0 = the optimum is unique (wfst_stats.tied_choices)
+  uint32_t early;  // EARLY_*: what sssp_tail_kernel made of the early tail's result
 };
+constexpr uint32_t EARLY_UNCHECKED = 0, EARLY_USED = 1, EARLY_ABSENT = 2, EARLY_REFUTED = 3;
+// what the extra workgroup of a mailbox launch needs for the tail's work (sssp_early_tail); by value, last kernel argument
+struct EarlyTail {
+  const uint2* fin_list;  // RevCsr::fin
+  const float* finals;
+  const wfst_tr* arcs;
+  const uint32_t* rev_off;
+  const uint4* rev_arc;
+  wfst_tr* out;   // pinned host memory
+  TailOut* hout;  // pinned host memory
+  uint32_t n_fin, out_cap;
+};
+__device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint32_t* __restrict__ offsets, const uint64_t* __restrict__ key,
+                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds);
 
 // threshold of sweep k from what sweep k-1 left in the ring (every thread computes the same value)
 // Called by one full wave (all 64 lanes): lanes 0..15 fetch the shards of sweep-1's counter, lanes 16..31 those of
@@ -804,12 +825,159 @@ __global__ void __launch_bounds__(64) sssp_backtrace_rev_kernel(const uint32_t* 
   }
 }
 
+// ---- what sssp_tail_kernel and the early tail (sssp_early_tail) share: the arg-min over the final states and the walk.
+// (enc(total) << 32 | final state) and whether ANOTHER final state attains the same total: merged pairwise; where the pair
+// travels as one word the flag sits in bit 31 of the state word (state ids have 31 bits)
+constexpr unsigned long long TIE_BIT = 1ull << 31;
+__device__ __forceinline__ void tail_merge(unsigned long long& best, bool& tie, unsigned long long o, bool o_tie) {
+  if (o == KEY_INF) return;
+  if ((o >> 32) == (best >> 32)) {
+    tie = true;
+    best = o < best ? o : best;
+  } else if (o < best) {
+    best = o;
+    tie = o_tie;
+  }
+}
+__device__ __forceinline__ unsigned long long tail_pack(unsigned long long best, bool tie) {
+  return best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
+}
+__device__ __forceinline__ void tail_merge_packed(unsigned long long& best, bool& tie, unsigned long long o) {
+  tail_merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
+}
+__device__ __forceinline__ void tail_wave_reduce(unsigned long long& best, bool& tie) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(best, d);
+    const bool ot = __shfl_xor((int)tie, d) != 0;
+    tail_merge(best, tie, o, ot);
+  }
+}
+__device__ __forceinline__ void tail_candidate(uint64_t k /* key[s] */, uint32_t s, float f, unsigned long long& best, bool& tie) {
+  if (k == KEY_INF) return;
+  const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
+  if (!(tot < INF)) return;
+  tail_merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
+}
+// the handle's list of its final states {state, final weight}: entries first, first + stride, ... — four in flight (two
+// dependent trips per four entries; the order of the merges does not matter).  (Sixteen in flight in the early tail's ONE
+// workgroup were no faster: 14 000 gathered keys are ~6 us of one compute unit's L1 however they are asked for.)
+__device__ __forceinline__ void tail_search_list(const uint64_t* __restrict__ key, const uint2* __restrict__ fin_list, uint32_t n_fin,
+                                                 uint32_t first, uint32_t stride, unsigned long long& best, bool& tie) {
+  constexpr uint32_t U = 4;
+  for (uint32_t i = first; i < n_fin; i += U * stride) {
+    uint2 e[U];
+    uint64_t k[U];
+    for (uint32_t u = 0; u < U; ++u) {
+      e[u] = make_uint2(0u, 0u);
+      if (i + u * stride < n_fin) e[u] = fin_list[i + u * stride];
+    }
+    for (uint32_t u = 0; u < U; ++u) {
+      k[u] = KEY_INF;
+      if (i + u * stride < n_fin) k[u] = key[e[u].x];
+    }
+    for (uint32_t u = 0; u < U; ++u) tail_candidate(k[u], e[u].x, __uint_as_float(e[u].y), best, tie);
+  }
+}
+// One wave, `best` / `tie` / `pad` uniform: the header of the result and the path's arcs go to pinned host memory (every
+// TailOut field except `done` and `early`), and to the control block where `ctl` is given.  Returns pad with the walk's flags.
+__device__ __forceinline__ uint32_t tail_walk_publish(unsigned long long best, bool tie, uint32_t pad, const float* __restrict__ finals,
+                                                      const uint64_t* __restrict__ key, const uint32_t* __restrict__ offsets,
+                                                      const wfst_tr* __restrict__ arcs, const uint32_t* __restrict__ rev_off,
+                                                      const uint4* __restrict__ rev_arc, wfst_tr* __restrict__ out, uint32_t out_cap,
+                                                      TailOut* __restrict__ hout, Ctl* __restrict__ ctl, uint2* s_walk) {
+  const uint32_t lane = threadIdx.x & 63u;
+  if (best == KEY_INF) {
+    if (lane == 0) {
+      if (ctl) {
+        ctl->has_path = 0;
+        ctl->hops = 0;
+      }
+      hout->has_path = 0u;
+      hout->hops = 0u;
+      hout->pad = pad;
+      hout->f_parent = 0u;
+      hout->final_weight = INF;
+      hout->total = INF;
+      hout->ties = 0u;
+    }
+    return pad;
+  }
+  const uint32_t fp = (uint32_t)best;
+  const float final_weight = finals[fp], total = key_f32((uint32_t)(best >> 32));
+  uint32_t k = 0, ties = tie ? 1u : 0u;
+  if ((uint32_t)key[fp] > out_cap) pad |= 8u;  // the host falls back to the parent pass
+  else k = sssp_walk_back(offsets, arcs, key, rev_off, rev_arc, fp, out, out_cap, pad, s_walk, ties);
+  if (lane == 0) {
+    const uint32_t hops = (pad & 12u) ? (uint32_t)key[fp] : k;
+    if (ctl) {
+      ctl->has_path = 1;
+      ctl->f_parent = fp;
+      ctl->hops = hops;
+      ctl->final_weight = final_weight;
+      ctl->total = total;
+    }
+    // (the walk's own flags go to the host only: a tail that ran ahead of the last sweeps is run again on this block)
+    hout->has_path = 1u;
+    hout->hops = hops;
+    hout->pad = pad;
+    hout->f_parent = fp;
+    hout->final_weight = final_weight;
+    hout->total = total;
+    hout->ties = ties;
+  }
+  return pad;
+}
+
+// The early tail: the extra workgroup of a NARROW launch behind a hand-over (sssp_mbox_kernel, blockIdx.x == nb) does the
+// tail's search and walk on keys that other workgroups of the SAME launch are still lowering, with plain loads, and leaves
+// {launch, best | TIE_BIT} in the control block; sssp_tail_kernel certifies the result or computes it again.  `lds`: 16 words
+// for the waves' results, WALK_LDS entries of the walk behind them.  Nothing the ordinary tail uses is touched.
+__device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint32_t* __restrict__ offsets, const uint64_t* __restrict__ key,
+                                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds) {
+  // (a launch queued behind the solve's last one: the fixed point was reached, or the solve gave up — as sssp_mbox_resident_kernel)
+  const uint32_t pf = prev_flag;
+  if (pf == 0u || pf == FLAG_NARROW_CLEAN || pf == FLAG_RES_ABORT) return;
+  unsigned long long* const s_best = lds;
+  uint2* const s_walk = (uint2*)(lds + 16);
+  const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
+  unsigned long long best = KEY_INF;
+  bool tie = false;
+  tail_search_list(key, et.fin_list, et.n_fin, threadIdx.x, blockDim.x, best, tie);
+  tail_wave_reduce(best, tie);
+  if (lane == 0) s_best[threadIdx.x >> 6] = tail_pack(best, tie);
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  best = KEY_INF;
+  tie = false;
+  if (lane < waves) tail_merge_packed(best, tie, s_best[lane]);
+  tail_wave_reduce(best, tie);
+  const uint32_t pad = tail_walk_publish(best, tie, 0u, et.finals, key, offsets, et.arcs, et.rev_off, et.rev_arc, et.out, et.out_cap,
+                                         et.hout, nullptr, s_walk);
+  host_stores_done();
+  // (a walk that did not end at the start state, or a path beyond the pinned buffer: the ordinary tail's business)
+  if (lane == 0 && !(pad & 12u)) {
+    ctl->early_best = tail_pack(best, tie);
+    ctl->early_sweep = sweep;
+  }
+}
+
 // The tail of a repeated query in ONE launch: arg-min over the final states (sssp_final_kernel), the header
 // (sssp_header_kernel) and the walk over the transpose (sssp_backtrace_rev_kernel), with the result header written into
 // pinned host memory next to the path arcs.  Every workgroup leaves the best final state of its share; the workgroup
 // that draws the last ticket reduces them and walks back.  (Three launches, a 1-thread kernel and a copy of the whole
 // control block cost ~30 us at the end of every solve; 1024 workgroups each polling and lowering ONE word were most of
 // the final-state search: same-address atomics serialise at ~12 ns.)
+//
+// `early_check`: the batch in front of this launch may have run the early tail (sssp_early_tail).  Let k be the launch it
+// ran in and B the best total it found.  Its result — header and path, already in host memory — stands if and only if
+// launch k's flag is FLAG_NARROW_CLEAN (the fixed point was reached in that launch: a launch that leaves anything waiting
+// is not CLEAN) and narrow_low[k] > enc(B), strictly: every key lowered while the early tail was reading went to a value
+// above B, from a value that was higher still.  Arc and final weights are >= 0 where the early tail runs, so
+//   * a predecessor s of a state t on the path needs enc(d[s] + w) == enc(d[t]) <= enc(B) in either predecessor class; with
+//     w >= 0 a source above B is never admissible, whether the walk read its key before or after it changed;
+//   * a final state whose key changed has a total >= its key, above B before and after: neither the optimum nor a tie;
+//   * a write AT B could make a tie (a second final state, a second tight in-arc), hence the strict inequality.
+// Every key at or below B is one no writer of launch k touched: the early tail read what this kernel would read.
 __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict__ finals, const uint64_t* __restrict__ key,
                                                          uint32_t n, const uint2* __restrict__ fin_list, uint32_t n_fin,
                                                          Ctl* __restrict__ ctl,
@@ -818,59 +986,61 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
                                                          const uint4* __restrict__ rev_arc, wfst_tr* __restrict__ out,
                                                          uint32_t out_cap, TailOut* __restrict__ hout,
                                                          uint32_t* __restrict__ improved_ring, uint32_t adv_count,
-                                                         uint32_t* __restrict__ host_ring, uint32_t done_ticket) {
+                                                         uint32_t* __restrict__ host_ring, uint32_t done_ticket, uint32_t early_check) {
   __shared__ unsigned long long s_best[16];
   __shared__ uint2 s_walk[WALK_LDS];
   __shared__ uint32_t s_last;
   const uint32_t lane = threadIdx.x & 63u;
-  // (enc(total) << 32 | final state) and whether ANOTHER final state attains the same total: merged pairwise; between
-  // workgroups the flag travels in bit 31 of the state word (state ids have 31 bits)
-  constexpr unsigned long long TIE_BIT = 1ull << 31;
-  auto merge = [](unsigned long long& best, bool& tie, unsigned long long o, bool o_tie) {
-    if (o == KEY_INF) return;
-    if ((o >> 32) == (best >> 32)) {
-      tie = true;
-      best = o < best ? o : best;
-    } else if (o < best) {
-      best = o;
-      tie = o_tie;
+  // closes the sweep batch queued in front of this launch (what sssp_advance_kernel does: the flags of its sweeps go to
+  // pinned host memory, the slots half a ring ahead are recycled, the base moves on) — one launch and one flush of
+  // host-memory writes less at the end of a predicted solve.  By the wave that writes the ticket at the end: ONE
+  // system-scope fence orders all of it.
+  auto advance = [&]() {
+    const uint32_t base = ctl->base;
+    for (uint32_t i = lane; i < adv_count; i += 64) {
+      host_ring[(base + i) % IMP_RING] = improved_ring[(base + i) % IMP_RING];
+      improved_ring[(base + IMP_RING / 2 + i) % IMP_RING] = 0;
     }
+    if (lane == 0) ctl->base = base + adv_count;  // (every lane of the wave has read the old value above)
   };
+  uint32_t early = EARLY_UNCHECKED;
+  if (early_check) {  // (uniform reads: the early tail's launch, then that launch's flag and its least write)
+    const uint32_t k = ctl->early_sweep;
+    early = EARLY_ABSENT;
+    if (k != 0u && k < adv_count && improved_ring[k % IMP_RING] == FLAG_NARROW_CLEAN) {
+      const unsigned long long eb = ctl->early_best;
+      early = ctl->narrow_low[k % RING] > (uint32_t)(eb >> 32) ? EARLY_USED : EARLY_REFUTED;
+    }
+    if (early == EARLY_USED) {
+      if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+      if (adv_count) advance();
+      if (lane == 0) {
+        hout->pad = ctl->pad;  // (the walk's flags were clear; a relaxation may have raised the hop-count flag since)
+        hout->early = EARLY_USED;
+      }
+      host_stores_done();
+      if (lane == 0) __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return;
+    }
+  }
   unsigned long long best = KEY_INF;
   bool tie = false;
-  auto candidate = [&](uint32_t s, float f) {
-    const uint64_t k = key[s];
-    if (k == KEY_INF) return;
-    const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
-    if (!(tot < INF)) return;
-    merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
-  };
-  if (fin_list) {  // the handle's list of its final states {state, final weight}: the same candidates, found without the scan
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_fin; i += gridDim.x * blockDim.x) {
-      const uint2 e = fin_list[i];
-      candidate(e.x, __uint_as_float(e.y));
-    }
+  if (fin_list) {  // the handle's list of its final states: the same candidates, found without the scan
+    tail_search_list(key, fin_list, n_fin, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, best, tie);
   } else {
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
       const float f = finals[s];
-      if (f < INF) candidate(s, f);  // most states are not final: their key is never fetched
+      if (f < INF) tail_candidate(key[s], s, f, best, tie);  // most states are not final: their key is never fetched
     }
   }
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(best, d);
-    const bool ot = __shfl_xor((int)tie, d) != 0;
-    merge(best, tie, o, ot);
-  }
-  if (lane == 0) s_best[threadIdx.x >> 6] = best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
+  tail_wave_reduce(best, tie);
+  if (lane == 0) s_best[threadIdx.x >> 6] = tail_pack(best, tie);
   __syncthreads();
   if (threadIdx.x == 0) {
     best = KEY_INF;
     tie = false;
-    for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) {
-      const unsigned long long o = s_best[w];
-      merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
-    }
-    const unsigned long long mine = best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
+    for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) tail_merge_packed(best, tie, s_best[w]);
+    const unsigned long long mine = tail_pack(best, tie);
     if (gridDim.x == 1) {  // the only workgroup is the last one: nothing to hand over, nothing to draw
       s_best[0] = mine;
       s_last = 1u;
@@ -882,71 +1052,20 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   }
   __syncthreads();
   if (!s_last || threadIdx.x >= 64) return;
-  if (adv_count) {
-    // closes the sweep batch queued in front of this launch (what sssp_advance_kernel does: the flags of its sweeps go to
-    // pinned host memory, the slots half a ring ahead are recycled, the base moves on) — one launch and one flush of
-    // host-memory writes less at the end of a predicted solve.  By the wave that writes the ticket at the end: ONE
-    // system-scope fence orders all of it.
-    const uint32_t base = ctl->base;
-    for (uint32_t i = lane; i < adv_count; i += 64) {
-      host_ring[(base + i) % IMP_RING] = improved_ring[(base + i) % IMP_RING];
-      improved_ring[(base + IMP_RING / 2 + i) % IMP_RING] = 0;
-    }
-    if (lane == 0) ctl->base = base + adv_count;  // (every lane of the wave has read the old value above)
-  }
+  if (adv_count) advance();
   // the last workgroup's first wave: every other workgroup's result is in memory
   best = KEY_INF;
   tie = false;
-  for (uint32_t b = lane; b < gridDim.x; b += 64) {
-    const unsigned long long o = gridDim.x == 1 ? s_best[0] : __hip_atomic_load(&ctl->tail_best[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(best, d);
-    const bool ot = __shfl_xor((int)tie, d) != 0;
-    merge(best, tie, o, ot);
-  }
-  uint32_t pad = ctl->pad;
+  for (uint32_t b = lane; b < gridDim.x; b += 64)
+    tail_merge_packed(best, tie, gridDim.x == 1 ? s_best[0] : __hip_atomic_load(&ctl->tail_best[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  tail_wave_reduce(best, tie);
+  const uint32_t pad = ctl->pad;
   if (lane == 0) {
     ctl->tail_ticket = 0;  // the tail may run again on the same control block (a solve that outran its prediction)
     ctl->best = best;
+    hout->early = early;
   }
-  if (best == KEY_INF) {
-    if (lane == 0) {
-      ctl->has_path = 0;
-      ctl->hops = 0;
-      hout->has_path = 0u;
-      hout->hops = 0u;
-      hout->pad = pad;
-      hout->f_parent = 0u;
-      hout->final_weight = INF;
-      hout->total = INF;
-      hout->ties = 0u;
-      host_stores_done();
-      __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return;
-  }
-  const uint32_t fp = (uint32_t)best;
-  const float final_weight = finals[fp], total = key_f32((uint32_t)(best >> 32));
-  uint32_t k = 0, ties = tie ? 1u : 0u;
-  if ((uint32_t)key[fp] > out_cap) pad |= 8u;  // the host falls back to the parent pass
-  else k = sssp_walk_back(offsets, arcs, key, rev_off, rev_arc, fp, out, out_cap, pad, s_walk, ties);
-  if (lane == 0) {
-    ctl->has_path = 1;
-    ctl->f_parent = fp;
-    ctl->hops = (pad & 12u) ? (uint32_t)key[fp] : k;
-    ctl->final_weight = final_weight;
-    ctl->total = total;
-    // (the walk's own flags go to the host only: a tail that ran ahead of the last sweeps is run again on this block)
-    hout->has_path = 1u;
-    hout->hops = (pad & 12u) ? (uint32_t)key[fp] : k;
-    hout->pad = pad;
-    hout->f_parent = fp;
-    hout->final_weight = final_weight;
-    hout->total = total;
-    hout->ties = ties;
-  }
+  tail_walk_publish(best, tie, pad, finals, key, offsets, arcs, rev_off, rev_arc, out, out_cap, hout, ctl, s_walk);
   // (the walk's arcs were written by several lanes of this wave)
   host_stores_done();
   if (lane == 0) __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1170,6 +1289,7 @@ struct Knobs {
   bool split_tail = false;              // WFST_SSSP_SPLIT_TAIL (by presence)
   bool count_atomics = false;           // WFST_SSSP_COUNT_ATOMICS (by presence)
   int final_list = 1;                   // WFST_SSSP_FINAL_LIST
+  int early_tail = 1;                   // WFST_SSSP_EARLY_TAIL
 };
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
@@ -1207,6 +1327,7 @@ Knobs read_knobs() {
   k.split_tail = env.get("WFST_SSSP_SPLIT_TAIL") != nullptr;
   k.count_atomics = env.get("WFST_SSSP_COUNT_ATOMICS") != nullptr;
   if (const char* e = env.get("WFST_SSSP_FINAL_LIST")) k.final_list = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_EARLY_TAIL")) k.early_tail = std::atoi(e);
   return k;
 }
 
@@ -1238,6 +1359,10 @@ struct Solve {
   size_t mb_dyn = 0;         // dynamic LDS bytes of a mailbox launch
   bool force_big = false;    // tests: the many-blocks variant of the kernel on a small FST (WFST_SSSP_BIG=1)
   decltype(&sssp_mbox_kernel<false>) mbox_kernel = nullptr;  // the variant for this many blocks (bind_mailbox)
+  // the early tail (sssp_early_tail): the one-level launches get a workgroup more, which does the tail's work inside the
+  // NARROW launch that drains the search (set by shortest_path_n1_begin before the first batch is queued)
+  bool early_on = false;
+  EarlyTail early{};
   // resident launches (sssp_resident.h): the WIDE levels of the solve inside ONE launch, every workgroup on a CU of its own
   bool resident = false;
   uint32_t log = 12;         // log2 of the block size (13: every launch of the solve is a resident one)
@@ -1407,9 +1532,9 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
                                                               sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, sv.narrow_t,
                                                               sv.res_max_levels, sv.res_lps_umax);
     else
-      sv.mbox_kernel<<<sv.mv.nb, MB_THREADS, sv.mb_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n,
-                                                              sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile, hint,
-                                                              sv.narrow_t);
+      sv.mbox_kernel<<<sv.mv.nb + (sv.early_on && !profile ? 1u : 0u), MB_THREADS, sv.mb_dyn, st>>>(
+          f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n, sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile,
+          hint, sv.narrow_t, sv.early);
   } else {
     uint8_t* const cur = sv.fl[j & 1u];
     uint8_t* const next = sv.fl[(j & 1u) ^ 1u];
@@ -2175,6 +2300,7 @@ void final_list_build(wfst_ctx* ctx, const wfst_fst* f, DevicePool& owner_pool, 
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
   r.has_fin = false;
+  r.fin_nonneg = false;
   r.n_fin = 0;
   if (n < 8 || n >= 0xFFFFFFF0u) return;
   DBuf<uint32_t> flag(*ctx->pool, (size_t)n + 1), pos(*ctx->pool, (size_t)n + 1);
@@ -2188,6 +2314,17 @@ void final_list_build(wfst_ctx* ctx, const wfst_fst* f, DevicePool& owner_pool, 
     final_list_kernel<<<(n + 255) / 256, 256, 0, st>>>(f->dev.finals, n, pos.p, r.fin.p, n_fin);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st));  // flag / pos / scan_tmp are released here
+  }
+  // (once per handle: the early tail needs every final weight >= 0)
+  r.fin_nonneg = true;
+  if (n_fin) {
+    std::vector<uint2> h(n_fin);
+    HIP_CHECK(hipMemcpy(h.data(), r.fin.p, (size_t)n_fin * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (const uint2& e : h) {
+      float w;
+      std::memcpy(&w, &e.y, sizeof(w));
+      if (!(w >= 0.0f)) r.fin_nonneg = false;
+    }
   }
   r.n_fin = n_fin;
   r.has_fin = true;
@@ -2283,7 +2420,8 @@ void queue_tail(wfst_sp_job* j, const SweepBatch* adv = nullptr) {
     sssp_tail_kernel<<<blocks, 1024, 0, st>>>(
         f->dev.finals, sv.key.p, n, listed ? j->rev->fin.p : nullptr, listed ? j->rev->n_fin : 0u, sv.ctl.p, f->dev.offsets, f->dev.arcs,
         j->rev->off.p, j->rev->arc.p, j->h_path,
-        PATH_PINNED, j->h_tail, sv.improved.p, adv ? adv->count : 0u, adv ? j->drv.host_flags(*adv) : nullptr, j->done_ticket);
+        PATH_PINNED, j->h_tail, sv.improved.p, adv ? adv->count : 0u, adv ? j->drv.host_flags(*adv) : nullptr, j->done_ticket,
+        adv && sv.early_on ? 1u : 0u);
     j->fused_tail = true;
     return;
   }
@@ -2343,6 +2481,12 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   ctx->stats.sweeps = 0;
   j->drv.init(ctx, f, &j->sv);
   const bool fuse = j->drv.predicted && j->rev && !j->sv.kn.split_tail;
+  // the early tail: the fused tail over the handle's list of final states, no negative weight anywhere (arcs: mbox_eligible)
+  if (fuse && j->sv.mbox && j->sv.kn.early_tail != 0 && j->rev->has_fin && j->sv.kn.final_list != 0 && j->rev->fin_nonneg) {
+    j->sv.early_on = true;
+    j->sv.early = EarlyTail{j->rev->fin.p, f->dev.finals, f->dev.arcs, j->rev->off.p, j->rev->arc.p, j->h_path, j->h_tail,
+                            j->rev->n_fin, PATH_PINNED};
+  }
   j->drv.start(/*defer_advance=*/fuse);
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
     queue_tail(j.get(), &j->drv.cur);
@@ -2392,6 +2536,12 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
       ctx->stats.relax_ms = ms;
       ctx->stats.relax_launches = j->drv.first_count;
     }
+  }
+  if (sv.kn.early_tail >= 2) {  // tests: the early tail's result or an error that says why not
+    const uint32_t e = sv.early_on && j->fused_tail && !j->drv.extended ? j->h_tail->early : EARLY_ABSENT;
+    if (e != EARLY_USED)
+      throw Error(std::string("shortest_path: WFST_SSSP_EARLY_TAIL=2 and the early tail's result was ") +
+                  (!sv.early_on ? "not eligible" : e == EARLY_REFUTED ? "refuted" : "absent"));
   }
   const Ctl* hc = j->hc;
   const uint32_t r_pad = j->fused_tail ? j->h_tail->pad : hc->pad, r_has_path = j->fused_tail ? j->h_tail->has_path : hc->has_path;

@@ -193,9 +193,9 @@ __global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restri
   }
   for (uint32_t i = tid; i < IMP_RING; i += nt) improved[i] = 0;
   uint32_t* cw = (uint32_t*)ctl;
-  constexpr uint32_t W_TAU0 = offsetof(Ctl, tau0) / 4, W_BEST = offsetof(Ctl, best) / 4;
+  constexpr uint32_t W_TAU0 = offsetof(Ctl, tau0) / 4, W_BEST = offsetof(Ctl, best) / 4, W_LOW = offsetof(Ctl, narrow_low) / 4;
   for (uint32_t i = tid; i < (uint32_t)(sizeof(Ctl) / 4); i += nt)
-    cw[i] = i == W_TAU0 ? __float_as_uint(tau0) : (i == W_BEST || i == W_BEST + 1) ? 0xFFFFFFFFu : 0u;
+    cw[i] = i == W_TAU0 ? __float_as_uint(tau0) : (i == W_BEST || i == W_BEST + 1 || (i >= W_LOW && i < W_LOW + RING)) ? 0xFFFFFFFFu : 0u;
 }
 
 // minimum over the 64 lanes of a wave (result in every lane): DPP row shifts / broadcasts, no LDS crossbar trips
@@ -317,7 +317,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
                                             uint64_t* __restrict__ key, const MboxView& mb, Ctl* __restrict__ ctl,
                                             uint32_t* __restrict__ improved, uint32_t sweep, float tau, uint32_t far_total,
                                             uint32_t near_low, uint32_t profile, uint32_t wl_n, bool waits, uint32_t bfar,
-                                            uint4* wl, uint32_t* s_n /*[8]: list sizes [0..2] (level mod 3), found beyond the threshold [3], left waiting [4]*/,
+                                            uint4* wl, uint32_t* s_n /*[8]: list sizes [0..2] (level mod 3), found beyond the threshold [3], left waiting [4], least enc(d) written [5]*/,
                                             uint32_t par_out, const uint32_t* l_roff_out, uint32_t* l_cur, uint32_t* l_cap) {
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, MB_HOP_BITS = 32 - LOG, NW_SEG = MB_B;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, j = blockIdx.x, nb = mb.nb;
@@ -343,6 +343,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     s_n[2] = 0;
     s_n[3] = 0;
     s_n[4] = (waits || wl_n > NW_CAP) ? 1u : 0u;  // something is left waiting after this launch
+    s_n[5] = 0xFFFFFFFFu;
     if (wl_n) mb.wl_cnt[j] = 0;
   }
   if (wl_n == 0) {  // (uniform) nothing to follow; whoever waits in this block's masks waits for a WIDE sweep
@@ -356,6 +357,8 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
   // (the two lists alternate; their COUNTERS rotate through three words, so that the one a level will fill next can be zeroed a
   // level ahead and a level needs ONE barrier: a hop of the tail is ~2 us, two trips and this)
   uint32_t cur = 0, cnt_i = 0, prev_n = 0, prev2_n = 0, far_new = 0;
+  // the least enc(d) this thread has written into key[]: what the early tail's result is certified against (Ctl::narrow_low)
+  uint32_t low = 0xFFFFFFFFu;
   bool left_any = false;
   unsigned long long p_arcs = 0, p_states = 0;
   bool grew = false;
@@ -446,6 +449,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
         for (uint32_t u = 0; u < NW_UNROLL; ++u) {
           const bool won = v[u] && ck[u] < old[u];
           if (won) {
+            low = min(low, enc[u]);
             if (h1_[u] >> MB_HOP_BITS) ctl->pad = 1u;  // hop count beyond the message format: the host refuses the result
             bool listed = false;
             if (key_f32(enc[u]) <= tau) {
@@ -489,8 +493,15 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     const uint4* __restrict__ in = wl + cur * NW_CAP;
     for (uint32_t e = tid; e < left; e += MB_THREADS) mbox_make_wait<LOG>(mb, in[e].x, in[e].z, false);
     if (__any(left_any || left != 0u) && lane == 0) s_n[4] = 1u;
+    if (__any(low != 0xFFFFFFFFu)) {  // one LDS atomic per wave that lowered a key, one global atomic per workgroup
+      low = wave_min_u32(low);
+      if (lane == 0) atomicMin(&s_n[5], low);
+    }
     __syncthreads();
-    if (tid == 0) atomicMax(improved, s_n[4] ? FLAG_NARROW_LEFT : FLAG_NARROW_CLEAN);
+    if (tid == 0) {
+      atomicMax(improved, s_n[4] ? FLAG_NARROW_LEFT : FLAG_NARROW_CLEAN);
+      if (s_n[5] != 0xFFFFFFFFu) atomicMin(&ctl->narrow_low[sweep % RING], s_n[5]);
+    }
     if (head) {  // the messages of the head: counts of the regions, like a WIDE sweep's publish
       bool any = false;
       for (uint32_t d = tid; d < nb; d += MB_THREADS) {
@@ -536,7 +547,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
                                                                uint64_t* __restrict__ key, MboxView mb, uint32_t par_in, uint32_t n,
                                                                uint32_t* __restrict__ improved_ring, Ctl* __restrict__ ctl,
                                                                uint32_t sweep, float delta, uint32_t near_low, uint32_t profile,
-                                                               uint32_t hint, uint32_t narrow_t) {
+                                                               uint32_t hint, uint32_t narrow_t, EarlyTail et) {
   extern __shared__ __align__(16) unsigned char mb_dyn[];
   __shared__ unsigned long long lkey[MB_B];
   __shared__ uint32_t l_off[MB_B + 1];
@@ -553,6 +564,16 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
   // scalar-cache misses one after the other (~0.3 us each) in front of the prologue's loads.  One word of every line is
   // asked for here, together; the later fetches hit.
   asm volatile("" ::"s"(offsets), "s"(mb.cnt[1]), "s"(ctl), "s"(narrow_t));
+  // The early tail: a launch of nb + 1 workgroups has one that owns no block.  When this launch is a NARROW one behind a
+  // hand-over it does the tail's search and walk while the others drain the search (sssp_early_tail; its LDS is lkey's).
+  if (blockIdx.x == mb.nb) {
+    if (sweep == 0) return;
+    const uint32_t prev_flag = improved_ring[(sweep - 1u) % IMP_RING];  // (asked for with the schedule words: one trip)
+    const SchedRaw raw = mbox_sched_load(ctl, sweep);
+    const Sched sc = mbox_sched_eval(ctl, raw, sweep, delta, near_low, narrow_t);
+    if (sc.mode == MODE_NARROW) sssp_early_tail(et, offsets, key, ctl, prev_flag, sweep, lkey);
+    return;
+  }
   // `sweep` is the absolute sweep index: the host knows it (plain launches), which saves the trip to ctl->base
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t j = blockIdx.x, nb = mb.nb, stg = mb.stg;
@@ -666,6 +687,9 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
         ctl->mode[sweep % RING] = mode;
       }
       if (tid < NEAR_SHARDS) ctl->nf[(sweep + 1) % NEAR_RING][tid * NF_STRIDE] = 0;  // recycle
+      // (a slot that is not recycled — a resident launch in between — only holds a value that is too low: the early result
+      // is then refuted, never wrongly certified)
+      if (tid == NEAR_SHARDS) ctl->narrow_low[(sweep + 1) % RING] = 0xFFFFFFFFu;
     }
   }
   {
