@@ -277,6 +277,40 @@ typedef struct {
 } wfst_minimize_config;
 wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out);
 
+/* ---- minimize_with_config of n acceptors in one call: outs[i] is a NEW handle, bit-identical (offsets, arcs with their
+ *      weights' bit patterns, finals, start state, property word) to what wfst_minimize(ctx, fsts[i], cfg, ..) returns.
+ *      cfg is shared by all items, NULL = the default as above.  The same handle may appear more than once in fsts.
+ *      n == 0: OK.  The inputs are left exactly as they are, their cached derived data and property words included.
+ *      One workgroup per item and ONE launch for the whole list: the workgroup runs every stage of the single call (facts
+ *      of the content, acyclicity and reverse distances by peeling sinks, push_weights(ToInitial), quantize + encode,
+ *      connect, the per-state sort, heights fused with the refinement, survivors, emit) on its item inside the item's
+ *      slice of one slab.  The slices are sized on the host from n_states and n_arcs alone (minimization never grows its
+ *      input: the encoded machine has at most n_states + 1 states and n_arcs + n_states arcs), so nothing is run twice.
+ *      Launches and host synchronisations of a call depend neither on n nor on any item's depth: one launch of the batch
+ *      kernel, one read-back of the items' control blocks, and one adoption of all results out of the slab (one
+ *      allocation, a gather and a derive launch with a block per result, one synchronisation).
+ *      A slice takes about 230 KB for an item of 500 states and 1500 arcs and 2.5 MB at the rule's limit below; the slices
+ *      of one call may take 8 GiB together (some 35 000 lattices of that size, 3 000 items at the limit): a list that
+ *      needs more is KO before anything is launched ("split the list").
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when item i has at most 4096 states and at most
+ *      16384 arcs: the batch kernel minimized it (an item without states never occupies a workgroup and counts as such;
+ *      so does an item without a start state that meets the rule).  in_kernel[i] == 0: the item went through
+ *      wfst_minimize unchanged.
+ *      One exception to the rule: an item whose stored word says INITIAL_CYCLIC is handed to wfst_minimize as well and
+ *      has in_kernel[i] == 0 whatever its size.  Such an input is cyclic, which is KO, or its word contradicts ACYCLIC,
+ *      and then reweight's start-state step adds a state, which a slice has no room for.
+ *      KO — every argument is checked before anything is launched: NULL pointers, NULL list entries ("item <i>: null FST
+ *      in batch"), a handle of another device or context, delta not finite or <= 0 — and whenever wfst_minimize would be
+ *      KO for an item, whether the stored word says so or the kernel finds it: the message is the single call's for the
+ *      LOWEST failing index, prefixed by "item <i>: "; within an item the checks come in the single call's order.  On
+ *      any KO every outs[i] is NULL, nothing is leaked and the context works afterwards. ---- */
+wfst_status wfst_minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_minimize_config* cfg,
+                                wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_minimize_batch call of ctx: launches of the batch kernel (0 or 1), items it minimized (in_kernel == 1), items
+ *      that went through the single-FST path.  All 0 after a KO before any launch. */
+wfst_status wfst_ctx_get_minimize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                              uint64_t* items_single);
+
 /* ---- tr_sum (rustfst/src/algorithms/tr_sum.rs:7-22, sum_trs_unchecked: fst_impls/vector_fst/mutable_fst.rs:380-405) and
  *      tr_unique (tr_unique.rs:8-51, unique_trs_unchecked: mutable_fst.rs:358-377).  Per state a STABLE sort by tr_compare:
  *      (ilabel, olabel, nextstate), unsigned, the weight not in the key.  tr_sum: of a run of equal keys the first arc

@@ -19,6 +19,7 @@
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
 //   determinize_with_distance(&fst, &in_dist, delta)             determinize_with_distance(fst, in_dist, delta)   determinize_static.rs:24-39
 //   (many acceptors in one call)                                 determinize_batch / determinize_with_distance_batch
+//                                                                minimize_batch
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
@@ -333,6 +334,25 @@ inline void minimize_with_config(VectorFst& fst, const MinimizeConfig& config) {
   fst = detail::download(c);
 }
 inline void minimize(VectorFst& fst) { minimize_with_config(fst, MinimizeConfig{}); }
+// minimize_with_config of many acceptors in one call (wfst_minimize_batch): one workgroup per FST, one launch for all; the
+// minimized FSTs (the arguments are left as they are)
+inline std::vector<VectorFst> minimize_batch(const std::vector<VectorFst>& fsts, const MinimizeConfig& config = MinimizeConfig{}) {
+  std::vector<detail::DeviceFst> in(fsts.size()), out(fsts.size());
+  std::vector<const wfst_fst*> hs(fsts.size());
+  std::vector<wfst_fst*> os(fsts.size(), nullptr);
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    detail::upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+  }
+  const wfst_minimize_config cfg{config.delta, config.allow_nondet ? 1u : 0u};
+  check(wfst_minimize_batch(Context::current().get(), hs.data(), hs.size(), &cfg, os.data(), nullptr));
+  std::vector<VectorFst> res;
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    out[i].h = os[i];
+    res.push_back(detail::download(out[i]));
+  }
+  return res;
+}
 
 // tr_sum (tr_sum.rs:7-22), tr_unique (tr_unique.rs:38-51) and optimize (optimize.rs:11-128; acyclic inputs, anything else
 // throws): in place, like the reference

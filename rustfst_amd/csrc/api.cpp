@@ -576,6 +576,30 @@ wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimiz
     *out = minimize_fst(ctx, fst, c.delta, c.allow_nondet != 0);
   });
 }
+// minimize_with_config of n acceptors (one workgroup each, one launch); every argument is checked before anything is launched
+wfst_status wfst_minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_minimize_config* cfg,
+                                wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    if (outs)
+      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    const wfst_minimize_config c = cfg ? *cfg : wfst_minimize_config{1e-6f, 0u};
+    if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("minimize: delta must be finite and > 0");
+    if (ctx) ctx->min_batch_launches = ctx->min_batch_in_kernel = ctx->min_batch_single = 0;
+    if (n == 0) return;
+    check_batch_args(ctx, fsts, n, outs);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    minimize_batch(ctx, fsts, n, c.delta, c.allow_nondet != 0, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_minimize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                              uint64_t* items_single) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (launches) *launches = ctx->min_batch_launches;
+    if (items_in_kernel) *items_in_kernel = ctx->min_batch_in_kernel;
+    if (items_single) *items_single = ctx->min_batch_single;
+  });
+}
 
 // tr_sum (tr_sum.rs:7-22) / tr_unique (tr_unique.rs:38-51)
 wfst_status wfst_tr_sum(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {

@@ -199,6 +199,8 @@ struct wfst_ctx {
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
   // the last wfst_determinize_batch / wfst_determinize_with_distance_batch call (wfst_ctx_get_determinize_batch_stats)
   uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
+  // the last wfst_minimize_batch call (wfst_ctx_get_minimize_batch_stats)
+  uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
   int n_cus = 256;
 };
 
@@ -486,6 +488,9 @@ void rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t*
 wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
 // minimize.hip: minimize_with_config of a deterministic acyclic acceptor (a NEW handle)
 wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow_nondet);
+// ... of n acceptors in one call, one workgroup each and one launch for all (new handles; on a throw every outs[i] is null)
+void minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, bool allow_nondet, wfst_fst** outs,
+                    uint8_t* in_kernel);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,
                        uint64_t out_props, uint64_t est_s);
 }  // namespace wfst

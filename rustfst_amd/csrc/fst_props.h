@@ -281,6 +281,15 @@ constexpr uint64_t WEIGHT_INVARIANT = ACCEPTOR | NOT_ACCEPTOR | I_DETERMINISTIC 
                                       ACCESSIBLE | NOT_ACCESSIBLE | COACCESSIBLE | NOT_COACCESSIBLE | STRING | NOT_STRING;
 // reweight_properties (mutate_properties.rs:640-644), applied with the all_properties() mask (reweight.rs:148-151)
 inline uint64_t reweight(uint64_t in) { return in & WEIGHT_INVARIANT & ~COACCESSIBLE; }
+// what reweight's passes over the final weights and the arcs leave in the word (reweight.rs:46-49, 84, 101): facts & 2 = some
+// final weight went through set_final, facts & 1 = some arc through set_weight_unchecked (their WEIGHTED / UNWEIGHTED
+// updates are dropped by reweight() above, which ends the call)
+inline uint64_t reweight_marks(uint64_t in, uint32_t facts) {
+  uint64_t p = in;
+  if (facts & 2u) p = set_final(p, nullptr, nullptr);
+  if (facts & 1u) p = p & ARC_RELEVANT;
+  return p;
+}
 // the trinary pairs (fst_properties/utils.rs:4-9 known_properties): a pair is known when either of its bits is set
 inline bool knows(uint64_t p, uint64_t pos_bit) { return (p & (pos_bit | (pos_bit << 1))) != 0; }
 // compute_and_update_properties(mask) with a mask of DFS bits only (fst_traits/mutable_fst.rs:435-441,

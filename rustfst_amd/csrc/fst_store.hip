@@ -94,11 +94,9 @@ __global__ void any_ieps_kernel(const uint4* __restrict__ srec, uint32_t n_state
 
 // one thread per state (of the concatenation): count olabel == 0 arcs; validate offsets.
 // seg_* describe the FSTs packed in the arena so that nextstate bounds are per FST.
-__global__ void derive_noeps_kernel(const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ arcs,
-                                    const float* __restrict__ finals, uint32_t* __restrict__ noeps,
-                                    uint4* __restrict__ srec, uint32_t n_states, uint32_t* __restrict__ err) {
-  uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_states) return;
+__device__ inline void derive_noeps_state(const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ arcs,
+                                          const float* __restrict__ finals, uint32_t* __restrict__ noeps,
+                                          uint4* __restrict__ srec, uint32_t s, uint32_t* __restrict__ err) {
   const uint32_t b = offsets[s], e = offsets[s + 1];
   if (e < b) {
     atomicOr(err, 2u);
@@ -115,6 +113,12 @@ __global__ void derive_noeps_kernel(const uint32_t* __restrict__ offsets, const 
   const uint32_t facts = (c == 0 ? SREC_NO_OEPS : 0u) | (c == e - b ? SREC_ALL_OEPS : 0u) | (ci == 0 ? SREC_NO_IEPS : 0u) |
                          (ci == e - b ? SREC_ALL_IEPS : 0u);
   srec[s] = make_uint4(b, e - b, __float_as_uint(finals[s]), facts);
+}
+__global__ void derive_noeps_kernel(const uint32_t* __restrict__ offsets, const wfst_tr* __restrict__ arcs,
+                                    const float* __restrict__ finals, uint32_t* __restrict__ noeps,
+                                    uint4* __restrict__ srec, uint32_t n_states, uint32_t* __restrict__ err) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n_states) derive_noeps_state(offsets, arcs, finals, noeps, srec, s, err);
 }
 
 struct Layout {
@@ -352,6 +356,9 @@ struct AdoptJob {
   wfst_tr* d_arcs;
   float* d_fin;
   uint32_t n_states, n_arcs;
+  uint2* d_wn;  // the derived arrays of the result
+  uint32_t* d_noeps;
+  uint4* d_srec;
 };
 // block k copies result k (offsets, finals, arcs) out of its problem arena into the batch's shared allocation
 __global__ void __launch_bounds__(256) adopt_gather_kernel(const AdoptJob* __restrict__ jobs) {
@@ -362,11 +369,57 @@ __global__ void __launch_bounds__(256) adopt_gather_kernel(const AdoptJob* __res
   uint4* dst = reinterpret_cast<uint4*>(j.d_arcs);
   for (uint32_t i = threadIdx.x; i < j.n_arcs; i += 256) dst[i] = src[i];
 }
+// block k derives what derive_wn_kernel and derive_noeps_kernel derive, for result k as the gather left it: the packed
+// {weight, nextstate} array with the nextstate check and the weight statistics (ws[k]: this block alone writes it), then
+// the epsilon counts and state records
+__global__ void __launch_bounds__(256) adopt_derive_kernel(const AdoptJob* __restrict__ jobs, uint32_t* __restrict__ err,
+                                                           WeightStats* __restrict__ ws) {
+  const AdoptJob j = jobs[blockIdx.x];
+  bool bad = false, neg = false;
+  double sum = 0.0;
+  unsigned long long cnt = 0;
+  for (uint32_t i = threadIdx.x; i < j.n_arcs; i += 256) {
+    const uint4 a = reinterpret_cast<const uint4*>(j.d_arcs)[i];
+    j.d_wn[i] = make_uint2(a.z, a.w);
+    bad |= a.w >= j.n_states;
+    const float w = __uint_as_float(a.z);
+    if (w < INF && w > -INF) {
+      sum += (double)w;
+      cnt++;
+      neg |= w < 0.0f;
+    }
+  }
+  if (bad) atomicOr(err, 1u);
+  __shared__ double s_sum[4];
+  __shared__ unsigned long long s_cnt[4];
+  __shared__ uint32_t s_neg;
+  if (threadIdx.x == 0) s_neg = 0u;
+  for (int d = 32; d >= 1; d >>= 1) {
+    sum += __shfl_xor(sum, d);
+    cnt += __shfl_xor(cnt, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_sum[threadIdx.x >> 6] = sum;
+    s_cnt[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (neg) s_neg = 1u;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    WeightStats r{0.0, 0ull, s_neg, 0u};
+    for (unsigned w = 0; w < 4; ++w) {
+      r.sum += s_sum[w];
+      r.count += s_cnt[w];
+    }
+    ws[blockIdx.x] = r;
+  }
+  for (uint32_t s = threadIdx.x; s < j.n_states; s += 256) derive_noeps_state(j.d_off, j.d_arcs, j.d_fin, j.d_noeps, j.d_srec, s, err);
+}
 }  // namespace
 
-// adopt_device for the m results of one batch: ONE allocation, one gather launch, the derive kernels queued without a
-// host round trip in between, ONE synchronisation (per result adopt_device costs ~40 us: three copy commands, two small
-// kernels and a read-back of the weight statistics each).
+// adopt_device for the m results of one batch: ONE allocation, one gather launch and one derive launch (a block per result
+// each) whatever m is, ONE synchronisation (per result adopt_device costs ~40 us: three copy commands, two small kernels
+// and a read-back of the weight statistics each).
 void adopt_device_many(wfst_ctx* ctx, size_t m, const AdoptDesc* descs, wfst_fst** outs) {
   if (m == 0) return;
   HIP_CHECK(hipSetDevice(ctx->device));
@@ -388,7 +441,8 @@ void adopt_device_many(wfst_ctx* ctx, size_t m, const AdoptDesc* descs, wfst_fst
   for (size_t i = 0; i < m; ++i)
     jobs[i] = AdoptJob{descs[i].off, descs[i].arcs, descs[i].fin, const_cast<uint32_t*>(all.offsets) + state_base[i] + i,
                        const_cast<wfst_tr*>(all.arcs) + arc_base[i], const_cast<float*>(all.finals) + state_base[i],
-                       descs[i].n_states, (uint32_t)descs[i].n_arcs};
+                       descs[i].n_states, (uint32_t)descs[i].n_arcs, const_cast<uint2*>(all.wn) + arc_base[i],
+                       const_cast<uint32_t*>(all.noeps) + state_base[i], const_cast<uint4*>(all.srec) + state_base[i]};
   DBuf<AdoptJob> d_jobs(*ctx->pool, m);
   DBuf<uint32_t> err(*ctx->pool, 1);
   DBuf<WeightStats> ws(*ctx->pool, m);
@@ -396,18 +450,7 @@ void adopt_device_many(wfst_ctx* ctx, size_t m, const AdoptDesc* descs, wfst_fst
   HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
   HIP_CHECK(hipMemsetAsync(ws.p, 0, m * sizeof(WeightStats), st));
   adopt_gather_kernel<<<(uint32_t)m, 256, 0, st>>>(d_jobs.p);
-  for (size_t i = 0; i < m; ++i) {
-    const uint32_t ns = descs[i].n_states;
-    const uint64_t na = descs[i].n_arcs;
-    if (na)
-      derive_wn_kernel<<<(int)std::min<uint64_t>((na + 255) / 256, 64), 256, 0, st>>>(all.arcs + arc_base[i],
-                                                                                         const_cast<uint2*>(all.wn) + arc_base[i], na, ns,
-                                                                                         err.p, ws.p + i);
-    if (ns)
-      derive_noeps_kernel<<<(ns + 255) / 256, 256, 0, st>>>(all.offsets + state_base[i] + i, all.arcs + arc_base[i],
-                                                            all.finals + state_base[i], const_cast<uint32_t*>(all.noeps) + state_base[i],
-                                                            const_cast<uint4*>(all.srec) + state_base[i], ns, err.p);
-  }
+  adopt_derive_kernel<<<(uint32_t)m, 256, 0, st>>>(d_jobs.p, err.p, ws.p);
   HIP_CHECK(hipGetLastError());
   std::vector<WeightStats> hws(m);
   uint32_t herr = 0;

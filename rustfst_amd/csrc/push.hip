@@ -334,8 +334,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
   uint64_t p = f->props;
   // set_final (reweight.rs:46-49, 101) and set_weight_unchecked (:84): masks (their WEIGHTED / UNWEIGHTED updates are
   // dropped by reweight_properties below)
-  if (rw.facts & 2u) p = props::set_final(p, nullptr, nullptr);
-  if (rw.facts & 1u) p = p & props::ARC_RELEVANT;
+  p = props::reweight_marks(p, rw.facts);
   int64_t start = f->start;
   uint32_t n_out = n;
   uint64_t e_out = E;

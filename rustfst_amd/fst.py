@@ -712,6 +712,34 @@ def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
 
 
+def minimize_batch(fsts: Sequence[DeviceFst], config: Optional["MinimizeConfig"] = None, ctx: Optional[Context] = None,
+                   return_in_kernel: bool = False):
+    """[f.minimize(config) for f in fsts] as ONE call (wfst_minimize_batch): one workgroup per acceptor and one launch
+    of the batch kernel for the whole list, whatever its length and the items' depths — the step after determinize_batch for the many small
+    lattices of a decoding batch.  return_in_kernel: also the uint8 array that says which items the batch kernel
+    minimized (0: more than 4096 states or 16384 arcs sent the item through the single-FST path).  Any item that
+    f.minimize would refuse raises WfstError with "item <i>: " in front of that call's message."""
+    n = len(fsts)
+    if n == 0:
+        return ([], np.zeros(0, np.uint8)) if return_in_kernel else []
+    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
+    outs = (C.c_void_p * n)()
+    flags = np.zeros(n, np.uint8)
+    check(_lib.lib().wfst_minimize_batch(ctx._h, _handles(fsts), n, config._c() if config is not None else None, outs,
+                                         flags.ctypes.data), "wfst_minimize_batch")
+    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
+    return (res, flags) if return_in_kernel else res
+
+
+def minimize_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last minimize_batch call of ctx (wfst_ctx_get_minimize_batch_stats)."""
+    ctx = ctx or default_context()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(_lib.lib().wfst_ctx_get_minimize_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
+          "wfst_ctx_get_minimize_batch_stats")
+    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+
+
 def _take_floats(ptr, count):
     out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(count,)).copy() if count else np.zeros(0, np.float32)
     _lib.lib().wfst_bytes_destroy(ptr)
