@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -387,6 +387,12 @@ wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t 
  *      thresholds): every epsilon:epsilon arc removed, the weighted relation kept, the result connected.  The reference
  *      works in place; here a NEW handle is returned.  An FST without a start state is returned unchanged. ---- */
 wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+/* the last wfst_rm_epsilon call of ctx (reset when the call begins; all 0 for an FST without a start state): batches of
+ *      mutually independent states that were scheduled, launches of the one-thread-per-state and of the one-wave-per-state
+ *      rewrite kernel, states that finished in either, and the largest closure capacity any launch was given.  Read-only
+ *      diagnostics of how the scratch sizes were climbed; any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
+                                          uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap);
 
 /* ---- project: fst_project (rustfst-ffi/src/algorithms/project.rs:45-70) = rustfst::algorithms::project
  *      (rustfst/src/algorithms/projection.rs:65-95), in place on the device-resident arcs.  project_output == 0:

@@ -736,6 +736,19 @@ wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) 
   });
 }
 
+wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
+                                          uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (batches) *batches = ctx->rm_eps.batches;
+    if (thread_launches) *thread_launches = ctx->rm_eps.thread_launches;
+    if (wave_launches) *wave_launches = ctx->rm_eps.wave_launches;
+    if (states_thread) *states_thread = ctx->rm_eps.states_thread;
+    if (states_wave) *states_wave = ctx->rm_eps.states_wave;
+    if (max_closure_cap) *max_closure_cap = ctx->rm_eps.max_closure_cap;
+  });
+}
+
 wfst_status wfst_connect(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

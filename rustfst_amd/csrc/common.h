@@ -201,6 +201,10 @@ struct wfst_ctx {
   uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
   // the last wfst_minimize_batch call (wfst_ctx_get_minimize_batch_stats)
   uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
+  // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
+  struct RmEpsilonStats {
+    uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
+  } rm_eps;
   int n_cus = 256;
 };
 

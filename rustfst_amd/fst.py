@@ -712,6 +712,15 @@ def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
 
 
+def rm_epsilon_stats(ctx: Optional[Context] = None) -> dict:
+    """The last rm_epsilon call of ctx (wfst_ctx_get_rm_epsilon_stats)."""
+    ctx = ctx or default_context()
+    names = ("batches", "thread_launches", "wave_launches", "states_thread", "states_wave", "max_closure_cap")
+    vals = [C.c_uint64() for _ in names]
+    check(_lib.lib().wfst_ctx_get_rm_epsilon_stats(ctx._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rm_epsilon_stats")
+    return {k: v.value for k, v in zip(names, vals)}
+
+
 def minimize_batch(fsts: Sequence[DeviceFst], config: Optional["MinimizeConfig"] = None, ctx: Optional[Context] = None,
                    return_in_kernel: bool = False):
     """[f.minimize(config) for f in fsts] as ONE call (wfst_minimize_batch): one workgroup per acceptor and one launch
