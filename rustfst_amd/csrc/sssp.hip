@@ -93,7 +93,10 @@ struct Ctl {
   // and the launch it ran in (0 = none: launch 0 never runs it).  sssp_tail_kernel decides whether that result stands.
   uint32_t narrow_low[RING];
   unsigned long long early_best;
-  uint32_t early_sweep, early_pad;
+  uint32_t early_sweep;
+  // the resident launch that left every block's best final state in MboxView::blk_best on its COLLECT exit (0 = none: a
+  // resident launch that hands over is never launch 0); the early tail of launch blk_best_sweep + 1 merges those words
+  uint32_t blk_best_sweep;
 };
 constexpr uint32_t TAIL_BLOCKS = 128;
 constexpr uint32_t TAIL_LIST_BLOCKS = 16;  // ... over the handle's list of final states (RevCsr::fin), 4096 entries each
@@ -107,8 +110,10 @@ struct TailOut {
   uint32_t ties;  // states of the returned path with more than one optimal predecessor (the start state: with any), + 1 when
                   // several final states attain the optimum: 0 = the optimum is unique (wfst_stats.tied_choices)
   uint32_t early;  // EARLY_*: what sssp_tail_kernel made of the early tail's result
+  uint32_t early_src;  // EARLY_SRC_*: where the early tail that published last took the best final state from
 };
 constexpr uint32_t EARLY_UNCHECKED = 0, EARLY_USED = 1, EARLY_ABSENT = 2, EARLY_REFUTED = 3;
+constexpr uint32_t EARLY_SRC_LIST = 1, EARLY_SRC_BLOCKS = 2;
 // what the extra workgroup of a mailbox launch needs for the tail's work (sssp_early_tail); by value, last kernel argument
 struct EarlyTail {
   const uint2* fin_list;  // RevCsr::fin
@@ -119,9 +124,11 @@ struct EarlyTail {
   wfst_tr* out;   // pinned host memory
   TailOut* hout;  // pinned host memory
   uint32_t n_fin, out_cap;
+  uint32_t blk_best_on;  // the resident launches of this solve leave the blocks' best final states (mbox_blk_best)
 };
 __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint32_t* __restrict__ offsets, const uint64_t* __restrict__ key,
-                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds);
+                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds, bool merged,
+                                unsigned long long best, bool tie);
 
 // threshold of sweep k from what sweep k-1 left in the ring (every thread computes the same value)
 // Called by one full wave (all 64 lanes): lanes 0..15 fetch the shards of sweep-1's counter, lanes 16..31 those of
@@ -159,6 +166,40 @@ __device__ __forceinline__ float sweep_tau(const Ctl* ctl, uint32_t sweep, float
   // at most everything that waits beyond it
   if (frontier_est) *frontier_est = cnt + (t != prev ? far : 0u);
   return t;
+}
+
+// ---- what sssp_tail_kernel, the early tail (sssp_early_tail) and the resident launch's epilogue share: the arg-min over final states.
+// (enc(total) << 32 | final state) and whether ANOTHER final state attains the same total: merged pairwise; where the pair
+// travels as one word the flag sits in bit 31 of the state word (state ids have 31 bits)
+constexpr unsigned long long TIE_BIT = 1ull << 31;
+__device__ __forceinline__ void tail_merge(unsigned long long& best, bool& tie, unsigned long long o, bool o_tie) {
+  if (o == KEY_INF) return;
+  if ((o >> 32) == (best >> 32)) {
+    tie = true;
+    best = o < best ? o : best;
+  } else if (o < best) {
+    best = o;
+    tie = o_tie;
+  }
+}
+__device__ __forceinline__ unsigned long long tail_pack(unsigned long long best, bool tie) {
+  return best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
+}
+__device__ __forceinline__ void tail_merge_packed(unsigned long long& best, bool& tie, unsigned long long o) {
+  tail_merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
+}
+__device__ __forceinline__ void tail_wave_reduce(unsigned long long& best, bool& tie) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(best, d);
+    const bool ot = __shfl_xor((int)tie, d) != 0;
+    tail_merge(best, tie, o, ot);
+  }
+}
+__device__ __forceinline__ void tail_candidate(uint64_t k /* key[s] */, uint32_t s, float f, unsigned long long& best, bool& tie) {
+  if (k == KEY_INF) return;
+  const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
+  if (!(tot < INF)) return;
+  tail_merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
 }
 
 #include "sssp_mailbox.h"
@@ -825,39 +866,7 @@ __global__ void __launch_bounds__(64) sssp_backtrace_rev_kernel(const uint32_t* 
   }
 }
 
-// ---- what sssp_tail_kernel and the early tail (sssp_early_tail) share: the arg-min over the final states and the walk.
-// (enc(total) << 32 | final state) and whether ANOTHER final state attains the same total: merged pairwise; where the pair
-// travels as one word the flag sits in bit 31 of the state word (state ids have 31 bits)
-constexpr unsigned long long TIE_BIT = 1ull << 31;
-__device__ __forceinline__ void tail_merge(unsigned long long& best, bool& tie, unsigned long long o, bool o_tie) {
-  if (o == KEY_INF) return;
-  if ((o >> 32) == (best >> 32)) {
-    tie = true;
-    best = o < best ? o : best;
-  } else if (o < best) {
-    best = o;
-    tie = o_tie;
-  }
-}
-__device__ __forceinline__ unsigned long long tail_pack(unsigned long long best, bool tie) {
-  return best == KEY_INF ? best : (best | (tie ? TIE_BIT : 0ull));
-}
-__device__ __forceinline__ void tail_merge_packed(unsigned long long& best, bool& tie, unsigned long long o) {
-  tail_merge(best, tie, o == KEY_INF ? o : (o & ~TIE_BIT), o != KEY_INF && (o & TIE_BIT) != 0ull);
-}
-__device__ __forceinline__ void tail_wave_reduce(unsigned long long& best, bool& tie) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(best, d);
-    const bool ot = __shfl_xor((int)tie, d) != 0;
-    tail_merge(best, tie, o, ot);
-  }
-}
-__device__ __forceinline__ void tail_candidate(uint64_t k /* key[s] */, uint32_t s, float f, unsigned long long& best, bool& tie) {
-  if (k == KEY_INF) return;
-  const float tot = (key_f32((uint32_t)(k >> 32)) + f) + 0.0f;  // d[s] (x) rho(s), shortest_path.rs:214-220
-  if (!(tot < INF)) return;
-  tail_merge(best, tie, ((unsigned long long)f32_key(tot) << 32) | s, false);
-}
+// ---- the search over the handle's list and the walk (the merge helpers are in front of sssp_mailbox.h)
 // the handle's list of its final states {state, final weight}: entries first, first + stride, ... — four in flight (two
 // dependent trips per four entries; the order of the merges does not matter).  (Sixteen in flight in the early tail's ONE
 // workgroup were no faster: 14 000 gathered keys are ~6 us of one compute unit's L1 however they are asked for.)
@@ -929,20 +938,23 @@ __device__ __forceinline__ uint32_t tail_walk_publish(unsigned long long best, b
 }
 
 // The early tail: the extra workgroup of a NARROW launch behind a hand-over (sssp_mbox_kernel, blockIdx.x == nb) does the
-// tail's search and walk on keys that other workgroups of the SAME launch are still lowering, with plain loads, and leaves
+// tail's search (or, behind a resident launch, the merge of the blocks' best final states that launch left: `merged`) and the
+// walk on keys that other workgroups of the SAME launch are still lowering, with plain loads, and leaves
 // {launch, best | TIE_BIT} in the control block; sssp_tail_kernel certifies the result or computes it again.  `lds`: 16 words
 // for the waves' results, WALK_LDS entries of the walk behind them.  Nothing the ordinary tail uses is touched.
 __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint32_t* __restrict__ offsets, const uint64_t* __restrict__ key,
-                                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds) {
+                                                Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds,
+                                                bool merged, unsigned long long best, bool tie) {
   // (a launch queued behind the solve's last one: the fixed point was reached, or the solve gave up — as sssp_mbox_resident_kernel)
   const uint32_t pf = prev_flag;
   if (pf == 0u || pf == FLAG_NARROW_CLEAN || pf == FLAG_RES_ABORT) return;
   unsigned long long* const s_best = lds;
   uint2* const s_walk = (uint2*)(lds + 16);
   const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
-  unsigned long long best = KEY_INF;
-  bool tie = false;
-  tail_search_list(key, et.fin_list, et.n_fin, threadIdx.x, blockDim.x, best, tie);
+  // `merged` (uniform): the resident launch in front of this one left every block's best final state (MboxView::blk_best) and
+  // best / tie hold this thread's share of those words — the keys as they stood before this launch wrote anything.  Otherwise
+  // the list is searched, on keys this launch is lowering.  Either way sssp_tail_kernel's certificate decides.
+  if (!merged) tail_search_list(key, et.fin_list, et.n_fin, threadIdx.x, blockDim.x, best, tie);
   tail_wave_reduce(best, tie);
   if (lane == 0) s_best[threadIdx.x >> 6] = tail_pack(best, tie);
   __syncthreads();
@@ -953,6 +965,7 @@ __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint3
   tail_wave_reduce(best, tie);
   const uint32_t pad = tail_walk_publish(best, tie, 0u, et.finals, key, offsets, et.arcs, et.rev_off, et.rev_arc, et.out, et.out_cap,
                                          et.hout, nullptr, s_walk);
+  if (lane == 0) et.hout->early_src = merged ? EARLY_SRC_BLOCKS : EARLY_SRC_LIST;
   host_stores_done();
   // (a walk that did not end at the start state, or a path beyond the pinned buffer: the ordinary tail's business)
   if (lane == 0 && !(pad & 12u)) {
@@ -978,6 +991,10 @@ __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint3
 //   * a final state whose key changed has a total >= its key, above B before and after: neither the optimum nor a tie;
 //   * a write AT B could make a tie (a second final state, a second tight in-arc), hence the strict inequality.
 // Every key at or below B is one no writer of launch k touched: the early tail read what this kernel would read.
+// Where the early tail took B from the blocks' best final states (mbox_blk_best: left by the resident launch k - 1 on its
+// hand-over) instead of searching the list, those words are the keys as they stood BEFORE launch k wrote anything — the
+// limiting case of "read while launch k was writing" — and the same two conditions cover it: a final state whose key launch k
+// lowered ended above B from a value higher still, so it was neither the optimum nor a tie in the words, and is neither now.
 __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict__ finals, const uint64_t* __restrict__ key,
                                                          uint32_t n, const uint2* __restrict__ fin_list, uint32_t n_fin,
                                                          Ctl* __restrict__ ctl,
@@ -1290,6 +1307,7 @@ struct Knobs {
   bool count_atomics = false;           // WFST_SSSP_COUNT_ATOMICS (by presence)
   int final_list = 1;                   // WFST_SSSP_FINAL_LIST
   int early_tail = 1;                   // WFST_SSSP_EARLY_TAIL
+  int early_best = 1;                   // WFST_SSSP_EARLY_BEST
 };
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
@@ -1328,6 +1346,7 @@ Knobs read_knobs() {
   k.count_atomics = env.get("WFST_SSSP_COUNT_ATOMICS") != nullptr;
   if (const char* e = env.get("WFST_SSSP_FINAL_LIST")) k.final_list = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_EARLY_TAIL")) k.early_tail = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_EARLY_BEST")) k.early_best = std::atoi(e);
   return k;
 }
 
@@ -1350,7 +1369,7 @@ struct Solve {
   bool mbox = false;
   std::shared_ptr<MboxPlan> plan;
   DBuf<uint2> mb_msgs;      // two message buffers of n_arcs entries
-  DBuf<uint32_t> mb_words;  // counts (2 x nb^2), wrote (2 x nb), pend masks, blk_pend, blk_mind, blk_far, wl_cnt
+  DBuf<uint32_t> mb_words;  // counts (2 x nb^2), wrote (2 x nb), pend masks, blk_pend, blk_mind, blk_far, wl_cnt, blk_best (nb x 64 bits)
   DBuf<uint4> mb_wl;        // work-list segments of the NARROW launches (nb x NW_SEG entries)
   DBuf<unsigned long long> mb_dbg;  // WFST_SSSP_MBOX_TRACE=<file>: per-block phase stamps of the first 64 sweeps
   MboxView mv{};
@@ -1363,6 +1382,10 @@ struct Solve {
   // NARROW launch that drains the search (set by shortest_path_n1_begin before the first batch is queued)
   bool early_on = false;
   EarlyTail early{};
+  // ... and the resident launch in front of that NARROW launch leaves every block's best final state for it (mbox_blk_best;
+  // the kernel's `blk_finals` is null and EarlyTail::blk_best_on 0 unless this is on): early tail, 4096-state blocks, a resident
+  // launch, WFST_SSSP_EARLY_BEST
+  bool blk_best_on = false;
   // resident launches (sssp_resident.h): the WIDE levels of the solve inside ONE launch, every workgroup on a CU of its own
   bool resident = false;
   uint32_t log = 12;         // log2 of the block size (13: every launch of the solve is a resident one)
@@ -1530,7 +1553,7 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
     if (sv.log == 13 || (sv.resident && !profile && (abs_sweep & 1u) && abs_sweep < RS_MAX_SWEEP))
       sv.res_kernel<<<sv.mv.nb, MB_THREADS, sv.res_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, sv.rv, abs_sweep & 1u, n,
                                                               sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, sv.narrow_t,
-                                                              sv.res_max_levels, sv.res_lps_umax);
+                                                              sv.res_max_levels, sv.res_lps_umax, sv.blk_best_on ? f->dev.finals : nullptr);
     else
       sv.mbox_kernel<<<sv.mv.nb + (sv.early_on && !profile ? 1u : 0u), MB_THREADS, sv.mb_dyn, st>>>(
           f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n, sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile,
@@ -1663,7 +1686,7 @@ bool plan_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
       }
       sv.mb_msgs = DBuf<uint2>(pool, 2 * (size_t)f->n_arcs);
       const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << log) / 32);
-      sv.mb_words = DBuf<uint32_t>(pool, 2 * w_cnt + 2 * nb + w_pend + 4 * nb);
+      sv.mb_words = DBuf<uint32_t>(pool, 2 * w_cnt + 2 * nb + w_pend + 4 * nb + 2 * nb);
       sv.mb_wl = DBuf<uint4>(pool, (size_t)nb << log);
       if (res) {  // what the resident launch needs beyond the plan
         sv.rs_msgs = DBuf<uint2>(pool, 2 * (size_t)sv.plan->res_units);
@@ -1710,6 +1733,8 @@ void bind_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
   mv.blk_mind = w + nb;
   mv.blk_far = w + 2 * nb;
   mv.wl_cnt = w + 3 * nb;
+  // (behind wl_cnt: blk_best, nb 64-bit words — an even number of 32-bit words in front of them: 8-byte aligned)
+  sv.blk_best_on = false;  // (shortest_path_n1_begin switches it on)
   mv.wl = sv.mb_wl.p;
   mv.nb = nb;
   // staging depth: what the dynamic LDS budget leaves after the three per-destination tables
@@ -2485,7 +2510,13 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   if (fuse && j->sv.mbox && j->sv.kn.early_tail != 0 && j->rev->has_fin && j->sv.kn.final_list != 0 && j->rev->fin_nonneg) {
     j->sv.early_on = true;
     j->sv.early = EarlyTail{j->rev->fin.p, f->dev.finals, f->dev.arcs, j->rev->off.p, j->rev->arc.p, j->h_path, j->h_tail,
-                            j->rev->n_fin, PATH_PINNED};
+                            j->rev->n_fin, PATH_PINNED, 0u};
+    // the blocks' best final states from the resident launch's hand-over (8192-state blocks: that kernel runs the NARROW
+    // launches itself and there is no extra workgroup)
+    if (j->sv.kn.early_best != 0 && j->sv.resident && j->sv.log == 12) {
+      j->sv.blk_best_on = true;
+      j->sv.early.blk_best_on = 1u;
+    }
   }
   j->drv.start(/*defer_advance=*/fuse);
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
@@ -2542,6 +2573,14 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
     if (e != EARLY_USED)
       throw Error(std::string("shortest_path: WFST_SSSP_EARLY_TAIL=2 and the early tail's result was ") +
                   (!sv.early_on ? "not eligible" : e == EARLY_REFUTED ? "refuted" : "absent"));
+  }
+  if (sv.kn.early_best >= 2) {  // tests: the result the early tail merged from the blocks' best final states, or an error that says why not
+    const bool ran = sv.early_on && sv.log == 12 && j->fused_tail && !j->drv.extended;
+    const uint32_t e = ran ? j->h_tail->early : EARLY_ABSENT;
+    if (e != EARLY_USED || !sv.blk_best_on || j->h_tail->early_src != EARLY_SRC_BLOCKS)
+      throw Error(std::string("shortest_path: WFST_SSSP_EARLY_BEST=2 and the blocks' best final states were not the result's source: ") +
+                  (!sv.early_on || sv.log != 12 ? "not eligible" : !sv.blk_best_on ? "no resident hand-over" : e == EARLY_REFUTED ? "refuted"
+                   : e != EARLY_USED ? "absent" : "no resident hand-over"));
   }
   const Ctl* hc = j->hc;
   const uint32_t r_pad = j->fused_tail ? j->h_tail->pad : hc->pad, r_has_path = j->fused_tail ? j->h_tail->has_path : hc->has_path;

@@ -76,12 +76,16 @@ struct MboxView {
   uint32_t* blk_mind;      // [nb] min enc(d) among them (a lower bound after a NARROW launch)
   uint32_t* blk_far;       // [nb] how many of them are beyond the threshold
   uint4* wl;               // [nb * NW_SEG] work list of the NARROW launches: {state, arc begin, enc(d), hops << 12 | arcs}
-  uint32_t* wl_cnt;        // [nb] entries in segment j
+  uint32_t* wl_cnt;        // [nb] entries in segment j; behind them blk_best (mbox_blk_best)
   uint32_t nb;
   uint32_t stg;            // staging slots per destination (MB_STG_MAX, fewer for many blocks)
   unsigned long long* dbg;  // tuning only (WFST_SSSP_MBOX_TRACE): wall-clock stamps [sweep][block][16], or null
 };
 constexpr uint32_t MB_DBG_SWEEPS = 64;
+// [nb] 64-bit words behind wl_cnt: the best final state of block j, tail_pack(enc(total) << 32 | state, tie), as its keys
+// stood when a resident launch handed over (KEY_INF: none reachable); valid for the launch behind Ctl::blk_best_sweep.
+// (Not a pointer of its own in the view: the resident kernel has no scalar register left to keep one until its epilogue.)
+__device__ __forceinline__ unsigned long long* mbox_blk_best(const MboxView& mb) { return (unsigned long long*)(mb.wl_cnt + mb.nb); }
 #define MB_STAMP(p) do { if (mb.dbg && tid == 0 && sweep < MB_DBG_SWEEPS) mb.dbg[((size_t)sweep * nb + j) * 16 + (p)] = wall_clock64(); } while (0)
 
 // ---- plan (cached on the FST handle): region offsets from the number of arcs between every pair of blocks
@@ -357,8 +361,6 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
   // (the two lists alternate; their COUNTERS rotate through three words, so that the one a level will fill next can be zeroed a
   // level ahead and a level needs ONE barrier: a hop of the tail is ~2 us, two trips and this)
   uint32_t cur = 0, cnt_i = 0, prev_n = 0, prev2_n = 0, far_new = 0;
-  // the least enc(d) this thread has written into key[]: what the early tail's result is certified against (Ctl::narrow_low)
-  uint32_t low = 0xFFFFFFFFu;
   bool left_any = false;
   unsigned long long p_arcs = 0, p_states = 0;
   bool grew = false;
@@ -449,7 +451,11 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
         for (uint32_t u = 0; u < NW_UNROLL; ++u) {
           const bool won = v[u] && ck[u] < old[u];
           if (won) {
-            low = min(low, enc[u]);
+            // the least enc(d) this launch writes into key[]: what the early tail's result is certified against
+            // (Ctl::narrow_low).  Straight into s_n[5], and not in launch 0 — the early tail never runs there and only
+            // launches k >= 1 are certified: kept in a register across the level loop and reduced at the end, the recording
+            // cost the head launch 2.6 us (profiles/early_block_best_ab.md)
+            if (!head) atomicMin(&s_n[5], enc[u]);
             if (h1_[u] >> MB_HOP_BITS) ctl->pad = 1u;  // hop count beyond the message format: the host refuses the result
             bool listed = false;
             if (key_f32(enc[u]) <= tau) {
@@ -493,14 +499,10 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     const uint4* __restrict__ in = wl + cur * NW_CAP;
     for (uint32_t e = tid; e < left; e += MB_THREADS) mbox_make_wait<LOG>(mb, in[e].x, in[e].z, false);
     if (__any(left_any || left != 0u) && lane == 0) s_n[4] = 1u;
-    if (__any(low != 0xFFFFFFFFu)) {  // one LDS atomic per wave that lowered a key, one global atomic per workgroup
-      low = wave_min_u32(low);
-      if (lane == 0) atomicMin(&s_n[5], low);
-    }
     __syncthreads();
     if (tid == 0) {
       atomicMax(improved, s_n[4] ? FLAG_NARROW_LEFT : FLAG_NARROW_CLEAN);
-      if (s_n[5] != 0xFFFFFFFFu) atomicMin(&ctl->narrow_low[sweep % RING], s_n[5]);
+      if (s_n[5] != 0xFFFFFFFFu) atomicMin(&ctl->narrow_low[sweep % RING], s_n[5]);  // (one global atomic per workgroup)
     }
     if (head) {  // the messages of the head: counts of the regions, like a WIDE sweep's publish
       bool any = false;
@@ -568,10 +570,26 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
   // hand-over it does the tail's search and walk while the others drain the search (sssp_early_tail; its LDS is lkey's).
   if (blockIdx.x == mb.nb) {
     if (sweep == 0) return;
-    const uint32_t prev_flag = improved_ring[(sweep - 1u) % IMP_RING];  // (asked for with the schedule words: one trip)
+    // (one trip: the previous launch's flag, the blocks' best final states with the launch that left them, the schedule words)
+    const uint32_t prev_flag = improved_ring[(sweep - 1u) % IMP_RING];
+    constexpr uint32_t NBB = BIG ? MB_NBMAX_BIG / MB_THREADS : 1;  // blocks per thread
+    unsigned long long bb[NBB];
+    uint32_t bb_sweep = 0;
+    for (uint32_t r = 0; r < NBB; ++r) bb[r] = KEY_INF;
+    if (et.blk_best_on) {
+      for (uint32_t r = 0; r < NBB; ++r) {
+        const uint32_t t = threadIdx.x + MB_THREADS * r;
+        if (t < mb.nb) bb[r] = mbox_blk_best(mb)[t];
+      }
+      bb_sweep = ctl->blk_best_sweep;
+    }
     const SchedRaw raw = mbox_sched_load(ctl, sweep);
+    const bool merged = bb_sweep != 0u && bb_sweep == sweep - 1u;  // (0 = nobody left any: a resident launch that hands over is not launch 0)
+    unsigned long long best = KEY_INF;
+    bool tie = false;
+    for (uint32_t r = 0; r < NBB; ++r) tail_merge_packed(best, tie, bb[r]);
     const Sched sc = mbox_sched_eval(ctl, raw, sweep, delta, near_low, narrow_t);
-    if (sc.mode == MODE_NARROW) sssp_early_tail(et, offsets, key, ctl, prev_flag, sweep, lkey);
+    if (sc.mode == MODE_NARROW) sssp_early_tail(et, offsets, key, ctl, prev_flag, sweep, lkey, merged, merged ? best : KEY_INF, merged && tie);
     return;
   }
   // `sweep` is the absolute sweep index: the host knows it (plain launches), which saves the trip to ctl->base

@@ -215,7 +215,8 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_resident_kernel(const ui
                                                                         uint64_t* __restrict__ key, MboxView mb, ResView rv, uint32_t par_in,
                                                                         uint32_t n, uint32_t* __restrict__ improved_ring, Ctl* __restrict__ ctl,
                                                                         uint32_t sweep, float delta, uint32_t near_low, uint32_t narrow_t,
-                                                                        uint32_t max_levels, uint32_t lps_umax) {
+                                                                        uint32_t max_levels, uint32_t lps_umax,
+                                                                        const float* __restrict__ blk_finals) {
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, MB_HOP_BITS = 32 - LOG, NW_SEG = MB_B;
   extern __shared__ __align__(16) unsigned char mb_dyn[];
   ResScalars& sc_ = *(ResScalars*)mb_dyn;
@@ -230,6 +231,8 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_resident_kernel(const ui
   constexpr uint32_t R = MB_B / MB_THREADS;
   constexpr uint32_t PW = MB_B / 32;
   constexpr uint32_t WPR = MB_THREADS / 32;
+  // (one word of every 64-byte line of the argument segment, asked for together as in sssp_mbox_kernel: five lines, the
+  // last one from max_levels on)
   asm volatile("" ::"s"(offsets), "s"(mb.cnt[1]), "s"(ctl), "s"(rv.roffh), "s"(max_levels));
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t j = blockIdx.x, nb = mb.nb, stg = mb.stg;
@@ -619,17 +622,56 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_resident_kernel(const ui
 
   // ---------------- the launch is over: keys, waiting masks, schedule ring as a one-level launch would leave them
   __syncthreads();
+  const bool collect_exit = !clean;
+  // `blk_finals` (the FST's final weights; null: off for this solve; 4096-state blocks only): on the COLLECT exit the workgroup
+  // leaves the best final state of its block in mbox_blk_best(mb)[j] — the keys are all in LDS here, the final weights are one
+  // coalesced trip asked for in front of the key stores and consumed behind them — and the early tail of the next launch
+  // merges nb words instead of gathering the keys of every final state through one compute unit (sssp_early_tail).
+  // (Asked for earlier — where the level turns out to be the hand-over, or behind the scan's barrier in front of the work-list
+  // stores — the four values cost the <12> instance 7 and 8 spilled registers inside the level loop: the kernel sits at its
+  // 128-register cap.)
+  const bool blk_best_on = LOG == 12 && collect_exit && blk_finals != nullptr;  // (uniform)
+  float fin_w[R];
+  for (uint32_t r = 0; r < R; ++r) {
+    const uint32_t s = s0 + tid + MB_THREADS * r;
+    fin_w[r] = INF;
+    if (blk_best_on && s < n) fin_w[r] = blk_finals[s];
+  }
   for (uint32_t r = 0; r < R; ++r) {
     const uint32_t tl = tid + MB_THREADS * r, s = s0 + tl;
     if (s < n) key[s] = lkey[tl];
     if ((tid & 31u) == 0) mb.pend[j * PW + (tid >> 5) + WPR * r] = 0;
   }
-  const bool collect_exit = !clean;
+  if (blk_best_on) {
+    unsigned long long best = KEY_INF;
+    bool tie = false;
+    for (uint32_t r = 0; r < R; ++r) {
+      const uint32_t tl = tid + MB_THREADS * r;
+      tail_candidate(lkey[tl], s0 + tl, fin_w[r], best, tie);  // (a state beyond n: key and weight are +inf)
+    }
+    tail_wave_reduce(best, tie);
+    unsigned long long* const s_best = (unsigned long long*)a_state;  // (the level's list: its last readers are behind the barrier above)
+    if (lane == 0) s_best[tid >> 6] = tail_pack(best, tie);
+    __syncthreads();
+    if (tid < 64) {
+      best = KEY_INF;
+      tie = false;
+      if (lane < MB_THREADS / 64) tail_merge_packed(best, tie, s_best[lane]);
+      tail_wave_reduce(best, tie);
+      if (tid == 0) {
+        mbox_blk_best(mb)[j] = tail_pack(best, tie);
+        if (j == 0) ctl->blk_best_sweep = sweep;
+      }
+    }
+  }
   if (tid == 0) {
     mb.blk_pend[j] = 0;
     mb.blk_mind[j] = 0xFFFFFFFFu;
     mb.blk_far[j] = 0;
-    mb.wl_cnt[j] = collect_exit ? last_an : 0u;
+    // (the block index through an opaque copy: the address of wl_cnt[j] from the prologue is not kept in a register, or spilled, for this)
+    uint32_t j_ = j;
+    asm volatile("" : "+s"(j_));
+    mb.wl_cnt[j_] = collect_exit ? last_an : 0u;
     if (collect_exit) {
       if (last_an) atomicMax(improved, 1u + MODE_COLLECT);
       if (last_an | last_nfar) atomicAdd(nf, ((unsigned long long)last_nfar << 32) | last_an);
