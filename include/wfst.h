@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -393,6 +393,16 @@ wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
  *      diagnostics of how the scratch sizes were climbed; any pointer after ctx may be NULL. */
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap);
+
+/* ---- the re-armed scratch of the single-shortest-path relaxation: a predicted mailbox solve has its scratch
+ *      cleaned on the device BEHIND its result and parks it on the context; the next solve with the same graph structure and
+ *      schedule on that context adopts it and starts without a set-up launch.  Counters of ctx since its creation: solves that
+ *      parked their scratch (armed), solves that started from parked scratch (adopted), and parked scratch that was given back
+ *      unused (dropped).  Any pointer after ctx may be NULL.  WFST_SSSP_REARM=0 switches the mechanism off. ---- */
+wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* adopted, uint64_t* dropped);
+/* hipFree of every block the context's device pool holds without an owner: cached blocks and parked scratch (the pool does
+ *      the same by itself when an allocation fails).  Synchronises the device.  Live buffers are not touched. */
+wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx);
 
 /* ---- project: fst_project (rustfst-ffi/src/algorithms/project.rs:45-70) = rustfst::algorithms::project
  *      (rustfst/src/algorithms/projection.rs:65-95), in place on the device-resident arcs.  project_output == 0:

@@ -79,6 +79,8 @@ SYMBOLS = [
     ("wfst_connect", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_rm_epsilon", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_ctx_get_rm_epsilon_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_ctx_get_rearm_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_ctx_trim_pool", C.c_int, [_vp]),
     ("wfst_fst_project", C.c_int, [_vp, _vp, C.c_int]),
     ("wfst_lookahead_create", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_lookahead_relabel", C.c_int, [_vp, _vp, _P(_vp)]),
@@ -187,7 +189,11 @@ def lib():
         # (experiments only: WFST_LIB_PATH points tools/ A/B scripts at another build of the same ABI)
         L = C.CDLL(os.environ.get("WFST_LIB_PATH") or LIB_PATH)
         for name, res, args in SYMBOLS:
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None and os.environ.get("WFST_LIB_PATH"):
+                continue  # (an older build of the same ABI version: what it lacks cannot be called)
+            if fn is None:
+                raise AttributeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m rustfst_amd.build)")
             fn.restype = res
             fn.argtypes = args
         _lib = L

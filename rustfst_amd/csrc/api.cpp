@@ -72,9 +72,32 @@ void DevicePool::free(void* p) {
   free_.emplace(it->second, p);
   live_.erase(it);
 }
+void DevicePool::park(void* const* ps, size_t count) {
+  std::lock_guard<std::mutex> lk(mu_);
+  for (size_t i = 0; i < count; ++i) {
+    auto it = ps[i] ? live_.find(ps[i]) : live_.end();
+    if (it == live_.end()) continue;
+    parked_.emplace(it->first, it->second);
+    live_.erase(it);
+  }
+}
+bool DevicePool::unpark(void* const* ps, size_t count) {
+  std::lock_guard<std::mutex> lk(mu_);
+  for (size_t i = 0; i < count; ++i)
+    if (ps[i] && parked_.find(ps[i]) == parked_.end()) return false;  // (trim takes all of them at once)
+  for (size_t i = 0; i < count; ++i) {
+    if (!ps[i]) continue;
+    auto it = parked_.find(ps[i]);
+    live_.emplace(it->first, it->second);
+    parked_.erase(it);
+  }
+  return true;
+}
 void DevicePool::trim_locked() {
   for (auto& kv : free_) (void)hipFree(kv.second);
   free_.clear();
+  for (auto& kv : parked_) (void)hipFree(kv.first);
+  parked_.clear();
 }
 void DevicePool::trim() {
   std::lock_guard<std::mutex> lk(mu_);
@@ -83,6 +106,16 @@ void DevicePool::trim() {
 DevicePool::~DevicePool() {
   trim();
   for (auto& kv : live_) (void)hipFree(kv.first);
+}
+
+void rearm_drop(wfst_ctx* ctx) {
+  RearmRecord& r = ctx->rearm;
+  if (!r.plan) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->pool && ctx->pool->unpark(r.blk, RearmRecord::BLOCKS))
+    for (void* b : r.blk) ctx->pool->free(b);
+  r.clear();
+  ctx->rearm_dropped += 1;
 }
 
 void* PinnedBuf::get(size_t bytes) {
@@ -229,6 +262,7 @@ wfst_status wfst_ctx_destroy(wfst_ctx* ctx) {
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (hipEvent_t e : ctx->ev_chain)
       if (e) (void)hipEventDestroy(e);
+    rearm_drop(ctx);  // (the pool may outlive the context: handles share it)
     ctx->pool.reset();
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -746,6 +780,22 @@ wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint
     if (states_thread) *states_thread = ctx->rm_eps.states_thread;
     if (states_wave) *states_wave = ctx->rm_eps.states_wave;
     if (max_closure_cap) *max_closure_cap = ctx->rm_eps.max_closure_cap;
+  });
+}
+
+wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* adopted, uint64_t* dropped) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (armed) *armed = ctx->rearm_armed;
+    if (adopted) *adopted = ctx->rearm_adopted;
+    if (dropped) *dropped = ctx->rearm_dropped;
+  });
+}
+wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx) {
+  return wrap([&] {
+    if (!ctx || !ctx->pool) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->pool->trim();
   });
 }
 

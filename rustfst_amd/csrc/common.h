@@ -97,6 +97,12 @@ class DevicePool {
   void* alloc(size_t bytes);
   void free(void* p);
   void trim();
+  // Parked blocks: live blocks set aside with their contents for a later owner (the re-armed scratch of a relaxation, which a
+  // kernel may still be writing when its solve lets go of it: wfst_ctx::rearm).  Out of alloc's reach; trim (the out-of-memory
+  // retry included) and the destructor hipFree them like cached blocks — hipFree synchronises the device, so a kernel that still
+  // writes one is over first — and the unpark that follows reports them gone.  All of `ps` or none, under one lock.
+  void park(void* const* ps, size_t count);
+  bool unpark(void* const* ps, size_t count);  // live again, as alloc would have returned them; false: reclaimed (none is live)
 
  private:
   static size_t bucket(size_t bytes);
@@ -104,6 +110,7 @@ class DevicePool {
   std::mutex mu_;
   std::multimap<size_t, void*> free_;
   std::map<void*, size_t> live_;
+  std::map<void*, size_t> parked_;
 };
 
 // RAII device buffer from the pool
@@ -128,6 +135,19 @@ struct DBuf {
   void reset() {
     if (p) pool->free(p);
     p = nullptr;
+  }
+  // a live block of the pool that somebody else allocated (DevicePool::unpark), and the way out again (DevicePool::park)
+  static DBuf adopt(DevicePool& pl, void* block, size_t count) {
+    DBuf b;
+    b.pool = &pl;
+    b.p = (T*)block;
+    b.n = count;
+    return b;
+  }
+  T* release() {
+    T* r = p;
+    p = nullptr;
+    return r;
   }
   ~DBuf() { reset(); }
 };
@@ -157,6 +177,25 @@ class PinnedRing : public std::enable_shared_from_this<PinnedRing> {
   std::vector<PinnedBlock*> free_;
 };
 
+struct MboxPlan;
+// The scratch of a mailbox relaxation that the re-arm launch behind the solve's tail has cleaned (or is cleaning) for the next
+// solve on this context (sssp.hip: relax_setup adopts it, shortest_path_n1_end parks it).  Nothing here refers to a handle by
+// address — a destroyed handle's address can be reused; the plan cannot while the record holds it.
+struct RearmRecord {
+  std::shared_ptr<DevicePool> plan_pool;  // the pool the plan's tables came from (the handle's owner's): outlives the plan
+  std::shared_ptr<MboxPlan> plan;         // identity of the graph's structure (null: nothing parked)
+  uint32_t n = 0, log = 0, stg = 0, tau0_bits = 0;
+  bool resident = false, narrow = false;
+  static constexpr size_t BLOCKS = 6;  // key, mb_words, improved, ctl, rs_msgs, rs_abort (null: the solve had none)
+  void* blk[BLOCKS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t cnt[BLOCKS] = {0, 0, 0, 0, 0, 0};
+  void clear() {  // (the plan goes before its pool)
+    plan.reset();
+    plan_pool.reset();
+    for (void*& b : blk) b = nullptr;
+    for (size_t& c : cnt) c = 0;
+  }
+};
 }  // namespace wfst
 
 // ---------------------------------------------------------------- handles
@@ -206,6 +245,8 @@ struct wfst_ctx {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
   } rm_eps;
   int n_cus = 256;
+  wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
+  uint64_t rearm_armed = 0, rearm_adopted = 0, rearm_dropped = 0;  // wfst_ctx_get_rearm_stats
 };
 
 // Device-resident CSR. All arrays live in one arena allocation that may be
@@ -401,6 +442,9 @@ void adopt_device_many(wfst_ctx* ctx, size_t m, const AdoptDesc* descs, wfst_fst
 wfst_fst* fst_from_openfst_bytes(wfst_ctx* ctx, const uint8_t* data, size_t len);
 void fst_to_openfst_bytes(const wfst_fst* f, std::vector<uint8_t>& out);
 void fst_to_openfst_const_bytes(const wfst_fst* f, std::vector<uint8_t>& out);
+// api.cpp: gives the parked scratch of ctx back to the pool (nothing parked: nothing happens).  The re-arm launch may still be
+// writing it, so the stream is waited for first — a rare path: a solve that matches the record adopts it instead.
+void rearm_drop(wfst_ctx* ctx);
 // sssp.hip
 wfst_fst* shortest_path_n1(wfst_ctx* ctx, const wfst_fst* f);
 wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f);

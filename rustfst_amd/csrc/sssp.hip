@@ -97,6 +97,10 @@ struct Ctl {
   // the resident launch that left every block's best final state in MboxView::blk_best on its COLLECT exit (0 = none: a
   // resident launch that hands over is never launch 0); the early tail of launch blk_best_sweep + 1 merges those words
   uint32_t blk_best_sweep;
+  // the fused tail's verdict for the re-arm launch queued behind it (sssp_mbox_rearm_kernel): 1 = the solve reached its fixed
+  // point inside the batch and the host will not read the keys again — clean the scratch for the next solve.  Written by every
+  // fused tail that has such a launch behind it; the cleaning itself leaves the word alone.
+  uint32_t rearm;
 };
 constexpr uint32_t TAIL_BLOCKS = 128;
 constexpr uint32_t TAIL_LIST_BLOCKS = 16;  // ... over the handle's list of final states (RevCsr::fin), 4096 entries each
@@ -111,6 +115,7 @@ struct TailOut {
                   // several final states attain the optimum: 0 = the optimum is unique (wfst_stats.tied_choices)
   uint32_t early;  // EARLY_*: what sssp_tail_kernel made of the early tail's result
   uint32_t early_src;  // EARLY_SRC_*: where the early tail that published last took the best final state from
+  uint32_t rearmed;    // Ctl::rearm as this launch wrote it (0 from a tail without a re-arm launch behind it): the host parks the scratch
 };
 constexpr uint32_t EARLY_UNCHECKED = 0, EARLY_USED = 1, EARLY_ABSENT = 2, EARLY_REFUTED = 3;
 constexpr uint32_t EARLY_SRC_LIST = 1, EARLY_SRC_BLOCKS = 2;
@@ -125,6 +130,7 @@ struct EarlyTail {
   TailOut* hout;  // pinned host memory
   uint32_t n_fin, out_cap;
   uint32_t blk_best_on;  // the resident launches of this solve leave the blocks' best final states (mbox_blk_best)
+  uint32_t seed;  // launch 0 on re-armed scratch: start state + 1 — the owner of its block seeds it (0: a set-up launch did)
 };
 __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint32_t* __restrict__ offsets, const uint64_t* __restrict__ key,
                                 Ctl* __restrict__ ctl, uint32_t prev_flag, uint32_t sweep, unsigned long long* lds, bool merged,
@@ -1003,7 +1009,8 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
                                                          const uint4* __restrict__ rev_arc, wfst_tr* __restrict__ out,
                                                          uint32_t out_cap, TailOut* __restrict__ hout,
                                                          uint32_t* __restrict__ improved_ring, uint32_t adv_count,
-                                                         uint32_t* __restrict__ host_ring, uint32_t done_ticket, uint32_t early_check) {
+                                                         uint32_t* __restrict__ host_ring, uint32_t done_ticket, uint32_t early_check,
+                                                         uint32_t rearm_on) {
   __shared__ unsigned long long s_best[16];
   __shared__ uint2 s_walk[WALK_LDS];
   __shared__ uint32_t s_last;
@@ -1012,13 +1019,35 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   // pinned host memory, the slots half a ring ahead are recycled, the base moves on) — one launch and one flush of
   // host-memory writes less at the end of a predicted solve.  By the wave that writes the ticket at the end: ONE
   // system-scope fence orders all of it.
-  auto advance = [&]() {
+  // Returns (uniform) what SweepDriver::scan_flags will make of the flags on the host: the first launch of the batch whose flag
+  // is 0, FLAG_NARROW_CLEAN or FLAG_RES_ABORT exists and did not abort — the solve is over and nothing will be queued behind it.
+  auto advance = [&]() -> bool {
     const uint32_t base = ctl->base;
-    for (uint32_t i = lane; i < adv_count; i += 64) {
-      host_ring[(base + i) % IMP_RING] = improved_ring[(base + i) % IMP_RING];
-      improved_ring[(base + IMP_RING / 2 + i) % IMP_RING] = 0;
+    bool finished = false, decided = false;
+    for (uint32_t i0 = 0; i0 < adv_count; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      uint32_t v = 1u;
+      if (i < adv_count) {
+        v = improved_ring[(base + i) % IMP_RING];
+        host_ring[(base + i) % IMP_RING] = v;
+        improved_ring[(base + IMP_RING / 2 + i) % IMP_RING] = 0;
+      }
+      const unsigned long long stop = __ballot(v == 0u || v == FLAG_NARROW_CLEAN || v == FLAG_RES_ABORT);
+      if (stop != 0ull && !decided) {
+        decided = true;
+        finished = ((__ballot(v == FLAG_RES_ABORT) >> (__ffsll((long long)stop) - 1)) & 1ull) == 0ull;
+      }
     }
     if (lane == 0) ctl->base = base + adv_count;  // (every lane of the wave has read the old value above)
+    return finished;
+  };
+  // The verdict for the re-arm launch behind this one, and for the host that parks the scratch: the solve is over AND the host
+  // will not come back for the keys (a path beyond the pinned buffer, pad & 8, sends it into the parent pass over them).
+  // In front of the ticket.
+  auto verdict = [&](bool finished, uint32_t pad) {
+    const uint32_t v = rearm_on && finished && !(pad & 8u) ? 1u : 0u;
+    if (rearm_on) ctl->rearm = v;
+    hout->rearmed = v;
   };
   uint32_t early = EARLY_UNCHECKED;
   if (early_check) {  // (uniform reads: the early tail's launch, then that launch's flag and its least write)
@@ -1030,10 +1059,12 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
     }
     if (early == EARLY_USED) {
       if (blockIdx.x != 0 || threadIdx.x >= 64) return;
-      if (adv_count) advance();
+      const bool finished = adv_count ? advance() : false;
       if (lane == 0) {
-        hout->pad = ctl->pad;  // (the walk's flags were clear; a relaxation may have raised the hop-count flag since)
+        const uint32_t pad = ctl->pad;
+        hout->pad = pad;  // (the walk's flags were clear; a relaxation may have raised the hop-count flag since)
         hout->early = EARLY_USED;
+        verdict(finished, pad);
       }
       host_stores_done();
       if (lane == 0) __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1069,7 +1100,7 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   }
   __syncthreads();
   if (!s_last || threadIdx.x >= 64) return;
-  if (adv_count) advance();
+  const bool finished = adv_count ? advance() : false;
   // the last workgroup's first wave: every other workgroup's result is in memory
   best = KEY_INF;
   tie = false;
@@ -1082,7 +1113,8 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
     ctl->best = best;
     hout->early = early;
   }
-  tail_walk_publish(best, tie, pad, finals, key, offsets, arcs, rev_off, rev_arc, out, out_cap, hout, ctl, s_walk);
+  const uint32_t pad_out = tail_walk_publish(best, tie, pad, finals, key, offsets, arcs, rev_off, rev_arc, out, out_cap, hout, ctl, s_walk);
+  if (lane == 0) verdict(finished, pad_out);
   // (the walk's arcs were written by several lanes of this wave)
   host_stores_done();
   if (lane == 0) __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1308,6 +1340,7 @@ struct Knobs {
   int final_list = 1;                   // WFST_SSSP_FINAL_LIST
   int early_tail = 1;                   // WFST_SSSP_EARLY_TAIL
   int early_best = 1;                   // WFST_SSSP_EARLY_BEST
+  int rearm = 1;                        // WFST_SSSP_REARM
 };
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
@@ -1347,6 +1380,7 @@ Knobs read_knobs() {
   if (const char* e = env.get("WFST_SSSP_FINAL_LIST")) k.final_list = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_EARLY_TAIL")) k.early_tail = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_EARLY_BEST")) k.early_best = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_REARM")) k.rearm = std::atoi(e);
   return k;
 }
 
@@ -1358,6 +1392,13 @@ struct Solve {
   DBuf<uint32_t> improved;
   DBuf<Ctl> ctl;
   uint32_t sweeps = 0;
+  // Re-armed scratch (wfst_ctx::rearm): `armed` = this solve started from the parked scratch of the last one — no set-up launch
+  // was queued and launch 0 seeds the start state itself (EarlyTail::seed); otherwise `rearm_why` says why not (WFST_SSSP_REARM=2).
+  // `rearm_unproven`, inside relax_setup only: buffers of this solve are parked blocks that the re-arm launch may still be writing —
+  // none of them goes back to the pool before the stream has been waited for.
+  bool armed = false, rearm_unproven = false;
+  const char* rearm_why = "nothing parked";
+  float tau0 = 0.0f;  // threshold of sweep 0, as the set-up (or the re-arm launch of the solve before) leaves it in Ctl::tau0
   // schedule parameters fixed by relax_setup
   uint8_t* fl[2] = {nullptr, nullptr};
   uint32_t blocks = 1, near_low = 4096;
@@ -1554,10 +1595,13 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
       sv.res_kernel<<<sv.mv.nb, MB_THREADS, sv.res_dyn, st>>>(f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, sv.rv, abs_sweep & 1u, n,
                                                               sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, sv.narrow_t,
                                                               sv.res_max_levels, sv.res_lps_umax, sv.blk_best_on ? f->dev.finals : nullptr);
-    else
+    else {
+      EarlyTail et = sv.early;
+      et.seed = sv.armed && abs_sweep == 0 ? (uint32_t)f->start + 1u : 0u;  // (re-armed scratch: no set-up launch seeded the start state)
       sv.mbox_kernel<<<sv.mv.nb + (sv.early_on && !profile ? 1u : 0u), MB_THREADS, sv.mb_dyn, st>>>(
           f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n, sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile,
-          hint, sv.narrow_t, sv.early);
+          hint, sv.narrow_t, et);
+    }
   } else {
     uint8_t* const cur = sv.fl[j & 1u];
     uint8_t* const next = sv.fl[(j & 1u) ^ 1u];
@@ -1571,6 +1615,73 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
                                                                            off, sv.bv);
     }
   }
+}
+
+// ---- re-armed scratch (wfst_ctx::rearm).  What relax_setup took out of the context's record for the solve it sets
+// up: the six blocks, live again, each handed to the buffer that would otherwise have been allocated.  The re-arm launch that
+// cleans them may still be running, so whatever no buffer took waits for the stream before it goes back to the pool.
+enum : size_t { RH_KEY = 0, RH_MB_WORDS, RH_IMPROVED, RH_CTL, RH_RS_MSGS, RH_RS_ABORT };
+void rearm_prove(wfst_ctx* ctx, Solve& sv) {  // before a buffer of sv goes back to the pool inside relax_setup
+  if (!sv.rearm_unproven) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  sv.rearm_unproven = false;
+}
+struct RearmHeld {
+  wfst_ctx* ctx;
+  RearmRecord rec;  // (plan null: nothing was taken)
+  explicit RearmHeld(wfst_ctx* c) : ctx(c) {}
+  RearmHeld(const RearmHeld&) = delete;
+  RearmHeld& operator=(const RearmHeld&) = delete;
+  ~RearmHeld() { settle(); }
+  bool left() const {
+    for (void* b : rec.blk)
+      if (b) return true;
+    return false;
+  }
+  void settle() {
+    if (!left()) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void*& b : rec.blk) {
+      ctx->pool->free(b);
+      b = nullptr;
+    }
+  }
+  template <class T>
+  void take_or_alloc(Solve& sv, DBuf<T>& buf, size_t idx, size_t count) {
+    void* b = rec.cnt[idx] == count ? rec.blk[idx] : nullptr;
+    if (b) {
+      rec.blk[idx] = nullptr;
+      sv.rearm_unproven = true;
+      buf = DBuf<T>::adopt(*ctx->pool, b, count);
+    } else {
+      buf = DBuf<T>(*ctx->pool, count);
+    }
+  }
+};
+// The parked scratch of ctx for the solve of f that relax_setup begins, as far as can be told before the solve is planned
+// (the rest is compared once it is: relax_setup).  Returns why nothing was taken, null when the blocks are in `held`.
+const char* rearm_take(wfst_ctx* ctx, const wfst_fst* f, const Knobs& kn, RearmHeld& held) {
+  RearmRecord& r = ctx->rearm;
+  if (!r.plan) return "nothing parked";
+  const char* why = nullptr;
+  if (kn.rearm == 0 || ctx->profiling) {
+    why = "not eligible";
+  } else {
+    std::lock_guard<std::mutex> lk(f->cache_mu);
+    if (f->mbox != r.plan || f->n_states != r.n) why = "parked for another plan";
+  }
+  if (why) {
+    rearm_drop(ctx);
+    return why;
+  }
+  if (!ctx->pool->unpark(r.blk, RearmRecord::BLOCKS)) {  // (the pool's trim: hipFree has waited for the re-arm launch)
+    r.clear();
+    ctx->rearm_dropped += 1;
+    return "blocks reclaimed";
+  }
+  held.rec = std::move(r);
+  r.clear();
+  return nullptr;
 }
 
 // ---- relax_setup, piece by piece: the band, the block size and the lease, the mailbox plan, the two views, the binned levels
@@ -1661,9 +1772,10 @@ uint32_t resident_staging(const MboxPlan& plan) {
 // dense graph) the atomic sweeps, which need none of it, run instead.  The 8192-state plan exists in the resident kernel
 // only: when it cannot be had (the pool, a region buffer beyond the buffer-descriptor range, no room for staging), the
 // solve is planned again with 4096-state blocks and one launch per level — never refused.
-bool plan_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
+bool plan_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res, RearmHeld& held) {
   DevicePool& pool = *ctx->pool;
   auto release_all = [&] {
+    rearm_prove(ctx, sv);
     want_res = false;
     sv.rs_msgs.reset();
     sv.rs_abort.reset();
@@ -1686,11 +1798,11 @@ bool plan_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
       }
       sv.mb_msgs = DBuf<uint2>(pool, 2 * (size_t)f->n_arcs);
       const size_t w_cnt = (size_t)nb * nb, w_pend = (size_t)nb * ((1u << log) / 32);
-      sv.mb_words = DBuf<uint32_t>(pool, 2 * w_cnt + 2 * nb + w_pend + 4 * nb + 2 * nb);
+      held.take_or_alloc(sv, sv.mb_words, RH_MB_WORDS, 2 * w_cnt + 2 * nb + w_pend + 4 * nb + 2 * nb);
       sv.mb_wl = DBuf<uint4>(pool, (size_t)nb << log);
       if (res) {  // what the resident launch needs beyond the plan
-        sv.rs_msgs = DBuf<uint2>(pool, 2 * (size_t)sv.plan->res_units);
-        sv.rs_abort = DBuf<uint32_t>(pool, 16);
+        held.take_or_alloc(sv, sv.rs_msgs, RH_RS_MSGS, 2 * (size_t)sv.plan->res_units);
+        held.take_or_alloc(sv, sv.rs_abort, RH_RS_ABORT, 16);
       }
       want_res = res;
       sv.mbox = true;
@@ -1775,6 +1887,7 @@ void bind_resident(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, bool want_res) {
   if (sv.kn.stg) stg = std::min<uint32_t>(stg, *sv.kn.stg);
   if (stg < 4) {
     if (sv.log == 13) throw Error("shortest_path: internal error (the 8192-state plan without a resident launch)");
+    rearm_prove(ctx, sv);
     sv.rs_msgs.reset();
     sv.rs_abort.reset();
     sv.lease.release();
@@ -1872,17 +1985,16 @@ void bind_binned(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
 }
 
 // relax_setup allocates and initialises the state of a solve (keys, frontier flags, control block) and fixes its schedule parameters
-void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
-  sv.kn = read_knobs();
+void relax_setup_held(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, RearmHeld& held) {
   const Knobs& kn = sv.kn;
   const uint32_t n = f->n_states;
   DevicePool& pool = *ctx->pool;
-  sv.key = DBuf<uint64_t>(pool, n);
+  held.take_or_alloc(sv, sv.key, RH_KEY, n);
   sv.shadow = DBuf<uint32_t>(pool, n);
   const size_t n_pad = ((size_t)n + 15) & ~(size_t)15;
   sv.flags = DBuf<uint8_t>(pool, 2 * n_pad);
-  sv.improved = DBuf<uint32_t>(pool, IMP_RING);
-  sv.ctl = DBuf<Ctl>(pool, 1);
+  held.take_or_alloc(sv, sv.improved, RH_IMPROVED, IMP_RING);
+  held.take_or_alloc(sv, sv.ctl, RH_CTL, 1);
   hipStream_t st = ctx->stream;
   sv.fl[0] = sv.flags.p;
   sv.fl[1] = sv.flags.p + n_pad;
@@ -1901,18 +2013,39 @@ void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
   sv.log = 12;
   sv.lease.release();
   bool want_res = mbox_mode >= 1 && lease_resident(ctx, n, sv);
-  if (mbox_mode >= 1) want_res = plan_mailbox(ctx, f, sv, want_res);
+  if (mbox_mode >= 1) want_res = plan_mailbox(ctx, f, sv, want_res, held);
   if (sv.mbox) {
     sv.delta = band_from_cheapest_arcs(f, *sv.plan, sv.delta, kn);
     bind_mailbox(ctx, f, sv);
     bind_resident(ctx, f, sv, want_res);
-    const auto setup_kernel = sv.log == 13 ? sssp_mbox_setup_kernel<13> : sssp_mbox_setup_kernel<12>;
-    setup_kernel<<<sv.blocks, 256, 0, st>>>(sv.key.p, sv.mv, sv.improved.p, sv.ctl.p, f->dev.offsets, n, (uint32_t)f->start,
-                                            sv.delta * tau0_mult, sv.narrow_t, sv.rv.msgs[0], sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
+  }
+  sv.tau0 = sv.delta * tau0_mult;
+  uint32_t tau0_bits;
+  std::memcpy(&tau0_bits, &sv.tau0, sizeof(tau0_bits));
+  if (held.rec.plan) {  // parked scratch was taken: it is this solve's initial state if the solve is the one it was cleaned for
+    const RearmRecord& r = held.rec;
+    const bool eligible = sv.mbox && sv.log == 12 && sv.narrow_t != 0;
+    if (eligible && !held.left() && sv.plan == r.plan && r.log == sv.log && r.resident == sv.resident && r.stg == sv.mv.stg && r.narrow &&
+        r.tau0_bits == tau0_bits) {
+      sv.armed = true;
+      sv.rearm_why = nullptr;
+      ctx->rearm_adopted += 1;
+    } else {  // (the blocks this solve took are its own now: whatever it queues comes behind the re-arm launch on the stream)
+      sv.rearm_why = eligible ? "knobs differ" : "not eligible";
+      ctx->rearm_dropped += 1;
+      held.settle();
+    }
+  }
+  if (sv.mbox) {
+    if (!sv.armed) {
+      const auto setup_kernel = sv.log == 13 ? sssp_mbox_setup_kernel<13> : sssp_mbox_setup_kernel<12>;
+      setup_kernel<<<sv.blocks, 256, 0, st>>>(sv.key.p, sv.mv, sv.improved.p, sv.ctl.p, f->dev.offsets, n, (uint32_t)f->start,
+                                              sv.tau0, sv.narrow_t, sv.rv.msgs[0], sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
+    }
   } else {
     bind_binned(ctx, f, sv);
     sssp_setup_kernel<<<sv.blocks, 256, 0, st>>>(sv.key.p, sv.shadow.p, (uint32_t*)sv.flags.p, (uint32_t)(2 * n_pad / 4),
-                                                 sv.improved.p, sv.ctl.p, n, (uint32_t)f->start, sv.delta * tau0_mult);
+                                                 sv.improved.p, sv.ctl.p, n, (uint32_t)f->start, sv.tau0);
   }
   HIP_CHECK(hipGetLastError());
   ctx->stats.relax_kernel = sv.mbox ? (sv.resident ? 2u : 1u) : (sv.binned ? 3u : 0u);
@@ -1920,6 +2053,21 @@ void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
   if (kn.chase_cap) sv.chase_cap = *kn.chase_cap;
   if (kn.chase_rounds) sv.chase_rounds = *kn.chase_rounds;
   if (kn.chase_low) sv.chase_low = *kn.chase_low;
+}
+void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
+  sv.kn = read_knobs();
+  sv.armed = false;
+  sv.rearm_unproven = false;
+  RearmHeld held(ctx);
+  sv.rearm_why = rearm_take(ctx, f, sv.kn, held);
+  try {
+    relax_setup_held(ctx, f, sv, held);
+  } catch (...) {
+    rearm_prove(ctx, sv);  // (the caller lets go of sv's buffers)
+    throw;
+  }
+  // (from here on a buffer of the solve is released only after the solve's own launches, which come behind the re-arm launch)
+  sv.rearm_unproven = false;
 }
 
 // Queues the sweeps of a solve in batches and finds the sweep that changed nothing.  start() queues the first batch and
@@ -2423,6 +2571,12 @@ struct wfst_sp_job {
   uint32_t done_ticket = 0;         // what the fused tail writes into h_tail->done when everything else is in host memory
   bool need_unique = false;         // tie order 1 on an input the reference does not relax in a topological order: the result
                                     // is returned only when the optimum is unique (then it IS the reference's), KO otherwise
+  // sssp_mbox_rearm_kernel is queued behind the fused tail and the solve's scratch has neither been parked nor waited for: the
+  // ticket no longer means that nothing of this job is on the stream
+  bool rearm_queued = false;
+  ~wfst_sp_job() {
+    if (rearm_queued && ctx) (void)hipStreamSynchronize(ctx->stream);  // (before sv's buffers go back to the pool)
+  }
 };
 
 namespace wfst {
@@ -2446,7 +2600,7 @@ void queue_tail(wfst_sp_job* j, const SweepBatch* adv = nullptr) {
         f->dev.finals, sv.key.p, n, listed ? j->rev->fin.p : nullptr, listed ? j->rev->n_fin : 0u, sv.ctl.p, f->dev.offsets, f->dev.arcs,
         j->rev->off.p, j->rev->arc.p, j->h_path,
         PATH_PINNED, j->h_tail, sv.improved.p, adv ? adv->count : 0u, adv ? j->drv.host_flags(*adv) : nullptr, j->done_ticket,
-        adv && sv.early_on ? 1u : 0u);
+        adv && sv.early_on ? 1u : 0u, adv && j->rearm_queued ? 1u : 0u);
     j->fused_tail = true;
     return;
   }
@@ -2493,6 +2647,7 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   static std::atomic<uint32_t> tickets{0};
   do j->done_ticket = tickets.fetch_add(1, std::memory_order_relaxed) + 1u; while (j->done_ticket == 0u);
   j->h_tail->done = 0u;
+  j->h_tail->rearmed = 0u;
   j->rev = reverse_csr(ctx, f, j->need_unique);  // may build the transpose (second query of a large FST): before anything is queued
   if (ctx->profiling) {
     run_relaxation(ctx, f, j->sv);  // per-sweep events: synchronous
@@ -2520,10 +2675,19 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   }
   j->drv.start(/*defer_advance=*/fuse);
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
+    // ... and behind the ticket, where the stream has nothing to do until the next query, the scratch is cleaned for that query
+    // if the tail finds this one over (Ctl::rearm): 4096-state blocks with NARROW launches (launch 0 then seeds the start itself)
+    Solve& sv = j->sv;
+    j->rearm_queued = sv.mbox && sv.log == 12 && sv.narrow_t != 0 && sv.kn.rearm != 0;
     queue_tail(j.get(), &j->drv.cur);
     j->tail_queued = true;
     j->drv.done_word = &j->h_tail->done;
     j->drv.done_ticket = j->done_ticket;
+    if (j->rearm_queued) {
+      sssp_mbox_rearm_kernel<12><<<sv.blocks, 256, 0, ctx->stream>>>(sv.key.p, sv.mv, sv.improved.p, sv.ctl.p, n, sv.tau0, sv.rv.msgs[0],
+                                                                     sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
+      HIP_CHECK(hipGetLastError());
+    }
   } else if (j->drv.predicted && j->rev) {
     queue_tail(j.get());
     j->tail_queued = true;
@@ -2558,6 +2722,46 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   else HIP_CHECK(hipPeekAtLastError());  // (no stream wait on this path.  Reports launch-configuration / sticky API errors the runtime has already
                                               // seen — NOT an asynchronous kernel fault: a chain that faults never writes its ticket, and the spin above then
                                               // ends in the stream wait, which reports it.  Peek, not Get: the error may belong to another thread's launch)
+  if (j->rearm_queued) {
+    // The tail's verdict, believed as it stands: the re-arm launch is cleaning (or has cleaned) the scratch, which is parked for
+    // the next solve on this context instead of going back to the pool — other contexts allocate from it on other streams.
+    // A re-arm launch that was queued and whose scratch is not parked is waited for (it returns at once when the verdict is 0).
+    RearmRecord& r = ctx->rearm;
+    if (j->h_tail->rearmed != 0u && !j->drv.extended && !r.plan) {
+      r.plan_pool = f->owner_pool ? f->owner_pool : ctx->pool;
+      r.plan = sv.plan;
+      r.n = n;
+      r.log = sv.log;
+      r.stg = sv.mv.stg;
+      std::memcpy(&r.tau0_bits, &sv.tau0, sizeof(r.tau0_bits));
+      r.resident = sv.resident;
+      r.narrow = sv.narrow_t != 0;
+      auto note = [&](size_t i, auto& buf) {
+        r.blk[i] = buf.p;
+        r.cnt[i] = buf.p ? buf.n : 0;
+      };
+      note(RH_KEY, sv.key);
+      note(RH_MB_WORDS, sv.mb_words);
+      note(RH_IMPROVED, sv.improved);
+      note(RH_CTL, sv.ctl);
+      note(RH_RS_MSGS, sv.rs_msgs);
+      note(RH_RS_ABORT, sv.rs_abort);
+      ctx->pool->park(r.blk, RearmRecord::BLOCKS);
+      (void)sv.key.release();
+      (void)sv.mb_words.release();
+      (void)sv.improved.release();
+      (void)sv.ctl.release();
+      (void)sv.rs_msgs.release();
+      (void)sv.rs_abort.release();
+      ctx->rearm_armed += 1;
+    } else {
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    j->rearm_queued = false;
+  }
+  if (sv.kn.rearm >= 2 && !sv.armed)  // tests: a solve that started from re-armed scratch, or an error that says why not
+    throw Error(std::string("shortest_path: WFST_SSSP_REARM=2 and the solve did not start from re-armed scratch: ") +
+                (sv.rearm_why ? sv.rearm_why : "not eligible"));
   if (ctx->chain_timing && !ctx->profiling) {  // the sweeps of this query as one chain (wfst_ctx_set_profiling(ctx, 2))
     ctx->stats.relax_ms = 0.0;
     ctx->stats.relax_launches = 0;

@@ -152,14 +152,17 @@ __global__ void mbox_transpose_kernel(const uint32_t* __restrict__ roff, uint32_
   roff_t[k] = roff[(size_t)j * nb + i];
 }
 
-// Initial state of a mailbox solve in one launch.  With NARROW launches the start state is the one entry of its block's
-// work-list segment (sweep 0 is NARROW); without, it waits in the pending mask (sweep 0 is WIDE).
+// Initial state of a mailbox solve.  With NARROW launches the start state is the one entry of its block's work-list segment
+// (sweep 0 is NARROW); without, it waits in the pending mask (sweep 0 is WIDE).  Two callers: the set-up launch in front of a
+// solve, and the re-arm launch behind a solve's tail (sssp_mbox_rearm_kernel), which has no start state (MB_NO_START: none of
+// the six start-dependent words is written — the start's key, its work-list entry and count, its pending bit, block count and
+// block minimum) and leaves Ctl::rearm, the word it was launched on, alone.
+constexpr uint32_t MB_NO_START = 0xFFFFFFFFu;  // (no state and no block has this index: n < 2^31)
 template <uint32_t LOG>
-__global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restrict__ key, MboxView mb, uint32_t* __restrict__ improved,
-                                                              Ctl* __restrict__ ctl, const uint32_t* __restrict__ offsets, uint32_t n,
-                                                              uint32_t start, float tau0, uint32_t narrow_on, uint2* rs_msgs0,
-                                                              uint2* rs_msgs1, const uint32_t* __restrict__ rs_roffh,
-                                                              uint32_t* __restrict__ rs_abort) {
+__device__ __forceinline__ void mbox_clean(uint64_t* __restrict__ key, const MboxView& mb, uint32_t* __restrict__ improved,
+                                           Ctl* __restrict__ ctl, const uint32_t* __restrict__ offsets, uint32_t n, uint32_t start,
+                                           float tau0, uint32_t narrow_on, uint2* rs_msgs0, uint2* rs_msgs1,
+                                           const uint32_t* __restrict__ rs_roffh, uint32_t* __restrict__ rs_abort) {
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, NW_SEG = MB_B;
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
   const uint32_t nb = mb.nb;
@@ -198,8 +201,33 @@ __global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restri
   for (uint32_t i = tid; i < IMP_RING; i += nt) improved[i] = 0;
   uint32_t* cw = (uint32_t*)ctl;
   constexpr uint32_t W_TAU0 = offsetof(Ctl, tau0) / 4, W_BEST = offsetof(Ctl, best) / 4, W_LOW = offsetof(Ctl, narrow_low) / 4;
-  for (uint32_t i = tid; i < (uint32_t)(sizeof(Ctl) / 4); i += nt)
+  constexpr uint32_t W_REARM = offsetof(Ctl, rearm) / 4;
+  for (uint32_t i = tid; i < (uint32_t)(sizeof(Ctl) / 4); i += nt) {
+    // (the re-arm launch: other workgroups may not have read the word yet; the next fused tail writes it before anybody reads it again)
+    if (i == W_REARM && start == MB_NO_START) continue;
     cw[i] = i == W_TAU0 ? __float_as_uint(tau0) : (i == W_BEST || i == W_BEST + 1 || (i >= W_LOW && i < W_LOW + RING)) ? 0xFFFFFFFFu : 0u;
+  }
+}
+template <uint32_t LOG>
+__global__ void __launch_bounds__(256) sssp_mbox_setup_kernel(uint64_t* __restrict__ key, MboxView mb, uint32_t* __restrict__ improved,
+                                                              Ctl* __restrict__ ctl, const uint32_t* __restrict__ offsets, uint32_t n,
+                                                              uint32_t start, float tau0, uint32_t narrow_on, uint2* rs_msgs0,
+                                                              uint2* rs_msgs1, const uint32_t* __restrict__ rs_roffh,
+                                                              uint32_t* __restrict__ rs_abort) {
+  mbox_clean<LOG>(key, mb, improved, ctl, offsets, n, start, tau0, narrow_on, rs_msgs0, rs_msgs1, rs_roffh, rs_abort);
+}
+// The same cleaning BEHIND a solve's fused tail, for the next solve on the same scratch (relax_setup adopts it and queues no
+// set-up launch; launch 0 then seeds the start state itself: EarlyTail::seed).  Runs in the gap in which the stream has nothing
+// to do — the host builds the result and comes back with the next query.  Only when the tail said so (Ctl::rearm: the solve
+// reached its fixed point inside the batch and the host will not read the keys again); writes nothing to host memory, waits
+// for nobody.  NARROW launches only (sweep 0 then reads no pending mask).
+template <uint32_t LOG>
+__global__ void __launch_bounds__(256) sssp_mbox_rearm_kernel(uint64_t* __restrict__ key, MboxView mb, uint32_t* __restrict__ improved,
+                                                              Ctl* __restrict__ ctl, uint32_t n, float tau0, uint2* rs_msgs0,
+                                                              uint2* rs_msgs1, const uint32_t* __restrict__ rs_roffh,
+                                                              uint32_t* __restrict__ rs_abort) {
+  if (ctl->rearm == 0u) return;  // (uniform)
+  mbox_clean<LOG>(key, mb, improved, ctl, nullptr, n, MB_NO_START, tau0, 1u, rs_msgs0, rs_msgs1, rs_roffh, rs_abort);
 }
 
 // minimum over the 64 lanes of a wave (result in every lane): DPP row shifts / broadcasts, no LDS crossbar trips
@@ -322,7 +350,9 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
                                             uint32_t* __restrict__ improved, uint32_t sweep, float tau, uint32_t far_total,
                                             uint32_t near_low, uint32_t profile, uint32_t wl_n, bool waits, uint32_t bfar,
                                             uint4* wl, uint32_t* s_n /*[8]: list sizes [0..2] (level mod 3), found beyond the threshold [3], left waiting [4], least enc(d) written [5]*/,
-                                            uint32_t par_out, const uint32_t* l_roff_out, uint32_t* l_cur, uint32_t* l_cap) {
+                                            uint32_t par_out, const uint32_t* l_roff_out, uint32_t* l_cur, uint32_t* l_cap,
+                                            uint32_t seed_p1 = 0u /*launch 0 of an armed solve, the start's block: start + 1*/,
+                                            uint32_t seed_off = 0u /*... lanes 0 / 1 of the first wave: offsets[start], offsets[start + 1]*/) {
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, MB_HOP_BITS = 32 - LOG, NW_SEG = MB_B;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, j = blockIdx.x, nb = mb.nb;
   const uint32_t sub = tid & 15u, grp = tid >> 4;
@@ -336,10 +366,19 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
   if (head && wl_n)
     for (uint32_t d = tid; d < nb; d += MB_THREADS) l_cap[d] = mb.roff[(size_t)d * nb + j + 1] - mb.roff[(size_t)d * nb + j];
   unsigned long long* const nf = &ctl->nf[sweep % NEAR_RING][(j % NEAR_SHARDS) * NF_STRIDE];
-  for (uint32_t e = tid; e < wl_n; e += MB_THREADS) {  // (a segment longer than the list: the rest keeps waiting)
-    const uint4 en = mb.wl[(size_t)j * NW_SEG + e];
-    if (e < NW_CAP) wl[e] = en;
-    else mbox_make_wait<LOG>(mb, en.x, en.z, false);
+  if (seed_p1) {  // (uniform) re-armed scratch: no set-up launch wrote the start state's entry and key — this workgroup does
+    // (a plain store: weights are not negative wherever the mailbox runs, so no candidate beats the key (0, 0 hops))
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)seed_off, 0), e1 = (uint32_t)__builtin_amdgcn_readlane((int)seed_off, 1);
+    if (tid == 0) {
+      wl[0] = make_uint4(seed_p1 - 1u, b, f32_key(0.0f), min(e1 - b, NW_DEG_SAT));
+      key[seed_p1 - 1u] = (uint64_t)f32_key(0.0f) << 32;
+    }
+  } else {
+    for (uint32_t e = tid; e < wl_n; e += MB_THREADS) {  // (a segment longer than the list: the rest keeps waiting)
+      const uint4 en = mb.wl[(size_t)j * NW_SEG + e];
+      if (e < NW_CAP) wl[e] = en;
+      else mbox_make_wait<LOG>(mb, en.x, en.z, false);
+    }
   }
   if (tid == 0) {
     s_n[0] = min(wl_n, NW_CAP);
@@ -636,7 +675,21 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
   // spot, in the middle of the prologue's loads — the waiting set and its statistics are stored unconditionally instead)
   const uint32_t bmind = mb.blk_mind[j], bfar = mb.blk_far[j];
   const bool wrote_out = mb.wrote[par_out][j] != 0u;
-  const uint32_t wl_n = min(mb.wl_cnt[j], NW_SEG);
+  uint32_t wl_n = min(mb.wl_cnt[j], NW_SEG);
+  // Launch 0 on re-armed scratch (EarlyTail::seed = start + 1; relax_setup queued no set-up launch): every count is zero and the
+  // owner of the start state's block takes its one entry for granted.  The two offsets the entry needs are asked for here, with
+  // the rest of the prologue, by lanes 0 and 1 through their own index (a uniform address would be a scalar load, waited for
+  // on the spot); mbox_narrow builds the entry and stores the key.
+  const bool seed = sweep == 0 && et.seed != 0u && j == (et.seed - 1u) >> MB_LOG;
+  uint32_t seed_off = 0;
+  if (seed) {
+    wl_n = 1u;
+    if (tid < 2) {
+      uint32_t t = tid;
+      asm volatile("" : "+v"(t));
+      seed_off = offsets[et.seed - 1u + t];
+    }
+  }
   unsigned long long kreg[R];
   uint32_t oreg[R], o_last = 0;
   auto bulk_load = [&]() {
@@ -728,7 +781,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
       if (tid == 0) mb.wrote[par_out][j] = 0;
     }
     mbox_narrow<MB_LOG>(offsets, wn, key, mb, ctl, improved, sweep, tau, sc.far_total, near_low, profile, wl_n, bmind != 0xFFFFFFFFu, bfar,
-                (uint4*)lkey, s_nw, par_out, l_roff_out, l_cur, l_base);
+                (uint4*)lkey, s_nw, par_out, l_roff_out, l_cur, l_base, seed ? et.seed : 0u, seed_off);
     MB_STAMP(15);
     return;
   }

@@ -77,6 +77,20 @@ class Context:
         beside a large fused batch instead of behind it (wfst_ctx_set_resident_share)."""
         check(_lib.lib().wfst_ctx_set_resident_share(self._h, int(share)), "wfst_ctx_set_resident_share")
 
+    def rearm_stats(self) -> dict:
+        """Re-armed relaxation scratch of this context (wfst_ctx_get_rearm_stats): solves that parked their cleaned scratch
+        (armed), that started from parked scratch without a set-up launch (adopted), parked scratch given back unused (dropped)."""
+        vals = [C.c_uint64() for _ in range(3)]
+        if not hasattr(_lib.lib(), "wfst_ctx_get_rearm_stats"):  # (WFST_LIB_PATH: a build from before the counters)
+            return dict(armed=0, adopted=0, dropped=0)
+        check(_lib.lib().wfst_ctx_get_rearm_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rearm_stats")
+        return dict(zip(("armed", "adopted", "dropped"), (int(v.value) for v in vals)))
+
+    def trim_pool(self):
+        """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
+        (wfst_ctx_trim_pool).  Synchronises the device."""
+        check(_lib.lib().wfst_ctx_trim_pool(self._h), "wfst_ctx_trim_pool")
+
     def set_tie_order(self, reference_order: bool):
         """shortest_path(nshortest = 1): False = the canonical tie rule (default); True = the reference's own choice among
         tied optima on ACYCLIC inputs (wfst_ctx_set_tie_order)."""

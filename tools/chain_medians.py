@@ -1,31 +1,48 @@
 #!/usr/bin/env python
 """Medians per launch of the shortest-path query's chain, from a rocprofv3 --kernel-trace rocpd database.
 usage: python tools/chain_medians.py <trace_results.db> [label]
-A solve is counted when its relaxation is the predicted three launches: set-up, head (sssp_mbox_kernel, NARROW), the resident
-launch, the NARROW tail launch (sssp_mbox_kernel again), sssp_tail_kernel.  Kernels of other streams (the string batch of the
-bench step) are ignored.  Prints one markdown row: median (min) in us per launch, and first start -> tail end."""
+A solve is counted when its relaxation is the predicted three launches, in one of two shapes:
+  set-up, head (sssp_mbox_kernel, NARROW), the resident launch, the NARROW tail launch (sssp_mbox_kernel again), sssp_tail_kernel
+  head, resident, NARROW tail launch, sssp_tail_kernel          (re-armed scratch: no set-up launch; WFST_SSSP_REARM)
+either of them with sssp_mbox_rearm_kernel behind the tail or without.  Kernels of other streams (the string batch of the bench
+step) are ignored.  Prints one markdown row: median (min) in us per launch (set-up over the solves that have one), first start ->
+tail end, the re-arm launch, and the gap from its end to the next launch of the chain (the next solve's first): the two are on one
+stream, so a re-arm launch that does not hide in the host's gap shows as a gap near zero — the share below 1 us is printed."""
 import sqlite3
 import statistics
 import sys
 
-ORDER = ("sssp_mbox_setup_kernel", "sssp_mbox_kernel", "sssp_mbox_resident_kernel", "sssp_mbox_kernel", "sssp_tail_kernel")
+SETUP, MBOX, RES, TAIL, REARM = ("sssp_mbox_setup_kernel", "sssp_mbox_kernel", "sssp_mbox_resident_kernel", "sssp_tail_kernel",
+                                 "sssp_mbox_rearm_kernel")
+BODY = (MBOX, RES, MBOX, TAIL)
+NAMES = (SETUP, MBOX, RES, TAIL, REARM)
 
 
 def solves(path):
+    """[(set-up row or None, the four rows of BODY, re-arm row or None, start of the chain's next launch or None)]"""
     c = sqlite3.connect(path)
     rows = c.execute("select name, start, end from kernels order by start").fetchall()
-    rows = [(next((k for k in set(ORDER) if k + "<" in n or k + "(" in n), None), s, e) for n, s, e in rows]
+    rows = [(next((k for k in NAMES if k + "<" in n or k + "(" in n), None), s, e) for n, s, e in rows]
     rows = [r for r in rows if r[0]]
     out, cur = [], []
-    for r in rows:
-        if r[0] == ORDER[0]:
+    for i, r in enumerate(rows):
+        if r[0] == REARM:
+            continue  # (attached to the solve in front of it below)
+        if r[0] == SETUP:
             cur = []
         cur.append(r)
-        if r[0] == ORDER[-1]:
-            if tuple(k for k, _, _ in cur) == ORDER:
-                out.append(cur)
+        if r[0] == TAIL:
+            names = tuple(k for k, _, _ in cur)
+            if names in (BODY, (SETUP,) + BODY):
+                rearm = rows[i + 1] if i + 1 < len(rows) and rows[i + 1][0] == REARM else None
+                nxt = rows[i + 2][1] if rearm and i + 2 < len(rows) else None
+                out.append((cur[0] if names[0] == SETUP else None, cur[-4:], rearm, nxt))
             cur = []
     return out
+
+
+def cell(v):
+    return f"{statistics.median(v):.2f} ({min(v):.2f})" if v else "-"
 
 
 def main():
@@ -35,9 +52,15 @@ def main():
         print(f"| {label} | only {len(sv)} solves of the predicted shape |")
         return
     sv = sv[len(sv) // 8:]  # (the first solves run while the clocks ramp)
-    cols = [[(e - s) / 1e3 for s, e in ((x[i][1], x[i][2]) for x in sv)] for i in range(len(ORDER))]
-    cols.append([(x[-1][2] - x[0][1]) / 1e3 for x in sv])
-    print(f"| {label} | {len(sv)} | " + " | ".join(f"{statistics.median(c):.2f} ({min(c):.2f})" for c in cols) + " |")
+    us = lambda r: (r[2] - r[1]) / 1e3
+    setup = [us(s) for s, _, _, _ in sv if s]
+    cols = [[us(b[i]) for _, b, _, _ in sv] for i in range(4)]
+    whole = [(b[-1][2] - (s or b[0])[1]) / 1e3 for s, b, _, _ in sv]
+    rearm = [us(r) for _, _, r, _ in sv if r]
+    gap = [(nx - r[2]) / 1e3 for _, _, r, nx in sv if r and nx is not None]
+    tight = f", {100.0 * sum(g < 1.0 for g in gap) / len(gap):.0f} % below 1 us" if gap else ""
+    print(f"| {label} | {len(sv)} | {len(setup)} with set-up: {cell(setup)} | " + " | ".join(cell(c) for c in cols) +
+          f" | {cell(whole)} | {len(rearm)} re-armed: {cell(rearm)} | {cell(gap)}{tight} |")
 
 
 if __name__ == "__main__":

@@ -22,6 +22,7 @@ print(f"best of {reps}: {best*1e3:.3f} ms, sweeps {ctx.stats()['sweeps']} (after
 # the same solves with the relaxation chain bracketed by HIP events (profiling mode 2): under `rocprofv3 --kernel-trace` this
 # process then holds BOTH clocks for the same launches — the events' chain time and the trace's per-kernel durations
 import statistics
+print("rearm_stats", ctx.rearm_stats())
 ctx.set_profiling(2)
 chain = []
 for _ in range(max(5, reps // 2)):

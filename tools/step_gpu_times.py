@@ -46,6 +46,7 @@ for it in range(30):
     f0.record(s1); sp_job = dt.shortest_path_begin(); f1.record(s1); sp_job.finish(); torch.cuda.synchronize()
     al.append([e0.elapsed_time(e1) * 1e3, f0.elapsed_time(f1) * 1e3])
 al = np.median(np.array(al[5:]), axis=0)
+print("rearm_stats (relaxation context, all steps)", ctx.rearm_stats())
 print("alone: batch stream %.1f us | relaxation stream %.1f us   (%d acceptors, resident share %s)" % (al[0], al[1], B, sys.argv[3] if len(sys.argv) > 3 else "0"))
 print("host: batch begin %.1f | sp begin %.1f | batch finish %.1f | sp finish %.1f | step %.1f us" % tuple(r[:5]))
 print("gpu : batch stream %.1f us | relaxation stream %.1f us | relaxation starts %.1f us after the batch | relaxation ends %.1f us after the batch started" % tuple(r[5:]))
