@@ -426,7 +426,8 @@ wfst_status wfst_fst_project(wfst_ctx* ctx, wfst_fst* fst, int project_output);
  *        (lookahead_matchers/label_lookahead_relabeler.rs:27-41, cmds/compose.rs:151): a NEW handle; labels fst1 never
  *        emits get fresh indices, the map inside `la` grows as the reference's does.
  *      wfst_compose_lookahead = the composition itself on the GPU; output numbered like LazyFst::compute, not connected.
- *      The handle owns the relabelled fst1 (wfst_lookahead_fst1 lends it). ---- */
+ *      The handle owns the relabelled fst1 (wfst_lookahead_fst1 lends it: it must not be edited in place with
+ *      wfst_fst_tr_sort, wfst_fst_project or wfst_fst_set_start, the reachability data describes it as it is). ---- */
 typedef struct wfst_lookahead wfst_lookahead;
 wfst_status wfst_lookahead_create(wfst_ctx* ctx, const wfst_fst* fst1, wfst_lookahead** out);
 wfst_status wfst_lookahead_relabel(wfst_lookahead* la, const wfst_fst* fst2, wfst_fst** out);

@@ -507,14 +507,23 @@ void upload_many(wfst_ctx* ctx, size_t n, const uint32_t* n_states, const int64_
   if (tot_arcs)
     HIP_CHECK(hipMemcpyAsync(const_cast<wfst_tr*>(all.arcs), arcs_cat, tot_arcs * sizeof(wfst_tr), hipMemcpyHostToDevice,
                              ctx->stream));
-  // validation on the host (these are small FSTs: acceptors), derive arrays on the device
+  // validation on the host (these are small FSTs: acceptors), derive arrays on the device; the weight statistics of each
+  // FST (what derive_single reads back for a single upload: has_negative keeps the one-wave searches off it) in the same pass
+  std::vector<WeightStats> hws(n, WeightStats{0.0, 0ull, 0u, 0u});
   for (size_t i = 0; i < n; ++i) {
     const uint32_t* off = offsets_cat + state_base[i] + i;
     for (uint32_t s = 0; s < n_states[i]; ++s)
       if (off[s + 1] < off[s]) throw Error("invalid FST in batch: offsets are not non-decreasing");
     const wfst_tr* a = arcs_cat + arc_base[i];
-    for (uint32_t e = 0; e < off[n_states[i]]; ++e)
+    for (uint32_t e = 0; e < off[n_states[i]]; ++e) {
       if (a[e].nextstate >= n_states[i]) throw Error("invalid FST in batch: an arc's nextstate is >= num_states");
+      const float w = a[e].weight;
+      if (w < INF && w > -INF) {
+        hws[i].sum += (double)w;
+        hws[i].count++;
+        if (w < 0.0f) hws[i].negative = 1u;
+      }
+    }
   }
   {
     DBuf<uint32_t> err(*ctx->pool, 1);
@@ -552,6 +561,8 @@ void upload_many(wfst_ctx* ctx, size_t n, const uint32_t* n_states, const int64_
     f->dev.wn = all.wn + arc_base[i];
     f->dev.srec = all.srec + state_base[i];
     f->has_dev = true;
+    f->mean_weight = hws[i].count ? (float)(hws[i].sum / (double)hws[i].count) : 0.0f;
+    f->has_negative = hws[i].negative != 0;
     f->is_string = n_states[i] <= 65536 && detect_string(n_states[i], starts[i], offsets_cat + state_base[i] + i,
                                                          arcs_cat + arc_base[i], finals_cat + state_base[i]);
     keep_small_host_copy(f.get(), offsets_cat + state_base[i] + i, arcs_cat + arc_base[i], finals_cat + state_base[i]);

@@ -114,3 +114,35 @@ def check_nbest_against_brute_force(result_flat, input_flat, n, what=""):
         ws = have.get((strip(il), strip(ol)))
         assert ws is not None, f"{what}: the result holds a string the input does not accept: {il} / {ol}"
         assert min(abs(w - x) for x in ws) <= 1e-4, f"{what}: path {il} has weight {w}, the input gives {ws}"
+
+
+def walk_labels(rng, flat, state, side, length):
+    """labels (`side`: ilabel|olabel) along a random walk of at most `length` labelled steps from `state`; epsilons are
+    followed without being recorded.  At least one label (1 where the walk finds none)."""
+    off, arcs = flat["offsets"], flat["arcs"]
+    labs, s = [], int(state)
+    for _ in range(4 * length):
+        if len(labs) == length or off[s] == off[s + 1]:
+            break
+        a = arcs[int(rng.integers(off[s], off[s + 1]))]
+        if int(a[side]):
+            labs.append(int(a[side]))
+        s = int(a["nextstate"])
+    return np.array(labs or [1], dtype=np.uint32)
+
+
+def linear_transducer_flat(rng, length, sigma):
+    """A chain like utils::acceptor's, but a transducer: every arc has ilabel != olabel, both non-epsilon."""
+    f = synth.linear_acceptor_flat(rng.integers(1, sigma + 1, length))
+    f["arcs"]["olabel"] = f["arcs"]["ilabel"] % sigma + 1
+    f["arcs"]["weight"] = (rng.integers(0, 2560, length) / 512).astype(np.float32)
+    f["props"] = 0
+    return f
+
+
+def one_sided_eps_transducer(rng, n_states, max_fanout, sigma, eps_side, p_eps=0.2, p_final=0.08, sort="ilabel"):
+    """Cyclic transducer with epsilons on `eps_side` (ilabel|olabel) only; arcs in `sort` order, sortedness stated truthfully."""
+    f = random_fst_flat(rng, n_states, max_fanout, sigma, p_eps_i=p_eps if eps_side == "ilabel" else 0.0,
+                        p_eps_o=p_eps if eps_side == "olabel" else 0.0, p_final=p_final, sort=sort, min_fanout=1)
+    assert np.any(f["arcs"][eps_side] == 0)
+    return f
