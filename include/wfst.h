@@ -393,6 +393,41 @@ wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
  *      diagnostics of how the scratch sizes were climbed; any pointer after ctx may be NULL. */
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap);
+/* ---- rm_epsilon of n FSTs in one call: outs[i] is a NEW handle, bit-identical (offsets, arcs with their weights' bit
+ *      patterns, finals, start state, property word) to what wfst_rm_epsilon(ctx, fsts[i], ..) returns.  The same handle may
+ *      appear more than once in fsts.  n == 0: OK.  The inputs are left exactly as they are, their cached derived data and
+ *      property words included.  An item without a start state is returned as the single call returns it (a copy), and an
+ *      item without states never occupies a workgroup; both count as in_kernel == 1.
+ *      One workgroup per item: it runs every stage of the single call on its item inside the item's slice of one slab —
+ *      noneps_in, the epsilon depths by peeling the sinks of the epsilon graph, the rewrites depth by depth (one thread per
+ *      state, a barrier between depths), the CSR of the result with the facts for the property word, connect.
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when
+ *        - item i has at most 4096 states and at most 16384 arcs,
+ *        - its epsilon graph (the 0:0 arcs) has no cycle, a self loop being one, and
+ *        - every state the reference rewrites (the start state and every state with a non-epsilon incoming arc) fits the
+ *          last rung of the single call's one-thread kernel: a closure of at most 64 states, at most 128 entries on the
+ *          depth-first stack, at most 128 arcs after combining (64 / 128 / 128).
+ *      The kernel finds whichever condition fails and leaves an exit code; in_kernel[i] == 0: the item went through
+ *      wfst_rm_epsilon unchanged.
+ *      Launches: ONE launch for every item that is still open.  The first launch's slices are sized on the host from
+ *      n_states and n_arcs alone (nothing is read from the device): an arc arena of 2 * n_arcs + 64 arcs, so every item whose
+ *      result before connect has no more arcs than its input (and up to twice as many) finishes in the first launch.  An item whose arena proves too small
+ *      reports what it needed and runs again in the next launch of the same call with an arena at least twice as large; at
+ *      most 64 launches.  The number of launches depends neither on n nor on any item's epsilon depth.  Per launch: the
+ *      kernel and one read-back of the control blocks; per call one adoption of all kernel results out of the slabs.
+ *      The slices of one launch may take 8 GiB together: a list that needs more is KO before that launch ("split the list").
+ *      WFST_RM_EPSILON_BATCH_ARENA=min (tests) makes the first launch's arenas as small as the kernel allows, so that every
+ *      item with arcs grows; any other value is KO.
+ *      KO — every argument is checked before anything is launched: NULL pointers, NULL list entries ("item <i>: null FST
+ *      in batch"), a handle of another device or context — and whenever wfst_rm_epsilon would be KO for an item: that
+ *      call's message for the LOWEST failing index, prefixed by "item <i>: ".  On any KO every outs[i] is NULL, nothing is
+ *      leaked and the context works afterwards.  The counters of wfst_ctx_get_rm_epsilon_stats are not specified after a
+ *      batch call. ---- */
+wfst_status wfst_rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_rm_epsilon_batch call of ctx: launches of the batch kernel, items it finished (in_kernel == 1), items that
+ *      went through the single-FST path.  All 0 after a KO before any launch. */
+wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                uint64_t* items_single);
 
 /* ---- the re-armed scratch of the single-shortest-path relaxation: a predicted mailbox solve has its scratch
  *      cleaned on the device BEHIND its result and parks it on the context; the next solve with the same graph structure and

@@ -19,7 +19,7 @@
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
 //   determinize_with_distance(&fst, &in_dist, delta)             determinize_with_distance(fst, in_dist, delta)   determinize_static.rs:24-39
 //   (many acceptors in one call)                                 determinize_batch / determinize_with_distance_batch
-//                                                                minimize_batch
+//                                                                minimize_batch, rm_epsilon_batch
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
@@ -346,6 +346,24 @@ inline std::vector<VectorFst> minimize_batch(const std::vector<VectorFst>& fsts,
   }
   const wfst_minimize_config cfg{config.delta, config.allow_nondet ? 1u : 0u};
   check(wfst_minimize_batch(Context::current().get(), hs.data(), hs.size(), &cfg, os.data(), nullptr));
+  std::vector<VectorFst> res;
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    out[i].h = os[i];
+    res.push_back(detail::download(out[i]));
+  }
+  return res;
+}
+// rm_epsilon of many FSTs in one call (wfst_rm_epsilon_batch): one workgroup per FST, the step in front of
+// determinize_batch and minimize_batch; the results (the arguments are left as they are)
+inline std::vector<VectorFst> rm_epsilon_batch(const std::vector<VectorFst>& fsts) {
+  std::vector<detail::DeviceFst> in(fsts.size()), out(fsts.size());
+  std::vector<const wfst_fst*> hs(fsts.size());
+  std::vector<wfst_fst*> os(fsts.size(), nullptr);
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    detail::upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+  }
+  check(wfst_rm_epsilon_batch(Context::current().get(), hs.data(), hs.size(), os.data(), nullptr));
   std::vector<VectorFst> res;
   for (size_t i = 0; i < fsts.size(); ++i) {
     out[i].h = os[i];

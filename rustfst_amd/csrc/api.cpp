@@ -770,6 +770,28 @@ wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) 
   });
 }
 
+// rm_epsilon of n FSTs (one workgroup each); every argument is checked before anything is launched
+wfst_status wfst_rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    if (outs)
+      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    if (ctx) ctx->rm_batch_launches = ctx->rm_batch_in_kernel = ctx->rm_batch_single = 0;
+    if (n == 0) return;
+    check_batch_args(ctx, fsts, n, outs);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    rm_epsilon_batch(ctx, fsts, n, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                uint64_t* items_single) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (launches) *launches = ctx->rm_batch_launches;
+    if (items_in_kernel) *items_in_kernel = ctx->rm_batch_in_kernel;
+    if (items_single) *items_single = ctx->rm_batch_single;
+  });
+}
+
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap) {
   return wrap([&] {

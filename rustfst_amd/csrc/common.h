@@ -240,6 +240,8 @@ struct wfst_ctx {
   uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
   // the last wfst_minimize_batch call (wfst_ctx_get_minimize_batch_stats)
   uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
+  // the last wfst_rm_epsilon_batch call (wfst_ctx_get_rm_epsilon_batch_stats)
+  uint64_t rm_batch_launches = 0, rm_batch_in_kernel = 0, rm_batch_single = 0;
   // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
@@ -504,6 +506,12 @@ wfst_fst* connect_and_adopt(wfst_ctx* ctx, uint32_t n, int64_t start, const uint
                             bool all_accessible, uint64_t out_props);
 // rm_epsilon.hip
 wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f);
+// ... its property word from the input's stored word and the facts of the added arcs (1 ilabel != olabel | 2 nextstate <=
+// its state | 4 an arc was added), and its result when connect leaves nothing
+uint64_t rm_epsilon_word(uint64_t in, uint32_t facts);
+wfst_fst* rm_epsilon_empty(wfst_ctx* ctx, uint64_t word);
+// rm_epsilon_batch.hip: n FSTs in one call, one workgroup each (new handles; on a throw every outs[i] is null)
+void rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
 // push.hip: shortest_distance(fst, reverse) with the reference's Vec length, reweight, push_weights (new handles)
 void shortest_distance_ex(wfst_ctx* ctx, const wfst_fst* f, bool reverse, float* distance, uint32_t* len);
 wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials, uint64_t n_potentials, uint32_t reweight_type);

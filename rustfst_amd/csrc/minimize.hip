@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "fst_props.h"
+#include "wg_ops.h"
 
 namespace wfst {
 
@@ -64,10 +65,6 @@ constexpr uint64_t HI32 = 0xFFFFFFFF00000000ull;
 constexpr uint32_t C_LO = 0, C_HI = 1, C_TAIL = 2, C_LEVEL = 3, C_CURMAX = 4, C_NEXTMAX = 5, C_NBIG = 6, C_WORDS = 8;
 
 __device__ inline uint32_t wkey(float f) { return f == 0.0f ? 0u : __float_as_uint(f); }  // -0.0 == +0.0
-// words that other lanes of the SAME launch wrote (narrow regime: level after level in one workgroup): device-scope
-// accesses, which do not stay in a compute unit's vector L1
-__device__ inline uint32_t ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void stg(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline uint64_t ld64(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -213,16 +210,6 @@ __global__ void __launch_bounds__(TPB) enc_facts_kernel(const uint32_t* __restri
 }
 
 // ---------------------------------------------------------------- transpose
-__device__ void transpose_fill(const uint32_t* __restrict__ off, const wfst_tr* __restrict__ arcs, uint32_t n,
-                               const uint32_t* __restrict__ roff, uint32_t* __restrict__ cursor, uint32_t* __restrict__ rsrc,
-                               uint32_t tid, uint32_t nth) {
-  const uint32_t lane = tid & 15u;
-  for (uint32_t s = tid >> 4; s < n; s += nth >> 4)
-    for (uint32_t i = off[s] + lane; i < off[s + 1]; i += 16) {
-      const uint32_t t = arcs[i].nextstate;
-      rsrc[roff[t] + atomicAdd(&cursor[t], 1u)] = s;
-    }
-}
 __global__ void __launch_bounds__(TPB) transpose_fill_kernel(const uint32_t* __restrict__ off, const wfst_tr* __restrict__ arcs,
                                                              uint32_t n, const uint32_t* __restrict__ roff,
                                                              uint32_t* __restrict__ cursor, uint32_t* __restrict__ rsrc) {
@@ -908,7 +895,6 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
 // (two frontier searches) and tr_sort's stable order (a rank sort fused with connect's compaction).
 namespace {
 
-constexpr uint32_t MB_TPB = 256;            // 4 waves: small lattices leave no more lanes busy, and 8 workgroups fit a compute unit
 constexpr uint32_t MB_MAX_STATES = 4096;    // the in_kernel rule (include/wfst.h)
 constexpr uint32_t MB_MAX_ARCS = 16384;
 constexpr size_t MB_MAX_SLAB = (size_t)8 << 30;  // all slices of a call together (include/wfst.h); beyond: KO before any launch
@@ -961,87 +947,6 @@ struct MbItem {
 
 __device__ inline float ldf(const float* p) { return __uint_as_float(ld((const uint32_t*)p)); }
 __device__ inline void stf(float* p, float v) { stg((uint32_t*)p, __float_as_uint(v)); }
-// every thread of the workgroup: what was written before is visible after
-__device__ inline void wg_bar() {
-  __threadfence();
-  __syncthreads();
-}
-__device__ inline void wg_fill(uint32_t* p, uint32_t count, uint32_t v) {
-  for (uint32_t i = threadIdx.x; i < count; i += MB_TPB) p[i] = v;
-}
-__device__ inline void wg_fill64(unsigned long long* p, uint32_t count, unsigned long long v) {
-  for (uint32_t i = threadIdx.x; i < count; i += MB_TPB) p[i] = v;
-}
-// out[i] = in[0] + .. + in[i - 1] for i < count (in == out allowed); returns the sum of all.  part: MB_TPB + 1 words of LDS
-__device__ uint32_t wg_exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t count, uint32_t* part) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t chunk = (count + MB_TPB - 1) / MB_TPB;
-  const uint32_t b = min(count, tid * chunk), e = min(count, b + chunk);
-  uint32_t sum = 0;
-  for (uint32_t i = b; i < e; ++i) sum += ld(&in[i]);
-  part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t run = 0;
-    for (uint32_t t = 0; t < MB_TPB; ++t) {
-      const uint32_t v = part[t];
-      part[t] = run;
-      run += v;
-    }
-    part[MB_TPB] = run;
-  }
-  __syncthreads();
-  uint32_t run = part[tid];
-  for (uint32_t i = b; i < e; ++i) {
-    const uint32_t v = ld(&in[i]);
-    stg(&out[i], run);
-    run += v;
-  }
-  const uint32_t total = part[MB_TPB];
-  wg_bar();
-  return total;
-}
-// transpose of (off, arcs) with n states into (roff, rsrc); rcnt: n + 1 words of scratch
-__device__ void wg_transpose(const uint32_t* off, const wfst_tr* arcs, uint32_t n, uint32_t E, uint32_t* roff, uint32_t* rcnt,
-                             uint32_t* rsrc, uint32_t* part) {
-  wg_fill(rcnt, n + 1, 0u);
-  wg_bar();
-  for (uint32_t i = threadIdx.x; i < E; i += MB_TPB) atomicAdd(&rcnt[arcs[i].nextstate], 1u);
-  wg_bar();
-  wg_exclusive_scan(rcnt, roff, n + 1, part);
-  wg_fill(rcnt, n + 1, 0u);
-  wg_bar();
-  transpose_fill(off, arcs, n, roff, rcnt, rsrc, threadIdx.x, MB_TPB);
-  wg_bar();
-}
-// frontier search: queue[0 .. q[2]) holds the marked seeds; every state reached over the adjacency (off, arcs' nextstate)
-// or, with arcs == nullptr, (off, src) is marked and queued once.  q: three words of LDS (level begin, level end, tail).
-__device__ void wg_search(const uint32_t* off, const wfst_tr* arcs, const uint32_t* src, uint32_t* mark, uint32_t* queue,
-                          uint32_t* q) {
-  const uint32_t tid = threadIdx.x, lane = tid & 15u;
-  if (tid == 0) {
-    q[0] = 0;
-    q[1] = q[2];
-  }
-  __syncthreads();
-  for (;;) {
-    const uint32_t lo = q[0], hi = q[1];
-    if (lo == hi) break;
-    for (uint32_t k = lo + (tid >> 4); k < hi; k += MB_TPB >> 4) {
-      const uint32_t s = ld(&queue[k]);
-      for (uint32_t i = off[s] + lane; i < off[s + 1]; i += 16) {
-        const uint32_t t = arcs ? arcs[i].nextstate : src[i];
-        if (ld(&mark[t]) == 0u && atomicExch(&mark[t], 1u) == 0u) stg(&queue[atomicAdd(&q[2], 1u)], t);
-      }
-    }
-    wg_bar();
-    if (tid == 0) {
-      q[0] = hi;
-      q[1] = q[2];
-    }
-    __syncthreads();
-  }
-}
 // the state's kept arcs (those into kept states) to their places in tr_sort's stable order: rank by (label key, position)
 // among the kept ones.  Lane `lane` of `g` lanes.
 __device__ void place_sorted(const wfst_tr* sarcs, uint32_t b, uint32_t deg, const uint32_t* keep, const uint32_t* new_id,

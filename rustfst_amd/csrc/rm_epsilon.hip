@@ -42,129 +42,27 @@
 
 #include "common.h"
 #include "fst_props.h"
+#include "rm_expand.h"
 
 namespace wfst {
 
 namespace {
 
-struct RmCaps {
-  uint32_t C;  // closure states
-  uint32_t K;  // depth-first stack entries
-  uint32_t A;  // arcs of the rewritten state
-};
-__host__ __device__ inline size_t rm_arcs_offset(const RmCaps& c) { return ((size_t)c.C * 12 + (size_t)c.K * 4 + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t rm_slice_bytes(const RmCaps& c) { return rm_arcs_offset(c) + (size_t)c.A * 16; }
-
-__device__ __forceinline__ bool is_eps(const wfst_tr& t) { return t.ilabel == 0u && t.olabel == 0u; }  // EpsilonTrFilter
-
-struct RmView {  // the FST as the reference's loop sees it at this moment
-  const uint32_t* offsets;
-  const wfst_tr* arcs;
-  const uint32_t* done;                 // state already rewritten
-  const uint32_t* cnt;                  // its new arc count
-  const unsigned long long* arc_ptr;    // and where its new arcs are
-  __device__ const wfst_tr* trs(uint32_t q, uint32_t* n) const {
-    if (done[q]) {
-      *n = cnt[q];
-      return (const wfst_tr*)arc_ptr[q];
-    }
-    *n = offsets[q + 1] - offsets[q];
-    return arcs + offsets[q];
-  }
-};
-
-// RmEpsilonState::expand + the rewrite of the listed states; status[i]: 0 done, 1 slice too small
+// RmEpsilonState::expand + the rewrite of the listed states (rm_expand.h); status[i]: 0 done, 1 slice too small
 __global__ void rm_expand(RmView v, const uint32_t* __restrict__ list, uint32_t n_list, RmCaps caps, char* __restrict__ scratch,
                           uint32_t* __restrict__ new_cnt, float* __restrict__ new_fin, unsigned long long* __restrict__ new_ptr,
                           const float* __restrict__ fin, uint32_t* __restrict__ status) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_list) return;
-  const uint32_t s = list[i];
   char* slice = scratch + (size_t)i * rm_slice_bytes(caps);
-  uint32_t* cl = (uint32_t*)slice;  // closure states, in discovery order
-  float* dist = (float*)(slice + (size_t)caps.C * 4);
-  uint32_t* vis = (uint32_t*)(slice + (size_t)caps.C * 8);
-  uint32_t* stack = (uint32_t*)(slice + (size_t)caps.C * 12);
-  wfst_tr* out = (wfst_tr*)(slice + rm_arcs_offset(caps));
   status[i] = 1u;  // (until done)
-  // 1. closure and distances over the epsilon arcs as they are now
-  uint32_t nc = 1;
-  cl[0] = s;
-  dist[0] = 0.0f;
-  for (uint32_t iter = 0;; ++iter) {
-    bool changed = false;
-    for (uint32_t k = 0; k < nc; ++k) {
-      const float dk = dist[k];
-      uint32_t nq;
-      const wfst_tr* tq = v.trs(cl[k], &nq);
-      for (uint32_t a = 0; a < nq; ++a) {
-        const wfst_tr tr = tq[a];
-        if (!is_eps(tr)) continue;
-        uint32_t j = 0;
-        while (j < nc && cl[j] != tr.nextstate) ++j;
-        if (j == nc) {
-          if (nc == caps.C) return;
-          cl[nc] = tr.nextstate;
-          dist[nc] = INF;
-          ++nc;
-          changed = true;
-        }
-        const float cand = wtimes(dk, tr.weight);
-        if (cand < dist[j]) {
-          dist[j] = cand;
-          changed = true;
-        }
-      }
-    }
-    if (!changed) break;
-    if (iter > nc + 1u) break;  // a negative epsilon cycle: the reference would not terminate either; stop improving
-  }
-  // 2. the depth-first walk of the closure: arcs and the final weight in visiting order
-  for (uint32_t k = 0; k < nc; ++k) vis[k] = 0u;
-  uint32_t sp = 0, na = 0;
-  stack[sp++] = 0u;  // (indices into cl)
-  float final_w = INF;
-  while (sp) {
-    const uint32_t k = stack[--sp];
-    if (vis[k]) continue;
-    vis[k] = 1u;
-    const uint32_t q = cl[k];
-    const float dq = dist[k];
-    uint32_t nq;
-    const wfst_tr* tq = v.trs(q, &nq);
-    for (uint32_t a = 0; a < nq; ++a) {
-      wfst_tr tr = tq[a];
-      tr.weight = wtimes(dq, tr.weight);
-      if (is_eps(tr)) {
-        uint32_t j = 0;
-        while (cl[j] != tr.nextstate) ++j;  // (in the closure since step 1)
-        if (!vis[j]) {
-          if (sp == caps.K) return;
-          stack[sp++] = j;
-        }
-      } else {
-        uint32_t j = 0;
-        while (j < na && !(out[j].ilabel == tr.ilabel && out[j].olabel == tr.olabel && out[j].nextstate == tr.nextstate)) ++j;
-        if (j < na) {
-          if (tr.weight < out[j].weight) out[j].weight = tr.weight;  // plus_assign at the first occurrence
-        } else {
-          if (na == caps.A) return;
-          out[na++] = tr;
-        }
-      }
-    }
-    const float f = wtimes(dq, fin[q]);
-    final_w = f < final_w ? f : final_w;
-  }
-  for (uint32_t a = 0; a < na / 2; ++a) {  // trs.into_iter().rev() (rm_epsilon_static.rs:125)
-    const wfst_tr t = out[a];
-    out[a] = out[na - 1 - a];
-    out[na - 1 - a] = t;
-  }
+  uint32_t na;
+  float final_w;
+  if (!rm_expand_state(v, list[i], caps, slice, fin, &na, &final_w)) return;
   // (published to later launches by rm_publish: nothing of this launch may read it)
   new_cnt[i] = na;
   new_fin[i] = final_w;
-  new_ptr[i] = (unsigned long long)out;
+  new_ptr[i] = (unsigned long long)(slice + rm_arcs_offset(caps));
   status[i] = 0u;
 }
 
@@ -556,8 +454,32 @@ void rm_schedule(const wfst_fst* f, const std::vector<uint8_t>& noneps_in, std::
 
 }  // namespace
 
-wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f) {
+// property word of the result from the input's stored word and the facts of rm_write (1 | 2 | 4): every rewrite applies
+// delete_trs_properties, add_tr over its new arcs and set_final; what rmepsilon_properties(.., delayed = false) then reads are
+// ACCEPTOR / ACYCLIC / INITIAL_ACYCLIC / TOP_SORTED, all of them functions of the three facts; connect finishes with
+// delete_states_properties | ACCESSIBLE | COACCESSIBLE
+uint64_t rm_epsilon_word(uint64_t in, uint32_t facts) {
   using namespace props;
+  const bool acceptor = (in & ACCEPTOR) && !(facts & 1u);
+  const bool top = (in & TOP_SORTED) && !(facts & 2u);
+  uint64_t out = NO_EPSILONS;
+  if (acceptor) out |= ACCEPTOR | NO_I_EPSILONS | NO_O_EPSILONS;
+  if (facts & 4u) {
+    if (top) out |= ACYCLIC | INITIAL_ACYCLIC;  // add_tr keeps them only next to TOP_SORTED (mutate_properties.rs:93-99)
+  } else {
+    out |= (ACYCLIC | INITIAL_ACYCLIC) & in;
+  }
+  if (top) out |= TOP_SORTED;
+  return delete_states(out) | ACCESSIBLE | COACCESSIBLE;
+}
+// ... and the result when connect leaves nothing (connect_and_adopt's own answer then): no states, no start state, that word
+wfst_fst* rm_epsilon_empty(wfst_ctx* ctx, uint64_t word) {
+  HostCsr hc;
+  hc.offsets.push_back(0);
+  return make_host_fst(ctx, 0, -1, word, std::move(hc));
+}
+
+wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f) {
   ensure_device(const_cast<wfst_fst*>(f));
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
@@ -660,21 +582,7 @@ wfst_fst* rm_epsilon_fst(wfst_ctx* ctx, const wfst_fst* f) {
   rm_write<<<(n + 255) / 256, 256, 0, st>>>(off.p, cnt.p, arc_ptr.p, new_arcs.p, n, facts.p);
   HIP_CHECK(hipGetLastError());
   h[1] = read_u32(ctx, facts.p);
-  // property word: every rewrite applies delete_trs_properties, add_tr over its new arcs and set_final; what
-  // rmepsilon_properties(.., delayed = false) then reads are ACCEPTOR / ACYCLIC / INITIAL_ACYCLIC / TOP_SORTED, all of
-  // them functions of the three facts; connect finishes with delete_states_properties | ACCESSIBLE | COACCESSIBLE
-  const uint64_t in = f->props;
-  const bool acceptor = (in & ACCEPTOR) && !(h[1] & 1u);
-  const bool top = (in & TOP_SORTED) && !(h[1] & 2u);
-  uint64_t out = NO_EPSILONS;
-  if (acceptor) out |= ACCEPTOR | NO_I_EPSILONS | NO_O_EPSILONS;
-  if (h[1] & 4u) {
-    if (top) out |= ACYCLIC | INITIAL_ACYCLIC;  // add_tr keeps them only next to TOP_SORTED (mutate_properties.rs:93-99)
-  } else {
-    out |= (ACYCLIC | INITIAL_ACYCLIC) & in;
-  }
-  if (top) out |= TOP_SORTED;
-  out = delete_states(out) | ACCESSIBLE | COACCESSIBLE;
+  const uint64_t out = rm_epsilon_word(f->props, h[1]);
   return connect_and_adopt(ctx, n, f->start, off.p, new_arcs.p, fin.p, /*all_accessible=*/false, out);
 }
 

@@ -763,6 +763,33 @@ def minimize_batch_stats(ctx: Optional[Context] = None) -> dict:
     return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
 
 
+def rm_epsilon_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
+    """[f.rm_epsilon() for f in fsts] as ONE call (wfst_rm_epsilon_batch): one workgroup per FST, and a number of launches
+    that depends neither on the length of the list nor on any item's epsilon depth — the step in front of
+    determinize_batch and minimize_batch for the many small lattices of a decoding batch.  return_in_kernel: also the uint8
+    array that says which items the batch kernel finished (0: more than 4096 states or 16384 arcs, an epsilon cycle, or a
+    rewritten state beyond a closure of 64 states, 128 stack entries or 128 arcs sent the item through the single-FST
+    path).  Any item that f.rm_epsilon would refuse raises WfstError with "item <i>: " in front of that call's message."""
+    n = len(fsts)
+    if n == 0:
+        return ([], np.zeros(0, np.uint8)) if return_in_kernel else []
+    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
+    outs = (C.c_void_p * n)()
+    flags = np.zeros(n, np.uint8)
+    check(_lib.lib().wfst_rm_epsilon_batch(ctx._h, _handles(fsts), n, outs, flags.ctypes.data), "wfst_rm_epsilon_batch")
+    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
+    return (res, flags) if return_in_kernel else res
+
+
+def rm_epsilon_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last rm_epsilon_batch call of ctx (wfst_ctx_get_rm_epsilon_batch_stats)."""
+    ctx = ctx or default_context()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(_lib.lib().wfst_ctx_get_rm_epsilon_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
+          "wfst_ctx_get_rm_epsilon_batch_stats")
+    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+
+
 def _take_floats(ptr, count):
     out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(count,)).copy() if count else np.zeros(0, np.float32)
     _lib.lib().wfst_bytes_destroy(ptr)
