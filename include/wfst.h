@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -578,6 +578,34 @@ wfst_status wfst_vec_fst_from_device(const wfst_fst* fst, wfst_vec_fst** out);
  * results as n calls of wfst_shortest_path. */
 wfst_status wfst_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_shortest_path_config* cfg,
                                      wfst_fst** outs);
+/* ---- which path answered the small shortest-path queries of ctx: the counters of the two one-wavefront-per-FST kernels.
+ *      An item that a kernel does not take, or hands back, goes through the general path and gives the same FST.
+ *      nshortest == 1 (sp1_wave_kernel).  Offered to the kernel: an item of a wfst_shortest_path_batch list of at least two
+ *      FSTs with at most 4096 states and at most 16384 arcs and no negative arc weight; a lone wfst_shortest_path (or a list
+ *      of one) with at most 4096 states and at most 2048 arcs and no negative arc weight; with unique = true and
+ *      nshortest > 1 (the kernel then exports distances and arrays) an item with a start state of a list of at least two,
+ *      at most 4096 states and at most 16384 arcs.  Never with WFST_SP1_DEVICE=0 (except the export), with the reference
+ *      tie order, or while a fused batch is in flight.  An item of at most 2048 states and at most 4096 arcs runs staged,
+ *      offsets and arcs in LDS; a larger one reads them from memory.  The three n1 values describe the LAST launch of that
+ *      kernel since the last wfst_shortest_path / wfst_shortest_path_batch call on ctx began — a batch, a lone call or an
+ *      export; when an item is handed back, the lone call that then answers it may launch again —:
+ *        n1_in_kernel    items the kernel answered (an item without states or start state included),
+ *        n1_staged       those of them that ran with their arcs in LDS,
+ *        n1_handed_back  items given to the kernel that came back with a non-zero status.
+ *      nshortest > 1, unique = false (nbest_wave_kernel).  Offered: an item with a start state, at most 4096 states, at most
+ *      8192 arcs, no negative arc weight, when nshortest <= 64 and WFST_NBEST_DEVICE is not 0.  The search tree of every item
+ *      of the launch has room for T = min(16384, max(2048, 2 * nshortest * (max_n + 8))) entries, max_n = the most states of
+ *      an offered item (WFST_NBEST_TREE overrides T in tests).  Dense inputs overflow T without help: the complete graph of 20
+ *      states at nshortest = 32 creates several times the 2048 entries it is given.  The four nbest values describe the last
+ *      wfst_shortest_path_batch call with nshortest > 1, unique = false:
+ *        nbest_in_kernel      items the kernel answered (== wfst_stats.nbest_device_problems),
+ *        nbest_tree_full      items that came back because the tree was full (or the distances did not settle),
+ *        nbest_out_full       items that came back because the launch's 256 MB result area was full,
+ *        nbest_tree_capacity  the T of the launch.
+ *      All values are 0 when no launch was made.  Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back,
+                                          uint64_t* nbest_in_kernel, uint64_t* nbest_tree_full, uint64_t* nbest_out_full,
+                                          uint64_t* nbest_tree_capacity);
 
 /* wfst_compose_shortest_path_batch with the results as RECORDS (the layout of wfst_fst_pack_paths below) instead of handles:
  * out[i * (4 + 4 * max_arcs) ...] = path i, written straight from the kernel's result buffers — for hosts that read the

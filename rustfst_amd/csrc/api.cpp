@@ -385,6 +385,7 @@ wfst_status wfst_shortest_path(wfst_ctx* ctx, const wfst_fst* fst, const wfst_sh
     if (!ctx || !fst || !out) throw Error("null pointer");
     wfst_shortest_path_config c = cfg ? *cfg : wfst_shortest_path_config{1e-6f, 1, 0};  // shortest_path.rs:31-39
     HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
     if (c.nshortest == 0) {  // shortest_path.rs:118-120: FO::new()
       HostCsr h;
       h.offsets.push_back(0);
@@ -411,6 +412,7 @@ wfst_status wfst_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* fsts,
     }
     wfst_shortest_path_config c = cfg ? *cfg : wfst_shortest_path_config{1e-6f, 1, 0};
     HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
     try {
       if (c.nshortest >= 2 && !c.unique) {
         shortest_path_nbest_batch(ctx, fsts, n, c.nshortest, c.delta, outs);
@@ -789,6 +791,21 @@ wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launche
     if (launches) *launches = ctx->rm_batch_launches;
     if (items_in_kernel) *items_in_kernel = ctx->rm_batch_in_kernel;
     if (items_single) *items_single = ctx->rm_batch_single;
+  });
+}
+
+wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back,
+                                          uint64_t* nbest_in_kernel, uint64_t* nbest_tree_full, uint64_t* nbest_out_full,
+                                          uint64_t* nbest_tree_capacity) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (n1_in_kernel) *n1_in_kernel = ctx->small_path.n1_in_kernel;
+    if (n1_staged) *n1_staged = ctx->small_path.n1_staged;
+    if (n1_handed_back) *n1_handed_back = ctx->small_path.n1_handed_back;
+    if (nbest_in_kernel) *nbest_in_kernel = ctx->small_path.nbest_in_kernel;
+    if (nbest_tree_full) *nbest_tree_full = ctx->small_path.nbest_tree_full;
+    if (nbest_out_full) *nbest_out_full = ctx->small_path.nbest_out_full;
+    if (nbest_tree_capacity) *nbest_tree_capacity = ctx->small_path.nbest_tree_capacity;
   });
 }
 

@@ -242,6 +242,12 @@ struct wfst_ctx {
   uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
   // the last wfst_rm_epsilon_batch call (wfst_ctx_get_rm_epsilon_batch_stats)
   uint64_t rm_batch_launches = 0, rm_batch_in_kernel = 0, rm_batch_single = 0;
+  // the one-wave path kernels (wfst_ctx_get_small_path_stats): the last sp1_wave_kernel launch since the last
+  // wfst_shortest_path / wfst_shortest_path_batch call began, and the last shortest_path_nbest_batch
+  struct SmallPathStats {
+    uint64_t n1_in_kernel = 0, n1_staged = 0, n1_handed_back = 0;
+    uint64_t nbest_in_kernel = 0, nbest_tree_full = 0, nbest_out_full = 0, nbest_tree_capacity = 0;
+  } small_path;
   // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;

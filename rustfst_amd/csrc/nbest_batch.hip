@@ -380,6 +380,8 @@ void shortest_path_nbest_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_
       max_arcs = std::max<uint32_t>(max_arcs, (uint32_t)f->n_arcs);
     }
   ctx->stats.nbest_device_problems = 0;
+  ctx->small_path.nbest_in_kernel = ctx->small_path.nbest_tree_full = ctx->small_path.nbest_out_full = 0;
+  ctx->small_path.nbest_tree_capacity = 0;
   if (!dev_idx.empty()) {
     // tree capacity: what n paths of about max_n states each can create, with room for side branches; the LDS it needs
     // (9 bytes per entry) bounds it
@@ -415,8 +417,11 @@ void shortest_path_nbest_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_
                                                     (uint32_t)nshortest, delta, T);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(st));
+      ctx->small_path.nbest_tree_capacity = T;
       for (size_t j = 0; j < m; ++j) {
         const NbOut& o = h_outs[j];
+        if (o.status == NB_TREE_FULL) ctx->small_path.nbest_tree_full += 1;
+        if (o.status == NB_OUT_FULL) ctx->small_path.nbest_out_full += 1;
         if (o.status != NB_OK) continue;  // does not fit: the host search below
         HostCsr h;
         const uint8_t* pl = h_payload + o.payload;
@@ -444,6 +449,7 @@ void shortest_path_nbest_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_
         }
         outs[dev_idx[j]] = make_host_fst(ctx, o.n_states, o.has_start ? 0 : -1, p, std::move(h));
         ctx->stats.nbest_device_problems += 1;
+        ctx->small_path.nbest_in_kernel += 1;
       }
     }
   }
@@ -678,6 +684,20 @@ __global__ void __launch_bounds__(64) sp1_wave_kernel(const NbProb* __restrict__
   if (lane == 0) outs[blockIdx.x] = o;
 }
 
+// the counters of one sp1_wave_kernel launch (wfst_ctx_get_small_path_stats), from the status words it wrote
+void sp1_count(wfst_ctx* ctx, const wfst_fst* const* fsts, const std::vector<size_t>& idx, const Sp1Out* h_outs) {
+  ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
+  for (size_t j = 0; j < idx.size(); ++j) {
+    const wfst_fst* f = fsts[idx[j]];
+    if (h_outs[j].status != 0u) {
+      ctx->small_path.n1_handed_back += 1;
+      continue;
+    }
+    ctx->small_path.n1_in_kernel += 1;  // (an item without states or without a start state is answered before anything is staged)
+    if (f->n_states && f->start >= 0 && sp1_staged(f->n_states, (uint32_t)f->n_arcs)) ctx->small_path.n1_staged += 1;
+  }
+}
+
 }  // namespace
 
 // Forward distances (the exact fixed point) and the CSR of the small inputs idx[..] of fsts, all in ONE launch and one
@@ -710,6 +730,7 @@ void export_small_with_distances(wfst_ctx* ctx, const wfst_fst* const* fsts, con
   sp1_wave_kernel<<<(uint32_t)m, 64, lds, st>>>(h_probs, h_outs, h_payload, 1u);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
+  sp1_count(ctx, fsts, idx, h_outs);
   for (size_t j = 0; j < m; ++j) {
     const Sp1Out& o = h_outs[j];
     if (o.status != 0u || !o.has_path) continue;
@@ -780,6 +801,7 @@ void shortest_path_n1_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n
     sp1_wave_kernel<<<(uint32_t)m, 64, lds, st>>>(h_probs, h_outs, h_payload, 0u);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st));
+    sp1_count(ctx, fsts, idx, h_outs);
     for (size_t j = 0; j < m; ++j) {
       const Sp1Out& o = h_outs[j];
       if (o.status != 0u) continue;  // the single-FST path below

@@ -86,6 +86,16 @@ class Context:
         check(_lib.lib().wfst_ctx_get_rearm_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rearm_stats")
         return dict(zip(("armed", "adopted", "dropped"), (int(v.value) for v in vals)))
 
+    def small_path_stats(self) -> dict:
+        """Which path answered the small shortest-path queries of this context (wfst_ctx_get_small_path_stats): the last
+        launch of the nshortest = 1 wave kernel (n1_in_kernel, n1_staged, n1_handed_back) and the last n-best batch
+        (nbest_in_kernel, nbest_tree_full, nbest_out_full, nbest_tree_capacity)."""
+        names = ("n1_in_kernel", "n1_staged", "n1_handed_back", "nbest_in_kernel", "nbest_tree_full", "nbest_out_full",
+                 "nbest_tree_capacity")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_small_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_small_path_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
