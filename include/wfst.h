@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -606,6 +606,42 @@ wfst_status wfst_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* fsts,
 wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back,
                                           uint64_t* nbest_in_kernel, uint64_t* nbest_tree_full, uint64_t* nbest_out_full,
                                           uint64_t* nbest_tree_capacity);
+
+/* ---- which route answered the problems of the last wfst_compose / wfst_compose_shortest_path_batch[_begin/_end/_packed]
+ *      call of ctx: the two kernels of compose.hip hand a problem from a fast route to a slower one that returns the same
+ *      FST, so only these counters show which one ran.  They are tallied on the host from the status word every problem
+ *      already reports; a call resets them when it begins.
+ *      string_compose_sp_kernel takes a problem of the fused batch whose first operand is a string (linear, epsilon-free,
+ *      one final state) of at most 2048 states, with filter Auto or Sequence, against a T without input epsilons
+ *      (WFST_STRING_KERNEL=0: never).  Inside it: a level of ONE state whose arc block has at most 12 arcs, and lies at
+ *      least 12 arcs before the end of T's arc array, is read through the scalar cache (on by default for batches of at most
+ *      8; WFST_STRING_SCALAR=0/1); a lone match of a one-state level with a block of at most 64 arcs asks for the next
+ *      level's first 64 rows early; blocks are read 64 arcs at a time, the string 64 labels at a time.  It hands back
+ *      (ST_NOT_A_STRING_CASE) a problem with a level of more than 64 states or with as many composed states as its LDS slice
+ *      holds: 2048, or for a batch of at least 16 without WFST_STRING_UNPACKED 512 / 1024 / 2048 = the least of them
+ *      that is >= 2 * max_states + 64, max_states = the most states of a string of the batch.
+ *      compose_wave_kernel stages a BFS level in LDS while it emits at most 64 arcs and redoes it through the arena when
+ *      it does not; matches by ballot against a searched block of at most 64 arcs and by binary search beyond; takes the
+ *      iterated side 64 items at a time (items = arcs + 1).  Its arena holds S states, A arcs and H hash slots:
+ *      wfst_compose starts at S = 4 * max(min(n1, n2), 64) + 1024, A = 4 * S; the fused batch at S = 4 * max(max_states, 64)
+ *      + 256, A = 2 * S; H = the power of two >= 2 * S + 128.  A level may hold hi + emitted + 64 <= H (hi = the states
+ *      numbered before it).  An overflow relaunches the problem with 4 * S and 4 * A.  wfst_compose hands a level that
+ *      adds more than 64 states (seen on the arena route only), or a relaunch beyond S = 16384, to the wide driver
+ *      (WFST_COMPOSE_PATH=wave: never).  The fused path is redone as compose + shortest_path when a state of the path has
+ *      no predecessor that is tight in the hop count (ST_TIE_ORDER).
+ *        string_answered     problems the string kernel answered (== wfst_stats.string_problems),
+ *        string_handed_back  problems it handed back to the wave kernel,
+ *        wave_first          problems the wave kernel answered in their first launch on it,
+ *        relaunch_states / relaunch_arcs / relaunch_hash / relaunch_path
+ *                            launches that ended in that overflow (a problem relaunched twice counts twice),
+ *        switched_wide       problems given to the wide driver by wfst_compose (either reason),
+ *        two_step            problems of a fused batch redone as compose + shortest_path (that inner compose is not tallied),
+ *        caps_states / caps_arcs / caps_hash   S, A and H of the last compose_wave_kernel launch (0: none was made).
+ *      Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answered, uint64_t* string_handed_back,
+                                            uint64_t* wave_first, uint64_t* relaunch_states, uint64_t* relaunch_arcs,
+                                            uint64_t* relaunch_hash, uint64_t* relaunch_path, uint64_t* switched_wide,
+                                            uint64_t* two_step, uint64_t* caps_states, uint64_t* caps_arcs, uint64_t* caps_hash);
 
 /* wfst_compose_shortest_path_batch with the results as RECORDS (the layout of wfst_fst_pack_paths below) instead of handles:
  * out[i * (4 + 4 * max_arcs) ...] = path i, written straight from the kernel's result buffers — for hosts that read the

@@ -809,6 +809,28 @@ wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel,
   });
 }
 
+wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answered, uint64_t* string_handed_back,
+                                            uint64_t* wave_first, uint64_t* relaunch_states, uint64_t* relaunch_arcs,
+                                            uint64_t* relaunch_hash, uint64_t* relaunch_path, uint64_t* switched_wide,
+                                            uint64_t* two_step, uint64_t* caps_states, uint64_t* caps_arcs, uint64_t* caps_hash) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::ComposePathStats& c = ctx->compose_path;
+    if (string_answered) *string_answered = c.string_answered;
+    if (string_handed_back) *string_handed_back = c.string_handed_back;
+    if (wave_first) *wave_first = c.wave_first;
+    if (relaunch_states) *relaunch_states = c.relaunch_states;
+    if (relaunch_arcs) *relaunch_arcs = c.relaunch_arcs;
+    if (relaunch_hash) *relaunch_hash = c.relaunch_hash;
+    if (relaunch_path) *relaunch_path = c.relaunch_path;
+    if (switched_wide) *switched_wide = c.switched_wide;
+    if (two_step) *two_step = c.two_step;
+    if (caps_states) *caps_states = c.caps_states;
+    if (caps_arcs) *caps_arcs = c.caps_arcs;
+    if (caps_hash) *caps_hash = c.caps_hash;
+  });
+}
+
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap) {
   return wrap([&] {

@@ -248,6 +248,14 @@ struct wfst_ctx {
     uint64_t n1_in_kernel = 0, n1_staged = 0, n1_handed_back = 0;
     uint64_t nbest_in_kernel = 0, nbest_tree_full = 0, nbest_out_full = 0, nbest_tree_capacity = 0;
   } small_path;
+  // which route answered the problems of the last compose / fused-batch call (wfst_ctx_get_compose_path_stats): tallied on
+  // the host from the status words the kernels of compose.hip already report
+  struct ComposePathStats {
+    uint64_t string_answered = 0, string_handed_back = 0, wave_first = 0;
+    uint64_t relaunch_states = 0, relaunch_arcs = 0, relaunch_hash = 0, relaunch_path = 0;
+    uint64_t switched_wide = 0, two_step = 0;
+    uint64_t caps_states = 0, caps_arcs = 0, caps_hash = 0;  // Caps of the last compose_wave_kernel launch
+  } compose_path;
   // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;

@@ -1494,9 +1494,13 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
         // scalar arc-block loads where a wave is alone on its SIMD (a handful of strings): -7 % per level; with eight waves
         // per compute unit the other waves hide the vector latency anyway and the extra scalar instructions cost 3 %
         env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u), run.done_ticket);
-  } else
+  } else {
     compose_wave_kernel<FLAGS><<<(uint32_t)n, 64, 0, st>>>(k_desc, f2, caps, run.arena.p, run.stride, k_res, k_paths, path_cap,
                                                             run.d_cursor.p);
+    ctx->compose_path.caps_states = caps.S;
+    ctx->compose_path.caps_arcs = caps.A;
+    ctx->compose_path.caps_hash = caps.H;
+  }
   HIP_CHECK(hipGetLastError());
   if (ctx->profiling) HIP_CHECK(hipEventRecord(ctx->ev1, st));
   if (run.zero_copy) return;
@@ -1626,11 +1630,29 @@ const char* status_name(uint32_t s) {
   }
 }
 
+// wfst_ctx_get_compose_path_stats: one status word of a finished launch.  `first`: this launch was the problem's first
+// on compose_wave_kernel (ST_OK then counts as answered there); string-kernel results pass first = false.
+void tally_status(wfst_ctx* ctx, uint32_t status, bool string_kernel, bool first) {
+  wfst_ctx::ComposePathStats& c = ctx->compose_path;
+  switch (status) {
+    case ST_OK: if (string_kernel) c.string_answered++; else if (first) c.wave_first++; break;
+    case ST_OVERFLOW_STATES: c.relaunch_states++; break;
+    case ST_OVERFLOW_ARCS: c.relaunch_arcs++; break;
+    case ST_OVERFLOW_HASH: c.relaunch_hash++; break;
+    case ST_OVERFLOW_PATH: c.relaunch_path++; break;
+    case ST_NOT_A_STRING_CASE: c.string_handed_back++; break;
+    case ST_SWITCH_WIDE: c.switched_wide++; break;
+    case ST_TIE_ORDER: c.two_step++; break;
+    default: break;
+  }
+}
+
 }  // namespace
 
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter) {
   if (f1->n_states > TUPLE_S1_MASK) throw Error("compose: the 1st FST has more than 2^30 states");
   const uint32_t mode = decide_match_mode(f1->props, f2->props);
+  ctx->compose_path = wfst_ctx::ComposePathStats{};
   ensure_device(const_cast<wfst_fst*>(f1));
   ensure_device(const_cast<wfst_fst*>(f2));
   const bool has_start = f1->start >= 0 && f2->start >= 0;
@@ -1666,6 +1688,7 @@ wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool co
     const Result& r = run.results[0];
     ctx->stats.compose_states = r.n_states;
     ctx->stats.compose_arcs = r.n_arcs;
+    tally_status(ctx, r.status, false, attempt == 0);
     if (r.status == ST_OK) {
       // carve the finished arrays out of the problem arena (same carve as the kernel)
       const Caps& c = run.caps;
@@ -1689,7 +1712,10 @@ wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool co
     est_a *= 4;
     // a result that has outgrown WIDE_COMPOSE_STATES is not a job for ONE wave: the wide driver (compose_wide.hip: one
     // wave per composed state of a BFS level) does a million states in tens of ms where this kernel needs seconds
-    if (wide_ok && est_s > WIDE_COMPOSE_STATES) return compose_wide(ctx, f1, f2, mode, filter, connect, out_props, est_s);
+    if (wide_ok && est_s > WIDE_COMPOSE_STATES) {
+      ctx->compose_path.switched_wide++;
+      return compose_wide(ctx, f1, f2, mode, filter, connect, out_props, est_s);
+    }
   }
 }
 
@@ -1715,6 +1741,13 @@ struct wfst_batch_job {
   wfst::FstView v2_s{};  // fst2 with its per-arc destination ranges
   std::shared_ptr<wfst::PinnedBlock> pin_block;  // descriptors, results and path arcs of the job's runs (pinned host memory)
   wfst::EnvSnap env;  // the WFST_* variables when the call began: asked by begin, both launch halves and end
+  std::vector<uint8_t> seen_wave;  // wfst_ctx_get_compose_path_stats: problems with a wave-kernel launch behind them (sized
+                                   // by the first relaunch: empty on the usual call)
+  bool first_wave(size_t idx) const { return seen_wave.empty() || !seen_wave[idx]; }
+  void mark_wave(size_t idx) {
+    if (seen_wave.empty()) seen_wave.assign(n, 0);
+    seen_wave[idx] = 1;
+  }
 };
 
 namespace wfst {
@@ -1724,6 +1757,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   auto job = std::make_unique<wfst_batch_job>();
   job->ctx = ctx;
   job->n = n;
+  ctx->compose_path = wfst_ctx::ComposePathStats{};
   if (n == 0) return job.release();
   job->env = EnvSnap::take();
   job->run_s.env = &job->env;
@@ -1829,6 +1863,7 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
       std::vector<size_t> more, ok;
       for (size_t k = 0; k < job->todo_s.size(); ++k) {
         const Result& r = job->run_s.results[k];
+        tally_status(ctx, r.status, true, false);
         if (r.status != ST_OK) {
           (r.status == ST_TIE_ORDER ? job->slow : more).push_back(job->todo_s[k]);
           continue;
@@ -1859,7 +1894,9 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
           std::vector<size_t> again;
           for (size_t k = 0; k < job->todo.size(); ++k) {
             const Result& r = job->run.results[k];
+            tally_status(ctx, r.status, false, job->first_wave(job->todo[k]));
             if (r.status != ST_OK) {
+              if (r.status != ST_TIE_ORDER) job->mark_wave(job->todo[k]);
               (r.status == ST_TIE_ORDER ? job->slow : again).push_back(job->todo[k]);
               continue;
             }
@@ -1884,7 +1921,9 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
       std::vector<size_t> again;
       for (size_t k = 0; k < job->todo.size(); ++k) {
         const Result& r = job->run.results[k];
+        tally_status(ctx, r.status, false, job->first_wave(job->todo[k]));
         if (r.status != ST_OK) {
+          if (r.status != ST_TIE_ORDER) job->mark_wave(job->todo[k]);
           (r.status == ST_TIE_ORDER ? job->slow : again).push_back(job->todo[k]);
           continue;
         }
@@ -1905,7 +1944,9 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
       launch_begin<FLAG_SP>(ctx, cur, job->v2, make_caps(job->est_s, job->est_a), job->run, true);
     }
     for (size_t idx : job->slow) {  // handed back by the fused kernel: the two-step route (always applicable)
+      const wfst_ctx::ComposePathStats batch_tally = ctx->compose_path;  // (compose() below starts its own tally)
       std::unique_ptr<wfst_fst> c(compose(ctx, job->accs[idx], job->t, true, job->filter));
+      ctx->compose_path = batch_tally;
       tot_arcs += c->n_arcs;
       tot_states += c->n_states;
       if (sink) {

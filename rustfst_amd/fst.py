@@ -96,6 +96,18 @@ class Context:
         check(_lib.lib().wfst_ctx_get_small_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_small_path_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def compose_path_stats(self) -> dict:
+        """Which route answered the problems of this context's last compose / compose_shortest_path_batch call
+        (wfst_ctx_get_compose_path_stats): the string kernel (string_answered) or its hand-backs (string_handed_back), the
+        wave kernel's first launch (wave_first), relaunches with a 4x arena by overflow status (relaunch_states / _arcs /
+        _hash / _path), the wide driver (switched_wide), the two-step route (two_step), and the capacities of the last
+        wave launch (caps_states, caps_arcs, caps_hash)."""
+        names = ("string_answered", "string_handed_back", "wave_first", "relaunch_states", "relaunch_arcs", "relaunch_hash",
+                 "relaunch_path", "switched_wide", "two_step", "caps_states", "caps_arcs", "caps_hash")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_compose_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_compose_path_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
