@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -642,6 +642,43 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
                                             uint64_t* wave_first, uint64_t* relaunch_states, uint64_t* relaunch_arcs,
                                             uint64_t* relaunch_hash, uint64_t* relaunch_path, uint64_t* switched_wide,
                                             uint64_t* two_step, uint64_t* caps_states, uint64_t* caps_arcs, uint64_t* caps_hash);
+
+/* ---- which route the levels of the last wfst_determinize / wfst_determinize_with_distance call of ctx took.  The result
+ *      is built breadth-first level by level, and every route returns the same FST, so only these counters show which one
+ *      ran.  They are tallied on the host from the control block the call already reads back (no launch, no read-back of
+ *      their own); a call resets them when it begins.  After wfst_determinize_batch / wfst_determinize_with_distance_batch
+ *      they are unspecified (an item handed to the single-FST path overwrites them).
+ *      One workgroup (det_narrow_kernel) runs level after level inside one launch while a level has at most 256 states and
+ *      at most 8192 raw candidates (WFST_DETERMINIZE_PATH=narrow: whatever their size), for at most 65536 levels per launch
+ *      (WFST_DETERMINIZE_LEVEL_BUDGET=n, 0 < n < 65536, lowers that for tests); any other level runs as one device-wide launch
+ *      per phase (WFST_DETERMINIZE_PATH=wide: every level), whose resolve rounds the host runs two at a time.  The arrays
+ *      start with room for 1024 states, 4096 subset elements, 4096 arcs and 4096 candidates of one level.  A level of K raw
+ *      candidates starts only when K <= candidates, hi + K <= states, elements + K <= element room and arcs + K <= arc room
+ *      (hi = the states numbered before it, elements and arcs = those stored so far); otherwise nothing of it is written, the
+ *      arrays short of hi + K + 1 states, elements + K, arcs + K or K candidates double until they hold them, the state
+ *      table is re-hashed when the states grew, and the level starts again.
+ *        levels            levels completed,
+ *        wide_levels       those of them the device-wide launches completed (the others ran in the narrow kernel),
+ *        narrow_launches   det_narrow_kernel launches,
+ *        exit_wide_states / exit_wide_cands
+ *                          launches that ended at a level of more than 256 states / of at most 256 states and more than 8192 raw
+ *                          candidates,
+ *        exit_budget       launches that ended after their budget of levels,
+ *        exit_need         launches that ended at a level that needs more room,
+ *        exit_done         launches that ended because no state was left (0 or 1),
+ *        wide_need         device-wide levels whose check asked for more room,
+ *        grow_states / grow_elts / grow_arcs / grow_cands
+ *                          times that array was enlarged after the first allocation,
+ *        rehashes          times the state table was re-hashed (== grow_states),
+ *        cap_states / cap_elts / cap_arcs / cap_cands   the room at the end of the call,
+ *        rounds_max        the most resolve rounds the host launched for one device-wide level (even; 0: no such level).
+ *      All values are 0 for an input without states or start state.  Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* wide_levels, uint64_t*
+                                           narrow_launches, uint64_t* exit_wide_states, uint64_t* exit_wide_cands,
+                                           uint64_t* exit_budget, uint64_t* exit_need, uint64_t* exit_done, uint64_t*
+                                           wide_need, uint64_t* grow_states, uint64_t* grow_elts, uint64_t* grow_arcs,
+                                           uint64_t* grow_cands, uint64_t* rehashes, uint64_t* cap_states, uint64_t*
+                                           cap_elts, uint64_t* cap_arcs, uint64_t* cap_cands, uint64_t* rounds_max);
 
 /* wfst_compose_shortest_path_batch with the results as RECORDS (the layout of wfst_fst_pack_paths below) instead of handles:
  * out[i * (4 + 4 * max_arcs) ...] = path i, written straight from the kernel's result buffers — for hosts that read the

@@ -831,6 +831,37 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
   });
 }
 
+wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* wide_levels, uint64_t*
+                                           narrow_launches, uint64_t* exit_wide_states, uint64_t* exit_wide_cands,
+                                           uint64_t* exit_budget, uint64_t* exit_need, uint64_t* exit_done, uint64_t*
+                                           wide_need, uint64_t* grow_states, uint64_t* grow_elts, uint64_t* grow_arcs,
+                                           uint64_t* grow_cands, uint64_t* rehashes, uint64_t* cap_states, uint64_t*
+                                           cap_elts, uint64_t* cap_arcs, uint64_t* cap_cands, uint64_t* rounds_max) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::DeterminizeStats& c = ctx->det_stats;
+    if (levels) *levels = c.levels;
+    if (wide_levels) *wide_levels = c.wide_levels;
+    if (narrow_launches) *narrow_launches = c.narrow_launches;
+    if (exit_wide_states) *exit_wide_states = c.exit_wide_states;
+    if (exit_wide_cands) *exit_wide_cands = c.exit_wide_cands;
+    if (exit_budget) *exit_budget = c.exit_budget;
+    if (exit_need) *exit_need = c.exit_need;
+    if (exit_done) *exit_done = c.exit_done;
+    if (wide_need) *wide_need = c.wide_need;
+    if (grow_states) *grow_states = c.grow_states;
+    if (grow_elts) *grow_elts = c.grow_elts;
+    if (grow_arcs) *grow_arcs = c.grow_arcs;
+    if (grow_cands) *grow_cands = c.grow_cands;
+    if (rehashes) *rehashes = c.rehashes;
+    if (cap_states) *cap_states = c.cap_states;
+    if (cap_elts) *cap_elts = c.cap_elts;
+    if (cap_arcs) *cap_arcs = c.cap_arcs;
+    if (cap_cands) *cap_cands = c.cap_cands;
+    if (rounds_max) *rounds_max = c.rounds_max;
+  });
+}
+
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap) {
   return wrap([&] {

@@ -238,6 +238,15 @@ struct wfst_ctx {
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
   // the last wfst_determinize_batch / wfst_determinize_with_distance_batch call (wfst_ctx_get_determinize_batch_stats)
   uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
+  // which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took
+  // (wfst_ctx_get_determinize_stats): tallied on the host from the control block determinize.hip already reads back
+  struct DeterminizeStats {
+    uint64_t levels = 0, wide_levels = 0, narrow_launches = 0;
+    uint64_t exit_wide_states = 0, exit_wide_cands = 0, exit_budget = 0, exit_need = 0, exit_done = 0, wide_need = 0;
+    uint64_t grow_states = 0, grow_elts = 0, grow_arcs = 0, grow_cands = 0, rehashes = 0;
+    uint64_t cap_states = 0, cap_elts = 0, cap_arcs = 0, cap_cands = 0;
+    uint64_t rounds_max = 0;
+  } det_stats;
   // the last wfst_minimize_batch call (wfst_ctx_get_minimize_batch_stats)
   uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
   // the last wfst_rm_epsilon_batch call (wfst_ctx_get_rm_epsilon_batch_stats)

@@ -686,6 +686,7 @@ struct Run {
   DBuf<uint64_t> hkey, lsc, chash, sc1, sc2, lkey, part;
   DBuf<uint4> ca, cb, crec;
   DBuf<Ctl> ctl;
+  wfst_ctx::DeterminizeStats* tally = nullptr;  // grow_* / rehashes: reserve calls after the first that enlarged an array
   explicit Run(DevicePool& p, hipStream_t s) : pool(p), st(s) {}
 
   // room for at least `states` ids, `elts` elements, `arcs` arcs and a level of `cands` slots; the first `kept_*` entries
@@ -698,6 +699,10 @@ struct Run {
       return n;
     };
     const uint64_t ns = up(cap.states, states), ne = up(cap.elts, elts), na = up(cap.arcs, arcs), nc = up(cap.cands, cands);
+    if (tally && so.p && ns > cap.states) tally->grow_states += 1;
+    if (tally && se.p && ne > cap.elts) tally->grow_elts += 1;
+    if (tally && oarc.p && na > cap.arcs) tally->grow_arcs += 1;
+    if (tally && ca.p && nc > cap.cands) tally->grow_cands += 1;
     if (ns > cap.states || !so.p) {
       grow(pool, so, ns + 1, c.hi + 1, st);
       grow(pool, aoff, ns + 1, c.lo, st);
@@ -734,6 +739,7 @@ struct Run {
         det_rehash_kernel<<<std::min<uint32_t>((cap.slots + TPB - 1) / TPB, 1024), TPB, 0, st>>>(hkey.p, hhead.p, cap.slots, nk.p,
                                                                                                   nh.p, slots);
         HIP_CHECK(hipGetLastError());
+        if (tally) tally->rehashes += 1;
       }
       hkey = std::move(nk);
       hhead = std::move(nh);
@@ -778,6 +784,14 @@ static uint32_t max_states_knob() {
   }
   return max_states;
 }
+static uint32_t level_budget_knob() {  // levels of one det_narrow_kernel launch
+  uint32_t budget = NARROW_LEVELS_PER_LAUNCH;
+  if (const char* e = std::getenv("WFST_DETERMINIZE_LEVEL_BUDGET")) {  // tests: reach the budget exit with a short input
+    const long v = std::atol(e);
+    if (v > 0 && (uint64_t)v < budget) budget = (uint32_t)v;
+  }
+  return budget;
+}
 
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type) {
   // the reference branches on the STORED word (determinize_static.rs:181-185): anything else takes the gallic path
@@ -794,6 +808,8 @@ wfst_fst* determinize_encoded_fst(wfst_ctx* ctx, const wfst_fst* f, float delta,
 
 static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type, const DistReq* dq) {
   const uint64_t out_props = props::determinize(f->props, det_type != 1);
+  wfst_ctx::DeterminizeStats& tally = ctx->det_stats;  // (wfst_ctx_get_determinize_stats: this call's, also when it ends KO)
+  tally = wfst_ctx::DeterminizeStats{};
   if (f->start < 0 || f->n_states == 0) {  // compute_start -> None: the empty FST (lazy_fst.rs:229-232)
     HostCsr h;
     h.offsets.push_back(0);
@@ -802,9 +818,10 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
   }
   ensure_device(const_cast<wfst_fst*>(f));
   const Path path = path_knob();
-  const uint32_t max_states = max_states_knob();
+  const uint32_t max_states = max_states_knob(), budget = level_budget_knob();
   hipStream_t st = ctx->stream;
   Run run(*ctx->pool, st);
+  run.tally = &tally;
   run.cap.max_states = max_states;
   run.cap.max_elts = 1u << 28;
   run.ctl = DBuf<Ctl>(*ctx->pool, 1);
@@ -838,12 +855,18 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
     if (narrow) {
       const uint32_t ml = path == Path::Narrow ? 0xFFFFFFFFu : NARROW_STATES;
       const uint32_t mk = path == Path::Narrow ? 0xFFFFFFFFu : NARROW_CANDS;
-      det_narrow_kernel<<<1, TPB, 0, st>>>(d, ml, mk, NARROW_LEVELS_PER_LAUNCH);
+      det_narrow_kernel<<<1, TPB, 0, st>>>(d, ml, mk, budget);
       HIP_CHECK(hipGetLastError());
       read_ctl();
+      tally.narrow_launches += 1;
+      if (c.exit == 1) (c.hi - c.lo > NARROW_STATES ? tally.exit_wide_states : tally.exit_wide_cands) += 1;
+      tally.exit_budget += c.exit == 2;
+      tally.exit_need += c.exit == 3;
+      tally.exit_done += c.exit == 4;
       if (!(c.exit == 1 && path == Path::Auto)) continue;  // else a level too wide for one workgroup: it runs wide
     }
-    // one wide level
+    // one wide level (after a narrow launch `L`, hence `grid`, is still the size of the level that launch began with, not of
+    // the level it stopped at: every phase strides by its grid, so `grid` only has to be >= 1)
     const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((L + TPB - 1) / TPB, (uint32_t)ctx->n_cus * 4));
     det_count_kernel<<<grid, TPB, 0, st>>>(d);
     det_scan_part_kernel<<<G, TPB, 0, st>>>(d, d.lsc, run.part.p, 0);
@@ -852,6 +875,7 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
     det_check_kernel<<<1, 1, 0, st>>>(d);
     HIP_CHECK(hipGetLastError());
     read_ctl();
+    if (!c.err && c.need) tally.wide_need += 1;
     if (c.err || c.need) continue;
     const uint32_t gk = std::max<uint32_t>(1, std::min<uint32_t>((c.K + TPB - 1) / TPB, (uint32_t)ctx->n_cus * 8));
     const uint32_t gt = std::max<uint32_t>(1, std::min<uint32_t>((c.T + TPB - 1) / TPB, (uint32_t)ctx->n_cus * 8));
@@ -881,7 +905,14 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
     det_advance_kernel<<<1, 1, 0, st>>>(d);
     HIP_CHECK(hipGetLastError());
     read_ctl();
+    tally.wide_levels += 1;
+    tally.rounds_max = std::max<uint64_t>(tally.rounds_max, r);
   }
+  tally.levels = c.levels;
+  tally.cap_states = run.cap.states;
+  tally.cap_elts = run.cap.elts;
+  tally.cap_arcs = run.cap.arcs;
+  tally.cap_cands = run.cap.cands;
   // CSR: aoff[N] = number of arcs
   const uint32_t N = c.hi;
   HIP_CHECK(hipMemcpyAsync(run.aoff.p + N, &c.n_arcs, sizeof(uint32_t), hipMemcpyHostToDevice, st));

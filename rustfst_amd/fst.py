@@ -108,6 +108,20 @@ class Context:
         check(_lib.lib().wfst_ctx_get_compose_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_compose_path_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def determinize_stats(self) -> dict:
+        """Which route the levels of this context's last determinize / determinize_with_distance call took
+        (wfst_ctx_get_determinize_stats): levels completed (levels) and those the device-wide launches ran (wide_levels),
+        launches of the one-workgroup kernel (narrow_launches) by how they ended (exit_wide_states, exit_wide_cands,
+        exit_budget, exit_need, exit_done), device-wide checks that asked for room (wide_need), arrays enlarged (grow_states,
+        grow_elts, grow_arcs, grow_cands, rehashes), their final sizes (cap_states, cap_elts, cap_arcs, cap_cands) and the most
+        resolve rounds of a device-wide level (rounds_max).  Unspecified after a batch call."""
+        names = ("levels", "wide_levels", "narrow_launches", "exit_wide_states", "exit_wide_cands", "exit_budget", "exit_need",
+                 "exit_done", "wide_need", "grow_states", "grow_elts", "grow_arcs", "grow_cands", "rehashes", "cap_states",
+                 "cap_elts", "cap_arcs", "cap_cands", "rounds_max")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_determinize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_determinize_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""

@@ -1,8 +1,8 @@
 """wfst_determinize_batch, wfst_determinize_with_distance and its batch form: the C-ABI surface without a GPU, a Python
 restatement of determinize_with_distance (test_determinize's determinize_ref extended with the subsets, the levels and
 out_dist) checked against the oracle's shortest distances, and on the device parity of every batch item with the oracle,
-the restatement and the single call, the in_kernel flags against their prediction from the level sizes, arena growth,
-distances and error handling."""
+the restatement and the single call, the in_kernel flags against their prediction from the level sizes (items on the kernel's
+limits and one beyond included), arena growth, distances and error handling."""
 import ctypes as C
 import functools
 import inspect
@@ -250,6 +250,32 @@ def test_in_kernel_prediction_of_the_test_inputs():
     assert collision_prediction() == 0
 
 
+LIMIT_ITEMS = ("states_256", "states_257", "cands_8192", "cands_8193")  # test_determinize_limits: on a limit, one beyond
+LDS_ITEMS = ("lds_496", "lds_497", "lds_alternating")
+BATCH_LDS_CANDS = 496  # determinize.hip: the levels whose scratch WFST_DETERMINIZE_BATCH_SCRATCH=lds keeps in LDS
+
+
+def limit_case(name):
+    import test_determinize_limits as tl
+    return tl.case(name)[0]
+
+
+def test_in_kernel_prediction_of_the_limit_items():
+    widest = {}
+    for name in LIMIT_ITEMS + LDS_ITEMS:
+        levels = determinize_with_distance_ref(limit_case(name))[3]
+        widest[name] = (max(n for n, _ in levels), max(k for _, k in levels))
+    assert widest["states_256"] == (NARROW_STATES, 256) and widest["states_257"] == (NARROW_STATES + 1, 257)
+    assert widest["cands_8192"] == (64, NARROW_CANDS) and widest["cands_8193"] == (64, NARROW_CANDS + 1)
+    assert [predict_in_kernel(limit_case(n)) for n in LIMIT_ITEMS] == [1, 0, 1, 0]
+    assert widest["lds_496"][1] == BATCH_LDS_CANDS and widest["lds_497"][1] == BATCH_LDS_CANDS + 1
+    levels = determinize_with_distance_ref(limit_case("lds_alternating"))[3]
+    sides = [k > BATCH_LDS_CANDS for _, k in levels]
+    assert sides == [False, True, False, True, False, False, True, False]  # the scratch moves at every level but one
+    assert {k for _, k in levels} >= {BATCH_LDS_CANDS, BATCH_LDS_CANDS + 1}
+    assert [predict_in_kernel(limit_case(n)) for n in LDS_ITEMS] == [1, 1, 1]
+
+
 # ================================================================ GPU
 def _cfg(delta=KDELTA, det_type=0):
     import rustfst_amd
@@ -284,6 +310,34 @@ def test_parity_with_oracle_and_single_call(gpu_ctx, oracle, monkeypatch, scratc
             exp["props"] = td.determinize_props(flat["props"], det_type != 1)
             same(g, exp, f"{name} {scratch} vs oracle")
             same(g, dev.determinize(_cfg(delta, det_type)).to_flat(), f"{name} {scratch} vs single")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scratch", SCRATCH)
+def test_items_on_the_kernel_limits(gpu_ctx, oracle, monkeypatch, scratch):
+    """a level of 256 | 257 states, of 8192 | 8193 raw candidates: the flags and items_single against predict_in_kernel; a
+    widest level of 496 | 497 raw candidates and levels on both sides of 496 in turn, under both scratch settings; every
+    item bit-identical to the single call and the oracle"""
+    import rustfst_amd
+    monkeypatch.setenv("WFST_DETERMINIZE_BATCH_SCRATCH", scratch)
+    names = LIMIT_ITEMS + LDS_ITEMS
+    flats = [limit_case(n) for n in names]
+    devs = [to_device(f, gpu_ctx) for f in flats]
+    got, flags = _batch(devs, gpu_ctx)
+    want = [predict_in_kernel(f) for f in flats]
+    assert flags == want == [1, 0, 1, 0, 1, 1, 1]
+    st = rustfst_amd.determinize_batch_stats(gpu_ctx)
+    assert st["items_single"] == 2 and st["items_in_kernel"] == 5
+    for name, flat, g, dev in zip(names, flats, got, devs):
+        exp = to_oracle(oracle, flat).determinize_fsa(KDELTA).to_flat()
+        exp["props"] = td.determinize_props(flat["props"], True)
+        same(g, exp, f"{name} {scratch} vs oracle")
+        same(g, dev.determinize().to_flat(), f"{name} {scratch} vs single")
+    # the LDS items alone, in the other order: no item leaves the kernel
+    got, flags = _batch(devs[:3:-1], gpu_ctx)
+    assert flags == [1, 1, 1] and rustfst_amd.determinize_batch_stats(gpu_ctx)["items_single"] == 0
+    for name, g, dev in zip(names[:3:-1], got, devs[:3:-1]):
+        same(g, dev.determinize().to_flat(), f"{name} {scratch} alone")
 
 
 @pytest.mark.gpu
