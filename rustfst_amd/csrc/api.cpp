@@ -508,25 +508,41 @@ wfst_status wfst_determinize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_dete
 }
 
 // determinize_with_config of n acceptors (one workgroup each); every argument is checked before anything is launched
-static void check_batch_args(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs) {
+static void null_outs(wfst_fst** outs, size_t n) {
   if (outs)
     for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+}
+static void check_batch_args(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs) {  // (behind null_outs)
   if (!ctx || !fsts || !outs) throw Error("null pointer");
   for (size_t i = 0; i < n; ++i)
     if (!fsts[i]) throw Error("item " + std::to_string(i) + ": null FST in batch");
 }
+// The preamble of the one-workgroup-per-item batch calls, behind null_outs and the op's own config checks: the counters of
+// the last call go, then the arguments are checked.  false: an empty list, nothing to do.
+static bool begin_batch_call(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, BatchStats wfst_ctx::*stats) {
+  if (ctx) ctx->*stats = {};
+  if (n == 0) return false;
+  check_batch_args(ctx, fsts, n, outs);
+  HIP_CHECK(hipSetDevice(ctx->device));
+  return true;
+}
+static wfst_status get_batch_stats(wfst_ctx* ctx, BatchStats wfst_ctx::*stats, uint64_t* launches, uint64_t* items_in_kernel,
+                                   uint64_t* items_single) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (launches) *launches = (ctx->*stats).launches;
+    if (items_in_kernel) *items_in_kernel = (ctx->*stats).in_kernel;
+    if (items_single) *items_single = (ctx->*stats).single;
+  });
+}
 wfst_status wfst_determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_determinize_config* cfg,
                                    wfst_fst** outs, uint8_t* in_kernel) {
   return wrap([&] {
-    if (outs)
-      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    null_outs(outs, n);
     const wfst_determinize_config c = cfg ? *cfg : wfst_determinize_config{1.0f / 1024.0f, 0u};
     if (c.det_type > 2) throw Error("determinize: unknown det_type " + std::to_string(c.det_type));
     if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("determinize: delta must be finite and > 0");
-    if (ctx) ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
-    if (n == 0) return;
-    check_batch_args(ctx, fsts, n, outs);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::det_batch)) return;
     determinize_batch(ctx, fsts, n, c.delta, c.det_type, outs, in_kernel);
   });
 }
@@ -559,11 +575,10 @@ wfst_status wfst_determinize_with_distance_batch(wfst_ctx* ctx, const wfst_fst* 
                                                  const float* const* in_dists, const uint64_t* n_in_dists, float delta,
                                                  wfst_fst** outs, float** out_dist, uint64_t* out_offsets, uint8_t* in_kernel) {
   return wrap([&] {
-    if (outs)
-      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    null_outs(outs, n);
     if (out_dist) *out_dist = nullptr;
     if (!(delta > 0.0f) || !std::isfinite(delta)) throw Error("determinize: delta must be finite and > 0");
-    if (ctx) ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
+    if (ctx) ctx->det_batch = {};  // (begin_batch_call's steps, with this call's own checks between them)
     if (!out_dist || !out_offsets) throw Error("null pointer");
     out_offsets[0] = 0;
     if (n == 0) {
@@ -593,12 +608,7 @@ wfst_status wfst_determinize_with_distance_batch(wfst_ctx* ctx, const wfst_fst* 
 }
 wfst_status wfst_ctx_get_determinize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                                  uint64_t* items_single) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (launches) *launches = ctx->det_batch_launches;
-    if (items_in_kernel) *items_in_kernel = ctx->det_batch_in_kernel;
-    if (items_single) *items_single = ctx->det_batch_single;
-  });
+  return get_batch_stats(ctx, &wfst_ctx::det_batch, launches, items_in_kernel, items_single);
 }
 
 // minimize_with_config (minimize.rs:92-176); MinimizeConfig::default() = {KSHORTESTDELTA, false} when cfg == NULL
@@ -616,25 +626,16 @@ wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimiz
 wfst_status wfst_minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_minimize_config* cfg,
                                 wfst_fst** outs, uint8_t* in_kernel) {
   return wrap([&] {
-    if (outs)
-      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    null_outs(outs, n);
     const wfst_minimize_config c = cfg ? *cfg : wfst_minimize_config{1e-6f, 0u};
     if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("minimize: delta must be finite and > 0");
-    if (ctx) ctx->min_batch_launches = ctx->min_batch_in_kernel = ctx->min_batch_single = 0;
-    if (n == 0) return;
-    check_batch_args(ctx, fsts, n, outs);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::min_batch)) return;
     minimize_batch(ctx, fsts, n, c.delta, c.allow_nondet != 0, outs, in_kernel);
   });
 }
 wfst_status wfst_ctx_get_minimize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                               uint64_t* items_single) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (launches) *launches = ctx->min_batch_launches;
-    if (items_in_kernel) *items_in_kernel = ctx->min_batch_in_kernel;
-    if (items_single) *items_single = ctx->min_batch_single;
-  });
+  return get_batch_stats(ctx, &wfst_ctx::min_batch, launches, items_in_kernel, items_single);
 }
 
 // tr_sum (tr_sum.rs:7-22) / tr_unique (tr_unique.rs:38-51)
@@ -775,23 +776,14 @@ wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) 
 // rm_epsilon of n FSTs (one workgroup each); every argument is checked before anything is launched
 wfst_status wfst_rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
   return wrap([&] {
-    if (outs)
-      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
-    if (ctx) ctx->rm_batch_launches = ctx->rm_batch_in_kernel = ctx->rm_batch_single = 0;
-    if (n == 0) return;
-    check_batch_args(ctx, fsts, n, outs);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    null_outs(outs, n);
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::rm_batch)) return;
     rm_epsilon_batch(ctx, fsts, n, outs, in_kernel);
   });
 }
 wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                                 uint64_t* items_single) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (launches) *launches = ctx->rm_batch_launches;
-    if (items_in_kernel) *items_in_kernel = ctx->rm_batch_in_kernel;
-    if (items_single) *items_single = ctx->rm_batch_single;
-  });
+  return get_batch_stats(ctx, &wfst_ctx::rm_batch, launches, items_in_kernel, items_single);
 }
 
 wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back,

@@ -196,6 +196,9 @@ struct RearmRecord {
     for (size_t& c : cnt) c = 0;
   }
 };
+struct BatchStats {  // one call of a one-workgroup-per-item batch operation
+  uint64_t launches = 0, in_kernel = 0, single = 0;
+};
 }  // namespace wfst
 
 // ---------------------------------------------------------------- handles
@@ -236,8 +239,9 @@ struct wfst_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags: [0] first batch of a solve, [1] batches of 8 sweeps, [2] of 64
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
-  // the last wfst_determinize_batch / wfst_determinize_with_distance_batch call (wfst_ctx_get_determinize_batch_stats)
-  uint64_t det_batch_launches = 0, det_batch_in_kernel = 0, det_batch_single = 0;
+  // the last wfst_determinize_batch / wfst_determinize_with_distance_batch, wfst_minimize_batch and wfst_rm_epsilon_batch
+  // call (wfst_ctx_get_{determinize,minimize,rm_epsilon}_batch_stats; batch_driver.h counts)
+  wfst::BatchStats det_batch, min_batch, rm_batch;
   // which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took
   // (wfst_ctx_get_determinize_stats): tallied on the host from the control block determinize.hip already reads back
   struct DeterminizeStats {
@@ -247,10 +251,6 @@ struct wfst_ctx {
     uint64_t cap_states = 0, cap_elts = 0, cap_arcs = 0, cap_cands = 0;
     uint64_t rounds_max = 0;
   } det_stats;
-  // the last wfst_minimize_batch call (wfst_ctx_get_minimize_batch_stats)
-  uint64_t min_batch_launches = 0, min_batch_in_kernel = 0, min_batch_single = 0;
-  // the last wfst_rm_epsilon_batch call (wfst_ctx_get_rm_epsilon_batch_stats)
-  uint64_t rm_batch_launches = 0, rm_batch_in_kernel = 0, rm_batch_single = 0;
   // the one-wave path kernels (wfst_ctx_get_small_path_stats): the last sp1_wave_kernel launch since the last
   // wfst_shortest_path / wfst_shortest_path_batch call began, and the last shortest_path_nbest_batch
   struct SmallPathStats {

@@ -34,6 +34,7 @@
 
 #pragma clang fp contract(off)  // (before tropical.h comes in: its functions compile without contraction here too)
 
+#include "batch_driver.h"
 #include "common.h"
 #include "fst_props.h"
 
@@ -946,36 +947,31 @@ struct Done {  // a finished item: its result arrays inside the slab of the laun
   const float* ofin = nullptr;
   const uint2* se = nullptr;
 };
-// carves one item's arrays out of [base + at, ...): every array 64-byte aligned; base == nullptr only measures
-size_t carve_slice(unsigned char* base, size_t at, const Slice& sl, const wfst_fst* f, float delta, uint32_t max_states, Det* d) {
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 63) & ~(size_t)63;
-    return base ? base + o : nullptr;
-  };
+// carves one item's arrays out of the slab: every array 64-byte aligned; d == nullptr only measures
+size_t carve_slice(Slab s, const Slice& sl, const wfst_fst* f, float delta, uint32_t max_states, Det* d) {
   const uint32_t slots = pow2_at_least(2 * sl.states, "determinize"), ltab = pow2_at_least(2 * sl.cands, "determinize");
   Det v{};
-  v.so = (uint32_t*)take(4 * (sl.states + 1));
-  v.aoff = (uint32_t*)take(4 * (sl.states + 1));
-  v.ofin = (float*)take(4 * sl.states);
-  v.hnext = (uint32_t*)take(4 * sl.states);
-  v.lsc = (uint64_t*)take(8 * (sl.states + 1));
-  v.se = (uint2*)take(8 * sl.elts);
-  v.oarc = (wfst_tr*)take(sizeof(wfst_tr) * sl.arcs);
-  v.hkey = (uint64_t*)take(8 * (size_t)slots);
-  v.hhead = (uint32_t*)take(4 * (size_t)slots);
-  v.ca = (uint4*)take(16 * sl.cands);
-  v.cb = (uint4*)take(16 * sl.cands);
-  v.crec = (uint4*)take(16 * sl.cands);
-  v.ce = (uint2*)take(8 * sl.cands);
-  v.chash = (uint64_t*)take(8 * sl.cands);
-  v.sc1 = (uint64_t*)take(8 * (sl.cands + 1));
-  v.sc2 = (uint64_t*)take(8 * (sl.cands + 1));
-  v.lkey = (uint64_t*)take(8 * (size_t)ltab);
-  v.cst = (uint32_t*)take(4 * sl.cands);
-  v.cdest = (uint32_t*)take(4 * sl.cands);
-  v.cslot = (uint32_t*)take(4 * sl.cands);
-  v.lead = (uint32_t*)take(4 * 2 * (size_t)ltab);
+  v.so = s.take<uint32_t>(sl.states + 1);
+  v.aoff = s.take<uint32_t>(sl.states + 1);
+  v.ofin = s.take<float>(sl.states);
+  v.hnext = s.take<uint32_t>(sl.states);
+  v.lsc = s.take<uint64_t>(sl.states + 1);
+  v.se = s.take<uint2>(sl.elts);
+  v.oarc = s.take<wfst_tr>(sl.arcs);
+  v.hkey = s.take<uint64_t>(slots);
+  v.hhead = s.take<uint32_t>(slots);
+  v.ca = s.take<uint4>(sl.cands);
+  v.cb = s.take<uint4>(sl.cands);
+  v.crec = s.take<uint4>(sl.cands);
+  v.ce = s.take<uint2>(sl.cands);
+  v.chash = s.take<uint64_t>(sl.cands);
+  v.sc1 = s.take<uint64_t>(sl.cands + 1);
+  v.sc2 = s.take<uint64_t>(sl.cands + 1);
+  v.lkey = s.take<uint64_t>(ltab);
+  v.cst = s.take<uint32_t>(sl.cands);
+  v.cdest = s.take<uint32_t>(sl.cands);
+  v.cslot = s.take<uint32_t>(sl.cands);
+  v.lead = s.take<uint32_t>(2 * (size_t)ltab);
   if (d) {
     v.off = f->dev.offsets;
     v.arcs = f->dev.arcs;
@@ -984,7 +980,7 @@ size_t carve_slice(unsigned char* base, size_t at, const Slice& sl, const wfst_f
     v.cap = Caps{(uint32_t)sl.states, (uint32_t)sl.elts, (uint32_t)sl.arcs, (uint32_t)sl.cands, slots, ltab, max_states, 1u << 28};
     *d = v;
   }
-  return at;
+  return s.at();
 }
 bool lds_scratch_knob() {
   const char* e = std::getenv("WFST_DETERMINIZE_BATCH_SCRATCH");
@@ -993,22 +989,18 @@ bool lds_scratch_knob() {
   if (!std::strcmp(e, "global")) return false;
   throw Error(std::string("WFST_DETERMINIZE_BATCH_SCRATCH: expected lds or global, not '") + e + "'");
 }
-bool min_arena_knob() {  // tests: the first launch's slices as small as the kernel allows, so that every item grows
-  const char* e = std::getenv("WFST_DETERMINIZE_BATCH_ARENA");
-  if (!e || !*e) return false;
-  if (!std::strcmp(e, "min")) return true;
-  throw Error(std::string("WFST_DETERMINIZE_BATCH_ARENA: expected min, not '") + e + "'");
-}
 }  // namespace
 
+// the host loop is batch_driver.h's, with the grow loop and without a slab limit
 void determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, uint32_t det_type, wfst_fst** outs,
                        uint8_t* in_kernel, const float* const* in_dist, const uint64_t* n_in_dist, std::vector<float>* out_dist,
                        std::vector<uint64_t>* out_off) {
-  ctx->det_batch_launches = ctx->det_batch_in_kernel = ctx->det_batch_single = 0;
+  ctx->det_batch = {};
+  // (no check_items_owned: this call has never refused an item of another device or context)
   // every stored word before anything is launched
   for (size_t i = 0; i < n; ++i)
     if (!(fsts[i]->props & props::ACCEPTOR)) throw Error("item " + std::to_string(i) + ": " + NOT_ACCEPTOR_MSG);
-  const bool use_lds = lds_scratch_knob(), min_arena = min_arena_knob();
+  const bool use_lds = lds_scratch_knob(), min_arena = arena_min_knob("WFST_DETERMINIZE_BATCH_ARENA");
   const uint32_t max_states = max_states_knob();
   hipStream_t st = ctx->stream;
   enum : uint8_t { OPEN, DONE, SINGLE, TRIVIAL };
@@ -1043,120 +1035,70 @@ void determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, flo
     HIP_CHECK(hipStreamSynchronize(st));
   }
   auto n_in = [&](size_t i) { return (uint32_t)std::min<uint64_t>(n_in_dist[i], 0xFFFFFFFFull); };
-  std::vector<DBuf<unsigned char>> slabs;  // one per launch; the results of finished items stay in theirs until adopted
-  size_t first_err = n;
+  size_t first_err = n;  // the in-flight KO: the lowest index wins, thrown after the loop
+  auto carve = [&](size_t i, Slab s, Det* d) { return carve_slice(s, slice[i], fsts[i], delta, max_states, d); };
+  auto init = [&](size_t i) {
+    Ctl c{};
+    c.hi = 1;
+    c.n_elts = 1;
+    c.start = (uint32_t)fsts[i]->start;
+    return c;
+  };
+  const uint32_t lds_bytes = use_lds ? (uint32_t)BATCH_LDS_BYTES : 0u;
+  auto launch = [&](const Det* d_dets, uint32_t m) { det_batch_kernel<<<m, TPB, lds_bytes, st>>>(d_dets, lds_bytes); };
+  auto classify = [&](size_t i, const Ctl& c, const Det& d) {
+    if (c.exit == 4) {
+      state[i] = DONE;
+      done[i] = Done{c.hi, c.n_arcs, d.aoff, d.so, d.oarc, d.ofin, d.se};
+      return BatchExit::FINISHED;
+    }
+    if (c.exit == 1 || c.exit == 5) {
+      if (c.exit == 5) first_err = std::min(first_err, i);  // (its single path never runs: the call is KO)
+      state[i] = SINGLE;
+      return BatchExit::SINGLE;
+    }
+    if (c.exit != 3) throw Error("determinize_batch: unexpected exit code " + std::to_string(c.exit));
+    Slice& sl = slice[i];
+    const uint64_t K = std::max<uint64_t>(c.K, 1);
+    auto up = [](uint64_t& have, uint64_t want) {
+      if (want > have) have = std::max<uint64_t>(2 * have, want);
+    };
+    const Slice before = sl;
+    up(sl.cands, K);
+    up(sl.states, (uint64_t)c.hi + K + 1);
+    up(sl.elts, (uint64_t)c.n_elts + K);
+    up(sl.arcs, (uint64_t)c.n_arcs + K);
+    if (sl.cands == before.cands && sl.states == before.states && sl.elts == before.elts && sl.arcs == before.arcs)
+      return BatchExit::STUCK;
+    if (sl.states > 0x7FFFFFFFull || sl.elts > 0x7FFFFFFFull || sl.arcs > 0x7FFFFFFFull)
+      throw Error("determinize: more than 2^31 states, elements, arcs or level candidates");
+    return BatchExit::GREW;
+  };
   // every launch finishes an item, hands it to the single path, or at least doubles what its slice was short of, and the
   // limits cap the slices: a bounded number of launches
-  while (!open.empty()) {
-    if (ctx->det_batch_launches >= 64) throw Error("determinize_batch: the arenas did not converge");
-    const size_t m = open.size();
-    std::vector<size_t> at(m + 1);
-    size_t bytes = (m * sizeof(Ctl) + 63) & ~(size_t)63;
-    for (size_t k = 0; k < m; ++k) {
-      at[k] = bytes;
-      bytes = carve_slice(nullptr, bytes, slice[open[k]], nullptr, delta, max_states, nullptr);
-    }
-    slabs.emplace_back(*ctx->pool, bytes);
-    unsigned char* base = slabs.back().p;
-    Ctl* d_ctl = (Ctl*)base;
-    std::vector<Det> dets(m);
-    std::vector<Ctl> ctls(m);
-    for (size_t k = 0; k < m; ++k) {
-      const wfst_fst* f = fsts[open[k]];
-      carve_slice(base, at[k], slice[open[k]], f, delta, max_states, &dets[k]);
-      dets[k].ctl = d_ctl + k;
-      Ctl c{};
-      c.hi = 1;
-      c.n_elts = 1;
-      c.start = (uint32_t)f->start;
-      ctls[k] = c;
-    }
-    DBuf<Det> d_dets(*ctx->pool, m);
-    HIP_CHECK(hipMemcpyAsync(d_dets.p, dets.data(), m * sizeof(Det), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_ctl, ctls.data(), m * sizeof(Ctl), hipMemcpyHostToDevice, st));
-    const uint32_t lds_bytes = use_lds ? (uint32_t)BATCH_LDS_BYTES : 0u;
-    det_batch_kernel<<<(uint32_t)m, TPB, lds_bytes, st>>>(d_dets.p, lds_bytes);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(ctls.data(), d_ctl, m * sizeof(Ctl), hipMemcpyDeviceToHost, st));  // the control blocks, once
-    HIP_CHECK(hipStreamSynchronize(st));
-    ctx->det_batch_launches += 1;
-    std::vector<size_t> still;
-    for (size_t k = 0; k < m; ++k) {
-      const size_t i = open[k];
-      const Ctl& c = ctls[k];
-      const Det& d = dets[k];
-      if (c.exit == 4) {
-        state[i] = DONE;
-        done[i] = Done{c.hi, c.n_arcs, d.aoff, d.so, d.oarc, d.ofin, d.se};
-      } else if (c.exit == 1) {
-        state[i] = SINGLE;
-      } else if (c.exit == 5) {
-        first_err = std::min(first_err, i);
-        state[i] = SINGLE;  // (never run: the call is KO)
-      } else if (c.exit == 3) {
-        Slice& sl = slice[i];
-        const uint64_t K = std::max<uint64_t>(c.K, 1);
-        auto up = [](uint64_t& have, uint64_t want) {
-          if (want > have) have = std::max<uint64_t>(2 * have, want);
-        };
-        const Slice before = sl;
-        up(sl.cands, K);
-        up(sl.states, (uint64_t)c.hi + K + 1);
-        up(sl.elts, (uint64_t)c.n_elts + K);
-        up(sl.arcs, (uint64_t)c.n_arcs + K);
-        if (sl.cands == before.cands && sl.states == before.states && sl.elts == before.elts && sl.arcs == before.arcs)
-          throw Error("determinize_batch: a slice reported a need it already covers");
-        if (sl.states > 0x7FFFFFFFull || sl.elts > 0x7FFFFFFFull || sl.arcs > 0x7FFFFFFFull)
-          throw Error("determinize: more than 2^31 states, elements, arcs or level candidates");
-        still.push_back(i);
-      } else {
-        throw Error("determinize_batch: unexpected exit code " + std::to_string(c.exit));
-      }
-    }
-    open.swap(still);
-  }
+  const auto slabs = batch_launch_loop<Det, Ctl>(ctx, ctx->det_batch, {"determinize_batch", BATCH_MAX_LAUNCHES, "a slice"}, std::move(open),
+                                                 carve, init, launch, classify);
   if (first_err < n) throw Error("item " + std::to_string(first_err) + ": " + LIMIT_MSG);
-  try {
-    std::vector<uint64_t> n_out(n, 0);
-    std::vector<std::vector<float>> single_dist(n);
-    // the items with a level too wide for one workgroup: the single-FST path
-    for (size_t i = 0; i < n; ++i) {
-      const uint64_t out_props = props::determinize(fsts[i]->props, det_type != 1);
-      if (state[i] == TRIVIAL) {
-        HostCsr h;
-        h.offsets.push_back(0);
-        outs[i] = make_host_fst(ctx, 0, -1, out_props, std::move(h));
-      } else if (state[i] == SINGLE) {
-        try {
-          if (out_dist) {
-            const DistReq dq{d_in.p + in_at[i], n_in(i), &single_dist[i]};
-            outs[i] = determinize_acceptor(ctx, fsts[i], delta, det_type, &dq);
-          } else {
-            outs[i] = determinize_acceptor(ctx, fsts[i], delta, det_type);
-          }
-        } catch (const std::exception& e) {
-          throw Error("item " + std::to_string(i) + ": " + e.what());
-        }
-        n_out[i] = outs[i]->n_states;
-        ctx->det_batch_single += 1;
-      } else {
-        n_out[i] = done[i].N;
-      }
-      if (in_kernel) in_kernel[i] = state[i] != SINGLE;
-      if (state[i] != SINGLE) ctx->det_batch_in_kernel += 1;
-    }
-    // the items the kernel finished: one adoption, one distance launch
-    std::vector<size_t> idx;
-    std::vector<AdoptDesc> descs;
-    for (size_t i = 0; i < n; ++i)
-      if (state[i] == DONE) {
-        idx.push_back(i);
-        descs.push_back(AdoptDesc{done[i].N, done[i].n_arcs, 0, props::determinize(fsts[i]->props, det_type != 1), done[i].aoff,
-                                  done[i].oarc, done[i].ofin});
-      }
-    std::vector<float> kd;      // out_dist of the kernel's items, in idx order
+  std::vector<std::vector<float>> single_dist(n);
+  auto outcome = [&](size_t i) {
+    const uint64_t out_props = props::determinize(fsts[i]->props, det_type != 1);
+    if (state[i] == SINGLE) return BatchOutcome::single();  // a level too wide for one workgroup
+    if (state[i] == DONE) return BatchOutcome::adopt({done[i].N, done[i].n_arcs, 0, out_props, done[i].aoff, done[i].oarc, done[i].ofin});
+    HostCsr h;
+    h.offsets.push_back(0);
+    return BatchOutcome::handle(make_host_fst(ctx, 0, -1, out_props, std::move(h)));
+  };
+  auto single = [&](size_t i) {
+    if (!out_dist) return determinize_acceptor(ctx, fsts[i], delta, det_type);
+    const DistReq dq{d_in.p + in_at[i], n_in(i), &single_dist[i]};
+    return determinize_acceptor(ctx, fsts[i], delta, det_type, &dq);
+  };
+  // out_dist: one distance launch for the items the kernel finished (idx), the single path's own for the others
+  auto distances = [&](const std::vector<size_t>& idx) {
+    if (!out_dist) return;
+    std::vector<float> kd;  // out_dist of the kernel's items, in idx order
     std::vector<uint32_t> koff(idx.size() + 1, 0);
-    if (out_dist && !idx.empty()) {
+    if (!idx.empty()) {
       std::vector<DistJob> jobs(idx.size());
       uint64_t tot = 0;
       for (size_t k = 0; k < idx.size(); ++k) {
@@ -1178,27 +1120,15 @@ void determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, flo
       HIP_CHECK(hipMemcpyAsync(kd.data(), d_out.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
     }
-    if (!idx.empty()) {
-      std::vector<wfst_fst*> got(idx.size(), nullptr);
-      adopt_device_many(ctx, idx.size(), descs.data(), got.data());
-      for (size_t k = 0; k < idx.size(); ++k) outs[idx[k]] = got[k];
-    }
-    if (out_dist) {
-      out_off->assign(n + 1, 0);
-      for (size_t i = 0; i < n; ++i) (*out_off)[i + 1] = (*out_off)[i] + n_out[i];
-      out_dist->assign((*out_off)[n], 0.0f);
-      for (size_t k = 0; k < idx.size(); ++k)
-        std::copy(kd.begin() + koff[k], kd.begin() + koff[k + 1], out_dist->begin() + (*out_off)[idx[k]]);
-      for (size_t i = 0; i < n; ++i)
-        if (state[i] == SINGLE) std::copy(single_dist[i].begin(), single_dist[i].end(), out_dist->begin() + (*out_off)[i]);
-    }
-  } catch (...) {
-    for (size_t i = 0; i < n; ++i) {
-      delete outs[i];
-      outs[i] = nullptr;
-    }
-    throw;
-  }
+    out_off->assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) (*out_off)[i + 1] = (*out_off)[i] + (state[i] == SINGLE ? outs[i]->n_states : done[i].N);
+    out_dist->assign((*out_off)[n], 0.0f);
+    for (size_t k = 0; k < idx.size(); ++k)
+      std::copy(kd.begin() + koff[k], kd.begin() + koff[k + 1], out_dist->begin() + (*out_off)[idx[k]]);
+    for (size_t i = 0; i < n; ++i)
+      if (state[i] == SINGLE) std::copy(single_dist[i].begin(), single_dist[i].end(), out_dist->begin() + (*out_off)[i]);
+  };
+  batch_finish(ctx, ctx->det_batch, n, outs, in_kernel, outcome, single, distances);
 }
 
 // determinize_with_distance (determinize_static.rs:24-39): the Functional construction and out_dist, for one acceptor

@@ -34,6 +34,7 @@
 
 #pragma clang fp contract(off)  // (before tropical.h comes in: its functions compile without contraction here too)
 
+#include "batch_driver.h"
 #include "common.h"
 #include "fst_props.h"
 #include "wg_ops.h"
@@ -1240,61 +1241,44 @@ __global__ void __launch_bounds__(MB_TPB) minimize_batch_kernel(const MbItem* __
   }
 }
 
-// carves one item's arrays out of [base + at, ...), every array 64-byte aligned; base == nullptr only measures
-size_t carve_minimize_slice(unsigned char* base, size_t at, uint32_t n, uint32_t E, MbItem* it) {
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 63) & ~(size_t)63;
-    return base ? base + o : nullptr;
-  };
+// carves one item's arrays out of the slab, every array 64-byte aligned; it == nullptr only measures
+size_t carve_minimize_slice(Slab s, uint32_t n, uint32_t E, MbItem* it) {
   const size_t N1 = (size_t)n + 1, E2 = (size_t)E + n;
   const uint32_t tsize = pow2_at_least(2 * E2, "minimize_batch"), ssize = pow2_at_least(2 * N1, "minimize_batch");
   MbItem v{};
-  v.cctl = (uint32_t*)take(4 * C_WORDS);
-  v.roff = (uint32_t*)take(4 * (N1 + 1));
-  v.rcnt = (uint32_t*)take(4 * (N1 + 1));
-  v.rsrc = (uint32_t*)take(4 * E2);
-  v.outdeg = (uint32_t*)take(4 * N1);
-  v.order = (uint32_t*)take(4 * N1);
-  v.d = (float*)take(4 * N1);
-  v.acc = (uint32_t*)take(4 * (N1 + 1));
-  v.co = (uint32_t*)take(4 * (N1 + 1));
-  v.new_id = (uint32_t*)take(4 * (N1 + 1));
-  v.off2 = (uint32_t*)take(4 * (N1 + 1));
-  v.enc = (wfst_tr*)take(sizeof(wfst_tr) * E2);
-  v.tarcs = (wfst_tr*)take(sizeof(wfst_tr) * E2);
-  v.tfin = (float*)take(4 * N1);
-  v.toff = (uint32_t*)take(4 * (N1 + 1));
-  v.keys = (unsigned long long*)take(8 * (size_t)tsize);
-  v.minpos = (uint32_t*)take(4 * (size_t)tsize);
-  v.cls = (uint32_t*)take(4 * N1);
-  v.slot_of = (uint32_t*)take(4 * N1);
-  v.big = (uint32_t*)take(4 * N1);
-  v.tab = (unsigned long long*)take(8 * (size_t)ssize);
-  v.smin = (uint32_t*)take(4 * (size_t)ssize);
-  v.smax = (uint32_t*)take(4 * (size_t)ssize);
-  v.keep = (uint32_t*)take(4 * (N1 + 1));
-  v.new_id2 = (uint32_t*)take(4 * (N1 + 1));
-  v.cnt = (uint32_t*)take(4 * (N1 + 1));
-  v.off_out = (uint32_t*)take(4 * (N1 + 1));
-  v.arcs_out = (wfst_tr*)take(sizeof(wfst_tr) * E2);
-  v.fin_out = (float*)take(4 * N1);
+  v.cctl = s.take<uint32_t>(C_WORDS);
+  v.roff = s.take<uint32_t>(N1 + 1);
+  v.rcnt = s.take<uint32_t>(N1 + 1);
+  v.rsrc = s.take<uint32_t>(E2);
+  v.outdeg = s.take<uint32_t>(N1);
+  v.order = s.take<uint32_t>(N1);
+  v.d = s.take<float>(N1);
+  v.acc = s.take<uint32_t>(N1 + 1);
+  v.co = s.take<uint32_t>(N1 + 1);
+  v.new_id = s.take<uint32_t>(N1 + 1);
+  v.off2 = s.take<uint32_t>(N1 + 1);
+  v.enc = s.take<wfst_tr>(E2);
+  v.tarcs = s.take<wfst_tr>(E2);
+  v.tfin = s.take<float>(N1);
+  v.toff = s.take<uint32_t>(N1 + 1);
+  v.keys = s.take<unsigned long long>(tsize);
+  v.minpos = s.take<uint32_t>(tsize);
+  v.cls = s.take<uint32_t>(N1);
+  v.slot_of = s.take<uint32_t>(N1);
+  v.big = s.take<uint32_t>(N1);
+  v.tab = s.take<unsigned long long>(ssize);
+  v.smin = s.take<uint32_t>(ssize);
+  v.smax = s.take<uint32_t>(ssize);
+  v.keep = s.take<uint32_t>(N1 + 1);
+  v.new_id2 = s.take<uint32_t>(N1 + 1);
+  v.cnt = s.take<uint32_t>(N1 + 1);
+  v.off_out = s.take<uint32_t>(N1 + 1);
+  v.arcs_out = s.take<wfst_tr>(E2);
+  v.fin_out = s.take<float>(N1);
   v.tsize = tsize;
   v.ssize = ssize;
-  if (it) {
-    const MbItem in = *it;  // (the input's side is the caller's)
-    *it = v;
-    it->off = in.off;
-    it->arcs = in.arcs;
-    it->fin = in.fin;
-    it->n = in.n;
-    it->E = in.E;
-    it->start = in.start;
-    it->known = in.known;
-    it->delta = in.delta;
-    it->ctl = in.ctl;
-  }
-  return at;
+  if (it) *it = v;  // (the input's side is the caller's)
+  return s.at();
 }
 
 // what minimize_fst decides on the host, from the stored word and what the kernel left in the item's MbCtl (for an item
@@ -1347,18 +1331,23 @@ MbVerdict minimize_batch_verdict(const wfst_fst* f, const MbCtl& c, bool allow_n
 
 }  // namespace
 
+// the host loop is batch_driver.h's, with the ownership check, one pass (nothing grows) and a slab limit per call
 void minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, bool allow_nondet, wfst_fst** outs,
                     uint8_t* in_kernel) {
   using namespace props;
-  ctx->min_batch_launches = ctx->min_batch_in_kernel = ctx->min_batch_single = 0;
-  for (size_t i = 0; i < n; ++i) {
-    if (fsts[i]->device != ctx->device) throw Error("item " + std::to_string(i) + ": minimize_batch: the FST lives on another device");
-    if (fsts[i]->ctx != ctx) throw Error("item " + std::to_string(i) + ": minimize_batch: the FST belongs to another context");
-  }
+  ctx->min_batch = {};
+  check_items_owned(ctx, fsts, n, "minimize_batch");
   (void)path_knob();  // (a bad WFST_MINIMIZE_PATH is KO here as in the single call)
   hipStream_t st = ctx->stream;
   enum : uint8_t { KERNEL, TRIVIAL, SINGLE };
+  struct Ran {  // what the kernel left of an item: its control block and its result arrays inside the slab
+    MbCtl c{};  // (an item without states: nothing ran, nothing was found)
+    const uint32_t* off = nullptr;
+    const wfst_tr* arcs = nullptr;
+    const float* fin = nullptr;
+  };
   std::vector<uint8_t> kind(n);
+  std::vector<Ran> ran(n);
   std::vector<size_t> run;  // the items that occupy a workgroup
   for (size_t i = 0; i < n; ++i) {
     const wfst_fst* f = fsts[i];
@@ -1371,95 +1360,42 @@ void minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float 
       run.push_back(i);
     }
   }
-  const size_t m = run.size();
-  std::vector<MbCtl> ctls(m);
-  std::vector<MbItem> items(m);
-  DBuf<unsigned char> slab;
-  if (m) {
-    std::vector<size_t> at(m);
-    size_t bytes = (m * sizeof(MbCtl) + 63) & ~(size_t)63;
-    for (size_t k = 0; k < m; ++k) {
-      at[k] = bytes;
-      bytes = carve_minimize_slice(nullptr, bytes, fsts[run[k]]->n_states, (uint32_t)fsts[run[k]]->n_arcs, nullptr);
-    }
-    if (bytes > MB_MAX_SLAB)
-      throw Error("minimize_batch: the list needs " + std::to_string(bytes >> 20) + " MiB of scratch, more than the " +
-                  std::to_string(MB_MAX_SLAB >> 20) + " MiB one call may take: split the list");
-    slab = DBuf<unsigned char>(*ctx->pool, bytes);
-    MbCtl* d_ctl = (MbCtl*)slab.p;
-    for (size_t k = 0; k < m; ++k) {
-      const wfst_fst* f = fsts[run[k]];
-      const uint64_t p = f->props & ALL;
-      MbItem& it = items[k];
-      it.off = f->dev.offsets;
-      it.arcs = f->dev.arcs;
-      it.fin = f->dev.finals;
-      it.n = f->n_states;
-      it.E = (uint32_t)f->n_arcs;
-      it.start = f->start < 0 ? NONE : (uint32_t)f->start;
-      it.known = 0;
-      if (knows(p, ACCEPTOR) && knows(p, I_DETERMINISTIC) && knows(p, WEIGHTED))
-        it.known |= MBK_FACTS | ((p & ACCEPTOR) ? MBK_ACCEPTOR : 0u) | ((p & I_DETERMINISTIC) ? MBK_IDET : 0u) |
-                    ((p & WEIGHTED) ? MBK_WEIGHTED : 0u);
-      if (knows(p, CYCLIC)) it.known |= MBK_CYCLIC_KNOWN | ((p & CYCLIC) ? MBK_CYCLIC : 0u);
-      it.delta = delta;
-      it.ctl = d_ctl + k;
-      carve_minimize_slice(slab.p, at[k], it.n, it.E, &it);
-    }
-    DBuf<MbItem> d_items(*ctx->pool, m);
-    HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), m * sizeof(MbItem), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(d_ctl, 0, m * sizeof(MbCtl), st));
-    minimize_batch_kernel<<<(uint32_t)m, MB_TPB, 0, st>>>(d_items.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(ctls.data(), d_ctl, m * sizeof(MbCtl), hipMemcpyDeviceToHost, st));  // the control blocks, once
-    HIP_CHECK(hipStreamSynchronize(st));
-    ctx->min_batch_launches = 1;
-  }
-  try {
-    // in index order, so that the first KO is the lowest failing index
-    std::vector<size_t> idx;
-    std::vector<AdoptDesc> descs;
-    size_t k = 0;
-    for (size_t i = 0; i < n; ++i) {
-      const wfst_fst* f = fsts[i];
-      if (kind[i] == SINGLE) {
-        try {
-          outs[i] = minimize_fst(ctx, f, delta, allow_nondet);
-        } catch (const std::exception& e) {
-          throw Error("item " + std::to_string(i) + ": " + e.what());
-        }
-        ctx->min_batch_single += 1;
-        continue;
-      }
-      const MbCtl none{};  // (an item without states: nothing ran, nothing was found)
-      const MbCtl& c = kind[i] == KERNEL ? ctls[k] : none;
-      if (kind[i] == KERNEL && c.exit == MB_RUNNING) throw Error("minimize_batch: the kernel left item " + std::to_string(i) + " unfinished");
-      const MbVerdict v = minimize_batch_verdict(f, c, allow_nondet);
-      if (v.error) throw Error("item " + std::to_string(i) + ": " + v.error);
-      if (v.empty) {
-        outs[i] = empty_fst(ctx, v.props);
-      } else {
-        const MbItem& it = items[k];
-        idx.push_back(i);
-        descs.push_back(AdoptDesc{c.n_out, c.e_out, (int64_t)c.start_out, v.props & ALL, it.off_out, it.arcs_out, it.fin_out});
-      }
-      if (kind[i] == KERNEL) ++k;
-      ctx->min_batch_in_kernel += 1;
-    }
-    if (!idx.empty()) {  // every result of the kernel out of the slab: one allocation, one synchronisation
-      std::vector<wfst_fst*> got(idx.size(), nullptr);
-      adopt_device_many(ctx, idx.size(), descs.data(), got.data());
-      for (size_t j = 0; j < idx.size(); ++j) outs[idx[j]] = got[j];
-    }
-    if (in_kernel)
-      for (size_t i = 0; i < n; ++i) in_kernel[i] = kind[i] != SINGLE;
-  } catch (...) {
-    for (size_t i = 0; i < n; ++i) {
-      delete outs[i];
-      outs[i] = nullptr;
-    }
-    throw;
-  }
+  auto carve = [&](size_t i, Slab s, MbItem* it) {
+    const wfst_fst* f = fsts[i];
+    const size_t end = carve_minimize_slice(s, f->n_states, (uint32_t)f->n_arcs, it);
+    if (!it) return end;
+    const uint64_t p = f->props & ALL;
+    it->off = f->dev.offsets;
+    it->arcs = f->dev.arcs;
+    it->fin = f->dev.finals;
+    it->n = f->n_states;
+    it->E = (uint32_t)f->n_arcs;
+    it->start = f->start < 0 ? NONE : (uint32_t)f->start;
+    it->known = 0;
+    if (knows(p, ACCEPTOR) && knows(p, I_DETERMINISTIC) && knows(p, WEIGHTED))
+      it->known |= MBK_FACTS | ((p & ACCEPTOR) ? MBK_ACCEPTOR : 0u) | ((p & I_DETERMINISTIC) ? MBK_IDET : 0u) |
+                   ((p & WEIGHTED) ? MBK_WEIGHTED : 0u);
+    if (knows(p, CYCLIC)) it->known |= MBK_CYCLIC_KNOWN | ((p & CYCLIC) ? MBK_CYCLIC : 0u);
+    it->delta = delta;
+    return end;
+  };
+  auto launch = [&](const MbItem* d_items, uint32_t m) { minimize_batch_kernel<<<m, MB_TPB, 0, st>>>(d_items); };
+  auto classify = [&](size_t i, const MbCtl& c, const MbItem& it) {
+    ran[i] = Ran{c, it.off_out, it.arcs_out, it.fin_out};
+    return BatchExit::FINISHED;
+  };
+  const auto slabs = batch_launch_loop<MbItem, MbCtl>(ctx, ctx->min_batch, {"minimize_batch", 1, nullptr, MB_MAX_SLAB, "call"},
+                                                      std::move(run), carve, nullptr, launch, classify);
+  auto outcome = [&](size_t i) {
+    if (kind[i] == SINGLE) return BatchOutcome::single();
+    const MbCtl& c = ran[i].c;
+    if (kind[i] == KERNEL && c.exit == MB_RUNNING) throw Error("minimize_batch: the kernel left item " + std::to_string(i) + " unfinished");
+    const MbVerdict v = minimize_batch_verdict(fsts[i], c, allow_nondet);
+    if (v.error) throw Error("item " + std::to_string(i) + ": " + v.error);
+    if (v.empty) return BatchOutcome::handle(empty_fst(ctx, v.props));
+    return BatchOutcome::adopt({c.n_out, c.e_out, (int64_t)c.start_out, v.props & ALL, ran[i].off, ran[i].arcs, ran[i].fin});
+  };
+  batch_finish(ctx, ctx->min_batch, n, outs, in_kernel, outcome, [&](size_t i) { return minimize_fst(ctx, fsts[i], delta, allow_nondet); });
 }
 
 }  // namespace wfst

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_driver.h"
 #include "common.h"
 #include "rm_expand.h"
 #include "wg_ops.h"
@@ -39,7 +40,6 @@ constexpr uint32_t RB_MAX_STATES = 4096;  // the in_kernel rule (include/wfst.h)
 constexpr uint32_t RB_MAX_ARCS = 16384;
 constexpr RmCaps RB_CAPS{64, 128, 128};   // ... and its third condition: the last rung of rm_epsilon_fst's one-thread kernel
 constexpr size_t RB_MAX_SLAB = (size_t)8 << 30;  // all slices of one launch together; beyond: KO before that launch
-constexpr uint32_t RB_MAX_LAUNCHES = 64;
 // exit codes of an item (RbCtl::exit)
 enum : uint32_t { RB_RUNNING = 0, RB_DONE = 1, RB_EMPTY = 2, RB_GROW = 3, RB_SINGLE_CYCLE = 4, RB_SINGLE_CAPS = 5 };
 
@@ -263,69 +263,47 @@ __global__ void __launch_bounds__(MB_TPB) rm_epsilon_batch_kernel(const RbItem* 
   }
 }
 
-// carves one item's arrays out of [base + at, ...), every array 64-byte aligned; base == nullptr only measures
-size_t carve_rm_slice(unsigned char* base, size_t at, uint32_t n, uint32_t E, uint32_t cap, RbItem* it) {
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 63) & ~(size_t)63;
-    return base ? base + o : nullptr;
-  };
+// carves one item's arrays out of the slab, every array 64-byte aligned; it == nullptr only measures
+size_t carve_rm_slice(Slab s, uint32_t n, uint32_t E, uint32_t cap, RbItem* it) {
   const size_t N = n, N1 = (size_t)n + 1, R = std::max(E, cap);
   const uint32_t n_slices = std::min(n, MB_TPB);
   RbItem v{};
-  v.noneps = (uint32_t*)take(4 * N);
-  v.edeg = (uint32_t*)take(4 * N);
-  v.roff = (uint32_t*)take(4 * N1);
-  v.rcnt = (uint32_t*)take(4 * N1);
-  v.rsrc = (uint32_t*)take(4 * R);
-  v.order = (uint32_t*)take(4 * N);
-  v.lend = (uint32_t*)take(4 * N);
-  v.done = (uint32_t*)take(4 * N);
-  v.cnt = (uint32_t*)take(4 * N1);
-  v.arc_ptr = (unsigned long long*)take(8 * N);
-  v.fin = (float*)take(4 * N);
-  v.scratch = (char*)take(rm_slice_bytes(RB_CAPS) * n_slices);
-  v.arena = (wfst_tr*)take(sizeof(wfst_tr) * (size_t)cap);
-  v.off1 = (uint32_t*)take(4 * N1);
-  v.pre = (wfst_tr*)take(sizeof(wfst_tr) * (size_t)cap);
-  v.acc = (uint32_t*)take(4 * N1);
-  v.co = (uint32_t*)take(4 * N1);
-  v.keep = (uint32_t*)take(4 * N1);
-  v.new_id = (uint32_t*)take(4 * N1);
-  v.cnt2 = (uint32_t*)take(4 * N1);
-  v.off_out = (uint32_t*)take(4 * N1);
-  v.fin_out = (float*)take(4 * N);
+  v.noneps = s.take<uint32_t>(N);
+  v.edeg = s.take<uint32_t>(N);
+  v.roff = s.take<uint32_t>(N1);
+  v.rcnt = s.take<uint32_t>(N1);
+  v.rsrc = s.take<uint32_t>(R);
+  v.order = s.take<uint32_t>(N);
+  v.lend = s.take<uint32_t>(N);
+  v.done = s.take<uint32_t>(N);
+  v.cnt = s.take<uint32_t>(N1);
+  v.arc_ptr = s.take<unsigned long long>(N);
+  v.fin = s.take<float>(N);
+  v.scratch = s.take<char>(rm_slice_bytes(RB_CAPS) * n_slices);
+  v.arena = s.take<wfst_tr>(cap);
+  v.off1 = s.take<uint32_t>(N1);
+  v.pre = s.take<wfst_tr>(cap);
+  v.acc = s.take<uint32_t>(N1);
+  v.co = s.take<uint32_t>(N1);
+  v.keep = s.take<uint32_t>(N1);
+  v.new_id = s.take<uint32_t>(N1);
+  v.cnt2 = s.take<uint32_t>(N1);
+  v.off_out = s.take<uint32_t>(N1);
+  v.fin_out = s.take<float>(N);
   v.n = n;
   v.cap = cap;
   v.n_slices = n_slices;
-  if (it) {
-    const RbItem in = *it;  // (the input's side is the caller's)
-    *it = v;
-    it->off = in.off;
-    it->arcs = in.arcs;
-    it->fin_in = in.fin_in;
-    it->start = in.start;
-    it->ctl = in.ctl;
-  }
-  return at;
-}
-
-bool min_arena_knob() {  // tests: the first launch's arc arenas as small as the kernel allows, so that every item grows
-  const char* e = std::getenv("WFST_RM_EPSILON_BATCH_ARENA");
-  if (!e || !*e) return false;
-  if (!std::strcmp(e, "min")) return true;
-  throw Error(std::string("WFST_RM_EPSILON_BATCH_ARENA: expected min, not '") + e + "'");
+  if (it) *it = v;  // (the input's side is the caller's)
+  return s.at();
 }
 
 }  // namespace
 
+// the host loop is batch_driver.h's, with the ownership check, the grow loop and a slab limit per launch
 void rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
-  ctx->rm_batch_launches = ctx->rm_batch_in_kernel = ctx->rm_batch_single = 0;
-  for (size_t i = 0; i < n; ++i) {
-    if (fsts[i]->device != ctx->device) throw Error("item " + std::to_string(i) + ": rm_epsilon_batch: the FST lives on another device");
-    if (fsts[i]->ctx != ctx) throw Error("item " + std::to_string(i) + ": rm_epsilon_batch: the FST belongs to another context");
-  }
-  const bool min_arena = min_arena_knob();
+  ctx->rm_batch = {};
+  check_items_owned(ctx, fsts, n, "rm_epsilon_batch");
+  const bool min_arena = arena_min_knob("WFST_RM_EPSILON_BATCH_ARENA");
   hipStream_t st = ctx->stream;
   enum : uint8_t { OPEN, DONE, EMPTY, SINGLE, TRIVIAL };
   struct Result {
@@ -351,108 +329,51 @@ void rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst
       open.push_back(i);
     }
   }
-  std::vector<DBuf<unsigned char>> slabs;  // one per launch; the results of finished items stay in theirs until adopted
+  auto carve = [&](size_t i, Slab s, RbItem* it) {
+    const wfst_fst* f = fsts[i];
+    const size_t end = carve_rm_slice(s, f->n_states, (uint32_t)f->n_arcs, cap[i], it);
+    if (it) {
+      it->off = f->dev.offsets;
+      it->arcs = f->dev.arcs;
+      it->fin_in = f->dev.finals;
+      it->start = (uint32_t)f->start;
+    }
+    return end;
+  };
+  auto launch = [&](const RbItem* d_items, uint32_t m) { rm_epsilon_batch_kernel<<<m, MB_TPB, 0, st>>>(d_items); };
+  auto classify = [&](size_t i, const RbCtl& c, const RbItem& it) {
+    if (c.exit == RB_DONE) {
+      state[i] = DONE;
+      res[i] = Result{c.facts, c.n_out, c.e_out, c.start_out, it.off_out, it.arena, it.fin_out};
+    } else if (c.exit == RB_EMPTY) {
+      state[i] = EMPTY;
+      res[i].facts = c.facts;
+    } else if (c.exit == RB_SINGLE_CYCLE || c.exit == RB_SINGLE_CAPS) {
+      state[i] = SINGLE;
+      return BatchExit::SINGLE;
+    } else if (c.exit == RB_GROW) {
+      if (c.need_arcs <= cap[i]) return BatchExit::STUCK;
+      cap[i] = (uint32_t)std::max<uint64_t>(2ull * cap[i], c.need_arcs);
+      return BatchExit::GREW;
+    } else {
+      throw Error("rm_epsilon_batch: the kernel left item " + std::to_string(i) + " with exit code " + std::to_string(c.exit));
+    }
+    return BatchExit::FINISHED;
+  };
   // every launch finishes an item, hands it to the single path, or at least doubles its arena, and 4096 states of at most
   // 128 arcs bound the arena: a bounded number of launches
-  while (!open.empty()) {
-    if (ctx->rm_batch_launches >= RB_MAX_LAUNCHES) throw Error("rm_epsilon_batch: the arenas did not converge");
-    const size_t m = open.size();
-    std::vector<size_t> at(m);
-    size_t bytes = (m * sizeof(RbCtl) + 63) & ~(size_t)63;
-    for (size_t k = 0; k < m; ++k) {
-      const wfst_fst* f = fsts[open[k]];
-      at[k] = bytes;
-      bytes = carve_rm_slice(nullptr, bytes, f->n_states, (uint32_t)f->n_arcs, cap[open[k]], nullptr);
-    }
-    if (bytes > RB_MAX_SLAB)
-      throw Error("rm_epsilon_batch: the list needs " + std::to_string(bytes >> 20) + " MiB of scratch, more than the " +
-                  std::to_string(RB_MAX_SLAB >> 20) + " MiB one launch may take: split the list");
-    slabs.emplace_back(*ctx->pool, bytes);
-    unsigned char* base = slabs.back().p;
-    RbCtl* d_ctl = (RbCtl*)base;
-    std::vector<RbItem> items(m);
-    std::vector<RbCtl> ctls(m);
-    for (size_t k = 0; k < m; ++k) {
-      const wfst_fst* f = fsts[open[k]];
-      RbItem& it = items[k];
-      it.off = f->dev.offsets;
-      it.arcs = f->dev.arcs;
-      it.fin_in = f->dev.finals;
-      it.start = (uint32_t)f->start;
-      it.ctl = d_ctl + k;
-      carve_rm_slice(base, at[k], f->n_states, (uint32_t)f->n_arcs, cap[open[k]], &it);
-    }
-    DBuf<RbItem> d_items(*ctx->pool, m);
-    HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), m * sizeof(RbItem), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(d_ctl, 0, m * sizeof(RbCtl), st));
-    rm_epsilon_batch_kernel<<<(uint32_t)m, MB_TPB, 0, st>>>(d_items.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(ctls.data(), d_ctl, m * sizeof(RbCtl), hipMemcpyDeviceToHost, st));  // the control blocks, once
-    HIP_CHECK(hipStreamSynchronize(st));
-    ctx->rm_batch_launches += 1;
-    std::vector<size_t> still;
-    for (size_t k = 0; k < m; ++k) {
-      const size_t i = open[k];
-      const RbCtl& c = ctls[k];
-      if (c.exit == RB_DONE) {
-        state[i] = DONE;
-        res[i] = Result{c.facts, c.n_out, c.e_out, c.start_out, items[k].off_out, items[k].arena, items[k].fin_out};
-      } else if (c.exit == RB_EMPTY) {
-        state[i] = EMPTY;
-        res[i].facts = c.facts;
-      } else if (c.exit == RB_SINGLE_CYCLE || c.exit == RB_SINGLE_CAPS) {
-        state[i] = SINGLE;
-      } else if (c.exit == RB_GROW) {
-        if (c.need_arcs <= cap[i]) throw Error("rm_epsilon_batch: an arena reported a need it already covers");
-        cap[i] = (uint32_t)std::max<uint64_t>(2ull * cap[i], c.need_arcs);
-        still.push_back(i);
-      } else {
-        throw Error("rm_epsilon_batch: the kernel left item " + std::to_string(i) + " with exit code " + std::to_string(c.exit));
-      }
-    }
-    open.swap(still);
-  }
-  try {
-    // in index order, so that the first KO is the lowest failing index
-    std::vector<size_t> idx;
-    std::vector<AdoptDesc> descs;
-    for (size_t i = 0; i < n; ++i) {
-      const wfst_fst* f = fsts[i];
-      if (state[i] == SINGLE) {
-        try {
-          outs[i] = rm_epsilon_fst(ctx, f);
-        } catch (const std::exception& e) {
-          throw Error("item " + std::to_string(i) + ": " + e.what());
-        }
-        ctx->rm_batch_single += 1;
-        continue;
-      }
-      ctx->rm_batch_in_kernel += 1;
-      if (state[i] == EMPTY) {
-        outs[i] = rm_epsilon_empty(ctx, rm_epsilon_word(f->props, res[i].facts));
-        continue;
-      }
-      idx.push_back(i);
-      if (state[i] == TRIVIAL)  // rm_epsilon_fst's own answer: a copy of the input, word included
-        descs.push_back(AdoptDesc{f->n_states, f->n_arcs, -1, f->props, f->dev.offsets, f->dev.arcs, f->dev.finals});
-      else
-        descs.push_back(AdoptDesc{res[i].n_out, res[i].e_out, (int64_t)res[i].start_out, rm_epsilon_word(f->props, res[i].facts),
-                                  res[i].off, res[i].arcs, res[i].fin});
-    }
-    if (!idx.empty()) {  // every result of the kernel out of the slabs: one allocation, one synchronisation
-      std::vector<wfst_fst*> got(idx.size(), nullptr);
-      adopt_device_many(ctx, idx.size(), descs.data(), got.data());
-      for (size_t j = 0; j < idx.size(); ++j) outs[idx[j]] = got[j];
-    }
-    if (in_kernel)
-      for (size_t i = 0; i < n; ++i) in_kernel[i] = state[i] != SINGLE;
-  } catch (...) {
-    for (size_t i = 0; i < n; ++i) {
-      delete outs[i];
-      outs[i] = nullptr;
-    }
-    throw;
-  }
+  const auto slabs = batch_launch_loop<RbItem, RbCtl>(ctx, ctx->rm_batch, {"rm_epsilon_batch", BATCH_MAX_LAUNCHES, "an arena", RB_MAX_SLAB, "launch"},
+                                                      std::move(open), carve, nullptr, launch, classify);
+  auto outcome = [&](size_t i) {
+    const wfst_fst* f = fsts[i];
+    if (state[i] == SINGLE) return BatchOutcome::single();
+    if (state[i] == EMPTY) return BatchOutcome::handle(rm_epsilon_empty(ctx, rm_epsilon_word(f->props, res[i].facts)));
+    if (state[i] == TRIVIAL)  // rm_epsilon_fst's own answer: a copy of the input, word included
+      return BatchOutcome::adopt({f->n_states, f->n_arcs, -1, f->props, f->dev.offsets, f->dev.arcs, f->dev.finals});
+    return BatchOutcome::adopt({res[i].n_out, res[i].e_out, (int64_t)res[i].start_out, rm_epsilon_word(f->props, res[i].facts),
+                                res[i].off, res[i].arcs, res[i].fin});
+  };
+  batch_finish(ctx, ctx->rm_batch, n, outs, in_kernel, outcome, [&](size_t i) { return rm_epsilon_fst(ctx, fsts[i]); });
 }
 
 }  // namespace wfst

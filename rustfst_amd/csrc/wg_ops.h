@@ -1,6 +1,6 @@
 // wg_ops.h — passes of ONE workgroup of MB_TPB threads over arrays in global memory, separated by barriers: fill, exclusive
 // scan, transpose of a CSR, frontier search.  What the one-workgroup-per-item batch kernels (minimize_batch_kernel in
-// minimize.hip, rm_epsilon_batch_kernel in rm_epsilon_batch.hip) are made of.
+// minimize.hip, rm_epsilon_batch_kernel in rm_epsilon_batch.hip) are made of; their host side is batch_driver.h.
 #pragma once
 #include "common.h"
 

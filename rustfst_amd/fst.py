@@ -717,27 +717,43 @@ def _handles(fsts):
     return fsts._arr if isinstance(fsts, HandleArray) else (C.c_void_p * n)(*[f._h.value if isinstance(f._h, C.c_void_p) else f._h for f in fsts])
 
 
+def _first_ctx(fsts):
+    return (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
+
+
+def _batch_call(fn_name, fsts, ctx, want_flags, *config):
+    """fn_name(ctx, fsts, n, *config, outs, in_kernel) of the one-workgroup-per-item batch calls: the results, and with
+    want_flags the uint8 array in_kernel too"""
+    n = len(fsts)
+    if n == 0:
+        return ([], np.zeros(0, np.uint8)) if want_flags else []
+    ctx = ctx or _first_ctx(fsts)
+    outs = (C.c_void_p * n)()
+    flags = np.zeros(n, np.uint8)
+    check(getattr(_lib.lib(), fn_name)(ctx._h, _handles(fsts), n, *config, outs, flags.ctypes.data), fn_name)
+    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
+    return (res, flags) if want_flags else res
+
+
+def _batch_stats(fn_name, ctx):
+    ctx = ctx or default_context()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(getattr(_lib.lib(), fn_name)(ctx._h, C.byref(a), C.byref(b), C.byref(c)), fn_name)
+    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+
+
 def determinize_batch(fsts: Sequence[DeviceFst], config: Optional["DeterminizeConfig"] = None,
                       ctx: Optional[Context] = None, want_flags: bool = False):
     """[f.determinize(config) for f in fsts] as ONE call (wfst_determinize_batch): one workgroup per acceptor, one launch
     for the batch — the form for the many small lattices of a decoding batch.  want_flags: also the uint8 array that
     says which items the batch kernel constructed (0: a level of more than 256 states or 8192 raw candidates sent the
     item through the single-FST path)."""
-    n = len(fsts)
-    if n == 0:
-        return ([], np.zeros(0, np.uint8)) if want_flags else []
-    ctx = ctx or fsts[0].ctx
-    outs = (C.c_void_p * n)()
-    flags = np.zeros(n, np.uint8)
-    check(_lib.lib().wfst_determinize_batch(ctx._h, _handles(fsts), n, config._c() if config is not None else None, outs,
-                                            flags.ctypes.data), "wfst_determinize_batch")
-    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
-    return (res, flags) if want_flags else res
+    return _batch_call("wfst_determinize_batch", fsts, ctx, want_flags, config._c() if config is not None else None)
 
 
 def _list_call(fn_name, fsts, ctx, what):
     n = len(fsts)
-    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
+    ctx = ctx or _first_ctx(fsts)
     out = C.c_void_p()
     check(getattr(_lib.lib(), fn_name)(ctx._h, _handles(fsts), n, C.byref(out)), what)
     return DeviceFst(out, ctx)
@@ -755,11 +771,7 @@ def _device_concat_list(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None
 
 def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last determinize_batch / determinize_with_distance_batch call of ctx (wfst_ctx_get_determinize_batch_stats)."""
-    ctx = ctx or default_context()
-    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    check(_lib.lib().wfst_ctx_get_determinize_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
-          "wfst_ctx_get_determinize_batch_stats")
-    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+    return _batch_stats("wfst_ctx_get_determinize_batch_stats", ctx)
 
 
 def rm_epsilon_stats(ctx: Optional[Context] = None) -> dict:
@@ -778,25 +790,12 @@ def minimize_batch(fsts: Sequence[DeviceFst], config: Optional["MinimizeConfig"]
     lattices of a decoding batch.  return_in_kernel: also the uint8 array that says which items the batch kernel
     minimized (0: more than 4096 states or 16384 arcs sent the item through the single-FST path).  Any item that
     f.minimize would refuse raises WfstError with "item <i>: " in front of that call's message."""
-    n = len(fsts)
-    if n == 0:
-        return ([], np.zeros(0, np.uint8)) if return_in_kernel else []
-    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
-    outs = (C.c_void_p * n)()
-    flags = np.zeros(n, np.uint8)
-    check(_lib.lib().wfst_minimize_batch(ctx._h, _handles(fsts), n, config._c() if config is not None else None, outs,
-                                         flags.ctypes.data), "wfst_minimize_batch")
-    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
-    return (res, flags) if return_in_kernel else res
+    return _batch_call("wfst_minimize_batch", fsts, ctx, return_in_kernel, config._c() if config is not None else None)
 
 
 def minimize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last minimize_batch call of ctx (wfst_ctx_get_minimize_batch_stats)."""
-    ctx = ctx or default_context()
-    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    check(_lib.lib().wfst_ctx_get_minimize_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
-          "wfst_ctx_get_minimize_batch_stats")
-    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+    return _batch_stats("wfst_ctx_get_minimize_batch_stats", ctx)
 
 
 def rm_epsilon_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
@@ -806,24 +805,12 @@ def rm_epsilon_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, r
     array that says which items the batch kernel finished (0: more than 4096 states or 16384 arcs, an epsilon cycle, or a
     rewritten state beyond a closure of 64 states, 128 stack entries or 128 arcs sent the item through the single-FST
     path).  Any item that f.rm_epsilon would refuse raises WfstError with "item <i>: " in front of that call's message."""
-    n = len(fsts)
-    if n == 0:
-        return ([], np.zeros(0, np.uint8)) if return_in_kernel else []
-    ctx = ctx or (fsts._keep[0] if isinstance(fsts, HandleArray) else fsts[0]).ctx
-    outs = (C.c_void_p * n)()
-    flags = np.zeros(n, np.uint8)
-    check(_lib.lib().wfst_rm_epsilon_batch(ctx._h, _handles(fsts), n, outs, flags.ctypes.data), "wfst_rm_epsilon_batch")
-    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
-    return (res, flags) if return_in_kernel else res
+    return _batch_call("wfst_rm_epsilon_batch", fsts, ctx, return_in_kernel)
 
 
 def rm_epsilon_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last rm_epsilon_batch call of ctx (wfst_ctx_get_rm_epsilon_batch_stats)."""
-    ctx = ctx or default_context()
-    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    check(_lib.lib().wfst_ctx_get_rm_epsilon_batch_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)),
-          "wfst_ctx_get_rm_epsilon_batch_stats")
-    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
+    return _batch_stats("wfst_ctx_get_rm_epsilon_batch_stats", ctx)
 
 
 def _take_floats(ptr, count):
@@ -853,7 +840,7 @@ def determinize_with_distance_batch(fsts: Sequence[DeviceFst], in_dists, delta: 
         raise ValueError("one in_dist per FST")
     if n == 0:
         return ([], np.zeros(0, np.uint8)) if want_flags else []
-    ctx = ctx or fsts[0].ctx
+    ctx = ctx or _first_ctx(fsts)
     ds = [np.ascontiguousarray(d, np.float32) for d in in_dists]
     ptrs = (C.c_void_p * n)(*[d.ctypes.data if len(d) else None for d in ds])
     lens = (C.c_uint64 * n)(*[len(d) for d in ds])
