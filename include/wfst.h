@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -435,6 +435,14 @@ wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launche
  *      parked their scratch (armed), solves that started from parked scratch (adopted), and parked scratch that was given back
  *      unused (dropped).  Any pointer after ctx may be NULL.  WFST_SSSP_REARM=0 switches the mechanism off. ---- */
 wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* adopted, uint64_t* dropped);
+/* ---- the bounded head of the single-shortest-path relaxation: where no arc or final weight is negative, the
+ *      first launch of a repeated wfst_shortest_path(nshortest = 1) query ends the search as soon as the best final state is
+ *      settled and nothing pending can come in at or below its total (the textbook early stop); the returned path, weight and
+ *      tied_choices are those of the full solve.  Counters of ctx since its creation: queries the head ended (stops), queries of
+ *      the large-FST route that ran the full solve (full_solves), and why the last of those did (last_reason: a static string,
+ *      "" before the first; not to be freed).  Any pointer after ctx may be NULL.  WFST_SSSP_BOUNDED=0 switches it off;
+ *      wfst_shortest_distance, n-best queries, reweight and push_weights never use it. ---- */
+wfst_status wfst_ctx_get_bounded_stats(wfst_ctx* ctx, uint64_t* stops, uint64_t* full_solves, const char** last_reason);
 /* hipFree of every block the context's device pool holds without an owner: cached blocks and parked scratch (the pool does
  *      the same by itself when an allocation fails).  Synchronises the device.  Live buffers are not touched. */
 wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx);

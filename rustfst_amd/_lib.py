@@ -82,6 +82,7 @@ SYMBOLS = [
     ("wfst_rm_epsilon_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
     ("wfst_ctx_get_rm_epsilon_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_ctx_get_rearm_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_ctx_get_bounded_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(C.c_char_p)]),
     ("wfst_ctx_get_small_path_stats", C.c_int, [_vp] + [_P(_u64)] * 7),
     ("wfst_ctx_get_compose_path_stats", C.c_int, [_vp] + [_P(_u64)] * 12),
     ("wfst_ctx_get_determinize_stats", C.c_int, [_vp] + [_P(_u64)] * 19),

@@ -744,6 +744,7 @@ wfst_status wfst_fst_set_start(wfst_ctx* ctx, wfst_fst* fst, uint32_t state) {  
     fst->props = props::set_start(fst->props);
     fst->rev_host.reset();  // reverse(fst) marks the old start state final (reverse.rs:80-86)
     fst->stable_sweeps.store(0, std::memory_order_relaxed);  // (the next queries are queued with a spare launch again)
+    fst->bounded_streak.store(0, std::memory_order_relaxed);  // (... and with the chain of a full solve: the head may not stop from here)
     // (what a solve learned about the launch pattern of the LAST source says little about this one: the first query predicts
     // from it all the same, and a solve that outruns its prediction is continued)
   });
@@ -873,6 +874,14 @@ wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* a
     if (armed) *armed = ctx->rearm_armed;
     if (adopted) *adopted = ctx->rearm_adopted;
     if (dropped) *dropped = ctx->rearm_dropped;
+  });
+}
+wfst_status wfst_ctx_get_bounded_stats(wfst_ctx* ctx, uint64_t* stops, uint64_t* full_solves, const char** last_reason) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (stops) *stops = ctx->bounded_stops;
+    if (full_solves) *full_solves = ctx->bounded_refused;
+    if (last_reason) *last_reason = ctx->bounded_last_refusal;
   });
 }
 wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx) {

@@ -272,6 +272,11 @@ struct wfst_ctx {
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   uint64_t rearm_armed = 0, rearm_adopted = 0, rearm_dropped = 0;  // wfst_ctx_get_rearm_stats
+  // the bounded head of the single-shortest-path relaxation (wfst_ctx_get_bounded_stats): queries it ended, queries that ran
+  // the full solve, and why the last of those did (a string literal); bounded_hold: the query being repeated may not stop
+  uint64_t bounded_stops = 0, bounded_refused = 0;
+  const char* bounded_last_refusal = "";
+  bool bounded_hold = false;
 };
 
 // Device-resident CSR. All arrays live in one arena allocation that may be
@@ -405,6 +410,10 @@ struct wfst_fst {
   // mailbox sweeps: bit k set = launch k of the last solve was NOT a busy wide sweep (idle, hand-over or narrow launch):
   // the next solve gates that launch's bulk loads behind its mode / sleep decision
   mutable std::atomic<uint64_t> last_hint_mask{~0ull};
+  // consecutive single-path queries of this FST that the bounded head ended in launch 0 (sssp_mailbox.h): while it lasts the
+  // next eligible query is queued as that launch (plus a spare one until three in a row).  last_sweeps keeps the count of the
+  // last FULL solve, which is what a solve that cannot stop is sized from.
+  mutable std::atomic<uint32_t> bounded_streak{0};
   mutable std::atomic<uint32_t> stable_sweeps{0};  // consecutive solves that needed exactly last_sweeps launches
   // the lazily built caches above may be requested from several contexts (threads) at once: built under this lock,
   // with buffers taken from the OWNER context's pool (this->ctx), which outlives the handle

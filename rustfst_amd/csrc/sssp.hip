@@ -101,7 +101,12 @@ struct Ctl {
   // point inside the batch and the host will not read the keys again — clean the scratch for the next solve.  Written by every
   // fused tail that has such a launch behind it; the cleaning itself leaves the word alone.
   uint32_t rearm;
+  // the bounded head (mbox_narrow<LOG, true>): launch + 1 of the head that ended the search once the best final state was
+  // settled (0 = none), and enc(B), the best total it had seen.  Every later launch of the chain reads the first word with its
+  // schedule words (mbox_sched_load) and leaves at entry.  bounded_why: why a bounded head that ran did NOT stop (BOUNDED_WHY_*).
+  uint32_t bounded_launch, bounded_b, bounded_why;
 };
+constexpr uint32_t BOUNDED_WHY_BAND = 1, BOUNDED_WHY_GREW = 2, BOUNDED_WHY_OTHER = 3;
 constexpr uint32_t TAIL_BLOCKS = 128;
 constexpr uint32_t TAIL_LIST_BLOCKS = 16;  // ... over the handle's list of final states (RevCsr::fin), 4096 entries each
 // what the host needs from the tail of a solve, written straight into pinned memory by sssp_tail_kernel
@@ -116,6 +121,7 @@ struct TailOut {
   uint32_t early;  // EARLY_*: what sssp_tail_kernel made of the early tail's result
   uint32_t early_src;  // EARLY_SRC_*: where the early tail that published last took the best final state from
   uint32_t rearmed;    // Ctl::rearm as this launch wrote it (0 from a tail without a re-arm launch behind it): the host parks the scratch
+  uint32_t bounded_why;  // Ctl::bounded_why: why the bounded head of this solve did not end it (0: it did, or there was none)
 };
 constexpr uint32_t EARLY_UNCHECKED = 0, EARLY_USED = 1, EARLY_ABSENT = 2, EARLY_REFUTED = 3;
 constexpr uint32_t EARLY_SRC_LIST = 1, EARLY_SRC_BLOCKS = 2;
@@ -1001,6 +1007,11 @@ __device__ __forceinline__ void sssp_early_tail(const EarlyTail& et, const uint3
 // hand-over) instead of searching the list, those words are the keys as they stood BEFORE launch k wrote anything — the
 // limiting case of "read while launch k was writing" — and the same two conditions cover it: a final state whose key launch k
 // lowered ended above B from a value higher still, so it was neither the optimum nor a tie in the words, and is neither now.
+//
+// Behind a BOUNDED head (FLAG_NARROW_BOUNDED in launch 0: sssp_mailbox.h, above mbox_narrow) the same two lines let this
+// kernel run its ordinary, uncertified search and walk on keys that are the fixed point only at and below the head's B: a final
+// state with an unsettled key has a key — hence a total — above B, so it is neither the optimum nor a tie; a predecessor with
+// an unsettled key is not admissible.  advance() treats the flag as "solve over" and the re-arm verdict is `finished`.
 __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict__ finals, const uint64_t* __restrict__ key,
                                                          uint32_t n, const uint2* __restrict__ fin_list, uint32_t n_fin,
                                                          Ctl* __restrict__ ctl,
@@ -1020,7 +1031,8 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   // host-memory writes less at the end of a predicted solve.  By the wave that writes the ticket at the end: ONE
   // system-scope fence orders all of it.
   // Returns (uniform) what SweepDriver::scan_flags will make of the flags on the host: the first launch of the batch whose flag
-  // is 0, FLAG_NARROW_CLEAN or FLAG_RES_ABORT exists and did not abort — the solve is over and nothing will be queued behind it.
+  // is 0, FLAG_NARROW_CLEAN, FLAG_NARROW_BOUNDED or FLAG_RES_ABORT exists and did not abort — the solve is over and nothing will
+  // be queued behind it.
   auto advance = [&]() -> bool {
     const uint32_t base = ctl->base;
     bool finished = false, decided = false;
@@ -1032,7 +1044,7 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
         host_ring[(base + i) % IMP_RING] = v;
         improved_ring[(base + IMP_RING / 2 + i) % IMP_RING] = 0;
       }
-      const unsigned long long stop = __ballot(v == 0u || v == FLAG_NARROW_CLEAN || v == FLAG_RES_ABORT);
+      const unsigned long long stop = __ballot(v == 0u || v == FLAG_NARROW_CLEAN || v == FLAG_RES_ABORT || v == FLAG_NARROW_BOUNDED);
       if (stop != 0ull && !decided) {
         decided = true;
         finished = ((__ballot(v == FLAG_RES_ABORT) >> (__ffsll((long long)stop) - 1)) & 1ull) == 0ull;
@@ -1048,6 +1060,7 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
     const uint32_t v = rearm_on && finished && !(pad & 8u) ? 1u : 0u;
     if (rearm_on) ctl->rearm = v;
     hout->rearmed = v;
+    hout->bounded_why = ctl->bounded_why;
   };
   uint32_t early = EARLY_UNCHECKED;
   if (early_check) {  // (uniform reads: the early tail's launch, then that launch's flag and its least write)
@@ -1341,6 +1354,7 @@ struct Knobs {
   int early_tail = 1;                   // WFST_SSSP_EARLY_TAIL
   int early_best = 1;                   // WFST_SSSP_EARLY_BEST
   int rearm = 1;                        // WFST_SSSP_REARM
+  int bounded = 1;                      // WFST_SSSP_BOUNDED
 };
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
@@ -1381,6 +1395,7 @@ Knobs read_knobs() {
   if (const char* e = env.get("WFST_SSSP_EARLY_TAIL")) k.early_tail = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_EARLY_BEST")) k.early_best = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_REARM")) k.rearm = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_BOUNDED")) k.bounded = std::atoi(e);
   return k;
 }
 
@@ -1419,6 +1434,12 @@ struct Solve {
   size_t mb_dyn = 0;         // dynamic LDS bytes of a mailbox launch
   bool force_big = false;    // tests: the many-blocks variant of the kernel on a small FST (WFST_SSSP_BIG=1)
   decltype(&sssp_mbox_kernel<false>) mbox_kernel = nullptr;  // the variant for this many blocks (bind_mailbox)
+  // the bounded head (mbox_narrow<LOG, true>): launch 0 of this solve is the instance that ends the search once the best final
+  // state is settled (set by shortest_path_n1_begin before the first batch is queued, with EarlyTail::finals); otherwise
+  // `bounded_why` says why the solve is not eligible (WFST_SSSP_BOUNDED=2)
+  decltype(&sssp_mbox_kernel<false>) mbox_head_kernel = nullptr;
+  bool bounded_on = false;
+  const char* bounded_why = "not a repeated single-path query";
   // the early tail (sssp_early_tail): the one-level launches get a workgroup more, which does the tail's work inside the
   // NARROW launch that drains the search (set by shortest_path_n1_begin before the first batch is queued)
   bool early_on = false;
@@ -1598,7 +1619,9 @@ void launch_sweep(const wfst_fst* f, Solve& sv, uint32_t n, hipStream_t st, uint
     else {
       EarlyTail et = sv.early;
       et.seed = sv.armed && abs_sweep == 0 ? (uint32_t)f->start + 1u : 0u;  // (re-armed scratch: no set-up launch seeded the start state)
-      sv.mbox_kernel<<<sv.mv.nb + (sv.early_on && !profile ? 1u : 0u), MB_THREADS, sv.mb_dyn, st>>>(
+      // (launch 0 of a query whose head may end the search: the bounded instance; never under profiling)
+      const auto kernel = sv.bounded_on && abs_sweep == 0 && !profile ? sv.mbox_head_kernel : sv.mbox_kernel;
+      kernel<<<sv.mv.nb + (sv.early_on && !profile ? 1u : 0u), MB_THREADS, sv.mb_dyn, st>>>(
           f->dev.offsets, f->dev.wn, sv.key.p, sv.mv, abs_sweep & 1u, n, sv.improved.p, sv.ctl.p, abs_sweep, sv.delta, sv.near_low, profile,
           hint, sv.narrow_t, et);
     }
@@ -1854,9 +1877,12 @@ void bind_mailbox(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
   if (sv.kn.stg) mv.stg = std::max<uint32_t>(1u, std::min<uint32_t>(mv.stg, *sv.kn.stg));
   sv.force_big = sv.kn.big;
   sv.mbox_kernel = nb > MB_NBMAX || sv.force_big ? sssp_mbox_kernel<true> : sssp_mbox_kernel<false>;
+  sv.mbox_head_kernel = nb > MB_NBMAX || sv.force_big ? sssp_mbox_kernel<true, true> : sssp_mbox_kernel<false, true>;
+  sv.bounded_on = false;  // (shortest_path_n1_begin switches it on)
   sv.mb_dyn = (size_t)nb * mv.stg * sizeof(uint2) + 3u * (size_t)nb * sizeof(uint32_t);
   static OncePerDevice lds_once;
-  raise_dynamic_lds(lds_once, ctx->device, (int)MB_DYN_BUDGET, {(const void*)sssp_mbox_kernel<false>, (const void*)sssp_mbox_kernel<true>});
+  raise_dynamic_lds(lds_once, ctx->device, (int)MB_DYN_BUDGET, {(const void*)sssp_mbox_kernel<false>, (const void*)sssp_mbox_kernel<true>,
+                                                                      (const void*)sssp_mbox_kernel<false, true>, (const void*)sssp_mbox_kernel<true, true>});
   // A mailbox sweep costs its ~10 us chain of dependent trips whatever it expands, up to ~256 states per block: the
   // threshold moves on as soon as the near set is below 1/16 of the states (measured, tools/param_sweep.py: 4096 ->
   // 65536 at 1M / 2M states is 0.407 -> 0.386 and 0.817 -> 0.741 ms; at 300 k states 16384 is the best)
@@ -2135,6 +2161,7 @@ struct SweepDriver {
   uint32_t* host_flags(const SweepBatch& b) const { return h_imp + b.which * IMP_RING; }
 
   bool aborted = false;    // a resident launch raised FLAG_RES_ABORT
+  bool bounded = false;    // a bounded head raised FLAG_NARROW_BOUNDED: the keys above its B are not the fixed point
   uint64_t seen_busy = 0;  // bit k: launch k was a busy WIDE sweep (flag value 1 + MODE_WIDE)
   bool scan_flags(const SweepBatch& b) {  // true when a sweep of the batch changed nothing
     const uint32_t* hf = h_imp + b.which * IMP_RING;
@@ -2147,6 +2174,10 @@ struct SweepDriver {
         return true;
       }
       if (v == FLAG_NARROW_CLEAN) return true;  // a NARROW launch that left nothing anywhere: the fixed point, certified
+      if (v == FLAG_NARROW_BOUNDED) {  // the head settled the best final state: the path is decided, the solve is over
+        bounded = true;
+        return true;
+      }
       // (WIDE and COLLECT launches have every block awake and loading its keys: no gate next time)
       if ((v == 1u + MODE_WIDE || v == 1u + MODE_COLLECT) && b.first + k < 64) seen_busy |= 1ull << (b.first + k);
     }
@@ -2221,11 +2252,14 @@ void dump_trace(wfst_ctx* ctx, const char* path, const unsigned long long* stamp
 }
 
 // the book-keeping of a solve that reached its fixed point after `sweeps` launches
-void record_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, uint32_t sweeps) {
+// (`bounded`: a bounded head ended it — its one launch says nothing about what a full solve of this FST needs)
+void record_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, uint32_t sweeps, bool bounded = false) {
   sv.lease.release();
   sv.sweeps = sweeps;
   ctx->stats.sweeps = sweeps;
-  note_sweeps(f, sweeps);
+  if (!bounded) note_sweeps(f, sweeps);
+  if (bounded) f->bounded_streak.fetch_add(1, std::memory_order_relaxed);
+  else if (sv.bounded_on) f->bounded_streak.store(0, std::memory_order_relaxed);
   if (sv.mbox) dump_trace(ctx, sv.kn.mbox_trace, sv.mb_dbg.p, MB_DBG_SWEEPS, sv.mv.nb, 16);
   if (sv.resident) dump_trace(ctx, sv.kn.res_trace, sv.rs_trace.p, RS_TRACE_LEVELS, sv.mv.nb, 4);
 }
@@ -2243,8 +2277,8 @@ bool finish_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, SweepDriver& drv)
     return false;
   }
   if (sv.resident) ctx->resident_completed();
-  f->last_hint_mask.store(drv.hint_mask(), std::memory_order_relaxed);
-  record_solve(ctx, f, sv, drv.sweeps_done);
+  if (!drv.bounded) f->last_hint_mask.store(drv.hint_mask(), std::memory_order_relaxed);
+  record_solve(ctx, f, sv, drv.sweeps_done, drv.bounded);
   return true;
 }
 struct ResidentHold {  // the repeat of a solve whose resident launch gave up: never a resident one (wfst_ctx::resident_allowed)
@@ -2648,6 +2682,7 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   do j->done_ticket = tickets.fetch_add(1, std::memory_order_relaxed) + 1u; while (j->done_ticket == 0u);
   j->h_tail->done = 0u;
   j->h_tail->rearmed = 0u;
+  j->h_tail->bounded_why = 0u;
   j->rev = reverse_csr(ctx, f, j->need_unique);  // may build the transpose (second query of a large FST): before anything is queued
   if (ctx->profiling) {
     run_relaxation(ctx, f, j->sv);  // per-sweep events: synchronous
@@ -2672,6 +2707,37 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
       j->sv.blk_best_on = true;
       j->sv.early.blk_best_on = 1u;
     }
+  }
+  // The bounded head (sssp_mailbox.h, above mbox_narrow): launch 0 ends the search once the best final state is settled.  Only
+  // where the ordinary tail that follows is the fused one over the handle's list of final states, the launches are mailbox ones
+  // with NARROW launches on 4096-state blocks, and no arc (mbox_eligible) or final weight is negative.  Profiling (1: this
+  // function has returned above; 2: the chain is timed as the relaxation of every arc) runs the full solve, and so do the strict
+  // settings of the knobs that demand a later stage of the solve (WFST_SSSP_EARLY_TAIL=2, WFST_SSSP_EARLY_BEST=2) and the
+  // repeat of a query whose path outgrew the pinned buffer (wfst_ctx::bounded_hold).
+  {
+    Solve& sv = j->sv;
+    const char* why = nullptr;
+    if (sv.kn.bounded == 0) why = "switched off (WFST_SSSP_BOUNDED=0)";
+    else if (ctx->chain_timing) why = "not eligible: profiling is on";
+    else if (ctx->bounded_hold) why = "not eligible: the repeat of a query whose path outgrew the pinned buffer";
+    else if (!sv.mbox || sv.narrow_t == 0) why = "not eligible: no mailbox solve with NARROW launches";
+    else if (sv.log != 12) why = "not eligible: blocks of 8192 states";
+    else if (!fuse) why = "not eligible: no fused tail (first query of the handle, no transpose, or WFST_SSSP_SPLIT_TAIL)";
+    else if (!j->rev->has_fin || sv.kn.final_list == 0) why = "not eligible: the handle has no list of final states";
+    else if (!j->rev->fin_nonneg) why = "not eligible: a negative final weight";
+    else if (sv.kn.early_tail >= 2 || sv.kn.early_best >= 2) why = "not eligible: WFST_SSSP_EARLY_TAIL=2 / WFST_SSSP_EARLY_BEST=2 demand the full solve";
+    // (WFST_SSSP_RES_LEVELS caps the levels of the resident launch so that a solve outruns its prediction, WFST_SSSP_RES_TLIM_US
+    // sets its wait limit so that it gives up: experiments on the later launches of the full solve, which a stop in launch 0
+    // would never reach — tests/test_rearm.py and tests/test_gpu_parity.py pin those routes)
+    else if (sv.kn.res_levels || sv.kn.res_tlim_us)
+      why = "not eligible: WFST_SSSP_RES_LEVELS / WFST_SSSP_RES_TLIM_US shape the later launches of the full solve";
+    sv.bounded_on = why == nullptr;
+    sv.bounded_why = why;
+    if (sv.bounded_on) sv.early.finals = f->dev.finals;  // (what the early tail, if it is on, has set already)
+    // The chain of a query whose predecessors on this FST stopped in launch 0: that launch and a spare one (none after three in a
+    // row).  A head that does not stop after all takes the extended path, like any solve that outruns its prediction.
+    const uint32_t streak = f->bounded_streak.load(std::memory_order_relaxed);
+    if (sv.bounded_on && streak) j->drv.first_count = std::min<uint32_t>(j->drv.first_count, streak >= 3 ? 1u : 2u);
   }
   j->drv.start(/*defer_advance=*/fuse);
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
@@ -2759,6 +2825,35 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
     }
     j->rearm_queued = false;
   }
+  // The bounded head's book-keeping.  `stopped`: launch 0 posted FLAG_NARROW_BOUNDED and the fused tail behind the first batch
+  // searched keys that are exact at and below B (never an extended solve: the flag is launch 0's).
+  const bool b_stopped = j->drv.bounded;
+  if (sv.bounded_on) {
+    if (b_stopped) ctx->bounded_stops += 1;
+    else {
+      const uint32_t w = j->fused_tail ? j->h_tail->bounded_why : 0u;
+      ctx->bounded_refused += 1;
+      ctx->bounded_last_refusal = w == BOUNDED_WHY_BAND   ? "the head did not stop: no total at or below the first band"
+                                  : w == BOUNDED_WHY_GREW ? "the head did not stop: a level outgrew its workgroup"
+                                                          : "the head did not stop: its list did not run empty";
+    }
+  } else {
+    ctx->bounded_refused += 1;
+    ctx->bounded_last_refusal = ctx->profiling ? "not eligible: profiling is on" : sv.bounded_why ? sv.bounded_why : "not eligible";
+  }
+  if (b_stopped && j->fused_tail && (j->h_tail->pad & 8u) && !(j->h_tail->pad & 5u)) {
+    // A path longer than the pinned buffer: the parent pass would read every key, and the keys above B are not the fixed point.
+    // The whole query again, unbounded (the tail gave this solve no re-arm verdict: the stream was waited for above).
+    j.reset();
+    struct Hold {
+      wfst_ctx* c;
+      explicit Hold(wfst_ctx* x) : c(x) { c->bounded_hold = true; }
+      ~Hold() { c->bounded_hold = false; }
+    } hold(ctx);
+    return shortest_path_n1_end(shortest_path_n1_begin(ctx, f));
+  }
+  if (sv.kn.bounded >= 2 && !b_stopped)  // tests: a query that the bounded head ended, or an error that says why not
+    throw Error(std::string("shortest_path: WFST_SSSP_BOUNDED=2 and the bounded head did not end the solve: ") + ctx->bounded_last_refusal);
   if (sv.kn.rearm >= 2 && !sv.armed)  // tests: a solve that started from re-armed scratch, or an error that says why not
     throw Error(std::string("shortest_path: WFST_SSSP_REARM=2 and the solve did not start from re-armed scratch: ") +
                 (sv.rearm_why ? sv.rearm_why : "not eligible"));

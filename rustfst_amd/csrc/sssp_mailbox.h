@@ -55,6 +55,10 @@ constexpr uint32_t MODE_WIDE = 0, MODE_COLLECT = 1, MODE_NARROW = 2;
 // message is in flight after such a launch either): the fixed point is reached and the host needs no quiet launch to see
 // it.  FLAG_NARROW_LEFT = some workgroup left states waiting (spilled, beyond the threshold, messages of the head).
 constexpr uint32_t FLAG_NARROW_CLEAN = 1u + MODE_NARROW, FLAG_NARROW_LEFT = 2u + MODE_NARROW;
+// FLAG_NARROW_BOUNDED = the head of a single-shortest-path query (launch 0) followed everything at or below the best total B
+// it had seen and nothing pending can come in at or below B: the PATH is decided and the solve is over, but the keys above B
+// are NOT the fixed point (never FLAG_NARROW_CLEAN: whoever reads all keys must be able to tell).  See mbox_narrow.
+constexpr uint32_t FLAG_NARROW_BOUNDED = 3u + MODE_NARROW;
 // NARROW launches
 constexpr uint32_t NW_SEG = MB_B;       // work-list segment of a block (COLLECT hands over every state it would have expanded)
 constexpr uint32_t NW_CAP = 1024;       // entries per level a workgroup keeps in LDS (two lists of 16 KB)
@@ -265,8 +269,14 @@ __device__ __forceinline__ SchedRaw mbox_sched_load(const Ctl* ctl, uint32_t swe
   else if (lane == 32) off = offsetof(Ctl, tau) + (size_t)p * 4;
   else if (lane == 33) off = offsetof(Ctl, streak) + (size_t)p * 4;
   else if (lane == 34) off = offsetof(Ctl, mode) + (size_t)p * 4;
+  else if (lane == 35) off = offsetof(Ctl, bounded_launch);
   r.mine = *(const uint2*)((const unsigned char*)ctl + off);  // (dword-aligned 8-byte loads are fine in global memory)
   return r;
+}
+// (uniform) a bounded head ended the solve in an earlier launch (Ctl::bounded_launch): this launch touches nothing and leaves
+// its own flag 0.  The word travels with the schedule words: lane 35 of the same load, no trip of its own.
+__device__ __forceinline__ bool mbox_sched_bounded(const SchedRaw& r) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)r.mine.x, 35) != 0u;
 }
 __device__ __forceinline__ Sched mbox_sched_eval(const Ctl* ctl, const SchedRaw& r, uint32_t sweep, float delta, uint32_t near_low,
                                                  uint32_t narrow_t) {
@@ -344,7 +354,27 @@ __device__ __forceinline__ void mbox_make_wait(const MboxView& mb, uint32_t t, u
 // One NARROW launch of workgroup j: follows the entries of its segment, and what they improve, until nothing near is
 // left, the frontier has grown beyond what one workgroup should carry, or (while states wait beyond the threshold) it
 // has started to shrink — the rule by which sweep_tau widens the band.  `wl` = 2 x NW_CAP entries of LDS.
-template <uint32_t LOG>
+//
+// BOUNDED (a compile-time instance: launch 0 of a single-shortest-path query over a list of final states, no negative arc or
+// final weight; the other launches do not pay for it): the head also tracks B, the least total d[t] (+) rho(t) over the states t
+// it has won (and the start state), computed as tail_candidate computes it, and follows by tau_eff = min(tau, B) — inclusive:
+// zero-weight arcs and ties live AT B.  While B <= tau a shrinking near set is the end of the search, not the tail of a band,
+// and the shrink rule does not apply.  When the list runs empty with B <= tau, no near candidate unlisted (list overflow, a
+// level wider than NW_GROW, NW_MAX_LEVELS) and nothing waiting from before, the launch is PATH-COMPLETE:
+//   * B only falls, and every candidate not followed was above min(tau, B as it stood at the start of that level) >= the
+//     final B: strictly above the final B;
+//   * weights are >= 0 and the f32 sum is monotone, so every state on a shortest path to a state at or below B is itself at or
+//     below B: by induction from the start state each of them was won with its final distance, listed and expanded.  Its hop
+//     word is final as well — a level is a hop count here, and a zero-weight predecessor is itself at or below B;
+//   * the optimum's total is at most B (B is the total of a real path), so the best final state and every final state tied
+//     with it have exact keys; a final state with an unsettled key has a key, hence a total, above B; a predecessor with an
+//     unsettled key is not admissible (d[s] (+) w == d[t] <= B needs d[s] <= B) — the early tail's two-line argument
+//     (sssp_tail_kernel).  The ordinary tail over the list of final states therefore returns what it would after the full solve.
+// Such a launch posts FLAG_NARROW_BOUNDED and records {launch + 1, enc(B)} in Ctl; the far messages and waits it leaves are the
+// next set-up's / re-arm's to clean, like those of any solve.  `s_n` has 12 words in this instance: B as found by the level
+// that fills list counter c in [8 + c] (rotating with the counters, so that the value a level reads is final and uniform),
+// near candidates left unlisted [11].
+template <uint32_t LOG, bool BOUNDED = false>
 __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets, const uint2* __restrict__ wn,
                                             uint64_t* __restrict__ key, const MboxView& mb, Ctl* __restrict__ ctl,
                                             uint32_t* __restrict__ improved, uint32_t sweep, float tau, uint32_t far_total,
@@ -352,7 +382,8 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
                                             uint4* wl, uint32_t* s_n /*[8]: list sizes [0..2] (level mod 3), found beyond the threshold [3], left waiting [4], least enc(d) written [5]*/,
                                             uint32_t par_out, const uint32_t* l_roff_out, uint32_t* l_cur, uint32_t* l_cap,
                                             uint32_t seed_p1 = 0u /*launch 0 of an armed solve, the start's block: start + 1*/,
-                                            uint32_t seed_off = 0u /*... lanes 0 / 1 of the first wave: offsets[start], offsets[start + 1]*/) {
+                                            uint32_t seed_off = 0u /*... lanes 0 / 1 of the first wave: offsets[start], offsets[start + 1]*/,
+                                            const float* __restrict__ finals = nullptr /*BOUNDED: the final weights*/) {
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, MB_HOP_BITS = 32 - LOG, NW_SEG = MB_B;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, j = blockIdx.x, nb = mb.nb;
   const uint32_t sub = tid & 15u, grp = tid >> 4;
@@ -388,6 +419,16 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     s_n[4] = (waits || wl_n > NW_CAP) ? 1u : 0u;  // something is left waiting after this launch
     s_n[5] = 0xFFFFFFFFu;
     if (wl_n) mb.wl_cnt[j] = 0;
+    if (BOUNDED) {  // B starts at the start state's own final weight: entry 0 of the head's list at distance 0
+      uint32_t b0 = 0xFFFFFFFFu;
+      if (head && wl_n == 1u) {
+        const float tot = (0.0f + finals[seed_p1 ? seed_p1 - 1u : mb.wl[(size_t)j * NW_SEG].x]) + 0.0f;
+        if (tot < INF) b0 = f32_key(tot);
+      }
+      s_n[8] = b0;
+      s_n[9] = s_n[10] = 0xFFFFFFFFu;
+      s_n[11] = 0;
+    }
   }
   if (wl_n == 0) {  // (uniform) nothing to follow; whoever waits in this block's masks waits for a WIDE sweep
     if (tid == 0) {
@@ -403,15 +444,30 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
   bool left_any = false;
   unsigned long long p_arcs = 0, p_states = 0;
   bool grew = false;
+  // BOUNDED: enc(B) as every level up to the last one left it (uniform: each word is read only after the barrier behind the
+  // level that wrote it), the threshold this level follows by, and whether the list ran empty (the only exit that may stop)
+  uint32_t b_run = 0xFFFFFFFFu;
+  float tau_eff = tau;
+  bool ran_empty = false;
   for (uint32_t level = 0;; ++level) {
     const uint32_t n_lv = min(s_n[cnt_i], NW_CAP);
     const uint32_t far_seen = s_n[3];
     const uint32_t cnt_o = cnt_i == 2u ? 0u : cnt_i + 1u, cnt_z = cnt_o == 2u ? 0u : cnt_o + 1u;
-    if (tid == 0) s_n[cnt_z] = 0;  // (last level's size: everybody read it before that level's barrier; next level's output)
+    if (BOUNDED && head) {
+      b_run = min(b_run, s_n[8u + cnt_i]);
+      if (b_run != 0xFFFFFFFFu) tau_eff = fminf(tau, key_f32(b_run));
+    }
+    if (tid == 0) {
+      s_n[cnt_z] = 0;  // (last level's size: everybody read it before that level's barrier; next level's output)
+      if (BOUNDED) s_n[8u + cnt_z] = 0xFFFFFFFFu;
+    }
 #ifdef WFST_NW_TRACE
     if (mb.dbg && tid == 0 && sweep < MB_DBG_SWEEPS && level < 13) mb.dbg[((size_t)sweep * nb + j) * 16 + 2 + level] = (wall_clock64() << 12) | min(n_lv, 4095u);
 #endif
-    if (n_lv == 0) break;
+    if (n_lv == 0) {
+      ran_empty = true;
+      break;
+    }
     // (8192-state blocks: a workgroup's share of the hand-over is twice as long — with the 4096-state limit the tail of a 1M-state
     // solve on half the device bounced back to the WIDE levels twice: 385 -> 350 us, 5 -> 3 launches; 2M states unchanged)
     if (n_lv > (sweep == 0 ? NW_GROW : (LOG == 13 ? 2u * NW_GROW_MANY : NW_GROW_MANY))) {
@@ -421,7 +477,9 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     // the head of the search is one workgroup: it applies sweep_tau's rule itself — a near set that shrinks while states
     // wait beyond the threshold is the tail of the band: widen instead.  (Later NARROW launches follow everything they
     // were given, whatever its distance: tau is +inf there.)
-    if (sweep == 0 && level >= 2 && prev_n < prev2_n && (far_total | far_seen) != 0u) break;
+    // (BOUNDED, B <= tau: the near set is everything at or below B, and it shrinks because the search is ending)
+    const bool b_in_band = BOUNDED && head && b_run != 0xFFFFFFFFu && key_f32(b_run) <= tau;
+    if (sweep == 0 && level >= 2 && prev_n < prev2_n && (far_total | far_seen) != 0u && !b_in_band) break;
     if (level >= NW_MAX_LEVELS) {
       grew = true;  // (keeps the threshold where it is: the rest is followed after the next WIDE sweep)
       break;
@@ -463,6 +521,8 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
         }
         uint32_t enc[NW_UNROLL], tb[NW_UNROLL], te[NW_UNROLL];
         unsigned long long ck[NW_UNROLL], old[NW_UNROLL];
+        float fw[NW_UNROLL];  // BOUNDED: the targets' final weights
+        const float thr = BOUNDED ? tau_eff : tau;
         for (uint32_t u = 0; u < NW_UNROLL; ++u) {
           const float c = (d_[u] + __uint_as_float(a[u].x)) + 0.0f;  // w1 (x) w2 = f32 add (tropical_weight.rs:60-70)
           v[u] = v[u] && c < INF;                                    // +inf never improves (shortest_path.rs:226)
@@ -470,7 +530,8 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
           ck[u] = ((unsigned long long)enc[u] << 32) | h1_[u];
           old[u] = 0;
           tb[u] = te[u] = 0;
-          if (head && v[u] && c > tau) {
+          if (BOUNDED) fw[u] = INF;
+          if (head && v[u] && c > thr) {
             const uint32_t db = a[u].y >> MB_LOG, slot = atomicAdd(&l_cur[db], 1u);
             if (slot < l_cap[db]) {
               msgs_out[l_roff_out[db] + slot] = make_uint2((h1_[u] << MB_LOG) | (a[u].y & (MB_B - 1u)), enc[u]);
@@ -484,6 +545,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
             old[u] = atomicMin((unsigned long long*)&key[a[u].y], ck[u]);
             tb[u] = offsets[a[u].y];
             te[u] = offsets[a[u].y + 1];
+            if (BOUNDED && head) fw[u] = finals[a[u].y];  // (the same trip: B is lowered by whoever wins)
           }
         }
         more = false;
@@ -497,7 +559,11 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
             if (!head) atomicMin(&s_n[5], enc[u]);
             if (h1_[u] >> MB_HOP_BITS) ctl->pad = 1u;  // hop count beyond the message format: the host refuses the result
             bool listed = false;
-            if (key_f32(enc[u]) <= tau) {
+            if (BOUNDED && head) {  // d[t] (+) rho(t), as tail_candidate computes it
+              const float tot = (key_f32(enc[u]) + fw[u]) + 0.0f;
+              if (tot < INF) atomicMin(&s_n[8u + cnt_o], f32_key(tot));
+            }
+            if (key_f32(enc[u]) <= thr) {
               const uint32_t slot = atomicAdd(n_out, 1u);
               if (slot < NW_CAP) {
                 out[slot] = make_uint4(a[u].y, tb[u], enc[u], (h1_[u] << MB_LOG) | min(te[u] - tb[u], NW_DEG_SAT));
@@ -506,6 +572,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
               if (!listed) {
                 mbox_make_wait<LOG>(mb, a[u].y, enc[u], false);
                 left_any = true;
+                if (BOUNDED) s_n[11] = 1u;  // a near candidate nobody follows: no stop in this launch
               }
             } else {
               mbox_make_wait<LOG>(mb, a[u].y, enc[u], true);
@@ -540,7 +607,19 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     if (__any(left_any || left != 0u) && lane == 0) s_n[4] = 1u;
     __syncthreads();
     if (tid == 0) {
-      atomicMax(improved, s_n[4] ? FLAG_NARROW_LEFT : FLAG_NARROW_CLEAN);
+      // (BOUNDED: the stop — the argument is above this function.  b_run is final: the exit through the empty list read the
+      // word of the last level that ran; the launch's one entry was the start state, and nothing waited before it.)
+      const bool stop = BOUNDED && head && ran_empty && wl_n == 1u && !waits && b_run != 0xFFFFFFFFu && key_f32(b_run) <= tau &&
+                        s_n[11] == 0u;
+      if (stop) {
+        ctl->bounded_launch = sweep + 1u;
+        ctl->bounded_b = b_run;
+      } else if (BOUNDED && head) {  // (for the host's statistics: WFST_SSSP_BOUNDED=2 names the reason)
+        ctl->bounded_why = (grew || s_n[11] != 0u)                             ? BOUNDED_WHY_GREW
+                           : !(b_run != 0xFFFFFFFFu && key_f32(b_run) <= tau) ? BOUNDED_WHY_BAND
+                                                                               : BOUNDED_WHY_OTHER;
+      }
+      atomicMax(improved, stop ? FLAG_NARROW_BOUNDED : s_n[4] ? FLAG_NARROW_LEFT : FLAG_NARROW_CLEAN);
       if (s_n[5] != 0xFFFFFFFFu) atomicMin(&ctl->narrow_low[sweep % RING], s_n[5]);  // (one global atomic per workgroup)
     }
     if (head) {  // the messages of the head: counts of the regions, like a WIDE sweep's publish
@@ -583,7 +662,9 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
 // The kernel is bound by its chain of dependent round trips (global AND LDS), so every phase asks for all it needs
 // at once: no prefix sums, no searches, no shuffle reductions (ballots and one LDS atomic per wave instead).
 // BIG: more than 256 blocks — inbox counts staged through LDS, regions visited in passes of 256.
-template <bool BIG>
+// BHEAD: the instance the host launches as launch 0 of a query whose head may end the search (mbox_narrow<.., true>; `et.finals`
+// is set); every other launch is the plain instance, which only learns from its schedule words that such a head stopped.
+template <bool BIG, bool BHEAD = false>
 __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* __restrict__ offsets, const uint2* __restrict__ wn,
                                                                uint64_t* __restrict__ key, MboxView mb, uint32_t par_in, uint32_t n,
                                                                uint32_t* __restrict__ improved_ring, Ctl* __restrict__ ctl,
@@ -595,7 +676,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
   __shared__ uint16_t a_state[MB_B];  // states expanded in this sweep
   __shared__ uint32_t s_wany[MB_THREADS / 64];
   __shared__ uint32_t s_an, s_sent, s_npend, s_mind, s_nfar;
-  __shared__ uint32_t s_nw[8];
+  __shared__ uint32_t s_nw[BHEAD ? 12 : 8];
   __shared__ unsigned long long s_prof_arcs;
   constexpr uint32_t R = MB_B / MB_THREADS;  // states per thread
   constexpr uint32_t PW = MB_B / 32;         // pending words per block
@@ -627,6 +708,7 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
     unsigned long long best = KEY_INF;
     bool tie = false;
     for (uint32_t r = 0; r < NBB; ++r) tail_merge_packed(best, tie, bb[r]);
+    if (mbox_sched_bounded(raw)) return;  // (the solve ended in a bounded head: the ordinary tail does the rest)
     const Sched sc = mbox_sched_eval(ctl, raw, sweep, delta, near_low, narrow_t);
     if (sc.mode == MODE_NARROW) sssp_early_tail(et, offsets, key, ctl, prev_flag, sweep, lkey, merged, merged ? best : KEY_INF, merged && tie);
     return;
@@ -738,6 +820,9 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
     }
   }
   if (!hint) bulk_store();
+  // a bounded head ended the solve in an earlier launch: nothing is touched, this launch's flag stays 0 (uniform; the LDS
+  // stores above are this workgroup's own)
+  if (mbox_sched_bounded(raw)) return;
   const Sched sc = mbox_sched_eval(ctl, raw, sweep, delta, near_low, narrow_t);
   const float tau = sc.tau_use;
   const uint32_t mode = sc.mode;
@@ -780,8 +865,8 @@ __global__ void __launch_bounds__(MB_THREADS) sssp_mbox_kernel(const uint32_t* _
       for (uint32_t d = tid; d < nb; d += MB_THREADS) mb.cnt[par_out][(size_t)d * nb + j] = 0;
       if (tid == 0) mb.wrote[par_out][j] = 0;
     }
-    mbox_narrow<MB_LOG>(offsets, wn, key, mb, ctl, improved, sweep, tau, sc.far_total, near_low, profile, wl_n, bmind != 0xFFFFFFFFu, bfar,
-                (uint4*)lkey, s_nw, par_out, l_roff_out, l_cur, l_base, seed ? et.seed : 0u, seed_off);
+    mbox_narrow<MB_LOG, BHEAD>(offsets, wn, key, mb, ctl, improved, sweep, tau, sc.far_total, near_low, profile, wl_n, bmind != 0xFFFFFFFFu,
+                               bfar, (uint4*)lkey, s_nw, par_out, l_roff_out, l_cur, l_base, seed ? et.seed : 0u, seed_off, et.finals);
     MB_STAMP(15);
     return;
   }

@@ -86,6 +86,16 @@ class Context:
         check(_lib.lib().wfst_ctx_get_rearm_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rearm_stats")
         return dict(zip(("armed", "adopted", "dropped"), (int(v.value) for v in vals)))
 
+    def bounded_stats(self) -> dict:
+        """The bounded head of the single-shortest-path relaxation on this context (wfst_ctx_get_bounded_stats): queries whose
+        first launch ended the search once the best final state was settled (stops), queries of the large-FST route that ran
+        the full solve (full_solves) and why the last of those did (last_reason)."""
+        if not hasattr(_lib.lib(), "wfst_ctx_get_bounded_stats"):  # (WFST_LIB_PATH: a build from before the counters)
+            return dict(stops=0, full_solves=0, last_reason="")
+        stops, full, why = C.c_uint64(), C.c_uint64(), C.c_char_p()
+        check(_lib.lib().wfst_ctx_get_bounded_stats(self._h, C.byref(stops), C.byref(full), C.byref(why)), "wfst_ctx_get_bounded_stats")
+        return dict(stops=int(stops.value), full_solves=int(full.value), last_reason=(why.value or b"").decode())
+
     def small_path_stats(self) -> dict:
         """Which path answered the small shortest-path queries of this context (wfst_ctx_get_small_path_stats): the last
         launch of the nshortest = 1 wave kernel (n1_in_kernel, n1_staged, n1_handed_back) and the last n-best batch

@@ -2,6 +2,8 @@
 # Runs on the GPU box (via gpurun): the end-of-round evidence set.  usage: tools/profile_round.sh <tag>
 #   kernel traces (bench step; the relaxation alone at 1M with the chain ALSO timed by HIP events in the same process; 5M;
 #   the wide look-ahead driver), level stamps of the resident launch, PMC passes of the relaxation at 1M (separate passes).
+#   The level stamps and the PMC passes ask for the full solve (sp_repeat.py --full): they are figures of the relaxation of
+#   every arc, not of a query that the bounded head ends in its first launch.
 set -u
 TAG=${1:-r06}
 export TMPDIR=/tmp
@@ -20,12 +22,12 @@ timeout -k 5 300 rocprofv3 --kernel-trace -d $OUT -o sp_5m -- python $R/tools/sp
 timeout -k 5 300 rocprofv3 --kernel-trace -d $OUT -o wide -- python $R/tools/wide_lookahead_run.py 5000000 4 > $OUT/wide.log 2>&1
 stamp traces
 cd $R
-WFST_SSSP_RES_TRACE=/tmp/res.bin timeout -k 5 200 python tools/sp_repeat.py 1000000 8 > /dev/null 2>&1; python tools/res_levels.py /tmp/res.bin > $OUT/res_levels.txt
+WFST_SSSP_RES_TRACE=/tmp/res.bin timeout -k 5 200 python tools/sp_repeat.py 1000000 8 --full > /dev/null 2>&1; python tools/res_levels.py /tmp/res.bin > $OUT/res_levels.txt
 stamp levels
 cd /tmp
 pass() {  # name, counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace -d $OUTP -o $name -- python $R/tools/sp_repeat.py 1000000 12 > $OUTP/$name.log 2>&1 || echo "pass $name failed: $(tail -2 $OUTP/$name.log)"
+  rocprofv3 --pmc "$@" --kernel-trace -d $OUTP -o $name -- python $R/tools/sp_repeat.py 1000000 12 --full > $OUTP/$name.log 2>&1 || echo "pass $name failed: $(tail -2 $OUTP/$name.log)"
 }
 pass fetch FETCH_SIZE
 pass write WRITE_SIZE

@@ -1,4 +1,5 @@
-"""Reads a WFST_SSSP_RES_TRACE file (u32 levels, u32 nb, u64 [levels][nb][4] wall-clock stamps at 100 MHz: inbox applied,
+"""(Take the trace from a full solve — sp_repeat.py --full: a query that the bounded head ends never reaches the resident launch.)
+Reads a WFST_SSSP_RES_TRACE file (u32 levels, u32 nb, u64 [levels][nb][4] wall-clock stamps at 100 MHz: inbox applied,
 scanned, expanded, published) and prints, per level, when the LAST / median block passed each stamp (us since the first
 block's `applied` stamp of level 0)."""
 import sys, struct

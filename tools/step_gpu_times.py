@@ -1,6 +1,10 @@
 """GPU-side durations inside one overlapped bench step (events on the two streams): the batch kernel's stream, the
-relaxation's stream, and the host phases around them.  usage: step_gpu_times.py [N] [acceptors] [resident share 0/1]"""
+relaxation's stream, and the host phases around them.  usage: step_gpu_times.py [N] [acceptors] [resident share 0/1] [--full]
+--full: the direct query relaxes every arc (WFST_SSSP_BOUNDED=0) instead of ending in the bounded head."""
 import os, sys, time
+if "--full" in sys.argv:
+    sys.argv.remove("--full")
+    os.environ["WFST_SSSP_BOUNDED"] = "0"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import rustfst_amd
@@ -46,7 +50,7 @@ for it in range(30):
     f0.record(s1); sp_job = dt.shortest_path_begin(); f1.record(s1); sp_job.finish(); torch.cuda.synchronize()
     al.append([e0.elapsed_time(e1) * 1e3, f0.elapsed_time(f1) * 1e3])
 al = np.median(np.array(al[5:]), axis=0)
-print("rearm_stats (relaxation context, all steps)", ctx.rearm_stats())
+print("rearm_stats (relaxation context, all steps)", ctx.rearm_stats(), "bounded_stats", ctx.bounded_stats())
 print("alone: batch stream %.1f us | relaxation stream %.1f us   (%d acceptors, resident share %s)" % (al[0], al[1], B, sys.argv[3] if len(sys.argv) > 3 else "0"))
 print("host: batch begin %.1f | sp begin %.1f | batch finish %.1f | sp finish %.1f | step %.1f us" % tuple(r[:5]))
 print("gpu : batch stream %.1f us | relaxation stream %.1f us | relaxation starts %.1f us after the batch | relaxation ends %.1f us after the batch started" % tuple(r[5:]))
