@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -687,6 +687,38 @@ wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint
                                            wide_need, uint64_t* grow_states, uint64_t* grow_elts, uint64_t* grow_arcs,
                                            uint64_t* grow_cands, uint64_t* rehashes, uint64_t* cap_states, uint64_t*
                                            cap_elts, uint64_t* cap_arcs, uint64_t* cap_cands, uint64_t* rounds_max);
+
+/* ---- which route the last wfst_minimize call of ctx took.  Every route returns the same FST, so only these counters show
+ *      which one ran.  wfst_minimize resets them when it begins; they hold that call's
+ *      values also when it ends KO.  They are tallied on the host from the control block the level loop already copies back
+ *      once per host step (no launch, no read-back of their own).  After wfst_minimize_batch and wfst_optimize they are
+ *      unspecified.
+ *      The call peels the heights of a graph level by level, sinks first, at most twice: the cycle check on the untrimmed
+ *      input when the stored word leaves ACYCLIC / CYCLIC unknown (check_*), then the refinement of the connected, sorted
+ *      machine (no prefix; in the weighted branch the encoded machine with its superfinal state).  A level of at most 4096
+ *      states runs in the one-workgroup narrow_kernel, which goes on level after level and leaves at an empty level or at
+ *      one of more than 4096 states; any other level runs as device-wide launches, after which the host chooses again
+ *      (WFST_MINIMIZE_PATH=narrow: one launch whatever the sizes; wide: every level device-wide).  A state of the refined
+ *      machine with more than 64 arcs is refined by a wave, any other by a lane.
+ *        levels            non-empty levels peeled,
+ *        wide_levels       those of them the device-wide launches ran,
+ *        narrow_launches   narrow_kernel launches,
+ *        exit_wide         launches that ended at a level of more than 4096 states,
+ *        exit_done         launches that ended at an empty level: every state was peeled, or a cycle holds the rest,
+ *        branch            0 KO before any branch, or no states; 1 unweighted; 2 weighted; 3 weighted without a start
+ *                          state; 4 nothing left after connect (either branch),
+ *        wave_states       states a wave refined,
+ *        unequal_compares  full signature compares that found a difference: two signatures shared a slot and the upper 32
+ *                          bits of their hash (counted modulo 2^32).
+ *      WFST_MINIMIZE_HASH_BITS=n (0 <= n <= 64, default 64; for tests) keeps only the low n bits of a signature's hash: with
+ *      0 every state starts at slot 0 with tag 0 and is compared in full with every representative in front of it.  Anything
+ *      else in the variable is KO.  The kernel of wfst_minimize_batch always keeps all 64 bits.
+ *      All values are 0 for an input without states.  Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, uint64_t* check_wide_levels,
+                                        uint64_t* check_narrow_launches, uint64_t* check_exit_wide, uint64_t* check_exit_done,
+                                        uint64_t* levels, uint64_t* wide_levels, uint64_t* narrow_launches, uint64_t* exit_wide,
+                                        uint64_t* exit_done, uint64_t* branch, uint64_t* wave_states,
+                                        uint64_t* unequal_compares);
 
 /* wfst_compose_shortest_path_batch with the results as RECORDS (the layout of wfst_fst_pack_paths below) instead of handles:
  * out[i * (4 + 4 * max_arcs) ...] = path i, written straight from the kernel's result buffers — for hosts that read the

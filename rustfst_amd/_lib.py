@@ -115,6 +115,7 @@ SYMBOLS = [
     ("wfst_minimize", C.c_int, [_vp, _vp, _P(MinimizeConfig), _P(_vp)]),
     ("wfst_minimize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(MinimizeConfig), _P(_vp), _vp]),
     ("wfst_ctx_get_minimize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_ctx_get_minimize_stats", C.c_int, [_vp] + [_P(_u64)] * 13),
     ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_optimize", C.c_int, [_vp, _vp, _P(_vp)]),

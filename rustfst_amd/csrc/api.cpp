@@ -615,6 +615,7 @@ wfst_status wfst_ctx_get_determinize_batch_stats(wfst_ctx* ctx, uint64_t* launch
 wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
+    if (ctx) ctx->min_stats = {};  // (wfst_ctx_get_minimize_stats: this call's, also when an argument is refused)
     const wfst_minimize_config c = cfg ? *cfg : wfst_minimize_config{1e-6f, 0u};
     if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("minimize: delta must be finite and > 0");
     if (!ctx || !fst || !out) throw Error("null pointer");
@@ -852,6 +853,30 @@ wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint
     if (cap_arcs) *cap_arcs = c.cap_arcs;
     if (cap_cands) *cap_cands = c.cap_cands;
     if (rounds_max) *rounds_max = c.rounds_max;
+  });
+}
+
+wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, uint64_t* check_wide_levels,
+                                        uint64_t* check_narrow_launches, uint64_t* check_exit_wide, uint64_t* check_exit_done,
+                                        uint64_t* levels, uint64_t* wide_levels, uint64_t* narrow_launches, uint64_t* exit_wide,
+                                        uint64_t* exit_done, uint64_t* branch, uint64_t* wave_states,
+                                        uint64_t* unequal_compares) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::MinimizeStats& c = ctx->min_stats;
+    if (check_levels) *check_levels = c.check.levels;
+    if (check_wide_levels) *check_wide_levels = c.check.wide_levels;
+    if (check_narrow_launches) *check_narrow_launches = c.check.narrow_launches;
+    if (check_exit_wide) *check_exit_wide = c.check.exit_wide;
+    if (check_exit_done) *check_exit_done = c.check.exit_done;
+    if (levels) *levels = c.refine.levels;
+    if (wide_levels) *wide_levels = c.refine.wide_levels;
+    if (narrow_launches) *narrow_launches = c.refine.narrow_launches;
+    if (exit_wide) *exit_wide = c.refine.exit_wide;
+    if (exit_done) *exit_done = c.refine.exit_done;
+    if (branch) *branch = c.branch;
+    if (wave_states) *wave_states = c.wave_states;
+    if (unequal_compares) *unequal_compares = c.unequal_compares;
   });
 }
 

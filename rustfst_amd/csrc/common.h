@@ -251,6 +251,15 @@ struct wfst_ctx {
     uint64_t cap_states = 0, cap_elts = 0, cap_arcs = 0, cap_cands = 0;
     uint64_t rounds_max = 0;
   } det_stats;
+  // which route the levels of the last wfst_minimize call took (wfst_ctx_get_minimize_stats): tallied on the host from the
+  // control block minimize.hip's level loop already reads back; check = the cycle check on the untrimmed input, refine =
+  // the refinement of the connected machine
+  struct MinimizeStats {
+    struct Pass {
+      uint64_t levels = 0, wide_levels = 0, narrow_launches = 0, exit_wide = 0, exit_done = 0;
+    } check, refine;
+    uint64_t branch = 0, wave_states = 0, unequal_compares = 0;
+  } min_stats;
   // the one-wave path kernels (wfst_ctx_get_small_path_stats): the last sp1_wave_kernel launch since the last
   // wfst_shortest_path / wfst_shortest_path_batch call began, and the last shortest_path_nbest_batch
   struct SmallPathStats {

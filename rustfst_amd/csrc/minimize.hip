@@ -19,7 +19,8 @@
 //                  order: partition.rs:46-92, minimize.rs:340-376).  A lane per state up to 64 arcs, a wave per state beyond.
 //   regimes        NARROW: one 1024-thread workgroup runs level after level inside one launch (lattices: thousands of
 //                  heights of a few states); WIDE: one device-wide launch per phase.  The host switches by the size of the
-//                  next level; WFST_MINIMIZE_PATH=auto|narrow|wide pins one.
+//                  next level; WFST_MINIMIZE_PATH=auto|narrow|wide pins one.  Which one ran: wfst_ctx_get_minimize_stats,
+//                  tallied on the host from the control block (include/wfst.h; WFST_MINIMIZE_HASH_BITS for tests).
 //   emit           survivors scanned into new ids, their arcs redirected in tr_unique's order (label key, then nextstate:
 //                  tr_unique.rs:8-35), labels / weights decoded from the first occurrence, the arcs into the superfinal state
 //                  folded back into final weights (rm_final_epsilon.rs), the property word, adopt_device.
@@ -63,7 +64,9 @@ constexpr uint32_t NARROW_MAX = 4096;   // levels of at most this many states st
 constexpr uint32_t LANE_MAX_DEG = 64;   // beyond: a wave per state
 constexpr uint64_t HI32 = 0xFFFFFFFF00000000ull;
 // ctl words
-constexpr uint32_t C_LO = 0, C_HI = 1, C_TAIL = 2, C_LEVEL = 3, C_CURMAX = 4, C_NEXTMAX = 5, C_NBIG = 6, C_WORDS = 8;
+// (C_WAVE: the C_NBIG of every level so far; C_UNEQ: full compares that found a difference — wfst_ctx_get_minimize_stats)
+constexpr uint32_t C_LO = 0, C_HI = 1, C_TAIL = 2, C_LEVEL = 3, C_CURMAX = 4, C_NEXTMAX = 5, C_NBIG = 6, C_WAVE = 7, C_UNEQ = 8,
+                   C_WORDS = 10;
 
 __device__ inline uint32_t wkey(float f) { return f == 0.0f ? 0u : __float_as_uint(f); }  // -0.0 == +0.0
 __device__ inline uint64_t ld64(const unsigned long long* p) {
@@ -237,6 +240,7 @@ struct Core {
   uint32_t* big;  // states of the level with more than LANE_MAX_DEG arcs
   uint32_t by_olabel;
   uint32_t refine;  // 0: heights only (the cycle check of an untrimmed input)
+  uint64_t hmask;   // the bits of a signature's hash that are kept (WFST_MINIMIZE_HASH_BITS; all ones otherwise)
 };
 
 __device__ inline void core_init_state(const Core& c, uint32_t s) {
@@ -260,6 +264,7 @@ __device__ inline void core_advance(const Core& c) {  // one thread
     stg(&c.ctl[C_CURMAX], ld(&c.ctl[C_NEXTMAX]));
     stg(&c.ctl[C_NEXTMAX], 0u);
   }
+  stg(&c.ctl[C_WAVE], ld(&c.ctl[C_WAVE]) + ld(&c.ctl[C_NBIG]));
   stg(&c.ctl[C_NBIG], 0u);
 }
 __global__ void core_advance_kernel(Core c) { core_advance(c); }
@@ -285,7 +290,7 @@ __device__ void refine_small(const Core& c, uint32_t lo, uint32_t hi, uint32_t t
     const uint32_t fk = wkey(c.fin[s]);
     uint64_t h = head_hash(fk, deg);
     for (uint32_t j = 0; j < deg; ++j) h += entry_hash(c, c.arcs[b + j], j);
-    h = mix64(h);
+    h = mix64(h) & c.hmask;
     const uint64_t word = (h & HI32) | (uint64_t)(s + 1);
     uint32_t i = (uint32_t)h & c.tmask;
     for (;;) {
@@ -300,6 +305,7 @@ __device__ void refine_small(const Core& c, uint32_t lo, uint32_t hi, uint32_t t
         bool eq = c.off[r + 1] - rb == deg && wkey(c.fin[r]) == fk;
         for (uint32_t j = 0; eq && j < deg; ++j) eq = entry_equal(c, c.arcs[b + j], c.arcs[rb + j]);
         if (eq) break;
+        atomicAdd(&c.ctl[C_UNEQ], 1u);
       }
       i = (i + 1) & c.tmask;
     }
@@ -317,7 +323,7 @@ __device__ void refine_big(const Core& c, uint32_t nbig, uint32_t wave, uint32_t
     uint64_t part = 0;
     for (uint32_t j = lane; j < deg; j += 64) part += entry_hash(c, c.arcs[b + j], j);
     for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    const uint64_t h = mix64(head_hash(fk, deg) + part);
+    const uint64_t h = mix64(head_hash(fk, deg) + part) & c.hmask;
     const uint64_t word = (h & HI32) | (uint64_t)(s + 1);
     uint32_t i = (uint32_t)h & c.tmask;
     for (;;) {
@@ -338,6 +344,7 @@ __device__ void refine_big(const Core& c, uint32_t nbig, uint32_t wave, uint32_t
         if (!diff)
           for (uint32_t j = lane; j < deg; j += 64) diff |= !entry_equal(c, c.arcs[b + j], c.arcs[rb + j]);
         if (!__any(diff)) break;
+        if (lane == 0) atomicAdd(&c.ctl[C_UNEQ], 1u);
       }
       i = (i + 1) & c.tmask;
     }
@@ -420,6 +427,7 @@ __device__ void narrow_levels(const Core& c, uint32_t narrow_max, uint32_t nth, 
       stg(&c.ctl[C_LEVEL], ld(&c.ctl[C_LEVEL]) + 1u);
       stg(&c.ctl[C_CURMAX], ld(&c.ctl[C_NEXTMAX]));
       stg(&c.ctl[C_NEXTMAX], 0u);
+      stg(&c.ctl[C_WAVE], ld(&c.ctl[C_WAVE]) + ld(&c.ctl[C_NBIG]));
       stg(&c.ctl[C_NBIG], 0u);
     }
     __threadfence();
@@ -535,6 +543,22 @@ Path path_knob() {
   throw Error(std::string("WFST_MINIMIZE_PATH: expected auto, narrow or wide, not '") + e + "'");
 }
 
+// WFST_MINIMIZE_HASH_BITS=n (0 <= n <= 64; tests): refine_small / refine_big keep the low n bits of a signature's hash, so
+// that different signatures meet in one slot with one tag and the full compare decides.  The mask of the bits kept.
+uint64_t hash_mask_knob() {
+  const char* e = std::getenv("WFST_MINIMIZE_HASH_BITS");
+  if (!e || !*e) return ~0ull;
+  char* end = nullptr;
+  const unsigned long v = std::strtoul(e, &end, 10);
+  if (*e < '0' || *e > '9' || *end || std::strlen(e) > 2 || v > 64)
+    throw Error(std::string("WFST_MINIMIZE_HASH_BITS: expected a number from 0 to 64, not '") + e + "'");
+  return v == 64 ? ~0ull : (1ull << v) - 1ull;
+}
+struct Knobs {
+  Path path;
+  uint64_t hmask;
+};
+
 uint32_t grid16(wfst_ctx* ctx, uint32_t n) {  // 16 lanes per state
   return std::max<uint32_t>(1, std::min<uint32_t>((n + 15) / 16, (uint32_t)ctx->n_cus * 32));
 }
@@ -643,9 +667,14 @@ struct CoreBufs {
   Core c{};
   uint32_t peeled = 0;
 };
-// heights (and, with `refine`, the classes) of the graph (off, arcs, fin) with n states and E arcs
+// heights (and, with `refine`, the classes) of the graph (off, arcs, fin) with n states and E arcs.  The route is tallied
+// from the control block every host step reads back anyway (wfst_ctx_get_minimize_stats): into the cycle check's counters
+// without `refine`, else into the refinement's.
 void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t* off, const wfst_tr* arcs, const float* fin,
-              bool refine, bool by_olabel, Path path) {
+              bool refine, bool by_olabel, Knobs knobs) {
+  const Path path = knobs.path;
+  wfst_ctx::MinimizeStats& tally = ctx->min_stats;
+  wfst_ctx::MinimizeStats::Pass& pass = refine ? tally.refine : tally.check;
   hipStream_t st = ctx->stream;
   DevicePool& pool = *ctx->pool;
   B.rcnt = DBuf<uint32_t>(pool, (size_t)n + 1);
@@ -675,6 +704,7 @@ void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t
   c.ctl = B.ctl.p;
   c.by_olabel = by_olabel ? 1u : 0u;
   c.refine = refine ? 1u : 0u;
+  c.hmask = knobs.hmask;
   if (refine) {
     const uint32_t size = pow2_at_least(2 * (uint64_t)n, "minimize");
     B.cls = DBuf<uint32_t>(pool, n);
@@ -699,13 +729,23 @@ void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t
   HIP_CHECK(hipGetLastError());
   uint32_t h[C_WORDS];
   const uint32_t narrow_max = path == Path::Narrow ? NONE : NARROW_MAX;
+  bool from_narrow = false;  // the block read next is what a narrow launch left
   for (;;) {
     HIP_CHECK(hipMemcpyAsync(h, B.ctl.p, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     const uint32_t cnt = h[C_HI] - h[C_LO];
+    pass.levels = h[C_LEVEL] - 1u;  // (C_LEVEL: 1 + the levels that left the graph; an empty one never does)
+    if (refine) {
+      tally.wave_states = h[C_WAVE];
+      tally.unequal_compares = h[C_UNEQ];
+    }
+    if (from_narrow) ++(cnt == 0 ? pass.exit_done : pass.exit_wide);
+    from_narrow = false;
     if (cnt == 0) break;
     if (path != Path::Wide && cnt <= narrow_max) {
       narrow_kernel<<<1, NARROW_TPB, 0, st>>>(c, narrow_max);
+      ++pass.narrow_launches;
+      from_narrow = true;
     } else {
       const uint32_t cap = (uint32_t)ctx->n_cus * 16;
       if (refine) {
@@ -714,6 +754,7 @@ void run_core(wfst_ctx* ctx, CoreBufs& B, uint32_t n, uint64_t E, const uint32_t
       }
       wide_peel_kernel<<<std::max(1u, std::min((cnt + 15) / 16, cap)), TPB, 0, st>>>(c);
       core_advance_kernel<<<1, 1, 0, st>>>(c);
+      ++pass.wide_levels;
     }
     HIP_CHECK(hipGetLastError());
   }
@@ -727,14 +768,14 @@ wfst_fst* empty_fst(wfst_ctx* ctx, uint64_t p) {
 }
 
 // AcyclicMinimizer + merge_states + tr_unique (+ decode for the weighted branch, enc != null) of the connected, sorted T
-wfst_fst* minimize_connected(wfst_ctx* ctx, const wfst_fst* T, const wfst_tr* enc, uint64_t out_props, Path path) {
+wfst_fst* minimize_connected(wfst_ctx* ctx, const wfst_fst* T, const wfst_tr* enc, uint64_t out_props, Knobs knobs) {
   hipStream_t st = ctx->stream;
   DevicePool& pool = *ctx->pool;
   const uint32_t n = T->n_states;
   const uint64_t E = T->n_arcs;
   const uint32_t superfinal = enc ? n - 1 : NONE;
   CoreBufs B;
-  run_core(ctx, B, n, E, T->dev.offsets, T->dev.arcs, T->dev.finals, true, enc != nullptr, path);
+  run_core(ctx, B, n, E, T->dev.offsets, T->dev.arcs, T->dev.finals, true, enc != nullptr, knobs);
   if (B.peeled != n) throw Error(MSG_CYCLIC);
   if (!enc && E) {
     DBuf<uint32_t> flag(pool, 1);
@@ -769,10 +810,10 @@ wfst_fst* minimize_connected(wfst_ctx* ctx, const wfst_fst* T, const wfst_tr* en
 }
 
 // the graph has a cycle (anywhere: the reference's DFS visits every state) — by peeling sinks, without refinement
-bool has_cycle(wfst_ctx* ctx, const wfst_fst* f, Path path) {
+bool has_cycle(wfst_ctx* ctx, const wfst_fst* f, Knobs knobs) {
   if (f->n_states == 0) return false;
   CoreBufs B;
-  run_core(ctx, B, f->n_states, f->n_arcs, f->dev.offsets, f->dev.arcs, f->dev.finals, false, false, path);
+  run_core(ctx, B, f->n_states, f->n_arcs, f->dev.offsets, f->dev.arcs, f->dev.finals, false, false, knobs);
   return B.peeled != f->n_states;
 }
 
@@ -781,7 +822,9 @@ bool has_cycle(wfst_ctx* ctx, const wfst_fst* f, Path path) {
 // minimize_with_config (minimize.rs:92-176) for the acyclic deterministic acceptor branch: a NEW handle
 wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow_nondet) {
   using namespace props;
-  const Path path = path_knob();
+  wfst_ctx::MinimizeStats& tally = ctx->min_stats;  // (wfst_ctx_get_minimize_stats: this call's, also when it ends KO)
+  tally = wfst_ctx::MinimizeStats{};
+  const Knobs knobs{path_knob(), hash_mask_knob()};
   hipStream_t st = ctx->stream;
   DevicePool& pool = *ctx->pool;
   ensure_device(const_cast<wfst_fst*>(f));
@@ -801,7 +844,7 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
   // computed.  Any cycle is KO here, also one that connect would remove (the reference takes Hopcroft's branch then).
   bool computed_dfs = false;
   if (!knows(p, CYCLIC)) {
-    if (has_cycle(ctx, f, path)) throw Error(MSG_CYCLIC);
+    if (has_cycle(ctx, f, knobs)) throw Error(MSG_CYCLIC);
     computed_dfs = true;
   } else if (p & CYCLIC) {
     throw Error(MSG_CYCLIC);
@@ -809,16 +852,22 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
 
   if (!(p & WEIGHTED)) {
     // ---- unweighted acceptor (:172-175): acceptor_minimize on the original labels
+    if (n) tally.branch = 1;
     if (computed_dfs) content_facts(ctx, f, fa);
     const uint64_t pc = unweighted_connect_word(p, computed_dfs, fa.bits);  // connect (:193)
     Handle T(connect_and_adopt(ctx, n, f->start, f->dev.offsets, f->dev.arcs, f->dev.finals, /*all_accessible=*/false, pc));
-    if (T->n_states == 0) return T.release();  // (:195-197)
+    if (T->n_states == 0) {  // (:195-197)
+      if (n) tally.branch = 4;
+      return T.release();
+    }
     tr_sort_device(ctx, T.get(), true);         // tr_sort(ILabelCompare) (:201)
-    return minimize_connected(ctx, T.get(), nullptr, unweighted_result_word(pc, T->n_arcs != 0), path);
+    return minimize_connected(ctx, T.get(), nullptr, unweighted_result_word(pc, T->n_arcs != 0), knobs);
   }
 
   // ---- weighted acceptor (:162-171)
+  if (n) tally.branch = 2;
   if (f->start < 0) {
+    if (n) tally.branch = 3;
     // No start state: push_weights still reweights arcs and final weights (reweight.rs skips only the start-state step),
     // then every tr_map returns at once (tr_map.rs:86-88): no quantization, no encoding.  acceptor_minimize recomputes its
     // facts from the PUSHED content (reweight_properties left WEIGHTED unknown) and bails on a weight that is still
@@ -875,6 +924,7 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
   // acceptor_minimize: connect (the word of the trimmed FST starts empty: every bit is fixed below)
   Handle T(connect_and_adopt(ctx, np + 1, P->start, off2.p, enc.p, fin2.p, /*all_accessible=*/false, 0));
   if (T->n_states == 0) {
+    tally.branch = 4;
     DBuf<uint32_t> out(pool, 1);  // nothing reaches a final state
     HIP_CHECK(hipMemsetAsync(out.p, 0, sizeof(uint32_t), st));
     enc_facts_kernel<<<grid16(ctx, np + 1), TPB, 0, st>>>(off2.p, enc.p, np + 1, out.p);
@@ -884,7 +934,7 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
   tr_sort_device(ctx, T.get(), false);  // tr_sort(ILabelCompare) on the encode labels (olabel carries their order)
   // decode's mapper keeps none of the bits tr_unique leaves (decode_static.rs:52-66); rm_final_epsilon's set_final /
   // del_trs pairs end in delete_trs_properties and connect (rm_final_epsilon.rs:62-75): ACCESSIBLE | COACCESSIBLE
-  return minimize_connected(ctx, T.get(), enc.p, ACCESSIBLE | COACCESSIBLE, path);
+  return minimize_connected(ctx, T.get(), enc.p, ACCESSIBLE | COACCESSIBLE, knobs);
 }
 
 // ================================================================ batch (wfst_minimize_batch)
@@ -1020,6 +1070,7 @@ __global__ void __launch_bounds__(MB_TPB) minimize_batch_kernel(const MbItem* __
     c.outdeg = it.outdeg;
     c.order = it.order;
     c.ctl = it.cctl;
+    c.hmask = ~0ull;
     wg_fill(it.cctl, C_WORDS, 0u);
     if (weighted_in) wg_fill((uint32_t*)it.d, n, __float_as_uint(INF));
     wg_bar();
@@ -1202,6 +1253,7 @@ __global__ void __launch_bounds__(MB_TPB) minimize_batch_kernel(const MbItem* __
   c.big = it.big;
   c.by_olabel = weighted_in ? 1u : 0u;
   c.refine = 1u;
+  c.hmask = ~0ull;
   wg_fill(it.cctl, C_WORDS, 0u);
   wg_fill64(it.tab, size, 0ull);
   wg_fill(it.smin, size, NONE);

@@ -132,6 +132,19 @@ class Context:
         check(_lib.lib().wfst_ctx_get_determinize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_determinize_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def minimize_stats(self) -> dict:
+        """Which route this context's last minimize call took (wfst_ctx_get_minimize_stats).  For the cycle check on the
+        untrimmed input (check_*) and for the refinement of the connected machine (no prefix): non-empty levels peeled
+        (levels), those the device-wide launches ran (wide_levels), launches of the one-workgroup kernel (narrow_launches)
+        by how they ended (exit_wide, exit_done).  For the call: the branch taken (branch: 0 none, 1 unweighted, 2 weighted,
+        3 weighted without a start state, 4 nothing left after connect), states a wave refined (wave_states) and full
+        signature compares that found a difference (unequal_compares).  Unspecified after minimize_batch and optimize."""
+        names = ("check_levels", "check_wide_levels", "check_narrow_launches", "check_exit_wide", "check_exit_done", "levels",
+                 "wide_levels", "narrow_launches", "exit_wide", "exit_done", "branch", "wave_states", "unequal_compares")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_minimize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_minimize_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""

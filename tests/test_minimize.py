@@ -396,7 +396,9 @@ def tr_unique(fst):  # tr_unique.rs:8-51: stable sort on (ilabel, olabel, nextst
     fst["props"] = p
 
 
-def acceptor_minimize(fst):  # minimize.rs:181-211
+def acceptor_minimize(fst, seen=None):  # minimize.rs:181-211
+    """seen (a dict): receives T, a copy of the connected, label-sorted machine the partition is computed on (what
+    minimize.hip's run_core refines), and part, its Partition"""
     props = compute_and_update(fst, ACCEPTOR | UNWEIGHTED | ACYCLIC)
     if props & (ACCEPTOR | UNWEIGHTED) != ACCEPTOR | UNWEIGHTED:
         raise Unsupported("FST is not an unweighted acceptor")
@@ -412,6 +414,10 @@ def acceptor_minimize(fst):  # minimize.rs:181-211
         p |= O_LABEL_SORTED
     fst["props"] = p
     part = acyclic_partition(fst)
+    if seen is not None:
+        seen["T"] = dict(rows=[[list(tr) for tr in row] for row in fst["rows"]], finals=list(fst["finals"]),
+                         start=fst["start"], props=fst["props"])
+        seen["part"] = part
     merge_states(part, fst)
     tr_unique(fst)
 
@@ -481,7 +487,8 @@ def is_cyclic(flat):
 
 def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=None):
     """minimize_with_config (minimize.rs:92-176), statement by statement, for the branch this project supports; raises
-    Unsupported with the KO message otherwise.  Returns flat arrays."""
+    Unsupported with the KO message otherwise.  Returns flat arrays.  partition_out (a dict): see acceptor_minimize (in the
+    weighted branch T is the encoded machine with its superfinal state)."""
     fst = flat_to_fst(flat)
     props = compute_and_update(fst, ACCEPTOR | I_DETERMINISTIC | WEIGHTED | UNWEIGHTED)
     if not props & I_DETERMINISTIC and not allow_nondet:
@@ -529,7 +536,7 @@ def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=N
             ftr[0], ftr[1], ftr[2] = lab, lab, F32(0.0)
         enc_mask = I_LABEL_INVARIANT & O_LABEL_INVARIANT & WEIGHT_INVARIANT & ADD_SUPER_FINAL
         tr_map(fst, e_arc, e_fin, True, lambda p: p & enc_mask)
-        acceptor_minimize(fst)
+        acceptor_minimize(fst, partition_out)
         # decode (decode_static.rs): labels and weights back, then rm_final_epsilon
         def d_arc(tr):
             il, ol, w = tuples[tr[0] - 1]
@@ -538,7 +545,7 @@ def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=N
         tr_map(fst, d_arc, lambda ftr: None, False, lambda p: p & dec_mask)
         rm_final_epsilon(fst)
     else:
-        acceptor_minimize(fst)
+        acceptor_minimize(fst, partition_out)
     return fst_to_flat(fst)
 
 
