@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -719,6 +719,37 @@ wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, u
                                         uint64_t* levels, uint64_t* wide_levels, uint64_t* narrow_launches, uint64_t* exit_wide,
                                         uint64_t* exit_done, uint64_t* branch, uint64_t* wave_states,
                                         uint64_t* unequal_compares);
+
+/* ---- which route the last wfst_shortest_distance_with_config, wfst_reweight or wfst_push_weights call of ctx took.  Each
+ *      of the three resets the counters when it begins, also when it refuses an argument; they hold that call's values also
+ *      when it ends KO.  They are tallied on the host from launch geometry, the round loop's counter and values the call
+ *      reads back anyway: no launch, no copy and no synchronisation of their own.  The structural passes are also entered
+ *      from wfst_minimize, wfst_closure, wfst_concat and the list forms: after any call but the three above the counters
+ *      are unspecified.
+ *      A frontier search (the Vec length of a distance call; reachability, co-reachability on the reversed FST, in-degree
+ *      peeling and the start-on-a-cycle search of the structural passes) over a graph of n states launches one
+ *      bfs_round_kernel per round.  After round R = 1, 2, .. the host reads the size of frontier R when R is a multiple of
+ *      16 or R = n + 1, and stops at the first read that finds it empty, or at R = n + 1 (the reversed FST has n + 1
+ *      states).
+ *        searches       frontier searches,
+ *        rounds         bfs_round_kernel launches of all of them,
+ *        reads          host reads of a frontier size,
+ *        rounds_max     the most rounds of one search,
+ *        bfs_blocks     blocks of the last bfs_round_kernel launch (16 lanes per frontier state, at most 8 blocks per
+ *                       compute unit),
+ *        arcs_blocks    ... of reweight_arcs_kernel (16 lanes per state, at most 32 per compute unit),
+ *        total_blocks   ... of total_weight_kernel (a lane per state, at most 4 per compute unit); 0: the kernel did not run,
+ *        structural     1: the four structural facts were searched (the start branch ran on a word that does not know
+ *                       INITIAL_CYCLIC / INITIAL_ACYCLIC),
+ *        start_branch   0 not taken, 1 the start state reweighted in place, 2 a new start state,
+ *        removed        remove_total_weight: 0 not requested, 1 skipped because the total is one or zero, 2 applied.
+ *      WFST_PUSH_MAX_BLOCKS=n (a positive integer; for tests) is an upper bound on those three grids, so that inputs of a
+ *      few hundred states run the kernels' stride loops; read per call, unset or empty changes nothing, anything else is
+ *      KO in the three calls above (before any other argument is looked at but reweight_type, potentials and delta).
+ *      Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_push_stats(wfst_ctx* ctx, uint64_t* searches, uint64_t* rounds, uint64_t* reads, uint64_t* rounds_max,
+                                    uint64_t* bfs_blocks, uint64_t* arcs_blocks, uint64_t* total_blocks, uint64_t* structural,
+                                    uint64_t* start_branch, uint64_t* removed);
 
 /* wfst_compose_shortest_path_batch with the results as RECORDS (the layout of wfst_fst_pack_paths below) instead of handles:
  * out[i * (4 + 4 * max_arcs) ...] = path i, written straight from the kernel's result buffers — for hosts that read the

@@ -773,6 +773,8 @@ struct SccVisitor {
   std::vector<bool> onstack;
   std::vector<uint32_t> scc_stack;
   int32_t nscc = 0;
+  // the four DFS pairs (scc_visitors.rs:29-37: all positive until the visit finds otherwise)
+  uint64_t props = P::ACYCLIC | P::INITIAL_ACYCLIC | P::ACCESSIBLE | P::COACCESSIBLE;
   explicit SccVisitor(const Fst& f, bool compute_scc_) : fst(&f), compute_scc(compute_scc_) {
     size_t n = f.num_states();
     if (compute_scc) scc.assign(n, -1);
@@ -790,6 +792,7 @@ struct SccVisitor {
     lowlink[s] = (int32_t)nstates;
     onstack[s] = true;
     access[s] = root == start;
+    if (root != start) props = (props | P::NOT_ACCESSIBLE) & ~P::ACCESSIBLE;  // scc_visitors.rs:73-79
     nstates++;
     return true;
   }
@@ -798,6 +801,8 @@ struct SccVisitor {
     uint32_t t = tr.nextstate;
     if (dfnumber[t] < lowlink[s]) lowlink[s] = dfnumber[t];
     if (coaccess[t]) coaccess[s] = true;
+    props = (props | P::CYCLIC) & ~P::ACYCLIC;  // scc_visitors.rs:97-102
+    if (t == start) props = (props | P::INITIAL_CYCLIC) & ~P::INITIAL_ACYCLIC;
     return true;
   }
   bool forward_or_cross_tr(uint32_t s, const Tr& tr) {  // connect.rs:133-146
@@ -824,6 +829,7 @@ struct SccVisitor {
         onstack[t] = false;
         scc_stack.pop_back();
       } while (s != t);
+      if (!scc_coaccess) props = (props | P::NOT_COACCESSIBLE) & ~P::COACCESSIBLE;  // scc_visitors.rs:155-158
       nscc++;
     }
     if (has_parent) {
@@ -3062,6 +3068,12 @@ void oracle_fst_project(oracle_fst* f, int project_output) {
 int oracle_rm_epsilon(oracle_fst* f) {
   DeltaGuard g(ORACLE_EQ_REF_KDELTA);
   return rm_epsilon_impl(*f) ? 0 : 1;
+}
+
+uint64_t oracle_fst_dfs_properties(const oracle_fst* f) {
+  SccVisitor visitor(*f, false);
+  dfs_visit(*f, visitor, false);
+  return visitor.props;
 }
 
 int oracle_connect(oracle_fst* f) {

@@ -117,6 +117,10 @@ void oracle_fst_project(oracle_fst*, int project_output);
 int oracle_rm_epsilon(oracle_fst*);
 /* connect(): connect.rs:51-66 */
 int oracle_connect(oracle_fst*);
+/* the word SccVisitor's depth-first visit leaves (visitors/scc_visitors.rs:29-37, 73-79, 97-102, 155-158): exactly one bit
+ * of each of ACCESSIBLE, COACCESSIBLE, CYCLIC / ACYCLIC, INITIAL_CYCLIC / INITIAL_ACYCLIC; the stored word is not read.
+ * Without a start state nothing is visited and all four positive bits come back. */
+uint64_t oracle_fst_dfs_properties(const oracle_fst* f);
 /* shortest_path_with_config(nshortest=1): shortest_path.rs:107-133,173-282.
  * Optional outputs (may be NULL): distance[n_states], total weight of the chosen path. */
 int oracle_shortest_path(const oracle_fst* f, int eq_mode, oracle_fst** out, float* distance,

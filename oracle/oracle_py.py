@@ -61,6 +61,8 @@ def lib():
         L.oracle_compose.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.oracle_compose_filter.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.oracle_connect.argtypes = [vp]
+        L.oracle_fst_dfs_properties.argtypes = [vp]
+        L.oracle_fst_dfs_properties.restype = u64
         L.oracle_rm_epsilon.argtypes = [vp]
         L.oracle_fst_project.argtypes = [vp, C.c_int]
         L.oracle_compose_lookahead.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
@@ -181,6 +183,10 @@ class OracleFst:
     @property
     def properties(self):
         return self.info()[3]
+
+    def dfs_properties(self):
+        """the four pairs SccVisitor's depth-first visit decides, as a word (the stored word is not read)"""
+        return int(lib().oracle_fst_dfs_properties(self._h))
 
     def to_flat(self):
         n, a, start, props = self.info()

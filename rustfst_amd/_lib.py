@@ -106,6 +106,7 @@ SYMBOLS = [
     ("wfst_shortest_distance_with_config", C.c_int, [_vp, _vp, _P(ShortestDistanceConfig), _vp, _P(_u32)]),
     ("wfst_push_weights", C.c_int, [_vp, _vp, _u32, _P(PushWeightsConfig), _P(_vp)]),
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
+    ("wfst_ctx_get_push_stats", C.c_int, [_vp] + [_P(_u64)] * 10),
     ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
     ("wfst_determinize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(DeterminizeConfig), _P(_vp), _vp]),
     ("wfst_determinize_with_distance", C.c_int, [_vp, _vp, _vp, _u64, _f32, _P(_vp), _P(_vp), _P(_u64)]),

@@ -459,8 +459,10 @@ wfst_status wfst_shortest_distance(wfst_ctx* ctx, const wfst_fst* fst, float* di
 wfst_status wfst_shortest_distance_with_config(wfst_ctx* ctx, const wfst_fst* fst, const wfst_shortest_distance_config* cfg,
                                                float* distance, uint32_t* len) {
   return wrap([&] {
+    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
     const wfst_shortest_distance_config c = cfg ? *cfg : wfst_shortest_distance_config{0u, 1e-6f};
     if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("shortest_distance: delta must be finite and >= 0");
+    (void)push_max_blocks_knob();
     if (!ctx || !fst || !distance) throw Error("null pointer");
     HIP_CHECK(hipSetDevice(ctx->device));
     shortest_distance_ex(ctx, fst, c.reverse != 0, distance, len);
@@ -472,9 +474,11 @@ wfst_status wfst_push_weights(wfst_ctx* ctx, const wfst_fst* fst, uint32_t rewei
                               wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
+    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
     const wfst_push_weights_config c = cfg ? *cfg : wfst_push_weights_config{1.0f / 1024.0f, 0u};
     if (reweight_type > 1) throw Error("push_weights: unknown reweight_type " + std::to_string(reweight_type));
     if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("push_weights: delta must be finite and >= 0");
+    (void)push_max_blocks_knob();
     if (!ctx || !fst || !out) throw Error("null pointer");
     HIP_CHECK(hipSetDevice(ctx->device));
     *out = push_weights_fst(ctx, fst, reweight_type, c.remove_total_weight != 0);
@@ -486,8 +490,10 @@ wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* poten
                           uint32_t reweight_type, wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
+    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
     if (reweight_type > 1) throw Error("reweight: unknown reweight_type " + std::to_string(reweight_type));
     if (!potentials && n_potentials) throw Error("reweight: potentials is NULL but n_potentials > 0");
+    (void)push_max_blocks_knob();
     if (!ctx || !fst || !out) throw Error("null pointer");
     HIP_CHECK(hipSetDevice(ctx->device));
     *out = reweight_fst(ctx, fst, potentials, n_potentials, reweight_type);
@@ -877,6 +883,25 @@ wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, u
     if (branch) *branch = c.branch;
     if (wave_states) *wave_states = c.wave_states;
     if (unequal_compares) *unequal_compares = c.unequal_compares;
+  });
+}
+
+wfst_status wfst_ctx_get_push_stats(wfst_ctx* ctx, uint64_t* searches, uint64_t* rounds, uint64_t* reads, uint64_t* rounds_max,
+                                    uint64_t* bfs_blocks, uint64_t* arcs_blocks, uint64_t* total_blocks, uint64_t* structural,
+                                    uint64_t* start_branch, uint64_t* removed) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::PushStats& c = ctx->push_stats;
+    if (searches) *searches = c.searches;
+    if (rounds) *rounds = c.rounds;
+    if (reads) *reads = c.reads;
+    if (rounds_max) *rounds_max = c.rounds_max;
+    if (bfs_blocks) *bfs_blocks = c.bfs_blocks;
+    if (arcs_blocks) *arcs_blocks = c.arcs_blocks;
+    if (total_blocks) *total_blocks = c.total_blocks;
+    if (structural) *structural = c.structural;
+    if (start_branch) *start_branch = c.start_branch;
+    if (removed) *removed = c.removed;
   });
 }
 

@@ -260,6 +260,14 @@ struct wfst_ctx {
     } check, refine;
     uint64_t branch = 0, wave_states = 0, unequal_compares = 0;
   } min_stats;
+  // the route of the last wfst_shortest_distance_with_config / wfst_reweight / wfst_push_weights call
+  // (wfst_ctx_get_push_stats): tallied on the host by push.hip from its launch geometry, its loop counter and the values
+  // it reads back anyway
+  struct PushStats {
+    uint64_t searches = 0, rounds = 0, reads = 0, rounds_max = 0;
+    uint64_t bfs_blocks = 0, arcs_blocks = 0, total_blocks = 0;
+    uint64_t structural = 0, start_branch = 0, removed = 0;
+  } push_stats;
   // the one-wave path kernels (wfst_ctx_get_small_path_stats): the last sp1_wave_kernel launch since the last
   // wfst_shortest_path / wfst_shortest_path_batch call began, and the last shortest_path_nbest_batch
   struct SmallPathStats {
@@ -559,6 +567,9 @@ wfst_fst* reweight_fst(wfst_ctx* ctx, const wfst_fst* f, const float* potentials
 wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_type, bool remove_total_weight);
 // push.hip: the four DFS pairs compute_and_update_properties(INITIAL_ACYCLIC) fills in (props::merge_dfs), searched on the device
 uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f);
+// push.hip: WFST_PUSH_MAX_BLOCKS (tests), the cap on the grids of push.hip's three strided kernels: 0 when unset or empty,
+// throws on anything but a positive integer.  Read per call; the three entry points call it before anything else runs.
+uint32_t push_max_blocks_knob();
 // determinize.hip: determinize_with_config of an acceptor (a NEW handle); det_type in the ffi numbering
 wfst_fst* determinize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, uint32_t det_type);
 // ... of a label-encoded machine (optimize.hip): no "the word must say ACCEPTOR" check, the gallic call's word

@@ -7,9 +7,13 @@
 //   INITIAL_ACYCLIC    only when the start branch runs and the word does not know it: reachability (BFS from the start),
 //                      co-reachability (BFS on the reversed handle), cycle existence (in-degree peeling), start on a cycle
 //   the start state    (at most one arc list and one final weight) and the property word: on the host
+//   which route ran    wfst_ctx_get_push_stats, tallied on the host (include/wfst.h; WFST_PUSH_MAX_BLOCKS for tests)
 // TropicalWeight with the reference's semantics: tropical.h (a start potential within 1/1024 of 0 is one).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -17,7 +21,29 @@
 
 namespace wfst {
 
+// WFST_PUSH_MAX_BLOCKS=n (tests): at most n blocks for bfs_round_kernel, reweight_arcs_kernel and total_weight_kernel, the
+// three kernels that stride, so that inputs of a few hundred states run their stride loops.  0: no cap (unset or empty).
+uint32_t push_max_blocks_knob() {
+  const char* e = std::getenv("WFST_PUSH_MAX_BLOCKS");
+  if (!e || !*e) return 0;
+  char* end = nullptr;
+  const unsigned long v = std::strtoul(e, &end, 10);
+  if (*e < '0' || *e > '9' || *end || std::strlen(e) > 9 || v == 0)
+    throw Error(std::string("WFST_PUSH_MAX_BLOCKS: expected a positive number of blocks, not '") + e + "'");
+  return (uint32_t)v;
+}
+
 namespace {
+
+// blocks of a strided launch: what the work asks for, at most per_cu blocks per compute unit, at most the knob's cap
+constexpr uint32_t BFS_BLOCKS_PER_CU = 8;     // bfs_round_kernel
+constexpr uint32_t ARCS_BLOCKS_PER_CU = 32;   // reweight_arcs_kernel
+constexpr uint32_t TOTAL_BLOCKS_PER_CU = 4;   // total_weight_kernel
+uint32_t strided_grid(const wfst_ctx* ctx, uint32_t wanted, uint32_t per_cu) {
+  uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(wanted, (uint32_t)ctx->n_cus * per_cu));
+  if (const uint32_t cap = push_max_blocks_knob()) blocks = std::min(blocks, cap);
+  return blocks;
+}
 
 // ---------------------------------------------------------------- structural passes
 // One round of a frontier search: every state of the frontier (16 lanes per state) looks at its arcs.
@@ -79,7 +105,9 @@ constexpr uint32_t ROUNDS_PER_CHECK = 16;  // rounds queued between two reads of
 // Frontier search over g (offsets / arcs on the device) from the states in `seeds`.  mode 0: `mark` holds the visited
 // flags (the caller sets those of the seeds it does not want visited again); mode 1: `mark` holds in-degrees and the
 // frontier starts with the states of in-degree 0 (seeds ignored).  Rounds are launched ROUNDS_PER_CHECK at a time; the
-// host reads the size of the next frontier between batches and stops at an empty one.
+// host reads the size of the next frontier between batches and stops at an empty one.  The round rule:
+// after round R = 1, 2, .. the host reads the size of frontier R when R is a multiple of ROUNDS_PER_CHECK or R = n + 1,
+// and stops at the first read that finds it empty or at R = n + 1.
 Search frontier_search(wfst_ctx* ctx, uint32_t n, const uint32_t* off, const wfst_tr* arcs, const std::vector<uint32_t>& seeds,
                        uint32_t* mark, int mode) {
   hipStream_t st = ctx->stream;
@@ -98,19 +126,28 @@ Search frontier_search(wfst_ctx* ctx, uint32_t n, const uint32_t* off, const wfs
     zero_indegree_kernel<<<(n + 255) / 256, 256, 0, st>>>(mark, n, fr0.p, cnt, stats);
     HIP_CHECK(hipGetLastError());
   }
-  const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 15) / 16, (uint32_t)ctx->n_cus * 8));  // 16 lanes per state
+  const uint32_t blocks = strided_grid(ctx, (n + 15) / 16, BFS_BLOCKS_PER_CU);  // 16 lanes per state
   uint32_t* fr[2] = {fr0.p, fr1.p};
   uint32_t next = 1;
+  uint32_t rounds = 0, reads = 0;
   for (uint32_t r = 0;; ++r) {
     bfs_round_kernel<<<blocks, 256, 0, st>>>(off, arcs, fr[r & 1], cnt + r % 3, fr[(r + 1) & 1], cnt + (r + 1) % 3,
                                              cnt + (r + 2) % 3, mark, stats, mode);
     HIP_CHECK(hipGetLastError());
+    rounds = r + 1;
     if ((r + 1) % ROUNDS_PER_CHECK == 0 || r + 1 >= n + 1) {
       HIP_CHECK(hipMemcpyAsync(&next, cnt + (r + 1) % 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
+      reads += 1;
       if (next == 0 || r + 1 >= n + 1) break;  // (n + 1 rounds empty any frontier: each state joins once)
     }
   }
+  wfst_ctx::PushStats& ps = ctx->push_stats;
+  ps.searches += 1;
+  ps.rounds += rounds;
+  ps.reads += reads;
+  ps.rounds_max = std::max<uint64_t>(ps.rounds_max, rounds);
+  ps.bfs_blocks = blocks;
   uint32_t h[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(h, stats, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
@@ -151,6 +188,7 @@ const wfst_fst* reversed_handle(wfst_ctx* ctx, const wfst_fst* f) {
 // visits anything (dfs_visit.rs:104-110), so the visitor's word is the one it was constructed with: all four positive bits.
 uint64_t structural_bits(wfst_ctx* ctx, const wfst_fst* f) {
   if (f->start < 0) return props::dfs_bits(true, true, false, false);
+  ctx->push_stats.structural = 1;
   const uint32_t n = f->n_states;
   const uint32_t s0 = (uint32_t)f->start;
   ensure_device(const_cast<wfst_fst*>(f));
@@ -305,6 +343,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
   DevicePool& pool = *ctx->pool;
   // remove_weight does nothing when the total is one or zero (push.rs:150-152)
   const bool remove = remove_total && !is_one(total) && !is_zero(total);
+  ctx->push_stats.removed = remove ? 2 : remove_total ? 1 : 0;
   // room for the state reweight may add (reweight.rs:129-138)
   DBuf<uint32_t> off_out(pool, (size_t)n + 2);
   DBuf<wfst_tr> arcs_out(pool, E + 1);
@@ -314,9 +353,10 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
   unsigned long long* last_op = (unsigned long long*)(facts.p + 2);
   HIP_CHECK(hipMemcpyAsync(off_out.p, f->dev.offsets, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   if (n && E) {
-    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 15) / 16, (uint32_t)ctx->n_cus * 32));
+    const uint32_t blocks = strided_grid(ctx, (n + 15) / 16, ARCS_BLOCKS_PER_CU);
     reweight_arcs_kernel<<<blocks, 256, 0, st>>>(f->dev.offsets, f->dev.arcs, n, pot, len, to_final, arcs_out.p, facts.p);
     HIP_CHECK(hipGetLastError());
+    ctx->push_stats.arcs_blocks = blocks;
   }
   if (n) {
     reweight_finals_kernel<<<(n + 255) / 256, 256, 0, st>>>(f->dev.finals, n, pot, len, to_final, total,
@@ -372,6 +412,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
         p = props::set_final(p, nullptr, nullptr);
       }
       start_dirty = true;
+      ctx->push_stats.start_branch = 1;
     } else {  // (:129-138) a new start state n with one eps:eps arc into the old start
       const wfst_tr a{0u, 0u, factor, (uint32_t)start};
       p = props::add_state(p);
@@ -385,6 +426,7 @@ wfst_fst* reweight_device(wfst_ctx* ctx, const wfst_fst* f, const float* pot, ui
       start = n;
       n_out = n + 1;
       e_out = E + 1;
+      ctx->push_stats.start_branch = 2;
     }
   }
   p = props::reweight(p);  // (:148-151)
@@ -485,9 +527,10 @@ wfst_fst* push_weights_fst(wfst_ctx* ctx, const wfst_fst* f, uint32_t reweight_t
       DBuf<uint32_t> key(*ctx->pool, 1);
       const uint32_t kinf = f32_key(INF);  // zero
       HIP_CHECK(hipMemcpyAsync(key.p, &kinf, sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-      const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)ctx->n_cus * 4));
+      const uint32_t blocks = strided_grid(ctx, (n + 255) / 256, TOTAL_BLOCKS_PER_CU);
       total_weight_kernel<<<blocks, 256, 0, ctx->stream>>>(d, f->dev.finals, n, key.p);
       HIP_CHECK(hipGetLastError());
+      ctx->push_stats.total_blocks = blocks;
       total = key_f32(read_u32(ctx, key.p));
     }
   }

@@ -145,6 +145,20 @@ class Context:
         check(_lib.lib().wfst_ctx_get_minimize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_minimize_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def push_stats(self) -> dict:
+        """Which route this context's last shortest_distance(reverse=..) with a length, reweight or push_weights call took
+        (wfst_ctx_get_push_stats): frontier searches (searches), their bfs_round_kernel launches (rounds), host reads of a
+        frontier size (reads), the most rounds of one search (rounds_max), the grids of the last bfs_round_kernel,
+        reweight_arcs_kernel and total_weight_kernel launch (bfs_blocks, arcs_blocks, total_blocks; 0: did not run), whether
+        the structural facts were searched (structural), the start branch (start_branch: 0 not taken, 1 in place, 2 new
+        start state) and remove_total_weight (removed: 0 not requested, 1 skipped, 2 applied).  Unspecified after any other
+        call."""
+        names = ("searches", "rounds", "reads", "rounds_max", "bfs_blocks", "arcs_blocks", "total_blocks", "structural",
+                 "start_branch", "removed")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_push_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_push_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
