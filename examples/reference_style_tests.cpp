@@ -6,6 +6,7 @@
 //   K7  rustfst-python/tests/algorithms/test_project.py:5-97           test_project_input / test_project_output
 //   K8  rustfst-python/tests/algorithms/test_connect.py:4-55           test_connect
 //   K11 rustfst-python/tests/algorithms/test_rm_epsilon.py:4-54        test_rm_epsilon
+//   K17 rustfst-python/tests/algorithms/test_optimize.py                test_optimize, through the list form as well
 //   the look-ahead recipe of rustfst-cli/src/cmds/compose.rs:77-181 on the K1 operands: same language as compose
 //   error behaviour of compose on unsorted operands (compose_fst_op.rs:169-197) and of missing states (mutable_fst.rs)
 //
@@ -214,6 +215,32 @@ static void test_rm_epsilon() {  // K11
   ASSERT(f == expected);
 }
 
+static void test_optimize_batch() {  // K17: the machine of the reference's test, alone and twice in one list
+  VectorFst f;
+  for (int i = 0; i < 4; ++i) f.add_state();
+  f.set_start(0);
+  f.set_final(3, 0.0f);
+  f.add_tr(0, tr(1, 2, 1.0f, 1));
+  f.add_tr(0, tr(1, 3, 2.0f, 2));
+  f.add_tr(1, tr(0, 0, 3.0f, 3));
+  f.add_tr(1, tr(4, 6, 4.0f, 3));
+  f.add_tr(2, tr(7, 8, 5.0f, 3));
+  VectorFst expected;
+  for (int i = 0; i < 4; ++i) expected.add_state();
+  expected.set_start(0);
+  expected.set_final(1, 0.0f);
+  expected.set_final(3, 0.0f);
+  expected.add_tr(0, tr(1, 2, 4.0f, 1));
+  expected.add_tr(0, tr(1, 3, 7.0f, 2));
+  expected.add_tr(1, tr(4, 6, 1.0f, 3));
+  expected.add_tr(2, tr(7, 8, 0.0f, 3));
+  const std::vector<VectorFst> got = optimize_batch({f, f});
+  ASSERT(got.size() == 2 && got[0] == expected && got[1] == expected);
+  ASSERT(optimize_batch({}).empty());
+  optimize(f);
+  ASSERT(f == expected);
+}
+
 static void test_lookahead_recipe() {
   // fst![1,2 => 2,3] o fst![2,3 => 3,4] through the look-ahead configuration: one path, input 1 2, output 3 4, weight one
   VectorFst a, b;
@@ -240,6 +267,7 @@ static void test_lookahead_recipe() {
 int main() {
   test_connect();
   test_rm_epsilon();
+  test_optimize_batch();
   test_project();
   test_lookahead_recipe();
   test_compose_fst();

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -324,6 +324,33 @@ wfst_status wfst_ctx_get_minimize_batch_stats(wfst_ctx* ctx, uint64_t* launches,
 wfst_status wfst_tr_sum(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
 wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
 
+/* ---- tr_sum / tr_unique of n FSTs in one call: outs[i] is a NEW handle, bit-identical (offsets, arcs with their weights'
+ *      bit patterns, finals, start state, property word) to what wfst_tr_sum / wfst_tr_unique(ctx, fsts[i], ..) returns.
+ *      The same handle may appear more than once in fsts.  n == 0: OK.  The inputs are left exactly as they are, their
+ *      cached derived data and property words included.
+ *      One workgroup per item and ONE launch for the whole list: the workgroup runs the passes of the single call (the
+ *      rank sort with 16 lanes per state, keep flags and survivors per state, a workgroup scan of the counts, the write
+ *      pass with the serial fold of tr_sum / the KDELTA chain of tr_unique) on its item inside the item's slice of one
+ *      slab.  The slices are sized on the host from n_states and n_arcs alone (the result never has more arcs than the
+ *      input), so nothing is run twice.  Launches and host synchronisations of a call do not depend on n: one launch of
+ *      the batch kernel, one read-back of the items' control blocks, and one adoption of all results out of the slab.
+ *      A slice takes 33 bytes per arc and 8 per state (about 50 KB for an item of 500 states and 1500 arcs, 560 KB at the
+ *      rule's limit below); the slices of one call may take 8 GiB together: a list that needs more is KO before anything
+ *      is launched ("split the list").
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when item i has at most 4096 states, at most
+ *      16384 arcs and no state with more than 256 arcs (the limit of the rank sort; the kernel finds such a state itself
+ *      and leaves the item).  An item without states and an item with at most one arc never occupy a workgroup, are
+ *      produced as the single call produces them and count as in_kernel[i] == 1.  in_kernel[i] == 0: the item went
+ *      through wfst_tr_sum / wfst_tr_unique unchanged.
+ *      KO — every argument is checked before anything is launched: NULL pointers, NULL list entries ("item <i>: null FST
+ *      in batch"), a handle of another device or context.  On any KO every outs[i] is NULL, nothing is leaked and the
+ *      context works afterwards. ---- */
+wfst_status wfst_tr_sum_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
+wfst_status wfst_tr_unique_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_tr_sum_batch / wfst_tr_unique_batch call of ctx: launches of the batch kernel (0 or 1), items with
+ *      in_kernel == 1, items that went through the single-FST path.  All 0 after a KO before any launch. */
+wfst_status wfst_ctx_get_tr_sum_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single);
+
 /* ---- optimize: fst_optimize (rustfst-ffi) = rustfst::algorithms::optimize (rustfst/src/algorithms/optimize.rs:11-128) for
  *      the tropical semiring (IDEMPOTENT), one call over device-resident stages.  Every branch is taken on the STORED
  *      property word:
@@ -351,6 +378,36 @@ wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
  *      No start state: rm_epsilon returns its input, tr_map (encode, decode) returns at once, determinize yields the empty
  *      FST.  An input that trims to nothing ends as the empty FST.  A NEW handle; fst is left as it is. ---- */
 wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+
+/* ---- optimize of n FSTs in one call: outs[i] is a NEW handle, bit-identical to what wfst_optimize(ctx, fsts[i], ..)
+ *      returns.  The same handle may appear more than once; n == 0: OK; the inputs are left exactly as they are.  Every
+ *      branch is taken on the stored word, as in wfst_optimize, and every stage is ONE batch call over the items that take it:
+ *        1. wfst_rm_epsilon_batch over the items whose word lacks NO_EPSILONS
+ *        2. wfst_tr_sum_batch over every item
+ *        3. on the word after 2: I_DETERMINISTIC -> 4; no I_DETERMINISTIC and no ACYCLIC -> KO with wfst_optimize's message;
+ *           otherwise an item whose INPUT word holds ACCEPTOR goes through wfst_determinize_batch (KDELTA, Functional) and
+ *           on to 4; any other item is a transducer and takes the single call's encode, determinize, minimize, decode on
+ *           its own (there is no batch form of the label encoding)
+ *        4. wfst_minimize_batch (KSHORTESTDELTA, allow_nondet = false)
+ *      Launches: those of the four batch calls (the rule, the slab limit of 8 GiB with "split the list" and the growth of
+ *      each are described with them), whatever n is, plus the single-call launches of every transducer and of every
+ *      item that a stage hands to its single path.  Intermediate handles are destroyed on every exit.
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when every stage item i went through ran it in that
+ *      stage's batch kernel (for wfst_tr_sum_batch: at most 4096 states, 16384 arcs, no state with more than 256 arcs).
+ *      A transducer has in_kernel[i] == 0.
+ *      KO — NULL pointers, NULL list entries ("item <i>: null FST in batch") and handles of another device or context are
+ *      checked before anything is launched.  Otherwise the answer is that of the loop `for i: wfst_optimize(fsts[i])`: the
+ *      single call's message for the LOWEST failing index, prefixed by "item <i>: ".  The stages run on sublists, so when
+ *      one reports item i, the call drops its intermediates and runs wfst_optimize's steps over items 0..i in index order
+ *      to find the first failing one (a cold path).  Errors that belong to no item ("split the list", "did not converge")
+ *      pass through unchanged.  On any KO every outs[i] is NULL, nothing is leaked and the context works afterwards. ---- */
+wfst_status wfst_optimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_optimize_batch call of ctx: launches[4] = launches of the batch kernels of rm_epsilon, tr_sum, determinize
+ *      and minimize; items by their in_kernel flag; and the transducers among the items_single.  Any pointer may be NULL.
+ *      The per-stage getters (wfst_ctx_get_{rm_epsilon,tr_sum,determinize,minimize}_batch_stats) read as the last call of
+ *      that stage, whoever made it. */
+wfst_status wfst_ctx_get_optimize_batch_stats(wfst_ctx* ctx, uint64_t* launches /* [4]: rm_epsilon, tr_sum, determinize, minimize */,
+                                              uint64_t* items_in_kernel, uint64_t* items_single, uint64_t* items_transducer);
 
 /* ---- union, concat, closure: fst_union / fst_concat (rustfst-ffi/src/algorithms/{union,concat}.rs) =
  *      rustfst::algorithms::{union::union, concat::concat, closure::closure} (union/union_static.rs:55-118,

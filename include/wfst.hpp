@@ -19,7 +19,8 @@
 //   determinize(&fst) / determinize_with_config(&fst, config)    determinize(fst) / determinize_with_config(..)   determinize_static.rs:149-190
 //   determinize_with_distance(&fst, &in_dist, delta)             determinize_with_distance(fst, in_dist, delta)   determinize_static.rs:24-39
 //   (many acceptors in one call)                                 determinize_batch / determinize_with_distance_batch
-//                                                                minimize_batch, rm_epsilon_batch
+//                                                                minimize_batch, rm_epsilon_batch, tr_sum_batch,
+//                                                                tr_unique_batch, optimize_batch
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
@@ -392,6 +393,30 @@ inline void optimize(VectorFst& fst) {
   check(wfst_optimize(Context::current().get(), a.h, &c.h));
   fst = detail::download(c);
 }
+// tr_sum, tr_unique and optimize of many FSTs in one call each (wfst_tr_sum_batch, wfst_tr_unique_batch,
+// wfst_optimize_batch): the results (the arguments are left as they are)
+namespace detail {
+template <class Call>
+inline std::vector<VectorFst> batch_call(const std::vector<VectorFst>& fsts, Call call) {
+  std::vector<DeviceFst> in(fsts.size()), out(fsts.size());
+  std::vector<const wfst_fst*> hs(fsts.size());
+  std::vector<wfst_fst*> os(fsts.size(), nullptr);
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    upload(fsts[i], in[i]);
+    hs[i] = in[i].h;
+  }
+  check(call(Context::current().get(), hs.data(), hs.size(), os.data(), nullptr));
+  std::vector<VectorFst> res;
+  for (size_t i = 0; i < fsts.size(); ++i) {
+    out[i].h = os[i];
+    res.push_back(download(out[i]));
+  }
+  return res;
+}
+}  // namespace detail
+inline std::vector<VectorFst> tr_sum_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_tr_sum_batch); }
+inline std::vector<VectorFst> tr_unique_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_tr_unique_batch); }
+inline std::vector<VectorFst> optimize_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_optimize_batch); }
 
 // union (union/union_static.rs:55-118), concat (concat/concat_static.rs:53-109) and closure (closure/closure_static.rs:25-73):
 // the first operand is changed in place, like the reference (`union` is a C++ keyword, hence union_).  Results are in general

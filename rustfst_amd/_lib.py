@@ -120,6 +120,11 @@ SYMBOLS = [
     ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_optimize", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_tr_sum_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
+    ("wfst_tr_unique_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
+    ("wfst_ctx_get_tr_sum_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_optimize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
+    ("wfst_ctx_get_optimize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_union", C.c_int, [_vp, _vp, _vp, _P(_vp)]),
     ("wfst_concat", C.c_int, [_vp, _vp, _vp, _P(_vp)]),
     ("wfst_closure", C.c_int, [_vp, _vp, _u32, _P(_vp)]),

@@ -525,7 +525,8 @@ static void check_batch_args(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t 
 }
 // The preamble of the one-workgroup-per-item batch calls, behind null_outs and the op's own config checks: the counters of
 // the last call go, then the arguments are checked.  false: an empty list, nothing to do.
-static bool begin_batch_call(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, BatchStats wfst_ctx::*stats) {
+extern "C++" template <class Stats>  // (BatchStats, and OptimizeBatchStats of wfst_optimize_batch)
+static bool begin_batch_call(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, Stats wfst_ctx::*stats) {
   if (ctx) ctx->*stats = {};
   if (n == 0) return false;
   check_batch_args(ctx, fsts, n, outs);
@@ -664,6 +665,25 @@ wfst_status wfst_tr_unique(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   });
 }
 
+// tr_sum / tr_unique of n FSTs (one workgroup each, one launch); every argument is checked before anything is launched
+wfst_status wfst_tr_sum_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    null_outs(outs, n);
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::trsum_batch)) return;
+    tr_sum_batch(ctx, fsts, n, false, outs, in_kernel);
+  });
+}
+wfst_status wfst_tr_unique_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    null_outs(outs, n);
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::trsum_batch)) return;
+    tr_sum_batch(ctx, fsts, n, true, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_tr_sum_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single) {
+  return get_batch_stats(ctx, &wfst_ctx::trsum_batch, launches, items_in_kernel, items_single);
+}
+
 // optimize (optimize.rs:11-128), tropical semiring
 wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
@@ -671,6 +691,24 @@ wfst_status wfst_optimize(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
     if (!ctx || !fst || !out) throw Error("null pointer");
     HIP_CHECK(hipSetDevice(ctx->device));
     *out = optimize_fst(ctx, fst);
+  });
+}
+// optimize of n FSTs over the four batch stages; every argument is checked before anything is launched
+wfst_status wfst_optimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    null_outs(outs, n);
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::opt_batch)) return;
+    optimize_batch(ctx, fsts, n, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_optimize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single,
+                                              uint64_t* items_transducer) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (launches) std::copy(ctx->opt_batch.launches, ctx->opt_batch.launches + 4, launches);
+    if (items_in_kernel) *items_in_kernel = ctx->opt_batch.in_kernel;
+    if (items_single) *items_single = ctx->opt_batch.single;
+    if (items_transducer) *items_transducer = ctx->opt_batch.transducer;
   });
 }
 

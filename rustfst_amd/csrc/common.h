@@ -199,6 +199,10 @@ struct RearmRecord {
 struct BatchStats {  // one call of a one-workgroup-per-item batch operation
   uint64_t launches = 0, in_kernel = 0, single = 0;
 };
+struct OptimizeBatchStats {  // one wfst_optimize_batch call; launches per stage: rm_epsilon, tr_sum, determinize, minimize
+  uint64_t launches[4] = {0, 0, 0, 0};
+  uint64_t in_kernel = 0, single = 0, transducer = 0;
+};
 }  // namespace wfst
 
 // ---------------------------------------------------------------- handles
@@ -242,6 +246,9 @@ struct wfst_ctx {
   // the last wfst_determinize_batch / wfst_determinize_with_distance_batch, wfst_minimize_batch and wfst_rm_epsilon_batch
   // call (wfst_ctx_get_{determinize,minimize,rm_epsilon}_batch_stats; batch_driver.h counts)
   wfst::BatchStats det_batch, min_batch, rm_batch;
+  // ... and the last wfst_tr_sum_batch / wfst_tr_unique_batch and wfst_optimize_batch calls
+  wfst::BatchStats trsum_batch;
+  wfst::OptimizeBatchStats opt_batch;
   // which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took
   // (wfst_ctx_get_determinize_stats): tallied on the host from the control block determinize.hip already reads back
   struct DeterminizeStats {
@@ -583,6 +590,8 @@ wfst_fst* determinize_with_distance_fst(wfst_ctx* ctx, const wfst_fst* f, const 
                                         std::vector<float>& out_dist);
 // tr_sum.hip: tr_sum / tr_unique (a NEW handle)
 wfst_fst* tr_sum_fst(wfst_ctx* ctx, const wfst_fst* f, bool unique);
+// ... of n FSTs in one call, one workgroup each (new handles; on a throw every outs[i] is null)
+void tr_sum_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, bool unique, wfst_fst** outs, uint8_t* in_kernel);
 // rational.hip: union / concat / closure and the list forms (NEW handles; the operands are left as they are)
 wfst_fst* union_fst(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b);
 wfst_fst* concat_fst(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b);
@@ -594,6 +603,8 @@ wfst_fst* concat_list_fst(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n);
 void rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n);
 // optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)
 wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
+// ... of n FSTs in one call over the four batch stages (new handles; on a throw every outs[i] is null)
+void optimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
 // minimize.hip: minimize_with_config of a deterministic acyclic acceptor (a NEW handle)
 wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow_nondet);
 // ... of n acceptors in one call, one workgroup each and one launch for all (new handles; on a throw every outs[i] is null)

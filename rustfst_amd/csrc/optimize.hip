@@ -14,9 +14,16 @@
 //          decode to pairs of an epsilon-free FST), so only its closing connect acts.
 // The encoded machine is determinized by the ACCEPTOR construction although its word lacks ACCEPTOR and the reference
 // takes the gallic one: DESIGN.md §3.10 shows the two results are identical on a label-encoded machine.
+// optimize_batch (wfst_optimize_batch) takes the same branches for a list, every stage as one batch call over the sublist
+// that needs it; transducers still take encode_deter_mini_decode one by one.
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <memory>
+#include <string>
+#include <vector>
 
+#include "batch_driver.h"
 #include "common.h"
 #include "fst_props.h"
 
@@ -177,6 +184,118 @@ wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f) {
   Handle det(determinize_fst(ctx, x, KDELTA, /*Functional*/ 0u));
   cur.reset();
   return minimize_fst(ctx, det.get(), KSHORTESTDELTA, false);
+}
+
+namespace {
+
+// "item <k>: <rest>", the form in which the batch stages report an item: k and where <rest> begins.  false: the error
+// belongs to no item ("split the list", "did not converge", a HIP error)
+bool item_error(const char* what, size_t* k, const char** rest) {
+  if (std::strncmp(what, "item ", 5) != 0) return false;
+  char* end = nullptr;
+  const unsigned long long v = std::strtoull(what + 5, &end, 10);
+  if (end == what + 5 || end[0] != ':' || end[1] != ' ') return false;
+  *k = (size_t)v;
+  *rest = end + 2;
+  return true;
+}
+
+}  // namespace
+
+// optimize of n FSTs: the branches of optimize_fst, each stage as ONE batch call over the sublist that takes it (DESIGN.md
+// §3.10).  cur[i] is item i's intermediate handle (none yet: the input itself); every one is destroyed on every exit.
+void optimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  using namespace props;
+  ctx->opt_batch = {};
+  check_items_owned(ctx, fsts, n, "optimize_batch");
+  OptimizeBatchStats& stats = ctx->opt_batch;
+  std::vector<Handle> cur(n);
+  std::vector<uint8_t> flag(n, 1);
+  auto at = [&](size_t i) -> const wfst_fst* { return cur[i] ? cur[i].get() : fsts[i]; };
+  // An item error at index i.  The stages run on sublists, so an item below i may fail in a LATER stage, and the loop of
+  // single calls would report that one: the intermediates go, optimize_fst replays items 0..i in index order and the first
+  // error met is thrown with its index in front.  A cold path.
+  auto replay = [&](size_t i, const std::string& message) {
+    for (Handle& h : cur) h.reset();
+    for (size_t j = 0; j <= i; ++j) {
+      try {
+        Handle again(optimize_fst(ctx, fsts[j]));
+      } catch (const std::exception& e) {
+        throw Error("item " + std::to_string(j) + ": " + e.what());
+      }
+    }
+    throw Error("item " + std::to_string(i) + ": " + message);  // (the replay found nothing: the stage's own message)
+  };
+  // one stage over the sublist `sub`: its results replace the items' intermediates, its flags join theirs
+  auto stage = [&](const std::vector<size_t>& sub, int which, const BatchStats& inner, auto&& call) {
+    if (sub.empty()) return;
+    const size_t m = sub.size();
+    std::vector<const wfst_fst*> in(m);
+    std::vector<wfst_fst*> got(m, nullptr);
+    std::vector<uint8_t> fl(m, 0);
+    for (size_t k = 0; k < m; ++k) in[k] = at(sub[k]);
+    try {
+      call(in.data(), m, got.data(), fl.data());
+    } catch (const std::exception& e) {
+      stats.launches[which] = inner.launches;
+      size_t k = 0;
+      const char* rest = nullptr;
+      if (!item_error(e.what(), &k, &rest) || k >= m) throw;
+      replay(sub[k], rest);
+    }
+    stats.launches[which] = inner.launches;
+    for (size_t k = 0; k < m; ++k) {
+      cur[sub[k]].reset(got[k]);
+      flag[sub[k]] &= fl[k];
+    }
+  };
+  std::vector<size_t> sub;
+  // 1. rm_epsilon unless the word holds NO_EPSILONS
+  for (size_t i = 0; i < n; ++i)
+    if (!(fsts[i]->props & NO_EPSILONS)) sub.push_back(i);
+  stage(sub, 0, ctx->rm_batch, [&](const wfst_fst* const* in, size_t m, wfst_fst** got, uint8_t* fl) { rm_epsilon_batch(ctx, in, m, got, fl); });
+  // 2. tr_sum of every item
+  sub.resize(n);
+  for (size_t i = 0; i < n; ++i) sub[i] = i;
+  stage(sub, 1, ctx->trsum_batch, [&](const wfst_fst* const* in, size_t m, wfst_fst** got, uint8_t* fl) { tr_sum_batch(ctx, in, m, false, got, fl); });
+  // 3. on the word after tr_sum (optimize_fst's branch table)
+  std::vector<size_t> det, mini, trans;
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t p = cur[i]->props;
+    if (p & I_DETERMINISTIC) {
+      mini.push_back(i);
+    } else if (!(p & ACYCLIC)) {
+      replay(i, "optimize: inputs whose property word does not hold ACYCLIC are not supported");
+    } else if (fsts[i]->props & ACCEPTOR) {
+      det.push_back(i);
+      mini.push_back(i);
+    } else {
+      trans.push_back(i);
+    }
+  }
+  stage(det, 2, ctx->det_batch, [&](const wfst_fst* const* in, size_t m, wfst_fst** got, uint8_t* fl) {
+    determinize_batch(ctx, in, m, KDELTA, /*Functional*/ 0u, got, fl);
+  });
+  // 4. minimize
+  stage(mini, 3, ctx->min_batch, [&](const wfst_fst* const* in, size_t m, wfst_fst** got, uint8_t* fl) {
+    minimize_batch(ctx, in, m, KSHORTESTDELTA, false, got, fl);
+  });
+  // transducers: no batch form of the label encoding; each on its own
+  for (size_t i : trans) {
+    try {
+      cur[i].reset(encode_deter_mini_decode(ctx, cur[i].get()));
+    } catch (const std::exception& e) {
+      const std::string message = e.what();
+      replay(i, message);
+    }
+    flag[i] = 0;
+    stats.transducer += 1;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    (flag[i] ? stats.in_kernel : stats.single) += 1;
+    outs[i] = cur[i].release();
+  }
+  if (in_kernel) std::copy(flag.begin(), flag.end(), in_kernel);
 }
 
 }  // namespace wfst

@@ -850,6 +850,45 @@ def rm_epsilon_batch_stats(ctx: Optional[Context] = None) -> dict:
     return _batch_stats("wfst_ctx_get_rm_epsilon_batch_stats", ctx)
 
 
+def tr_sum_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
+    """[f.tr_sum() for f in fsts] as ONE call (wfst_tr_sum_batch): one workgroup per FST and one launch for the whole
+    list — the step between rm_epsilon_batch and determinize_batch.  return_in_kernel: also the uint8 array that says
+    which items the batch kernel finished (0: more than 4096 states or 16384 arcs, or a state with more than 256 arcs,
+    sent the item through the single-FST path)."""
+    return _batch_call("wfst_tr_sum_batch", fsts, ctx, return_in_kernel)
+
+
+def tr_unique_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
+    """[f.tr_unique() for f in fsts] as ONE call (wfst_tr_unique_batch); see tr_sum_batch."""
+    return _batch_call("wfst_tr_unique_batch", fsts, ctx, return_in_kernel)
+
+
+def tr_sum_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last tr_sum_batch / tr_unique_batch call of ctx (wfst_ctx_get_tr_sum_batch_stats)."""
+    return _batch_stats("wfst_ctx_get_tr_sum_batch_stats", ctx)
+
+
+def optimize_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
+    """[f.optimize() for f in fsts] as ONE call (wfst_optimize_batch): rm_epsilon_batch over the items whose word lacks
+    NO_EPSILONS, tr_sum_batch over all, determinize_batch and minimize_batch over the acceptors; a transducer takes the
+    label encoding of the single call on its own.  return_in_kernel: also the uint8 array that says which items every
+    stage ran in its batch kernel (0 for a transducer).  Any item that f.optimize would refuse raises WfstError with
+    "item <i>: " in front of that call's message, for the lowest such i."""
+    return _batch_call("wfst_optimize_batch", fsts, ctx, return_in_kernel)
+
+
+def optimize_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last optimize_batch call of ctx (wfst_ctx_get_optimize_batch_stats): launches per stage, items by flag, and
+    the transducers among the items_single."""
+    ctx = ctx or default_context()
+    launches = (C.c_uint64 * 4)()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(_lib.lib().wfst_ctx_get_optimize_batch_stats(ctx._h, launches, C.byref(a), C.byref(b), C.byref(c)),
+          "wfst_ctx_get_optimize_batch_stats")
+    return dict(launches=dict(zip(("rm_epsilon", "tr_sum", "determinize", "minimize"), (int(x) for x in launches))),
+                items_in_kernel=a.value, items_single=b.value, items_transducer=c.value)
+
+
 def _take_floats(ptr, count):
     out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(count,)).copy() if count else np.zeros(0, np.float32)
     _lib.lib().wfst_bytes_destroy(ptr)
