@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -707,6 +707,19 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
                                             uint64_t* wave_first, uint64_t* relaunch_states, uint64_t* relaunch_arcs,
                                             uint64_t* relaunch_hash, uint64_t* relaunch_path, uint64_t* switched_wide,
                                             uint64_t* two_step, uint64_t* caps_states, uint64_t* caps_arcs, uint64_t* caps_hash);
+
+/* ---- the chase runs of string_compose_sp_kernel in the last wfst_compose_shortest_path_batch[_begin/_end/_packed] call of
+ *      ctx.  On its vector path (batches of more than 8 strings, or WFST_STRING_SCALAR=0) a level with ONE frontier state,
+ *      a block of at most 64 arcs, exactly ONE arc that carries the string's label, a level behind it in the string and two
+ *      free states in the problem's LDS slice is taken by a loop that only follows the matched arc to the next block; the
+ *      distances, parents and arc weights of such a run's states are filled in when the run ends.  Every other level, and
+ *      every level with WFST_STRING_RUN=0, is done one by one as before; the results are the same bit for bit, so only
+ *      these counters show what ran.  Tallied on the host from two words every problem's result already carries, over the
+ *      problems the string kernel answered; a call resets them when it begins.
+ *        run_levels  levels taken inside runs,
+ *        runs        runs of at least one level.
+ *      Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_string_run_stats(wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs);
 
 /* ---- which route the levels of the last wfst_determinize / wfst_determinize_with_distance call of ctx took.  The result
  *      is built breadth-first level by level, and every route returns the same FST, so only these counters show which one

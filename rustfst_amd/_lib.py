@@ -85,6 +85,7 @@ SYMBOLS = [
     ("wfst_ctx_get_bounded_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(C.c_char_p)]),
     ("wfst_ctx_get_small_path_stats", C.c_int, [_vp] + [_P(_u64)] * 7),
     ("wfst_ctx_get_compose_path_stats", C.c_int, [_vp] + [_P(_u64)] * 12),
+    ("wfst_ctx_get_string_run_stats", C.c_int, [_vp] + [_P(_u64)] * 2),
     ("wfst_ctx_get_determinize_stats", C.c_int, [_vp] + [_P(_u64)] * 19),
     ("wfst_ctx_trim_pool", C.c_int, [_vp]),
     ("wfst_fst_project", C.c_int, [_vp, _vp, C.c_int]),

@@ -869,6 +869,14 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
   });
 }
 
+wfst_status wfst_ctx_get_string_run_stats(wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    if (run_levels) *run_levels = ctx->string_run_levels;
+    if (runs) *runs = ctx->string_runs;
+  });
+}
+
 wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* wide_levels, uint64_t*
                                            narrow_launches, uint64_t* exit_wide_states, uint64_t* exit_wide_cands,
                                            uint64_t* exit_budget, uint64_t* exit_need, uint64_t* exit_done, uint64_t*

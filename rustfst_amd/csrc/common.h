@@ -289,6 +289,9 @@ struct wfst_ctx {
     uint64_t switched_wide = 0, two_step = 0;
     uint64_t caps_states = 0, caps_arcs = 0, caps_hash = 0;  // Caps of the last compose_wave_kernel launch
   } compose_path;
+  // the chase runs of the string o T kernel in the last fused-batch call (wfst_ctx_get_string_run_stats): levels taken inside
+  // runs and the number of runs, summed over the problems the kernel answered
+  uint64_t string_run_levels = 0, string_runs = 0;
   // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;

@@ -97,6 +97,7 @@ struct Result {
   uint32_t n_levels;
   uint32_t facts;     // string_compose_sp_kernel: OR of the path arcs' property facts (fst_props.h: path_arc_facts), or
                       // PATH_FACTS_NONE: the host knows the path FST's properties without reading its arcs back
+  uint32_t run_levels, runs;  // string_compose_sp_kernel: levels taken inside chase runs, and the number of runs (0 elsewhere)
   uint32_t done;      // string_compose_sp_kernel, results in pinned memory: the run's ticket, written after everything else of
                       // the problem (system-scope fence in between): the host waits for these words instead of the stream
 #ifdef WFST_PHASE_TIMING
@@ -308,10 +309,14 @@ __device__ inline void equal_range_global(const wfst_tr* arcs, uint32_t n, bool 
   }
 #define PT_STORE(res) \
   for (int pt_i = 0; pt_i < 8; ++pt_i) (res).dbg[pt_i] = pt_acc[pt_i];
+// (string_compose_sp_kernel: the rows asked for so far have arrived.  The wait is part of the timing build only: it ends the
+// overlap the real kernel has, so such a build gives the SHARES of a level, not its length)
+#define PT_ROWS_IN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
 #define PT_DECL
 #define PT_MARK(k)
 #define PT_STORE(res)
+#define PT_ROWS_IN()
 #endif
 
 struct Level {
@@ -1026,7 +1031,7 @@ constexpr uint32_t STR_NONE = 0xFFFFFFFFu;
 __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDesc* __restrict__ descs, FstView f2,
                                                                 Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
                                                                 uint32_t path_cap, uint32_t n_problems, uint32_t maxs, uint64_t f2_n_arcs,
-                                                                uint32_t scalar_rows, uint32_t done_ticket) {
+                                                                uint32_t scalar_rows, uint32_t run_on, uint32_t done_ticket) {
   extern __shared__ uint32_t s_dyn[];
   const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (p >= n_problems) return;
@@ -1037,6 +1042,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   const uint32_t lane = lane_id();
   // the problem's result, then (everything this wave wrote is in host memory) its ticket
 #define STR_RESULT() do {                                                                                  \
+    PT_STORE(res)                                                                                          \
     res.done = 0u;                                                                                         \
     if (lane == 0) results[p] = res;                                                                       \
     if (done_ticket != 0u) { /* (0: a large batch — the host waits for the stream, see launch_begin) */     \
@@ -1056,6 +1062,8 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   res.path_off = 0;
   res.n_levels = 0;
   res.facts = props::PATH_FACTS_NONE;
+  res.run_levels = res.runs = 0;
+  PT_DECL
   if (f1.start < 0 || f2.start < 0) {  // compute_start -> None
     STR_RESULT();
     return;
@@ -1089,15 +1097,121 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   const uint32_t L_u = rl(L, 0);  // (L in a scalar register: the early-issue decision stays a scalar branch)
   uint4 pf_a = make_uint4(0, 0, 0, 0);
   uint2 pf_nx = make_uint2(0, 0);
+  // The chase run (vector path, run_on): while the frontier is ONE state whose block fits one chunk and ONE arc of it carries
+  // the label, the only dependence from level to level is rows -> the matched lane -> that arc's anext pair -> the next rows.
+  // A run level does that and nothing else: the matched lane parks its arc's output label and weight in the new state's LDS
+  // slots, and the distances, parents and arc weights of the run's states (consecutive ids, one per level) are settled when the
+  // run ends, 64 levels at a time, by on_match's own arithmetic in level order.  A level that is not such a one (no match,
+  // several matches, a longer block, the string's last level, the last state of the slice) ends the run with `pos` on it and is
+  // done by the general level below, from the rows the run already holds (pf) where it has them.
+  PT_MARK(6)  // prologue
   for (uint32_t pos = 0; pos < L && F && ok; ++pos) {
-    const bool use_pf = pf;  // set by the last level: this level is one state, and lanes < min(its arc count, 64) hold its rows
-    pf = false;
-    const uint32_t pl = pos & 63u;
-    if (pos && pl == 0u) {
+    if (pos && (pos & 63u) == 0u) {
       ch_cur = ch_nxt;
       ch_nxt = make_uint4(0, 0, 0, 0);
       if (pos + 64u + lane < L) ch_nxt = ld_global16(f1.arcs + pos + 64u + lane);
     }
+    if (run_on && F == 1u && (!scalar_rows || run_on == 2u)) {
+      uint32_t fb = rl(nb, 0), fc = rl(nc, 0);
+      if (fc <= 64u && pos + 1u < L_u && hi + 1u < maxs) {
+        const uint32_t p0 = pos, h0 = hi;
+        uint4 a = pf_a;
+        uint2 nx = pf_nx;
+        if (!pf) {
+          a = make_uint4(0, 0, 0, 0);
+          nx = make_uint2(0, 0);
+          if (lane < fc) {
+            a = ld_global16(f2.arcs + fb + lane);
+            nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
+          }
+        }
+        uint32_t qd = 0;
+        for (;;) {
+          PT_MARK(5)  // run: from the rows' arrival to the next rows' issue
+          PT_ROWS_IN()
+          PT_MARK(4)  // run: waiting for the rows
+          const uint64_t m = __ballot(lane < fc && a.x == rl(ch_cur.x, pos & 63u));
+          if (m == 0ull || (m & (m - 1ull)) != 0ull) {  // the general level's: lanes < fc hold its rows
+            pf_a = a;
+            pf_nx = nx;
+            pf = true;
+            break;
+          }
+          const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+          if (lane == l) {  // state hi = (pos + 1, a.w): its slots hold the arc until the settle
+            s_ol[hi] = a.y;
+            s_w[hi] = __uint_as_float(a.z);
+          }
+          qd = rl(a.w, l);
+          fb = rl(nx.x, l);
+          fc = rl(nx.y, l);
+          n_arcs += 1;
+          hi += 1;
+          pos += 1;
+          pf = false;
+          if ((pos & 63u) == 0u) {
+            ch_cur = ch_nxt;
+            ch_nxt = make_uint4(0, 0, 0, 0);
+            if (pos + 64u + lane < L) ch_nxt = ld_global16(f1.arcs + pos + 64u + lane);
+          }
+          if (fc > 64u) break;
+          a = make_uint4(0, 0, 0, 0);
+          nx = make_uint2(0, 0);
+          if (lane < fc) {
+            a = ld_global16(f2.arcs + fb + lane);
+            nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
+          }
+          if (!(pos + 1u < L_u && hi + 1u < maxs)) {  // the general level's, with these rows
+            pf_a = a;
+            pf_nx = nx;
+            pf = true;
+            break;
+          }
+        }
+        const uint32_t n_run = pos - p0;
+        if (n_run) {
+          PT_MARK(5)
+          // the settle.  State h0 + j entered level p0 + j + 1 over the arc parked in its slots, from state h0 + j - 1 (F == 1:
+          // lo == hi - 1 all along the run)
+          lds_handoff();
+          float dd = __uint_as_float(rl(__float_as_uint(d), 0));
+          for (uint32_t base = 0; base < n_run; base += 64u) {
+            const uint32_t j = base + lane;
+            float ws = INF;
+            if (j < n_run) {
+              const float w1 = __uint_as_float(ld_global16(f1.arcs + p0 + j).z);
+              ws = wtimes(w1, s_w[h0 + j]);  // add_tr, compose_fst_op.rs:267-285
+              s_w[h0 + j] = ws;
+            }
+            uint32_t par = STR_NONE;
+            const uint32_t cnt = n_run - base < 64u ? n_run - base : 64u;
+            for (uint32_t k = 0; k < cnt; ++k) {  // (a float sum is not associative: in level order, as on_match does it)
+              const float wk = __uint_as_float(rl(__float_as_uint(ws), k));
+              float c = INF;
+              if (dd < INF) c = (dd + wk) + 0.0f;
+              const bool reached = c < INF;
+              if (lane == k && reached) par = h0 + base + k - 1u;
+              dd = reached ? c : INF;
+            }
+            if (j < n_run) s_par[h0 + j] = par;
+          }
+          if (lane == 0) {
+            q = qd;
+            nb = fb;
+            nc = fc;
+            d = dd;
+          }
+          lo = hi - 1u;
+          level = pos;
+          res.run_levels += n_run;
+          res.runs += 1u;
+          PT_MARK(3)  // run: the settle
+        }
+      }
+    }
+    const bool use_pf = pf;  // set by the last level: this level is one state, and lanes < min(its arc count, 64) hold its rows
+    pf = false;
+    const uint32_t pl = pos & 63u;
     const uint32_t label = rl(ch_cur.x, pl);
     const float w1 = __uint_as_float(rl(ch_cur.z, pl));
     uint32_t nq = 0, nnb = 0, nnc = 0, n_new = 0;  // new states of the next level: lane k holds state hi + k
@@ -1196,10 +1310,16 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
         if (use_pf && base == 0u) {  // (F == 1: f == 0)
           a = pf_a;
           nx = pf_nx;
-        } else if (have) {
-          a = ld_global16(f2.arcs + fb + base + lane);
-          nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + base + lane));
+          PT_MARK(1)  // general level: bookkeeping since the early issue (under the load)
+        } else {
+          PT_MARK(2)  // general level: from the rows' arrival to the next rows' issue
+          if (have) {
+            a = ld_global16(f2.arcs + fb + base + lane);
+            nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + base + lane));
+          }
         }
+        PT_ROWS_IN()
+        PT_MARK(0)  // general level: waiting for the rows
         uint64_t m = __ballot(have && a.x == label);  // the label-equal run of fst2's (sorted) block, in arc order
         n_arcs += (uint32_t)__popcll(m);
         if (F == 1u && fc <= 64u && !scalar_rows && pos + 1u < L_u && m != 0ull && (m & (m - 1ull)) == 0ull) {
@@ -1215,6 +1335,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
             pf_nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (xb + lane));
           }
           pf = true;
+          PT_MARK(2)
           if (!on_match(f, fd, qd, ol, xb, xc, w2)) ok = false;
           m = 0;
         }
@@ -1237,6 +1358,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
     d = nd;
     if (F) level = pos + 1;
   }
+  PT_MARK(2)
   if (!ok) {
     res.status = ST_NOT_A_STRING_CASE;
     STR_RESULT();
@@ -1321,6 +1443,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
       res.facts = facts;
     }
   }
+  PT_MARK(7)  // epilogue: finals, pointer jumping, path write
   STR_RESULT();
 }
 
@@ -1493,7 +1616,10 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
         k_desc, f2, k_res, k_paths, path_cap, (uint32_t)n, maxs, f2.n_arcs,
         // scalar arc-block loads where a wave is alone on its SIMD (a handful of strings): -7 % per level; with eight waves
         // per compute unit the other waves hide the vector latency anyway and the extra scalar instructions cost 3 %
-        env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u), run.done_ticket);
+        env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u),
+        // the chase run of the vector path (WFST_STRING_RUN=0: every level is the general one; 2: also on the scalar-row path:
+        // a measurement setting — profiles/string_run_ab.md has its figure; launches of <= 8 strings keep their route)
+        env.has("WFST_STRING_RUN") ? (uint32_t)std::min(std::max(std::atoi(env.get("WFST_STRING_RUN")), 0), 2) : 1u, run.done_ticket);
   } else {
     compose_wave_kernel<FLAGS><<<(uint32_t)n, 64, 0, st>>>(k_desc, f2, caps, run.arena.p, run.stride, k_res, k_paths, path_cap,
                                                             run.d_cursor.p);
@@ -1546,6 +1672,16 @@ void launch_end(wfst_ctx* ctx, BatchRun& run) {
   }
   run.results.assign(h_res, h_res + n);
 #ifdef WFST_PHASE_TIMING
+  if (run.string_kernel) {
+    unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lv = 0, rlv = 0;
+    for (size_t i = 0; i < n; ++i) {
+      for (int k = 0; k < 8; ++k) tot[k] += h_res[i].dbg[k];
+      lv += h_res[i].n_levels;
+      rlv += h_res[i].run_levels;
+    }
+    std::fprintf(stderr, "[string phase ticks/problem] general: rows wait %llu | under the early load %llu | arrival->issue %llu || run: rows wait %llu | arrival->issue %llu | settle %llu || prologue %llu | epilogue %llu  (n=%zu, levels/problem %.1f, of them in runs %.1f)\n",
+                 tot[0] / n, tot[1] / n, tot[2] / n, tot[4] / n, tot[5] / n, tot[3] / n, tot[6] / n, tot[7] / n, n, (double)lv / n, (double)rlv / n);
+  }
   if (!run.string_kernel) {
     unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (size_t i = 0; i < n; ++i)
@@ -1758,6 +1894,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   job->ctx = ctx;
   job->n = n;
   ctx->compose_path = wfst_ctx::ComposePathStats{};
+  ctx->string_run_levels = ctx->string_runs = 0;
   if (n == 0) return job.release();
   job->env = EnvSnap::take();
   job->run_s.env = &job->env;
@@ -1871,6 +2008,8 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
         tot_arcs += r.n_arcs;
         tot_states += r.n_states;
         n_string_ok += 1;
+        ctx->string_run_levels += r.run_levels;
+        ctx->string_runs += r.runs;
         ok.push_back(k);
       }
       // the path FSTs (three small vectors and a handle each: ~0.4 us): a large batch shares them out among host threads

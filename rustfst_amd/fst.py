@@ -118,6 +118,15 @@ class Context:
         check(_lib.lib().wfst_ctx_get_compose_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_compose_path_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def string_run_stats(self) -> dict:
+        """The chase runs of the string kernel in this context's last compose_shortest_path_batch call
+        (wfst_ctx_get_string_run_stats): levels taken inside runs (run_levels) and the number of runs (runs), summed over
+        the problems the kernel answered.  Both are 0 with WFST_STRING_RUN=0 and on the scalar-row path."""
+        names = ("run_levels", "runs")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_string_run_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_string_run_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def determinize_stats(self) -> dict:
         """Which route the levels of this context's last determinize / determinize_with_distance call took
         (wfst_ctx_get_determinize_stats): levels completed (levels) and those the device-wide launches ran (wide_levels),
