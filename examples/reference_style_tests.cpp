@@ -241,6 +241,26 @@ static void test_optimize_batch() {  // K17: the machine of the reference's test
   ASSERT(f == expected);
 }
 
+static void test_top_sort() {  // K19: the machine of the reference's python test: two states, the start is the second
+  VectorFst f;
+  const StateId s1 = f.add_state(), s2 = f.add_state();
+  f.set_start(s2);
+  f.set_final(s1, 0.0f);
+  f.add_tr(s2, tr(1, 2, 1.0f, s1));
+  ASSERT(*f.start() == s2);
+  top_sort(f);
+  ASSERT(*f.start() == s1);
+  VectorFst expected;
+  expected.add_state();
+  expected.add_state();
+  expected.set_start(0);
+  expected.set_final(1, 0.0f);
+  expected.add_tr(0, tr(1, 2, 1.0f, 1));
+  ASSERT(f == expected);
+  state_sort(f, {1, 0});  // ... and back
+  ASSERT(*f.start() == 1 && f.num_trs(1) == 1 && f.get_trs(1)[0].nextstate == 0);
+}
+
 static void test_lookahead_recipe() {
   // fst![1,2 => 2,3] o fst![2,3 => 3,4] through the look-ahead configuration: one path, input 1 2, output 3 4, weight one
   VectorFst a, b;
@@ -268,6 +288,7 @@ int main() {
   test_connect();
   test_rm_epsilon();
   test_optimize_batch();
+  test_top_sort();
   test_project();
   test_lookahead_recipe();
   test_compose_fst();

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -438,6 +438,40 @@ wfst_status wfst_concat(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfs
 wfst_status wfst_closure(wfst_ctx* ctx, const wfst_fst* f, uint32_t closure_type, wfst_fst** out);
 wfst_status wfst_union_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
 wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
+
+/* ---- state_sort, top_sort: fst_top_sort (rustfst-ffi/src/algorithms/top_sort.rs) = rustfst::algorithms::{state_sort,
+ *      top_sort} (state_sort.rs:16-78, top_sort.rs:76-94).  The reference works in place; here a NEW handle is returned and
+ *      fst, its cached derived data and its property word are left as they are.
+ *      state_sort: state order[s] of the result holds state s's arcs in their stored order, nextstate = order[nextstate],
+ *              and s's final weight; the start is order[start]; the word is word(fst) & statesort_properties()
+ *              (fst_properties/properties.rs:319-348).  n_order != the number of states: KO "StateSort : Bad order vector
+ *              size : {n_order}. Expected {n_states}".  An order that is not a permutation of the states (a debug_assert in
+ *              the reference): KO "state_sort: order is not a permutation of the states", found on the device before
+ *              anything is written.  No start state: a copy, word unchanged.
+ *      top_sort: decided on the CONTENT, never on the stored word.  Acyclic: state_sort by the reference's order — the
+ *              reverse finishing order of the depth-first search of dfs_visit.rs:97-187, roots the start state, then 0, 1,
+ *              2, .., arcs in stored order — then ACYCLIC | INITIAL_ACYCLIC | TOP_SORTED set in the word and nothing
+ *              cleared (set_properties_with_mask(p, p), vector_fst/mutable_fst.rs:411-414).  A cycle anywhere (a self loop,
+ *              a cycle the start cannot reach): a copy with CYCLIC | NOT_TOP_SORTED set the same way — a stored ACYCLIC,
+ *              INITIAL_ACYCLIC or TOP_SORTED stays.  No start state: without states a copy with the three acyclic bits, with
+ *              states KO "StateSort : Bad order vector size : 0. Expected {n_states}" (the search returns an empty order).
+ *              The order is computed level by level over the Kahn levels of the DAG: consecutive levels
+ *              of at most 256 states inside one launch of one workgroup, a wider level by one device-wide launch per phase;
+ *              WFST_TOP_SORT_PATH=auto|narrow|wide (tests) pins a regime, any other value is KO.  Every route returns the
+ *              same FST. ---- */
+wfst_status wfst_state_sort(wfst_ctx* ctx, const wfst_fst* fst, const uint32_t* order, size_t n_order, wfst_fst** out);
+wfst_status wfst_top_sort(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
+/* the last wfst_top_sort call of ctx (reset when the call begins): Kahn levels peeled (levels; a cyclic input: those peeled
+ *      before the peel ran dry), launches of the one-workgroup and of the device-wide level kernels over the four level
+ *      phases peel, select, sizes, pre (narrow_launches, wide_launches; a cyclic input: the peel's only), levels peeled
+ *      inside one-workgroup launches (narrow_levels), the widest level, the depth of the deepest state in the search forest
+ *      (max_tree_depth: a root has 1), rows of the ancestor table (lift_rows: the least J >= 1 with 2^J > levels), states
+ *      whose in-arcs come from at least two different states (states_compared: they needed a lifted comparison), states
+ *      with 32 in-arcs or more, which a whole wave took (wave_states), and cyclic = 1 for the CYCLIC exit, after which
+ *      max_tree_depth, lift_rows, states_compared and wave_states are 0.  Any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_top_sort_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
+                                        uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* max_tree_depth,
+                                        uint64_t* lift_rows, uint64_t* states_compared, uint64_t* wave_states, uint64_t* cyclic);
 
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no

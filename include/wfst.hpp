@@ -24,6 +24,7 @@
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
+//   top_sort(&mut fst) / state_sort(&mut fst, &order)            top_sort(fst) / state_sort(fst, order)            top_sort.rs, state_sort.rs
 //   union(&mut a, &b) / concat(&mut a, &b)                       union_(a, b) / concat(a, b)                       union_static.rs:55-118, concat_static.rs:53-109
 //   closure(&mut fst, ClosureType)                               closure(fst, ClosureType)                         closure_static.rs:25-73
 //   (rustfst-python union_list / concat_list)                    union_list(fsts) / concat_list(fsts)
@@ -371,6 +372,21 @@ inline std::vector<VectorFst> rm_epsilon_batch(const std::vector<VectorFst>& fst
     res.push_back(detail::download(out[i]));
   }
   return res;
+}
+
+// top_sort (top_sort.rs:76-94) and state_sort (state_sort.rs:16-78): in place, like the reference; a cyclic FST comes back
+// unchanged but for CYCLIC | NOT_TOP_SORTED in its word
+inline void top_sort(VectorFst& fst) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_top_sort(Context::current().get(), a.h, &c.h));
+  fst = detail::download(c);
+}
+inline void state_sort(VectorFst& fst, const std::vector<uint32_t>& order) {
+  detail::DeviceFst a, c;
+  detail::upload(fst, a);
+  check(wfst_state_sort(Context::current().get(), a.h, order.data(), order.size(), &c.h));
+  fst = detail::download(c);
 }
 
 // tr_sum (tr_sum.rs:7-22), tr_unique (tr_unique.rs:38-51) and optimize (optimize.rs:11-128; acyclic inputs, anything else

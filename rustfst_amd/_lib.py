@@ -132,6 +132,9 @@ SYMBOLS = [
     ("wfst_union_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
     ("wfst_concat_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
     ("wfst_rational_check_sizes", C.c_int, [_u32, _vp, _vp, _sz]),
+    ("wfst_state_sort", C.c_int, [_vp, _vp, _vp, _sz, _P(_vp)]),
+    ("wfst_top_sort", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_ctx_get_top_sort_stats", C.c_int, [_vp] + [_P(_u64)] * 10),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

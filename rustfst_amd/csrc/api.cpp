@@ -764,6 +764,42 @@ wfst_status wfst_rational_check_sizes(uint32_t op, const uint64_t* n_states, con
   return wrap([&] { rational_check_sizes(op, n_states, n_arcs, n); });
 }
 
+// state_sort (state_sort.rs:16-78) and top_sort (top_sort.rs:76-94): new handles
+wfst_status wfst_state_sort(wfst_ctx* ctx, const wfst_fst* fst, const uint32_t* order, size_t n_order, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = state_sort_fst(ctx, fst, order, n_order);
+  });
+}
+wfst_status wfst_top_sort(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = top_sort_fst(ctx, fst);
+  });
+}
+wfst_status wfst_ctx_get_top_sort_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
+                                        uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* max_tree_depth,
+                                        uint64_t* lift_rows, uint64_t* states_compared, uint64_t* wave_states, uint64_t* cyclic) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::TopSortStats& c = ctx->top_sort;
+    if (levels) *levels = c.levels;
+    if (narrow_launches) *narrow_launches = c.narrow_launches;
+    if (wide_launches) *wide_launches = c.wide_launches;
+    if (narrow_levels) *narrow_levels = c.narrow_levels;
+    if (max_level_width) *max_level_width = c.max_level_width;
+    if (max_tree_depth) *max_tree_depth = c.max_tree_depth;
+    if (lift_rows) *lift_rows = c.lift_rows;
+    if (states_compared) *states_compared = c.states_compared;
+    if (wave_states) *wave_states = c.wave_states;
+    if (cyclic) *cyclic = c.cyclic;
+  });
+}
+
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

@@ -296,6 +296,12 @@ struct wfst_ctx {
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
   } rm_eps;
+  // the last wfst_top_sort call (wfst_ctx_get_top_sort_stats): tallied on the host by top_sort.hip from its launches, the
+  // level bounds and the three words it reads back anyway
+  struct TopSortStats {
+    uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, max_tree_depth = 0;
+    uint64_t lift_rows = 0, states_compared = 0, wave_states = 0, cyclic = 0;
+  } top_sort;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   uint64_t rearm_armed = 0, rearm_adopted = 0, rearm_dropped = 0;  // wfst_ctx_get_rearm_stats
@@ -604,6 +610,9 @@ wfst_fst* concat_list_fst(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n);
 // the size rule of the five calls above, which each of them calls first, on bare counts (op: 0 union, 1 concat, 2 closure
 // star, 3 closure plus): throws "<op>: result too large: ..."
 void rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n);
+// top_sort.hip: state_sort by an order given on the host and top_sort in the reference's DFS order (NEW handles)
+wfst_fst* state_sort_fst(wfst_ctx* ctx, const wfst_fst* f, const uint32_t* order, size_t n_order);
+wfst_fst* top_sort_fst(wfst_ctx* ctx, const wfst_fst* f);
 // optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)
 wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
 // ... of n FSTs in one call over the four batch stages (new handles; on a throw every outs[i] is null)

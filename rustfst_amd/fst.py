@@ -168,6 +168,18 @@ class Context:
         check(_lib.lib().wfst_ctx_get_push_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_push_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
+    def top_sort_stats(self) -> dict:
+        """Which route this context's last top_sort call took (wfst_ctx_get_top_sort_stats): Kahn levels peeled (levels),
+        launches of the one-workgroup and of the device-wide level kernels over the four level phases (narrow_launches,
+        wide_launches), levels peeled inside one-workgroup launches (narrow_levels), the widest level (max_level_width), the
+        deepest state of the search forest (max_tree_depth), rows of the ancestor table (lift_rows), states with in-arcs from
+        at least two states (states_compared), states a whole wave took (wave_states) and the CYCLIC exit (cyclic)."""
+        names = ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "max_tree_depth", "lift_rows",
+                 "states_compared", "wave_states", "cyclic")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_top_sort_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_top_sort_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
@@ -384,6 +396,20 @@ class DeviceFst:
         """algorithms::rm_epsilon, default config (rm_epsilon_static.rs:50-163): a NEW FST without epsilon:epsilon arcs."""
         out = C.c_void_p()
         check(_lib.lib().wfst_rm_epsilon(self.ctx._h, self._h, C.byref(out)), "Error during rm_epsilon")
+        return DeviceFst(out, self.ctx)
+
+    def top_sort(self) -> "DeviceFst":
+        """algorithms::top_sort (top_sort.rs:76-94): a NEW FST.  Acyclic content: the states in the reference's depth-first
+        order and ACYCLIC | INITIAL_ACYCLIC | TOP_SORTED in the word; a cycle anywhere: a copy with CYCLIC | NOT_TOP_SORTED."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_top_sort(self.ctx._h, self._h, C.byref(out)), "Error during top_sort")
+        return DeviceFst(out, self.ctx)
+
+    def state_sort(self, order) -> "DeviceFst":
+        """algorithms::state_sort (state_sort.rs:16-78): a NEW FST in which state order[s] is this FST's state s."""
+        arr = np.ascontiguousarray(np.asarray(order, dtype=np.uint32))
+        out = C.c_void_p()
+        check(_lib.lib().wfst_state_sort(self.ctx._h, self._h, arr.ctypes.data, arr.size, C.byref(out)), "Error during state_sort")
         return DeviceFst(out, self.ctx)
 
     def connect(self) -> "DeviceFst":
@@ -1195,6 +1221,20 @@ class VectorFst:
         self._dev = None
         return self
 
+    def top_sort(self) -> "VectorFst":
+        """rustfst-python vector_fst.py `top_sort` (algorithms/top_sort.py): in place, returns this FST."""
+        res = self.to_device().top_sort().to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
+    def state_sort(self, order) -> "VectorFst":
+        """algorithms::state_sort (state_sort.rs:16-78): in place, returns this FST."""
+        res = self.to_device().state_sort(order).to_vector_fst()
+        self._p, res._p = res._p, self._p
+        self._dev = None
+        return self
+
     def connect(self) -> "VectorFst":
         """rustfst-python vector_fst.py `connect` (algorithms/connect.py): trims this FST in place and returns it."""
         trimmed = self.to_device().connect().to_vector_fst()
@@ -1375,6 +1415,16 @@ def tr_unique(fst: VectorFst) -> VectorFst:
 def optimize(fst: VectorFst) -> VectorFst:
     """algorithms::optimize (optimize.rs:11-128): in place, returns fst (acyclic inputs only)."""
     return fst.optimize()
+
+
+def top_sort(fst: VectorFst) -> VectorFst:
+    """rustfst-python/rustfst/algorithms/top_sort.py `top_sort`: in place, returns fst."""
+    return fst.top_sort()
+
+
+def state_sort(fst: VectorFst, order) -> VectorFst:
+    """algorithms::state_sort (state_sort.rs:16-78): in place, returns fst."""
+    return fst.state_sort(order)
 
 
 def minimize_with_config(fst: VectorFst, config: MinimizeConfig) -> VectorFst:
