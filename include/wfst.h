@@ -746,7 +746,8 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
  *      ctx.  On its vector path (batches of more than 8 strings, or WFST_STRING_SCALAR=0) a level with ONE frontier state,
  *      a block of at most 64 arcs, exactly ONE arc that carries the string's label, a level behind it in the string and two
  *      free states in the problem's LDS slice is taken by a loop that only follows the matched arc to the next block; the
- *      distances, parents and arc weights of such a run's states are filled in when the run ends.  Every other level, and
+ *      distance, parent and arc weight of the level's one new state are filled in while that block's rows are on their
+ *      way.  Every other level, and
  *      every level with WFST_STRING_RUN=0, is done one by one as before; the results are the same bit for bit, so only
  *      these counters show what ran.  Tallied on the host from two words every problem's result already carries, over the
  *      problems the string kernel answered; a call resets them when it begins.

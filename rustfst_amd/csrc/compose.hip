@@ -1099,10 +1099,12 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   uint2 pf_nx = make_uint2(0, 0);
   // The chase run (vector path, run_on): while the frontier is ONE state whose block fits one chunk and ONE arc of it carries
   // the label, the only dependence from level to level is rows -> the matched lane -> that arc's anext pair -> the next rows.
-  // A run level does that and nothing else: the matched lane parks its arc's output label and weight in the new state's LDS
-  // slots, and the distances, parents and arc weights of the run's states (consecutive ids, one per level) are settled when the
-  // run ends, 64 levels at a time, by on_match's own arithmetic in level order.  A level that is not such a one (no match,
-  // several matches, a longer block, the string's last level, the last state of the slice) ends the run with `pos` on it and is
+  // A run level puts that and nothing else between the rows' arrival and the next rows' issue: the matched arc's fields are
+  // read off its lane first, so the next rows land in the registers the level reads them from (no copy behind a wait; lanes
+  // that do not load keep what they held: every reader masks with lane < fc).  The level's one new state (consecutive ids,
+  // one per level) is settled under that load, by on_match's own arithmetic in level order.  The string's 64-label chunks
+  // are rotated between the segments of a run, not inside the level.  A level that is not such a one (no match, several
+  // matches, a longer block, the string's last level, the last state of the slice) ends the run with `pos` on it and is
   // done by the general level below, from the rows the run already holds (pf) where it has them.
   PT_MARK(6)  // prologue
   for (uint32_t pos = 0; pos < L && F && ok; ++pos) {
@@ -1114,89 +1116,87 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
     if (run_on && F == 1u && (!scalar_rows || run_on == 2u)) {
       uint32_t fb = rl(nb, 0), fc = rl(nc, 0);
       if (fc <= 64u && pos + 1u < L_u && hi + 1u < maxs) {
-        const uint32_t p0 = pos, h0 = hi;
+        const uint32_t p0 = pos;
+        // the rows of the level in (a, nx): lanes < fc hold them, the other lanes hold whatever they held (every reader masks)
         uint4 a = pf_a;
         uint2 nx = pf_nx;
-        if (!pf) {
-          a = make_uint4(0, 0, 0, 0);
-          nx = make_uint2(0, 0);
-          if (lane < fc) {
-            a = ld_global16(f2.arcs + fb + lane);
-            nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
-          }
+        if (!pf && lane < fc) {
+          a = ld_global16(f2.arcs + fb + lane);
+          nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
         }
-        uint32_t qd = 0;
-        for (;;) {
-          PT_MARK(5)  // run: from the rows' arrival to the next rows' issue
-          PT_ROWS_IN()
-          PT_MARK(4)  // run: waiting for the rows
-          const uint64_t m = __ballot(lane < fc && a.x == rl(ch_cur.x, pos & 63u));
-          if (m == 0ull || (m & (m - 1ull)) != 0ull) {  // the general level's: lanes < fc hold its rows
-            pf_a = a;
-            pf_nx = nx;
-            pf = true;
-            break;
+        pf = false;
+        float dd = __uint_as_float(rl(__float_as_uint(d), 0));  // the distance of the run's last state (uniform)
+        // `lane < fc` as a scalar mask, made under the load: the compare's own mask is then the ballot (the predicate as a lane
+        // value costs the chain two dependent vector instructions more)
+        uint64_t fcm = fc >= 64u ? ~0ull : (1ull << fc) - 1ull;
+        PT_MARK(5)
+        for (bool go = true; go;) {  // one pass = the run's levels inside one 64-label chunk of the string
+          bool on_boundary = false;  // the last level taken moved pos onto the next chunk
+          for (;;) {
+            const uint32_t label = rl(ch_cur.x, pos & 63u);
+            const float w1 = __uint_as_float(rl(ch_cur.z, pos & 63u));
+            PT_MARK(3)  // run: the last level's settle and counters, under the load
+            PT_ROWS_IN()
+            PT_MARK(4)  // run: waiting for the rows
+            // ---- on the chain: rows -> ballot -> the matched lane's fields -> the next rows
+            const uint64_t m = __ballot(a.x == label) & fcm;
+            if (m == 0ull || (m & (m - 1ull)) != 0ull) {  // the general level's: lanes < fc hold its rows
+              pf = true;
+              go = false;
+              break;
+            }
+            const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+            const uint32_t xb = rl(nx.x, l), xc = rl(nx.y, l);
+            const uint32_t ol = rl(a.y, l), w2u = rl(a.z, l);  // (a.w, the destination, is the general level's to name: it
+                                                               // ends every run and sets q from its own matches)
+            if (lane < xc && xc <= 64u) {  // (everything of the old rows is read off: the new ones land in their place)
+              a = ld_global16(f2.arcs + xb + lane);
+              nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (xb + lane));
+            }
+            PT_MARK(5)  // run: from the rows' arrival to the next rows' issue
+            // ---- under the load: state hi = (pos + 1, a.w) is settled as on_match settles the one new state of a level (F == 1:
+            // its only way in is from state hi - 1)
+            const float ws = wtimes(w1, __uint_as_float(w2u));  // add_tr, compose_fst_op.rs:267-285
+            float c = INF;
+            if (dd < INF) c = (dd + ws) + 0.0f;
+            const bool reached = c < INF;
+            if (lane == 0) {
+              s_ol[hi] = ol;
+              s_w[hi] = ws;
+              s_par[hi] = reached ? hi - 1u : STR_NONE;
+            }
+            dd = reached ? c : INF;
+            fb = xb;
+            fc = xc;
+            fcm = fc >= 64u ? ~0ull : (1ull << fc) - 1ull;
+            n_arcs += 1;
+            hi += 1;
+            pos += 1;
+            on_boundary = (pos & 63u) == 0u;
+            if (fc > 64u) {  // a longer block: the general level loads it chunk by chunk
+              go = false;
+              break;
+            }
+            if (!(pos + 1u < L_u && hi + 1u < maxs)) {  // the general level's, with these rows
+              pf = true;
+              go = false;
+              break;
+            }
+            if (on_boundary) break;
           }
-          const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
-          if (lane == l) {  // state hi = (pos + 1, a.w): its slots hold the arc until the settle
-            s_ol[hi] = a.y;
-            s_w[hi] = __uint_as_float(a.z);
-          }
-          qd = rl(a.w, l);
-          fb = rl(nx.x, l);
-          fc = rl(nx.y, l);
-          n_arcs += 1;
-          hi += 1;
-          pos += 1;
-          pf = false;
-          if ((pos & 63u) == 0u) {
+          if (on_boundary) {  // the next 64 labels of the string (the loop's head does this only where no run moved pos there)
             ch_cur = ch_nxt;
             ch_nxt = make_uint4(0, 0, 0, 0);
             if (pos + 64u + lane < L) ch_nxt = ld_global16(f1.arcs + pos + 64u + lane);
           }
-          if (fc > 64u) break;
-          a = make_uint4(0, 0, 0, 0);
-          nx = make_uint2(0, 0);
-          if (lane < fc) {
-            a = ld_global16(f2.arcs + fb + lane);
-            nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
-          }
-          if (!(pos + 1u < L_u && hi + 1u < maxs)) {  // the general level's, with these rows
-            pf_a = a;
-            pf_nx = nx;
-            pf = true;
-            break;
-          }
+        }
+        if (pf) {
+          pf_a = a;
+          pf_nx = nx;
         }
         const uint32_t n_run = pos - p0;
         if (n_run) {
-          PT_MARK(5)
-          // the settle.  State h0 + j entered level p0 + j + 1 over the arc parked in its slots, from state h0 + j - 1 (F == 1:
-          // lo == hi - 1 all along the run)
-          lds_handoff();
-          float dd = __uint_as_float(rl(__float_as_uint(d), 0));
-          for (uint32_t base = 0; base < n_run; base += 64u) {
-            const uint32_t j = base + lane;
-            float ws = INF;
-            if (j < n_run) {
-              const float w1 = __uint_as_float(ld_global16(f1.arcs + p0 + j).z);
-              ws = wtimes(w1, s_w[h0 + j]);  // add_tr, compose_fst_op.rs:267-285
-              s_w[h0 + j] = ws;
-            }
-            uint32_t par = STR_NONE;
-            const uint32_t cnt = n_run - base < 64u ? n_run - base : 64u;
-            for (uint32_t k = 0; k < cnt; ++k) {  // (a float sum is not associative: in level order, as on_match does it)
-              const float wk = __uint_as_float(rl(__float_as_uint(ws), k));
-              float c = INF;
-              if (dd < INF) c = (dd + wk) + 0.0f;
-              const bool reached = c < INF;
-              if (lane == k && reached) par = h0 + base + k - 1u;
-              dd = reached ? c : INF;
-            }
-            if (j < n_run) s_par[h0 + j] = par;
-          }
           if (lane == 0) {
-            q = qd;
             nb = fb;
             nc = fc;
             d = dd;
@@ -1205,8 +1205,8 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
           level = pos;
           res.run_levels += n_run;
           res.runs += 1u;
-          PT_MARK(3)  // run: the settle
         }
+        PT_MARK(3)
       }
     }
     const bool use_pf = pf;  // set by the last level: this level is one state, and lanes < min(its arc count, 64) hold its rows
@@ -1300,7 +1300,49 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
         }
       }
     }
-    for (uint32_t f = 0; f < F && ok && !took_scalar; ++f) {
+    // A narrow level: two to four frontier states, every block within one chunk.  The rows of all of them are asked for at
+    // once and taken in the loop's order, state by state and arc by arc: one trip to memory where the loop below pays one
+    // per state.
+    bool took_together = false;
+    if (!took_scalar && ok && F >= 2u && F <= 4u && __ballot(lane < F && nc > 64u) == 0ull) {
+      took_together = true;
+      PT_MARK(2)
+      uint4 ta[4];
+      uint2 tn[4];
+#pragma unroll
+      for (uint32_t f = 0; f < 4u; ++f) {
+        ta[f] = make_uint4(0, 0, 0, 0);
+        tn[f] = make_uint2(0, 0);
+        if (f < F) {
+          const uint32_t fb = rl(nb, f), fc = rl(nc, f);
+          if (lane < fc) {
+            ta[f] = ld_global16(f2.arcs + fb + lane);
+            tn[f] = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (fb + lane));
+          }
+        }
+      }
+      PT_MARK(2)
+      PT_ROWS_IN()
+      PT_MARK(0)
+#pragma unroll
+      for (uint32_t f = 0; f < 4u; ++f) {
+        if (f < F && ok) {
+          const uint32_t fc = rl(nc, f);
+          const float fd = __uint_as_float(rl(__float_as_uint(d), f));
+          uint64_t m = __ballot(lane < fc && ta[f].x == label);
+          n_arcs += (uint32_t)__popcll(m);
+          while (m) {
+            const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+            m &= m - 1;
+            if (!on_match(f, fd, rl(ta[f].w, l), rl(ta[f].y, l), rl(tn[f].x, l), rl(tn[f].y, l), __uint_as_float(rl(ta[f].z, l)))) {
+              ok = false;
+              break;
+            }
+          }
+        }
+      }
+    }
+    for (uint32_t f = 0; f < F && ok && !took_scalar && !took_together; ++f) {
       const uint32_t fb = rl(nb, f), fc = rl(nc, f);
       const float fd = __uint_as_float(rl(__float_as_uint(d), f));
       for (uint32_t base = 0; base < fc && ok; base += 64) {
@@ -1679,7 +1721,7 @@ void launch_end(wfst_ctx* ctx, BatchRun& run) {
       lv += h_res[i].n_levels;
       rlv += h_res[i].run_levels;
     }
-    std::fprintf(stderr, "[string phase ticks/problem] general: rows wait %llu | under the early load %llu | arrival->issue %llu || run: rows wait %llu | arrival->issue %llu | settle %llu || prologue %llu | epilogue %llu  (n=%zu, levels/problem %.1f, of them in runs %.1f)\n",
+    std::fprintf(stderr, "[string phase ticks/problem] general: rows wait %llu | under the early load %llu | arrival->issue %llu || run: rows wait %llu | arrival->issue %llu | under the load %llu || prologue %llu | epilogue %llu  (n=%zu, levels/problem %.1f, of them in runs %.1f)\n",
                  tot[0] / n, tot[1] / n, tot[2] / n, tot[4] / n, tot[5] / n, tot[3] / n, tot[6] / n, tot[7] / n, n, (double)lv / n, (double)rlv / n);
   }
   if (!run.string_kernel) {
