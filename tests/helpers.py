@@ -1,12 +1,16 @@
-"""Shared test helpers: seeded random FSTs, flat <-> oracle conversion, comparison."""
+"""Shared test helpers: seeded random FSTs, flat <-> oracle conversion, comparison, the library's last error."""
+import ctypes as C
+import os
+
 import numpy as np
 
 from rustfst_amd._lib import TR_DTYPE
-from rustfst_amd import synth
+from rustfst_amd import ComposeFilter, synth
+
+from oracle.model.props import NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED
 
 P = synth  # property bit names
-NOT_I_LABEL_SORTED = 0x0000_0000_2000_0000
-NOT_O_LABEL_SORTED = 0x0000_0000_8000_0000
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def random_fst_flat(rng, n_states, max_fanout, sigma, p_eps_i=0.0, p_eps_o=0.0, p_final=0.3, sort="ilabel",
@@ -146,3 +150,37 @@ def one_sided_eps_transducer(rng, n_states, max_fanout, sigma, eps_side, p_eps=0
                         p_eps_o=p_eps if eps_side == "olabel" else 0.0, p_final=p_final, sort=sort, min_fanout=1)
     assert np.any(f["arcs"][eps_side] == 0)
     return f
+
+
+def ko_message(status):
+    from rustfst_amd import _lib
+    assert status == 1
+    msg = C.c_char_p()
+    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
+    text = msg.value.decode()
+    _lib.lib().wfst_string_destroy(msg)
+    return text
+
+
+FILTERS = [ComposeFilter.NULLFILTER, ComposeFilter.TRIVIALFILTER, ComposeFilter.SEQUENCEFILTER,
+           ComposeFilter.ALTSEQUENCEFILTER, ComposeFilter.MATCHFILTER, ComposeFilter.NOMATCHFILTER]
+
+
+def flat_matches_spec(flat, spec):
+    assert flat["n_states"] == spec["n_states"]
+    assert flat["start"] == spec.get("start")
+    got = []
+    for s in range(flat["n_states"]):
+        for a in flat["arcs"][flat["offsets"][s]:flat["offsets"][s + 1]]:
+            got.append([s, int(a["ilabel"]), int(a["olabel"]), float(a["weight"]), int(a["nextstate"])])
+    exp = spec["arcs"]
+    assert len(got) == len(exp)
+    for g, e in zip(got, exp):
+        assert g[:3] == e[:3] and g[4] == e[4], (g, e)
+        assert abs(g[3] - e[3]) <= 1.0 / 1024.0, (g, e)
+    fin = {s: w for s, w in spec["finals"]}
+    for s in range(flat["n_states"]):
+        if s in fin:
+            assert abs(float(flat["finals"][s]) - fin[s]) <= 1.0 / 1024.0
+        else:
+            assert np.isinf(flat["finals"][s])

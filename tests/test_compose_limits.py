@@ -28,12 +28,10 @@ import pytest
 
 from rustfst_amd import synth
 
-import test_determinize as td
 import test_small_path_limits as sl
-from helpers import NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, assert_flat_identical, to_device, to_oracle
-from test_gpu_parity import FILTERS
+import helpers
+from helpers import FILTERS, NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, ROOT, assert_flat_identical, to_device, to_oracle
 
-ROOT = td.ROOT
 INF = float("inf")
 # ---- the kernels' own limits (rustfst_amd/csrc/compose.hip), restated once
 WAVE = 64               # :383 small = n_se <= 64; :396 items 64 at a time; :452 level_cnt + total > 64u; :780 / :1017 W = 64
@@ -628,7 +626,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
 def test_null_ctx_is_ko(wfst_lib):
     v = C.c_uint64(5)
     args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in td._ko_message(wfst_lib.wfst_ctx_get_compose_path_stats(None, *args))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_compose_path_stats(None, *args))
     assert v.value == 5
 
 

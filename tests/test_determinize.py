@@ -11,58 +11,18 @@ import re
 import numpy as np
 import pytest
 
-from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
 
-from helpers import assert_flat_identical, enumerate_paths, random_fst_flat, to_device, to_oracle
+from oracle.model import ACCEPTOR, F32, INF, KDELTA, approx_eq, determinize_props, plus, quantize, times
+from helpers import ROOT, assert_flat_identical, enumerate_paths, ko_message, random_fst_flat, to_device, to_oracle
+from inputs import diamond_chain, twin_copy
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-KDELTA = 1.0 / 1024.0
-INF = np.float32(np.inf)
-f32 = np.float32
 
-# fst_properties/properties.rs:22-103
-ACCEPTOR, I_DETERMINISTIC = 1 << 16, 1 << 18
-NO_EPSILONS, I_EPSILONS, NO_I_EPSILONS, O_EPSILONS, NO_O_EPSILONS = 1 << 23, 1 << 24, 1 << 25, 1 << 26, 1 << 27
-CYCLIC, ACYCLIC, INITIAL_ACYCLIC = 1 << 34, 1 << 35, 1 << 37
-ACCESSIBLE, COACCESSIBLE, STRING = 1 << 40, 1 << 42, 1 << 44
 PATHS = ("narrow", "wide", "auto")
 
 
 # ---------------------------------------------------------------- restatement (determinize_fsa_op.rs, state_table.rs)
-def determinize_props(p, distinct):  # mutate_properties.rs:247-279 with has_subsequential_label = false
-    out = ACCESSIBLE
-    if p & ACCEPTOR or (p & NO_I_EPSILONS and distinct):
-        out |= I_DETERMINISTIC
-    out |= (ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | COACCESSIBLE | STRING) & p
-    if p & NO_I_EPSILONS and distinct:
-        out |= NO_EPSILONS & p
-    if p & ACCESSIBLE:
-        out |= (I_EPSILONS | O_EPSILONS | CYCLIC) & p
-    if p & ACCEPTOR:
-        out |= (NO_I_EPSILONS | NO_O_EPSILONS) & p
-    return out
-
-
-def wplus(a, b):  # plus_assign: exact <
-    return b if b < a else a
-
-
-def wtimes(a, b):
-    return a if a == INF else (b if b == INF else f32(a + b))
-
-
-def quantize(v, delta):  # semiring.rs:132-145
-    if np.isinf(v):
-        return v
-    return f32(f32(np.floor(f32(f32(v / f32(delta)) + f32(0.5)))) * f32(delta))
-
-
-def approx_eq(a, b):  # |a - b| <= KDELTA, whatever delta is
-    return a <= f32(b + f32(KDELTA)) and b <= f32(a + f32(KDELTA))
-
-
 def determinize_ref(flat, delta=KDELTA, det_type=0, max_states=1 << 20):
     """DeterminizeFsa with DefaultCommonDivisor in LazyFst::compute's FIFO first-touch order; subsets in ascending state
     order; a candidate joins the lowest-id state with the same states and approx_eq weights."""
@@ -73,7 +33,7 @@ def determinize_ref(flat, delta=KDELTA, det_type=0, max_states=1 << 20):
         return dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
                     finals=np.zeros(0, np.float32), props=props)
     off, arcs, fin = flat["offsets"], flat["arcs"], flat["finals"]
-    tuples = [((int(flat["start"]), f32(0.0)),)]
+    tuples = [((int(flat["start"]), F32(0.0)),)]
     by_states = {(int(flat["start"]),): [0]}
     rows, finals, offsets = [], [], [0]
 
@@ -90,25 +50,25 @@ def determinize_ref(flat, delta=KDELTA, det_type=0, max_states=1 << 20):
 
     s = 0
     while s < len(tuples):
-        cand = [(int(a["ilabel"]), int(a["nextstate"]), wtimes(w, f32(a["weight"])))
+        cand = [(int(a["ilabel"]), int(a["nextstate"]), times(w, F32(a["weight"])))
                 for q, w in tuples[s] for a in arcs[off[q]:off[q + 1]]]
         cand.sort(key=lambda c: (c[0], c[1]))  # stable
         fw = INF
         for q, w in tuples[s]:
-            fw = wplus(fw, wtimes(w, f32(fin[q])))
+            fw = plus(fw, times(w, F32(fin[q])))
         i = 0
         while i < len(cand):
             j, weight = i, INF
             while j < len(cand) and cand[j][0] == cand[i][0]:
-                weight = wplus(weight, cand[j][2])
+                weight = plus(weight, cand[j][2])
                 j += 1
             merged = []
             for _, q, w in cand[i:j]:
                 if merged and merged[-1][0] == q:
-                    merged[-1][1] = wplus(merged[-1][1], w)
+                    merged[-1][1] = plus(merged[-1][1], w)
                 else:
                     merged.append([q, w])
-            t = tuple((q, quantize(f32(w - weight), delta)) for q, w in merged)
+            t = tuple((q, quantize(F32(w - weight), delta)) for q, w in merged)
             rows.append((cand[i][0], cand[i][0], weight, find(t)))
             i = j
         offsets.append(len(rows))
@@ -207,84 +167,6 @@ def collision_level(S=64, M=200, seed=7):
     return dict(n_states=S + 4, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
 
 
-def twin_copy(n, seed=3):
-    """D = make_transducer(n) with the first arc per (state, ilabel), olabel = ilabel; N on 2n states (every arc four
-    times, the copy +0.5), finals f(q) on both copies.  Returns (N, expected det(N)): D in FIFO first-touch order from
-    {(0, 0)}, the other states {(r, 0), (r + n, 0.5)}, D's weights and finals."""
-    t = synth.make_transducer(n, seed=seed)
-    off, arcs = t["offsets"].astype(np.int64), t["arcs"]
-    src = np.repeat(np.arange(n), np.diff(off))
-    keep = np.ones(len(arcs), bool)
-    keep[1:] = (src[1:] != src[:-1]) | (arcs["ilabel"][1:] != arcs["ilabel"][:-1])
-    src, da = src[keep], arcs[keep].copy()
-    da["olabel"] = da["ilabel"]
-    doff = np.zeros(n + 1, np.int64)
-    np.add.at(doff, src + 1, 1)
-    doff = np.cumsum(doff)
-    deg = np.diff(doff)
-    fin = t["finals"].astype(np.float32)
-    # N: state q (q < n) and q + n both carry, per kept arc (a, w, r): (a, w, r), (a, w + 0.5, r + n)
-    nd = 2 * deg
-    noff = np.concatenate([[0], np.cumsum(np.concatenate([nd, nd]))]).astype(np.uint32)
-    one = np.empty(2 * len(da), TR_DTYPE)
-    one["ilabel"] = np.repeat(da["ilabel"], 2)
-    one["olabel"] = one["ilabel"]
-    one["weight"] = np.repeat(da["weight"], 2)
-    one["weight"][1::2] = da["weight"] + np.float32(0.5)
-    one["nextstate"] = np.repeat(da["nextstate"], 2)
-    one["nextstate"][1::2] = da["nextstate"] + n
-    N = dict(n_states=2 * n, start=0, offsets=noff, arcs=np.concatenate([one, one]),
-             finals=np.concatenate([fin, fin]), props=ACCEPTOR)
-    # expected: BFS over D; id 0 = the start subset, D state r -> its own id the first time an arc reaches it
-    ids = np.full(n, -1, np.int64)
-    order = [0]  # D state of every result state (the start first)
-    frontier = np.array([0])
-    out_rows = []
-    next_id = 1
-    while len(frontier):
-        seg = [np.arange(doff[q], doff[q + 1]) for q in frontier]
-        idx = np.concatenate(seg) if seg else np.zeros(0, np.int64)
-        tgt = da["nextstate"][idx].astype(np.int64)
-        new = tgt[ids[tgt] < 0]
-        _, first = np.unique(new, return_index=True)
-        fresh = new[np.sort(first)]
-        ids[fresh] = next_id + np.arange(len(fresh))
-        next_id += len(fresh)
-        order += list(fresh)
-        out_rows.append((idx, ids[tgt]))
-        frontier = fresh
-    idx = np.concatenate([r[0] for r in out_rows])
-    dst = np.concatenate([r[1] for r in out_rows])
-    exp_arcs = np.empty(len(idx), TR_DTYPE)
-    exp_arcs["ilabel"] = da["ilabel"][idx]
-    exp_arcs["olabel"] = da["ilabel"][idx]
-    exp_arcs["weight"] = da["weight"][idx]
-    exp_arcs["nextstate"] = dst
-    order = np.array(order)
-    exp = dict(n_states=len(order), start=0,
-               offsets=np.concatenate([[0], np.cumsum(deg[order])]).astype(np.uint32), arcs=exp_arcs,
-               finals=fin[order], props=determinize_props(ACCEPTOR, True))
-    return N, exp
-
-
-def diamond_chain(levels, seed=11):
-    """start 0 -> {1, 2}; states 2k-1, 2k each with arcs (label 1) into 2k+1 and 2k+2; the last two states final"""
-    rng = np.random.default_rng(seed)
-    n = 2 * levels + 1
-    rows = [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)]]
-    for s in range(1, n):
-        if s < n - 2:
-            base = 2 * ((s + 1) // 2) + 1
-            rows.append([(1, 1, float(rng.integers(0, 4)), base), (1, 1, float(rng.integers(0, 4)), base + 1)])
-        else:
-            rows.append([])
-    arcs = np.array([x for r in rows for x in r], dtype=TR_DTYPE)
-    offsets = np.cumsum([0] + [len(r) for r in rows]).astype(np.uint32)
-    fin = np.full(n, np.inf, np.float32)
-    fin[n - 2:] = [0.0, 2.0]
-    return dict(n_states=n, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
-
-
 def same(got, exp, what, props=True):
     assert_flat_identical(got, exp, what, check_props=props)
 
@@ -302,26 +184,16 @@ def test_new_symbol_declared_and_bound(wfst_lib):
     assert _lib.DeterminizeConfig.delta.offset == 0 and _lib.DeterminizeConfig.det_type.offset == 4
 
 
-def _ko_message(status):
-    from rustfst_amd import _lib
-    assert status == 1
-    msg = C.c_char_p()
-    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
-    text = msg.value.decode()
-    _lib.lib().wfst_string_destroy(msg)
-    return text
-
-
 def test_argument_validation_without_gpu(wfst_lib):
     from rustfst_amd import _lib
     out = C.c_void_p()
-    assert "null" in _ko_message(wfst_lib.wfst_determinize(None, None, None, C.byref(out)))
-    assert "null" in _ko_message(wfst_lib.wfst_determinize(None, None, None, None))
+    assert "null" in ko_message(wfst_lib.wfst_determinize(None, None, None, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_determinize(None, None, None, None))
     bad = _lib.DeterminizeConfig(KDELTA, 3)
-    assert "det_type" in _ko_message(wfst_lib.wfst_determinize(None, None, C.byref(bad), C.byref(out)))
+    assert "det_type" in ko_message(wfst_lib.wfst_determinize(None, None, C.byref(bad), C.byref(out)))
     for d in (0.0, -1.0, float("nan"), float("inf")):
         cfg = _lib.DeterminizeConfig(d, 0)
-        assert "delta" in _ko_message(wfst_lib.wfst_determinize(None, None, C.byref(cfg), C.byref(out)))
+        assert "delta" in ko_message(wfst_lib.wfst_determinize(None, None, C.byref(cfg), C.byref(out)))
     assert out.value is None
 
 

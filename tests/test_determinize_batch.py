@@ -15,10 +15,13 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 
 import test_determinize as td
+from oracle import model
+import helpers
 from helpers import assert_flat_identical, random_fst_flat, to_device, to_oracle
+import inputs
 
-ROOT = td.ROOT
-KDELTA, INF, f32, ACCEPTOR = td.KDELTA, td.INF, td.f32, td.ACCEPTOR
+ROOT = helpers.ROOT
+KDELTA, INF, f32, ACCEPTOR = model.KDELTA, model.INF, model.F32, model.ACCEPTOR
 NARROW_STATES, NARROW_CANDS = 256, 8192  # include/wfst.h: the levels the batch kernel keeps
 SCRATCH = ("lds", "global")
 
@@ -30,7 +33,7 @@ def determinize_with_distance_ref(flat, in_dist=(), delta=KDELTA, max_states=1 <
     +inf) and, per breadth-first level, (states, raw candidates): (fst, out_dist, subsets, levels)."""
     if not flat["props"] & ACCEPTOR:
         raise ValueError("transducers are not supported")
-    props = td.determinize_props(flat["props"], True)
+    props = model.determinize_props(flat["props"], True)
     if flat["start"] is None or flat["n_states"] == 0:
         return (dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
                      finals=np.zeros(0, np.float32), props=props), np.zeros(0, np.float32), [], [])
@@ -43,7 +46,7 @@ def determinize_with_distance_ref(flat, in_dist=(), delta=KDELTA, max_states=1 <
     def find(t):
         ids = by_states.setdefault(tuple(s for s, _ in t), [])
         for i in ids:
-            if all(td.approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[i])):
+            if all(model.approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[i])):
                 return i
         ids.append(len(tuples))
         tuples.append(t)
@@ -55,27 +58,27 @@ def determinize_with_distance_ref(flat, in_dist=(), delta=KDELTA, max_states=1 <
     s, level_end = 0, 1
     n_level, k_level = 0, 0
     while s < len(tuples):
-        cand = [(int(a["ilabel"]), int(a["nextstate"]), td.wtimes(w, f32(a["weight"])))
+        cand = [(int(a["ilabel"]), int(a["nextstate"]), model.times(w, f32(a["weight"])))
                 for q, w in tuples[s] for a in arcs[off[q]:off[q + 1]]]
         n_level += 1
         k_level += len(cand)
         cand.sort(key=lambda c: (c[0], c[1]))  # stable
         fw = INF
         for q, w in tuples[s]:
-            fw = td.wplus(fw, td.wtimes(w, f32(fin[q])))
+            fw = model.plus(fw, model.times(w, f32(fin[q])))
         i = 0
         while i < len(cand):
             j, weight = i, INF
             while j < len(cand) and cand[j][0] == cand[i][0]:
-                weight = td.wplus(weight, cand[j][2])
+                weight = model.plus(weight, cand[j][2])
                 j += 1
             merged = []
             for _, q, w in cand[i:j]:
                 if merged and merged[-1][0] == q:
-                    merged[-1][1] = td.wplus(merged[-1][1], w)
+                    merged[-1][1] = model.plus(merged[-1][1], w)
                 else:
                     merged.append([q, w])
-            t = tuple((q, td.quantize(f32(w - weight), delta)) for q, w in merged)
+            t = tuple((q, model.quantize(f32(w - weight), delta)) for q, w in merged)
             rows.append((cand[i][0], cand[i][0], weight, find(t)))
             i = j
         offsets.append(len(rows))
@@ -91,7 +94,7 @@ def determinize_with_distance_ref(flat, in_dist=(), delta=KDELTA, max_states=1 <
     for k, t in enumerate(tuples):
         d = INF
         for q, w in t:
-            d = td.wplus(d, td.wtimes(w, f32(in_dist[q]) if q < len(in_dist) else INF))
+            d = model.plus(d, model.times(w, f32(in_dist[q]) if q < len(in_dist) else INF))
         out_dist[k] = d
     fst = dict(n_states=len(tuples), start=0, offsets=np.array(offsets, np.uint32), arcs=a,
                finals=np.array(finals, np.float32), props=props)
@@ -166,7 +169,7 @@ def test_new_symbols_declared_exported_and_bound(wfst_lib):
 
 def test_argument_validation_without_gpu(wfst_lib):
     from rustfst_amd import _lib
-    ko = td._ko_message
+    ko = helpers.ko_message
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
     assert wfst_lib.wfst_determinize_batch(None, None, 0, None, None, None) == 0  # n == 0: OK
@@ -307,7 +310,7 @@ def test_parity_with_oracle_and_single_call(gpu_ctx, oracle, monkeypatch, scratc
         assert st["items_in_kernel"] == len(items) and st["items_single"] == 0 and st["launches"] >= 1
         for (name, flat, weigh_props), g, dev in zip(items, got, devs):
             exp = to_oracle(oracle, flat).determinize_fsa(delta).to_flat()
-            exp["props"] = td.determinize_props(flat["props"], det_type != 1)
+            exp["props"] = model.determinize_props(flat["props"], det_type != 1)
             same(g, exp, f"{name} {scratch} vs oracle")
             same(g, dev.determinize(_cfg(delta, det_type)).to_flat(), f"{name} {scratch} vs single")
 
@@ -330,7 +333,7 @@ def test_items_on_the_kernel_limits(gpu_ctx, oracle, monkeypatch, scratch):
     assert st["items_single"] == 2 and st["items_in_kernel"] == 5
     for name, flat, g, dev in zip(names, flats, got, devs):
         exp = to_oracle(oracle, flat).determinize_fsa(KDELTA).to_flat()
-        exp["props"] = td.determinize_props(flat["props"], True)
+        exp["props"] = model.determinize_props(flat["props"], True)
         same(g, exp, f"{name} {scratch} vs oracle")
         same(g, dev.determinize().to_flat(), f"{name} {scratch} vs single")
     # the LDS items alone, in the other order: no item leaves the kernel
@@ -347,7 +350,7 @@ def test_mixed_batch(gpu_ctx, monkeypatch, scratch):
     monkeypatch.setenv("WFST_DETERMINIZE_BATCH_SCRATCH", scratch)
     rng = np.random.default_rng(8)
     tiny = td.random_acceptor(rng, 6, 3, 2, acyclic=True)
-    flats = [tiny, empty_flat(), no_start(), collision_flat(), tiny, td.diamond_chain(2000), cyclic_unweighted()]
+    flats = [tiny, empty_flat(), no_start(), collision_flat(), tiny, inputs.diamond_chain(2000), cyclic_unweighted()]
     devs = [to_device(f, gpu_ctx) for f in flats]
     devs[4] = devs[0]  # the same handle twice
     got, flags = _batch(devs, gpu_ctx)
@@ -475,7 +478,7 @@ def test_ko_leaves_nothing_behind(gpu_ctx, monkeypatch):
     n = len(mixed)
     arr = (C.c_void_p * n)(*[d._h.value for d in mixed])
     outs = (C.c_void_p * n)(*([1] * n))
-    msg = td._ko_message(_lib.lib().wfst_determinize_batch(gpu_ctx._h, arr, n, None, outs, None))
+    msg = helpers.ko_message(_lib.lib().wfst_determinize_batch(gpu_ctx._h, arr, n, None, outs, None))
     assert "item 2" in msg and "transducers are not supported" in msg
     assert [outs[i] for i in range(n)] == [None] * n
     assert rustfst_amd.determinize_batch_stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)
@@ -489,7 +492,7 @@ def test_ko_leaves_nothing_behind(gpu_ctx, monkeypatch):
 
     def ko():
         outs = (C.c_void_p * n)(*([1] * n))
-        msg = td._ko_message(_lib.lib().wfst_determinize_batch(gpu_ctx._h, arr, n, None, outs, None))
+        msg = helpers.ko_message(_lib.lib().wfst_determinize_batch(gpu_ctx._h, arr, n, None, outs, None))
         assert "item 3" in msg and "more than" in msg
         assert [outs[i] for i in range(n)] == [None] * n
 

@@ -42,10 +42,13 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 
 import test_determinize as td
+from oracle import model
+from oracle.model import ACCEPTOR, F32, INF, KDELTA
+import helpers
 from helpers import assert_flat_identical, to_device, to_oracle
+import inputs
 
-ROOT = td.ROOT
-KDELTA, INF, f32, ACCEPTOR = td.KDELTA, td.INF, td.f32, td.ACCEPTOR
+ROOT = helpers.ROOT
 PATHS = ("auto", "narrow", "wide")
 NARROW_STATES, NARROW_CANDS, BUDGET = 256, 8192, 1 << 16  # determinize.hip
 FIRST_RESERVE = (1024, 4096, 4096, 4096)  # states, elements, arcs, candidates of one level
@@ -66,7 +69,7 @@ def det_levels(flat, delta=KDELTA, reverse_ties=False):
     reverse_ties: candidates of equal (label, dest) in reverse arrival order (what a sort that is not stable may do)."""
     assert flat["props"] & ACCEPTOR and flat["start"] is not None
     off, arcs, fin = flat["offsets"], flat["arcs"], flat["finals"]
-    tuples = [((int(flat["start"]), f32(0.0)),)]
+    tuples = [((int(flat["start"]), F32(0.0)),)]
     by_states = {(int(flat["start"]),): [0]}
     level_of = [0]
     rows, finals, offsets = [], [], [0]
@@ -75,7 +78,7 @@ def det_levels(flat, delta=KDELTA, reverse_ties=False):
     n_raw = n_valid = 0
     found = set()
     while s < len(tuples):
-        cand = [(int(a["ilabel"]), int(a["nextstate"]), td.wtimes(w, f32(a["weight"])))
+        cand = [(int(a["ilabel"]), int(a["nextstate"]), model.times(w, F32(a["weight"])))
                 for q, w in tuples[s] for a in arcs[off[q]:off[q + 1]]]
         assert not any(c[2] == 0 and np.signbit(c[2]) for c in cand), "a raw candidate of weight -0.0"
         n_raw += len(cand)
@@ -84,22 +87,22 @@ def det_levels(flat, delta=KDELTA, reverse_ties=False):
         cand.sort(key=lambda c: (c[0], c[1]))  # stable
         fw = INF
         for q, w in tuples[s]:
-            fw = td.wplus(fw, td.wtimes(w, f32(fin[q])))
+            fw = model.plus(fw, model.times(w, F32(fin[q])))
         i = 0
         while i < len(cand):
             j, weight = i, INF
             while j < len(cand) and cand[j][0] == cand[i][0]:
-                weight = td.wplus(weight, cand[j][2])
+                weight = model.plus(weight, cand[j][2])
                 j += 1
             merged = []
             for _, q, w in cand[i:j]:
                 if merged and merged[-1][0] == q:
-                    merged[-1][1] = td.wplus(merged[-1][1], w)
+                    merged[-1][1] = model.plus(merged[-1][1], w)
                 else:
                     merged.append([q, w])
-            t = tuple((q, td.quantize(f32(w - weight), delta)) for q, w in merged)
+            t = tuple((q, model.quantize(F32(w - weight), delta)) for q, w in merged)
             ids = by_states.setdefault(tuple(q for q, _ in t), [])
-            dest = next((k for k in ids if all(td.approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[k]))), None)
+            dest = next((k for k in ids if all(model.approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[k]))), None)
             if dest is None:
                 dest = len(tuples)
                 ids.append(dest)
@@ -123,7 +126,7 @@ def det_levels(flat, delta=KDELTA, reverse_ties=False):
     for k, r in enumerate(rows):
         a[k] = r
     fst = dict(n_states=len(tuples), start=0, offsets=np.array(offsets, np.uint32), arcs=a,
-               finals=np.array(finals, np.float32), props=td.determinize_props(flat["props"], True))
+               finals=np.array(finals, np.float32), props=model.determinize_props(flat["props"], True))
     return dict(fst=fst, tuples=tuples, level_of=level_of, figs=figs, reach=reach)
 
 
@@ -440,7 +443,7 @@ LAYERED = {
 }
 # name -> builder of a flat whose figures come from det_levels
 OTHER = {
-    "diamond_300": lambda: td.diamond_chain(300),
+    "diamond_300": lambda: inputs.diamond_chain(300),
     "lowest_id_levels": lambda: lowest_id_chain(False),
     "lowest_id_same_level": lambda: lowest_id_chain(True),
     "chain_across_growth": chain_across_growth,
@@ -497,7 +500,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
 def test_null_ctx_is_ko(wfst_lib):
     v = C.c_uint64(5)
     args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in td._ko_message(wfst_lib.wfst_ctx_get_determinize_stats(None, *args))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_determinize_stats(None, *args))
     assert v.value == 5
 
 
@@ -657,9 +660,9 @@ def test_lowest_id_inputs_match_two_older_states():
         res = [int(round(float(an["tuples"][k][1][1]) / KDELTA)) for k in ab]
         assert res == [3, 5] and ab[0] < ab[1], name  # no state for the 4 KDELTA candidate
         older, newer = an["tuples"][ab[0]], an["tuples"][ab[1]]
-        mid = ((4, f32(0.0)), (5, f32(4 * KDELTA)))
+        mid = ((4, F32(0.0)), (5, F32(4 * KDELTA)))
         for t in (older, newer):
-            assert all(td.approx_eq(w, v) for (_, w), (_, v) in zip(mid, t))
+            assert all(model.approx_eq(w, v) for (_, w), (_, v) in zip(mid, t))
         arcs = an["fst"]["arcs"]
         assert int((arcs["nextstate"] == ab[0]).sum()) == 2 and int((arcs["nextstate"] == ab[1]).sum()) == 1, name
         levels = [an["level_of"][k] for k in ab]
@@ -694,9 +697,9 @@ def test_sort_ties_cannot_be_observed():
         flat = case(name)[0]
         same(det_levels(flat, reverse_ties=True)["fst"], analysis(name)["fst"], name)
     # the one way to -0.0: both terms -0.0, and quantize never returns it
-    assert np.signbit(f32(-0.0) + f32(-0.0)) and not np.signbit(f32(0.0) + f32(-0.0))
-    for v in (f32(0.0), f32(-0.0), f32(KDELTA / 4), f32(3 * KDELTA)):
-        q = td.quantize(v, KDELTA)
+    assert np.signbit(F32(-0.0) + F32(-0.0)) and not np.signbit(F32(0.0) + F32(-0.0))
+    for v in (F32(0.0), F32(-0.0), F32(KDELTA / 4), F32(3 * KDELTA)):
+        q = model.quantize(v, KDELTA)
         assert not (q == 0 and np.signbit(q))
 
 
@@ -704,7 +707,7 @@ def test_restatement_matches_the_oracle(oracle):
     for name in SMALL:
         flat = case(name)[0]
         exp = to_oracle(oracle, flat).determinize_fsa(KDELTA).to_flat()
-        exp["props"] = td.determinize_props(flat["props"], True)
+        exp["props"] = model.determinize_props(flat["props"], True)
         same(analysis(name)["fst"], exp, name)
 
 
@@ -713,7 +716,7 @@ def test_restatement_matches_the_oracle(oracle):
 def _expected(oracle, name):
     flat = case(name)[0]
     exp = to_oracle(oracle, flat).determinize_fsa(KDELTA).to_flat()
-    exp["props"] = td.determinize_props(flat["props"], True)
+    exp["props"] = model.determinize_props(flat["props"], True)
     return exp
 
 

@@ -15,7 +15,7 @@ import pytest
 
 import rustfst_amd
 from rustfst_amd import ComposeConfig, ComposeFilter, ShortestPathConfig, Tr, VectorFst, synth
-from helpers import assert_flat_identical, random_fst_flat, to_device, to_oracle
+from helpers import FILTERS, assert_flat_identical, flat_matches_spec, random_fst_flat, to_device, to_oracle
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -1262,7 +1262,6 @@ def test_k13_nshortest_hand_traced_known_answers(gpu_ctx):
     reference's heap resolves it — through the single call (host search) and through the batch call (wave kernel)."""
     g = golden("k13_nshortest_k2.json")
     d = vbuild(g["fst"]).to_device()
-    from test_oracle import flat_matches_spec
     for n, key in ((2, "n2"), (3, "n3")):
         flat_matches_spec(d.shortest_path(ShortestPathConfig(nshortest=n)).to_flat(), g[key])
         both = rustfst_amd.shortest_path_batch([d, d], ShortestPathConfig(nshortest=n))
@@ -1774,11 +1773,6 @@ def test_async_shortest_path_small_and_degenerate(gpu_ctx, oracle, seed):
     assert out.num_states == 0
 
 
-# ------------------------------------------------------------------ §8(f) N4: the other ComposeFilterEnum values
-FILTERS = [ComposeFilter.NULLFILTER, ComposeFilter.TRIVIALFILTER, ComposeFilter.SEQUENCEFILTER,
-           ComposeFilter.ALTSEQUENCEFILTER, ComposeFilter.MATCHFILTER, ComposeFilter.NOMATCHFILTER]
-
-
 @pytest.mark.parametrize("flt", FILTERS, ids=lambda f: f.name)
 @pytest.mark.parametrize("seed", range(6))
 def test_compose_filters_match_oracle(gpu_ctx, oracle, flt, seed):
@@ -2268,7 +2262,6 @@ def test_k13_lookahead_hand_traced_known_answers(gpu_ctx, monkeypatch, path):
     (tests/golden/K13_DERIVATION.md section 2, tests/golden/k13_lookahead.json): the relabelled second operand, the pruned
     dead end, pushed weights and labels, state numbering and arc order — on the single-wave kernel and on the wide driver,
     and through the batch entry point."""
-    from test_oracle import flat_matches_spec
     monkeypatch.setenv("WFST_LOOKAHEAD_PATH", path)
     g = golden("k13_lookahead.json")
     for case in g["cases"]:

@@ -24,12 +24,13 @@ import pytest
 import rustfst_amd
 from rustfst_amd import (ClosureType, ComposeConfig, DeviceFst, ProjectType, PushWeightsConfig, ReweightType,
                          ShortestPathConfig, synth)
+from oracle import model
 from helpers import (assert_flat_identical, linear_transducer_flat, one_sided_eps_transducer, random_fst_flat, to_device,
                      to_oracle, walk_labels)
 import test_push_weights as pw
 
-ACCEPTOR = 0x0000_0000_0001_0000
-NOT_I_SORTED, NOT_O_SORTED = 0x0000_0000_2000_0000, 0x0000_0000_8000_0000
+ACCEPTOR = model.ACCEPTOR
+NOT_I_SORTED, NOT_O_SORTED = model.NOT_I_LABEL_SORTED, model.NOT_O_LABEL_SORTED
 SIGMA = 5
 
 # ------------------------------------------------------------------ edits
@@ -183,7 +184,7 @@ def ora_O4(m, inp):  # the restatement of tests/test_push_weights.py on the orac
     out = []
     for rt, rm in PUSHES:
         to_final = rt == ReweightType.REWEIGHT_TO_FINAL
-        out.append(pw.to_flat(pw.push_ref(m.flat, pw._oracle_dist(m.oracle, m.flat, to_final), to_final, rm)))
+        out.append(model.to_flat(pw.push_ref(m.flat, pw._oracle_dist(m.oracle, m.flat, to_final), to_final, rm)))
     return out
 
 
@@ -837,7 +838,7 @@ def test_negative_weights_beyond_the_one_wave_sizes_born_by_upload_many(gpu_ctx,
     a, b = to_device(f, gpu_ctx), DeviceFst.upload_many([synth.linear_acceptor_flat([1, 2]), f], gpu_ctx)[1]
     want = a.shortest_path().to_flat()
     ref = to_oracle(oracle, f).shortest_path()
-    assert want["n_states"] > 1 and abs(float(pw.F32(0) + sum(want["arcs"]["weight"][::-1].astype(np.float64)) + want["finals"][0]) - ref.total_weight) <= 1e-3
+    assert want["n_states"] > 1 and abs(float(model.F32(0) + sum(want["arcs"]["weight"][::-1].astype(np.float64)) + want["finals"][0]) - ref.total_weight) <= 1e-3
     for q in range(3):
         assert_flat_identical(b.shortest_path().to_flat(), want, f"upload_many, query {q}")
     np.testing.assert_array_equal(b.shortest_distance().view(np.uint32), a.shortest_distance().view(np.uint32))

@@ -20,259 +20,24 @@ import pytest
 
 from rustfst_amd._lib import TR_DTYPE
 
-from helpers import assert_flat_identical, to_device
+from oracle import model
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ADD_SUPER_FINAL, ALL, ARCSORT, ARC_RELEVANT, COACCESSIBLE,
+                          CYCLIC, EPSILONS, F32, INF, INITIAL_ACYCLIC, I_DETERMINISTIC, I_EPSILONS, I_LABEL_INVARIANT,
+                          I_LABEL_SORTED, KSHORTESTDELTA, NOT_ACCEPTOR, NOT_I_DETERMINISTIC, NOT_I_LABEL_SORTED,
+                          NOT_O_LABEL_SORTED, NOT_TOP_SORTED, NO_EPSILONS, NO_I_EPSILONS, NO_O_EPSILONS,
+                          O_DETERMINISTIC, O_EPSILONS, O_LABEL_INVARIANT, O_LABEL_SORTED, RM_SUPER_FINAL, TOP_SORTED,
+                          UNWEIGHTED, Unsupported, WEIGHTED, WEIGHT_INVARIANT, compute_and_update, connect, flat_to_fst,
+                          fst_to_flat, is_cyclic, known, make_flat, p_add_tr, quantize, rm_final_epsilon, tr_map,
+                          tr_unique, wkey)
+from helpers import ROOT, assert_flat_identical, ko_message, to_device
 import test_push_weights as pw
-from test_push_weights import (ACCEPTOR, NOT_ACCEPTOR, I_DETERMINISTIC, NOT_I_DETERMINISTIC, O_DETERMINISTIC,  # noqa: F401
-                               EPSILONS, NO_EPSILONS, I_EPSILONS, NO_I_EPSILONS, O_EPSILONS, NO_O_EPSILONS,
-                               I_LABEL_SORTED, NOT_I_LABEL_SORTED, O_LABEL_SORTED, NOT_O_LABEL_SORTED, WEIGHTED, UNWEIGHTED,
-                               CYCLIC, ACYCLIC, INITIAL_CYCLIC, INITIAL_ACYCLIC, TOP_SORTED, NOT_TOP_SORTED, ACCESSIBLE,
-                               NOT_ACCESSIBLE, COACCESSIBLE, NOT_COACCESSIBLE, STRING, NOT_STRING, WEIGHTED_CYCLES,
-                               UNWEIGHTED_CYCLES, ALL, ARC_RELEVANT, WEIGHT_INVARIANT, _m)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k16_minimize.json")
-F32, INF = np.float32, np.float32(np.inf)
-KSHORTESTDELTA = 1e-6
 PATHS = ("narrow", "wide", "auto")
 MSG_NONDET = "Refusing to minimize a non-deterministic FST with allow_nondet = false"
 
-# properties.rs:283-316, 351-381, 383-432, 469-517
-DELETE_STATES = _m("ACCEPTOR", "I_DETERMINISTIC", "O_DETERMINISTIC", "NO_EPSILONS", "NO_I_EPSILONS", "NO_O_EPSILONS",
-                   "I_LABEL_SORTED", "O_LABEL_SORTED", "UNWEIGHTED", "ACYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
-                   "UNWEIGHTED_CYCLES")
-DELETE_ARCS = DELETE_STATES | NOT_ACCESSIBLE | NOT_COACCESSIBLE
-ARCSORT = ALL & ~(I_LABEL_SORTED | NOT_I_LABEL_SORTED | O_LABEL_SORTED | NOT_O_LABEL_SORTED)
-_COMMON_INV = _m("WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
-                 "NOT_TOP_SORTED", "ACCESSIBLE", "NOT_ACCESSIBLE", "COACCESSIBLE", "NOT_COACCESSIBLE", "STRING", "NOT_STRING",
-                 "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-I_LABEL_INVARIANT = _COMMON_INV | _m("O_DETERMINISTIC", "NOT_O_DETERMINISTIC", "O_EPSILONS", "NO_O_EPSILONS",
-                                     "O_LABEL_SORTED", "NOT_O_LABEL_SORTED")
-O_LABEL_INVARIANT = _COMMON_INV | _m("I_DETERMINISTIC", "NOT_I_DETERMINISTIC", "I_EPSILONS", "NO_I_EPSILONS",
-                                     "I_LABEL_SORTED", "NOT_I_LABEL_SORTED")
-ADD_SUPER_FINAL = _m("NOT_ACCEPTOR", "NOT_I_DETERMINISTIC", "NOT_O_DETERMINISTIC", "EPSILONS", "I_EPSILONS", "O_EPSILONS",
-                     "NOT_I_LABEL_SORTED", "NOT_O_LABEL_SORTED", "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC",
-                     "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "NOT_TOP_SORTED", "NOT_ACCESSIBLE", "COACCESSIBLE",
-                     "NOT_COACCESSIBLE", "NOT_STRING", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-RM_SUPER_FINAL = _m("ACCEPTOR", "NOT_ACCEPTOR", "I_DETERMINISTIC", "O_DETERMINISTIC", "NO_EPSILONS", "NO_I_EPSILONS",
-                    "NO_O_EPSILONS", "I_LABEL_SORTED", "O_LABEL_SORTED", "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC",
-                    "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED", "ACCESSIBLE", "COACCESSIBLE", "NOT_COACCESSIBLE",
-                    "STRING", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-NULL_PROPS = _m("ACCEPTOR", "I_DETERMINISTIC", "O_DETERMINISTIC", "NO_EPSILONS", "NO_I_EPSILONS", "NO_O_EPSILONS",
-                "I_LABEL_SORTED", "O_LABEL_SORTED", "UNWEIGHTED", "ACYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED", "ACCESSIBLE",
-                "COACCESSIBLE", "STRING", "UNWEIGHTED_CYCLES")
-POS, NEG = 0x5555555555555555 & ALL, 0xAAAAAAAAAAAAAAAA & ALL
-
-
-class Unsupported(Exception):
-    """what the device answers with KO (the message in args[0])"""
-
 
 # ---------------------------------------------------------------- the restatement
-def known(p):  # fst_properties/utils.rs:4-9 (without the binary bits: the words here carry none)
-    return (p & ALL) | ((p & POS) << 1) | ((p & NEG) >> 1)
-
-
-def quantize(v, delta):  # semiring.rs:132-145
-    if np.isinf(v):
-        return F32(v)
-    return F32(F32(np.floor(F32(F32(F32(v) / F32(delta)) + F32(0.5)))) * F32(delta))
-
-
-def wkey(w):  # exact tuple identity: the value, -0.0 == +0.0
-    w = F32(w)
-    return 0 if w == 0 else int(w.view(np.uint32))
-
-
-def p_add_tr(p, state, tr, prev):  # mutate_properties.rs:43-100
-    il, ol, w, ns = tr
-    if il != ol:
-        p = (p | NOT_ACCEPTOR) & ~ACCEPTOR
-    if il == 0:
-        p = (p | I_EPSILONS) & ~NO_I_EPSILONS
-        if ol == 0:
-            p = (p | EPSILONS) & ~NO_EPSILONS
-    if ol == 0:
-        p = (p | O_EPSILONS) & ~NO_O_EPSILONS
-    if prev is not None:
-        if prev[0] > il:
-            p = (p | NOT_I_LABEL_SORTED) & ~I_LABEL_SORTED
-        if prev[1] > ol:
-            p = (p | NOT_O_LABEL_SORTED) & ~O_LABEL_SORTED
-    if pw.weighted(w):
-        p = (p | WEIGHTED) & ~UNWEIGHTED
-    if ns <= state:
-        p = (p | NOT_TOP_SORTED) & ~TOP_SORTED
-    p &= pw.ADD_ARC_MASK | ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | \
-        UNWEIGHTED | TOP_SORTED
-    if p & TOP_SORTED:
-        p |= ACYCLIC | INITIAL_ACYCLIC
-    return p
-
-
-def fst_to_flat(fst):
-    rows = fst["rows"]
-    n = len(rows)
-    off = np.zeros(n + 1, dtype=np.uint32)
-    if n:
-        off[1:] = np.cumsum([len(r) for r in rows])
-    arcs = np.array([tuple(a) for r in rows for a in r], dtype=TR_DTYPE) if off[-1] else np.zeros(0, dtype=TR_DTYPE)
-    finals = np.array([INF if f is None else f for f in fst["finals"]], dtype=np.float32)
-    return dict(n_states=n, start=fst["start"], offsets=off, arcs=arcs, finals=finals, props=fst["props"] & ALL)
-
-
-def flat_to_fst(flat):
-    off, arcs = flat["offsets"], flat["arcs"]
-    rows = [[[int(a["ilabel"]), int(a["olabel"]), F32(a["weight"]), int(a["nextstate"])] for a in arcs[off[s]:off[s + 1]]]
-            for s in range(flat["n_states"])]
-    finals = [None if not np.isfinite(f) else F32(f) for f in flat["finals"]]
-    return dict(rows=rows, finals=finals, start=flat["start"], props=int(flat["props"]) & ALL)
-
-
-def dfs_facts(fst):
-    """(accessible, coaccessible, cyclic, initial_cyclic) as the SccVisitor finds them (every state is visited)"""
-    n = len(fst["rows"])
-    if n == 0:
-        return True, True, False, False
-    flat = fst_to_flat(fst)
-    if flat["start"] is None:
-        flat = dict(flat, start=0)
-        a, c, cy, ic = pw.graph_facts(flat)
-        return False, c, cy, False
-    return pw.graph_facts(flat)
-
-
-def compute_and_update(fst, mask):
-    """compute_and_update_properties(mask) (mutable_fst.rs:435-441, compute_fst_properties.rs:13-207); returns the word & mask"""
-    p = fst["props"]
-    if known(p) & mask == mask:  # use_stored
-        return p & mask
-    comp = 0
-    dfs = pw.DFS_BITS
-    want_dfs = bool(mask & (dfs | WEIGHTED_CYCLES | UNWEIGHTED_CYCLES))
-    if want_dfs:
-        comp |= pw.dfs_bits(dfs_facts(fst))
-    if mask & ~dfs:
-        comp |= ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | UNWEIGHTED | \
-            TOP_SORTED | STRING
-        want_idet = bool(mask & (I_DETERMINISTIC | NOT_I_DETERMINISTIC))
-        want_odet = bool(mask & (O_DETERMINISTIC | (O_DETERMINISTIC << 1)))
-        if want_idet:
-            comp |= I_DETERMINISTIC
-        if want_odet:
-            comp |= O_DETERMINISTIC
-        if want_dfs:
-            comp |= UNWEIGHTED_CYCLES
-        nfinal = 0
-        for s, row in enumerate(fst["rows"]):
-            ils, ols, prev = set(), set(), None
-            for il, ol, w, ns in row:
-                if want_idet and il in ils:
-                    comp = (comp | NOT_I_DETERMINISTIC) & ~I_DETERMINISTIC
-                if want_odet and ol in ols:
-                    comp = (comp | (O_DETERMINISTIC << 1)) & ~O_DETERMINISTIC
-                if il != ol:
-                    comp = (comp | NOT_ACCEPTOR) & ~ACCEPTOR
-                if il == 0 and ol == 0:
-                    comp = (comp | EPSILONS) & ~NO_EPSILONS
-                if il == 0:
-                    comp = (comp | I_EPSILONS) & ~NO_I_EPSILONS
-                if ol == 0:
-                    comp = (comp | O_EPSILONS) & ~NO_O_EPSILONS
-                if prev is not None:
-                    if il < prev[0]:
-                        comp = (comp | NOT_I_LABEL_SORTED) & ~I_LABEL_SORTED
-                    if ol < prev[1]:
-                        comp = (comp | NOT_O_LABEL_SORTED) & ~O_LABEL_SORTED
-                if not pw.is_one(w) and not pw.is_zero(w):
-                    comp = (comp | WEIGHTED) & ~UNWEIGHTED
-                    if comp & CYCLIC and comp & UNWEIGHTED_CYCLES:
-                        raise Unsupported("cyclic inputs are not supported")  # (the SCC test is not restated)
-                if ns <= s:
-                    comp = (comp | NOT_TOP_SORTED) & ~TOP_SORTED
-                if ns != s + 1:
-                    comp = (comp | NOT_STRING) & ~STRING
-                prev = (il, ol)
-                ils.add(il)
-                ols.add(ol)
-            if nfinal > 0:
-                comp = (comp | NOT_STRING) & ~STRING
-            if fst["finals"][s] is not None:
-                if not pw.is_one(fst["finals"][s]):
-                    comp = (comp | WEIGHTED) & ~UNWEIGHTED
-                nfinal += 1
-            elif len(row) != 1:
-                comp = (comp | NOT_STRING) & ~STRING
-        if fst["start"] is not None and fst["start"] != 0:
-            comp = (comp | NOT_STRING) & ~STRING
-    k = known(comp)
-    fst["props"] = (p & ~k) | (comp & k)
-    return comp & mask
-
-
-def connect(fst):  # connect.rs:51-66, del_states (vector_fst/mutable_fst.rs:132-189)
-    rows, finals = fst["rows"], fst["finals"]
-    n = len(rows)
-    access, co = [False] * n, [False] * n
-    if fst["start"] is not None:
-        stack = [fst["start"]]
-        access[fst["start"]] = True
-        while stack:
-            s = stack.pop()
-            for tr in rows[s]:
-                if not access[tr[3]]:
-                    access[tr[3]] = True
-                    stack.append(tr[3])
-    pred = [[] for _ in range(n)]
-    for s, row in enumerate(rows):
-        for tr in row:
-            pred[tr[3]].append(s)
-    stack = [s for s in range(n) if finals[s] is not None]
-    for s in stack:
-        co[s] = True
-    while stack:
-        s = stack.pop()
-        for q in pred[s]:
-            if not co[q]:
-                co[q] = True
-                stack.append(q)
-    new_id, k = [-1] * n, 0
-    for s in range(n):
-        if access[s] and co[s]:
-            new_id[s] = k
-            k += 1
-    fst["rows"] = [[[il, ol, w, new_id[ns]] for il, ol, w, ns in rows[s] if new_id[ns] != -1] for s in range(n) if new_id[s] != -1]
-    fst["finals"] = [finals[s] for s in range(n) if new_id[s] != -1]
-    if fst["start"] is not None:
-        fst["start"] = new_id[fst["start"]] if new_id[fst["start"]] != -1 else None
-    fst["props"] = (fst["props"] & DELETE_STATES & ~(ACCESSIBLE | NOT_ACCESSIBLE | COACCESSIBLE | NOT_COACCESSIBLE)) | \
-        ACCESSIBLE | COACCESSIBLE
-
-
-def tr_map(fst, arc_fn, final_fn, superfinal, props_fn):  # tr_map.rs:80-181 (MapNoSuperfinal / MapRequireSuperfinal)
-    if fst["start"] is None:
-        return
-    inprops = fst["props"]
-    sf = None
-    if superfinal:
-        sf = len(fst["rows"])
-        fst["rows"].append([])
-        fst["finals"].append(F32(0.0))
-    for s in range(len(fst["rows"])):
-        for tr in fst["rows"][s]:
-            arc_fn(tr)
-        w = fst["finals"][s]
-        if w is not None:
-            ftr = [0, 0, w]
-            final_fn(ftr)
-            if not superfinal:
-                assert ftr[0] == 0 and ftr[1] == 0
-                fst["finals"][s] = ftr[2]
-            elif s != sf and (ftr[0] != 0 or ftr[1] != 0 or not pw.is_zero(ftr[2])):
-                fst["rows"][s].append([ftr[0], ftr[1], ftr[2], sf])
-                fst["finals"][s] = None
-    fst["props"] = props_fn(inprops)
-
-
 class Partition:  # partition.rs:6-92
     def __init__(self, n):
         self.cls = [None] * n
@@ -377,23 +142,8 @@ def merge_states(part, fst):  # minimize.rs:213-266
                     dst.append(tr)
                     p = p_add_tr(p, state_map[c], tr, dst[-2] if len(dst) > 1 else None)
     fst["start"] = state_map[part.cls[fst["start"]]]
-    fst["props"] = pw.p_set_start(p)
+    fst["props"] = model.p_set_start(p)
     connect(fst)
-
-
-def tr_unique(fst):  # tr_unique.rs:8-51: stable sort on (ilabel, olabel, nextstate), dedup with Tr's == (weight: approximate)
-    for s, row in enumerate(fst["rows"]):
-        row.sort(key=lambda t: (t[0], t[1], t[3]))
-        out = []
-        for t in row:
-            if out and out[-1][0] == t[0] and out[-1][1] == t[1] and out[-1][3] == t[3] and pw.approx_eq(out[-1][2], t[2]):
-                continue
-            out.append(t)
-        fst["rows"][s] = out
-    p = fst["props"] & ARCSORT & DELETE_ARCS
-    if not fst["rows"]:
-        p |= NULL_PROPS
-    fst["props"] = p
 
 
 def acceptor_minimize(fst, seen=None):  # minimize.rs:181-211
@@ -422,37 +172,6 @@ def acceptor_minimize(fst, seen=None):  # minimize.rs:181-211
     tr_unique(fst)
 
 
-def rm_final_epsilon(fst):  # rm_final_epsilon.rs:20-78
-    rows, finals = fst["rows"], fst["finals"]
-    n = len(rows)
-    co = [f is not None for f in finals]
-    changed = True
-    while changed:
-        changed = False
-        for s in range(n):
-            if not co[s] and any(co[tr[3]] for tr in rows[s]):
-                co[s] = changed = True
-    fin_set = {s for s in range(n) if finals[s] is not None and not any(co[tr[3]] for tr in rows[s])}
-    p = fst["props"]
-    for s in range(n):
-        weight, dele = None, []
-        for i, tr in enumerate(rows[s]):
-            if tr[3] in fin_set and tr[0] == 0 and tr[1] == 0:
-                if weight is None:
-                    weight = finals[s] if finals[s] is not None else INF
-                v = pw.times(finals[tr[3]], tr[2])
-                weight = v if v < weight else weight  # plus_assign
-                dele.append(i)
-        if dele:
-            if not pw.is_zero(weight):
-                p = pw.p_set_final(p, finals[s], weight)
-                finals[s] = weight
-            rows[s] = [tr for i, tr in enumerate(rows[s]) if i not in dele]
-            p &= DELETE_ARCS
-    fst["props"] = p
-    connect(fst)
-
-
 def rdist_dag(flat):
     """reverse shortest distances of an acyclic FST in f32: d[s] = min(final[s], min over arcs (w + d[next])), the value the
     relaxation converges to (f32 addition is monotone); +inf for a state that reaches no final state"""
@@ -475,14 +194,10 @@ def rdist_dag(flat):
                 stack.pop()
                 best = F32(fin[s])
                 for a in arcs[b:e]:
-                    v = pw.times(F32(a["weight"]), d[int(a["nextstate"])])
+                    v = model.times(F32(a["weight"]), d[int(a["nextstate"])])
                     best = v if v < best else best
                 d[s] = best
     return d
-
-
-def is_cyclic(flat):
-    return pw.graph_facts(dict(flat, start=0))[2] if flat["n_states"] else False
 
 
 def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=None):
@@ -547,14 +262,6 @@ def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=N
     else:
         acceptor_minimize(fst, partition_out)
     return fst_to_flat(fst)
-
-
-# ---------------------------------------------------------------- generators
-def make_flat(n, start, rows, finals, props=0):
-    off = np.zeros(n + 1, dtype=np.uint32)
-    off[1:] = np.cumsum([len(r) for r in rows]) if n else []
-    arcs = np.array([tuple(a) for r in rows for a in r], dtype=TR_DTYPE) if n and off[-1] else np.zeros(0, dtype=TR_DTYPE)
-    return dict(n_states=n, start=start, offsets=off, arcs=arcs, finals=np.array(finals, dtype=np.float32), props=props)
 
 
 def trie_flat(rng, n_words, sigma, max_len, weighted=True, props=ACCEPTOR):
@@ -694,26 +401,16 @@ def test_symbol_declared_and_bound(wfst_lib):
     assert _lib.MinimizeConfig.delta.offset == 0 and _lib.MinimizeConfig.allow_nondet.offset == 4
 
 
-def _ko_message(status):
-    from rustfst_amd import _lib
-    assert status == 1
-    msg = C.c_char_p()
-    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
-    text = msg.value.decode()
-    _lib.lib().wfst_string_destroy(msg)
-    return text
-
-
 def test_argument_validation_without_gpu(wfst_lib):
     from rustfst_amd import _lib
     out = C.c_void_p(1)
     for d in (0.0, -1e-3, float("nan"), float("inf")):
         cfg = _lib.MinimizeConfig(d, 0)
-        assert "delta" in _ko_message(wfst_lib.wfst_minimize(None, None, C.byref(cfg), C.byref(out)))
+        assert "delta" in ko_message(wfst_lib.wfst_minimize(None, None, C.byref(cfg), C.byref(out)))
         assert out.value is None
-    assert "null" in _ko_message(wfst_lib.wfst_minimize(None, None, None, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_minimize(None, None, None, C.byref(out)))
     good = _lib.MinimizeConfig(1e-6, 1)
-    assert "null" in _ko_message(wfst_lib.wfst_minimize(None, None, C.byref(good), None))
+    assert "null" in ko_message(wfst_lib.wfst_minimize(None, None, C.byref(good), None))
 
 
 def test_python_surface():
@@ -890,7 +587,7 @@ def check_invariants(src_flat, got_dev, delta, ctx, rng, what, idempotent=True):
     for s in range(min(n, 2000)):
         labs = arcs["ilabel"][off[s]:off[s + 1]]
         assert len(set(labs.tolist())) == len(labs), f"{what}: state {s} is not deterministic"
-    acc, co, cyc, _ = pw.graph_facts(got)
+    acc, co, cyc, _ = model.graph_facts(got)
     assert acc and co and not cyc, what
     d_in = to_device(src_flat, ctx).shortest_distance(reverse=True)
     d_out = got_dev.shortest_distance(reverse=True)
@@ -898,7 +595,7 @@ def check_invariants(src_flat, got_dev, delta, ctx, rng, what, idempotent=True):
     unweighted = bool(got["props"] & UNWEIGHTED)
 
     def bound(length):
-        return length * float(pw.KDELTA) if unweighted else weight_bound(length, wmax, delta)
+        return length * float(model.KDELTA) if unweighted else weight_bound(length, wmax, delta)
     # the longest string of the result: its height (longest path from the start), by peeling in topological order
     height = np.zeros(n, dtype=np.int64)
     indeg = np.bincount(arcs["nextstate"], minlength=n)
@@ -1149,7 +846,7 @@ def test_word_list(gpu_ctx):
     mini = dev_minimize(flat, gpu_ctx)
     got = mini.to_flat()
     assert got["n_states"] < n // 2
-    acc, co, cyc, _ = pw.graph_facts(got)
+    acc, co, cyc, _ = model.graph_facts(got)
     assert acc and co and not cyc
     for w in [words[i] for i in rng.integers(0, len(words), size=300)]:
         assert accepts(got, w) == 0.0
@@ -1175,7 +872,7 @@ def test_errors(gpu_ctx):
         cfg = _lib.MinimizeConfig(kw.get("delta") or 1e-6, 1 if kw.get("allow_nondet") else 0)
         src = to_device(flat, gpu_ctx)
         assert _lib.lib().wfst_minimize(gpu_ctx._h, src._h, C.byref(cfg), C.byref(out)) == 1 and out.value is None
-        assert re.search(match, _ko_message(1))
+        assert re.search(match, ko_message(1))
 
     nd = make_flat(3, 0, [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)], [], []], [INF, 0.0, 0.0])
     for props in (0, ACCEPTOR | NOT_I_DETERMINISTIC | WEIGHTED):
@@ -1217,7 +914,7 @@ def test_errors(gpu_ctx):
 FACT_PAIRS = ((1, NOT_ACCEPTOR, ACCEPTOR), (2, I_EPSILONS, NO_I_EPSILONS), (4, EPSILONS, NO_EPSILONS), (8, O_EPSILONS, NO_O_EPSILONS),
               (16, NOT_I_LABEL_SORTED, I_LABEL_SORTED), (32, NOT_O_LABEL_SORTED, O_LABEL_SORTED), (64, WEIGHTED, UNWEIGHTED),
               (128, NOT_TOP_SORTED, TOP_SORTED))
-_KD_UP = float(np.nextafter(pw.KDELTA, F32(1.0)))
+_KD_UP = float(np.nextafter(model.KDELTA, F32(1.0)))
 
 
 def _fact_fst(rows, finals=(INF, INF, INF), start=2):
@@ -1239,7 +936,7 @@ FACT_CASES = {
     "16_ilabel_order": (_fact_fst([[], [(1, 1, 0.0, 0)], [(5, 3, 0.0, 0), (3, 4, 0.0, 0)]]), 1 | 16),
     "32_olabel_order": (_fact_fst([[], [(1, 1, 0.0, 0)], [(3, 5, 0.0, 0), (4, 3, 0.0, 0)]]), 1 | 32),
     # is_one is the approximate ==: a weight of exactly KDELTA is still one, the next f32 is a weight
-    "64_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, float(pw.KDELTA), 1)]]), 0),
+    "64_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, float(model.KDELTA), 1)]]), 0),
     "64_weight_above_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, _KD_UP, 1)]]), 64),
     "64_weighted": (_fact_fst([[], [(4, 4, 0.75, 0)], [(3, 3, 0.0, 1)]]), 64),
     # one arc running up, 0 -> 1: reversed it runs down
@@ -1249,7 +946,7 @@ FACT_CASES = {
     # a final weight that is not one (minimize.hip's FACT_FINAL_WEIGHTED): reverse() turns it into the weight of the
     # super-initial state's eps:eps arc
     "256_final_weight": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]], finals=(F32(0.75), INF, INF)), 2 | 4 | 8 | 64),
-    "256_final_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]], finals=(pw.KDELTA, INF, INF)), 2 | 4 | 8),
+    "256_final_weight_kdelta": (_fact_fst([[], [(4, 4, 0.0, 0)], [(3, 3, 0.0, 1)]], finals=(model.KDELTA, INF, INF)), 2 | 4 | 8),
 }
 
 

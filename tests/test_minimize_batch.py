@@ -17,16 +17,18 @@ from rustfst_amd._lib import TR_DTYPE
 
 import test_determinize as td
 import test_minimize as tm
+from oracle import model
+import helpers
 from helpers import assert_flat_identical, to_device
 
-ROOT = tm.ROOT
+ROOT = helpers.ROOT
 INF = float("inf")
 F32 = np.float32
 MAX_STATES, MAX_ARCS = 4096, 16384  # include/wfst.h: the in_kernel rule of wfst_minimize_batch
 DELTAS = (1e-6, 1.0 / 1024.0)
-KNOWN_W = tm.ACCEPTOR | tm.I_DETERMINISTIC | tm.WEIGHTED | tm.ACYCLIC | tm.INITIAL_ACYCLIC
-KNOWN_U = tm.ACCEPTOR | tm.I_DETERMINISTIC | tm.UNWEIGHTED | tm.ACYCLIC | tm.INITIAL_ACYCLIC
-INITIAL_CYCLIC = 0x0000_0010_0000_0000
+KNOWN_W = model.ACCEPTOR | model.I_DETERMINISTIC | model.WEIGHTED | model.ACYCLIC | model.INITIAL_ACYCLIC
+KNOWN_U = model.ACCEPTOR | model.I_DETERMINISTIC | model.UNWEIGHTED | model.ACYCLIC | model.INITIAL_ACYCLIC
+INITIAL_CYCLIC = model.INITIAL_CYCLIC
 
 
 def predict_in_kernel(flat):
@@ -42,12 +44,12 @@ def same(got, exp, what):
 def with_true_word(flat):
     """the item with a word that knows every fact minimize asks for (truthfully)"""
     w = np.concatenate([flat["arcs"]["weight"], flat["finals"][np.isfinite(flat["finals"])]])
-    weighted = bool(np.any(np.abs(w) > tm.pw.KDELTA))
+    weighted = bool(np.any(np.abs(w) > model.KDELTA))
     return dict(flat, props=KNOWN_W if weighted else KNOWN_U)
 
 
 def empty_flat(props=0):
-    return tm.make_flat(0, None, [], [], props)
+    return model.make_flat(0, None, [], [], props)
 
 
 # ================================================================ no GPU
@@ -69,7 +71,7 @@ def test_new_symbols_declared_exported_and_bound(wfst_lib):
 
 def test_argument_validation_without_gpu(wfst_lib):
     from rustfst_amd import _lib
-    ko = tm._ko_message
+    ko = helpers.ko_message
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
     assert wfst_lib.wfst_minimize_batch(None, None, 0, None, None, None) == 0  # n == 0: OK
@@ -93,7 +95,7 @@ def test_null_entry_is_ko(wfst_lib):
     a device, so the one here is a block of zeroed memory: THIS TEST DEPENDS ON THE LAYOUT OF wfst_ctx, in that the struct
     must stay smaller than the block (1 MiB) and the call must do no more with the context, before it has checked the
     list, than clear its three stat words (which keeps "all 0 after a KO before any launch" true for this KO too)."""
-    ko = tm._ko_message
+    ko = helpers.ko_message
     ctx = C.create_string_buffer(1 << 20)
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
@@ -116,7 +118,7 @@ def test_python_surface():
 
 
 def test_prediction_of_the_rule():
-    f = tm.make_flat(2, 0, [[(1, 1, 0.0, 1)], []], [INF, 0.0])
+    f = model.make_flat(2, 0, [[(1, 1, 0.0, 1)], []], [INF, 0.0])
     assert predict_in_kernel(f) == 1 and predict_in_kernel(empty_flat()) == 1
     assert predict_in_kernel(dict(f, n_states=MAX_STATES)) == 1 and predict_in_kernel(dict(f, n_states=MAX_STATES + 1)) == 0
     assert predict_in_kernel(dict(f, arcs=np.zeros(MAX_ARCS, TR_DTYPE))) == 1
@@ -152,7 +154,7 @@ def check_list(items, ctx, delta=None, single=True, upload_many=False):
     st = _stats(ctx)
     assert st["items_in_kernel"] == sum(want) and st["items_single"] == len(want) - sum(want)
     assert st["launches"] == (1 if any(w and f["n_states"] for w, f in zip(want, flats)) else 0)
-    d = tm.KSHORTESTDELTA if delta is None else delta
+    d = model.KSHORTESTDELTA if delta is None else delta
     which = range(len(items)) if single is True else single
     for k, ((name, flat), g) in enumerate(zip(items, got)):
         same(g, tm.minimize_ref(flat, d), f"item {k} ({name}) delta {d} vs the restatement")
@@ -172,13 +174,13 @@ def test_known_answers_and_degenerate_items(gpu_ctx):
     gone, gone_known = tm.no_start_cases()[0][0], tm.no_start_cases()[1][0]
     degenerate = [
         ("no states", empty_flat()), ("no states, known word", empty_flat(KNOWN_U)),
-        ("no start, unweighted", tm.make_flat(2, None, [[(1, 1, 0.0, 1)], []], [INF, 0.0], tm.ACCEPTOR)),
-        ("no start, unweighted, word 0", tm.make_flat(2, None, [[(1, 1, 0.0, 1)], []], [INF, 0.0], 0)),
+        ("no start, unweighted", model.make_flat(2, None, [[(1, 1, 0.0, 1)], []], [INF, 0.0], model.ACCEPTOR)),
+        ("no start, unweighted, word 0", model.make_flat(2, None, [[(1, 1, 0.0, 1)], []], [INF, 0.0], 0)),
         ("no start, weighted, all-one pushed", gone), ("no start, weighted, known word", gone_known),
-        ("one final state", tm.make_flat(1, 0, [[]], [0.0], 0)), ("one final state, weight 2", tm.make_flat(1, 0, [[]], [2.0], 0)),
-        ("trims to nothing", tm.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 2.0, 2)], []], [INF, INF, INF], tm.ACCEPTOR)),
-        ("trims to nothing, unweighted", tm.make_flat(3, 0, [[(1, 1, 0.0, 1)], [(2, 2, 0.0, 2)], []], [INF, INF, INF], 0)),
-        ("final state out of reach", tm.make_flat(3, 0, [[(1, 1, 1.0, 1)], [], [(1, 1, 0.5, 1)]], [INF, INF, 1.0], 0)),
+        ("one final state", model.make_flat(1, 0, [[]], [0.0], 0)), ("one final state, weight 2", model.make_flat(1, 0, [[]], [2.0], 0)),
+        ("trims to nothing", model.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 2.0, 2)], []], [INF, INF, INF], model.ACCEPTOR)),
+        ("trims to nothing, unweighted", model.make_flat(3, 0, [[(1, 1, 0.0, 1)], [(2, 2, 0.0, 2)], []], [INF, INF, INF], 0)),
+        ("final state out of reach", model.make_flat(3, 0, [[(1, 1, 1.0, 1)], [], [(1, 1, 0.5, 1)]], [INF, INF, 1.0], 0)),
     ]
     for delta, cases in groups.items():
         items = [(name, flat) for name, flat, _ in cases] + degenerate
@@ -222,7 +224,7 @@ def chain(n, weighted, real=False, seed=1):
     rows = [[(1 + s % 3, 1 + s % 3, float(F32(rng.random() * 3)) if real else (float(s % 4) if weighted else 0.0), s + 1)]
             for s in range(n - 1)] + [[]]
     finals = [INF] * (n - 1) + [1.0 if weighted else 0.0]
-    return tm.make_flat(n, 0, rows, finals, tm.ACCEPTOR if weighted else 0)
+    return model.make_flat(n, 0, rows, finals, model.ACCEPTOR if weighted else 0)
 
 
 def hubs(width, weighted):
@@ -241,15 +243,15 @@ def hubs(width, weighted):
     if not weighted:
         rows[8], rows[9] = [(7, 7, 0.0, 4)], [(7, 7, 0.0, 5)]
     finals = [INF] * 4 + ([0.0, 0.0, 1.0, 1.0] if weighted else [0.0] * 4) + [INF, INF]
-    return tm.make_flat(10, 0, rows, finals, tm.ACCEPTOR if weighted else 0)
+    return model.make_flat(10, 0, rows, finals, model.ACCEPTOR if weighted else 0)
 
 
 def real_dag(n):
     """a random DAG with real-valued weights of which a good part survives connect"""
     for seed in range(100):
         f = tm.random_dag(np.random.default_rng(seed), n, 4, True, real=True)
-        fst = tm.flat_to_fst(f)
-        tm.connect(fst)
+        fst = model.flat_to_fst(f)
+        model.connect(fst)
         if 3 * len(fst["rows"]) >= n:
             return f
     raise AssertionError("no seed gives a connected part")
@@ -264,8 +266,8 @@ def boundary_items():
     m = tm.closed_form_base(np.random.default_rng(33))
     all_final = tm.random_dag(rng, 120, 4, True, real=True)
     all_final["finals"] = (rng.permutation(120).astype(np.float32) / F32(7.0) + F32(0.01)).astype(np.float32)
-    one_tuple = tm.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [1.0], 0)
-    one_tuple_u = tm.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [0.0], 0)
+    one_tuple = model.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [1.0], 0)
+    one_tuple_u = model.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [0.0], 0)
     items = [("chain 1500 weighted", chain(1500, True)), ("chain 1500 unweighted", chain(1500, False)),
              ("chain 700 real", chain(700, True, real=True)),
              ("hubs 300", hubs(300, True)), ("hubs 1100", hubs(1100, True)), ("hubs 1100 unweighted", hubs(1100, False)),
@@ -307,7 +309,7 @@ def dag_with(n_states, n_arcs, seed, weighted=True):
         t = int(rng.integers(s + 1, n_states))
         rows[s].append((3 + j // heads, 3 + j // heads, float((s + j) % 2) if weighted else 0.0, t))
     finals = [0.0 if not r else INF for r in rows]
-    f = tm.make_flat(n_states, 0, rows, finals, tm.ACCEPTOR)
+    f = model.make_flat(n_states, 0, rows, finals, model.ACCEPTOR)
     assert f["n_states"] == n_states and len(f["arcs"]) == n_arcs
     return f
 
@@ -329,7 +331,7 @@ def test_edges_of_the_in_kernel_rule(gpu_ctx):
     assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=1)
     # the one exception to the rule: a word that says INITIAL_CYCLIC (here against ACYCLIC and the content) sends a small item
     # to the single call, whose answer, or KO, is the batch call's
-    odd = dict(items[5][1], props=(KNOWN_W & ~tm.INITIAL_ACYCLIC) | INITIAL_CYCLIC)
+    odd = dict(items[5][1], props=(KNOWN_W & ~model.INITIAL_ACYCLIC) | INITIAL_CYCLIC)
     assert predict_in_kernel(odd) == 0 and odd["n_states"] == 20
     devs = [to_device(items[5][1], gpu_ctx), to_device(odd, gpu_ctx)]
     try:
@@ -350,7 +352,7 @@ def test_more_items_than_resident_workgroups(gpu_ctx):
     items = []
     for k in range(3000):
         n = int(rng.integers(1, 9))
-        flat = tm.random_dag(rng, n, 3, weighted=k % 2 == 0, props=tm.ACCEPTOR if k % 3 else 0, real=k % 5 == 0)
+        flat = tm.random_dag(rng, n, 3, weighted=k % 2 == 0, props=model.ACCEPTOR if k % 3 else 0, real=k % 5 == 0)
         items.append((f"tiny {k}", flat))
     assert max(f["n_states"] for _, f in items) <= 8
     check_list(items, gpu_ctx, single=[int(i) for i in rng.choice(3000, size=50, replace=False)], upload_many=True)
@@ -375,17 +377,17 @@ def test_determinize_batch_then_minimize_batch(gpu_ctx):
         same(got, tm.minimize_ref(det_flat), f"lattice {k} vs the restatement")
         shrunk += got["n_states"] < det_flat["n_states"]
         if k % 4 == 0:
-            tm.check_invariants(det_flat, mini, tm.KSHORTESTDELTA, gpu_ctx, rng, f"lattice {k}")
+            tm.check_invariants(det_flat, mini, model.KSHORTESTDELTA, gpu_ctx, rng, f"lattice {k}")
     assert shrunk >= 4
 
 
 def bad_items():
-    cyc = tm.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 0.0, 2), (2, 2, 0.0, 0)], []], [INF, INF, 0.0], 0)
+    cyc = model.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 0.0, 2), (2, 2, 0.0, 0)], []], [INF, INF, 0.0], 0)
     # states 3 and 4 form a cycle nothing reaches: connect would remove it
-    hidden = tm.make_flat(5, 0, [[(1, 1, 1.0, 1)], [(1, 1, 0.0, 2)], [], [(1, 1, 0.0, 4)], [(1, 1, 0.0, 3)]],
-                          [INF, INF, 0.0, INF, INF], tm.ACCEPTOR)
-    nd = tm.make_flat(3, 0, [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)], [], []], [INF, 0.0, 0.0], 0)
-    tr = tm.make_flat(2, 0, [[(1, 2, 0.0, 1)], []], [INF, 0.0], 0)
+    hidden = model.make_flat(5, 0, [[(1, 1, 1.0, 1)], [(1, 1, 0.0, 2)], [], [(1, 1, 0.0, 4)], [(1, 1, 0.0, 3)]],
+                          [INF, INF, 0.0, INF, INF], model.ACCEPTOR)
+    nd = model.make_flat(3, 0, [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)], [], []], [INF, 0.0, 0.0], 0)
+    tr = model.make_flat(2, 0, [[(1, 2, 0.0, 1)], []], [INF, 0.0], 0)
     far = tm.far_apart_cases()[0]
     stays = tm.no_start_cases()[2][0]
     return [("cyclic", cyc, "cyclic inputs"), ("hidden cycle", hidden, "cyclic inputs"), ("non-deterministic", nd, "Refusing"),
@@ -398,7 +400,7 @@ def _single_message(dev, ctx, allow_nondet=False):
     out = C.c_void_p()
     cfg = _lib.MinimizeConfig(1e-6, 1 if allow_nondet else 0)
     assert _lib.lib().wfst_minimize(ctx._h, dev._h, C.byref(cfg), C.byref(out)) == 1 and out.value is None
-    return tm._ko_message(1)
+    return helpers.ko_message(1)
 
 
 def _raw_batch(devs, ctx, allow_nondet=False):
@@ -426,12 +428,12 @@ def test_errors(gpu_ctx):
             assert re.search("non-deterministic inputs are not supported" if nondet else pattern, single), (name, single)
             mixed = devs[:5] + [bad] + devs[6:]
             status, outs = _raw_batch(mixed, gpu_ctx, nondet)
-            assert status == 1 and tm._ko_message(1) == "item 5: " + single, name
+            assert status == 1 and helpers.ko_message(1) == "item 5: " + single, name
             assert [outs[i] for i in range(12)] == [None] * 12, name
             # a second bad item further on: the lowest index is reported
             mixed[9] = bad_devs[(k + 1) % len(bads)]
             status, outs = _raw_batch(mixed, gpu_ctx, nondet)
-            assert status == 1 and tm._ko_message(1) == "item 5: " + single, name
+            assert status == 1 and helpers.ko_message(1) == "item 5: " + single, name
             assert [outs[i] for i in range(12)] == [None] * 12, name
             # the context works afterwards
             for g, e in zip(_batch(devs, gpu_ctx)[0], good):
@@ -442,7 +444,7 @@ def test_errors(gpu_ctx):
     other = rustfst_amd.Context(0)
     foreign = to_device(goods[3], other)
     status, outs = _raw_batch(devs[:3] + [foreign] + devs[4:], gpu_ctx)
-    msg = tm._ko_message(status)
+    msg = helpers.ko_message(status)
     assert "item 3" in msg and "another context" in msg
     assert [outs[i] for i in range(12)] == [None] * 12
     assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)

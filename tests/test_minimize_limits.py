@@ -26,10 +26,12 @@ import numpy as np
 import pytest
 
 import test_minimize as tm
+from oracle import model
+import helpers
 from helpers import assert_flat_identical, to_device
 
-ROOT = tm.ROOT
-INF, ACCEPTOR = tm.INF, tm.ACCEPTOR
+ROOT = helpers.ROOT
+INF, ACCEPTOR = model.INF, model.ACCEPTOR
 PATHS = ("auto", "narrow", "wide")
 NARROW_MAX, LANE_MAX_DEG, NARROW_WAVES = 4096, 64, 16  # minimize.hip (a 1024-thread workgroup: 16 waves)
 PASS = ("levels", "wide_levels", "narrow_launches", "exit_wide", "exit_done")
@@ -180,7 +182,7 @@ def instantiate(levels, weighted, seed, props=ACCEPTOR, unreachable_copy_of=None
         rows[start] = rows[start] + [(5, 5, 1.0 if weighted else 0.0, len(rows))]
         rows.append([])
         finals.append(INF)
-    return dict(tm.make_flat(len(rows), start, rows, finals, props), members=members)
+    return dict(model.make_flat(len(rows), start, rows, finals, props), members=members)
 
 
 TAPER = (300, 9, 1)  # the top of every large profile: 1 start state reaches 9, those 300, those a level of 4097
@@ -250,7 +252,7 @@ CASES = {
     "small_alternating": lambda w: instantiate(layers(SMALL_ALTERNATING, ALTERNATING_COVERS), w, 6),
     # level 1 holds 4096 states, and one more that nothing reaches: 4097 for the cycle check, 4096 for the refinement
     "check_differs": lambda w: instantiate(layers((300, 4096) + TAPER), w, 7, unreachable_copy_of=(1, 0), dead_end=True),
-    "check_skipped": lambda w: instantiate(layers((300, 4096) + TAPER), w, 7, ACCEPTOR | tm.ACYCLIC | tm.INITIAL_ACYCLIC,
+    "check_skipped": lambda w: instantiate(layers((300, 4096) + TAPER), w, 7, ACCEPTOR | model.ACYCLIC | model.INITIAL_ACYCLIC,
                                            unreachable_copy_of=(1, 0), dead_end=True),
     # (the hubs' rows in label order: a group's labels are its own, so the encode order of the weighted T, the order of first
     # occurrence, is then the label order within a group)
@@ -272,7 +274,7 @@ def analysis(name, kind):
     seen = {}
     exp = tm.minimize_ref(flat, partition_out=seen)
     profile, height = heights(seen["T"])
-    check = None if tm.known(flat["props"]) & tm.ACYCLIC else level_profile(flat)
+    check = None if model.known(flat["props"]) & model.ACYCLIC else level_profile(flat)
     return dict(exp=exp, T=seen["T"], part=seen["part"], profile_check=check, profile=profile, height=height,
                 degrees=[len(r) for r in seen["T"]["rows"]])
 
@@ -321,7 +323,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
 def test_null_ctx_is_ko(wfst_lib):
     v = C.c_uint64(5)
     args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in tm._ko_message(wfst_lib.wfst_ctx_get_minimize_stats(None, *args))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_minimize_stats(None, *args))
     assert v.value == 5
 
 
@@ -359,18 +361,18 @@ def test_routing_restatement_against_closed_forms():
 
 def test_level_profile_on_hand_made_graphs():
     # 0 -> 1 -> 3, 0 -> 2 -> 3, 2 -> 4: sinks 3 and 4, then 1 and 2, then 0
-    dag = tm.make_flat(5, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(1, 1, 0.0, 3)], [(1, 1, 0.0, 3), (2, 2, 0.0, 4)], [], []],
+    dag = model.make_flat(5, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(1, 1, 0.0, 3)], [(1, 1, 0.0, 3), (2, 2, 0.0, 4)], [], []],
                        [INF, INF, INF, 0.0, 0.0])
-    assert level_profile(dag) == level_profile(tm.flat_to_fst(dag)) == [2, 2, 1]
+    assert level_profile(dag) == level_profile(model.flat_to_fst(dag)) == [2, 2, 1]
     assert heights(dag)[1].tolist() == [2, 1, 1, 0, 0]
     # the height is the LONGEST way down: 0 -> 1 -> 2 and 0 -> 2
-    assert level_profile(tm.make_flat(3, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(1, 1, 0.0, 2)], []], [INF, INF, 0.0])) == [1, 1, 1]
+    assert level_profile(model.make_flat(3, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(1, 1, 0.0, 2)], []], [INF, INF, 0.0])) == [1, 1, 1]
     # two arcs of one state into one state leave together
-    assert level_profile(tm.make_flat(2, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 1)], []], [INF, 0.0])) == [1, 1]
+    assert level_profile(model.make_flat(2, 0, [[(1, 1, 0.0, 1), (2, 2, 0.0, 1)], []], [INF, 0.0])) == [1, 1]
     # a cycle holds itself and what leads to it: 0 -> 1 <-> 2, 1 -> 3
-    cyc = tm.make_flat(4, 0, [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 2), (2, 2, 0.0, 3)], [(1, 1, 0.0, 1)], []], [INF, INF, INF, 0.0])
+    cyc = model.make_flat(4, 0, [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 2), (2, 2, 0.0, 3)], [(1, 1, 0.0, 1)], []], [INF, INF, INF, 0.0])
     assert level_profile(cyc) == [1] and heights(cyc)[1].tolist() == [-1, -1, -1, 0]
-    assert level_profile(tm.make_flat(2, 0, [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 0)]], [INF, 0.0])) == []
+    assert level_profile(model.make_flat(2, 0, [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 0)]], [INF, 0.0])) == []
 
 
 def _on_profile(name, kind, check=None):
@@ -378,8 +380,8 @@ def _on_profile(name, kind, check=None):
     flat = case(name, kind)
     assert an["profile"] == refine_profile(name, kind), (name, kind)
     assert an["profile_check"] == (list(PROFILES[name]) if check is None else check), (name, kind)
-    assert tm.known(flat["props"]) & (tm.ACYCLIC | tm.I_DETERMINISTIC | tm.WEIGHTED) == 0 and flat["n_states"] <= 25000
-    assert bool(an["exp"]["props"] & tm.UNWEIGHTED) == (kind == "u"), "the branch"
+    assert model.known(flat["props"]) & (model.ACYCLIC | model.I_DETERMINISTIC | model.WEIGHTED) == 0 and flat["n_states"] <= 25000
+    assert bool(an["exp"]["props"] & model.UNWEIGHTED) == (kind == "u"), "the branch"
     assert max(an["degrees"]) <= LANE_MAX_DEG
     assert an["exp"]["n_states"] < len(an["T"]["rows"]) // 4, "classes merge"
     return an
@@ -444,7 +446,7 @@ def test_check_pass_inputs_sit_on_their_limit(kind):
     assert (a["wide_levels"], a["narrow_launches"], a["exit_wide"], a["exit_done"]) == (0, 1, 0, 1)
     skipped = analysis("check_skipped", kind)
     assert skipped["profile_check"] is None and skipped["profile"] == an["profile"]
-    assert tm.known(case("check_skipped", kind)["props"]) & tm.ACYCLIC
+    assert model.known(case("check_skipped", kind)["props"]) & model.ACYCLIC
     b = want("check_skipped", kind, "auto")
     assert all(b["check_" + k] == 0 for k in PASS) and {k: b[k] for k in PASS} == {k: a[k] for k in PASS}
 
@@ -518,9 +520,9 @@ def test_degree_inputs_sit_on_their_limit(name):
 def test_cyclic_inputs_stop_where_they_are_built_to():
     for name, (flat, profile) in cyclic_cases().items():
         assert level_profile(flat) == profile, name
-        assert sum(profile) < flat["n_states"] and tm.is_cyclic(flat), name
-        assert tm.known(flat["props"]) & tm.ACYCLIC == 0
-        with pytest.raises(tm.Unsupported, match="cyclic"):
+        assert sum(profile) < flat["n_states"] and model.is_cyclic(flat), name
+        assert model.known(flat["props"]) & model.ACYCLIC == 0
+        with pytest.raises(model.Unsupported, match="cyclic"):
             tm.minimize_ref(flat)
     c = {k: route(v[1], "auto") for k, v in cyclic_cases().items()}
     assert c["ring"] == _pass()
@@ -529,28 +531,28 @@ def test_cyclic_inputs_stop_where_they_are_built_to():
     assert c["removed_by_connect"]["exit_done"] == 1
     # the cycle of the last one lies among states connect removes: the connected machine is acyclic
     flat = cyclic_cases()["removed_by_connect"][0]
-    fst = tm.flat_to_fst(flat)
-    tm.connect(fst)
-    assert len(fst["rows"]) == flat["n_states"] - 2 and not tm.is_cyclic(tm.fst_to_flat(fst))
+    fst = model.flat_to_fst(flat)
+    model.connect(fst)
+    assert len(fst["rows"]) == flat["n_states"] - 2 and not model.is_cyclic(model.fst_to_flat(fst))
 
 
 def cyclic_cases():
     """name -> (flat, the levels the cycle check peels); every word leaves ACYCLIC unknown"""
     out = {}
     # (a) a cycle through every state
-    out["ring"] = (tm.make_flat(6, 0, [[(1, 1, 0.0, (s + 1) % 6)] for s in range(6)], [INF] * 5 + [0.0], ACCEPTOR), [])
+    out["ring"] = (model.make_flat(6, 0, [[(1, 1, 0.0, (s + 1) % 6)] for s in range(6)], [INF] * 5 + [0.0], ACCEPTOR), [])
     # (b) 4097 sinks under a ring of 70 states with 60 arcs each into them: the one level that leaves is wide
     rows = [[(1, 1, 0.0, (s + 1) % 70)] + [(2 + j, 2 + j, 0.0, 70 + (60 * s + j) % 4097) for j in range(60)] for s in range(70)]
-    out["after_wide"] = (tm.make_flat(70 + 4097, 0, rows + [[]] * 4097, [INF] * 70 + [0.0] * 4097, ACCEPTOR), [4097])
+    out["after_wide"] = (model.make_flat(70 + 4097, 0, rows + [[]] * 4097, [INF] * 70 + [0.0] * 4097, ACCEPTOR), [4097])
     # (c) 0 -> 1 <-> 2 above a chain 3 -> 4 -> 5 (from 1): three levels leave inside one narrow launch
     rows = [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 2), (2, 2, 0.0, 3)], [(1, 1, 0.0, 1)], [(1, 1, 0.0, 4)], [(1, 1, 0.0, 5)], []]
-    out["inside_narrow"] = (tm.make_flat(6, 0, rows, [INF] * 5 + [0.0], 0), [1, 1, 1])
+    out["inside_narrow"] = (model.make_flat(6, 0, rows, [INF] * 5 + [0.0], 0), [1, 1, 1])
     # (d) a good machine and two states nothing reaches that form a cycle
     good = case("small_alternating", "u")
     rows = [[tuple(a) for a in good["arcs"][good["offsets"][s]:good["offsets"][s + 1]]] for s in range(good["n_states"])]
     n = good["n_states"]
     rows += [[(1, 1, 0.0, n + 1)], [(1, 1, 0.0, n)]]
-    out["removed_by_connect"] = (tm.make_flat(n + 2, good["start"], rows, list(good["finals"]) + [0.0, INF], ACCEPTOR),
+    out["removed_by_connect"] = (model.make_flat(n + 2, good["start"], rows, list(good["finals"]) + [0.0, INF], ACCEPTOR),
                                  list(SMALL_ALTERNATING))
     return out
 
@@ -708,14 +710,14 @@ def test_counters_reset_and_empty_inputs(gpu_ctx, monkeypatch):
     dev.minimize()
     first = gpu_ctx.minimize_stats()
     assert {k: first[k] for k in PREDICTED} == want("one_4097", "w", "auto")
-    for props in (0, ACCEPTOR, ACCEPTOR | tm.I_DETERMINISTIC | tm.WEIGHTED):
-        empty = tm.make_flat(0, None, [], [], props)
+    for props in (0, ACCEPTOR, ACCEPTOR | model.I_DETERMINISTIC | model.WEIGHTED):
+        empty = model.make_flat(0, None, [], [], props)
         assert to_device(empty, gpu_ctx).minimize().to_flat()["n_states"] == 0
         assert gpu_ctx.minimize_stats() == dict.fromkeys(COUNTERS, 0), hex(props)
         dev.minimize()
         assert gpu_ctx.minimize_stats() == first
     # the branches that end early: nothing left after connect (4), weighted without a start state (3)
-    dead = tm.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 2.0, 2)], []], [INF, INF, INF], ACCEPTOR)
+    dead = model.make_flat(3, 0, [[(1, 1, 1.0, 1)], [(1, 1, 2.0, 2)], []], [INF, INF, INF], ACCEPTOR)
     to_device(dead, gpu_ctx).minimize()
     st = gpu_ctx.minimize_stats()
     assert st["branch"] == 4 and st["check_levels"] == 3 and st["levels"] == 0

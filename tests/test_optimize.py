@@ -3,8 +3,8 @@ sequential Python restatement of rustfst's tr_sum.rs, tr_unique.rs, encode/decod
 optimize.rs (tropical semiring) written out below and checked against the hand-derived K17 known answers, and on the device
 bit-exact parity with the restatement: states, offsets, arcs (weights by bit pattern), finals and property word.
 
-The restatement reuses determinize_ref / determinize_props (test_determinize.py), minimize_ref and the property helpers
-(test_minimize.py, test_push_weights.py) and the oracle's rm_epsilon.
+The restatement reuses determinize_ref (test_determinize.py), minimize_ref (test_minimize.py), the weight and property
+rules, tr_unique and rm_final_epsilon of oracle/model/ and the oracle's rm_epsilon.
 
 Shapes of the arc-list tests, and why: the kernel keeps a state in one register per lane up to 16 arcs, works in chunks of
 16 up to 256 arcs and hands larger states to a radix sort, so the degrees are 0, 1, 16, 17, 256, 257 and 300; duplicate
@@ -19,21 +19,18 @@ import pytest
 
 from rustfst_amd._lib import TR_DTYPE
 
-from helpers import assert_flat_identical, to_device, to_oracle
+from oracle import model
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ALL, EPSILONS, F32, INF, I_DETERMINISTIC, LABEL_INVARIANT,
+                          NOT_I_DETERMINISTIC, NO_EPSILONS, UNWEIGHTED, UNWEIGHTED_CYCLES, Unsupported,
+                          WEIGHT_INVARIANT, content_word_of_flat, rm_final_epsilon, rows_flat, tr_unique)
+from helpers import assert_flat_identical, ko_message, to_device, to_oracle
 import test_determinize as td
 import test_minimize as tm
-import test_push_weights as pw
-from test_push_weights import (ACCEPTOR, NOT_ACCEPTOR, I_DETERMINISTIC, NOT_I_DETERMINISTIC, NO_EPSILONS, EPSILONS,  # noqa: F401
-                               ACYCLIC, CYCLIC, TOP_SORTED, UNWEIGHTED, UNWEIGHTED_CYCLES, ACCESSIBLE, NOT_ACCESSIBLE,
-                               COACCESSIBLE, NOT_COACCESSIBLE, ALL, WEIGHT_INVARIANT)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k17_optimize.json")
-F32, INF = np.float32, np.float32(np.inf)
 PATHS = ("narrow", "wide", "auto")
 MSG_ACYCLIC = "optimize: inputs whose property word does not hold ACYCLIC are not supported"
-LABEL_INVARIANT = tm.I_LABEL_INVARIANT & tm.O_LABEL_INVARIANT
-Unsupported = tm.Unsupported
 
 
 # ---------------------------------------------------------------- the restatement
@@ -53,25 +50,9 @@ def tr_sum(fst):  # tr_sum.rs:7-22, sum_trs_unchecked (vector_fst/mutable_fst.rs
             else:
                 out.append(list(t))
         fst["rows"][s] = out
-    p = props & tm.ARCSORT & tm.DELETE_ARCS & WEIGHT_INVARIANT
+    p = props & model.ARCSORT & model.DELETE_ARCS & WEIGHT_INVARIANT
     if not fst["rows"]:
-        p |= tm.NULL_PROPS
-    fst["props"] = p
-
-
-def tr_unique(fst):  # tr_unique.rs:38-51, unique_trs_unchecked (:358-377): Vec::dedup compares with the last KEPT arc
-    props = fst["props"]
-    for s, row in enumerate(fst["rows"]):
-        row = sorted(row, key=tr_key)
-        out = []
-        for t in row:
-            if out and tr_key(out[-1]) == tr_key(t) and pw.approx_eq(out[-1][2], t[2]):  # Tr's ==: the weight within KDELTA
-                continue
-            out.append(list(t))
-        fst["rows"][s] = out
-    p = props & tm.ARCSORT & tm.DELETE_ARCS
-    if not fst["rows"]:
-        p |= tm.NULL_PROPS
+        p |= model.NULL_PROPS
     fst["props"] = p
 
 
@@ -84,50 +65,14 @@ def encode_labels(fst):  # encode(EncodeLabels): encode_static.rs, table.rs; Map
             pairs.append(k)
             table[k] = len(pairs)
         tr[0] = tr[1] = table[k]
-    tm.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
+    model.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
     return pairs
-
-
-def rm_final_epsilon(fst):  # rm_final_epsilon.rs:20-78
-    rows, finals = fst["rows"], fst["finals"]
-    n = len(rows)
-    pred = [[] for _ in range(n)]
-    for s, row in enumerate(rows):
-        for tr in row:
-            pred[tr[3]].append(s)
-    co = [f is not None for f in finals]
-    stack = [s for s in range(n) if co[s]]
-    while stack:
-        s = stack.pop()
-        for q in pred[s]:
-            if not co[q]:
-                co[q] = True
-                stack.append(q)
-    fin_set = {s for s in range(n) if finals[s] is not None and not any(co[tr[3]] for tr in rows[s])}
-    p = fst["props"]
-    for s in range(n):
-        weight, dele = None, []
-        for i, tr in enumerate(rows[s]):
-            if tr[3] in fin_set and tr[0] == 0 and tr[1] == 0:
-                if weight is None:
-                    weight = finals[s] if finals[s] is not None else INF
-                v = pw.times(finals[tr[3]], tr[2])
-                weight = v if v < weight else weight
-                dele.append(i)
-        if dele:
-            if not pw.is_zero(weight):
-                p = pw.p_set_final(p, finals[s], weight)
-                finals[s] = weight
-            rows[s] = [tr for i, tr in enumerate(rows[s]) if i not in dele]
-            p &= tm.DELETE_ARCS
-    fst["props"] = p
-    tm.connect(fst)
 
 
 def decode_labels(fst, pairs):  # decode (decode_static.rs): the pair back, the same mask, rm_final_epsilon
     def arc(tr):
         tr[0], tr[1] = pairs[tr[0] - 1]
-    tm.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
+    model.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
     rm_final_epsilon(fst)
 
 
@@ -140,7 +85,7 @@ def determinize_encoded(flat):
     """determinize of a label-encoded machine (ilabel == olabel >= 1, the word without ACCEPTOR): the acceptor
     construction, the word of the gallic call (determinize_static.rs:177-192)"""
     out = td.determinize_ref(dict(flat, props=flat["props"] | ACCEPTOR))
-    out["props"] = td.determinize_props(flat["props"], True)
+    out["props"] = model.determinize_props(flat["props"], True)
     return out
 
 
@@ -157,9 +102,9 @@ def optimize_ref(flat, oracle):
     cur = flat
     if not cur["props"] & NO_EPSILONS:
         cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
-    fst = tm.flat_to_fst(cur)
+    fst = model.flat_to_fst(cur)
     tr_sum(fst)
-    cur = tm.fst_to_flat(fst)
+    cur = model.fst_to_flat(fst)
     p = cur["props"]
     if p & I_DETERMINISTIC:
         return tm.minimize_ref(cur)
@@ -169,34 +114,23 @@ def optimize_ref(flat, oracle):
     if acceptor:
         return det_min(cur, False)
     pairs = encode_labels(fst)
-    mini = tm.flat_to_fst(det_min(tm.fst_to_flat(fst), True))
+    mini = model.flat_to_fst(det_min(model.fst_to_flat(fst), True))
     decode_labels(mini, pairs)
-    return tm.fst_to_flat(mini)
+    return model.fst_to_flat(mini)
 
 
 def apply_op(op, flat, oracle=None):
     if op == "optimize":
         return optimize_ref(flat, oracle)
-    fst = tm.flat_to_fst(norm(flat))
+    fst = model.flat_to_fst(norm(flat))
     (tr_sum if op == "tr_sum" else tr_unique)(fst)
-    return tm.fst_to_flat(fst)
-
-
-def content_word(flat):
-    """the word compute_fst_properties finds on the content: every trinary pair known"""
-    fst = tm.flat_to_fst(dict(flat, props=0))
-    tm.compute_and_update(fst, ALL)
-    return fst["props"]
+    return model.fst_to_flat(fst)
 
 
 # ---------------------------------------------------------------- inputs
 def golden_cases():
     with open(GOLDEN) as f:
         return json.load(f)["cases"]
-
-
-def rows_flat(rows, finals, start=0, props=0):
-    return tm.make_flat(len(rows), start, rows, finals, props)
 
 
 def part_a_rows():
@@ -282,7 +216,7 @@ def optimize_input(rng, n, transducer, deterministic=False, eps=True):
         rows.append(row)
         finals.append(float(rng.integers(0, 2)) if rng.random() < 0.3 or s == n - 1 else INF)
     flat = rows_flat(rows, finals)
-    flat["props"] = content_word(flat)
+    flat["props"] = content_word_of_flat(flat)
     return flat
 
 
@@ -304,7 +238,7 @@ def branch_of(flat, oracle):
     cur = norm(flat)
     if not cur["props"] & NO_EPSILONS:
         cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
-    fst = tm.flat_to_fst(cur)
+    fst = model.flat_to_fst(cur)
     tr_sum(fst)
     if fst["props"] & I_DETERMINISTIC:
         return "min"
@@ -324,23 +258,13 @@ def test_symbols_declared_and_bound(wfst_lib):
         assert hasattr(wfst_lib, name)
 
 
-def _ko_message(status):
-    from rustfst_amd import _lib
-    assert status == 1
-    msg = C.c_char_p()
-    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
-    text = msg.value.decode()
-    _lib.lib().wfst_string_destroy(msg)
-    return text
-
-
 def test_argument_validation_without_gpu(wfst_lib):
     for name in ("wfst_tr_sum", "wfst_tr_unique", "wfst_optimize"):
         fn = getattr(wfst_lib, name)
         out = C.c_void_p(1)
-        assert "null" in _ko_message(fn(None, None, C.byref(out)))
+        assert "null" in ko_message(fn(None, None, C.byref(out)))
         assert out.value is None
-        assert "null" in _ko_message(fn(None, None, None))
+        assert "null" in ko_message(fn(None, None, None))
 
 
 def test_python_surface():
@@ -381,14 +305,14 @@ def stage_words(flat, oracle):
     if not cur["props"] & NO_EPSILONS:
         cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
     out["rm_epsilon"] = cur["props"]
-    fst = tm.flat_to_fst(cur)
+    fst = model.flat_to_fst(cur)
     tr_sum(fst)
     out["tr_sum"] = fst["props"]
     encoded = not flat["props"] & ACCEPTOR
     if encoded:
         encode_labels(fst)
         out["encode"] = fst["props"]
-    cur = tm.fst_to_flat(fst)
+    cur = model.fst_to_flat(fst)
     if not cur["props"] & I_DETERMINISTIC:
         cur = norm(determinize_encoded(cur) if encoded else td.determinize_ref(cur))
         out["determinize"] = cur["props"]
@@ -431,18 +355,18 @@ def test_transducer_branch_equals_the_acceptor_steps_on_pair_ids(oracle):
             rows.append(row)
             finals.append(float(rng.integers(0, 2)) if rng.random() < 0.3 or s == n - 1 else INF)
         acc = rows_flat(rows, finals)
-        acc["props"] = content_word(acc)
+        acc["props"] = content_word_of_flat(acc)
         tra = rows_flat([[pair(il) + (w, t) for il, _, w, t in r] for r in rows], finals)
-        tra["props"] = content_word(tra)
+        tra["props"] = content_word_of_flat(tra)
         assert not tra["props"] & ACCEPTOR and tra["props"] & ACYCLIC and tra["props"] & NO_EPSILONS
         assert branch_of(tra, oracle) == "encode" and branch_of(acc, oracle) == "det-min"
         got = optimize_ref(tra, oracle)
-        fst = tm.flat_to_fst(norm(acc))
+        fst = model.flat_to_fst(norm(acc))
         tr_sum(fst)
-        assert tm.fst_to_flat(fst)["arcs"].tolist() == norm(acc)["arcs"].tolist()
-        mini = tm.flat_to_fst(det_min(tm.fst_to_flat(fst), False))
+        assert model.fst_to_flat(fst)["arcs"].tolist() == norm(acc)["arcs"].tolist()
+        mini = model.flat_to_fst(det_min(model.fst_to_flat(fst), False))
         decode_labels(mini, [pair(i) for i in range(1, next_id)])
-        assert_flat_identical(got, tm.fst_to_flat(mini), f"case {case}", check_props=False)
+        assert_flat_identical(got, model.fst_to_flat(mini), f"case {case}", check_props=False)
 
 
 def test_tr_sum_is_idempotent_and_keeps_duplicate_free_rows():

@@ -15,14 +15,16 @@ import re
 import numpy as np
 import pytest
 
-import test_determinize as td
 import test_minimize as tm
 import test_optimize as to
+from oracle import model
+from oracle.model import (ACCEPTOR, ACYCLIC, INF, I_DETERMINISTIC, NOT_I_DETERMINISTIC, NO_EPSILONS,
+                          content_word_of_flat, rows_flat)
+import helpers
 from helpers import assert_flat_identical, to_device
-from test_optimize import (ACCEPTOR, ACYCLIC, I_DETERMINISTIC, INF, MSG_ACYCLIC, NO_EPSILONS, NOT_I_DETERMINISTIC, branch_of,
-                           content_word, optimize_input, optimize_ref, rows_flat)
+from test_optimize import MSG_ACYCLIC, branch_of, optimize_input, optimize_ref
 
-ROOT = td.ROOT
+ROOT = helpers.ROOT
 STAGES = ("rm_epsilon", "tr_sum", "determinize", "minimize")
 SIGNATURES = {
     "wfst_optimize_batch": "wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel",
@@ -55,7 +57,7 @@ def mixed_items():
         out.append((f"transducer {k}", draw(True, k % 2 == 0, eps=(k % 2 == 0)), "trans"))
     out.append(("no start state", dict(optimize_input(rng, 12, False), start=None), "start-less"))
     dead = rows_flat([[(1, 1, 1.0, 1), (1, 1, 2.0, 1), (0, 0, 0.0, 2)], [(2, 2, 0.0, 2)], []] + [[]] * 5, [INF] * 8)
-    out.append(("trims to nothing", dict(dead, props=content_word(dead)), "dead"))
+    out.append(("trims to nothing", dict(dead, props=content_word_of_flat(dead)), "dead"))
     return out
 
 
@@ -77,13 +79,13 @@ def wide_state_acceptor():
     """a deterministic acceptor whose start state has 257 arcs: beyond the tr_sum kernel's rank sort"""
     rows = [[(1 + j, 1 + j, float(j % 3), 1 + j % 7) for j in range(257)]] + [[(1, 1, 1.0, 8)] for _ in range(7)] + [[]]
     f = rows_flat(rows, [INF] * 8 + [0.0])
-    return dict(f, props=content_word(f))
+    return dict(f, props=content_word_of_flat(f))
 
 
 def long_chain(n=4097):
     rows = [[(1 + s % 5, 1 + s % 5, float(s % 3), s + 1)] for s in range(n - 1)] + [[]]
     f = rows_flat(rows, [INF] * (n - 1) + [0.0])
-    return dict(f, props=int(tm.ACCEPTOR | I_DETERMINISTIC | NO_EPSILONS | ACYCLIC | tm.INITIAL_ACYCLIC | tm.WEIGHTED))
+    return dict(f, props=int(model.ACCEPTOR | I_DETERMINISTIC | NO_EPSILONS | ACYCLIC | model.INITIAL_ACYCLIC | model.WEIGHTED))
 
 
 def nondeterministic_acceptor(rng, n):
@@ -121,7 +123,7 @@ def test_new_symbols_declared_exported_and_bound(wfst_lib):
 
 
 def test_argument_validation_without_gpu(wfst_lib):
-    ko = td._ko_message
+    ko = helpers.ko_message
     fn = wfst_lib.wfst_optimize_batch
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
@@ -203,7 +205,7 @@ def _single_message(dev, ctx):
     from rustfst_amd import _lib
     out = C.c_void_p(1)
     assert _lib.lib().wfst_optimize(ctx._h, dev._h, C.byref(out)) == 1 and out.value is None
-    return td._ko_message(1)
+    return helpers.ko_message(1)
 
 
 @pytest.mark.gpu
@@ -250,7 +252,7 @@ def test_k17_as_a_list(gpu_ctx, oracle):
         single = _single_message(dev, gpu_ctx)
         assert c["error"] in single
         status, outs = _raw_batch(devs + [dev], gpu_ctx)
-        assert status == 1 and td._ko_message(1) == "item %d: %s" % (len(devs), single), c["name"]
+        assert status == 1 and helpers.ko_message(1) == "item %d: %s" % (len(devs), single), c["name"]
         assert outs == [None] * (len(devs) + 1)
     again, _ = _batch(devs, gpu_ctx)
     for c, g in zip(good, again):
@@ -299,7 +301,7 @@ def test_ko_is_the_loop_of_single_calls(gpu_ctx):
     good, _ = _batch(devs, gpu_ctx)
     nd = nondeterministic_acceptor(rng, 12)
     no_acyclic = to_device(dict(nd, props=nd["props"] & ~ACYCLIC), gpu_ctx)  # KO on the word after tr_sum
-    word = tm.ACCEPTOR | I_DETERMINISTIC | NO_EPSILONS
+    word = model.ACCEPTOR | I_DETERMINISTIC | NO_EPSILONS
     lying = to_device(two_state_cycle(word | ACYCLIC), gpu_ctx)  # its word sends it to minimize, which finds the cycle
     silent = to_device(two_state_cycle(word), gpu_ctx)           # ... and here minimize has to look for itself
     assert _single_message(no_acyclic, gpu_ctx) == MSG_ACYCLIC
@@ -308,7 +310,7 @@ def test_ko_is_the_loop_of_single_calls(gpu_ctx):
 
     def check(listed, want):
         status, outs = _raw_batch(listed, gpu_ctx)
-        assert status == 1 and td._ko_message(1) == want
+        assert status == 1 and helpers.ko_message(1) == want
         assert outs == [None] * len(listed)
         for k, (g, e) in enumerate(zip(_batch(devs, gpu_ctx)[0], good)):  # a following valid call succeeds
             same(g, e, f"item {k} after the KO '{want}'")
@@ -321,12 +323,12 @@ def test_ko_is_the_loop_of_single_calls(gpu_ctx):
     check(devs[:2] + [silent] + devs[3:5] + [no_acyclic] + devs[6:], "item 2: " + silent_msg)
     # the argument checks come first
     status, outs = _raw_batch(devs[:5] + [no_acyclic, None] + devs[7:], gpu_ctx)
-    assert status == 1 and td._ko_message(1) == "item 6: null FST in batch" and outs == [None] * 8
+    assert status == 1 and helpers.ko_message(1) == "item 6: null FST in batch" and outs == [None] * 8
     import rustfst_amd
     other = rustfst_amd.Context(0)
     foreign = to_device(goods[3], other)
     status, outs = _raw_batch(devs[:3] + [foreign] + devs[4:], gpu_ctx)
-    msg = td._ko_message(status)
+    msg = helpers.ko_message(status)
     assert msg == "item 3: optimize_batch: the FST belongs to another context" and outs == [None] * 8
     assert _stats(gpu_ctx) == dict(launches=dict.fromkeys(STAGES, 0), items_in_kernel=0, items_single=0, items_transducer=0)
     del foreign

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import random_fst_flat, to_oracle
+from helpers import flat_matches_spec, random_fst_flat, to_oracle
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -28,26 +28,6 @@ def build(oracle, spec):
 def load_golden(name):
     with open(os.path.join(GOLDEN, name)) as fh:
         return json.load(fh)
-
-
-def flat_matches_spec(flat, spec):
-    assert flat["n_states"] == spec["n_states"]
-    assert flat["start"] == spec.get("start")
-    got = []
-    for s in range(flat["n_states"]):
-        for a in flat["arcs"][flat["offsets"][s]:flat["offsets"][s + 1]]:
-            got.append([s, int(a["ilabel"]), int(a["olabel"]), float(a["weight"]), int(a["nextstate"])])
-    exp = spec["arcs"]
-    assert len(got) == len(exp)
-    for g, e in zip(got, exp):
-        assert g[:3] == e[:3] and g[4] == e[4], (g, e)
-        assert abs(g[3] - e[3]) <= 1.0 / 1024.0, (g, e)
-    fin = {s: w for s, w in spec["finals"]}
-    for s in range(flat["n_states"]):
-        if s in fin:
-            assert abs(float(flat["finals"][s]) - fin[s]) <= 1.0 / 1024.0
-        else:
-            assert np.isinf(flat["finals"][s])
 
 
 # ---------------------------------------------------------------- K1: test_compose.py:13-81

@@ -25,10 +25,13 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 
 import test_push_weights as tp
-from test_push_weights import assert_same, graph_facts, push_ref, reverse_len_rule, reweight_ref, to_flat
+from test_push_weights import assert_same, push_ref, reverse_len_rule, reweight_ref
+from oracle import model
+from oracle.model import graph_facts, to_flat
+import helpers
 from helpers import to_device, to_oracle
 
-ROOT = tp.ROOT
+ROOT = helpers.ROOT
 F32, INF = np.float32, np.float32(np.inf)
 COUNTERS = ("searches", "rounds", "reads", "rounds_max", "bfs_blocks", "arcs_blocks", "total_blocks", "structural",
             "start_branch", "removed")
@@ -274,15 +277,15 @@ def empty_after(off, nxt, frontier, mark, peel):
 def reversed_graph(flat):
     """reverse(f) as the searches see it: n + 1 states, 0 -> s + 1 for every final s, t + 1 -> s + 1 for every arc s -> t"""
     n = flat["n_states"]
-    off, nxt = tp._csr_next(flat)
-    roff, rsrc = tp._transpose(n, off, nxt)
+    off, nxt = model.csr_next(flat)
+    roff, rsrc = model.transpose(n, off, nxt)
     fin = np.nonzero(np.isfinite(flat["finals"]))[0]
     return n + 1, np.r_[0, roff + fin.size], np.r_[fin + 1, rsrc + 1]
 
 
 def search_forward_len(flat):
     n, s0 = flat["n_states"], flat["start"]
-    off, nxt = tp._csr_next(flat)
+    off, nxt = model.csr_next(flat)
     mark = np.zeros(n, dtype=np.int64)
     mark[s0] = 1
     return n, empty_after(off, nxt, [s0], mark, False)
@@ -299,7 +302,7 @@ def searches_structural(flat):
     """the four searches of structural_bits: from the start, from state 0 of the reversed FST, the peeling, and from the
     start with the start left unvisited"""
     n, s0 = flat["n_states"], flat["start"]
-    off, nxt = tp._csr_next(flat)
+    off, nxt = model.csr_next(flat)
     indeg = np.bincount(nxt, minlength=n).astype(np.int64)
     return [search_forward_len(flat), search_reverse_len(flat),
             (n, empty_after(off, nxt, np.nonzero(indeg == 0)[0], indeg, True)),
@@ -319,17 +322,17 @@ def total_weight(flat, dist, to_final):
     if not to_final:
         s0 = flat["start"]
         return F32(dist[s0]) if s0 is not None and s0 < len(dist) else INF
-    return min([INF] + [tp.times(d, f) for d, f in zip(dist, flat["finals"]) if np.isfinite(f)])
+    return min([INF] + [model.times(d, f) for d, f in zip(dist, flat["finals"]) if np.isfinite(f)])
 
 
 def start_branch_of(flat, pot, facts):
     """0 not taken, 1 in place, 2 new start state; and whether the four facts have to be searched"""
     s0 = flat["start"]
     d = F32(pot[s0]) if s0 is not None and s0 < len(pot) else INF
-    if s0 is None or tp.is_one(d) or tp.is_zero(d):
+    if s0 is None or model.is_one(d) or model.is_zero(d):
         return 0, False
-    known = flat["props"] & (tp.INITIAL_CYCLIC | tp.INITIAL_ACYCLIC)
-    cyclic = bool(flat["props"] & tp.INITIAL_CYCLIC) if known else facts[3]
+    known = flat["props"] & (model.INITIAL_CYCLIC | model.INITIAL_ACYCLIC)
+    cyclic = bool(flat["props"] & model.INITIAL_CYCLIC) if known else facts[3]
     return (2 if cyclic else 1), not known
 
 
@@ -348,7 +351,7 @@ def expected_counters(flat, call, pot, facts, cap=None):
         exp["arcs_blocks"] = blocks((n + 15) // 16) if len(flat["arcs"]) else 0
         if call[0] == "push" and call[2]:
             t = total_weight(flat, pot, call[1] == 1)
-            exp["removed"] = 1 if tp.is_one(t) or tp.is_zero(t) else 2
+            exp["removed"] = 1 if model.is_one(t) or model.is_zero(t) else 2
             exp["total_blocks"] = blocks((n + 255) // 256) if call[1] == 1 else 0
     if exp["bfs_blocks"]:
         exp["bfs_blocks"] = blocks(exp["bfs_blocks"])
@@ -397,8 +400,8 @@ def restate(oracle, flat, call, facts):
     if call[0] == "len":
         if call[1]:
             return reverse_len_rule(flat), None
-        off, nxt = tp._csr_next(flat)
-        return int(np.nonzero(tp._reach(flat["n_states"], off, nxt, [flat["start"]]))[0].max()) + 1, None
+        off, nxt = model.csr_next(flat)
+        return int(np.nonzero(model.reach(flat["n_states"], off, nxt, [flat["start"]]))[0].max()) + 1, None
     if call[0] == "reweight":
         return to_flat(reweight_ref(flat, list(call[2]), call[1] == 1, facts)), call[2]
     dist = oracle_dist(oracle, flat, call[1] == 1)
@@ -409,7 +412,7 @@ def dfs_facts(oracle, flat):
     """the two references of the structural facts, which must agree before anything else is asked"""
     facts = graph_facts(flat)
     word = to_oracle(oracle, flat).dfs_properties()
-    assert word == tp.dfs_bits(facts), f"graph_facts {facts} but the oracle's DFS says {word:#x}"
+    assert word == model.dfs_bits(facts), f"graph_facts {facts} but the oracle's DFS says {word:#x}"
     return facts
 
 
@@ -466,15 +469,15 @@ def decider(mid, total):
     best = None
     for s, f in enumerate(mid["finals"]):
         if f is not None:
-            new = tp.divide(f, total)
-            if tp.weighted(f) or tp.weighted(new):
-                best = (s, tp.weighted(new))
+            new = model.divide(f, total)
+            if model.weighted(f) or model.weighted(new):
+                best = (s, model.weighted(new))
     return best
 
 
 # facts of the word that reweight_marks may clear: NOT_STRING and NOT_COACCESSIBLE go with any set_final, and with an arc
 # through set_weight_unchecked everything but the arc-relevant bits
-FACTS_WORD = tp.NOT_STRING | tp.NOT_COACCESSIBLE | tp.ACCESSIBLE | tp.ACYCLIC | tp.INITIAL_ACYCLIC | tp.I_LABEL_SORTED
+FACTS_WORD = model.NOT_STRING | model.NOT_COACCESSIBLE | model.ACCESSIBLE | model.ACYCLIC | model.INITIAL_ACYCLIC | model.I_LABEL_SORTED
 
 
 def facts_cases(n, seed=71):
@@ -531,7 +534,7 @@ def test_symbol_declared_and_bound(wfst_lib):
 def test_null_ctx_is_ko(wfst_lib):
     v = C.c_uint64(5)
     args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in tp._ko_message(wfst_lib.wfst_ctx_get_push_stats(None, *args))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_push_stats(None, *args))
     assert v.value == 5
 
 
@@ -588,15 +591,15 @@ def test_knob_validation_without_gpu(wfst_lib, monkeypatch):
     for value in BAD_KNOB:
         monkeypatch.setenv(KNOB, value)
         for name, call in _entry_points(wfst_lib):
-            msg = tp._ko_message(call())
+            msg = helpers.ko_message(call())
             assert KNOB in msg and f"'{value}'" in msg, (name, value, msg)
     for value in GOOD_KNOB:
         monkeypatch.setenv(KNOB, value)
         for name, call in _entry_points(wfst_lib):
-            assert "null" in tp._ko_message(call()), (name, value)
+            assert "null" in helpers.ko_message(call()), (name, value)
     monkeypatch.delenv(KNOB)
     for name, call in _entry_points(wfst_lib):
-        assert "null" in tp._ko_message(call()), name
+        assert "null" in helpers.ko_message(call()), name
 
 
 def test_restatement_agrees_with_the_oracle_dfs(oracle):
@@ -610,7 +613,7 @@ def test_restatement_agrees_with_the_oracle_dfs(oracle):
         assert {f[i] for f in seen} == {True, False}, f"fact {i} is never {'true' if seen else 'false'}"
     # without a start state nothing is visited
     none = dict(case("ladder:cyclic"), start=None)
-    assert to_oracle(oracle, none).dfs_properties() == tp.dfs_bits((True, True, False, False))
+    assert to_oracle(oracle, none).dfs_properties() == model.dfs_bits((True, True, False, False))
 
 
 def test_generators_reach_every_case(oracle):
@@ -684,7 +687,7 @@ def test_generators_reach_every_case(oracle):
     # (c): widths against the capped grids
     for name in STRIDE_CASES:
         flat = case(name)
-        off, nxt = tp._csr_next(flat)
+        off, nxt = model.csr_next(flat)
         kids = _rows_of(off, nxt, np.array([flat["start"]]))
         assert flat["n_states"] == 401 and kids.size == 100 and _rows_of(off, nxt, kids).size == 300
     assert graph_facts(case("tree:plain"))[2:] == (False, False) and graph_facts(case("tree:back"))[2:] == (True, True)
@@ -697,12 +700,12 @@ def test_generators_reach_every_case(oracle):
             src = np.repeat(np.arange(n), np.diff(flat["offsets"].astype(np.int64)))
             assert np.all(flat["arcs"]["nextstate"] > src), name
             dist = oracle_dist(oracle, flat, True)
-            sums = [tp.times(d, f) for d, f in zip(dist, flat["finals"])] + [INF] * (n - len(dist))
+            sums = [model.times(d, f) for d, f in zip(dist, flat["finals"])] + [INF] * (n - len(dist))
             total = total_weight(flat, dist, True)
             mid = reweight_ref(flat, dist, True, graph_facts(flat))
             out = push_ref(flat, dist, True, True, graph_facts(flat))
             dec = decider(mid, total)
-            removed = not (tp.is_one(total) or tp.is_zero(total))
+            removed = not (model.is_one(total) or model.is_zero(total))
             if what in ("total_pos", "total_neg"):
                 assert [s for s in range(n) if sums[s] == total] == [a] and removed, name
                 assert (total > 0) == (what == "total_pos") and abs(total) > 0.5, (name, total)
@@ -716,11 +719,11 @@ def test_generators_reach_every_case(oracle):
             else:
                 assert removed and dec is not None and dec[0] == b, (name, dec)
                 assert dec[1] == (what == "decider_weighted"), (name, dec)
-                assert bool(out["props"] & tp.WEIGHTED) == dec[1], name
+                assert bool(out["props"] & model.WEIGHTED) == dec[1], name
                 above = [s for s in range(b + 1, n) if np.isfinite(flat["finals"][s])]
                 assert above or b == n - 1, name  # final states above the decider: their weights are zero before and after
                 if what == "decider_one" and b >= 64:  # another wave would have said WEIGHTED
-                    assert any(f is not None and tp.weighted(tp.divide(f, total)) for f in mid["finals"][:64]), name
+                    assert any(f is not None and model.weighted(model.divide(f, total)) for f in mid["finals"][:64]), name
             want[what] += 1
             for rt in (0, 1):
                 st = expected_counters(flat, ("push", rt, True), dist if rt else oracle_dist(oracle, flat, False),
@@ -790,8 +793,8 @@ def check_call(gpu_ctx, oracle, flat, dev, call, facts, what, cap=None):
 def check_structural(gpu_ctx, oracle, flat, dev, facts, what, cap=None):
     """the device's four facts, as far as a reweight result shows them: the start branch follows INITIAL_CYCLIC, and every
     DFS pair that survives the later masks carries the fact"""
-    pairs = ((tp.ACCESSIBLE, tp.NOT_ACCESSIBLE), (tp.COACCESSIBLE, tp.NOT_COACCESSIBLE), (tp.CYCLIC, tp.ACYCLIC),
-             (tp.INITIAL_CYCLIC, tp.INITIAL_ACYCLIC))
+    pairs = ((model.ACCESSIBLE, model.NOT_ACCESSIBLE), (model.COACCESSIBLE, model.NOT_COACCESSIBLE), (model.CYCLIC, model.ACYCLIC),
+             (model.INITIAL_CYCLIC, model.INITIAL_ACYCLIC))
     for call in structural_calls(flat):
         got, stats = check_call(gpu_ctx, oracle, flat, dev, call, facts, what, cap)
         assert stats["structural"] == 1 and stats["searches"] == 4, what
@@ -818,9 +821,9 @@ def test_row_ladder(gpu_ctx, oracle, monkeypatch, name):
     check_case(gpu_ctx, oracle, name)
     if name == "ladder:isolated":  # the pairs the searches found are in the word: a lost arc of the peeling would say CYCLIC
         dev = to_device(case(name), gpu_ctx)
-        pairs = tp.CYCLIC | tp.ACYCLIC | tp.ACCESSIBLE | tp.NOT_ACCESSIBLE | tp.INITIAL_CYCLIC | tp.INITIAL_ACYCLIC
+        pairs = model.CYCLIC | model.ACYCLIC | model.ACCESSIBLE | model.NOT_ACCESSIBLE | model.INITIAL_CYCLIC | model.INITIAL_ACYCLIC
         for call in structural_calls(case(name)):
-            assert run_call(dev, call)["props"] & pairs == tp.ACYCLIC | tp.NOT_ACCESSIBLE | tp.INITIAL_ACYCLIC
+            assert run_call(dev, call)["props"] & pairs == model.ACYCLIC | model.NOT_ACCESSIBLE | model.INITIAL_ACYCLIC
 
 
 @pytest.mark.gpu
@@ -903,7 +906,7 @@ def test_reductions_across_waves_and_blocks(gpu_ctx, oracle, monkeypatch, n):
         assert st["removed"] == (1 if what in ("total_one", "total_zero") else 2), name
         assert st["total_blocks"] == (n + 255) // 256
         if what.startswith("decider"):
-            assert bool(got["props"] & tp.WEIGHTED) == (what == "decider_weighted"), name
+            assert bool(got["props"] & model.WEIGHTED) == (what == "decider_weighted"), name
         check_call(gpu_ctx, oracle, flat, dev, ("push", 0, True), facts, name)
     for what, flat, pot in facts_cases(n):
         facts = dfs_facts(oracle, flat)
@@ -931,20 +934,20 @@ def test_counters_on_refusal_and_reuse(gpu_ctx, oracle, monkeypatch):
         assert gpu_ctx.push_stats()["searches"] == 4
         return dev
     dev = fresh()
-    assert "reweight_type" in tp._ko_message(lib.wfst_reweight(gpu_ctx._h, dev._h, None, 0, 2, C.byref(out)))
+    assert "reweight_type" in helpers.ko_message(lib.wfst_reweight(gpu_ctx._h, dev._h, None, 0, 2, C.byref(out)))
     assert gpu_ctx.push_stats() == zero
     dev = fresh()
-    assert "potentials" in tp._ko_message(lib.wfst_reweight(gpu_ctx._h, dev._h, None, 3, 0, C.byref(out)))
+    assert "potentials" in helpers.ko_message(lib.wfst_reweight(gpu_ctx._h, dev._h, None, 3, 0, C.byref(out)))
     assert gpu_ctx.push_stats() == zero
     dev = fresh()
-    assert "reweight_type" in tp._ko_message(lib.wfst_push_weights(gpu_ctx._h, dev._h, 7, None, C.byref(out)))
+    assert "reweight_type" in helpers.ko_message(lib.wfst_push_weights(gpu_ctx._h, dev._h, 7, None, C.byref(out)))
     assert gpu_ctx.push_stats() == zero
     dev = fresh()
     cfg = _lib.ShortestDistanceConfig(1, float("nan"))
-    assert "delta" in tp._ko_message(lib.wfst_shortest_distance_with_config(gpu_ctx._h, dev._h, C.byref(cfg), None, None))
+    assert "delta" in helpers.ko_message(lib.wfst_shortest_distance_with_config(gpu_ctx._h, dev._h, C.byref(cfg), None, None))
     assert gpu_ctx.push_stats() == zero
     dev = fresh()
-    assert "null" in tp._ko_message(lib.wfst_reweight(gpu_ctx._h, None, None, 0, 0, C.byref(out)))
+    assert "null" in helpers.ko_message(lib.wfst_reweight(gpu_ctx._h, None, None, 0, 0, C.byref(out)))
     assert gpu_ctx.push_stats() == zero
     for value in BAD_KNOB[:4]:
         dev = fresh()

@@ -14,187 +14,14 @@ import pytest
 from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
 
-from helpers import random_fst_flat, to_device, to_oracle
+from oracle.model import (ACCESSIBLE, ACYCLIC, ALL, ARC_RELEVANT, COACCESSIBLE, CYCLIC, DFS_BITS, F32, INF,
+                          INITIAL_ACYCLIC, INITIAL_CYCLIC, NOT_ACCESSIBLE, WEIGHT_INVARIANT, csr_next, dfs_bits, divide,
+                          graph_facts, is_one, is_zero, p_add_state, p_add_tr, p_set_final, p_set_start, p_set_weight,
+                          reach, times, to_flat, transpose)
+from helpers import ROOT, ko_message, random_fst_flat, to_device, to_oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k14_push.json")
 NEW_SYMBOLS = ("wfst_shortest_distance_with_config", "wfst_push_weights", "wfst_reweight")
-
-# ---------------------------------------------------------------- property bits (fst_properties/properties.rs:22-103)
-B = dict(ACCEPTOR=16, NOT_ACCEPTOR=17, I_DETERMINISTIC=18, NOT_I_DETERMINISTIC=19, O_DETERMINISTIC=20,
-         NOT_O_DETERMINISTIC=21, EPSILONS=22, NO_EPSILONS=23, I_EPSILONS=24, NO_I_EPSILONS=25, O_EPSILONS=26,
-         NO_O_EPSILONS=27, I_LABEL_SORTED=28, NOT_I_LABEL_SORTED=29, O_LABEL_SORTED=30, NOT_O_LABEL_SORTED=31,
-         WEIGHTED=32, UNWEIGHTED=33, CYCLIC=34, ACYCLIC=35, INITIAL_CYCLIC=36, INITIAL_ACYCLIC=37, TOP_SORTED=38,
-         NOT_TOP_SORTED=39, ACCESSIBLE=40, NOT_ACCESSIBLE=41, COACCESSIBLE=42, NOT_COACCESSIBLE=43, STRING=44,
-         NOT_STRING=45, WEIGHTED_CYCLES=46, UNWEIGHTED_CYCLES=47)
-globals().update({k: 1 << v for k, v in B.items()})
-
-
-def _m(*names):
-    return sum(1 << B[n] for n in names)
-
-
-LABEL_BITS = ("ACCEPTOR", "NOT_ACCEPTOR", "I_DETERMINISTIC", "NOT_I_DETERMINISTIC", "O_DETERMINISTIC",
-              "NOT_O_DETERMINISTIC", "EPSILONS", "NO_EPSILONS", "I_EPSILONS", "NO_I_EPSILONS", "O_EPSILONS",
-              "NO_O_EPSILONS", "I_LABEL_SORTED", "NOT_I_LABEL_SORTED", "O_LABEL_SORTED", "NOT_O_LABEL_SORTED")
-# properties.rs:166-300 / 436-465
-SET_START_MASK = _m(*LABEL_BITS, "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC", "TOP_SORTED", "NOT_TOP_SORTED",
-                    "COACCESSIBLE", "NOT_COACCESSIBLE", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-SET_FINAL_MASK = _m(*LABEL_BITS, "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
-                    "NOT_TOP_SORTED", "ACCESSIBLE", "NOT_ACCESSIBLE", "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-ADD_STATE_MASK = _m(*LABEL_BITS, "WEIGHTED", "UNWEIGHTED", "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC",
-                    "TOP_SORTED", "NOT_TOP_SORTED", "NOT_ACCESSIBLE", "NOT_COACCESSIBLE", "NOT_STRING",
-                    "WEIGHTED_CYCLES", "UNWEIGHTED_CYCLES")
-ADD_ARC_MASK = _m("NOT_ACCEPTOR", "NOT_I_DETERMINISTIC", "NOT_O_DETERMINISTIC", "EPSILONS", "I_EPSILONS", "O_EPSILONS",
-                  "NOT_I_LABEL_SORTED", "NOT_O_LABEL_SORTED", "WEIGHTED", "CYCLIC", "INITIAL_CYCLIC", "NOT_TOP_SORTED",
-                  "ACCESSIBLE", "COACCESSIBLE", "WEIGHTED_CYCLES")
-ARC_RELEVANT = _m("ACCEPTOR", "NOT_ACCEPTOR", "EPSILONS", "NO_EPSILONS", "I_EPSILONS", "NO_I_EPSILONS", "O_EPSILONS",
-                  "NO_O_EPSILONS", "WEIGHTED", "UNWEIGHTED")
-WEIGHT_INVARIANT = _m(*LABEL_BITS, "CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "TOP_SORTED",
-                      "NOT_TOP_SORTED", "ACCESSIBLE", "NOT_ACCESSIBLE", "COACCESSIBLE", "NOT_COACCESSIBLE", "STRING",
-                      "NOT_STRING")
-DFS_BITS = _m("CYCLIC", "ACYCLIC", "INITIAL_CYCLIC", "INITIAL_ACYCLIC", "ACCESSIBLE", "NOT_ACCESSIBLE", "COACCESSIBLE",
-              "NOT_COACCESSIBLE")
-ALL = 0x0000FFFFFFFF0000
-
-# ---------------------------------------------------------------- TropicalWeight (tropical_weight.rs, semiring.rs)
-F32, INF = np.float32, np.float32(np.inf)
-KDELTA = F32(1.0 / 1024.0)
-
-
-def times(a, b):  # tropical_weight.rs:60-70
-    a, b = F32(a), F32(b)
-    return a if a == INF else (b if b == INF else F32(a + b))
-
-
-def divide(a, b):  # tropical_weight.rs:128-131: plain a - b
-    with np.errstate(invalid="ignore"):
-        return F32(F32(a) - F32(b))
-
-
-def approx_eq(a, b):  # semiring.rs:159-168
-    return bool(F32(a) <= F32(F32(b) + KDELTA) and F32(b) <= F32(F32(a) + KDELTA))
-
-
-def is_zero(w):
-    return approx_eq(w, INF)
-
-
-def is_one(w):
-    return approx_eq(w, 0.0)
-
-
-def weighted(w):
-    return not is_zero(w) and not is_one(w)
-
-
-# ---------------------------------------------------------------- mutate_properties.rs / trs_iter_mut.rs
-def p_set_final(p, old, new):  # mutate_properties.rs:15-37 (None = no final weight)
-    if old is not None and weighted(old):
-        p &= ~WEIGHTED
-    if new is not None and weighted(new):
-        p = (p | WEIGHTED) & ~UNWEIGHTED
-    return p & (SET_FINAL_MASK | WEIGHTED | UNWEIGHTED)
-
-
-def p_set_weight(p, old, new):  # trs_iter_mut.rs:279-305, 342-350
-    if weighted(old):
-        p &= ~WEIGHTED
-    if weighted(new):
-        p = (p | WEIGHTED) & ~UNWEIGHTED
-    return p & ARC_RELEVANT
-
-
-def p_add_state(p):  # :39-41
-    return p & ADD_STATE_MASK
-
-
-def p_add_tr(p, state, il, ol, w, ns):  # :43-100 (the new state has no previous arc)
-    if il != ol:
-        p = (p | NOT_ACCEPTOR) & ~ACCEPTOR
-    if il == 0:
-        p = (p | I_EPSILONS) & ~NO_I_EPSILONS
-        if ol == 0:
-            p = (p | EPSILONS) & ~NO_EPSILONS
-    if ol == 0:
-        p = (p | O_EPSILONS) & ~NO_O_EPSILONS
-    if weighted(w):
-        p = (p | WEIGHTED) & ~UNWEIGHTED
-    if ns <= state:
-        p = (p | NOT_TOP_SORTED) & ~TOP_SORTED
-    p &= ADD_ARC_MASK | ACCEPTOR | NO_EPSILONS | NO_I_EPSILONS | NO_O_EPSILONS | I_LABEL_SORTED | O_LABEL_SORTED | \
-        UNWEIGHTED | TOP_SORTED
-    if p & TOP_SORTED:
-        p |= ACYCLIC | INITIAL_ACYCLIC
-    return p
-
-
-def p_set_start(p):  # :7-13
-    out = p & SET_START_MASK
-    if p & ACYCLIC:
-        out |= INITIAL_ACYCLIC
-    return out
-
-
-# ---------------------------------------------------------------- graph facts (what SccVisitor's DFS decides)
-def _csr_next(flat):
-    return np.asarray(flat["offsets"], dtype=np.int64), np.asarray(flat["arcs"]["nextstate"], dtype=np.int64)
-
-
-def _reach(n, off, nxt, seeds, mark_seeds=True):
-    """states reachable from `seeds` (vectorised frontier search); the seeds count only when mark_seeds"""
-    vis = np.zeros(n, dtype=bool)
-    fr = np.asarray(seeds, dtype=np.int64)
-    if mark_seeds:
-        vis[fr] = True
-    while fr.size:
-        cnt = off[fr + 1] - off[fr]
-        idx = np.repeat(off[fr] - np.cumsum(np.r_[0, cnt[:-1]]), cnt) + np.arange(cnt.sum())
-        t = np.unique(nxt[idx])
-        t = t[~vis[t]]
-        vis[t] = True
-        fr = t
-    return vis
-
-
-def _transpose(n, off, nxt):
-    src = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
-    order = np.argsort(nxt, kind="stable")
-    roff = np.zeros(n + 1, dtype=np.int64)
-    np.add.at(roff, nxt + 1, 1)
-    return np.cumsum(roff), src[order]
-
-
-def graph_facts(flat):
-    """(accessible, coaccessible, cyclic, initial_cyclic) of the graph: every state reachable from the start, every state
-    reaches a final state, a cycle anywhere, the start on a cycle — the four DFS pairs compute_fst_properties fills in
-    (visitors/scc_visitors.rs: a new DFS tree for an unreachable state, back arcs, back arcs into the start, SCCs without
-    a final state)."""
-    n, s0 = flat["n_states"], flat["start"]
-    off, nxt = _csr_next(flat)
-    accessible = bool(_reach(n, off, nxt, [s0]).all())
-    roff, rsrc = _transpose(n, off, nxt)
-    finals = np.nonzero(np.isfinite(flat["finals"]))[0]
-    coaccessible = bool(_reach(n, roff, rsrc, finals).all()) if finals.size else n == 0
-    indeg = np.bincount(nxt, minlength=n)
-    fr, removed = np.nonzero(indeg == 0)[0], 0
-    while fr.size:
-        removed += fr.size
-        cnt = off[fr + 1] - off[fr]
-        idx = np.repeat(off[fr] - np.cumsum(np.r_[0, cnt[:-1]]), cnt) + np.arange(cnt.sum())
-        t = nxt[idx]
-        np.subtract.at(indeg, t, 1)
-        t = np.unique(t)
-        fr = t[indeg[t] == 0]
-    cyclic = removed != n
-    initial_cyclic = bool(_reach(n, off, nxt, nxt[off[s0]:off[s0 + 1]])[s0])
-    return accessible, coaccessible, cyclic, initial_cyclic
-
-
-def dfs_bits(facts):
-    a, c, cy, ic = facts
-    return (ACCESSIBLE if a else NOT_ACCESSIBLE) | (COACCESSIBLE if c else NOT_COACCESSIBLE) | \
-        (CYCLIC if cy else ACYCLIC) | (INITIAL_CYCLIC if ic else INITIAL_ACYCLIC)
 
 
 # ---------------------------------------------------------------- restatement of reweight.rs / push.rs
@@ -264,7 +91,7 @@ def reweight_ref(flat, potentials, to_final, facts=None):
                 finals.append(None)
                 p = p_add_state(p)
                 w = divide(0.0, d_s) if to_final else d_s
-                p = p_add_tr(p, s, 0, 0, w, start)
+                p = p_add_tr(p, s, (0, 0, w, start))
                 rows[s].append([0, 0, w, start])
                 p = p_set_start(p)
                 fst["start"] = s
@@ -316,27 +143,16 @@ def push_ref(flat, dist, to_final, remove_total=False, facts=None):
     return fst
 
 
-def to_flat(fst):
-    """restatement output -> flat arrays as the device stores them (+inf = None: Some(zero) reads as not final)"""
-    rows = fst["rows"]
-    off = np.zeros(fst["n_states"] + 1, dtype=np.uint32)
-    off[1:] = np.cumsum([len(r) for r in rows]) if rows else []
-    arcs = np.array([tuple(a) for r in rows for a in r], dtype=TR_DTYPE) if off[-1] else np.zeros(0, dtype=TR_DTYPE)
-    finals = np.array([INF if f is None else f for f in fst["finals"]], dtype=np.float32)
-    return dict(n_states=fst["n_states"], start=fst["start"], offsets=off, arcs=arcs, finals=finals,
-                props=fst["props"] & ALL)
-
-
 def reverse_len_rule(flat):
     """rdistance.len() - 1 (shortest_distance.rs:322-334): the reversed search dequeues every state reachable from the
     super-initial state (the states that reach a final state, + 1) and grows its Vec to the largest of them."""
     n = flat["n_states"]
-    off, nxt = _csr_next(flat)
-    roff, rsrc = _transpose(n, off, nxt)
+    off, nxt = csr_next(flat)
+    roff, rsrc = transpose(n, off, nxt)
     finals = np.nonzero(np.isfinite(flat["finals"]))[0]
     if not finals.size:
         return 0
-    return int(np.nonzero(_reach(n, roff, rsrc, finals))[0].max()) + 1
+    return int(np.nonzero(reach(n, roff, rsrc, finals))[0].max()) + 1
 
 
 def assert_same(got, exp, what):
@@ -392,30 +208,20 @@ def test_config_structs_match_the_header():
     assert _lib.PushWeightsConfig.delta.offset == 0 and _lib.PushWeightsConfig.remove_total_weight.offset == 4
 
 
-def _ko_message(status):
-    from rustfst_amd import _lib
-    assert status == 1
-    msg = C.c_char_p()
-    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
-    text = msg.value.decode()
-    _lib.lib().wfst_string_destroy(msg)
-    return text
-
-
 def test_argument_validation_without_gpu(wfst_lib):
     from rustfst_amd import _lib
     out = C.c_void_p()
-    assert "reweight_type" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 2, C.byref(out)))
-    assert "potentials" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 3, 0, C.byref(out)))
-    assert "reweight_type" in _ko_message(wfst_lib.wfst_push_weights(None, None, 7, None, C.byref(out)))
+    assert "reweight_type" in ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 2, C.byref(out)))
+    assert "potentials" in ko_message(wfst_lib.wfst_reweight(None, None, None, 3, 0, C.byref(out)))
+    assert "reweight_type" in ko_message(wfst_lib.wfst_push_weights(None, None, 7, None, C.byref(out)))
     bad = _lib.PushWeightsConfig(-1.0, 0)
-    assert "delta" in _ko_message(wfst_lib.wfst_push_weights(None, None, 0, C.byref(bad), C.byref(out)))
+    assert "delta" in ko_message(wfst_lib.wfst_push_weights(None, None, 0, C.byref(bad), C.byref(out)))
     for d in (-1e-3, float("nan"), float("inf")):
         cfg = _lib.ShortestDistanceConfig(1, d)
-        assert "delta" in _ko_message(wfst_lib.wfst_shortest_distance_with_config(None, None, C.byref(cfg), None, None))
+        assert "delta" in ko_message(wfst_lib.wfst_shortest_distance_with_config(None, None, C.byref(cfg), None, None))
     assert out.value is None
     # valid arguments, no handles: the usual null-pointer KO, nothing dereferenced
-    assert "null" in _ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 1, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_reweight(None, None, None, 0, 1, C.byref(out)))
 
 
 def test_python_surface():
@@ -486,8 +292,8 @@ def test_reverse_distances_match_the_oracle(gpu_ctx, oracle, shape):
         # forward: unchanged, and its length is 1 + the largest reachable id
         fwd, fl = dev.shortest_distance_with_len()
         np.testing.assert_array_equal(fwd.view(np.uint32), dev.shortest_distance().view(np.uint32))
-        off, nxt = _csr_next(flat)
-        assert fl == int(np.nonzero(_reach(n, off, nxt, [0]))[0].max()) + 1
+        off, nxt = csr_next(flat)
+        assert fl == int(np.nonzero(reach(n, off, nxt, [0]))[0].max()) + 1
 
 
 @pytest.mark.gpu
@@ -541,8 +347,8 @@ def _oracle_dist(oracle, flat, to_final):
         if flat["start"] is None:
             return []
         n = flat["n_states"]
-        off, nxt = _csr_next(flat)
-        ln = int(np.nonzero(_reach(n, off, nxt, [flat["start"]]))[0].max()) + 1
+        off, nxt = csr_next(flat)
+        ln = int(np.nonzero(reach(n, off, nxt, [flat["start"]]))[0].max()) + 1
         return list(o.shortest_distance()[:ln])
     return list(o.reverse().shortest_distance()[1:][:reverse_len_rule(flat)])
 
@@ -574,10 +380,10 @@ def test_push_invariants(gpu_ctx, oracle):
         pushed = dev.push_weights(rustfst_amd.ReweightType.REWEIGHT_TO_INITIAL).to_flat()
         # every coaccessible state but the start: min(out-arc weights, final weight) is exactly 0
         n = flat["n_states"]
-        off, nxt = _csr_next(flat)
-        roff, rsrc = _transpose(n, off, nxt)
+        off, nxt = csr_next(flat)
+        roff, rsrc = transpose(n, off, nxt)
         fin = np.nonzero(np.isfinite(flat["finals"]))[0]
-        coacc = _reach(n, roff, rsrc, fin) if fin.size else np.zeros(n, dtype=bool)
+        coacc = reach(n, roff, rsrc, fin) if fin.size else np.zeros(n, dtype=bool)
         po, pa, pf = pushed["offsets"], pushed["arcs"], pushed["finals"]
         for s in np.nonzero(coacc)[0]:
             if s == pushed["start"] or s == flat["start"]:
@@ -703,7 +509,7 @@ def _push_to_initial_numpy(flat, dist, facts):
         if not (p & (INITIAL_CYCLIC | INITIAL_ACYCLIC)):
             p = (p & ~DFS_BITS) | dfs_bits(facts)
         assert not p & INITIAL_ACYCLIC  # (T: arc 0 of every state runs round a ring)
-        p = p_set_start(p_add_tr(p_add_state(p), n, 0, 0, ds0, s0))
+        p = p_set_start(p_add_tr(p_add_state(p), n, (0, 0, ds0, s0)))
         out["n_states"], out["start"] = n + 1, n
         out["offsets"] = np.r_[flat["offsets"], flat["offsets"][-1] + 1].astype(np.uint32)
         out["arcs"] = np.r_[arcs, np.array([(0, 0, ds0, s0)], dtype=TR_DTYPE)]

@@ -6,7 +6,7 @@ the closed forms of the list folds checked against the literal folds, and on the
 restatement: states, offsets, arcs (weights by bit pattern), finals, start state and property word.
 
 The restatement reuses the per-mutation property functions, the DFS facts and the flat <-> fst conversions of
-test_minimize.py / test_push_weights.py.
+oracle/model/props.py and oracle/model/fst.py.
 
 Shapes of the list tests, and why: the copy kernel covers the concatenation of all items' states (and arcs) with tiles of
 TILE = 256 elements, one lane per element, and finds a lane's item between the first items of two neighbouring tiles.  So
@@ -22,14 +22,12 @@ import re
 import numpy as np
 import pytest
 
-from helpers import assert_flat_identical, enumerate_paths, to_device
+from oracle import model
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, B, COACCESSIBLE, EPSILONS, INITIAL_ACYCLIC, I_EPSILONS,
+                          O_EPSILONS, closure_properties, compute_initial_acyclic, concat_properties, content_word,
+                          fst_to_flat, m_add_state, m_add_tr, m_set_final, m_set_props, m_set_start, union_properties)
+from helpers import assert_flat_identical, enumerate_paths, ko_message, to_device
 import test_minimize as tm
-import test_push_weights as pw
-from test_minimize import dfs_facts, fst_to_flat, flat_to_fst, known, p_add_tr
-from test_push_weights import (ACCEPTOR, NOT_ACCEPTOR, NOT_I_DETERMINISTIC, NOT_O_DETERMINISTIC, EPSILONS, I_EPSILONS,  # noqa: F401
-                               O_EPSILONS, NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, WEIGHTED, UNWEIGHTED, CYCLIC, ACYCLIC,
-                               INITIAL_CYCLIC, INITIAL_ACYCLIC, NOT_TOP_SORTED, ACCESSIBLE, NOT_ACCESSIBLE, COACCESSIBLE,
-                               NOT_COACCESSIBLE, NOT_STRING, WEIGHTED_CYCLES, UNWEIGHTED_CYCLES, ALL, B)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k18_rational.json")
@@ -39,97 +37,6 @@ ONE = F32(0.0)
 TILE = 256  # rustfst_amd/csrc/rational.hip
 STAR, PLUS = 0, 1  # closure/mod.rs:9-12
 MAX_STATES, MAX_ARCS = 2 ** 31 - 2, 2 ** 32 - 1
-
-
-# ---------------------------------------------------------------- the restatement: property functions
-# what both operands hand on (mutate_properties.rs:207-220, 717-729)
-NEGATIVE = NOT_ACCEPTOR | NOT_I_DETERMINISTIC | NOT_O_DETERMINISTIC | EPSILONS | I_EPSILONS | O_EPSILONS | NOT_I_LABEL_SORTED | \
-    NOT_O_LABEL_SORTED | WEIGHTED | WEIGHTED_CYCLES | CYCLIC | NOT_ACCESSIBLE
-
-
-def closure_properties(p):  # mutate_properties.rs:114-145, delayed = false
-    out = (ACCEPTOR | UNWEIGHTED | ACCESSIBLE) & p
-    if p & UNWEIGHTED:
-        out |= UNWEIGHTED_CYCLES
-    out |= (COACCESSIBLE | NOT_TOP_SORTED | NOT_STRING) & p
-    out |= (NOT_ACCEPTOR | NOT_I_DETERMINISTIC | NOT_O_DETERMINISTIC | NOT_I_LABEL_SORTED | NOT_O_LABEL_SORTED | WEIGHTED |
-            WEIGHTED_CYCLES | NOT_ACCESSIBLE | NOT_COACCESSIBLE) & p
-    if p & WEIGHTED and p & ACCESSIBLE and p & COACCESSIBLE:
-        out |= WEIGHTED_CYCLES
-    return out
-
-
-def concat_properties(p1, p2):  # mutate_properties.rs:186-245, delayed = false
-    out = (ACCEPTOR | UNWEIGHTED | UNWEIGHTED_CYCLES | ACYCLIC) & p1 & p2
-    out |= (NOT_TOP_SORTED | NOT_STRING) & p1
-    out |= (NOT_TOP_SORTED | NOT_STRING) & p2
-    out |= (INITIAL_ACYCLIC | INITIAL_CYCLIC) & p1
-    out |= (NEGATIVE | NOT_COACCESSIBLE) & p1
-    if p1 & ACCESSIBLE and p1 & COACCESSIBLE:
-        out |= ACCESSIBLE & p2
-        out |= COACCESSIBLE & p2
-        out |= (NEGATIVE | NOT_COACCESSIBLE) & p2
-    return out
-
-
-def union_properties(p1, p2):  # mutate_properties.rs:692-748, delayed = false
-    out = (ACCEPTOR | UNWEIGHTED | UNWEIGHTED_CYCLES | ACYCLIC | ACCESSIBLE) & p1 & p2
-    out |= INITIAL_ACYCLIC
-    out |= NOT_TOP_SORTED & p1
-    out |= NOT_TOP_SORTED & p2
-    out |= EPSILONS | I_EPSILONS | O_EPSILONS
-    out |= COACCESSIBLE & p1 & p2
-    out |= NEGATIVE & p1
-    out |= (NEGATIVE | NOT_COACCESSIBLE) & p2
-    return out
-
-
-def dfs_facts_ref(fst):
-    """the SccVisitor's facts; without a start state dfs_visit returns before it visits anything (dfs_visit.rs:104-110),
-    which leaves the visitor's initial word: all four positive bits"""
-    if fst["start"] is None:
-        return True, True, False, False
-    return dfs_facts(fst)
-
-
-def compute_initial_acyclic(fst):
-    """compute_and_update_properties(INITIAL_ACYCLIC) (fst_traits/mutable_fst.rs:435-441, compute_fst_properties.rs:13-58)"""
-    p = fst["props"]
-    if known(p) & INITIAL_ACYCLIC:  # use_stored
-        return bool(p & INITIAL_ACYCLIC)
-    comp = pw.dfs_bits(dfs_facts_ref(fst))
-    k = known(comp)
-    fst["props"] = (p & ~k) | (comp & k)
-    return bool(comp & INITIAL_ACYCLIC)
-
-
-# ---------------------------------------------------------------- the restatement: VectorFst mutations (vector_fst/mutable_fst.rs)
-def m_add_state(f):  # :80-85
-    f["rows"].append([])
-    f["finals"].append(None)
-    f["props"] = pw.p_add_state(f["props"])
-    return len(f["rows"]) - 1
-
-
-def m_set_final(f, s, w):  # :66-78; w None = delete_final_weight_unchecked (:293-297)
-    f["props"] = pw.p_set_final(f["props"], f["finals"][s], w)
-    f["finals"][s] = w
-
-
-def m_add_tr(f, s, tr):  # :247-252, data_structure.rs:80-91
-    row = f["rows"][s]
-    prev = row[-1] if row else None
-    row.append(list(tr))
-    f["props"] = p_add_tr(f["props"], s, tr, prev)
-
-
-def m_set_start(f, s):  # :46-49
-    f["start"] = s
-    f["props"] = pw.p_set_start(f["props"])
-
-
-def m_set_props(f, props, mask=ALL):  # :411-414
-    f["props"] = (f["props"] & ~mask) | (props & mask)
 
 
 # ---------------------------------------------------------------- the restatement: the three algorithms, in place on fst_1
@@ -290,19 +197,12 @@ def run_ref(op, args, closure_type=None):
     return fold_ref(union_ref if op == "union_list" else concat_ref, args)
 
 
-def content_word(fst):
-    """the word compute_fst_properties finds on the content: every trinary pair known"""
-    f = dict(copy.deepcopy(fst), props=0)
-    tm.compute_and_update(f, ALL)
-    return f["props"]
-
-
 SHAPES = ("empty", "no_start", "one_state", "start_last", "start_no_arcs", "start_self_loop", "start_cycle3",
           "unreachable_into_start", "all_final", "none_final")
 
 
 def shape_fst(name, rng):
-    """one operand of the pair tests.  Arcs on cycles carry weight one or zero (test_minimize's compute_and_update does not
+    """one operand of the pair tests.  Arcs on cycles carry weight one or zero (oracle.model's compute_and_update does not
     restate the SCC test of WEIGHTED_CYCLES); final weights and the arcs of the acyclic shapes are weighted."""
     def lab():
         return int(rng.integers(0, 4))
@@ -387,29 +287,19 @@ def test_tile_constant_is_the_kernels():
     assert m and int(m.group(1)) == TILE
 
 
-def _ko_message(status):
-    from rustfst_amd import _lib
-    assert status == 1
-    msg = C.c_char_p()
-    assert _lib.lib().wfst_last_error(C.byref(msg)) == 0
-    text = msg.value.decode()
-    _lib.lib().wfst_string_destroy(msg)
-    return text
-
-
 def test_argument_validation_without_gpu(wfst_lib):
     out = C.c_void_p(1)
-    assert "null" in _ko_message(wfst_lib.wfst_union(None, None, None, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_union(None, None, None, C.byref(out)))
     assert out.value is None
-    assert "null" in _ko_message(wfst_lib.wfst_concat(None, None, None, C.byref(out)))
-    assert "null" in _ko_message(wfst_lib.wfst_closure(None, None, 0, C.byref(out)))
-    assert "closure_type" in _ko_message(wfst_lib.wfst_closure(None, None, 2, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_concat(None, None, None, C.byref(out)))
+    assert "null" in ko_message(wfst_lib.wfst_closure(None, None, 0, C.byref(out)))
+    assert "closure_type" in ko_message(wfst_lib.wfst_closure(None, None, 2, C.byref(out)))
     arr = (C.c_void_p * 2)()
     for fn in (wfst_lib.wfst_union_list, wfst_lib.wfst_concat_list):
-        assert _ko_message(fn(None, arr, 0, C.byref(out))) == "fsts must be at least of len 1"
-        assert "null" in _ko_message(fn(None, arr, 2, C.byref(out)))
-        assert "null" in _ko_message(fn(None, None, 2, C.byref(out)))
-        assert "null" in _ko_message(fn(None, arr, 2, None))
+        assert ko_message(fn(None, arr, 0, C.byref(out))) == "fsts must be at least of len 1"
+        assert "null" in ko_message(fn(None, arr, 2, C.byref(out)))
+        assert "null" in ko_message(fn(None, None, 2, C.byref(out)))
+        assert "null" in ko_message(fn(None, arr, 2, None))
 
 
 def _check_sizes(lib, op, states, arcs):
@@ -424,26 +314,26 @@ def test_overflow_guard_on_bare_counts(wfst_lib):
     assert _check_sizes(wfst_lib, 0, [1000, 2000], [5000, 7000]) == 0
     # union: states
     assert _check_sizes(wfst_lib, 0, [MAX_STATES - 10, 9], [5, 5]) == 0                 # + the new start state: the limit
-    msg = _ko_message(_check_sizes(wfst_lib, 0, [MAX_STATES - 10, 10], [5, 5]))
+    msg = ko_message(_check_sizes(wfst_lib, 0, [MAX_STATES - 10, 10], [5, 5]))
     assert msg == f"union: result too large: up to {MAX_STATES + 1} states, the limit is {MAX_STATES}"
     # union: arcs, + n
     assert _check_sizes(wfst_lib, 0, [10, 10], [2 ** 31, 2 ** 31 - 3]) == 0
-    msg = _ko_message(_check_sizes(wfst_lib, 0, [10, 10], [2 ** 31, 2 ** 31 - 2]))
+    msg = ko_message(_check_sizes(wfst_lib, 0, [10, 10], [2 ** 31, 2 ** 31 - 2]))
     assert msg == f"union: result too large: up to {MAX_ARCS + 1} arcs, the limit is {MAX_ARCS}"
     assert _check_sizes(wfst_lib, 0, [1, 1, 1], [2 ** 31, 2 ** 31 - 4, 0]) == 0
-    assert "arcs" in _ko_message(_check_sizes(wfst_lib, 0, [1, 1, 1], [2 ** 31, 2 ** 31 - 3, 0]))
+    assert "arcs" in ko_message(_check_sizes(wfst_lib, 0, [1, 1, 1], [2 ** 31, 2 ** 31 - 3, 0]))
     # concat: the last operand's states append nothing
     assert _check_sizes(wfst_lib, 1, [10, 1000], [2 ** 31, 2 ** 31 - 11]) == 0
-    msg = _ko_message(_check_sizes(wfst_lib, 1, [10, 1000], [2 ** 31, 2 ** 31 - 10]))
+    msg = ko_message(_check_sizes(wfst_lib, 1, [10, 1000], [2 ** 31, 2 ** 31 - 10]))
     assert msg == f"concat: result too large: up to {MAX_ARCS + 1} arcs, the limit is {MAX_ARCS}"
     assert _check_sizes(wfst_lib, 1, [2 ** 30, 2 ** 30 - 2], [0, 0]) == 0
-    assert "states" in _ko_message(_check_sizes(wfst_lib, 1, [2 ** 30, 2 ** 30 - 1], [0, 0]))
+    assert "states" in ko_message(_check_sizes(wfst_lib, 1, [2 ** 30, 2 ** 30 - 1], [0, 0]))
     # closure: star adds a state and an arc
     assert _check_sizes(wfst_lib, 3, [MAX_STATES], [5]) == 0
-    assert "closure: result too large" in _ko_message(_check_sizes(wfst_lib, 2, [MAX_STATES], [5]))
+    assert "closure: result too large" in ko_message(_check_sizes(wfst_lib, 2, [MAX_STATES], [5]))
     assert _check_sizes(wfst_lib, 3, [100], [MAX_ARCS - 100]) == 0
-    assert "arcs" in _ko_message(_check_sizes(wfst_lib, 2, [100], [MAX_ARCS - 100]))
-    assert "arcs" in _ko_message(_check_sizes(wfst_lib, 3, [100], [MAX_ARCS - 99]))
+    assert "arcs" in ko_message(_check_sizes(wfst_lib, 2, [100], [MAX_ARCS - 100]))
+    assert "arcs" in ko_message(_check_sizes(wfst_lib, 3, [100], [MAX_ARCS - 99]))
     assert _check_sizes(wfst_lib, 0, [5, 5], [5, 5]) == 0                               # and the library works afterwards
 
 
@@ -499,7 +389,7 @@ def test_the_reference_test_words_are_the_incremental_ones():
     g = golden()
     for name in ("ref_union_1", "ref_union_2", "ref_concat_2"):
         m = golden_fst(g["machines"][name])
-        f = dict(rows=[], finals=[], start=None, props=tm.NULL_PROPS)
+        f = dict(rows=[], finals=[], start=None, props=model.NULL_PROPS)
         for _ in m["rows"]:
             m_add_state(f)
         m_set_start(f, m["start"])
@@ -721,7 +611,7 @@ def test_union_of_nbest_paths_then_optimize(gpu_ctx, oracle):
     assert_flat_identical(union.to_flat(), union_flat, "union_list(n-best)", check_props=True)
     # optimize straight away is KO here as in the restatement: union_properties never holds TOP_SORTED, and without it the
     # set_trs bookkeeping of rm_epsilon (rm_epsilon_static.rs:148-167) drops ACYCLIC, which wfst_optimize's step 4 needs
-    with pytest.raises(to.Unsupported, match=re.escape(to.MSG_ACYCLIC)):
+    with pytest.raises(model.Unsupported, match=re.escape(to.MSG_ACYCLIC)):
         to.optimize_ref(union_flat, oracle)
     with pytest.raises(rustfst_amd.WfstError, match=re.escape(to.MSG_ACYCLIC)):
         union.optimize()
@@ -746,7 +636,7 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx):
         return f._h.value if isinstance(f._h, C.c_void_p) else f._h
     arr = (C.c_void_p * 3)(raw(a), None, raw(b))
     for fn in (L.wfst_union_list, L.wfst_concat_list):
-        assert "item 1: null FST in list" in _ko_message(fn(gpu_ctx._h, arr, 3, C.byref(out)))
+        assert "item 1: null FST in list" in ko_message(fn(gpu_ctx._h, arr, 3, C.byref(out)))
         assert out.value is None
     other = rustfst_amd.Context(0)
     foreign = dev(string3(), other)
@@ -757,7 +647,7 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx):
     with pytest.raises(rustfst_amd.WfstError, match="closure_type"):
         check = _lib.check
         check(L.wfst_closure(gpu_ctx._h, a._h, 7, C.byref(out)))
-    assert "result too large" in _ko_message(_check_sizes(L, 0, [MAX_STATES, 1], [1, 1]))
+    assert "result too large" in ko_message(_check_sizes(L, 0, [MAX_STATES, 1], [1, 1]))
     # ... and the same context, the same handles, a successful call
     exp = fst_to_flat(union_ref(string3(), string3(1.5)))
     assert_flat_identical(a.union(b).to_flat(), exp, "union after the KOs", check_props=True)

@@ -20,12 +20,11 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 from rustfst_amd import synth as P
 
-import test_determinize as td
+from oracle.model import F32, INF
+import helpers
 from helpers import assert_flat_identical, random_fst_flat, to_device, to_oracle
 
-ROOT = td.ROOT
-INF = np.float32(np.inf)
-f32 = np.float32
+ROOT = helpers.ROOT
 
 # The retry ladder of rm_epsilon_fst, restated once (rustfst_amd/csrc/rm_epsilon.hip, the attempt loop of rm_epsilon_fst:
 # `RmCaps caps{16, 32, 32}`, `RmBigCaps big{1024, 1024, 1024}`, `const bool wave = caps.C > 64`, every size times 4 per
@@ -68,11 +67,11 @@ def _rewrite(cur, finals, s):
         else:
             post.append(q)
     d = {q: INF for q in post}
-    d[s] = f32(0.0)
+    d[s] = F32(0.0)
     for q in reversed(post):
         for il, ol, w, ns in cur[q]:
             if il == 0 and ol == 0:
-                cand = f32(d[q] + w)
+                cand = F32(d[q] + w)
                 if cand < d[ns]:
                     d[ns] = cand
     # the explicit-stack depth-first walk: pop, mark, push the unvisited epsilon targets in arc order
@@ -83,7 +82,7 @@ def _rewrite(cur, finals, s):
             continue
         visited.add(q)
         for il, ol, w, ns in cur[q]:
-            w = f32(d[q] + w)
+            w = F32(d[q] + w)
             if il == 0 and ol == 0:
                 if ns not in visited:
                     walk.append(ns)
@@ -95,7 +94,7 @@ def _rewrite(cur, finals, s):
             else:
                 index[(il, ol, ns)] = len(out)
                 out.append((il, ol, w, ns))
-        fq = f32(d[q] + finals[q])
+        fq = F32(d[q] + finals[q])
         fw = fq if fq < fw else fw
     out.reverse()
     return out, fw, (len(d), k_max, len(out))
@@ -124,9 +123,9 @@ def rm_epsilon_model(flat):
     if start is None or start < 0:
         return flat, {}, dict.fromkeys(STAT_KEYS, 0)
     off, arcs = flat["offsets"], flat["arcs"]
-    cur = [[(int(a["ilabel"]), int(a["olabel"]), f32(a["weight"]), int(a["nextstate"])) for a in arcs[off[s]:off[s + 1]]]
+    cur = [[(int(a["ilabel"]), int(a["olabel"]), F32(a["weight"]), int(a["nextstate"])) for a in arcs[off[s]:off[s + 1]]]
            for s in range(n)]
-    finals = [f32(x) for x in flat["finals"]]
+    finals = [F32(x) for x in flat["finals"]]
     noneps_in = [False] * n
     noneps_in[start] = True
     for trs in cur:
@@ -559,9 +558,9 @@ def test_stats_symbol_declared_exported_and_bound(wfst_lib):
 
 
 def test_stats_null_context_is_ko(wfst_lib):
-    assert "null" in td._ko_message(wfst_lib.wfst_ctx_get_rm_epsilon_stats(None, None, None, None, None, None, None))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_rm_epsilon_stats(None, None, None, None, None, None, None))
     vals = [C.c_uint64(7) for _ in STAT_KEYS]
-    assert "null" in td._ko_message(wfst_lib.wfst_ctx_get_rm_epsilon_stats(None, *[C.byref(v) for v in vals]))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_rm_epsilon_stats(None, *[C.byref(v) for v in vals]))
     assert [v.value for v in vals] == [7] * len(STAT_KEYS)
 
 

@@ -20,10 +20,12 @@ from rustfst_amd._lib import TR_DTYPE
 
 import test_determinize as td
 import test_rm_epsilon as tre
+from oracle.model import ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, INITIAL_ACYCLIC, fst_to_flat
+import helpers
 from helpers import assert_flat_identical, enumerate_paths, random_fst_flat, to_device, to_oracle
 from test_rm_epsilon import Builder, chain, fan, par, rm_epsilon_model, wide
 
-ROOT = td.ROOT
+ROOT = helpers.ROOT
 INF = np.float32(np.inf)
 MAX_STATES, MAX_ARCS = 4096, 16384  # include/wfst.h: the in_kernel rule of wfst_rm_epsilon_batch
 CAPS = tre.THREAD_RUNGS[-1]         # ... and the last rung of the single call's one-thread kernel
@@ -155,7 +157,7 @@ def nbest_union_flat():
     import test_minimize as tm
     import test_rational_ops as tro
     rng = np.random.default_rng(1806)
-    word = tro.ACCEPTOR | tro.ACYCLIC | tro.INITIAL_ACYCLIC | tro.ACCESSIBLE | tro.COACCESSIBLE
+    word = ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | ACCESSIBLE | COACCESSIBLE
     lattice = tm.random_dag(rng, 12, 4)
     paths = sorted(enumerate_paths(lattice))[:5]
     strings = []
@@ -163,7 +165,7 @@ def nbest_union_flat():
         il = list(il) or [1]
         rows = [[[x, x, w if i == 0 else 0.0, i + 1]] for i, x in enumerate(il)] + [[]]
         strings.append(tro.make_fst(rows, [None] * len(il) + [0.0], 0, word))
-    return tro.fst_to_flat(tro.fold_ref(tro.union_ref, strings))
+    return fst_to_flat(tro.fold_ref(tro.union_ref, strings))
 
 
 @functools.lru_cache(maxsize=None)
@@ -231,7 +233,7 @@ def test_new_symbols_declared_exported_and_bound(wfst_lib):
 
 
 def test_argument_validation_without_gpu(wfst_lib):
-    ko = td._ko_message
+    ko = helpers.ko_message
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
     assert wfst_lib.wfst_rm_epsilon_batch(None, None, 0, None, None) == 0  # n == 0: OK
@@ -251,7 +253,7 @@ def test_null_entry_is_ko_before_the_context_is_used(wfst_lib):
     ctx = C.create_string_buffer(1 << 20)
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
-    msg = td._ko_message(wfst_lib.wfst_rm_epsilon_batch(C.cast(ctx, C.c_void_p), fsts, 3, outs, None))
+    msg = helpers.ko_message(wfst_lib.wfst_rm_epsilon_batch(C.cast(ctx, C.c_void_p), fsts, 3, outs, None))
     assert msg == "item 0: null FST in batch" and [outs[i] for i in range(3)] == [None] * 3
     assert ctx.raw == bytes(1 << 20)
 
@@ -320,7 +322,7 @@ def chain_lattices():
 def test_chain_lattices_have_epsilons_and_stay_in_the_kernel():
     lats = chain_lattices()
     assert len(lats) == 32 and all(predict_in_kernel(f) for f in lats)
-    assert all(((f["arcs"]["ilabel"] == 0) & (f["arcs"]["olabel"] == 0)).any() and f["props"] & td.ACCEPTOR for f in lats)
+    assert all(((f["arcs"]["ilabel"] == 0) & (f["arcs"]["olabel"] == 0)).any() and f["props"] & ACCEPTOR for f in lats)
 
 
 # ================================================================ GPU
@@ -459,7 +461,7 @@ def test_errors(gpu_ctx, oracle):
     hs = [d._h.value for d in devs]
     # a NULL entry: the message carries the index
     status, outs = _raw_batch(hs[:5] + [None] + hs[6:], gpu_ctx)
-    assert status == 1 and td._ko_message(1) == "item 5: null FST in batch"
+    assert status == 1 and helpers.ko_message(1) == "item 5: null FST in batch"
     assert [outs[i] for i in range(12)] == [None] * 12
     assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)
     for g, e in zip(_batch(devs, gpu_ctx)[0], good):
@@ -468,7 +470,7 @@ def test_errors(gpu_ctx, oracle):
     other = rustfst_amd.Context(0)
     foreign = to_device(items[3][1], other)
     status, outs = _raw_batch(hs[:3] + [foreign._h.value] + hs[4:], gpu_ctx)
-    msg = td._ko_message(status)
+    msg = helpers.ko_message(status)
     assert "item 3" in msg and "another context" in msg
     assert [outs[i] for i in range(12)] == [None] * 12
     assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)

@@ -19,11 +19,11 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 from rustfst_amd import synth
 
-import test_determinize as td
+import helpers
 from helpers import (NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, assert_flat_identical, check_nbest_against_brute_force,
                      enumerate_paths, to_device, to_oracle)
 
-ROOT = td.ROOT
+ROOT = helpers.ROOT
 INF = float("inf")
 # ---- the limits of nbest_batch.hip, restated (include/wfst.h states them in numbers)
 SP1_MAX_STATES, SP1_MAX_ARCS, SP1_LONE_ARCS = 4096, 16384, 2048
@@ -467,7 +467,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
 
 def test_null_ctx_is_ko(wfst_lib):
     v = C.c_uint64(5)
-    assert "null" in td._ko_message(wfst_lib.wfst_ctx_get_small_path_stats(None, C.byref(v), None, None, None, None, None, None))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_small_path_stats(None, C.byref(v), None, None, None, None, None, None))
     assert v.value == 5
 
 

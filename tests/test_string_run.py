@@ -14,6 +14,7 @@ import pytest
 from rustfst_amd import synth
 
 import test_compose_limits as cl
+import helpers
 from helpers import to_device
 
 INF = float("inf")
@@ -175,7 +176,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
     import rustfst_amd
     from rustfst_amd import _lib
     name = "wfst_ctx_get_string_run_stats"
-    with open(os.path.join(cl.ROOT, "include", "wfst.h")) as f:
+    with open(os.path.join(helpers.ROOT, "include", "wfst.h")) as f:
         header = f.read()
     m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
     assert m and " ".join(m.group(1).split()) == "wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs"

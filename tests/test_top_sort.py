@@ -16,14 +16,14 @@ import re
 import numpy as np
 import pytest
 
-from helpers import assert_flat_identical, enumerate_paths, to_device
+from oracle import model
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ALL, COACCESSIBLE, CYCLIC, INITIAL_ACYCLIC, NOT_STRING,
+                          NOT_TOP_SORTED, STRING, TOP_SORTED, fst_to_flat)
+import helpers
+from helpers import ROOT, assert_flat_identical, enumerate_paths
 import test_minimize as tm
 import test_rational_ops as tr
-from test_minimize import fst_to_flat
-from test_push_weights import (ACCEPTOR, ACYCLIC, INITIAL_ACYCLIC, TOP_SORTED, NOT_TOP_SORTED, CYCLIC, STRING, NOT_STRING,
-                               ACCESSIBLE, COACCESSIBLE, ALL)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k19_top_sort.json")
 NEW_SYMBOLS = ("wfst_state_sort", "wfst_top_sort", "wfst_ctx_get_top_sort_stats")
 STATESORT_MASK = ALL & ~(TOP_SORTED | NOT_TOP_SORTED | STRING | NOT_STRING)  # properties.rs:319-348
@@ -181,14 +181,14 @@ def test_symbols_declared_and_bound(wfst_lib):
 def test_argument_validation_without_gpu(wfst_lib):
     out = C.c_void_p(1)
     order = (C.c_uint32 * 2)(1, 0)
-    assert "null" in tr._ko_message(wfst_lib.wfst_top_sort(None, None, C.byref(out)))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_top_sort(None, None, C.byref(out)))
     assert out.value is None
     out = C.c_void_p(1)
-    assert "null" in tr._ko_message(wfst_lib.wfst_state_sort(None, None, order, 2, C.byref(out)))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_state_sort(None, None, order, 2, C.byref(out)))
     assert out.value is None
-    assert "null" in tr._ko_message(wfst_lib.wfst_top_sort(None, None, None))
-    assert "null" in tr._ko_message(wfst_lib.wfst_state_sort(None, None, order, 2, None))
-    assert "null" in tr._ko_message(wfst_lib.wfst_ctx_get_top_sort_stats(None, *[None] * 10))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_top_sort(None, None, None))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_state_sort(None, None, order, 2, None))
+    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_top_sort_stats(None, *[None] * 10))
 
 
 def test_python_surface():
@@ -286,9 +286,9 @@ def test_random_dags_against_the_restatement(gpu_ctx, word, where):
         n = int(rng.integers(1, 60)) if i else 1
         m = random_dag(rng, n, start={"start_0": 0, "start_last": n - 1, "start_middle": n // 2}[where])
         if word == "content_word":
-            m["props"] = tr.content_word(m)
+            m["props"] = model.content_word(m)
         elif word == "stale_cyclic":
-            m["props"] = (tr.content_word(m) & ~(ACYCLIC | INITIAL_ACYCLIC)) | CYCLIC
+            m["props"] = (model.content_word(m) & ~(ACYCLIC | INITIAL_ACYCLIC)) | CYCLIC
         exp = top_sort_ref(m)
         h = tr.dev(m, gpu_ctx)
         before = h.to_flat()
@@ -323,7 +323,7 @@ def test_state_sort_cases(gpu_ctx):
     rng = np.random.default_rng(1904)
     for n in (1, 2, 7, 300, 1000):
         m = tr.chain(n, rng, fan=3, start=int(rng.integers(0, n))) if n > 1 else tr.make_fst([[]], [0.5], 0)
-        m["props"] = tr.content_word(m)
+        m["props"] = model.content_word(m)
         h = tr.dev(m, gpu_ctx)
         for name, order in (("random", rng.permutation(n).tolist()), ("identity", list(range(n)))):
             exp = state_sort_ref(copy.deepcopy(m), order)
@@ -350,10 +350,10 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, monkeypatch):
     h = tr.dev(diamond, gpu_ctx)
     out = C.c_void_p(1)
     order = (C.c_uint32 * 3)(0, 1, 2)
-    assert tr._ko_message(L.wfst_state_sort(gpu_ctx._h, h._h, order, 3, C.byref(out))) == "StateSort : Bad order vector size : 3. Expected 4"
+    assert helpers.ko_message(L.wfst_state_sort(gpu_ctx._h, h._h, order, 3, C.byref(out))) == "StateSort : Bad order vector size : 3. Expected 4"
     assert out.value is None
-    assert "null" in tr._ko_message(L.wfst_state_sort(gpu_ctx._h, h._h, None, 4, C.byref(out)))
-    assert "null" in tr._ko_message(L.wfst_top_sort(gpu_ctx._h, h._h, None))
+    assert "null" in helpers.ko_message(L.wfst_state_sort(gpu_ctx._h, h._h, None, 4, C.byref(out)))
+    assert "null" in helpers.ko_message(L.wfst_top_sort(gpu_ctx._h, h._h, None))
     with pytest.raises(rustfst_amd.WfstError, match=re.escape(MSG_PERMUTATION)):
         h.state_sort([0, 1, 1, 3])
     with pytest.raises(rustfst_amd.WfstError, match=re.escape(MSG_PERMUTATION)):

@@ -4,11 +4,10 @@ renamed machine (in the manner of test_handle_state.py: fill a cache, call, obse
 import numpy as np
 import pytest
 
+from oracle.model import ACYCLIC, INITIAL_ACYCLIC, fst_to_flat
 from helpers import assert_flat_identical
 import test_rational_ops as tr
 import test_top_sort as tt
-from test_minimize import fst_to_flat
-from test_push_weights import ACYCLIC, INITIAL_ACYCLIC
 
 
 def _weights(flat):

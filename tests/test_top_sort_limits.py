@@ -22,12 +22,14 @@ import re
 import numpy as np
 import pytest
 
+from oracle import model
+from oracle.model import fst_to_flat
+import helpers
 from helpers import assert_flat_identical
 import test_rational_ops as tr
 import test_top_sort as tt
-from test_minimize import fst_to_flat
 
-ROOT = tt.ROOT
+ROOT = helpers.ROOT
 PATHS = ("auto", "narrow", "wide")
 NARROW_STATES, WAVE_INDEG, WAVE_ROW = 256, 32, 64  # top_sort.hip
 COUNTERS = ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "max_tree_depth", "lift_rows",
@@ -359,7 +361,7 @@ def test_restatement_on_every_shape():
         m = make()
         got = tt.top_sort_ref(m)
         if name.startswith("cyclic_"):
-            assert got["rows"] == m["rows"] and got["props"] == tt.CYCLIC | tt.NOT_TOP_SORTED, name
+            assert got["rows"] == m["rows"] and got["props"] == model.CYCLIC | model.NOT_TOP_SORTED, name
         else:
             assert all(ns > s for s, row in enumerate(got["rows"]) for _, _, _, ns in row), name
 

@@ -15,11 +15,12 @@ import re
 import numpy as np
 import pytest
 
-import test_determinize as td
+from oracle.model import INF, rows_flat
+import helpers
 from helpers import assert_flat_identical, to_device
-from test_optimize import INF, apply_op, part_a_rows, part_b_rows, random_arc_lists, rows_flat
+from test_optimize import apply_op, part_a_rows, part_b_rows, random_arc_lists
 
-ROOT = td.ROOT
+ROOT = helpers.ROOT
 MAX_STATES, MAX_ARCS, RANK_MAX = 4096, 16384, 256  # include/wfst.h: the in_kernel rule
 OPS = ("tr_sum", "tr_unique")
 BATCH_ARGS = "wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel"
@@ -162,7 +163,7 @@ def test_new_symbols_declared_exported_and_bound(wfst_lib):
 
 @pytest.mark.parametrize("name", ["wfst_tr_sum_batch", "wfst_tr_unique_batch"])
 def test_argument_validation_without_gpu(wfst_lib, name):
-    ko = td._ko_message
+    ko = helpers.ko_message
     fn = getattr(wfst_lib, name)
     outs = (C.c_void_p * 3)(1, 1, 1)
     fsts = (C.c_void_p * 3)()
@@ -341,7 +342,7 @@ def test_foreign_handle_is_ko_and_the_context_works_afterwards(gpu_ctx):
             arr = (C.c_void_p * 4)(*handles)
             outs = (C.c_void_p * 4)(1, 1, 1, 1)
             status = getattr(_lib.lib(), fn_name)(gpu_ctx._h, arr, 4, outs, None)
-            assert td._ko_message(status) == text
+            assert helpers.ko_message(status) == text
             assert [outs[i] for i in range(4)] == [None] * 4
             assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)
     del foreign

@@ -20,8 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rustfst_amd  # noqa: E402
 from rustfst_amd import synth  # noqa: E402
 from rustfst_amd._lib import TR_DTYPE  # noqa: E402
-
-ACCEPTOR = 1 << 16
+from oracle.model.props import ACCEPTOR  # noqa: E402
 
 
 def lattice(rng):

@@ -10,7 +10,7 @@ import numpy as np
 import rustfst_amd
 from rustfst_amd import synth
 from oracle import oracle_py
-from test_determinize import diamond_chain, twin_copy  # the inputs the tests use
+from inputs import diamond_chain, twin_copy  # the inputs the tests use
 
 TWIN = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 DIAMONDS = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000

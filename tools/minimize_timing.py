@@ -10,7 +10,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import rustfst_amd
 from rustfst_amd._lib import TR_DTYPE
-from test_minimize import ACCEPTOR, blow_up, closed_form_base, minimize_ref  # the inputs the tests use
+from oracle.model import ACCEPTOR
+from test_minimize import blow_up, closed_form_base, minimize_ref  # the inputs the tests use
 
 STATES = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
 HEIGHTS = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000

@@ -16,8 +16,8 @@ import numpy as np
 import rustfst_amd
 from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
-from test_determinize import diamond_chain  # the input the tests use
-from test_push_weights import ACCEPTOR, ACYCLIC, INITIAL_ACYCLIC, TOP_SORTED, NO_EPSILONS
+from oracle.model import ACCEPTOR, ACYCLIC, INITIAL_ACYCLIC, NO_EPSILONS, TOP_SORTED
+from inputs import diamond_chain  # the input the tests use
 
 T_STATES = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 WIDTH = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000

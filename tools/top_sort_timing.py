@@ -14,7 +14,7 @@ import numpy as np
 import rustfst_amd
 from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
-from test_determinize import diamond_chain  # the input the tests use
+from inputs import diamond_chain  # the input the tests use
 
 WIDE = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 DIAMONDS = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000
