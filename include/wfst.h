@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -438,6 +438,56 @@ wfst_status wfst_concat(wfst_ctx* ctx, const wfst_fst* a, const wfst_fst* b, wfs
 wfst_status wfst_closure(wfst_ctx* ctx, const wfst_fst* f, uint32_t closure_type, wfst_fst** out);
 wfst_status wfst_union_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
 wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** out);
+
+/* ---- replace: fst_replace (rustfst-ffi/src/algorithms/replace.rs) = rustfst::algorithms::replace::replace(fst_list, root,
+ *      epsilon_on_replace) (replace/replace_static.rs:44-58): the recursive transition network over pairs[0..n), expanded from
+ *      the FST whose label is `root`.  *out is a NEW handle equal, bit for bit (state numbering, arc order, labels, weights,
+ *      start, final weights, property word), to what the reference returns; the inputs are left as they are (cached
+ *      transposes, plans and words included).  Only the two-argument options of the reference's FFI exist:
+ *      epsilon_on_replace != 0 makes call arcs 0:0, epsilon_on_replace == 0 makes them ilabel:0; return arcs are 0:0.
+ *      The list  fst_id is the list position.  Of two entries with one label the LAST is the one that is called, and the
+ *              root is the last entry whose label is `root`; the list length n is what a label is compared with for the
+ *              "dense range" of the word.  No entry with label `root` (an empty list included): KO "ReplaceFstImpl: No FST
+ *              corresponding to root label {root} in the input tuple vector".
+ *      States  tuples (call stack, fst_id, state) in the first-touch order of the reference's FIFO search.  A state's arcs:
+ *              first, if the stack is not empty and the state has Some(final weight w), the return arc 0:0/w into the
+ *              caller's (fst_id, nextstate) under the popped stack; then its stored arcs in order.  An arc is a CALL iff its
+ *              olabel is not 0, lies within [least label, greatest label] of the list and is a label of the list; it becomes
+ *              (ilabel or 0):0/weight into the callee's start state under the stack + (this fst_id, the arc's nextstate), or
+ *              is dropped when the callee has no start state.  Every other arc is copied.  A label-0 entry can be the root
+ *              but is never called.  Only states of the root instance (empty stack) are final, with the root's weights.
+ *              A root without a start state: the empty FST with the word of VectorFst::new().
+ *      Word    replace_properties (replace_fst_op.rs:120-186, fst_properties/mutate_properties.rs:496-620) of the inputs'
+ *              STORED words, stored as it is; never computed from the content.  The result is in general NOT label-sorted
+ *              unless the word says so: tr_sort before compose.
+ *      Cycles  the reference does not terminate on a grammar whose expansion reaches a recursive call.  Here such a call is
+ *              KO "replace: cyclic dependency between the FSTs: the reference does not terminate on this input", found when
+ *              a call stack holds more frames than the list has distinct labels; a recursive arc the expansion never reaches is harmless.
+ *      KO before anything is launched: a NULL ctx or out, NULL pairs with n > 0 ("null pointer"), a NULL entry ("item {i}:
+ *      null FST in list"), an entry of another device or context ("replace: item {i} lives on another device" / "belongs
+ *      to another context"), the root error above.  A result beyond what the search's arena can hold (2^31 - 16 states or
+ *      arcs; the reference's own limits are 2^31 - 2 states and 2^32 - 1 arcs) is KO "replace: result too large" or
+ *      "replace: arena overflow after retries" from the driver's overflow path.  A recursive grammar that fans out may reach
+ *      that limit before a stack is deep enough to prove the recursion: it is KO either way, with whichever message comes
+ *      first.  Tropical weights only.
+ *      WFST_REPLACE_PREFIX_SLOTS (tests): slots of the call-stack table at the first attempt, a power of two. ---- */
+typedef struct {
+  uint32_t label;
+  const wfst_fst* fst;
+} wfst_label_fst_pair; /* CLabelFstPair, rustfst-ffi/src/algorithms/replace.rs:11-16 */
+wfst_status wfst_replace(wfst_ctx* ctx, uint32_t root, const wfst_label_fst_pair* pairs, size_t n, uint32_t epsilon_on_replace,
+                         wfst_fst** out);
+/* the last wfst_replace call of ctx (reset when the call begins; all 0 after a KO or an empty result, except the two growth
+ *      counters): levels of the search, states and arcs of the result, distinct non-empty call stacks interned (prefixes), the
+ *      deepest of them (max_depth), call arcs emitted, call arcs dropped for a callee without a start state, return arcs
+ *      emitted, times the search's arena grew (arena_grows), times the expansion ran again with a call-stack table twice
+ *      the size (prefix_reruns), and the level kernels queued over all attempts (level_launches: three per level, the levels
+ *      queued behind the last one included).  The three arc counters are tallied while levels are emitted: a level that did not fit the
+ *      arena and was emitted again counts twice (arena_grows tells; growth AHEAD of a level, the usual kind, does not).
+ *      Any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_replace_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* states, uint64_t* arcs, uint64_t* prefixes,
+                                       uint64_t* max_depth, uint64_t* call_arcs, uint64_t* dropped_calls, uint64_t* return_arcs,
+                                       uint64_t* arena_grows, uint64_t* prefix_reruns, uint64_t* level_launches);
 
 /* ---- state_sort, top_sort: fst_top_sort (rustfst-ffi/src/algorithms/top_sort.rs) = rustfst::algorithms::{state_sort,
  *      top_sort} (state_sort.rs:16-78, top_sort.rs:76-94).  The reference works in place; here a NEW handle is returned and

@@ -28,6 +28,7 @@
 //   union(&mut a, &b) / concat(&mut a, &b)                       union_(a, b) / concat(a, b)                       union_static.rs:55-118, concat_static.rs:53-109
 //   closure(&mut fst, ClosureType)                               closure(fst, ClosureType)                         closure_static.rs:25-73
 //   (rustfst-python union_list / concat_list)                    union_list(fsts) / concat_list(fsts)
+//   replace(fst_list, root, epsilon_on_replace)                  replace(fst_list, root, epsilon_on_replace)       replace/replace_static.rs:44-58
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
@@ -476,6 +477,26 @@ inline VectorFst list_call(const std::vector<VectorFst>& fsts, Call call) {
 }  // namespace detail
 inline VectorFst union_list(const std::vector<VectorFst>& fsts) { return detail::list_call(fsts, wfst_union_list); }
 inline VectorFst concat_list(const std::vector<VectorFst>& fsts) { return detail::list_call(fsts, wfst_concat_list); }
+
+// replace(fst_list, root, epsilon_on_replace) (replace/replace_static.rs:44-58) in one device call (wfst_replace): the
+// recursive transition network over the (label, fst) pairs, expanded from the FST whose label is `root`.  Throws the
+// reference's message when no pair has that label, and on a grammar whose expansion reaches a recursive call (the reference
+// does not terminate there).  A null entry throws the library's "item {i}: null FST in list"; an FST named more than once is
+// uploaded once.
+inline VectorFst replace(const std::vector<std::pair<Label, const VectorFst*>>& fst_list, Label root, bool epsilon_on_replace) {
+  std::vector<detail::DeviceFst> in(fst_list.size());
+  std::vector<wfst_label_fst_pair> pairs(fst_list.size());
+  for (size_t i = 0; i < fst_list.size(); ++i) {
+    if (!fst_list[i].second) throw Error("item " + std::to_string(i) + ": null FST in list");
+    size_t first = 0;
+    while (fst_list[first].second != fst_list[i].second) ++first;
+    if (first == i) detail::upload(*fst_list[i].second, in[i]);
+    pairs[i] = wfst_label_fst_pair{fst_list[i].first, in[first].h};
+  }
+  detail::DeviceFst c;
+  check(wfst_replace(Context::current().get(), root, pairs.data(), pairs.size(), epsilon_on_replace ? 1u : 0u, &c.h));
+  return detail::download(c);
+}
 
 // Look-ahead composition.  The reference has no single function for it: callers assemble MatcherFst::new_with_relabeling,
 // a LabelLookAheadMatcher and the PushLabels(PushWeights(LookAhead(AltSequence))) filter by hand and call compute()

@@ -42,6 +42,10 @@ class MinimizeConfig(C.Structure):
 TIES_UNKNOWN = (1 << 64) - 1  # WFST_TIES_UNKNOWN
 
 
+class LabelFstPair(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("fst", C.c_void_p)]
+
+
 class Stats(C.Structure):
     _fields_ = [("relax_launches", C.c_uint64), ("relax_ms", C.c_double), ("relax_arcs", C.c_uint64),
                 ("relax_states", C.c_uint64), ("sweeps", C.c_uint64), ("compose_states", C.c_uint64),
@@ -131,6 +135,8 @@ SYMBOLS = [
     ("wfst_closure", C.c_int, [_vp, _vp, _u32, _P(_vp)]),
     ("wfst_union_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
     ("wfst_concat_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
+    ("wfst_replace", C.c_int, [_vp, _u32, _P(LabelFstPair), _sz, _u32, _P(_vp)]),
+    ("wfst_ctx_get_replace_stats", C.c_int, [_vp] + [_P(_u64)] * 11),
     ("wfst_rational_check_sizes", C.c_int, [_u32, _vp, _vp, _sz]),
     ("wfst_state_sort", C.c_int, [_vp, _vp, _vp, _sz, _P(_vp)]),
     ("wfst_top_sort", C.c_int, [_vp, _vp, _P(_vp)]),

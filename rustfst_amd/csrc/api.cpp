@@ -760,6 +760,43 @@ wfst_status wfst_concat_list(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t 
     *out = concat_list_fst(ctx, fsts, n);
   });
 }
+// replace (replace/replace_static.rs:44-58, rustfst-ffi/src/algorithms/replace.rs): every argument is checked before anything
+// is launched
+wfst_status wfst_replace(wfst_ctx* ctx, uint32_t root, const wfst_label_fst_pair* pairs, size_t n, uint32_t epsilon_on_replace,
+                         wfst_fst** out) {
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (n && !pairs)) throw Error("null pointer");
+    std::vector<uint32_t> labels(n);
+    std::vector<const wfst_fst*> fsts(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (!pairs[i].fst) throw Error("item " + std::to_string(i) + ": null FST in list");
+      labels[i] = pairs[i].label;
+      fsts[i] = pairs[i].fst;
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = replace_fst(ctx, root, labels.data(), fsts.data(), n, epsilon_on_replace != 0);
+  });
+}
+wfst_status wfst_ctx_get_replace_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* states, uint64_t* arcs, uint64_t* prefixes,
+                                       uint64_t* max_depth, uint64_t* call_arcs, uint64_t* dropped_calls, uint64_t* return_arcs,
+                                       uint64_t* arena_grows, uint64_t* prefix_reruns, uint64_t* level_launches) {
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    const wfst_ctx::ReplaceStats& c = ctx->replace;
+    if (levels) *levels = c.levels;
+    if (states) *states = c.states;
+    if (arcs) *arcs = c.arcs;
+    if (prefixes) *prefixes = c.prefixes;
+    if (max_depth) *max_depth = c.max_depth;
+    if (call_arcs) *call_arcs = c.calls;
+    if (dropped_calls) *dropped_calls = c.dropped;
+    if (return_arcs) *return_arcs = c.returns;
+    if (arena_grows) *arena_grows = c.grows;
+    if (prefix_reruns) *prefix_reruns = c.prefix_reruns;
+    if (level_launches) *level_launches = c.level_launches;
+  });
+}
 wfst_status wfst_rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n) {
   return wrap([&] { rational_check_sizes(op, n_states, n_arcs, n); });
 }

@@ -302,6 +302,12 @@ struct wfst_ctx {
     uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, max_tree_depth = 0;
     uint64_t lift_rows = 0, states_compared = 0, wave_states = 0, cyclic = 0;
   } top_sort;
+  // the last wfst_replace call (wfst_ctx_get_replace_stats): the driver's level and size figures, the counters of
+  // replace.hip's policy block, and the two kinds of growth (the driver's arena in place, the prefix table by a rerun)
+  struct ReplaceStats {
+    uint64_t levels = 0, states = 0, arcs = 0, prefixes = 0, max_depth = 0, calls = 0, dropped = 0, returns = 0;
+    uint64_t grows = 0, prefix_reruns = 0, level_launches = 0;
+  } replace;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   uint64_t rearm_armed = 0, rearm_adopted = 0, rearm_dropped = 0;  // wfst_ctx_get_rearm_stats
@@ -622,6 +628,9 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
 // ... of n acceptors in one call, one workgroup each and one launch for all (new handles; on a throw every outs[i] is null)
 void minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float delta, bool allow_nondet, wfst_fst** outs,
                     uint8_t* in_kernel);
+// replace.hip: replace(fst_list, root, epsilon_on_replace) over (labels[i], fsts[i]) (a NEW handle; the items are left as they are)
+wfst_fst* replace_fst(wfst_ctx* ctx, uint32_t root_label, const uint32_t* labels, const wfst_fst* const* fsts, size_t n,
+                      bool epsilon_on_replace);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,
                        uint64_t out_props, uint64_t est_s);
 }  // namespace wfst

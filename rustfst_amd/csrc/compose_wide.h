@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "common.h"
 
@@ -520,6 +521,7 @@ inline uint32_t wide_next_pow2(uint64_t x) {
 struct WideOutput {
   DBuf<char> arena;
   uint32_t n_states = 0, n_arcs = 0, n_levels = 0;
+  uint64_t n_level_launches = 0;  // la_emit / la_first / la_assign launches queued (levels queued behind the last one included)
   const uint32_t* off = nullptr;
   const wfst_tr* arcs = nullptr;
   const float* fin = nullptr;
@@ -529,6 +531,13 @@ struct WideOutput {
 // table filling up) the arena GROWS (x4, x2 beyond a million states) and the search goes on from that level: the numbered tuples, their
 // segments and final weights are copied, the table is rebuilt from the ids, the level is emitted again — nothing that
 // was finished is redone (restarting from scratch cost up to one full composition per overflow).
+// who runs the driver, for its messages and its growth count: the two compositions by default; another policy names itself
+// and the counter its arena's growths go to
+struct WideWho {
+  const char* op = "compose";
+  const char* result = "composition";
+  uint64_t* grows = nullptr;  // null: wfst_stats::compose_retries
+};
 struct WideBuffers {
   DBuf<char> arena;
   WideArena ar{};
@@ -536,8 +545,8 @@ struct WideBuffers {
   wfst_tr* d_out = nullptr;
   LaCaps caps{};
 };
-inline void wide_alloc(wfst_ctx* ctx, uint64_t est_s, uint64_t est_a, WideBuffers& w) {
-  if (est_s > 0x7FFFFFF0ull || est_a > 0x7FFFFFF0ull) throw Error("compose: composition too large");
+inline void wide_alloc(wfst_ctx* ctx, uint64_t est_s, uint64_t est_a, WideBuffers& w, const WideWho& who = WideWho{}) {
+  if (est_s > 0x7FFFFFF0ull || est_a > 0x7FFFFFF0ull) throw Error(std::string(who.op) + ": " + who.result + " too large");
   const LaCaps caps{(uint32_t)est_s, (uint32_t)est_a, wide_next_pow2(2 * est_s + 128)};
   size_t bytes = 0;
   auto take = [&](size_t n) {
@@ -565,7 +574,8 @@ inline void wide_alloc(wfst_ctx* ctx, uint64_t est_s, uint64_t est_a, WideBuffer
 // did not fit, return at once.  Grids are sized from the last width the host has seen (every kernel strides, so any grid
 // is correct).
 template <class P, uint32_t G>
-void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_t est_s, uint64_t est_a, WideOutput& out) {
+void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_t est_s, uint64_t est_a, WideOutput& out,
+                const WideWho& who) {
   constexpr uint32_t SPB = 4 * (64 / G);  // states a block of 256 threads works on at a time
   hipStream_t st = ctx->stream;
   if (const char* e = std::getenv("WFST_WIDE_EST_STATES")) {  // tests: start from a tiny arena so that it has to grow
@@ -579,7 +589,7 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
     est_a = std::max<uint64_t>(est_a, est_s <= (1ull << 22) ? 4 * est_s : est_s);
   }
   WideBuffers w;
-  wide_alloc(ctx, est_s, est_a, w);
+  wide_alloc(ctx, est_s, est_a, w, who);
   DBuf<WideCtl> d_ctl(*ctx->pool, 1);
   struct HostCtl {
     uint32_t head[WIDE_CTL_HEAD / 4];  // status, k_done, pad, lvl ring
@@ -597,15 +607,15 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
   const bool trace = std::getenv("WFST_WIDE_TRACE") != nullptr;
   int grows = 0;
   auto grow = [&]() {
-    ctx->stats.compose_retries++;
-    if (++grows > 24) throw Error("compose: arena overflow after retries");
+    ++(who.grows ? *who.grows : ctx->stats.compose_retries);
+    if (++grows > 24) throw Error(std::string(who.op) + ": arena overflow after retries");
     // the arcs of the finished levels still name table slots, and the table is about to be rebuilt
     if (lo > patch_from) la_patch_range<<<std::min<uint32_t>(max_blocks, (lo - patch_from + 31) / 32), 256, 0, st>>>(w.ar, patch_from, lo);
     patch_from = lo;
     WideBuffers nw;
     // (growing is cheap now, an over-sized table is not: its random accesses leave the caches — x2 once it is large)
     const uint64_t g = w.caps.S >= (1u << 20) ? 2 : 4;
-    wide_alloc(ctx, g * w.caps.S, g * w.caps.A, nw);
+    wide_alloc(ctx, g * w.caps.S, g * w.caps.A, nw, who);
     auto copy = [&](void* d, const void* s_, size_t n) { HIP_CHECK(hipMemcpyAsync(d, s_, n, hipMemcpyDeviceToDevice, st)); };
     copy(nw.ar.t_lo, w.ar.t_lo, (size_t)hi * 8);
     copy(nw.ar.t_hi, w.ar.t_hi, (size_t)hi * 8);
@@ -637,6 +647,7 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
       la_first<G><<<blocks, 256, 0, st>>>(w.ar, k + j, d_ctl.p);
       la_assign<G><<<blocks, 256, 0, st>>>(w.ar, w.caps, k + j, d_ctl.p);
     }
+    out.n_level_launches += 3ull * batch;
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(hc->head, d_ctl.p, WIDE_CTL_HEAD, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -704,18 +715,18 @@ void run_wide_g(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_
 // `items_hint`: arcs a composed state has on its iterated side, on average (+ the loop item) — picks the lanes per state
 template <class P>
 void run_wide(wfst_ctx* ctx, const P& pol, uint64_t lo0, uint64_t hi0, uint64_t est_s, uint64_t est_a, double items_hint,
-              WideOutput& out) {
+              WideOutput& out, const WideWho& who = WideWho{}) {
   // (2 / 4 lanes per state where a state has a handful of items — a linear acceptor against a transducer: 2 — : the kernels move
   // a few sectors per composed state through a chain of dependent trips, and 32 / 16 states per wave instead of 8 is that many
   // more loads in flight for the same registers: the 90 M-state look-ahead composition 107.8 (8 lanes) -> 87.0 (4) -> 77.1 ms
   // (2), profiles/r06d_wide_lookahead.md)
   uint32_t g = items_hint <= 2.5 ? 2u : (items_hint <= 4.0 ? 4u : (items_hint <= 8.0 ? 8u : (items_hint <= 16.0 ? 16u : 64u)));
   if (const char* e = std::getenv("WFST_WIDE_GROUP")) g = (uint32_t)std::atoi(e);  // tests: 2, 4, 8, 16 or 64 lanes per state
-  if (g == 2) run_wide_g<P, 2>(ctx, pol, lo0, hi0, est_s, est_a, out);
-  else if (g == 4) run_wide_g<P, 4>(ctx, pol, lo0, hi0, est_s, est_a, out);
-  else if (g == 8) run_wide_g<P, 8>(ctx, pol, lo0, hi0, est_s, est_a, out);
-  else if (g == 16) run_wide_g<P, 16>(ctx, pol, lo0, hi0, est_s, est_a, out);
-  else run_wide_g<P, 64>(ctx, pol, lo0, hi0, est_s, est_a, out);
+  if (g == 2) run_wide_g<P, 2>(ctx, pol, lo0, hi0, est_s, est_a, out, who);
+  else if (g == 4) run_wide_g<P, 4>(ctx, pol, lo0, hi0, est_s, est_a, out, who);
+  else if (g == 8) run_wide_g<P, 8>(ctx, pol, lo0, hi0, est_s, est_a, out, who);
+  else if (g == 16) run_wide_g<P, 16>(ctx, pol, lo0, hi0, est_s, est_a, out, who);
+  else run_wide_g<P, 64>(ctx, pol, lo0, hi0, est_s, est_a, out, who);
 }
 
 }  // namespace

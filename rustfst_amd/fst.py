@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from enum import Enum
-from typing import List, Optional, Sequence, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -178,6 +178,18 @@ class Context:
                  "states_compared", "wave_states", "cyclic")
         vals = [C.c_uint64() for _ in names]
         check(_lib.lib().wfst_ctx_get_top_sort_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_top_sort_stats")
+        return dict(zip(names, (int(v.value) for v in vals)))
+
+    def replace_stats(self) -> dict:
+        """This context's last replace call (wfst_ctx_get_replace_stats): levels of the search, states and arcs of the result,
+        distinct non-empty call stacks interned (prefixes) and the deepest of them (max_depth), call arcs emitted, call arcs
+        dropped for a callee without a start state, return arcs emitted, times the search's arena grew (arena_grows) and
+        times the expansion ran again with a larger call-stack table (prefix_reruns), and the level kernels queued
+        (level_launches: three per level, idle ones behind the last level included)."""
+        names = ("levels", "states", "arcs", "prefixes", "max_depth", "call_arcs", "dropped_calls", "return_arcs", "arena_grows",
+                 "prefix_reruns", "level_launches")
+        vals = [C.c_uint64() for _ in names]
+        check(_lib.lib().wfst_ctx_get_replace_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_replace_stats")
         return dict(zip(names, (int(v.value) for v in vals)))
 
     def trim_pool(self):
@@ -841,6 +853,20 @@ def _device_concat_list(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None
     return _list_call("wfst_concat_list", fsts, ctx, "Error during concat")
 
 
+def _device_replace(root_idx: int, fst_list, epsilon_on_replace: bool, ctx: Optional[Context] = None) -> DeviceFst:
+    """replace over (label, DeviceFst) pairs as ONE call (wfst_replace): a NEW FST"""
+    n = len(fst_list)
+    ctx = ctx or (fst_list[0][1].ctx if n else default_context())
+    pairs = (_lib.LabelFstPair * max(n, 1))()
+    for i, (label, f) in enumerate(fst_list):
+        pairs[i].label = int(label)
+        pairs[i].fst = f._h.value if isinstance(f._h, C.c_void_p) else f._h
+    out = C.c_void_p()
+    check(_lib.lib().wfst_replace(ctx._h, int(root_idx), pairs, n, 1 if epsilon_on_replace else 0, C.byref(out)),
+          "Error performing replace")
+    return DeviceFst(out, ctx)
+
+
 def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last determinize_batch / determinize_with_distance_batch call of ctx (wfst_ctx_get_determinize_batch_stats)."""
     return _batch_stats("wfst_ctx_get_determinize_batch_stats", ctx)
@@ -1467,3 +1493,16 @@ def concat_list(fsts: Sequence[Union[VectorFst, DeviceFst]]) -> Union[VectorFst,
     """rustfst-python/rustfst/algorithms/concat.py `concat_list`: the left fold of concat, as ONE device call
     (wfst_concat_list).  A NEW FST of the items' kind."""
     return _list_form(fsts, _device_concat_list)
+
+
+def replace(root_idx: int, fst_list: Sequence[Tuple[int, Union[VectorFst, DeviceFst]]],
+            epsilon_on_replace: bool) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/replace.py:19-80 `replace`: the recursive transition network over the (label, fst)
+    pairs of `fst_list`, expanded from the FST whose label is `root_idx`, as ONE device call (wfst_replace).  A NEW FST of the
+    items' kind; the items are left as they are.  A grammar whose expansion reaches a recursive call raises (the reference
+    does not terminate on it)."""
+    fst_list = list(fst_list)
+    if len(fst_list) == 0 or isinstance(fst_list[0][1], DeviceFst):
+        return _device_replace(root_idx, fst_list, epsilon_on_replace)
+    ctx = fst_list[0][1].to_device().ctx
+    return _device_replace(root_idx, [(label, f.to_device(ctx)) for label, f in fst_list], epsilon_on_replace, ctx).to_vector_fst()
