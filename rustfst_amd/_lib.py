@@ -54,10 +54,46 @@ class Stats(C.Structure):
                 ("resident_aborts", C.c_uint64), ("tied_choices", C.c_uint64)]
 
 
+# The route counters: family -> (getter, the names of its uint64_t* parameters behind ctx, in order).  The one statement of
+# the names on this side; include/wfst.h and the family's struct in csrc/common.h say the same (tests/test_host.py).
+_BATCH = ("launches", "items_in_kernel", "items_single")
+COUNTERS = {
+    "rm_epsilon": ("wfst_ctx_get_rm_epsilon_stats",
+                   ("batches", "thread_launches", "wave_launches", "states_thread", "states_wave", "max_closure_cap")),
+    "rm_epsilon_batch": ("wfst_ctx_get_rm_epsilon_batch_stats", _BATCH),
+    "rearm": ("wfst_ctx_get_rearm_stats", ("armed", "adopted", "dropped")),
+    "small_path": ("wfst_ctx_get_small_path_stats",
+                   ("n1_in_kernel", "n1_staged", "n1_handed_back", "nbest_in_kernel", "nbest_tree_full", "nbest_out_full",
+                    "nbest_tree_capacity")),
+    "compose_path": ("wfst_ctx_get_compose_path_stats",
+                     ("string_answered", "string_handed_back", "wave_first", "relaunch_states", "relaunch_arcs",
+                      "relaunch_hash", "relaunch_path", "switched_wide", "two_step", "caps_states", "caps_arcs", "caps_hash")),
+    "string_run": ("wfst_ctx_get_string_run_stats", ("run_levels", "runs")),
+    "determinize": ("wfst_ctx_get_determinize_stats",
+                    ("levels", "wide_levels", "narrow_launches", "exit_wide_states", "exit_wide_cands", "exit_budget",
+                     "exit_need", "exit_done", "wide_need", "grow_states", "grow_elts", "grow_arcs", "grow_cands", "rehashes",
+                     "cap_states", "cap_elts", "cap_arcs", "cap_cands", "rounds_max")),
+    "determinize_batch": ("wfst_ctx_get_determinize_batch_stats", _BATCH),
+    "minimize": ("wfst_ctx_get_minimize_stats",
+                 ("check_levels", "check_wide_levels", "check_narrow_launches", "check_exit_wide", "check_exit_done", "levels",
+                  "wide_levels", "narrow_launches", "exit_wide", "exit_done", "branch", "wave_states", "unequal_compares")),
+    "minimize_batch": ("wfst_ctx_get_minimize_batch_stats", _BATCH),
+    "push": ("wfst_ctx_get_push_stats",
+             ("searches", "rounds", "reads", "rounds_max", "bfs_blocks", "arcs_blocks", "total_blocks", "structural",
+              "start_branch", "removed")),
+    "tr_sum_batch": ("wfst_ctx_get_tr_sum_batch_stats", _BATCH),
+    "replace": ("wfst_ctx_get_replace_stats",
+                ("levels", "states", "arcs", "prefixes", "max_depth", "call_arcs", "dropped_calls", "return_arcs", "arena_grows",
+                 "prefix_reruns", "level_launches")),
+    "top_sort": ("wfst_ctx_get_top_sort_stats",
+                 ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "max_tree_depth", "lift_rows",
+                  "states_compared", "wave_states", "cyclic")),
+}
+
 # every symbol include/wfst.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _f32, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_size_t
 _P = C.POINTER
-SYMBOLS = [
+SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names in COUNTERS.values()] + [
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
     ("wfst_string_destroy", C.c_int, [C.c_char_p]),
     ("wfst_abi_version", _u32, []),
@@ -82,15 +118,8 @@ SYMBOLS = [
     ("wfst_shortest_path", C.c_int, [_vp, _vp, _P(ShortestPathConfig), _P(_vp)]),
     ("wfst_connect", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_rm_epsilon", C.c_int, [_vp, _vp, _P(_vp)]),
-    ("wfst_ctx_get_rm_epsilon_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_rm_epsilon_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
-    ("wfst_ctx_get_rm_epsilon_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
-    ("wfst_ctx_get_rearm_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_ctx_get_bounded_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(C.c_char_p)]),
-    ("wfst_ctx_get_small_path_stats", C.c_int, [_vp] + [_P(_u64)] * 7),
-    ("wfst_ctx_get_compose_path_stats", C.c_int, [_vp] + [_P(_u64)] * 12),
-    ("wfst_ctx_get_string_run_stats", C.c_int, [_vp] + [_P(_u64)] * 2),
-    ("wfst_ctx_get_determinize_stats", C.c_int, [_vp] + [_P(_u64)] * 19),
     ("wfst_ctx_trim_pool", C.c_int, [_vp]),
     ("wfst_fst_project", C.c_int, [_vp, _vp, C.c_int]),
     ("wfst_lookahead_create", C.c_int, [_vp, _vp, _P(_vp)]),
@@ -111,23 +140,18 @@ SYMBOLS = [
     ("wfst_shortest_distance_with_config", C.c_int, [_vp, _vp, _P(ShortestDistanceConfig), _vp, _P(_u32)]),
     ("wfst_push_weights", C.c_int, [_vp, _vp, _u32, _P(PushWeightsConfig), _P(_vp)]),
     ("wfst_reweight", C.c_int, [_vp, _vp, _vp, _u64, _u32, _P(_vp)]),
-    ("wfst_ctx_get_push_stats", C.c_int, [_vp] + [_P(_u64)] * 10),
     ("wfst_determinize", C.c_int, [_vp, _vp, _P(DeterminizeConfig), _P(_vp)]),
     ("wfst_determinize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(DeterminizeConfig), _P(_vp), _vp]),
     ("wfst_determinize_with_distance", C.c_int, [_vp, _vp, _vp, _u64, _f32, _P(_vp), _P(_vp), _P(_u64)]),
     ("wfst_determinize_with_distance_batch", C.c_int,
      [_vp, _P(_vp), _sz, _P(_vp), _P(_u64), _f32, _P(_vp), _P(_vp), _P(_u64), _vp]),
-    ("wfst_ctx_get_determinize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_minimize", C.c_int, [_vp, _vp, _P(MinimizeConfig), _P(_vp)]),
     ("wfst_minimize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(MinimizeConfig), _P(_vp), _vp]),
-    ("wfst_ctx_get_minimize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
-    ("wfst_ctx_get_minimize_stats", C.c_int, [_vp] + [_P(_u64)] * 13),
     ("wfst_tr_sum", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_unique", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_optimize", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_tr_sum_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
     ("wfst_tr_unique_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
-    ("wfst_ctx_get_tr_sum_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_optimize_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
     ("wfst_ctx_get_optimize_batch_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
     ("wfst_union", C.c_int, [_vp, _vp, _vp, _P(_vp)]),
@@ -136,11 +160,9 @@ SYMBOLS = [
     ("wfst_union_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
     ("wfst_concat_list", C.c_int, [_vp, _P(_vp), _sz, _P(_vp)]),
     ("wfst_replace", C.c_int, [_vp, _u32, _P(LabelFstPair), _sz, _u32, _P(_vp)]),
-    ("wfst_ctx_get_replace_stats", C.c_int, [_vp] + [_P(_u64)] * 11),
     ("wfst_rational_check_sizes", C.c_int, [_u32, _vp, _vp, _sz]),
     ("wfst_state_sort", C.c_int, [_vp, _vp, _vp, _sz, _P(_vp)]),
     ("wfst_top_sort", C.c_int, [_vp, _vp, _P(_vp)]),
-    ("wfst_ctx_get_top_sort_stats", C.c_int, [_vp] + [_P(_u64)] * 10),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,

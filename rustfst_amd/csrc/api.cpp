@@ -1,6 +1,7 @@
 // api.cpp — the extern "C" surface declared in include/wfst.h (conventions: rustfst-ffi/src/lib.rs:29-97).
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "lookahead.h"
@@ -115,7 +116,7 @@ void rearm_drop(wfst_ctx* ctx) {
   if (ctx->pool && ctx->pool->unpark(r.blk, RearmRecord::BLOCKS))
     for (void* b : r.blk) ctx->pool->free(b);
   r.clear();
-  ctx->rearm_dropped += 1;
+  ctx->rearm_stats.dropped += 1;
 }
 
 void* PinnedBuf::get(size_t bytes) {
@@ -209,6 +210,24 @@ static wfst_ctx* ctx_create(int device, void* stream, bool own, const uint32_t* 
     ctx->n_cus = std::min(ctx->n_cus, bits);
   }
   return ctx.release();
+}
+
+// The body of a wfst_ctx_get_*_stats getter: counter i of `family` (common.h: fields in the order of the getter's
+// parameters) goes through out[i] where that is not null.
+template <class F, size_t N>
+static wfst_status get_counters(wfst_ctx* ctx, F wfst_ctx::*family, uint64_t* const (&out)[N]) {
+  static_assert(std::is_trivially_copyable_v<F> && sizeof(F) == N * sizeof(uint64_t));
+  return wrap([&] {
+    if (!ctx) throw Error("null pointer");
+    uint64_t v[N];
+    std::memcpy(v, &(ctx->*family), sizeof v);
+    for (size_t i = 0; i < N; ++i)
+      if (out[i]) *out[i] = v[i];
+  });
+}
+// wfst_shortest_path / wfst_shortest_path_batch begin: the n1_* counters are those of this call's last sp1_wave_kernel launch
+static void small_path_begin(wfst_ctx* ctx) {
+  ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
 }
 
 extern "C" {
@@ -385,7 +404,7 @@ wfst_status wfst_shortest_path(wfst_ctx* ctx, const wfst_fst* fst, const wfst_sh
     if (!ctx || !fst || !out) throw Error("null pointer");
     wfst_shortest_path_config c = cfg ? *cfg : wfst_shortest_path_config{1e-6f, 1, 0};  // shortest_path.rs:31-39
     HIP_CHECK(hipSetDevice(ctx->device));
-    ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
+    small_path_begin(ctx);
     if (c.nshortest == 0) {  // shortest_path.rs:118-120: FO::new()
       HostCsr h;
       h.offsets.push_back(0);
@@ -412,7 +431,7 @@ wfst_status wfst_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* fsts,
     }
     wfst_shortest_path_config c = cfg ? *cfg : wfst_shortest_path_config{1e-6f, 1, 0};
     HIP_CHECK(hipSetDevice(ctx->device));
-    ctx->small_path.n1_in_kernel = ctx->small_path.n1_staged = ctx->small_path.n1_handed_back = 0;
+    small_path_begin(ctx);
     try {
       if (c.nshortest >= 2 && !c.unique) {
         shortest_path_nbest_batch(ctx, fsts, n, c.nshortest, c.delta, outs);
@@ -459,7 +478,7 @@ wfst_status wfst_shortest_distance(wfst_ctx* ctx, const wfst_fst* fst, float* di
 wfst_status wfst_shortest_distance_with_config(wfst_ctx* ctx, const wfst_fst* fst, const wfst_shortest_distance_config* cfg,
                                                float* distance, uint32_t* len) {
   return wrap([&] {
-    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
+    if (ctx) ctx->push_stats = {};  // (before any argument is looked at: common.h)
     const wfst_shortest_distance_config c = cfg ? *cfg : wfst_shortest_distance_config{0u, 1e-6f};
     if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("shortest_distance: delta must be finite and >= 0");
     (void)push_max_blocks_knob();
@@ -474,7 +493,7 @@ wfst_status wfst_push_weights(wfst_ctx* ctx, const wfst_fst* fst, uint32_t rewei
                               wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
-    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
+    if (ctx) ctx->push_stats = {};  // (before any argument is looked at: common.h)
     const wfst_push_weights_config c = cfg ? *cfg : wfst_push_weights_config{1.0f / 1024.0f, 0u};
     if (reweight_type > 1) throw Error("push_weights: unknown reweight_type " + std::to_string(reweight_type));
     if (!(c.delta >= 0.0f) || !std::isfinite(c.delta)) throw Error("push_weights: delta must be finite and >= 0");
@@ -490,7 +509,7 @@ wfst_status wfst_reweight(wfst_ctx* ctx, const wfst_fst* fst, const float* poten
                           uint32_t reweight_type, wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
-    if (ctx) ctx->push_stats = {};  // (wfst_ctx_get_push_stats: this call's, also when an argument is refused)
+    if (ctx) ctx->push_stats = {};  // (before any argument is looked at: common.h)
     if (reweight_type > 1) throw Error("reweight: unknown reweight_type " + std::to_string(reweight_type));
     if (!potentials && n_potentials) throw Error("reweight: potentials is NULL but n_potentials > 0");
     (void)push_max_blocks_knob();
@@ -532,15 +551,6 @@ static bool begin_batch_call(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t 
   check_batch_args(ctx, fsts, n, outs);
   HIP_CHECK(hipSetDevice(ctx->device));
   return true;
-}
-static wfst_status get_batch_stats(wfst_ctx* ctx, BatchStats wfst_ctx::*stats, uint64_t* launches, uint64_t* items_in_kernel,
-                                   uint64_t* items_single) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (launches) *launches = (ctx->*stats).launches;
-    if (items_in_kernel) *items_in_kernel = (ctx->*stats).in_kernel;
-    if (items_single) *items_single = (ctx->*stats).single;
-  });
 }
 wfst_status wfst_determinize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, const wfst_determinize_config* cfg,
                                    wfst_fst** outs, uint8_t* in_kernel) {
@@ -615,14 +625,14 @@ wfst_status wfst_determinize_with_distance_batch(wfst_ctx* ctx, const wfst_fst* 
 }
 wfst_status wfst_ctx_get_determinize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                                  uint64_t* items_single) {
-  return get_batch_stats(ctx, &wfst_ctx::det_batch, launches, items_in_kernel, items_single);
+  return get_counters(ctx, &wfst_ctx::det_batch, {launches, items_in_kernel, items_single});
 }
 
 // minimize_with_config (minimize.rs:92-176); MinimizeConfig::default() = {KSHORTESTDELTA, false} when cfg == NULL
 wfst_status wfst_minimize(wfst_ctx* ctx, const wfst_fst* fst, const wfst_minimize_config* cfg, wfst_fst** out) {
   return wrap([&] {
     if (out) *out = nullptr;
-    if (ctx) ctx->min_stats = {};  // (wfst_ctx_get_minimize_stats: this call's, also when an argument is refused)
+    if (ctx) ctx->min_stats = {};  // (before any argument is looked at: common.h)
     const wfst_minimize_config c = cfg ? *cfg : wfst_minimize_config{1e-6f, 0u};
     if (!(c.delta > 0.0f) || !std::isfinite(c.delta)) throw Error("minimize: delta must be finite and > 0");
     if (!ctx || !fst || !out) throw Error("null pointer");
@@ -643,7 +653,7 @@ wfst_status wfst_minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size
 }
 wfst_status wfst_ctx_get_minimize_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                               uint64_t* items_single) {
-  return get_batch_stats(ctx, &wfst_ctx::min_batch, launches, items_in_kernel, items_single);
+  return get_counters(ctx, &wfst_ctx::min_batch, {launches, items_in_kernel, items_single});
 }
 
 // tr_sum (tr_sum.rs:7-22) / tr_unique (tr_unique.rs:38-51)
@@ -681,7 +691,7 @@ wfst_status wfst_tr_unique_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, siz
   });
 }
 wfst_status wfst_ctx_get_tr_sum_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single) {
-  return get_batch_stats(ctx, &wfst_ctx::trsum_batch, launches, items_in_kernel, items_single);
+  return get_counters(ctx, &wfst_ctx::trsum_batch, {launches, items_in_kernel, items_single});
 }
 
 // optimize (optimize.rs:11-128), tropical semiring
@@ -706,9 +716,9 @@ wfst_status wfst_ctx_get_optimize_batch_stats(wfst_ctx* ctx, uint64_t* launches,
   return wrap([&] {
     if (!ctx) throw Error("null pointer");
     if (launches) std::copy(ctx->opt_batch.launches, ctx->opt_batch.launches + 4, launches);
-    if (items_in_kernel) *items_in_kernel = ctx->opt_batch.in_kernel;
-    if (items_single) *items_single = ctx->opt_batch.single;
-    if (items_transducer) *items_transducer = ctx->opt_batch.transducer;
+    if (items_in_kernel) *items_in_kernel = ctx->opt_batch.items_in_kernel;
+    if (items_single) *items_single = ctx->opt_batch.items_single;
+    if (items_transducer) *items_transducer = ctx->opt_batch.items_transducer;
   });
 }
 
@@ -781,21 +791,8 @@ wfst_status wfst_replace(wfst_ctx* ctx, uint32_t root, const wfst_label_fst_pair
 wfst_status wfst_ctx_get_replace_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* states, uint64_t* arcs, uint64_t* prefixes,
                                        uint64_t* max_depth, uint64_t* call_arcs, uint64_t* dropped_calls, uint64_t* return_arcs,
                                        uint64_t* arena_grows, uint64_t* prefix_reruns, uint64_t* level_launches) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::ReplaceStats& c = ctx->replace;
-    if (levels) *levels = c.levels;
-    if (states) *states = c.states;
-    if (arcs) *arcs = c.arcs;
-    if (prefixes) *prefixes = c.prefixes;
-    if (max_depth) *max_depth = c.max_depth;
-    if (call_arcs) *call_arcs = c.calls;
-    if (dropped_calls) *dropped_calls = c.dropped;
-    if (return_arcs) *return_arcs = c.returns;
-    if (arena_grows) *arena_grows = c.grows;
-    if (prefix_reruns) *prefix_reruns = c.prefix_reruns;
-    if (level_launches) *level_launches = c.level_launches;
-  });
+  return get_counters(ctx, &wfst_ctx::replace, {levels, states, arcs, prefixes, max_depth, call_arcs, dropped_calls,
+                                                return_arcs, arena_grows, prefix_reruns, level_launches});
 }
 wfst_status wfst_rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t* n_arcs, size_t n) {
   return wrap([&] { rational_check_sizes(op, n_states, n_arcs, n); });
@@ -821,20 +818,8 @@ wfst_status wfst_top_sort(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
 wfst_status wfst_ctx_get_top_sort_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
                                         uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* max_tree_depth,
                                         uint64_t* lift_rows, uint64_t* states_compared, uint64_t* wave_states, uint64_t* cyclic) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::TopSortStats& c = ctx->top_sort;
-    if (levels) *levels = c.levels;
-    if (narrow_launches) *narrow_launches = c.narrow_launches;
-    if (wide_launches) *wide_launches = c.wide_launches;
-    if (narrow_levels) *narrow_levels = c.narrow_levels;
-    if (max_level_width) *max_level_width = c.max_level_width;
-    if (max_tree_depth) *max_tree_depth = c.max_tree_depth;
-    if (lift_rows) *lift_rows = c.lift_rows;
-    if (states_compared) *states_compared = c.states_compared;
-    if (wave_states) *wave_states = c.wave_states;
-    if (cyclic) *cyclic = c.cyclic;
-  });
+  return get_counters(ctx, &wfst_ctx::top_sort, {levels, narrow_launches, wide_launches, narrow_levels, max_level_width,
+                                                 max_tree_depth, lift_rows, states_compared, wave_states, cyclic});
 }
 
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
@@ -902,52 +887,27 @@ wfst_status wfst_rm_epsilon_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, si
 }
 wfst_status wfst_ctx_get_rm_epsilon_batch_stats(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
                                                 uint64_t* items_single) {
-  return get_batch_stats(ctx, &wfst_ctx::rm_batch, launches, items_in_kernel, items_single);
+  return get_counters(ctx, &wfst_ctx::rm_batch, {launches, items_in_kernel, items_single});
 }
 
 wfst_status wfst_ctx_get_small_path_stats(wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back,
                                           uint64_t* nbest_in_kernel, uint64_t* nbest_tree_full, uint64_t* nbest_out_full,
                                           uint64_t* nbest_tree_capacity) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (n1_in_kernel) *n1_in_kernel = ctx->small_path.n1_in_kernel;
-    if (n1_staged) *n1_staged = ctx->small_path.n1_staged;
-    if (n1_handed_back) *n1_handed_back = ctx->small_path.n1_handed_back;
-    if (nbest_in_kernel) *nbest_in_kernel = ctx->small_path.nbest_in_kernel;
-    if (nbest_tree_full) *nbest_tree_full = ctx->small_path.nbest_tree_full;
-    if (nbest_out_full) *nbest_out_full = ctx->small_path.nbest_out_full;
-    if (nbest_tree_capacity) *nbest_tree_capacity = ctx->small_path.nbest_tree_capacity;
-  });
+  return get_counters(ctx, &wfst_ctx::small_path, {n1_in_kernel, n1_staged, n1_handed_back, nbest_in_kernel, nbest_tree_full,
+                                                   nbest_out_full, nbest_tree_capacity});
 }
 
 wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answered, uint64_t* string_handed_back,
                                             uint64_t* wave_first, uint64_t* relaunch_states, uint64_t* relaunch_arcs,
                                             uint64_t* relaunch_hash, uint64_t* relaunch_path, uint64_t* switched_wide,
                                             uint64_t* two_step, uint64_t* caps_states, uint64_t* caps_arcs, uint64_t* caps_hash) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::ComposePathStats& c = ctx->compose_path;
-    if (string_answered) *string_answered = c.string_answered;
-    if (string_handed_back) *string_handed_back = c.string_handed_back;
-    if (wave_first) *wave_first = c.wave_first;
-    if (relaunch_states) *relaunch_states = c.relaunch_states;
-    if (relaunch_arcs) *relaunch_arcs = c.relaunch_arcs;
-    if (relaunch_hash) *relaunch_hash = c.relaunch_hash;
-    if (relaunch_path) *relaunch_path = c.relaunch_path;
-    if (switched_wide) *switched_wide = c.switched_wide;
-    if (two_step) *two_step = c.two_step;
-    if (caps_states) *caps_states = c.caps_states;
-    if (caps_arcs) *caps_arcs = c.caps_arcs;
-    if (caps_hash) *caps_hash = c.caps_hash;
-  });
+  return get_counters(ctx, &wfst_ctx::compose_path, {string_answered, string_handed_back, wave_first, relaunch_states,
+                                                     relaunch_arcs, relaunch_hash, relaunch_path, switched_wide, two_step,
+                                                     caps_states, caps_arcs, caps_hash});
 }
 
 wfst_status wfst_ctx_get_string_run_stats(wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (run_levels) *run_levels = ctx->string_run_levels;
-    if (runs) *runs = ctx->string_runs;
-  });
+  return get_counters(ctx, &wfst_ctx::string_run, {run_levels, runs});
 }
 
 wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* wide_levels, uint64_t*
@@ -956,29 +916,10 @@ wfst_status wfst_ctx_get_determinize_stats(wfst_ctx* ctx, uint64_t* levels, uint
                                            wide_need, uint64_t* grow_states, uint64_t* grow_elts, uint64_t* grow_arcs,
                                            uint64_t* grow_cands, uint64_t* rehashes, uint64_t* cap_states, uint64_t*
                                            cap_elts, uint64_t* cap_arcs, uint64_t* cap_cands, uint64_t* rounds_max) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::DeterminizeStats& c = ctx->det_stats;
-    if (levels) *levels = c.levels;
-    if (wide_levels) *wide_levels = c.wide_levels;
-    if (narrow_launches) *narrow_launches = c.narrow_launches;
-    if (exit_wide_states) *exit_wide_states = c.exit_wide_states;
-    if (exit_wide_cands) *exit_wide_cands = c.exit_wide_cands;
-    if (exit_budget) *exit_budget = c.exit_budget;
-    if (exit_need) *exit_need = c.exit_need;
-    if (exit_done) *exit_done = c.exit_done;
-    if (wide_need) *wide_need = c.wide_need;
-    if (grow_states) *grow_states = c.grow_states;
-    if (grow_elts) *grow_elts = c.grow_elts;
-    if (grow_arcs) *grow_arcs = c.grow_arcs;
-    if (grow_cands) *grow_cands = c.grow_cands;
-    if (rehashes) *rehashes = c.rehashes;
-    if (cap_states) *cap_states = c.cap_states;
-    if (cap_elts) *cap_elts = c.cap_elts;
-    if (cap_arcs) *cap_arcs = c.cap_arcs;
-    if (cap_cands) *cap_cands = c.cap_cands;
-    if (rounds_max) *rounds_max = c.rounds_max;
-  });
+  return get_counters(ctx, &wfst_ctx::det_stats, {levels, wide_levels, narrow_launches, exit_wide_states, exit_wide_cands,
+                                                  exit_budget, exit_need, exit_done, wide_need, grow_states, grow_elts,
+                                                  grow_arcs, grow_cands, rehashes, cap_states, cap_elts, cap_arcs, cap_cands,
+                                                  rounds_max});
 }
 
 wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, uint64_t* check_wide_levels,
@@ -986,70 +927,32 @@ wfst_status wfst_ctx_get_minimize_stats(wfst_ctx* ctx, uint64_t* check_levels, u
                                         uint64_t* levels, uint64_t* wide_levels, uint64_t* narrow_launches, uint64_t* exit_wide,
                                         uint64_t* exit_done, uint64_t* branch, uint64_t* wave_states,
                                         uint64_t* unequal_compares) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::MinimizeStats& c = ctx->min_stats;
-    if (check_levels) *check_levels = c.check.levels;
-    if (check_wide_levels) *check_wide_levels = c.check.wide_levels;
-    if (check_narrow_launches) *check_narrow_launches = c.check.narrow_launches;
-    if (check_exit_wide) *check_exit_wide = c.check.exit_wide;
-    if (check_exit_done) *check_exit_done = c.check.exit_done;
-    if (levels) *levels = c.refine.levels;
-    if (wide_levels) *wide_levels = c.refine.wide_levels;
-    if (narrow_launches) *narrow_launches = c.refine.narrow_launches;
-    if (exit_wide) *exit_wide = c.refine.exit_wide;
-    if (exit_done) *exit_done = c.refine.exit_done;
-    if (branch) *branch = c.branch;
-    if (wave_states) *wave_states = c.wave_states;
-    if (unequal_compares) *unequal_compares = c.unequal_compares;
-  });
+  return get_counters(ctx, &wfst_ctx::min_stats, {check_levels, check_wide_levels, check_narrow_launches, check_exit_wide,
+                                                  check_exit_done, levels, wide_levels, narrow_launches, exit_wide, exit_done,
+                                                  branch, wave_states, unequal_compares});
 }
 
 wfst_status wfst_ctx_get_push_stats(wfst_ctx* ctx, uint64_t* searches, uint64_t* rounds, uint64_t* reads, uint64_t* rounds_max,
                                     uint64_t* bfs_blocks, uint64_t* arcs_blocks, uint64_t* total_blocks, uint64_t* structural,
                                     uint64_t* start_branch, uint64_t* removed) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    const wfst_ctx::PushStats& c = ctx->push_stats;
-    if (searches) *searches = c.searches;
-    if (rounds) *rounds = c.rounds;
-    if (reads) *reads = c.reads;
-    if (rounds_max) *rounds_max = c.rounds_max;
-    if (bfs_blocks) *bfs_blocks = c.bfs_blocks;
-    if (arcs_blocks) *arcs_blocks = c.arcs_blocks;
-    if (total_blocks) *total_blocks = c.total_blocks;
-    if (structural) *structural = c.structural;
-    if (start_branch) *start_branch = c.start_branch;
-    if (removed) *removed = c.removed;
-  });
+  return get_counters(ctx, &wfst_ctx::push_stats, {searches, rounds, reads, rounds_max, bfs_blocks, arcs_blocks, total_blocks,
+                                                   structural, start_branch, removed});
 }
 
 wfst_status wfst_ctx_get_rm_epsilon_stats(wfst_ctx* ctx, uint64_t* batches, uint64_t* thread_launches, uint64_t* wave_launches,
                                           uint64_t* states_thread, uint64_t* states_wave, uint64_t* max_closure_cap) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (batches) *batches = ctx->rm_eps.batches;
-    if (thread_launches) *thread_launches = ctx->rm_eps.thread_launches;
-    if (wave_launches) *wave_launches = ctx->rm_eps.wave_launches;
-    if (states_thread) *states_thread = ctx->rm_eps.states_thread;
-    if (states_wave) *states_wave = ctx->rm_eps.states_wave;
-    if (max_closure_cap) *max_closure_cap = ctx->rm_eps.max_closure_cap;
-  });
+  return get_counters(ctx, &wfst_ctx::rm_eps, {batches, thread_launches, wave_launches, states_thread, states_wave,
+                                               max_closure_cap});
 }
 
 wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* adopted, uint64_t* dropped) {
-  return wrap([&] {
-    if (!ctx) throw Error("null pointer");
-    if (armed) *armed = ctx->rearm_armed;
-    if (adopted) *adopted = ctx->rearm_adopted;
-    if (dropped) *dropped = ctx->rearm_dropped;
-  });
+  return get_counters(ctx, &wfst_ctx::rearm_stats, {armed, adopted, dropped});
 }
 wfst_status wfst_ctx_get_bounded_stats(wfst_ctx* ctx, uint64_t* stops, uint64_t* full_solves, const char** last_reason) {
   return wrap([&] {
     if (!ctx) throw Error("null pointer");
-    if (stops) *stops = ctx->bounded_stops;
-    if (full_solves) *full_solves = ctx->bounded_refused;
+    if (stops) *stops = ctx->bounded.stops;
+    if (full_solves) *full_solves = ctx->bounded.full_solves;
     if (last_reason) *last_reason = ctx->bounded_last_refusal;
   });
 }

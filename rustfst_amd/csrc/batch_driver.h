@@ -134,11 +134,11 @@ void batch_finish(wfst_ctx* ctx, BatchStats& stats, size_t n, wfst_fst** outs, u
         } catch (const std::exception& e) {
           throw Error("item " + std::to_string(i) + ": " + e.what());
         }
-        stats.single += 1;
+        stats.items_single += 1;
         flag[i] = 0;
         continue;
       }
-      stats.in_kernel += 1;
+      stats.items_in_kernel += 1;
       if (o.kind == BatchOutcome::READY) {
         outs[i] = o.ready;
       } else {

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <atomic>
 #include <map>
@@ -64,6 +65,16 @@ struct Error : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
 void set_last_error(const std::string& msg);
+
+// a WFST_*_PATH variable (tests): which of an operation's two level routes may run
+enum class Path { Auto, Narrow, Wide };
+static inline Path path_knob(const char* var) {  // (internal linkage: no exported symbol)
+  const char* e = std::getenv(var);
+  if (!e || !*e || !std::strcmp(e, "auto")) return Path::Auto;
+  if (!std::strcmp(e, "narrow")) return Path::Narrow;
+  if (!std::strcmp(e, "wide")) return Path::Wide;
+  throw Error(std::string(var) + ": expected auto, narrow or wide, not '" + e + "'");
+}
 
 #define HIP_CHECK(expr)                                                                                  \
   do {                                                                                                   \
@@ -196,12 +207,17 @@ struct RearmRecord {
     for (size_t& c : cnt) c = 0;
   }
 };
-struct BatchStats {  // one call of a one-workgroup-per-item batch operation
-  uint64_t launches = 0, in_kernel = 0, single = 0;
+// Route counters: host-side tallies that say which kernel route a call took.  One struct per family, uint64_t fields only, declared
+// in the order of the family's wfst_ctx_get_*_stats parameters (include/wfst.h) and named exactly as they are: api.cpp copies a
+// family out by position, tests/test_host.py compares the names.  Each comment says when the family is zeroed.
+// One call of a one-workgroup-per-item batch operation; zeroed when that call begins, also when an argument is refused.
+struct BatchStats {
+  uint64_t launches = 0, items_in_kernel = 0, items_single = 0;
 };
-struct OptimizeBatchStats {  // one wfst_optimize_batch call; launches per stage: rm_epsilon, tr_sum, determinize, minimize
+// One wfst_optimize_batch call, zeroed like BatchStats; launches per stage: rm_epsilon, tr_sum, determinize, minimize
+struct OptimizeBatchStats {
   uint64_t launches[4] = {0, 0, 0, 0};
-  uint64_t in_kernel = 0, single = 0, transducer = 0;
+  uint64_t items_in_kernel = 0, items_single = 0, items_transducer = 0;
 };
 }  // namespace wfst
 
@@ -243,14 +259,13 @@ struct wfst_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags: [0] first batch of a solve, [1] batches of 8 sweeps, [2] of 64
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
-  // the last wfst_determinize_batch / wfst_determinize_with_distance_batch, wfst_minimize_batch and wfst_rm_epsilon_batch
-  // call (wfst_ctx_get_{determinize,minimize,rm_epsilon}_batch_stats; batch_driver.h counts)
-  wfst::BatchStats det_batch, min_batch, rm_batch;
-  // ... and the last wfst_tr_sum_batch / wfst_tr_unique_batch and wfst_optimize_batch calls
-  wfst::BatchStats trsum_batch;
+  // ---- route counters (the rules: wfst::BatchStats above).  The last wfst_determinize_batch / wfst_determinize_with_distance_batch,
+  // wfst_minimize_batch, wfst_rm_epsilon_batch, wfst_tr_sum_batch / wfst_tr_unique_batch and wfst_optimize_batch call
+  // (batch_driver.h counts)
+  wfst::BatchStats det_batch, min_batch, rm_batch, trsum_batch;
   wfst::OptimizeBatchStats opt_batch;
-  // which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took
-  // (wfst_ctx_get_determinize_stats): tallied on the host from the control block determinize.hip already reads back
+  // Which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took: tallied on the host from
+  // the control block determinize.hip already reads back.  Zeroed when determinize.hip's driver begins.
   struct DeterminizeStats {
     uint64_t levels = 0, wide_levels = 0, narrow_launches = 0;
     uint64_t exit_wide_states = 0, exit_wide_cands = 0, exit_budget = 0, exit_need = 0, exit_done = 0, wide_need = 0;
@@ -258,62 +273,73 @@ struct wfst_ctx {
     uint64_t cap_states = 0, cap_elts = 0, cap_arcs = 0, cap_cands = 0;
     uint64_t rounds_max = 0;
   } det_stats;
-  // which route the levels of the last wfst_minimize call took (wfst_ctx_get_minimize_stats): tallied on the host from the
-  // control block minimize.hip's level loop already reads back; check = the cycle check on the untrimmed input, refine =
-  // the refinement of the connected machine
+  // Which route the last wfst_minimize call took: tallied on the host from the control block minimize.hip's level loop already
+  // reads back; check = the cycle check on the untrimmed input, refine = the refinement of the connected machine.  Zeroed when
+  // wfst_minimize begins, also when an argument is refused, and when minimize.hip's driver begins.
   struct MinimizeStats {
+    // flat: check_levels, check_wide_levels, check_narrow_launches, check_exit_wide, check_exit_done, levels, wide_levels,
+    //       narrow_launches, exit_wide, exit_done, branch, wave_states, unequal_compares
     struct Pass {
       uint64_t levels = 0, wide_levels = 0, narrow_launches = 0, exit_wide = 0, exit_done = 0;
     } check, refine;
     uint64_t branch = 0, wave_states = 0, unequal_compares = 0;
   } min_stats;
-  // the route of the last wfst_shortest_distance_with_config / wfst_reweight / wfst_push_weights call
-  // (wfst_ctx_get_push_stats): tallied on the host by push.hip from its launch geometry, its loop counter and the values
-  // it reads back anyway
+  // The route of the last wfst_shortest_distance_with_config / wfst_reweight / wfst_push_weights call: tallied on the host by
+  // push.hip from its launch geometry, its loop counter and the values it reads back anyway.  Zeroed when one of the three
+  // begins, also when an argument is refused.
   struct PushStats {
     uint64_t searches = 0, rounds = 0, reads = 0, rounds_max = 0;
     uint64_t bfs_blocks = 0, arcs_blocks = 0, total_blocks = 0;
     uint64_t structural = 0, start_branch = 0, removed = 0;
   } push_stats;
-  // the one-wave path kernels (wfst_ctx_get_small_path_stats): the last sp1_wave_kernel launch since the last
-  // wfst_shortest_path / wfst_shortest_path_batch call began, and the last shortest_path_nbest_batch
+  // The one-wave path kernels.  n1_*: the last sp1_wave_kernel launch since the last wfst_shortest_path /
+  // wfst_shortest_path_batch call began — zeroed when either begins (small_path_begin, api.cpp) and before each such launch is
+  // counted; nbest_*: the last shortest_path_nbest_batch, zeroed when it begins.
   struct SmallPathStats {
     uint64_t n1_in_kernel = 0, n1_staged = 0, n1_handed_back = 0;
     uint64_t nbest_in_kernel = 0, nbest_tree_full = 0, nbest_out_full = 0, nbest_tree_capacity = 0;
   } small_path;
-  // which route answered the problems of the last compose / fused-batch call (wfst_ctx_get_compose_path_stats): tallied on
-  // the host from the status words the kernels of compose.hip already report
+  // Which route answered the problems of the last compose / fused-batch call: tallied on the host from the status words the
+  // kernels of compose.hip already report.  Zeroed when either call begins.
   struct ComposePathStats {
     uint64_t string_answered = 0, string_handed_back = 0, wave_first = 0;
     uint64_t relaunch_states = 0, relaunch_arcs = 0, relaunch_hash = 0, relaunch_path = 0;
     uint64_t switched_wide = 0, two_step = 0;
     uint64_t caps_states = 0, caps_arcs = 0, caps_hash = 0;  // Caps of the last compose_wave_kernel launch
   } compose_path;
-  // the chase runs of the string o T kernel in the last fused-batch call (wfst_ctx_get_string_run_stats): levels taken inside
-  // runs and the number of runs, summed over the problems the kernel answered
-  uint64_t string_run_levels = 0, string_runs = 0;
-  // the last wfst_rm_epsilon call (wfst_ctx_get_rm_epsilon_stats)
+  // The chase runs of the string o T kernel in the last fused-batch call: levels taken inside runs and the number of runs,
+  // summed over the problems the kernel answered.  Zeroed when the fused-batch call begins.
+  struct StringRunStats {
+    uint64_t run_levels = 0, runs = 0;
+  } string_run;
+  // The last wfst_rm_epsilon call; zeroed when rm_epsilon.hip's driver begins.
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
   } rm_eps;
-  // the last wfst_top_sort call (wfst_ctx_get_top_sort_stats): tallied on the host by top_sort.hip from its launches, the
-  // level bounds and the three words it reads back anyway
+  // The last wfst_top_sort call: tallied on the host by top_sort.hip from its launches, the level bounds and the three words it
+  // reads back anyway.  Zeroed when top_sort.hip's driver begins.
   struct TopSortStats {
     uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, max_tree_depth = 0;
     uint64_t lift_rows = 0, states_compared = 0, wave_states = 0, cyclic = 0;
   } top_sort;
-  // the last wfst_replace call (wfst_ctx_get_replace_stats): the driver's level and size figures, the counters of
-  // replace.hip's policy block, and the two kinds of growth (the driver's arena in place, the prefix table by a rerun)
+  // The last wfst_replace call: the driver's level and size figures, the counters of replace.hip's policy block, and the two
+  // kinds of growth (the driver's arena in place, the prefix table by a rerun).  Zeroed when replace.hip's driver begins.
   struct ReplaceStats {
-    uint64_t levels = 0, states = 0, arcs = 0, prefixes = 0, max_depth = 0, calls = 0, dropped = 0, returns = 0;
-    uint64_t grows = 0, prefix_reruns = 0, level_launches = 0;
+    uint64_t levels = 0, states = 0, arcs = 0, prefixes = 0, max_depth = 0, call_arcs = 0, dropped_calls = 0, return_arcs = 0;
+    uint64_t arena_grows = 0, prefix_reruns = 0, level_launches = 0;
   } replace;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
-  uint64_t rearm_armed = 0, rearm_adopted = 0, rearm_dropped = 0;  // wfst_ctx_get_rearm_stats
-  // the bounded head of the single-shortest-path relaxation (wfst_ctx_get_bounded_stats): queries it ended, queries that ran
-  // the full solve, and why the last of those did (a string literal); bounded_hold: the query being repeated may not stop
-  uint64_t bounded_stops = 0, bounded_refused = 0;
+  // ... and what became of such scratch; never zeroed (counts since the context's creation)
+  struct RearmStats {
+    uint64_t armed = 0, adopted = 0, dropped = 0;
+  } rearm_stats;
+  // The bounded head of the single-shortest-path relaxation (wfst_ctx_get_bounded_stats, with bounded_last_refusal as its
+  // last_reason): queries it ended and queries that ran the full solve; never zeroed.  bounded_last_refusal: why the last of
+  // those did (a string literal); bounded_hold: the query being repeated may not stop
+  struct BoundedStats {
+    uint64_t stops = 0, full_solves = 0;
+  } bounded;
   const char* bounded_last_refusal = "";
   bool bounded_hold = false;
 };

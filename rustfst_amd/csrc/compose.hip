@@ -1936,7 +1936,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   job->ctx = ctx;
   job->n = n;
   ctx->compose_path = wfst_ctx::ComposePathStats{};
-  ctx->string_run_levels = ctx->string_runs = 0;
+  ctx->string_run = {};
   if (n == 0) return job.release();
   job->env = EnvSnap::take();
   job->run_s.env = &job->env;
@@ -2050,8 +2050,8 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
         tot_arcs += r.n_arcs;
         tot_states += r.n_states;
         n_string_ok += 1;
-        ctx->string_run_levels += r.run_levels;
-        ctx->string_runs += r.runs;
+        ctx->string_run.run_levels += r.run_levels;
+        ctx->string_run.runs += r.runs;
         ok.push_back(k);
       }
       // the path FSTs (three small vectors and a handle each: ~0.4 us): a large batch shares them out among host threads

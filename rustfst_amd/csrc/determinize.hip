@@ -754,15 +754,6 @@ struct Run {
   }
 };
 
-enum class Path { Auto, Narrow, Wide };
-Path path_knob() {
-  const char* e = std::getenv("WFST_DETERMINIZE_PATH");
-  if (!e || !*e || !std::strcmp(e, "auto")) return Path::Auto;
-  if (!std::strcmp(e, "narrow")) return Path::Narrow;
-  if (!std::strcmp(e, "wide")) return Path::Wide;
-  throw Error(std::string("WFST_DETERMINIZE_PATH: expected auto, narrow or wide, not '") + e + "'");
-}
-
 }  // namespace
 
 // out_dist of determinize_with_distance for ONE result: in_dist on the device, the answer on the host
@@ -818,7 +809,7 @@ static wfst_fst* determinize_acceptor(wfst_ctx* ctx, const wfst_fst* f, float de
     return make_host_fst(ctx, 0, -1, out_props, std::move(h));
   }
   ensure_device(const_cast<wfst_fst*>(f));
-  const Path path = path_knob();
+  const Path path = path_knob("WFST_DETERMINIZE_PATH");
   const uint32_t max_states = max_states_knob(), budget = level_budget_knob();
   hipStream_t st = ctx->stream;
   Run run(*ctx->pool, st);

@@ -534,15 +534,6 @@ __global__ void __launch_bounds__(TPB) emit_kernel(const uint32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- host side
-enum class Path { Auto, Narrow, Wide };
-Path path_knob() {
-  const char* e = std::getenv("WFST_MINIMIZE_PATH");
-  if (!e || !*e || !std::strcmp(e, "auto")) return Path::Auto;
-  if (!std::strcmp(e, "narrow")) return Path::Narrow;
-  if (!std::strcmp(e, "wide")) return Path::Wide;
-  throw Error(std::string("WFST_MINIMIZE_PATH: expected auto, narrow or wide, not '") + e + "'");
-}
-
 // WFST_MINIMIZE_HASH_BITS=n (0 <= n <= 64; tests): refine_small / refine_big keep the low n bits of a signature's hash, so
 // that different signatures meet in one slot with one tag and the full compare decides.  The mask of the bits kept.
 uint64_t hash_mask_knob() {
@@ -824,7 +815,7 @@ wfst_fst* minimize_fst(wfst_ctx* ctx, const wfst_fst* f, float delta, bool allow
   using namespace props;
   wfst_ctx::MinimizeStats& tally = ctx->min_stats;  // (wfst_ctx_get_minimize_stats: this call's, also when it ends KO)
   tally = wfst_ctx::MinimizeStats{};
-  const Knobs knobs{path_knob(), hash_mask_knob()};
+  const Knobs knobs{path_knob("WFST_MINIMIZE_PATH"), hash_mask_knob()};
   hipStream_t st = ctx->stream;
   DevicePool& pool = *ctx->pool;
   ensure_device(const_cast<wfst_fst*>(f));
@@ -1389,7 +1380,7 @@ void minimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, float 
   using namespace props;
   ctx->min_batch = {};
   check_items_owned(ctx, fsts, n, "minimize_batch");
-  (void)path_knob();  // (a bad WFST_MINIMIZE_PATH is KO here as in the single call)
+  (void)path_knob("WFST_MINIMIZE_PATH");  // (a bad WFST_MINIMIZE_PATH is KO here as in the single call)
   hipStream_t st = ctx->stream;
   enum : uint8_t { KERNEL, TRIVIAL, SINGLE };
   struct Ran {  // what the kernel left of an item: its control block and its result arrays inside the slab

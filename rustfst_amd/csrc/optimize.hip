@@ -289,10 +289,10 @@ void optimize_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_f
       replay(i, message);
     }
     flag[i] = 0;
-    stats.transducer += 1;
+    stats.items_transducer += 1;
   }
   for (size_t i = 0; i < n; ++i) {
-    (flag[i] ? stats.in_kernel : stats.single) += 1;
+    (flag[i] ? stats.items_in_kernel : stats.items_single) += 1;
     outs[i] = cur[i].release();
   }
   if (in_kernel) std::copy(flag.begin(), flag.end(), in_kernel);

@@ -318,7 +318,7 @@ wfst_fst* replace_fst(wfst_ctx* ctx, uint32_t root_label, const uint32_t* labels
   // doubled and the expansion runs again from the start state.
   uint64_t slots = slots_knob ? slots_knob : wide_next_pow2(std::min<uint64_t>(std::max<uint64_t>(1ull << 17, 2 * sum_arcs), 1ull << 22));
   const double items = 1.0 + (double)sum_arcs / (double)std::max<uint64_t>(sum_states, 1);
-  const WideWho who{"replace", "result", &ctx->replace.grows};
+  const WideWho who{"replace", "result", &ctx->replace.arena_grows};
   for (;;) {
     DBuf<uint64_t> d_prefix(*ctx->pool, 2 * slots);
     HIP_CHECK(hipMemsetAsync(d_prefix.p, 0xFF, 2 * slots * sizeof(uint64_t), st));  // K_EMPTY, KHI_UNSET
@@ -344,9 +344,9 @@ wfst_fst* replace_fst(wfst_ctx* ctx, uint32_t root_label, const uint32_t* labels
     ctx->replace.arcs = w.n_arcs;
     ctx->replace.prefixes = hc[RP_PREFIXES];
     ctx->replace.max_depth = hc[RP_DEPTH];
-    ctx->replace.calls = hc[RP_CALLS];
-    ctx->replace.dropped = hc[RP_DROPPED];
-    ctx->replace.returns = hc[RP_RETURNS];
+    ctx->replace.call_arcs = hc[RP_CALLS];
+    ctx->replace.dropped_calls = hc[RP_DROPPED];
+    ctx->replace.return_arcs = hc[RP_RETURNS];
     return adopt_device(ctx, w.n_states, w.n_arcs, 0, word, w.off, w.arcs, w.fin);
   }
 }

@@ -1699,7 +1699,7 @@ const char* rearm_take(wfst_ctx* ctx, const wfst_fst* f, const Knobs& kn, RearmH
   }
   if (!ctx->pool->unpark(r.blk, RearmRecord::BLOCKS)) {  // (the pool's trim: hipFree has waited for the re-arm launch)
     r.clear();
-    ctx->rearm_dropped += 1;
+    ctx->rearm_stats.dropped += 1;
     return "blocks reclaimed";
   }
   held.rec = std::move(r);
@@ -2055,10 +2055,10 @@ void relax_setup_held(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, RearmHeld& he
         r.tau0_bits == tau0_bits) {
       sv.armed = true;
       sv.rearm_why = nullptr;
-      ctx->rearm_adopted += 1;
+      ctx->rearm_stats.adopted += 1;
     } else {  // (the blocks this solve took are its own now: whatever it queues comes behind the re-arm launch on the stream)
       sv.rearm_why = eligible ? "knobs differ" : "not eligible";
-      ctx->rearm_dropped += 1;
+      ctx->rearm_stats.dropped += 1;
       held.settle();
     }
   }
@@ -2819,7 +2819,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
       (void)sv.ctl.release();
       (void)sv.rs_msgs.release();
       (void)sv.rs_abort.release();
-      ctx->rearm_armed += 1;
+      ctx->rearm_stats.armed += 1;
     } else {
       HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -2829,16 +2829,16 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   // searched keys that are exact at and below B (never an extended solve: the flag is launch 0's).
   const bool b_stopped = j->drv.bounded;
   if (sv.bounded_on) {
-    if (b_stopped) ctx->bounded_stops += 1;
+    if (b_stopped) ctx->bounded.stops += 1;
     else {
       const uint32_t w = j->fused_tail ? j->h_tail->bounded_why : 0u;
-      ctx->bounded_refused += 1;
+      ctx->bounded.full_solves += 1;
       ctx->bounded_last_refusal = w == BOUNDED_WHY_BAND   ? "the head did not stop: no total at or below the first band"
                                   : w == BOUNDED_WHY_GREW ? "the head did not stop: a level outgrew its workgroup"
                                                           : "the head did not stop: its list did not run empty";
     }
   } else {
-    ctx->bounded_refused += 1;
+    ctx->bounded.full_solves += 1;
     ctx->bounded_last_refusal = ctx->profiling ? "not eligible: profiling is on" : sv.bounded_why ? sv.bounded_why : "not eligible";
   }
   if (b_stopped && j->fused_tail && (j->h_tail->pad & 8u) && !(j->h_tail->pad & 5u)) {

@@ -376,15 +376,6 @@ uint32_t grid_for(const wfst_ctx* ctx, uint64_t items) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + BLOCK - 1) / BLOCK, (uint64_t)ctx->n_cus * 8));
 }
 
-enum class Path { Auto, Narrow, Wide };
-Path path_knob() {
-  const char* e = std::getenv("WFST_TOP_SORT_PATH");
-  if (!e || !*e || !std::strcmp(e, "auto")) return Path::Auto;
-  if (!std::strcmp(e, "narrow")) return Path::Narrow;
-  if (!std::strcmp(e, "wide")) return Path::Wide;
-  throw Error(std::string("WFST_TOP_SORT_PATH: expected auto, narrow or wide, not '") + e + "'");
-}
-
 void check_operand(wfst_ctx* ctx, const wfst_fst* f, const char* op) {
   if (f->device != ctx->device) throw Error(std::string(op) + ": the operand lives on another device");
 }
@@ -467,7 +458,7 @@ wfst_fst* state_sort_fst(wfst_ctx* ctx, const wfst_fst* f, const uint32_t* order
 wfst_fst* top_sort_fst(wfst_ctx* ctx, const wfst_fst* f) {
   ctx->top_sort = wfst_ctx::TopSortStats{};
   wfst_ctx::TopSortStats& stats = ctx->top_sort;
-  const Path path = path_knob();
+  const Path path = path_knob("WFST_TOP_SORT_PATH");
   check_operand(ctx, f, "top_sort");
   const uint32_t n = f->n_states;
   const uint64_t word = f->props & props::ALL;

@@ -41,6 +41,14 @@ class Tr:
 
 
 # ------------------------------------------------------------------ context
+def _counters(family: str, ctx: "Context") -> dict:
+    """One family of route counters of ctx (_lib.COUNTERS) as a dict of ints, in the order of the getter's parameters."""
+    symbol, names = _lib.COUNTERS[family]
+    vals = [C.c_uint64() for _ in names]
+    check(getattr(_lib.lib(), symbol)(ctx._h, *[C.byref(v) for v in vals]), symbol)
+    return {k: int(v.value) for k, v in zip(names, vals)}
+
+
 class Context:
     """One engine context per (host thread, GPU): a HIP stream + device memory pools."""
 
@@ -80,11 +88,9 @@ class Context:
     def rearm_stats(self) -> dict:
         """Re-armed relaxation scratch of this context (wfst_ctx_get_rearm_stats): solves that parked their cleaned scratch
         (armed), that started from parked scratch without a set-up launch (adopted), parked scratch given back unused (dropped)."""
-        vals = [C.c_uint64() for _ in range(3)]
         if not hasattr(_lib.lib(), "wfst_ctx_get_rearm_stats"):  # (WFST_LIB_PATH: a build from before the counters)
             return dict(armed=0, adopted=0, dropped=0)
-        check(_lib.lib().wfst_ctx_get_rearm_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rearm_stats")
-        return dict(zip(("armed", "adopted", "dropped"), (int(v.value) for v in vals)))
+        return _counters("rearm", self)
 
     def bounded_stats(self) -> dict:
         """The bounded head of the single-shortest-path relaxation on this context (wfst_ctx_get_bounded_stats): queries whose
@@ -100,11 +106,7 @@ class Context:
         """Which path answered the small shortest-path queries of this context (wfst_ctx_get_small_path_stats): the last
         launch of the nshortest = 1 wave kernel (n1_in_kernel, n1_staged, n1_handed_back) and the last n-best batch
         (nbest_in_kernel, nbest_tree_full, nbest_out_full, nbest_tree_capacity)."""
-        names = ("n1_in_kernel", "n1_staged", "n1_handed_back", "nbest_in_kernel", "nbest_tree_full", "nbest_out_full",
-                 "nbest_tree_capacity")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_small_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_small_path_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("small_path", self)
 
     def compose_path_stats(self) -> dict:
         """Which route answered the problems of this context's last compose / compose_shortest_path_batch call
@@ -112,20 +114,13 @@ class Context:
         wave kernel's first launch (wave_first), relaunches with a 4x arena by overflow status (relaunch_states / _arcs /
         _hash / _path), the wide driver (switched_wide), the two-step route (two_step), and the capacities of the last
         wave launch (caps_states, caps_arcs, caps_hash)."""
-        names = ("string_answered", "string_handed_back", "wave_first", "relaunch_states", "relaunch_arcs", "relaunch_hash",
-                 "relaunch_path", "switched_wide", "two_step", "caps_states", "caps_arcs", "caps_hash")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_compose_path_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_compose_path_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("compose_path", self)
 
     def string_run_stats(self) -> dict:
         """The chase runs of the string kernel in this context's last compose_shortest_path_batch call
         (wfst_ctx_get_string_run_stats): levels taken inside runs (run_levels) and the number of runs (runs), summed over
         the problems the kernel answered.  Both are 0 with WFST_STRING_RUN=0 and on the scalar-row path."""
-        names = ("run_levels", "runs")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_string_run_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_string_run_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("string_run", self)
 
     def determinize_stats(self) -> dict:
         """Which route the levels of this context's last determinize / determinize_with_distance call took
@@ -134,12 +129,7 @@ class Context:
         exit_budget, exit_need, exit_done), device-wide checks that asked for room (wide_need), arrays enlarged (grow_states,
         grow_elts, grow_arcs, grow_cands, rehashes), their final sizes (cap_states, cap_elts, cap_arcs, cap_cands) and the most
         resolve rounds of a device-wide level (rounds_max).  Unspecified after a batch call."""
-        names = ("levels", "wide_levels", "narrow_launches", "exit_wide_states", "exit_wide_cands", "exit_budget", "exit_need",
-                 "exit_done", "wide_need", "grow_states", "grow_elts", "grow_arcs", "grow_cands", "rehashes", "cap_states",
-                 "cap_elts", "cap_arcs", "cap_cands", "rounds_max")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_determinize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_determinize_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("determinize", self)
 
     def minimize_stats(self) -> dict:
         """Which route this context's last minimize call took (wfst_ctx_get_minimize_stats).  For the cycle check on the
@@ -148,11 +138,7 @@ class Context:
         by how they ended (exit_wide, exit_done).  For the call: the branch taken (branch: 0 none, 1 unweighted, 2 weighted,
         3 weighted without a start state, 4 nothing left after connect), states a wave refined (wave_states) and full
         signature compares that found a difference (unequal_compares).  Unspecified after minimize_batch and optimize."""
-        names = ("check_levels", "check_wide_levels", "check_narrow_launches", "check_exit_wide", "check_exit_done", "levels",
-                 "wide_levels", "narrow_launches", "exit_wide", "exit_done", "branch", "wave_states", "unequal_compares")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_minimize_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_minimize_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("minimize", self)
 
     def push_stats(self) -> dict:
         """Which route this context's last shortest_distance(reverse=..) with a length, reweight or push_weights call took
@@ -162,11 +148,7 @@ class Context:
         the structural facts were searched (structural), the start branch (start_branch: 0 not taken, 1 in place, 2 new
         start state) and remove_total_weight (removed: 0 not requested, 1 skipped, 2 applied).  Unspecified after any other
         call."""
-        names = ("searches", "rounds", "reads", "rounds_max", "bfs_blocks", "arcs_blocks", "total_blocks", "structural",
-                 "start_branch", "removed")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_push_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_push_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("push", self)
 
     def top_sort_stats(self) -> dict:
         """Which route this context's last top_sort call took (wfst_ctx_get_top_sort_stats): Kahn levels peeled (levels),
@@ -174,11 +156,7 @@ class Context:
         wide_launches), levels peeled inside one-workgroup launches (narrow_levels), the widest level (max_level_width), the
         deepest state of the search forest (max_tree_depth), rows of the ancestor table (lift_rows), states with in-arcs from
         at least two states (states_compared), states a whole wave took (wave_states) and the CYCLIC exit (cyclic)."""
-        names = ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "max_tree_depth", "lift_rows",
-                 "states_compared", "wave_states", "cyclic")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_top_sort_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_top_sort_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("top_sort", self)
 
     def replace_stats(self) -> dict:
         """This context's last replace call (wfst_ctx_get_replace_stats): levels of the search, states and arcs of the result,
@@ -186,11 +164,7 @@ class Context:
         dropped for a callee without a start state, return arcs emitted, times the search's arena grew (arena_grows) and
         times the expansion ran again with a larger call-stack table (prefix_reruns), and the level kernels queued
         (level_launches: three per level, idle ones behind the last level included)."""
-        names = ("levels", "states", "arcs", "prefixes", "max_depth", "call_arcs", "dropped_calls", "return_arcs", "arena_grows",
-                 "prefix_reruns", "level_launches")
-        vals = [C.c_uint64() for _ in names]
-        check(_lib.lib().wfst_ctx_get_replace_stats(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_replace_stats")
-        return dict(zip(names, (int(v.value) for v in vals)))
+        return _counters("replace", self)
 
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
@@ -819,13 +793,6 @@ def _batch_call(fn_name, fsts, ctx, want_flags, *config):
     return (res, flags) if want_flags else res
 
 
-def _batch_stats(fn_name, ctx):
-    ctx = ctx or default_context()
-    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    check(getattr(_lib.lib(), fn_name)(ctx._h, C.byref(a), C.byref(b), C.byref(c)), fn_name)
-    return dict(launches=a.value, items_in_kernel=b.value, items_single=c.value)
-
-
 def determinize_batch(fsts: Sequence[DeviceFst], config: Optional["DeterminizeConfig"] = None,
                       ctx: Optional[Context] = None, want_flags: bool = False):
     """[f.determinize(config) for f in fsts] as ONE call (wfst_determinize_batch): one workgroup per acceptor, one launch
@@ -869,16 +836,12 @@ def _device_replace(root_idx: int, fst_list, epsilon_on_replace: bool, ctx: Opti
 
 def determinize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last determinize_batch / determinize_with_distance_batch call of ctx (wfst_ctx_get_determinize_batch_stats)."""
-    return _batch_stats("wfst_ctx_get_determinize_batch_stats", ctx)
+    return _counters("determinize_batch", ctx or default_context())
 
 
 def rm_epsilon_stats(ctx: Optional[Context] = None) -> dict:
     """The last rm_epsilon call of ctx (wfst_ctx_get_rm_epsilon_stats)."""
-    ctx = ctx or default_context()
-    names = ("batches", "thread_launches", "wave_launches", "states_thread", "states_wave", "max_closure_cap")
-    vals = [C.c_uint64() for _ in names]
-    check(_lib.lib().wfst_ctx_get_rm_epsilon_stats(ctx._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_rm_epsilon_stats")
-    return {k: v.value for k, v in zip(names, vals)}
+    return _counters("rm_epsilon", ctx or default_context())
 
 
 def minimize_batch(fsts: Sequence[DeviceFst], config: Optional["MinimizeConfig"] = None, ctx: Optional[Context] = None,
@@ -893,7 +856,7 @@ def minimize_batch(fsts: Sequence[DeviceFst], config: Optional["MinimizeConfig"]
 
 def minimize_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last minimize_batch call of ctx (wfst_ctx_get_minimize_batch_stats)."""
-    return _batch_stats("wfst_ctx_get_minimize_batch_stats", ctx)
+    return _counters("minimize_batch", ctx or default_context())
 
 
 def rm_epsilon_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
@@ -908,7 +871,7 @@ def rm_epsilon_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, r
 
 def rm_epsilon_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last rm_epsilon_batch call of ctx (wfst_ctx_get_rm_epsilon_batch_stats)."""
-    return _batch_stats("wfst_ctx_get_rm_epsilon_batch_stats", ctx)
+    return _counters("rm_epsilon_batch", ctx or default_context())
 
 
 def tr_sum_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
@@ -926,7 +889,7 @@ def tr_unique_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, re
 
 def tr_sum_batch_stats(ctx: Optional[Context] = None) -> dict:
     """The last tr_sum_batch / tr_unique_batch call of ctx (wfst_ctx_get_tr_sum_batch_stats)."""
-    return _batch_stats("wfst_ctx_get_tr_sum_batch_stats", ctx)
+    return _counters("tr_sum_batch", ctx or default_context())
 
 
 def optimize_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):

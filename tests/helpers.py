@@ -162,6 +162,39 @@ def ko_message(status):
     return text
 
 
+def header_params(header, name):
+    """the parameter list of `name` as include/wfst.h declares it, comments dropped and white space folded"""
+    import re
+    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
+    assert m, name
+    return " ".join(re.sub(r"/\*.*?\*/", " ", m.group(1), flags=re.S).split()).replace(" ,", ",")
+
+
+def null_ctx_is_ko(lib, name, n):
+    """a null ctx is KO with "null", and what the first out-pointer points at is left as it was"""
+    v = C.c_uint64(5)
+    assert "null" in ko_message(getattr(lib, name)(None, C.byref(v), *[None] * (n - 1)))
+    assert v.value == 5
+
+
+def check_counter_getter(lib, name, counters, accessor):
+    """The plumbing of one route-counter getter, against the test's own restatement of its counters: declared in wfst.h as
+    (wfst_ctx* ctx, uint64_t* <counter>, ...) in that order, bound with those argtypes, exported, named in the version-7
+    note of WFST_ABI_VERSION by a library of that version, read by a callable Python accessor, and KO on a null ctx."""
+    import re
+    from rustfst_amd import _lib
+    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
+        header = f.read()
+    assert header_params(header, name) == "wfst_ctx* ctx, " + ", ".join("uint64_t* " + k for k in counters)
+    bound = {n: a for n, _, a in _lib.SYMBOLS}
+    assert bound[name] == [C.c_void_p] + [C.POINTER(C.c_uint64)] * len(counters) and hasattr(lib, name)
+    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
+    assert m and name in m.group(1).split("; 6:")[0] and lib.wfst_abi_version() == 7
+    assert callable(accessor)
+    null_ctx_is_ko(lib, name, len(counters))
+    return header
+
+
 FILTERS = [ComposeFilter.NULLFILTER, ComposeFilter.TRIVIALFILTER, ComposeFilter.SEQUENCEFILTER,
            ComposeFilter.ALTSEQUENCEFILTER, ComposeFilter.MATCHFILTER, ComposeFilter.NOMATCHFILTER]
 

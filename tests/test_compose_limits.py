@@ -18,10 +18,8 @@ n_states - 1 arcs.  Neither can fill before 2^31 arcs.  A hash overflow needs hi
 n_arcs + emitted <= A: under the fused batch's caps (A = 2 S) that asks for hi > n_arcs + 64 states, and every state but the
 first has an arc into it — it cannot occur there at any attempt; under compose()'s caps (A = 4 S) one level of 4032 arcs
 into one state does it at S = 1280, H = 4096."""
-import ctypes as C
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -600,34 +598,21 @@ def same(got, exp, what):
 
 # ================================================================ no GPU
 def test_new_symbol_declared_exported_and_bound(wfst_lib):
-    from rustfst_amd import _lib
     import rustfst_amd
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
     name = "wfst_ctx_get_compose_path_stats"
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m and " ".join(m.group(1).split()) == "wfst_ctx* ctx, " + ", ".join("uint64_t* " + k for k in COUNTERS)
-    u64 = C.POINTER(C.c_uint64)
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert bound[name] == [C.c_void_p] + [u64] * len(COUNTERS) and hasattr(wfst_lib, name)
-    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
-    assert m and name in m.group(1).split("; 6:")[0] and wfst_lib.wfst_abi_version() == 7
+    header = helpers.check_counter_getter(wfst_lib, name, COUNTERS, rustfst_amd.Context.compose_path_stats)
     text = header[header.index("which route answered the problems of the last wfst_compose"):header.index("wfst_status " + name)]
     text = " ".join(text.replace("\n *", " ").split())
     for limit in ("at most 2048 states", "at most 12 arcs", "more than 64 states", "512 / 1024 / 2048", "2 * max_states + 64",
                   "at most 64 arcs", "items = arcs + 1", "4 * max(min(n1, n2), 64) + 1024", "A = 4 * S", "4 * max(max_states, 64) + 256",
                   "A = 2 * S", "2 * S + 128", "hi + emitted + 64 <= H", "S = 16384", "batches of at most 8", "at least 16"):
         assert limit in text, limit
-    assert callable(rustfst_amd.Context.compose_path_stats)
     with open(os.path.join(ROOT, "DESIGN.md")) as f:
         assert name in f.read()
 
 
 def test_null_ctx_is_ko(wfst_lib):
-    v = C.c_uint64(5)
-    args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_compose_path_stats(None, *args))
-    assert v.value == 5
+    helpers.null_ctx_is_ko(wfst_lib, "wfst_ctx_get_compose_path_stats", len(COUNTERS))
 
 
 def test_capacity_formulas():

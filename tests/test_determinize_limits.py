@@ -30,10 +30,7 @@ different levels in descending order and the LAST match is the lowest id with or
 of one sequence created in the SAME wide level can sit on the chain in ascending order (their atomicExch race), which no
 input can force; lowest_id_same_level is the input in which it would show."""
 import collections
-import ctypes as C
 import functools
-import os
-import re
 import time
 
 import numpy as np
@@ -48,7 +45,6 @@ import helpers
 from helpers import assert_flat_identical, to_device, to_oracle
 import inputs
 
-ROOT = helpers.ROOT
 PATHS = ("auto", "narrow", "wide")
 NARROW_STATES, NARROW_CANDS, BUDGET = 256, 8192, 1 << 16  # determinize.hip
 FIRST_RESERVE = (1024, 4096, 4096, 4096)  # states, elements, arcs, candidates of one level
@@ -482,26 +478,12 @@ def same(got, exp, what):
 
 # ================================================================ no GPU
 def test_new_symbol_declared_exported_and_bound(wfst_lib):
-    from rustfst_amd import _lib
     import rustfst_amd
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
-    name = "wfst_ctx_get_determinize_stats"
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m and " ".join(m.group(1).split()) == "wfst_ctx* ctx, " + ", ".join("uint64_t* " + k for k in COUNTERS)
-    u64 = C.POINTER(C.c_uint64)
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert bound[name] == [C.c_void_p] + [u64] * len(COUNTERS) and hasattr(wfst_lib, name)
-    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
-    assert m and name in m.group(1).split("; 6:")[0] and wfst_lib.wfst_abi_version() == 7
-    assert callable(rustfst_amd.Context.determinize_stats)
+    helpers.check_counter_getter(wfst_lib, "wfst_ctx_get_determinize_stats", COUNTERS, rustfst_amd.Context.determinize_stats)
 
 
 def test_null_ctx_is_ko(wfst_lib):
-    v = C.c_uint64(5)
-    args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_determinize_stats(None, *args))
-    assert v.value == 5
+    helpers.null_ctx_is_ko(wfst_lib, "wfst_ctx_get_determinize_stats", len(COUNTERS))
 
 
 def _stats(**kw):

@@ -30,6 +30,66 @@ def test_library_exports_every_declared_symbol(wfst_lib):
     assert wfst_lib.wfst_abi_version() == 7
 
 
+def _counter_structs(common):
+    """The route-counter structs of csrc/common.h, as the source states them: ({struct: field names}, {wfst_ctx member:
+    struct}).  A struct is `struct <Name>Stats { ... }`, closed by the matching brace; what follows the brace up to ';' are
+    the members declared with it, and `wfst::<Name>Stats a, b;` declares more.  The fields are the declarators of the
+    `uint64_t a = 0, b = 0;` statements of the body, comments dropped — except where the body holds a `// flat: a, b, ...`
+    comment (MinimizeStats, whose two nested passes lie flat in that order): then they are the names of that comment,
+    which runs on over the `//` lines behind it."""
+    fields, member_of = {}, {}
+    for m in re.finditer(r"\bstruct (\w+Stats) \{", common):
+        depth, end = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(common[end], 0)
+            end += 1
+        body = common[m.end():end - 1]
+        flat = re.search(r"// flat:((?:[^\n]*\n\s*//)*[^\n]*)", body)
+        if flat:
+            names = re.findall(r"\w+", flat.group(1).replace("//", " "))
+        else:
+            code = re.sub(r"//[^\n]*", "", body)
+            code = re.sub(r"\buint64_t \w+\[\d+\] = \{[^}]*\};", "", code)  # (the array OptimizeBatchStats begins with)
+            names = [d.split("=")[0].strip() for stmt in re.findall(r"\buint64_t\s+([^;]*);", code) for d in stmt.split(",")]
+            assert re.sub(r"\buint64_t\s+[^;]*;", "", code).strip() == "", (m.group(1), "holds more than uint64_t fields")
+        fields[m.group(1)] = names
+        for member in re.findall(r"\w+", common[end:common.index(";", end)]):
+            member_of[member] = m.group(1)
+    for m in re.finditer(r"\bwfst::(\w+Stats) ([\w, ]+);", common):
+        for member in re.findall(r"\w+", m.group(2)):
+            member_of[member] = m.group(1)
+    return fields, member_of
+
+
+def test_counter_tables_agree():
+    """_lib.COUNTERS, the parameters of include/wfst.h, the braces of api.cpp's getters and the fields of the family's
+    struct in common.h name the same counters in the same order: a swapped pair anywhere fails here."""
+    def read(*path):
+        with open(os.path.join(ROOT, *path)) as f:
+            return f.read()
+    header = re.sub(r"/\*.*?\*/", "", read("include", "wfst.h"), flags=re.S)
+    fields, member_of = _counter_structs(read("rustfst_amd", "csrc", "common.h"))
+    getters = dict((name, (member, re.findall(r"\w+", args))) for name, member, args in re.findall(
+        r"wfst_status (wfst_ctx_get_\w+_stats)\([^)]*\) \{\s*return get_counters\(ctx, &wfst_ctx::(\w+), \{([^}]*)\}\);\s*\}",
+        read("rustfst_amd", "csrc", "api.cpp")))
+    assert len(_lib.COUNTERS) == 14
+    for family, (symbol, names) in _lib.COUNTERS.items():
+        assert symbol == "wfst_ctx_get_%s_stats" % family
+        params = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % symbol, header).group(1)
+        assert " ".join(params.split()) == "wfst_ctx* ctx, " + ", ".join("uint64_t* " + k for k in names), symbol
+        member, passed = getters[symbol]
+        assert passed == list(names), (symbol, "api.cpp passes its out-pointers in another order")
+        assert fields[member_of[member]] == list(names), (symbol, member_of[member])
+    declared = set(re.findall(r"\bwfst_status\s+(wfst_ctx_get_\w+_stats)\s*\(", header))
+    table = {symbol for symbol, _ in _lib.COUNTERS.values()}
+    assert declared == table | {"wfst_ctx_get_optimize_batch_stats", "wfst_ctx_get_bounded_stats"} and len(declared) == 16
+    # the two exceptions: the plain counters behind the array / before the string are the struct's fields all the same
+    assert fields["OptimizeBatchStats"] == ["items_in_kernel", "items_single", "items_transducer"]
+    assert fields["BoundedStats"] == ["stops", "full_solves"]
+    # no two getters read one member
+    assert len(set(member for member, _ in getters.values())) == len(getters) == 14
+
+
 def test_no_torch_types_in_the_abi():
     text = open(os.path.join(ROOT, "include", "wfst.h")).read()
     assert "torch" not in re.sub(r"/\*.*?\*/", "", text, flags=re.S)

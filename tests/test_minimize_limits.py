@@ -17,9 +17,7 @@ share the upper 32 bits of a 64-bit hash AND meet on one probe chain; which chai
 concurrent lanes.  test_default_run_records_unequal_compares therefore asserts only that the result is unchanged and
 prints the figure.  With WFST_MINIMIZE_HASH_BITS=0 there is a bound that does not depend on the order (test_hash_bits)."""
 import collections
-import ctypes as C
 import functools
-import os
 import re
 
 import numpy as np
@@ -30,7 +28,6 @@ from oracle import model
 import helpers
 from helpers import assert_flat_identical, to_device
 
-ROOT = helpers.ROOT
 INF, ACCEPTOR = model.INF, model.ACCEPTOR
 PATHS = ("auto", "narrow", "wide")
 NARROW_MAX, LANE_MAX_DEG, NARROW_WAVES = 4096, 64, 16  # minimize.hip (a 1024-thread workgroup: 16 waves)
@@ -304,27 +301,13 @@ PROFILES = {"one_4096": (300, 4096) + TAPER, "one_4097": (300, 4097) + TAPER, "s
 
 # ================================================================ no GPU
 def test_new_symbol_declared_exported_and_bound(wfst_lib):
-    from rustfst_amd import _lib
     import rustfst_amd
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
-    name = "wfst_ctx_get_minimize_stats"
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m and " ".join(m.group(1).split()) == "wfst_ctx* ctx, " + ", ".join("uint64_t* " + k for k in COUNTERS)
-    u64 = C.POINTER(C.c_uint64)
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert bound[name] == [C.c_void_p] + [u64] * len(COUNTERS) and hasattr(wfst_lib, name)
-    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
-    assert m and name in m.group(1).split("; 6:")[0] and wfst_lib.wfst_abi_version() == 7
-    assert callable(rustfst_amd.Context.minimize_stats)
+    header = helpers.check_counter_getter(wfst_lib, "wfst_ctx_get_minimize_stats", COUNTERS, rustfst_amd.Context.minimize_stats)
     assert "WFST_MINIMIZE_HASH_BITS" in header
 
 
 def test_null_ctx_is_ko(wfst_lib):
-    v = C.c_uint64(5)
-    args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_minimize_stats(None, *args))
-    assert v.value == 5
+    helpers.null_ctx_is_ko(wfst_lib, "wfst_ctx_get_minimize_stats", len(COUNTERS))
 
 
 def _pass(prefix="", **kw):

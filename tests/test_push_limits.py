@@ -513,29 +513,15 @@ def facts_cases(n, seed=71):
 # ================================================================ no GPU
 def test_symbol_declared_and_bound(wfst_lib):
     import rustfst_amd
-    from rustfst_amd import _lib
     name = "wfst_ctx_get_push_stats"
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
-    assert re.search(r"\bwfst_status\s+" + name + r"\s*\(", header)
-    u64 = C.POINTER(C.c_uint64)
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert bound[name] == [C.c_void_p] + [u64] * len(COUNTERS) and hasattr(wfst_lib, name)
-    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
-    assert m and name in m.group(1).split("; 6:")[0] and wfst_lib.wfst_abi_version() == 7
-    assert callable(rustfst_amd.Context.push_stats)
-    for c in COUNTERS:
-        assert re.search(r"\buint64_t\*\s+" + c + r"\b", header), c
+    header = helpers.check_counter_getter(wfst_lib, name, COUNTERS, rustfst_amd.Context.push_stats)
     assert KNOB in header and "unspecified" in header.split("wfst_status " + name)[0].rsplit("/* ----", 1)[1]
     with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
         assert name in f.read()
 
 
 def test_null_ctx_is_ko(wfst_lib):
-    v = C.c_uint64(5)
-    args = [C.byref(v)] + [None] * (len(COUNTERS) - 1)
-    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_push_stats(None, *args))
-    assert v.value == 5
+    helpers.null_ctx_is_ko(wfst_lib, "wfst_ctx_get_push_stats", len(COUNTERS))
 
 
 def test_constants_are_the_kernels():

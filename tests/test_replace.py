@@ -22,6 +22,8 @@ from replace_ref import Diverged, ReplaceError, replace_ref
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k20_replace.json")
 NEW_SYMBOLS = ("wfst_replace", "wfst_ctx_get_replace_stats")
+COUNTERS = ("levels", "states", "arcs", "prefixes", "max_depth", "call_arcs", "dropped_calls", "return_arcs", "arena_grows",
+            "prefix_reruns", "level_launches")
 MSG_CYCLIC = "replace: cyclic dependency between the FSTs: the reference does not terminate on this input"
 MSG_ROOT = "ReplaceFstImpl: No FST corresponding to root label {} in the input tuple vector"
 KEY0 = 50  # FST i of a random grammar has the label KEY0 + 2 i: the odd labels between are in range and no key
@@ -174,6 +176,8 @@ def test_symbols_declared_and_bound(wfst_lib):
         assert re.search(r"\bwfst_status\s+" + name + r"\s*\(", header), name
         assert name in bound, name
         assert hasattr(wfst_lib, name), name
+    import rustfst_amd
+    helpers.check_counter_getter(wfst_lib, "wfst_ctx_get_replace_stats", COUNTERS, rustfst_amd.Context.replace_stats)
     assert re.search(r"typedef\s+struct\s*\{\s*uint32_t\s+label;\s*const\s+wfst_fst\*\s+fst;\s*\}\s*wfst_label_fst_pair;", header)
     m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
     assert m and all(name in m.group(1).split("; 6:")[0] for name in NEW_SYMBOLS) and wfst_lib.wfst_abi_version() == 7

@@ -11,8 +11,6 @@ retries changes.  Weights are on the 1/512 grid, where the exact minimum the ker
 import ctypes as C
 import functools
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -24,7 +22,6 @@ from oracle.model import F32, INF
 import helpers
 from helpers import assert_flat_identical, random_fst_flat, to_device, to_oracle
 
-ROOT = helpers.ROOT
 
 # The retry ladder of rm_epsilon_fst, restated once (rustfst_amd/csrc/rm_epsilon.hip, the attempt loop of rm_epsilon_fst:
 # `RmCaps caps{16, 32, 32}`, `RmBigCaps big{1024, 1024, 1024}`, `const bool wave = caps.C > 64`, every size times 4 per
@@ -541,20 +538,8 @@ def props_hand_made():
 
 # ================================================================ no GPU
 def test_stats_symbol_declared_exported_and_bound(wfst_lib):
-    from rustfst_amd import _lib
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
-    name = "wfst_ctx_get_rm_epsilon_stats"
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m, name
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert args[0] == "wfst_ctx* ctx" and args[1:] == ["uint64_t* " + k for k in STAT_KEYS]
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert name in bound and hasattr(wfst_lib, name)
-    assert bound[name] == [C.c_void_p] + [C.POINTER(C.c_uint64)] * len(STAT_KEYS)
-    assert wfst_lib.wfst_abi_version() == 7
-    version_comment = header[header.index("#define WFST_ABI_VERSION"):header.index("typedef enum")]
-    assert name in version_comment
+    import rustfst_amd
+    helpers.check_counter_getter(wfst_lib, "wfst_ctx_get_rm_epsilon_stats", STAT_KEYS, rustfst_amd.rm_epsilon_stats)
 
 
 def test_stats_null_context_is_ko(wfst_lib):

@@ -7,11 +7,8 @@ on the same handles, bit for bit including the property word, and the counters a
 
 Weights are on the 1/4 grid (many ties) or the 1/512 grid (few): sums of them are exact in f32 and in Python floats alike,
 which is what lets the restatement compute distances and search keys with Python floats."""
-import ctypes as C
 import functools
 import heapq
-import os
-import re
 
 import numpy as np
 import pytest
@@ -23,7 +20,6 @@ import helpers
 from helpers import (NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, assert_flat_identical, check_nbest_against_brute_force,
                      enumerate_paths, to_device, to_oracle)
 
-ROOT = helpers.ROOT
 INF = float("inf")
 # ---- the limits of nbest_batch.hip, restated (include/wfst.h states them in numbers)
 SP1_MAX_STATES, SP1_MAX_ARCS, SP1_LONE_ARCS = 4096, 16384, 2048
@@ -444,31 +440,18 @@ def same(got, exp, what):
 
 # ================================================================ no GPU
 def test_new_symbol_declared_exported_and_bound(wfst_lib):
-    from rustfst_amd import _lib
     import rustfst_amd
-    with open(os.path.join(ROOT, "include", "wfst.h")) as f:
-        header = f.read()
     name = "wfst_ctx_get_small_path_stats"
-    want = ("wfst_ctx* ctx, uint64_t* n1_in_kernel, uint64_t* n1_staged, uint64_t* n1_handed_back, uint64_t* nbest_in_kernel, "
-            "uint64_t* nbest_tree_full, uint64_t* nbest_out_full, uint64_t* nbest_tree_capacity")
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m and " ".join(m.group(1).split()) == want
-    u64 = C.POINTER(C.c_uint64)
-    bound = {n: a for n, _, a in _lib.SYMBOLS}
-    assert bound[name] == [C.c_void_p] + [u64] * 7 and hasattr(wfst_lib, name)
-    m = re.search(r"#define\s+WFST_ABI_VERSION\s+7\b(.*)", header)
-    assert m and name in m.group(1).split("; 6:")[0] and wfst_lib.wfst_abi_version() == 7
+    assert len(COUNTERS) == 7
+    header = helpers.check_counter_getter(wfst_lib, name, COUNTERS, rustfst_amd.Context.small_path_stats)
     text = header[header.index("which path answered the small shortest-path queries"):header.index("wfst_status " + name)]
     for limit in ("4096 states", "16384 arcs", "2048 arcs", "2048 states", "4096 arcs", "8192 arcs", "nshortest <= 64",
                   "min(16384, max(2048, 2 * nshortest * (max_n + 8)))"):
         assert limit in text, limit
-    assert callable(rustfst_amd.Context.small_path_stats)
 
 
 def test_null_ctx_is_ko(wfst_lib):
-    v = C.c_uint64(5)
-    assert "null" in helpers.ko_message(wfst_lib.wfst_ctx_get_small_path_stats(None, C.byref(v), None, None, None, None, None, None))
-    assert v.value == 5
+    helpers.null_ctx_is_ko(wfst_lib, "wfst_ctx_get_small_path_stats", 7)
 
 
 def test_generators_hit_their_counts():

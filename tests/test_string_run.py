@@ -171,18 +171,9 @@ def inf_t(n=140):
 # ================================================================ no GPU
 def test_new_symbol_declared_exported_and_bound(wfst_lib):
     import ctypes as C
-    import os
-    import re
     import rustfst_amd
-    from rustfst_amd import _lib
     name = "wfst_ctx_get_string_run_stats"
-    with open(os.path.join(helpers.ROOT, "include", "wfst.h")) as f:
-        header = f.read()
-    m = re.search(r"\bwfst_status\s+%s\s*\(([^)]*)\)" % name, header)
-    assert m and " ".join(m.group(1).split()) == "wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs"
-    u64 = C.POINTER(C.c_uint64)
-    assert {n: a for n, _, a in _lib.SYMBOLS}[name] == [C.c_void_p, u64, u64] and hasattr(wfst_lib, name)
-    assert callable(rustfst_amd.Context.string_run_stats)
+    helpers.check_counter_getter(wfst_lib, name, ("run_levels", "runs"), rustfst_amd.Context.string_run_stats)
     v = C.c_uint64(5)
     assert wfst_lib.wfst_ctx_get_string_run_stats(None, C.byref(v), C.byref(v)) != 0 and v.value == 5
 

@@ -311,6 +311,11 @@ SHAPES.update({f"cyclic_{kind}": (lambda kind=kind: cyclic(kind, 900)) for kind 
 
 
 # ================================================================ no GPU
+def test_getter_declared_exported_and_bound(wfst_lib):
+    import rustfst_amd
+    helpers.check_counter_getter(wfst_lib, "wfst_ctx_get_top_sort_stats", COUNTERS, rustfst_amd.Context.top_sort_stats)
+
+
 def test_constants_are_the_kernels():
     with open(os.path.join(ROOT, "rustfst_amd", "csrc", "top_sort.hip")) as f:
         src = f.read()
