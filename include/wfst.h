@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -115,8 +115,8 @@ wfst_status wfst_fst_destroy_many(wfst_fst* const* fsts, size_t n);
  * compose_filter uses the ffi numbering (compose.rs:20-33): 0 Auto (= Sequence, compose_fst.rs:58-92), 1 Null,
  * 2 Trivial, 3 Sequence, 4 AltSequence, 5 Match, 6 NoMatch — all with the default SortedMatcher pair
  * (rustfst/src/algorithms/compose/compose_filters/{null,trivial,sequence,alt_sequence,match,no_match}_compose_filter.rs);
- * custom matcher configs (sigma matcher) are not part of this ABI.  cfg == NULL means
- * ComposeConfig::default() = {Auto, connect = true} (compose_static.rs:56-65).
+ * matcher configs (the sigma matcher) go through wfst_compose_with_matchers below, wfst_compose_config keeps its layout.
+ * cfg == NULL means ComposeConfig::default() = {Auto, connect = true} (compose_static.rs:56-65).
  * KO with the reference's message when neither side is known label-sorted
  * (compose/compose_fst_op.rs:169-197).  Output state ids / arc order are the reference's
  * (FIFO BFS discovery order, then stable trim: lazy/lazy_fst.rs:226-269, connect.rs:51-66). ---- */
@@ -126,6 +126,48 @@ typedef struct {
 } wfst_compose_config;
 wfst_status wfst_compose(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2,
                          const wfst_compose_config* cfg, wfst_fst** out);
+
+/* ---- compose with matcher configs: fst_compose_with_config with a non-empty matcher1_config / matcher2_config
+ *      (rustfst-ffi/src/algorithms/compose.rs:183-250) = compose_with_config with SigmaMatcher<SortedMatcher> on side 1 (m1),
+ *      side 2 (m2) or both (compose_static.rs:78-109, 166-266; compose/matchers/sigma_matcher.rs): an arc labelled
+ *      sigma_label on the matched tape (olabel of fst1, ilabel of fst2) stands for "any other label".  m1 == m2 == NULL is
+ *      wfst_compose, call for call.  Otherwise the call runs on the wide driver whatever its size, and returns bit for bit
+ *      what the reference returns, the property word (that of the plain call) included.
+ *      iter(state, label) of a sigma side (sigma_matcher.rs:190-239): whatever the sorted matcher yields for `label`, if it
+ *      yields anything (for label 0 the epsilon loop, so always), unrewritten; otherwise the state's sigma arcs, in order and
+ *      rewritten, iff `label` is neither 0 nor NO_LABEL and sigma_allowed_matches is unrestricted or holds it.  Exhausted exact
+ *      matches do NOT fall through to the sigma arcs (the branch of :270-284 is dead; OpenFst's matcher differs).
+ *      Rewriting (:246-266): rewrite_mode 0 Auto = 1 iff the sigma operand's word says ACCEPTOR, else 2; 1 Always: each of
+ *      ilabel / olabel that equals sigma becomes the matched label; 2 Never: only the matched tape's label is set.
+ *      n_allowed == 0 means no restriction (rustfst-ffi compose.rs:199-211); order and duplicates do not matter.
+ *      sigma_label == WFST_NO_LABEL: no state has a sigma arc, the result is wfst_compose's (on the wide driver).
+ *      KO, in this order: rewrite_mode > 2 "unknown rewrite_mode"; sigma_label 0 "SigmaMatcher: 0 cannot be used as
+ *      sigma_label" (sigma_matcher.rs:64-66); compose_filter 0 "Custom MatcherConfig not supported with AutoFilter"
+ *      (compose_static.rs:186-191); a side with a real sigma that is not known sorted on its matched tape "ComposeFst: 1st
+ *      [2nd] argument cannot perform required matching (sort?)" (compose_fst_op.rs:169-180; an unknown bit pair: "...
+ *      label-sortedness properties are not known (sort?)"); then the mode errors of wfst_compose.  While composing: the first
+ *      offending composed state in id order, and within it first "Both sides can't require match" (both states carry a sigma
+ *      arc and both sides are sorted, compose_fst_op.rs:207-209), then per item of the iterated side "SigmaMatcher::Find: bad
+ *      label (sigma)" (its label IS the searched side's sigma, sigma_matcher.rs:199-201).  The context works on after a KO.
+ *      wfst_stats.compose_states / compose_arcs are set; arena growths go to compose_retries and to arena_grows below. ---- */
+typedef struct {
+  uint32_t sigma_label;
+  uint32_t rewrite_mode; /* 0 Auto, 1 Always, 2 Never (MatcherRewriteMode) */
+  const uint32_t* sigma_allowed_matches;
+  size_t n_allowed; /* 0 = unrestricted */
+} wfst_matcher_config;
+wfst_status wfst_compose_with_matchers(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2, const wfst_compose_config* cfg,
+                                       const wfst_matcher_config* m1, const wfst_matcher_config* m2, wfst_fst** out);
+/* the last wfst_compose_with_matchers call of ctx that had a config (reset when it begins; all 0 after a KO or an empty
+ * result, except arena_grows): levels of the search, states and arcs before connect, composed states whose fst1 / fst2 state
+ * carries a sigma arc, items (loop item included) of a sigma side that its sorted matcher answered, that its sigma arcs
+ * answered, the arcs those emitted, items the allowed set refused, growths of the arena, level launches queued.  A level
+ * that is emitted again after an overflow counts its items again.  Any out-pointer may be NULL.  (Not one of the
+ * wfst_ctx_get_*_stats route-counter families: it is read through the same helper, outside their table.) */
+wfst_status wfst_ctx_get_compose_sigma_counters(wfst_ctx* ctx, uint64_t* levels, uint64_t* states, uint64_t* arcs,
+                                             uint64_t* require1_states, uint64_t* require2_states, uint64_t* exact_items,
+                                             uint64_t* sigma_items, uint64_t* sigma_arcs, uint64_t* refused_items,
+                                             uint64_t* arena_grows, uint64_t* level_launches);
 
 /* ---- shortest path: fst_shortest_path / fst_shortest_path_with_config
  *      (rustfst-ffi/src/algorithms/shortest_path.rs:44-83) = rustfst::algorithms::shortest_path

@@ -31,6 +31,7 @@
 //   replace(fst_list, root, epsilon_on_replace)                  replace(fst_list, root, epsilon_on_replace)       replace/replace_static.rs:44-58
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
+//   MatcherConfig { sigma_matcher_config: Some(SigmaMatcherConfig) } ComposeConfig::matcher1_config / matcher2_config  compose_static.rs:30-54
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
 //   anyhow::Result<T> Err(e)                                     throws wfst_amd::Error (what() = the library's message)
 //
@@ -74,9 +75,21 @@ constexpr Label EPS_LABEL = 0;
 enum class ComposeFilterEnum : uint32_t {  // compose_static.rs:19-33
   AutoFilter = 0, NullFilter = 1, TrivialFilter = 2, SequenceFilter = 3, AltSequenceFilter = 4, MatchFilter = 5, NoMatchFilter = 6
 };
-struct ComposeConfig {  // compose_static.rs:35-65 (default: AutoFilter, connect = true)
-  ComposeFilterEnum compose_filter = ComposeFilterEnum::AutoFilter;
+enum class MatcherRewriteMode : uint32_t { MatcherRewriteAuto = 0, MatcherRewriteAlways = 1, MatcherRewriteNever = 2 };  // matchers/mod.rs
+struct SigmaMatcherConfig {  // compose_static.rs:30-35
+  Label sigma_label = 0;
+  MatcherRewriteMode rewrite_mode = MatcherRewriteMode::MatcherRewriteAuto;
+  std::optional<std::vector<Label>> sigma_allowed_matches = std::nullopt;
+};
+struct MatcherConfig {  // compose_static.rs:37-46
+  std::optional<SigmaMatcherConfig> sigma_matcher_config = std::nullopt;
+  bool empty() const { return !sigma_matcher_config.has_value(); }
+};
+struct ComposeConfig {  // compose_static.rs:48-65 (default: AutoFilter, connect = true, no matcher configs); the matcher configs
+  ComposeFilterEnum compose_filter = ComposeFilterEnum::AutoFilter;  // come last here, so that {filter, connect} still initialises
   bool connect = true;
+  MatcherConfig matcher1_config = {};
+  MatcherConfig matcher2_config = {};
 };
 struct ShortestPathConfig {  // shortest_path.rs:26-74 (default: delta 1e-6, nshortest 1, unique false)
   float delta = 1e-6f;
@@ -177,7 +190,18 @@ inline VectorFst compose_with_config(const VectorFst& fst1, const VectorFst& fst
   detail::upload(fst1, a);
   detail::upload(fst2, b);
   const wfst_compose_config cfg{(uint32_t)config.compose_filter, config.connect ? 1u : 0u};
-  check(wfst_compose(Context::current().get(), a.h, b.h, &cfg, &c.h));
+  // a SigmaMatcherConfig goes through wfst_compose_with_matchers; Some(empty list) is None there (rustfst-ffi compose.rs:199-211)
+  wfst_matcher_config m[2];
+  const MatcherConfig* mc[2] = {&config.matcher1_config, &config.matcher2_config};
+  for (int i = 0; i < 2; ++i) {
+    if (mc[i]->empty()) continue;
+    const SigmaMatcherConfig& sc = *mc[i]->sigma_matcher_config;
+    const bool some = sc.sigma_allowed_matches.has_value() && !sc.sigma_allowed_matches->empty();
+    m[i] = wfst_matcher_config{sc.sigma_label, (uint32_t)sc.rewrite_mode, some ? sc.sigma_allowed_matches->data() : nullptr,
+                               some ? sc.sigma_allowed_matches->size() : 0};
+  }
+  check(wfst_compose_with_matchers(Context::current().get(), a.h, b.h, &cfg, mc[0]->empty() ? nullptr : &m[0],
+                                   mc[1]->empty() ? nullptr : &m[1], &c.h));
   return detail::download(c);
 }
 inline VectorFst compose(const VectorFst& fst1, const VectorFst& fst2) {  // compose_static.rs:293-303

@@ -19,6 +19,11 @@ class ComposeConfig(C.Structure):
     _fields_ = [("compose_filter", C.c_uint32), ("connect", C.c_uint32)]
 
 
+class MatcherConfig(C.Structure):  # wfst_matcher_config
+    _fields_ = [("sigma_label", C.c_uint32), ("rewrite_mode", C.c_uint32), ("sigma_allowed_matches", C.POINTER(C.c_uint32)),
+                ("n_allowed", C.c_size_t)]
+
+
 class ShortestPathConfig(C.Structure):
     _fields_ = [("delta", C.c_float), ("nshortest", C.c_uint64), ("unique", C.c_uint32)]
 
@@ -90,10 +95,15 @@ COUNTERS = {
                   "states_compared", "wave_states", "cyclic")),
 }
 
+# wfst_ctx_get_compose_sigma_counters: the uint64_t* parameters behind ctx, in order (outside the table of the *_stats families)
+COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "require2_states", "exact_items", "sigma_items",
+                          "sigma_arcs", "refused_items", "arena_grows", "level_launches")
+
 # every symbol include/wfst.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _f32, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_size_t
 _P = C.POINTER
 SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names in COUNTERS.values()] + [
+    ("wfst_ctx_get_compose_sigma_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_SIGMA_COUNTERS)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
     ("wfst_string_destroy", C.c_int, [C.c_char_p]),
     ("wfst_abi_version", _u32, []),
@@ -115,6 +125,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_fst_destroy", C.c_int, [_vp]),
     ("wfst_fst_destroy_many", C.c_int, [_P(_vp), _sz]),
     ("wfst_compose", C.c_int, [_vp, _vp, _vp, _P(ComposeConfig), _P(_vp)]),
+    ("wfst_compose_with_matchers", C.c_int, [_vp, _vp, _vp, _P(ComposeConfig), _P(MatcherConfig), _P(MatcherConfig), _P(_vp)]),
     ("wfst_shortest_path", C.c_int, [_vp, _vp, _P(ShortestPathConfig), _P(_vp)]),
     ("wfst_connect", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_rm_epsilon", C.c_int, [_vp, _vp, _P(_vp)]),

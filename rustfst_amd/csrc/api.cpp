@@ -398,6 +398,36 @@ wfst_status wfst_compose(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fs
   });
 }
 
+// compose_with_config with matcher configs (compose_static.rs:166-266; rustfst-ffi/src/algorithms/compose.rs:199-211: an empty
+// allowed list is None); without any it is wfst_compose
+wfst_status wfst_compose_with_matchers(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2, const wfst_compose_config* cfg,
+                                       const wfst_matcher_config* m1, const wfst_matcher_config* m2, wfst_fst** out) {
+  if (!m1 && !m2) return wfst_compose(ctx, fst1, fst2, cfg, out);
+  return wrap([&] {
+    if (out) *out = nullptr;
+    if (!ctx || !fst1 || !fst2 || !out) throw Error("null pointer");
+    wfst_compose_config c = cfg ? *cfg : wfst_compose_config{0, 1};
+    if (c.compose_filter > 6) throw Error("unknown compose_filter " + std::to_string(c.compose_filter));
+    SigmaSpec specs[2];
+    const wfst_matcher_config* ms[2] = {m1, m2};
+    for (int i = 0; i < 2; ++i) {
+      if (!ms[i]) continue;
+      if (ms[i]->rewrite_mode > 2) throw Error("unknown rewrite_mode " + std::to_string(ms[i]->rewrite_mode));
+      if (ms[i]->n_allowed && !ms[i]->sigma_allowed_matches) throw Error("null pointer");
+      specs[i] = SigmaSpec{ms[i]->sigma_label, ms[i]->rewrite_mode, ms[i]->sigma_allowed_matches, ms[i]->n_allowed};
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = compose_sigma(ctx, fst1, fst2, c.connect != 0, c.compose_filter, m1 ? &specs[0] : nullptr, m2 ? &specs[1] : nullptr);
+  });
+}
+wfst_status wfst_ctx_get_compose_sigma_counters(wfst_ctx* ctx, uint64_t* levels, uint64_t* states, uint64_t* arcs,
+                                             uint64_t* require1_states, uint64_t* require2_states, uint64_t* exact_items,
+                                             uint64_t* sigma_items, uint64_t* sigma_arcs, uint64_t* refused_items,
+                                             uint64_t* arena_grows, uint64_t* level_launches) {
+  return get_counters(ctx, &wfst_ctx::compose_sigma, {levels, states, arcs, require1_states, require2_states, exact_items,
+                                                      sigma_items, sigma_arcs, refused_items, arena_grows, level_launches});
+}
+
 wfst_status wfst_shortest_path(wfst_ctx* ctx, const wfst_fst* fst, const wfst_shortest_path_config* cfg,
                                wfst_fst** out) {
   return wrap([&] {

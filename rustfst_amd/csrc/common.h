@@ -328,6 +328,15 @@ struct wfst_ctx {
     uint64_t levels = 0, states = 0, arcs = 0, prefixes = 0, max_depth = 0, call_arcs = 0, dropped_calls = 0, return_arcs = 0;
     uint64_t arena_grows = 0, prefix_reruns = 0, level_launches = 0;
   } replace;
+  // The last wfst_compose_with_matchers call that had a matcher config: the driver's level and size figures, then the counters
+  // of compose_sigma.hip's policy block — composed states whose side-1 / side-2 state carries a sigma arc, items of a sigma
+  // side that the sorted matcher answered, that the sigma arcs answered, the arcs those emitted, items the allowed set refused
+  // (a level that is emitted again after an overflow counts its items again) — and the arena's growths.  Zeroed when
+  // compose_sigma.hip's driver begins; all 0 after a KO, except the growths.
+  struct ComposeSigmaStats {
+    uint64_t levels = 0, states = 0, arcs = 0, require1_states = 0, require2_states = 0, exact_items = 0, sigma_items = 0;
+    uint64_t sigma_arcs = 0, refused_items = 0, arena_grows = 0, level_launches = 0;
+  } compose_sigma;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   // ... and what became of such scratch; never zeroed (counts since the context's creation)
@@ -659,4 +668,13 @@ wfst_fst* replace_fst(wfst_ctx* ctx, uint32_t root_label, const uint32_t* labels
                       bool epsilon_on_replace);
 wfst_fst* compose_wide(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, uint32_t mode, uint32_t filter, bool connect,
                        uint64_t out_props, uint64_t est_s);
+// compose_sigma.hip: compose_with_config with a SigmaMatcher on side 1 (m1), side 2 (m2) or both (a NEW handle); a null spec is
+// the plain SortedMatcher.  rewrite_mode: 0 Auto, 1 Always, 2 Never; n_allowed == 0: no restriction
+struct SigmaSpec {
+  uint32_t sigma_label, rewrite_mode;
+  const uint32_t* allowed;
+  size_t n_allowed;
+};
+wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter, const SigmaSpec* m1,
+                        const SigmaSpec* m2);
 }  // namespace wfst

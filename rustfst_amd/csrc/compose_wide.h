@@ -118,6 +118,15 @@ struct WideCtl {
 };
 constexpr size_t WIDE_CTL_HEAD = offsetof(WideCtl, cursor);  // what the host reads back per look
 
+// a policy whose Expand has a member `wide_state_id` is told the id of the composed state it expands (compose_sigma.hip
+// orders its errors by it); for every other policy this is nothing at all
+template <class X>
+__device__ __forceinline__ auto wide_note_state(X& x, uint32_t q, int) -> decltype((void)(x.wide_state_id = q)) {
+  x.wide_state_id = q;
+}
+template <class X>
+__device__ __forceinline__ void wide_note_state(X&, uint32_t, long) {}
+
 template <uint32_t G>
 __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
 #pragma unroll
@@ -239,6 +248,7 @@ __global__ void __launch_bounds__(256) WFST_WIDE_EMIT_ATTR la_emit(P pol, LaCaps
     const bool valid = q < hi;
     const uint32_t qc = valid ? q : hi - 1;
     typename P::Expand x = pol.make_expand(ar.t_lo[qc], ar.t_hi[qc]);
+    wide_note_state(x, qc, 0);
     // The searched side's arcs go to LDS, one trip for the group: every item is matched against them by binary searches
     // (equal_range: ~8 dependent probes per item), and a probe of a 16-byte arc in memory is a round trip of its own — a
     // composed state of the look-ahead recipe (10 arcs searched, 2 items) walked ~20 of them one after the other, which was

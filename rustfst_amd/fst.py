@@ -166,6 +166,17 @@ class Context:
         (level_launches: three per level, idle ones behind the last level included)."""
         return _counters("replace", self)
 
+    def compose_sigma_stats(self) -> dict:
+        """This context's last composition with a MatcherConfig (wfst_ctx_get_compose_sigma_counters): levels of the search,
+        states and arcs before connect, composed states whose fst1 / fst2 state carries a sigma arc (require1_states,
+        require2_states), items of a sigma side answered by its sorted matcher (exact_items) and by its sigma arcs
+        (sigma_items), the arcs those emitted (sigma_arcs), items the allowed set refused (refused_items), times the
+        search's arena grew (arena_grows) and the level kernels queued (level_launches)."""
+        vals = [C.c_uint64() for _ in _lib.COMPOSE_SIGMA_COUNTERS]
+        check(_lib.lib().wfst_ctx_get_compose_sigma_counters(self._h, *[C.byref(v) for v in vals]),
+              "wfst_ctx_get_compose_sigma_counters")
+        return {k: int(v.value) for k, v in zip(_lib.COMPOSE_SIGMA_COUNTERS, vals)}
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
@@ -354,7 +365,12 @@ class DeviceFst:
     # algorithms on device handles (no host round trip of the operands)
     def compose(self, other: "DeviceFst", config: Optional["ComposeConfig"] = None) -> "DeviceFst":
         out = C.c_void_p()
-        cfg = config._c() if config is not None else None
+        cfg = config._c(matchers=True) if config is not None else None
+        if config is not None and (config.matcher1_config is not None or config.matcher2_config is not None):
+            m1, m2 = config.matcher1_config, config.matcher2_config  # (kept alive over the call: they own the allowed arrays)
+            check(_lib.lib().wfst_compose_with_matchers(self.ctx._h, self._h, other._h, cfg, m1._c() if m1 else None,
+                                                        m2._c() if m2 else None, C.byref(out)), "Error during composition")
+            return DeviceFst(out, self.ctx)
         check(_lib.lib().wfst_compose(self.ctx._h, self._h, other._h, cfg, C.byref(out)), "Error during composition")
         return DeviceFst(out, self.ctx)
 
@@ -977,17 +993,53 @@ class ComposeFilter(Enum):  # rustfst-python/rustfst/algorithms/compose.py:55-62
     NOMATCHFILTER = 6
 
 
-class ComposeConfig:
-    """rustfst-python/rustfst/algorithms/compose.py:65-113 (sigma matcher configs are not supported)."""
+class MatcherRewriteMode(Enum):  # rustfst-python/rustfst/algorithms/compose.py:16-19
+    AUTO = 0
+    ALWAYS = 1
+    NEVER = 2
 
-    def __init__(self, compose_filter: ComposeFilter = ComposeFilter.AUTOFILTER, connect: bool = True,
-                 matcher1_config=None, matcher2_config=None):
-        if matcher1_config is not None or matcher2_config is not None:
-            raise WfstError("unsupported: custom MatcherConfig (sigma matcher) is not implemented on the GPU path")
-        self.compose_filter = compose_filter
-        self.connect = bool(connect)
+
+class MatcherConfig:
+    """rustfst-python/rustfst/algorithms/compose.py:26-53: a sigma matcher for one side of a composition.  An arc labelled
+    `sigma_label` on the side's matched tape stands for any label the state does not carry explicitly — any of
+    `sigma_allowed_matches` when that is given (None or empty: no restriction, as in rustfst-ffi)."""
+
+    def __init__(self, sigma_label: int, rewrite_mode: MatcherRewriteMode = MatcherRewriteMode.AUTO,
+                 sigma_allowed_matches: Optional[Sequence[int]] = None):
+        if not isinstance(rewrite_mode, MatcherRewriteMode):
+            raise TypeError("rewrite_mode must be a MatcherRewriteMode")
+        self.sigma_label = int(sigma_label)
+        self.rewrite_mode = rewrite_mode
+        self.sigma_allowed_matches = [int(x) for x in sigma_allowed_matches] if sigma_allowed_matches is not None else []
+        if not 0 <= self.sigma_label <= 0xFFFFFFFF or any(not 0 <= x <= 0xFFFFFFFF for x in self.sigma_allowed_matches):
+            raise ValueError("labels are 32-bit unsigned")
+        self._arr = (C.c_uint32 * len(self.sigma_allowed_matches))(*self.sigma_allowed_matches)
 
     def _c(self):
+        n = len(self.sigma_allowed_matches)
+        return C.pointer(_lib.MatcherConfig(self.sigma_label, self.rewrite_mode.value,
+                                            C.cast(self._arr, C.POINTER(C.c_uint32)) if n else None, n))
+
+
+class ComposeConfig:
+    """rustfst-python/rustfst/algorithms/compose.py:65-113.  With a `matcher1_config` / `matcher2_config` (MatcherConfig: the
+    sigma matcher of the left / right FST) the composition goes through wfst_compose_with_matchers; AUTOFILTER is then
+    refused, as in the reference."""
+
+    def __init__(self, compose_filter: ComposeFilter = ComposeFilter.AUTOFILTER, connect: bool = True,
+                 matcher1_config: Optional[MatcherConfig] = None, matcher2_config: Optional[MatcherConfig] = None):
+        for m in (matcher1_config, matcher2_config):
+            if m is not None and not isinstance(m, MatcherConfig):
+                raise TypeError("matcher configs must be MatcherConfig or None")
+        self.compose_filter = compose_filter
+        self.connect = bool(connect)
+        self.matcher1_config = matcher1_config
+        self.matcher2_config = matcher2_config
+
+    def _c(self, matchers: bool = False):
+        """wfst_compose_config; `matchers`: the caller passes the matcher configs on (only DeviceFst.compose does)"""
+        if not matchers and (self.matcher1_config is not None or self.matcher2_config is not None):
+            raise WfstError("unsupported: a MatcherConfig (sigma matcher) outside compose / compose_with_config")
         return C.pointer(_lib.ComposeConfig(self.compose_filter.value, 1 if self.connect else 0))
 
 
