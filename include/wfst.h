@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -729,6 +729,35 @@ wfst_status wfst_compose_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* cons
                                              const wfst_fst* t, const wfst_compose_config* ccfg,
                                              const wfst_shortest_path_config* scfg, wfst_fst** outs,
                                              uint64_t* composed_arcs);
+
+/* ---- fused batch with matcher configs: for each acceptor i, outs[i] is bit for bit what
+ *      wfst_shortest_path(wfst_compose_with_matchers(acceptors[i], t, ccfg, m1, m2), scfg) returns, property word included;
+ *      m1 is the matcher of every acceptors[i] (side 1), m2 the matcher of t (side 2).  With m1 == m2 == NULL the call is
+ *      wfst_compose_shortest_path_batch.  Otherwise outs[0..n) are zeroed before anything is looked at, and composed_arcs (may be
+ *      NULL) receives the sum of the compositions' arc counts before trimming.
+ *      Routes: items that are linear epsilon-free acceptors of at most 2048 states, against a t that has arcs, is known
+ *      ilabel-sorted and has no input epsilons, with compose_filter 3 (Sequence) and m1 == NULL, run one wavefront each in ONE
+ *      launch whatever n is; an item whose composition has a BFS level of more than 64 states or more states than its
+ *      wavefront's slice of LDS holds is handed back.  Handed-back items and all others go one by one through the two calls
+ *      above on ctx, in item order.
+ *      KO: a null pointer "null pointer" (no GPU is touched); "unknown compose_filter"; nshortest != 1 "unsupported: nshortest !=
+ *      1 in the fused batch"; then the set-up errors of wfst_compose_with_matchers in its order (unknown rewrite_mode, sigma_label
+ *      0, AutoFilter with a matcher config, "cannot perform required matching (sort?)", the mode errors), decided for item 0
+ *      first, then item 1 and so on, all before anything is launched; while composing, per item, "SigmaMatcher::Find: bad label
+ *      (sigma)" and "Both sides can't require match": the call is KO with the message of the lowest failing item.  After a KO
+ *      every outs[i] is NULL and the context works on. ---- */
+wfst_status wfst_compose_shortest_path_batch_with_matchers(wfst_ctx* ctx, const wfst_fst* const* acceptors, size_t n, const wfst_fst* t,
+                                                           const wfst_compose_config* ccfg, const wfst_matcher_config* m1,
+                                                           const wfst_matcher_config* m2, const wfst_shortest_path_config* scfg,
+                                                           wfst_fst** outs, uint64_t* composed_arcs);
+/* the last wfst_compose_shortest_path_batch_with_matchers call of ctx that had a matcher config (reset when it begins): launches
+ * of the wave-per-item kernel, items it answered, items it handed back, items never sent to it, then — summed over the items
+ * the kernel answered — items of t's matcher that its sorted matcher answered, that its sigma arcs answered, the arcs those
+ * emitted, items the allowed set refused, and the widest BFS level among them.  Any out-pointer may be NULL.  (Like
+ * wfst_ctx_get_compose_sigma_counters: outside the table of the wfst_ctx_get_*_stats families.) */
+wfst_status wfst_ctx_get_sigma_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_handed_back,
+                                              uint64_t* items_loop, uint64_t* exact_items, uint64_t* sigma_items, uint64_t* sigma_arcs,
+                                              uint64_t* refused_items, uint64_t* max_level_width);
 
 /* ---- host-side mutable VectorFst<TropicalWeight> mirror.  What rustfst-ffi exposes as vec_fst_* /
  * fst_* (rustfst-ffi/src/fst/vector_fst.rs:13-354, src/fst/mod.rs:128-216, src/algorithms/tr_sort.rs:15)

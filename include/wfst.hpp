@@ -33,6 +33,7 @@
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   MatcherConfig { sigma_matcher_config: Some(SigmaMatcherConfig) } ComposeConfig::matcher1_config / matcher2_config  compose_static.rs:30-54
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
+//   (a loop of the two over many acceptors)                      compose_shortest_path_batch(acceptors, t, config)
 //   anyhow::Result<T> Err(e)                                     throws wfst_amd::Error (what() = the library's message)
 //
 // The algorithms run on the GPU through a per-thread Context; a VectorFst lives on the host (wfst_vec_fst) and is
@@ -182,6 +183,24 @@ inline VectorFst download(const DeviceFst& d) {
   check(wfst_vec_fst_from_device(d.h, &out));
   return VectorFst::adopt(out);
 }
+// the two matcher configs of a ComposeConfig in the C-ABI's form (they point into `config`: it must outlive them).  A
+// SigmaMatcherConfig goes through the ..._with_matchers calls; Some(empty list) is None there (rustfst-ffi compose.rs:199-211)
+struct MatcherPair {
+  wfst_matcher_config m[2];
+  bool some[2];
+  explicit MatcherPair(const ComposeConfig& config) {
+    const MatcherConfig* mc[2] = {&config.matcher1_config, &config.matcher2_config};
+    for (int i = 0; i < 2; ++i) {
+      some[i] = !mc[i]->empty();
+      if (!some[i]) continue;
+      const SigmaMatcherConfig& sc = *mc[i]->sigma_matcher_config;
+      const bool list = sc.sigma_allowed_matches.has_value() && !sc.sigma_allowed_matches->empty();
+      m[i] = wfst_matcher_config{sc.sigma_label, (uint32_t)sc.rewrite_mode, list ? sc.sigma_allowed_matches->data() : nullptr,
+                                 list ? sc.sigma_allowed_matches->size() : 0};
+    }
+  }
+  const wfst_matcher_config* side(int i) const { return some[i] ? &m[i] : nullptr; }
+};
 }  // namespace detail
 
 // compose_with_config (compose_static.rs:166-266): Err when neither side is known label-sorted ("... (sort?)")
@@ -190,18 +209,8 @@ inline VectorFst compose_with_config(const VectorFst& fst1, const VectorFst& fst
   detail::upload(fst1, a);
   detail::upload(fst2, b);
   const wfst_compose_config cfg{(uint32_t)config.compose_filter, config.connect ? 1u : 0u};
-  // a SigmaMatcherConfig goes through wfst_compose_with_matchers; Some(empty list) is None there (rustfst-ffi compose.rs:199-211)
-  wfst_matcher_config m[2];
-  const MatcherConfig* mc[2] = {&config.matcher1_config, &config.matcher2_config};
-  for (int i = 0; i < 2; ++i) {
-    if (mc[i]->empty()) continue;
-    const SigmaMatcherConfig& sc = *mc[i]->sigma_matcher_config;
-    const bool some = sc.sigma_allowed_matches.has_value() && !sc.sigma_allowed_matches->empty();
-    m[i] = wfst_matcher_config{sc.sigma_label, (uint32_t)sc.rewrite_mode, some ? sc.sigma_allowed_matches->data() : nullptr,
-                               some ? sc.sigma_allowed_matches->size() : 0};
-  }
-  check(wfst_compose_with_matchers(Context::current().get(), a.h, b.h, &cfg, mc[0]->empty() ? nullptr : &m[0],
-                                   mc[1]->empty() ? nullptr : &m[1], &c.h));
+  const detail::MatcherPair m(config);
+  check(wfst_compose_with_matchers(Context::current().get(), a.h, b.h, &cfg, m.side(0), m.side(1), &c.h));
   return detail::download(c);
 }
 inline VectorFst compose(const VectorFst& fst1, const VectorFst& fst2) {  // compose_static.rs:293-303
@@ -217,6 +226,37 @@ inline VectorFst shortest_path_with_config(const VectorFst& ifst, const Shortest
   return detail::download(c);
 }
 inline VectorFst shortest_path(const VectorFst& ifst) { return shortest_path_with_config(ifst, ShortestPathConfig{}); }
+
+// for a in acceptors: shortest_path_with_config(compose_with_config(a, t, compose_config), shortest_path_config) as ONE call
+// (wfst_compose_shortest_path_batch_with_matchers; without matcher configs that is wfst_compose_shortest_path_batch): strings
+// against a sigma matcher on t run one wavefront each in one launch.  nshortest must be 1.
+inline std::vector<VectorFst> compose_shortest_path_batch(const std::vector<VectorFst>& acceptors, const VectorFst& t,
+                                                          const ComposeConfig& compose_config,
+                                                          const ShortestPathConfig& shortest_path_config = ShortestPathConfig{}) {
+  const size_t n = acceptors.size();
+  if (n == 0) return {};
+  std::vector<detail::DeviceFst> a(n), out(n);
+  detail::DeviceFst b;
+  std::vector<const wfst_fst*> in(n);
+  std::vector<wfst_fst*> res(n, nullptr);
+  for (size_t i = 0; i < n; ++i) {
+    detail::upload(acceptors[i], a[i]);
+    in[i] = a[i].h;
+  }
+  detail::upload(t, b);
+  const wfst_compose_config ccfg{(uint32_t)compose_config.compose_filter, compose_config.connect ? 1u : 0u};
+  const wfst_shortest_path_config scfg{shortest_path_config.delta, (uint64_t)shortest_path_config.nshortest,
+                                       shortest_path_config.unique ? 1u : 0u};
+  const detail::MatcherPair m(compose_config);
+  check(wfst_compose_shortest_path_batch_with_matchers(Context::current().get(), in.data(), n, b.h, &ccfg, m.side(0), m.side(1), &scfg,
+                                                       res.data(), nullptr));
+  std::vector<VectorFst> paths;
+  for (size_t i = 0; i < n; ++i) {
+    out[i].h = res[i];
+    paths.push_back(detail::download(out[i]));
+  }
+  return paths;
+}
 
 // project (algorithms/projection.rs:65-95): in place, like the reference
 enum class ProjectType { ProjectInput, ProjectOutput };  // projection.rs:7-13

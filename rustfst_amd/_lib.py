@@ -99,11 +99,16 @@ COUNTERS = {
 COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "require2_states", "exact_items", "sigma_items",
                           "sigma_arcs", "refused_items", "arena_grows", "level_launches")
 
+# wfst_ctx_get_sigma_batch_counters: the same, for the fused batch with matcher configs
+SIGMA_BATCH_COUNTERS = ("launches", "items_in_kernel", "items_handed_back", "items_loop", "exact_items", "sigma_items", "sigma_arcs",
+                        "refused_items", "max_level_width")
+
 # every symbol include/wfst.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _f32, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_size_t
 _P = C.POINTER
 SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names in COUNTERS.values()] + [
     ("wfst_ctx_get_compose_sigma_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_SIGMA_COUNTERS)),
+    ("wfst_ctx_get_sigma_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(SIGMA_BATCH_COUNTERS)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
     ("wfst_string_destroy", C.c_int, [C.c_char_p]),
     ("wfst_abi_version", _u32, []),
@@ -176,6 +181,8 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_top_sort", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
+    ("wfst_compose_shortest_path_batch_with_matchers", C.c_int,
+     [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(MatcherConfig), _P(MatcherConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_begin", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp)]),
     ("wfst_compose_shortest_path_batch_end", C.c_int, [_vp, _P(_vp), _P(_u64)]),

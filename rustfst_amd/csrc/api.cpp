@@ -898,6 +898,39 @@ wfst_status wfst_compose_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* cons
   });
 }
 
+// the fused batch with matcher configs (compose_sigma_batch.hip); without any it is wfst_compose_shortest_path_batch
+wfst_status wfst_compose_shortest_path_batch_with_matchers(wfst_ctx* ctx, const wfst_fst* const* acceptors, size_t n, const wfst_fst* t,
+                                                           const wfst_compose_config* ccfg, const wfst_matcher_config* m1,
+                                                           const wfst_matcher_config* m2, const wfst_shortest_path_config* scfg,
+                                                           wfst_fst** outs, uint64_t* composed_arcs) {
+  if (!m1 && !m2) return wfst_compose_shortest_path_batch(ctx, acceptors, n, t, ccfg, scfg, outs, composed_arcs);
+  return wrap([&] {
+    null_outs(outs, n);
+    if (!ctx || !t || !outs || (n && !acceptors)) throw Error("null pointer");
+    wfst_compose_config c = ccfg ? *ccfg : wfst_compose_config{0, 1};
+    wfst_shortest_path_config s = scfg ? *scfg : wfst_shortest_path_config{1e-6f, 1, 0};
+    if (c.compose_filter > 6) throw Error("unknown compose_filter");
+    if (s.nshortest != 1) throw Error("unsupported: nshortest != 1 in the fused batch");
+    SigmaSpec specs[2];
+    const wfst_matcher_config* ms[2] = {m1, m2};
+    for (int i = 0; i < 2; ++i) {
+      if (!ms[i]) continue;
+      if (ms[i]->rewrite_mode > 2) throw Error("unknown rewrite_mode " + std::to_string(ms[i]->rewrite_mode));
+      if (ms[i]->n_allowed && !ms[i]->sigma_allowed_matches) throw Error("null pointer");
+      specs[i] = SigmaSpec{ms[i]->sigma_label, ms[i]->rewrite_mode, ms[i]->sigma_allowed_matches, ms[i]->n_allowed};
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    compose_sigma_sp_batch(ctx, acceptors, n, t, c.connect != 0, c.compose_filter, m1 ? &specs[0] : nullptr, m2 ? &specs[1] : nullptr, outs,
+                           composed_arcs);
+  });
+}
+wfst_status wfst_ctx_get_sigma_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_handed_back,
+                                              uint64_t* items_loop, uint64_t* exact_items, uint64_t* sigma_items, uint64_t* sigma_arcs,
+                                              uint64_t* refused_items, uint64_t* max_level_width) {
+  return get_counters(ctx, &wfst_ctx::sigma_batch, {launches, items_in_kernel, items_handed_back, items_loop, exact_items, sigma_items,
+                                                    sigma_arcs, refused_items, max_level_width});
+}
+
 wfst_status wfst_rm_epsilon(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {
     if (!ctx || !fst || !out) throw Error("null pointer");

@@ -337,6 +337,14 @@ struct wfst_ctx {
     uint64_t levels = 0, states = 0, arcs = 0, require1_states = 0, require2_states = 0, exact_items = 0, sigma_items = 0;
     uint64_t sigma_arcs = 0, refused_items = 0, arena_grows = 0, level_launches = 0;
   } compose_sigma;
+  // The last wfst_compose_shortest_path_batch_with_matchers call that had a matcher config (compose_sigma_batch.hip): launches
+  // of string_sigma_sp_kernel, items it answered, items it handed back (a level wider than one wave, or more composed states
+  // than its slice of LDS holds), items that were never sent to it, the four item counters of ComposeSigmaStats summed over
+  // the items the kernel answered, and the widest level among those.  Zeroed when the call begins.
+  struct SigmaBatchCounters {
+    uint64_t launches = 0, items_in_kernel = 0, items_handed_back = 0, items_loop = 0, exact_items = 0, sigma_items = 0;
+    uint64_t sigma_arcs = 0, refused_items = 0, max_level_width = 0;
+  } sigma_batch;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   // ... and what became of such scratch; never zeroed (counts since the context's creation)
@@ -677,4 +685,12 @@ struct SigmaSpec {
 };
 wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter, const SigmaSpec* m1,
                         const SigmaSpec* m2);
+// ... its set-up errors in the reference's order (nothing is launched), and the match mode (0 both, 1 input, 2 output)
+uint32_t sigma_setup_mode(const wfst_fst* f1, const wfst_fst* f2, uint32_t filter, const SigmaSpec* m1, const SigmaSpec* m2);
+// compose_sigma_batch.hip: outs[i] = shortest_path(compose_sigma(accs[i], t, ...)) for n acceptors (new handles; on a throw every
+// outs[i] is null); strings against a sigma matcher on t run one wavefront each in one launch, the rest one by one
+void compose_sigma_sp_batch(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n, const wfst_fst* t, bool connect, uint32_t filter,
+                            const SigmaSpec* m1, const SigmaSpec* m2, wfst_fst** outs, uint64_t* composed_arcs);
+// compose.hip: the fused batch's path FST from a kernel's report (facts: the OR of props::path_arc_facts, or PATH_FACTS_NONE)
+wfst_fst* batch_path_fst(wfst_ctx* ctx, bool has_path, uint32_t hops, float final_weight, uint32_t facts, const wfst_tr* path_arcs);
 }  // namespace wfst

@@ -2166,4 +2166,14 @@ void compose_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* accs, siz
   compose_shortest_path_batch_end(compose_shortest_path_batch_begin(ctx, accs, n, t, filter), outs, composed_arcs);
 }
 
+// path_to_fst for a kernel of another file that reports a path the way string_compose_sp_kernel does (compose_sigma_batch.hip)
+wfst_fst* batch_path_fst(wfst_ctx* ctx, bool has_path, uint32_t hops, float final_weight, uint32_t facts, const wfst_tr* path_arcs) {
+  Result r{};
+  r.has_path = has_path ? 1u : 0u;
+  r.hops = hops;
+  r.final_weight = final_weight;
+  r.facts = facts;
+  return path_to_fst(ctx, r, path_arcs);
+}
+
 }  // namespace wfst

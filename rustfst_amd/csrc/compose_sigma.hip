@@ -31,11 +31,12 @@
 //                            sides require, found before the items; kind 1: bad label at item j).  Every state of a level
 //                            reports its errors; once the word is set the states of later levels emit nothing, so the search
 //                            ends within a level.
-// Every sigma call runs on this driver, whatever its size: the wave-per-problem kernels of compose.hip do not learn about
-// sigma.
+// Every single sigma call runs on this driver, whatever its size: the wave-per-problem kernels of compose.hip do not learn
+// about sigma.  Many utterances against one sigma grammar: compose_sigma_batch.hip.
 #include "compose_filters.h"
 #include "compose_wide.h"
 #include "fst_props.h"
+#include "sigma_ranges.h"
 
 namespace wfst {
 namespace {
@@ -73,36 +74,6 @@ struct SgExpand {
   bool dead;         // an error is known: the state emits nothing
   bool req1, req2;
 };
-
-__device__ void sg_equal_range(const wfst_tr* arcs, uint32_t n, bool by_ilabel, uint32_t key, uint32_t* lo_out, uint32_t* cnt_out) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k < key) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k <= key) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = first;
-  *cnt_out = lo - first;
-}
-
-// has_sigma of every state of a sigma operand (sigma_matcher.rs:33-45: matcher.iter(state, sigma).next().is_some()) as the
-// range the sorted matcher would walk: one thread per state, two binary searches on the matched tape
-__global__ void __launch_bounds__(256) sigma_ranges(const wfst_tr* __restrict__ arcs, const uint4* __restrict__ srec, uint32_t n_states,
-                                                    bool by_ilabel, uint32_t sigma, uint2* __restrict__ sig) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_states) return;
-  const uint4 r = srec[s];
-  uint32_t lo = 0, cnt = 0;
-  sg_equal_range(arcs + r.x, r.y, by_ilabel, sigma, &lo, &cnt);
-  sig[s] = make_uint2(lo, cnt);
-}
 
 // one add per wave for the lanes (of those that are here together) whose `pred` holds
 __device__ __forceinline__ void sg_count(unsigned long long* ctr, bool pred) {
@@ -262,17 +233,12 @@ uint32_t sigma_match_mode(uint64_t p1, uint64_t p2) {
   throw Error("ComposeFst: 1st argument cannot match on output labels and 2nd argument cannot match on input labels (sort?).");
 }
 
-struct SideBuffers {
-  DBuf<uint2> sig;
-  DBuf<uint32_t> allowed;
-};
-
 }  // namespace
 
-wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter, const SigmaSpec* m1,
-                        const SigmaSpec* m2) {
+// the set-up errors of compose_with_config with matcher configs, in the reference's order, and the match mode they leave:
+// nothing here touches the device (compose_sigma_batch.hip decides every item of a batch with it before anything is launched)
+uint32_t sigma_setup_mode(const wfst_fst* f1, const wfst_fst* f2, uint32_t filter, const SigmaSpec* m1, const SigmaSpec* m2) {
   using namespace props;
-  ctx->compose_sigma = wfst_ctx::ComposeSigmaStats{};
   // compose_with_config creates both matchers first (compose_static.rs:178-183): SigmaMatcher::new, sigma_matcher.rs:64-66
   for (const SigmaSpec* m : {m1, m2})
     if (m && m->sigma_label == 0u) throw Error("SigmaMatcher: 0 cannot be used as sigma_label");
@@ -288,7 +254,14 @@ wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, b
     if (!(f2->props & (I_LABEL_SORTED | NOT_I_LABEL_SORTED))) throw Error("ComposeFst: 2nd argument: label-sortedness properties are not known (sort?)");
     if (!(f2->props & I_LABEL_SORTED)) throw Error("ComposeFst: 2nd argument cannot perform required matching (sort?)");
   }
-  const uint32_t mode = sigma_match_mode(f1->props, f2->props);
+  return sigma_match_mode(f1->props, f2->props);
+}
+
+wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter, const SigmaSpec* m1,
+                        const SigmaSpec* m2) {
+  using namespace props;
+  ctx->compose_sigma = wfst_ctx::ComposeSigmaStats{};
+  const uint32_t mode = sigma_setup_mode(f1, f2, filter, m1, m2);
   ensure_device(const_cast<wfst_fst*>(f1));
   ensure_device(const_cast<wfst_fst*>(f2));
   const bool has_start = f1->start >= 0 && f2->start >= 0;
@@ -300,30 +273,12 @@ wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, b
     return make_host_fst(ctx, 0, -1, out_props, std::move(h));
   }
   hipStream_t st = ctx->stream;
-  SideBuffers b1, b2;
-  std::vector<uint32_t> h_allowed[2];
-  auto side = [&](const wfst_fst* f, const SigmaSpec* m, bool by_ilabel, SideBuffers& b, std::vector<uint32_t>& ha) {
-    SgSide s{f->dev.arcs, f->dev.srec, nullptr, nullptr, 0u, NO_LABEL, 0u, 0u};
-    if (!m || m->sigma_label == NO_LABEL) return s;
-    s.sigma = m->sigma_label;
-    s.rewrite_both = m->rewrite_mode == 1u || (m->rewrite_mode == 0u && (f->props & ACCEPTOR)) ? 1u : 0u;  // sigma_matcher.rs:67-75
-    b.sig = DBuf<uint2>(*ctx->pool, std::max<uint32_t>(f->n_states, 1));
-    if (f->n_states)
-      sigma_ranges<<<(f->n_states + 255) / 256, 256, 0, st>>>(f->dev.arcs, f->dev.srec, f->n_states, by_ilabel, s.sigma, b.sig.p);
-    HIP_CHECK(hipGetLastError());
-    s.sig = b.sig.p;
-    if (m->n_allowed) {  // a HashSet in the reference (compose_static.rs:101-103): order and duplicates do not matter
-      ha.assign(m->allowed, m->allowed + m->n_allowed);
-      std::sort(ha.begin(), ha.end());
-      ha.erase(std::unique(ha.begin(), ha.end()), ha.end());
-      b.allowed = DBuf<uint32_t>(*ctx->pool, ha.size());
-      HIP_CHECK(hipMemcpyAsync(b.allowed.p, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      s.allowed = b.allowed.p;
-      s.n_allowed = (uint32_t)ha.size();
-    }
-    return s;
+  SigmaTables b1, b2;
+  auto side = [&](const wfst_fst* f, const SigmaSpec* m, bool by_ilabel, SigmaTables& b) {
+    sigma_tables(ctx, f, m, by_ilabel, b);  // sigma_ranges.h
+    return SgSide{f->dev.arcs, f->dev.srec, b.sig.p, b.allowed.p, b.n_allowed, b.sigma, b.rewrite_both, 0u};
   };
-  const SgSide s1 = side(f1, m1, /*by_ilabel=*/false, b1, h_allowed[0]), s2 = side(f2, m2, /*by_ilabel=*/true, b2, h_allowed[1]);
+  const SgSide s1 = side(f1, m1, /*by_ilabel=*/false, b1), s2 = side(f2, m2, /*by_ilabel=*/true, b2);
   constexpr size_t BLK_WORDS = (size_t)(SG_COUNTERS + 1) * SG_STRIDE;
   DBuf<unsigned long long> d_blk(*ctx->pool, BLK_WORDS);
   HIP_CHECK(hipMemsetAsync(d_blk.p, 0, SG_COUNTERS * SG_STRIDE * sizeof(unsigned long long), st));

@@ -177,6 +177,17 @@ class Context:
               "wfst_ctx_get_compose_sigma_counters")
         return {k: int(v.value) for k, v in zip(_lib.COMPOSE_SIGMA_COUNTERS, vals)}
 
+    def sigma_batch_stats(self) -> dict:
+        """This context's last compose_shortest_path_batch with a MatcherConfig (wfst_ctx_get_sigma_batch_counters): launches
+        of the wave-per-utterance kernel, items it answered (items_in_kernel), items it handed back (a level wider than 64
+        states or more composed states than its slice of LDS holds), items never sent to it (items_loop), then, summed over
+        the items the kernel answered, the item counters of compose_sigma_stats (exact_items, sigma_items, sigma_arcs,
+        refused_items) and the widest level among them (max_level_width)."""
+        vals = [C.c_uint64() for _ in _lib.SIGMA_BATCH_COUNTERS]
+        check(_lib.lib().wfst_ctx_get_sigma_batch_counters(self._h, *[C.byref(v) for v in vals]),
+              "wfst_ctx_get_sigma_batch_counters")
+        return {k: int(v.value) for k, v in zip(_lib.SIGMA_BATCH_COUNTERS, vals)}
+
     def trim_pool(self):
         """Frees every device block the context's pool holds without an owner: cached blocks and parked scratch
         (wfst_ctx_trim_pool).  Synchronises the device."""
@@ -734,12 +745,21 @@ def compose_shortest_path_batch(acceptors: Sequence[DeviceFst], t: DeviceFst,
                                 shortest_path_config: Optional["ShortestPathConfig"] = None,
                                 ctx: Optional[Context] = None):
     """for a in acceptors: shortest_path(compose(a, t)) as one device-resident pipeline.
-    Returns (list of DeviceFst paths, total composed arcs before trimming)."""
+    Returns (list of DeviceFst paths, total composed arcs before trimming).  A `compose_config` that carries a MatcherConfig
+    goes through wfst_compose_shortest_path_batch_with_matchers: strings against a sigma matcher on `t` run one wavefront
+    each in one launch, everything else as compose + shortest_path per item (Context.sigma_batch_stats says which)."""
     n = len(acceptors)
     ctx = ctx or t.ctx
     arr = acceptors._arr if isinstance(acceptors, HandleArray) else HandleArray(acceptors)._arr
     outs = (C.c_void_p * n)()
     na = C.c_uint64()
+    if compose_config is not None and (compose_config.matcher1_config is not None or compose_config.matcher2_config is not None):
+        m1, m2 = compose_config.matcher1_config, compose_config.matcher2_config  # (kept alive over the call)
+        check(_lib.lib().wfst_compose_shortest_path_batch_with_matchers(
+            ctx._h, arr, n, t._h, compose_config._c(matchers=True), m1._c() if m1 else None, m2._c() if m2 else None,
+            shortest_path_config._c() if shortest_path_config else None, outs, C.byref(na)),
+            "wfst_compose_shortest_path_batch_with_matchers")
+        return PathList(outs, n, ctx), na.value
     check(_lib.lib().wfst_compose_shortest_path_batch(
         ctx._h, arr, n, t._h, compose_config._c() if compose_config else None,
         shortest_path_config._c() if shortest_path_config else None, outs, C.byref(na)),
@@ -1037,7 +1057,7 @@ class ComposeConfig:
         self.matcher2_config = matcher2_config
 
     def _c(self, matchers: bool = False):
-        """wfst_compose_config; `matchers`: the caller passes the matcher configs on (only DeviceFst.compose does)"""
+        """wfst_compose_config; `matchers`: the caller passes the matcher configs on (DeviceFst.compose and compose_shortest_path_batch do)"""
         if not matchers and (self.matcher1_config is not None or self.matcher2_config is not None):
             raise WfstError("unsupported: a MatcherConfig (sigma matcher) outside compose / compose_with_config")
         return C.pointer(_lib.ComposeConfig(self.compose_filter.value, 1 if self.connect else 0))
