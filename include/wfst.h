@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -876,6 +876,18 @@ wfst_status wfst_ctx_get_compose_path_stats(wfst_ctx* ctx, uint64_t* string_answ
  *        runs        runs of at least one level.
  *      Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
 wfst_status wfst_ctx_get_string_run_stats(wfst_ctx* ctx, uint64_t* run_levels, uint64_t* runs);
+
+/* ---- the pair levels of the same kernel in the same call.  The loop that takes the run levels also carries a frontier of
+ *      one or two states (every block of at most 64 arcs) over a level whose matches, in (frontier state, arc position)
+ *      order, are one or two with distinct destinations, where a level behind it in the string and the new states plus
+ *      one fit the problem's LDS slice: match j makes state hi + j with its one way in, and the rows of the new states are
+ *      asked for before they are settled.  A level of one state and one match is a run level and counted above, not here.
+ *      WFST_STRING_PAIR=0 (and WFST_STRING_RUN=0) turns them off; same results bit for bit.  Tallied and reset like the run
+ *      counters.
+ *        pair_levels  levels carried that are not run levels,
+ *        pair_splits  those of them with two matches.
+ *      Either pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_string_pair_counts(wfst_ctx* ctx, uint64_t* pair_levels, uint64_t* pair_splits);
 
 /* ---- which route the levels of the last wfst_determinize / wfst_determinize_with_distance call of ctx took.  The result
  *      is built breadth-first level by level, and every route returns the same FST, so only these counters show which one

@@ -103,12 +103,16 @@ COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "requir
 SIGMA_BATCH_COUNTERS = ("launches", "items_in_kernel", "items_handed_back", "items_loop", "exact_items", "sigma_items", "sigma_arcs",
                         "refused_items", "max_level_width")
 
+# wfst_ctx_get_string_pair_counts: the same, for the pair levels of the string kernel
+STRING_PAIR_COUNTS = ("pair_levels", "pair_splits")
+
 # every symbol include/wfst.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _f32, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_size_t
 _P = C.POINTER
 SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names in COUNTERS.values()] + [
     ("wfst_ctx_get_compose_sigma_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_SIGMA_COUNTERS)),
     ("wfst_ctx_get_sigma_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(SIGMA_BATCH_COUNTERS)),
+    ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
     ("wfst_string_destroy", C.c_int, [C.c_char_p]),
     ("wfst_abi_version", _u32, []),

@@ -312,6 +312,12 @@ struct wfst_ctx {
   struct StringRunStats {
     uint64_t run_levels = 0, runs = 0;
   } string_run;
+  // The pair levels of the same kernel in the same call (compose.hip, wfst_ctx_get_string_pair_counts): levels its run loop
+  // carried that are not run levels — a frontier of two states, or one state that matches two arcs — and those of them with
+  // two matches.  Tallied and zeroed where string_run is.
+  struct StringPairCounts {
+    uint64_t pair_levels = 0, pair_splits = 0;
+  } string_pair;
   // The last wfst_rm_epsilon call; zeroed when rm_epsilon.hip's driver begins.
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;

@@ -98,7 +98,9 @@ struct Result {
   uint32_t facts;     // string_compose_sp_kernel: OR of the path arcs' property facts (fst_props.h: path_arc_facts), or
                       // PATH_FACTS_NONE: the host knows the path FST's properties without reading its arcs back
   uint32_t run_levels, runs;  // string_compose_sp_kernel: levels taken inside chase runs, and the number of runs (0 elsewhere)
-  uint32_t done;      // string_compose_sp_kernel, results in pinned memory: the run's ticket, written after everything else of
+  uint32_t pair_levels, pair_splits;  // ... levels the run's loop carried that are not run levels (a frontier of two states, or one
+                                      // state that matches two arcs), and those of them with two matches (0 elsewhere)
+  uint32_t done;     // string_compose_sp_kernel, results in pinned memory: the run's ticket, written after everything else of
                       // the problem (system-scope fence in between): the host waits for these words instead of the stream
 #ifdef WFST_PHASE_TIMING
   unsigned long long dbg[8];
@@ -580,6 +582,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
   res.path_off = 0;
   res.n_levels = 0;
   res.facts = props::PATH_FACTS_NONE;
+  res.run_levels = res.runs = res.pair_levels = res.pair_splits = 0;
 
   __shared__ FastStage stg;
   PT_DECL
@@ -1031,7 +1034,8 @@ constexpr uint32_t STR_NONE = 0xFFFFFFFFu;
 __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDesc* __restrict__ descs, FstView f2,
                                                                 Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
                                                                 uint32_t path_cap, uint32_t n_problems, uint32_t maxs, uint64_t f2_n_arcs,
-                                                                uint32_t scalar_rows, uint32_t run_on, uint32_t done_ticket) {
+                                                                uint32_t scalar_rows, uint32_t run_on, uint32_t pair_on,
+                                                                uint32_t done_ticket) {
   extern __shared__ uint32_t s_dyn[];
   const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (p >= n_problems) return;
@@ -1062,7 +1066,7 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   res.path_off = 0;
   res.n_levels = 0;
   res.facts = props::PATH_FACTS_NONE;
-  res.run_levels = res.runs = 0;
+  res.run_levels = res.runs = res.pair_levels = res.pair_splits = 0;
   PT_DECL
   if (f1.start < 0 || f2.start < 0) {  // compute_start -> None
     STR_RESULT();
@@ -1106,6 +1110,14 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
   // are rotated between the segments of a run, not inside the level.  A level that is not such a one (no match, several
   // matches, a longer block, the string's last level, the last state of the slice) ends the run with `pos` on it and is
   // done by the general level below, from the rows the run already holds (pf) where it has them.
+  // Pair levels (pair_on, vector rows): the run's loop also carries a frontier of TWO states.  A level whose frontier has one
+  // or two states (each block within one chunk) and whose matches, taken in (frontier state, arc position) order, are one or
+  // two with distinct destinations makes exactly those states, in that order: no destination is met twice, so there is no
+  // find_id hit and no second way in, and on_match would give match j the id hi + j, the parent lo + f and the value
+  // (d_f + ws) + 0 — which is what the pair level writes, asking for the rows of both new states first and settling under
+  // that load.  Everything else (no match, three matches or more, two matches into one state — dedup and the strict tie
+  // rule stay on_match's —, a longer block, the last level, hi + t reaching the slice) ends the run as before; a frontier of
+  // two goes to the general level without rows (it asks for both blocks at once), a frontier of one with its rows.
   PT_MARK(6)  // prologue
   for (uint32_t pos = 0; pos < L && F && ok; ++pos) {
     if (pos && (pos & 63u) == 0u) {
@@ -1129,10 +1141,22 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
         // `lane < fc` as a scalar mask, made under the load: the compare's own mask is then the ballot (the predicate as a lane
         // value costs the chain two dependent vector instructions more)
         uint64_t fcm = fc >= 64u ? ~0ull : (1ull << fc) - 1ull;
+        // the second state of a carried frontier (`two`): its rows in (b, bx), its block and its distance; state 0's are
+        // (a, nx), fb / fc and dd
+        uint4 b = make_uint4(0, 0, 0, 0);
+        uint2 bx = make_uint2(0, 0);
+        uint32_t fb1 = 0, fc1 = 0;
+        float dd1 = INF;
+        bool two = false;
+        const bool pairs = pair_on != 0u && !scalar_rows;
+        uint32_t n_run = 0, n_runs = 0, n_pair = 0, n_split = 0;
+        bool in_run = false;  // the last level taken was a run level: the counter's runs are maximal sequences of those
         PT_MARK(5)
         for (bool go = true; go;) {  // one pass = the run's levels inside one 64-label chunk of the string
           bool on_boundary = false;  // the last level taken moved pos onto the next chunk
-          for (;;) {
+          bool split = false;        // the run levels stopped on a level of two matches: the pair level below looks at it
+          const uint32_t s0 = pos;
+          if (!two) for (;;) {
             const uint32_t label = rl(ch_cur.x, pos & 63u);
             const float w1 = __uint_as_float(rl(ch_cur.z, pos & 63u));
             PT_MARK(3)  // run: the last level's settle and counters, under the load
@@ -1184,6 +1208,112 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
             }
             if (on_boundary) break;
           }
+          if (pos != s0) {
+            n_run += pos - s0;
+            n_runs += in_run ? 0u : 1u;
+            in_run = true;
+          }
+          // (the run level's loop is left as it was: whether the level it stopped on, rows in hand, has two matches is asked here)
+          if (pairs && !two && pf && pos + 1u < L_u && hi + 2u < maxs &&
+              __popcll(__ballot(a.x == rl(ch_cur.x, pos & 63u)) & fcm) == 2) {
+            split = true;
+            pf = false;
+            go = true;
+          }
+          // ---- pair levels: a frontier of two states, or the level of two matches the run levels stopped on.  One trip to
+          // memory per level like a run level, off the run level's chain
+          if (go && (two || split)) for (;;) {
+            const uint32_t label = rl(ch_cur.x, pos & 63u);
+            const float w1 = __uint_as_float(rl(ch_cur.z, pos & 63u));
+            PT_MARK(3)
+            PT_ROWS_IN()
+            PT_MARK(4)
+            const uint64_t m0 = __ballot(a.x == label) & fcm;
+            const uint64_t m1 = two ? __ballot(b.x == label) & (fc1 >= 64u ? ~0ull : (1ull << fc1) - 1ull) : 0ull;
+            const uint32_t c0 = (uint32_t)__popcll(m0), t = c0 + (uint32_t)__popcll(m1);
+            if (t == 0u || t > 2u || hi + t >= maxs) {  // the general level's (one state: with its rows)
+              pf = !two;
+              go = false;
+              break;
+            }
+            // match j, in (frontier state, arc position) order, sits in lane lj of state 0's rows, or (from_b) of state 1's
+            const bool from_b0 = c0 == 0u, from_b1 = c0 < 2u;
+            const uint32_t l0 = (uint32_t)__ffsll((unsigned long long)(from_b0 ? m1 : m0)) - 1u;
+            const uint64_t rest = c0 == 1u ? m1 : (from_b1 ? m1 & (m1 - 1ull) : m0 & (m0 - 1ull));
+            const uint32_t l1 = t == 2u ? (uint32_t)__ffsll((unsigned long long)rest) - 1u : 0u;
+            auto field = [&](bool from_b, uint32_t va, uint32_t vb, uint32_t l) -> uint32_t { return from_b ? rl(vb, l) : rl(va, l); };
+            const uint32_t xb0 = field(from_b0, nx.x, bx.x, l0), xc0 = field(from_b0, nx.y, bx.y, l0);
+            const uint32_t ol0 = field(from_b0, a.y, b.y, l0), w2u0 = field(from_b0, a.z, b.z, l0);
+            uint32_t xb1 = 0, xc1 = 0, ol1 = 0, w2u1 = 0;
+            if (t == 2u) {
+              if (field(from_b0, a.w, b.w, l0) == field(from_b1, a.w, b.w, l1)) {  // one destination by two ways: on_match's
+                pf = !two;
+                go = false;
+                break;
+              }
+              xb1 = field(from_b1, nx.x, bx.x, l1);
+              xc1 = field(from_b1, nx.y, bx.y, l1);
+              ol1 = field(from_b1, a.y, b.y, l1);
+              w2u1 = field(from_b1, a.z, b.z, l1);
+            }
+            if (lane < xc0 && xc0 <= 64u) {  // (everything of the old rows is read off)
+              a = ld_global16(f2.arcs + xb0 + lane);
+              nx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (xb0 + lane));
+            }
+            if (t == 2u && lane < xc1 && xc1 <= 64u) {
+              b = ld_global16(f2.arcs + xb1 + lane);
+              bx = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(f2.anext) + 8ull * (xb1 + lane));
+            }
+            PT_MARK(5)
+            // ---- under the load: states hi and (t == 2) hi + 1, each with one way in
+            const uint32_t lo_r = hi - (two ? 2u : 1u);
+            const float d0 = from_b0 ? dd1 : dd, d1 = from_b1 ? dd1 : dd;
+            const float ws0 = wtimes(w1, __uint_as_float(w2u0));  // add_tr, compose_fst_op.rs:267-285
+            float cand0 = INF, cand1 = INF, ws1 = 0.0f;
+            if (d0 < INF) cand0 = (d0 + ws0) + 0.0f;
+            const bool reached0 = cand0 < INF;
+            bool reached1 = false;
+            if (t == 2u) {
+              ws1 = wtimes(w1, __uint_as_float(w2u1));
+              if (d1 < INF) cand1 = (d1 + ws1) + 0.0f;
+              reached1 = cand1 < INF;
+            }
+            if (lane == 0) {
+              s_ol[hi] = ol0;
+              s_w[hi] = ws0;
+              s_par[hi] = reached0 ? lo_r + (from_b0 ? 1u : 0u) : STR_NONE;
+              if (t == 2u) {
+                s_ol[hi + 1u] = ol1;
+                s_w[hi + 1u] = ws1;
+                s_par[hi + 1u] = reached1 ? lo_r + (from_b1 ? 1u : 0u) : STR_NONE;
+              }
+            }
+            dd = reached0 ? cand0 : INF;
+            dd1 = reached1 ? cand1 : INF;
+            fb = xb0;
+            fc = xc0;
+            fcm = fc >= 64u ? ~0ull : (1ull << fc) - 1ull;
+            fb1 = xb1;
+            fc1 = xc1;
+            two = t == 2u;
+            n_arcs += t;
+            hi += t;
+            pos += 1;
+            n_pair += 1u;
+            n_split += two ? 1u : 0u;
+            in_run = false;
+            on_boundary = (pos & 63u) == 0u;
+            if (fc > 64u || fc1 > 64u) {  // a longer block: the general level loads it chunk by chunk
+              go = false;
+              break;
+            }
+            if (!(pos + 1u < L_u && hi + 1u < maxs)) {  // the general level's
+              pf = !two;
+              go = false;
+              break;
+            }
+            if (on_boundary || !two) break;
+          }
           if (on_boundary) {  // the next 64 labels of the string (the loop's head does this only where no run moved pos there)
             ch_cur = ch_nxt;
             ch_nxt = make_uint4(0, 0, 0, 0);
@@ -1194,17 +1324,24 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
           pf_a = a;
           pf_nx = nx;
         }
-        const uint32_t n_run = pos - p0;
-        if (n_run) {
+        if (pos != p0) {
           if (lane == 0) {
             nb = fb;
             nc = fc;
             d = dd;
           }
-          lo = hi - 1u;
+          if (two && lane == 1) {
+            nb = fb1;
+            nc = fc1;
+            d = dd1;
+          }
+          F = two ? 2u : 1u;
+          lo = hi - F;
           level = pos;
           res.run_levels += n_run;
-          res.runs += 1u;
+          res.runs += n_runs;
+          res.pair_levels += n_pair;
+          res.pair_splits += n_split;
         }
         PT_MARK(3)
       }
@@ -1661,7 +1798,10 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
         env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u),
         // the chase run of the vector path (WFST_STRING_RUN=0: every level is the general one; 2: also on the scalar-row path:
         // a measurement setting — profiles/string_run_ab.md has its figure; launches of <= 8 strings keep their route)
-        env.has("WFST_STRING_RUN") ? (uint32_t)std::min(std::max(std::atoi(env.get("WFST_STRING_RUN")), 0), 2) : 1u, run.done_ticket);
+        env.has("WFST_STRING_RUN") ? (uint32_t)std::min(std::max(std::atoi(env.get("WFST_STRING_RUN")), 0), 2) : 1u,
+        // pair levels inside the run of the vector path (WFST_STRING_PAIR=0: a run ends at every level that is not one state
+        // with one match, as before profiles/string_pair_ab.md)
+        env.has("WFST_STRING_PAIR") ? (std::atoi(env.get("WFST_STRING_PAIR")) != 0 ? 1u : 0u) : 1u, run.done_ticket);
   } else {
     compose_wave_kernel<FLAGS><<<(uint32_t)n, 64, 0, st>>>(k_desc, f2, caps, run.arena.p, run.stride, k_res, k_paths, path_cap,
                                                             run.d_cursor.p);
@@ -1721,6 +1861,12 @@ void launch_end(wfst_ctx* ctx, BatchRun& run) {
       lv += h_res[i].n_levels;
       rlv += h_res[i].run_levels;
     }
+    if (std::getenv("WFST_PHASE_PER_PROBLEM"))  // one line per problem: its stamped total against the levels it took outside runs
+      for (size_t i = 0; i < n; ++i) {
+        unsigned long long sum = 0;
+        for (int k = 0; k < 8; ++k) sum += h_res[i].dbg[k];
+        std::fprintf(stderr, "[string problem] %zu cycles %llu levels %u in_runs %u pair_levels %u\n", i, sum, h_res[i].n_levels, h_res[i].run_levels, h_res[i].pair_levels);
+      }
     std::fprintf(stderr, "[string phase ticks/problem] general: rows wait %llu | under the early load %llu | arrival->issue %llu || run: rows wait %llu | arrival->issue %llu | under the load %llu || prologue %llu | epilogue %llu  (n=%zu, levels/problem %.1f, of them in runs %.1f)\n",
                  tot[0] / n, tot[1] / n, tot[2] / n, tot[4] / n, tot[5] / n, tot[3] / n, tot[6] / n, tot[7] / n, n, (double)lv / n, (double)rlv / n);
   }
@@ -1937,6 +2083,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   job->n = n;
   ctx->compose_path = wfst_ctx::ComposePathStats{};
   ctx->string_run = {};
+  ctx->string_pair = {};
   if (n == 0) return job.release();
   job->env = EnvSnap::take();
   job->run_s.env = &job->env;
@@ -2052,6 +2199,8 @@ void compose_shortest_path_batch_end(wfst_batch_job* job_raw, wfst_fst** outs, u
         n_string_ok += 1;
         ctx->string_run.run_levels += r.run_levels;
         ctx->string_run.runs += r.runs;
+        ctx->string_pair.pair_levels += r.pair_levels;
+        ctx->string_pair.pair_splits += r.pair_splits;
         ok.push_back(k);
       }
       // the path FSTs (three small vectors and a handle each: ~0.4 us): a large batch shares them out among host threads
@@ -2177,3 +2326,13 @@ wfst_fst* batch_path_fst(wfst_ctx* ctx, bool has_path, uint32_t hops, float fina
 }
 
 }  // namespace wfst
+
+// The pair levels of the last fused-batch call of ctx (common.h: wfst_ctx::string_pair), beside their tally in
+// compose_shortest_path_batch_end.  Either out-pointer may be null.
+extern "C" wfst_status wfst_ctx_get_string_pair_counts(wfst_ctx* ctx, uint64_t* pair_levels, uint64_t* pair_splits) {
+  return wfst::wrap([&] {
+    if (!ctx) throw wfst::Error("null pointer");
+    if (pair_levels) *pair_levels = ctx->string_pair.pair_levels;
+    if (pair_splits) *pair_splits = ctx->string_pair.pair_splits;
+  });
+}

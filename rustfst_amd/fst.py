@@ -122,6 +122,17 @@ class Context:
         the problems the kernel answered.  Both are 0 with WFST_STRING_RUN=0 and on the scalar-row path."""
         return _counters("string_run", self)
 
+    def string_pair_counts(self) -> dict:
+        """The pair levels of the string kernel in this context's last compose_shortest_path_batch call
+        (wfst_ctx_get_string_pair_counts): levels its run loop carried that are not run levels — a frontier of two states,
+        or one state that matches two arcs, one or two matches in all with distinct destinations — (pair_levels) and those
+        of them with two matches (pair_splits), summed over the problems the kernel answered.  Both are 0 with
+        WFST_STRING_PAIR=0, with WFST_STRING_RUN=0 and on the scalar-row path."""
+        vals = [C.c_uint64() for _ in _lib.STRING_PAIR_COUNTS]
+        check(_lib.lib().wfst_ctx_get_string_pair_counts(self._h, *[C.byref(v) for v in vals]),
+              "wfst_ctx_get_string_pair_counts")
+        return {k: int(v.value) for k, v in zip(_lib.STRING_PAIR_COUNTS, vals)}
+
     def determinize_stats(self) -> dict:
         """Which route the levels of this context's last determinize / determinize_with_distance call took
         (wfst_ctx_get_determinize_stats): levels completed (levels) and those the device-wide launches ran (wide_levels),
