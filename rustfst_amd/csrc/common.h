@@ -518,7 +518,9 @@ struct HandleDeleter {
   }
 };
 using Handle = std::unique_ptr<wfst_fst, HandleDeleter>;
-// 64-bit finalizer (MurmurHash3 fmix64) of the device hash tables
+// 64-bit finalizer (MurmurHash3 fmix64) of the device hash tables, and the odd word (2^64 / phi) that spreads a second key
+// word before it
+constexpr uint64_t GOLDEN64 = 0x9E3779B97F4A7C15ull;
 __device__ inline uint64_t mix64(uint64_t x) {
   x ^= x >> 33;
   x *= 0xff51afd7ed558ccdull;
@@ -590,6 +592,8 @@ void tr_sort_device(wfst_ctx* ctx, wfst_fst* f, bool ilabel_cmp);
 void project_device(wfst_ctx* ctx, wfst_fst* f, bool project_output);
 // compose.hip
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter = 0);
+// ... the match mode its operands' property words leave (0 both, 1 input, 2 output), or the reference's error
+uint32_t decide_match_mode(uint64_t p1, uint64_t p2);
 void compose_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n, const wfst_fst* t, bool connect,
                                  wfst_fst** outs, uint64_t* composed_arcs, uint32_t filter = 0);
 wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n, const wfst_fst* t,

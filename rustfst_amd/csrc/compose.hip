@@ -28,7 +28,7 @@
 #include <cstring>
 
 #include "common.h"
-#include "compose_filters.h"
+#include "compose_match.h"
 #include "fst_props.h"
 #include "host_parallel.h"
 
@@ -36,8 +36,6 @@ namespace wfst {
 
 namespace {
 
-constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
-constexpr uint32_t REJECT = 0xFFFFFFFFu;  // FilterState::new_no_state()
 // bits of the 4th word of a state record (fst_store.hip derive_noeps_kernel; common.h SREC_*)
 using wfst::SREC_ALL_IEPS;
 using wfst::SREC_ALL_OEPS;
@@ -48,7 +46,6 @@ constexpr uint32_t HV_INIT = 0xFFFFFFFFu;
 constexpr uint32_t HV_PEND = 0x80000000u;
 constexpr uint64_t KEY_INF = ~0ull;
 
-enum : uint32_t { MODE_BOTH = 0, MODE_INPUT = 1, MODE_OUTPUT = 2 };  // MatchType after match_type()
 enum : uint32_t {
   ST_OK = 0, ST_OVERFLOW_STATES = 1, ST_OVERFLOW_ARCS = 2, ST_OVERFLOW_HASH = 3, ST_OVERFLOW_PATH = 4,
   ST_NOT_A_STRING_CASE = 5,  // the string o T kernel met a case it does not cover: redo on the general kernel
@@ -125,25 +122,8 @@ struct Arena {
 };
 
 __host__ __device__ inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t arena_bytes(const Caps& c) {
-  size_t b = 0;
-  b += al16((size_t)c.S * 8);        // tuples
-  b += al16((size_t)c.H * 8);        // hkeys
-  b += al16((size_t)c.S * 8);        // skey
-  b += al16((size_t)c.S * 8);        // parent
-  b += al16((size_t)c.A * 16);       // arcs
-  b += al16((size_t)c.A * 16);       // t_arcs
-  b += al16((size_t)c.H * 4);        // hvals
-  b += al16((size_t)(c.S + 1) * 4);  // off
-  b += al16((size_t)(c.S + 1) * 4);  // t_off
-  b += al16((size_t)c.S * 4);        // fin
-  b += al16((size_t)c.S * 4);        // t_fin
-  b += al16((size_t)c.S * 4);        // aux
-  b += al16((size_t)c.S * 4);        // aux2
-  b += al16((size_t)(c.S + 1) * 4);  // lvl
-  return (b + 255) & ~(size_t)255;
-}
-__device__ inline Arena carve_arena(char* base, const Caps& c) {
+// one problem's arena (a batch = arena_bytes(caps) apart); *bytes_out, when asked for, is its size
+__host__ __device__ inline Arena carve_arena(char* base, const Caps& c, size_t* bytes_out = nullptr) {
   Arena a;
   char* p = base;
   a.tuples = (uint64_t*)p; p += al16((size_t)c.S * 8);
@@ -159,72 +139,16 @@ __device__ inline Arena carve_arena(char* base, const Caps& c) {
   a.t_fin = (float*)p; p += al16((size_t)c.S * 4);
   a.aux = (uint32_t*)p; p += al16((size_t)c.S * 4);
   a.aux2 = (uint32_t*)p; p += al16((size_t)c.S * 4);
-  a.lvl = (uint32_t*)p;
+  a.lvl = (uint32_t*)p; p += al16((size_t)(c.S + 1) * 4);
+  if (bytes_out) *bytes_out = ((size_t)(p - base) + 255) & ~(size_t)255;
   return a;
 }
-
-// ---------------------------------------------------------------- wave helpers (wave = 64 lanes)
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {  // popcount of mask bits below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, uint32_t* total) {
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  *total = __shfl(x, 63);
-  return x - v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    unsigned long long o = __shfl_xor(v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-// broadcast from a wave-uniform lane: v_readlane (scalar path) instead of a ds_bpermute round trip
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
-}
-__device__ __forceinline__ uint64_t rl64(uint64_t v, uint32_t src) {
-  return ((uint64_t)rl((uint32_t)(v >> 32), src) << 32) | rl((uint32_t)v, src);
-}
-__device__ __forceinline__ uint4 rl128(uint4 v, uint32_t src) {
-  return make_uint4(rl(v.x, src), rl(v.y, src), rl(v.z, src), rl(v.w, src));
-}
-// LDS traffic of one wave is processed in issue order, so lanes of the (single-wave) workgroup only need
-// the compiler not to reorder around the hand-off and the LDS counter drained: no vmcnt wait, no s_barrier.
-__device__ __forceinline__ void lds_handoff() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// The wave is a whole workgroup (blockDim == 64): __syncthreads() is the wave-level fence that makes
-// the lanes' global-memory writes visible to each other between phases.
-__device__ __forceinline__ void wave_sync() { __syncthreads(); }
-
-template <class T>
-__device__ __forceinline__ T ld_l2(const T* p) {  // L2-served load for words other lanes update atomically
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <class T>
-__device__ __forceinline__ void st_l2(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+inline size_t arena_bytes(const Caps& c) {
+  size_t b = 0;
+  carve_arena(nullptr, c, &b);
+  return b;
 }
 
-__device__ __forceinline__ uint32_t hash_u64(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return (uint32_t)h;
-}
 // ComposeStateTuple {fs, s1, s2} in one u64: fs (0..2) : 2 | s1 : 30 | s2 : 32
 constexpr uint32_t TUPLE_S1_MASK = 0x3FFFFFFFu;
 __device__ __forceinline__ uint64_t pack_tuple(uint32_t fs, uint32_t s1, uint32_t s2) {
@@ -236,7 +160,7 @@ __device__ __forceinline__ uint32_t tuple_s1(uint64_t tk) { return (uint32_t)(tk
 // atomicMin(first emission index of this level) while the tuple is new, then its final id.
 __device__ __forceinline__ uint32_t ht_insert(uint64_t* hkeys, uint32_t* hvals, uint32_t hmask, uint64_t key,
                                               uint32_t pend) {
-  uint32_t slot = hash_u64(key) & hmask;
+  uint32_t slot = (uint32_t)mix64(key) & hmask;
   for (uint32_t probes = 0; probes <= hmask; ++probes) {
     const uint64_t k = hkeys[slot];  // may be a stale EMPTY: the CAS below is the arbiter
     if (k == key) break;
@@ -249,55 +173,6 @@ __device__ __forceinline__ uint32_t ht_insert(uint64_t* hkeys, uint32_t* hvals, 
   }
   atomicMin(&hvals[slot], pend);
   return slot;
-}
-
-struct ArcReg {
-  uint32_t il, ol;
-  float w;
-  uint32_t ns;
-};
-// Pointers that reach the kernel through a descriptor in memory (fst1 of every problem) are generic to the compiler,
-// which then emits FLAT loads: slower, and they tie the LDS and the vector-memory wait counters together.  Everything an
-// FstView points to is device memory, so say so.
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef const u32x4_t __attribute__((address_space(1)))* global_u4_ptr;
-__device__ __forceinline__ uint4 ld_global16(const void* p) {
-  // (the integer round trip is what makes the compiler drop "generic")
-  const u32x4_t v = *(global_u4_ptr)(unsigned long long)p;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-typedef const uint32_t __attribute__((address_space(1)))* global_u32_ptr;
-__device__ __forceinline__ uint32_t ld_global4(const void* p) { return *(global_u32_ptr)(unsigned long long)p; }
-__device__ __forceinline__ ArcReg load_arc(const wfst_tr* p) {
-  const uint4 v = ld_global16(p);  // one 16-B load
-  return ArcReg{v.x, v.y, __uint_as_float(v.z), v.w};
-}
-__device__ __forceinline__ void store_arc(wfst_tr* p, uint32_t il, uint32_t ol, float w, uint32_t ns) {
-  *reinterpret_cast<uint4*>(p) = make_uint4(il, ol, __float_as_uint(w), ns);
-}
-__device__ __forceinline__ ArcReg shfl_arc(const ArcReg& a, uint32_t src) {
-  return ArcReg{(uint32_t)__shfl(a.il, src), (uint32_t)__shfl(a.ol, src), __shfl(a.w, src), (uint32_t)__shfl(a.ns, src)};
-}
-
-// lower / upper bound on the searched side's key column (superslice lower_bound_by,
-// matchers/sorted_matcher.rs:141-142), per lane, for arc blocks larger than one wave.
-__device__ inline void equal_range_global(const wfst_tr* arcs, uint32_t n, bool by_ilabel, uint32_t key, uint32_t* lo_out,
-                                          uint32_t* cnt_out) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint32_t mid = lo + ((hi - lo) >> 1);
-    uint32_t k = ld_global4(by_ilabel ? &arcs[mid].ilabel : &arcs[mid].olabel);
-    if (k < key) lo = mid + 1; else hi = mid;
-  }
-  uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    uint32_t mid = lo + ((hi - lo) >> 1);
-    uint32_t k = ld_global4(by_ilabel ? &arcs[mid].ilabel : &arcs[mid].olabel);
-    if (k <= key) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = first;
-  *cnt_out = lo - first;
 }
 
 // Optional per-phase cycle accounting (build with -DWFST_PHASE_TIMING; results land in Result::dbg).
@@ -391,7 +266,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
   ArcReg se{0, 0, 0.0f, 0};
   uint32_t se_key = 0xFFFFFFFEu;
   if (small && lane < n_se) {
-    se = load_arc(se_arcs + lane);
+    se = load_arc<GlobalLoad>(se_arcs + lane);
     se_key = mi ? se.il : se.ol;
   }
   const float src_d = key_f32((uint32_t)(src_sk >> 32));
@@ -408,7 +283,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
       if (j == 0)
         ab = mi ? ArcReg{0u, NO_LABEL, 0.0f, sb} : ArcReg{NO_LABEL, 0u, 0.0f, sb};
       else
-        ab = load_arc(it_arcs + (j - 1));
+        ab = load_arc<GlobalLoad>(it_arcs + (j - 1));
     }
     const uint32_t label = mi ? ab.ol : ab.il;                    // match_tr :333
     const uint32_t skey = label == NO_LABEL ? 0u : label;          // IteratorSortedMatcher::new :131-135
@@ -424,27 +299,27 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
         }
       }
     } else if (have) {
-      equal_range_global(se_arcs, n_se, mi, skey, &lo, &cnt);
+      equal_range<GlobalLoad>(se_arcs, n_se, mi, skey, &lo, &cnt);
     }
     uint32_t fsn;  // filter state of the emitted arcs of this item (of its real pairs when eps_item)
     bool eps_item = false;
     uint32_t loop1 = 0;  // 1: the first pair of an eps_item is the matcher's EpsLoop (accepted by the filter)
     if (!have) {
       cnt = 0;
-      fsn = REJECT;
+      fsn = FILTER_REJECT;
     } else if (label == NO_LABEL) {
       fsn = fs_nolabel;  // real arcs with key 0, no EpsLoop (sorted_matcher.rs:127-139)
     } else if (label == 0u) {
       // the matcher yields EpsLoop first, then the real epsilon arcs (:124-184); the filter sees the loop as class
       // X/Y and the real ones as class Z (rejected by the sequence filters, accepted by Null/Trivial/Match)
       eps_item = true;
-      loop1 = fs_eps != REJECT ? 1u : 0u;
+      loop1 = fs_eps != FILTER_REJECT ? 1u : 0u;
       fsn = fsZ;
-      cnt = loop1 + (fsZ != REJECT ? cnt : 0u);
+      cnt = loop1 + (fsZ != FILTER_REJECT ? cnt : 0u);
     } else {
       fsn = fsM;
     }
-    if (!eps_item && fsn == REJECT) cnt = 0;
+    if (!eps_item && fsn == FILTER_REJECT) cnt = 0;
     uint32_t total, pos, maxcnt;
     if (__ballot(cnt > 1u) == 0) {  // every item emits 0 or 1 arc (the usual case): two ballots replace the scans
       const uint64_t em = __ballot(cnt == 1u);
@@ -472,7 +347,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
         aa = shfl_arc(se, (lo + m - loop1) & 63u);
       } else {
         aa = ArcReg{0, 0, 0.0f, 0};
-        if (m < cnt && !is_loop) aa = load_arc(se_arcs + lo + m - loop1);
+        if (m < cnt && !is_loop) aa = load_arc<GlobalLoad>(se_arcs + lo + m - loop1);
       }
       if (m < cnt) {
         const uint32_t fsn_m = is_loop ? fs_eps : fsn;
@@ -517,7 +392,7 @@ __device__ int expand_state(const FstView& f1, const FstView& f2, uint32_t mode,
 // StateTable::find_id for a tuple seen for the first time in this level (fast path): CAS first, so a
 // new tuple costs one L2 round trip.  Returns the slot; *existed tells whether an earlier level owns it.
 __device__ __forceinline__ uint32_t ht_find_or_insert(uint64_t* hkeys, uint32_t hmask, uint64_t key, bool* existed) {
-  uint32_t slot = hash_u64(key) & hmask;
+  uint32_t slot = (uint32_t)mix64(key) & hmask;
   for (uint32_t probes = 0; probes <= hmask; ++probes) {
     const uint64_t prev = atomicCAS((unsigned long long*)&hkeys[slot], (unsigned long long)HT_EMPTY,
                                     (unsigned long long)key);
@@ -548,7 +423,7 @@ __device__ bool relax_states(const Arena& ar, uint32_t lo, uint32_t hi, uint32_t
         const uint32_t h1 = (uint32_t)kq + 1u;
         const uint32_t b = ar.off[q], e = ar.off[q + 1];
         for (uint32_t i = b; i < e && i < n_arcs_total; ++i) {
-          const ArcReg a = load_arc(ar.arcs + i);
+          const ArcReg a = load_arc<GlobalLoad>(ar.arcs + i);
           const float c = (d + a.w) + 0.0f;
           if (!(c < INF)) continue;
           const uint64_t ck = ((uint64_t)f32_key(c) << 32) | h1;
@@ -847,7 +722,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
       const uint32_t q = base + lane;
       const bool keep = q < n_states && ld_l2(&ar.aux[q]) != 0u;
       const uint64_t m = __ballot(keep);
-      if (q < n_states) ar.aux2[q] = keep ? kept + lanes_below(m) : REJECT;
+      if (q < n_states) ar.aux2[q] = keep ? kept + lanes_below(m) : FILTER_REJECT;
       kept += (uint32_t)__popcll(m);
     }
     wave_sync();
@@ -855,12 +730,12 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
     uint32_t t_arcs = 0;
     for (uint32_t base = 0; base < n_states; base += 64) {
       const uint32_t q = base + lane;
-      const bool keep = q < n_states && ar.aux2[q] != REJECT;
+      const bool keep = q < n_states && ar.aux2[q] != FILTER_REJECT;
       uint32_t b = 0, e = 0, cnt = 0;
       if (keep) {
         b = ar.off[q];
         e = ar.off[q + 1];
-        for (uint32_t i = b; i < e; ++i) cnt += ar.aux2[ar.arcs[i].nextstate] != REJECT;
+        for (uint32_t i = b; i < e; ++i) cnt += ar.aux2[ar.arcs[i].nextstate] != FILTER_REJECT;
       }
       uint32_t total;
       const uint32_t pos = wave_excl_scan(cnt, lane, &total);
@@ -870,9 +745,9 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
         ar.t_off[nq] = w;
         ar.t_fin[nq] = ar.fin[q];
         for (uint32_t i = b; i < e; ++i) {
-          const ArcReg a = load_arc(ar.arcs + i);
+          const ArcReg a = load_arc<GlobalLoad>(ar.arcs + i);
           const uint32_t nn = ar.aux2[a.ns];
-          if (nn != REJECT) store_arc(ar.t_arcs + (w++), a.il, a.ol, a.w, nn);
+          if (nn != FILTER_REJECT) store_arc(ar.t_arcs + (w++), a.il, a.ol, a.w, nn);
         }
       }
       t_arcs += total;
@@ -880,7 +755,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
     if (lane == 0) ar.t_off[kept] = t_arcs;
     res.t_states = kept;
     res.t_arcs = t_arcs;
-    res.t_start = (kept && ar.aux2[0] != REJECT) ? (int32_t)ar.aux2[0] : -1;
+    res.t_start = (kept && ar.aux2[0] != FILTER_REJECT) ? (int32_t)ar.aux2[0] : -1;
     wave_sync();
   }
 
@@ -931,7 +806,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
             const uint32_t h1 = (uint32_t)kq + 1u;
             const uint32_t b = ar.off[q], e = ar.off[q + 1];
             for (uint32_t i = b; i < e; ++i) {
-              const ArcReg a = load_arc(ar.arcs + i);
+              const ArcReg a = load_arc<GlobalLoad>(ar.arcs + i);
               const float c = (d + a.w) + 0.0f;
               if (!(c < INF)) continue;
               const uint64_t ck = ((uint64_t)f32_key(c) << 32) | h1, kt = ld_l2(&ar.skey[a.ns]);
@@ -989,7 +864,7 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
             if (hi_ >= 1u) {
               const uint64_t pr = ld_l2(&ar.parent[i]);
               const uint32_t s = (uint32_t)(pr >> 32), pos = (uint32_t)pr;
-              const ArcReg a = load_arc(ar.arcs + ar.off[s] + pos);
+              const ArcReg a = load_arc<GlobalLoad>(ar.arcs + ar.off[s] + pos);
               const uint32_t k = hops - hi_;  // i is the k-th state created by the backtrace
               store_arc(path_buf + poff + k, a.il, a.ol, a.w, k);
             }
@@ -1629,22 +1504,6 @@ __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDes
 #undef STR_RESULT
 
 // ---------------------------------------------------------------- host side
-// ComposeFstOp::match_type (compose_fst_op.rs:169-197) with SortedMatcher::match_type
-// (matchers/sorted_matcher.rs:56-85): decided from the property bits only.
-uint32_t decide_match_mode(uint64_t p1, uint64_t p2) {
-  using namespace props;
-  const bool o_sorted = p1 & O_LABEL_SORTED, o_known = p1 & (O_LABEL_SORTED | NOT_O_LABEL_SORTED);
-  const bool i_sorted = p2 & I_LABEL_SORTED, i_known = p2 & (I_LABEL_SORTED | NOT_I_LABEL_SORTED);
-  if (o_sorted && i_sorted) return MODE_BOTH;
-  if (o_sorted) return MODE_OUTPUT;
-  if (i_sorted) return MODE_INPUT;
-  // neither known-sorted: match_type(true) -> properties_check fails when the bit pair is unknown
-  if (!o_known) throw Error("ComposeFst: 1st argument: label-sortedness properties are not known (sort?)");
-  if (!i_known) throw Error("ComposeFst: 2nd argument: label-sortedness properties are not known (sort?)");
-  throw Error(
-      "ComposeFst: 1st argument cannot match on output labels and 2nd argument cannot match on input labels (sort?).");
-}
-
 FstView view_of(const wfst_fst* f) {
   FstView v;
   v.offsets = f->dev.offsets;
@@ -1973,6 +1832,22 @@ void tally_status(wfst_ctx* ctx, uint32_t status, bool string_kernel, bool first
 
 }  // namespace
 
+// ComposeFstOp::match_type (compose_fst_op.rs:169-197) with SortedMatcher::match_type
+// (matchers/sorted_matcher.rs:56-85): decided from the property bits only.
+uint32_t decide_match_mode(uint64_t p1, uint64_t p2) {
+  using namespace props;
+  const bool o_sorted = p1 & O_LABEL_SORTED, o_known = p1 & (O_LABEL_SORTED | NOT_O_LABEL_SORTED);
+  const bool i_sorted = p2 & I_LABEL_SORTED, i_known = p2 & (I_LABEL_SORTED | NOT_I_LABEL_SORTED);
+  if (o_sorted && i_sorted) return MODE_BOTH;
+  if (o_sorted) return MODE_OUTPUT;
+  if (i_sorted) return MODE_INPUT;
+  // neither known-sorted: match_type(true) -> properties_check fails when the bit pair is unknown
+  if (!o_known) throw Error("ComposeFst: 1st argument: label-sortedness properties are not known (sort?)");
+  if (!i_known) throw Error("ComposeFst: 2nd argument: label-sortedness properties are not known (sort?)");
+  throw Error(
+      "ComposeFst: 1st argument cannot match on output labels and 2nd argument cannot match on input labels (sort?).");
+}
+
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter) {
   if (f1->n_states > TUPLE_S1_MASK) throw Error("compose: the 1st FST has more than 2^30 states");
   const uint32_t mode = decide_match_mode(f1->props, f2->props);
@@ -2014,20 +1889,10 @@ wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool co
     ctx->stats.compose_arcs = r.n_arcs;
     tally_status(ctx, r.status, false, attempt == 0);
     if (r.status == ST_OK) {
-      // carve the finished arrays out of the problem arena (same carve as the kernel)
-      const Caps& c = run.caps;
-      char* p = run.arena.p;
-      p += al16((size_t)c.S * 8) + al16((size_t)c.H * 8) + al16((size_t)c.S * 8) + al16((size_t)c.S * 8);
-      const wfst_tr* arcs = (const wfst_tr*)p; p += al16((size_t)c.A * 16);
-      const wfst_tr* t_arcs = (const wfst_tr*)p; p += al16((size_t)c.A * 16);
-      p += al16((size_t)c.H * 4);
-      const uint32_t* off = (const uint32_t*)p; p += al16((size_t)(c.S + 1) * 4);
-      const uint32_t* t_off = (const uint32_t*)p; p += al16((size_t)(c.S + 1) * 4);
-      const float* fin = (const float*)p; p += al16((size_t)c.S * 4);
-      const float* t_fin = (const float*)p;
+      const Arena a = carve_arena(run.arena.p, run.caps);  // the finished arrays, where the kernel put them
       if (connect)
-        return adopt_device(ctx, r.t_states, r.t_arcs, r.t_start, out_props, t_off, t_arcs, t_fin);
-      return adopt_device(ctx, r.n_states, r.n_arcs, r.n_states ? 0 : -1, out_props, off, arcs, fin);
+        return adopt_device(ctx, r.t_states, r.t_arcs, r.t_start, out_props, a.t_off, a.t_arcs, a.t_fin);
+      return adopt_device(ctx, r.n_states, r.n_arcs, r.n_states ? 0 : -1, out_props, a.off, a.arcs, a.fin);
     }
     if (r.status == ST_SWITCH_WIDE) return compose_wide(ctx, f1, f2, mode, filter, connect, out_props, 4 * est_s);
     ctx->stats.compose_retries++;

@@ -44,8 +44,6 @@ namespace wfst {
 
 namespace {
 
-constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
-constexpr uint32_t REJECT = 0xFFFFFFFFu;
 constexpr uint32_t WIDE_SWITCH_STATES = 2048;  // results larger than this are redone on the wide path
 constexpr uint32_t WIDE_SWITCH_WIDTH = 256;    // ... and so are results with a BFS level wider than this
 constexpr uint32_t WIDE_SWITCH_STATES_ONE = 512;  // the same two limits for a call with ONE composition
@@ -216,11 +214,11 @@ __device__ bool la_filter(const Reach& r, const LaView& f2, const StateCtx& c, c
     return false;
   }
   uint32_t f;  // AltSequenceComposeFilter::filter_tr :160-181
-  if (a2.il == NO_LABEL) f = c.alleps2 ? REJECT : (c.noeps2 ? 0u : 1u);
-  else if (a1.ol == NO_LABEL) f = c.fs.fs == 1u ? REJECT : 0u;
-  else if (a1.ol == 0u) f = REJECT;
+  if (a2.il == NO_LABEL) f = c.alleps2 ? FILTER_REJECT : (c.noeps2 ? 0u : 1u);
+  else if (a1.ol == NO_LABEL) f = c.fs.fs == 1u ? FILTER_REJECT : 0u;
+  else if (a1.ol == 0u) f = FILTER_REJECT;
   else f = 0u;
-  if (f == REJECT) return false;
+  if (f == FILTER_REJECT) return false;
   // LookAheadComposeFilter::lookahead_filter_tr :191-228: only an epsilon on fst1's output side looks ahead
   // (LOOKAHEAD_EPSILONS set, LOOKAHEAD_NON_EPSILONS not)
   const bool la_tr = a1.ol == 0u;
@@ -244,25 +242,6 @@ __device__ bool la_filter(const Reach& r, const LaView& f2, const StateCtx& c, c
   a2.ns = prefix.ns;
   *out = FState{f, q, prefix.il};
   return true;
-}
-
-// arcs of the searched side with key == label: [*lo, *lo + *cnt) relative to the state's first arc
-__device__ void equal_range(const wfst_tr* arcs, uint32_t n, bool by_ilabel, uint32_t key, uint32_t* lo_out, uint32_t* cnt_out) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k < key) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k <= key) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = first;
-  *cnt_out = lo - first;
 }
 
 // everything the expansion of ONE composed state needs (compute_trs, compose_fst_op.rs:406-418)
@@ -290,13 +269,7 @@ __device__ Expand make_expand(const LaView& f1, const LaView& f2, uint64_t tlo, 
     if (x.c.fs.flabel != NO_LABEL) w1 = INF;
     x.final_weight = wtimes(w1, fin2);
   }
-  x.mi = n1 <= n2;
-  x.it_arcs = x.mi ? f1.arcs + r1.x : f2.arcs + r2.x;
-  x.se_arcs = x.mi ? f2.arcs + r2.x : f1.arcs + r1.x;
-  x.n_it = x.mi ? n1 : n2;
-  x.n_se = x.mi ? n2 : n1;
-  x.sa = x.mi ? s2 : s1;
-  x.sb = x.mi ? s1 : s2;
+  select_sides(x, n1 <= n2, f1.arcs + r1.x, n1, s1, f2.arcs + r2.x, n2, s2);
   return x;
 }
 
@@ -309,7 +282,7 @@ __device__ Expand make_expand(const LaView& f1, const LaView& f2, uint64_t tlo, 
 __device__ uint32_t eval_item(const Reach& reach, const LaView& f2, const Expand& x, uint32_t j, bool write, uint32_t write_pos,
                               wfst_tr* arcs, uint64_t* a_lo, uint64_t* a_hi, Emitted* first = nullptr) {
   const bool mi = x.mi;
-  const ArcReg ab = j == 0 ? (mi ? ArcReg{0u, NO_LABEL, 0.0f, x.sb} : ArcReg{NO_LABEL, 0u, 0.0f, x.sb}) : load_arc(x.it_arcs + (j - 1));
+  const ArcReg ab = j == 0 ? loop_item(mi, x.sb) : load_arc(x.it_arcs + (j - 1));
   const uint32_t label = mi ? ab.ol : ab.il;
   const uint32_t flabel = x.c.fs.flabel;
   uint32_t has_loop = 0, loA = 0, cntA = 0, loB = 0, cntB = 0;
@@ -328,7 +301,7 @@ __device__ uint32_t eval_item(const Reach& reach, const LaView& f2, const Expand
   uint32_t k = 0;
   for (uint32_t m = 0; m < n_match; ++m) {
     ArcReg aa;
-    if (m < has_loop) aa = mi ? ArcReg{NO_LABEL, 0u, 0.0f, x.sa} : ArcReg{0u, NO_LABEL, 0.0f, x.sa};  // eps_loop, mod.rs:98-105
+    if (m < has_loop) aa = eps_loop(mi, x.sa);
     else if (m - has_loop < cntA) aa = load_arc(x.se_arcs + loA + (m - has_loop));
     else aa = load_arc(x.se_arcs + loB + (m - has_loop - cntA));
     const ArcReg a1 = mi ? ab : aa;  // arc1 from fst1, arc2 from fst2 (match_tr_selected :301-319)

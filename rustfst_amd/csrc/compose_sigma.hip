@@ -33,7 +33,6 @@
 //                            ends within a level.
 // Every single sigma call runs on this driver, whatever its size: the wave-per-problem kernels of compose.hip do not learn
 // about sigma.  Many utterances against one sigma grammar: compose_sigma_batch.hip.
-#include "compose_filters.h"
 #include "compose_wide.h"
 #include "fst_props.h"
 #include "sigma_ranges.h"
@@ -41,9 +40,6 @@
 namespace wfst {
 namespace {
 
-constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
-constexpr uint32_t REJECT = 0xFFFFFFFFu;
-enum : uint32_t { MODE_BOTH = 0, MODE_INPUT = 1, MODE_OUTPUT = 2 };
 constexpr uint64_t SG_NO_ERROR = ~0ull;
 // counters of the policy block: one 128-byte line each (same-address atomics serialise), 64-bit words
 enum : uint32_t { SG_REQUIRE1 = 0, SG_REQUIRE2, SG_EXACT, SG_SIGMA_ITEMS, SG_SIGMA_ARCS, SG_REFUSED, SG_COUNTERS };
@@ -148,7 +144,7 @@ struct SigmaPolicy {
     }
     const bool mi = x.mi;
     const SgSide& se = mi ? f2 : f1;
-    const ArcReg ab = j == 0 ? (mi ? ArcReg{0u, NO_LABEL, 0.0f, x.sb} : ArcReg{NO_LABEL, 0u, 0.0f, x.sb}) : load_arc(x.it_arcs + (j - 1));
+    const ArcReg ab = j == 0 ? loop_item(mi, x.sb) : load_arc(x.it_arcs + (j - 1));
     const uint32_t label = mi ? ab.ol : ab.il;
     if (se.sigma != NO_LABEL && label == se.sigma) {  // sigma_matcher.rs:199-201
       if (first_walk) atomicMin(err(), ((unsigned long long)x.wide_state_id << 32) | ((unsigned long long)j << 1) | 1ull);
@@ -160,12 +156,12 @@ struct SigmaPolicy {
     }
     if (x.dead) return 0u;
     uint32_t lo = 0, cnt = 0;
-    sg_equal_range(x.se_arcs, x.n_se, mi, label == NO_LABEL ? 0u : label, &lo, &cnt);
+    equal_range(x.se_arcs, x.n_se, mi, label == NO_LABEL ? 0u : label, &lo, &cnt);
     uint32_t loop1 = 0, fsn;
     if (label == NO_LABEL) {
       fsn = x.fs_nolabel;
     } else if (label == 0u) {
-      loop1 = x.fs_eps != REJECT ? 1u : 0u;
+      loop1 = x.fs_eps != FILTER_REJECT ? 1u : 0u;
       fsn = x.fsZ;
     } else {
       fsn = x.fsM;
@@ -185,11 +181,11 @@ struct SigmaPolicy {
       if (by_sigma && cnt > 1u) atomicAdd(ctr(SG_SIGMA_ARCS), (unsigned long long)cnt);
       sg_count(ctr(SG_REFUSED), fallback && !by_sigma);
     }
-    const uint32_t n_real = fsn != REJECT ? cnt : 0u;
+    const uint32_t n_real = fsn != FILTER_REJECT ? cnt : 0u;
     uint32_t k = 0;
     for (uint32_t m = 0; m < loop1 + n_real; ++m) {
       const bool is_loop = m < loop1;
-      ArcReg aa = is_loop ? (mi ? ArcReg{NO_LABEL, 0u, 0.0f, x.sa} : ArcReg{0u, NO_LABEL, 0.0f, x.sa}) : load_arc(x.se_arcs + lo + (m - loop1));
+      ArcReg aa = is_loop ? eps_loop(mi, x.sa) : load_arc(x.se_arcs + lo + (m - loop1));
       if (by_sigma) {  // value_openfst, sigma_matcher.rs:246-266
         if (se.rewrite_both) {
           if (aa.il == se.sigma) aa.il = label;
@@ -219,20 +215,6 @@ struct SigmaPolicy {
   }
 };
 
-// ComposeFstOp::match_type (compose_fst_op.rs:181-196) with SortedMatcher::match_type (sorted_matcher.rs:56-85), from the
-// property bits only: compose.hip's decide_match_mode, restated
-uint32_t sigma_match_mode(uint64_t p1, uint64_t p2) {
-  using namespace props;
-  const bool o_sorted = p1 & O_LABEL_SORTED, o_known = p1 & (O_LABEL_SORTED | NOT_O_LABEL_SORTED);
-  const bool i_sorted = p2 & I_LABEL_SORTED, i_known = p2 & (I_LABEL_SORTED | NOT_I_LABEL_SORTED);
-  if (o_sorted && i_sorted) return MODE_BOTH;
-  if (o_sorted) return MODE_OUTPUT;
-  if (i_sorted) return MODE_INPUT;
-  if (!o_known) throw Error("ComposeFst: 1st argument: label-sortedness properties are not known (sort?)");
-  if (!i_known) throw Error("ComposeFst: 2nd argument: label-sortedness properties are not known (sort?)");
-  throw Error("ComposeFst: 1st argument cannot match on output labels and 2nd argument cannot match on input labels (sort?).");
-}
-
 }  // namespace
 
 // the set-up errors of compose_with_config with matcher configs, in the reference's order, and the match mode they leave:
@@ -254,7 +236,7 @@ uint32_t sigma_setup_mode(const wfst_fst* f1, const wfst_fst* f2, uint32_t filte
     if (!(f2->props & (I_LABEL_SORTED | NOT_I_LABEL_SORTED))) throw Error("ComposeFst: 2nd argument: label-sortedness properties are not known (sort?)");
     if (!(f2->props & I_LABEL_SORTED)) throw Error("ComposeFst: 2nd argument cannot perform required matching (sort?)");
   }
-  return sigma_match_mode(f1->props, f2->props);
+  return decide_match_mode(f1->props, f2->props);
 }
 
 wfst_fst* compose_sigma(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter, const SigmaSpec* m1,

@@ -31,7 +31,6 @@
 namespace wfst {
 namespace {
 
-constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
 constexpr uint32_t SSB_MAXS = 2048;  // states of an acceptor, and composed states of an item, at most (compose.hip: STR_MAXS)
 constexpr uint32_t SSB_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SSB_LDS_BYTES = 64u << 10;  // per workgroup
@@ -64,11 +63,6 @@ struct SsbResult {
   uint32_t exact_items, sigma_items, sigma_arcs, refused_items, max_level_width;
   uint32_t pad;
 };
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src); }
-__device__ __forceinline__ float rlf(float v, uint32_t src) { return __uint_as_float(rl(__float_as_uint(v), src)); }
-// what one lane wrote to LDS is read by other lanes of the same wave behind this (the waves of a workgroup never meet)
-__device__ __forceinline__ void lds_handoff() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // is_match_label_allowed (sigma_matcher.rs:172-181) by the whole wave: each round the lanes probe 64 evenly spaced entries
 // of [lo, hi) and the range shrinks to the stride that holds `label`; the last round compares 64 neighbours
@@ -266,11 +260,7 @@ __global__ void __launch_bounds__(512) string_sigma_sp_kernel(const SsbDesc* __r
       }
     }
   }
-  for (int o = 32; o >= 1; o >>= 1) {  // the smallest (total, state id)
-    const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), o) << 32) |
-                                     (uint32_t)__shfl_xor((int)(uint32_t)best, o);
-    best = other < best ? other : best;
-  }
+  best = wave_min_u64(best);  // the smallest (total, state id)
   if (best != SSB_KEY_INF) {
     const uint32_t fp = (uint32_t)best;
     res.has_path = 1;

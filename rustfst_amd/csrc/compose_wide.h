@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <string>
 
-#include "common.h"
+#include "compose_match.h"
 
 namespace wfst {
 namespace {
@@ -40,49 +40,7 @@ struct Emitted {  // a composed arc and its destination tuple
   uint64_t lo, hi;
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, uint32_t* total) {
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  *total = __shfl(x, 63);
-  return x - v;
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
-  return ((uint64_t)(uint32_t)__shfl((uint32_t)(v >> 32), src) << 32) | (uint32_t)__shfl((uint32_t)v, src);
-}
-template <class T>
-__device__ __forceinline__ T ld_l2(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <class T>
-__device__ __forceinline__ void st_l2(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t hash_128(uint64_t lo, uint64_t hi) {
-  uint64_t h = lo ^ (hi * 0x9E3779B97F4A7C15ull);
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return (uint32_t)h;
-}
-struct ArcReg {
-  uint32_t il, ol;
-  float w;
-  uint32_t ns;
-};
-__device__ __forceinline__ ArcReg load_arc(const wfst_tr* p) {
-  const uint4 v = *reinterpret_cast<const uint4*>(p);
-  return ArcReg{v.x, v.y, __uint_as_float(v.z), v.w};
-}
+__device__ __forceinline__ uint32_t hash_128(uint64_t lo, uint64_t hi) { return (uint32_t)mix64(lo ^ (hi * GOLDEN64)); }
 
 // ---------------------------------------------------------------- wide path: G lanes per composed state of a level
 struct WideArena {

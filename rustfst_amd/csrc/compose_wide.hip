@@ -8,16 +8,11 @@
 // SortedMatcher + EpsLoop (matchers/sorted_matcher.rs:124-184, matchers/mod.rs:98-105), the six filters as per-state
 // outcome classes, ComposeFstOp::{compute_trs, compute_final_weight} (compose_fst_op.rs:406-449), first-touch state ids,
 // connect + del_states (connect.rs:51-66, vector_fst/mutable_fst.rs:132-189).
-#include "compose_filters.h"
 #include "compose_wide.h"
 #include "fst_props.h"
 
 namespace wfst {
 namespace {
-
-constexpr uint32_t NO_LABEL = WFST_NO_LABEL;
-constexpr uint32_t REJECT = 0xFFFFFFFFu;
-enum : uint32_t { MODE_BOTH = 0, MODE_INPUT = 1, MODE_OUTPUT = 2 };
 
 struct PlainView {
   const wfst_tr* arcs;
@@ -32,24 +27,6 @@ struct PlainExpand {
   uint32_t fs_nolabel, fs_eps, fsZ, fsM;  // filter_tr outcomes of the four pair classes (see compose.hip expand_state)
   float final_weight;
 };
-
-__device__ void plain_equal_range(const wfst_tr* arcs, uint32_t n, bool by_ilabel, uint32_t key, uint32_t* lo_out, uint32_t* cnt_out) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k < key) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k <= key) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = first;
-  *cnt_out = lo - first;
-}
 
 struct PlainPolicy {
   PlainView f1, f2;
@@ -67,13 +44,8 @@ struct PlainPolicy {
     const bool noeps1 = (r1.w & SREC_NO_OEPS) != 0;
     const bool alleps2 = (r2.w & SREC_ALL_IEPS) && !(fin2 != INF);
     const bool noeps2 = (r2.w & SREC_NO_IEPS) != 0;
-    x.mi = mode == MODE_BOTH ? (n1 <= n2) : (mode == MODE_INPUT);  // match_input :199-219
-    x.it_arcs = x.mi ? f1.arcs + r1.x : f2.arcs + r2.x;
-    x.se_arcs = x.mi ? f2.arcs + r2.x : f1.arcs + r1.x;
-    x.n_it = x.mi ? n1 : n2;
-    x.n_se = x.mi ? n2 : n1;
-    x.sa = x.mi ? s2 : s1;
-    x.sb = x.mi ? s1 : s2;
+    // match_input :199-219
+    select_sides(x, mode == MODE_BOTH ? (n1 <= n2) : (mode == MODE_INPUT), f1.arcs + r1.x, n1, s1, f2.arcs + r2.x, n2, s2);
     const FilterOutcomes fo = filter_outcomes(filter, fs, alleps1, noeps1, alleps2, noeps2);  // compose_filters.h
     const uint32_t fsX = fo.fsX, fsY = fo.fsY, fsZ = fo.fsZ;
     x.fs_nolabel = x.mi ? fsX : fsY;  // the loop pseudo-arc of the iterated side against the searched side's epsilon arcs
@@ -88,24 +60,24 @@ struct PlainPolicy {
   __device__ uint32_t eval_item(const Expand& x, uint32_t j, bool write, uint32_t write_pos, wfst_tr* arcs, uint64_t* a_lo,
                                 uint64_t* a_hi, Emitted* first) const {
     const bool mi = x.mi;
-    const ArcReg ab = j == 0 ? (mi ? ArcReg{0u, NO_LABEL, 0.0f, x.sb} : ArcReg{NO_LABEL, 0u, 0.0f, x.sb}) : load_arc(x.it_arcs + (j - 1));
+    const ArcReg ab = j == 0 ? loop_item(mi, x.sb) : load_arc(x.it_arcs + (j - 1));
     const uint32_t label = mi ? ab.ol : ab.il;
     uint32_t lo = 0, cnt = 0;
-    plain_equal_range(x.se_arcs, x.n_se, mi, label == NO_LABEL ? 0u : label, &lo, &cnt);
+    equal_range(x.se_arcs, x.n_se, mi, label == NO_LABEL ? 0u : label, &lo, &cnt);
     uint32_t loop1 = 0, fsn;
     if (label == NO_LABEL) {
       fsn = x.fs_nolabel;
     } else if (label == 0u) {
-      loop1 = x.fs_eps != REJECT ? 1u : 0u;
+      loop1 = x.fs_eps != FILTER_REJECT ? 1u : 0u;
       fsn = x.fsZ;
     } else {
       fsn = x.fsM;
     }
-    const uint32_t n_real = fsn != REJECT ? cnt : 0u;
+    const uint32_t n_real = fsn != FILTER_REJECT ? cnt : 0u;
     uint32_t k = 0;
     for (uint32_t m = 0; m < loop1 + n_real; ++m) {
       const bool is_loop = m < loop1;
-      const ArcReg aa = is_loop ? (mi ? ArcReg{NO_LABEL, 0u, 0.0f, x.sa} : ArcReg{0u, NO_LABEL, 0.0f, x.sa}) : load_arc(x.se_arcs + lo + (m - loop1));
+      const ArcReg aa = is_loop ? eps_loop(mi, x.sa) : load_arc(x.se_arcs + lo + (m - loop1));
       const ArcReg a1 = mi ? ab : aa;  // arc1 from fst1, arc2 from fst2 (match_tr_selected :301-319)
       const ArcReg a2 = mi ? aa : ab;
       const uint4 arc = make_uint4(a1.il, a2.ol, __float_as_uint(wtimes(a1.w, a2.w)), 0u);  // add_tr :267-285

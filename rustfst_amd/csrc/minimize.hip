@@ -271,7 +271,7 @@ __global__ void core_advance_kernel(Core c) { core_advance(c); }
 
 __device__ inline uint32_t label_key(const Core& c, const wfst_tr& a) { return c.by_olabel ? a.olabel : a.ilabel; }
 __device__ inline uint64_t entry_hash(const Core& c, const wfst_tr& a, uint32_t j) {
-  return mix64((((uint64_t)label_key(c, a) << 32) | ld(&c.cls[a.nextstate])) + (uint64_t)(j + 1) * 0x9E3779B97F4A7C15ull);
+  return mix64((((uint64_t)label_key(c, a) << 32) | ld(&c.cls[a.nextstate])) + (uint64_t)(j + 1) * GOLDEN64);
 }
 __device__ inline uint64_t head_hash(uint32_t fk, uint32_t deg) { return mix64(((uint64_t)fk << 32) | deg); }
 __device__ inline bool entry_equal(const Core& c, const wfst_tr& x, const wfst_tr& y) {

@@ -6,30 +6,11 @@
 #pragma once
 #include <algorithm>
 
-#include "common.h"
+#include "compose_match.h"
 #include "fst_props.h"
 
 namespace wfst {
 namespace {
-
-// the run of `key` on the matched tape of a sorted arc block: two binary searches
-__device__ void sg_equal_range(const wfst_tr* arcs, uint32_t n, bool by_ilabel, uint32_t key, uint32_t* lo_out, uint32_t* cnt_out) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k < key) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint32_t k = by_ilabel ? arcs[mid].ilabel : arcs[mid].olabel;
-    if (k <= key) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = first;
-  *cnt_out = lo - first;
-}
 
 // sig[s] = {first sigma arc within the state's arcs, how many}: one thread per state
 __global__ void __launch_bounds__(256) sigma_ranges(const wfst_tr* __restrict__ arcs, const uint4* __restrict__ srec, uint32_t n_states,
@@ -38,7 +19,7 @@ __global__ void __launch_bounds__(256) sigma_ranges(const wfst_tr* __restrict__ 
   if (s >= n_states) return;
   const uint4 r = srec[s];
   uint32_t lo = 0, cnt = 0;
-  sg_equal_range(arcs + r.x, r.y, by_ilabel, sigma, &lo, &cnt);
+  equal_range(arcs + r.x, r.y, by_ilabel, sigma, &lo, &cnt);
   sig[s] = make_uint2(lo, cnt);
 }
 
