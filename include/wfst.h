@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -888,6 +888,25 @@ wfst_status wfst_ctx_get_string_run_stats(wfst_ctx* ctx, uint64_t* run_levels, u
  *        pair_splits  those of them with two matches.
  *      Either pointer after ctx may be NULL.  KO: NULL ctx. ---- */
 wfst_status wfst_ctx_get_string_pair_counts(wfst_ctx* ctx, uint64_t* pair_levels, uint64_t* pair_splits);
+
+/* ---- where the waves of the last string launch of ctx sat: string_compose_sp_kernel in a
+ *      wfst_compose_shortest_path_batch[_begin/_end/_packed] call, string_sigma_sp_kernel in a
+ *      wfst_compose_shortest_path_batch_with_matchers call with a matcher config.  One wave answers one string from its own
+ *      slice of the workgroup's LDS; how many waves share a workgroup changes no result and no other counter, only which
+ *      compute units work.  With cap = 64 KB / (16 * slice_states) = 8, 4 or 2: WFST_STRING_WPB=1|2|4|8 (other numbers: the
+ *      next lower power of two; 0 and non-numbers are ignored) gives min(that, cap); WFST_STRING_UNPACKED gives 1 and the 2048-state slice, in either kernel; fewer
+ *      than 16 strings give 1; while the last large-FST shortest-path solve that finished on the device in this process ran its
+ *      levels in a resident launch, cap (such a launch needs nearly every compute unit whole); otherwise the least of 1, 2,
+ *      4, 8 and cap that gives every workgroup a compute unit of the context (those of its mask) to itself.  Either call
+ *      resets them when it begins.
+ *        waves_per_workgroup  of that launch (0: the call made none),
+ *        slice_states         composed states a wave's LDS slice holds: 512, 1024 or 2048,
+ *        workgroups           of that launch,
+ *        packed_for_resident  1: the resident launch decided, 0: not,
+ *        forced               1: WFST_STRING_WPB or WFST_STRING_UNPACKED decided, 0: not.
+ *      Any pointer after ctx may be NULL.  KO: NULL ctx. ---- */
+wfst_status wfst_ctx_get_string_placement(wfst_ctx* ctx, uint64_t* waves_per_workgroup, uint64_t* slice_states, uint64_t* workgroups,
+                                          uint64_t* packed_for_resident, uint64_t* forced);
 
 /* ---- which route the levels of the last wfst_determinize / wfst_determinize_with_distance call of ctx took.  The result
  *      is built breadth-first level by level, and every route returns the same FST, so only these counters show which one

@@ -318,6 +318,12 @@ struct wfst_ctx {
   struct StringPairCounts {
     uint64_t pair_levels = 0, pair_splits = 0;
   } string_pair;
+  // Where the waves of this context's last string launch sat (string_placement.h; wfst_ctx_get_string_placement, defined in
+  // compose.hip): string_compose_sp_kernel in a fused-batch call, string_sigma_sp_kernel in one with matcher configs.
+  // packed_for_resident, forced: 0 / 1.  Zeroed where string_run is, and where sigma_batch is.
+  struct StringPlacementCounts {
+    uint64_t waves_per_workgroup = 0, slice_states = 0, workgroups = 0, packed_for_resident = 0, forced = 0;
+  } string_placement;
   // The last wfst_rm_epsilon call; zeroed when rm_epsilon.hip's driver begins.
   struct RmEpsilonStats {
     uint64_t batches = 0, thread_launches = 0, wave_launches = 0, states_thread = 0, states_wave = 0, max_closure_cap = 0;
@@ -575,6 +581,8 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f);
 wfst_fst* shortest_path_n1_end(wfst_sp_job* job);
 void shortest_path_n1_abandon(wfst_sp_job* job);
 wfst_ctx* sp_job_ctx(wfst_sp_job* job);
+// the last solve that finished on `device` in this process ran WIDE levels in a resident launch (never solved: false)
+bool resident_grid_at_work(int device);
 void shortest_distance(wfst_ctx* ctx, const wfst_fst* f, float* distance, uint32_t* hops);
 void shortest_distance_device(wfst_ctx* ctx, const wfst_fst* f, float* d_distance);
 // nshortest.hip

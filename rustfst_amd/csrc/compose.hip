@@ -31,6 +31,7 @@
 #include "compose_match.h"
 #include "fst_props.h"
 #include "host_parallel.h"
+#include "string_placement.h"
 
 namespace wfst {
 
@@ -101,6 +102,7 @@ struct Result {
                       // the problem (system-scope fence in between): the host waits for these words instead of the stream
 #ifdef WFST_PHASE_TIMING
   unsigned long long dbg[8];
+  uint32_t hw_id, xcc_id;  // where the wave ran: HW_REG_HW_ID (wave 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13) and HW_REG_XCC_ID (3:0)
 #endif
 };
 
@@ -184,8 +186,11 @@ __device__ __forceinline__ uint32_t ht_insert(uint64_t* hkeys, uint32_t* hvals, 
     pt_acc[k] += pt_n - pt_t;                   \
     pt_t = pt_n;                                \
   }
-#define PT_STORE(res) \
-  for (int pt_i = 0; pt_i < 8; ++pt_i) (res).dbg[pt_i] = pt_acc[pt_i];
+// (s_getreg's operand: register id | first bit << 6 | (bits - 1) << 11; HW_REG_HW_ID is 4, HW_REG_XCC_ID 20)
+#define PT_STORE(res)                                                          \
+  for (int pt_i = 0; pt_i < 8; ++pt_i) (res).dbg[pt_i] = pt_acc[pt_i];        \
+  (res).hw_id = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));          \
+  (res).xcc_id = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
 // (string_compose_sp_kernel: the rows asked for so far have arrived.  The wait is part of the timing build only: it ends the
 // overlap the real kernel has, so such a build gives the SHARES of a level, not its length)
 #define PT_ROWS_IN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -902,10 +907,13 @@ constexpr uint32_t STR_MAXS = 2048;
 constexpr uint32_t STR_NONE = 0xFFFFFFFFu;
 
 // One wave = one problem; a workgroup holds blockDim.x / 64 of them, each with its own `maxs`-state slice of the dynamic
-// LDS (the waves never meet: no workgroup barrier anywhere).  Why several waves per workgroup: a resident wave of this
-// kernel blocks its whole CU for the 1024-thread, 128-VGPR workgroups of the mailbox relaxation sweeps (they need every
-// register of all four SIMDs), so 64 lone waves on 64 CUs sent a quarter of every concurrent sweep into a second round;
-// 8 workgroups of 8 waves land on one CU per XCD and leave 31 CUs per XCD to the sweeps' 30-31 workgroups per XCD.
+// LDS (the waves never meet: no workgroup barrier anywhere).  How many waves share a workgroup is the host's choice
+// (string_placement.h) and changes nothing but where they sit.  Spread — a workgroup per compute unit, a wave per SIMD, for as
+// long as the context has them — a level's dependent load and its ~26-instruction chain wait for nobody (profiles/
+// string_placement_ab.md).  Packed — what 64 KB of LDS hold, eight waves at the 512-state slice — while a resident
+// relaxation grid is at work on the device: a resident wave of this kernel blocks its whole CU for that grid's 1024-thread,
+// 128-VGPR workgroups (they need every register of all four SIMDs), the grid needs ~245 whole CUs at once, and 8 workgroups of 8
+// waves land on one CU per XCD and leave it 31 of 32.
 __global__ void __launch_bounds__(512) string_compose_sp_kernel(const ProblemDesc* __restrict__ descs, FstView f2,
                                                                 Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
                                                                 uint32_t path_cap, uint32_t n_problems, uint32_t maxs, uint64_t f2_n_arcs,
@@ -1631,17 +1639,23 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
   if (!string_kernel) HIP_CHECK(hipMemsetAsync(run.d_cursor.p, 0, sizeof(uint32_t), st));
   if (ctx->profiling) HIP_CHECK(hipEventRecord(ctx->ev0, st));
   if (string_kernel) {
-    // waves per workgroup x states per problem: 64 KB of LDS per workgroup at most
-    uint32_t wpb = 1, maxs = STR_MAXS;
+    // states per problem, then waves per workgroup (string_placement.h): 64 KB of LDS per workgroup at most
+    uint32_t maxs = STR_MAXS;
     const EnvSnap none;
     const EnvSnap& env = run.env ? *run.env : none;
-    if (!env.has("WFST_STRING_UNPACKED") && n >= 16) {
+    const bool unpacked = env.has("WFST_STRING_UNPACKED");
+    if (!unpacked && n >= STRING_PACK_MIN) {
       // a string of L arcs against an input-deterministic-ish T composes to a little more than L states; a problem that
       // outgrows its slice reports ST_NOT_A_STRING_CASE and is redone by the general kernel like any other misfit
       const uint64_t need = max_f1_states ? 2ull * max_f1_states + 64 : STR_MAXS;
       maxs = need <= 512 ? 512u : (need <= 1024 ? 1024u : STR_MAXS);
-      wpb = (64u << 10) / (16u * maxs);
     }
+    // (WFST_STRING_UNPACKED: one wave per workgroup whatever else is set; WFST_STRING_WPB=8: the packing of every batch of 16
+    // strings or more before the rule)
+    const StringPlacement pl = string_placement(n, maxs, (uint32_t)std::max(ctx->n_cus, 1), resident_grid_at_work(ctx->device),
+                                                unpacked ? 1u : string_forced_wpb(env.get("WFST_STRING_WPB")));
+    const uint32_t wpb = pl.wpb;
+    ctx->string_placement = {wpb, maxs, pl.workgroups, pl.packed_for_resident ? 1u : 0u, pl.forced ? 1u : 0u};
     // tickets for serving-size batches only: the fence in front of a ticket writes the L2 back, and thousands of waves doing
     // that made a 4096-problem batch 0.7 ms slower; a kernel of milliseconds does not care about 10 us of wake-up latency
     static std::atomic<uint32_t> tickets{0};
@@ -1652,8 +1666,9 @@ void launch_begin(wfst_ctx* ctx, const std::vector<ProblemDesc>& descs, const Fs
     }
     string_compose_sp_kernel<<<(uint32_t)((n + wpb - 1) / wpb), 64 * wpb, (size_t)wpb * 16u * maxs, st>>>(
         k_desc, f2, k_res, k_paths, path_cap, (uint32_t)n, maxs, f2.n_arcs,
-        // scalar arc-block loads where a wave is alone on its SIMD (a handful of strings): -7 % per level; with eight waves
-        // per compute unit the other waves hide the vector latency anyway and the extra scalar instructions cost 3 %
+        // scalar arc-block loads for a handful of strings: -7 % per level.  Not for a batch, even where every wave is alone on
+        // its SIMD (string_placement.h): 64 strings at one wave per workgroup take 104.3 us of batch finish with scalar rows and
+        // the run forced on them against 95.0 with vector rows (profiles/string_placement_ab.md section 7)
         env.has("WFST_STRING_SCALAR") ? (uint32_t)std::atoi(env.get("WFST_STRING_SCALAR")) : (n <= 8 ? 1u : 0u),
         // the chase run of the vector path (WFST_STRING_RUN=0: every level is the general one; 2: also on the scalar-row path:
         // a measurement setting — profiles/string_run_ab.md has its figure; launches of <= 8 strings keep their route)
@@ -1726,6 +1741,23 @@ void launch_end(wfst_ctx* ctx, BatchRun& run) {
         for (int k = 0; k < 8; ++k) sum += h_res[i].dbg[k];
         std::fprintf(stderr, "[string problem] %zu cycles %llu levels %u in_runs %u pair_levels %u\n", i, sum, h_res[i].n_levels, h_res[i].run_levels, h_res[i].pair_levels);
       }
+    {  // where the waves landed: a compute unit is (XCD, SE, SH, CU), a SIMD one of its four
+      std::map<uint32_t, uint32_t> per_cu, per_simd;
+      uint32_t xcds = 0;
+      for (size_t i = 0; i < n; ++i) {
+        const uint32_t hw = h_res[i].hw_id, xcc = h_res[i].xcc_id & 15u;
+        const uint32_t cu = (xcc << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
+        per_cu[cu] += 1;
+        per_simd[(cu << 2) | ((hw >> 4) & 3u)] += 1;
+        xcds |= 1u << xcc;
+      }
+      uint32_t max_cu = 0, max_simd = 0;
+      for (const auto& kv : per_cu) max_cu = std::max(max_cu, kv.second);
+      for (const auto& kv : per_simd) max_simd = std::max(max_simd, kv.second);
+      std::fprintf(stderr, "[string landing] %u waves per workgroup, %u workgroups: waves per CU: max %u / mean %.2f (%zu CUs); waves per SIMD: max %u / mean %.2f (%zu SIMDs); XCDs used %d\n",
+                   (unsigned)ctx->string_placement.waves_per_workgroup, (unsigned)ctx->string_placement.workgroups, max_cu, (double)n / per_cu.size(),
+                   per_cu.size(), max_simd, (double)n / per_simd.size(), per_simd.size(), __builtin_popcount(xcds));
+    }
     std::fprintf(stderr, "[string phase ticks/problem] general: rows wait %llu | under the early load %llu | arrival->issue %llu || run: rows wait %llu | arrival->issue %llu | under the load %llu || prologue %llu | epilogue %llu  (n=%zu, levels/problem %.1f, of them in runs %.1f)\n",
                  tot[0] / n, tot[1] / n, tot[2] / n, tot[4] / n, tot[5] / n, tot[3] / n, tot[6] / n, tot[7] / n, n, (double)lv / n, (double)rlv / n);
   }
@@ -1949,6 +1981,7 @@ wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst*
   ctx->compose_path = wfst_ctx::ComposePathStats{};
   ctx->string_run = {};
   ctx->string_pair = {};
+  ctx->string_placement = {};
   if (n == 0) return job.release();
   job->env = EnvSnap::take();
   job->run_s.env = &job->env;
@@ -2199,5 +2232,20 @@ extern "C" wfst_status wfst_ctx_get_string_pair_counts(wfst_ctx* ctx, uint64_t* 
     if (!ctx) throw wfst::Error("null pointer");
     if (pair_levels) *pair_levels = ctx->string_pair.pair_levels;
     if (pair_splits) *pair_splits = ctx->string_pair.pair_splits;
+  });
+}
+
+// Where the waves of ctx's last string launch sat (common.h: wfst_ctx::string_placement), beside launch_begin, which decides
+// it.  Any out-pointer may be null.
+extern "C" wfst_status wfst_ctx_get_string_placement(wfst_ctx* ctx, uint64_t* waves_per_workgroup, uint64_t* slice_states,
+                                                     uint64_t* workgroups, uint64_t* packed_for_resident, uint64_t* forced) {
+  return wfst::wrap([&] {
+    if (!ctx) throw wfst::Error("null pointer");
+    const wfst_ctx::StringPlacementCounts& c = ctx->string_placement;
+    if (waves_per_workgroup) *waves_per_workgroup = c.waves_per_workgroup;
+    if (slice_states) *slice_states = c.slice_states;
+    if (workgroups) *workgroups = c.workgroups;
+    if (packed_for_resident) *packed_for_resident = c.packed_for_resident;
+    if (forced) *forced = c.forced;
   });
 }

@@ -27,13 +27,14 @@
 // input epsilons or not known sorted, a non-linear acceptor, wfst_ctx_set_tie_order — never reaches the kernel: those
 // items go one by one through compose_sigma + shortest_path_n1 on the same context, in item order.
 #include "sigma_ranges.h"
+#include "string_placement.h"
 
 namespace wfst {
 namespace {
 
 constexpr uint32_t SSB_MAXS = 2048;  // states of an acceptor, and composed states of an item, at most (compose.hip: STR_MAXS)
 constexpr uint32_t SSB_NONE = 0xFFFFFFFFu;
-constexpr uint32_t SSB_LDS_BYTES = 64u << 10;  // per workgroup
+static_assert(SSB_MAXS * 16u * 2u <= STRING_LDS_BYTES, "string_placement.h: two of the largest slices per workgroup");
 constexpr unsigned long long SSB_KEY_INF = ~0ull;
 enum : uint32_t { SSB_OK = 0, SSB_NOT_A_STRING_CASE = 1, SSB_BAD_LABEL = 2 };
 
@@ -295,9 +296,11 @@ void compose_sigma_sp_batch(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n
                             const SigmaSpec* m1, const SigmaSpec* m2, wfst_fst** outs, uint64_t* composed_arcs) {
   using namespace props;
   ctx->sigma_batch = wfst_ctx::SigmaBatchCounters{};
+  ctx->string_placement = {};
   wfst_ctx::SigmaBatchCounters& cnt = ctx->sigma_batch;
   if (composed_arcs) *composed_arcs = 0;
   if (n == 0) return;
+  const EnvSnap env = EnvSnap::take();  // the WFST_* variables as the call found them
   // the set-up errors of every item, in item order, before anything is launched
   std::vector<uint32_t> mode(n);
   for (size_t i = 0; i < n; ++i) {
@@ -363,12 +366,15 @@ void compose_sigma_sp_batch(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n
       const SsbGrammar g{t->dev.arcs, t->dev.srec, anext, tabs.sig.p, tabs.allowed.p, tabs.n_allowed, tabs.sigma, tabs.rewrite_both,
                          (uint32_t)t->start};
       // states per slice: a string of L arcs against an input-deterministic-ish T composes to a little more than L states; an
-      // item that outgrows its slice is handed back.  Waves per workgroup: what 64 KB of LDS hold
+      // item that outgrows its slice is handed back.  Waves per workgroup: string_placement.h
+      // (WFST_STRING_UNPACKED, as in compose.hip: one wave per workgroup and the largest slice, whatever WFST_STRING_WPB says)
+      const bool unpacked = env.has("WFST_STRING_UNPACKED");
       const uint64_t need = 2ull * max_states + 64;
-      const uint32_t maxs = need <= 512 ? 512u : (need <= 1024 ? 1024u : SSB_MAXS);
-      const uint32_t wpb = (uint32_t)std::min<size_t>(SSB_LDS_BYTES / (16u * maxs), k);
-      string_sigma_sp_kernel<<<(uint32_t)((k + wpb - 1) / wpb), 64 * wpb, (size_t)wpb * 16u * maxs, st>>>(d_desc.p, g, d_res.p, d_path.p,
-                                                                                                            (uint32_t)k, maxs);
+      const uint32_t maxs = unpacked ? SSB_MAXS : (need <= 512 ? 512u : (need <= 1024 ? 1024u : SSB_MAXS));
+      const StringPlacement pl = string_placement(k, maxs, (uint32_t)std::max(ctx->n_cus, 1), resident_grid_at_work(ctx->device),
+                                                  unpacked ? 1u : string_forced_wpb(env.get("WFST_STRING_WPB")));
+      ctx->string_placement = {pl.wpb, maxs, pl.workgroups, pl.packed_for_resident ? 1u : 0u, pl.forced ? 1u : 0u};
+      string_sigma_sp_kernel<<<pl.workgroups, 64 * pl.wpb, (size_t)pl.wpb * 16u * maxs, st>>>(d_desc.p, g, d_res.p, d_path.p, (uint32_t)k, maxs);
       HIP_CHECK(hipGetLastError());
       cnt.launches += 1;
       HIP_CHECK(hipMemcpyAsync(pin + off_res, d_res.p, k * sizeof(SsbResult), hipMemcpyDeviceToHost, st));

@@ -1303,7 +1303,16 @@ struct ResidentLease {
   ~ResidentLease() { release(); }
 };
 
+// Beside the lease's counter, per device and process: did the last solve that finished on the device run WIDE levels in a
+// resident launch?  record_solve writes it, the string kernels' placement reads it (string_placement.h): a grid of ~245
+// whole compute units is then likely at work beside the next batch.  A process that has never solved reads "no".
+std::atomic<uint8_t>& resident_work_of(int device) {
+  static std::atomic<uint8_t> w[64];
+  return w[(unsigned)device & 63u];
+}
+
 }  // namespace
+bool resident_grid_at_work(int device) { return resident_work_of(device).load(std::memory_order_relaxed) != 0; }
 }  // namespace wfst
 bool wfst_ctx::resident_allowed() const {
   if (resident_hold) return false;
@@ -2260,6 +2269,8 @@ void record_solve(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, uint32_t sweeps, 
   if (!bounded) note_sweeps(f, sweeps);
   if (bounded) f->bounded_streak.fetch_add(1, std::memory_order_relaxed);
   else if (sv.bounded_on) f->bounded_streak.store(0, std::memory_order_relaxed);
+  // (a head that stopped leaves its resident launch at entry; a solve of one launch per level never holds whole compute units)
+  resident_work_of(ctx->device).store(sv.resident && !bounded ? 1 : 0, std::memory_order_relaxed);
   if (sv.mbox) dump_trace(ctx, sv.kn.mbox_trace, sv.mb_dbg.p, MB_DBG_SWEEPS, sv.mv.nb, 16);
   if (sv.resident) dump_trace(ctx, sv.kn.res_trace, sv.rs_trace.p, RS_TRACE_LEVELS, sv.mv.nb, 4);
 }

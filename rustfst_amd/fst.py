@@ -133,6 +133,18 @@ class Context:
               "wfst_ctx_get_string_pair_counts")
         return {k: int(v.value) for k, v in zip(_lib.STRING_PAIR_COUNTS, vals)}
 
+    def string_placement(self) -> dict:
+        """Where the waves of this context's last string launch sat (wfst_ctx_get_string_placement): waves per workgroup
+        (waves_per_workgroup), composed states a wave's LDS slice holds (slice_states), workgroups of the launch
+        (workgroups), whether a resident relaxation launch on the device made the launch pack its waves
+        (packed_for_resident) and whether WFST_STRING_WPB or WFST_STRING_UNPACKED decided (forced).  All 0 when the last
+        compose_shortest_path_batch call launched no string kernel, and with a library from before the counters."""
+        if not hasattr(_lib.lib(), "wfst_ctx_get_string_placement"):  # (WFST_LIB_PATH: a build from before the counters)
+            return dict.fromkeys(_lib.STRING_PLACEMENT, 0)
+        vals = [C.c_uint64() for _ in _lib.STRING_PLACEMENT]
+        check(_lib.lib().wfst_ctx_get_string_placement(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_string_placement")
+        return {k: int(v.value) for k, v in zip(_lib.STRING_PLACEMENT, vals)}
+
     def determinize_stats(self) -> dict:
         """Which route the levels of this context's last determinize / determinize_with_distance call took
         (wfst_ctx_get_determinize_stats): levels completed (levels) and those the device-wide launches ran (wide_levels),
