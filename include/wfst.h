@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -564,6 +564,38 @@ wfst_status wfst_top_sort(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out);
 wfst_status wfst_ctx_get_top_sort_stats(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
                                         uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* max_tree_depth,
                                         uint64_t* lift_rows, uint64_t* states_compared, uint64_t* wave_states, uint64_t* cyclic);
+
+/* ---- top_sort of n FSTs in one call: outs[i] is a NEW handle, bit-identical (offsets, arcs with their weights' bit
+ *      patterns, finals, start state, property word) to what wfst_top_sort(ctx, fsts[i], ..) returns: an acyclic item in
+ *      the reference's depth-first order, an item with a cycle anywhere as a copy with CYCLIC | NOT_TOP_SORTED set (not an
+ *      error), an item without states and without a start state as the empty FST with the three acyclic bits.  The same
+ *      handle may appear more than once in fsts.  n == 0: OK.  The inputs are left exactly as they are, their cached
+ *      derived data and property words included.
+ *      One workgroup per item and ONE launch for the whole list, whatever its length and the items' depths: the
+ *      workgroup stages the item's nextstate column and offsets in LDS as 16-bit words, ONE lane runs the reference's
+ *      sequential search on them (explicit stack, white / grey / black, the first grey target ends it; a step bound of
+ *      2 * states + arcs + 2 makes a search that does not end impossible), and all lanes apply the order as state_sort
+ *      does (row lengths and finals scattered, a workgroup scan, arcs copied as 16-byte words with nextstate renamed) into
+ *      the item's slice of one slab.  The slices are sized on the host from n_states and n_arcs alone, so nothing is run
+ *      twice: one launch, one read-back of the items' control blocks, one adoption of all results out of the slab.  A
+ *      slice takes 16 bytes per arc and 12 per state; the slices of one call may take 8 GiB together: a list that needs
+ *      more is KO before anything is launched ("split the list").  The launch asks for the LDS of its largest item, at
+ *      most 58 KB.
+ *      in_kernel (uint8_t[n], may be NULL): in_kernel[i] == 1 exactly when item i has a start state, at most 4096 states
+ *      and at most 16384 arcs, or has neither states nor a start state (such an item occupies no workgroup).
+ *      in_kernel[i] == 0: the item went through wfst_top_sort unchanged — anything larger, which gives the same FST, and
+ *      an item with states but no start state, which is that call's KO.  wfst_ctx_get_top_sort_stats keeps describing
+ *      the last single call, one made for such an item included.
+ *      KO — every argument is checked before anything is launched: NULL pointers, NULL list entries ("item <i>: null FST
+ *      in batch"), a handle of another device or context ("item <i>: top_sort_batch: the FST belongs to another context").
+ *      An item with states but no start state: "item <i>: StateSort : Bad order vector size : 0. Expected {n_states}", the
+ *      lowest such i, as a loop of single calls would stop.  On any KO every outs[i] is NULL, nothing is leaked and the
+ *      context works afterwards. ---- */
+wfst_status wfst_top_sort_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_top_sort_batch call of ctx: launches of the batch kernel (0 when no item occupied a workgroup, else 1),
+ *      items with in_kernel == 1, items that went through the single-FST path.  All 0 after a KO before any launch.  Any
+ *      pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_top_sort_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single);
 
 /* ---- rm_epsilon: fst_rm_epsilon (rustfst-ffi/src/algorithms/rm_epsilon.rs) = rustfst::algorithms::rm_epsilon
  *      (rustfst/src/algorithms/rm_epsilon/rm_epsilon_static.rs:50-163) with its default configuration (connect, no

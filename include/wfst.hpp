@@ -20,7 +20,7 @@
 //   determinize_with_distance(&fst, &in_dist, delta)             determinize_with_distance(fst, in_dist, delta)   determinize_static.rs:24-39
 //   (many acceptors in one call)                                 determinize_batch / determinize_with_distance_batch
 //                                                                minimize_batch, rm_epsilon_batch, tr_sum_batch,
-//                                                                tr_unique_batch, optimize_batch
+//                                                                tr_unique_batch, optimize_batch, top_sort_batch
 //   minimize(&mut fst) / minimize_with_config(&mut fst, config)  minimize(fst) / minimize_with_config(fst, config)  minimize.rs:77-176
 //   tr_sum(&mut fst) / tr_unique(&mut fst)                       tr_sum(fst) / tr_unique(fst)                      tr_sum.rs, tr_unique.rs
 //   optimize(&mut fst)                                           optimize(fst)                                     optimize.rs:11-128
@@ -498,6 +498,8 @@ inline std::vector<VectorFst> batch_call(const std::vector<VectorFst>& fsts, Cal
 inline std::vector<VectorFst> tr_sum_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_tr_sum_batch); }
 inline std::vector<VectorFst> tr_unique_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_tr_unique_batch); }
 inline std::vector<VectorFst> optimize_batch(const std::vector<VectorFst>& fsts) { return detail::batch_call(fsts, wfst_optimize_batch); }
+// top_sort of many FSTs in one call (wfst_top_sort_batch): in place like top_sort, every fsts[i] replaced by its result
+inline void top_sort_batch(std::vector<VectorFst>& fsts) { fsts = detail::batch_call(fsts, wfst_top_sort_batch); }
 
 // union (union/union_static.rs:55-118), concat (concat/concat_static.rs:53-109) and closure (closure/closure_static.rs:25-73):
 // the first operand is changed in place, like the reference (`union` is a C++ keyword, hence union_).  Results are in general

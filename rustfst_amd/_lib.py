@@ -95,6 +95,10 @@ COUNTERS = {
                   "states_compared", "wave_states", "cyclic")),
 }
 
+# wfst_ctx_get_top_sort_batch_counters: the uint64_t* parameters behind ctx, in order: a one-workgroup-per-item batch family
+# like the *_batch entries above, its getter outside the table of the *_stats families
+TOP_SORT_BATCH_COUNTERS = _BATCH
+
 # wfst_ctx_get_compose_sigma_counters: the uint64_t* parameters behind ctx, in order (outside the table of the *_stats families)
 COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "require2_states", "exact_items", "sigma_items",
                           "sigma_arcs", "refused_items", "arena_grows", "level_launches")
@@ -115,6 +119,7 @@ _P = C.POINTER
 SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names in COUNTERS.values()] + [
     ("wfst_ctx_get_compose_sigma_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_SIGMA_COUNTERS)),
     ("wfst_ctx_get_sigma_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(SIGMA_BATCH_COUNTERS)),
+    ("wfst_ctx_get_top_sort_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(TOP_SORT_BATCH_COUNTERS)),
     ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_ctx_get_string_placement", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PLACEMENT)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
@@ -187,6 +192,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_rational_check_sizes", C.c_int, [_u32, _vp, _vp, _sz]),
     ("wfst_state_sort", C.c_int, [_vp, _vp, _vp, _sz, _P(_vp)]),
     ("wfst_top_sort", C.c_int, [_vp, _vp, _P(_vp)]),
+    ("wfst_top_sort_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _vp]),
     ("wfst_compose_shortest_path_batch", C.c_int,
      [_vp, _P(_vp), _sz, _vp, _P(ComposeConfig), _P(ShortestPathConfig), _P(_vp), _P(_u64)]),
     ("wfst_compose_shortest_path_batch_with_matchers", C.c_int,

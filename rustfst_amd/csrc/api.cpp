@@ -851,6 +851,17 @@ wfst_status wfst_ctx_get_top_sort_stats(wfst_ctx* ctx, uint64_t* levels, uint64_
   return get_counters(ctx, &wfst_ctx::top_sort, {levels, narrow_launches, wide_launches, narrow_levels, max_level_width,
                                                  max_tree_depth, lift_rows, states_compared, wave_states, cyclic});
 }
+// top_sort of n FSTs (one workgroup each, one launch); every argument is checked before anything is launched
+wfst_status wfst_top_sort_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    null_outs(outs, n);
+    if (!begin_batch_call(ctx, fsts, n, outs, &wfst_ctx::top_sort_batch)) return;
+    top_sort_batch(ctx, fsts, n, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_top_sort_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single) {
+  return get_counters(ctx, &wfst_ctx::top_sort_batch, {launches, items_in_kernel, items_single});
+}
 
 wfst_status wfst_reverse(wfst_ctx* ctx, const wfst_fst* fst, wfst_fst** out) {
   return wrap([&] {

@@ -260,9 +260,9 @@ struct wfst_ctx {
   wfst::PinnedBuf pinned_flags;  // host mirror of the per-sweep activity flags: [0] first batch of a solve, [1] batches of 8 sweeps, [2] of 64
   std::shared_ptr<wfst::PinnedRing> pinned_ring = std::make_shared<wfst::PinnedRing>();  // result blocks of the fused batches
   // ---- route counters (the rules: wfst::BatchStats above).  The last wfst_determinize_batch / wfst_determinize_with_distance_batch,
-  // wfst_minimize_batch, wfst_rm_epsilon_batch, wfst_tr_sum_batch / wfst_tr_unique_batch and wfst_optimize_batch call
-  // (batch_driver.h counts)
-  wfst::BatchStats det_batch, min_batch, rm_batch, trsum_batch;
+  // wfst_minimize_batch, wfst_rm_epsilon_batch, wfst_tr_sum_batch / wfst_tr_unique_batch, wfst_top_sort_batch and
+  // wfst_optimize_batch call (batch_driver.h counts)
+  wfst::BatchStats det_batch, min_batch, rm_batch, trsum_batch, top_sort_batch;
   wfst::OptimizeBatchStats opt_batch;
   // Which route the levels of the last wfst_determinize / wfst_determinize_with_distance call took: tallied on the host from
   // the control block determinize.hip already reads back.  Zeroed when determinize.hip's driver begins.
@@ -680,6 +680,8 @@ void rational_check_sizes(uint32_t op, const uint64_t* n_states, const uint64_t*
 // top_sort.hip: state_sort by an order given on the host and top_sort in the reference's DFS order (NEW handles)
 wfst_fst* state_sort_fst(wfst_ctx* ctx, const wfst_fst* f, const uint32_t* order, size_t n_order);
 wfst_fst* top_sort_fst(wfst_ctx* ctx, const wfst_fst* f);
+// ... of n FSTs in one call, one workgroup each and one launch for all (new handles; on a throw every outs[i] is null)
+void top_sort_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel);
 // optimize.hip: optimize of an acyclic FST, acceptor or transducer (a NEW handle)
 wfst_fst* optimize_fst(wfst_ctx* ctx, const wfst_fst* f);
 // ... of n FSTs in one call over the four batch stages (new handles; on a throw every outs[i] is null)

@@ -31,14 +31,20 @@
 // WFST_TOP_SORT_PATH=narrow|wide pins one.  Work mapping inside a level, the same in both regimes: a lane per state; a
 // state with TOP_SORT_WAVE_INDEG in-slots or more (select) or a row of TOP_SORT_WAVE_ROW arcs or more (pre) is handed to
 // its whole wave (a strided minimum and a butterfly reduce; a wave scan over the row).  Every route gives the same FST.
+// The list form (wfst_top_sort_batch) is ONE launch of top_sort_batch_kernel below, one workgroup per
+// item: for items of a few hundred states the reference's sequential search itself (top_sort_dfs.h), run by one lane on
+// 16-bit arrays in LDS, then the apply pass by all lanes.  An item beyond 4096 states or 16384 arcs goes through top_sort_fst.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "batch_driver.h"
 #include "common.h"
 #include "fst_props.h"
+#include "top_sort_dfs.h"
+#include "wg_ops.h"
 
 namespace wfst {
 namespace {
@@ -561,6 +567,197 @@ wfst_fst* top_sort_fst(wfst_ctx* ctx, const wfst_fst* f) {
   stats.states_compared = h_ctr[0], stats.wave_states = h_ctr[1], stats.max_tree_depth = h_ctr[2];
   // ---- apply (top_sort.rs:84-87): state_sort's word, then the three bits set and nothing cleared
   return apply_order(ctx, f, order.p, new_start, (word & STATESORT_MASK) | TOP_SORTED_BITS);
+}
+
+// ================================================================ batch (wfst_top_sort_batch)
+namespace {
+
+constexpr uint32_t TSB_MAX_STATES = 4096;  // the in_kernel rule (include/wfst.h): tr_sum_batch's sizes
+constexpr uint32_t TSB_MAX_ARCS = 16384;
+constexpr size_t TSB_MAX_SLAB = (size_t)8 << 30;  // all slices of a call together; beyond: KO before any launch
+constexpr size_t TSB_MAX_LDS = 64u << 10;         // what one launch may ask for
+// TsbCtl::exit.  TSB_BAD_ITEM: sizes beyond the rule, a start state or an arc's nextstate beyond the states, offsets beyond
+// the arcs (the host never sends one); TSB_STEPS: the search passed its step bound
+enum : uint32_t { TSB_RUNNING = 0, TSB_DONE = 1, TSB_BAD_ITEM = 2, TSB_STEPS = 3 };
+
+struct TsbCtl {  // one per item, at the head of the slab; read back once
+  uint32_t exit;
+  uint32_t cyclic;
+  uint32_t new_start;
+  uint32_t n_states, n_arcs;
+  uint32_t pad[3];
+};
+struct TsbItem {
+  const uint32_t* off;
+  const wfst_tr* arcs;
+  const float* fin;
+  uint32_t n, E, start;
+  TsbCtl* ctl;
+  // the slice
+  uint32_t* deg;      // [n + 1] row lengths by new id
+  uint32_t* off_out;  // [n + 1] the result
+  float* fin_out;     // [n]
+  wfst_tr* arcs_out;  // [E]
+};
+
+// the dynamic LDS of an item: next[E], off[n + 1], rank[n], stack[n] of top_sort_dfs.h, 16-bit words one after the other
+constexpr size_t tsb_lds_bytes(uint32_t n, uint32_t E) { return ((size_t)E + 3u * (size_t)n + 1u) * sizeof(uint16_t); }
+static_assert(tsb_lds_bytes(TSB_MAX_STATES, TSB_MAX_ARCS) + (MB_TPB + 3) * sizeof(uint32_t) <= TSB_MAX_LDS, "the rule's largest item fits");
+static_assert(TSB_MAX_STATES < TSD_GREY && TSB_MAX_ARCS <= 0xFFFFu, "ranks, cursors and offsets fit 16 bits");
+
+// one workgroup per item: stage (all threads), the reference's search (one lane, top_sort_dfs.h), apply (all threads:
+// state_sort.rs:40-75 for the order the search left in LDS; a cyclic item takes the identity)
+__global__ void __launch_bounds__(MB_TPB) top_sort_batch_kernel(const TsbItem* __restrict__ items) {
+  extern __shared__ uint16_t tsb_lds[];
+  __shared__ uint32_t part[MB_TPB + 1];
+  __shared__ uint32_t s_code, s_bad;
+  const TsbItem it = items[blockIdx.x];
+  const uint32_t tid = threadIdx.x, gl = tid & 15u;
+  const uint32_t n = it.n, E = it.E;
+  if (n == 0 || n > TSB_MAX_STATES || E > TSB_MAX_ARCS || it.start >= n) {  // (before any index is made of them)
+    if (tid == 0) it.ctl->exit = TSB_BAD_ITEM;
+    return;
+  }
+  uint16_t* next = tsb_lds;       // [E]
+  uint16_t* off = next + E;       // [n + 1]
+  uint16_t* rank = off + n + 1u;  // [n]
+  uint16_t* stack = rank + n;     // [n]
+  // ---- 1. stage
+  if (tid == 0) s_bad = 0u;
+  __syncthreads();
+  for (uint32_t i = tid; i < E; i += MB_TPB) {
+    const uint32_t t = it.arcs[i].nextstate;
+    if (t >= n) s_bad = 1u;
+    next[i] = (uint16_t)t;
+  }
+  for (uint32_t s = tid; s <= n; s += MB_TPB) {
+    const uint32_t o = it.off[s];
+    if (o > E || (s == n ? o != E : it.off[s + 1] < o)) s_bad = 1u;  // (the apply phase places rows by these)
+    off[s] = (uint16_t)o;
+    if (s < n) rank[s] = TSD_WHITE;
+  }
+  __syncthreads();
+  if (s_bad) {
+    if (tid == 0) it.ctl->exit = TSB_BAD_ITEM;
+    return;
+  }
+  // ---- 2. search
+  if (tid == 0) s_code = top_sort_dfs(next, off, n, it.start, rank, stack, top_sort_dfs_max_steps(n, E));
+  __syncthreads();
+  const uint32_t code = s_code;
+  if (code == TSD_STEPS) {
+    if (tid == 0) it.ctl->exit = TSB_STEPS;
+    return;
+  }
+  if (code == TSD_CYCLIC) {
+    for (uint32_t s = tid; s < n; s += MB_TPB) rank[s] = (uint16_t)s;
+    __syncthreads();
+  }
+  // ---- 3. apply: row lengths and finals by new id, the new offsets, the arcs (16 lanes per state, 16-byte words)
+  for (uint32_t s = tid; s <= n; s += MB_TPB) {
+    if (s == n) {
+      stg(&it.deg[n], 0u);
+      continue;
+    }
+    const uint32_t o = rank[s];
+    stg(&it.deg[o], (uint32_t)off[s + 1] - (uint32_t)off[s]);
+    it.fin_out[o] = it.fin[s];
+  }
+  wg_bar();
+  wg_exclusive_scan(it.deg, it.off_out, n + 1, part);
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(it.arcs);
+  uint4* __restrict__ dst = reinterpret_cast<uint4*>(it.arcs_out);
+  for (uint32_t s = tid >> 4; s < n; s += MB_TPB >> 4) {
+    const uint32_t b = off[s], e = off[s + 1], base = ld(&it.off_out[rank[s]]);
+    for (uint32_t i = b + gl; i < e; i += 16) {
+      uint4 a = src[i];
+      a.w = rank[next[i]];
+      dst[base + (i - b)] = a;
+    }
+  }
+  if (tid == 0) {
+    it.ctl->cyclic = code == TSD_CYCLIC ? 1u : 0u;
+    it.ctl->new_start = rank[it.start];
+    it.ctl->n_states = n;
+    it.ctl->n_arcs = E;
+    it.ctl->exit = TSB_DONE;
+  }
+}
+
+// carves one item's arrays out of the slab; it == nullptr only measures
+size_t carve_top_sort_slice(Slab s, uint32_t n, uint32_t E, TsbItem* it) {
+  TsbItem v{};
+  v.deg = s.take<uint32_t>((size_t)n + 1);
+  v.off_out = s.take<uint32_t>((size_t)n + 1);
+  v.fin_out = s.take<float>(n);
+  v.arcs_out = s.take<wfst_tr>(E);
+  v.n = n;
+  v.E = E;
+  if (it) *it = v;  // (the input's side is the caller's)
+  return s.at();
+}
+
+}  // namespace
+
+// the host loop is batch_driver.h's, with the ownership check and one pass: every size is the input's, nothing grows
+void top_sort_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, wfst_fst** outs, uint8_t* in_kernel) {
+  ctx->top_sort_batch = {};
+  check_items_owned(ctx, fsts, n, "top_sort_batch");
+  hipStream_t st = ctx->stream;
+  enum : uint8_t { KERNEL, EMPTY, SINGLE };
+  struct Ran {
+    uint32_t cyclic = 0, new_start = 0;
+    const uint32_t* off = nullptr;
+    const wfst_tr* arcs = nullptr;
+    const float* fin = nullptr;
+  };
+  std::vector<uint8_t> kind(n);
+  std::vector<Ran> ran(n);
+  std::vector<size_t> run;  // the items that occupy a workgroup
+  size_t lds = 0;           // of the launch: its largest item's
+  for (size_t i = 0; i < n; ++i) {
+    const wfst_fst* f = fsts[i];
+    // no start state: without states the single call's own early answer, with states its KO (both without a launch)
+    kind[i] = f->start < 0 ? (f->n_states == 0 ? EMPTY : SINGLE)
+              : (f->n_states <= TSB_MAX_STATES && f->n_arcs <= TSB_MAX_ARCS) ? KERNEL : SINGLE;
+    if (kind[i] == KERNEL) {
+      ensure_device(const_cast<wfst_fst*>(f));
+      run.push_back(i);
+      lds = std::max(lds, tsb_lds_bytes(f->n_states, (uint32_t)f->n_arcs));
+    }
+  }
+  auto carve = [&](size_t i, Slab s, TsbItem* it) {
+    const wfst_fst* f = fsts[i];
+    const size_t end = carve_top_sort_slice(s, f->n_states, (uint32_t)f->n_arcs, it);
+    if (it) {
+      it->off = f->dev.offsets;
+      it->arcs = f->dev.arcs;
+      it->fin = f->dev.finals;
+      it->start = (uint32_t)f->start;
+    }
+    return end;
+  };
+  auto launch = [&](const TsbItem* d_items, uint32_t m) { top_sort_batch_kernel<<<m, MB_TPB, lds, st>>>(d_items); };
+  auto classify = [&](size_t i, const TsbCtl& c, const TsbItem& it) {
+    const wfst_fst* f = fsts[i];
+    if (c.exit != TSB_DONE || c.n_states != f->n_states || c.n_arcs != f->n_arcs || c.new_start >= f->n_states)
+      throw Error("top_sort_batch: internal error: the kernel left item " + std::to_string(i) + " with exit code " +
+                  std::to_string(c.exit));
+    ran[i] = Ran{c.cyclic, c.new_start, it.off_out, it.arcs_out, it.fin_out};
+    return BatchExit::FINISHED;
+  };
+  const auto slabs = batch_launch_loop<TsbItem, TsbCtl>(ctx, ctx->top_sort_batch, {"top_sort_batch", 1, nullptr, TSB_MAX_SLAB, "call"},
+                                                        std::move(run), carve, nullptr, launch, classify);
+  auto outcome = [&](size_t i) {
+    const wfst_fst* f = fsts[i];
+    const uint64_t word = f->props & props::ALL;
+    if (kind[i] == SINGLE) return BatchOutcome::single();
+    if (kind[i] == EMPTY) return BatchOutcome::handle(copy_with_word(ctx, f, word | TOP_SORTED_BITS));
+    const Ran& r = ran[i];
+    return BatchOutcome::adopt({f->n_states, f->n_arcs, (int64_t)r.new_start,
+                                r.cyclic ? (word | CYCLIC_BITS) : ((word & STATESORT_MASK) | TOP_SORTED_BITS), r.off, r.arcs, r.fin});
+  };
+  batch_finish(ctx, ctx->top_sort_batch, n, outs, in_kernel, outcome, [&](size_t i) { return top_sort_fst(ctx, fsts[i]); });
 }
 
 }  // namespace wfst

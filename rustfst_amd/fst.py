@@ -951,6 +951,25 @@ def tr_sum_batch_stats(ctx: Optional[Context] = None) -> dict:
     return _counters("tr_sum_batch", ctx or default_context())
 
 
+def top_sort_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
+    """[f.top_sort() for f in fsts] as ONE call (wfst_top_sort_batch): one workgroup per FST and one launch for the whole
+    list, whatever its length and the items' depths — the step between a list of compositions or unions and
+    optimize_batch, which wants ACYCLIC in the word.  A cyclic item comes back as a copy with CYCLIC | NOT_TOP_SORTED, as
+    from top_sort.  return_in_kernel: also the uint8 array that says which items the batch kernel finished (0: more than
+    4096 states or 16384 arcs sent the item through the single-FST path).  An item with states but no start state raises
+    WfstError with "item <i>: " in front of top_sort's message."""
+    return _batch_call("wfst_top_sort_batch", fsts, ctx, return_in_kernel)
+
+
+def top_sort_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last top_sort_batch call of ctx (wfst_ctx_get_top_sort_batch_counters): launches, items_in_kernel, items_single."""
+    ctx = ctx or default_context()
+    vals = [C.c_uint64() for _ in _lib.TOP_SORT_BATCH_COUNTERS]
+    check(_lib.lib().wfst_ctx_get_top_sort_batch_counters(ctx._h, *[C.byref(v) for v in vals]),
+          "wfst_ctx_get_top_sort_batch_counters")
+    return {k: int(v.value) for k, v in zip(_lib.TOP_SORT_BATCH_COUNTERS, vals)}
+
+
 def optimize_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
     """[f.optimize() for f in fsts] as ONE call (wfst_optimize_batch): rm_epsilon_batch over the items whose word lacks
     NO_EPSILONS, tr_sum_batch over all, determinize_batch and minimize_batch over the acceptors; a transducer takes the

@@ -16,10 +16,7 @@ from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
 from inputs import diamond_chain  # the input the tests use
 
-WIDE = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-DIAMONDS = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000
-BACKBONE = int(sys.argv[3]) if len(sys.argv) > 3 else 100_000
-ctx = rustfst_amd.default_context()
+ctx = None  # main() makes it: importing this file (tools/top_sort_batch_timing.py takes host_dfs_order) starts nothing
 
 
 def dev(f):
@@ -139,9 +136,19 @@ def report(name, flat):
     print(f"          " + "  ".join(f"{k}={v}" for k, v in st.items()), flush=True)
 
 
-rng = np.random.default_rng(19)
-report("wide", forward_dag(WIDE, rng, 64))
-report("lattice", lattice(rng))
-report("diamonds", diamond_chain(DIAMONDS))
-if BACKBONE:
-    report("backbone", forward_dag(BACKBONE, rng, BACKBONE))
+def main(argv):
+    global ctx
+    wide = int(argv[1]) if len(argv) > 1 else 1_000_000
+    diamonds = int(argv[2]) if len(argv) > 2 else 20_000
+    backbone = int(argv[3]) if len(argv) > 3 else 100_000
+    ctx = rustfst_amd.default_context()
+    rng = np.random.default_rng(19)
+    report("wide", forward_dag(wide, rng, 64))
+    report("lattice", lattice(rng))
+    report("diamonds", diamond_chain(diamonds))
+    if backbone:
+        report("backbone", forward_dag(backbone, rng, backbone))
+
+
+if __name__ == "__main__":
+    main(sys.argv)
