@@ -5,3 +5,9 @@ from .weight import *  # noqa: F401,F403
 from .props import *  # noqa: F401,F403
 from .fst import *  # noqa: F401,F403
 from .algorithms import *  # noqa: F401,F403
+from .determinize import *  # noqa: F401,F403
+from .push import *  # noqa: F401,F403
+from .minimize import *  # noqa: F401,F403
+from .optimize import *  # noqa: F401,F403
+from .rational import *  # noqa: F401,F403
+from .top_sort import *  # noqa: F401,F403

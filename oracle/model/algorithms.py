@@ -1,7 +1,7 @@
 """rustfst's algorithms restated in sequential Python, each with the lines of the reference it follows: what the
-device results are compared with, bit for bit, where the C++ oracle has no such operation.  So far the passes that more
-than one restatement runs (connect, tr_map, tr_unique, rm_final_epsilon); the drivers are still written out in
-tests/test_push_weights.py, test_determinize.py, test_minimize.py, test_optimize.py, test_rational_ops.py, test_top_sort.py."""
+device results are compared with, bit for bit, where the C++ oracle has no such operation.  Here the passes that more
+than one restatement runs (connect, tr_map, tr_unique, rm_final_epsilon); the drivers are in the modules beside this one
+(determinize.py, push.py, minimize.py, optimize.py, rational.py, top_sort.py)."""
 from .weight import F32, INF, approx_eq, is_zero, times
 from .props import (ACCESSIBLE, ARCSORT, COACCESSIBLE, DELETE_ARCS, DELETE_STATES, NOT_ACCESSIBLE, NOT_COACCESSIBLE,
                     NULL_PROPS, p_set_final)

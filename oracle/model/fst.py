@@ -259,3 +259,8 @@ def content_word(fst):
     f = dict(copy.deepcopy(fst), props=0)
     compute_and_update(f, ALL)
     return f["props"]
+
+
+def to_oracle(oracle, flat):
+    return oracle.OracleFst.from_flat(flat["n_states"], flat["start"], flat["offsets"], flat["arcs"], flat["finals"],
+                                      flat["props"])

@@ -1,5 +1,6 @@
 """Shared test helpers: seeded random FSTs, flat <-> oracle conversion, comparison, the library's last error."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -7,6 +8,7 @@ import numpy as np
 from rustfst_amd._lib import TR_DTYPE
 from rustfst_amd import ComposeFilter, synth
 
+from oracle.model import ACCEPTOR, B, F32, INF, csr_next, fst_to_flat, make_flat, reach, reverse_len_rule, to_oracle
 from oracle.model.props import NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED
 
 P = synth  # property bit names
@@ -51,11 +53,6 @@ def random_fst_flat(rng, n_states, max_fanout, sigma, p_eps_i=0.0, p_eps_o=0.0, 
     props |= P.O_LABEL_SORTED if ol_sorted else NOT_O_LABEL_SORTED
     return dict(n_states=n_states, start=0 if n_states else None, offsets=np.array(offsets, dtype=np.uint32), arcs=arcs,
                 finals=finals, props=props)
-
-
-def to_oracle(oracle, flat):
-    return oracle.OracleFst.from_flat(flat["n_states"], flat["start"], flat["offsets"], flat["arcs"], flat["finals"],
-                                      flat["props"])
 
 
 def to_device(flat, ctx=None):
@@ -217,3 +214,186 @@ def flat_matches_spec(flat, spec):
             assert abs(float(flat["finals"][s]) - fin[s]) <= 1.0 / 1024.0
         else:
             assert np.isinf(flat["finals"][s])
+
+
+def _flat(n, start, rows, finals, props=None):
+    """rows[s] = [(ilabel, olabel, weight, nextstate)]; the property word states label sortedness truthfully"""
+    offsets = np.zeros(n + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    flat_rows = [a for r in rows for a in r]
+    arcs = np.array(flat_rows, dtype=TR_DTYPE) if flat_rows else np.zeros(0, dtype=TR_DTYPE)
+    if props is None:
+        il = all(all(r[i][0] <= r[i + 1][0] for i in range(len(r) - 1)) for r in rows)
+        ol = all(all(r[i][1] <= r[i + 1][1] for i in range(len(r) - 1)) for r in rows)
+        props = (synth.I_LABEL_SORTED if il else NOT_I_LABEL_SORTED) | (synth.O_LABEL_SORTED if ol else NOT_O_LABEL_SORTED)
+    return dict(n_states=n, start=start, offsets=offsets, arcs=arcs, finals=np.asarray(finals, dtype=np.float32), props=props)
+
+
+def empty_flat(props=0, start=None):
+    return dict(n_states=0, start=start, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE), finals=np.zeros(0, np.float32),
+                props=props)
+
+
+def fst(rows, finals, props=None):
+    return _flat(len(rows), 0, rows, finals, props)
+
+
+def finals_of(n, where):
+    f = np.full(n, np.inf, dtype=np.float32)
+    for s, w in where.items():
+        f[s] = w
+    return f
+
+
+def string(labels, final_weight=0.0):
+    return synth.linear_acceptor_flat(np.asarray(labels, dtype=np.uint32), final_weight)
+
+
+_AN = {}
+
+
+def analyse(oracle, a, b, flt=0):
+    """the untrimmed composition with its BFS levels (lo, hi, arcs emitted, new states), the trimmed one, the canonical path"""
+    key = (id(a), id(b), flt)
+    if key not in _AN:
+        oa, ob = to_oracle(oracle, a), to_oracle(oracle, b)
+        c = oa.compose(ob, connect=False, compose_filter=flt)
+        cf = c.to_flat()
+        n, off, nx = cf["n_states"], cf["offsets"].astype(np.int64), cf["arcs"]["nextstate"].astype(np.int64)
+        if len(nx):  # first-touch order: an arc names a state seen before, or the next new one
+            seen = np.maximum.accumulate(np.concatenate([[0], nx]))
+            assert np.all(np.diff(seen) <= 1), "the oracle's ids are not first-touch order"
+        levels, lo, hi = [], 0, min(n, 1)
+        while lo < hi:
+            e0, e1 = int(off[lo]), int(off[hi])
+            new_hi = max(hi, int(nx[e0:e1].max()) + 1 if e1 > e0 else 0)
+            levels.append((lo, hi, e1 - e0, new_hi - hi))
+            lo, hi = hi, new_hi
+        assert hi == n
+        path = c.shortest_path_canonical().to_flat()
+        _AN[key] = dict(a=a, b=b, full=cf, trim=oa.compose(ob, connect=True, compose_filter=flt).to_flat(), levels=levels, path=path,
+                        hops=path["n_states"] - 1 if path["n_states"] else None)
+    return _AN[key]
+
+
+_AN_STRING = {}
+
+
+def analyse_string(oracle, a, t):
+    """the oracle's untrimmed composition (states, arcs) and its canonical shortest path"""
+    key = (id(a), id(t))
+    if key not in _AN_STRING:
+        c = to_oracle(oracle, a).compose(to_oracle(oracle, t), connect=False, compose_filter=0)
+        cf = c.to_flat()
+        _AN_STRING[key] = dict(a=a, t=t, n_states=cf["n_states"], n_arcs=len(cf["arcs"]), path=c.shortest_path_canonical().to_flat())
+    return _AN_STRING[key]
+
+
+def wstring(labels, weights=None, final_weight=0.0):
+    """a string whose arcs carry weights"""
+    L = len(labels)
+    weights = [0.0] * L if weights is None else weights
+    rows = [[(int(labels[i]), int(labels[i]), float(weights[i]), i + 1)] for i in range(L)] + [[]]
+    return fst(rows, finals_of(L + 1, {L: final_weight}))
+
+
+def names_to_word(names):
+    return sum(1 << B[n] for n in names)
+
+
+def golden_fst(m):
+    return dict(rows=[[[il, ol, F32(w), ns] for il, ol, w, ns in row] for row in m["rows"]],
+                finals=[None if w is None else F32(w) for w in m["finals"]], start=m["start"], props=names_to_word(m["props"]))
+
+
+def make_fst(rows, finals, start, props=0):
+    return dict(rows=[[[il, ol, F32(w), ns] for il, ol, w, ns in row] for row in rows],
+                finals=[None if w is None else F32(w) for w in finals], start=start, props=props)
+
+
+def dev(fst, ctx):
+    return to_device(fst_to_flat(fst), ctx)
+
+
+def _vector_fst(m):
+    import rustfst_amd
+    f = rustfst_amd.VectorFst()
+    for _ in m["rows"]:
+        f.add_state()
+    if m["start"] is not None:
+        f.set_start(m["start"])
+    for s, w in enumerate(m["finals"]):
+        if w is not None:
+            f.set_final(s, float(w))
+    for s, row in enumerate(m["rows"]):
+        for il, ol, w, ns in row:
+            f.add_tr(s, rustfst_amd.Tr(il, ol, float(w), ns))
+    return f
+
+
+def golden_flat(c, key="input"):
+    g = c[key]
+    n = g["n_states"]
+    rows = [[] for _ in range(n)]
+    for s, il, ol, w, ns in g["arcs"]:
+        rows[s].append((il, ol, w, ns))
+    finals = [INF] * n
+    for s, w in g["finals"]:
+        finals[s] = w
+    return make_flat(n, g["start"], rows, finals, int(g["props"], 16))
+
+
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+
+
+def golden(name):
+    with open(os.path.join(GOLDEN_DIR, name)) as f:
+        return json.load(f)["cases"]
+
+
+def flat_of(e, default_props=ACCEPTOR):
+    """the k15 format (offsets, [il, ol, w, ns] rows, finals with null) or the k12 one (arc rows [s, il, ol, w, ns],
+    finals as [s, w] pairs)"""
+    n = e["n_states"]
+    if "offsets" in e:
+        rows, offsets = e["arcs"], e["offsets"]
+        fin = [np.inf if w is None else w for w in e["finals"]]
+    else:
+        per = [[] for _ in range(n)]
+        for s, il, ol, w, ns in e["arcs"]:
+            per[s].append((il, ol, w, ns))
+        rows, offsets = [r for p in per for r in p], np.cumsum([0] + [len(p) for p in per])
+        fin = [np.inf] * n
+        for s, w in e["finals"]:
+            fin[s] = w
+    arcs = np.zeros(len(rows), TR_DTYPE)
+    for k, r in enumerate(rows):
+        arcs[k] = tuple(r)
+    props = int(e["props"], 16) if "props" in e else default_props
+    return dict(n_states=n, start=e["start"], offsets=np.array(offsets, np.uint32), arcs=arcs,
+                finals=np.array(fin, np.float32), props=props)
+
+
+def assert_same(got, exp, what):
+    assert got["n_states"] == exp["n_states"], f"{what}: num_states {got['n_states']} != {exp['n_states']}"
+    assert got["start"] == exp["start"], f"{what}: start"
+    np.testing.assert_array_equal(got["offsets"], exp["offsets"], err_msg=f"{what}: offsets")
+    for k in ("ilabel", "olabel", "nextstate"):
+        np.testing.assert_array_equal(got["arcs"][k], exp["arcs"][k], err_msg=f"{what}: arcs.{k}")
+    np.testing.assert_array_equal(got["arcs"]["weight"].view(np.uint32), exp["arcs"]["weight"].view(np.uint32),
+                                  err_msg=f"{what}: arc weights (bit pattern)")
+    np.testing.assert_array_equal(got["finals"].view(np.uint32), exp["finals"].view(np.uint32),
+                                  err_msg=f"{what}: final weights (bit pattern)")
+    assert got["props"] == exp["props"], f"{what}: props {got['props']:#x} != {exp['props']:#x}"
+
+
+def _oracle_dist(oracle, flat, to_final):
+    o = to_oracle(oracle, flat)
+    if to_final:
+        if flat["start"] is None:
+            return []
+        n = flat["n_states"]
+        off, nxt = csr_next(flat)
+        ln = int(np.nonzero(reach(n, off, nxt, [flat["start"]]))[0].max()) + 1
+        return list(o.shortest_distance()[:ln])
+    return list(o.reverse().shortest_distance()[1:][:reverse_len_rule(flat)])

@@ -1,10 +1,14 @@
 """Input families and kernel-route restatements that more than one test module, or a tool, uses."""
+import json
+import os
+
 import numpy as np
 
 from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
 
 from oracle.model.props import ACCEPTOR, determinize_props
+from helpers import ROOT, make_fst
 
 
 # ================================================================ determinize
@@ -84,3 +88,41 @@ def diamond_chain(levels, seed=11):
     fin = np.full(n, np.inf, np.float32)
     fin[n - 2:] = [0.0, 2.0]
     return dict(n_states=n, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
+
+
+# ================================================================ top_sort, the rational operations
+TOP_SORT_GOLDEN = os.path.join(ROOT, "tests", "golden", "k19_top_sort.json")
+
+
+def top_sort_golden():
+    with open(TOP_SORT_GOLDEN) as f:
+        return json.load(f)
+
+
+def random_shuffled_dag(rng, n, max_arcs_per_state=3, start=None):
+    """n states in a hidden topological order; arcs (multi-arcs too) from earlier to later places, rows shuffled; some states
+    the start cannot reach; the start anywhere"""
+    place = rng.permutation(n)  # place[k] = the state at topological place k
+    rows = [[] for _ in range(n)]
+    if n > 1:
+        for _ in range(int(rng.integers(0, max_arcs_per_state * n + 1))):
+            a, b = sorted(int(x) for x in rng.choice(n, 2, replace=False))
+            il = int(rng.integers(0, 4))
+            rows[place[a]].append([il, il if rng.random() < 0.5 else int(rng.integers(0, 4)), float(rng.integers(0, 9)) / 4, int(place[b])])
+        if rng.random() < 0.5:  # a doubled arc
+            src = [s for s in range(n) if rows[s]]
+            if src:
+                s = src[int(rng.integers(0, len(src)))]
+                rows[s].append(list(rows[s][0]))
+    for r in rows:
+        rng.shuffle(r)
+    finals = [float(rng.integers(0, 8)) / 4 if rng.random() < 0.4 else None for _ in range(n)]
+    return make_fst(rows, finals, int(rng.integers(0, n)) if start is None else start)
+
+
+def chain(n, rng, finals_from=None, fan=1, start=0):
+    """n states; state s has `fan` arcs into later states (none from the last); finals at states >= finals_from"""
+    rows = [[[int(rng.integers(1, 9)), int(rng.integers(1, 9)), float(rng.integers(0, 16)) / 8,
+              int(rng.integers(s + 1, n))] for _ in range(fan)] if s + 1 < n else [] for s in range(n)]
+    ff = n - 1 if finals_from is None else finals_from
+    return make_fst(rows, [float(rng.integers(0, 8)) / 4 if s >= ff else None for s in range(n)], start)

@@ -21,7 +21,7 @@ RW_ACC = [(rw, acc) for rw in (0, 1, 2) for acc in (False, True)]
 THOUSAND = [2 * x for x in range(1, 1001)]
 
 
-def string(labels, weights=None, final=0.0):
+def weighted_string(labels, weights=None, final=0.0):
     """utils::acceptor with weights: a linear, epsilon-free acceptor"""
     n = len(labels)
     w = weights if weights is not None else [0.0] * n
@@ -109,7 +109,7 @@ def seeded_strings(seed, n, sigma):
         length = int(rng.integers(0, 13))
         labels = [int(x) for x in rng.integers(1, 9, length)]
         labels = [l if l != sigma else 7 for l in labels]
-        out.append(string(labels, [float(rng.integers(0, 2560)) / 512 for _ in labels], float(rng.integers(0, 512)) / 512))
+        out.append(weighted_string(labels, [float(rng.integers(0, 2560)) / 512 for _ in labels], float(rng.integers(0, 512)) / 512))
     return out
 
 

@@ -26,19 +26,17 @@ import pytest
 
 from rustfst_amd import synth
 
-import test_small_path_limits as sl
 import helpers
-from helpers import FILTERS, NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, ROOT, assert_flat_identical, to_device, to_oracle
+from helpers import (FILTERS, NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, ROOT, analyse, assert_flat_identical, empty_flat,
+                     finals_of, fst, string, to_device)
+import small_path_cases as spc
+from string_cases import STR_LEVEL, STR_MAXS, STR_PACKED_MIN, STR_SLICES, ladder_t, string_slice
 
 INF = float("inf")
 # ---- the kernels' own limits (rustfst_amd/csrc/compose.hip), restated once
 WAVE = 64               # :383 small = n_se <= 64; :396 items 64 at a time; :452 level_cnt + total > 64u; :780 / :1017 W = 64
 WIDE_STATES = 16384     # :1016 WIDE_COMPOSE_STATES
-STR_MAXS = 2048         # :1018
-STR_LEVEL = 64          # :1115 idx >= 64u
 STR_SCALAR_ARCS = 12    # :1146 fc <= 12u && fb + 12u <= f2_n_arcs
-STR_SLICES = (512, 1024, 2048)  # :1480-1481 the least slice >= 2 * max_states + 64, packed batches of >= 16
-STR_PACKED_MIN, STR_SCALAR_MAX_N = 16, 8  # :1477 n >= 16; :1496 n <= 8
 COUNTERS = ("string_answered", "string_handed_back", "wave_first", "relaunch_states", "relaunch_arcs", "relaunch_hash",
             "relaunch_path", "switched_wide", "two_step", "caps_states", "caps_arcs", "caps_hash")
 ZERO = dict.fromkeys(COUNTERS, 0)
@@ -69,17 +67,6 @@ def hash_slots(s):
 
 
 # ================================================================ generators
-def fst(rows, finals, props=None):
-    return sl._flat(len(rows), 0, rows, finals, props)
-
-
-def finals_of(n, where):
-    f = np.full(n, np.inf, dtype=np.float32)
-    for s, w in where.items():
-        f[s] = w
-    return f
-
-
 @functools.lru_cache(maxsize=None)
 def loop_t(n_labels, doubled=0):
     """one final state, an arc l:l back to it for every label 1..n_labels; the first `doubled` labels carry a second arc
@@ -172,7 +159,7 @@ def tie_case():
 
 def cyclic_case(grid):
     """a ring with chords (cyclic, sorted by input label only: the second operand alone decides the matching side)"""
-    return sl.ring_with_chords(np.random.default_rng(50 + grid), 40, 90, grid), loop_t(5)
+    return spc.ring_with_chords(np.random.default_rng(50 + grid), 40, 90, grid), loop_t(5)
 
 
 def chain_t(n, par, extra=0):
@@ -274,18 +261,6 @@ def block_t(last):
 
 
 @functools.lru_cache(maxsize=None)
-def ladder_t(w):
-    """label 1 leads from the start state to w states that loop on it: every level of 1^L has w states.  Label 2 loops too,
-    and adds ONE state from g0: a string that ends in 2 has one state more in all, and w + 1 in its last level."""
-    g = lambda j: 1 + j
-    rows = [[(1, 100 + j, (j % 4) / 4.0, g(j)) for j in range(w)]]
-    for j in range(w):
-        rows.append([(1, 100 + j, 0.25, g(j)), (2, 200 + j, 0.0, g(j))] + ([(2, 300, 0.25, g(w))] if j == 0 else []))
-    rows.append([(1, 400, 0.25, g(w))])
-    return fst(rows, finals_of(w + 2, {g(j): ((j * 3) % 5) / 4.0 for j in range(w + 1)}))
-
-
-@functools.lru_cache(maxsize=None)
 def tie_t():
     """a and b reach c at 3/4 both (the earlier source, a, stays); c has two equal arcs to d (the earlier position stays); the
     only way into e costs +inf: the string 1^4 has no path, 1^3 ends in d"""
@@ -301,10 +276,6 @@ def len_t():
     rows = [[(l, 10 * s + l, ((s + l) % 4) / 4.0, (2 * s + l) % 5) for l in (1, 2, 3)] + [(3, 10 * s + 4, ((s + 1) % 4) / 4.0, (s + 1) % 5)]
             for s in range(5)]
     return fst(rows, finals_of(5, {s: s / 512.0 for s in range(5)}))
-
-
-def string(labels, final_weight=0.0):
-    return synth.linear_acceptor_flat(np.asarray(labels, dtype=np.uint32), final_weight)
 
 
 STRING_LENGTHS = (0, 1, 63, 64, 65, 127, 128, 129)
@@ -344,33 +315,6 @@ def slice_batch(slice_, beyond):
 
 
 # ================================================================ what the oracle says about an input
-_AN = {}
-
-
-def analyse(oracle, a, b, flt=0):
-    """the untrimmed composition with its BFS levels (lo, hi, arcs emitted, new states), the trimmed one, the canonical path"""
-    key = (id(a), id(b), flt)
-    if key not in _AN:
-        oa, ob = to_oracle(oracle, a), to_oracle(oracle, b)
-        c = oa.compose(ob, connect=False, compose_filter=flt)
-        cf = c.to_flat()
-        n, off, nx = cf["n_states"], cf["offsets"].astype(np.int64), cf["arcs"]["nextstate"].astype(np.int64)
-        if len(nx):  # first-touch order: an arc names a state seen before, or the next new one
-            seen = np.maximum.accumulate(np.concatenate([[0], nx]))
-            assert np.all(np.diff(seen) <= 1), "the oracle's ids are not first-touch order"
-        levels, lo, hi = [], 0, min(n, 1)
-        while lo < hi:
-            e0, e1 = int(off[lo]), int(off[hi])
-            new_hi = max(hi, int(nx[e0:e1].max()) + 1 if e1 > e0 else 0)
-            levels.append((lo, hi, e1 - e0, new_hi - hi))
-            lo, hi = hi, new_hi
-        assert hi == n
-        path = c.shortest_path_canonical().to_flat()
-        _AN[key] = dict(a=a, b=b, full=cf, trim=oa.compose(ob, connect=True, compose_filter=flt).to_flat(), levels=levels, path=path,
-                        hops=path["n_states"] - 1 if path["n_states"] else None)
-    return _AN[key]
-
-
 def dead_states(cf):
     """ids of the untrimmed composition from which no final state is reached"""
     n, off, nx = cf["n_states"], cf["offsets"], cf["arcs"]["nextstate"]
@@ -483,12 +427,6 @@ def predict_compose(an, pinned_wave):
         if not pinned_wave and s > WIDE_STATES:
             c["switched_wide"] += 1
             return c
-
-
-def string_slice(n_eligible, max_states, unpacked):
-    if unpacked or n_eligible < STR_PACKED_MIN:
-        return STR_MAXS
-    return next(m for m in STR_SLICES if 2 * max_states + 64 <= m or m == STR_MAXS)
 
 
 def predict_batch(oracle, accs, t, flt=0, string_kernel=True, unpacked=False):
@@ -779,7 +717,7 @@ def test_predicted_counters_of_the_wave_cases(oracle):
         a, b = wave_case(name)
         p = predict_batch(oracle, [a], b, string_kernel=False)
         assert p["wave_first"] + p["two_step"] == 1 and sum(p[k] for k in COUNTERS[:2] + COUNTERS[3:8]) == 0, name
-    empty = sl.empty_flat()
+    empty = empty_flat()
     assert predict_compose(analyse(oracle, empty, loop_t(2)), False) == ZERO
     assert wave_status([(0, 1, 65, 65)], 1280, 5120, 64) == "wide" and wave_status([(0, 1, 64, 64), (1, 65, 64, 1)], 1280, 5120, 64) == "ok"
     assert wave_status([(0, 1, 10, 3)], 3, 128, 0) == "states" and wave_status([(0, 1, 10, 2)], 3, 128, 0) == "ok"

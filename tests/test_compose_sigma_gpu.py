@@ -17,16 +17,13 @@ from oracle.model import O_LABEL_SORTED, flat_to_fst, fst_to_flat
 from oracle.model.props import NOT_I_LABEL_SORTED
 
 import helpers
+from helpers import dev
 import sigma_cases as S
 import sigma_ref as R
 
 pytestmark = pytest.mark.gpu
 INF = np.inf
 DEVICE_COUNTERS = ("require1_states", "require2_states", "exact_items", "sigma_items", "sigma_arcs", "refused_items")
-
-
-def dev(fst, ctx):
-    return helpers.to_device(fst_to_flat(fst), ctx)
 
 
 def matcher(m):

@@ -1,9 +1,8 @@
 """determinize / determinize_with_config of acceptors (wfst_determinize): the C-ABI surface without a GPU, a Python
-restatement of rustfst's DeterminizeFsa (written out below) checked against the K12 / K15 known answers and the oracle,
+restatement of rustfst's DeterminizeFsa (oracle/model/determinize.py) checked against the K12 / K15 known answers and the oracle,
 and on the device parity with the oracle in every regime, closed-form answers at scale, invariants and error handling."""
 import ctypes as C
 import inspect
-import json
 import math
 import os
 import re
@@ -13,158 +12,13 @@ import pytest
 
 from rustfst_amd._lib import TR_DTYPE
 
-from oracle.model import ACCEPTOR, F32, INF, KDELTA, approx_eq, determinize_props, plus, quantize, times
-from helpers import ROOT, assert_flat_identical, enumerate_paths, ko_message, random_fst_flat, to_device, to_oracle
+from oracle.model import ACCEPTOR, KDELTA, determinize_props, determinize_ref
+from helpers import (ROOT, assert_flat_identical, enumerate_paths, flat_of, golden, ko_message, random_fst_flat,
+                     to_device, to_oracle)
 from inputs import diamond_chain, twin_copy
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+from determinize_cases import collision_level, parity_inputs, random_acceptor
 
 PATHS = ("narrow", "wide", "auto")
-
-
-# ---------------------------------------------------------------- restatement (determinize_fsa_op.rs, state_table.rs)
-def determinize_ref(flat, delta=KDELTA, det_type=0, max_states=1 << 20):
-    """DeterminizeFsa with DefaultCommonDivisor in LazyFst::compute's FIFO first-touch order; subsets in ascending state
-    order; a candidate joins the lowest-id state with the same states and approx_eq weights."""
-    if not flat["props"] & ACCEPTOR:
-        raise ValueError("transducers are not supported")
-    props = determinize_props(flat["props"], det_type != 1)
-    if flat["start"] is None or flat["n_states"] == 0:
-        return dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
-                    finals=np.zeros(0, np.float32), props=props)
-    off, arcs, fin = flat["offsets"], flat["arcs"], flat["finals"]
-    tuples = [((int(flat["start"]), F32(0.0)),)]
-    by_states = {(int(flat["start"]),): [0]}
-    rows, finals, offsets = [], [], [0]
-
-    def find(t):
-        ids = by_states.setdefault(tuple(s for s, _ in t), [])
-        for i in ids:
-            if all(approx_eq(w, v) for (_, w), (_, v) in zip(t, tuples[i])):
-                return i
-        ids.append(len(tuples))
-        tuples.append(t)
-        if len(tuples) > max_states:
-            raise RuntimeError("does not determinize")
-        return len(tuples) - 1
-
-    s = 0
-    while s < len(tuples):
-        cand = [(int(a["ilabel"]), int(a["nextstate"]), times(w, F32(a["weight"])))
-                for q, w in tuples[s] for a in arcs[off[q]:off[q + 1]]]
-        cand.sort(key=lambda c: (c[0], c[1]))  # stable
-        fw = INF
-        for q, w in tuples[s]:
-            fw = plus(fw, times(w, F32(fin[q])))
-        i = 0
-        while i < len(cand):
-            j, weight = i, INF
-            while j < len(cand) and cand[j][0] == cand[i][0]:
-                weight = plus(weight, cand[j][2])
-                j += 1
-            merged = []
-            for _, q, w in cand[i:j]:
-                if merged and merged[-1][0] == q:
-                    merged[-1][1] = plus(merged[-1][1], w)
-                else:
-                    merged.append([q, w])
-            t = tuple((q, quantize(F32(w - weight), delta)) for q, w in merged)
-            rows.append((cand[i][0], cand[i][0], weight, find(t)))
-            i = j
-        offsets.append(len(rows))
-        finals.append(fw)
-        s += 1
-    a = np.zeros(len(rows), TR_DTYPE)
-    for k, r in enumerate(rows):
-        a[k] = r
-    return dict(n_states=len(tuples), start=0, offsets=np.array(offsets, np.uint32), arcs=a,
-                finals=np.array(finals, np.float32), props=props)
-
-
-# ---------------------------------------------------------------- inputs
-def golden(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)["cases"]
-
-
-def flat_of(e, default_props=ACCEPTOR):
-    """the k15 format (offsets, [il, ol, w, ns] rows, finals with null) or the k12 one (arc rows [s, il, ol, w, ns],
-    finals as [s, w] pairs)"""
-    n = e["n_states"]
-    if "offsets" in e:
-        rows, offsets = e["arcs"], e["offsets"]
-        fin = [np.inf if w is None else w for w in e["finals"]]
-    else:
-        per = [[] for _ in range(n)]
-        for s, il, ol, w, ns in e["arcs"]:
-            per[s].append((il, ol, w, ns))
-        rows, offsets = [r for p in per for r in p], np.cumsum([0] + [len(p) for p in per])
-        fin = [np.inf] * n
-        for s, w in e["finals"]:
-            fin[s] = w
-    arcs = np.zeros(len(rows), TR_DTYPE)
-    for k, r in enumerate(rows):
-        arcs[k] = tuple(r)
-    props = int(e["props"], 16) if "props" in e else default_props
-    return dict(n_states=n, start=e["start"], offsets=np.array(offsets, np.uint32), arcs=arcs,
-                finals=np.array(fin, np.float32), props=props)
-
-
-def random_acceptor(rng, n, fanout, sigma, **kw):
-    f = random_fst_flat(rng, n, fanout, sigma, **kw)
-    f["arcs"]["olabel"] = f["arcs"]["ilabel"]
-    f["props"] |= ACCEPTOR
-    return f
-
-
-def f32_weights(rng, f):
-    f["arcs"]["weight"] = rng.random(len(f["arcs"])).astype(np.float32) * np.float32(3.0)
-    fin = f["finals"]
-    f["finals"] = np.where(np.isfinite(fin), rng.random(len(fin)).astype(np.float32), np.inf).astype(np.float32)
-    return f
-
-
-def parity_inputs():
-    """(name, flat, delta) — acyclic DAGs with small alphabets, epsilon labels, cyclic unweighted, integer and arbitrary
-    f32 weights, non-default deltas"""
-    rng = np.random.default_rng(1515)
-    out = []
-    for k in range(6):
-        n = int(rng.integers(2, 40))
-        out.append((f"dag{k}", random_acceptor(rng, n, 4, 2 + k % 2, acyclic=True), KDELTA))
-    for k in range(3):
-        out.append((f"eps{k}", random_acceptor(rng, 30, 3, 3, p_eps_i=0.3, acyclic=True), KDELTA))
-    for k in range(4):
-        out.append((f"cyclic_unweighted{k}", random_acceptor(rng, 25 + 10 * k, 3, 3, max_w=1, p_eps_i=0.1), KDELTA))
-    for k in range(3):
-        out.append((f"int{k}", random_acceptor(rng, 40, 4, 3, weight_grid=1, max_w=5, acyclic=True), KDELTA))
-    for k in range(3):
-        out.append((f"f32_{k}", f32_weights(rng, random_acceptor(rng, 40, 4, 3, acyclic=True)), KDELTA))
-    for k, d in enumerate((0.5, 0.1, 1.0 / 3.0)):
-        out.append((f"delta{k}", random_acceptor(rng, 40, 4, 3, acyclic=True), d))
-    out.append(("empty", dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
-                              finals=np.zeros(0, np.float32), props=ACCEPTOR), KDELTA))
-    return out
-
-
-def collision_level(S=64, M=200, seed=7):
-    """a start state with S arcs (distinct labels) into states 1..S; each of those has M labels, every label with one
-    arc into A (weight 0) and one into B (weight k * KDELTA, k random in 0..12): the second level holds S * M candidates
-    with the same state set {A, B} and weights a KDELTA apart"""
-    rng = np.random.default_rng(seed)
-    A, B, F = S + 1, S + 2, S + 3
-    rows = [[(j + 1, j + 1, 0.0, j + 1) for j in range(S)]]
-    for s in range(S):
-        r = []
-        for i in range(M):
-            r += [(i + 1, i + 1, 0.0, A), (i + 1, i + 1, float(rng.integers(0, 13)) * KDELTA, B)]
-        rows.append(r)
-    rows += [[(1, 1, 0.0, F)], [(1, 1, 0.0, F)], []]
-    arcs = np.array([x for r in rows for x in r], dtype=TR_DTYPE)
-    offsets = np.cumsum([0] + [len(r) for r in rows]).astype(np.uint32)
-    fin = np.full(S + 4, np.inf, np.float32)
-    fin[F] = 0.0
-    return dict(n_states=S + 4, start=0, offsets=offsets, arcs=arcs, finals=fin, props=ACCEPTOR)
 
 
 def same(got, exp, what, props=True):

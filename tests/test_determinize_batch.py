@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 from rustfst_amd._lib import TR_DTYPE
-
-import test_determinize as td
 from oracle import model
 import helpers
-from helpers import assert_flat_identical, random_fst_flat, to_device, to_oracle
+from helpers import assert_flat_identical, empty_flat, flat_of, golden, random_fst_flat, to_device, to_oracle
 import inputs
+import determinize_cases as dc
+from oracle.model import determinize_ref
 
 ROOT = helpers.ROOT
 KDELTA, INF, f32, ACCEPTOR = model.KDELTA, model.INF, model.F32, model.ACCEPTOR
@@ -28,7 +28,7 @@ SCRATCH = ("lds", "global")
 
 # ---------------------------------------------------------------- restatement (determinize_static.rs:24-39)
 def determinize_with_distance_ref(flat, in_dist=(), delta=KDELTA, max_states=1 << 20):
-    """td.determinize_ref (the same construction, statement by statement) that also returns the subsets, out_dist
+    """determinize_ref (the same construction, statement by statement) that also returns the subsets, out_dist
     (state_table.rs:25-39,79-96: plus over the subset's elements in stored order of w (x) in_dist[q], q beyond in_dist =
     +inf) and, per breadth-first level, (states, raw candidates): (fst, out_dist, subsets, levels)."""
     if not flat["props"] & ACCEPTOR:
@@ -108,14 +108,14 @@ def predict_in_kernel(flat, delta=KDELTA):
 
 
 def golden_inputs():
-    out = [(c["name"], td.flat_of(c["fst"]), KDELTA, 0) for c in td.golden("k12_determinize.json")]
-    out += [(c["name"], td.flat_of(c["fst"]), c["delta"], c["det_type"]) for c in td.golden("k15_determinize.json")]
+    out = [(c["name"], flat_of(c["fst"]), KDELTA, 0) for c in golden("k12_determinize.json")]
+    out += [(c["name"], flat_of(c["fst"]), c["delta"], c["det_type"]) for c in golden("k15_determinize.json")]
     return out
 
 
 @functools.lru_cache(maxsize=None)
 def collision_flat():
-    return td.collision_level(64, 200)
+    return dc.collision_level(64, 200)
 
 
 @functools.lru_cache(maxsize=None)
@@ -124,18 +124,13 @@ def collision_prediction():
 
 
 def no_start(n=4):
-    f = td.random_acceptor(np.random.default_rng(3), n, 2, 2, acyclic=True)
+    f = dc.random_acceptor(np.random.default_rng(3), n, 2, 2, acyclic=True)
     f["start"] = None
     return f
 
 
-def empty_flat():
-    return dict(n_states=0, start=None, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
-                finals=np.zeros(0, np.float32), props=ACCEPTOR)
-
-
 def cyclic_unweighted(seed=21):
-    return td.random_acceptor(np.random.default_rng(seed), 25, 3, 3, max_w=1, p_eps_i=0.1)
+    return dc.random_acceptor(np.random.default_rng(seed), 25, 3, 3, max_w=1, p_eps_i=0.1)
 
 
 def non_determinizing():
@@ -221,9 +216,9 @@ def test_python_surface():
 
 
 def test_restatement_equals_determinize_ref():
-    for name, flat, delta in td.parity_inputs():
+    for name, flat, delta in dc.parity_inputs():
         got = determinize_with_distance_ref(flat, (), delta)
-        same(got[0], td.determinize_ref(flat, delta), name)
+        same(got[0], determinize_ref(flat, delta), name)
         assert len(got[1]) == got[0]["n_states"] == len(got[2])
         assert sum(n for n, _ in got[3]) == got[0]["n_states"]
 
@@ -232,7 +227,7 @@ def test_restatement_distances_are_reverse_distances(oracle):
     rng = np.random.default_rng(77)
     finite = 0
     for k in range(6):
-        flat = td.random_acceptor(rng, 30 + 5 * k, 4, 3, weight_grid=1, max_w=6, acyclic=True, min_fanout=1)
+        flat = dc.random_acceptor(rng, 30 + 5 * k, 4, 3, weight_grid=1, max_w=6, acyclic=True, min_fanout=1)
         flat["finals"][-1] = 2.0  # every state has an arc forward and the last one is final: every distance is finite
         rev = to_oracle(oracle, flat).reverse().shortest_distance()[1:]
         det, out_dist, _, _ = determinize_with_distance_ref(flat, rev)
@@ -244,7 +239,7 @@ def test_restatement_distances_are_reverse_distances(oracle):
 
 
 def test_in_kernel_prediction_of_the_test_inputs():
-    for name, flat, delta in td.parity_inputs():
+    for name, flat, delta in dc.parity_inputs():
         assert predict_in_kernel(flat, delta) == 1, name
     for name, flat, delta, _ in golden_inputs():
         assert predict_in_kernel(flat, delta) == 1, name
@@ -259,8 +254,7 @@ BATCH_LDS_CANDS = 496  # determinize.hip: the levels whose scratch WFST_DETERMIN
 
 
 def limit_case(name):
-    import test_determinize_limits as tl
-    return tl.case(name)[0]
+    return dc.case(name)[0]
 
 
 def test_in_kernel_prediction_of_the_limit_items():
@@ -297,7 +291,7 @@ def test_parity_with_oracle_and_single_call(gpu_ctx, oracle, monkeypatch, scratc
     import rustfst_amd
     monkeypatch.setenv("WFST_DETERMINIZE_BATCH_SCRATCH", scratch)
     groups = {}
-    for name, flat, delta in td.parity_inputs():
+    for name, flat, delta in dc.parity_inputs():
         groups.setdefault((delta, 0), []).append((name, flat, True))
     for name, flat, delta, det_type in golden_inputs():
         groups.setdefault((delta, det_type), []).append((name, flat, False))
@@ -349,8 +343,8 @@ def test_mixed_batch(gpu_ctx, monkeypatch, scratch):
     import rustfst_amd
     monkeypatch.setenv("WFST_DETERMINIZE_BATCH_SCRATCH", scratch)
     rng = np.random.default_rng(8)
-    tiny = td.random_acceptor(rng, 6, 3, 2, acyclic=True)
-    flats = [tiny, empty_flat(), no_start(), collision_flat(), tiny, inputs.diamond_chain(2000), cyclic_unweighted()]
+    tiny = dc.random_acceptor(rng, 6, 3, 2, acyclic=True)
+    flats = [tiny, empty_flat(ACCEPTOR), no_start(), collision_flat(), tiny, inputs.diamond_chain(2000), cyclic_unweighted()]
     devs = [to_device(f, gpu_ctx) for f in flats]
     devs[4] = devs[0]  # the same handle twice
     got, flags = _batch(devs, gpu_ctx)
@@ -361,8 +355,8 @@ def test_mixed_batch(gpu_ctx, monkeypatch, scratch):
     for k, (g, dev) in enumerate(zip(got, devs)):
         same(g, dev.determinize().to_flat(), f"item {k} {scratch}")
     # the neighbours of the fallback item against the restatement as well
-    same(got[2], td.determinize_ref(flats[2]), "no start state")
-    same(got[4], td.determinize_ref(tiny), "after the fallback item")
+    same(got[2], determinize_ref(flats[2]), "no start state")
+    same(got[4], determinize_ref(tiny), "after the fallback item")
     assert got[1]["n_states"] == 0 and got[2]["n_states"] == 0 and got[5]["n_states"] == 2001
 
 
@@ -372,7 +366,7 @@ def test_arena_growth(gpu_ctx, monkeypatch, scratch):
     import rustfst_amd
     monkeypatch.setenv("WFST_DETERMINIZE_BATCH_SCRATCH", scratch)
     rng = np.random.default_rng(40)
-    flats = [td.f32_weights(rng, td.random_acceptor(rng, 40, 4, 3, acyclic=True)) for _ in range(12)]
+    flats = [dc.f32_weights(rng, dc.random_acceptor(rng, 40, 4, 3, acyclic=True)) for _ in range(12)]
     devs = [to_device(f, gpu_ctx) for f in flats]
     plain, flags0 = _batch(devs, gpu_ctx)
     monkeypatch.setenv("WFST_DETERMINIZE_BATCH_ARENA", "min")
@@ -380,22 +374,22 @@ def test_arena_growth(gpu_ctx, monkeypatch, scratch):
     st = rustfst_amd.determinize_batch_stats(gpu_ctx)
     assert st["launches"] > 1 and flags == flags0 == [1] * len(flats)
     for k, (f, g, p) in enumerate(zip(flats, got, plain)):
-        same(g, td.determinize_ref(f), f"item {k} grown")
+        same(g, determinize_ref(f), f"item {k} grown")
         same(g, p, f"item {k} grown vs not")
 
 
 @pytest.mark.gpu
 def test_batch_sizes(gpu_ctx):
     rng = np.random.default_rng(300)
-    flats = [td.random_acceptor(rng, int(rng.integers(2, 41)), 4, 2 + k % 3, acyclic=True) for k in range(300)]
+    flats = [dc.random_acceptor(rng, int(rng.integers(2, 41)), 4, 2 + k % 3, acyclic=True) for k in range(300)]
     devs = [to_device(f, gpu_ctx) for f in flats]
     got, flags = _batch(devs[:1], gpu_ctx)
     assert flags == [1]
-    same(got[0], td.determinize_ref(flats[0]), "n = 1")
+    same(got[0], determinize_ref(flats[0]), "n = 1")
     got, flags = _batch(devs, gpu_ctx)  # more workgroups than compute units
     assert flags == [1] * 300
     for k, (f, g) in enumerate(zip(flats, got)):
-        same(g, td.determinize_ref(f), f"item {k} of 300")
+        same(g, determinize_ref(f), f"item {k} of 300")
 
 
 def _same_dist(got, exp, what):
@@ -407,9 +401,9 @@ def _same_dist(got, exp, what):
 def test_distances_single_and_batch(gpu_ctx):
     import rustfst_amd
     rng = np.random.default_rng(55)
-    flats = [td.random_acceptor(rng, 35, 4, 3, weight_grid=1, max_w=6, acyclic=True),
-             td.f32_weights(rng, td.random_acceptor(rng, 40, 4, 3, acyclic=True)),
-             cyclic_unweighted(), td.random_acceptor(rng, 30, 3, 3, p_eps_i=0.3, acyclic=True), no_start(), collision_flat()]
+    flats = [dc.random_acceptor(rng, 35, 4, 3, weight_grid=1, max_w=6, acyclic=True),
+             dc.f32_weights(rng, dc.random_acceptor(rng, 40, 4, 3, acyclic=True)),
+             cyclic_unweighted(), dc.random_acceptor(rng, 30, 3, 3, p_eps_i=0.3, acyclic=True), no_start(), collision_flat()]
     devs = [to_device(f, gpu_ctx) for f in flats]
 
     def in_dists(kind):
@@ -465,9 +459,9 @@ def test_ko_leaves_nothing_behind(gpu_ctx, monkeypatch):
     import rustfst_amd
     from rustfst_amd import _lib
     rng = np.random.default_rng(6)
-    goods = [td.random_acceptor(rng, 6, 2, 2, acyclic=True) for _ in range(5)]
+    goods = [dc.random_acceptor(rng, 6, 2, 2, acyclic=True) for _ in range(5)]
     for f in goods:
-        assert td.determinize_ref(f)["n_states"] <= 64
+        assert determinize_ref(f)["n_states"] <= 64
     devs = [to_device(f, gpu_ctx) for f in goods]
     good, _ = _batch(devs, gpu_ctx)
     assert rustfst_amd.determinize_batch_stats(gpu_ctx)["launches"] >= 1  # the sentinel the KO below must clear
@@ -517,13 +511,13 @@ def test_ko_leaves_nothing_behind(gpu_ctx, monkeypatch):
 def test_python_surface_round_trip(gpu_ctx):
     import rustfst_amd
     rng = np.random.default_rng(12)
-    flats = [td.random_acceptor(rng, 12, 3, 3, acyclic=True) for _ in range(4)]
+    flats = [dc.random_acceptor(rng, 12, 3, 3, acyclic=True) for _ in range(4)]
     vs = [to_device(f, gpu_ctx).to_vector_fst() for f in flats]
     devs = [v.to_device(gpu_ctx) for v in vs]
     outs = rustfst_amd.determinize_batch(devs)
     assert len(outs) == 4 and all(isinstance(o, rustfst_amd.DeviceFst) for o in outs)
     for f, v, o in zip(flats, vs, outs):
-        same(o.to_flat(), td.determinize_ref(f), "determinize_batch", props=False)
+        same(o.to_flat(), determinize_ref(f), "determinize_batch", props=False)
         back = o.to_vector_fst()
         assert back == rustfst_amd.determinize(v) and back.num_states() == o.num_states
         assert back.to_device(gpu_ctx).to_flat()["n_states"] == o.num_states

@@ -16,6 +16,7 @@ import pytest
 import rustfst_amd
 from rustfst_amd import ComposeConfig, ComposeFilter, ShortestPathConfig, Tr, VectorFst, synth
 from helpers import FILTERS, assert_flat_identical, flat_matches_spec, random_fst_flat, to_device, to_oracle
+from small_path_cases import predict_nbest
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -1238,9 +1239,8 @@ def test_nshortest_batch_wave_kernel_vs_oracle(gpu_ctx, oracle, device, monkeypa
         got = rustfst_amd.shortest_path_batch(devs, ShortestPathConfig(nshortest=n))
         n_dev = int(rustfst_amd.default_context().stats()["nbest_device_problems"])
         if device == "1":
-            # the routing rules and the search's tree growth, restated in test_small_path_limits: every input but the empty
+            # the routing rules and the search's tree growth, restated in small_path_cases: every input but the empty
             # one is offered (one without a reachable final state is answered by the kernel too) and none outgrows T = 2048
-            from test_small_path_limits import predict_nbest
             want = predict_nbest(flats, n)
             assert want["nbest_in_kernel"] == len(flats) - 1 and want["nbest_tree_full"] == 0
             assert n_dev == want["nbest_in_kernel"], n_dev

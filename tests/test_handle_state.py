@@ -25,9 +25,10 @@ import rustfst_amd
 from rustfst_amd import (ClosureType, ComposeConfig, DeviceFst, ProjectType, PushWeightsConfig, ReweightType,
                          ShortestPathConfig, synth)
 from oracle import model
-from helpers import (assert_flat_identical, linear_transducer_flat, one_sided_eps_transducer, random_fst_flat, to_device,
-                     to_oracle, walk_labels)
-import test_push_weights as pw
+from oracle.model import push_ref, reverse_len_rule
+from helpers import (_oracle_dist, assert_flat_identical, linear_transducer_flat, one_sided_eps_transducer,
+                     random_fst_flat, to_device, to_oracle, walk_labels)
+import minimize_cases as mc
 
 ACCEPTOR = model.ACCEPTOR
 NOT_I_SORTED, NOT_O_SORTED = model.NOT_I_LABEL_SORTED, model.NOT_O_LABEL_SORTED
@@ -170,7 +171,7 @@ def dev_O3(h, inp, mp):  # rev_fst, plans
 def ora_O3(m, inp):
     can = m.fresh().shortest_path_canonical()
     rdist = m.fresh().reverse().shortest_distance()[1:]
-    return [can.distance, can.hops, rdist, ("len", pw.reverse_len_rule(m.flat))]
+    return [can.distance, can.hops, rdist, ("len", reverse_len_rule(m.flat))]
 
 
 PUSHES = ((ReweightType.REWEIGHT_TO_INITIAL, False), (ReweightType.REWEIGHT_TO_FINAL, True))
@@ -180,11 +181,11 @@ def dev_O4(h, inp, mp):  # rev_fst, structural searches
     return [h.push_weights(rt, PushWeightsConfig(remove_total_weight=rm)).to_flat() for rt, rm in PUSHES]
 
 
-def ora_O4(m, inp):  # the restatement of tests/test_push_weights.py on the oracle's distances
+def ora_O4(m, inp):  # the restatement of oracle/model/push.py on the oracle's distances
     out = []
     for rt, rm in PUSHES:
         to_final = rt == ReweightType.REWEIGHT_TO_FINAL
-        out.append(model.to_flat(pw.push_ref(m.flat, pw._oracle_dist(m.oracle, m.flat, to_final), to_final, rm)))
+        out.append(model.to_flat(push_ref(m.flat, _oracle_dist(m.oracle, m.flat, to_final), to_final, rm)))
     return out
 
 
@@ -691,12 +692,11 @@ def _negative_potentials(flat):
 
 def _producers(ctx, oracle, mp):
     """(name, result handle) of every way a handle is born; S-sized inputs, acyclic acceptors where the producer needs them"""
-    import test_minimize as tm
     small = _small_inputs_cached(oracle)
     s, s2 = small[f"S{S_SEEDS[0]}"]["flat"], small[f"S{S_SEEDS[1]}"]["flat"]
     rng = np.random.default_rng(90_000)
     acc = [_acyclic_acceptor(rng) for _ in range(4)]
-    tries = [tm.trie_flat(rng, 12, 4, 6) for _ in range(3)]
+    tries = [mc.trie_flat(rng, 12, 4, 6) for _ in range(3)]
     x, y = small[f"S{S_SEEDS[0]}"]["x_sorted"], small[f"S{S_SEEDS[0]}"]["y_sorted"]
     dev = lambda f: to_device(f, ctx)  # noqa: E731
     mp.setenv("WFST_COMPOSE_PATH", "wave")

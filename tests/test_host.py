@@ -336,43 +336,23 @@ def test_slab_carver(tmp_path):
     assert " 0 mismatches" in out.stdout
 
 
-# what still imports a test module: the restatement drivers and the input families that have not moved to oracle/model/,
-# helpers.py or inputs.py yet.  The list only shrinks: an edge that is not here fails, and so does an entry that is gone.
-STILL_IMPORTS_A_TEST_MODULE = {
-    "tests/test_compose_limits.py": "test_small_path_limits",
-    "tests/test_determinize_batch.py": "test_determinize test_determinize_limits",
-    "tests/test_determinize_limits.py": "test_determinize",
-    "tests/test_gpu_parity.py": "test_small_path_limits",
-    "tests/test_handle_state.py": "test_minimize test_push_weights",
-    "tests/test_minimize.py": "test_push_weights",
-    "tests/test_minimize_batch.py": "test_determinize test_minimize",
-    "tests/test_minimize_limits.py": "test_minimize",
-    "tests/test_optimize.py": "test_determinize test_minimize",
-    "tests/test_optimize_batch.py": "test_minimize test_optimize",
-    "tests/test_push_limits.py": "test_push_weights",
-    "tests/test_rational_ops.py": "test_minimize test_optimize",
-    "tests/test_rm_epsilon_batch.py": "test_determinize test_minimize test_rational_ops test_rm_epsilon",
-    "tests/test_string_run.py": "test_compose_limits",
-    "tests/test_string_run_lean.py": "test_compose_limits test_string_run",
-    "tests/test_top_sort.py": "test_minimize test_optimize test_rational_ops",
-    "tests/test_top_sort_handle.py": "test_rational_ops test_top_sort",
-    "tests/test_top_sort_limits.py": "test_rational_ops test_top_sort",
-    "tests/test_tr_sum_batch.py": "test_optimize",
-    "tools/minimize_timing.py": "test_minimize",
-}
-
-
 def test_nobody_imports_a_test_module():
-    """what more than one module needs lives in oracle/model/ (the reference restated), helpers.py or inputs.py: a test
-    module is nobody's library, under tests/ and under tools/, but for the edges listed above"""
+    """what more than one module needs lives in oracle/model/ (the reference restated), helpers.py, inputs.py or a
+    <operation>_cases.py: a test module is nobody's library, under tests/ and under tools/, by an import statement, by
+    importlib or by __import__.  There is no list of exceptions.  oracle/model/ in turn imports neither the library under
+    test nor anything from tests/."""
     import glob
     found = {}
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "*.py")) + glob.glob(os.path.join(ROOT, "tools", "*.py"))):
         with open(path) as f:
-            mods = set(re.findall(r"^\s*(?:import\s+|from\s+)(test_\w+)", f.read(), re.M))
+            text = f.read()
+        mods = set(re.findall(r"^\s*(?:import\s+|from\s+)(test_\w+)", text, re.M))
+        mods |= set(re.findall(r"""(?:import_module|__import__)\(\s*["'](test_\w*)""", text))
         if mods:
             found[os.path.relpath(path, ROOT).replace(os.sep, "/")] = " ".join(sorted(mods))
-    assert found == STILL_IMPORTS_A_TEST_MODULE
-    for module in ("oracle/model/weight.py", "oracle/model/props.py", "oracle/model/fst.py", "oracle/model/algorithms.py"):
-        with open(os.path.join(ROOT, module)) as f:
-            assert not re.search(r"^\s*(import|from)\s+(rustfst_amd|helpers|inputs|test_)", f.read(), re.M), module
+    assert found == {}
+    modules = sorted(glob.glob(os.path.join(ROOT, "oracle", "model", "*.py")))
+    assert len(modules) >= 4
+    for module in modules:
+        with open(module) as f:
+            assert not re.search(r"^\s*(import|from)\s+(rustfst_amd|helpers|inputs|\w+_cases|test_)", f.read(), re.M), module

@@ -1,6 +1,6 @@
 """minimize / minimize_with_config of input-deterministic acyclic acceptors (wfst_minimize): the C-ABI surface without a
-GPU, a literal sequential Python restatement of rustfst's minimize_with_config (AcyclicMinimizer branch; written out
-below) checked against the hand-derived K16 known answers, the survivor rule checked against it, and on the device
+GPU, a literal sequential Python restatement of rustfst's minimize_with_config (AcyclicMinimizer branch;
+oracle/model/minimize.py) checked against the hand-derived K16 known answers, the survivor rule checked against it, and on the device
 parity with the restatement in every regime, closed-form answers at scale, invariants and error handling.
 
 Bound on weights (used by the invariants): push_weights(ToInitial) replaces w by (w + d[t]) - d[s]; along a path these
@@ -11,7 +11,6 @@ L arcs and one final weight therefore moves by at most
     weight_bound(L, W, delta) = (L + 1) * (delta / 2 + 8 * 2^-24 * max(1, 2 W))."""
 import ctypes as C
 import inspect
-import json
 import os
 import re
 
@@ -21,371 +20,17 @@ import pytest
 from rustfst_amd._lib import TR_DTYPE
 
 from oracle import model
-from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ADD_SUPER_FINAL, ALL, ARCSORT, ARC_RELEVANT, COACCESSIBLE,
-                          CYCLIC, EPSILONS, F32, INF, INITIAL_ACYCLIC, I_DETERMINISTIC, I_EPSILONS, I_LABEL_INVARIANT,
-                          I_LABEL_SORTED, KSHORTESTDELTA, NOT_ACCEPTOR, NOT_I_DETERMINISTIC, NOT_I_LABEL_SORTED,
-                          NOT_O_LABEL_SORTED, NOT_TOP_SORTED, NO_EPSILONS, NO_I_EPSILONS, NO_O_EPSILONS,
-                          O_DETERMINISTIC, O_EPSILONS, O_LABEL_INVARIANT, O_LABEL_SORTED, RM_SUPER_FINAL, TOP_SORTED,
-                          UNWEIGHTED, Unsupported, WEIGHTED, WEIGHT_INVARIANT, compute_and_update, connect, flat_to_fst,
-                          fst_to_flat, is_cyclic, known, make_flat, p_add_tr, quantize, rm_final_epsilon, tr_map,
-                          tr_unique, wkey)
-from helpers import ROOT, assert_flat_identical, ko_message, to_device
-import test_push_weights as pw
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, CYCLIC, EPSILONS, F32, INF, INITIAL_ACYCLIC,
+                          I_DETERMINISTIC, I_EPSILONS, I_LABEL_SORTED, KSHORTESTDELTA, MSG_NONDET, NOT_ACCEPTOR,
+                          NOT_I_DETERMINISTIC, NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, NOT_TOP_SORTED, NO_EPSILONS,
+                          NO_I_EPSILONS, NO_O_EPSILONS, O_DETERMINISTIC, O_EPSILONS, O_LABEL_SORTED, TOP_SORTED,
+                          UNWEIGHTED, Unsupported, WEIGHTED, acyclic_partition, connect, flat_to_fst, fst_depth,
+                          make_flat, minimize_ref)
+from helpers import ROOT, assert_flat_identical, golden_flat, ko_message, to_device
+from minimize_cases import (accepts, assert_idempotent, blow_up, cfg_of, check_invariants, closed_form_base,
+                            far_apart_cases, golden_cases, no_start_cases, random_cases, random_dag, trie_flat)
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "k16_minimize.json")
 PATHS = ("narrow", "wide", "auto")
-MSG_NONDET = "Refusing to minimize a non-deterministic FST with allow_nondet = false"
-
-
-# ---------------------------------------------------------------- the restatement
-class Partition:  # partition.rs:6-92
-    def __init__(self, n):
-        self.cls = [None] * n
-        self.nxt = [-1] * n
-        self.prv = [-1] * n
-        self.head = []
-
-    def add_class(self):
-        self.head.append(-1)
-        return len(self.head) - 1
-
-    def add(self, e, c):
-        h = self.head[c]
-        if h >= 0:
-            self.prv[h] = e
-        self.head[c] = e
-        self.cls[e] = c
-        self.nxt[e] = h
-        self.prv[e] = -1
-
-    def move_element(self, e, c):
-        p, nx, old = self.prv[e], self.nxt[e], self.cls[e]
-        if p >= 0:
-            self.nxt[p] = nx
-        else:
-            self.head[old] = nx
-        if nx >= 0:
-            self.prv[nx] = p
-        self.add(e, c)
-
-    def members(self, c):
-        e = self.head[c]
-        while e >= 0:
-            yield e
-            e = self.nxt[e]
-
-
-def fst_depth(fst):  # minimize.rs:269-304 (an explicit stack in place of the recursion; same post-order)
-    rows = fst["rows"]
-    heights = []
-    visited = set()
-    stack = [(fst["start"], 0)]
-    visited.add(fst["start"])
-    while stack:
-        s, i = stack[-1]
-        while len(heights) <= s:
-            heights.append(-1)
-        if i < len(rows[s]):
-            stack[-1] = (s, i + 1)
-            t = rows[s][i][3]
-            if t not in visited:
-                visited.add(t)
-                stack.append((t, 0))
-        else:
-            stack.pop()
-            heights[s] = max([0] + [1 + heights[tr[3]] for tr in rows[s]])
-    return heights
-
-
-def acyclic_partition(fst):
-    """AcyclicMinimizer::new (minimize.rs:306-387): classes by height, refined height by height; two states compare Equal
-    when StateComparator finds neither below the other (:389-456): final weight (exact), arc count, positionally
-    (ilabel, class of nextstate)."""
-    heights = fst_depth(fst)
-    part = Partition(len(heights))
-    for _ in range(max(heights) + 1):
-        part.add_class()
-    for s, h in enumerate(heights):
-        part.add(s, h)
-    n_height = len(part.head)
-    for h in range(n_height):
-        def key(s):
-            f = fst["finals"][s]
-            return (float(INF if f is None else f), len(fst["rows"][s]), tuple((tr[0], part.cls[tr[3]]) for tr in fst["rows"][s]))
-        members = list(part.members(h))
-        equiv = {key(members[0]): h}
-        for e in members[1:]:
-            k = key(e)
-            if k not in equiv:
-                equiv[k] = part.add_class()
-        target = {s: equiv[key(s)] for s in members}  # (the keys read the partition before any move of this height)
-        for s in members:
-            if part.cls[s] != target[s]:
-                part.move_element(s, target[s])
-    return part
-
-
-def merge_states(part, fst):  # minimize.rs:213-266
-    rows = fst["rows"]
-    state_map = [next(part.members(c)) for c in range(len(part.head))]
-    p = fst["props"]
-    for c in range(len(part.head)):
-        for s in part.members(c):
-            if s == state_map[c]:
-                for tr in rows[s]:
-                    p &= ARC_RELEVANT  # set_nextstate_unchecked (trs_iter_mut.rs:222-225, 293-305)
-                    tr[3] = state_map[part.cls[tr[3]]]
-            else:
-                for tr in [list(t) for t in rows[s]]:
-                    tr[3] = state_map[part.cls[tr[3]]]
-                    dst = rows[state_map[c]]
-                    dst.append(tr)
-                    p = p_add_tr(p, state_map[c], tr, dst[-2] if len(dst) > 1 else None)
-    fst["start"] = state_map[part.cls[fst["start"]]]
-    fst["props"] = model.p_set_start(p)
-    connect(fst)
-
-
-def acceptor_minimize(fst, seen=None):  # minimize.rs:181-211
-    """seen (a dict): receives T, a copy of the connected, label-sorted machine the partition is computed on (what
-    minimize.hip's run_core refines), and part, its Partition"""
-    props = compute_and_update(fst, ACCEPTOR | UNWEIGHTED | ACYCLIC)
-    if props & (ACCEPTOR | UNWEIGHTED) != ACCEPTOR | UNWEIGHTED:
-        raise Unsupported("FST is not an unweighted acceptor")
-    if not props & ACYCLIC:
-        raise Unsupported("cyclic inputs are not supported")  # (this project: a cycle anywhere, before connect)
-    connect(fst)
-    if not fst["rows"]:
-        return
-    for row in fst["rows"]:  # tr_sort(ILabelCompare): stable
-        row.sort(key=lambda t: t[0])
-    p = (fst["props"] & ARCSORT) | I_LABEL_SORTED
-    if fst["props"] & ACCEPTOR:
-        p |= O_LABEL_SORTED
-    fst["props"] = p
-    part = acyclic_partition(fst)
-    if seen is not None:
-        seen["T"] = dict(rows=[[list(tr) for tr in row] for row in fst["rows"]], finals=list(fst["finals"]),
-                         start=fst["start"], props=fst["props"])
-        seen["part"] = part
-    merge_states(part, fst)
-    tr_unique(fst)
-
-
-def rdist_dag(flat):
-    """reverse shortest distances of an acyclic FST in f32: d[s] = min(final[s], min over arcs (w + d[next])), the value the
-    relaxation converges to (f32 addition is monotone); +inf for a state that reaches no final state"""
-    n = flat["n_states"]
-    off, arcs, fin = flat["offsets"], flat["arcs"], flat["finals"]
-    d = [None] * n
-    for root in range(n):
-        if d[root] is not None:
-            continue
-        stack = [(root, 0)]
-        while stack:
-            s, i = stack[-1]
-            b, e = int(off[s]), int(off[s + 1])
-            if b + i < e:
-                stack[-1] = (s, i + 1)
-                t = int(arcs["nextstate"][b + i])
-                if d[t] is None and all(t != q for q, _ in stack):
-                    stack.append((t, 0))
-            else:
-                stack.pop()
-                best = F32(fin[s])
-                for a in arcs[b:e]:
-                    v = model.times(F32(a["weight"]), d[int(a["nextstate"])])
-                    best = v if v < best else best
-                d[s] = best
-    return d
-
-
-def minimize_ref(flat, delta=KSHORTESTDELTA, allow_nondet=False, partition_out=None):
-    """minimize_with_config (minimize.rs:92-176), statement by statement, for the branch this project supports; raises
-    Unsupported with the KO message otherwise.  Returns flat arrays.  partition_out (a dict): see acceptor_minimize (in the
-    weighted branch T is the encoded machine with its superfinal state)."""
-    fst = flat_to_fst(flat)
-    props = compute_and_update(fst, ACCEPTOR | I_DETERMINISTIC | WEIGHTED | UNWEIGHTED)
-    if not props & I_DETERMINISTIC and not allow_nondet:
-        raise Unsupported(MSG_NONDET)
-    if not props & ACCEPTOR:
-        raise Unsupported("transducers are not supported")
-    if not props & I_DETERMINISTIC:
-        raise Unsupported("non-deterministic inputs are not supported")
-    if not known(fst["props"]) & ACYCLIC:
-        if is_cyclic(flat):
-            raise Unsupported("cyclic inputs are not supported")
-    elif fst["props"] & CYCLIC:
-        raise Unsupported("cyclic inputs are not supported")
-    if props & WEIGHTED:
-        # (without a start state push still reweights, every tr_map below returns at once, and acceptor_minimize decides
-        # from the pushed content: the empty FST, or "FST is not an unweighted acceptor")
-        # push_weights_with_config(ToInitial, default.with_delta(delta)) (push.rs:89-118)
-        cur = fst_to_flat(fst)
-        dist = rdist_dag(cur)[:pw.reverse_len_rule(cur)]
-        fst = pw.push_ref(cur, dist, False, False)
-        fst["props"] &= ALL
-        # tr_map(QuantizeMapper(delta)) (quantize_mapper.rs)
-        def q_arc(tr):
-            tr[2] = quantize(tr[2], delta)
-
-        def q_fin(ftr):
-            ftr[2] = quantize(ftr[2], delta)
-        tr_map(fst, q_arc, q_fin, False, lambda p: p & WEIGHT_INVARIANT)
-        # encode(EncodeWeightsAndLabels) (encode_static.rs): one table for arc and final tuples, in scan order
-        table, tuples = {}, []
-
-        def enc(il, ol, w):
-            k = (il, ol, wkey(w))
-            if k not in table:
-                table[k] = len(tuples) + 1
-                tuples.append((il, ol, F32(w)))
-            return table[k]
-
-        def e_arc(tr):
-            lab = enc(tr[0], tr[1], tr[2])
-            tr[0], tr[1], tr[2] = lab, lab, F32(0.0)
-
-        def e_fin(ftr):
-            lab = enc(ftr[0], ftr[1], ftr[2])
-            ftr[0], ftr[1], ftr[2] = lab, lab, F32(0.0)
-        enc_mask = I_LABEL_INVARIANT & O_LABEL_INVARIANT & WEIGHT_INVARIANT & ADD_SUPER_FINAL
-        tr_map(fst, e_arc, e_fin, True, lambda p: p & enc_mask)
-        acceptor_minimize(fst, partition_out)
-        # decode (decode_static.rs): labels and weights back, then rm_final_epsilon
-        def d_arc(tr):
-            il, ol, w = tuples[tr[0] - 1]
-            tr[0], tr[1], tr[2] = il, ol, w
-        dec_mask = I_LABEL_INVARIANT & O_LABEL_INVARIANT & WEIGHT_INVARIANT & RM_SUPER_FINAL
-        tr_map(fst, d_arc, lambda ftr: None, False, lambda p: p & dec_mask)
-        rm_final_epsilon(fst)
-    else:
-        acceptor_minimize(fst, partition_out)
-    return fst_to_flat(fst)
-
-
-def trie_flat(rng, n_words, sigma, max_len, weighted=True, props=ACCEPTOR):
-    """a trie of random words over `sigma` labels; arcs in insertion order (not label order).  Weights depend on the
-    label alone (plus a rare odd one), so that many suffixes carry equal pushed weights and merge."""
-    rows, finals = [[]], [INF]
-    for _ in range(n_words):
-        s = 0
-        for _ in range(int(rng.integers(1, max_len + 1))):
-            lab = int(rng.integers(1, sigma + 1))
-            nxt = next((a[3] for a in rows[s] if a[0] == lab), None)
-            if nxt is None:
-                nxt = len(rows)
-                rows.append([])
-                finals.append(INF)
-                w = float(lab % 3) if weighted else 0.0
-                if weighted and rng.random() < 0.05:
-                    w += float(rng.integers(1, 4))
-                rows[s].append((lab, lab, w, nxt))
-            s = nxt
-        finals[s] = float(rng.integers(0, 2)) if weighted else 0.0
-    return make_flat(len(rows), 0, rows, finals, props)
-
-
-def random_dag(rng, n, sigma, weighted=True, props=ACCEPTOR, real=False):
-    """a random deterministic acyclic acceptor (distinct labels per state, arcs forward), untrimmed"""
-    rows, finals = [], []
-    for s in range(n):
-        labs = rng.permutation(np.arange(1, sigma + 1))[:int(rng.integers(0, sigma + 1))]
-        row = []
-        for lab in labs:
-            if s + 1 >= n:
-                break
-            t = int(rng.integers(s + 1, min(n, s + 6)))
-            w = (float(F32(rng.random() * 4)) if real else float(rng.integers(0, 3))) if weighted else 0.0
-            row.append((int(lab), int(lab), w, t))
-        rows.append(row)
-        f = (float(F32(rng.random())) if real else float(rng.integers(0, 2))) if weighted else 0.0
-        finals.append(f if rng.random() < 0.3 or s == n - 1 else INF)
-    return make_flat(n, 0, rows, finals, props)
-
-
-def random_cases(seed, count):
-    rng = np.random.default_rng(seed)
-    out = []
-    for i in range(count):
-        kind = i % 4
-        if kind == 0:
-            out.append(("trie-w", trie_flat(rng, int(rng.integers(5, 60)), int(rng.integers(3, 6)), 6, True)))
-        elif kind == 1:
-            out.append(("trie-u", trie_flat(rng, int(rng.integers(5, 60)), int(rng.integers(3, 6)), 6, False)))
-        elif kind == 2:
-            out.append(("dag-w", random_dag(rng, int(rng.integers(2, 60)), 3, True)))
-        else:
-            out.append(("dag-u", random_dag(rng, int(rng.integers(2, 60)), 3, False, props=0)))
-    return out
-
-
-def golden_cases():
-    with open(GOLDEN) as f:
-        return json.load(f)["cases"]
-
-
-def golden_flat(c, key="input"):
-    g = c[key]
-    n = g["n_states"]
-    rows = [[] for _ in range(n)]
-    for s, il, ol, w, ns in g["arcs"]:
-        rows[s].append((il, ol, w, ns))
-    finals = [INF] * n
-    for s, w in g["finals"]:
-        finals[s] = w
-    return make_flat(n, g["start"], rows, finals, int(g["props"], 16))
-
-
-def cfg_of(c):
-    return c.get("delta", KSHORTESTDELTA), bool(c.get("allow_nondet", False))
-
-
-def accepts(flat, labels):
-    """weight of the string in a deterministic acceptor, or None"""
-    if flat["start"] is None:
-        return None
-    s, w = flat["start"], F32(0.0)
-    off, arcs = flat["offsets"], flat["arcs"]
-    for lab in labels:
-        seg = arcs[off[s]:off[s + 1]]
-        hit = np.nonzero(seg["ilabel"] == lab)[0]
-        if not hit.size:
-            return None
-        w = F32(w + seg["weight"][hit[0]])
-        s = int(seg["nextstate"][hit[0]])
-    return None if not np.isfinite(flat["finals"][s]) else float(F32(w + flat["finals"][s]))
-
-
-def label_sorted(flat):
-    """the same FST with every state's arcs in label order"""
-    arcs = flat["arcs"].copy()
-    off = flat["offsets"]
-    for s in range(flat["n_states"]):
-        seg = arcs[off[s]:off[s + 1]]
-        arcs[off[s]:off[s + 1]] = seg[np.argsort(seg["ilabel"], kind="stable")]
-    return dict(flat, arcs=arcs)
-
-
-def assert_idempotent(again, got, what):
-    """minimize(minimize(x)) against minimize(x).  Exactly equal for the unweighted branch.  In the weighted branch the
-    reference orders a state's arcs by the first occurrence of their (label, weight) tuples over the UNTRIMMED input of that
-    call; the second call no longer sees the states the first one removed, so that order may differ (the restatement shows
-    it, test_generator_shrinks_and_restatement_is_idempotent): there the two are equal once every state's arcs are put
-    in label order — same states, same numbering, same weights.
-    The property word is left out: the result of the weighted branch may have no weight left (then the second call takes
-    the unweighted branch, whose word differs), and an empty result keeps what its input's content gave it; the word of
-    the second call is checked against the restatement instead."""
-    if got["n_states"] == 0:
-        assert again["n_states"] == 0 and again["start"] is None, what
-    elif np.array_equal(again["arcs"]["ilabel"], got["arcs"]["ilabel"]):
-        assert_flat_identical(again, got, what, check_props=False)
-    else:
-        assert_flat_identical(label_sorted(again), label_sorted(got), what, check_props=False)
-
-
-def weight_bound(length, wmax, delta):
-    return (length + 1) * (delta / 2 + 8 * 2.0 ** -24 * max(1.0, 2 * wmax))
 
 
 # ================================================================ CPU
@@ -510,25 +155,6 @@ def test_restatement_errors():
         minimize_ref(make_flat(2, 0, [[(1, 1, 0.0, 1)], [(1, 1, 0.0, 0)]], [INF, 0.0]))
 
 
-def no_start_cases():
-    """weighted inputs without a start state: (flat, None) where pushing leaves no weight (the reference returns the empty
-    FST), (flat, message) where a pushed weight stays (its acceptor_minimize bails)"""
-    gone = make_flat(2, None, [[(1, 1, 1.0, 1)], []], [INF, 0.0], 0)  # d = [1, 0]: the arc becomes (1 + 0) - 1 = 0
-    gone_known = dict(gone, props=ACCEPTOR | I_DETERMINISTIC | O_DETERMINISTIC | WEIGHTED | ACYCLIC | INITIAL_ACYCLIC)
-    stays = make_flat(2, None, [[(1, 1, 1.0, 1), (2, 2, 3.0, 1)], []], [INF, 0.0], ACCEPTOR)  # d = [1, 0]: arcs 0 and 2
-    return [(gone, None), (gone_known, None), (stays, "FST is not an unweighted acceptor")]
-
-
-def far_apart_cases():
-    """the unweighted branch compares no arc weight: states 1 and 2 merge although their arcs weigh -0.0009 / +0.0009
-    (each within KDELTA of one, 0.0018 apart), or 0 / 0.5 under a stored UNWEIGHTED word"""
-    rows = [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(3, 3, -0.0009, 3)], [(3, 3, 0.0009, 3)], []]
-    a = make_flat(4, 0, rows, [INF, INF, INF, 0.0], 0)
-    rows = [[(1, 1, 0.0, 1), (2, 2, 0.0, 2)], [(3, 3, 0.0, 3)], [(3, 3, 0.5, 3)], []]
-    b = make_flat(4, 0, rows, [INF, INF, INF, 0.0], ACCEPTOR | I_DETERMINISTIC | UNWEIGHTED | ACYCLIC | INITIAL_ACYCLIC)
-    return [a, b]
-
-
 def test_restatement_without_a_start_state():
     for flat, message in no_start_cases():
         if message is None:
@@ -559,79 +185,6 @@ def dev_minimize(flat, ctx, delta=None, allow_nondet=False):
     import rustfst_amd
     cfg = None if delta is None and not allow_nondet else rustfst_amd.MinimizeConfig(delta, allow_nondet)
     return to_device(flat, ctx).minimize(cfg)
-
-
-def finite_max(*arrays):
-    m = 0.0
-    for a in arrays:
-        a = np.abs(np.asarray(a, dtype=np.float64))
-        a = a[np.isfinite(a)]
-        if a.size:
-            m = max(m, float(a.max()))
-    return m
-
-
-def check_invariants(src_flat, got_dev, delta, ctx, rng, what, idempotent=True):
-    """On a device result `got_dev` of minimizing `src_flat`: deterministic, acyclic, connected; the start's shortest
-    distance and sampled strings keep their weight within the bound; minimizing again equals the restatement of that
-    second call and (idempotent) changes nothing but, in the weighted branch, the arc order (assert_idempotent).
-    The bound: weight_bound(L, W, delta) of the module docstring in the weighted branch, with W taken from the reverse
-    distances, arc and final weights of the source and of the result.  The unweighted branch neither pushes nor quantizes:
-    a merged state takes its survivor's arc weights, which tr_unique found within KDELTA of its own, and final weights are
-    compared exactly, so a string with L arcs moves by at most L * KDELTA."""
-    got = got_dev.to_flat()
-    n = got["n_states"]
-    if n == 0 or src_flat["start"] is None:
-        return
-    off, arcs = got["offsets"], got["arcs"]
-    for s in range(min(n, 2000)):
-        labs = arcs["ilabel"][off[s]:off[s + 1]]
-        assert len(set(labs.tolist())) == len(labs), f"{what}: state {s} is not deterministic"
-    acc, co, cyc, _ = model.graph_facts(got)
-    assert acc and co and not cyc, what
-    d_in = to_device(src_flat, ctx).shortest_distance(reverse=True)
-    d_out = got_dev.shortest_distance(reverse=True)
-    wmax = finite_max(d_in, d_out, src_flat["arcs"]["weight"], src_flat["finals"], got["arcs"]["weight"], got["finals"])
-    unweighted = bool(got["props"] & UNWEIGHTED)
-
-    def bound(length):
-        return length * float(model.KDELTA) if unweighted else weight_bound(length, wmax, delta)
-    # the longest string of the result: its height (longest path from the start), by peeling in topological order
-    height = np.zeros(n, dtype=np.int64)
-    indeg = np.bincount(arcs["nextstate"], minlength=n)
-    fr = np.nonzero(indeg == 0)[0]
-    src_of = np.repeat(np.arange(n), np.diff(off.astype(np.int64)))
-    while fr.size:
-        sel = np.isin(src_of, fr)
-        t = arcs["nextstate"][sel].astype(np.int64)
-        np.maximum.at(height, t, height[src_of[sel]] + 1)
-        np.subtract.at(indeg, t, 1)
-        t = np.unique(t)
-        fr = t[indeg[t] == 0]
-    longest = int(height.max())
-    assert abs(float(d_in[src_flat["start"]]) - float(d_out[got["start"]])) <= bound(longest), what
-    for _ in range(50):  # random walks in the result: the same string in the source
-        s, labels = got["start"], []
-        while True:
-            deg = int(off[s + 1] - off[s])
-            if deg == 0 or (np.isfinite(got["finals"][s]) and rng.random() < 0.3):
-                break
-            a = arcs[int(off[s]) + int(rng.integers(0, deg))]
-            labels.append(int(a["ilabel"]))
-            s = int(a["nextstate"])
-        w_out, w_in = accepts(got, labels), accepts(src_flat, labels)
-        assert (w_out is None) == (w_in is None), (what, labels)
-        if w_out is not None:
-            assert abs(w_out - w_in) <= bound(len(labels)), (what, labels, w_out, w_in)
-    again = got_dev.minimize(None if delta == KSHORTESTDELTA else _cfg(delta)).to_flat()
-    assert_flat_identical(again, minimize_ref(got, delta), f"{what} second call")
-    if idempotent:
-        assert_idempotent(again, got, f"{what} idempotent")
-
-
-def _cfg(delta):
-    import rustfst_amd
-    return rustfst_amd.MinimizeConfig(delta)
 
 
 @pytest.mark.gpu
@@ -733,52 +286,6 @@ def test_real_valued_weights(gpu_ctx, delta):
         # (idempotent=False: the second push computes (w - d) + d at the start state, which need not round back to w on
         # real-valued weights; the second call is still compared bit for bit with the restatement of that call)
         check_invariants(flat, got_dev, delta, gpu_ctx, rng, f"real {i}", idempotent=False)
-
-
-def blow_up(rng, m, k):
-    """k copies of every state of the minimal pushed DAG m (state-major: copy c of s is s * k + c), every arc to a random
-    copy of its target, integer potentials V added (w + V(t) - V(s), finals f - V(s)); V = 0 on copy 0 of the start"""
-    n = m["n_states"]
-    V = rng.integers(-3, 4, size=n * k).astype(np.float32)
-    V[m["start"] * k] = 0.0
-    deg = np.diff(m["offsets"].astype(np.int64))
-    src = np.repeat(np.arange(n), deg)
-    big_src = (np.repeat(src, k).reshape(-1, k) * k + np.arange(k)).reshape(-1)  # arcs of copy c of s: grouped per state
-    # state-major CSR: for state s, copy c: the arcs of s in order
-    order = np.argsort(big_src, kind="stable")
-    arc_of = np.repeat(np.arange(len(src)), k)[order]
-    big_src = big_src[order]
-    tgt = m["arcs"]["nextstate"][arc_of].astype(np.int64) * k + rng.integers(0, k, size=len(arc_of))
-    arcs = np.zeros(len(arc_of), dtype=TR_DTYPE)
-    arcs["ilabel"] = m["arcs"]["ilabel"][arc_of]
-    arcs["olabel"] = m["arcs"]["olabel"][arc_of]
-    arcs["weight"] = m["arcs"]["weight"][arc_of] + V[tgt] - V[big_src]
-    arcs["nextstate"] = tgt
-    off = np.zeros(n * k + 1, dtype=np.uint32)
-    off[1:] = np.cumsum(np.repeat(deg, k))
-    finals = np.repeat(m["finals"], k) - V
-    return dict(n_states=n * k, start=int(m["start"]) * k, offsets=off, arcs=arcs, finals=finals.astype(np.float32),
-                props=ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC)
-
-
-def closed_form_base(rng):
-    """a minimal weighted DAG with integer weights that minimize_ref maps to itself, arc order included (the arc order of
-    a result follows the untrimmed input of that call, so the restatement is applied until nothing moves)"""
-    for _ in range(50):
-        m = minimize_ref(random_dag(rng, 60, 3, True))
-        if m["n_states"] < 20 or m["props"] != ACCESSIBLE | COACCESSIBLE:
-            continue
-        for _ in range(10):
-            m["props"] = ACCEPTOR
-            again = minimize_ref(m)
-            if again["props"] != ACCESSIBLE | COACCESSIBLE:
-                break
-            same = np.array_equal(again["arcs"], m["arcs"]) and again["n_states"] == m["n_states"]
-            m = again
-            if same:
-                m["props"] = ACCEPTOR
-                return m
-    raise AssertionError("no base graph found")
 
 
 def test_closed_form_on_the_restatement():

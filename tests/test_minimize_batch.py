@@ -1,5 +1,5 @@
 """wfst_minimize_batch: the C-ABI and Python surface without a GPU, and on the device parity of every batch item with the
-Python restatement of minimize_with_config (test_minimize.minimize_ref) AND with the single call on the same handle, bit for
+Python restatement of minimize_with_config (oracle.model's minimize_ref) AND with the single call on the same handle, bit for
 bit including the property word: known answers and degenerate items, mixed random lists of three lengths (one launch
 each), shapes that cross the kernel's internal boundaries (more states / arcs / levels than the workgroup has threads,
 fan-out above 64 and above 256), the edges of the in_kernel rule, more items than workgroups can be resident, the
@@ -14,12 +14,12 @@ import numpy as np
 import pytest
 
 from rustfst_amd._lib import TR_DTYPE
-
-import test_determinize as td
-import test_minimize as tm
 from oracle import model
 import helpers
-from helpers import assert_flat_identical, to_device
+from helpers import assert_flat_identical, empty_flat, golden_flat, to_device
+import determinize_cases as dc
+import minimize_cases as mc
+from oracle.model import minimize_ref
 
 ROOT = helpers.ROOT
 INF = float("inf")
@@ -46,10 +46,6 @@ def with_true_word(flat):
     w = np.concatenate([flat["arcs"]["weight"], flat["finals"][np.isfinite(flat["finals"])]])
     weighted = bool(np.any(np.abs(w) > model.KDELTA))
     return dict(flat, props=KNOWN_W if weighted else KNOWN_U)
-
-
-def empty_flat(props=0):
-    return model.make_flat(0, None, [], [], props)
 
 
 # ================================================================ no GPU
@@ -157,7 +153,7 @@ def check_list(items, ctx, delta=None, single=True, upload_many=False):
     d = model.KSHORTESTDELTA if delta is None else delta
     which = range(len(items)) if single is True else single
     for k, ((name, flat), g) in enumerate(zip(items, got)):
-        same(g, tm.minimize_ref(flat, d), f"item {k} ({name}) delta {d} vs the restatement")
+        same(g, minimize_ref(flat, d), f"item {k} ({name}) delta {d} vs the restatement")
     for k in which:
         same(got[k], devs[k].minimize(_cfg(delta)).to_flat(), f"item {k} ({items[k][0]}) delta {d} vs the single call")
     return got, devs
@@ -166,12 +162,12 @@ def check_list(items, ctx, delta=None, single=True, upload_many=False):
 @pytest.mark.gpu
 def test_known_answers_and_degenerate_items(gpu_ctx):
     groups = {}
-    for c in tm.golden_cases():
-        delta, nondet = tm.cfg_of(c)
+    for c in mc.golden_cases():
+        delta, nondet = mc.cfg_of(c)
         if not nondet:
-            groups.setdefault(delta, []).append((c["name"], tm.golden_flat(c), tm.golden_flat(c, "expected")))
+            groups.setdefault(delta, []).append((c["name"], golden_flat(c), golden_flat(c, "expected")))
     assert sum(len(g) for g in groups.values()) >= 8
-    gone, gone_known = tm.no_start_cases()[0][0], tm.no_start_cases()[1][0]
+    gone, gone_known = mc.no_start_cases()[0][0], mc.no_start_cases()[1][0]
     degenerate = [
         ("no states", empty_flat()), ("no states, known word", empty_flat(KNOWN_U)),
         ("no start, unweighted", model.make_flat(2, None, [[(1, 1, 0.0, 1)], []], [INF, 0.0], model.ACCEPTOR)),
@@ -200,7 +196,7 @@ def test_known_answers_and_degenerate_items(gpu_ctx):
     import rustfst_amd
     f = dict(degenerate)["one final state, weight 2"]
     out = rustfst_amd.minimize_batch([to_device(f, gpu_ctx)], _cfg(1e-6, True), gpu_ctx)[0]
-    same(out.to_flat(), tm.minimize_ref(f, 1e-6, True), "allow_nondet")
+    same(out.to_flat(), minimize_ref(f, 1e-6, True), "allow_nondet")
 
 
 @pytest.mark.gpu
@@ -208,7 +204,7 @@ def test_mixed_random_lists_take_one_launch_each(gpu_ctx):
     launches = []
     for seed, count in ((41, 64), (42, 8), (43, 200)):
         items = []
-        for k, (name, flat) in enumerate(tm.random_cases(seed, count)):
+        for k, (name, flat) in enumerate(mc.random_cases(seed, count)):
             items.append((name, with_true_word(flat) if k % 3 == 2 else flat))
         kinds = {name for name, _ in items}
         assert {"trie-w", "trie-u", "dag-w", "dag-u"} <= kinds
@@ -249,7 +245,7 @@ def hubs(width, weighted):
 def real_dag(n):
     """a random DAG with real-valued weights of which a good part survives connect"""
     for seed in range(100):
-        f = tm.random_dag(np.random.default_rng(seed), n, 4, True, real=True)
+        f = mc.random_dag(np.random.default_rng(seed), n, 4, True, real=True)
         fst = model.flat_to_fst(f)
         model.connect(fst)
         if 3 * len(fst["rows"]) >= n:
@@ -260,11 +256,11 @@ def real_dag(n):
 @functools.lru_cache(maxsize=None)
 def boundary_items():
     rng = np.random.default_rng(77)
-    trie = tm.trie_flat(rng, 800, 10, 10, True)
-    trie_u = tm.trie_flat(rng, 800, 10, 10, False)
+    trie = mc.trie_flat(rng, 800, 10, 10, True)
+    trie_u = mc.trie_flat(rng, 800, 10, 10, False)
     assert 2500 <= trie["n_states"] <= MAX_STATES and 2500 <= trie_u["n_states"] <= MAX_STATES
-    m = tm.closed_form_base(np.random.default_rng(33))
-    all_final = tm.random_dag(rng, 120, 4, True, real=True)
+    m = mc.closed_form_base(np.random.default_rng(33))
+    all_final = mc.random_dag(rng, 120, 4, True, real=True)
     all_final["finals"] = (rng.permutation(120).astype(np.float32) / F32(7.0) + F32(0.01)).astype(np.float32)
     one_tuple = model.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [1.0], 0)
     one_tuple_u = model.make_flat(40, 0, [[(1, 1, 0.0, s + 1)] for s in range(39)] + [[]], [INF] * 39 + [0.0], 0)
@@ -272,7 +268,7 @@ def boundary_items():
              ("chain 700 real", chain(700, True, real=True)),
              ("hubs 300", hubs(300, True)), ("hubs 1100", hubs(1100, True)), ("hubs 1100 unweighted", hubs(1100, False)),
              ("trie", trie), ("trie unweighted", trie_u),
-             ("blow_up 3", tm.blow_up(rng, m, 3)), ("blow_up 7", tm.blow_up(rng, m, 7)),
+             ("blow_up 3", mc.blow_up(rng, m, 3)), ("blow_up 7", mc.blow_up(rng, m, 7)),
              ("every state final", all_final), ("one tuple", one_tuple), ("one tuple unweighted", one_tuple_u),
              ("real dag", real_dag(300))]
     return items
@@ -288,7 +284,7 @@ def test_shapes_across_the_kernel_boundaries(gpu_ctx, delta):
     assert by["chain 1500 weighted"]["n_states"] == 1500  # deeper than the workgroup has threads, nothing merges
     assert by["hubs 1100"]["n_states"] < 10 and len(by["hubs 1100"]["arcs"]) > 2 * 1100
     assert by["every state final"]["n_states"] >= 90 and by["real dag"]["n_states"] >= 50
-    m = tm.closed_form_base(np.random.default_rng(33))
+    m = mc.closed_form_base(np.random.default_rng(33))
     assert by["blow_up 7"]["n_states"] == m["n_states"] < dict(items)["blow_up 7"]["n_states"] // 6
 
 
@@ -343,7 +339,7 @@ def test_edges_of_the_in_kernel_rule(gpu_ctx):
         got, flags = _batch(devs, gpu_ctx)
         assert flags == [1, 0] and _stats(gpu_ctx) == dict(launches=1, items_in_kernel=1, items_single=1)
         same(got[1], want, "INITIAL_CYCLIC word vs the single call")
-        same(got[0], tm.minimize_ref(items[5][1]), "the item beside it")
+        same(got[0], minimize_ref(items[5][1]), "the item beside it")
 
 
 @pytest.mark.gpu
@@ -352,7 +348,7 @@ def test_more_items_than_resident_workgroups(gpu_ctx):
     items = []
     for k in range(3000):
         n = int(rng.integers(1, 9))
-        flat = tm.random_dag(rng, n, 3, weighted=k % 2 == 0, props=model.ACCEPTOR if k % 3 else 0, real=k % 5 == 0)
+        flat = mc.random_dag(rng, n, 3, weighted=k % 2 == 0, props=model.ACCEPTOR if k % 3 else 0, real=k % 5 == 0)
         items.append((f"tiny {k}", flat))
     assert max(f["n_states"] for _, f in items) <= 8
     check_list(items, gpu_ctx, single=[int(i) for i in rng.choice(3000, size=50, replace=False)], upload_many=True)
@@ -363,7 +359,7 @@ def test_more_items_than_resident_workgroups(gpu_ctx):
 def test_determinize_batch_then_minimize_batch(gpu_ctx):
     import rustfst_amd
     rng = np.random.default_rng(66)
-    lats = [td.random_acceptor(rng, int(rng.integers(10, 50)), 3, 3, acyclic=True, weight_grid=1, max_w=4) for _ in range(32)]
+    lats = [dc.random_acceptor(rng, int(rng.integers(10, 50)), 3, 3, acyclic=True, weight_grid=1, max_w=4) for _ in range(32)]
     for f in lats:
         f["finals"][-1] = 0.0
     devs = [to_device(f, gpu_ctx) for f in lats]
@@ -374,10 +370,10 @@ def test_determinize_batch_then_minimize_batch(gpu_ctx):
     for k, (det, mini) in enumerate(zip(dets, minis)):
         det_flat, got = det.to_flat(), mini.to_flat()
         same(got, det.minimize().to_flat(), f"lattice {k} vs the single call")
-        same(got, tm.minimize_ref(det_flat), f"lattice {k} vs the restatement")
+        same(got, minimize_ref(det_flat), f"lattice {k} vs the restatement")
         shrunk += got["n_states"] < det_flat["n_states"]
         if k % 4 == 0:
-            tm.check_invariants(det_flat, mini, model.KSHORTESTDELTA, gpu_ctx, rng, f"lattice {k}")
+            mc.check_invariants(det_flat, mini, model.KSHORTESTDELTA, gpu_ctx, rng, f"lattice {k}")
     assert shrunk >= 4
 
 
@@ -388,8 +384,8 @@ def bad_items():
                           [INF, INF, 0.0, INF, INF], model.ACCEPTOR)
     nd = model.make_flat(3, 0, [[(1, 1, 0.0, 1), (1, 1, 1.0, 2)], [], []], [INF, 0.0, 0.0], 0)
     tr = model.make_flat(2, 0, [[(1, 2, 0.0, 1)], []], [INF, 0.0], 0)
-    far = tm.far_apart_cases()[0]
-    stays = tm.no_start_cases()[2][0]
+    far = mc.far_apart_cases()[0]
+    stays = mc.no_start_cases()[2][0]
     return [("cyclic", cyc, "cyclic inputs"), ("hidden cycle", hidden, "cyclic inputs"), ("non-deterministic", nd, "Refusing"),
             ("transducer", tr, "transducers"), ("far apart", far, "further than 1/1024 apart"),
             ("start-less with a leftover weight", stays, "FST is not an unweighted acceptor")]
@@ -416,7 +412,7 @@ def _raw_batch(devs, ctx, allow_nondet=False):
 @pytest.mark.gpu
 def test_errors(gpu_ctx):
     import rustfst_amd
-    goods = [f for _, f in tm.random_cases(5, 12)]
+    goods = [f for _, f in mc.random_cases(5, 12)]
     devs = [to_device(f, gpu_ctx) for f in goods]
     good, _ = _batch(devs, gpu_ctx)
     assert _stats(gpu_ctx)["launches"] == 1
@@ -455,8 +451,8 @@ def test_errors(gpu_ctx):
 
 @pytest.mark.gpu
 def test_inputs_are_left_as_they_are(gpu_ctx):
-    items = [(name, with_true_word(f) if k % 2 else f) for k, (name, f) in enumerate(tm.random_cases(9, 24))]
-    items += [("no start", tm.no_start_cases()[0][0]), ("empty", empty_flat()), ("hubs", hubs(300, True))]
+    items = [(name, with_true_word(f) if k % 2 else f) for k, (name, f) in enumerate(mc.random_cases(9, 24))]
+    items += [("no start", mc.no_start_cases()[0][0]), ("empty", empty_flat()), ("hubs", hubs(300, True))]
     devs = [to_device(f, gpu_ctx) for _, f in items]
     before = [d.to_flat() for d in devs]
     for (name, f), b in zip(items, before):

@@ -2,7 +2,7 @@
 narrow kernel, the device-wide launches per level, the hand-over between them in `auto`, a lane or a wave per state — so
 only the counters of wfst_ctx_get_minimize_stats show which one ran.  Without a GPU: the symbol, the restatement of the
 routing (level_profile, predict) against closed forms written out by hand, and every input below on the limit it is built
-for (level sizes, degrees, class sizes: all from test_minimize's restatement).  On the device: every input ON a limit and
+for (level sizes, degrees, class sizes: all taken from oracle.model's restatement of minimize).  On the device: every input ON a limit and
 its twin one step beyond it, bit-exact against minimize_ref, the source handle unchanged, every counter against the
 prediction, under WFST_MINIMIZE_PATH = auto, narrow and wide, as an unweighted and as a weighted acceptor.
 
@@ -22,11 +22,11 @@ import re
 
 import numpy as np
 import pytest
-
-import test_minimize as tm
 from oracle import model
 import helpers
 from helpers import assert_flat_identical, to_device
+import minimize_cases as mc
+from oracle.model import minimize_ref
 
 INF, ACCEPTOR = model.INF, model.ACCEPTOR
 PATHS = ("auto", "narrow", "wide")
@@ -269,7 +269,7 @@ def analysis(name, kind):
     """the restatement's answer and what it saw: dict(exp, T, part, profile_check, profile, height, degrees)"""
     flat = case(name, kind)
     seen = {}
-    exp = tm.minimize_ref(flat, partition_out=seen)
+    exp = minimize_ref(flat, partition_out=seen)
     profile, height = heights(seen["T"])
     check = None if model.known(flat["props"]) & model.ACYCLIC else level_profile(flat)
     return dict(exp=exp, T=seen["T"], part=seen["part"], profile_check=check, profile=profile, height=height,
@@ -506,7 +506,7 @@ def test_cyclic_inputs_stop_where_they_are_built_to():
         assert sum(profile) < flat["n_states"] and model.is_cyclic(flat), name
         assert model.known(flat["props"]) & model.ACYCLIC == 0
         with pytest.raises(model.Unsupported, match="cyclic"):
-            tm.minimize_ref(flat)
+            minimize_ref(flat)
     c = {k: route(v[1], "auto") for k, v in cyclic_cases().items()}
     assert c["ring"] == _pass()
     assert c["after_wide"] == _pass(levels=1, wide_levels=1)
@@ -704,7 +704,7 @@ def test_counters_reset_and_empty_inputs(gpu_ctx, monkeypatch):
     to_device(dead, gpu_ctx).minimize()
     st = gpu_ctx.minimize_stats()
     assert st["branch"] == 4 and st["check_levels"] == 3 and st["levels"] == 0
-    flat, message = tm.no_start_cases()[0]
+    flat, message = mc.no_start_cases()[0]
     assert message is None
     to_device(flat, gpu_ctx).minimize()
     assert gpu_ctx.minimize_stats()["branch"] == 3

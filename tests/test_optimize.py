@@ -1,225 +1,34 @@
 """tr_sum, tr_unique and optimize (wfst_tr_sum, wfst_tr_unique, wfst_optimize): the C-ABI surface without a GPU, a literal
 sequential Python restatement of rustfst's tr_sum.rs, tr_unique.rs, encode/decode (EncodeLabels), rm_final_epsilon.rs and
-optimize.rs (tropical semiring) written out below and checked against the hand-derived K17 known answers, and on the device
+optimize.rs (tropical semiring; oracle/model/optimize.py) checked against the hand-derived K17 known answers, and on the device
 bit-exact parity with the restatement: states, offsets, arcs (weights by bit pattern), finals and property word.
 
-The restatement reuses determinize_ref (test_determinize.py), minimize_ref (test_minimize.py), the weight and property
-rules, tr_unique and rm_final_epsilon of oracle/model/ and the oracle's rm_epsilon.
+The restatement reuses determinize_ref, minimize_ref, the weight and property rules, tr_unique and rm_final_epsilon of
+oracle/model/ and the oracle's rm_epsilon.
 
 Shapes of the arc-list tests, and why: the kernel keeps a state in one register per lane up to 16 arcs, works in chunks of
 16 up to 256 arcs and hands larger states to a radix sort, so the degrees are 0, 1, 16, 17, 256, 257 and 300; duplicate
 runs straddle a 16-arc chunk boundary (the write pass counts survivors per chunk) and cover a whole state."""
 import ctypes as C
-import json
 import os
 import re
 
 import numpy as np
 import pytest
 
-from rustfst_amd._lib import TR_DTYPE
-
 from oracle import model
-from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ALL, EPSILONS, F32, INF, I_DETERMINISTIC, LABEL_INVARIANT,
-                          NOT_I_DETERMINISTIC, NO_EPSILONS, UNWEIGHTED, UNWEIGHTED_CYCLES, Unsupported,
-                          WEIGHT_INVARIANT, content_word_of_flat, rm_final_epsilon, rows_flat, tr_unique)
-from helpers import assert_flat_identical, ko_message, to_device, to_oracle
-import test_determinize as td
-import test_minimize as tm
+from oracle.model import (ACCEPTOR, ACYCLIC, EPSILONS, F32, INF, I_DETERMINISTIC, NOT_I_DETERMINISTIC, NO_EPSILONS,
+                          Unsupported, apply_op, branch_of, content_word_of_flat, decode_labels, det_min,
+                          determinize_encoded, determinize_ref, encode_labels, minimize_ref, norm, optimize_ref,
+                          rows_flat, tr_key, tr_sum)
+from helpers import assert_flat_identical, golden_flat, ko_message, to_device, to_oracle
+from optimize_cases import golden_cases, optimize_input, part_a_rows, part_b_rows, random_arc_lists
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "k17_optimize.json")
 PATHS = ("narrow", "wide", "auto")
-MSG_ACYCLIC = "optimize: inputs whose property word does not hold ACYCLIC are not supported"
-
-
-# ---------------------------------------------------------------- the restatement
-def tr_key(t):  # tr_compare (tr_unique.rs:8-34): ilabel, olabel, nextstate; the weight is not in the key
-    return (t[0], t[1], t[3])
-
-
-def tr_sum(fst):  # tr_sum.rs:7-22, sum_trs_unchecked (vector_fst/mutable_fst.rs:380-405)
-    props = fst["props"]
-    for s, row in enumerate(fst["rows"]):
-        row = sorted(row, key=tr_key)  # stable
-        out = []
-        for t in row:
-            if out and tr_key(out[-1]) == tr_key(t):
-                if F32(t[2]) < F32(out[-1][2]):  # plus_assign (tropical_weight.rs:53-58)
-                    out[-1][2] = F32(t[2])
-            else:
-                out.append(list(t))
-        fst["rows"][s] = out
-    p = props & model.ARCSORT & model.DELETE_ARCS & WEIGHT_INVARIANT
-    if not fst["rows"]:
-        p |= model.NULL_PROPS
-    fst["props"] = p
-
-
-def encode_labels(fst):  # encode(EncodeLabels): encode_static.rs, table.rs; MapNoSuperfinal, weights untouched
-    table, pairs = {}, []
-
-    def arc(tr):
-        k = (tr[0], tr[1])
-        if k not in table:
-            pairs.append(k)
-            table[k] = len(pairs)
-        tr[0] = tr[1] = table[k]
-    model.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
-    return pairs
-
-
-def decode_labels(fst, pairs):  # decode (decode_static.rs): the pair back, the same mask, rm_final_epsilon
-    def arc(tr):
-        tr[0], tr[1] = pairs[tr[0] - 1]
-    model.tr_map(fst, arc, lambda ftr: None, False, lambda p: p & LABEL_INVARIANT)
-    rm_final_epsilon(fst)
-
-
-def norm(flat):
-    start = flat["start"]
-    return dict(flat, start=None if start is None or start < 0 else int(start), props=int(flat["props"]) & ALL)
-
-
-def determinize_encoded(flat):
-    """determinize of a label-encoded machine (ilabel == olabel >= 1, the word without ACCEPTOR): the acceptor
-    construction, the word of the gallic call (determinize_static.rs:177-192)"""
-    out = td.determinize_ref(dict(flat, props=flat["props"] | ACCEPTOR))
-    out["props"] = model.determinize_props(flat["props"], True)
-    return out
-
-
-def det_min(flat, encoded):
-    det = determinize_encoded(flat) if encoded else td.determinize_ref(flat)
-    return tm.minimize_ref(norm(det))
-
-
-def optimize_ref(flat, oracle):
-    """optimize (optimize.rs:11-128) for the tropical semiring; raises Unsupported (or determinize_ref's ValueError) with the
-    KO message"""
-    flat = norm(flat)
-    acceptor = bool(flat["props"] & ACCEPTOR)
-    cur = flat
-    if not cur["props"] & NO_EPSILONS:
-        cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
-    fst = model.flat_to_fst(cur)
-    tr_sum(fst)
-    cur = model.fst_to_flat(fst)
-    p = cur["props"]
-    if p & I_DETERMINISTIC:
-        return tm.minimize_ref(cur)
-    if not p & ACYCLIC:  # intersects(ACYCLIC | UNWEIGHTED | UNWEIGHTED_CYCLES): tr_sum's mask left neither of the others
-        assert not p & (UNWEIGHTED | UNWEIGHTED_CYCLES)
-        raise Unsupported(MSG_ACYCLIC)
-    if acceptor:
-        return det_min(cur, False)
-    pairs = encode_labels(fst)
-    mini = model.flat_to_fst(det_min(model.fst_to_flat(fst), True))
-    decode_labels(mini, pairs)
-    return model.fst_to_flat(mini)
-
-
-def apply_op(op, flat, oracle=None):
-    if op == "optimize":
-        return optimize_ref(flat, oracle)
-    fst = model.flat_to_fst(norm(flat))
-    (tr_sum if op == "tr_sum" else tr_unique)(fst)
-    return model.fst_to_flat(fst)
 
 
 # ---------------------------------------------------------------- inputs
-def golden_cases():
-    with open(GOLDEN) as f:
-        return json.load(f)["cases"]
-
-
-def part_a_rows():
-    """degrees at every path boundary; duplicate runs across a chunk boundary and over a whole state"""
-    rng = np.random.default_rng(5)
-    n = 24
-
-    def rnd(k, dup=0.5, sigma=6):
-        row = []
-        for _ in range(k):
-            if row and rng.random() < dup:
-                il, ol, _, ns = row[int(rng.integers(0, len(row)))]
-            else:
-                il, ol, ns = int(rng.integers(0, sigma)), int(rng.integers(0, sigma)), int(rng.integers(0, n))
-            row.append((il, ol, float(rng.integers(0, 8)) / 4, ns))
-        return row
-    rows = [[], rnd(1), rnd(16), rnd(17), rnd(256), rnd(257), rnd(300), rnd(300, dup=0.0, sigma=1000)]
-    rows.append([(3, 3, float(8 - i % 8), 2) for i in range(40)])                    # a run that covers a whole state
-    rows.append([(2, 2, float(i % 5), 1) for i in range(300)])                       # ... of a big state
-    rows.append([(1, 1, 1.0, 0)] * 10 + [(5, 5, float(20 - i), 3) for i in range(12)] + [(9, 9, 0.0, 1)] * 3)  # run over 16
-    rows.append([(i + 1, i + 1, float(i), i % n) for i in range(16)])               # no duplicates
-    rows.append([(i + 1, 7, 0.5, 4) for i in range(40)])                            # no duplicates, chunked
-    rows.append([(7, 7, 0.25 * (i % 3), 5) for i in range(15)] + [(7, 7, 3.0, 5), (7, 7, 0.0, 5), (8, 8, 1.0, 5)])  # run 15..17
-    while len(rows) < n:
-        rows.append(rnd(int(rng.integers(0, 20))))
-    return rows_flat(rows, [INF] * n)
-
-
-def part_b_rows():
-    """keys that differ in one field only, labels >= 2^31, ilabel 0, signed zeros, +inf, empty states, a run in the last state"""
-    big = 0x80000000
-    rows = [
-        [(5, 2, 1.0, 1), (5, 1, 2.0, 1), (5, 2, 0.5, 1), (5, 1, 3.0, 1)],                      # differ in olabel only
-        [],
-        [(5, 5, 1.0, 3), (5, 5, 2.0, 2), (5, 5, 0.5, 3), (5, 5, 3.0, 2)],                      # differ in nextstate only
-        [(big + 1, 1, 1.0, 0), (1, big, 2.0, 0), (big, big + 7, 0.0, 0), (0xFFFFFFFE, 0, 1.0, 0), (7, 7, 1.0, 0),
-         (big + 1, 1, 0.5, 0), (1, big, 2.5, 0)],                                              # unsigned compare
-        [],
-        [],
-        [(0, 0, 1.0, 1), (0, 3, 1.0, 1), (0, 0, 0.5, 1), (3, 0, 2.0, 1), (0, 3, 4.0, 1)],      # ilabel 0
-        [(1, 1, 0.0, 0), (1, 1, -0.0, 0), (2, 2, -0.0, 0), (2, 2, 0.0, 0)],                    # ties keep the earlier bits
-        [(1, 1, INF, 0), (1, 1, INF, 0), (2, 2, INF, 0), (2, 2, 1.0, 0), (3, 3, 1.0, 0), (3, 3, INF, 0)],
-        [(4, 4, 0.0, 2), (4, 4, 0.0009, 2), (4, 4, 0.0018, 2), (4, 4, 0.0027, 2)],             # the KDELTA chain
-        [],
-        [(6, 6, 2.0, 9), (6, 6, 1.0, 9), (6, 6, 1.0, 9), (6, 6, 3.0, 9)],                      # a run in the LAST state
-    ]
-    return rows_flat(rows, [INF, 0.0] + [INF] * 9 + [1.5])
-
-
-def random_arc_lists(seed, n):
-    rng = np.random.default_rng(seed)
-    rows = []
-    for s in range(n):
-        row = []
-        for _ in range(int(rng.integers(0, 12))):
-            if row and rng.random() < 0.5:
-                il, ol, _, ns = row[int(rng.integers(0, len(row)))]
-            else:
-                il, ol, ns = int(rng.integers(0, 4)), int(rng.integers(0, 4)), int(rng.integers(0, n))
-            row.append((il, ol, float(rng.integers(0, 64)) / 1024.0 if rng.random() < 0.5 else float(rng.integers(0, 4)), ns))
-        rows.append(row)
-    return rows_flat(rows, [0.0 if rng.random() < 0.2 else INF for _ in range(n)], props=int(ACYCLIC | ACCESSIBLE))
-
-
-def optimize_input(rng, n, transducer, deterministic=False, eps=True):
-    """an acyclic FST by construction (arcs to higher ids only), integer weights (a grid far coarser than KDELTA), eps:eps
-    arcs and parallel arcs; the word is the one computed from its content"""
-    rows, finals = [], []
-    for s in range(n):
-        row = []
-        labs = rng.permutation(np.arange(1, 4))
-        for k in range(int(rng.integers(1, 4))):  # at least one arc forward: every path ends in the last state, a final one
-            if s + 1 >= n:
-                break
-            il = int(labs[k]) if deterministic else int(rng.integers(1, 4 if transducer else 10))  # nine labels or pairs
-            ol = il if not transducer else int(rng.integers(0, 3)) + 4 * il
-            t = int(rng.integers(s + 1, min(n, s + 5)))
-            row.append((il, ol, float(rng.integers(0, 3)), t))
-            if not deterministic and rng.random() < 0.3:  # a parallel arc: tr_sum has work
-                row.append((il, ol, float(rng.integers(0, 3)), t))
-        if eps and not deterministic and s + 1 < n and rng.random() < 0.2:
-            row.append((0, 0, float(rng.integers(0, 2)), int(rng.integers(s + 1, min(n, s + 4)))))
-        rows.append(row)
-        finals.append(float(rng.integers(0, 2)) if rng.random() < 0.3 or s == n - 1 else INF)
-    flat = rows_flat(rows, finals)
-    flat["props"] = content_word_of_flat(flat)
-    return flat
-
-
 def regime_cases(seed=21):
     """(name, flat, branch of step 4 it must take)"""
     rng = np.random.default_rng(seed)
@@ -232,19 +41,6 @@ def regime_cases(seed=21):
     out.append(("acceptor-no-eps", optimize_input(rng, 200, False, eps=False), "det-min"))
     out.append(("transducer-no-eps", optimize_input(rng, 200, True, eps=False), "encode"))
     return out
-
-
-def branch_of(flat, oracle):
-    cur = norm(flat)
-    if not cur["props"] & NO_EPSILONS:
-        cur = norm(to_oracle(oracle, cur).rm_epsilon().to_flat())
-    fst = model.flat_to_fst(cur)
-    tr_sum(fst)
-    if fst["props"] & I_DETERMINISTIC:
-        return "min"
-    if not fst["props"] & ACYCLIC:
-        return "ko"
-    return "det-min" if flat["props"] & ACCEPTOR else "encode"
 
 
 # ================================================================ CPU
@@ -276,7 +72,7 @@ def test_python_surface():
 
 def golden_error(c, oracle):
     try:
-        apply_op(c["op"], tm.golden_flat(c), oracle)
+        apply_op(c["op"], golden_flat(c), oracle)
     except (Unsupported, ValueError) as e:
         return e.args[0]
     return None
@@ -292,10 +88,10 @@ def test_k17_restatement_reproduces_the_derivations(oracle):
             msg = golden_error(c, oracle)
             assert msg is not None and (msg in c["error"] or c["error"] in msg), (c["name"], msg)
             continue
-        got = apply_op(c["op"], tm.golden_flat(c), oracle)
-        assert_flat_identical(got, tm.golden_flat(c, "expected"), c["name"])
+        got = apply_op(c["op"], golden_flat(c), oracle)
+        assert_flat_identical(got, golden_flat(c, "expected"), c["name"])
         for stage, word in c.get("words", {}).items():  # the property word after every stage of the derivation
-            assert stage_words(tm.golden_flat(c), oracle)[stage] == int(word, 16), (c["name"], stage)
+            assert stage_words(golden_flat(c), oracle)[stage] == int(word, 16), (c["name"], stage)
 
 
 def stage_words(flat, oracle):
@@ -314,9 +110,9 @@ def stage_words(flat, oracle):
         out["encode"] = fst["props"]
     cur = model.fst_to_flat(fst)
     if not cur["props"] & I_DETERMINISTIC:
-        cur = norm(determinize_encoded(cur) if encoded else td.determinize_ref(cur))
+        cur = norm(determinize_encoded(cur) if encoded else determinize_ref(cur))
         out["determinize"] = cur["props"]
-    out["minimize"] = tm.minimize_ref(cur)["props"]
+    out["minimize"] = minimize_ref(cur)["props"]
     return out
 
 
@@ -324,7 +120,7 @@ def test_reference_python_test_machine(oracle):
     """rustfst-python/tests/algorithms/test_optimize.py: the one transducer result on record that rustfst itself produced
     (through its gallic determinizer)"""
     c = next(c for c in golden_cases() if c["name"] == "reference_python_test")
-    got = optimize_ref(tm.golden_flat(c), oracle)
+    got = optimize_ref(golden_flat(c), oracle)
     assert got["n_states"] == 4 and got["start"] == 0
     arcs = [(int(a["ilabel"]), int(a["olabel"]), float(a["weight"]), int(a["nextstate"])) for a in got["arcs"]]
     assert arcs == [(1, 2, 4.0, 1), (1, 3, 7.0, 2), (4, 6, 1.0, 3), (7, 8, 0.0, 3)]
@@ -441,12 +237,12 @@ def test_arc_lists_part_b(gpu_ctx, op):
 def test_k17_on_the_device(gpu_ctx, oracle):
     import rustfst_amd
     for c in golden_cases():
-        flat = tm.golden_flat(c)
+        flat = golden_flat(c)
         if "error" in c:
             with pytest.raises(rustfst_amd.WfstError, match=re.escape(c["error"])):
                 dev_op(c["op"], flat, gpu_ctx)
             continue
-        assert_flat_identical(dev_op(c["op"], flat, gpu_ctx).to_flat(), tm.golden_flat(c, "expected"), c["name"])
+        assert_flat_identical(dev_op(c["op"], flat, gpu_ctx).to_flat(), golden_flat(c, "expected"), c["name"])
 
 
 @pytest.mark.gpu
@@ -465,13 +261,13 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, oracle):
     for c in golden_cases():
         if "error" not in c:
             continue
-        dev = to_device(tm.golden_flat(c), gpu_ctx)
+        dev = to_device(golden_flat(c), gpu_ctx)
         before = dev.to_flat()
         with pytest.raises(rustfst_amd.WfstError, match=re.escape(c["error"])):
             dev.optimize()
         assert_flat_identical(dev.to_flat(), before, c["name"] + ": the input handle")
-        got = dev_op("optimize", tm.golden_flat(good), gpu_ctx).to_flat()  # the context still works
-        assert_flat_identical(got, tm.golden_flat(good, "expected"), "after " + c["name"])
+        got = dev_op("optimize", golden_flat(good), gpu_ctx).to_flat()  # the context still works
+        assert_flat_identical(got, golden_flat(good, "expected"), "after " + c["name"])
 
 
 @pytest.mark.gpu

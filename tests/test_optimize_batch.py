@@ -4,7 +4,7 @@ the property word; the K17 known answers as a list; the in_kernel flags and the 
 depend on the list's length; the KO order of the loop of single calls (a later stage may fail at a lower index than an
 earlier one); and the four batch stages chained by hand against the one call.
 
-Items have 8 to 40 states (test_optimize.optimize_input: acyclic by construction, integer weights, eps:eps and parallel
+Items have 8 to 40 states (optimize_cases.optimize_input: acyclic by construction, integer weights, eps:eps and parallel
 arcs, the word computed from the content); only the two items that leave the tr_sum kernel by size are larger."""
 import ctypes as C
 import functools
@@ -14,15 +14,13 @@ import re
 
 import numpy as np
 import pytest
-
-import test_minimize as tm
-import test_optimize as to
 from oracle import model
-from oracle.model import (ACCEPTOR, ACYCLIC, INF, I_DETERMINISTIC, NOT_I_DETERMINISTIC, NO_EPSILONS,
-                          content_word_of_flat, rows_flat)
+from oracle.model import (ACCEPTOR, ACYCLIC, INF, I_DETERMINISTIC, MSG_ACYCLIC, NOT_I_DETERMINISTIC, NO_EPSILONS,
+                          branch_of, content_word_of_flat, optimize_ref, rows_flat)
 import helpers
-from helpers import assert_flat_identical, to_device
-from test_optimize import MSG_ACYCLIC, branch_of, optimize_input, optimize_ref
+from helpers import assert_flat_identical, golden_flat, to_device
+import optimize_cases as oc
+from optimize_cases import optimize_input
 
 ROOT = helpers.ROOT
 STAGES = ("rm_epsilon", "tr_sum", "determinize", "minimize")
@@ -239,16 +237,16 @@ def test_parity_of_one_mixed_list(gpu_ctx, oracle):
 
 @pytest.mark.gpu
 def test_k17_as_a_list(gpu_ctx, oracle):
-    cases = [c for c in to.golden_cases() if c["op"] == "optimize"]
+    cases = [c for c in oc.golden_cases() if c["op"] == "optimize"]
     good = [c for c in cases if "error" not in c]
     bad = [c for c in cases if "error" in c]
     assert len(good) >= 3
-    devs = [to_device(tm.golden_flat(c), gpu_ctx) for c in good]
+    devs = [to_device(golden_flat(c), gpu_ctx) for c in good]
     got, _ = _batch(devs, gpu_ctx)
     for c, g in zip(good, got):
-        assert_flat_identical(g, tm.golden_flat(c, "expected"), c["name"])
+        assert_flat_identical(g, golden_flat(c, "expected"), c["name"])
     for c in bad:  # behind the good ones: the index in front of the single call's message
-        dev = to_device(tm.golden_flat(c), gpu_ctx)
+        dev = to_device(golden_flat(c), gpu_ctx)
         single = _single_message(dev, gpu_ctx)
         assert c["error"] in single
         status, outs = _raw_batch(devs + [dev], gpu_ctx)
@@ -256,7 +254,7 @@ def test_k17_as_a_list(gpu_ctx, oracle):
         assert outs == [None] * (len(devs) + 1)
     again, _ = _batch(devs, gpu_ctx)
     for c, g in zip(good, again):
-        assert_flat_identical(g, tm.golden_flat(c, "expected"), c["name"] + " after the KO calls")
+        assert_flat_identical(g, golden_flat(c, "expected"), c["name"] + " after the KO calls")
 
 
 @pytest.mark.gpu

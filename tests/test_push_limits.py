@@ -1,6 +1,6 @@
 """push.hip at its limits: rows longer than the 16 lanes a state gets, frontier searches whose depth sits on the edges of the
 round batching, grids small enough to stride (WFST_PUSH_MAX_BLOCKS), and reductions that cross waves and blocks — each
-compared bit for bit with the restatement of reweight.rs / push.rs in test_push_weights.py over the oracle's distances, and
+compared bit for bit with the restatement of reweight.rs / push.rs in oracle/model/push.py over the oracle's distances, and
 with wfst_ctx_get_push_stats saying which route ran.
 
 The structural facts are checked three ways: numpy graph_facts and the oracle's own depth-first visit (OracleFst.
@@ -23,13 +23,10 @@ import numpy as np
 import pytest
 
 from rustfst_amd._lib import TR_DTYPE
-
-import test_push_weights as tp
-from test_push_weights import assert_same, push_ref, reverse_len_rule, reweight_ref
 from oracle import model
-from oracle.model import graph_facts, to_flat
+from oracle.model import graph_facts, push_ref, reverse_len_rule, reweight_ref, to_flat
 import helpers
-from helpers import to_device, to_oracle
+from helpers import _oracle_dist, assert_same, to_device, to_oracle
 
 ROOT = helpers.ROOT
 F32, INF = np.float32, np.float32(np.inf)
@@ -43,7 +40,7 @@ KNOB = "WFST_PUSH_MAX_BLOCKS"
 
 
 # ---------------------------------------------------------------- builders
-def make_fst(rows, finals, start, props=0):
+def make_flat_fst(rows, finals, start, props=0):
     """rows[s] = [(ilabel, olabel, weight, nextstate), ..]; finals[s] = weight or None"""
     n = len(rows)
     off = np.zeros(n + 1, dtype=np.uint32)
@@ -68,7 +65,7 @@ def renumber(flat, perm):
         rows[perm[s]] = [(int(a["ilabel"]), int(a["olabel"]), float(a["weight"]), int(perm[a["nextstate"]]))
                          for a in arcs[off[s]:off[s + 1]]]
         finals[perm[s]] = None if not np.isfinite(flat["finals"][s]) else float(flat["finals"][s])
-    return make_fst(rows, finals, None if flat["start"] is None else int(perm[flat["start"]]), flat["props"])
+    return make_flat_fst(rows, finals, None if flat["start"] is None else int(perm[flat["start"]]), flat["props"])
 
 
 LADDER_DEGREES = (0, 1, 15, 16, 17, 31, 32, 33, 100)
@@ -124,7 +121,7 @@ def ladder(variant, seed=11):
         rows.append([])
         finals.append(0.75)
         start = n
-    return make_fst(rows, finals, start)
+    return make_flat_fst(rows, finals, start)
 
 
 CHAIN_DEPTHS = (1, 2, 15, 16, 17, 31, 32, 33, 48, 49)
@@ -142,7 +139,7 @@ def chain(d, form, flipped, seed=23):
         assert d >= 2
         rows[d - 1].append((3, 3, grid(rng, 0, 5), 1))
     finals = [None] * (d - 1) + [grid(rng, 0, 5)]
-    f = make_fst(rows, finals, 0)
+    f = make_flat_fst(rows, finals, 0)
     return renumber(f, np.arange(d)[::-1]) if flipped else f
 
 
@@ -156,7 +153,7 @@ def tree(back_arc, seed=31):
     if back_arc:
         rows[400].append((5, 5, 0.5, 0))
     finals = [None] * 101 + [grid(rng, 0, 5) for _ in range(300)]
-    return renumber(make_fst(rows, finals, 0), rng.permutation(401))
+    return renumber(make_flat_fst(rows, finals, 0), rng.permutation(401))
 
 
 def random_cyclic(n, seed):
@@ -164,7 +161,7 @@ def random_cyclic(n, seed):
     rows = [[(int(rng.integers(1, 9)), int(rng.integers(1, 9)), grid(rng, 0, 5), int(rng.integers(0, n)))
              for _ in range(int(rng.integers(0, 5)))] for _ in range(n)]
     finals = [grid(rng, 0, 5) if rng.random() < 0.3 else None for _ in range(n)]
-    return make_fst(rows, finals, 0)
+    return make_flat_fst(rows, finals, 0)
 
 
 def acyclic_dist(rows, n):
@@ -222,7 +219,7 @@ def reduction_fst(n, seed, a, b, total="pos", b_new="weighted", b_eps=False):
         if b != a:
             db = float(acyclic_dist(rows, n)[b])
             finals[b] = t + (1.5 if b_new == "weighted" else (1 / 2048 if b_eps else 0.0)) - db
-    return make_fst(rows, finals, 0)
+    return make_flat_fst(rows, finals, 0)
 
 
 REDUCTION_SIZES = (63, 64, 65, 255, 256, 257, 600)
@@ -392,7 +389,7 @@ def structural_calls(flat):
 
 
 def oracle_dist(oracle, flat, to_final):
-    return tp._oracle_dist(oracle, flat, to_final)
+    return _oracle_dist(oracle, flat, to_final)
 
 
 def restate(oracle, flat, call, facts):
@@ -492,7 +489,7 @@ def facts_cases(n, seed=71):
     finals = [grid(rng, 0, 5) if s % 3 == 0 else None for s in range(n)]
     out = []
     inf = np.full(n, np.inf, dtype=np.float32)
-    out.append(("none", make_fst(rows, finals, 0, FACTS_WORD), inf))
+    out.append(("none", make_flat_fst(rows, finals, 0, FACTS_WORD), inf))
     for s in positions(n, 16):
         r, f = [list(x) for x in rows], list(finals)
         t = r[s][0][3]
@@ -500,13 +497,13 @@ def facts_cases(n, seed=71):
         r[t] = [a for a in r[t] if a[3] not in (s, t)] or [(1, 1, 0.5, 0)]
         pot = inf.copy()
         pot[s], pot[t] = 1.25, -0.75
-        out.append((f"arc@{s}", make_fst(r, f, 0, FACTS_WORD), pot))
+        out.append((f"arc@{s}", make_flat_fst(r, f, 0, FACTS_WORD), pot))
     for s in positions(n):
         f = list(finals)
         f[s] = 0.5
         pot = inf.copy()
         pot[s] = 1.25
-        out.append((f"final@{s}", make_fst(rows, f, 0, FACTS_WORD), pot))
+        out.append((f"final@{s}", make_flat_fst(rows, f, 0, FACTS_WORD), pot))
     return out
 
 

@@ -1,6 +1,6 @@
 """shortest_distance(fst, reverse), reweight and push_weights (wfst_shortest_distance_with_config, wfst_reweight,
 wfst_push_weights): C-ABI surface without a GPU, the K14 known answers, and on the device parity with a restatement of
-rustfst's algorithms/reweight.rs + push.rs (written out below) over the oracle's distances, plus invariants that do not
+rustfst's algorithms/reweight.rs + push.rs (oracle/model/push.py) over the oracle's distances, plus invariants that do not
 depend on that restatement."""
 import ctypes as C
 import inspect
@@ -14,166 +14,23 @@ import pytest
 from rustfst_amd import synth
 from rustfst_amd._lib import TR_DTYPE
 
-from oracle.model import (ACCESSIBLE, ACYCLIC, ALL, ARC_RELEVANT, COACCESSIBLE, CYCLIC, DFS_BITS, F32, INF,
-                          INITIAL_ACYCLIC, INITIAL_CYCLIC, NOT_ACCESSIBLE, WEIGHT_INVARIANT, csr_next, dfs_bits, divide,
-                          graph_facts, is_one, is_zero, p_add_state, p_add_tr, p_set_final, p_set_start, p_set_weight,
-                          reach, times, to_flat, transpose)
-from helpers import ROOT, ko_message, random_fst_flat, to_device, to_oracle
+from oracle.model import (ACCESSIBLE, ACYCLIC, ALL, ARC_RELEVANT, COACCESSIBLE, CYCLIC, DFS_BITS, INITIAL_ACYCLIC,
+                          INITIAL_CYCLIC, NOT_ACCESSIBLE, WEIGHT_INVARIANT, csr_next, dfs_bits, graph_facts, is_one,
+                          is_zero, p_add_state, p_add_tr, p_set_final, p_set_start, push_ref, reach, reverse_len_rule,
+                          reweight_ref, to_flat, transpose)
+from helpers import ROOT, _oracle_dist, assert_same, ko_message, random_fst_flat, to_device, to_oracle
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k14_push.json")
 NEW_SYMBOLS = ("wfst_shortest_distance_with_config", "wfst_push_weights", "wfst_reweight")
 
 
-# ---------------------------------------------------------------- restatement of reweight.rs / push.rs
-def reweight_ref(flat, potentials, to_final, facts=None):
-    """reweight(fst, potentials, type) (reweight.rs:29-154), statement by statement; finals as Option (None / value).
-    Returns a mutable dict: n_states, start, rows (list of [ilabel, olabel, weight, nextstate] lists per state), finals,
-    props."""
-    n, start = flat["n_states"], flat["start"]
-    off, arcs = flat["offsets"], flat["arcs"]
-    rows = [[[int(a["ilabel"]), int(a["olabel"]), F32(a["weight"]), int(a["nextstate"])] for a in arcs[off[s]:off[s + 1]]]
-            for s in range(n)]
-    finals = [None if not np.isfinite(f) else F32(f) for f in flat["finals"]]
-    pot = [F32(x) for x in potentials]
-    p = int(flat["props"])
-    fst = dict(n_states=n, start=start, rows=rows, finals=finals)
-    if n == 0:
-        fst["props"] = p
-        return fst
-    zero = INF
-    for state in range(n):
-        if state >= len(pot):  # :42-53
-            if to_final and finals[state] is not None:
-                new = times(zero, finals[state])
-                p = p_set_final(p, finals[state], new)
-                finals[state] = new
-            continue
-        d_s = pot[state]
-        if is_zero(d_s):  # :57-59
-            continue
-        for tr in rows[state]:  # :61-86
-            d_ns = pot[tr[3]] if tr[3] < len(pot) else zero
-            if is_zero(d_ns):
-                continue
-            w = divide(times(d_s, tr[2]), d_ns) if to_final else divide(times(tr[2], d_ns), d_s)
-            p = p_set_weight(p, tr[2], w)
-            tr[2] = w
-    for s in range(n):  # :88-103
-        fw = finals[s]
-        if fw is None:
-            continue
-        d_s = pot[s] if s < len(pot) else zero
-        if to_final:
-            fw = times(fw, d_s)
-        else:
-            if is_zero(d_s):
-                continue
-            fw = divide(fw, d_s)
-        p = p_set_final(p, finals[s], fw)
-        finals[s] = fw
-    if start is not None:  # :105-146
-        d_s = pot[start] if start < len(pot) else zero
-        if not is_one(d_s) and not is_zero(d_s):
-            if not (p & (INITIAL_CYCLIC | INITIAL_ACYCLIC)):  # compute_and_update_properties(INITIAL_ACYCLIC)
-                p = (p & ~DFS_BITS) | dfs_bits(facts if facts is not None else graph_facts(flat))
-            if p & INITIAL_ACYCLIC:
-                for tr in rows[start]:
-                    w = times(divide(0.0, d_s), tr[2]) if to_final else times(d_s, tr[2])
-                    p = p_set_weight(p, tr[2], w)
-                    tr[2] = w
-                if finals[start] is not None:
-                    fw = times(divide(0.0, d_s), finals[start]) if to_final else times(d_s, finals[start])
-                    p = p_set_final(p, finals[start], fw)
-                    finals[start] = fw
-            else:
-                s = n
-                rows.append([])
-                finals.append(None)
-                p = p_add_state(p)
-                w = divide(0.0, d_s) if to_final else d_s
-                p = p_add_tr(p, s, (0, 0, w, start))
-                rows[s].append([0, 0, w, start])
-                p = p_set_start(p)
-                fst["start"] = s
-                fst["n_states"] = n + 1
-    fst["props"] = p & WEIGHT_INVARIANT & ~COACCESSIBLE  # reweight_properties (mutate_properties.rs:640-644)
-    return fst
-
-
-def remove_weight_ref(fst, weight, at_final):  # push.rs:147-170
-    if is_one(weight) or is_zero(weight):
-        return fst
-    p = fst["props"]
-    if at_final:
-        for s in range(fst["n_states"]):
-            if fst["finals"][s] is not None:
-                fw = divide(fst["finals"][s], weight)
-                p = p_set_final(p, fst["finals"][s], fw)
-                fst["finals"][s] = fw
-    elif fst["start"] is not None:
-        st = fst["start"]
-        for tr in fst["rows"][st]:
-            w = divide(tr[2], weight)
-            p = p_set_weight(p, tr[2], w)
-            tr[2] = w
-        if fst["finals"][st] is not None:
-            fw = divide(fst["finals"][st], weight)
-            p = p_set_final(p, fst["finals"][st], fw)
-            fst["finals"][st] = fw
-    fst["props"] = p
-    return fst
-
-
-def push_ref(flat, dist, to_final, remove_total=False, facts=None):
-    """push_weights_with_config (push.rs:89-118) given the Vec shortest_distance_with_config returns (reverse distances
-    for ToInitial)."""
-    total = None
-    if remove_total:  # compute_total_weight (push.rs:120-142), on the FST before reweight
-        if not to_final:
-            s0 = flat["start"]
-            total = F32(dist[s0]) if s0 is not None and s0 < len(dist) else INF
-        else:
-            total = INF
-            for s, d in enumerate(dist):
-                f = flat["finals"][s]
-                total = min(total, times(d, f if np.isfinite(f) else INF))
-    fst = reweight_ref(flat, dist, to_final, facts)
-    if remove_total:
-        fst = remove_weight_ref(fst, total, to_final)
-    return fst
-
-
-def reverse_len_rule(flat):
-    """rdistance.len() - 1 (shortest_distance.rs:322-334): the reversed search dequeues every state reachable from the
-    super-initial state (the states that reach a final state, + 1) and grows its Vec to the largest of them."""
-    n = flat["n_states"]
-    off, nxt = csr_next(flat)
-    roff, rsrc = transpose(n, off, nxt)
-    finals = np.nonzero(np.isfinite(flat["finals"]))[0]
-    if not finals.size:
-        return 0
-    return int(np.nonzero(reach(n, roff, rsrc, finals))[0].max()) + 1
-
-
-def assert_same(got, exp, what):
-    assert got["n_states"] == exp["n_states"], f"{what}: num_states {got['n_states']} != {exp['n_states']}"
-    assert got["start"] == exp["start"], f"{what}: start"
-    np.testing.assert_array_equal(got["offsets"], exp["offsets"], err_msg=f"{what}: offsets")
-    for k in ("ilabel", "olabel", "nextstate"):
-        np.testing.assert_array_equal(got["arcs"][k], exp["arcs"][k], err_msg=f"{what}: arcs.{k}")
-    np.testing.assert_array_equal(got["arcs"]["weight"].view(np.uint32), exp["arcs"]["weight"].view(np.uint32),
-                                  err_msg=f"{what}: arc weights (bit pattern)")
-    np.testing.assert_array_equal(got["finals"].view(np.uint32), exp["finals"].view(np.uint32),
-                                  err_msg=f"{what}: final weights (bit pattern)")
-    assert got["props"] == exp["props"], f"{what}: props {got['props']:#x} != {exp['props']:#x}"
-
-
+# ---------------------------------------------------------------- inputs
 def golden_cases():
     with open(GOLDEN) as f:
         return json.load(f)["cases"]
 
 
-def golden_flat(c):
+def k14_flat(c):
     arcs = np.array([tuple(a) for a in c["arcs"]], dtype=TR_DTYPE) if c["arcs"] else np.zeros(0, dtype=TR_DTYPE)
     fin = np.array([np.inf if f is None else f for f in c["finals"]], dtype=np.float32)
     return dict(n_states=c["n_states"], start=c["start"], offsets=np.array(c["offsets"], dtype=np.uint32), arcs=arcs,
@@ -240,7 +97,7 @@ def test_python_surface():
 
 
 def _golden_run_ref(c):
-    flat = golden_flat(c)
+    flat = k14_flat(c)
     to_final = c["reweight_type"] == 1
     if c["op"] == "reweight":
         return to_flat(reweight_ref(flat, c["potentials"], to_final))
@@ -264,7 +121,7 @@ def _dev_flat(d):
 def test_k14_on_the_device(gpu_ctx):
     import rustfst_amd
     for c in golden_cases():
-        dev = to_device(golden_flat(c), gpu_ctx)
+        dev = to_device(k14_flat(c), gpu_ctx)
         rt = rustfst_amd.ReweightType(c["reweight_type"])
         if c["op"] == "reweight":
             got = dev.reweight(np.array(c["potentials"], dtype=np.float32), rt)
@@ -339,18 +196,6 @@ def test_reweight_matches_the_restatement(gpu_ctx):
             got = dev.reweight(pot, rustfst_amd.ReweightType(rt)).to_flat()
             exp = to_flat(reweight_ref(flat, list(pot), rt == 1))
             assert_same(got, exp, f"seed {seed} type {rt}")
-
-
-def _oracle_dist(oracle, flat, to_final):
-    o = to_oracle(oracle, flat)
-    if to_final:
-        if flat["start"] is None:
-            return []
-        n = flat["n_states"]
-        off, nxt = csr_next(flat)
-        ln = int(np.nonzero(reach(n, off, nxt, [flat["start"]]))[0].max()) + 1
-        return list(o.shortest_distance()[:ln])
-    return list(o.reverse().shortest_distance()[1:][:reverse_len_rule(flat)])
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """union, concat, closure and the list forms (wfst_union, wfst_concat, wfst_closure, wfst_union_list, wfst_concat_list): the
 C-ABI surface without a GPU, a literal sequential Python restatement of rustfst's union_static.rs, concat_static.rs and
 closure_static.rs with the property functions they call (union_properties, concat_properties, closure_properties,
-compute_and_update_properties(INITIAL_ACYCLIC)) written out below and checked against the hand-derived K18 known answers,
+compute_and_update_properties(INITIAL_ACYCLIC)) (oracle/model/rational.py) checked against the hand-derived K18 known answers,
 the closed forms of the list folds checked against the literal folds, and on the device bit-exact parity with the
 restatement: states, offsets, arcs (weights by bit pattern), finals, start state and property word.
 
@@ -23,167 +23,27 @@ import numpy as np
 import pytest
 
 from oracle import model
-from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, B, COACCESSIBLE, EPSILONS, INITIAL_ACYCLIC, I_EPSILONS,
-                          O_EPSILONS, closure_properties, compute_initial_acyclic, concat_properties, content_word,
-                          fst_to_flat, m_add_state, m_add_tr, m_set_final, m_set_props, m_set_start, union_properties)
-from helpers import assert_flat_identical, enumerate_paths, ko_message, to_device
-import test_minimize as tm
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, EPSILONS, INITIAL_ACYCLIC, I_EPSILONS,
+                          MSG_ACYCLIC, O_EPSILONS, PLUS, STAR, closure_ref, concat_list_closed, concat_properties,
+                          concat_ref, content_word, fold_ref, fst_to_flat, m_add_state, m_add_tr, m_set_final,
+                          m_set_start, norm, optimize_ref, union_list_closed, union_properties, union_ref)
+from helpers import (_vector_fst, assert_flat_identical, dev, enumerate_paths, golden_fst, ko_message, make_fst,
+                     to_device)
+import minimize_cases as mc
+from inputs import chain
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k18_rational.json")
 NEW_SYMBOLS = ("wfst_union", "wfst_concat", "wfst_closure", "wfst_union_list", "wfst_concat_list")
 F32, INF = np.float32, np.float32(np.inf)
-ONE = F32(0.0)
 TILE = 256  # rustfst_amd/csrc/rational.hip
-STAR, PLUS = 0, 1  # closure/mod.rs:9-12
 MAX_STATES, MAX_ARCS = 2 ** 31 - 2, 2 ** 32 - 1
 
 
-# ---------------------------------------------------------------- the restatement: the three algorithms, in place on fst_1
-def union_ref(f1, f2):  # union/union_static.rs:55-118
-    ia1 = compute_initial_acyclic(f1)
-    props1, props2 = f1["props"], f2["props"]
-    n1 = len(f1["rows"])
-    start2 = f2["start"]
-    if start2 is None:
-        return f1
-    for s2 in range(len(f2["rows"])):
-        s1 = m_add_state(f1)
-        if f2["finals"][s2] is not None:
-            m_set_final(f1, s1, f2["finals"][s2])
-        for il, ol, w, ns in f2["rows"][s2]:
-            m_add_tr(f1, s1, [il, ol, w, ns + n1])
-    start1 = f1["start"]
-    if start1 is None:
-        m_set_start(f1, start2)  # (:89) without the offset
-        m_set_props(f1, props2)  # copy_properties() holds every trinary bit (properties.rs:130-163)
-        return f1
-    if ia1:
-        m_add_tr(f1, start1, [0, 0, ONE, start2 + n1])
-    else:
-        nstart = m_add_state(f1)
-        m_set_start(f1, nstart)
-        m_add_tr(f1, nstart, [0, 0, ONE, start1])
-        m_add_tr(f1, nstart, [0, 0, ONE, start2 + n1])
-    m_set_props(f1, union_properties(props1, props2))
-    return f1
-
-
-def concat_ref(f1, f2):  # concat/concat_static.rs:53-109
-    props1, props2 = f1["props"], f2["props"]
-    if f1["start"] is None:
-        return f1
-    n1 = len(f1["rows"])
-    for s2 in range(len(f2["rows"])):
-        s1 = m_add_state(f1)
-        if f2["finals"][s2] is not None:
-            m_set_final(f1, s1, f2["finals"][s2])
-        for il, ol, w, ns in f2["rows"][s2]:
-            m_add_tr(f1, s1, [il, ol, w, ns + n1])
-    start2 = f2["start"]
-    for s1 in range(n1):
-        w = f1["finals"][s1]
-        if w is not None:
-            if start2 is not None:
-                m_add_tr(f1, s1, [0, 0, w, start2 + n1])
-            m_set_final(f1, s1, None)
-    if start2 is not None:
-        m_set_props(f1, concat_properties(props1, props2))
-    return f1
-
-
-def closure_ref(f, closure_type):  # closure/closure_static.rs:25-73
-    props = f["props"]
-    if f["start"] is not None:
-        for s, w in [(s, w) for s, w in enumerate(f["finals"]) if w is not None]:
-            m_add_tr(f, s, [0, 0, w, f["start"]])
-    if closure_type == STAR:
-        nstart = m_add_state(f)
-        if f["start"] is not None:
-            m_add_tr(f, nstart, [0, 0, ONE, f["start"]])
-        m_set_start(f, nstart)
-        m_set_final(f, nstart, ONE)
-    m_set_props(f, closure_properties(props))
-    return f
-
-
-def fold_ref(op, fsts):  # rustfst-python union_list / concat_list (algorithms/union.py:47-64, concat.py)
-    if not fsts:
-        raise ValueError("fsts must be at least of len 1")
-    acc = copy.deepcopy(fsts[0])
-    for f in fsts[1:]:
-        acc = op(acc, f)
-    return acc
-
-
-# ---------------------------------------------------------------- the closed forms of the folds (structure only)
-def union_list_closed(fsts):
-    """fsts[0] has a start state: states i_0, i_1, the new state if fsts[0] is not initial-acyclic, i_2, ...; the root's
-    row = (its own arcs | 0:0/One -> start(i_0)) + 0:0/One -> base_k + start(i_k)"""
-    first = copy.deepcopy(fsts[0])
-    ia = compute_initial_acyclic(first)
-    items = [fsts[0]] + [f for f in fsts[1:] if f["start"] is not None]
-    if len(items) == 1:
-        return first["rows"], first["finals"], first["start"]
-    rows, finals, bases = [], [], []
-    new_state = None
-    for k, f in enumerate(items):
-        if not ia and k == 2:
-            new_state = len(rows)
-            rows.append(None)
-            finals.append(None)
-        bases.append(len(rows))
-        rows += [[[il, ol, w, ns + bases[k]] for il, ol, w, ns in row] for row in f["rows"]]
-        finals += list(f["finals"])
-    if not ia and new_state is None:
-        new_state = len(rows)
-        rows.append(None)
-        finals.append(None)
-    extra = [[0, 0, ONE, bases[k] + items[k]["start"]] for k in range(1, len(items))]
-    if ia:
-        root = items[0]["start"]
-        rows[root] = rows[root] + extra
-    else:
-        root = new_state
-        rows[root] = [[0, 0, ONE, items[0]["start"]]] + extra
-    return rows, finals, root
-
-
-def concat_list_closed(fsts):
-    """every item has a start state: all states one after the other; a final state of item k < n - 1 gets
-    0:0/w -> base_{k+1} + start_{k+1} and loses its final weight"""
-    bases = np.concatenate([[0], np.cumsum([len(f["rows"]) for f in fsts])]).tolist()
-    rows, finals = [], []
-    for k, f in enumerate(fsts):
-        for s, row in enumerate(f["rows"]):
-            row = [[il, ol, w, ns + bases[k]] for il, ol, w, ns in row]
-            w = f["finals"][s]
-            if w is not None and k + 1 < len(fsts):
-                row.append([0, 0, w, bases[k + 1] + fsts[k + 1]["start"]])
-                w = None
-            rows.append(row)
-            finals.append(w)
-    return rows, finals, fsts[0]["start"]
-
-
 # ---------------------------------------------------------------- inputs
-def names_to_word(names):
-    return sum(1 << B[n] for n in names)
-
-
 def golden():
     with open(GOLDEN) as f:
         return json.load(f)
-
-
-def golden_fst(m):
-    return dict(rows=[[[il, ol, F32(w), ns] for il, ol, w, ns in row] for row in m["rows"]],
-                finals=[None if w is None else F32(w) for w in m["finals"]], start=m["start"], props=names_to_word(m["props"]))
-
-
-def make_fst(rows, finals, start, props=0):
-    return dict(rows=[[[il, ol, F32(w), ns] for il, ol, w, ns in row] for row in rows],
-                finals=[None if w is None else F32(w) for w in finals], start=start, props=props)
 
 
 def run_ref(op, args, closure_type=None):
@@ -233,14 +93,6 @@ def shape_fst(name, rng):
         return make_fst([[arc(1), arc(2)], [arc(2)], []], [0.0, 0.5, 1.5], 0)
     assert name == "none_final"
     return make_fst([[arc(1), arc(2)], [arc(2)], []], [None, None, None], 0)
-
-
-def chain(n, rng, finals_from=None, fan=1, start=0):
-    """n states; state s has `fan` arcs into later states (none from the last); finals at states >= finals_from"""
-    rows = [[[int(rng.integers(1, 9)), int(rng.integers(1, 9)), float(rng.integers(0, 16)) / 8,
-              int(rng.integers(s + 1, n))] for _ in range(fan)] if s + 1 < n else [] for s in range(n)]
-    ff = n - 1 if finals_from is None else finals_from
-    return make_fst(rows, [float(rng.integers(0, 8)) / 4 if s >= ff else None for s in range(n)], start)
 
 
 def fat_row(k, rng):
@@ -430,10 +282,6 @@ def test_closed_forms_equal_the_literal_folds():
 
 
 # ================================================================ GPU
-def dev(fst, ctx):
-    return to_device(fst_to_flat(fst), ctx)
-
-
 def run_dev(op, handles, closure_type=None):
     import rustfst_amd
     if op == "union":
@@ -594,10 +442,9 @@ def test_operand_still_answers_shortest_path(gpu_ctx):
 def test_union_of_nbest_paths_then_optimize(gpu_ctx, oracle):
     """the use this was built for: the n best paths of a lattice as strings, their union, optimize"""
     import rustfst_amd
-    import test_optimize as to
     rng = np.random.default_rng(1806)
     word = ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | ACCESSIBLE | COACCESSIBLE
-    lattice = tm.random_dag(rng, 12, 4)
+    lattice = mc.random_dag(rng, 12, 4)
     paths = sorted(enumerate_paths(lattice))[:5]  # (the lattice is deterministic: distinct paths, distinct strings)
     assert len(paths) == 5
     strings = []
@@ -611,18 +458,18 @@ def test_union_of_nbest_paths_then_optimize(gpu_ctx, oracle):
     assert_flat_identical(union.to_flat(), union_flat, "union_list(n-best)", check_props=True)
     # optimize straight away is KO here as in the restatement: union_properties never holds TOP_SORTED, and without it the
     # set_trs bookkeeping of rm_epsilon (rm_epsilon_static.rs:148-167) drops ACYCLIC, which wfst_optimize's step 4 needs
-    with pytest.raises(model.Unsupported, match=re.escape(to.MSG_ACYCLIC)):
-        to.optimize_ref(union_flat, oracle)
-    with pytest.raises(rustfst_amd.WfstError, match=re.escape(to.MSG_ACYCLIC)):
+    with pytest.raises(model.Unsupported, match=re.escape(MSG_ACYCLIC)):
+        optimize_ref(union_flat, oracle)
+    with pytest.raises(rustfst_amd.WfstError, match=re.escape(MSG_ACYCLIC)):
         union.optimize()
     # the caller knows that a union of acyclic machines is acyclic: rm_epsilon, ACYCLIC back into the word, optimize
     no_eps = union.rm_epsilon().to_flat()
-    no_eps_ref = to.norm(to_oracle(oracle, to.norm(union_flat)).rm_epsilon().to_flat())
-    assert_flat_identical(to.norm(no_eps), no_eps_ref, "rm_epsilon(union_list(n-best))", check_props=True)
+    no_eps_ref = norm(to_oracle(oracle, norm(union_flat)).rm_epsilon().to_flat())
+    assert_flat_identical(norm(no_eps), no_eps_ref, "rm_epsilon(union_list(n-best))", check_props=True)
     got = to_device(dict(no_eps, props=no_eps["props"] | ACYCLIC), gpu_ctx).optimize()
-    exp = to.optimize_ref(dict(no_eps_ref, props=no_eps_ref["props"] | ACYCLIC), oracle)
+    exp = optimize_ref(dict(no_eps_ref, props=no_eps_ref["props"] | ACYCLIC), oracle)
     assert exp["n_states"] < union_flat["n_states"]
-    assert_flat_identical(to.norm(got.to_flat()), to.norm(exp), "optimize(rm_epsilon(union_list(n-best)))", check_props=True)
+    assert_flat_identical(norm(got.to_flat()), norm(exp), "optimize(rm_epsilon(union_list(n-best)))", check_props=True)
 
 
 @pytest.mark.gpu
@@ -652,22 +499,6 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx):
     exp = fst_to_flat(union_ref(string3(), string3(1.5)))
     assert_flat_identical(a.union(b).to_flat(), exp, "union after the KOs", check_props=True)
     assert_flat_identical(foreign.union(dev(string3(1.5), other)).to_flat(), exp, "union on the other context", check_props=True)
-
-
-def _vector_fst(m):
-    import rustfst_amd
-    f = rustfst_amd.VectorFst()
-    for _ in m["rows"]:
-        f.add_state()
-    if m["start"] is not None:
-        f.set_start(m["start"])
-    for s, w in enumerate(m["finals"]):
-        if w is not None:
-            f.set_final(s, float(w))
-    for s, row in enumerate(m["rows"]):
-        for il, ol, w, ns in row:
-            f.add_tr(s, rustfst_amd.Tr(il, ol, float(w), ns))
-    return f
 
 
 @pytest.mark.gpu

@@ -14,10 +14,9 @@ import numpy as np
 import pytest
 
 from oracle import model
-from oracle.model import ALL, F32, I_LABEL_SORTED, O_LABEL_SORTED, fst_to_flat
-from oracle.model.props import B
+from oracle.model import ALL, I_LABEL_SORTED, O_LABEL_SORTED, fst_to_flat
 import helpers
-from helpers import ROOT, assert_flat_identical, enumerate_paths
+from helpers import ROOT, assert_flat_identical, dev, enumerate_paths, golden_fst, make_fst
 from replace_ref import Diverged, ReplaceError, replace_ref
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "k20_replace.json")
@@ -32,22 +31,6 @@ KEY0 = 50  # FST i of a random grammar has the label KEY0 + 2 i: the odd labels 
 def golden():
     with open(GOLDEN) as f:
         return json.load(f)
-
-
-def make_fst(rows, finals, start, props=0):
-    return dict(rows=[[[il, ol, F32(w), ns] for il, ol, w, ns in row] for row in rows],
-                finals=[None if w is None else F32(w) for w in finals], start=start, props=props)
-
-
-def golden_fst(m):
-    word = 0
-    for name in m["props"]:
-        word |= 1 << B[name]
-    return make_fst(m["rows"], m["finals"], m["start"], word)
-
-
-def dev(fst, ctx):
-    return helpers.to_device(fst_to_flat(fst), ctx)
 
 
 def probe_dag(n, rng):

@@ -17,18 +17,20 @@ import numpy as np
 import pytest
 
 from rustfst_amd._lib import TR_DTYPE
-
-import test_determinize as td
-import test_rm_epsilon as tre
-from oracle.model import ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, INITIAL_ACYCLIC, fst_to_flat
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, INITIAL_ACYCLIC, fold_ref, fst_to_flat,
+                          union_ref)
 import helpers
-from helpers import assert_flat_identical, enumerate_paths, random_fst_flat, to_device, to_oracle
-from test_rm_epsilon import Builder, chain, fan, par, rm_epsilon_model, wide
+from helpers import (assert_flat_identical, empty_flat, enumerate_paths, make_fst, random_fst_flat, to_device,
+                     to_oracle)
+import determinize_cases as dc
+import minimize_cases as mc
+import rm_epsilon_cases as rc
+from rm_epsilon_cases import Builder, chain, fan, par, rm_epsilon_model, wide
 
 ROOT = helpers.ROOT
 INF = np.float32(np.inf)
 MAX_STATES, MAX_ARCS = 4096, 16384  # include/wfst.h: the in_kernel rule of wfst_rm_epsilon_batch
-CAPS = tre.THREAD_RUNGS[-1]         # ... and the last rung of the single call's one-thread kernel
+CAPS = rc.THREAD_RUNGS[-1]         # ... and the last rung of the single call's one-thread kernel
 NEW_SYMBOLS = ("wfst_rm_epsilon_batch", "wfst_ctx_get_rm_epsilon_batch_stats")
 
 
@@ -124,7 +126,7 @@ def limit_families():
            ("closure 64 (chain)", chain(63), 1), ("closure 65 (chain)", chain(64), 0),
            ("stack 128", par(128), 1), ("stack 129", par(129), 0),
            ("arcs of a state 128", wide(128), 1), ("arcs of a state 129", wide(129), 0),
-           ("self loop", tre.value_cases()["self_loop"][0], 0), ("two-cycle", two_cycle(), 0)]
+           ("self loop", rc.value_cases()["self_loop"][0], 0), ("two-cycle", two_cycle(), 0)]
     edges = {"closure 64 (fan)": (64, 63, 63), "closure 65 (fan)": (65, 64, 64), "closure 64 (chain)": (64, 1, 1),
              "closure 65 (chain)": (65, 1, 1), "stack 128": (2, 128, 1), "stack 129": (2, 129, 1),
              "arcs of a state 128": (2, 1, 128), "arcs of a state 129": (2, 1, 129)}
@@ -134,12 +136,7 @@ def limit_families():
     return out
 
 
-def empty_flat(props=0):
-    return dict(n_states=0, start=-1, offsets=np.zeros(1, np.uint32), arcs=np.zeros(0, TR_DTYPE),
-                finals=np.zeros(0, np.float32), props=props)
-
-
-def golden_flat():
+def k11_flat():
     with open(os.path.join(ROOT, "tests", "golden", "k11_rm_epsilon.json")) as fh:
         g = json.load(fh)["fst"]
     rows = [[] for _ in range(g["n_states"])]
@@ -154,25 +151,23 @@ def golden_flat():
 
 def nbest_union_flat():
     """test_rational_ops' pipeline: the five best paths of a lattice as strings, their union (epsilon arcs from the start)"""
-    import test_minimize as tm
-    import test_rational_ops as tro
     rng = np.random.default_rng(1806)
     word = ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | ACCESSIBLE | COACCESSIBLE
-    lattice = tm.random_dag(rng, 12, 4)
+    lattice = mc.random_dag(rng, 12, 4)
     paths = sorted(enumerate_paths(lattice))[:5]
     strings = []
     for w, il, _ in paths:
         il = list(il) or [1]
         rows = [[[x, x, w if i == 0 else 0.0, i + 1]] for i, x in enumerate(il)] + [[]]
-        strings.append(tro.make_fst(rows, [None] * len(il) + [0.0], 0, word))
-    return fst_to_flat(tro.fold_ref(tro.union_ref, strings))
+        strings.append(make_fst(rows, [None] * len(il) + [0.0], 0, word))
+    return fst_to_flat(fold_ref(union_ref, strings))
 
 
 @functools.lru_cache(maxsize=None)
 def parity_items():
     """[(name, flat)]: the mixed batch"""
     rng = np.random.default_rng(2611)
-    items = [("k11", golden_flat())]
+    items = [("k11", k11_flat())]
     for k, p in enumerate((0.1, 0.2, 0.3, 0.4, 0.5) * 3):
         acyclic = k % 3 != 2
         f = random_fst_flat(rng, int(rng.integers(5, 60)), 3, 3, p_eps_i=p, p_eps_o=p, p_final=0.3, acyclic=acyclic,
@@ -183,10 +178,10 @@ def parity_items():
             f["arcs"]["olabel"] = f["arcs"]["ilabel"]
         items.append(("random %d p %.1f %s %s" % (k, p, "acyclic" if acyclic else "cyclic", "acceptor" if k % 2 == 0 else "transducer"), f))
     items.append(("union of n-best", nbest_union_flat()))
-    items += tre.props_random_inputs()[:6] + tre.props_hand_made()  # words with / without TOP_SORTED and ACCEPTOR
+    items += rc.props_random_inputs()[:6] + rc.props_hand_made()  # words with / without TOP_SORTED and ACCEPTOR
     items.append(("no start", dict(fan(15), start=-1)))
-    items.append(("no states", empty_flat()))
-    items.append(("no arcs", tre.value_cases()["start_without_arcs"][0]))
+    items.append(("no states", empty_flat(start=-1)))
+    items.append(("no arcs", rc.value_cases()["start_without_arcs"][0]))
     b = Builder()
     root, u, v = b.state(), b.state(), b.state()
     b.eps(root, 3, u)
@@ -195,7 +190,7 @@ def parity_items():
     f = random_fst_flat(rng, 30, 3, 3, p_final=0.3, acyclic=True)
     f["finals"][-1] = 1.0
     items.append(("no epsilon at all", f))
-    items += [(name, flat) for name, (flat, _) in sorted(tre.value_cases().items())]
+    items += [(name, flat) for name, (flat, _) in sorted(rc.value_cases().items())]
     return items
 
 
@@ -289,7 +284,7 @@ def test_limit_families_sit_on_their_edges():
 
 
 def test_prediction_of_the_degenerate_items():
-    assert predict_in_kernel(empty_flat()) == 1 and predict_in_kernel(dict(fan(64), start=-1)) == 1
+    assert predict_in_kernel(empty_flat(start=-1)) == 1 and predict_in_kernel(dict(fan(64), start=-1)) == 1
     assert predict_in_kernel(dict(long_chain(MAX_STATES + 1), start=None)) == 1
     items = dict(parity_items())
     assert predict_in_kernel(items["k11"]) == 0  # (an epsilon self loop)
@@ -312,7 +307,7 @@ def chain_lattices():
     rng = np.random.default_rng(67)
     lats = []
     while len(lats) < 32:
-        f = td.random_acceptor(rng, int(rng.integers(10, 50)), 3, 3, p_eps_i=0.2, acyclic=True, weight_grid=1, max_w=4)
+        f = dc.random_acceptor(rng, int(rng.integers(10, 50)), 3, 3, p_eps_i=0.2, acyclic=True, weight_grid=1, max_w=4)
         f["finals"][-1] = 0.0
         if (f["arcs"]["ilabel"] == 0).any():
             lats.append(f)

@@ -95,14 +95,14 @@ def test_seeded_batches_fit_the_kernel():
 def test_limit_machines_sit_where_the_tests_say():
     # a level of exactly 64 states, and of 65
     for n, fits in ((64, True), (65, False)):
-        c, info, widths = B.reference(B.string([7]), B.fan_grammar(n), (B.SG, 0, None))
+        c, info, widths = B.reference(B.weighted_string([7]), B.fan_grammar(n), (B.SG, 0, None))
         assert widths == [1, n] and B.in_kernel(info, widths) == fits
     # 70 sigma arcs into 10 states: a sigma range longer than a chunk, a level of 10
-    c, info, widths = B.reference(B.string([7]), B.fan_grammar(70, 10), (B.SG, 0, None))
+    c, info, widths = B.reference(B.weighted_string([7]), B.fan_grammar(70, 10), (B.SG, 0, None))
     assert widths == [1, 10] and info["sigma_arcs"] == 70
     # composed states exactly at the slice, and one beyond
     for m, states in ((57, B.SLICE), (56, B.SLICE + 1)):
-        c, info, widths = B.reference(B.string(B.SLICE_STRING), B.slice_grammar(m), (B.SG, 0, None))
+        c, info, widths = B.reference(B.weighted_string(B.SLICE_STRING), B.slice_grammar(m), (B.SG, 0, None))
         assert info["states"] == states and max(widths) <= B.WIDTH and B.in_kernel(info, widths) == (states <= B.SLICE)
     # the run of label 300 crosses the first 64-arc chunk of the block
     for n_arcs, sigma_first in ((65, True), (200, True), (200, False)):
@@ -113,7 +113,7 @@ def test_limit_machines_sit_where_the_tests_say():
     pos = [k for k, a in enumerate(t["rows"][0]) if a[0] == sigma]
     assert pos == [62, 63, 64]
     # the tie: both ways into state 3 weigh the same, the first in emission order carries olabel 5
-    c, info, widths = B.reference(B.string([2, 9]), B.tie_grammar(), (B.SG, 2, None))
+    c, info, widths = B.reference(B.weighted_string([2, 9]), B.tie_grammar(), (B.SG, 2, None))
     assert widths == [1, 2, 1] and [a[1] for r in c["rows"][1:3] for a in r] == [5, 6]
     assert c["rows"][1][0][2] == c["rows"][2][0][2] and c["rows"][0][0][2] == c["rows"][0][1][2]
 

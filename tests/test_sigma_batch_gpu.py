@@ -14,9 +14,10 @@ import pytest
 import rustfst_amd
 from rustfst_amd import ComposeConfig, ComposeFilter, MatcherConfig, MatcherRewriteMode, WfstError, _lib
 
-from oracle.model import I_LABEL_SORTED, O_LABEL_SORTED, fst_to_flat
+from oracle.model import I_LABEL_SORTED, O_LABEL_SORTED
 
 import helpers
+from helpers import dev
 import sigma_batch_cases as B
 import sigma_cases as S
 import sigma_ref as R
@@ -25,10 +26,6 @@ pytestmark = pytest.mark.gpu
 INF = np.inf
 BAD_LABEL = "SigmaMatcher::Find: bad label (sigma)"
 ITEM_COUNTERS = ("exact_items", "sigma_items", "sigma_arcs", "refused_items")
-
-
-def dev(fst, ctx):
-    return helpers.to_device(fst_to_flat(fst), ctx)
 
 
 def matcher(m):
@@ -120,25 +117,25 @@ def test_cpp_sigma_batch_tests_run(gpu_ctx, tmp_path):
 
 # ---------------------------------------------------------------- dedup, ties and the limits
 def test_tie_keeps_the_first_parent_in_emission_order(gpu_ctx, oracle):
-    got, _, st = run_batch(gpu_ctx, [B.string([2, 9])], B.tie_grammar(), (B.SG, 2, None))
-    check_batch(gpu_ctx, oracle, [B.string([2, 9])], B.tie_grammar(), (B.SG, 2, None), "tie")
+    got, _, st = run_batch(gpu_ctx, [B.weighted_string([2, 9])], B.tie_grammar(), (B.SG, 2, None))
+    check_batch(gpu_ctx, oracle, [B.weighted_string([2, 9])], B.tie_grammar(), (B.SG, 2, None), "tie")
     assert st["items_in_kernel"] == 1 and st["max_level_width"] == 2
     assert sorted(got[0]["arcs"]["olabel"].tolist()) == [2, 5]  # (through state 1, whose sigma arc says 5)
 
 
 def test_level_of_64_states_and_65(gpu_ctx, oracle):
-    st = check_batch(gpu_ctx, oracle, [B.string([7])], B.fan_grammar(64), (B.SG, 0, None), "64 wide")
+    st = check_batch(gpu_ctx, oracle, [B.weighted_string([7])], B.fan_grammar(64), (B.SG, 0, None), "64 wide")
     assert (st["items_in_kernel"], st["items_handed_back"], st["max_level_width"], st["sigma_arcs"]) == (1, 0, 64, 64)
-    st = check_batch(gpu_ctx, oracle, [B.string([7])], B.fan_grammar(65), (B.SG, 0, None), "65 wide")
+    st = check_batch(gpu_ctx, oracle, [B.weighted_string([7])], B.fan_grammar(65), (B.SG, 0, None), "65 wide")
     assert (st["items_in_kernel"], st["items_handed_back"], st["launches"]) == (0, 1, 1)
-    st = check_batch(gpu_ctx, oracle, [B.string([7])], B.fan_grammar(70, 10), (B.SG, 0, None), "70 sigma arcs, 10 states")
+    st = check_batch(gpu_ctx, oracle, [B.weighted_string([7])], B.fan_grammar(70, 10), (B.SG, 0, None), "70 sigma arcs, 10 states")
     assert (st["items_in_kernel"], st["max_level_width"], st["sigma_arcs"]) == (1, 10, 70)
 
 
 def test_composed_states_at_the_slice_and_one_beyond(gpu_ctx, oracle):
-    st = check_batch(gpu_ctx, oracle, [B.string(B.SLICE_STRING)], B.slice_grammar(57), (B.SG, 0, None), "slice")
+    st = check_batch(gpu_ctx, oracle, [B.weighted_string(B.SLICE_STRING)], B.slice_grammar(57), (B.SG, 0, None), "slice")
     assert (st["items_in_kernel"], st["items_handed_back"]) == (1, 0)
-    st = check_batch(gpu_ctx, oracle, [B.string(B.SLICE_STRING)], B.slice_grammar(56), (B.SG, 0, None), "slice + 1")
+    st = check_batch(gpu_ctx, oracle, [B.weighted_string(B.SLICE_STRING)], B.slice_grammar(56), (B.SG, 0, None), "slice + 1")
     assert (st["items_in_kernel"], st["items_handed_back"]) == (0, 1)
 
 
@@ -147,7 +144,7 @@ def test_arc_blocks_longer_than_a_chunk(gpu_ctx, oracle, n_arcs, sigma_first):
     t, sigma = B.long_block_grammar(n_arcs, sigma_first)
     labels = sorted({a[0] for a in t["rows"][0]} - {sigma})
     # the run across the chunk boundary, the block's first, last and 64th label, and labels only sigma answers
-    strs = [B.string([l]) for l in (300, labels[0], labels[-1], t["rows"][0][64][0] if t["rows"][0][64][0] != sigma else 300, 7, 9999)]
+    strs = [B.weighted_string([l]) for l in (300, labels[0], labels[-1], t["rows"][0][64][0] if t["rows"][0][64][0] != sigma else 300, 7, 9999)]
     exact = 4 if 300 in labels else 2  # (65 arcs with sigma at the tail: the block ends before the run, sigma answers 300)
     for rw in (0, 2):
         st = check_batch(gpu_ctx, oracle, strs, t, (sigma, rw, None), "%d arcs rw=%d" % (n_arcs, rw))
@@ -259,7 +256,7 @@ def test_degenerate_inputs(gpu_ctx, oracle):
     strs, g, m2 = B.k21_batch()
     got, n_arcs, st = run_batch(gpu_ctx, [], g, m2)
     assert (got, n_arcs) == ([], 0) and st == dict.fromkeys(_lib.SIGMA_BATCH_COUNTERS, 0)
-    empty_string = B.string([], final=0.25)
+    empty_string = B.weighted_string([], final=0.25)
     no_start = dict(S.chain_query([2, 3, 5]), start=None)
     no_path = S.chain_query([2, 3])  # (ends in state 2 of the grammar, which is not final)
     final_start = S.machine([[(1, 1, 0.5, 1)], []], [0.75, 0.0])  # a grammar whose start state is final: the empty string has a path

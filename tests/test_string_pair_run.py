@@ -11,68 +11,22 @@ level, the slice limit.
 
 Every case is answered five ways and compared bit for bit — pair levels on, WFST_STRING_PAIR=0, WFST_STRING_RUN=0, the general
 kernel (WFST_STRING_KERNEL=0), the oracle: path arcs, weights and final weight of every string, the composed states and arcs
-of the call — and both counter sets are compared with the walk, so a pair path that is silently off fails the test.
-
-This module restates the few generators and the slice rule it shares with the other string-kernel tests instead of importing
-them: a test module is nobody's library (test_host.test_nobody_imports_a_test_module)."""
+of the call — and both counter sets are compared with the walk, so a pair path that is silently off fails the test."""
 import collections
 import functools
 
 import numpy as np
 import pytest
 
-from rustfst_amd._lib import TR_DTYPE
 from rustfst_amd import synth
 
 import helpers
-from helpers import NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, assert_flat_identical, to_device, to_oracle
+from helpers import analyse_string, assert_flat_identical, finals_of, fst, string, to_device, wstring
+from string_cases import RUN_BLOCK, STR_LEVEL, STR_MAXS, STR_SCALAR_MAX_N, string_slice
 
 INF = float("inf")
-RUN_BLOCK = 64               # fc <= 64u
-STR_MAXS, STR_LEVEL = 2048, 64
-STR_SLICES = (512, 1024, 2048)
-STR_PACKED_MIN, STR_SCALAR_MAX_N = 16, 8
 ZERO_RUN = dict(run_levels=0, runs=0)
 ZERO_PAIR = dict(pair_levels=0, pair_splits=0)
-
-
-# ================================================================ inputs
-def fst(rows, finals):
-    """rows[s] = [(ilabel, olabel, weight, nextstate)], start state 0; the property word states label sortedness truthfully"""
-    n = len(rows)
-    offsets = np.zeros(n + 1, dtype=np.uint32)
-    offsets[1:] = np.cumsum([len(r) for r in rows])
-    flat_rows = [a for r in rows for a in r]
-    arcs = np.array(flat_rows, dtype=TR_DTYPE) if flat_rows else np.zeros(0, dtype=TR_DTYPE)
-    il = all(all(r[i][0] <= r[i + 1][0] for i in range(len(r) - 1)) for r in rows)
-    ol = all(all(r[i][1] <= r[i + 1][1] for i in range(len(r) - 1)) for r in rows)
-    props = (synth.I_LABEL_SORTED if il else NOT_I_LABEL_SORTED) | (synth.O_LABEL_SORTED if ol else NOT_O_LABEL_SORTED)
-    return dict(n_states=n, start=0, offsets=offsets, arcs=arcs, finals=np.asarray(finals, dtype=np.float32), props=props)
-
-
-def finals_of(n, where):
-    f = np.full(n, np.inf, dtype=np.float32)
-    for s, w in where.items():
-        f[s] = w
-    return f
-
-
-def string(labels, final_weight=0.0):
-    return synth.linear_acceptor_flat(np.asarray(labels, dtype=np.uint32), final_weight)
-
-
-def wstring(labels, weights, final_weight=0.0):
-    """a string whose arcs carry weights"""
-    L = len(labels)
-    rows = [[(int(labels[i]), int(labels[i]), float(weights[i]), i + 1)] for i in range(L)] + [[]]
-    return fst(rows, finals_of(L + 1, {L: final_weight}))
-
-
-def string_slice(n_eligible, max_states, unpacked):
-    """states per problem of the string kernel's LDS slice: packed batches of >= 16 take the least slice >= 2 * states + 64"""
-    if unpacked or n_eligible < STR_PACKED_MIN:
-        return STR_MAXS
-    return next(m for m in STR_SLICES if 2 * max_states + 64 <= m or m == STR_MAXS)
 
 
 # ================================================================ the prediction
@@ -96,7 +50,7 @@ def walk(labels, t, maxs, pairs=True):
         is_run = on and F == 1 and t_ == 1
         carried = is_run or (on and pairs and F <= 2 and blocks_ok and pos + 1 < L and 1 <= t_ <= 2 and len(new) == t_
                              and hi + t_ < maxs)
-        # the run level as test_string_run.walk states it, without the state `on`
+        # the run level as string_cases.walk states it, without the state `on`
         assert is_run == (F == 1 and blocks_ok and pos + 1 < L and hi + 1 < maxs and t_ == 1)
         if is_run:
             c["run_levels"] += 1
@@ -172,19 +126,6 @@ def predict(strs, t, scalar, unpacked):
     return run, pair, answered, back
 
 
-_AN = {}
-
-
-def analyse(oracle, a, t):
-    """the oracle's untrimmed composition (states, arcs) and its canonical shortest path"""
-    key = (id(a), id(t))
-    if key not in _AN:
-        c = to_oracle(oracle, a).compose(to_oracle(oracle, t), connect=False, compose_filter=0)
-        cf = c.to_flat()
-        _AN[key] = dict(a=a, t=t, n_states=cf["n_states"], n_arcs=len(cf["arcs"]), path=c.shortest_path_canonical().to_flat())
-    return _AN[key]
-
-
 MODES = (("pair", {}), ("no_pair", {"WFST_STRING_PAIR": "0"}), ("no_run", {"WFST_STRING_RUN": "0"}),
          ("general", {"WFST_STRING_KERNEL": "0"}))
 KNOBS = ("WFST_STRING_PAIR", "WFST_STRING_RUN", "WFST_STRING_KERNEL", "WFST_STRING_SCALAR", "WFST_STRING_UNPACKED")
@@ -193,7 +134,7 @@ KNOBS = ("WFST_STRING_PAIR", "WFST_STRING_RUN", "WFST_STRING_KERNEL", "WFST_STRI
 def five_ways(ctx, oracle, monkeypatch, strs, t, sizes, scalar=None, unpacked=False, min_pair_levels=1, handed_back=0):
     import rustfst_amd
     dt, handles = to_device(t, ctx), rustfst_amd.DeviceFst.upload_many(strs, ctx)
-    ans = [analyse(oracle, s, t) for s in strs]
+    ans = [analyse_string(oracle, s, t) for s in strs]
     seen = 0
     for n in sizes:
         want_run, want_pair, answered, back = predict(strs[:n], t, scalar, unpacked)
@@ -509,7 +450,7 @@ def test_chains_of_two_state_levels_and_their_parents(gpu_ctx, oracle, monkeypat
     assert len(strs) == 16
     five_ways(gpu_ctx, oracle, monkeypatch, strs, ev_t(), (16,), min_pair_levels=50)
     # the path of "state_1_matches_two" goes through B both times (parent lo + 1), that of "state_0_matches_two" through A
-    arcs = {int(o) for s in strs for o in analyse(oracle, s, ev_t())["path"]["arcs"]["olabel"]}
+    arcs = {int(o) for s in strs for o in analyse_string(oracle, s, ev_t())["path"]["arcs"]["olabel"]}
     t = ev_t()
     by_b = {int(a["olabel"]) for a in t["arcs"][t["offsets"][B]:t["offsets"][B + 1]] if a["ilabel"] == 11}
     by_a = {int(a["olabel"]) for a in t["arcs"][t["offsets"][A]:t["offsets"][A + 1]] if a["ilabel"] == 12}
@@ -521,8 +462,8 @@ def test_equal_destinations_three_matches_and_no_match_end_the_run(gpu_ctx, orac
     strs = not_carried_strings()
     five_ways(gpu_ctx, oracle, monkeypatch, strs, ev_t(), (len(strs),), min_pair_levels=6)
     t = ev_t()
-    tie = {int(o) for o in analyse(oracle, strs[4], t)["path"]["arcs"]["olabel"]}
-    better = {int(o) for o in analyse(oracle, strs[6], t)["path"]["arcs"]["olabel"]}
+    tie = {int(o) for o in analyse_string(oracle, strs[4], t)["path"]["arcs"]["olabel"]}
+    better = {int(o) for o in analyse_string(oracle, strs[6], t)["path"]["arcs"]["olabel"]}
     via = lambda s, label: {int(a["olabel"]) for a in t["arcs"][t["offsets"][s]:t["offsets"][s + 1]] if a["ilabel"] == label}
     assert via(A, 3) <= tie and via(B, 13) <= better  # the earlier source stays on a tie; the second way wins when it is better
 
@@ -555,7 +496,7 @@ def test_the_same_batch_unpacked(gpu_ctx, oracle, monkeypatch):
 def test_infinite_and_signed_zero_weights_on_pair_levels(gpu_ctx, oracle, monkeypatch, kind):
     strs = ladder_strings(kind)
     five_ways(gpu_ctx, oracle, monkeypatch, strs, ladder_t(kind), (len(strs),), min_pair_levels=30)
-    paths = [analyse(oracle, s, ladder_t(kind))["path"] for s in strs]
+    paths = [analyse_string(oracle, s, ladder_t(kind))["path"] for s in strs]
     assert paths[0]["n_states"] == LADDER_L + 1 and len(paths[1]["arcs"]) == 0  # through V; through the unreached U: none
     if kind == "neg":
         signs = np.signbit(paths[0]["arcs"]["weight"])

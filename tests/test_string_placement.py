@@ -5,10 +5,7 @@ call are the same under every placement, and Context.string_placement() says whi
 
 Host: tests/placement_check.cpp restates the rule as its issue words it and sweeps the header's function over the edges of
 every line (built under the address and undefined-behaviour sanitizers, like slab_check).  The GPU tests ask the same program
-what the header gives for the launch they made, so the counters are compared with the header, not with a third restatement.
-
-This module restates the few generators it shares with the other string-kernel tests instead of importing them: a test module
-is nobody's library (test_host.test_nobody_imports_a_test_module)."""
+what the header gives for the launch they made, so the counters are compared with the header, not with a third restatement."""
 import functools
 import os
 import shutil
@@ -18,16 +15,14 @@ import sys
 import numpy as np
 import pytest
 
-from rustfst_amd._lib import TR_DTYPE, STRING_PLACEMENT
+from rustfst_amd._lib import STRING_PLACEMENT
 from rustfst_amd import synth
 
 import helpers
-from helpers import NOT_I_LABEL_SORTED, NOT_O_LABEL_SORTED, assert_flat_identical, to_device, to_oracle
+from helpers import analyse_string, assert_flat_identical, finals_of, fst, string, to_device
+from string_cases import string_slice
 
 ROOT = helpers.ROOT
-STR_MAXS = 2048
-STR_SLICES = (512, 1024, 2048)
-STR_PACKED_MIN = 16
 KNOBS = ("WFST_STRING_WPB", "WFST_STRING_UNPACKED", "WFST_STRING_SCALAR", "WFST_STRING_KERNEL", "WFST_STRING_RUN",
          "WFST_STRING_PAIR", "WFST_SSSP_BOUNDED")
 ZERO = dict.fromkeys(STRING_PLACEMENT, 0)
@@ -68,37 +63,6 @@ def test_placement_rule(tmp_path):
 
 
 # ================================================================ inputs
-def fst(rows, finals):
-    """rows[s] = [(ilabel, olabel, weight, nextstate)], start state 0; the property word states label sortedness truthfully"""
-    n = len(rows)
-    offsets = np.zeros(n + 1, dtype=np.uint32)
-    offsets[1:] = np.cumsum([len(r) for r in rows])
-    flat_rows = [a for r in rows for a in r]
-    arcs = np.array(flat_rows, dtype=TR_DTYPE) if flat_rows else np.zeros(0, dtype=TR_DTYPE)
-    il = all(all(r[i][0] <= r[i + 1][0] for i in range(len(r) - 1)) for r in rows)
-    ol = all(all(r[i][1] <= r[i + 1][1] for i in range(len(r) - 1)) for r in rows)
-    props = (synth.I_LABEL_SORTED if il else NOT_I_LABEL_SORTED) | (synth.O_LABEL_SORTED if ol else NOT_O_LABEL_SORTED)
-    return dict(n_states=n, start=0, offsets=offsets, arcs=arcs, finals=np.asarray(finals, dtype=np.float32), props=props)
-
-
-def finals_of(n, where):
-    f = np.full(n, np.inf, dtype=np.float32)
-    for s, w in where.items():
-        f[s] = w
-    return f
-
-
-def string(labels, final_weight=0.0):
-    return synth.linear_acceptor_flat(np.asarray(labels, dtype=np.uint32), final_weight)
-
-
-def string_slice(n_eligible, max_states, unpacked=False):
-    """states per problem of the string kernel's LDS slice: batches of >= 16 take the least slice >= 2 * states + 64"""
-    if unpacked or n_eligible < STR_PACKED_MIN:
-        return STR_MAXS
-    return next(m for m in STR_SLICES if 2 * max_states + 64 <= m or m == STR_MAXS)
-
-
 N_T = 20
 
 
@@ -136,19 +100,6 @@ def strings33():
 @functools.lru_cache(maxsize=None)
 def no_start():
     return dict(string([1, 2, 3]), start=-1)
-
-
-_AN = {}
-
-
-def analyse(oracle, a, t):
-    """the oracle's untrimmed composition (states, arcs) and its canonical shortest path"""
-    key = (id(a), id(t))
-    if key not in _AN:
-        c = to_oracle(oracle, a).compose(to_oracle(oracle, t), connect=False, compose_filter=0)
-        cf = c.to_flat()
-        _AN[key] = dict(a=a, t=t, n_states=cf["n_states"], n_arcs=len(cf["arcs"]), path=c.shortest_path_canonical().to_flat())
-    return _AN[key]
 
 
 def clear(monkeypatch):
@@ -223,7 +174,7 @@ def test_every_placement_answers_alike(gpu_ctx, oracle, monkeypatch, no_resident
     strs, t = strings33()[:n], t20()
     extra = [no_start()] if n > 16 else []
     dt, handles = to_device(t, gpu_ctx), rustfst_amd.DeviceFst.upload_many(strs + extra, gpu_ctx)
-    ans = [analyse(oracle, s, t) for s in strs + extra]
+    ans = [analyse_string(oracle, s, t) for s in strs + extra]
     maxs = string_slice(n, max(s["n_states"] for s in strs))
     assert maxs == 512 and all(a["n_states"] <= maxs for a in ans)  # every string is the kernel's
     assert not extra or (ans[-1]["n_states"] == 0 and ans[-1]["path"]["n_states"] == 0)
@@ -256,7 +207,7 @@ def test_knob_values_and_small_batches(gpu_ctx, oracle, monkeypatch, no_resident
     import rustfst_amd
     strs, t = strings33()[:16], t20()
     dt, handles = to_device(t, gpu_ctx), rustfst_amd.DeviceFst.upload_many(strs, gpu_ctx)
-    ans = [analyse(oracle, s, t) for s in strs]
+    ans = [analyse_string(oracle, s, t) for s in strs]
     cus = n_cus_of_device()
     first = None
     for text, wpb in (("3", 2), ("9", 8), ("0", 1), ("many", 1), ("", 1)):
@@ -309,7 +260,7 @@ def test_slice_of_a_batch_wherever_it_sits(gpu_ctx, oracle, monkeypatch, no_resi
     import rustfst_amd
     accs, t = slice_batch(beyond)
     dt, handles = to_device(t, gpu_ctx), rustfst_amd.DeviceFst.upload_many(accs, gpu_ctx)
-    ans = [analyse(oracle, a, t) for a in accs]
+    ans = [analyse_string(oracle, a, t) for a in accs]
     assert ans[0]["n_states"] == 512 + beyond and string_slice(16, accs[0]["n_states"]) == 512
     if forced is not None:
         monkeypatch.setenv("WFST_STRING_WPB", forced)
@@ -327,7 +278,7 @@ def test_forced_eight_with_the_largest_slice_is_two(gpu_ctx, oracle, monkeypatch
     import rustfst_amd
     accs, t = [string([1] * 1000)] + [string([1] * (1 + k % 3)) for k in range(15)], ladder_t(1)
     dt, handles = to_device(t, gpu_ctx), rustfst_amd.DeviceFst.upload_many(accs, gpu_ctx)
-    ans = [analyse(oracle, a, t) for a in accs]
+    ans = [analyse_string(oracle, a, t) for a in accs]
     monkeypatch.setenv("WFST_STRING_WPB", "8")
     got = batch(gpu_ctx, handles, dt, ans, "2048-state slice, WFST_STRING_WPB=8")
     assert got["path"]["string_answered"] == 16
@@ -345,7 +296,7 @@ def test_four_compute_units_take_four_waves_each(wfst_lib, oracle, monkeypatch, 
     ctx = rustfst_amd.Context(0, cu_mask=words)
     strs, t = strings33()[:16], t20()
     dt, handles = to_device(t, ctx), rustfst_amd.DeviceFst.upload_many(strs, ctx)
-    ans = [analyse(oracle, s, t) for s in strs]
+    ans = [analyse_string(oracle, s, t) for s in strs]
     got = batch(ctx, handles, dt, ans, "4-CU mask")
     assert got["path"]["string_answered"] == 16
     assert ctx.string_placement() == dict(waves_per_workgroup=4, slice_states=512, workgroups=4, packed_for_resident=0, forced=0)
@@ -362,7 +313,7 @@ def test_a_resident_solve_packs_the_next_batch_and_a_stopped_one_spreads_it(gpu_
     clear(monkeypatch)
     strs, t = strings33()[:16], t20()
     dt, handles = to_device(t, gpu_ctx), rustfst_amd.DeviceFst.upload_many(strs, gpu_ctx)
-    ans = [analyse(oracle, s, t) for s in strs]
+    ans = [analyse_string(oracle, s, t) for s in strs]
     cus = n_cus_of_device()
     solve(monkeypatch, full=True)
     packed = batch(gpu_ctx, handles, dt, ans, "after a resident solve")

@@ -13,116 +13,15 @@ import pytest
 
 from rustfst_amd import synth
 
-import test_compose_limits as cl
 import helpers
-from helpers import to_device
+from helpers import finals_of, fst, string, wstring
+import string_cases as sc
+from string_cases import four_ways, mix_t, predict, walk
 
 INF = float("inf")
-RUN_BLOCK = 64  # fc <= 64u
-
-
-# ================================================================ the prediction
-def walk(labels, t, maxs):
-    """(composed states, widest level, run levels, runs) of string o T as the kernel's vector path does it with slice maxs"""
-    off, arcs = t["offsets"], t["arcs"]
-    il, ns = arcs["ilabel"], arcs["nextstate"]
-    L = len(labels)
-    frontier, hi, widest, run_levels, runs, in_run = [int(t["start"])], 1, 1, 0, 0, False
-    for pos in range(L):
-        nxt, matches = [], 0
-        for q in frontier:
-            for e in range(int(off[q]), int(off[q + 1])):
-                if int(il[e]) == int(labels[pos]):
-                    matches += 1
-                    if int(ns[e]) not in nxt:
-                        nxt.append(int(ns[e]))
-        q = frontier[0]
-        taken = (len(frontier) == 1 and int(off[q + 1]) - int(off[q]) <= RUN_BLOCK and pos + 1 < L and hi + 1 < maxs
-                 and matches == 1)
-        if taken:
-            run_levels += 1
-            runs += not in_run
-        in_run = taken
-        hi += len(nxt)
-        widest = max(widest, len(nxt))
-        frontier = nxt
-        if not frontier:
-            break
-    return hi, widest, run_levels, runs
-
-
-def predict(strs, t, scalar, unpacked):
-    """(string_run_stats(), problems the string kernel answers) of one call with the run on"""
-    eligible = [s for s in strs if s["n_states"] <= cl.STR_MAXS]
-    out, answered = dict(run_levels=0, runs=0), 0
-    if not eligible:
-        return out, answered
-    vector = scalar == "0" or (scalar is None and len(eligible) > 8)
-    maxs = cl.string_slice(len(eligible), max(s["n_states"] for s in eligible), unpacked)
-    for s in eligible:
-        n, widest, rl, r = walk(s["arcs"]["ilabel"], t, maxs)
-        if widest <= cl.STR_LEVEL and n <= maxs:  # answered by the string kernel: its counters are tallied
-            answered += 1
-            if vector:  # (scalar rows: the run is not entered)
-                out["run_levels"] += rl
-                out["runs"] += r
-    return out, answered
-
-
-def four_ways(ctx, oracle, monkeypatch, strs, t, sizes, scalar=None, unpacked=False, min_run_levels=1):
-    import rustfst_amd
-    dt, handles = to_device(t, ctx), rustfst_amd.DeviceFst.upload_many(strs, ctx)
-    ans = [cl.analyse(oracle, s, t) for s in strs]
-    for name, val in (("WFST_STRING_SCALAR", scalar), ("WFST_STRING_UNPACKED", "1" if unpacked else None)):
-        monkeypatch.delenv(name, raising=False) if val is None else monkeypatch.setenv(name, val)
-    seen = 0
-    for n in sizes:
-        want, answered = predict(strs[:n], t, scalar, unpacked)
-        seen += want["run_levels"]
-        for mode in ("run", "no_run", "general"):
-            monkeypatch.setenv("WFST_STRING_RUN", "0" if mode == "no_run" else "1")
-            monkeypatch.setenv("WFST_STRING_KERNEL", "0" if mode == "general" else "1")
-            outs, n_arcs = rustfst_amd.compose_shortest_path_batch(handles[:n], dt)
-            what = "%s, batch of %d" % (mode, n)
-            for k in range(n):
-                cl.same(outs[k].to_flat(), ans[k]["path"], "%s, string %d" % (what, k))
-            assert n_arcs == sum(len(a["full"]["arcs"]) for a in ans[:n]), what
-            assert int(ctx.stats()["compose_states"]) == sum(a["full"]["n_states"] for a in ans[:n]), what
-            got, st = ctx.string_run_stats(), ctx.compose_path_stats()
-            assert got == (want if mode == "run" else dict(run_levels=0, runs=0)), (what, got, want)
-            assert st["string_answered"] == (answered if mode != "general" else 0), (what, st)
-    for name in ("WFST_STRING_RUN", "WFST_STRING_KERNEL", "WFST_STRING_SCALAR", "WFST_STRING_UNPACKED"):
-        monkeypatch.delenv(name, raising=False)
-    assert seen >= min_run_levels, "the case has no run level at all"
 
 
 # ================================================================ generators
-def wstring(labels, weights=None, final_weight=0.0):
-    """a string whose arcs carry weights"""
-    L = len(labels)
-    weights = [0.0] * L if weights is None else weights
-    rows = [[(int(labels[i]), int(labels[i]), float(weights[i]), i + 1)] for i in range(L)] + [[]]
-    return cl.fst(rows, cl.finals_of(L + 1, {L: final_weight}))
-
-
-N_MIX = 9
-
-
-@functools.lru_cache(maxsize=None)
-def mix_t():
-    """9 states, all final.  Labels 1, 2, 3: one arc each (a level of them is one match).  4: two arcs to ONE state, the
-    second the cheaper one.  5: two arcs to two states.  6: no arc.  7: three arcs to three states.  8: one arc to state 0
-    (whatever the frontier was, it collapses to one state)."""
-    rows = []
-    for s in range(N_MIX):
-        g = lambda k: (s + k) % N_MIX
-        rows.append([(1, 10 + s, ((s * 5) % 9) / 512.0, g(1)), (2, 20 + s, ((s * 7) % 11) / 512.0, g(4)),
-                     (3, 30 + s, 0.0, (2 * s + 1) % N_MIX), (4, 40 + s, 3 / 512.0, g(2)), (4, 50 + s, 1 / 512.0, g(2)),
-                     (5, 60 + s, 2 / 512.0, g(1)), (5, 70 + s, 1 / 512.0, g(5)), (7, 80 + s, 0.0, g(1)), (7, 90 + s, 5 / 512.0, g(2)),
-                     (7, 100 + s, 1 / 512.0, g(3)), (8, 110 + s, (s % 3) / 512.0, 0)])
-    return cl.fst(rows, cl.finals_of(N_MIX, {s: s / 512.0 for s in range(N_MIX)}))
-
-
 INTERRUPTS = {"same_destination": [4], "two_destinations": [5, 8], "two_destinations_stay": [5], "no_match": [6], "fan_and_collapse": [7, 7, 8]}
 
 
@@ -131,12 +30,12 @@ def interrupted_strings(L=21):
     """single-match labels with each interrupt at positions 0, 1, mid and L - 2 (its first label), and the plain string"""
     rng = np.random.default_rng(21)
     base = [int(x) for x in rng.integers(1, 4, L)]
-    out = [cl.string(base)]
+    out = [string(base)]
     for ins in INTERRUPTS.values():
         for pos in (0, 1, L // 2, L - 2):
             s = list(base)
             s[pos:pos + len(ins)] = ins
-            out.append(cl.string(s))
+            out.append(string(s))
     return out
 
 
@@ -148,7 +47,7 @@ def chain_t(n=7):
     """every state has ONE arc per label 1..3 with its own output label and weight (zeros among them): every level of a
     string over 1..3 is one match, and a label read from the wrong place changes the path"""
     rows = [[(l, 10 * s + l, ((s * 37 + l * 5) % 11) / 512.0, (s * l + 1) % n) for l in (1, 2, 3)] for s in range(n)]
-    return cl.fst(rows, cl.finals_of(n, {s: (s % 4) / 512.0 for s in range(n)}))
+    return fst(rows, finals_of(n, {s: (s % 4) / 512.0 for s in range(n)}))
 
 
 @functools.lru_cache(maxsize=None)
@@ -158,14 +57,14 @@ def block_t():
             [(l, 1000 + l, (l % 5) / 512.0, 3) for l in range(1, 65)],
             [(l, 2000 + l, (l % 7) / 512.0, 3) for l in range(1, 66)],
             [(1, 3001, 1 / 512.0, 3), (2, 3002, 0.0, 0)]]
-    return cl.fst(rows, cl.finals_of(4, {3: 0.0, 0: 0.5}))
+    return fst(rows, finals_of(4, {3: 0.0, 0: 0.5}))
 
 
 @functools.lru_cache(maxsize=None)
 def inf_t(n=140):
     """a chain: label 1 goes on at a finite weight, label 2 goes on at +inf"""
     rows = [[(1, 10 + s, ((s * 3) % 7) / 512.0, s + 1), (2, 2000 + s, INF, s + 1)] for s in range(n)] + [[]]
-    return cl.fst(rows, cl.finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
+    return fst(rows, finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
 
 
 # ================================================================ no GPU
@@ -181,7 +80,7 @@ def test_new_symbol_declared_exported_and_bound(wfst_lib):
 def test_the_walk_counts_what_the_generators_promise():
     """every level but the last of a string over 1..3 against chain_t is a run level, in one run; an interrupt splits it"""
     for n in RUN_LENGTHS:
-        s = cl.string([1 + k % 3 for k in range(n)])
+        s = string([1 + k % 3 for k in range(n)])
         assert walk(s["arcs"]["ilabel"], chain_t(), 2048) == (n + 1, 1, n - 1, 1 if n > 1 else 0)
     plain, at0, at1, mid, late = interrupted_strings()[:5]  # (same_destination)
     L = plain["n_states"] - 1
@@ -190,15 +89,15 @@ def test_the_walk_counts_what_the_generators_promise():
     assert walk(at1["arcs"]["ilabel"], mix_t(), 2048) == (L + 1, 1, L - 2, 2)
     assert walk(mid["arcs"]["ilabel"], mix_t(), 2048) == (L + 1, 1, L - 2, 2)
     assert walk(late["arcs"]["ilabel"], mix_t(), 2048) == (L + 1, 1, L - 2, 1)
-    assert walk(cl.string([1, 1, 1, 1])["arcs"]["ilabel"], block_t(), 2048)[2:] == (3, 1)   # the block of 64 is in the run
-    assert walk(cl.string([2, 1, 1, 1])["arcs"]["ilabel"], block_t(), 2048)[2:] == (2, 2)   # the block of 65 ends it
+    assert walk(string([1, 1, 1, 1])["arcs"]["ilabel"], block_t(), 2048)[2:] == (3, 1)   # the block of 64 is in the run
+    assert walk(string([2, 1, 1, 1])["arcs"]["ilabel"], block_t(), 2048)[2:] == (2, 2)   # the block of 65 ends it
 
 
 # ================================================================ GPU
 @pytest.mark.gpu
 def test_run_lengths_around_the_label_chunks(gpu_ctx, oracle, monkeypatch):
     rng = np.random.default_rng(130)
-    strs = [cl.string(rng.integers(1, 4, n), 0.25 * (k % 2)) for k, n in enumerate(RUN_LENGTHS)]
+    strs = [string(rng.integers(1, 4, n), 0.25 * (k % 2)) for k, n in enumerate(RUN_LENGTHS)]
     four_ways(gpu_ctx, oracle, monkeypatch, strs, chain_t(), (len(strs),))
 
 
@@ -217,7 +116,7 @@ def test_interrupted_and_resumed_runs_in_every_batch_shape(gpu_ctx, oracle, monk
 def test_blocks_of_64_and_65_arcs(gpu_ctx, oracle, monkeypatch):
     """the match in the first and in the last lane of a block of 64 (in the run) and of 65 (ends it: its last arc is the
     general level's second chunk)"""
-    strs = [cl.string(s) for s in ([1, 1, 1, 1], [1, 64, 1, 1], [2, 1, 1, 1], [2, 65, 1, 1], [1, 64, 2, 1, 64, 1], [2, 64, 2, 2, 65, 1])]
+    strs = [string(s) for s in ([1, 1, 1, 1], [1, 64, 1, 1], [2, 1, 1, 1], [2, 65, 1, 1], [1, 64, 2, 1, 64, 1], [2, 64, 2, 2, 65, 1])]
     four_ways(gpu_ctx, oracle, monkeypatch, strs * 2, block_t(), (12,))
 
 
@@ -242,9 +141,9 @@ def test_infinite_and_zero_weights_inside_a_run(gpu_ctx, oracle, monkeypatch):
 def test_state_limit_unpacked(gpu_ctx, oracle, monkeypatch):
     """2048 composed states are taken (the run stops one state short of the slice), 2049 are handed back as
     test_string_of_2048_states_is_taken_and_2049_is_not expects"""
-    strs = [cl.string([1] * 2047), cl.string([1] * 2048)]
-    assert walk(strs[0]["arcs"]["ilabel"], cl.ladder_t(1), 2048) == (2048, 1, 2046, 1)
-    four_ways(gpu_ctx, oracle, monkeypatch, strs, cl.ladder_t(1), (2,), scalar="0", min_run_levels=2046)
+    strs = [string([1] * 2047), string([1] * 2048)]
+    assert walk(strs[0]["arcs"]["ilabel"], sc.ladder_t(1), 2048) == (2048, 1, 2046, 1)
+    four_ways(gpu_ctx, oracle, monkeypatch, strs, sc.ladder_t(1), (2,), scalar="0", min_run_levels=2046)
 
 
 @pytest.mark.gpu
@@ -254,10 +153,10 @@ def test_state_limit_packed(gpu_ctx, oracle, monkeypatch):
     t = mix_t()
     head = [7] * 50 + [8]
     tail = next(r for r in range(1, 200) if walk(head + [1 + k % 3 for k in range(r)], t, 512)[0] == 512)
-    strs = [cl.string(head + [1 + k % 3 for k in range(tail + extra)]) for extra in (0, -1, 1)]
+    strs = [string(head + [1 + k % 3 for k in range(tail + extra)]) for extra in (0, -1, 1)]
     assert [walk(s["arcs"]["ilabel"], t, 512)[0] for s in strs] == [512, 511, 513]
     assert 2 * strs[2]["n_states"] + 64 <= 512
-    short = [cl.string([1 + k % 3 for k in range(2 + j % 4)]) for j in range(13)]
+    short = [string([1 + k % 3 for k in range(2 + j % 4)]) for j in range(13)]
     four_ways(gpu_ctx, oracle, monkeypatch, strs + short, t, (16,), min_run_levels=2 * (tail - 2))
     four_ways(gpu_ctx, oracle, monkeypatch, strs[:2] + short + [strs[2]], t, (15,), scalar="0")  # (unpacked: 2048 states each)
 

@@ -4,7 +4,7 @@ run used to park the arc and settle all of its states when it ended.  The string
 chunk in registers that is rotated between the segments of a run, not inside the level.  And the narrow general level: two
 to four frontier states whose blocks each fit one 64-arc chunk have all their rows asked for at once and taken in order.
 
-Every case is answered four ways and compared bit for bit (test_string_run.four_ways: run on, WFST_STRING_RUN=0, the general
+Every case is answered four ways and compared bit for bit (string_cases.four_ways: run on, WFST_STRING_RUN=0, the general
 kernel, the oracle), with the composed states and arcs and with string_run_stats() against walk().  What the cases are built
 to catch: a sum taken in another order or with a weight of the neighbouring chunk, a level settled from the wrong state, a
 row loaded beyond its block, an exit that leaves the run with the wrong rows or on the wrong side of a chunk rotation."""
@@ -12,10 +12,9 @@ import functools
 
 import numpy as np
 import pytest
-
-import test_compose_limits as cl
-import test_string_run as sr
-from test_string_run import four_ways, walk, wstring
+import string_cases as sc
+from helpers import analyse, finals_of, fst, string, wstring
+from string_cases import four_ways, walk
 
 INF = float("inf")
 SINGLES = (1, 2, 3)
@@ -31,7 +30,7 @@ def sum_t(n=11):
     """every state carries the labels 1..3 once, each arc with its own output label and its own weight off the 1/512 grid:
     every level of a string over 1..3 is one match, and no two additions of a running sum are alike"""
     rows = [[(l, 10 * s + l, 0.1 * (3 * s + l + 1), (s * l + 1) % n) for l in SINGLES] for s in range(n)]
-    return cl.fst(rows, cl.finals_of(n, {s: 0.1 * (s % 4) for s in range(n)}))
+    return fst(rows, finals_of(n, {s: 0.1 * (s % 4) for s in range(n)}))
 
 
 SUM_RUNS = (63, 64, 65, 66, 127, 128, 129, 130, 193)
@@ -59,9 +58,9 @@ def short_run_strings():
     strings whose first level already fails the run's test, and one with no run level at all"""
     out = []
     for r in range(1, 7):
-        out.append(cl.string(singles(r) + [4] + singles(r, 1) + [5, 8] + singles(r, 2) + [4, 4] + singles(r + 1), 0.25 * (r % 2)))
-    out += [cl.string([4] + singles(2) + [4] + singles(1) + [4, 1]), cl.string([5, 8, 4] + singles(3) + [5, 8] + singles(2)),
-            cl.string([7, 7, 8] + singles(5) + [4] + singles(4)), cl.string([4, 4, 5, 8, 4])]
+        out.append(string(singles(r) + [4] + singles(r, 1) + [5, 8] + singles(r, 2) + [4, 4] + singles(r + 1), 0.25 * (r % 2)))
+    out += [string([4] + singles(2) + [4] + singles(1) + [4, 1]), string([5, 8, 4] + singles(3) + [5, 8] + singles(2)),
+            string([7, 7, 8] + singles(5) + [4] + singles(4)), string([4, 4, 5, 8, 4])]
     return out
 
 
@@ -82,7 +81,7 @@ def exit_t():
     rows.append([(l, 1000 + l, 0.01 * l, l % N_CYC) for l in range(1, 65)])
     rows.append([(l, 2000 + l, 0.02 * l, l % N_CYC) for l in range(1, 66)])
     rows.append([(l, 3000 + l, 0.03 * l, l % N_CYC) for l in SINGLES])
-    return cl.fst(rows, cl.finals_of(N_CYC + 3, {0: 0.0, 1: 0.35, 2: 0.05, z: 0.5}))
+    return fst(rows, finals_of(N_CYC + 3, {0: 0.0, 1: 0.35, 2: 0.05, z: 0.5}))
 
 
 EXITS = {"no_match": [6, 1, 1], "same_destination": [4, 1, 1], "two_destinations": [5, 1, 1], "last_level": [1],
@@ -93,7 +92,7 @@ EXIT_AFTER = (0, 1, 2, 3, 63, 64, 65)  # run levels in front of the exit = the s
 
 @functools.lru_cache(maxsize=None)
 def exit_strings():
-    return [cl.string([1] * n + tail, 0.25 * (n % 2)) for tail in EXITS.values() for n in EXIT_AFTER]
+    return [string([1] * n + tail, 0.25 * (n % 2)) for tail in EXITS.values() for n in EXIT_AFTER]
 
 
 N_FAN = 20
@@ -101,7 +100,7 @@ N_FAN = 20
 
 @functools.lru_cache(maxsize=None)
 def fan_t():
-    """test_string_run.mix_t with 20 states, so that a level of 7s holds up to 20 states and a slice of 2048 fills within
+    """string_cases.mix_t with 20 states, so that a level of 7s holds up to 20 states and a slice of 2048 fills within
     ~200 labels.  1, 2, 3: one arc each.  4: two arcs to ONE state.  5: two arcs to two states.  6: no arc.  7: three arcs to
     three states.  8: one arc to state 0"""
     rows = []
@@ -111,7 +110,7 @@ def fan_t():
                      (3, 70 + s, 0.0, (2 * s + 1) % N_FAN), (4, 100 + s, 3 / 512.0, g(2)), (4, 130 + s, 1 / 512.0, g(2)),
                      (5, 160 + s, 2 / 512.0, g(1)), (5, 190 + s, 1 / 512.0, g(5)), (7, 220 + s, 0.0, g(1)), (7, 250 + s, 5 / 512.0, g(2)),
                      (7, 280 + s, 1 / 512.0, g(3)), (8, 310 + s, (s % 3) / 512.0, 0)])
-    return cl.fst(rows, cl.finals_of(N_FAN, {s: s / 512.0 for s in range(N_FAN)}))
+    return fst(rows, finals_of(N_FAN, {s: s / 512.0 for s in range(N_FAN)}))
 
 
 LIMIT_CASES = ((0, None), (1, None), (2, None), (3, None), (2, 63), (2, 64), (2, 65))  # (run levels before the exit, its position mod 64)
@@ -148,9 +147,9 @@ def limit_labels(maxs, k, at):
 def limit_strings(maxs):
     """the exit at hi + 1 == maxs after 0..3 run levels and on both sides of a label chunk; then a string that makes one state
     more than the slice holds (handed back)"""
-    out = [cl.string(limit_labels(maxs, k, at)) for k, at in LIMIT_CASES]
+    out = [string(limit_labels(maxs, k, at)) for k, at in LIMIT_CASES]
     over = limit_labels(maxs, 2, None)
-    out.append(cl.string(over[:-2] + [1]))
+    out.append(string(over[:-2] + [1]))
     return out
 
 
@@ -160,7 +159,7 @@ def inf_t(zero, n=140):
     w = lambda s, k: 0.0 if zero else 0.1 * ((s * 3 + k) % 7)
     rows = [[(1, 10 + s, w(s, 0), s + 1), (2, 2000 + s, INF, s + 1), (3, 4000 + s, w(s, 1), s + 1), (3, 6000 + s, w(s, 2), s + 1)]
             for s in range(n)] + [[]]
-    return cl.fst(rows, cl.finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
+    return fst(rows, finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
 
 
 @functools.lru_cache(maxsize=None)
@@ -168,7 +167,7 @@ def signed_zero_t(n=80):
     """a chain: 1 goes on at -0.0, 2 goes on at +0.0, 3 goes on over two arcs at -0.0 and +0.0 (no run level)"""
     rows = [[(1, 10 + s, -0.0, s + 1), (2, 2000 + s, 0.0, s + 1), (3, 4000 + s, -0.0, s + 1), (3, 6000 + s, 0.0, s + 1)]
             for s in range(n)] + [[]]
-    return cl.fst(rows, cl.finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
+    return fst(rows, finals_of(n + 1, {s: 0.0 for s in range(n + 1)}))
 
 
 @functools.lru_cache(maxsize=None)
@@ -214,8 +213,8 @@ def test_the_generators_promise_their_runs():
     assert len(set(w.tolist())) == len(w) and np.mean(w * 512 == np.round(w * 512)) < 0.25  # (0.5 and its like are on the grid)
     assert any(np.signbit(s["arcs"]["weight"][0]) for s in sum_strings())
     for r, s in zip(range(1, 7), short_run_strings()):
-        assert walk(s["arcs"]["ilabel"], sr.mix_t(), 2048)[2:] == (4 * r, 4)
-    assert walk(short_run_strings()[-1]["arcs"]["ilabel"], sr.mix_t(), 2048)[2:] == (0, 0)
+        assert walk(s["arcs"]["ilabel"], sc.mix_t(), 2048)[2:] == (4 * r, 4)
+    assert walk(short_run_strings()[-1]["arcs"]["ilabel"], sc.mix_t(), 2048)[2:] == (0, 0)
     t, per = exit_t(), len(EXIT_AFTER)
     assert int(t["offsets"][-1]) == int(t["offsets"][-2]) + 3  # Z's block ends T's arcs
     for j, name in enumerate(EXITS):
@@ -253,7 +252,7 @@ def test_sums_in_level_order_across_label_chunks(gpu_ctx, oracle, monkeypatch):
 @pytest.mark.gpu
 def test_runs_of_one_to_six_levels(gpu_ctx, oracle, monkeypatch):
     strs = short_run_strings()
-    four_ways(gpu_ctx, oracle, monkeypatch, strs + strs[:6], sr.mix_t(), (9, 10, 16))
+    four_ways(gpu_ctx, oracle, monkeypatch, strs + strs[:6], sc.mix_t(), (9, 10, 16))
 
 
 @pytest.mark.gpu
@@ -267,14 +266,14 @@ def test_every_exit_after_0_to_3_levels_and_around_a_label_chunk(gpu_ctx, oracle
 @pytest.mark.gpu
 def test_exit_at_the_last_state_of_a_packed_slice(gpu_ctx, oracle, monkeypatch):
     strs = limit_strings(512)
-    short = [cl.string(singles(2 + j % 4)) for j in range(8)]
+    short = [string(singles(2 + j % 4)) for j in range(8)]
     four_ways(gpu_ctx, oracle, monkeypatch, strs + short, fan_t(), (16,))
 
 
 @pytest.mark.gpu
 def test_exit_at_the_last_state_of_an_unpacked_slice(gpu_ctx, oracle, monkeypatch):
     strs = limit_strings(2048)
-    short = [cl.string(singles(2 + j % 4)) for j in range(8)]
+    short = [string(singles(2 + j % 4)) for j in range(8)]
     four_ways(gpu_ctx, oracle, monkeypatch, strs + short, fan_t(), (16,), unpacked=True)
 
 
@@ -316,7 +315,7 @@ def narrow_t():
     rows.append([(1, 601, 0.25, d), (2, 602, 0.1, e), (3, 603, 0.3, e)])
     rows.append([(1, 701, 0.2, d), (2, 702, 0.3, d), (2, 703, 0.1, e), (3, 704, 0.1, d)])
     rows.append([(1, 801, 0.3, d), (2, 802, 0.7, e), (3, 803, 0.05, e)])
-    return cl.fst(rows, cl.finals_of(9, {d: 0.125, e: 0.0}))
+    return fst(rows, finals_of(9, {d: 0.125, e: 0.0}))
 
 
 NARROW = ([2, 1, 1], [2, 2, 2], [2, 5, 1], [3, 1, 1], [3, 2, 1], [3, 64, 2], [4, 1, 1], [4, 2, 2, 1], [4, 10, 3], [5, 1, 1], [5, 3, 1],
@@ -325,7 +324,7 @@ NARROW = ([2, 1, 1], [2, 2, 2], [2, 5, 1], [3, 1, 1], [3, 2, 1], [3, 64, 2], [4,
 
 @functools.lru_cache(maxsize=None)
 def narrow_strings():
-    return [cl.string(s, 0.25 * (k % 2)) for k, s in enumerate(NARROW)]
+    return [string(s, 0.25 * (k % 2)) for k, s in enumerate(NARROW)]
 
 
 def test_narrow_generator_has_its_frontiers_and_ties(oracle):
@@ -333,18 +332,18 @@ def test_narrow_generator_has_its_frontiers_and_ties(oracle):
     assert int(t["offsets"][-1]) - int(t["offsets"][-2]) == 3
     widths = {}
     for s, a in zip(NARROW, narrow_strings()):
-        an = cl.analyse(oracle, a, t)
+        an = analyse(oracle, a, t)
         widths[tuple(s)] = [hi - lo for lo, hi, _, _ in an["levels"]]
     assert [widths[(k, 1, 1)][1] for k in (2, 3, 4, 5)] == [2, 3, 4, 5]
     assert widths[(6, 65, 2)][1] == 2 and widths[(7, 3, 1)][1] == 2 and widths[(8, 1, 1)][1] == 3
-    tie = cl.analyse(oracle, narrow_strings()[NARROW.index([3, 1, 1])], t)["path"]
+    tie = analyse(oracle, narrow_strings()[NARROW.index([3, 1, 1])], t)["path"]
     assert {14, 101} <= set(tie["arcs"]["olabel"].tolist())  # A1, the earlier of the two sources at 3/4
-    better = cl.analyse(oracle, narrow_strings()[NARROW.index([3, 2, 1])], t)["path"]
+    better = analyse(oracle, narrow_strings()[NARROW.index([3, 2, 1])], t)["path"]
     assert {16, 302} <= set(better["arcs"]["olabel"].tolist())  # A3, the later and strictly better one
 
 
 def test_signed_zero_generator_has_both_signs_on_its_paths(oracle):
-    signs = [np.signbit(cl.analyse(oracle, a, signed_zero_t())["path"]["arcs"]["weight"]) for a in signed_zero_strings()]
+    signs = [np.signbit(analyse(oracle, a, signed_zero_t())["path"]["arcs"]["weight"]) for a in signed_zero_strings()]
     assert all(len(s) == a["n_states"] - 1 for s, a in zip(signs, signed_zero_strings()))  # every string has its path
     assert signs[0].all() and signs[1].any() and not signs[1].all() and signs[2].any() and not signs[2].all()
     assert all(s.any() for s in signs[3:])

@@ -1,6 +1,6 @@
 """top_sort and state_sort (wfst_top_sort, wfst_state_sort, wfst_ctx_get_top_sort_stats): the C-ABI surface without a GPU, a
 literal sequential Python restatement of rustfst's dfs_visit.rs:97-187 with top_sort.rs's TopOrderVisitor, of
-state_sort.rs:16-78 (cycle by cycle, as the reference permutes) and of top_sort.rs:76-94, checked against the hand-traced
+state_sort.rs:16-78 (cycle by cycle, as the reference permutes) and of top_sort.rs:76-94 (oracle/model/top_sort.py), checked against the hand-traced
 K19 known answers, and on the device bit-exact parity with the restatement: states, arc order, weights by bit pattern,
 finals, start state and property word.
 
@@ -9,7 +9,6 @@ wfst_state_sort's size check needs a handle, which needs a device: without a GPU
 (test_ko_messages_and_the_context_afterwards)."""
 import copy
 import ctypes as C
-import json
 import os
 import re
 
@@ -17,150 +16,29 @@ import numpy as np
 import pytest
 
 from oracle import model
-from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, ALL, COACCESSIBLE, CYCLIC, INITIAL_ACYCLIC, NOT_STRING,
-                          NOT_TOP_SORTED, STRING, TOP_SORTED, fst_to_flat)
+from oracle.model import (ACCEPTOR, ACCESSIBLE, ACYCLIC, COACCESSIBLE, CYCLIC, INITIAL_ACYCLIC, MSG_ACYCLIC, NOT_STRING,
+                          NOT_TOP_SORTED, TOP_SORTED, dfs_top_order, fold_ref, fst_to_flat, norm, optimize_ref,
+                          state_sort_ref, top_sort_ref)
 import helpers
-from helpers import ROOT, assert_flat_identical, enumerate_paths
-import test_minimize as tm
-import test_rational_ops as tr
+from helpers import ROOT, _vector_fst, assert_flat_identical, dev, enumerate_paths, golden_fst, make_fst
+import minimize_cases as mc
+from inputs import chain, random_shuffled_dag, top_sort_golden
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "k19_top_sort.json")
 NEW_SYMBOLS = ("wfst_state_sort", "wfst_top_sort", "wfst_ctx_get_top_sort_stats")
-STATESORT_MASK = ALL & ~(TOP_SORTED | NOT_TOP_SORTED | STRING | NOT_STRING)  # properties.rs:319-348
-WHITE, GREY, BLACK = 0, 1, 2
 MSG_PERMUTATION = "state_sort: order is not a permutation of the states"
-
-
-# ---------------------------------------------------------------- the restatement
-def dfs_top_order(fst):
-    """dfs_visit(fst, TopOrderVisitor, AnyTrFilter, access_only = false) (dfs_visit.rs:97-187, top_sort.rs:12-61):
-    (acyclic, order); order is empty when the search found a back arc or the FST has no start state"""
-    rows = fst["rows"]
-    finish, acyclic = [], True
-    start = fst["start"]
-    if start is not None:
-        n = len(rows)
-        color = [WHITE] * n
-        stack = []
-        dfs, root = True, start
-        while dfs and root < n:
-            color[root] = GREY
-            stack.append([root, 0])
-            dfs = True  # init_state
-            while stack:
-                s, pos = stack[-1]
-                if not dfs or pos >= len(rows[s]):
-                    color[s] = BLACK
-                    stack.pop()
-                    finish.append(s)  # finish_state, with or without a parent
-                    if stack:
-                        stack[-1][1] += 1
-                    continue
-                t = rows[s][pos][3]
-                if color[t] == WHITE:
-                    dfs = True  # tree_tr
-                    color[t] = GREY
-                    stack.append([t, 0])
-                    dfs = True  # init_state
-                elif color[t] == GREY:
-                    acyclic = False  # back_tr
-                    dfs = False
-                    stack[-1][1] += 1
-                else:
-                    dfs = True  # forward_or_cross_tr
-                    stack[-1][1] += 1
-            root = 0 if root == start else root + 1
-            while root < n and color[root] != WHITE:
-                root += 1
-    order = []
-    if acyclic:  # finish_visit
-        order = [0] * len(finish)
-        for s in range(len(finish)):
-            order[finish[len(finish) - s - 1]] = s
-    return acyclic, order
-
-
-def state_sort_ref(fst, order):
-    """state_sort.rs:16-78, in place; the mutations' own property updates are overwritten by the last statement"""
-    n = len(fst["rows"])
-    if len(order) != n:
-        raise ValueError(f"StateSort : Bad order vector size : {len(order)}. Expected {n}")
-    if fst["start"] is None:
-        return fst
-    props = fst["props"] & STATESORT_MASK
-    done = [False] * n
-    fst["start"] = order[fst["start"]]
-    for s1 in range(n):
-        if done[s1]:
-            continue
-        final1, final2 = fst["finals"][s1], None
-        trsa, trsb = [list(t) for t in fst["rows"][s1]], []
-        while not done[s1]:
-            s2 = order[s1]
-            if not done[s2]:
-                final2 = fst["finals"][s2]
-                trsb = [list(t) for t in fst["rows"][s2]]
-            fst["finals"][s2] = final1
-            fst["rows"][s2] = [[il, ol, w, order[ns]] for il, ol, w, ns in trsa]
-            done[s1] = True
-            trsa, trsb = trsb, trsa
-            final1 = final2
-            s1 = s2
-    fst["props"] = props  # set_properties_with_mask(props, all_properties())
-    return fst
-
-
-def top_sort_ref(fst):
-    """top_sort.rs:76-94 on a copy; raises ValueError with state_sort's message"""
-    fst = copy.deepcopy(fst)
-    acyclic, order = dfs_top_order(fst)
-    if acyclic:
-        state_sort_ref(fst, order)
-        p = ACYCLIC | INITIAL_ACYCLIC | TOP_SORTED
-    else:
-        p = CYCLIC | NOT_TOP_SORTED
-    fst["props"] = (fst["props"] & ~p) | (p & p)  # set_properties_with_mask(p, p) (vector_fst/mutable_fst.rs:411-414)
-    return fst
 
 
 def is_permutation(order, n):
     return sorted(int(x) for x in order) == list(range(n))
 
 
-# ---------------------------------------------------------------- inputs
-def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
-
-
-def random_dag(rng, n, max_arcs_per_state=3, start=None):
-    """n states in a hidden topological order; arcs (multi-arcs too) from earlier to later places, rows shuffled; some states
-    the start cannot reach; the start anywhere"""
-    place = rng.permutation(n)  # place[k] = the state at topological place k
-    rows = [[] for _ in range(n)]
-    if n > 1:
-        for _ in range(int(rng.integers(0, max_arcs_per_state * n + 1))):
-            a, b = sorted(int(x) for x in rng.choice(n, 2, replace=False))
-            il = int(rng.integers(0, 4))
-            rows[place[a]].append([il, il if rng.random() < 0.5 else int(rng.integers(0, 4)), float(rng.integers(0, 9)) / 4, int(place[b])])
-        if rng.random() < 0.5:  # a doubled arc
-            src = [s for s in range(n) if rows[s]]
-            if src:
-                s = src[int(rng.integers(0, len(src)))]
-                rows[s].append(list(rows[s][0]))
-    for r in rows:
-        rng.shuffle(r)
-    finals = [float(rng.integers(0, 8)) / 4 if rng.random() < 0.4 else None for _ in range(n)]
-    return tr.make_fst(rows, finals, int(rng.integers(0, n)) if start is None else start)
-
-
 def run_dev(c, g, ctx):
-    h = tr.dev(tr.golden_fst(g["machines"][c["arg"]]), ctx)
+    h = dev(golden_fst(g["machines"][c["arg"]]), ctx)
     return h.top_sort() if c["op"] == "top_sort" else h.state_sort(c["order"])
 
 
 def run_ref(c, g):
-    m = tr.golden_fst(g["machines"][c["arg"]])
+    m = golden_fst(g["machines"][c["arg"]])
     return top_sort_ref(m) if c["op"] == "top_sort" else state_sort_ref(copy.deepcopy(m), c["order"])
 
 
@@ -205,10 +83,10 @@ def test_python_surface():
 
 def test_k19_restatement_reproduces_the_derivations():
     """the hand traces of K19_DERIVATION.md, replayed by this file's restatement (checks the restatement itself)"""
-    g = golden()
+    g = top_sort_golden()
     assert len(g["cases"]) == 12
     for c in g["cases"]:
-        m = tr.golden_fst(g["machines"][c["arg"]])
+        m = golden_fst(g["machines"][c["arg"]])
         if c["op"] == "top_sort":
             acyclic, order = dfs_top_order(m)
             assert acyclic == (c["order"] is not None), c["name"]
@@ -217,13 +95,13 @@ def test_k19_restatement_reproduces_the_derivations():
             with pytest.raises(ValueError, match=re.escape(c["error"])):
                 run_ref(c, g)
             continue
-        assert_flat_identical(fst_to_flat(run_ref(c, g)), fst_to_flat(tr.golden_fst(c["expected"])), c["name"], check_props=True)
+        assert_flat_identical(fst_to_flat(run_ref(c, g)), fst_to_flat(golden_fst(c["expected"])), c["name"], check_props=True)
 
 
 def test_cyclic_keeps_a_stale_acyclic_word():
     """top_sort.rs:88-91: p equals its own mask, so CYCLIC | NOT_TOP_SORTED are set and nothing is cleared"""
-    g = golden()
-    got = top_sort_ref(tr.golden_fst(g["machines"]["self_loop"]))
+    g = top_sort_golden()
+    got = top_sort_ref(golden_fst(g["machines"]["self_loop"]))
     assert got["props"] == ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | TOP_SORTED | CYCLIC | NOT_TOP_SORTED
 
 
@@ -233,7 +111,7 @@ def test_restated_result_is_top_sorted():
     rng = np.random.default_rng(1901)
     for i in range(300):
         n = int(rng.integers(1, 15))
-        m = random_dag(rng, n)
+        m = random_shuffled_dag(rng, n)
         acyclic, order = dfs_top_order(m)
         assert acyclic and is_permutation(order, n), i
         got = top_sort_ref(m)
@@ -249,7 +127,7 @@ def test_restated_result_is_top_sorted():
 def test_start_is_not_always_numbered_zero():
     """the start state is the first root, but a later root finishes later still and takes a lower number: the start becomes
     state 0 only when it is the only root (K19 root_with_predecessor is the counterexample)"""
-    g = golden()
+    g = top_sort_golden()
     c = {c["name"]: c for c in g["cases"]}
     assert c["root_with_predecessor"]["expected"]["start"] == 1 and c["reference_python_test"]["expected"]["start"] == 0
 
@@ -262,12 +140,12 @@ def _check_case(c, g, ctx):
             run_dev(c, g, ctx)
         return
     got = run_dev(c, g, ctx).to_flat()
-    assert_flat_identical(got, fst_to_flat(tr.golden_fst(c["expected"])), c["name"], check_props=True)
+    assert_flat_identical(got, fst_to_flat(golden_fst(c["expected"])), c["name"], check_props=True)
 
 
 @pytest.mark.gpu
 def test_k19_on_the_device(gpu_ctx):
-    g = golden()
+    g = top_sort_golden()
     for c in g["cases"]:
         _check_case(c, g, gpu_ctx)
         if c["op"] == "top_sort" and "error" not in c:
@@ -284,13 +162,13 @@ def test_random_dags_against_the_restatement(gpu_ctx, word, where):
     rng = np.random.default_rng(1902 + WORDS.index(word))
     for i in range(40):
         n = int(rng.integers(1, 60)) if i else 1
-        m = random_dag(rng, n, start={"start_0": 0, "start_last": n - 1, "start_middle": n // 2}[where])
+        m = random_shuffled_dag(rng, n, start={"start_0": 0, "start_last": n - 1, "start_middle": n // 2}[where])
         if word == "content_word":
             m["props"] = model.content_word(m)
         elif word == "stale_cyclic":
             m["props"] = (model.content_word(m) & ~(ACYCLIC | INITIAL_ACYCLIC)) | CYCLIC
         exp = top_sort_ref(m)
-        h = tr.dev(m, gpu_ctx)
+        h = dev(m, gpu_ctx)
         before = h.to_flat()
         assert_flat_identical(h.top_sort().to_flat(), fst_to_flat(exp), f"{word} {where} dag {i}", check_props=True)
         assert_flat_identical(h.to_flat(), before, "the input after top_sort", check_props=True)
@@ -304,7 +182,7 @@ def test_random_cyclic_inputs_come_back_as_copies(gpu_ctx):
     rng = np.random.default_rng(1903)
     for i in range(20):
         n = int(rng.integers(2, 40))
-        m = random_dag(rng, n)
+        m = random_shuffled_dag(rng, n)
         a, b = (int(x) for x in rng.choice(n, 2, replace=False))
         _, order = dfs_top_order(m)
         lo, hi = (a, b) if order[a] < order[b] else (b, a)
@@ -313,7 +191,7 @@ def test_random_cyclic_inputs_come_back_as_copies(gpu_ctx):
         m["props"] = ACYCLIC | TOP_SORTED | INITIAL_ACYCLIC if i % 2 else 0
         exp = top_sort_ref(m)
         assert exp["props"] == m["props"] | CYCLIC | NOT_TOP_SORTED and exp["rows"] == m["rows"]
-        assert_flat_identical(tr.dev(m, gpu_ctx).top_sort().to_flat(), fst_to_flat(exp), f"cyclic {i}", check_props=True)
+        assert_flat_identical(dev(m, gpu_ctx).top_sort().to_flat(), fst_to_flat(exp), f"cyclic {i}", check_props=True)
         assert gpu_ctx.top_sort_stats()["cyclic"] == 1
 
 
@@ -322,9 +200,9 @@ def test_state_sort_cases(gpu_ctx):
     import rustfst_amd
     rng = np.random.default_rng(1904)
     for n in (1, 2, 7, 300, 1000):
-        m = tr.chain(n, rng, fan=3, start=int(rng.integers(0, n))) if n > 1 else tr.make_fst([[]], [0.5], 0)
+        m = chain(n, rng, fan=3, start=int(rng.integers(0, n))) if n > 1 else make_fst([[]], [0.5], 0)
         m["props"] = model.content_word(m)
-        h = tr.dev(m, gpu_ctx)
+        h = dev(m, gpu_ctx)
         for name, order in (("random", rng.permutation(n).tolist()), ("identity", list(range(n)))):
             exp = state_sort_ref(copy.deepcopy(m), order)
             assert_flat_identical(h.state_sort(order).to_flat(), fst_to_flat(exp), f"state_sort {name} n={n}", check_props=True)
@@ -334,10 +212,10 @@ def test_state_sort_cases(gpu_ctx):
                     h.state_sort(bad)
         assert_flat_identical(h.to_flat(), fst_to_flat(m), "the input after state_sort", check_props=True)
     # start-less: a copy, word unchanged, whatever the order says
-    m = tr.make_fst([[[1, 1, 0.5, 1]], [], [[2, 3, 0.0, 0]]], [None, 0.25, None], None, ACCEPTOR | TOP_SORTED | NOT_STRING)
-    assert_flat_identical(tr.dev(m, gpu_ctx).state_sort([2, 0, 1]).to_flat(), fst_to_flat(m), "start-less state_sort", check_props=True)
-    empty = tr.make_fst([], [], None, ACCEPTOR)
-    assert_flat_identical(tr.dev(empty, gpu_ctx).state_sort([]).to_flat(), fst_to_flat(empty), "state_sort without states", check_props=True)
+    m = make_fst([[[1, 1, 0.5, 1]], [], [[2, 3, 0.0, 0]]], [None, 0.25, None], None, ACCEPTOR | TOP_SORTED | NOT_STRING)
+    assert_flat_identical(dev(m, gpu_ctx).state_sort([2, 0, 1]).to_flat(), fst_to_flat(m), "start-less state_sort", check_props=True)
+    empty = make_fst([], [], None, ACCEPTOR)
+    assert_flat_identical(dev(empty, gpu_ctx).state_sort([]).to_flat(), fst_to_flat(empty), "state_sort without states", check_props=True)
 
 
 @pytest.mark.gpu
@@ -345,9 +223,9 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, monkeypatch):
     import rustfst_amd
     from rustfst_amd import _lib
     L = _lib.lib()
-    g = golden()
-    diamond = tr.golden_fst(g["machines"]["diamond"])
-    h = tr.dev(diamond, gpu_ctx)
+    g = top_sort_golden()
+    diamond = golden_fst(g["machines"]["diamond"])
+    h = dev(diamond, gpu_ctx)
     out = C.c_void_p(1)
     order = (C.c_uint32 * 3)(0, 1, 2)
     assert helpers.ko_message(L.wfst_state_sort(gpu_ctx._h, h._h, order, 3, C.byref(out))) == "StateSort : Bad order vector size : 3. Expected 4"
@@ -358,7 +236,7 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, monkeypatch):
         h.state_sort([0, 1, 1, 3])
     with pytest.raises(rustfst_amd.WfstError, match=re.escape(MSG_PERMUTATION)):
         h.state_sort([0, 1, 2, 4])
-    no_start = tr.dev(tr.golden_fst(g["machines"]["two_states_no_start"]), gpu_ctx)
+    no_start = dev(golden_fst(g["machines"]["two_states_no_start"]), gpu_ctx)
     with pytest.raises(rustfst_amd.WfstError, match=re.escape("StateSort : Bad order vector size : 0. Expected 2")):
         no_start.top_sort()
     monkeypatch.setenv("WFST_TOP_SORT_PATH", "sideways")
@@ -367,9 +245,9 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, monkeypatch):
     monkeypatch.delenv("WFST_TOP_SORT_PATH")
     # ... and the same context, the same handle, successful calls
     cases = {c["name"]: c for c in g["cases"]}
-    assert_flat_identical(h.top_sort().to_flat(), fst_to_flat(tr.golden_fst(cases["diamond_second_arc_first"]["expected"])),
+    assert_flat_identical(h.top_sort().to_flat(), fst_to_flat(golden_fst(cases["diamond_second_arc_first"]["expected"])),
                           "top_sort after the KOs", check_props=True)
-    assert_flat_identical(h.state_sort([2, 3, 0, 1]).to_flat(), fst_to_flat(tr.golden_fst(cases["state_sort_two_cycles"]["expected"])),
+    assert_flat_identical(h.state_sort([2, 3, 0, 1]).to_flat(), fst_to_flat(golden_fst(cases["state_sort_two_cycles"]["expected"])),
                           "state_sort after the KOs", check_props=True)
 
 
@@ -377,19 +255,19 @@ def test_ko_messages_and_the_context_afterwards(gpu_ctx, monkeypatch):
 def test_vector_fst_and_module_surface(gpu_ctx):
     """rustfst-python's test_top_sort: in place, returns self, the start moves from the second state to the first"""
     import rustfst_amd
-    g = golden()
+    g = top_sort_golden()
     cases = {c["name"]: c for c in g["cases"]}
-    m = tr.golden_fst(g["machines"]["reference_python_test"])
-    expected = tr._vector_fst(tr.golden_fst(cases["reference_python_test"]["expected"]))
-    f = tr._vector_fst(m)
+    m = golden_fst(g["machines"]["reference_python_test"])
+    expected = _vector_fst(golden_fst(cases["reference_python_test"]["expected"]))
+    f = _vector_fst(m)
     assert f.start() == 1
     assert f.top_sort() is f
     assert f.start() == 0 and f == expected
-    f2 = tr._vector_fst(m)
+    f2 = _vector_fst(m)
     assert rustfst_amd.top_sort(f2) is f2 and f2 == expected
-    assert rustfst_amd.state_sort(f2, [1, 0]) is f2 and f2 == tr._vector_fst(m)
-    f3 = tr._vector_fst(m)
-    assert f3.state_sort([0, 1]) is f3 and f3 == tr._vector_fst(m)
+    assert rustfst_amd.state_sort(f2, [1, 0]) is f2 and f2 == _vector_fst(m)
+    f3 = _vector_fst(m)
+    assert f3.state_sort([0, 1]) is f3 and f3 == _vector_fst(m)
 
 
 @pytest.mark.gpu
@@ -398,25 +276,24 @@ def test_union_of_nbest_paths_top_sort_then_optimize(gpu_ctx, oracle):
     union is still KO (union_properties never holds TOP_SORTED, and rm_epsilon's set_trs bookkeeping then drops ACYCLIC);
     after top_sort the word holds TOP_SORTED and ACYCLIC and the restated optimize accepts it, as the device does."""
     import rustfst_amd
-    import test_optimize as to
     rng = np.random.default_rng(1806)
     word = ACCEPTOR | ACYCLIC | INITIAL_ACYCLIC | ACCESSIBLE | COACCESSIBLE
-    lattice = tm.random_dag(rng, 12, 4)
+    lattice = mc.random_dag(rng, 12, 4)
     paths = sorted(enumerate_paths(lattice))[:5]
     assert len(paths) == 5
     strings = []
     for w, il, _ in paths:
         il = list(il) or [1]
         rows = [[[x, x, w if i == 0 else 0.0, i + 1]] for i, x in enumerate(il)] + [[]]
-        strings.append(tr.make_fst(rows, [None] * len(il) + [0.0], 0, word))
-    union = rustfst_amd.union_list([tr.dev(s, gpu_ctx) for s in strings])
-    union_ref = tr.fold_ref(tr.union_ref, strings)
-    with pytest.raises(rustfst_amd.WfstError, match=re.escape(to.MSG_ACYCLIC)):
+        strings.append(make_fst(rows, [None] * len(il) + [0.0], 0, word))
+    union = rustfst_amd.union_list([dev(s, gpu_ctx) for s in strings])
+    union_ref = fold_ref(model.union_ref, strings)
+    with pytest.raises(rustfst_amd.WfstError, match=re.escape(MSG_ACYCLIC)):
         union.optimize()
     sorted_ref = top_sort_ref(union_ref)
     sorted_dev = union.top_sort()
     assert_flat_identical(sorted_dev.to_flat(), fst_to_flat(sorted_ref), "top_sort(union_list(n-best))", check_props=True)
-    exp = to.optimize_ref(fst_to_flat(sorted_ref), oracle)  # (raises Unsupported if the restatement itself answers KO)
+    exp = optimize_ref(fst_to_flat(sorted_ref), oracle)  # (raises Unsupported if the restatement itself answers KO)
     got = sorted_dev.optimize()
     assert exp["n_states"] < len(union_ref["rows"])
-    assert_flat_identical(to.norm(got.to_flat()), to.norm(exp), "optimize(top_sort(union_list(n-best)))", check_props=True)
+    assert_flat_identical(norm(got.to_flat()), norm(exp), "optimize(top_sort(union_list(n-best)))", check_props=True)

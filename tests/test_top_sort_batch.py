@@ -1,7 +1,7 @@
 """wfst_top_sort_batch / wfst_ctx_get_top_sort_batch_counters: the C-ABI and Python surface without a GPU, the search of
 csrc/top_sort_dfs.h as a stand-alone program under the address and undefined-behaviour sanitizers against
-test_top_sort.dfs_top_order, a host predictor of the in_kernel flag with one input on each side of every limit; and on the
-device parity of every batch item with test_top_sort.top_sort_ref AND with top_sort() on the same handle, bit for bit
+oracle.model's dfs_top_order, a host predictor of the in_kernel flag with one input on each side of every limit; and on the
+device parity of every batch item with oracle.model's top_sort_ref AND with top_sort() on the same handle, bit for bit
 including the property word, the flags against the predictor, the counters against the list, untouched inputs and the KOs.
 
 Shapes, and why: rows without arcs, a grey target at depth 1, a cycle that only a later root finds; a diamond whose
@@ -10,7 +10,6 @@ as the rule allows) and of 4097 (the single call); 16384 arcs (cursors and offse
 bits) and 16385; one row of 300 arcs walked by one cursor; 300 items are more workgroups than one wave of blocks holds."""
 import ctypes as C
 import functools
-import importlib
 import inspect
 import os
 import re
@@ -21,15 +20,11 @@ import numpy as np
 import pytest
 
 from oracle import model
-from oracle.model import ACYCLIC, CYCLIC, INITIAL_ACYCLIC, NOT_TOP_SORTED, TOP_SORTED, fst_to_flat
+from oracle.model import (ACYCLIC, CYCLIC, INITIAL_ACYCLIC, NOT_TOP_SORTED, TOP_SORTED, dfs_top_order, fold_ref,
+                          fst_to_flat, top_sort_ref, union_ref)
 import helpers
-from helpers import ROOT, assert_flat_identical
-
-# top_sort_ref, dfs_top_order, random_dag and the K19 loader are test_top_sort's and make_fst / dev / union_ref
-# test_rational_ops': taken from there, not restated.  By name: the list of import statements between test modules that
-# test_host.py keeps is closed.
-tr = importlib.import_module("test_rational_ops")
-tt = importlib.import_module("test_top_sort")
+from helpers import ROOT, assert_flat_identical, dev, golden_fst, make_fst
+from inputs import random_shuffled_dag, top_sort_golden
 
 MAX_STATES, MAX_ARCS = 4096, 16384  # include/wfst.h: the in_kernel rule
 SIGNATURES = {
@@ -54,8 +49,8 @@ def same(got, exp, what):
 
 # ---------------------------------------------------------------- inputs
 def k19_machines():
-    g = tt.golden()
-    return [("k19 " + name, tr.golden_fst(m)) for name, m in g["machines"].items()]
+    g = top_sort_golden()
+    return [("k19 " + name, golden_fst(m)) for name, m in g["machines"].items()]
 
 
 @functools.lru_cache(maxsize=None)
@@ -64,7 +59,7 @@ def random_dags():
     out = []
     for seed in range(40):
         rng = np.random.default_rng(2100 + seed)
-        m = tt.random_dag(rng, 1 + seed)
+        m = random_shuffled_dag(rng, 1 + seed)
         if seed % 2:
             m["props"] = model.content_word(m)
         out.append(("dag %d" % seed, m))
@@ -78,19 +73,19 @@ def tiny_shapes():
 
     def flipped(rows):
         return [list(reversed(rows[0]))] + rows[1:]
-    return [("one state, no arc", tr.make_fst([[]], [0.5], 0)),
-            ("one state, a self loop", tr.make_fst([[[1, 1, 0.0, 0]]], [0.0], 0)),
-            ("a cycle the start cannot reach", tr.make_fst([[[1, 1, 0.0, 1]], [[2, 2, 0.0, 0]], []], [None, None, 0.0], 2)),
-            ("skew diamond, 0->1 first", tr.make_fst(skew, fin, 0)),
-            ("skew diamond, 0->2 first", tr.make_fst(flipped(skew), fin, 0)),
-            ("diamond, 0->1 first", tr.make_fst(diamond, fin, 0)),
-            ("diamond, 0->2 first", tr.make_fst(flipped(diamond), fin, 0))]
+    return [("one state, no arc", make_fst([[]], [0.5], 0)),
+            ("one state, a self loop", make_fst([[[1, 1, 0.0, 0]]], [0.0], 0)),
+            ("a cycle the start cannot reach", make_fst([[[1, 1, 0.0, 1]], [[2, 2, 0.0, 0]], []], [None, None, 0.0], 2)),
+            ("skew diamond, 0->1 first", make_fst(skew, fin, 0)),
+            ("skew diamond, 0->2 first", make_fst(flipped(skew), fin, 0)),
+            ("diamond, 0->1 first", make_fst(diamond, fin, 0)),
+            ("diamond, 0->2 first", make_fst(flipped(diamond), fin, 0))]
 
 
 def chain_of(n):
     """n states in a row, numbered against the order so that every state moves; the start is the last id"""
     rows = [[[1 + s % 5, 1 + s % 3, (s % 8) / 4, s - 1]] if s else [] for s in range(n)]
-    return tr.make_fst(rows, [0.0] + [None] * (n - 1), n - 1)
+    return make_fst(rows, [0.0] + [None] * (n - 1), n - 1)
 
 
 def block_of_arcs(total, per_state=128):
@@ -98,13 +93,13 @@ def block_of_arcs(total, per_state=128):
     k = total // per_state
     rows = [[]] + [[[1 + j, 1 + s, (j % 7) / 2, 0] for j in range(per_state)] for s in range(k)]
     rows[-1] += [[900 + j, 1, 0.0, 0] for j in range(total - k * per_state)]
-    return tr.make_fst(rows, [0.25] + [None] * k, k)
+    return make_fst(rows, [0.25] + [None] * k, k)
 
 
 def wide_row():
     """one state with 300 arcs, many to the same target, finals on every state"""
     rows = [[[1 + j % 50, 2, (j % 11) / 4, 1 + (j * 7) % 5] for j in range(300)], [[3, 3, 0.5, 3]], [], [], [[4, 4, 0.0, 5]], []]
-    return tr.make_fst(rows, [s / 4 for s in range(6)], 0)
+    return make_fst(rows, [s / 4 for s in range(6)], 0)
 
 
 @functools.lru_cache(maxsize=None)
@@ -119,7 +114,7 @@ def many_small(count=300):
     out = []
     for k in range(count):
         rng = np.random.default_rng(3000 + k)
-        out.append(("small %d" % k, tt.random_dag(rng, 2 + k % 19)))
+        out.append(("small %d" % k, random_shuffled_dag(rng, 2 + k % 19)))
     return out
 
 
@@ -128,7 +123,7 @@ def with_cycle(m, rng):
     m = dict(m, rows=[[list(t) for t in r] for r in m["rows"]])
     n = len(m["rows"])
     a, b = (int(x) for x in rng.choice(n, 2, replace=False))
-    _, order = tt.dfs_top_order(m)
+    _, order = dfs_top_order(m)
     lo, hi = (a, b) if order[a] < order[b] else (b, a)
     m["rows"][hi].append([1, 1, 0.0, lo])
     m["rows"][lo].append([2, 2, 0.0, hi])
@@ -150,7 +145,7 @@ _REF = {}
 def reference(name, m):
     """top_sort_ref's answer as flat arrays, computed once per item and left unchanged"""
     if name not in _REF:
-        _REF[name] = fst_to_flat(tt.top_sort_ref(m))
+        _REF[name] = fst_to_flat(top_sort_ref(m))
     return _REF[name]
 
 
@@ -219,11 +214,11 @@ def test_predictor_on_both_sides_of_every_limit():
     assert all(n <= MAX_STATES for n, _ in (sizes["arcs 16384"], sizes["arcs 16385"]))  # (only the arcs decide these two)
     assert [predict_in_kernel(fams[k]) for k in ("states 4096", "states 4097", "arcs 16384", "arcs 16385")] == [1, 0, 1, 0]
     # the start state: without states in the kernel's count, with states the single call's
-    assert predict_in_kernel(tr.make_fst([], [], None)) == 1
-    assert predict_in_kernel(tr.make_fst([[]], [0.0], None)) == 0 and predict_in_kernel(tr.make_fst([[]], [0.0], 0)) == 1
+    assert predict_in_kernel(make_fst([], [], None)) == 1
+    assert predict_in_kernel(make_fst([[]], [0.0], None)) == 0 and predict_in_kernel(make_fst([[]], [0.0], 0)) == 1
     assert all(predict_in_kernel(m) for _, m in many_small() + random_dags() + tiny_shapes())
     assert [predict_in_kernel(m) for _, m in mixed_list()].count(0) == 2
-    cyc = [tt.dfs_top_order(m)[0] for _, m in mixed_list()]
+    cyc = [dfs_top_order(m)[0] for _, m in mixed_list()]
     assert cyc.count(False) == 100
 
 
@@ -232,7 +227,7 @@ def dfs_case(m):
     n = len(m["rows"])
     off = np.concatenate([[0], np.cumsum([len(r) for r in m["rows"]])]).astype(int).tolist()
     words = [n, m["start"]] + off + [t[3] for r in m["rows"] for t in r]
-    acyclic, order = tt.dfs_top_order(m)
+    acyclic, order = dfs_top_order(m)
     want = [TSD_ACYCLIC] + order if acyclic else [TSD_CYCLIC] + list(range(n))
     return " ".join(str(w) for w in words), " ".join(str(w) for w in want)
 
@@ -279,7 +274,7 @@ def check_list(items, ctx, launches=None):
     """one batch call; every result against the restatement and the single call on the same handle, the flags against the
     predictor, the counters against the list, the inputs unchanged.  Returns (results, handles)."""
     import rustfst_amd
-    devs = [tr.dev(m, ctx) for _, m in items]
+    devs = [dev(m, ctx) for _, m in items]
     outs, flags = rustfst_amd.top_sort_batch(devs, ctx, return_in_kernel=True)
     st = _stats(ctx)
     got = [o.to_flat() for o in outs]
@@ -300,11 +295,11 @@ def check_list(items, ctx, launches=None):
 def test_k19_machines_in_one_list(gpu_ctx):
     items = [x for x in k19_machines() if x[0] != "k19 two_states_no_start"]
     got, _ = check_list(items, gpu_ctx)
-    g = tt.golden()
+    g = top_sort_golden()
     by = dict(zip((name for name, _ in items), got))
     for c in g["cases"]:
         if c["op"] == "top_sort" and "error" not in c:
-            same(by["k19 " + c["arg"]], fst_to_flat(tr.golden_fst(c["expected"])), c["name"])
+            same(by["k19 " + c["arg"]], fst_to_flat(golden_fst(c["expected"])), c["name"])
     assert by["k19 no_states"]["n_states"] == 0
 
 
@@ -314,7 +309,7 @@ def test_random_dags_in_one_list(gpu_ctx):
     got, _ = check_list(items, gpu_ctx)
     bits = ACYCLIC | INITIAL_ACYCLIC | TOP_SORTED
     for (name, m), g in zip(items, got):
-        assert g["props"] & bits == bits and g["start"] == tt.dfs_top_order(m)[1][m["start"]], name
+        assert g["props"] & bits == bits and g["start"] == dfs_top_order(m)[1][m["start"]], name
         assert np.all(g["arcs"]["nextstate"] > np.repeat(np.arange(g["n_states"]), np.diff(g["offsets"].astype(np.int64)))), name
 
 
@@ -327,7 +322,7 @@ def test_small_shapes_and_the_order_of_the_search(gpu_ctx):
         assert by[name]["props"] & (CYCLIC | NOT_TOP_SORTED) == CYCLIC | NOT_TOP_SORTED, name
     # the order is the search's, not the levels': the diamond's levels are {0}, {1, 2}, {3} whichever arc of state 0 is
     # stored first, but the search numbers last the branch it takes first; the skew diamond has one order either way
-    orders = {name: tt.dfs_top_order(m)[1] for name, m in items if "diamond" in name}
+    orders = {name: dfs_top_order(m)[1] for name, m in items if "diamond" in name}
     assert orders == {"skew diamond, 0->1 first": [0, 2, 1, 3], "skew diamond, 0->2 first": [0, 2, 1, 3],
                       "diamond, 0->1 first": [0, 2, 1, 3], "diamond, 0->2 first": [0, 1, 2, 3]}
     assert by["diamond, 0->1 first"]["arcs"]["nextstate"].tolist() == [2, 1, 3, 3]
@@ -369,11 +364,11 @@ def test_lists_of_one_of_none_and_of_empty_fsts(gpu_ctx):
     assert rustfst_amd.top_sort_batch([], gpu_ctx) == []  # (the Python side answers an empty list itself)
     assert _lib.lib().wfst_top_sort_batch(gpu_ctx._h, None, 0, None, None) == 0
     assert _stats(gpu_ctx) == dict(launches=0, items_in_kernel=0, items_single=0)
-    empty = tr.make_fst([], [], None, model.ACCEPTOR)
+    empty = make_fst([], [], None, model.ACCEPTOR)
     got, _ = check_list([("empty a", empty), ("empty b", dict(empty, props=0)), ("empty c", empty)], gpu_ctx, launches=0)
     assert all(g["n_states"] == 0 and g["props"] & TOP_SORTED for g in got)
     # the same handle twice, and an item between the two
-    devs = [tr.dev(m, gpu_ctx) for _, m in random_dags()[20:22]]
+    devs = [dev(m, gpu_ctx) for _, m in random_dags()[20:22]]
     outs = rustfst_amd.top_sort_batch([devs[0], devs[1], devs[0]], gpu_ctx)
     for o, k in zip(outs, (20, 21, 20)):
         same(o.to_flat(), reference(*random_dags()[k]), "the same handle twice")
@@ -399,13 +394,13 @@ def test_getter_pointer_by_pointer(gpu_ctx):
 def test_counters_of_the_single_call_describe_the_last_single_call(gpu_ctx):
     """wfst_ctx_get_top_sort_stats: a batch without a fallback item leaves it alone, one with such an item leaves that item's"""
     import rustfst_amd
-    small = tr.dev(random_dags()[30][1], gpu_ctx)
+    small = dev(random_dags()[30][1], gpu_ctx)
     small.top_sort()
     before = gpu_ctx.top_sort_stats()
     assert before["levels"] > 0
     rustfst_amd.top_sort_batch([small, small], gpu_ctx)
     assert gpu_ctx.top_sort_stats() == before
-    big = tr.dev(dict(limit_families())["states 4097"], gpu_ctx)
+    big = dev(dict(limit_families())["states 4097"], gpu_ctx)
     rustfst_amd.top_sort_batch([small, big], gpu_ctx)
     assert gpu_ctx.top_sort_stats()["levels"] == MAX_STATES + 1
     assert _stats(gpu_ctx) == dict(launches=1, items_in_kernel=1, items_single=1)
@@ -420,7 +415,7 @@ def test_no_start_state_is_the_loops_ko_and_the_context_works_afterwards(gpu_ctx
     items[7] = dict(items[7], start=None)
     n3 = len(items[3]["rows"])
     assert n3 > 0 and len(items[7]["rows"]) not in (0, n3)
-    devs = [tr.dev(m, gpu_ctx) for m in items]
+    devs = [dev(m, gpu_ctx) for m in items]
     arr = (C.c_void_p * 8)(*[d._h.value for d in devs])
     outs = (C.c_void_p * 8)(*[1] * 8)
     flags = (C.c_uint8 * 8)(*[9] * 8)
@@ -439,9 +434,9 @@ def test_foreign_handle_is_ko_before_any_launch(gpu_ctx):
     import rustfst_amd
     from rustfst_amd import _lib
     items = random_dags()[2:6]
-    devs = [tr.dev(m, gpu_ctx) for _, m in items]
+    devs = [dev(m, gpu_ctx) for _, m in items]
     other = rustfst_amd.Context(0)
-    foreign = tr.dev(items[1][1], other)
+    foreign = dev(items[1][1], other)
     hs = [d._h.value for d in devs]
     for handles, text in ((hs[:1] + [foreign._h.value] + hs[2:], "item 1: top_sort_batch: the FST belongs to another context"),
                           (hs[:3] + [None], "item 3: null FST in batch")):
@@ -470,15 +465,15 @@ def test_unions_of_nbest_paths_top_sort_batch_then_optimize_batch(gpu_ctx):
         for k in range(int(rng.integers(2, 6))):
             labels = [int(x) for x in rng.integers(1, 4, size=int(rng.integers(1, 7)))]
             rows = [[[x, x, float(rng.integers(0, 9)) / 4 if i == 0 else 0.0, i + 1]] for i, x in enumerate(labels)] + [[]]
-            strings.append(tr.make_fst(rows, [None] * len(labels) + [0.0], 0, word))
-        unions.append(rustfst_amd.union_list([tr.dev(s, gpu_ctx) for s in strings]))
-        refs.append(tr.fold_ref(tr.union_ref, strings))
+            strings.append(make_fst(rows, [None] * len(labels) + [0.0], 0, word))
+        unions.append(rustfst_amd.union_list([dev(s, gpu_ctx) for s in strings]))
+        refs.append(fold_ref(union_ref, strings))
     with pytest.raises(rustfst_amd.WfstError, match="does not hold ACYCLIC"):
         rustfst_amd.optimize_batch(unions, gpu_ctx)
     sorted_devs, flags = rustfst_amd.top_sort_batch(unions, gpu_ctx, return_in_kernel=True)
     assert flags.tolist() == [1] * 6 and _stats(gpu_ctx) == dict(launches=1, items_in_kernel=6, items_single=0)
     for k, (s, u, r) in enumerate(zip(sorted_devs, unions, refs)):
-        same(s.to_flat(), fst_to_flat(tt.top_sort_ref(r)), f"top_sort_batch(union {k}) vs the restatement")
+        same(s.to_flat(), fst_to_flat(top_sort_ref(r)), f"top_sort_batch(union {k}) vs the restatement")
         same(s.to_flat(), u.top_sort().to_flat(), f"top_sort_batch(union {k}) vs the single call")
     optimized = rustfst_amd.optimize_batch(sorted_devs, gpu_ctx)
     for k, (o, u) in enumerate(zip(optimized, unions)):

@@ -23,11 +23,9 @@ import numpy as np
 import pytest
 
 from oracle import model
-from oracle.model import fst_to_flat
+from oracle.model import fst_to_flat, top_sort_ref
 import helpers
-from helpers import assert_flat_identical
-import test_rational_ops as tr
-import test_top_sort as tt
+from helpers import assert_flat_identical, dev, make_fst
 
 ROOT = helpers.ROOT
 PATHS = ("auto", "narrow", "wide")
@@ -62,7 +60,7 @@ def kahn_levels(fst):
 
 
 def dfs_depths(fst):
-    """depth of every state in the forest of the literal search (test_top_sort.dfs_top_order, with the parents kept)"""
+    """depth of every state in the forest of the literal search (oracle.model's dfs_top_order, with the parents kept)"""
     rows, start = fst["rows"], fst["start"]
     n = len(rows)
     depth = [0] * n
@@ -148,7 +146,7 @@ class Builder:
             rows[name[s]] = [[il, ol, w, name[t]] for il, ol, w, t in row]
         finals = [float(self.rng.integers(0, 8)) / 4 if self.rng.random() < 0.3 else None for _ in range(n)]
         start = n - 1 if start == "last" else name[start]
-        return tr.make_fst(rows, finals, start)
+        return make_fst(rows, finals, start)
 
 
 def layers(widths, seed, start=0, fan_in=3):
@@ -364,7 +362,7 @@ def test_restatement_on_every_shape():
     """the restated result of every acyclic shape is topologically sorted; the cyclic ones come back as they are"""
     for name, make in SHAPES.items():
         m = make()
-        got = tt.top_sort_ref(m)
+        got = top_sort_ref(m)
         if name.startswith("cyclic_"):
             assert got["rows"] == m["rows"] and got["props"] == model.CYCLIC | model.NOT_TOP_SORTED, name
         else:
@@ -378,8 +376,8 @@ def test_every_shape_on_every_route(gpu_ctx, monkeypatch, path):
     monkeypatch.setenv("WFST_TOP_SORT_PATH", path)
     for name, make in SHAPES.items():
         m = make()
-        exp = fst_to_flat(tt.top_sort_ref(m))
-        got = tr.dev(m, gpu_ctx).top_sort().to_flat()
+        exp = fst_to_flat(top_sort_ref(m))
+        got = dev(m, gpu_ctx).top_sort().to_flat()
         assert_flat_identical(got, exp, f"{name} under {path}", check_props=True)
         assert gpu_ctx.top_sort_stats() == predict(m, path), f"{name} under {path}"
 
@@ -392,7 +390,7 @@ def test_routes_were_taken(gpu_ctx, monkeypatch):
     seen = {}
     for path in PATHS:
         monkeypatch.setenv("WFST_TOP_SORT_PATH", path)
-        tr.dev(m, gpu_ctx).top_sort()
+        dev(m, gpu_ctx).top_sort()
         seen[path] = gpu_ctx.top_sort_stats()
     assert seen["auto"]["narrow_launches"] == 8 and seen["auto"]["wide_launches"] == 4
     assert seen["narrow"]["narrow_launches"] == 4 and seen["narrow"]["wide_launches"] == 0

@@ -15,10 +15,10 @@ import re
 import numpy as np
 import pytest
 
-from oracle.model import INF, rows_flat
+from oracle.model import INF, apply_op, rows_flat
 import helpers
 from helpers import assert_flat_identical, to_device
-from test_optimize import apply_op, part_a_rows, part_b_rows, random_arc_lists
+from optimize_cases import part_a_rows, part_b_rows, random_arc_lists
 
 ROOT = helpers.ROOT
 MAX_STATES, MAX_ARCS, RANK_MAX = 4096, 16384, 256  # include/wfst.h: the in_kernel rule
@@ -53,7 +53,7 @@ def rows_of(flat):
 
 
 def part_a_in_kernel():
-    """test_optimize.part_a_rows with its states of more than 256 arcs cut to 256: degrees 0, 1, 16, 17, 256, the runs over a
+    """optimize_cases.part_a_rows with its states of more than 256 arcs cut to 256: degrees 0, 1, 16, 17, 256, the runs over a
     chunk boundary and over a whole state, all inside the kernel"""
     flat = part_a_rows()
     return rows_flat([r[:RANK_MAX] for r in rows_of(flat)], list(flat["finals"]))

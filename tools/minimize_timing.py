@@ -1,6 +1,6 @@
 """minimize on three shapes: the closed-form blow-up of a small minimal DAG (>= 1 M states, wide heights), a deep thin
 chain (20 000 heights of two states) and a determinized lattice.  First call and median of repeated calls, wall clock
-around the synchronous call, then the Python restatement of tests/test_minimize.py on the same host where it finishes
+around the synchronous call, then the Python restatement of oracle/model/minimize.py on the same host where it finishes
 within a minute (it is a literal sequential restatement, not an optimised CPU implementation).
 python tools/minimize_timing.py [blow_up_states] [chain_heights]"""
 import os, sys, time
@@ -10,8 +10,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import rustfst_amd
 from rustfst_amd._lib import TR_DTYPE
-from oracle.model import ACCEPTOR
-from test_minimize import blow_up, closed_form_base, minimize_ref  # the inputs the tests use
+from oracle.model import ACCEPTOR, minimize_ref
+from minimize_cases import blow_up, closed_form_base  # the inputs the tests use
 
 STATES = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
 HEIGHTS = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000

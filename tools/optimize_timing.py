@@ -3,7 +3,7 @@ around the synchronous call.
   1. tr_sum / tr_unique of the benchmark transducer (1 M states / ~10 M arcs) and of a copy with every arc duplicated;
      yardstick: the device tr_sort of the same arcs (a fresh upload per repetition: tr_sort works in place and returns at
      once on a sorted handle)
-  2. optimize of a wide acyclic input: the twin-copy construction of tests/test_determinize.py on a layered DAG (twin_copy
+  2. optimize of a wide acyclic input: the twin-copy construction of tests/inputs.py on a layered DAG (twin_copy
      itself sits on the cyclic benchmark transducer), with parallel and eps:eps arcs added, as an acceptor and as the same
      machine with pair labels; yardstick: the separately timed stages on handles
   3. optimize of one deep, thin lattice (diamond_chain)
