@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -696,6 +696,26 @@ wfst_status wfst_compose_lookahead(wfst_ctx* ctx, const wfst_lookahead* la, cons
  * left allocated. */
 wfst_status wfst_compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst_fst* const* relabeled_fst2s,
                                          size_t n, wfst_fst** outs);
+/* which route answered the compositions of the last wfst_compose_lookahead / wfst_compose_lookahead_batch call of ctx (reset
+ * when the call begins; every route returns the same FST).  With m = the items that have a start state: one launch of the
+ * single-wave kernel takes the m compositions, one wave each, in arenas of S = 2 * 2048 + 256 = 4352 states, A = 4 * S =
+ * 17408 arcs and H = pow2(2 * S + 128) = 16384 table slots.  A wave gives up once its result passes 2048 states at the end
+ * of a level that found new states, or a level adds more than 256 states; with m == 1 the limits are 512 and 48
+ * (one_limits = 1).  items: n; items_no_start: items without a start state (the empty FST, nothing launched);
+ * wave_answered: compositions the single-wave kernel finished; handed_over_states: it gave up with more states than the state
+ * limit in force; handed_over_width: it gave up otherwise (a level wider than the width limit); overflow_arcs /
+ * overflow_states: its arena's arcs / states were full; wide_items: compositions the wide driver ran (the four before it
+ * summed; all m under WFST_LOOKAHEAD_PATH=wide, where nothing else counts); wave_regrows: under WFST_LOOKAHEAD_PATH=wave
+ * (no hand-over, one_limits = 0) the lone launches that redo a composition whose arena was full, S = 16 * 2048 and four times
+ * that per attempt, the successful one included; wide_grows: growths of the wide driver's arena; wide_hinted: compositions
+ * whose wide arena was raised by the size the handle's last wide result left (applies when the arcs of the two second
+ * operands are within a factor of two); hint_fallbacks: such an allocation was refused and the unhinted estimate used.  Any
+ * out-pointer may be NULL. */
+wfst_status wfst_ctx_get_lookahead_stats(wfst_ctx* ctx, uint64_t* items, uint64_t* items_no_start, uint64_t* wave_answered,
+                                         uint64_t* handed_over_states, uint64_t* handed_over_width, uint64_t* overflow_arcs,
+                                         uint64_t* overflow_states, uint64_t* wide_items, uint64_t* wave_regrows,
+                                         uint64_t* wide_grows, uint64_t* wide_hinted, uint64_t* hint_fallbacks,
+                                         uint64_t* one_limits);
 wfst_status wfst_lookahead_destroy(wfst_lookahead* la);
 /* LabelReachableData of a look-ahead handle: sizes, then the arrays (interval_offsets[n_states + 1], intervals[2 *
  * n_intervals] = half-open [begin, end) pairs over relabelled labels, labels[n_labels] ascending with their indices;

@@ -39,6 +39,7 @@ thread_local const char* t_queue_kind = "";
 // look-ahead composition bookkeeping for tools/lookahead_tuple_gap.py: tuples created, and how many of them had an
 // already-present tuple equal in everything but a pushed weight exactly one KDELTA step away
 thread_local uint64_t t_la_tuples = 0, t_la_adjacent = 0;
+thread_local std::vector<uint32_t> t_la_tuple_list;  // five words per composed state of the last look-ahead composition
 
 struct DeltaGuard {
   float saved;
@@ -2845,6 +2846,11 @@ bool compose_lookahead(const Fst& in1, const Fst& in2, Fst& out, Fst& r1, Fst& r
     }
     out.set_properties(op.properties);
   }
+  for (const Tuple5& t : op.id_to_tuple) {
+    uint32_t wb;
+    std::memcpy(&wb, &t.fs.fweight, 4);
+    t_la_tuple_list.insert(t_la_tuple_list.end(), {t.s1, t.s2, t.fs.fs1, wb, t.fs.flabel});
+  }
   return true;
 }
 
@@ -2860,6 +2866,11 @@ const char* oracle_last_queue_kind(void) { return t_queue_kind; }
 void oracle_last_lookahead_tuples(uint64_t* tuples, uint64_t* adjacent) {
   *tuples = t_la_tuples;
   *adjacent = t_la_adjacent;
+}
+size_t oracle_last_lookahead_tuple_list(uint32_t* out, size_t cap) {
+  const size_t n = t_la_tuple_list.size() / 5;
+  if (out) std::memcpy(out, t_la_tuple_list.data(), std::min(n, cap) * 5 * sizeof(uint32_t));
+  return n;
 }
 
 oracle_fst* oracle_fst_new(void) { return new oracle_fst(); }
@@ -2965,6 +2976,7 @@ int oracle_compose_lookahead(const oracle_fst* f1, const oracle_fst* f2, oracle_
                              oracle_fst** relabeled2) {
   DeltaGuard g(ORACLE_EQ_REF_KDELTA);
   t_la_tuples = t_la_adjacent = 0;
+  t_la_tuple_list.clear();
   std::unique_ptr<oracle_fst> o(new oracle_fst()), r1(new oracle_fst()), r2(new oracle_fst());
   la::LabelReachableData data;
   if (!la::compose_lookahead(*f1, *f2, *o, *r1, *r2, data)) return 1;

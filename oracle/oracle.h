@@ -143,6 +143,9 @@ const char* oracle_last_queue_kind(void);
 /* after oracle_compose_lookahead on this thread: composed-state tuples created, and how many had a twin differing only by
  * a pushed weight one KDELTA step away (the pairs the reference's approximate PartialEq could merge) */
 void oracle_last_lookahead_tuples(uint64_t* tuples, uint64_t* adjacent);
+/* ... and the tuples themselves, in id order: five words per composed state (fst1 state, fst2 state, AltSequence state, bits
+ * of the pushed weight, pushed label or NO_LABEL); writes at most `cap` tuples, returns how many there are */
+size_t oracle_last_lookahead_tuple_list(uint32_t* out, size_t cap);
 
 /* CANONICAL single shortest path: the deterministic tie rule the GPU engine implements
  * (DESIGN.md §Shortest path): (d,h)[t] = lexicographic min over paths of (left-fold f32 sum,

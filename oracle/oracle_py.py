@@ -68,6 +68,8 @@ def lib():
         L.oracle_compose_lookahead.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.oracle_last_lookahead_tuples.argtypes = [C.POINTER(u64), C.POINTER(u64)]
         L.oracle_last_lookahead_tuples.restype = None
+        L.oracle_last_lookahead_tuple_list.argtypes = [vp, C.c_size_t]
+        L.oracle_last_lookahead_tuple_list.restype = C.c_size_t
         L.oracle_interval_set_normalize.argtypes = [vp, C.c_size_t, C.POINTER(u64)]
         L.oracle_interval_set_normalize.restype = i64
         L.oracle_interval_set_member.argtypes = [vp, C.c_size_t, u64]
@@ -228,6 +230,16 @@ class OracleFst:
         a, b = C.c_uint64(), C.c_uint64()
         lib().oracle_last_lookahead_tuples(C.byref(a), C.byref(b))
         return a.value, b.value
+
+    @staticmethod
+    def last_lookahead_tuple_list():
+        """The composed-state tuples of this thread's last compose_lookahead in id order: a uint32 array [n, 5] of (fst1
+        state, fst2 state, AltSequence state, bits of the pushed weight, pushed label or 0xFFFFFFFF)."""
+        n = lib().oracle_last_lookahead_tuple_list(None, 0)
+        out = np.zeros((n, 5), dtype=np.uint32)
+        if n:
+            lib().oracle_last_lookahead_tuple_list(out.ctypes.data, n)
+        return out
 
     def label_reachable(self, reach_input=False):
         """LabelReachable::compute_data (label_reachable.rs:135-273): dict(final_label, label2index {label: index},

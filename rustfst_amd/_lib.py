@@ -93,6 +93,9 @@ COUNTERS = {
     "top_sort": ("wfst_ctx_get_top_sort_stats",
                  ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "max_tree_depth", "lift_rows",
                   "states_compared", "wave_states", "cyclic")),
+    "lookahead": ("wfst_ctx_get_lookahead_stats",
+                  ("items", "items_no_start", "wave_answered", "handed_over_states", "handed_over_width", "overflow_arcs",
+                   "overflow_states", "wide_items", "wave_regrows", "wide_grows", "wide_hinted", "hint_fallbacks", "one_limits")),
 }
 
 # wfst_ctx_get_top_sort_batch_counters: the uint64_t* parameters behind ctx, in order: a one-workgroup-per-item batch family

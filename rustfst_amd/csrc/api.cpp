@@ -1098,6 +1098,15 @@ wfst_status wfst_compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la
     compose_lookahead_batch(ctx, la, relabeled_fst2s, n, outs);
   });
 }
+wfst_status wfst_ctx_get_lookahead_stats(wfst_ctx* ctx, uint64_t* items, uint64_t* items_no_start, uint64_t* wave_answered,
+                                         uint64_t* handed_over_states, uint64_t* handed_over_width, uint64_t* overflow_arcs,
+                                         uint64_t* overflow_states, uint64_t* wide_items, uint64_t* wave_regrows,
+                                         uint64_t* wide_grows, uint64_t* wide_hinted, uint64_t* hint_fallbacks,
+                                         uint64_t* one_limits) {
+  return get_counters(ctx, &wfst_ctx::lookahead, {items, items_no_start, wave_answered, handed_over_states, handed_over_width,
+                                                  overflow_arcs, overflow_states, wide_items, wave_regrows, wide_grows,
+                                                  wide_hinted, hint_fallbacks, one_limits});
+}
 
 wfst_status wfst_lookahead_destroy(wfst_lookahead* la) {
   return wrap([&] {

@@ -334,6 +334,16 @@ struct wfst_ctx {
     uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, max_tree_depth = 0;
     uint64_t lift_rows = 0, states_compared = 0, wave_states = 0, cyclic = 0;
   } top_sort;
+  // Which route answered the compositions of the last wfst_compose_lookahead / wfst_compose_lookahead_batch call: tallied on the
+  // host by compose_lookahead.hip from the LaResult words its kernel already reports and from what the wide driver returns.
+  // handed_over_states / _width: LA_SWITCH_WIDE with n_states above the state limit in force / otherwise; wave_regrows: arena
+  // attempts under WFST_LOOKAHEAD_PATH=wave; one_limits: 1 when the limits of a call with ONE composition applied.  Zeroed when
+  // the driver begins.
+  struct LookaheadStats {
+    uint64_t items = 0, items_no_start = 0, wave_answered = 0, handed_over_states = 0, handed_over_width = 0;
+    uint64_t overflow_arcs = 0, overflow_states = 0, wide_items = 0, wave_regrows = 0, wide_grows = 0, wide_hinted = 0;
+    uint64_t hint_fallbacks = 0, one_limits = 0;
+  } lookahead;
   // The last wfst_replace call: the driver's level and size figures, the counters of replace.hip's policy block, and the two
   // kinds of growth (the driver's arena in place, the prefix table by a rerun).  Zeroed when replace.hip's driver begins.
   struct ReplaceStats {

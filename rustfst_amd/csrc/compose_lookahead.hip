@@ -596,14 +596,26 @@ wfst_fst* compose_lookahead_wide(wfst_ctx* ctx, const wfst_lookahead* la, const 
     }
   }
   const uint64_t t0 = ((uint64_t)(uint32_t)f1->start << 32) | (uint32_t)fst2->start;
+  uint64_t grows = 0;
+  const WideWho who{"compose", "composition", &grows};
+  auto count = [&]() {
+    ctx->stats.compose_retries += grows;
+    ctx->lookahead.wide_grows += grows;
+    grows = 0;
+  };
+  ctx->lookahead.wide_items++;
+  ctx->lookahead.wide_hinted += hinted ? 1 : 0;
   try {
-    run_wide(ctx, pol, t0, pack_hi(FState{0u, 0.0f, NO_LABEL}), est_s, est_a, 1.0 + std::min(d1, d2), w);
+    run_wide(ctx, pol, t0, pack_hi(FState{0u, 0.0f, NO_LABEL}), est_s, est_a, 1.0 + std::min(d1, d2), w, who);
   } catch (const Error&) {
+    count();
     if (!hinted) throw;
     (void)hipGetLastError();  // (a refused allocation must not surface at the next launch check)
+    ctx->lookahead.hint_fallbacks++;
     w = WideOutput{};
-    run_wide(ctx, pol, t0, pack_hi(FState{0u, 0.0f, NO_LABEL}), est_s0, est_a0, 1.0 + std::min(d1, d2), w);
+    run_wide(ctx, pol, t0, pack_hi(FState{0u, 0.0f, NO_LABEL}), est_s0, est_a0, 1.0 + std::min(d1, d2), w, who);
   }
+  count();
   la->last_wide_states.store(w.n_states, std::memory_order_relaxed);
   la->last_wide_arcs.store(w.n_arcs, std::memory_order_relaxed);
   la->last_wide_input_arcs.store(fst2->n_arcs, std::memory_order_relaxed);
@@ -627,6 +639,9 @@ void check_lookahead_operands(const wfst_lookahead* la, const wfst_fst* fst2) {
 // n problems (la's fst1, fst2s[i]) in one launch of the single-wave kernel, one wave each; results that outgrow it (or its
 // arena) are redone one by one: bigger arena, then the wide path
 void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst_fst* const* fst2s, size_t n, wfst_fst** outs) {
+  ctx->lookahead = wfst_ctx::LookaheadStats{};  // (a call that refuses an operand leaves items alone)
+  wfst_ctx::LookaheadStats& stats = ctx->lookahead;
+  stats.items = n;
   for (size_t i = 0; i < n; ++i) {
     outs[i] = nullptr;
     if (!fst2s[i]) throw Error("null pointer");
@@ -646,6 +661,7 @@ void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst
         HostCsr h;
         h.offsets.push_back(0);
         done[i].reset(make_host_fst(ctx, 0, -1, lookahead_result_props(f1->props, fst2s[i]->props, false), std::move(h)));
+        stats.items_no_start++;
       } else {
         todo.push_back(i);
         views.push_back(view_of(fst2s[i]));
@@ -660,6 +676,8 @@ void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst
       size_t stride = 0;
       la_carve(nullptr, caps, &stride);
       const size_t m = todo.size();
+      const uint32_t switch_states = m == 1 ? WIDE_SWITCH_STATES_ONE : WIDE_SWITCH_STATES;
+      stats.one_limits = force != 1 && m == 1 ? 1 : 0;
       DBuf<char> arena(*ctx->pool, stride * m);
       DBuf<LaView> d_views(*ctx->pool, m);
       DBuf<LaResult> d_res(*ctx->pool, m);
@@ -668,7 +686,7 @@ void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst
       // a lone composition hands over early (the wide driver costs ~15 us per narrow level, this kernel ~3 us per STATE);
       // in a batch the other waves are busy meanwhile, and the wide driver would take the problems one by one
       compose_lookahead_kernel<<<(uint32_t)m, 64, 0, st>>>(view_of(f1), d_views.p, reach, caps, arena.p, stride, d_res.p,
-                                                            force == 1 ? 0xFFFFFFFFu : (m == 1 ? WIDE_SWITCH_STATES_ONE : WIDE_SWITCH_STATES),
+                                                            force == 1 ? 0xFFFFFFFFu : switch_states,
                                                             m == 1 ? WIDE_SWITCH_WIDTH_ONE : WIDE_SWITCH_WIDTH);
       HIP_CHECK(hipGetLastError());
       std::vector<LaResult> res(m);
@@ -680,9 +698,12 @@ void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst
         const size_t i = todo[k];
         const LaResult& r = res[k];
         if (r.status != LA_OK) {
+          if (r.status == LA_SWITCH_WIDE) ++(r.n_states > switch_states ? stats.handed_over_states : stats.handed_over_width);
+          else ++(r.status == LA_OVERFLOW_ARCS ? stats.overflow_arcs : stats.overflow_states);
           redo.push_back(k);
           continue;
         }
+        stats.wave_answered++;
         const LaArena ar = la_carve(arena.p + k * stride, caps, nullptr);
         ok.push_back(AdoptDesc{r.n_states, r.n_arcs, r.n_states ? 0 : -1, lookahead_result_props(f1->props, fst2s[i]->props, true),
                                ar.off, ar.arcs, ar.fin});
@@ -720,7 +741,9 @@ void compose_lookahead_batch(wfst_ctx* ctx, const wfst_lookahead* la, const wfst
           LaResult r;
           HIP_CHECK(hipMemcpyAsync(&r, d_res.p, sizeof(r), hipMemcpyDeviceToHost, st));
           HIP_CHECK(hipStreamSynchronize(st));
+          stats.wave_regrows++;
           if (r.status == LA_OK) {
+            stats.wave_answered++;
             const LaArena ar = la_carve(arena.p, caps, nullptr);
             done[i].reset(adopt_device(ctx, r.n_states, r.n_arcs, r.n_states ? 0 : -1, out_props, ar.off, ar.arcs, ar.fin));
             ctx->stats.compose_states = r.n_states;

@@ -181,6 +181,16 @@ class Context:
         at least two states (states_compared), states a whole wave took (wave_states) and the CYCLIC exit (cyclic)."""
         return _counters("top_sort", self)
 
+    def lookahead_stats(self) -> dict:
+        """Which route answered the compositions of this context's last LookAhead.compose / compose_batch call
+        (wfst_ctx_get_lookahead_stats): items and those without a start state, compositions the single-wave kernel finished
+        (wave_answered), gave up on for their states or for a level's width (handed_over_states, handed_over_width) or for a
+        full arena (overflow_arcs, overflow_states), compositions the wide driver ran (wide_items), lone relaunches under
+        WFST_LOOKAHEAD_PATH=wave (wave_regrows), growths of the wide arena (wide_grows), wide arenas raised by the handle's
+        hint (wide_hinted) and hinted allocations that were refused (hint_fallbacks), and whether the limits of a call with
+        one composition applied (one_limits)."""
+        return _counters("lookahead", self)
+
     def replace_stats(self) -> dict:
         """This context's last replace call (wfst_ctx_get_replace_stats): levels of the search, states and arcs of the result,
         distinct non-empty call stacks interned (prefixes) and the deepest of them (max_depth), call arcs emitted, call arcs

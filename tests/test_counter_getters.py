@@ -1,4 +1,4 @@
-"""The per-pointer contract of the 16 wfst_ctx_get_*_stats getters: any out-pointer behind ctx may be NULL, and each one
+"""The per-pointer contract of the 17 wfst_ctx_get_*_stats getters: any out-pointer behind ctx may be NULL, and each one
 alone receives the counter of its position.  What the counters COUNT is pinned by the limit tests of each family through the
 Python dicts; here one context runs one smallest-possible call per family, so that most counters hold something, and every
 getter is then read pointer by pointer against the dict its Python accessor returns."""
@@ -56,6 +56,8 @@ def run_every_family(ctx):
     rustfst_amd.minimize_batch([d], ctx=ctx)
     rustfst_amd.optimize_batch([a], ctx)
     rustfst_amd.compose_shortest_path_batch([to_device(synth.linear_acceptor_flat([1, 2, 1]), ctx)], t, ctx=ctx)
+    la = rustfst_amd.LookAhead(a)  # one composition the wave answers, one item without a start state
+    la.compose_batch([la.relabel(t), la.relabel(rustfst_amd.VectorFst().to_device(ctx))], ctx)
     ctx.synchronize()
 
 
@@ -84,6 +86,8 @@ def test_every_getter_pointer_by_pointer(wfst_lib):
     for family in ("determinize_batch", "minimize_batch", "rm_epsilon_batch", "tr_sum_batch"):
         assert full[family]["items_in_kernel"] + full[family]["items_single"] == 1, family
     assert opt["items_in_kernel"] + opt["items_single"] == 1
+    la = full["lookahead"]
+    assert (la["items"], la["items_no_start"], la["wave_answered"], la["one_limits"]) == (2, 1, 1, 1)
 
     for family, (symbol, names) in _lib.COUNTERS.items():
         fn, n = getattr(wfst_lib, symbol), len(names)

@@ -2374,6 +2374,8 @@ def test_lookahead_compose_larger(gpu_ctx, oracle, n1, n2, fan2, sigma, seed):
     assert_flat_identical(d2.to_flat(), r2.to_flat(), "relabelled fst2")
     out = la.compose(d2)
     assert out.num_states > 2048  # beyond the single-wave driver: redone on the wide path
+    st = gpu_ctx.lookahead_stats()
+    assert (st["items"], st["wide_items"], st["wave_answered"], st["one_limits"]) == (1, 1, 0, 1)
     assert_flat_identical(out.to_flat(), ref.to_flat(), f"look-ahead composition {n1}x{n2}")
     # the same handle serves further second operands (labels unseen so far get fresh indices, as in the reference)
     b2 = synth.make_transducer(50, 3, 40, 0.05, seed=500 + seed, p_final=0.1)
@@ -2414,6 +2416,9 @@ def test_lookahead_compose_batch(gpu_ctx, oracle):
     outs = la.compose_batch(d2)
     assert len(outs) == 40 and outs[-1].num_states == 0
     assert outs[38].num_states > 2048
+    st = gpu_ctx.lookahead_stats()
+    assert (st["items"], st["items_no_start"], st["wave_answered"] + st["wide_items"], st["one_limits"]) == (40, 1, 39, 0)
+    assert st["wide_items"] >= 1  # (outs[38] at least)
     for i, b in enumerate(bs):
         ref = oa.compose_lookahead(to_oracle(oracle, b)).to_flat()
         assert_flat_identical(outs[i].to_flat(), ref, f"batched look-ahead composition {i}")
