@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats, wfst_compose_batch, wfst_ctx_get_compose_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -126,6 +126,46 @@ typedef struct {
 } wfst_compose_config;
 wfst_status wfst_compose(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2,
                          const wfst_compose_config* cfg, wfst_fst** out);
+
+/* ---- compose of a list: n = max(n1, n2) compositions in one call; each of n1, n2 is n or 1, and a list of one serves every
+ *      item (one grammar against n lattices, one lattice against n grammars).  outs[i] (new handles, each owning its memory)
+ *      is bit for bit what wfst_compose(ctx, fst1s[i or 0], fst2s[i or 0], cfg) returns — state numbering, arc order, finals,
+ *      start and property word — for every compose_filter 0..6, connect on and off, and cfg == NULL.  The inputs are left as
+ *      they are; a handle may appear more than once.  n == 0: OK, nothing is touched.
+ *      Routing, decided from sizes alone (in_kernel: uint8_t[n], may be NULL):
+ *      - an item with no start state on either side is the empty FST with the single call's word: it occupies no workgroup,
+ *        in_kernel[i] == 1, counted in items_no_start and in items_in_kernel;
+ *      - with exactly ONE item that has both start states, that item IS the single call, limits and all: in_kernel[i] == 0,
+ *        items_single;
+ *      - otherwise every such item takes one wavefront of compose_batch_kernel, <<<open items, 64>>>, with its OWN second
+ *        operand, capacities and arena, carved from the launch's slab (a 20-state item beside a 4 000-state item pays for 20
+ *        states).  Attempt k of an item has the single call's capacities: S_k = (4 * max(min(n_states1, n_states2), 64)
+ *        + 1024) * 4^k composed states, A_k = 4 * S_k arcs, H_k = the power of two at or above 2 * S_k + 128 hash slots.  An
+ *        overflow of states, arcs or hash reopens the item with k + 1 in the next launch and counts once, per item and
+ *        attempt, in regrown_states, regrown_arcs or regrown_hash; `launches` therefore follows the deepest regrowth among
+ *        the items, not n.  An item whose next S_k exceeds 16384 leaves the kernel — at k = 0 when min(n_states1, n_states2)
+ *        > 3840 — for the wide driver with that estimate: in_kernel[i] == 0, items_single;
+ *      - the width hand-over of the single call is OFF in a list: while other waves are busy, a BFS level of more than 64 new
+ *        states stays with its wave on the arena route (the single call would redo such a pair on the wide driver, and a list
+ *        of lattices would then run one by one).  The result is the same FST.
+ *      The slices of one launch may take 8 GiB together: beyond that the call is KO before that launch ("split the list").
+ *      WFST_COMPOSE_BATCH_ARENA=min (tests) starts every item at the kernel's minimum, S = 64 and A = 128, so that every item
+ *      grows.
+ *      KO, decided before any GPU work and in this order: a NULL pointer "null pointer"; "compose_batch: the lists hold {n1}
+ *      and {n2} FSTs (equal lengths, or one of them 1)"; "unknown compose_filter"; a NULL entry ("item <i>: null FST in
+ *      batch"); an entry of another device or context ("item <i>: compose_batch: the FST lives on another device" / "...
+ *      belongs to another context").  Then, per item in index order and before anything is launched, the single call's own
+ *      errors behind "item <i>: " (the "(sort?)" messages, "compose: the 1st FST has more than 2^30 states"): the lowest
+ *      failing index wins.  After a KO every outs[i] is NULL, no handle leaks and the context works on. ---- */
+wfst_status wfst_compose_batch(wfst_ctx* ctx, const wfst_fst* const* fst1s, size_t n1, const wfst_fst* const* fst2s, size_t n2,
+                               const wfst_compose_config* cfg, wfst_fst** outs, uint8_t* in_kernel);
+/* the last wfst_compose_batch call of ctx that passed the checks above (reset when such a call begins; a call that is KO
+ *      before anything is launched, and one with n == 0, leaves them alone): launches of compose_batch_kernel, items with in_kernel
+ *      == 1, items that went through the single call or the wide driver, items without a start state, and the regrowths by
+ *      cause.  Any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_compose_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                uint64_t* items_single, uint64_t* items_no_start, uint64_t* regrown_states,
+                                                uint64_t* regrown_arcs, uint64_t* regrown_hash);
 
 /* ---- compose with matcher configs: fst_compose_with_config with a non-empty matcher1_config / matcher2_config
  *      (rustfst-ffi/src/algorithms/compose.rs:183-250) = compose_with_config with SigmaMatcher<SortedMatcher> on side 1 (m1),

@@ -32,6 +32,7 @@
 //   (look-ahead recipe of rustfst-cli/src/cmds/compose.rs)       LookAheadFst(fst1).compose(fst2) / compose_lookahead
 //   compose(fst1, fst2) / compose_with_config(.., ComposeConfig) compose(..) / compose_with_config(..)   compose_static.rs:166-306
 //   MatcherConfig { sigma_matcher_config: Some(SigmaMatcherConfig) } ComposeConfig::matcher1_config / matcher2_config  compose_static.rs:30-54
+//   (a loop of compose_with_config over many pairs)              compose_batch(fst1s, fst2s, config)
 //   shortest_path(&fst) / shortest_path_with_config(..)          shortest_path(..) / shortest_path_with_config(..)  shortest_path.rs:76-133
 //   (a loop of the two over many acceptors)                      compose_shortest_path_batch(acceptors, t, config)
 //   anyhow::Result<T> Err(e)                                     throws wfst_amd::Error (what() = the library's message)
@@ -215,6 +216,34 @@ inline VectorFst compose_with_config(const VectorFst& fst1, const VectorFst& fst
 }
 inline VectorFst compose(const VectorFst& fst1, const VectorFst& fst2) {  // compose_static.rs:293-303
   return compose_with_config(fst1, fst2, ComposeConfig{});
+}
+
+// for i: compose_with_config(fst1s[i or 0], fst2s[i or 0], config) as ONE call (wfst_compose_batch): equal lengths, or a list
+// of one on either side, which serves every item.  Matcher configs are not part of this call.
+inline std::vector<VectorFst> compose_batch(const std::vector<VectorFst>& fst1s, const std::vector<VectorFst>& fst2s,
+                                            const ComposeConfig& config = ComposeConfig{}) {
+  if (!config.matcher1_config.empty() || !config.matcher2_config.empty())
+    throw Error("unsupported: a MatcherConfig (sigma matcher) in compose_batch");
+  const size_t n1 = fst1s.size(), n2 = fst2s.size(), n = n1 > n2 ? n1 : n2;
+  std::vector<detail::DeviceFst> a(n1), b(n2), out(n);
+  std::vector<const wfst_fst*> h1(n1), h2(n2);
+  std::vector<wfst_fst*> res(n, nullptr);
+  for (size_t i = 0; i < n1; ++i) {
+    detail::upload(fst1s[i], a[i]);
+    h1[i] = a[i].h;
+  }
+  for (size_t i = 0; i < n2; ++i) {
+    detail::upload(fst2s[i], b[i]);
+    h2[i] = b[i].h;
+  }
+  const wfst_compose_config cfg{(uint32_t)config.compose_filter, config.connect ? 1u : 0u};
+  check(wfst_compose_batch(Context::current().get(), h1.data(), n1, h2.data(), n2, &cfg, res.data(), nullptr));
+  std::vector<VectorFst> fsts;
+  for (size_t i = 0; i < n; ++i) {
+    out[i].h = res[i];
+    fsts.push_back(detail::download(out[i]));
+  }
+  return fsts;
 }
 
 // shortest_path_with_config (shortest_path.rs:107-170)

@@ -102,6 +102,9 @@ COUNTERS = {
 # like the *_batch entries above, its getter outside the table of the *_stats families
 TOP_SORT_BATCH_COUNTERS = _BATCH
 
+# wfst_ctx_get_compose_batch_counters: the same driver's three counts, then what the list form of compose adds to them
+COMPOSE_BATCH_COUNTERS = _BATCH + ("items_no_start", "regrown_states", "regrown_arcs", "regrown_hash")
+
 # wfst_ctx_get_compose_sigma_counters: the uint64_t* parameters behind ctx, in order (outside the table of the *_stats families)
 COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "require2_states", "exact_items", "sigma_items",
                           "sigma_arcs", "refused_items", "arena_grows", "level_launches")
@@ -123,6 +126,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_ctx_get_compose_sigma_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_SIGMA_COUNTERS)),
     ("wfst_ctx_get_sigma_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(SIGMA_BATCH_COUNTERS)),
     ("wfst_ctx_get_top_sort_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(TOP_SORT_BATCH_COUNTERS)),
+    ("wfst_ctx_get_compose_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_BATCH_COUNTERS)),
     ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_ctx_get_string_placement", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PLACEMENT)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
@@ -146,6 +150,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_fst_destroy", C.c_int, [_vp]),
     ("wfst_fst_destroy_many", C.c_int, [_P(_vp), _sz]),
     ("wfst_compose", C.c_int, [_vp, _vp, _vp, _P(ComposeConfig), _P(_vp)]),
+    ("wfst_compose_batch", C.c_int, [_vp, _P(_vp), _sz, _P(_vp), _sz, _P(ComposeConfig), _P(_vp), _vp]),
     ("wfst_compose_with_matchers", C.c_int, [_vp, _vp, _vp, _P(ComposeConfig), _P(MatcherConfig), _P(MatcherConfig), _P(_vp)]),
     ("wfst_shortest_path", C.c_int, [_vp, _vp, _P(ShortestPathConfig), _P(_vp)]),
     ("wfst_connect", C.c_int, [_vp, _vp, _P(_vp)]),

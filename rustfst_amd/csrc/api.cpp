@@ -398,6 +398,35 @@ wfst_status wfst_compose(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fs
   });
 }
 
+// compose of n = max(n1, n2) pairs in one call; every argument is checked before anything is launched
+wfst_status wfst_compose_batch(wfst_ctx* ctx, const wfst_fst* const* fst1s, size_t n1, const wfst_fst* const* fst2s, size_t n2,
+                               const wfst_compose_config* cfg, wfst_fst** outs, uint8_t* in_kernel) {
+  return wrap([&] {
+    const size_t n = std::max(n1, n2);
+    if (outs)
+      for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    if (!ctx || !fst1s || !fst2s || !outs) throw Error("null pointer");
+    if ((n1 != n && n1 != 1) || (n2 != n && n2 != 1))
+      throw Error("compose_batch: the lists hold " + std::to_string(n1) + " and " + std::to_string(n2) +
+                  " FSTs (equal lengths, or one of them 1)");
+    const wfst_compose_config c = cfg ? *cfg : wfst_compose_config{0, 1};
+    if (c.compose_filter > 6) throw Error("unknown compose_filter");
+    if (n == 0) return;
+    for (size_t i = 0; i < n1; ++i)
+      if (!fst1s[i]) throw Error("item " + std::to_string(i) + ": null FST in batch");
+    for (size_t i = 0; i < n2; ++i)
+      if (!fst2s[i]) throw Error("item " + std::to_string(i) + ": null FST in batch");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    compose_batch(ctx, fst1s, n1, fst2s, n2, c.connect != 0, c.compose_filter, outs, in_kernel);
+  });
+}
+wfst_status wfst_ctx_get_compose_batch_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel,
+                                                uint64_t* items_single, uint64_t* items_no_start, uint64_t* regrown_states,
+                                                uint64_t* regrown_arcs, uint64_t* regrown_hash) {
+  return get_counters(ctx, &wfst_ctx::compose_batch, {launches, items_in_kernel, items_single, items_no_start, regrown_states,
+                                                      regrown_arcs, regrown_hash});
+}
+
 // compose_with_config with matcher configs (compose_static.rs:166-266; rustfst-ffi/src/algorithms/compose.rs:199-211: an empty
 // allowed list is None); without any it is wfst_compose
 wfst_status wfst_compose_with_matchers(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2, const wfst_compose_config* cfg,

@@ -367,6 +367,12 @@ struct wfst_ctx {
     uint64_t launches = 0, items_in_kernel = 0, items_handed_back = 0, items_loop = 0, exact_items = 0, sigma_items = 0;
     uint64_t sigma_arcs = 0, refused_items = 0, max_level_width = 0;
   } sigma_batch;
+  // The last wfst_compose_batch call (compose.hip; wfst_ctx_get_compose_batch_counters): batch_driver.h's three counts, then
+  // the items without a start state on either side (they are among items_in_kernel), and per item and attempt the overflows
+  // that reopened an item with four times the capacities.  Zeroed when the call begins, behind every check that needs no launch.
+  struct ComposeBatchCounters : wfst::BatchStats {
+    uint64_t items_no_start = 0, regrown_states = 0, regrown_arcs = 0, regrown_hash = 0;
+  } compose_batch;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   // ... and what became of such scratch; never zeroed (counts since the context's creation)
@@ -612,6 +618,9 @@ void project_device(wfst_ctx* ctx, wfst_fst* f, bool project_output);
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter = 0);
 // ... the match mode its operands' property words leave (0 both, 1 input, 2 output), or the reference's error
 uint32_t decide_match_mode(uint64_t p1, uint64_t p2);
+// ... of n = max(n1, n2) pairs in one call (a list of one serves every item); on a throw every outs[i] is null
+void compose_batch(wfst_ctx* ctx, const wfst_fst* const* f1s, size_t n1, const wfst_fst* const* f2s, size_t n2, bool connect,
+                   uint32_t filter, wfst_fst** outs, uint8_t* in_kernel);
 void compose_shortest_path_batch(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n, const wfst_fst* t, bool connect,
                                  wfst_fst** outs, uint64_t* composed_arcs, uint32_t filter = 0);
 wfst_batch_job* compose_shortest_path_batch_begin(wfst_ctx* ctx, const wfst_fst* const* accs, size_t n, const wfst_fst* t,

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "batch_driver.h"
 #include "common.h"
 #include "compose_match.h"
 #include "fst_props.h"
@@ -441,19 +442,15 @@ __device__ bool relax_states(const Arena& ar, uint32_t lo, uint32_t hi, uint32_t
   return __any(changed);
 }
 
+// One composition problem on the calling wavefront: the body of compose_wave_kernel (second operand and capacities are the
+// launch's) and of compose_batch_kernel (both are the item's).  Always inlined: where an argument comes from is the
+// entry's business and costs the body nothing.  `res` is filled; the entry stores it.
 template <uint32_t FLAGS>
-__global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __restrict__ descs, FstView f2, Caps caps,
-                                                          char* __restrict__ arena_base, size_t arena_stride,
-                                                          Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
-                                                          uint32_t path_cap, uint32_t* __restrict__ path_cursor) {
-  const uint32_t p = blockIdx.x;
+__device__ __forceinline__ void compose_wave_problem(const FstView& f1, const FstView& f2, const uint32_t mode,
+                                                     const uint32_t filter, const Caps& caps, const Arena& ar, Result& res,
+                                                     wfst_tr* __restrict__ path_buf, const uint32_t path_cap,
+                                                     uint32_t* __restrict__ path_cursor) {
   const uint32_t lane = lane_id();
-  const ProblemDesc desc = descs[p];
-  const FstView f1 = desc.f1;
-  const uint32_t mode = desc.mode;
-  const uint32_t filter = desc.filter;
-  const Arena ar = carve_arena(arena_base + (size_t)p * arena_stride, caps);
-  Result res;
   res.status = ST_OK;
   res.n_states = res.n_arcs = res.t_states = res.t_arcs = 0;
   res.t_start = -1;
@@ -880,7 +877,58 @@ __global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __r
   }
   PT_MARK(6)  // trim / shortest-path epilogue
   PT_STORE(res)
-  if (lane == 0) results[p] = res;
+}
+
+template <uint32_t FLAGS>
+__global__ void __launch_bounds__(64) compose_wave_kernel(const ProblemDesc* __restrict__ descs, FstView f2, Caps caps,
+                                                          char* __restrict__ arena_base, size_t arena_stride,
+                                                          Result* __restrict__ results, wfst_tr* __restrict__ path_buf,
+                                                          uint32_t path_cap, uint32_t* __restrict__ path_cursor) {
+  const uint32_t p = blockIdx.x;
+  const ProblemDesc desc = descs[p];
+  const Arena ar = carve_arena(arena_base + (size_t)p * arena_stride, caps);
+  Result res;
+  compose_wave_problem<FLAGS>(desc.f1, f2, desc.mode, desc.filter, caps, ar, res, path_buf, path_cap, path_cursor);
+  if (lane_id() == 0) results[p] = res;
+}
+
+// wfst_compose_batch: one wavefront per item, every item with its own second operand, capacities and arena (carved on
+// the host from the launch's slab: a 20-state item beside a 4 000-state item pays for 20 states; skey and parent, which
+// only the fused shortest path uses, are not part of it).  The width hand-over is off (caps.W == 0): include/wfst.h.
+struct ComposeBatchCtl {  // one per item, at the head of the slab; read back once
+  uint32_t status;            // ST_*
+  uint32_t n_states, n_arcs;  // pre-trim
+  uint32_t t_states, t_arcs;  // after trim (== pre-trim when not trimming)
+  int32_t t_start;
+  uint32_t done;  // 1: the wave wrote this block (the host zeroes the blocks before the launch)
+  uint32_t pad;
+};
+struct ComposeBatchItem {
+  FstView f1, f2;
+  uint32_t mode, filter;
+  Caps caps;
+  Arena ar;
+  ComposeBatchCtl* ctl;
+};
+
+template <uint32_t FLAGS>
+__global__ void __launch_bounds__(64) compose_batch_kernel(const ComposeBatchItem* __restrict__ items) {
+  static_assert((FLAGS & FLAG_SP) == 0, "the arenas of a list have no shortest-path arrays");
+  const ComposeBatchItem it = items[blockIdx.x];
+  Result res;
+  compose_wave_problem<FLAGS>(it.f1, it.f2, it.mode, it.filter, it.caps, it.ar, res, nullptr, 0u, nullptr);
+  if (lane_id() == 0) {
+    ComposeBatchCtl c;
+    c.status = res.status;
+    c.n_states = res.n_states;
+    c.n_arcs = res.n_arcs;
+    c.t_states = res.t_states;
+    c.t_arcs = res.t_arcs;
+    c.t_start = res.t_start;
+    c.done = 1u;
+    c.pad = 0u;
+    *it.ctl = c;
+  }
 }
 
 
@@ -1938,6 +1986,155 @@ wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool co
       return compose_wide(ctx, f1, f2, mode, filter, connect, out_props, est_s);
     }
   }
+}
+
+// ================================================================ list form (wfst_compose_batch)
+namespace {
+
+constexpr size_t COMPOSE_BATCH_MAX_SLAB = (size_t)8 << 30;  // all slices of one launch together; beyond: KO before that launch
+
+// one item's arena out of the slab: carve_arena's arrays without skey / parent (the fused shortest path's); ar == nullptr
+// only measures
+size_t carve_compose_slice(Slab s, const Caps& c, Arena* ar) {
+  Arena a{};
+  a.tuples = s.take<uint64_t>(c.S);
+  a.hkeys = s.take<uint64_t>(c.H);
+  a.arcs = s.take<wfst_tr>(c.A);
+  a.t_arcs = s.take<wfst_tr>(c.A);
+  a.hvals = s.take<uint32_t>(c.H);
+  a.off = s.take<uint32_t>((size_t)c.S + 1);
+  a.t_off = s.take<uint32_t>((size_t)c.S + 1);
+  a.fin = s.take<float>(c.S);
+  a.t_fin = s.take<float>(c.S);
+  a.aux = s.take<uint32_t>(c.S);
+  a.aux2 = s.take<uint32_t>(c.S);
+  a.lvl = s.take<uint32_t>((size_t)c.S + 1);
+  if (ar) *ar = a;
+  return s.at();
+}
+
+}  // namespace
+
+// The routing rule is stated in include/wfst.h; the host loop is batch_driver.h's.
+void compose_batch(wfst_ctx* ctx, const wfst_fst* const* f1s, size_t n1, const wfst_fst* const* f2s, size_t n2, bool connect,
+                   uint32_t filter, wfst_fst** outs, uint8_t* in_kernel) {
+  wfst_ctx::ComposeBatchCounters& stats = ctx->compose_batch;
+  const size_t n = std::max(n1, n2);
+  check_items_owned(ctx, f1s, n1, "compose_batch");
+  check_items_owned(ctx, f2s, n2, "compose_batch");
+  auto first = [&](size_t i) { return f1s[n1 == 1 ? 0 : i]; };
+  auto second = [&](size_t i) { return f2s[n2 == 1 ? 0 : i]; };
+  enum : uint8_t { NO_START, KERNEL, SINGLE, WIDE };
+  struct Item {
+    uint8_t kind = NO_START;
+    uint32_t mode = 0;
+    uint64_t out_props = 0;
+    uint64_t est_s = 0, est_a = 0;  // the next attempt's estimate (compose()'s sequence)
+    ComposeBatchCtl ctl{};          // of the attempt that finished
+    Arena ar{};
+  };
+  std::vector<Item> items(n);
+  // the single call's own errors, lowest index first, before anything is launched
+  size_t live = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const wfst_fst *f1 = first(i), *f2 = second(i);
+    try {
+      if (f1->n_states > TUPLE_S1_MASK) throw Error("compose: the 1st FST has more than 2^30 states");
+      items[i].mode = decide_match_mode(f1->props, f2->props);
+    } catch (const std::exception& e) {
+      throw Error("item " + std::to_string(i) + ": " + e.what());
+    }
+    const bool has_start = f1->start >= 0 && f2->start >= 0;
+    items[i].out_props = props::compose_result(f1->props, f2->props, connect, has_start);
+    if (has_start) {
+      items[i].kind = KERNEL;
+      live += 1;
+    }
+  }
+  const bool arena_min = arena_min_knob("WFST_COMPOSE_BATCH_ARENA");
+  stats = {};  // (every refusal that needs no launch is behind us: such a call leaves the last call's counters alone)
+  std::vector<size_t> open;
+  for (size_t i = 0; i < n; ++i) {
+    Item& it = items[i];
+    if (it.kind != KERNEL) continue;
+    if (live == 1) {  // the single call, limits and all
+      it.kind = SINGLE;
+      continue;
+    }
+    const wfst_fst *f1 = first(i), *f2 = second(i);
+    it.est_s = arena_min ? 64 : 4ull * std::max<uint64_t>(std::min(f1->n_states, f2->n_states), 64) + 1024;
+    it.est_a = arena_min ? 128 : 4ull * it.est_s;
+    ensure_device(const_cast<wfst_fst*>(f1));
+    ensure_device(const_cast<wfst_fst*>(f2));
+    if (it.est_s > WIDE_COMPOSE_STATES) {  // (k = 0: min(n_states1, n_states2) > 3840)
+      it.kind = WIDE;
+      continue;
+    }
+    open.push_back(i);
+  }
+  hipStream_t st = ctx->stream;
+  auto carve = [&](size_t i, Slab s, ComposeBatchItem* out) {
+    const Caps caps = make_caps(items[i].est_s, items[i].est_a);  // (W = 0: no width hand-over in a list)
+    Arena ar{};
+    const size_t end = carve_compose_slice(s, caps, &ar);
+    if (out) {
+      out->f1 = view_of(first(i));
+      out->f2 = view_of(second(i));
+      out->mode = items[i].mode;
+      out->filter = filter;
+      out->caps = caps;
+      out->ar = ar;
+    }
+    return end;
+  };
+  auto launch = [&](const ComposeBatchItem* d_items, uint32_t m) {
+    if (connect)
+      compose_batch_kernel<FLAG_TRIM><<<m, 64, 0, st>>>(d_items);
+    else
+      compose_batch_kernel<0><<<m, 64, 0, st>>>(d_items);
+  };
+  auto classify = [&](size_t i, const ComposeBatchCtl& c, const ComposeBatchItem& sent) {
+    Item& it = items[i];
+    if (c.done != 1u || c.status > ST_OVERFLOW_HASH || c.n_states > sent.caps.S || c.n_arcs > sent.caps.A ||
+        c.t_states > c.n_states || c.t_arcs > c.n_arcs)
+      throw Error("compose_batch: internal error: the kernel left item " + std::to_string(i) + " with status " +
+                  std::to_string(c.status));
+    if (c.status == ST_OK) {
+      it.ctl = c;
+      it.ar = sent.ar;
+      return BatchExit::FINISHED;
+    }
+    (c.status == ST_OVERFLOW_STATES ? stats.regrown_states : c.status == ST_OVERFLOW_ARCS ? stats.regrown_arcs : stats.regrown_hash) += 1;
+    it.est_s *= 4;
+    it.est_a *= 4;
+    if (it.est_s > WIDE_COMPOSE_STATES) {  // not a job for one wave: the wide driver, with this estimate
+      it.kind = WIDE;
+      return BatchExit::SINGLE;
+    }
+    return BatchExit::GREW;
+  };
+  const auto slabs = batch_launch_loop<ComposeBatchItem, ComposeBatchCtl>(
+      ctx, stats, {"compose_batch", BATCH_MAX_LAUNCHES, "an arena", COMPOSE_BATCH_MAX_SLAB, "launch"}, std::move(open), carve, nullptr,
+      launch, classify);
+  auto outcome = [&](size_t i) {
+    const Item& it = items[i];
+    if (it.kind == SINGLE || it.kind == WIDE) return BatchOutcome::single();
+    if (it.kind == NO_START) {  // compute_start -> None: the empty FST (lazy_fst.rs:229-232)
+      HostCsr h;
+      h.offsets.push_back(0);
+      stats.items_no_start += 1;
+      return BatchOutcome::handle(make_host_fst(ctx, 0, -1, it.out_props, std::move(h)));
+    }
+    const ComposeBatchCtl& c = it.ctl;
+    if (connect) return BatchOutcome::adopt({c.t_states, c.t_arcs, (int64_t)c.t_start, it.out_props, it.ar.t_off, it.ar.t_arcs, it.ar.t_fin});
+    return BatchOutcome::adopt({c.n_states, c.n_arcs, c.n_states ? 0 : -1, it.out_props, it.ar.off, it.ar.arcs, it.ar.fin});
+  };
+  auto single = [&](size_t i) {
+    const Item& it = items[i];
+    if (it.kind == SINGLE) return compose(ctx, first(i), second(i), connect, filter);
+    return compose_wide(ctx, first(i), second(i), it.mode, filter, connect, it.out_props, it.est_s);
+  };
+  batch_finish(ctx, stats, n, outs, in_kernel, outcome, single);
 }
 
 }  // namespace wfst

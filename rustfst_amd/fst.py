@@ -980,6 +980,42 @@ def top_sort_batch_stats(ctx: Optional[Context] = None) -> dict:
     return {k: int(v.value) for k, v in zip(_lib.TOP_SORT_BATCH_COUNTERS, vals)}
 
 
+def compose_batch(fst1s, fst2s, config: Optional["ComposeConfig"] = None, ctx: Optional[Context] = None,
+                  return_in_kernel: bool = False):
+    """[a.compose(b, config) for a, b in zip(fst1s, fst2s)] as ONE call (wfst_compose_batch): one wavefront per pair, each
+    with its own second operand and its own arena, results bit for bit the single call's.  Either side may be a single
+    DeviceFst (or a list of one), which then serves every item: one grammar against n lattices, one lattice against n
+    grammars.  return_in_kernel: also the uint8 array that says which items the batch kernel finished (0: the only item
+    with start states, which is the single call, or an item whose estimate passed 16384 composed states and went to the
+    wide driver).  A config with matcher configs is refused; an item's own error raises WfstError with "item <i>: " in
+    front."""
+    if isinstance(fst1s, DeviceFst):
+        fst1s = [fst1s]
+    if isinstance(fst2s, DeviceFst):
+        fst2s = [fst2s]
+    cfg = config._c() if config is not None else None
+    n1, n2 = len(fst1s), len(fst2s)
+    n = max(n1, n2)
+    if ctx is None:
+        ctx = _first_ctx(fst1s) if n1 else (_first_ctx(fst2s) if n2 else default_context())
+    outs = (C.c_void_p * max(n, 1))()
+    flags = np.zeros(n, np.uint8)
+    check(_lib.lib().wfst_compose_batch(ctx._h, _handles(fst1s), n1, _handles(fst2s), n2, cfg, outs, flags.ctypes.data),
+          "wfst_compose_batch")
+    res = [DeviceFst(C.c_void_p(outs[i]), ctx) for i in range(n)]
+    return (res, flags) if return_in_kernel else res
+
+
+def compose_batch_stats(ctx: Optional[Context] = None) -> dict:
+    """The last compose_batch call of ctx that passed its argument checks (wfst_ctx_get_compose_batch_counters): launches,
+    items_in_kernel, items_single, items_no_start, regrown_states, regrown_arcs, regrown_hash."""
+    ctx = ctx or default_context()
+    vals = [C.c_uint64() for _ in _lib.COMPOSE_BATCH_COUNTERS]
+    check(_lib.lib().wfst_ctx_get_compose_batch_counters(ctx._h, *[C.byref(v) for v in vals]),
+          "wfst_ctx_get_compose_batch_counters")
+    return {k: int(v.value) for k, v in zip(_lib.COMPOSE_BATCH_COUNTERS, vals)}
+
+
 def optimize_batch(fsts: Sequence[DeviceFst], ctx: Optional[Context] = None, return_in_kernel: bool = False):
     """[f.optimize() for f in fsts] as ONE call (wfst_optimize_batch): rm_epsilon_batch over the items whose word lacks
     NO_EPSILONS, tr_sum_batch over all, determinize_batch and minimize_batch over the acceptors; a transducer takes the
