@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats, wfst_compose_batch, wfst_ctx_get_compose_batch_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats, wfst_compose_batch, wfst_ctx_get_compose_batch_counters, wfst_fst_invert, wfst_isomorphic, wfst_ctx_get_isomorphic_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -708,6 +708,71 @@ wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx);
  *      project_properties (fst_properties/mutate_properties.rs:365-445).  The usual recipe around the hot path is
  *      compose -> project -> shortest_path (rustfst/src/lib.rs:70-82). ---- */
 wfst_status wfst_fst_project(wfst_ctx* ctx, wfst_fst* fst, int project_output);
+
+/* ---- invert: rustfst::algorithms::invert (rustfst/src/algorithms/inversion.rs:32-48), in place on the device-resident
+ *      arcs like wfst_fst_project: every arc's ilabel and olabel change places (one grid-stride kernel), and the property
+ *      word becomes invert_properties(word) (fst_properties/mutate_properties.rs:302-363): the tape-neutral pairs stay,
+ *      every input-side pair (deterministic, epsilons, label-sorted) changes places with its output-side pair — so a
+ *      handle that wfst_fst_tr_sort sorted on one tape is known to be sorted on the other afterwards.  Everything the
+ *      handle derives from the labels follows: the per-state epsilon facts are derived again, the host mirror and the
+ *      cached host reverse are dropped, the input-epsilon answer and the string shape are asked again.  An FST without
+ *      arcs only gets the new word.  Inverting twice restores arrays and word bit for bit.
+ *      KO: NULL pointers ("null pointer"); a handle of another device or context ("invert: the FST lives on another
+ *      device", "invert: the FST belongs to another context"). ---- */
+wfst_status wfst_fst_invert(wfst_ctx* ctx, wfst_fst* fst);
+
+/* ---- isomorphic: rustfst::algorithms::isomorphic_with_config (rustfst/src/algorithms/isomorphic.rs:134-158, 200-212)
+ *      for two handles of ctx.  cfg == NULL: IsomorphicConfig::default(), delta = KDELTA = 1/1024.  OK with
+ *      *is_isomorphic = 0 or 1, or KO with the reference's message "Isomorphic: Non-determinism as an unweighted
+ *      automaton. state1 = {s1} state2 = {s2}".  Both operands, their cached derived data and their property words are
+ *      left as they are.
+ *      The reference's semantics, reproduced and not improved:
+ *        - both operands without a start state: 1; exactly one without: 0 (both before any GPU work);
+ *        - no comparison of state counts and no injectivity check: only states of fst1 are recorded as paired, so two
+ *          states of fst1 may pair with one state of fst2, the call is NOT symmetric in its operands, and states the
+ *          search does not reach are never looked at;
+ *        - per pair popped from the FIFO queue, in this order: final weights (none / none equal, both present by
+ *          approx_equal), arc counts, then both arc lists sorted by tr_compare = (ilabel, olabel, weight, nextstate) and
+ *          walked index by index: ilabel, olabel, approx_equal of the weights, pair_state(next1, next2) — the first
+ *          pairing of a state of fst1 wins — and only after a successful pairing the non-determinism mark, set when arc i
+ *          and arc i - 1 of fst1 agree in labels and approx-equal weight;
+ *        - approx_equal(a, b) is |a - b| <= delta with IEEE semantics: two +inf arc weights are NOT approx-equal, so an
+ *          FST with an infinite arc weight is not isomorphic to itself;
+ *        - the sort compares weights in OrderedFloat's total order on the exact bits (-0.0 == +0.0, NaN greatest and
+ *          equal to itself); only the walk compares approximately;
+ *        - the first failure in queue order gives the KO above, naming that pair, iff a mark was set strictly before
+ *          it in sequential order, otherwise 0.
+ *      Final weights are what the handle stores: +inf is "not final", as everywhere in this library, so the reference's
+ *      (Some(inf), Some(inf)) case (two final states with weight zero(), not approx-equal) cannot be expressed: such
+ *      states count as not final on both sides, which is equal.
+ *      The search runs level by level over two temporary copies of the arcs in tr_compare order: every
+ *      arc slot of a level has its position in the reference's sequential order, pairings, marks and failures are
+ *      decided by atomic minima on positions, and the next level is written in that order.  Two regimes: consecutive
+ *      levels of at most WFST_ISOMORPHIC_NARROW_PAIRS pairs and WFST_ISOMORPHIC_NARROW_EVENTS arc slots run inside one
+ *      launch of one workgroup; a larger level takes one device-wide launch per phase and one read-back.  A pair whose
+ *      fst1 state has 64 arcs or more is walked by a whole wave in both.  WFST_ISOMORPHIC_PATH=auto|narrow|wide (tests)
+ *      pins a regime.  Every route gives the same verdict and the same message.
+ *      Scratch comes from the context's pool and goes back at the end, also on KO: 16 bytes per arc of each operand,
+ *      32 bytes per state and 8 bytes per arc of fst1 (pairings, two queues, slot offsets and counts, one level's flags
+ *      and their scan).  A refused allocation is an ordinary KO and the context works afterwards.  An operand with
+ *      2^32 - 2 arcs or more is KO (positions are 32-bit).
+ *      KO before any GPU work, in this order: NULL pointers ("null pointer"); a handle of another device or context
+ *      ("isomorphic: fst1 lives on another device", "isomorphic: fst2 belongs to another context"); a value of
+ *      WFST_ISOMORPHIC_PATH other than auto, narrow or wide. ---- */
+#define WFST_ISOMORPHIC_NARROW_PAIRS 256
+#define WFST_ISOMORPHIC_NARROW_EVENTS 2048
+typedef struct { float delta; } wfst_isomorphic_config;   /* NULL = IsomorphicConfig::default() = KDELTA */
+wfst_status wfst_isomorphic(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2, const wfst_isomorphic_config* cfg,
+                            int* is_isomorphic);
+/* the last wfst_isomorphic call of ctx (reset when a call has passed its checks): levels of the search that ran, the
+ *      failing one included; launches of the one-workgroup kernel and of the device-wide phase kernels (four per wide
+ *      level); levels that ran inside one-workgroup launches; the widest level in pairs; pairs and arc slots of the
+ *      levels that ran; pairs that a whole wave walked; states of both operands with more than 256 arcs, which the
+ *      segmented radix passes sorted; non-determinism marks made (those of the failing level behind the failure
+ *      included).  All 0 for a call decided by the start states.  Any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_isomorphic_counters(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
+                                             uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* pairs, uint64_t* events,
+                                             uint64_t* wave_pairs, uint64_t* big_states_sorted, uint64_t* nondet_marks);
 
 /* ---- look-ahead composition: the configuration rustfst-cli/src/cmds/compose.rs:77-181 (ComposeType::LookAhead) and
  *      rustfst/src/tests_openfst/algorithms/compose.rs:118-254 build by hand — there is no single reference entry point:

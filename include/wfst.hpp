@@ -12,6 +12,8 @@
 //   ExpandedFst::num_states, Fst::properties                     Option<T> -> std::optional<T>
 //   tr_sort(&mut fst, ILabelCompare{} | OLabelCompare{})         tr_sort(fst, ILabelCompare{} | OLabelCompare{})
 //   project(&mut fst, ProjectType::ProjectInput)                 project(fst, ProjectType::ProjectInput)
+//   invert(&mut fst)                                             invert(fst)                                       inversion.rs:32-48
+//   isomorphic(&a, &b) / isomorphic_with_config(&a, &b, config)  isomorphic(a, b) / isomorphic_with_config(a, b, config)  isomorphic.rs:184-212
 //   connect(&mut fst) / rm_epsilon(&mut fst)                     connect(fst) / rm_epsilon(fst)
 //   shortest_distance(&fst, reverse) -> Vec<W>                   shortest_distance(fst, reverse) -> std::vector<float>
 //   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
@@ -295,6 +297,31 @@ inline void project(VectorFst& fst, ProjectType project_type) {
   check(wfst_fst_project(Context::current().get(), a.h, project_type == ProjectType::ProjectOutput ? 1 : 0));
   fst = detail::download(a);
 }
+
+// invert (algorithms/inversion.rs:32-48): in place, like the reference
+inline void invert(VectorFst& fst) {
+  detail::DeviceFst a;
+  detail::upload(fst, a);
+  check(wfst_fst_invert(Context::current().get(), a.h));
+  fst = detail::download(a);
+}
+
+// isomorphic / isomorphic_with_config (algorithms/isomorphic.rs:162-212): the reference's verdict, its error thrown
+struct IsomorphicConfig {  // isomorphic.rs:162-176
+  float delta = 1.0f / 1024.0f;  // KDELTA
+  IsomorphicConfig() = default;
+  explicit IsomorphicConfig(float d) : delta(d) {}
+};
+inline bool isomorphic_with_config(const VectorFst& fst_1, const VectorFst& fst_2, const IsomorphicConfig& config) {
+  detail::DeviceFst a, b;
+  detail::upload(fst_1, a);
+  detail::upload(fst_2, b);
+  const wfst_isomorphic_config cfg{config.delta};
+  int res = 0;
+  check(wfst_isomorphic(Context::current().get(), a.h, b.h, &cfg, &res));
+  return res != 0;
+}
+inline bool isomorphic(const VectorFst& fst_1, const VectorFst& fst_2) { return isomorphic_with_config(fst_1, fst_2, IsomorphicConfig{}); }
 
 // connect (algorithms/connect.rs:51-66) and rm_epsilon (algorithms/rm_epsilon/rm_epsilon_static.rs:50-163): in place
 inline void connect(VectorFst& fst) {

@@ -44,6 +44,10 @@ class MinimizeConfig(C.Structure):
     _fields_ = [("delta", C.c_float), ("allow_nondet", C.c_uint32)]
 
 
+class IsomorphicConfig(C.Structure):  # wfst_isomorphic_config
+    _fields_ = [("delta", C.c_float)]
+
+
 TIES_UNKNOWN = (1 << 64) - 1  # WFST_TIES_UNKNOWN
 
 
@@ -113,6 +117,10 @@ COMPOSE_SIGMA_COUNTERS = ("levels", "states", "arcs", "require1_states", "requir
 SIGMA_BATCH_COUNTERS = ("launches", "items_in_kernel", "items_handed_back", "items_loop", "exact_items", "sigma_items", "sigma_arcs",
                         "refused_items", "max_level_width")
 
+# wfst_ctx_get_isomorphic_counters: the same, for the level search of isomorphic
+ISOMORPHIC_COUNTERS = ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "pairs", "events",
+                       "wave_pairs", "big_states_sorted", "nondet_marks")
+
 # wfst_ctx_get_string_pair_counts: the same, for the pair levels of the string kernel
 STRING_PAIR_COUNTS = ("pair_levels", "pair_splits")
 
@@ -127,6 +135,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_ctx_get_sigma_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(SIGMA_BATCH_COUNTERS)),
     ("wfst_ctx_get_top_sort_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(TOP_SORT_BATCH_COUNTERS)),
     ("wfst_ctx_get_compose_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_BATCH_COUNTERS)),
+    ("wfst_ctx_get_isomorphic_counters", C.c_int, [_vp] + [_P(_u64)] * len(ISOMORPHIC_COUNTERS)),
     ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_ctx_get_string_placement", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PLACEMENT)),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
@@ -159,6 +168,8 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_ctx_get_bounded_stats", C.c_int, [_vp, _P(_u64), _P(_u64), _P(C.c_char_p)]),
     ("wfst_ctx_trim_pool", C.c_int, [_vp]),
     ("wfst_fst_project", C.c_int, [_vp, _vp, C.c_int]),
+    ("wfst_fst_invert", C.c_int, [_vp, _vp]),
+    ("wfst_isomorphic", C.c_int, [_vp, _vp, _vp, _P(IsomorphicConfig), _P(C.c_int)]),
     ("wfst_lookahead_create", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_lookahead_relabel", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_lookahead_fst1", C.c_int, [_vp, _P(_vp)]),

@@ -1083,6 +1083,29 @@ wfst_status wfst_fst_project(wfst_ctx* ctx, wfst_fst* fst, int project_output) {
   });
 }
 
+// invert (inversion.rs:32-48) in place, and isomorphic_with_config (isomorphic.rs:134-158, 200-212)
+wfst_status wfst_fst_invert(wfst_ctx* ctx, wfst_fst* fst) {
+  return wrap([&] {
+    if (!ctx || !fst) throw Error("null pointer");
+    invert_device(ctx, fst);
+  });
+}
+wfst_status wfst_isomorphic(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst* fst2, const wfst_isomorphic_config* cfg,
+                            int* is_isomorphic) {
+  return wrap([&] {
+    if (!ctx || !fst1 || !fst2 || !is_isomorphic) throw Error("null pointer");
+    *is_isomorphic = 0;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *is_isomorphic = isomorphic_fsts(ctx, fst1, fst2, cfg ? cfg->delta : KDELTA) ? 1 : 0;
+  });
+}
+wfst_status wfst_ctx_get_isomorphic_counters(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
+                                             uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* pairs, uint64_t* events,
+                                             uint64_t* wave_pairs, uint64_t* big_states_sorted, uint64_t* nondet_marks) {
+  return get_counters(ctx, &wfst_ctx::isomorphic, {levels, narrow_launches, wide_launches, narrow_levels, max_level_width, pairs,
+                                                   events, wave_pairs, big_states_sorted, nondet_marks});
+}
+
 wfst_status wfst_lookahead_create(wfst_ctx* ctx, const wfst_fst* fst1, wfst_lookahead** out) {
   return wrap([&] {
     if (!ctx || !fst1 || !out) throw Error("null pointer");

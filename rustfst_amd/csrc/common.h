@@ -373,6 +373,14 @@ struct wfst_ctx {
   struct ComposeBatchCounters : wfst::BatchStats {
     uint64_t items_no_start = 0, regrown_states = 0, regrown_arcs = 0, regrown_hash = 0;
   } compose_batch;
+  // The last wfst_isomorphic call (isomorphic.hip; wfst_ctx_get_isomorphic_counters): levels of the search that ran, launches of
+  // the one-workgroup kernel and of the device-wide phase kernels, levels the former ran, the widest level, pairs and arc
+  // slots of the levels that ran, pairs walked by a wave, states of both operands sorted by the radix route, mark atomics.
+  // Zeroed when the call has passed its checks.
+  struct IsomorphicCounters {
+    uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, pairs = 0, events = 0;
+    uint64_t wave_pairs = 0, big_states_sorted = 0, nondet_marks = 0;
+  } isomorphic;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   // ... and what became of such scratch; never zeroed (counts since the context's creation)
@@ -614,6 +622,9 @@ bool detect_string(uint32_t n_states, int64_t start, const uint32_t* offsets, co
 void tr_sort_device(wfst_ctx* ctx, wfst_fst* f, bool ilabel_cmp);
 // fst_store.hip
 void project_device(wfst_ctx* ctx, wfst_fst* f, bool project_output);
+void invert_device(wfst_ctx* ctx, wfst_fst* f);
+// isomorphic.hip: isomorphic_with_config for two handles of ctx (both left as they are); throws the reference's error
+bool isomorphic_fsts(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, float delta);
 // compose.hip
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter = 0);
 // ... the match mode its operands' property words leave (0 both, 1 input, 2 output), or the reference's error

@@ -261,6 +261,27 @@ inline uint64_t project(uint64_t in, bool project_output) {
   return (in & ~ALL) | out;
 }
 
+// invert_properties (fst_properties/mutate_properties.rs:302-363) as applied by invert() with the all_properties() mask
+// (algorithms/inversion.rs:44-47): the tape-neutral pairs stay, every input-side pair changes places with its output-side one
+inline uint64_t invert(uint64_t in) {
+  uint64_t out = (ACCEPTOR | NOT_ACCEPTOR | EPSILONS | NO_EPSILONS | WEIGHTED | UNWEIGHTED | WEIGHTED_CYCLES | UNWEIGHTED_CYCLES |
+                  CYCLIC | ACYCLIC | INITIAL_CYCLIC | INITIAL_ACYCLIC | TOP_SORTED | NOT_TOP_SORTED | ACCESSIBLE | NOT_ACCESSIBLE |
+                  COACCESSIBLE | NOT_COACCESSIBLE | STRING | NOT_STRING) & in;
+  if (in & I_DETERMINISTIC) out |= O_DETERMINISTIC;
+  if (in & NOT_I_DETERMINISTIC) out |= NOT_O_DETERMINISTIC;
+  if (in & O_DETERMINISTIC) out |= I_DETERMINISTIC;
+  if (in & NOT_O_DETERMINISTIC) out |= NOT_I_DETERMINISTIC;
+  if (in & I_EPSILONS) out |= O_EPSILONS;
+  if (in & NO_I_EPSILONS) out |= NO_O_EPSILONS;
+  if (in & O_EPSILONS) out |= I_EPSILONS;
+  if (in & NO_O_EPSILONS) out |= NO_I_EPSILONS;
+  if (in & I_LABEL_SORTED) out |= O_LABEL_SORTED;
+  if (in & NOT_I_LABEL_SORTED) out |= NOT_O_LABEL_SORTED;
+  if (in & O_LABEL_SORTED) out |= I_LABEL_SORTED;
+  if (in & NOT_O_LABEL_SORTED) out |= NOT_I_LABEL_SORTED;
+  return (in & ~ALL) | out;
+}
+
 // ---- reweight() / remove_weight() bookkeeping (algorithms/reweight.rs, algorithms/push.rs:150-170)
 // keep_only_relevant_properties (trs_iter_mut.rs:293-305): set_arc_properties() is empty (properties.rs:278-280), so every
 // set_weight_unchecked keeps the label / epsilon bits and WEIGHTED / UNWEIGHTED only

@@ -610,6 +610,49 @@ void project_device(wfst_ctx* ctx, wfst_fst* f, bool project_output) {
   f->props = props::project(f->props, project_output);
 }
 
+namespace {
+// one lane per arc: the 16-byte arc comes back with its two labels exchanged
+__global__ void invert_kernel(wfst_tr* __restrict__ arcs, uint64_t n_arcs) {
+  uint4* __restrict__ a = reinterpret_cast<uint4*>(arcs);
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_arcs; k += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 v = a[k];
+    a[k] = make_uint4(v.y, v.x, v.z, v.w);
+  }
+}
+}  // namespace
+
+// invert (algorithms/inversion.rs:32-48) in place on the device-resident arcs: every arc's labels exchanged, then what
+// project_device derives again for the same reason (the labels changed, the graph did not), the property word from
+// invert_properties.  What the word says about the sorted tape (tr_sort_device's only record of it) moves with the tapes.
+void invert_device(wfst_ctx* ctx, wfst_fst* f) {
+  if (f->device != ctx->device) throw Error("invert: the FST lives on another device");
+  if (f->ctx != ctx) throw Error("invert: the FST belongs to another context");
+  HIP_CHECK(hipSetDevice(ctx->device));
+  if (f->n_arcs) {
+    ensure_device(f);
+    const int blocks = (int)std::min<uint64_t>((f->n_arcs + 255) / 256, (uint64_t)ctx->n_cus * 16);
+    invert_kernel<<<blocks, 256, 0, ctx->stream>>>(const_cast<wfst_tr*>(f->dev.arcs), f->n_arcs);
+    DBuf<uint32_t> err(*ctx->pool, 1);
+    HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(uint32_t), ctx->stream));
+    derive_noeps_kernel<<<(f->n_states + 255) / 256, 256, 0, ctx->stream>>>(f->dev.offsets, f->dev.arcs, f->dev.finals,
+                                                                             const_cast<uint32_t*>(f->dev.noeps),
+                                                                             const_cast<uint4*>(f->dev.srec), f->n_states, err.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (f->has_host) {  // the host mirror described the old labels
+      f->host = HostCsr{};
+      f->has_host = false;
+    }
+    f->rev_host.reset();  // reverse() carries labels
+    f->ieps_state = 0;
+    if (f->is_string) {  // (ilabel == olabel on every arc of a string: the same answer, asked as an upload would)
+      ensure_host(f);
+      f->is_string = detect_string(f->n_states, f->start, f->host.offsets.data(), f->host.arcs.data(), f->host.finals.data());
+    }
+  }
+  f->props = props::invert(f->props);
+}
+
 void ensure_device(wfst_fst* f) {
   if (f->has_dev) return;
   if (f->path_form) ensure_host(f);

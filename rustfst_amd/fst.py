@@ -181,6 +181,17 @@ class Context:
         at least two states (states_compared), states a whole wave took (wave_states) and the CYCLIC exit (cyclic)."""
         return _counters("top_sort", self)
 
+    def isomorphic_stats(self) -> dict:
+        """Which route this context's last isomorphic call took (wfst_ctx_get_isomorphic_counters): levels of the search that
+        ran, launches of the one-workgroup and of the device-wide phase kernels (narrow_launches, wide_launches: four per
+        wide level), levels inside one-workgroup launches (narrow_levels), the widest level in pairs (max_level_width),
+        pairs and arc slots of the levels that ran (pairs, events), pairs a whole wave walked (wave_pairs), states of both
+        operands sorted by the radix route (big_states_sorted) and non-determinism marks made (nondet_marks)."""
+        vals = [C.c_uint64() for _ in _lib.ISOMORPHIC_COUNTERS]
+        check(_lib.lib().wfst_ctx_get_isomorphic_counters(self._h, *[C.byref(v) for v in vals]),
+              "wfst_ctx_get_isomorphic_counters")
+        return {k: int(v.value) for k, v in zip(_lib.ISOMORPHIC_COUNTERS, vals)}
+
     def lookahead_stats(self) -> dict:
         """Which route answered the compositions of this context's last LookAhead.compose / compose_batch call
         (wfst_ctx_get_lookahead_stats): items and those without a start state, compositions the single-wave kernel finished
@@ -470,6 +481,21 @@ class DeviceFst:
         out = proj_type is not None and ProjectType(proj_type) == ProjectType.PROJECT_OUTPUT
         check(_lib.lib().wfst_fst_project(self.ctx._h, self._h, 1 if out else 0), "Error during projection")
         return self
+
+    def invert(self) -> "DeviceFst":
+        """In-place inversion on the device (algorithms/inversion.rs:32-48): every arc's input and output label change
+        places, the property word follows invert_properties.  Returns this FST."""
+        check(_lib.lib().wfst_fst_invert(self.ctx._h, self._h), "Error during invert")
+        return self
+
+    def isomorphic(self, other: "DeviceFst", delta: Optional[float] = None) -> bool:
+        """algorithms::isomorphic_with_config (isomorphic.rs:134-158, 200-212) of this FST and `other` on the device; delta
+        None: IsomorphicConfig::default() (KDELTA).  The reference's verdict, not symmetric in the operands; raises WfstError
+        with the reference's message where it reports non-determinism.  Both FSTs are left as they are."""
+        cfg = None if delta is None else C.byref(_lib.IsomorphicConfig(float(delta)))
+        res = C.c_int()
+        check(_lib.lib().wfst_isomorphic(self.ctx._h, self._h, other._h, cfg, C.byref(res)), "Error checking isomorphic FSTs")
+        return bool(res.value)
 
     def tr_sort(self, ilabel_cmp: bool = True) -> "DeviceFst":
         """In-place stable per-state arc sort on the device by ilabel (ILabelCompare) or olabel
@@ -1474,6 +1500,20 @@ class VectorFst:
         self._dev = None
         return self
 
+    def invert(self) -> "VectorFst":
+        """rustfst-python vector_fst.py:730-740 `invert` (algorithms/inversion.py): inverts THIS FST in place and returns
+        it; the device copy is inverted and becomes this object's host data, like project."""
+        inverted = self.to_device().invert().to_vector_fst()
+        self._p, inverted._p = inverted._p, self._p
+        self._dev = None
+        return self
+
+    def isomorphic(self, other: "VectorFst") -> bool:
+        """rustfst-python vector_fst.py:718-728 `isomorphic` (algorithms/isomorphic.py): both FSTs are uploaded and compared
+        on the device."""
+        dev = self.to_device()
+        return dev.isomorphic(other.to_device(dev.ctx))
+
 
 # ------------------------------------------------------------------ free functions
 def compose(fst: VectorFst, fst2: VectorFst) -> VectorFst:
@@ -1488,6 +1528,16 @@ def compose_with_config(fst: VectorFst, fst2: VectorFst, config: ComposeConfig) 
 def project(fst: VectorFst, proj_type: ProjectType = ProjectType.PROJECT_INPUT) -> VectorFst:
     """rustfst-python/rustfst/algorithms/project.py:27-50."""
     return fst.project(proj_type)
+
+
+def invert(fst: Union[VectorFst, DeviceFst]) -> Union[VectorFst, DeviceFst]:
+    """rustfst-python/rustfst/algorithms/inversion.py `invert`: in place, returns fst."""
+    return fst.invert()
+
+
+def isomorphic(fst: Union[VectorFst, DeviceFst], other_fst: Union[VectorFst, DeviceFst]) -> bool:
+    """rustfst-python/rustfst/algorithms/isomorphic.py `isomorphic`."""
+    return fst.isomorphic(other_fst)
 
 
 def shortestpath(fst: VectorFst) -> VectorFst:
