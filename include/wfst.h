@@ -698,6 +698,22 @@ wfst_status wfst_ctx_get_rearm_stats(wfst_ctx* ctx, uint64_t* armed, uint64_t* a
  *      "" before the first; not to be freed).  Any pointer after ctx may be NULL.  WFST_SSSP_BOUNDED=0 switches it off;
  *      wfst_shortest_distance, n-best queries, reweight and push_weights never use it. ---- */
 wfst_status wfst_ctx_get_bounded_stats(wfst_ctx* ctx, uint64_t* stops, uint64_t* full_solves, const char** last_reason);
+/* ---- the solo query: once three queries in a row on ctx have been ended by the bounded head (or by this
+ *      route) and the cleaned scratch of the last is parked on ctx for the same graph structure, first band and knobs, the next
+ *      such query is ONE launch of one workgroup that searches, finds the path, writes it to pinned memory and puts the keys it
+ *      wrote back, so that the parked scratch is armed as before.  A launch that cannot answer (a best total beyond the first
+ *      band, a level wider than its workgroup, a full log of written keys) gives the query up: it is asked again by the
+ *      ordinary route, and the next queries are ordinary until three stop in a row again.  Results and the other counters
+ *      (wfst_stats.sweeps == 1, stops, armed, adopted, tied_choices) are those of the bounded stop it replaces.  Counters of
+ *      ctx since its creation: launches (attempts), those that answered, those that gave up (aborted), why the last of those
+ *      did (last_abort: 0 none yet, 1 band, 2 level outgrown, 3 log full, 4 other), and the keys the last launch put back
+ *      (cleaned).  Any pointer after ctx may be NULL.  WFST_SSSP_SOLO=0 switches the route off; =2 tries it whatever the
+ *      streak and makes the call KO, after the query, with the reason unless the solo launch answered. ---- */
+wfst_status wfst_ctx_get_solo_query(wfst_ctx* ctx, uint64_t* attempts, uint64_t* answered, uint64_t* aborted, uint64_t* last_abort,
+                                    uint64_t* cleaned);
+/* tests: the words of ctx's parked key array that are not +inf — an armed scratch has none.  Synchronises the context's
+ *      stream.  KO, and 0 words, when nothing is parked on ctx. */
+wfst_status wfst_ctx_parked_key_check(wfst_ctx* ctx, uint64_t* not_inf);
 /* hipFree of every block the context's device pool holds without an owner: cached blocks and parked scratch (the pool does
  *      the same by itself when an allocation fails).  Synchronises the device.  Live buffers are not touched. */
 wfst_status wfst_ctx_trim_pool(wfst_ctx* ctx);

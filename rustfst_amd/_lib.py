@@ -127,6 +127,10 @@ STRING_PAIR_COUNTS = ("pair_levels", "pair_splits")
 # wfst_ctx_get_string_placement: the same, for where the waves of the last string launch sat
 STRING_PLACEMENT = ("waves_per_workgroup", "slice_states", "workgroups", "packed_for_resident", "forced")
 
+# wfst_ctx_get_solo_query: the same, for the one-launch route of a repeated bounded shortest-path query
+SOLO_QUERY = ("attempts", "answered", "aborted", "last_abort", "cleaned")
+SOLO_ABORTS = ("", "BAND", "GREW", "LOG", "OTHER")  # last_abort, by value
+
 # every symbol include/wfst.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _f32, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_size_t
 _P = C.POINTER
@@ -138,6 +142,8 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_ctx_get_isomorphic_counters", C.c_int, [_vp] + [_P(_u64)] * len(ISOMORPHIC_COUNTERS)),
     ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_ctx_get_string_placement", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PLACEMENT)),
+    ("wfst_ctx_get_solo_query", C.c_int, [_vp] + [_P(_u64)] * len(SOLO_QUERY)),
+    ("wfst_ctx_parked_key_check", C.c_int, [_vp, _P(_u64)]),
     ("wfst_last_error", C.c_int, [_P(C.c_char_p)]),
     ("wfst_string_destroy", C.c_int, [C.c_char_p]),
     ("wfst_abi_version", _u32, []),

@@ -282,6 +282,8 @@ wfst_status wfst_ctx_destroy(wfst_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_chain)
       if (e) (void)hipEventDestroy(e);
     rearm_drop(ctx);  // (the pool may outlive the context: handles share it)
+    ctx->solo_log.reset();
+    sp_host_timing_report(ctx);
     ctx->pool.reset();
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

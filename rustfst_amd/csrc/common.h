@@ -200,7 +200,17 @@ struct RearmRecord {
   static constexpr size_t BLOCKS = 6;  // key, mb_words, improved, ctl, rs_msgs, rs_abort (null: the solve had none)
   void* blk[BLOCKS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t cnt[BLOCKS] = {0, 0, 0, 0, 0, 0};
+  // The solo query (sssp_solo.h) answers from this scratch without adopting it.  `solo`: what the solve that parked it was planned
+  // under (sssp.hip SoloArm; null: that solve was not one a bounded head may end); `stops`: the queries in a row up to the one
+  // that parked it that a bounded head or the solo kernel ended on this context; `epoch`: wfst_fst::sp_epoch as the last of them
+  // left it — any other single-path query of the handle since, from whatever context, shows there.
+  std::shared_ptr<void> solo;
+  uint32_t stops = 0;
+  uint64_t epoch = 0;
   void clear() {  // (the plan goes before its pool)
+    solo.reset();
+    stops = 0;
+    epoch = 0;
     plan.reset();
     plan_pool.reset();
     for (void*& b : blk) b = nullptr;
@@ -395,6 +405,15 @@ struct wfst_ctx {
   } bounded;
   const char* bounded_last_refusal = "";
   bool bounded_hold = false;
+  // The solo query (sssp_solo.h; wfst_ctx_get_solo_query, defined in sssp.hip): launches of its kernel, those that answered,
+  // those that gave the query up, why the last of those did (0 = none yet, 1 BAND, 2 GREW, 3 LOG, 4 OTHER), and the keys the
+  // last launch put back; never zeroed.  solo_hold: the query being repeated by the ordinary route behind such an abort;
+  // solo_log: the kernel's log of the keys it wrote (device memory, allocated by the first attempt)
+  struct SoloQueryCounts {
+    uint64_t attempts = 0, answered = 0, aborted = 0, last_abort = 0, cleaned = 0;
+  } solo_query;
+  bool solo_hold = false;
+  wfst::DBuf<uint32_t> solo_log;
 };
 
 // Device-resident CSR. All arrays live in one arena allocation that may be
@@ -533,6 +552,9 @@ struct wfst_fst {
   // last FULL solve, which is what a solve that cannot stop is sized from.
   mutable std::atomic<uint32_t> bounded_streak{0};
   mutable std::atomic<uint32_t> stable_sweeps{0};  // consecutive solves that needed exactly last_sweeps launches
+  // single-path queries of the large-FST route begun on this FST, from any context (shortest_path_n1_begin): what a context's
+  // parked scratch remembers of it tells whether anybody else has queried the handle since (RearmRecord::epoch)
+  mutable std::atomic<uint64_t> sp_epoch{0};
   // the lazily built caches above may be requested from several contexts (threads) at once: built under this lock,
   // with buffers taken from the OWNER context's pool (this->ctx), which outlives the handle
   mutable std::mutex cache_mu;
@@ -604,6 +626,7 @@ wfst_fst* shortest_path_n1(wfst_ctx* ctx, const wfst_fst* f);
 wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f);
 wfst_fst* shortest_path_n1_end(wfst_sp_job* job);
 void shortest_path_n1_abandon(wfst_sp_job* job);
+void sp_host_timing_report(wfst_ctx* ctx);  // (prints under WFST_SP_HOST_TIMING; called when the context is destroyed)
 wfst_ctx* sp_job_ctx(wfst_sp_job* job);
 // the last solve that finished on `device` in this process ran WIDE levels in a resident launch (never solved: false)
 bool resident_grid_at_work(int device);

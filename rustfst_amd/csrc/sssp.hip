@@ -122,6 +122,8 @@ struct TailOut {
   uint32_t early_src;  // EARLY_SRC_*: where the early tail that published last took the best final state from
   uint32_t rearmed;    // Ctl::rearm as this launch wrote it (0 from a tail without a re-arm launch behind it): the host parks the scratch
   uint32_t bounded_why;  // Ctl::bounded_why: why the bounded head of this solve did not end it (0: it did, or there was none)
+  uint32_t solo;         // SOLO_* (sssp_solo.h): the solo query's verdict; never written by another kernel
+  uint32_t solo_cleaned;  // ... and the keys it put back to KEY_INF (n: every key, behind a log that overflowed)
 };
 constexpr uint32_t EARLY_UNCHECKED = 0, EARLY_USED = 1, EARLY_ABSENT = 2, EARLY_REFUTED = 3;
 constexpr uint32_t EARLY_SRC_LIST = 1, EARLY_SRC_BLOCKS = 2;
@@ -1133,6 +1135,8 @@ __global__ void __launch_bounds__(1024) sssp_tail_kernel(const float* __restrict
   if (lane == 0) __hip_atomic_store(&hout->done, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+#include "sssp_solo.h"
+
 // ---- the reference's tie order on acyclic inputs (wfst_ctx_set_tie_order; include/wfst.h).  rank[s] = position of s in
 // the topological order of the reference's depth-first visit (host), r2s = its inverse.
 // f_parent: the FIRST state in that order whose d[s] (x) rho(s) attains the minimum (shortest_path.rs:214-220: only a
@@ -1331,6 +1335,8 @@ namespace {
 
 // The WFST_SSSP_* variables a solve reads (experiments and tests), in the order of the appendix of DESIGN.md, which says what
 // each one does.  An empty optional / null / false = not set: the default stands where the variable is used.
+// A NEW FIELD GOES INTO knobs_same_plan BELOW AS WELL (the solo query runs only under the knobs its scratch was planned with);
+// the static_assert behind that function stops the build until both have been visited.
 struct Knobs {
   std::optional<int> mailbox;           // WFST_SSSP_MAILBOX
   std::optional<uint32_t> narrow;       // WFST_SSSP_NARROW
@@ -1364,7 +1370,24 @@ struct Knobs {
   int early_best = 1;                   // WFST_SSSP_EARLY_BEST
   int rearm = 1;                        // WFST_SSSP_REARM
   int bounded = 1;                      // WFST_SSSP_BOUNDED
+  int solo = 1;                         // WFST_SSSP_SOLO
+  std::optional<uint32_t> solo_log;     // WFST_SSSP_SOLO_LOG
 };
+// Field by field, every knob that shapes a solve's plan or route (the solo query compares the knobs of the call with those the
+// parked scratch was planned under: RearmRecord::solo).  Not `solo` / `solo_log`, which only say whether and how that route is
+// tried; a trace file on either side is "different" (the solo kernel writes none).
+bool knobs_same_plan(const Knobs& a, const Knobs& b) {
+  return a.mailbox == b.mailbox && a.narrow == b.narrow && a.hint == b.hint && a.big == b.big && a.stg == b.stg && a.delta == b.delta &&
+         a.near_low == b.near_low && a.tau0_mult == b.tau0_mult && a.chase_cap == b.chase_cap && a.chase_rounds == b.chase_rounds &&
+         a.chase_low == b.chase_low && !a.mbox_trace && !b.mbox_trace && a.resident == b.resident && a.res_levels == b.res_levels &&
+         a.res_tlim_us == b.res_tlim_us && a.log12 == b.log12 && !a.res_trace && !b.res_trace && a.binned == b.binned &&
+         a.dense_low == b.dense_low && a.bin_log14 == b.bin_log14 && a.bin_hopcap == b.bin_hopcap && a.res_retry_ms == b.res_retry_ms &&
+         a.test_fail_log13 == b.test_fail_log13 && a.event_wait == b.event_wait && a.log13 == b.log13 && a.lps == b.lps &&
+         a.umax == b.umax && a.split_tail == b.split_tail && a.count_atomics == b.count_atomics && a.final_list == b.final_list &&
+         a.early_tail == b.early_tail && a.early_best == b.early_best && a.rearm == b.rearm && a.bounded == b.bounded;
+}
+constexpr size_t KNOBS_BYTES = 232;
+static_assert(sizeof(Knobs) == KNOBS_BYTES, "Knobs has changed: add the field to knobs_same_plan, then update KNOBS_BYTES");
 
 // Read once per solve, by relax_setup — not once per process: tests and tools change the variables between two solves.
 // One pass over the environment (EnvSnap) instead of a getenv per variable: this runs in front of the first launch.
@@ -1405,6 +1428,8 @@ Knobs read_knobs() {
   if (const char* e = env.get("WFST_SSSP_EARLY_BEST")) k.early_best = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_REARM")) k.rearm = std::atoi(e);
   if (const char* e = env.get("WFST_SSSP_BOUNDED")) k.bounded = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_SOLO")) k.solo = std::atoi(e);
+  if (const char* e = env.get("WFST_SSSP_SOLO_LOG")) k.solo_log = std::max<uint32_t>(1u, (uint32_t)std::atol(e));
   return k;
 }
 
@@ -1422,6 +1447,8 @@ struct Solve {
   // none of them goes back to the pool before the stream has been waited for.
   bool armed = false, rearm_unproven = false;
   const char* rearm_why = "nothing parked";
+  uint32_t rearm_stops = 0;  // armed: RearmRecord::stops / ::epoch of the scratch this solve adopted (the solo query's streak)
+  uint64_t rearm_epoch = 0;
   float tau0 = 0.0f;  // threshold of sweep 0, as the set-up (or the re-arm launch of the solve before) leaves it in Ctl::tau0
   // schedule parameters fixed by relax_setup
   uint8_t* fl[2] = {nullptr, nullptr};
@@ -2064,6 +2091,8 @@ void relax_setup_held(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, RearmHeld& he
         r.tau0_bits == tau0_bits) {
       sv.armed = true;
       sv.rearm_why = nullptr;
+      sv.rearm_stops = r.stops;
+      sv.rearm_epoch = r.epoch;
       ctx->rearm_stats.adopted += 1;
     } else {  // (the blocks this solve took are its own now: whatever it queues comes behind the re-arm launch on the stream)
       sv.rearm_why = eligible ? "knobs differ" : "not eligible";
@@ -2089,9 +2118,10 @@ void relax_setup_held(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, RearmHeld& he
   if (kn.chase_rounds) sv.chase_rounds = *kn.chase_rounds;
   if (kn.chase_low) sv.chase_low = *kn.chase_low;
 }
-void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv) {
-  sv.kn = read_knobs();
+void relax_setup(wfst_ctx* ctx, const wfst_fst* f, Solve& sv, const Knobs* kn = nullptr /*the caller has read them already*/) {
+  sv.kn = kn ? *kn : read_knobs();
   sv.armed = false;
+  sv.rearm_stops = 0;
   sv.rearm_unproven = false;
   RearmHeld held(ctx);
   sv.rearm_why = rearm_take(ctx, f, sv.kn, held);
@@ -2619,8 +2649,25 @@ struct wfst_sp_job {
   // sssp_mbox_rearm_kernel is queued behind the fused tail and the solve's scratch has neither been parked nor waited for: the
   // ticket no longer means that nothing of this job is on the stream
   bool rearm_queued = false;
+  // The solo query (sssp_solo.h): the whole job is ONE launch on the context's parked scratch, which is live (unparked) until end
+  // parks it again; sv holds the knobs only, drv the ticket.  solo_why: why the route was not taken (WFST_SSSP_SOLO=2).
+  bool solo = false;
+  wfst::RearmRecord solo_rec;  // ... taken out of the context while the launch is in flight (whatever else runs on the context
+                               // between begin and end finds nothing parked), put back by end
+  const char* solo_why = nullptr;
+  uint64_t epoch = 0;  // wfst_fst::sp_epoch as this query left it
+#ifdef WFST_SP_HOST_TIMING
+  std::chrono::steady_clock::time_point t_begin[4];
+#endif
   ~wfst_sp_job() {
     if (rearm_queued && ctx) (void)hipStreamSynchronize(ctx->stream);  // (before sv's buffers go back to the pool)
+    // a solo job that ends on an error between its launch and solo_restore (the ticket's stream-wait fall-back reporting a fault):
+    // the six blocks it holds are live in the pool and nobody else knows them — back to the pool behind the stream
+    if (solo_rec.plan && ctx) {
+      (void)hipStreamSynchronize(ctx->stream);
+      for (void* b : solo_rec.blk) ctx->pool->free(b);
+      solo_rec.clear();
+    }
   }
 };
 
@@ -2659,12 +2706,190 @@ void queue_tail(wfst_sp_job* j, const SweepBatch* adv = nullptr) {
                                                 j->rev->arc.p, sv.ctl.p, j->h_path, PATH_PINNED);
   HIP_CHECK(hipMemcpyAsync(j->hc, sv.ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, st));
 }
+
+// ---- host phases of begin / end by steady-clock stamps (build with -DWFST_SP_HOST_TIMING; printed by sp_host_timing_report).
+// begin: entry -> checks and set-up done -> launches queued -> return; end: entry -> ticket seen -> scratch parked -> FST built.
+#ifdef WFST_SP_HOST_TIMING
+#define SP_STAMP(t) (t) = std::chrono::steady_clock::now()
+// [route: 0 ordinary, 1 solo][the three phases of begin, then those of end]; per context, kept in this file so that the macro
+// changes no struct another source sees (tools/build_variant.sh compiles this source alone with it)
+struct SpHostTiming {
+  uint64_t calls[2] = {0, 0};
+  double sum_us[2][6] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+  double min_us[2][6] = {{1e30, 1e30, 1e30, 1e30, 1e30, 1e30}, {1e30, 1e30, 1e30, 1e30, 1e30, 1e30}};
+};
+void sp_timing_print(const SpHostTiming& s) {
+  static const char* const route[2] = {"ordinary", "solo"};
+  static const char* const phase[6] = {"begin: entry -> set-up done", "begin: -> launches queued", "begin: -> return",
+                                       "end: entry -> ticket seen", "end: -> parked", "end: -> FST built"};
+  for (int r = 0; r < 2; ++r) {
+    const uint64_t c = s.calls[r];
+    if (!c) continue;
+    for (int k = 0; k < 6; ++k)
+      std::fprintf(stderr, "sp_host_timing %-8s %-30s calls %8llu mean %8.2f us min %8.2f us\n", route[r], phase[k], (unsigned long long)c,
+                   s.sum_us[r][k] / (double)c, s.min_us[r][k]);
+  }
+}
+std::mutex sp_timing_mu;
+std::map<const wfst_ctx*, SpHostTiming> sp_timing_of;
+struct SpTimingAtExit {  // (a context that is never destroyed — an interpreter that exits with it — is reported here)
+  ~SpTimingAtExit() {
+    for (const auto& kv : sp_timing_of) sp_timing_print(kv.second);
+  }
+} sp_timing_at_exit;
+void sp_timing_add(wfst_ctx* ctx, int route, int first, const std::chrono::steady_clock::time_point* t) {
+  std::lock_guard<std::mutex> lk(sp_timing_mu);
+  SpHostTiming& s = sp_timing_of[ctx];
+  for (int k = 0; k < 3; ++k) {
+    const double us = std::chrono::duration<double, std::micro>(t[k + 1] - t[k]).count();
+    s.sum_us[route][first + k] += us;
+    s.min_us[route][first + k] = std::min(s.min_us[route][first + k], us);
+  }
+  if (first == 0) s.calls[route] += 1;
+}
+struct SpEndTimer {  // (end has many exits: the last stamp is taken when the result has been built)
+  wfst_ctx* ctx;
+  int route = 0;
+  std::chrono::steady_clock::time_point t[4];
+  explicit SpEndTimer(wfst_ctx* c) : ctx(c) { t[0] = t[1] = t[2] = std::chrono::steady_clock::now(); }
+  ~SpEndTimer() {
+    t[3] = std::chrono::steady_clock::now();
+    sp_timing_add(ctx, route, 3, t);
+  }
+};
+#else
+#define SP_STAMP(t) ((void)0)
+#endif
+
+// What the solve that parked a context's scratch was planned under (RearmRecord::solo), kept only where a bounded head could
+// have ended that solve: the solo query compares the knobs of its call with these, field by field.
+struct SoloArm {
+  Knobs kn;
+  uint32_t relax_kernel;  // wfst_stats::relax_kernel as relax_setup set it
+};
+const char* solo_abort_text(uint32_t verdict) {
+  return verdict == SOLO_ABORT_BAND   ? "no total at or below the first band"
+         : verdict == SOLO_ABORT_GREW ? "a level outgrew its workgroup"
+         : verdict == SOLO_ABORT_LOG  ? "the log of written keys is full"
+                                      : "its list did not run empty";
+}
+
+// The scratch a solo job took out of its context goes back, parked as it was (the kernel has put every key back; the caller has
+// seen the ticket or waited for the stream).  false: other scratch has been parked on the context since — these blocks go back
+// to the pool.
+bool solo_restore(wfst_sp_job* j) {
+  wfst_ctx* ctx = j->ctx;
+  RearmRecord& r = ctx->rearm;
+  const bool back = !r.plan;
+  if (back) {
+    r = std::move(j->solo_rec);
+    ctx->pool->park(r.blk, RearmRecord::BLOCKS);
+    ctx->rearm_stats.armed += 1;
+  } else {
+    // (the ticket only says that wave 0's stores have landed: blocks that leave this stream's custody — another context may take
+    // them from the shared pool at once — wait for the kernel's end)
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void* b : j->solo_rec.blk) ctx->pool->free(b);
+    ctx->rearm_stats.dropped += 1;
+  }
+  j->solo_rec.clear();
+  return back;
+}
+
+// The solo query (sssp_solo.h) where today's code would queue "the bounded head and nothing behind it" on re-armed scratch: the
+// checks that keep the route correct across edits, knob changes and other queries, then ONE launch on the parked key[].  No
+// allocation, no plan, no view: the scratch stays as the re-arm launch left it, apart from the keys the kernel writes and puts
+// back.  What is left of the pool and the lease: the six parked blocks are made live for the launch and parked again by end (one
+// lock each way), and the resident lease is held where the scratch was planned with it (below).  Returns why the route is not taken (nothing has happened then), null when the launch is queued.
+const char* solo_begin(wfst_sp_job* j, const Knobs& kn) {
+  wfst_ctx* ctx = j->ctx;
+  const wfst_fst* f = j->f;
+  RearmRecord& r = ctx->rearm;
+  if (kn.solo == 0) return "switched off (WFST_SSSP_SOLO=0)";
+  if (ctx->solo_hold) return "not eligible: the repeat of a query that the solo kernel gave up";
+  if (ctx->chain_timing || ctx->bounded_hold || ctx->resident_hold) return "not eligible: profiling, or the repeat of a query";
+  if (!r.plan) return "nothing parked";
+  if (!r.solo) return "not eligible: the parked scratch is not that of a query a bounded head may end";
+  const SoloArm& arm = *static_cast<const SoloArm*>(r.solo.get());
+  if (!knobs_same_plan(kn, arm.kn)) return "knobs differ";
+  if (!j->rev || !j->rev->has_fin || !j->rev->fin_nonneg) return "not eligible: no list of final states, or a negative final weight";
+  if (!mbox_eligible(f) || f->last_sweeps.load(std::memory_order_relaxed) == 0) return "not eligible";
+  {
+    std::lock_guard<std::mutex> lk(f->cache_mu);
+    if (f->mbox != r.plan || f->n_states != r.n) return "parked for another plan";
+  }
+  // (the first band, as relax_setup computes it: an edit of the weights that keeps the plan shows here)
+  const float tau0 = band_from_cheapest_arcs(f, *r.plan, band_from_mean_weight(f, kn), kn) * (kn.tau0_mult > 0.0f ? kn.tau0_mult : 1.0f);
+  uint32_t tau0_bits;
+  std::memcpy(&tau0_bits, &tau0, sizeof(tau0_bits));
+  if (tau0_bits != r.tau0_bits || r.log != 12 || !r.narrow) return "knobs differ";
+  // (resident or not, as lease_resident would decide now: a lease that is out, a pause behind an abort or another device share
+  // would make the ordinary route drop this scratch and plan again — and say so in wfst_stats.relax_kernel)
+  const bool res_now = kn.resident && resident_block_log(ctx, f->n_states, kn) != 0 && ctx->resident_allowed() && !kn.big;
+  if (res_now != r.resident) return "not eligible: the device share or a pause of the resident launches has changed the plan";
+  // three stops in a row on this context, nobody else's query of the handle in between, and the start where it was (set_start
+  // resets the handle's own streak); WFST_SSSP_SOLO=2 goes whatever the streak
+  if (kn.solo < 2 && (r.stops < 3 || r.epoch + 1 != j->epoch || f->bounded_streak.load(std::memory_order_relaxed) < 3))
+    return "fewer than three stops in a row";
+  if (!ctx->solo_log.p) ctx->solo_log = DBuf<uint32_t>(*ctx->pool, SOLO_LOG_CAP);
+  // The lease, held from here to end like that of the solve this launch replaces — the kernel itself needs no compute unit to
+  // itself, but who else finds a unit while this query is in flight, and what their wfst_stats.relax_kernel says, stays as it was
+  // (tests/test_gpu_parity.py: a third query beside two half-device ones takes one launch per level).
+  if (r.resident && !j->sv.lease.acquire(ctx->device, ctx->resident_share == 1u ? 1 : 2)) return "not eligible: the resident lease is out";
+  if (!ctx->pool->unpark(r.blk, RearmRecord::BLOCKS)) {  // (the pool's trim: hipFree has waited for the re-arm launch)
+    j->sv.lease.release();
+    r.clear();
+    ctx->rearm_stats.dropped += 1;
+    return "blocks reclaimed";
+  }
+  ctx->rearm_stats.adopted += 1;
+  j->solo_rec = std::move(r);
+  r.clear();
+  const uint32_t log_cap = std::min<uint32_t>(SOLO_LOG_CAP, kn.solo_log.value_or(SOLO_LOG_CAP));
+  SP_STAMP(j->t_begin[1]);
+  sssp_solo_kernel<<<1, MB_THREADS, 0, ctx->stream>>>(f->dev.offsets, f->dev.wn, (uint64_t*)j->solo_rec.blk[RH_KEY], f->n_states, (uint32_t)f->start,
+                                                      tau0, f->dev.finals, j->rev->fin.p, j->rev->n_fin, f->dev.arcs, j->rev->off.p,
+                                                      j->rev->arc.p, j->h_path, PATH_PINNED, j->h_tail, ctx->solo_log.p, log_cap,
+                                                      j->done_ticket);
+  SP_STAMP(j->t_begin[2]);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    (void)solo_restore(j);
+    throw Error(std::string("HIP error ") + hipGetErrorString(err) + " launching the solo query");
+  }
+  ctx->solo_query.attempts += 1;
+  ctx->stats.sweeps = 0;
+  ctx->stats.relax_kernel = arm.relax_kernel;
+  j->solo = true;
+  j->fused_tail = true;
+  j->tail_queued = true;
+  j->sv.kn = kn;
+  j->sv.armed = true;
+  j->drv.ctx = ctx;
+  j->drv.sv = &j->sv;
+  j->drv.done_word = &j->h_tail->done;
+  j->drv.done_ticket = j->done_ticket;
+  return nullptr;
+}
 }  // namespace
+
+void sp_host_timing_report(wfst_ctx* ctx) {
+#ifdef WFST_SP_HOST_TIMING
+  std::lock_guard<std::mutex> lk(sp_timing_mu);
+  const auto it = sp_timing_of.find(ctx);
+  if (it == sp_timing_of.end()) return;
+  sp_timing_print(it->second);
+  sp_timing_of.erase(it);
+#else
+  (void)ctx;
+#endif
+}
 
 wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   std::unique_ptr<wfst_sp_job> j(new wfst_sp_job());
   j->ctx = ctx;
   j->f = f;
+  SP_STAMP(j->t_begin[0]);
   const uint32_t n = f->n_states;
   if (f->start < 0 || n == 0) {
     j->trivial = true;
@@ -2694,12 +2919,25 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
   j->h_tail->done = 0u;
   j->h_tail->rearmed = 0u;
   j->h_tail->bounded_why = 0u;
+  j->h_tail->solo = 0u;
   j->rev = reverse_csr(ctx, f, j->need_unique);  // may build the transpose (second query of a large FST): before anything is queued
+  j->epoch = f->sp_epoch.fetch_add(1, std::memory_order_relaxed) + 1u;
   if (ctx->profiling) {
     run_relaxation(ctx, f, j->sv);  // per-sweep events: synchronous
     return j.release();
   }
-  relax_setup(ctx, f, j->sv);
+  const Knobs kn = read_knobs();
+  j->solo_why = solo_begin(j.get(), kn);
+  if (j->solo) {  // (one launch is queued; end waits for its ticket)
+    SP_STAMP(j->t_begin[3]);  // ([1], [2]: solo_begin, in front of and behind the launch)
+#ifdef WFST_SP_HOST_TIMING
+    sp_timing_add(ctx, 1, 0, j->t_begin);
+#endif
+    return j.release();
+  }
+  relax_setup(ctx, f, j->sv, &kn);
+  SP_STAMP(j->t_begin[1]);
+  if (j->sv.armed && j->sv.rearm_epoch + 1u != j->epoch) j->sv.rearm_stops = 0;  // (somebody else has queried the handle since)
   if (j->sv.kn.final_list >= 2 && j->rev && !j->rev->has_fin) {  // tests: which of the two tails a handle gets
     (void)hipStreamSynchronize(ctx->stream);  // (the set-up is queued: the solve's buffers go back to the pool after this)
     throw Error("shortest_path: WFST_SSSP_FINAL_LIST=2 and the handle has no list of final states");
@@ -2751,6 +2989,7 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
     if (sv.bounded_on && streak) j->drv.first_count = std::min<uint32_t>(j->drv.first_count, streak >= 3 ? 1u : 2u);
   }
   j->drv.start(/*defer_advance=*/fuse);
+  SP_STAMP(j->t_begin[2]);  // (taken again behind each later launch: what is left to [3] is the launch checks and the return)
   if (fuse) {  // the tail closes the batch: flags to the host, base advanced, then the ticket finish() waits for
     // ... and behind the ticket, where the stream has nothing to do until the next query, the scratch is cleaned for that query
     // if the tail finds this one over (Ctl::rearm): 4096-state blocks with NARROW launches (launch 0 then seeds the start itself)
@@ -2763,12 +3002,20 @@ wfst_sp_job* shortest_path_n1_begin(wfst_ctx* ctx, const wfst_fst* f) {
     if (j->rearm_queued) {
       sssp_mbox_rearm_kernel<12><<<sv.blocks, 256, 0, ctx->stream>>>(sv.key.p, sv.mv, sv.improved.p, sv.ctl.p, n, sv.tau0, sv.rv.msgs[0],
                                                                      sv.rv.msgs[1], sv.rv.roffh, sv.rv.abort);
+      SP_STAMP(j->t_begin[2]);
       HIP_CHECK(hipGetLastError());
+    } else {
+      SP_STAMP(j->t_begin[2]);
     }
   } else if (j->drv.predicted && j->rev) {
     queue_tail(j.get());
+    SP_STAMP(j->t_begin[2]);
     j->tail_queued = true;
   }
+  SP_STAMP(j->t_begin[3]);
+#ifdef WFST_SP_HOST_TIMING
+  sp_timing_add(ctx, 0, 0, j->t_begin);
+#endif
   return j.release();
 }
 
@@ -2784,6 +3031,75 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   const uint32_t n = f->n_states;
   hipStream_t st = ctx->stream;
   Solve& sv = j->sv;
+#ifdef WFST_SP_HOST_TIMING
+  SpEndTimer timer(ctx);
+  timer.route = j->solo ? 1 : 0;
+#endif
+  // A bounded stop (or the solo kernel's answer) whose path is longer than the pinned buffer: the parent pass would read every
+  // key, and the keys above B are not the fixed point.  The whole query again, unbounded.
+  auto again_unbounded = [&]() -> wfst_fst* {
+    j.reset();
+    struct Hold {
+      wfst_ctx* c;
+      explicit Hold(wfst_ctx* x) : c(x) { c->bounded_hold = true; }
+      ~Hold() { c->bounded_hold = false; }
+    } hold(ctx);
+    return shortest_path_n1_end(shortest_path_n1_begin(ctx, f));
+  };
+  if (j->solo) {
+    // The ticket, then the scratch parked again as it was (the kernel has put every key back), then the verdict: an abort is the
+    // query again by the ordinary route — nothing of the attempt is reused, and the next queries are ordinary until three stop in
+    // a row again.  An answer is booked as the bounded stop of one launch that it replaces.
+    j->drv.wait_first_batch();
+    sv.lease.release();
+    SP_STAMP(timer.t[1]);
+    HIP_CHECK(hipPeekAtLastError());
+    RearmRecord& r = ctx->rearm;
+    const bool back = solo_restore(j.get());
+    SP_STAMP(timer.t[2]);
+    const uint32_t verdict = j->h_tail->solo;
+    ctx->solo_query.cleaned = j->h_tail->solo_cleaned;
+    // (a stop whose path is longer than the pinned buffer is no answer either: the result comes from the unbounded repeat, and
+    // it is decided before anything is booked as answered)
+    const bool too_long = verdict == SOLO_ANSWERED && (j->h_tail->pad & 8u) && !(j->h_tail->pad & 5u);
+    if (verdict != SOLO_ANSWERED || too_long) {
+      ctx->solo_query.aborted += 1;
+      ctx->solo_query.last_abort = too_long ? SOLO_ABORT_OTHER - 1u : verdict - 1u;
+      if (back) r.stops = 0;
+      f->bounded_streak.store(0, std::memory_order_relaxed);
+      const bool strict = sv.kn.solo >= 2;
+      j.reset();
+      Handle out;
+      {
+        struct Hold {  // (too_long: the repeat may not stop bounded either — the same header would come back)
+          wfst_ctx* c;
+          bool unbounded;
+          Hold(wfst_ctx* x, bool u) : c(x), unbounded(u) {
+            c->solo_hold = true;
+            if (unbounded) c->bounded_hold = true;
+          }
+          ~Hold() {
+            c->solo_hold = false;
+            if (unbounded) c->bounded_hold = false;
+          }
+        } hold(ctx, too_long);
+        out.reset(shortest_path_n1_end(shortest_path_n1_begin(ctx, f)));
+      }
+      if (strict)  // tests: a query that the solo kernel answered, or an error that says why not
+        throw Error(std::string("shortest_path: WFST_SSSP_SOLO=2 and the solo kernel gave the query up: ") +
+                    (too_long ? "the path is longer than the pinned buffer" : solo_abort_text(verdict)));
+      return out.release();
+    }
+    ctx->solo_query.answered += 1;
+    if (back) {
+      r.stops += 1;
+      r.epoch = j->epoch;
+    }
+    ctx->stats.sweeps = 1;
+    ctx->bounded.stops += 1;
+    f->bounded_streak.fetch_add(1, std::memory_order_relaxed);
+    resident_work_of(ctx->device).store(0, std::memory_order_relaxed);  // (record_solve's hint: no grid of whole compute units ran)
+  } else {
   if (!ctx->profiling && !finish_solve(ctx, f, sv, j->drv)) {  // a resident launch gave up waiting: the whole query again
     j.reset();  // (its buffers go back to the pool)
     ResidentHold hold(ctx);
@@ -2799,6 +3115,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
   else HIP_CHECK(hipPeekAtLastError());  // (no stream wait on this path.  Reports launch-configuration / sticky API errors the runtime has already
                                               // seen — NOT an asynchronous kernel fault: a chain that faults never writes its ticket, and the spin above then
                                               // ends in the stream wait, which reports it.  Peek, not Get: the error may belong to another thread's launch)
+  SP_STAMP(timer.t[1]);
   if (j->rearm_queued) {
     // The tail's verdict, believed as it stands: the re-arm launch is cleaning (or has cleaned) the scratch, which is parked for
     // the next solve on this context instead of going back to the pool — other contexts allocate from it on other streams.
@@ -2813,6 +3130,10 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
       std::memcpy(&r.tau0_bits, &sv.tau0, sizeof(r.tau0_bits));
       r.resident = sv.resident;
       r.narrow = sv.narrow_t != 0;
+      // (the solo query's view of this scratch: sssp_solo.h)
+      r.solo = sv.bounded_on ? std::make_shared<SoloArm>(SoloArm{sv.kn, (uint32_t)ctx->stats.relax_kernel}) : nullptr;
+      r.stops = j->drv.bounded ? sv.rearm_stops + 1u : 0u;
+      r.epoch = j->epoch;
       auto note = [&](size_t i, auto& buf) {
         r.blk[i] = buf.p;
         r.cnt[i] = buf.p ? buf.n : 0;
@@ -2836,6 +3157,7 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
     }
     j->rearm_queued = false;
   }
+  SP_STAMP(timer.t[2]);
   // The bounded head's book-keeping.  `stopped`: launch 0 posted FLAG_NARROW_BOUNDED and the fused tail behind the first batch
   // searched keys that are exact at and below B (never an extended solve: the flag is launch 0's).
   const bool b_stopped = j->drv.bounded;
@@ -2852,17 +3174,8 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
     ctx->bounded.full_solves += 1;
     ctx->bounded_last_refusal = ctx->profiling ? "not eligible: profiling is on" : sv.bounded_why ? sv.bounded_why : "not eligible";
   }
-  if (b_stopped && j->fused_tail && (j->h_tail->pad & 8u) && !(j->h_tail->pad & 5u)) {
-    // A path longer than the pinned buffer: the parent pass would read every key, and the keys above B are not the fixed point.
-    // The whole query again, unbounded (the tail gave this solve no re-arm verdict: the stream was waited for above).
-    j.reset();
-    struct Hold {
-      wfst_ctx* c;
-      explicit Hold(wfst_ctx* x) : c(x) { c->bounded_hold = true; }
-      ~Hold() { c->bounded_hold = false; }
-    } hold(ctx);
-    return shortest_path_n1_end(shortest_path_n1_begin(ctx, f));
-  }
+  // (a path longer than the pinned buffer; the tail gave this solve no re-arm verdict: the stream was waited for above)
+  if (b_stopped && j->fused_tail && (j->h_tail->pad & 8u) && !(j->h_tail->pad & 5u)) return again_unbounded();
   if (sv.kn.bounded >= 2 && !b_stopped)  // tests: a query that the bounded head ended, or an error that says why not
     throw Error(std::string("shortest_path: WFST_SSSP_BOUNDED=2 and the bounded head did not end the solve: ") + ctx->bounded_last_refusal);
   if (sv.kn.rearm >= 2 && !sv.armed)  // tests: a solve that started from re-armed scratch, or an error that says why not
@@ -2892,6 +3205,12 @@ wfst_fst* shortest_path_n1_end(wfst_sp_job* job) {
                   (!sv.early_on || sv.log != 12 ? "not eligible" : !sv.blk_best_on ? "no resident hand-over" : e == EARLY_REFUTED ? "refuted"
                    : e != EARLY_USED ? "absent" : "no resident hand-over"));
   }
+  // tests: a query that the solo kernel answered, or an error that says why the route was not taken (the repeat behind an abort
+  // of that kernel reports through the call that made it)
+  if (sv.kn.solo >= 2 && !ctx->solo_hold)
+    throw Error(std::string("shortest_path: WFST_SSSP_SOLO=2 and the solo kernel did not answer the query: ") +
+                (j->solo_why ? j->solo_why : "not eligible"));
+  }  // (the ordinary route)
   const Ctl* hc = j->hc;
   const uint32_t r_pad = j->fused_tail ? j->h_tail->pad : hc->pad, r_has_path = j->fused_tail ? j->h_tail->has_path : hc->has_path;
   if (r_pad & 1u) throw Error("shortest_path: hop count overflow in the mailbox sweeps (internal error)");
@@ -2948,6 +3267,9 @@ void shortest_path_n1_abandon(wfst_sp_job* job) {
   std::unique_ptr<wfst_sp_job> j(job);
   delete j->ready;
   if (!j->trivial) (void)hipStreamSynchronize(j->ctx->stream);  // the solve's buffers go back to the pool after this
+  if (j->solo) {  // (the kernel has put every key back: the scratch is parked again as it was, its streak over)
+    if (solo_restore(j.get())) j->ctx->rearm.stops = 0;
+  }
 }
 
 wfst_ctx* sp_job_ctx(wfst_sp_job* job) { return job->ctx; }
@@ -2959,3 +3281,48 @@ wfst_fst* shortest_path_n1(wfst_ctx* ctx, const wfst_fst* f) {
 }
 
 }  // namespace wfst
+
+// The solo query's counters (common.h: wfst_ctx::solo_query), beside the route that keeps them.  Any out-pointer may be null.
+extern "C" wfst_status wfst_ctx_get_solo_query(wfst_ctx* ctx, uint64_t* attempts, uint64_t* answered, uint64_t* aborted,
+                                               uint64_t* last_abort, uint64_t* cleaned) {
+  return wfst::wrap([&] {
+    if (!ctx) throw wfst::Error("null pointer");
+    const wfst_ctx::SoloQueryCounts& c = ctx->solo_query;
+    if (attempts) *attempts = c.attempts;
+    if (answered) *answered = c.answered;
+    if (aborted) *aborted = c.aborted;
+    if (last_abort) *last_abort = c.last_abort;
+    if (cleaned) *cleaned = c.cleaned;
+  });
+}
+
+// Tests: the words of ctx's parked key[] that are not KEY_INF (an armed scratch has none).  Synchronous; KO and 0 words when
+// nothing is parked.
+extern "C" wfst_status wfst_ctx_parked_key_check(wfst_ctx* ctx, uint64_t* not_inf) {
+  return wfst::wrap([&] {
+    using namespace wfst;
+    if (!ctx || !not_inf) throw Error("null pointer");
+    *not_inf = 0;
+    RearmRecord& r = ctx->rearm;
+    if (!r.plan || !r.blk[RH_KEY]) throw Error("wfst_ctx_parked_key_check: nothing is parked on this context");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->pool->unpark(r.blk, RearmRecord::BLOCKS)) {  // (the pool's trim has taken the blocks)
+      r.clear();
+      ctx->rearm_stats.dropped += 1;
+      throw Error("wfst_ctx_parked_key_check: nothing is parked on this context");
+    }
+    struct Repark {  // (live while the kernel reads them, parked again on every exit)
+      wfst_ctx* c;
+      ~Repark() { c->pool->park(c->rearm.blk, RearmRecord::BLOCKS); }
+    } repark{ctx};
+    DBuf<unsigned long long> count(*ctx->pool, 1);
+    HIP_CHECK(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), ctx->stream));
+    sssp_key_check_kernel<<<std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)ctx->n_cus * 4, (r.n + 255) / 256)), 256, 0, ctx->stream>>>(
+        (const uint64_t*)r.blk[RH_KEY], r.n, count.p);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long h = 0;
+    HIP_CHECK(hipMemcpyAsync(&h, count.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *not_inf = h;
+  });
+}

@@ -374,7 +374,20 @@ __device__ __forceinline__ void mbox_make_wait(const MboxView& mb, uint32_t t, u
 // next set-up's / re-arm's to clean, like those of any solve.  `s_n` has 12 words in this instance: B as found by the level
 // that fills list counter c in [8 + c] (rotating with the counters, so that the value a level reads is final and uniform),
 // near candidates left unlisted [11].
-template <uint32_t LOG, bool BOUNDED = false>
+//
+// SOLO (a compile-time instance of the bounded head: sssp_solo.h, ONE workgroup answers the whole query or gives it up): the far
+// side of the head's search exists only so that later launches can continue it, and a query that is either answered in this
+// launch or asked again from scratch needs none of it.  A candidate above min(tau, B) is DROPPED — no message, no atomicMin,
+// no wait — and nothing of the view or the control block is read or written.  The argument above carries over unchanged: every
+// candidate not followed was above the final B, and the only difference is what such a candidate leaves behind — a key above B
+// before, KEY_INF now.  tail_candidate skips a final state at KEY_INF (its total would have been above B: neither the optimum
+// nor a tie), and sssp_walk_back skips a predecessor at KEY_INF for the same reason an unsettled key is inadmissible today
+// (d[s] (+) w == d[t] <= B needs d[s] <= B, and every state at or below B was won, listed and expanded).  Whatever would keep
+// the head from stopping is an abort here (a near winner that does not fit the list, a level above NW_GROW, NW_MAX_LEVELS, a
+// B above tau, the shrink rule).  Every state that wins a key is appended to `solo_log` (the kernel puts key[] back from it);
+// s_n has 16 words: hop-count overflow [12] (Ctl::pad in the other instances), log entries [13], log capacity [14], and the
+// verdict [15]: 0 = stop, else BOUNDED_WHY_*.
+template <uint32_t LOG, bool BOUNDED = false, bool SOLO = false>
 __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets, const uint2* __restrict__ wn,
                                             uint64_t* __restrict__ key, const MboxView& mb, Ctl* __restrict__ ctl,
                                             uint32_t* __restrict__ improved, uint32_t sweep, float tau, uint32_t far_total,
@@ -383,7 +396,9 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
                                             uint32_t par_out, const uint32_t* l_roff_out, uint32_t* l_cur, uint32_t* l_cap,
                                             uint32_t seed_p1 = 0u /*launch 0 of an armed solve, the start's block: start + 1*/,
                                             uint32_t seed_off = 0u /*... lanes 0 / 1 of the first wave: offsets[start], offsets[start + 1]*/,
-                                            const float* __restrict__ finals = nullptr /*BOUNDED: the final weights*/) {
+                                            const float* __restrict__ finals = nullptr /*BOUNDED: the final weights*/,
+                                            uint32_t* __restrict__ solo_log = nullptr /*SOLO: the states whose key this launch wrote*/) {
+  static_assert(!SOLO || BOUNDED, "the solo query is an instance of the bounded head");
   constexpr uint32_t MB_LOG = LOG, MB_B = 1u << LOG, MB_HOP_BITS = 32 - LOG, NW_SEG = MB_B;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, j = blockIdx.x, nb = mb.nb;
   const uint32_t sub = tid & 15u, grp = tid >> 4;
@@ -394,15 +409,16 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
   // atomic path.
   const bool head = sweep == 0;
   uint2* __restrict__ msgs_out = mb.msgs[par_out];
-  if (head && wl_n)
+  if (!SOLO && head && wl_n)
     for (uint32_t d = tid; d < nb; d += MB_THREADS) l_cap[d] = mb.roff[(size_t)d * nb + j + 1] - mb.roff[(size_t)d * nb + j];
-  unsigned long long* const nf = &ctl->nf[sweep % NEAR_RING][(j % NEAR_SHARDS) * NF_STRIDE];
+  unsigned long long* const nf = SOLO ? nullptr : &ctl->nf[sweep % NEAR_RING][(j % NEAR_SHARDS) * NF_STRIDE];
   if (seed_p1) {  // (uniform) re-armed scratch: no set-up launch wrote the start state's entry and key — this workgroup does
     // (a plain store: weights are not negative wherever the mailbox runs, so no candidate beats the key (0, 0 hops))
     const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)seed_off, 0), e1 = (uint32_t)__builtin_amdgcn_readlane((int)seed_off, 1);
     if (tid == 0) {
       wl[0] = make_uint4(seed_p1 - 1u, b, f32_key(0.0f), min(e1 - b, NW_DEG_SAT));
       key[seed_p1 - 1u] = (uint64_t)f32_key(0.0f) << 32;
+      if (SOLO) solo_log[0] = seed_p1 - 1u;  // (entry 0 of the log: s_n[13] starts at 1 and the capacity is at least 1)
     }
   } else {
     for (uint32_t e = tid; e < wl_n; e += MB_THREADS) {  // (a segment longer than the list: the rest keeps waiting)
@@ -418,7 +434,7 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     s_n[3] = 0;
     s_n[4] = (waits || wl_n > NW_CAP) ? 1u : 0u;  // something is left waiting after this launch
     s_n[5] = 0xFFFFFFFFu;
-    if (wl_n) mb.wl_cnt[j] = 0;
+    if (!SOLO && wl_n) mb.wl_cnt[j] = 0;
     if (BOUNDED) {  // B starts at the start state's own final weight: entry 0 of the head's list at distance 0
       uint32_t b0 = 0xFFFFFFFFu;
       if (head && wl_n == 1u) {
@@ -531,7 +547,12 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
           old[u] = 0;
           tb[u] = te[u] = 0;
           if (BOUNDED) fw[u] = INF;
-          if (head && v[u] && c > thr) {
+          if (SOLO) {  // beyond min(tau, B): not this query's business (counted all the same: the head's shrink rule)
+            if (v[u] && c > thr) {
+              far_new += 1u;
+              v[u] = false;
+            }
+          } else if (head && v[u] && c > thr) {
             const uint32_t db = a[u].y >> MB_LOG, slot = atomicAdd(&l_cur[db], 1u);
             if (slot < l_cap[db]) {
               msgs_out[l_roff_out[db] + slot] = make_uint2((h1_[u] << MB_LOG) | (a[u].y & (MB_B - 1u)), enc[u]);
@@ -557,7 +578,14 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
             // launches k >= 1 are certified: kept in a register across the level loop and reduced at the end, the recording
             // cost the head launch 2.6 us (profiles/early_block_best_ab.md)
             if (!head) atomicMin(&s_n[5], enc[u]);
-            if (h1_[u] >> MB_HOP_BITS) ctl->pad = 1u;  // hop count beyond the message format: the host refuses the result
+            if (h1_[u] >> MB_HOP_BITS) {  // hop count beyond the message format: the host refuses the result
+              if (SOLO) s_n[12] = 1u;
+              else ctl->pad = 1u;
+            }
+            if (SOLO) {  // the key is to be put back: a log that is full says so in its count, and the kernel cleans every key
+              const uint32_t at = atomicAdd(&s_n[13], 1u);
+              if (at < s_n[14]) solo_log[at] = a[u].y;
+            }
             bool listed = false;
             if (BOUNDED && head) {  // d[t] (+) rho(t), as tail_candidate computes it
               const float tot = (key_f32(enc[u]) + fw[u]) + 0.0f;
@@ -570,11 +598,11 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
                 listed = true;
               }
               if (!listed) {
-                mbox_make_wait<LOG>(mb, a[u].y, enc[u], false);
+                if (!SOLO) mbox_make_wait<LOG>(mb, a[u].y, enc[u], false);
                 left_any = true;
                 if (BOUNDED) s_n[11] = 1u;  // a near candidate nobody follows: no stop in this launch
               }
-            } else {
+            } else if (!SOLO) {  // (SOLO: nothing above the threshold is ever won)
               mbox_make_wait<LOG>(mb, a[u].y, enc[u], true);
               far_new += 1u;
               left_any = true;
@@ -598,6 +626,14 @@ __device__ __forceinline__ void mbox_narrow(const uint32_t* __restrict__ offsets
     prev_n = n_lv;
     cur ^= 1u;
     cnt_i = cnt_o;
+  }
+  if (SOLO) {  // the verdict, for the kernel around this call; nothing waits for anybody (what is still listed is in the log)
+    if (tid == 0) {
+      const bool in_band = b_run != 0xFFFFFFFFu && key_f32(b_run) <= tau;
+      const bool stop = ran_empty && in_band && s_n[11] == 0u;
+      s_n[15] = stop ? 0u : (grew || s_n[11] != 0u) ? BOUNDED_WHY_GREW : !in_band ? BOUNDED_WHY_BAND : BOUNDED_WHY_OTHER;
+    }
+    return;
   }
   // whatever is still listed waits for the next WIDE sweep (near states: it expands them at once)
   {

@@ -102,6 +102,26 @@ class Context:
         check(_lib.lib().wfst_ctx_get_bounded_stats(self._h, C.byref(stops), C.byref(full), C.byref(why)), "wfst_ctx_get_bounded_stats")
         return dict(stops=int(stops.value), full_solves=int(full.value), last_reason=(why.value or b"").decode())
 
+    def solo_query(self) -> dict:
+        """The solo query of this context (wfst_ctx_get_solo_query): launches of the one-workgroup kernel that answers a repeated
+        bounded shortest-path query on the parked scratch (attempts), those that answered, those that gave the query up to the
+        ordinary route (aborted), why the last of those did (last_abort: "", "BAND", "GREW", "LOG" or "OTHER") and the keys
+        the last launch put back (cleaned).  All 0 / "" with a library from before the route."""
+        if not hasattr(_lib.lib(), "wfst_ctx_get_solo_query"):  # (WFST_LIB_PATH: a build from before the route)
+            return dict(dict.fromkeys(_lib.SOLO_QUERY, 0), last_abort="")
+        vals = [C.c_uint64() for _ in _lib.SOLO_QUERY]
+        check(_lib.lib().wfst_ctx_get_solo_query(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_solo_query")
+        out = {k: int(v.value) for k, v in zip(_lib.SOLO_QUERY, vals)}
+        out["last_abort"] = _lib.SOLO_ABORTS[out["last_abort"]]
+        return out
+
+    def parked_key_check(self) -> int:
+        """Tests: how many words of this context's parked relaxation keys are not +inf (wfst_ctx_parked_key_check): an armed
+        scratch has none.  Raises when nothing is parked."""
+        not_inf = C.c_uint64()
+        check(_lib.lib().wfst_ctx_parked_key_check(self._h, C.byref(not_inf)), "wfst_ctx_parked_key_check")
+        return int(not_inf.value)
+
     def small_path_stats(self) -> dict:
         """Which path answered the small shortest-path queries of this context (wfst_ctx_get_small_path_stats): the last
         launch of the nshortest = 1 wave kernel (n1_in_kernel, n1_staged, n1_handed_back) and the last n-best batch
