@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats, wfst_compose_batch, wfst_ctx_get_compose_batch_counters, wfst_fst_invert, wfst_isomorphic, wfst_ctx_get_isomorphic_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
+#define WFST_ABI_VERSION 7 /* 7: wfst_fst_set_start, then wfst_shortest_distance_with_config, wfst_push_weights, wfst_reweight, wfst_determinize, wfst_minimize, wfst_ctx_get_rm_epsilon_stats, wfst_ctx_get_rearm_stats, wfst_ctx_get_bounded_stats, wfst_ctx_trim_pool, wfst_ctx_get_small_path_stats, wfst_ctx_get_compose_path_stats, wfst_ctx_get_string_run_stats, wfst_ctx_get_string_pair_counts, wfst_ctx_get_string_placement, wfst_ctx_get_determinize_stats, wfst_ctx_get_minimize_stats, wfst_ctx_get_push_stats, wfst_tr_sum_batch, wfst_tr_unique_batch, wfst_ctx_get_tr_sum_batch_stats, wfst_optimize_batch, wfst_ctx_get_optimize_batch_stats, wfst_state_sort, wfst_top_sort, wfst_ctx_get_top_sort_stats, wfst_replace, wfst_ctx_get_replace_stats, wfst_compose_with_matchers, wfst_ctx_get_compose_sigma_counters, wfst_compose_shortest_path_batch_with_matchers, wfst_ctx_get_sigma_batch_counters, wfst_top_sort_batch, wfst_ctx_get_top_sort_batch_counters, wfst_ctx_get_lookahead_stats, wfst_compose_batch, wfst_ctx_get_compose_batch_counters, wfst_fst_invert, wfst_isomorphic, wfst_ctx_get_isomorphic_counters, wfst_fst_count_paths, wfst_fst_paths, wfst_fst_paths_batch, wfst_paths_info, wfst_paths_download, wfst_paths_destroy, wfst_ctx_get_paths_counters; 6: wfst_ctx_set_resident_share; 5: wfst_ctx_get_sweep_modes, relax_kernel may be 3, wfst_stats gained tied_choices;
                              * 2: wfst_stats gained relax_kernel; 3: wfst_comm_* / wfst_gather_paths_*, ..._batch_packed;
                              * 4: wfst_stats gained resident_aborts, relax_kernel may be 2; wfst_comm_create_host, wfst_gather_records_begin */
 
@@ -789,6 +789,59 @@ wfst_status wfst_isomorphic(wfst_ctx* ctx, const wfst_fst* fst1, const wfst_fst*
 wfst_status wfst_ctx_get_isomorphic_counters(wfst_ctx* ctx, uint64_t* levels, uint64_t* narrow_launches, uint64_t* wide_launches,
                                              uint64_t* narrow_levels, uint64_t* max_level_width, uint64_t* pairs, uint64_t* events,
                                              uint64_t* wave_pairs, uint64_t* big_states_sorted, uint64_t* nondet_marks);
+
+/* ---- paths: Fst::paths_iter (rustfst/src/fst_traits/paths_iterator.rs:24-62, under rustfst-python's string_paths) of
+ *      one handle or of a list of handles of ctx, as a table in HBM: every successful path from the start state to a
+ *      final state, in the order the reference's iterator yields them, bit for bit.  The operands are left as they are.
+ *        - a path is its input labels and its output labels with label 0 dropped per tape (fst_path.rs:35-45: the two
+ *          lists may differ in length) and weight = ((one (x) w1) (x) w2 ...) (x) final, left to right: f32 additions
+ *          in path order, +inf absorbing;
+ *        - the order is (number of arcs, arc positions read lexicographically): the reference's FIFO of prefixes is
+ *          always sorted that way.  Parallel arcs to one state are distinct paths;
+ *        - no states or no start state: no paths, OK.  A final start state: the empty path with its final weight;
+ *        - a cycle that is ACCESSIBLE from the start state, whether or not it reaches a final state: KO "paths: a
+ *          cycle is accessible from the start state: the reference's paths_iter never returns" (the reference would
+ *          push prefixes for ever).  A cycle among states the start does not reach is no error.  The stored property
+ *          word is not consulted: the peel that counts the paths decides from the content;
+ *        - counts are u64 with saturating addition.  A count above max_paths — a saturated one always — is KO "paths:
+ *          the FST has <N> paths, more than max_paths (<M>)", decided before any per-path memory is allocated; for a
+ *          saturated count N is 18446744073709551615 and the same text goes on ": the count is saturated".  A
+ *          table holds at most 2^32 - 2 paths; a refused allocation is an ordinary KO.
+ *      wfst_fst_count_paths: the count alone, saturated at UINT64_MAX; KO on an accessible cycle.
+ *      wfst_fst_paths: one FST of any size — accessibility and the count take one launch per level of the graph.
+ *      wfst_fst_paths_batch: n FSTs into ONE table, max_paths applying per item.  The items of at most
+ *      WFST_PATHS_BATCH_MAX_STATES states and WFST_PATHS_BATCH_MAX_ARCS arcs are counted by one launch, one workgroup
+ *      each (in_kernel[i] = 1; items without states or start state too, they need no launch); an item beyond either
+ *      limit is counted as wfst_fst_paths counts it (in_kernel[i] = 0).  The unranking, the sort and the emission run
+ *      once over all paths of all items, so the call's launch count depends neither on n nor on the items' depths.
+ *      Item for item the rows are those of the single call.  in_kernel may be NULL.  n == 0: OK, a table of no items.
+ *      KO — checked before anything is launched: NULL ctx, fst / fsts or out ("null pointer"), NULL list entries ("item
+ *      <i>: null FST in batch"), a handle of another device or context ("paths: the FST belongs to another context",
+ *      "item <i>: paths_batch: the FST lives on another device").  The KOs of an item carry "item <i>: " in front, the
+ *      lowest failing i first, as a loop of single calls would stop.  On any KO *out is left as it was.
+ *      A wfst_paths lives until wfst_paths_destroy, independent of the FSTs it came from.  wfst_paths_info: items,
+ *      paths, and the total numbers of input and output labels (any pointer may be NULL).  wfst_paths_download copies
+ *      out item_off[n_items + 1] (rows of item i: item_off[i] .. item_off[i + 1]), weights[n_paths],
+ *      ilabel_off[n_paths + 1] with ilabels[n_ilabels], olabel_off[n_paths + 1] with olabels[n_olabels]; any pointer
+ *      may be NULL. ---- */
+#define WFST_PATHS_BATCH_MAX_STATES 4096
+#define WFST_PATHS_BATCH_MAX_ARCS 16384
+typedef struct wfst_paths wfst_paths;
+wfst_status wfst_fst_count_paths(wfst_ctx* ctx, const wfst_fst* fst, uint64_t* count);
+wfst_status wfst_fst_paths(wfst_ctx* ctx, const wfst_fst* fst, uint64_t max_paths, wfst_paths** out);
+wfst_status wfst_fst_paths_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, uint64_t max_paths, wfst_paths** out,
+                                 uint8_t* in_kernel);
+wfst_status wfst_paths_info(const wfst_paths* paths, uint64_t* n_items, uint64_t* n_paths, uint64_t* n_ilabels, uint64_t* n_olabels);
+wfst_status wfst_paths_download(wfst_ctx* ctx, const wfst_paths* paths, uint64_t* item_off, float* weights, uint64_t* ilabel_off,
+                                uint32_t* ilabels, uint64_t* olabel_off, uint32_t* olabels);
+wfst_status wfst_paths_destroy(wfst_paths* paths);
+/* the last wfst_fst_count_paths / wfst_fst_paths / wfst_fst_paths_batch call of ctx (reset when a call begins, also when
+ *      an argument is refused): kernel launches and library calls (a rocPRIM sort or scan counts as one) of the call;
+ *      items counted by the one-workgroup kernel (those without a start state among them) and by the device-wide
+ *      route; the deepest peel of an item, in levels; the paths counted, saturating, up to and including a refused
+ *      item; the arcs of the table's longest path; items whose count saturated.  Any pointer after ctx may be NULL. */
+wfst_status wfst_ctx_get_paths_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single,
+                                        uint64_t* levels, uint64_t* paths, uint64_t* max_path_arcs, uint64_t* saturated);
 
 /* ---- look-ahead composition: the configuration rustfst-cli/src/cmds/compose.rs:77-181 (ComposeType::LookAhead) and
  *      rustfst/src/tests_openfst/algorithms/compose.rs:118-254 build by hand — there is no single reference entry point:

@@ -14,6 +14,7 @@
 //   project(&mut fst, ProjectType::ProjectInput)                 project(fst, ProjectType::ProjectInput)
 //   invert(&mut fst)                                             invert(fst)                                       inversion.rs:32-48
 //   isomorphic(&a, &b) / isomorphic_with_config(&a, &b, config)  isomorphic(a, b) / isomorphic_with_config(a, b, config)  isomorphic.rs:184-212
+//   fst.paths_iter() -> impl Iterator<Item = FstPath<W>>         fst.paths_iter() -> std::vector<FstPath>          paths_iterator.rs:24-62
 //   connect(&mut fst) / rm_epsilon(&mut fst)                     connect(fst) / rm_epsilon(fst)
 //   shortest_distance(&fst, reverse) -> Vec<W>                   shortest_distance(fst, reverse) -> std::vector<float>
 //   reweight(&mut fst, &potentials, ReweightType::..)            reweight(fst, potentials, ReweightType::..)       reweight.rs
@@ -121,6 +122,13 @@ class Context {  // one per (thread, GPU)
   wfst_ctx* h_ = nullptr;
 };
 
+// FstPath (fst_path.rs:13-20): labels with epsilons dropped per tape, and the weight; == is exact
+struct FstPath {
+  std::vector<Label> ilabels, olabels;
+  float weight = 0.0f;  // W::one()
+  bool operator==(const FstPath& o) const { return ilabels == o.ilabels && olabels == o.olabels && weight == o.weight; }
+};
+
 class VectorFst {
  public:
   VectorFst() { check(wfst_vec_fst_new(&h_)); }
@@ -161,6 +169,9 @@ class VectorFst {
   // PartialEq of VectorFst (vector_fst/data_structure.rs:36-41): states, arcs, finals (approximate weights), start
   bool operator==(const VectorFst& o) const { int eq; check(wfst_vec_fst_equals(h_, o.h_, &eq)); return eq != 0; }
   bool operator!=(const VectorFst& o) const { return !(*this == o); }
+  // Fst::paths_iter (fst_traits/paths_iterator.rs:24-62): every successful path, in the iterator's order; enumerated on the
+  // device (defined below).  Throws when a cycle is accessible from the start state or the FST has more than max_paths paths.
+  std::vector<FstPath> paths_iter(uint64_t max_paths = 1u << 20) const;
 
   wfst_vec_fst* raw() const { return h_; }
   static VectorFst adopt(wfst_vec_fst* h) { VectorFst f(nullptr); f.h_ = h; return f; }
@@ -322,6 +333,30 @@ inline bool isomorphic_with_config(const VectorFst& fst_1, const VectorFst& fst_
   return res != 0;
 }
 inline bool isomorphic(const VectorFst& fst_1, const VectorFst& fst_2) { return isomorphic_with_config(fst_1, fst_2, IsomorphicConfig{}); }
+
+inline std::vector<FstPath> VectorFst::paths_iter(uint64_t max_paths) const {
+  detail::DeviceFst a;
+  detail::upload(*this, a);
+  wfst_paths* t = nullptr;
+  check(wfst_fst_paths(Context::current().get(), a.h, max_paths, &t));
+  struct Guard {
+    wfst_paths* t;
+    ~Guard() { wfst_paths_destroy(t); }
+  } guard{t};
+  uint64_t n_paths = 0, n_il = 0, n_ol = 0;
+  check(wfst_paths_info(t, nullptr, &n_paths, &n_il, &n_ol));
+  std::vector<float> weights(n_paths);
+  std::vector<uint64_t> iloff(n_paths + 1), oloff(n_paths + 1);
+  std::vector<uint32_t> il(n_il), ol(n_ol);
+  check(wfst_paths_download(Context::current().get(), t, nullptr, weights.data(), iloff.data(), il.data(), oloff.data(), ol.data()));
+  std::vector<FstPath> out(n_paths);
+  for (uint64_t k = 0; k < n_paths; ++k) {
+    out[k].ilabels.assign(il.begin() + iloff[k], il.begin() + iloff[k + 1]);
+    out[k].olabels.assign(ol.begin() + oloff[k], ol.begin() + oloff[k + 1]);
+    out[k].weight = weights[k];
+  }
+  return out;
+}
 
 // connect (algorithms/connect.rs:51-66) and rm_epsilon (algorithms/rm_epsilon/rm_epsilon_static.rs:50-163): in place
 inline void connect(VectorFst& fst) {

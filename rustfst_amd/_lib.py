@@ -121,6 +121,9 @@ SIGMA_BATCH_COUNTERS = ("launches", "items_in_kernel", "items_handed_back", "ite
 ISOMORPHIC_COUNTERS = ("levels", "narrow_launches", "wide_launches", "narrow_levels", "max_level_width", "pairs", "events",
                        "wave_pairs", "big_states_sorted", "nondet_marks")
 
+# wfst_ctx_get_paths_counters: the same, for the last count_paths / paths / paths_batch call
+PATHS_COUNTERS = ("launches", "items_in_kernel", "items_single", "levels", "paths", "max_path_arcs", "saturated")
+
 # wfst_ctx_get_string_pair_counts: the same, for the pair levels of the string kernel
 STRING_PAIR_COUNTS = ("pair_levels", "pair_splits")
 
@@ -140,6 +143,7 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_ctx_get_top_sort_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(TOP_SORT_BATCH_COUNTERS)),
     ("wfst_ctx_get_compose_batch_counters", C.c_int, [_vp] + [_P(_u64)] * len(COMPOSE_BATCH_COUNTERS)),
     ("wfst_ctx_get_isomorphic_counters", C.c_int, [_vp] + [_P(_u64)] * len(ISOMORPHIC_COUNTERS)),
+    ("wfst_ctx_get_paths_counters", C.c_int, [_vp] + [_P(_u64)] * len(PATHS_COUNTERS)),
     ("wfst_ctx_get_string_pair_counts", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PAIR_COUNTS)),
     ("wfst_ctx_get_string_placement", C.c_int, [_vp] + [_P(_u64)] * len(STRING_PLACEMENT)),
     ("wfst_ctx_get_solo_query", C.c_int, [_vp] + [_P(_u64)] * len(SOLO_QUERY)),
@@ -176,6 +180,12 @@ SYMBOLS = [(symbol, C.c_int, [_vp] + [_P(_u64)] * len(names)) for symbol, names 
     ("wfst_fst_project", C.c_int, [_vp, _vp, C.c_int]),
     ("wfst_fst_invert", C.c_int, [_vp, _vp]),
     ("wfst_isomorphic", C.c_int, [_vp, _vp, _vp, _P(IsomorphicConfig), _P(C.c_int)]),
+    ("wfst_fst_count_paths", C.c_int, [_vp, _vp, _P(_u64)]),
+    ("wfst_fst_paths", C.c_int, [_vp, _vp, _u64, _P(_vp)]),
+    ("wfst_fst_paths_batch", C.c_int, [_vp, _P(_vp), _sz, _u64, _P(_vp), _vp]),
+    ("wfst_paths_info", C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
+    ("wfst_paths_download", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("wfst_paths_destroy", C.c_int, [_vp]),
     ("wfst_lookahead_create", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_lookahead_relabel", C.c_int, [_vp, _vp, _P(_vp)]),
     ("wfst_lookahead_fst1", C.c_int, [_vp, _P(_vp)]),

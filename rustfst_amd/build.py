@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwfst_amd.so")
-SOURCES = ["api.cpp", "vector_fst.cpp", "fst_store.hip", "openfst_io.cpp", "sssp.hip", "nshortest.hip", "nbest_batch.hip", "tr_sort.hip", "compose.hip", "lookahead.cpp", "compose_lookahead.hip", "compose_wide.hip", "compose_sigma.hip", "compose_sigma_batch.hip", "rm_epsilon.hip", "rm_epsilon_batch.hip", "push.hip", "determinize.hip", "minimize.hip", "tr_sum.hip", "optimize.hip", "rational.hip", "replace.hip", "top_sort.hip", "isomorphic.hip", "device_ops.hip", "gather.cpp"]
+SOURCES = ["api.cpp", "vector_fst.cpp", "fst_store.hip", "openfst_io.cpp", "sssp.hip", "nshortest.hip", "nbest_batch.hip", "tr_sort.hip", "compose.hip", "lookahead.cpp", "compose_lookahead.hip", "compose_wide.hip", "compose_sigma.hip", "compose_sigma_batch.hip", "rm_epsilon.hip", "rm_epsilon_batch.hip", "push.hip", "determinize.hip", "minimize.hip", "tr_sum.hip", "optimize.hip", "rational.hip", "replace.hip", "top_sort.hip", "isomorphic.hip", "paths.hip", "device_ops.hip", "gather.cpp"]
 HEADERS = ["common.h", "tropical.h", "sssp_mailbox.h", "sssp_solo.h", "sssp_resident.h", "sssp_binned.h", "fst_props.h", "lookahead.h", "compose_wide.h", "compose_match.h", "compose_filters.h", "host_parallel.h", "rm_expand.h", "wg_ops.h", "batch_driver.h", "slab.h", "sigma_ranges.h", "string_placement.h", "top_sort_dfs.h", os.path.join("..", "..", "include", "wfst.h")]
 ARCH = "gfx950"
 

@@ -1108,6 +1108,63 @@ wfst_status wfst_ctx_get_isomorphic_counters(wfst_ctx* ctx, uint64_t* levels, ui
                                                    events, wave_pairs, big_states_sorted, nondet_marks});
 }
 
+// paths_iter (paths_iterator.rs:24-62) as a table in HBM: one handle, a list of handles, the count alone
+wfst_status wfst_fst_count_paths(wfst_ctx* ctx, const wfst_fst* fst, uint64_t* count) {
+  return wrap([&] {
+    if (ctx) ctx->paths = {};
+    if (!ctx || !fst || !count) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *count = count_paths_fst(ctx, fst);
+  });
+}
+wfst_status wfst_fst_paths(wfst_ctx* ctx, const wfst_fst* fst, uint64_t max_paths, wfst_paths** out) {
+  return wrap([&] {
+    if (ctx) ctx->paths = {};
+    if (!ctx || !fst || !out) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = paths_fst(ctx, fst, max_paths);
+  });
+}
+wfst_status wfst_fst_paths_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, uint64_t max_paths, wfst_paths** out,
+                                 uint8_t* in_kernel) {
+  return wrap([&] {
+    if (ctx) ctx->paths = {};
+    if (!ctx || !out || (n && !fsts)) throw Error("null pointer");
+    for (size_t i = 0; i < n; ++i)
+      if (!fsts[i]) throw Error("item " + std::to_string(i) + ": null FST in batch");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    *out = paths_batch(ctx, fsts, n, max_paths, in_kernel);
+  });
+}
+wfst_status wfst_paths_info(const wfst_paths* paths, uint64_t* n_items, uint64_t* n_paths, uint64_t* n_ilabels, uint64_t* n_olabels) {
+  return wrap([&] {
+    if (!paths) throw Error("null pointer");
+    if (n_items) *n_items = paths->item_off.size() - 1;
+    if (n_paths) *n_paths = paths->n_paths;
+    if (n_ilabels) *n_ilabels = paths->n_il;
+    if (n_olabels) *n_olabels = paths->n_ol;
+  });
+}
+wfst_status wfst_paths_download(wfst_ctx* ctx, const wfst_paths* paths, uint64_t* item_off, float* weights, uint64_t* ilabel_off,
+                                uint32_t* ilabels, uint64_t* olabel_off, uint32_t* olabels) {
+  return wrap([&] {
+    if (!ctx || !paths) throw Error("null pointer");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    paths_download(ctx, paths, item_off, weights, ilabel_off, ilabels, olabel_off, olabels);
+  });
+}
+wfst_status wfst_paths_destroy(wfst_paths* paths) {
+  return wrap([&] {
+    if (!paths) return;
+    (void)hipSetDevice(paths->device);
+    delete paths;
+  });
+}
+wfst_status wfst_ctx_get_paths_counters(wfst_ctx* ctx, uint64_t* launches, uint64_t* items_in_kernel, uint64_t* items_single,
+                                        uint64_t* levels, uint64_t* paths, uint64_t* max_path_arcs, uint64_t* saturated) {
+  return get_counters(ctx, &wfst_ctx::paths, {launches, items_in_kernel, items_single, levels, paths, max_path_arcs, saturated});
+}
+
 wfst_status wfst_lookahead_create(wfst_ctx* ctx, const wfst_fst* fst1, wfst_lookahead** out) {
   return wrap([&] {
     if (!ctx || !fst1 || !out) throw Error("null pointer");

@@ -229,6 +229,14 @@ struct OptimizeBatchStats {
   uint64_t launches[4] = {0, 0, 0, 0};
   uint64_t items_in_kernel = 0, items_single = 0, items_transducer = 0;
 };
+// The last wfst_fst_count_paths / wfst_fst_paths / wfst_fst_paths_batch call (paths.hip; wfst_ctx_get_paths_counters): kernel
+// launches and library calls (a rocPRIM sort or scan counts one) of the call; items counted by the one-workgroup kernel (those
+// without a start state among them) and by the device-wide route; the deepest peel of an item; the paths counted (saturating,
+// up to and including a refused item); the arcs of the longest path of the table; items whose count saturated.  Zeroed when
+// the call begins, also when an argument is refused.
+struct PathsCounters {
+  uint64_t launches = 0, items_in_kernel = 0, items_single = 0, levels = 0, paths = 0, max_path_arcs = 0, saturated = 0;
+};
 }  // namespace wfst
 
 // ---------------------------------------------------------------- handles
@@ -391,6 +399,7 @@ struct wfst_ctx {
     uint64_t levels = 0, narrow_launches = 0, wide_launches = 0, narrow_levels = 0, max_level_width = 0, pairs = 0, events = 0;
     uint64_t wave_pairs = 0, big_states_sorted = 0, nondet_marks = 0;
   } isomorphic;
+  wfst::PathsCounters paths;
   int n_cus = 256;
   wfst::RearmRecord rearm;  // the parked scratch of this context's last predicted mailbox solve
   // ... and what became of such scratch; never zeroed (counts since the context's creation)
@@ -560,6 +569,19 @@ struct wfst_fst {
   mutable std::mutex cache_mu;
 };
 
+// The table of paths of one call of paths.hip, in HBM: the paths of item i are rows item_off[i] .. item_off[i + 1], in the
+// reference's order.  A table without paths holds no device array.
+struct wfst_paths {
+  // (first member = destroyed last: the buffers below go back to it)
+  std::shared_ptr<wfst::DevicePool> pool;
+  int device = 0;
+  uint64_t n_paths = 0, n_il = 0, n_ol = 0;
+  std::vector<uint64_t> item_off;      // [items + 1]
+  wfst::DBuf<float> weights;           // [n_paths]
+  wfst::DBuf<uint64_t> iloff, oloff;   // [n_paths + 1]
+  wfst::DBuf<uint32_t> il, ol;         // [n_il], [n_ol]
+};
+
 namespace wfst {
 // an intermediate FST handle of an operation: destroyed on every exit, with its device current
 struct HandleDeleter {
@@ -648,6 +670,13 @@ void project_device(wfst_ctx* ctx, wfst_fst* f, bool project_output);
 void invert_device(wfst_ctx* ctx, wfst_fst* f);
 // isomorphic.hip: isomorphic_with_config for two handles of ctx (both left as they are); throws the reference's error
 bool isomorphic_fsts(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, float delta);
+// paths.hip: paths_iter of one handle or a list of handles of ctx as a table (a NEW table; the operands are left as they are),
+// and the number of paths alone (saturated at UINT64_MAX); an accessible cycle throws
+uint64_t count_paths_fst(wfst_ctx* ctx, const wfst_fst* f);
+wfst_paths* paths_fst(wfst_ctx* ctx, const wfst_fst* f, uint64_t max_paths);
+wfst_paths* paths_batch(wfst_ctx* ctx, const wfst_fst* const* fsts, size_t n, uint64_t max_paths, uint8_t* in_kernel);
+void paths_download(wfst_ctx* ctx, const wfst_paths* t, uint64_t* item_off, float* weights, uint64_t* ilabel_off, uint32_t* ilabels,
+                    uint64_t* olabel_off, uint32_t* olabels);
 // compose.hip
 wfst_fst* compose(wfst_ctx* ctx, const wfst_fst* f1, const wfst_fst* f2, bool connect, uint32_t filter = 0);
 // ... the match mode its operands' property words leave (0 both, 1 input, 2 output), or the reference's error

@@ -212,6 +212,15 @@ class Context:
               "wfst_ctx_get_isomorphic_counters")
         return {k: int(v.value) for k, v in zip(_lib.ISOMORPHIC_COUNTERS, vals)}
 
+    def paths_counters(self) -> dict:
+        """The route of this context's last count_paths / paths / paths_batch call (wfst_ctx_get_paths_counters): kernel
+        launches and library calls (launches), items counted by the one-workgroup kernel and by the device-wide route
+        (items_in_kernel, items_single), the deepest peel (levels), the paths counted (paths), the arcs of the longest path
+        (max_path_arcs) and items whose count saturated (saturated)."""
+        vals = [C.c_uint64() for _ in _lib.PATHS_COUNTERS]
+        check(_lib.lib().wfst_ctx_get_paths_counters(self._h, *[C.byref(v) for v in vals]), "wfst_ctx_get_paths_counters")
+        return {k: int(v.value) for k, v in zip(_lib.PATHS_COUNTERS, vals)}
+
     def lookahead_stats(self) -> dict:
         """Which route answered the compositions of this context's last LookAhead.compose / compose_batch call
         (wfst_ctx_get_lookahead_stats): items and those without a start state, compositions the single-wave kernel finished
@@ -517,6 +526,22 @@ class DeviceFst:
         check(_lib.lib().wfst_isomorphic(self.ctx._h, self._h, other._h, cfg, C.byref(res)), "Error checking isomorphic FSTs")
         return bool(res.value)
 
+    def paths(self, max_paths: int = 1 << 20) -> "PathTable":
+        """Fst::paths_iter (fst_traits/paths_iterator.rs:24-62) on the device (wfst_fst_paths): every successful path in the
+        reference's order — (number of arcs, arc positions) — as a PathTable, weights bit for bit.  Raises WfstError when a
+        cycle is accessible from the start state (the reference would never return) and when the FST has more than
+        max_paths paths, which is decided before any per-path memory is taken."""
+        out = C.c_void_p()
+        check(_lib.lib().wfst_fst_paths(self.ctx._h, self._h, int(max_paths), C.byref(out)), "Error enumerating paths")
+        return PathTable._take(out, self.ctx)
+
+    def count_paths(self) -> int:
+        """The number of successful paths (wfst_fst_count_paths), saturated at 2^64 - 1; raises WfstError when a cycle is
+        accessible from the start state."""
+        res = C.c_uint64()
+        check(_lib.lib().wfst_fst_count_paths(self.ctx._h, self._h, C.byref(res)), "Error counting paths")
+        return int(res.value)
+
     def tr_sort(self, ilabel_cmp: bool = True) -> "DeviceFst":
         """In-place stable per-state arc sort on the device by ilabel (ILabelCompare) or olabel
         (OLabelCompare) + the reference's property update: algorithms/tr_sort.rs:13-62,
@@ -675,6 +700,103 @@ class PathList(Sequence):
             except Exception:
                 pass
             self._arr = None
+
+
+class FstPath:
+    """A successful path (rustfst/src/fst_path.rs:13-20): the input labels and the output labels with label 0 dropped per
+    tape, and the weight.  == compares the labels exactly and the weight bit for bit."""
+
+    __slots__ = ("ilabels", "olabels", "weight")
+
+    def __init__(self, ilabels=(), olabels=(), weight: float = 0.0):
+        self.ilabels = [int(l) for l in ilabels]
+        self.olabels = [int(l) for l in olabels]
+        self.weight = np.float32(weight)
+
+    def __eq__(self, other):
+        if not isinstance(other, FstPath):
+            return NotImplemented
+        return (self.ilabels, self.olabels) == (other.ilabels, other.olabels) and \
+            self.weight.view(np.uint32) == other.weight.view(np.uint32)
+
+    def __hash__(self):  # (fst_path.rs:76-82: labels and weight; consistent with ==)
+        return hash((tuple(self.ilabels), tuple(self.olabels), int(self.weight.view(np.uint32))))
+
+    def __repr__(self):
+        return f"<FstPath ilabels={self.ilabels}, olabels={self.olabels}, weight={self.weight}>"
+
+
+class PathTable(Sequence):
+    """The downloaded table of wfst_fst_paths / wfst_fst_paths_batch: a sequence of FstPath in the reference's order over
+    six numpy arrays, which a decoder may take as they are — `item_off` (rows of item i: item_off[i] .. item_off[i + 1]),
+    `weights`, `ilabel_off` with `ilabels`, `olabel_off` with `olabels` (row k's labels: labels[off[k]:off[k + 1]])."""
+
+    def __init__(self, item_off, weights, ilabel_off, ilabels, olabel_off, olabels):
+        self.item_off, self.weights = item_off, weights
+        self.ilabel_off, self.ilabels, self.olabel_off, self.olabels = ilabel_off, ilabels, olabel_off, olabels
+
+    @classmethod
+    def _take(cls, handle, ctx: "Context") -> "PathTable":
+        """downloads the table behind `handle` and destroys it"""
+        L = _lib.lib()
+        try:
+            counts = [C.c_uint64() for _ in range(4)]
+            check(L.wfst_paths_info(handle, *[C.byref(c) for c in counts]), "wfst_paths_info")
+            n_items, n_paths, n_il, n_ol = (int(c.value) for c in counts)
+            item_off, weights = np.zeros(n_items + 1, np.uint64), np.zeros(n_paths, np.float32)
+            iloff, il = np.zeros(n_paths + 1, np.uint64), np.zeros(n_il, np.uint32)
+            oloff, ol = np.zeros(n_paths + 1, np.uint64), np.zeros(n_ol, np.uint32)
+            check(L.wfst_paths_download(ctx._h, handle, item_off.ctypes.data, weights.ctypes.data, iloff.ctypes.data,
+                                        il.ctypes.data, oloff.ctypes.data, ol.ctypes.data), "wfst_paths_download")
+        finally:
+            L.wfst_paths_destroy(handle)
+        return cls(item_off, weights, iloff, il, oloff, ol)
+
+    @property
+    def num_items(self) -> int:
+        return len(self.item_off) - 1
+
+    def __len__(self):
+        return len(self.weights)
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [self[j] for j in range(*k.indices(len(self)))]
+        if k < 0:
+            k += len(self)
+        if not 0 <= k < len(self):
+            raise IndexError(k)
+        return FstPath(self.ilabels[int(self.ilabel_off[k]):int(self.ilabel_off[k + 1])],
+                       self.olabels[int(self.olabel_off[k]):int(self.olabel_off[k + 1])], self.weights[k])
+
+    def item(self, i: int) -> "PathTable":
+        """the rows of item i as a table of one item (views of this table's arrays, offsets rebased)"""
+        if not 0 <= i < self.num_items:
+            raise IndexError(i)
+        b, e = int(self.item_off[i]), int(self.item_off[i + 1])
+        iloff, oloff = self.ilabel_off[b:e + 1], self.olabel_off[b:e + 1]
+        return PathTable(np.array([0, e - b], np.uint64), self.weights[b:e], iloff - iloff[0],
+                         self.ilabels[int(iloff[0]):int(iloff[-1])], oloff - oloff[0], self.olabels[int(oloff[0]):int(oloff[-1])])
+
+
+DEFAULT_MAX_PATHS = 1 << 20
+
+
+def paths_batch(fsts: Sequence["DeviceFst"], max_paths: int = DEFAULT_MAX_PATHS, ctx: Optional[Context] = None,
+                return_in_kernel: bool = False):
+    """[f.paths(max_paths) for f in fsts] as ONE call and ONE table (wfst_fst_paths_batch): the items of at most 4096
+    states and 16384 arcs — the n-best results of a decoding batch — are counted by one launch, one workgroup each, and
+    the paths of all items are unranked, ordered and written together.  max_paths applies per item.
+    return_in_kernel: also the uint8 array that says which items the batch kernel counted."""
+    n = len(fsts)
+    if ctx is None:
+        ctx = _first_ctx(fsts) if n else default_context()
+    out = C.c_void_p()
+    flags = np.zeros(n, np.uint8)
+    check(_lib.lib().wfst_fst_paths_batch(ctx._h, _handles(fsts), n, int(max_paths), C.byref(out), flags.ctypes.data),
+          "wfst_fst_paths_batch")
+    table = PathTable._take(out, ctx)
+    return (table, flags) if return_in_kernel else table
 
 
 class LookAhead:
@@ -1533,6 +1655,11 @@ class VectorFst:
         on the device."""
         dev = self.to_device()
         return dev.isomorphic(other.to_device(dev.ctx))
+
+    def paths_iter(self, max_paths: int = 1 << 20) -> "PathTable":
+        """Fst::paths_iter (fst_traits/paths_iterator.rs:24-62): the FST is uploaded and enumerated on the device; the
+        table iterates as FstPath in the reference's order."""
+        return self.to_device().paths(max_paths)
 
 
 # ------------------------------------------------------------------ free functions
